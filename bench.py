@@ -25,12 +25,16 @@ pass launches (state not advanced) before the warm-up so the clocks are settled 
 (ctrl_end, SigmaA, lambda_max + loop test, SigmaB), stamped on the device.  `--shard-of N` runs rank 0's share of an N-rank
 job on one GPU; `--config cfg2|cfg4|cfg5` the other BASELINE shapes; `--full-cov` (with --config cfg5 --H <= 64) the
 per-column full-covariance branch of the sparse model.
+`--dump-outputs DIR` writes, after the timed sweeps, the model state the last timed sweep left (what a caller of the run
+reads back) as DIR/<name>.npy, float64, at most DUMP_BYTES in all; every input is seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -46,6 +50,7 @@ CONFIGS = {
     "cfg5": (100000, 10000, 256, "bf16"),      # vbmf_sparse.jl ARD-sparse (diagonal branch)
 }
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: all files together
 
 
 def parse():
@@ -77,7 +82,31 @@ def parse():
     ap.add_argument("--settle-seconds", type=float, default=0.3,
                     help="untimed sweeps run for this long BEFORE the W warm-up sweeps, so that the device's clocks have ramped "
                          "up from idle when the timed region starts (reported as clock_settle in the JSON line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed sweeps, write the state the last one left (rank 0: its shard of B) as DIR/<name>.npy "
+                         "in float64, at most 64 MB in all: an array that does not fit keeps a fixed, seeded sample of its rows")
     return ap.parse_args()
+
+
+def dump_outputs(outdir, arrays):
+    """Write `arrays` (name -> array or scalar) as outdir/<name>.npy in float64, DUMP_BYTES in all.  Smallest first, each
+    array may take an equal share of what is left; one larger than its share keeps that many of its rows (leading axis),
+    drawn without replacement by a generator seeded from the name alone, in ascending order -- the same rows on every run
+    and every build.  Returns {name: [rows kept, rows]} of the sampled arrays."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = sorted(((k, np.asarray(v, dtype=np.float64)) for k, v in arrays.items()), key=lambda kv: kv[1].nbytes)
+    left, sampled = DUMP_BYTES - 1024 * len(arrays), {}          # (room for the .npy headers)
+    for i, (name, x) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if x.nbytes > share and x.ndim > 0:
+            n = x.shape[0]
+            keep = max(1, share // (x.nbytes // n))
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, keep, replace=False))
+            x = x[rows]
+            sampled[name] = [int(keep), int(n)]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(x))
+        left -= x.nbytes
+    return sampled
 
 
 def cpu_baseline(ctx, L, M, H, rows, sweeps, seed):
@@ -237,6 +266,11 @@ def main():
 
     chain = None if sparse else ctx.chain_us()
     s = {"sigma2": ctx.sparse_get_state(want_B=False)["sigmaHat"]} if sparse else ctx.get_state(want_B=False)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        state = ctx.sparse_get_state() if sparse else ctx.get_state()
+        state["d"] = d
+        dumped = {"dir": a.dump_outputs, "sampled": dump_outputs(a.dump_outputs, state)}
     bytes1, bytes2 = ctx.pass_bytes(1), ctx.pass_bytes(2)
     n = prof["pass1_n"] + prof["pass2_n"]
     avg_ms = (prof["pass1_ms"] + prof["pass2_ms"]) / max(n, 1)
@@ -299,6 +333,8 @@ def main():
         "clock_settle": {"seconds": a.settle_seconds, "untimed_pass_launches": settle_launches},
         "control_chain_us": chain,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     # SURVEY 8(d) counts 2*L*M*H flops per contraction -- the factor's lo part (bf16x2) and the padding of H to the rank
     # class are work the precision / tiling choice added, not algorithmic work: both figures are printed
     alg_flops = 2.0 * L_loc * M * H

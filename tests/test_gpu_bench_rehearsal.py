@@ -49,3 +49,20 @@ def test_bench_two_ranks_rehearsal_matches_one_rank():
     assert abs(d2["final"]["sigma2"] - d1["final"]["sigma2"]) <= 1e-4 * abs(d1["final"]["sigma2"]), (d1["final"], d2["final"])
     # d = ||B_old - B_new|| / ||B_old|| is a difference of fp32-stored factors: 5e-3 relative + the 2e-6 noise floor of the parity tests
     assert abs(d2["final"]["d"] - d1["final"]["d"]) <= 5e-3 * abs(d1["final"]["d"]) + 2e-6, (d1["final"], d2["final"])
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the state after the last of exactly --steps timed sweeps, float64, whole at this shape; ms_per_step is
+    the wall time of one of those sweeps."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path)] + SHAPE,
+                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 4 and abs(d["ms_per_step"] * d["value"] - 1e3) <= 1e-6 * 1e3
+    assert d["dump_outputs"] == {"dir": str(tmp_path), "sampled": {}}
+    z = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(z) == ["AHat", "BHat", "CA_diag", "CB_diag", "SigmaA", "SigmaB", "d", "sigma2"]
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in z.values())
+    assert z["AHat"].shape == (700, 24) and z["BHat"].shape == (6000, 24) and z["SigmaA"].shape == (24, 24)
+    assert float(z["sigma2"]) == d["final"]["sigma2"] and float(z["d"]) == d["final"]["d"]
