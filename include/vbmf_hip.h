@@ -126,6 +126,15 @@ int vbmf_step(vbmf_ctx* ctx, int which);
  * SigmaB, CB frozen.  B is fixed, so Y'B is formed once: ONE pass over Y per call instead of two per iteration. */
 int vbmf_run_fixed_basis(vbmf_ctx* ctx, int64_t niter);
 
+/* vbls! over many bags with one fixed basis (examples/mil_util.jl:473-479 in one call).  The context's Y is the bags side by
+ * side: bag b = columns col_off[b] .. col_off[b+1]-1 (col_off[0] = 0, col_off[nbags] = M, every bag >= 1 column).
+ * BHat, SigmaB, CB from vbmf_set_state; no label mask; H <= 64; one rank; niter >= 1.
+ * In/out per bag: sigma2[nbags], CA_diag[nbags*H] (start values in, final values out).  Out: SigmaA[nbags*H*H],
+ * AHat (M x H, ldA >= M).  The context's state is not changed.  SigmaA or AHat may be NULL (not formed / not copied).
+ * Any other input returns VBMF_ERR_INVALID before a launch; a non-finite pivot in any bag VBMF_ERR_NUMERIC. */
+int vbmf_run_fixed_basis_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t niter,
+                                 double* sigma2, double* CA_diag, double* SigmaA, double* AHat, int64_t ldA);
+
 /* The vbmf! loop (src/vbmf.jl:187-214): while i <= niter && d > eps { A; B; [CA; CB]; [sigma2]; d }.
  * Runs entirely on the device; the stop test is evaluated device-side so the state freezes exactly
  * where the reference would stop.  iters_done = i-1 (src/vbmf.jl:221), d_last = last d.

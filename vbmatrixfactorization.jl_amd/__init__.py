@@ -44,7 +44,8 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_dual_parameters", "vbmf_dual_init", "vbmf_dual", "vbmf_dual_", "lowerBound_dual", "dual_updateA_",
            "dual_updateB_", "dual_updateCA_", "dual_updateCB_", "dual_updateSigma_", "dual_updateCA_and_priors_",
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
-           "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_"]
+           "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
+           "vbls_batch_", "Bags"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
 # elements the field is left None and computed on demand with updateYHat_ (8 GB at 100k x 10k).
@@ -1140,6 +1141,107 @@ def vbls_(Y, params, niter, diag_var=False, full_cov=False):
     s.pull(params)
     params.YHat = s.ctx.YHat() if params.L * params.M <= YHAT_AUTO_LIMIT else None     # :201
     return params.AHat
+
+
+_BATCH_MAX_H = 64
+
+
+def _batch_refuse(why):
+    raise ValueError(f"vbls_batch_: {why}; run such bags one at a time with vbls_")
+
+
+def _batch_shapes(Ys, H):
+    """(L, [M_b]) of a list of bags, checked on the host: matrices, one L, H <= 64."""
+    if int(H) > _BATCH_MAX_H:
+        _batch_refuse(f"H = {int(H)} > {_BATCH_MAX_H}")
+    if len(Ys) == 0:
+        _batch_refuse("no bags")
+    Ls, Ms = [], []
+    for Y in Ys:
+        shape = np.shape(Y)
+        if len(shape) != 2 or shape[1] < 1:
+            _batch_refuse(f"every bag must be a matrix with at least one column (got shape {shape})")
+        Ls.append(int(shape[0]))
+        Ms.append(int(shape[1]))
+    if len(set(Ls)) != 1:
+        _batch_refuse(f"the bags have different row counts L {sorted(set(Ls))}")
+    return Ls[0], Ms
+
+
+class Bags:
+    """Many bags (L x M_b matrices with one L) uploaded side by side as ONE L x sum(M_b) matrix on the device, for vbls_batch_.
+    One upload serves several bases: the MIL classifier runs every bag against two trained models (examples/mil_util.jl:473-479)."""
+
+    def __init__(self, Ys, H):
+        self.L, self.Ms = _batch_shapes(Ys, H)
+        self.H = int(H)
+        self.col_off = np.concatenate([[0], np.cumsum(self.Ms)]).astype(np.int64)
+        self.M = int(self.col_off[-1])
+        Yall = np.empty((self.L, self.M), order="F")
+        for Y, c0, c1 in zip(Ys, self.col_off[:-1], self.col_off[1:]):
+            Yall[:, c0:c1] = Y
+        self.session = Session(self.L, self.M, self.H)
+        self.session.set_Y(Yall)
+
+    def __len__(self):
+        return len(self.Ms)
+
+    def close(self):
+        self.session.close()
+
+
+def _batch_check_params(L, Ms, H, params):
+    if len(params) != len(Ms):
+        _batch_refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
+    p0 = params[0]
+    for b, (p, M) in enumerate(zip(params, Ms)):
+        if type(p) is not vbmf_parameters:
+            _batch_refuse(f"bag {b}: {type(p).__name__} (the basic model's vbmf_parameters only)")
+        if int(p.H) != H:
+            _batch_refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
+        if p.L != L or p.M != M:
+            _batch_refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
+        if int(p.H1) > 0 or np.asarray(p.labels).size > 0:
+            _batch_refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
+        if p is not p0 and not (np.array_equal(p.BHat, p0.BHat) and np.array_equal(p.SigmaB, p0.SigmaB)
+                                and np.array_equal(p.CB, p0.CB)):
+            _batch_refuse(f"bag {b} does not share BHat, SigmaB and CB with bag 0 (one fixed basis per call)")
+
+
+def vbls_batch_(Ys, params, niter):
+    """vbls! over many bags with one fixed basis in one device call: does what [vbls_(Y, p, niter) for Y, p in zip(Ys, params)]
+    does for the basic model (examples/mil_util.jl:473-479) -- fills AHat, SigmaA, CA, invCA, sigma2 (and YHat under
+    YHAT_AUTO_LIMIT) of every p and returns the list of AHat.  Ys: a list of L x M_b arrays, or a Bags holding them on the device.
+    params: one vbmf_parameters per bag (copy_vbmf_params), all with the same BHat, SigmaB and CB, no labels, H <= 64.
+    Every bag runs all niter iterations in one workgroup of one launch (include/vbmf_hip.h, vbmf_run_fixed_basis_batched)."""
+    params = list(params)
+    H = int(params[0].H) if params else 0
+    if isinstance(Ys, Bags):
+        bags = Ys
+        if bags.H != H:
+            _batch_refuse(f"the Bags were uploaded for H = {bags.H}, the parameters have H = {H}")
+        _batch_check_params(bags.L, bags.Ms, H, params)
+    else:
+        L, Ms = _batch_shapes(Ys, H)
+        _batch_check_params(L, Ms, H, params)
+        bags = Bags(Ys, H)
+    p0 = params[0]
+    ctx = bags.session.ctx
+    ctx.set_state(np.zeros((bags.M, H)), p0.BHat, p0.SigmaA, p0.SigmaB, np.diag(p0.CA), np.diag(p0.CB), p0.sigma2)
+    r = ctx.run_fixed_basis_batched(bags.col_off, int(niter), [p.sigma2 for p in params], [np.diag(p.CA) for p in params])
+    idx = np.arange(H)
+    out = []
+    for b, p in enumerate(params):
+        c0, c1 = bags.col_off[b], bags.col_off[b + 1]
+        ca = r["CA_diag"][b]
+        p.AHat = np.array(r["AHat"][c0:c1], order="F")             # rebound, like updateA! (src/vbmf.jl:96-98)
+        p.SigmaA = r["SigmaA"][b].copy()
+        p.CA[idx, idx] = ca                                          # in place (src/vbmf.jl:131)
+        p.invCA = np.diag(1.0 / ca)
+        p.sigma2 = float(r["sigma2"][b])
+        p.YHat = p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None     # :201
+        out.append(p.AHat)
+    return out
 
 
 def copy_vbmf_params(Y, old_params, rng=None):

@@ -29,7 +29,7 @@ UNIQUE_ID_BYTES = 128
 SYMBOLS = [
     "vbmf_default_opts", "vbmf_create", "vbmf_destroy", "vbmf_last_error", "vbmf_set_Y", "vbmf_set_Y_synthetic",
     "vbmf_get_Y", "vbmf_get_trYY", "vbmf_set_state", "vbmf_get_state", "vbmf_step", "vbmf_run", "vbmf_run_fixed_basis",
-    "vbmf_get_YHat",
+    "vbmf_run_fixed_basis_batched", "vbmf_get_YHat",
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
@@ -106,6 +106,7 @@ def lib():
     L.vbmf_step.argtypes = [vp, i32]
     L.vbmf_run.argtypes = [vp, i64, C.c_double, i32, i32, C.POINTER(i64), dp, dp]
     L.vbmf_run_fixed_basis.argtypes = [vp, i64]
+    L.vbmf_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, dp, dp, dp, dp, i64]
     L.vbmf_sparse_run_fixed_basis.argtypes = [vp, i64]
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
     L.vbmf_elbo.argtypes = [vp, dp]
@@ -309,6 +310,22 @@ class Context:
 
     def run_fixed_basis(self, niter):
         self._chk(self._lib.vbmf_run_fixed_basis(self._h, int(niter)))
+
+    def run_fixed_basis_batched(self, col_off, niter, sigma2, CA_diag, want_A=True):
+        """vbls! over the bags side by side in this context's Y (vbmf_run_fixed_basis_batched): bag b = columns
+        col_off[b] .. col_off[b+1]-1; B, SigmaB, CB from set_state; per-bag start values sigma2 (nbags,) and CA_diag (nbags, H).
+        Returns dict(sigma2 (nbags,), CA_diag (nbags, H), SigmaA (nbags, H, H), AHat (M, H) or None).  The state is not changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        s2 = np.array(sigma2, dtype=np.float64, copy=True).reshape(-1)
+        ca = np.array(CA_diag, dtype=np.float64, copy=True, order="C")
+        if nb < 1 or s2.shape != (nb,) or ca.shape != (nb, self.H):
+            raise ValueError(f"col_off describes {nb} bags: sigma2 must be ({nb},) and CA_diag ({nb}, {self.H})")
+        SA = np.empty((nb, self.H, self.H))
+        A = np.empty((self.M, self.H), order="F") if want_A else None
+        self._chk(self._lib.vbmf_run_fixed_basis_batched(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), int(niter), _dptr(s2),
+                                                         _dptr(ca), _dptr(SA), _dptr(A), self.M))
+        return dict(sigma2=s2, CA_diag=ca, SigmaA=SA, AHat=A)
 
     def sparse_run_fixed_basis(self, niter):
         self._chk(self._lib.vbmf_sparse_run_fixed_basis(self._h, int(niter)))

@@ -922,11 +922,23 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
 // iterations on bags of a few tens of columns and H <= 10 (examples/mil_util.jl:473-479): per call 5.6-7.6 ms with one launch
 // group per iteration (profiles/r03_f_vbls_mil.txt: break-even with NumPy on the host), most of it launch latency.
 // 256 threads; LDS: four 16 NB x (16 NB + 2) fp64 images (W, S, SigmaA, T).  Blocks (I, J) are owned by wave (I NB + J) % 4.
-// Reads GB, SB, ca, sigma2, ||Y||^2 and S (at st + lay.W1()); writes SA, ca, sigma2, log det SigmaA and the fp32 table inv(K).
+// The loop body is vbls_loop_dev: one workgroup runs one matrix ("bag").  B'B and SigmaB come from the state (GB, SB), everything
+// that belongs to the bag through VblsBag -- so the single-matrix launch (vbls_loop_kernel: the bag IS the state) and the batched
+// one (vbls_batch_kernel: one workgroup per bag of a context holding many bags side by side) run the same code.
+constexpr size_t vbls_lds_bytes(int NB) { return (size_t)4 * (16 * NB) * (16 * NB + 2) * sizeof(double); }
+struct VblsBag {
+    const double* S; int lds;      // S = P'P, H x H at leading dimension lds
+    double trYY, M;                // ||Y||^2 and the column count of the bag
+    double* sigma2;                // in: start value; out: after the last updateSigma2!
+    double* ca;                    // in / out: diag(CA), H entries
+    double* SA; int ldsa, nsa;     // out: SigmaA of the last updateA!, nsa x nsa at leading dimension ldsa (zero beyond H)
+    float* SA32;                   // out (optional): SigmaA / sigma2 of that update, fp32 (the post kernel's table), same layout
+    double* T;                     // out (optional): the same table in fp64
+    double* logdet;                // out (optional): log det SigmaA
+};
 template <int NB>
-__global__ __launch_bounds__(256) void vbls_loop_kernel(double* __restrict__ st, StateLayout lay, int H, double Lg, double M,
-                                                        int niter, float* __restrict__ SA32, int* __restrict__ ints) {
-    extern __shared__ __attribute__((aligned(16))) double lds_vl[];
+__device__ __forceinline__ void vbls_loop_dev(const double* st, StateLayout lay, int H, double Lg, int niter,
+                                              const VblsBag& g, double* lds_vl, int* __restrict__ err) {
     __shared__ double red[16];
     __shared__ double ca_s[16 * NB], dg_s[16 * NB];
     constexpr int NP = 16 * NB, LD = NP + 2, IMG = NP * LD;
@@ -938,10 +950,10 @@ __global__ __launch_bounds__(256) void vbls_loop_kernel(double* __restrict__ st,
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c16 = lane & 15, q16 = lane >> 4;
     const int Hp = lay.Hp, nbu = (H + 15) >> 4;
-    double* scal = st + lay.scal();
-    double sigma2 = scal[S_SIGMA2];
-    const double trYY = scal[S_TRYY];
-    const double* Sg = st + lay.W1();
+    const double M = g.M;
+    double sigma2 = *g.sigma2;
+    const double trYY = g.trYY;
+    const double* Sg = g.S;
     // K0 = B'B + L SigmaB of this wave's blocks (C/D layout), S into LDS, CA into LDS
     f64x4 k0[NOWN];
 #pragma unroll
@@ -955,9 +967,9 @@ __global__ __launch_bounds__(256) void vbls_loop_kernel(double* __restrict__ st,
     }
     for (int t = threadIdx.x; t < NP * NP; t += 256) {
         const int i = t / NP, j = t % NP;
-        Sm[i * LD + j] = (i < H && j < H) ? Sg[(long long)i * Hp + j] : 0.0;
+        Sm[i * LD + j] = (i < H && j < H) ? Sg[(long long)i * g.lds + j] : 0.0;
     }
-    if (threadIdx.x < NP) ca_s[threadIdx.x] = threadIdx.x < H ? st[lay.ca() + threadIdx.x] : 1.0;
+    if (threadIdx.x < NP) ca_s[threadIdx.x] = threadIdx.x < H ? g.ca[threadIdx.x] : 1.0;
     __syncthreads();
     double ldK = 0.0;
     int bad = 0;
@@ -1021,22 +1033,52 @@ __global__ __launch_bounds__(256) void vbls_loop_kernel(double* __restrict__ st,
         trs = block_sum(trs, red);                               // (its barriers publish dg_s)
         const bool last = it + 1 == niter;
         if (last) {                                              // what the last updateA! leaves: SigmaA, inv(K) as the post kernel's table
-            for (int t = threadIdx.x; t < Hp * Hp; t += 256) {
-                const int i = t / Hp, j = t % Hp;
+            for (int t = threadIdx.x; t < g.nsa * g.nsa; t += 256) {
+                const int i = t / g.nsa, j = t % g.nsa;
                 const double v = (i < H && j < H) ? SAm[i * LD + j] : 0.0;
-                st[lay.SA() + t] = v;
-                SA32[t] = (float)(v / sigma2);
+                g.SA[(long long)i * g.ldsa + j] = v;
+                if (g.SA32) g.SA32[(long long)i * g.ldsa + j] = (float)(v / sigma2);
+                if (g.T) g.T[(long long)i * g.ldsa + j] = v / sigma2;
             }
-            if (threadIdx.x == 0) scal[S_LOGDET_SA] = (double)H * log(sigma2) - ldK;
+            if (threadIdx.x == 0 && g.logdet) *g.logdet = (double)H * log(sigma2) - ldK;
         }
         __syncthreads();
         if (threadIdx.x < NP) ca_s[threadIdx.x] = threadIdx.x < H ? dg_s[threadIdx.x] : 1.0;
         sigma2 = (trYY - 2.0 * trs / sigma2 + t2) / (Lg * M);
         __syncthreads();
     }
-    if (threadIdx.x < H) st[lay.ca() + threadIdx.x] = ca_s[threadIdx.x];
-    if (threadIdx.x == 0) scal[S_SIGMA2] = sigma2;
-    if (bad) atomicExch(ints + I_ERR, 1);
+    if (threadIdx.x < H) g.ca[threadIdx.x] = ca_s[threadIdx.x];
+    if (threadIdx.x == 0) *g.sigma2 = sigma2;
+    if (bad) atomicExch(err, 1);
+}
+
+// Reads GB, SB, ca, sigma2, ||Y||^2 and S (at st + lay.W1()); writes SA, ca, sigma2, log det SigmaA and the fp32 table inv(K).
+template <int NB>
+__global__ __launch_bounds__(256) void vbls_loop_kernel(double* __restrict__ st, StateLayout lay, int H, double Lg, double M,
+                                                        int niter, float* __restrict__ SA32, int* __restrict__ ints) {
+    extern __shared__ __attribute__((aligned(16))) double lds_vl[];
+    double* scal = st + lay.scal();
+    const VblsBag g{st + lay.W1(), lay.Hp, scal[S_TRYY], M, scal + S_SIGMA2, st + lay.ca(), st + lay.SA(), lay.Hp, lay.Hp, SA32,
+                    nullptr, scal + S_LOGDET_SA};
+    vbls_loop_dev<NB>(st, lay, H, Lg, niter, g, lds_vl, ints + I_ERR);
+}
+
+// vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): workgroup b runs ALL niter iterations of bag b = columns
+// col_off[b] .. col_off[b+1]-1 of the context's Y (updateA! does not read the previous A, src/vbmf.jl:96-98, so no iteration has to run
+// the general way).  Per bag: S_b (H x H, ld H) and ||Y_b||^2 from bag_gram_kernel; sigma2 / CA start values in, final values out;
+// SigmaA_b and the fp64 table SigmaA_b / sigma2_b of the last updateA! out (bag_a_kernel forms A_b = P_b T_b from it).
+template <int NB>
+__global__ __launch_bounds__(256) void vbls_batch_kernel(const double* __restrict__ st, StateLayout lay, int H, double Lg,
+                                                         const long long* __restrict__ col_off, int niter, const double* __restrict__ S,
+                                                         const double* __restrict__ yy, double* __restrict__ sigma2,
+                                                         double* __restrict__ ca, double* __restrict__ SA, double* __restrict__ T,
+                                                         int* __restrict__ ints) {
+    extern __shared__ __attribute__((aligned(16))) double lds_vl[];
+    const int b = blockIdx.x;
+    const long long o2 = (long long)b * H * H;
+    const VblsBag g{S + o2, H, yy[b], (double)(col_off[b + 1] - col_off[b]), sigma2 + b, ca + (long long)b * H, SA + o2, H, H,
+                    nullptr, T + o2, nullptr};
+    vbls_loop_dev<NB>(st, lay, H, Lg, niter, g, lds_vl, ints + I_ERR);
 }
 
 // identity (H x H, zero-padded to Hp) as a post kernel's table: A = P I, whose Gram is S = P'P

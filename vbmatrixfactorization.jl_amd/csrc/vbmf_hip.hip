@@ -17,6 +17,9 @@
 // Every kernel of a sweep starts with `if (*stop) return`, and ctrl_end raises `stop` exactly when
 // the reference's `while (i <= niter) && (d > eps)` would exit, so the host can enqueue sweeps ahead
 // without a per-sweep synchronisation and the state still freezes at the reference's iteration.
+//
+// vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): ONE pass 1 with the frozen B over the bags side by side,
+// then bag_gram (S_b = P_b'P_b, ||Y_b||^2), vbls_batch (all iterations, one workgroup per bag) and bag_a (A_b = P_b SigmaA_b / sigma2_b).
 #include "../../include/vbmf_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -37,6 +40,7 @@
 #include "stream_gemm.hpp"
 #include "tile_kernels.hpp"
 #include "prep_kernels.hpp"
+#include "batch_kernels.hpp"
 
 using namespace vbmf;
 
@@ -151,6 +155,8 @@ struct vbmf_ctx {
     vbmf_allreduce_fn ar_hook = nullptr;   // bring-up transport instead of RCCL (vbmf_comm_set_transport)
     void* ar_user = nullptr;
     int lds_limit = 65536;
+    double* bat = nullptr;            // vbmf_run_fixed_basis_batched: per-bag inputs / outputs and the fp64 A (grown on demand)
+    size_t bat_bytes = 0;
 };
 
 // the collective code path runs whenever a communicator is attached (also a 1-rank one: used to test it)
@@ -1088,7 +1094,7 @@ int vbmf_destroy(vbmf_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     void* bufs[] = {c->sk_list, c->sk_tail, c->gw, c->hmean, c->fws, c->t2part, c->Y1, c->Y2, c->FA_alloc, c->FB_alloc, c->FD, c->SBf, c->P, c->Q, c->Pred, c->A32, c->B32[0], c->B32[1], c->SA32,
                     c->SB32, c->gslab, c->st, c->gtmp, c->ypart, c->trpart, c->ints, c->mask, c->dS32, c->CA32, c->beta32, c->vtab,
-                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart};
+                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bat};
     for (void* b : bufs) if (b) hipFree(b);
     if (c->ints_host) hipHostFree(c->ints_host);
     if (c->scal_host) hipHostFree(c->scal_host);
@@ -1338,6 +1344,9 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
                                         hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
             });
         }
+        // vbls! as H x H algebra at 32 < H <= 64: four 64 x 66 fp64 images (135 KB)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_loop_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_batch_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
         if (e == hipSuccess && c->NH == 4)
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
         if (e == hipSuccess && c->NH == 4)
@@ -1722,9 +1731,7 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
         TRY(launch_post_gram(c, 0, Psrc));
         hipLaunchKernelGGL(copy_doubles_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, c->stream, c->st + c->lay.GA(), c->st + c->lay.W1(), n2);
         const int NBv = H <= 16 ? 1 : (H <= 32 ? 2 : 4);
-        const size_t lds = (size_t)4 * (16 * NBv) * (16 * NBv + 2) * sizeof(double);
-        static bool attr4 = false;
-        if (NBv == 4 && !attr4) { hipFuncSetAttribute((const void*)vbls_loop_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr4 = true; }
+        const size_t lds = vbls_lds_bytes(NBv);                // (the attribute for NB = 4: vbmf_create)
         if (NBv == 1) hipLaunchKernelGGL((vbls_loop_kernel<1>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M, (int)(niter - 1), c->SA32, c->ints);
         else if (NBv == 2) hipLaunchKernelGGL((vbls_loop_kernel<2>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M, (int)(niter - 1), c->SA32, c->ints);
         else hipLaunchKernelGGL((vbls_loop_kernel<4>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M, (int)(niter - 1), c->SA32, c->ints);
@@ -1733,6 +1740,96 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
         c->gA_valid = true;
         c->tr_valid = false;
     }
+    return check_device_err(c);
+}
+
+// vbls! over many bags with one fixed basis (examples/mil_util.jl:473-479 in one call).  The context's Y holds the bags side by side;
+// B, SigmaB, CB come from the state, every other input and output is per bag and lives in c->bat -- the state itself (A, SigmaA, CA,
+// sigma2) is not touched, so the same upload can be run against another basis after another vbmf_set_state.
+int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, double* sigma2, double* CA_diag,
+                                 double* SigmaA, double* AHat, int64_t ldA) {
+    if (!c) return VBMF_ERR_INVALID;
+    if (c->sparse) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: sparse context (the basic model only)");
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: a label mask is set (use vbmf_run_fixed_basis per bag)");
+    if (c->H > 64) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: H = %lld > 64", (long long)c->H);
+    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: row-sharded context (one rank only)");
+    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: niter must be >= 1");
+    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: bad nbags / col_off");
+    if (col_off[0] != 0 || col_off[nbags] != c->M)
+        FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: col_off must run from 0 to M = %lld", (long long)c->M);
+    for (int64_t b = 0; b < nbags; ++b)
+        if (col_off[b + 1] <= col_off[b]) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: bag %lld is empty or col_off decreases", (long long)b);
+    if (!sigma2 || !CA_diag) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: null sigma2 / CA_diag");
+    if (AHat && ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: ldA < M");
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    TRY(ensure_gram_B(c));
+    const int H = (int)c->H;
+    const int64_t nb = nbags, h2 = (int64_t)H * H;
+    // c->bat: [col_off (nb + 1 int64) | sigma2 nb | CA nb H | SigmaA nb H^2 | T nb H^2 | S nb H^2 | ||Y_b||^2 nb | A M H]
+    const int64_t n_off = nb + 1, o_s2 = n_off, o_ca = o_s2 + nb, o_sa = o_ca + nb * H, o_t = o_sa + nb * h2, o_s = o_t + nb * h2,
+                  o_yy = o_s + nb * h2, o_a = o_yy + nb, total = o_a + (int64_t)c->M * H;
+    if ((size_t)total * 8 > c->bat_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->bat) HIPCHK(c, hipFree(c->bat));
+        c->bat = nullptr;
+        c->bat_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&c->bat, (size_t)total * 8));
+        c->bat_bytes = (size_t)total * 8;
+    }
+    double* d = c->bat;
+    long long* d_off = reinterpret_cast<long long*>(d);
+    std::vector<double> in((size_t)(nb + nb * H));
+    memcpy(in.data(), sigma2, (size_t)nb * 8);
+    memcpy(in.data() + nb, CA_diag, (size_t)nb * H * 8);
+    HIPCHK(c, hipMemcpyAsync(d_off, col_off, (size_t)n_off * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_s2, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+    // P = Y'B of every bag: one pass 1 with the frozen B (no control chain, no A update: the state stays as it is)
+    c->P_frag = fused_gram(c) || frag_post(c);
+    TRY(launch_stream(c, 0, 0, false, nullptr, c->P_frag));
+    c->P_valid = false;
+    if (sharded(c) || c->d1.nsplit > 1) {
+        const long long n = (long long)c->Hp * c->d1.XT * 32;
+        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(n / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, n,
+                           sharded(c) ? c->P : c->Pred, n, c->ints + I_STOP, SideCopy{});
+        HIPCHK(c, hipGetLastError());
+        if (sharded(c)) TRY(allreduce_sum(c, c->P, c->Pred, (size_t)n, false));
+    }
+    const float* Psrc = (sharded(c) || c->d1.nsplit > 1) ? c->Pred : c->P;
+    const long long ldP = (long long)c->d1.XT * 32;
+    const int fnh = c->P_frag ? c->NH : 0;
+    if (c->mode == MODE_F32)
+        hipLaunchKernelGGL((bag_gram_kernel<MODE_F32>), dim3((unsigned)nb), dim3(256), 0, c->stream, Psrc, ldP, fnh, c->Y2, c->d2.KS,
+                           (long long)c->L, d_off, H, d + o_s, d + o_yy);
+    else
+        hipLaunchKernelGGL((bag_gram_kernel<MODE_BF16>), dim3((unsigned)nb), dim3(256), 0, c->stream, Psrc, ldP, fnh, c->Y2, c->d2.KS,
+                           (long long)c->L, d_off, H, d + o_s, d + o_yy);
+    HIPCHK(c, hipGetLastError());
+    const int NBv = H <= 16 ? 1 : (H <= 32 ? 2 : 4);
+    const size_t lds = vbls_lds_bytes(NBv);
+#define VBLS_BATCH(NBc_)                                                                                                              \
+    hipLaunchKernelGGL((vbls_batch_kernel<NBc_>), dim3((unsigned)nb), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg,   \
+                       d_off, (int)niter, d + o_s, d + o_yy, d + o_s2, d + o_ca, d + o_sa, d + o_t, c->ints)
+    if (NBv == 1) VBLS_BATCH(1);
+    else if (NBv == 2) VBLS_BATCH(2);
+    else VBLS_BATCH(4);
+#undef VBLS_BATCH
+    HIPCHK(c, hipGetLastError());
+    if (AHat) {
+        hipLaunchKernelGGL(bag_a_kernel, dim3(grid_for(c->M * H)), dim3(256), 0, c->stream, Psrc, ldP, fnh, d_off, (int)nb, H, d + o_t,
+                           (long long)c->M, d + o_a);
+        HIPCHK(c, hipGetLastError());
+    }
+    // read-back: [sigma2 | CA | SigmaA] is one contiguous block, A one 2-D copy into the caller's leading dimension
+    std::vector<double> out((size_t)(o_t - o_s2));
+    HIPCHK(c, hipMemcpyAsync(out.data(), d + o_s2, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    if (AHat)
+        HIPCHK(c, hipMemcpy2DAsync(AHat, (size_t)ldA * 8, d + o_a, (size_t)c->M * 8, (size_t)c->M * 8, (size_t)H, hipMemcpyDeviceToHost,
+                                   c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(sigma2, out.data(), (size_t)nb * 8);
+    memcpy(CA_diag, out.data() + nb, (size_t)nb * H * 8);
+    if (SigmaA) memcpy(SigmaA, out.data() + (o_sa - o_s2), (size_t)nb * h2 * 8);     // symmetric: row- and column-major alike
     return check_device_err(c);
 }
 

@@ -11,7 +11,7 @@
 module VBMatrixFactorizationHIP
 
 export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, updateCB!, updateSigma2!, updateYHat!,
-       vbls!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
+       vbls!, vbls_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!
@@ -251,6 +251,63 @@ function vbls!(Y::Array{Float64,2}, params::vbmf_parameters, niter::Int; diag_va
     pull!(c, params)
     params.L * params.M <= (1 << 24) && updateYHat!(params)                                   # :201
     return params.AHat
+end
+
+"""
+vbls! over many bags with one fixed basis in ONE device call (examples/mil_util.jl:473-479): does what
+`[vbls!(Y, p, niter) for (Y, p) in zip(Ys, ps)]` does for the basic model -- fills AHat, SigmaA, CA, invCA, sigma2 (and YHat up
+to 2^24 entries) of every p and returns their AHat.  The bags share L; the parameters share BHat, SigmaB and CB, carry no labels,
+and H <= 64 (anything else: vbls! per bag).  The bags are uploaded side by side into one context for the call.
+"""
+function vbls_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}, niter::Int)
+    nb = length(Ys)
+    (nb >= 1 && length(ps) == nb) || error("vbls_batch!: one parameter set per bag")
+    p0 = ps[1]
+    H, L = p0.H, size(Ys[1], 1)
+    H <= 64 || error("vbls_batch!: H = $H > 64; use vbls! per bag")
+    for b in 1:nb
+        Y, p = Ys[b], ps[b]
+        size(Y, 1) == L || error("vbls_batch!: the bags have different L; use vbls! per bag")
+        (size(Y, 2) >= 1 && (p.L, p.M, p.H) == (L, size(Y, 2), H)) || error("vbls_batch!: bag $b does not match its parameters")
+        (p.H1 == 0 && isempty(p.labels)) || error("vbls_batch!: bag $b has labels; use vbls! per bag")
+        (p.BHat == p0.BHat && p.SigmaB == p0.SigmaB && p.CB == p0.CB) ||
+            error("vbls_batch!: bag $b does not share BHat, SigmaB and CB with bag 1; use vbls! per bag")
+    end
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    M = off[end]
+    Yall = reduce(hcat, Ys)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, 0, 0xffffffff, 1, 0, 0, 0, 0, 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
+    s2 = [p.sigma2 for p in ps]
+    ca = Float64[ps[b].CA[i, i] for i in 1:H, b in 1:nb]           # CA_diag[b*H + h] (0-based)
+    SA = Array{Float64}(undef, H, H, nb)
+    A = Array{Float64}(undef, M, H)
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        ca0 = [p0.CA[i, i] for i in 1:H]; cb0 = [p0.CB[i, i] for i in 1:H]
+        chk(h[], ccall((:vbmf_set_state, libvbmf), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Float64, Ptr{Int64}, Int64, Int64),
+            h[], zeros(M, H), M, p0.BHat, L, p0.SigmaA, p0.SigmaB, ca0, cb0, p0.sigma2, Int64[], 0, 0))
+        chk(h[], ccall((:vbmf_run_fixed_basis_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+            h[], nb, off, niter, s2, ca, SA, A, M))
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+    for b in 1:nb
+        p = ps[b]
+        p.AHat = A[off[b]+1:off[b+1], :]
+        p.SigmaA = SA[:, :, b]
+        for i in 1:H                                                # CA diagonal in place (src/vbmf.jl:131)
+            p.CA[i, i] = ca[i, b]
+        end
+        p.invCA = inv(p.CA)
+        p.sigma2 = s2[b]
+        p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')        # :201
+    end
+    return [p.AHat for p in ps]
 end
 
 "copy_vbmf_params -- examples/mil_util.jl:212-236 (vbmf_parameters branch)"
