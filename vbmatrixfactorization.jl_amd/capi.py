@@ -499,9 +499,10 @@ class Context:
                         (float(x) * 0.01 for x in v)))
 
     def dims(self):
-        v = self.peek(PEEK_DIMS, 16, dtype=np.int32)
+        v = self.peek(PEEK_DIMS, 20, dtype=np.int32)
         keys = ["Hp", "NH", "mode", "XT1", "KS1", "nsplit1", "sps1", "XT2", "KS2", "nsplit2", "sps2", "kstep", "npart", "narrow",
-                "streamk_per", "streamk_grid"]       # segment-list plan of the Y*A pass: pieces per cut block (0: off), segments = workgroups
+                "streamk_per", "streamk_grid",       # segment-list plan of the Y*A pass: pieces per cut block (0: off), segments = workgroups
+                "gram", "gram_built", "gram_build_us", "gram_nsplit"]   # vbmf_run takes the Gram form; G built; its build time; split-K
         return dict(zip(keys, (int(x) for x in v)))
 
     def time_pass(self, p, iters=10):

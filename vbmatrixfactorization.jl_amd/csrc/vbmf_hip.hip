@@ -18,6 +18,9 @@
 // the reference's `while (i <= niter) && (d > eps)` would exit, so the host can enqueue sweeps ahead
 // without a per-sweep synchronisation and the state still freezes at the reference's iteration.
 //
+// Tall matrices (gram_eligible): vbmf_run takes the Gram form instead -- B = Y W with W = A SigmaB / sigma2, so a sweep reads the
+// M x M matrix G = Y'Y (built once per Y) in place of Y (gram_kernels.hpp).
+//
 // vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): ONE pass 1 with the frozen B over the bags side by side,
 // then bag_gram (S_b = P_b'P_b, ||Y_b||^2), vbls_batch (all iterations, one workgroup per bag) and bag_a (A_b = P_b SigmaA_b / sigma2_b).
 #include "../../include/vbmf_hip.h"
@@ -41,6 +44,7 @@
 #include "tile_kernels.hpp"
 #include "prep_kernels.hpp"
 #include "batch_kernels.hpp"
+#include "gram_kernels.hpp"
 
 using namespace vbmf;
 
@@ -157,6 +161,21 @@ struct vbmf_ctx {
     int lds_limit = 65536;
     double* bat = nullptr;            // vbmf_run_fixed_basis_batched: per-bag inputs / outputs and the fp64 A (grown on demand)
     size_t bat_bytes = 0;
+    // Gram-form sweep of vbmf_run (gram_kernels.hpp); buffers allocated by the first run that takes it
+    int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows
+    int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
+    int g_nsplit = 1, g_sps = 0, g_nrg = 0, g_nchunk = 0, g_rpc = 0;
+    float* Gt = nullptr;              // G = Y'Y as fp32 MFMA operand fragments [GT][2 GT][64][8]
+    bool G_valid = false;             // G is of the current Y
+    float* W32g[2] = {nullptr, nullptr};   // W = A SigmaB / sigma2, fp32 [32 GT][Hp], double-buffered like B32
+    int wcur = 0;
+    bool W_valid = false;             // B = Y W32g[wcur] and gPQ holds [G W | G D] of that W: the next sweep may take the Gram form
+    uint4* Wt = nullptr;              // operand planes of the product: W in 3 bf16 parts, D in 2
+    float* gslabs = nullptr;          // the product's split-K slabs [g_nsplit][P | Q]
+    float* gPQ = nullptr;             // [P = G W | Q = G D], fragment-major (P in the layout of the pass-1 product)
+    double* g_part = nullptr;         // per-chunk shares of [W'P | D'Q | sum A o P]
+    double* gsave = nullptr;          // [GB | GD | GX] kept across the B materialisation at the end of a run
+    double gram_build_ms = 0.0;       // device time of the last G build (HIP events)
 };
 
 // the collective code path runs whenever a communicator is attached (also a 1-rank one: used to test it)
@@ -920,7 +939,8 @@ static int fold_Q_slabs(vbmf_ctx* c) {
     return VBMF_OK;
 }
 
-static int do_update_B(vbmf_ctx* c) {
+// keep_sigma: B from the SigmaB / sigma2 table already in place (the end of a Gram-form run materialises B with the last sweep's table)
+static int do_update_B(vbmf_ctx* c, bool keep_sigma = false) {
     TRY(ensure_gram_A(c));
     // un-split pass at H <= 64: B, its tiles and the Gram partials come out of the pass's register epilogue
     const bool epi = fused_gram(c) && !c->narrow && c->d2.nsplit == 1 && (c->d2.XT / nxw_of(c->NH) + 3) / 4 <= c->gslab_cap;
@@ -929,7 +949,7 @@ static int do_update_B(vbmf_ctx* c) {
         if (fused_ctrl(c)) {
             TRY(launch_stream(c, 1, CTRL_COV_B | CTRL_EIG_BOLD, true, &nslab));
         } else {
-            TRY(launch_ctrl_cov(c, 1));
+            if (!keep_sigma) TRY(launch_ctrl_cov(c, 1));
             TRY(launch_stream(c, 1, 0, true, &nslab));
         }
         TRY(launch_pair_reduce(c, 1, nslab, c->ntr));
@@ -951,7 +971,7 @@ static int do_update_B(vbmf_ctx* c) {
         TRY(side_end(c));
         TRY(launch_stream(c, 1, 0, false, nullptr, fragq));
     } else {
-        TRY(launch_ctrl_cov(c, 1));
+        if (!keep_sigma) TRY(launch_ctrl_cov(c, 1));
         TRY(launch_stream(c, 1, 0, false, nullptr, fragq));
     }
     TRY(fold_Q_slabs(c));
@@ -965,6 +985,149 @@ static int do_update_B(vbmf_ctx* c) {
     }
     c->bcur ^= 1;
     c->gB_valid = true;
+    c->P_valid = false;
+    c->tr_valid = true;
+    return VBMF_OK;
+}
+
+// ---- Gram-form sweep (gram_kernels.hpp) ----------------------------------------------------------------
+// Taken by vbmf_run when the structure allows it (basic variant, one rank, bf16 Y, bf16x2 factors, Hp <= 128) and Y is tall enough
+// for building G = Y'Y once to pay: L >= 4 M and L M >= 2^27 (below that a streaming pass costs a few launch latencies).
+// VBMF_GRAM=0 turns it off, VBMF_GRAM=1 on whenever the structure allows.
+static bool gram_structural(const vbmf_ctx* c) {
+    return !c->sparse && !c->diagvar && !c->dual && !c->trial && !sharded(c) && c->o.nranks == 1 && c->o.y_dtype == VBMF_Y_BF16 &&
+           c->mode == MODE_BF16X2 && c->Hp <= 128;
+}
+static bool gram_eligible(const vbmf_ctx* c) {
+    if (c->gram_env == 0 || !gram_structural(c)) return false;
+    if (c->gram_env == 1) return true;
+    return c->L >= 4 * c->M && (double)c->L * (double)c->M >= 134217728.0;
+}
+
+// buffers (first time) and G of the current Y (once per Y)
+static int gram_prepare(vbmf_ctx* c) {
+    if (!c->Gt) {
+        c->GT = (int)rup(c->d1.XT, 16);
+        const int KT = 2 * c->GT;
+        const int nxw = c->NH == 4 ? 1 : (c->NH == 2 ? 2 : 4);                 // = the gram_prod_kernel instantiations below
+        c->g_nrg = c->GT / (4 * nxw);
+        // split-K: about one workgroup per CU, each split at least 8 k-steps
+        c->g_nsplit = std::max(1, std::min(KT / 8, NUM_CU / std::max(1, c->g_nrg)));
+        c->g_sps = cdiv(KT, c->g_nsplit);
+        c->g_nsplit = cdiv(KT, c->g_sps);
+        const int64_t Mp1 = (int64_t)c->d1.XT * 32;
+        c->g_nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(256, cdiv(c->M, 32)));
+        c->g_rpc = (int)rup(cdiv(c->M, c->g_nchunk), GPART_ROWS);
+        c->g_nchunk = cdiv(c->M, c->g_rpc);
+        const size_t n = (size_t)c->Hp * Mp1;
+        const size_t wrows = (size_t)32 * c->GT;
+        auto alloc = [&](void** p, size_t bytes) -> hipError_t {
+            hipError_t e = hipMalloc(p, bytes);
+            if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+            return e;
+        };
+        hipError_t e = alloc((void**)&c->Gt, (size_t)c->GT * KT * 64 * 8 * 4);
+        if (e == hipSuccess) e = alloc((void**)&c->W32g[0], wrows * c->Hp * 4);
+        if (e == hipSuccess) e = alloc((void**)&c->W32g[1], wrows * c->Hp * 4);
+        if (e == hipSuccess) e = alloc((void**)&c->Wt, (size_t)GRAM_PLANES * KT * c->NH * 64 * 16);
+        if (e == hipSuccess) e = alloc((void**)&c->gPQ, 2 * n * 4);
+        if (e == hipSuccess && c->g_nsplit > 1) e = alloc((void**)&c->gslabs, (size_t)c->g_nsplit * 2 * n * 4);
+        if (e == hipSuccess) e = alloc((void**)&c->g_part, (size_t)c->g_nchunk * (2 * (size_t)c->Hp * c->Hp + 1) * 8);
+        if (e == hipSuccess) e = alloc((void**)&c->gsave, (2 * (size_t)c->Hp * c->Hp + 8) * 8);
+        if (e != hipSuccess) {
+            for (void* b : {(void*)c->Gt, (void*)c->W32g[0], (void*)c->W32g[1], (void*)c->Wt, (void*)c->gPQ, (void*)c->gslabs,
+                            (void*)c->g_part, (void*)c->gsave})
+                if (b) hipFree(b);
+            c->Gt = nullptr; c->W32g[0] = c->W32g[1] = nullptr; c->Wt = nullptr; c->gPQ = nullptr; c->gslabs = nullptr;
+            c->g_part = nullptr; c->gsave = nullptr;
+            FAIL(c, VBMF_ERR_HIP, "Gram-form sweep: device allocation failed (%s)", hipGetErrorString(e));
+        }
+        c->G_valid = false;
+    }
+    if (c->G_valid) return VBMF_OK;
+    hipEvent_t a, b;
+    HIPCHK(c, hipEventCreate(&a));
+    HIPCHK(c, hipEventCreate(&b));
+    hipEventRecord(a, c->stream);
+    const int NB = c->GT / 4;
+    hipLaunchKernelGGL(gram_build_kernel, dim3(NB, NB), dim3(256), 0, c->stream, c->Y1, c->d1.XT, c->d1.KS, c->Gt, c->GT);
+    const hipError_t le = hipGetLastError();
+    hipEventRecord(b, c->stream);
+    const hipError_t se = hipEventSynchronize(b);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, a, b);
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    HIPCHK(c, le);
+    HIPCHK(c, se);
+    c->gram_build_ms = ms;
+    c->G_valid = true;
+    c->W_valid = false;
+    return VBMF_OK;
+}
+
+// W_new = A SigmaB / sigma2 and D = W_new - W_old (into W32g[wcur ^ 1]; the caller flips wcur), then [P | Q] = G [W_new | D];
+// partials: the state's [B'B | dB'dB | tr(B'YA)] of B = Y W_new from it.  Profile slot 1 brackets the product.
+static int gram_product(vbmf_ctx* c, bool partials) {
+    const int* stop = c->ints + I_STOP;
+    const int KT = 2 * c->GT;
+    const int64_t Mp1 = (int64_t)c->d1.XT * 32;
+    const long long n = (long long)c->Hp * Mp1;
+    const float* Wo = c->W32g[c->wcur];
+    float* Wn = c->W32g[c->wcur ^ 1];
+    hipLaunchKernelGGL(gram_w_kernel, dim3(KT), dim3(256), 0, c->stream, c->A32, c->SB32,
+                       Wo, Wn, c->Wt, (long long)c->M, c->Hp, KT, stop);
+    HIPCHK(c, hipGetLastError());
+    float* out = c->g_nsplit > 1 ? c->gslabs : c->gPQ;
+    const dim3 grid(c->g_nrg * c->g_nsplit);
+    const float4* G4 = reinterpret_cast<const float4*>(c->Gt);
+    prof_begin(c, 0);
+    if (c->NH == 1) hipLaunchKernelGGL((gram_prod_kernel<1, 4>), grid, dim3(256), 0, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    else if (c->NH == 2) hipLaunchKernelGGL((gram_prod_kernel<2, 2>), grid, dim3(256), 0, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    else hipLaunchKernelGGL((gram_prod_kernel<4, 1>), grid, dim3(256), 0, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    prof_end(c);
+    HIPCHK(c, hipGetLastError());
+    if (c->g_nsplit > 1) {
+        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(2 * n / 4, 256, 2048)), dim3(256), 0, c->stream, c->gslabs, c->g_nsplit, 2 * n,
+                           c->gPQ, 2 * n, stop, SideCopy{});
+        HIPCHK(c, hipGetLastError());
+    }
+    if (partials) {
+        const dim3 pg(c->g_nchunk);
+        if (c->Hp == 32) hipLaunchKernelGGL((gram_part_kernel<32>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
+        else if (c->Hp == 64) hipLaunchKernelGGL((gram_part_kernel<64>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
+        else hipLaunchKernelGGL((gram_part_kernel<128>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(gram_part_reduce_kernel, dim3(cdiv(2 * (int64_t)c->Hp * c->Hp + 1, GRED_E)), dim3(256), 0, c->stream, c->g_part,
+                           c->g_nchunk, c->Hp, c->st, c->lay, stop);
+        HIPCHK(c, hipGetLastError());
+    }
+    return VBMF_OK;
+}
+
+// the end of a sweep in the Gram form: lambda_max of dB'dB and of the new B'B, then CA, CB, sigma2, ELBO, d and the loop test
+static int gram_sweep_end(vbmf_ctx* c) {
+    TRY(launch_eig(c, 1, 1));
+    TRY(launch_ctrl_end(c, c->run_flags, c->run_eps, c->run_trace));
+    ++c->ends_enqueued;
+    return VBMF_OK;
+}
+
+// one sweep from P = Y'B_old = G W_old (in gPQ) and the state's B'B: SigmaA, A (label mask) and A'A, SigmaB, then W, the product
+// and the closing control step.  The control kernels are the stand-alone forms of the ones that ride in the pass launches.
+static int gram_sweep(vbmf_ctx* c) {
+    TRY(launch_ctrl_cov(c, 0));
+    c->P_frag = true;
+    if (fused_gram(c)) TRY(launch_post_gram(c, 0, c->gPQ));
+    else {
+        TRY(launch_post_frag(c, 0, c->gPQ));
+        TRY(launch_gram(c, 0, c->A32, nullptr, true));
+    }
+    TRY(launch_ctrl_cov(c, 1));
+    TRY(gram_product(c, true));
+    c->wcur ^= 1;
+    TRY(gram_sweep_end(c));
+    c->gA_valid = c->gB_valid = true;
     c->P_valid = false;
     c->tr_valid = true;
     return VBMF_OK;
@@ -1094,7 +1257,8 @@ int vbmf_destroy(vbmf_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     void* bufs[] = {c->sk_list, c->sk_tail, c->gw, c->hmean, c->fws, c->t2part, c->Y1, c->Y2, c->FA_alloc, c->FB_alloc, c->FD, c->SBf, c->P, c->Q, c->Pred, c->A32, c->B32[0], c->B32[1], c->SA32,
                     c->SB32, c->gslab, c->st, c->gtmp, c->ypart, c->trpart, c->ints, c->mask, c->dS32, c->CA32, c->beta32, c->vtab,
-                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bat};
+                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bat, c->Gt, c->W32g[0], c->W32g[1], c->Wt, c->gslabs, c->gPQ,
+                    c->g_part, c->gsave};
     for (void* b : bufs) if (b) hipFree(b);
     if (c->ints_host) hipHostFree(c->ints_host);
     if (c->scal_host) hipHostFree(c->scal_host);
@@ -1155,6 +1319,7 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
     if (c->Hp > 128 && c->Hp < 256) c->Hp = 256;
     c->NH = c->Hp / 32;
     if (const char* e = getenv("VBMF_XCD_MAP")) c->xcd_map = atoi(e) != 0;      // A/B switch for the tuning record
+    if (const char* e = getenv("VBMF_GRAM")) c->gram_env = atoi(e) != 0 ? 1 : 0;  // Gram-form sweep: force off / on (gram_eligible)
     if (const char* e = getenv("VBMF_EPI_BALANCE")) c->epi_balance = atoi(e) != 0;
     if (const char* e = getenv("VBMF_LDS8")) c->lds8 = atoi(e) != 0;
     if (const char* e = getenv("VBMF_POST3")) c->post3 = atoi(e) != 0;
@@ -1395,6 +1560,7 @@ static int finish_Y(vbmf_ctx* c) {
     c->haveY = true;
     c->P_valid = false;
     c->Q_valid = false;
+    c->G_valid = c->W_valid = false;                   // G = Y'Y is rebuilt by the next run that takes the Gram form
     c->tr_valid = false;
     if (c->diagvar) {                                  // ||Y_l||^2 of every row (:310), from the stored values
         DISPATCH_MODE(c->mode, {
@@ -1646,6 +1812,7 @@ int vbmf_set_state(vbmf_ctx* c, const double* AHat, int64_t ldA, const double* B
     if (c->dbg_sb_ppm) HIPCHK(c, hipMemcpyAsync(c->ints + I_DBG_SB_PPM, &c->dbg_sb_ppm, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->gA_valid = c->gB_valid = c->P_valid = c->tr_valid = false;
+    c->W_valid = false;                                // B is no longer Y W: the next run starts by the streaming path
     c->B32_stale = false;
     c->haveState = true;
     return VBMF_OK;
@@ -1681,6 +1848,7 @@ int vbmf_step(vbmf_ctx* c, int which) {
     if (which & ~31) FAIL(c, VBMF_ERR_INVALID, "vbmf_step: unknown update bits");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c, (which & (VBMF_STEP_A | VBMF_STEP_B | VBMF_STEP_SIGMA2)) != 0));
+    c->W_valid = false;
     if (which & VBMF_STEP_A) TRY(do_update_A(c));
     if (which & VBMF_STEP_B) TRY(do_update_B(c));
     int flags = 0;
@@ -1709,6 +1877,7 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
     if (niter < 0 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis: bad niter");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c));
+    c->W_valid = false;
     // Without a label mask the loop is H x H algebra on S = P'P (ctrl_kernels.hpp, vbls_loop_kernel): the first iteration runs the
     // general way (it forms P = Y'B), the rest in ONE launch of one workgroup, and A is formed once at the end.  H <= 64.
     // (VBMF_VBLS_LOOP=0: every iteration the general way -- the A/B switch of profiles/r03_f_vbls_mil.txt)
@@ -1763,6 +1932,7 @@ int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_
     if (AHat && ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: ldA < M");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c));
+    c->W_valid = false;
     TRY(ensure_gram_B(c));
     const int H = (int)c->H;
     const int64_t nb = nbags, h2 = (int64_t)H * H;
@@ -1843,6 +2013,11 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     if (iters_done) *iters_done = 0;
     if (d_last) *d_last = eps + 1.0;                       // src/vbmf.jl:189
     if (niter == 0) return VBMF_OK;
+    // Gram form: G = Y'Y is built here once per Y; a run that starts without a valid W does its first sweep
+    // by the streaming path
+    const bool gram = gram_eligible(c);
+    if (gram) TRY(gram_prepare(c));
+    else c->W_valid = false;
     double* trace_dev = nullptr;
     if (trace) {
         HIPCHK(c, hipMalloc((void**)&trace_dev, (size_t)niter * 4 * 8));
@@ -1861,7 +2036,8 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
             hipLaunchKernelGGL(copy_scalar_kernel, dim3(1), dim3(1), 0, c->stream, c->st, c->lay, (int)S_LAMB_PREV, (int)S_LAMB_NEW);
     }
     const int flags = (est_covs ? 3 : 0) | (est_var ? 4 : 0) | 8 | 16;
-    const int bstart = c->bcur;
+    const int bstart = c->bcur, wstart = c->wcur;
+    int64_t stream_sweeps = 0;                             // sweeps enqueued by the streaming path (Gram form: at most the first)
     c->in_run = true;
     c->ends_enqueued = 0;
     c->tail_pending = false;
@@ -1877,11 +2053,24 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     int slot = 0;
     bool pending[2] = {false, false};
     while (rc == VBMF_OK && it < niter && !stopped) {
-        rc = do_update_A(c);                 // carries lambda_max + ctrl_end of the previous sweep when fused
-        if (rc == VBMF_OK) rc = do_update_B(c);
-        ++it;
+        if (gram && c->W_valid) {
+            rc = gram_sweep(c);              // the whole sweep, its closing control step included
+            ++it;
+        } else {
+            rc = do_update_A(c);             // carries lambda_max + ctrl_end of the previous sweep when fused
+            if (rc == VBMF_OK) rc = do_update_B(c);
+            ++it;
+            ++stream_sweeps;
+            if (rc == VBMF_OK && gram) {
+                // W of this sweep and P = G W for the next one; the Grams of this sweep came from the pass's epilogue
+                rc = gram_product(c, false);
+                c->wcur ^= 1;
+                c->W_valid = true;
+                if (rc == VBMF_OK) rc = gram_sweep_end(c);
+            }
+        }
         const bool last = (it == niter);
-        if (rc == VBMF_OK) {
+        if (rc == VBMF_OK && !gram) {
             if (fused_ctrl(c) && !last) {
                 c->tail_pending = true;      // rides in the next sweep's pass-1 launch
             } else if (fused_ctrl(c)) {
@@ -1925,9 +2114,17 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { c->err = std::string("run readback: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
     }
+    int64_t gram_done = 0;                                 // Gram-form sweeps the device executed
     if (rc == VBMF_OK) {
         const int done = c->ints_host[I_ITERS];
-        c->bcur = bstart ^ (done & 1);                    // sweeps after `stop` were no-ops on the device
+        // sweeps after `stop` were no-ops on the device; in the Gram form only the streaming sweep (the first, if any) moves B,
+        // and every sweep moves W
+        const int64_t sdone = std::min<int64_t>(done, stream_sweeps);
+        c->bcur = bstart ^ (int)(sdone & 1);
+        if (gram) {
+            c->wcur = wstart ^ (done & 1);
+            gram_done = done - sdone;
+        }
         rc = rebuild_B32_if_stale(c);                     // the fp32 factor from the tiles the last executed sweep wrote
         if (iters_done) *iters_done = done;
         if (d_last && done > 0) *d_last = c->scal_host[S_D];
@@ -1943,6 +2140,23 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     c->gA_valid = c->gB_valid = true;
     c->P_valid = false;
     c->tr_valid = true;
+    if (gram && rc != VBMF_OK) c->W_valid = false;
+    if (gram && rc == VBMF_OK && gram_done > 0) {
+        // B of the last executed sweep, eagerly, by the streaming pass 2 with that sweep's A and SigmaB / sigma2 (the table in place):
+        // B, its operand tiles and the fp32 copy as a streaming run leaves them.  The state's [B'B | dB'dB | tr(B'YA)] stay the Gram
+        // form's, so a run that continues from here computes what one longer run computes.
+        const size_t nsave = 2 * (size_t)c->Hp * c->Hp + 8;
+        hipError_t e = hipMemcpyAsync(c->gsave, c->st + c->lay.GB(), nsave * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) rc = do_update_B(c, true);
+        else { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+        if (rc == VBMF_OK) {
+            e = hipMemcpyAsync(c->st + c->lay.GB(), c->gsave, nsave * 8, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+        }
+        if (rc == VBMF_OK) rc = check_device_err(c);
+        if (rc != VBMF_OK) c->W_valid = false;
+    }
     return rc;
 }
 
@@ -2045,6 +2259,13 @@ int vbmf_pass_bytes(vbmf_ctx* c, int pass, double* bytes) {
     // (fp32 equivalent), the H-wide result out (fp32)
     const double ybytes = (c->mode == MODE_F32) ? 4.0 : 2.0;
     const double LM = (double)c->L * (double)c->M;
+    if (pass == 1 && gram_eligible(c)) {
+        // Gram form: profile slot 1 times the product [G W | G D] -- G once (fp32), the five bf16 operand planes, the fp32 slabs out
+        const double n = (double)c->Hp * c->d1.XT * 32.0;
+        const int nsplit = c->Gt ? c->g_nsplit : 1;
+        *bytes = (double)c->M * c->M * 4.0 + 5.0 * c->M * c->H * 2.0 + 2.0 * n * 4.0 * nsplit;
+        return VBMF_OK;
+    }
     if (pass == 1) *bytes = LM * ybytes + (double)c->L * c->H * 4.0 + (double)c->M * c->H * 4.0;
     else {
         // with the register epilogue (un-split pass, H <= 64) the launch writes B and re-reads B_old instead of writing
@@ -2060,9 +2281,10 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (what == VBMF_PEEK_DIMS) {
-        const int v[16] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
-                           c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid};
-        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(16, nwords));
+        const int v[20] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
+                           c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
+                           gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit};
+        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(20, nwords));
         return VBMF_OK;
     }
     if (what == VBMF_PEEK_CHAIN) {
