@@ -294,6 +294,9 @@ int vbmf_device_sync(vbmf_ctx* ctx);
 #define VBMF_PEEK_CHAIN 9  /* uint64 x 8 (16 words): last durations in 10 ns ticks of the in-launch control chain's parts
                               (ctrl_end, SigmaA, lambda_max(dB'dB) + loop test, SigmaB) and of the register epilogue's tail in
                               workgroup 0 of the Y*A pass (wait for + load of the SigmaB table, tiles, fold + store, reserved) */
+#define VBMF_PEEK_STATE 10 /* fp64 control state (two words per double): [A'A | B'B | dB'dB | tr(B'YA) x 8 | ...], Hp x Hp blocks */
+#define VBMF_PEEK_GRAM_W 11 /* Gram form: the current W fp32 row-major [32 GT][Hp] (rows >= M zero) */
+#define VBMF_PEEK_GRAM_PQ 12 /* Gram form: [P | Q] = G [W | W - W_old], fp32, each [XT1][NH][64][16] fragment-major */
 int vbmf_debug_peek(vbmf_ctx* ctx, int what, uint32_t* out, int64_t nwords, int64_t word_offset);
 /* tuning hook: average milliseconds of `iters` back-to-back launches of streaming pass p (1|2) alone */
 int vbmf_debug_time_pass(vbmf_ctx* ctx, int pass, int iters, double* ms);

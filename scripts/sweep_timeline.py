@@ -21,6 +21,10 @@ def short(n):
 idx = [i for i, e in enumerate(ev) if "stream_gemm_kernel" in e[2] or "stream_lds8_kernel" in e[2]]
 # pass 1 and pass 2 alternate in the run loop: take launches from the end
 starts = idx[::2] if len(idx) % 2 == 0 else idx[1::2]
+# the Gram form streams Y only at run boundaries: one sweep runs from one gram_w launch to the next
+gw = [i for i, e in enumerate(ev) if "gram_w_kernel" in e[2]]
+if len(gw) > back + 1:
+    starts = gw
 s0, s1 = starts[-back - 1], starts[-back]
 t0 = ev[s0][0]
 prev_end = None

@@ -6,10 +6,10 @@
 //
 //   gram_build_kernel      G = Y'Y from the pass-1 tiles of Y (bf16 products are exact in fp32; fp32 over chunks of GRAM_CHUNK
 //                          k-steps, the chunks summed in fp64, rounded once); upper 128 x 128 blocks, each stored with its mirror
-//   gram_w_kernel          W_new = A (SigmaB / sigma2), D = W_new - W_old; fp32 W and the product's bf16 operand planes
+//   gram_w_kernel          W_new = A (SigmaB / sigma2) on fp64 MFMA, D = W_new - W_old; fp32 W and the product's bf16 operand planes
 //   gram_prod_kernel       [P | Q] = G [W | D] as split-K slabs in the fragment-major layout of the pass-1 product
-//   gram_part_kernel       per-chunk fp64 shares of W'P, D'Q and sum A o P
-//   gram_part_reduce_kernel  fixed-order sum of the shares -> the state's [B'B | dB'dB | tr(B'YA)] (symmetrised)
+//   gram_part_kernel       per-chunk fp64 shares of W'P, D'Q (each product once, on fp64 MFMA) and sum A o P
+//   gram_part_reduce_kernel  fixed-order sum of the shares -> the state's [B'B | dB'dB | tr(B'YA)], symmetrised as (C + C') / 2
 //
 // Layouts.  G is stored as MFMA operand fragments, fp32: Gt[row tile p][k-step j][lane][8], lane (half, c) holds
 // G[32p + c][16j + 8 half + e], e = 0..7 (GT row tiles, KT = 2 GT k-steps; rows / columns >= M are zero).  Because G is symmetric this
@@ -118,57 +118,79 @@ __global__ __launch_bounds__(256) void gram_build_kernel(const uint4* __restrict
         }
 }
 
-// W_new = A S (S = SigmaB / sigma2, Hp x Hp fp32, zero outside H x H), D = W_new - W_old.  Workgroup j: the 16 rows of k-step j
-// (A rows through LDS); thread (h tile ht, lane) the eight rows m = 16 j + 8 half + e of column h = 32 ht + c.  Rows >= M are zero.
-__global__ __launch_bounds__(256) void gram_w_kernel(const float* __restrict__ A32, const float* __restrict__ S,
-                                                     const float* __restrict__ Wold, float* __restrict__ Wnew,
-                                                     uint4* __restrict__ Wt, long long M, int Hp, int KT, const int* __restrict__ stop) {
+// W_new = A S (S = SigmaB / sigma2, Hp x Hp fp32, zero outside H x H), D = W_new - W_old, on v_mfma_f64_16x16x4_f64 (blk_inverse.hpp's
+// register layouts).  Workgroup b: the GW_ROWS rows of k-steps [GW_KS b, GW_KS (b + 1)); wave cb (HP / 16 of them) the 16 columns
+// [16 cb, 16 cb + 16).  The wave holds its column panel of S in registers as B operands (lane (q, c), chunk (s, t): S[16 s + 4 q + t]
+// [16 cb + c]) and reads A as float4 rows (lane (q, c): A[m0 + c][16 s + 4 q .. + 3], element t the A operand of chunk (s, t)), so
+// every product is an fp64 sum of exact fp32 x fp32 products.  W, rounded to fp32, goes through LDS to the pack stage: thread
+// (k-step, h tile ht, lane) the eight rows m = 16 j + 8 half + e of column h = 32 ht + c, written as the old one-workgroup-per-k-step
+// kernel wrote them (fp32 W, D formed in fp64 then rounded, 3 + 2 bf16 planes).  Rows >= M are zero.
+constexpr int GW_KS = 2, GW_ROWS = 16 * GW_KS;
+template <int HP>
+__global__ __launch_bounds__(HP * 4) void gram_w_kernel(const float* __restrict__ A32, const float* __restrict__ S,
+                                                        const float* __restrict__ Wold, float* __restrict__ Wnew,
+                                                        uint4* __restrict__ Wt, long long M, int KT, const int* __restrict__ stop) {
     if (*stop) return;
-    __shared__ float sA[16][128];
-    const long long j = blockIdx.x;
-    for (int t = threadIdx.x; t < 16 * Hp; t += blockDim.x) {
-        const int r = t / Hp, i = t % Hp;
-        const long long m = 16 * j + r;
-        sA[r][i] = m < M ? A32[m * Hp + i] : 0.f;
+    constexpr int NS = HP / 16, NH = HP / 32, NT = HP * 4;
+    __shared__ float sW[GW_ROWS][HP + 1];
+    const int lane = threadIdx.x & 63, cb = threadIdx.x >> 6;
+    const int q = lane >> 4, c = lane & 15;
+    const long long row0 = (long long)blockIdx.x * GW_ROWS;
+    double sb[NS][4];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sb[s][t] = (double)S[(long long)(16 * s + 4 * q + t) * HP + 16 * cb + c];
+#pragma unroll
+    for (int mb = 0; mb < GW_KS; ++mb) {
+        const long long m = row0 + 16 * mb + c;
+        float4 a[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            a[s] = m < M ? *reinterpret_cast<const float4*>(A32 + m * HP + 16 * s + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[s].x, sb[s][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[s].y, sb[s][1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[s].z, sb[s][2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[s].w, sb[s][3], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sW[16 * mb + q + 4 * r][16 * cb + c] = (float)acc[r];
     }
     __syncthreads();
-    const int NH = Hp / 32;
-    if ((int)threadIdx.x >= NH * 64) return;
-    const int lane = threadIdx.x & 63, ht = threadIdx.x >> 6;
-    const int half = lane >> 5, h = 32 * ht + (lane & 31);
-    double acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.0;
-    for (int i = 0; i < Hp; ++i) {
-        const double sv = (double)S[(long long)i * Hp + h];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += (double)sA[8 * half + e][i] * sv;
-    }
-    unsigned short wp[3][8], dp[2][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const long long m = 16 * j + 8 * half + e;
-        const float wv = (float)acc[e];
-        const float dv = (float)((double)wv - (double)Wold[m * Hp + h]);
-        Wnew[m * Hp + h] = wv;
-        wp[0][e] = f2bf(wv);
-        float res = wv - bf2f(wp[0][e]);
-        wp[1][e] = f2bf(res);
-        res -= bf2f(wp[1][e]);
-        wp[2][e] = f2bf(res);
-        dp[0][e] = f2bf(dv);
-        dp[1][e] = f2bf(dv - bf2f(dp[0][e]));
-    }
     const long long plane = (long long)KT * NH * 64;
-    const long long o = (j * NH + ht) * 64 + lane;
+    for (int it = threadIdx.x; it < GW_KS * NH * 64; it += NT) {
+        const int jj = it / (NH * 64), ht = (it / 64) % NH, ln = it & 63;
+        const int half = ln >> 5, h = 32 * ht + (ln & 31);
+        const long long j = (long long)blockIdx.x * GW_KS + jj;
+        if (j >= KT) continue;
+        unsigned short wp[3][8], dp[2][8];
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-        Wt[q * plane + o] = make_uint4(pack_bf2(wp[q][0], wp[q][1]), pack_bf2(wp[q][2], wp[q][3]), pack_bf2(wp[q][4], wp[q][5]),
-                                       pack_bf2(wp[q][6], wp[q][7]));
+        for (int e = 0; e < 8; ++e) {
+            const long long m = 16 * j + 8 * half + e;
+            const float wv = sW[16 * jj + 8 * half + e][h];
+            const float dv = (float)((double)wv - (double)Wold[m * HP + h]);
+            Wnew[m * HP + h] = wv;
+            wp[0][e] = f2bf(wv);
+            float res = wv - bf2f(wp[0][e]);
+            wp[1][e] = f2bf(res);
+            res -= bf2f(wp[1][e]);
+            wp[2][e] = f2bf(res);
+            dp[0][e] = f2bf(dv);
+            dp[1][e] = f2bf(dv - bf2f(dp[0][e]));
+        }
+        const long long o = (j * NH + ht) * 64 + ln;
 #pragma unroll
-    for (int q = 0; q < 2; ++q)
-        Wt[(3 + q) * plane + o] = make_uint4(pack_bf2(dp[q][0], dp[q][1]), pack_bf2(dp[q][2], dp[q][3]), pack_bf2(dp[q][4], dp[q][5]),
-                                             pack_bf2(dp[q][6], dp[q][7]));
+        for (int p = 0; p < 3; ++p)
+            Wt[p * plane + o] = make_uint4(pack_bf2(wp[p][0], wp[p][1]), pack_bf2(wp[p][2], wp[p][3]), pack_bf2(wp[p][4], wp[p][5]),
+                                           pack_bf2(wp[p][6], wp[p][7]));
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            Wt[(3 + p) * plane + o] = make_uint4(pack_bf2(dp[p][0], dp[p][1]), pack_bf2(dp[p][2], dp[p][3]), pack_bf2(dp[p][4], dp[p][5]),
+                                                 pack_bf2(dp[p][6], dp[p][7]));
+    }
 }
 
 // three bf16 parts of 8 fp32 values as MFMA operand fragments
@@ -275,93 +297,143 @@ __global__ __launch_bounds__(256) void gram_prod_kernel(const float4* __restrict
     }
 }
 
-// per-chunk fp64 shares: part[c] = [W'P + P'W (Hp^2) | D'Q + Q'D (Hp^2) | sum A o P] over rows [c rpc, (c + 1) rpc) of the M real
-// rows (symmetrised here, halved by the reduction).  1024 threads; rows pass through LDS GPART_ROWS at a time, P and Q read through
-// frag_index from the fragment-major products.  (Staging them as fp64 instead, to save the conversions, was slower: 50 vs 33 us.)
-constexpr int GPART_ROWS = 16;
+// per-chunk fp64 shares on v_mfma_f64_16x16x4_f64: part[c] = [W'P (Hp^2) | D'Q (Hp^2) | sum A o P] over rows [c rpc, (c + 1) rpc) of
+// the M real rows, each product formed once (the reduction symmetrises).  1024 threads = S row subsets x 2 products x V column
+// offsets, V = HP / 16, S = 8 / V.  Lane (q, c) of wave (s, pi, tw) takes, per 4-row step of its subset (steps s, s + S, ...), row
+// m = m0 + 4 step + q: the V columns V c .. V c + V - 1 of P (pi = 0) or Q (pi = 1) as whole 16-byte pieces of the fragment-major
+// product (frag_index; V = 2: 8 bytes), which are its B operands (column V c + t in accumulator t), and the one value of W (or D,
+// formed in fp64 and rounded to fp32, as gram_w forms it) at column V c + tw, its A operand.  Accumulator t thus holds
+// C[V (q + 4 r) + tw][V c + t] in register r; fp32 x fp32 products are exact in fp64.  The pi = 0 waves also sum A o P at their
+// column.  The S subsets are folded through LDS in subset order; the share is stored in register order (gpart_index).
+template <int HP>
+struct GPart {
+    static constexpr int V = HP / 16, S = 8 / V, NH = HP / 32;
+};
+// position of C[a][b] of one product inside a share (register order of gram_part_kernel)
+template <int HP>
+__device__ __forceinline__ int gpart_index(int a, int b) {
+    constexpr int V = GPart<HP>::V;
+    const int tw = a % V, i = a / V, t = b % V, c = b / V;
+    return ((((tw * V + t) * 4 + (i >> 2)) << 6) + 16 * (i & 3) + c);
+}
 template <int HP>
 __global__ __launch_bounds__(1024) void gram_part_kernel(const float* __restrict__ PQ, long long n, const float* __restrict__ Wn,
                                                          const float* __restrict__ Wo, const float* __restrict__ A32, long long M,
                                                          int rpc, double* __restrict__ part, const int* __restrict__ stop) {
     if (*stop) return;
-    constexpr int NH = HP / 32, EPT = HP * HP / 1024, RB = GPART_ROWS;
-    __shared__ float sW[RB][HP], sP[RB][HP], sD[RB][HP], sQ[RB][HP];
+    constexpr int V = GPart<HP>::V, S = GPart<HP>::S, NH = GPart<HP>::NH, U = 4;   // U steps' loads in flight
+    __shared__ f64x4 fold[S > 1 ? (S - 1) * 2 * V * V * 64 : 1];
     __shared__ double red[16];
-    double gb[EPT], gd[EPT], tr = 0.0;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int s = w / (2 * V), task = w % (2 * V), pi = task / V, tw = task % V;
+    const int q = lane >> 4, c = lane & 15;
+    const float* src = PQ + (pi ? n : 0);
+    f64x4 acc[V];
 #pragma unroll
-    for (int u = 0; u < EPT; ++u) { gb[u] = 0.0; gd[u] = 0.0; }
+    for (int t = 0; t < V; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double tr = 0.0;
     const long long m0 = (long long)blockIdx.x * rpc, m1 = min(m0 + rpc, M);
-    for (long long mb = m0; mb < m1; mb += RB) {
-        __syncthreads();
-        for (int t = threadIdx.x; t < RB * HP; t += 1024) {
-            const int r = t / HP, h = t % HP;
-            const long long m = mb + r;
-            float w = 0.f, p = 0.f, d = 0.f, q = 0.f;
-            if (m < m1) {
-                const long long f = frag_index(h, m, NH);
-                w = Wn[m * HP + h];
-                d = (float)((double)w - (double)Wo[m * HP + h]);
-                p = PQ[f];
-                q = PQ[n + f];
-                tr += (double)A32[m * HP + h] * (double)p;
-            }
-            sW[r][h] = w; sP[r][h] = p; sD[r][h] = d; sQ[r][h] = q;
-        }
-        __syncthreads();
+    const int nstep = (int)((m1 - m0 + 3) / 4);
+    for (int k0 = s; k0 < nstep; k0 += S * U) {
+        float pv[U][V], wv[U], xv[U];
 #pragma unroll
-        for (int u = 0; u < EPT; ++u) {
-            const int e = threadIdx.x + 1024 * u, i = e / HP, k = e % HP;
-            double sb = 0.0, sd = 0.0;
-#pragma unroll 4
-            for (int r = 0; r < RB; ++r) {
-                sb += (double)sW[r][i] * (double)sP[r][k] + (double)sW[r][k] * (double)sP[r][i];
-                sd += (double)sD[r][i] * (double)sQ[r][k] + (double)sD[r][k] * (double)sQ[r][i];
+        for (int u = 0; u < U; ++u) {
+            const long long m = m0 + 4LL * (k0 + u * S) + q;
+            if (m < m1) {
+                if constexpr (V == 2) {
+                    const float2 v = *reinterpret_cast<const float2*>(src + frag_index(2 * c, m, NH));
+                    pv[u][0] = v.x; pv[u][1] = v.y;
+                } else {
+#pragma unroll
+                    for (int g = 0; g < V / 4; ++g) {
+                        const float4 v = *reinterpret_cast<const float4*>(src + frag_index(V * c + 4 * g, m, NH));
+                        pv[u][4 * g] = v.x; pv[u][4 * g + 1] = v.y; pv[u][4 * g + 2] = v.z; pv[u][4 * g + 3] = v.w;
+                    }
+                }
+                wv[u] = Wn[m * HP + V * c + tw];
+                xv[u] = (pi ? Wo : A32)[m * HP + V * c + tw];
+            } else {
+#pragma unroll
+                for (int t = 0; t < V; ++t) pv[u][t] = 0.f;
+                wv[u] = 0.f; xv[u] = 0.f;
             }
-            gb[u] += sb;
-            gd[u] += sd;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            double a = (double)wv[u];
+            if (pi) a = (double)(float)(a - (double)xv[u]);
+            else {
+                float p = 0.f;
+#pragma unroll
+                for (int t = 0; t < V; ++t) p = t == tw ? pv[u][t] : p;
+                tr += (double)xv[u] * (double)p;
+            }
+#pragma unroll
+            for (int t = 0; t < V; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, (double)pv[u][t], acc[t], 0, 0, 0);
         }
     }
-    double* o = part + (long long)blockIdx.x * (2 * HP * HP + 1);
+    if constexpr (S > 1) {
+        if (s > 0) {
 #pragma unroll
-    for (int u = 0; u < EPT; ++u) {
-        const int e = threadIdx.x + 1024 * u;
-        o[e] = gb[u];
-        o[HP * HP + e] = gd[u];
+            for (int t = 0; t < V; ++t) fold[(((s - 1) * 2 * V + task) * V + t) * 64 + lane] = acc[t];
+        }
+        __syncthreads();
+        if (s == 0) {
+            for (int s2 = 1; s2 < S; ++s2)
+#pragma unroll
+                for (int t = 0; t < V; ++t) acc[t] += fold[(((s2 - 1) * 2 * V + task) * V + t) * 64 + lane];
+        }
+    }
+    double* o = part + (long long)blockIdx.x * (2 * HP * HP + 1) + pi * HP * HP;
+    if (s == 0) {
+#pragma unroll
+        for (int t = 0; t < V; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[(((tw * V + t) * 4 + r) << 6) + lane] = acc[t][r];
     }
     tr = block_sum(tr, red);
-    if (threadIdx.x == 0) o[2 * HP * HP] = tr;
+    if (threadIdx.x == 0) part[(long long)blockIdx.x * (2 * HP * HP + 1) + 2 * HP * HP] = tr;
 }
 
-// the shares summed in a fixed order into st: GB = (W'P + P'W) / 2, GD likewise, GX[0] = sum A o P.  Workgroup: 16 entries x 16
-// chunk groups (group g sums chunks g, g + 16, ...; eight loads in flight), the 16 group sums then added in group order.
-constexpr int GRED_E = 16, GRED_G = 16;
-__global__ __launch_bounds__(256) void gram_part_reduce_kernel(const double* __restrict__ part, int nchunk, int Hp,
-                                                               double* __restrict__ st, StateLayout lay, const int* __restrict__ stop) {
+// the shares summed in a fixed order into st: GB[a][b] = (sum_c C_c[a][b] + sum_c C_c[b][a]) / 2 (every sum in chunk order, so GB is
+// exactly symmetric), GD likewise, GX[0] = sum A o P.  Workgroup: 64 share positions (register order) x 4 chunk groups (group g sums
+// chunks g, g + 4, ...; eight loads in flight), each position together with its transposed one; the group sums added in group order.
+constexpr int GRED_E = 64, GRED_G = 4;
+template <int HP>
+__global__ __launch_bounds__(256) void gram_part_reduce_kernel(const double* __restrict__ part, int nchunk, double* __restrict__ st,
+                                                               StateLayout lay, const int* __restrict__ stop) {
     if (*stop) return;
-    __shared__ double sum[GRED_G][GRED_E];
-    const int n2 = Hp * Hp;
-    const long long stride = 2LL * n2 + 1;
+    constexpr int V = GPart<HP>::V, n2 = HP * HP;
+    constexpr long long stride = 2LL * n2 + 1;
+    __shared__ double sum[2][GRED_G][GRED_E];
     const int el = threadIdx.x % GRED_E, g = threadIdx.x / GRED_E;
-    const int t = blockIdx.x * GRED_E + el;
-    double a = 0.0;
-    if (t <= 2 * n2) {
-        int c = g;
-        for (; c + 7 * GRED_G < nchunk; c += 8 * GRED_G) {
-            double v[8];
+    const int e = blockIdx.x * GRED_E + el;                       // < 2 n2 + GRED_E; e == 2 n2: the trace
+    // e = pi n2 + register-order index ((tw V + t) 4 + rq) 64 + 16 q + c  <->  C[a][b], a = V (q + 4 rq) + tw, b = V c + t
+    const int pi = e / n2, x = e % n2;
+    const int tw = (x >> 8) / V, t = (x >> 8) % V, rq = (x >> 6) & 3, q = (x >> 4) & 3, c = x & 15;
+    const int a = V * (q + 4 * rq) + tw, b = V * c + t;
+    const bool mat = e < 2 * n2, tro = e == 2 * n2;
+    const long long i0 = mat ? e : 2LL * n2, i1 = mat ? (long long)pi * n2 + gpart_index<HP>(b, a) : 2LL * n2;
+    double s0 = 0.0, s1 = 0.0;
+    if (mat || tro) {
+        int k = g;
+        for (; k + 7 * GRED_G < nchunk; k += 8 * GRED_G) {
+            double v0[8], v1[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = part[(long long)(c + k * GRED_G) * stride + t];
+            for (int u = 0; u < 8; ++u) { v0[u] = part[(k + u * GRED_G) * stride + i0]; v1[u] = part[(k + u * GRED_G) * stride + i1]; }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) a += v[k];
+            for (int u = 0; u < 8; ++u) { s0 += v0[u]; s1 += v1[u]; }
         }
-        for (; c < nchunk; c += GRED_G) a += part[(long long)c * stride + t];
+        for (; k < nchunk; k += GRED_G) { s0 += part[k * stride + i0]; s1 += part[k * stride + i1]; }
     }
-    sum[g][el] = a;
+    sum[0][g][el] = s0;
+    sum[1][g][el] = s1;
     __syncthreads();
-    if (g != 0 || t > 2 * n2) return;
-    double s = 0.0;
-    for (int k = 0; k < GRED_G; ++k) s += sum[k][el];
-    if (t == 2 * n2) st[lay.GX()] = s;
-    else st[(t < n2 ? lay.GB() : lay.GD()) + (t % n2)] = 0.5 * s;
+    if (g != 0 || !(mat || tro)) return;
+    double t0 = 0.0, t1 = 0.0;
+    for (int k = 0; k < GRED_G; ++k) { t0 += sum[0][k][el]; t1 += sum[1][k][el]; }
+    if (tro) st[lay.GX()] = t0;
+    else st[(pi ? lay.GD() : lay.GB()) + a * HP + b] = 0.5 * (t0 + t1);
 }
 
 }  // namespace vbmf

@@ -1016,8 +1016,9 @@ static int gram_prepare(vbmf_ctx* c) {
         c->g_sps = cdiv(KT, c->g_nsplit);
         c->g_nsplit = cdiv(KT, c->g_sps);
         const int64_t Mp1 = (int64_t)c->d1.XT * 32;
-        c->g_nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(256, cdiv(c->M, 32)));
-        c->g_rpc = (int)rup(cdiv(c->M, c->g_nchunk), GPART_ROWS);
+        // gram_part: 16 waves per chunk; 128 chunks (2 waves per SIMD) at Hp <= 64, 64 at Hp = 128, where a share is 4x larger
+        c->g_nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(c->Hp == 128 ? 64 : 128, cdiv(c->M, 64)));
+        c->g_rpc = (int)rup(cdiv(c->M, c->g_nchunk), 16);
         c->g_nchunk = cdiv(c->M, c->g_rpc);
         const size_t n = (size_t)c->Hp * Mp1;
         const size_t wrows = (size_t)32 * c->GT;
@@ -1075,8 +1076,10 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     const long long n = (long long)c->Hp * Mp1;
     const float* Wo = c->W32g[c->wcur];
     float* Wn = c->W32g[c->wcur ^ 1];
-    hipLaunchKernelGGL(gram_w_kernel, dim3(KT), dim3(256), 0, c->stream, c->A32, c->SB32,
-                       Wo, Wn, c->Wt, (long long)c->M, c->Hp, KT, stop);
+    const dim3 wg(cdiv(KT, GW_KS));
+    if (c->Hp == 32) hipLaunchKernelGGL((gram_w_kernel<32>), wg, dim3(128), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+    else if (c->Hp == 64) hipLaunchKernelGGL((gram_w_kernel<64>), wg, dim3(256), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+    else hipLaunchKernelGGL((gram_w_kernel<128>), wg, dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
     HIPCHK(c, hipGetLastError());
     float* out = c->g_nsplit > 1 ? c->gslabs : c->gPQ;
     const dim3 grid(c->g_nrg * c->g_nsplit);
@@ -1098,8 +1101,10 @@ static int gram_product(vbmf_ctx* c, bool partials) {
         else if (c->Hp == 64) hipLaunchKernelGGL((gram_part_kernel<64>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
         else hipLaunchKernelGGL((gram_part_kernel<128>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(gram_part_reduce_kernel, dim3(cdiv(2 * (int64_t)c->Hp * c->Hp + 1, GRED_E)), dim3(256), 0, c->stream, c->g_part,
-                           c->g_nchunk, c->Hp, c->st, c->lay, stop);
+        const dim3 rg(cdiv(2 * (int64_t)c->Hp * c->Hp + 1, GRED_E));
+        if (c->Hp == 32) hipLaunchKernelGGL((gram_part_reduce_kernel<32>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
+        else if (c->Hp == 64) hipLaunchKernelGGL((gram_part_reduce_kernel<64>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
+        else hipLaunchKernelGGL((gram_part_reduce_kernel<128>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
         HIPCHK(c, hipGetLastError());
     }
     return VBMF_OK;
@@ -2303,6 +2308,9 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
         case VBMF_PEEK_FB: base = c->FB; words = c->nFB * 4; break;
         case VBMF_PEEK_Y1: base = c->Y1; words = c->nY1 * 4; break;
         case VBMF_PEEK_Y2: base = c->Y2; words = c->nY2 * 4; break;
+        case VBMF_PEEK_STATE: base = c->st; words = (size_t)c->lay.total() * 2; break;
+        case VBMF_PEEK_GRAM_W: base = c->W32g[c->wcur]; words = c->W32g[c->wcur] ? (size_t)32 * c->GT * c->Hp : 0; break;
+        case VBMF_PEEK_GRAM_PQ: base = c->gPQ; words = c->gPQ ? (size_t)2 * c->Hp * c->d1.XT * 32 : 0; break;
         default: FAIL(c, VBMF_ERR_INVALID, "vbmf_debug_peek: unknown buffer");
     }
     if ((size_t)(word_offset + nwords) > words) FAIL(c, VBMF_ERR_INVALID, "vbmf_debug_peek: range exceeds buffer (%zu words)", words);
