@@ -287,7 +287,13 @@ __device__ __forceinline__ void ctrl_cov_dev(double* __restrict__ st, StateLayou
                                              float* __restrict__ S32, int* __restrict__ ints, double* lds,
                                              bool shadow = false) {
     __shared__ double red[16];
-    if (load_stop(ints)) return;
+    __shared__ int stop_s;
+    // Workgroup-uniform stop test: inside ctrl_chain the other part of the launch may raise the flag while this one starts, and
+    // waves that disagreed would leave the inverse's barriers unmatched.  (A bad pivot of a speculative SigmaA -- shadow -- still
+    // raises I_ERR even if the loop then stops before that SigmaA would be used; the streaming chain has always done the same.)
+    if (threadIdx.x == 0) stop_s = load_stop(ints);
+    __syncthreads();
+    if (stop_s) return;
     constexpr int NP = T * R;
     const int Hp = lay.Hp;
     const int tx = threadIdx.x % T, ty = threadIdx.x / T;
@@ -363,6 +369,26 @@ __global__ __launch_bounds__(256) void commit_cov_a_kernel(double* __restrict__ 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         st[lay.SA() + i] = st[lay.W0() + i];
     if (blockIdx.x == 0 && threadIdx.x == 0) st[lay.scal() + S_LOGDET_SA] = st[lay.scal() + S_LOGDET_SA_SHADOW];
+}
+// the same commit by one workgroup (CTRL_COMMIT_A of ctrl_chain), published to the rest of the workgroup by the barrier.
+// It sits ahead of SigmaB on the critical path, so a round's loads are all issued before its stores (src and dst may alias as far
+// as the compiler knows: one element per iteration would cost a memory latency each, 64 of them per thread at Hp = 128).
+__device__ __forceinline__ void commit_cov_a_dev(double* __restrict__ st, StateLayout lay, const int* __restrict__ ints) {
+    if (load_stop(ints)) return;                               // (no other workgroup writes the flag during this launch)
+    const double* src = st + lay.W0();
+    double* dst = st + lay.SA();
+    constexpr int U = 16;
+    const int n = (int)lay.n2(), nt = ctrl_nthreads();         // n = Hp * Hp, a multiple of 4 * 256
+    for (int i0 = threadIdx.x; i0 < n; i0 += U * nt) {
+        double v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = i0 + u * nt < n ? src[i0 + u * nt] : 0.0;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (i0 + u * nt < n) dst[i0 + u * nt] = v[u];
+    }
+    if (threadIdx.x == 0) st[lay.scal() + S_LOGDET_SA] = st[lay.scal() + S_LOGDET_SA_SHADOW];
+    __syncthreads();
 }
 
 template <int R, int T>
@@ -846,7 +872,9 @@ struct CtrlArgs {
 //   pass 2 of sweep j : SigmaB of sweep j  and  lambda_max(B_{j-1}'B_{j-1})  (the denominator of d_j; the
 //                       Gram of B_{j-1} is still in place: post(B) of sweep j runs after this launch)
 // so each pass carries a chain of similar length (~75 / ~65 us at H = 64).
-enum : int { CTRL_PREV_END = 1, CTRL_COV_A = 2, CTRL_COV_B = 4, CTRL_EIG_BOLD = 8 };
+// The Gram form has no pass launches: the same two parts run as a launch of their own (ctrl_chain_kernel),
+// and the commit of the SigmaA shadow rides in the SigmaB launch ahead of SigmaB (CTRL_COMMIT_A).
+enum : int { CTRL_PREV_END = 1, CTRL_COV_A = 2, CTRL_COV_B = 4, CTRL_EIG_BOLD = 8, CTRL_COMMIT_A = 16 };
 
 // d = ||B_old - B_new||_2 / ||B_old||_2 (src/util.jl:27-29) and the loop test (src/vbmf.jl:193) of sweep it_row
 __device__ __forceinline__ void ctrl_loop_dev(double* __restrict__ st, StateLayout lay, double eps,
@@ -883,6 +911,7 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
     if (part == 0) {
         if (a.mode & CTRL_PREV_END)
             ctrl_end_dev(a.st, a.lay, a.H, a.Lg, a.M, (a.end_flags & ~8) | 64, a.eps, a.trace, a.ints, a.it_row);
+        if (a.mode & CTRL_COMMIT_A) commit_cov_a_dev(a.st, a.lay, a.ints);
         const unsigned long long t1 = wall_clock64();
         if (a.mode & CTRL_COV_A)
             ctrl_cov_dev<R, 16>(a.st, a.lay, a.H, 0, a.Lg, a.S32, a.ints, reinterpret_cast<double*>(lds), true);
@@ -907,6 +936,13 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
         if (a.mode & CTRL_EIG_BOLD)
             eig_dev<R>(a.st, a.lay, a.H, a.spectral, 1, a.ints, reinterpret_cast<float*>(lds), S_LAMB_PREV);
     }
+}
+
+// the chain as a launch of its own: two workgroups of 256 threads, dynamic LDS as for the pass launches' control workgroups
+template <int R>
+__global__ __launch_bounds__(256) void ctrl_chain_kernel(CtrlArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_chain[];
+    ctrl_chain<R>(a, lds_chain, blockIdx.x);
 }
 
 // ---- vbls! as H x H algebra (examples/mil_util.jl:179-203, vbmf_parameters branch, no label mask) ----------------------------

@@ -366,14 +366,14 @@ static int spectral_arg(const vbmf_ctx* c) {
 }
 static bool use_lds8(const vbmf_ctx* c) { return c->lds8 && c->NH >= 4 && c->mode == MODE_BF16X2; }
 
-static size_t ctrl_lds_bytes(int NH) {
-    const int R = NH <= 4 ? 2 * NH : 0;
-    if (R == 0) return 0;
+// dynamic LDS of the control chain's workgroups at R = NP / 16 (pass launches: R = 2 NH; ctrl_chain_kernel: R of the stand-alone kernels)
+static size_t ctrl_lds_bytes_r(int R) {
     const size_t NP = 16 * (size_t)R;
     // lambda_max (Lanczos vector + tridiagonal: EIG_LDS_BYTES) | the blocked inverse's NP x (NP + 2) fp64 image (ctrl_kernels.hpp)
     const size_t eig = std::max(R <= 4 ? (size_t)2 * NP * (NP + 4) * sizeof(float) : (size_t)0, (size_t)EIG_LDS_BYTES);      // squaring | Lanczos
     return std::max(eig, spd_inverse_lds_bytes(R));
 }
+static size_t ctrl_lds_bytes(int NH) { return NH <= 4 ? ctrl_lds_bytes_r(2 * NH) : 0; }
 static bool fused_ctrl(const vbmf_ctx* c) { return c->in_run && c->NH <= 4; }
 
 // ctrl_mode != 0: workgroup 0 of the launch runs that part of the control chain (CtrlArgs)
@@ -1110,28 +1110,48 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     return VBMF_OK;
 }
 
-// the end of a sweep in the Gram form: lambda_max of dB'dB and of the new B'B, then CA, CB, sigma2, ELBO, d and the loop test
-static int gram_sweep_end(vbmf_ctx* c) {
-    TRY(launch_eig(c, 1, 1));
-    TRY(launch_ctrl_end(c, c->run_flags, c->run_eps, c->run_trace));
-    ++c->ends_enqueued;
+// the control chain as a launch of its own (ctrl_chain_kernel: two workgroups, the parts of ctrl_chain).  R follows H as for the
+// stand-alone control kernels, so every fp64 operation sees the inputs, the work split and the summation order it saw there.
+template <int R>
+static void launch_chain_t(vbmf_ctx* c, const CtrlArgs& ca) {
+    hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(2), dim3(256), ctrl_lds_bytes_r(R), c->stream, ca);
+}
+static int launch_chain(vbmf_ctx* c, int mode, float* S32) {
+    CtrlArgs ca{};
+    ca.st = c->st; ca.lay = c->lay; ca.ints = c->ints; ca.trace = c->run_trace;
+    ca.S32 = S32;
+    ca.Lg = (double)c->Lg; ca.M = (double)c->M; ca.eps = c->run_eps;
+    ca.H = (int)c->H; ca.spectral = spectral_arg(c);
+    ca.end_flags = c->run_flags; ca.mode = mode; ca.it_row = (int)c->ends_enqueued;
+    const int H = (int)c->H;
+    if (H <= 16) launch_chain_t<1>(c, ca);
+    else if (H <= 32) launch_chain_t<2>(c, ca);
+    else if (H <= 64) launch_chain_t<4>(c, ca);
+    else if (H <= 128) launch_chain_t<8>(c, ca);
+    else FAIL(c, VBMF_ERR_INVALID, "internal: the stand-alone control chain covers H <= 128");
+    HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
 
-// one sweep from P = Y'B_old = G W_old (in gPQ) and the state's B'B: SigmaA, A (label mask) and A'A, SigmaB, then W, the product
-// and the closing control step.  The control kernels are the stand-alone forms of the ones that ride in the pass launches.
+// one sweep from P = Y'B_old = G W_old (in gPQ) and the state's B'B: SigmaA, A (label mask) and A'A, SigmaB, then W and the product.
+// The H x H chain runs in two launches of ctrl_chain_kernel, split as in the pass launches of the streaming sweep:
+//   L1  part 0: [ctrl_end of the previous sweep] -> SigmaA (speculative, into the shadow)  |  part 1: [lambda_max(dB'dB) -> d, stop]
+//   L2  part 0: commit of the shadow -> SigmaB                                              |  part 1: lambda_max(B_old'B_old)
+// so the lambda_max solves leave the critical path.  L2 part 1 reads GB before gram_part_reduce overwrites it (kernel boundary).
+// This sweep's closing step rides in the next sweep's L1, or is the run's stand-alone tail (vbmf_run).
 static int gram_sweep(vbmf_ctx* c) {
-    TRY(launch_ctrl_cov(c, 0));
+    TRY(launch_chain(c, CTRL_COV_A | (c->tail_pending ? CTRL_PREV_END : 0), c->SA32));
+    if (c->tail_pending) ++c->ends_enqueued;
+    c->tail_pending = false;
     c->P_frag = true;
     if (fused_gram(c)) TRY(launch_post_gram(c, 0, c->gPQ));
     else {
         TRY(launch_post_frag(c, 0, c->gPQ));
         TRY(launch_gram(c, 0, c->A32, nullptr, true));
     }
-    TRY(launch_ctrl_cov(c, 1));
+    TRY(launch_chain(c, CTRL_COMMIT_A | CTRL_COV_B | CTRL_EIG_BOLD, c->SB32));
     TRY(gram_product(c, true));
     c->wcur ^= 1;
-    TRY(gram_sweep_end(c));
     c->gA_valid = c->gB_valid = true;
     c->P_valid = false;
     c->tr_valid = true;
@@ -1502,6 +1522,7 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         hipError_t e = hipFuncSetAttribute((const void*)eig_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
         // 64 < H <= 128: the blocked inverse keeps the 128 x 130 fp64 image in LDS (133 KB)
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ctrl_cov_kernel<8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ctrl_chain_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_cov_b_kernel<8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
         // 128 < H <= 256: the register-resident blocked sweep's two panel strips (70 KB: above the 64 KB a launch may ask for unannounced)
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ctrl_cov_kernel<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
@@ -2059,7 +2080,7 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     bool pending[2] = {false, false};
     while (rc == VBMF_OK && it < niter && !stopped) {
         if (gram && c->W_valid) {
-            rc = gram_sweep(c);              // the whole sweep, its closing control step included
+            rc = gram_sweep(c);              // carries the closing control step of the previous sweep
             ++it;
         } else {
             rc = do_update_A(c);             // carries lambda_max + ctrl_end of the previous sweep when fused
@@ -2071,13 +2092,12 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
                 rc = gram_product(c, false);
                 c->wcur ^= 1;
                 c->W_valid = true;
-                if (rc == VBMF_OK) rc = gram_sweep_end(c);
             }
         }
         const bool last = (it == niter);
-        if (rc == VBMF_OK && !gram) {
+        if (rc == VBMF_OK) {                 // (the Gram form is always fused: Hp <= 128)
             if (fused_ctrl(c) && !last) {
-                c->tail_pending = true;      // rides in the next sweep's pass-1 launch
+                c->tail_pending = true;      // rides in the next sweep's pass-1 launch (Gram form: its first chain launch)
             } else if (fused_ctrl(c)) {
                 rc = launch_eig(c, 1, 0);
                 if (rc == VBMF_OK) rc = launch_ctrl_end(c, flags | 32, eps, trace_dev);
