@@ -185,6 +185,19 @@ int vbmf_sparse_set_noise_rows(vbmf_ctx* ctx, const double* sigmaVecHat, const d
 int vbmf_sparse_get_noise_rows(vbmf_ctx* ctx, double* sigmaVecHat, double* zetaVec);
 /* vbls! on the sparse model (examples/mil_util.jl:187-190): niter x (updateA!, updateCA!, updateSigma!), B frozen */
 int vbmf_sparse_run_fixed_basis(vbmf_ctx* ctx, int64_t niter);
+/* vbls! on the sparse models over many bags with one fixed basis (examples/mil_util.jl:187-197 in one call), the diagonal or
+ * (full_cov != 0) the full_cov form of updateA!.  Context: VBMF_VARIANT_SPARSE_DIAG, _DUAL_DIAG or _TRIAL_DIAG whose Y is the bags side
+ * by side (col_off as in vbmf_run_fixed_basis_batched); BHat, SigmaB from vbmf_sparse_set_state; no label mask; H <= 64; one rank;
+ * niter >= 1.  Per bag: alpha[nbags*H], beta0[nbags*H] (updateCA!'s alpha_h and beta0_h: the three families differ only there),
+ * eta[nbags] (eta0 + L*M_b/2), zeta0[nbags].  In/out: sigmaHat[nbags], CA[M*H] in vec(A') order (start values in, final values out).
+ * Out: zeta[nbags], beta[M*H], diagSigmaATVec[M*H], SigmaA[nbags*H*H], ATVecHat[M*H]; each may be NULL (not copied).  The QS1 layout
+ * (VBMF_COMPAT_SPARSE_REPEAT) follows each bag's own M_b; a 1-column bag is valid.  The context's state is not changed.  Any other
+ * input returns VBMF_ERR_INVALID before a launch; a non-positive or non-finite pivot, or a non-finite precision, in any bag
+ * VBMF_ERR_NUMERIC. */
+int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t niter, int full_cov,
+                                        const double* alpha, const double* beta0, const double* eta, const double* zeta0,
+                                        double* sigmaHat, double* CA, double* zeta, double* beta, double* diagSigmaATVec,
+                                        double* SigmaA, double* ATVecHat);
 int vbmf_sparse_step(vbmf_ctx* ctx, int which);            /* reference order A, B, CA, CB, SIGMA (:369-376) */
 /* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0) */
 int vbmf_sparse_run(vbmf_ctx* ctx, int64_t niter, double eps, int est_cb, int64_t* iters_done, double* d_last,

@@ -45,7 +45,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "dual_updateB_", "dual_updateCA_", "dual_updateCB_", "dual_updateSigma_", "dual_updateCA_and_priors_",
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
-           "vbls_batch_", "Bags"]
+           "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
 # elements the field is left None and computed on demand with updateYHat_ (8 GB at 100k x 10k).
@@ -1150,21 +1150,21 @@ def _batch_refuse(why):
     raise ValueError(f"vbls_batch_: {why}; run such bags one at a time with vbls_")
 
 
-def _batch_shapes(Ys, H):
+def _batch_shapes(Ys, H, refuse=_batch_refuse):
     """(L, [M_b]) of a list of bags, checked on the host: matrices, one L, H <= 64."""
     if int(H) > _BATCH_MAX_H:
-        _batch_refuse(f"H = {int(H)} > {_BATCH_MAX_H}")
+        refuse(f"H = {int(H)} > {_BATCH_MAX_H}")
     if len(Ys) == 0:
-        _batch_refuse("no bags")
+        refuse("no bags")
     Ls, Ms = [], []
     for Y in Ys:
         shape = np.shape(Y)
         if len(shape) != 2 or shape[1] < 1:
-            _batch_refuse(f"every bag must be a matrix with at least one column (got shape {shape})")
+            refuse(f"every bag must be a matrix with at least one column (got shape {shape})")
         Ls.append(int(shape[0]))
         Ms.append(int(shape[1]))
     if len(set(Ls)) != 1:
-        _batch_refuse(f"the bags have different row counts L {sorted(set(Ls))}")
+        refuse(f"the bags have different row counts L {sorted(set(Ls))}")
     return Ls[0], Ms
 
 
@@ -1239,6 +1239,138 @@ def vbls_batch_(Ys, params, niter):
         p.CA[idx, idx] = ca                                          # in place (src/vbmf.jl:131)
         p.invCA = np.diag(1.0 / ca)
         p.sigma2 = float(r["sigma2"][b])
+        p.YHat = p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None     # :201
+        out.append(p.AHat)
+    return out
+
+
+def _sbatch_refuse(why):
+    raise ValueError(f"vbls_sparse_batch_: {why}; run such bags one at a time with vbls_")
+
+
+class SparseBags:
+    """Many bags (L x M_b matrices with one L) uploaded side by side as ONE L x sum(M_b) matrix into a sparse-variant context, for
+    vbls_sparse_batch_.  One upload serves several bases (examples/mil_util.jl:469-521 runs every bag against two trained models).
+    ctx_kw: Context options over the package defaults (e.g. reference_compat)."""
+
+    def __init__(self, Ys, H, **ctx_kw):
+        self.L, self.Ms = _batch_shapes(Ys, H, _sbatch_refuse)
+        self.H = int(H)
+        self.col_off = np.concatenate([[0], np.cumsum(self.Ms)]).astype(np.int64)
+        self.M = int(self.col_off[-1])
+        Yall = np.empty((self.L, self.M), order="F")
+        for Y, c0, c1 in zip(Ys, self.col_off[:-1], self.col_off[1:]):
+            Yall[:, c0:c1] = Y
+        self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **{**_defaults, **ctx_kw})
+        self.ctx.set_Y(Yall)
+
+    def __len__(self):
+        return len(self.Ms)
+
+    def close(self):
+        self.ctx.close()
+
+
+_SBATCH_TYPES = (vbmf_sparse_parameters, vbmf_dual_parameters, vbmf_trial_parameters)
+
+
+def _sbatch_check_params(L, Ms, H, params):
+    if len(params) != len(Ms):
+        _sbatch_refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
+    p0 = params[0]
+    kind = type(p0)
+    if kind not in _SBATCH_TYPES:
+        _sbatch_refuse(f"{kind.__name__} (vbmf_sparse_parameters, vbmf_dual_parameters or vbmf_trial_parameters only)")
+    for b, (p, M) in enumerate(zip(params, Ms)):
+        if type(p) is not kind:
+            _sbatch_refuse(f"bag {b}: {type(p).__name__} beside {kind.__name__} (one model type per call)")
+        if int(p.H) != H:
+            _sbatch_refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
+        if p.L != L or p.M != M:
+            _sbatch_refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
+        if kind is vbmf_sparse_parameters and (int(p.H1) > 0 or np.asarray(p.labels).size > 0):
+            _sbatch_refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
+        if kind is vbmf_trial_parameters and int(p.M0) != M:
+            _sbatch_refuse(f"bag {b}: trial set with M0 = {p.M0} != M = {M} (copy_vbmf_params gives M0 = M)")
+        if np.size(p.CA) != M * H:
+            _sbatch_refuse(f"bag {b}: CA has {np.size(p.CA)} entries, not M H = {M * H}")
+        if p is not p0 and not (np.array_equal(p.BHat, p0.BHat) and np.array_equal(p.SigmaB, p0.SigmaB)):
+            _sbatch_refuse(f"bag {b} does not share BHat and SigmaB with bag 0 (one fixed basis per call)")
+        _check_derived(p)
+        if kind is vbmf_sparse_parameters and np.isscalar(p.alpha) and p.alpha != 0.0 and abs(p.alpha - (p.alpha0 + 0.5)) > 1e-12:
+            _sbatch_refuse(f"bag {b}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
+
+
+def _sbatch_priors(p, H):
+    """updateCA!'s per-column (alpha_h, beta0_h) of one parameter set (src/vbmf_sparse.jl:284-288, src/vbmf_dual.jl:322-351,
+    src/vbmf_trial.jl:357-400 with M0 = M: its third group is empty)."""
+    if isinstance(p, vbmf_dual_parameters):
+        g0, (a0, b0), (a1, b1) = p.H0, (p.alpha00, p.beta00), (p.alpha01, p.beta01)
+    elif isinstance(p, vbmf_trial_parameters):
+        g0, (a0, b0), (a1, b1) = p.H0, (p.alpha01, p.beta01), (p.alpha02, p.beta02)
+    else:
+        g0, (a0, b0), (a1, b1) = H, (p.alpha0, p.beta0), (p.alpha0, p.beta0)
+    h = np.arange(H)
+    return np.where(h < g0, a0, a1) + 0.5, np.where(h < g0, b0, b1).astype(np.float64)
+
+
+def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
+    """vbls! of the sparse models over many bags with one fixed basis in one device call: does what
+    [vbls_(Y, p, niter, full_cov=full_cov) for Y, p in zip(Ys, params)] does (examples/mil_util.jl:187-197; the MIL classifiers of
+    :393-416, :469-479, :497-521) -- fills on every p the fields per-bag vbls_ fills and returns the list of AHat.
+    Ys: a list of L x M_b arrays, or a SparseBags holding them on the device.  params: one vbmf_sparse_parameters,
+    vbmf_dual_parameters or vbmf_trial_parameters (with M0 = M_b, what copy_vbmf_params returns) per bag, all of one type, with
+    the same BHat and SigmaB, no labels, H <= 64.  Every bag runs all niter iterations in one workgroup of one launch
+    (include/vbmf_hip.h, vbmf_sparse_run_fixed_basis_batched)."""
+    params = list(params)
+    H = int(params[0].H) if params else 0
+    if H > _BATCH_MAX_H:
+        _sbatch_refuse(f"H = {H} > {_BATCH_MAX_H}")
+    if isinstance(Ys, SparseBags):
+        bags = Ys
+        if bags.H != H:
+            _sbatch_refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
+        _sbatch_check_params(bags.L, bags.Ms, H, params)
+    else:
+        L, Ms = _batch_shapes(Ys, H, _sbatch_refuse)
+        _sbatch_check_params(L, Ms, H, params)
+        bags = SparseBags(Ys, H)
+    try:
+        p0 = params[0]
+        nb = len(params)
+        ctx = bags.ctx
+        zero = np.zeros(bags.M * H)
+        hyper = dict(alpha0=1e-10, beta0=1e-10, gamma0=p0.gamma0, delta0=p0.delta0, eta0=p0.eta0, zeta0=p0.zeta0)
+        ctx.sparse_set_state(zero, zero + 1.0, zero + 1.0, zero + 1.0, p0.BHat, p0.SigmaB, np.ones(H), np.ones(H), 1.0, 0.0, hyper)
+        pri = [_sbatch_priors(p, H) for p in params]
+        r = ctx.sparse_run_fixed_basis_batched(bags.col_off, int(niter), np.array([a for a, _ in pri]), np.array([b for _, b in pri]),
+                                               [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
+                                               [p.sigmaHat for p in params], np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1)
+                                                                                              for p in params]), full_cov=full_cov)
+    finally:
+        if not isinstance(Ys, SparseBags):
+            bags.close()
+    out = []
+    for b, p in enumerate(params):
+        s0, s1 = bags.col_off[b] * H, bags.col_off[b + 1] * H
+        M = p.M
+        p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
+        p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
+        p.AHat = p.ATVecHat.reshape(M, H).copy()
+        p.SigmaA = r["SigmaA"][b].copy()
+        p.sigmaHat, p.zeta = float(r["sigmaHat"][b]), float(r["zeta"][b])
+        if isinstance(p, vbmf_dual_parameters):                         # _dpull, _dpull_priors
+            p.A0Hat, p.A1Hat = p.AHat[:, :p.H0].copy(), p.AHat[:, p.H0:].copy()
+            p.CA0, p.CA1 = _dual_split(p.CA, M, H, p.H0)
+            p.beta0, p.beta1 = _dual_split(p.beta, M, H, p.H0)
+            p.alpha0, p.alpha1 = p.alpha00 + 0.5, p.alpha01 + 0.5        # src/vbmf_dual.jl:324-325
+            p.alpha = np.array([p.alpha0, p.alpha1])
+        elif isinstance(p, vbmf_trial_parameters):                      # _tpull
+            p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, :p.H0].copy(), p.AHat[:p.M0, p.H0:].copy(), p.AHat[p.M0:, p.H0:].copy()
+            p.CA1, p.CA2, p.CA3 = _trial_split(p.CA, M, H, p.H0, p.M0)
+            p.beta1, p.beta2, p.beta3 = _trial_split(p.beta, M, H, p.H0, p.M0)
+            p.alpha1, p.alpha2, p.alpha3 = p.alpha01 + 0.5, p.alpha02 + 0.5, p.alpha03 + 0.5   # src/vbmf_trial.jl:359-361
+            p.alpha = np.array([p.alpha1, p.alpha2, p.alpha3])
         p.YHat = p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None     # :201
         out.append(p.AHat)
     return out

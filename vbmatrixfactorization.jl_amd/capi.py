@@ -33,6 +33,7 @@ SYMBOLS = [
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
+    "vbmf_sparse_run_fixed_basis_batched",
     "vbmf_sparse_lower_bound", "vbmf_sparse_set_noise_rows", "vbmf_sparse_get_noise_rows", "vbmf_preprocess_open", "vbmf_preprocess_rows", "vbmf_set_Y_preprocessed",
     "vbmf_preprocess_close", "vbmf_dual_set_priors", "vbmf_dual_get_priors", "vbmf_dual_run",
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
@@ -109,6 +110,7 @@ def lib():
     L.vbmf_run_fixed_basis.argtypes = [vp, i64]
     L.vbmf_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, dp, dp, dp, dp, i64]
     L.vbmf_sparse_run_fixed_basis.argtypes = [vp, i64]
+    L.vbmf_sparse_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
     L.vbmf_elbo.argtypes = [vp, dp]
     L.vbmf_comm_unique_id.argtypes = [vp]
@@ -330,6 +332,32 @@ class Context:
 
     def sparse_run_fixed_basis(self, niter):
         self._chk(self._lib.vbmf_sparse_run_fixed_basis(self._h, int(niter)))
+
+    def sparse_run_fixed_basis_batched(self, col_off, niter, alpha, beta0, eta, zeta0, sigmaHat, CA, full_cov=False):
+        """vbls! of the sparse models over the bags side by side in this context's Y (vbmf_sparse_run_fixed_basis_batched): bag b =
+        columns col_off[b] .. col_off[b+1]-1; B, SigmaB from sparse_set_state; per bag alpha, beta0 (nbags, H), eta, zeta0 and the start
+        value sigmaHat (nbags,); CA (M*H,) the start values in vec(A') order.  Returns dict(sigmaHat, zeta (nbags,), CA, beta,
+        diagSigmaATVec, ATVecHat (M*H,), SigmaA (nbags, H, H)).  The state is not changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        al = np.array(alpha, dtype=np.float64, copy=True, order="C")
+        b0 = np.array(beta0, dtype=np.float64, copy=True, order="C")
+        et = np.array(eta, dtype=np.float64, copy=True).reshape(-1)
+        z0 = np.array(zeta0, dtype=np.float64, copy=True).reshape(-1)
+        sg = np.array(sigmaHat, dtype=np.float64, copy=True).reshape(-1)
+        ca = np.array(CA, dtype=np.float64, copy=True).reshape(-1)
+        if (nb < 1 or al.shape != (nb, self.H) or b0.shape != (nb, self.H) or et.shape != (nb,) or z0.shape != (nb,)
+                or sg.shape != (nb,) or ca.shape != (self.M * self.H,)):
+            raise ValueError(f"col_off describes {nb} bags: alpha, beta0 must be ({nb}, {self.H}), eta, zeta0, sigmaHat ({nb},) "
+                             f"and CA ({self.M * self.H},)")
+        MH = self.M * self.H
+        zeta, beta, dS, A = np.empty(nb), np.empty(MH), np.empty(MH), np.empty(MH)
+        SA = np.empty((nb, self.H, self.H))
+        self._chk(self._lib.vbmf_sparse_run_fixed_basis_batched(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), int(niter),
+                                                                int(bool(full_cov)), _dptr(al), _dptr(b0), _dptr(et), _dptr(z0),
+                                                                _dptr(sg), _dptr(ca), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA),
+                                                                _dptr(A)))
+        return dict(sigmaHat=sg, zeta=zeta, CA=ca, beta=beta, diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA)
 
     def YHat(self):
         out = np.empty((self.L, self.M), order="F")

@@ -2,7 +2,7 @@
 //
 // The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.  One pass 1 with the frozen B forms
 // P = Y'B for all of them; then
-//   bag_gram_kernel   S_b = P_b'P_b (fp64 accumulate) and ||Y_b||^2 of Y as stored, one workgroup per bag
+//   bag_gram_kernel   S_b = P_b'P_b (fp64 accumulate; S = nullptr: not formed) and ||Y_b||^2 of Y as stored, one workgroup per bag
 //   vbls_batch_kernel the niter iterations, one workgroup per bag (ctrl_kernels.hpp)
 //   bag_a_kernel      A_b = P_b T_b with T_b = SigmaA_b / sigma2_b of the bag's last updateA!, row by row (fp64 out)
 // Bags do not align with the 32-column tiles of P or Y: every access goes through the column index.
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void bag_gram_kernel(const float* __restrict__
     double acc[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) acc[k] = 0.0;
-    for (long long c0 = m0; c0 < m1; c0 += CH) {
+    for (long long c0 = m0; S != nullptr && c0 < m1; c0 += CH) {         // (S = nullptr: ||Y_b||^2 only)
         const int nc = (int)(m1 - c0 < CH ? m1 - c0 : CH);
         for (int t = threadIdx.x; t < nc * H; t += 256) {
             const int h = t / nc, cc = t % nc;
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void bag_gram_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
         const int t = threadIdx.x + 256 * k;
-        if (t < nent) S[(long long)b * nent + t] = acc[k];
+        if (S != nullptr && t < nent) S[(long long)b * nent + t] = acc[k];
     }
     // ||Y_b||^2 from the pass-2 tiles (the layout untile_y_kernel reads), the quantity vbmf_get_trYY reports for a whole matrix
     double ys = 0.0;

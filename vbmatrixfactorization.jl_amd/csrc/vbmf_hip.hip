@@ -44,6 +44,7 @@
 #include "tile_kernels.hpp"
 #include "prep_kernels.hpp"
 #include "batch_kernels.hpp"
+#include "sparse_batch_kernels.hpp"
 #include "gram_kernels.hpp"
 
 using namespace vbmf;
@@ -161,6 +162,8 @@ struct vbmf_ctx {
     int lds_limit = 65536;
     double* bat = nullptr;            // vbmf_run_fixed_basis_batched: per-bag inputs / outputs and the fp64 A (grown on demand)
     size_t bat_bytes = 0;
+    double* sbat = nullptr;           // vbmf_sparse_run_fixed_basis_batched: the same for the sparse models (grown on demand)
+    size_t sbat_bytes = 0;
     // Gram-form sweep of vbmf_run (gram_kernels.hpp); buffers allocated by the first run that takes it
     int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows
     int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
@@ -1283,7 +1286,7 @@ int vbmf_destroy(vbmf_ctx* c) {
     void* bufs[] = {c->sk_list, c->sk_tail, c->gw, c->hmean, c->fws, c->t2part, c->Y1, c->Y2, c->FA_alloc, c->FB_alloc, c->FD, c->SBf, c->P, c->Q, c->Pred, c->A32, c->B32[0], c->B32[1], c->SA32,
                     c->SB32, c->gslab, c->st, c->gtmp, c->ypart, c->trpart, c->ints, c->mask, c->dS32, c->CA32, c->beta32, c->vtab,
                     c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bat, c->Gt, c->W32g[0], c->W32g[1], c->Wt, c->gslabs, c->gPQ,
-                    c->g_part, c->gsave};
+                    c->g_part, c->gsave, c->sbat};
     for (void* b : bufs) if (b) hipFree(b);
     if (c->ints_host) hipHostFree(c->ints_host);
     if (c->scal_host) hipHostFree(c->scal_host);
@@ -1538,6 +1541,8 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         // vbls! as H x H algebra at 32 < H <= 64: four 64 x 66 fp64 images (135 KB)
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_loop_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_batch_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
+        // batched vbls! of the sparse models, full_cov at 32 < H <= 64: four 64 x 66 fp64 images and the bag's state
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_batch_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SBATCH_LDS_BIG);
         if (e == hipSuccess && c->NH == 4)
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
         if (e == hipSuccess && c->NH == 4)
@@ -2853,6 +2858,118 @@ int vbmf_sparse_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
         TRY(launch_sparse_ctrl_end(c, 4 | f, 0.0, nullptr));
         if ((it & 63) == 63) TRY(check_device_err(c));
     }
+    return check_device_err(c);
+}
+
+// vbls! of the sparse models over many bags with one fixed basis (examples/mil_util.jl:187-197 in one call, both updateA! forms).
+// The context's Y holds the bags side by side; B, SigmaB come from the state, every other input and output is per bag and lives in
+// c->sbat -- the state itself (A, CA, beta, SigmaA, sigma, zeta) is not touched, so one upload serves another basis.
+int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, int full_cov,
+                                        const double* alpha, const double* beta0, const double* eta, const double* zeta0,
+                                        double* sigmaHat, double* CA, double* zeta, double* beta, double* diagSigmaATVec,
+                                        double* SigmaA, double* ATVecHat) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_run_fixed_basis_batched";
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse models only; use vbmf_run_fixed_basis_batched)", fn);
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run_fixed_basis per bag)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run_fixed_basis per bag)", fn);
+    if (c->H > 64) FAIL(c, VBMF_ERR_INVALID, "%s: H = %lld > 64", fn, (long long)c->H);
+    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "%s: row-sharded context (one rank only)", fn);
+    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "%s: bad nbags / col_off", fn);
+    if (col_off[0] != 0 || col_off[nbags] != c->M) FAIL(c, VBMF_ERR_INVALID, "%s: col_off must run from 0 to M = %lld", fn, (long long)c->M);
+    int64_t Mmax = 0;
+    for (int64_t b = 0; b < nbags; ++b) {
+        if (col_off[b + 1] <= col_off[b]) FAIL(c, VBMF_ERR_INVALID, "%s: bag %lld is empty or col_off decreases", fn, (long long)b);
+        Mmax = std::max<int64_t>(Mmax, col_off[b + 1] - col_off[b]);
+    }
+    if (!alpha || !beta0 || !eta || !zeta0 || !sigmaHat || !CA) FAIL(c, VBMF_ERR_INVALID, "%s: null alpha / beta0 / eta / zeta0 / sigmaHat / CA", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    TRY(ensure_gram_B(c));
+    const int H = (int)c->H;
+    const int64_t nb = nbags, MH = (int64_t)c->M * H, h2 = (int64_t)H * H;
+    // c->sbat: [col_off nb + 1 | alpha nb H | beta0 nb H | eta | zeta0 | sigma | zeta | ||Y_b||^2 (nb each) | CA | A | dS | beta | P (M H each)
+    //           | SigmaA nb H^2 | G H^2 | diag(B'B) H | L diag(SigmaB) H]
+    const int64_t o_al = nb + 1, o_b0 = o_al + nb * H, o_eta = o_b0 + nb * H, o_z0 = o_eta + nb, o_sig = o_z0 + nb, o_zeta = o_sig + nb,
+                  o_yy = o_zeta + nb, o_ca = o_yy + nb, o_a = o_ca + MH, o_ds = o_a + MH, o_be = o_ds + MH, o_p = o_be + MH,
+                  o_sa = o_p + MH, o_g = o_sa + nb * h2, o_gd = o_g + h2, o_sd = o_gd + H, total = o_sd + H;
+    if ((size_t)total * 8 > c->sbat_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->sbat) HIPCHK(c, hipFree(c->sbat));
+        c->sbat = nullptr;
+        c->sbat_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&c->sbat, (size_t)total * 8));
+        c->sbat_bytes = (size_t)total * 8;
+    }
+    double* d = c->sbat;
+    long long* d_off = reinterpret_cast<long long*>(d);
+    std::vector<double> in((size_t)(o_zeta - o_al));
+    memcpy(in.data(), alpha, (size_t)nb * H * 8);
+    memcpy(in.data() + (o_b0 - o_al), beta0, (size_t)nb * H * 8);
+    memcpy(in.data() + (o_eta - o_al), eta, (size_t)nb * 8);
+    memcpy(in.data() + (o_z0 - o_al), zeta0, (size_t)nb * 8);
+    memcpy(in.data() + (o_sig - o_al), sigmaHat, (size_t)nb * 8);
+    // a finished vbmf_sparse_run leaves the stop flag raised, and the pass and slab kernels are gated by it: lowered for this call and
+    // raised again after it
+    int ints0[4];
+    HIPCHK(c, memcpy_sync(c, ints0, c->ints, sizeof ints0, hipMemcpyDeviceToHost));
+    if (ints0[I_STOP]) HIPCHK(c, hipMemsetAsync(c->ints + I_STOP, 0, sizeof(int), c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off, col_off, (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_al, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    // P = Y'B of every bag in the plain [h][m] layout: one pass 1 with the frozen B (no A update: the state stays as it is)
+    const int* stop = c->ints + I_STOP;
+    c->P_frag = false;
+    TRY(launch_stream(c, 0));
+    const long long np = (long long)c->Hp * c->d1.XT * 32;
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(np / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, np, c->Pred, np, stop,
+                       SideCopy{});
+    c->P_valid = false;
+    const long long ldP = (long long)c->d1.XT * 32;
+    if (c->mode == MODE_F32)
+        hipLaunchKernelGGL((bag_gram_kernel<MODE_F32>), dim3((unsigned)nb), dim3(256), 0, c->stream, c->Pred, ldP, 0, c->Y2, c->d2.KS,
+                           (long long)c->L, d_off, H, (double*)nullptr, d + o_yy);
+    else
+        hipLaunchKernelGGL((bag_gram_kernel<MODE_BF16>), dim3((unsigned)nb), dim3(256), 0, c->stream, c->Pred, ldP, 0, c->Y2, c->d2.KS,
+                           (long long)c->L, d_off, H, (double*)nullptr, d + o_yy);
+    hipLaunchKernelGGL(sbatch_g_kernel, dim3(cdiv(h2, 256)), dim3(256), 0, c->stream, c->st, c->lay, H, (double)c->Lg, d + o_g, d + o_gd,
+                       d + o_sd);
+    HIPCHK(c, hipGetLastError());
+    // the bag's state in LDS up to the launch's budget (every bag of an MIL study fits), else in its slices of c->sbat
+    const int NBK = H <= 16 ? 1 : (H <= 32 ? 2 : 4);
+    const size_t cap = (full_cov && NBK == 4) ? SBATCH_LDS_BIG : SBATCH_LDS_SMALL;
+    const int nfix = sbatch_fixed_doubles(full_cov != 0, NBK, H);
+    const int64_t room = (int64_t)(cap / 8) - nfix;
+    const int lds_state = (int)std::max<int64_t>(0, std::min<int64_t>(4 * Mmax * H, room));
+    const size_t lds = (size_t)(nfix + lds_state) * 8;
+    SbatchArgs a{c->Pred, ldP, d_off, H, (int)niter, (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) ? 1 : 0, lds_state, (double)c->Lg,
+                 d + o_g, d + o_gd, d + o_sd, d + o_al, d + o_b0, d + o_eta, d + o_z0, d + o_yy, d + o_sig, d + o_zeta,
+                 d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_p, d + o_sa, c->ints + I_ERR};
+#define SBATCH(NBc_, FULLc_) hipLaunchKernelGGL((sparse_batch_kernel<NBc_, FULLc_>), dim3((unsigned)nb), dim3(SBATCH_THREADS), lds, c->stream, a)
+    if (full_cov) {
+        if (NBK == 1) SBATCH(1, true);
+        else if (NBK == 2) SBATCH(2, true);
+        else SBATCH(4, true);
+    } else {
+        if (NBK == 1) SBATCH(1, false);
+        else if (NBK == 2) SBATCH(2, false);
+        else SBATCH(4, false);
+    }
+#undef SBATCH
+    HIPCHK(c, hipGetLastError());
+    if (ints0[I_STOP]) HIPCHK(c, hipMemcpyAsync(c->ints + I_STOP, &ints0[I_STOP], sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // read-back: [sigma | zeta] and [CA | A | dS | beta] and SigmaA are contiguous blocks
+    std::vector<double> sz((size_t)2 * nb);
+    HIPCHK(c, hipMemcpyAsync(sz.data(), d + o_sig, sz.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(CA, d + o_ca, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ATVecHat) HIPCHK(c, hipMemcpyAsync(ATVecHat, d + o_a, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (diagSigmaATVec) HIPCHK(c, hipMemcpyAsync(diagSigmaATVec, d + o_ds, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (beta) HIPCHK(c, hipMemcpyAsync(beta, d + o_be, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (SigmaA) HIPCHK(c, hipMemcpyAsync(SigmaA, d + o_sa, (size_t)(nb * h2) * 8, hipMemcpyDeviceToHost, c->stream));   // symmetric
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(sigmaHat, sz.data(), (size_t)nb * 8);
+    if (zeta) memcpy(zeta, sz.data() + nb, (size_t)nb * 8);
     return check_device_err(c);
 }
 

@@ -536,6 +536,91 @@ function vbmf_dual_init(Y::Array{Float64,2}, H::Int, H0::Int; ca = 1.0, alpha0 =
     return p
 end
 
+# vbls! of the sparse models over many bags with one fixed basis in ONE device call (examples/mil_util.jl:187-193, the classifiers of
+# :393-416, :469-479, :497-521): the bags go side by side into one sparse context, every bag runs all niter iterations in one
+# workgroup of one launch (vbmf_sparse_run_fixed_basis_batched).  al, b0: updateCA!'s (alpha_h, beta0_h) of every bag, H x nb.
+function sparse_batch_run!(Ys::Vector{Matrix{Float64}}, ps, niter::Int, full_cov::Bool, al::Matrix{Float64}, b0::Matrix{Float64})
+    nb = length(Ys)
+    (nb >= 1 && length(ps) == nb) || error("vbls_batch!: one parameter set per bag")
+    p0 = ps[1]
+    H, L = p0.H, size(Ys[1], 1)
+    H <= 64 || error("vbls_batch!: H = $H > 64; use vbls! per bag")
+    for b in 1:nb
+        Y, p = Ys[b], ps[b]
+        size(Y, 1) == L || error("vbls_batch!: the bags have different L; use vbls! per bag")
+        (size(Y, 2) >= 1 && (p.L, p.M, p.H) == (L, size(Y, 2), H)) || error("vbls_batch!: bag $b does not match its parameters")
+        (p.BHat == p0.BHat && p.SigmaB == p0.SigmaB) ||
+            error("vbls_batch!: bag $b does not share BHat and SigmaB with bag 1; use vbls! per bag")
+    end
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    M = off[end]
+    Yall = reduce(hcat, Ys)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, 1, 0xffffffff, 1, 0, 0, 0, 0, 0))   # VBMF_VARIANT_SPARSE_DIAG
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
+    eta = Float64[p.eta0 + p.L * p.M / 2 for p in ps]
+    z0 = Float64[p.zeta0 for p in ps]
+    sg = Float64[p.sigmaHat for p in ps]
+    ca = reduce(vcat, [Vector{Float64}(p.CA) for p in ps])
+    ze = Array{Float64}(undef, nb); be = Array{Float64}(undef, M * H); ds = similar(be); a = similar(be)
+    SA = Array{Float64}(undef, H, H, nb)
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        hy = Ref(SparseHyper(1e-10, 1e-10, p0.gamma0, p0.delta0, p0.eta0, p0.zeta0))
+        z, o = zeros(M * H), ones(M * H)
+        chk(h[], ccall((:vbmf_sparse_set_state, libvbmf), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Float64, Float64, Ref{SparseHyper}, Ptr{Int64}, Int64, Int64),
+            h[], z, o, o, o, p0.BHat, L, p0.SigmaB, ones(H), ones(H), 1.0, 0.0, hy, C_NULL, 0, 0))
+        chk(h[], ccall((:vbmf_sparse_run_fixed_basis_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            h[], nb, off, niter, full_cov, al, b0, eta, z0, sg, ca, ze, be, ds, SA, a))
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+    for b in 1:nb
+        p, r = ps[b], off[b]*H+1:off[b+1]*H
+        p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta = a[r], ds[r], ca[r], be[r]
+        p.AHat = permutedims(reshape(p.ATVecHat, H, p.M))
+        p.SigmaA = SA[:, :, b]
+        p.sigmaHat, p.zeta = sg[b], ze[b]
+        p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')        # :201
+    end
+    return [p.AHat for p in ps]
+end
+
+"""
+vbls! on the ARD-sparse model over many bags with one fixed basis in ONE device call (examples/mil_util.jl:187-190, :469-479 and
+:393-416): does what `[vbls!(Y, p, niter; full_cov = full_cov) for (Y, p) in zip(Ys, ps)]` does.  No labels, H <= 64.
+"""
+function vbls_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; full_cov::Bool = false)
+    for (b, p) in enumerate(ps)
+        (p.H1 == 0 && isempty(p.labels)) || error("vbls_batch!: bag $b has labels; use vbls! per bag")
+    end
+    al = Float64[p.alpha0 + 0.5 for h in 1:ps[1].H, p in ps]
+    b0 = Float64[p.beta0 for h in 1:ps[1].H, p in ps]
+    return sparse_batch_run!(Ys, ps, niter, full_cov, al, b0)
+end
+
+"""
+vbls! on the two-group model over many bags with one fixed basis in ONE device call (examples/mil_util.jl:190-193, :514-521):
+does what `[vbls!(Y, p, niter; full_cov = full_cov) for (Y, p) in zip(Ys, ps)]` does, the group views and posterior shapes included.
+"""
+function vbls_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameters}, niter::Int; full_cov::Bool = false)
+    H = ps[1].H
+    al = Float64[h <= p.H0 ? p.alpha00 + 0.5 : p.alpha01 + 0.5 for h in 1:H, p in ps]
+    b0 = Float64[h <= p.H0 ? p.beta00 : p.beta01 for h in 1:H, p in ps]
+    out = sparse_batch_run!(Ys, ps, niter, full_cov, al, b0)
+    for p in ps
+        p.A0Hat, p.A1Hat = p.AHat[:, 1:p.H0], p.AHat[:, p.H0+1:end]
+        p.CA0, p.CA1 = dual_split(p.CA, p.M, p.H, p.H0); p.beta0, p.beta1 = dual_split(p.beta, p.M, p.H, p.H0)
+        p.alpha0, p.alpha1 = p.alpha00 + 0.5, p.alpha01 + 0.5                                 # src/vbmf_dual.jl:324-325
+        p.alpha = [p.alpha0, p.alpha1]
+    end
+    return out
+end
+
 "vbmf_dual! -- src/vbmf_dual.jl:455-530 (returns d); est_priors: the hyper-prior fits of :393-434 run on the device"
 function vbmf_dual!(Y::Array{Float64,2}, p::vbmf_dual_parameters, niter::Int; eps::Float64 = 1e-6, diag_var::Bool = false,
                     full_cov::Bool = false, logdir = "", desc = "", verb = false, est_priors = true, est_cb::Bool = true)
