@@ -310,6 +310,9 @@ int vbmf_device_sync(vbmf_ctx* ctx);
 #define VBMF_PEEK_STATE 10 /* fp64 control state (two words per double): [A'A | B'B | dB'dB | tr(B'YA) x 8 | ...], Hp x Hp blocks */
 #define VBMF_PEEK_GRAM_W 11 /* Gram form: the current W fp32 row-major [32 GT][Hp] (rows >= M zero) */
 #define VBMF_PEEK_GRAM_PQ 12 /* Gram form: [P | Q] = G [W | W - W_old], fp32, each [XT1][NH][64][16] fragment-major */
+#define VBMF_PEEK_GRAM_G 13  /* Gram form: G = Y'Y as fp32 MFMA operand fragments [GT][2 GT][64][8], GT = XT1 rounded up to 16:
+                               word ((p 2 GT + j) 64 + lane) 8 + e, lane = 32 half + c, holds G[32 p + c][16 j + 8 half + e];
+                               rows / columns >= M zero (0 words before the first run that takes the Gram form) */
 int vbmf_debug_peek(vbmf_ctx* ctx, int what, uint32_t* out, int64_t nwords, int64_t word_offset);
 /* tuning hook: average milliseconds of `iters` back-to-back launches of streaming pass p (1|2) alone */
 int vbmf_debug_time_pass(vbmf_ctx* ctx, int pass, int iters, double* ms);

@@ -93,3 +93,20 @@ def bf16_round(Y):
             take = (err < berr) | ((err == berr) & even & ~beven)
             best = np.where(take, cand, best); berr = np.where(take, err, berr); beven = np.where(take, even, beven)
     return best
+
+
+def frag_to_rows(F, M, Hp):
+    """[XT][NH][64][16] fragment-major (lane (half, x), element r: column 8 (r >> 2) + 4 half + (r & 3)) -> M x Hp (the layout of
+    the Gram form's [P | Q], post_kernels.hpp frag_index)."""
+    XT, NH = F.size // (Hp * 32), Hp // 32
+    F = F.reshape(XT, NH, 2, 32, 4, 4)                       # x tile, h tile, half, x, r >> 2, r & 3
+    R = F.transpose(0, 3, 1, 4, 2, 5).reshape(XT * 32, Hp)  # row 32 tile + x; column 32 ht + 8 g + 4 half + e
+    return R[:M].astype(np.float64)
+
+
+def gram_frag_to_matrix(F, GT):
+    """G's fp32 operand fragments (VBMF_PEEK_GRAM_G: [row tile p][k-step j][lane (half, c)][8], holding G[32 p + c][16 j + 8 half + e],
+    KT = 2 GT k-steps per row tile) -> the 32 np x 32 GT matrix of the np = F.size / (KT 512) row tiles F holds (np = GT: all of G)."""
+    KT = 2 * GT
+    F = np.asarray(F).reshape(-1, KT, 2, 32, 8)             # p, j, half, c, e
+    return F.transpose(0, 3, 1, 2, 4).reshape(F.shape[0] * 32, KT * 16)

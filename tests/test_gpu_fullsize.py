@@ -206,3 +206,77 @@ def test_config4_whole_matrix_properties(pkg):
         c.set_Y_synthetic(20170101, H, 0.05)
         shard = c.get_Y()
     assert np.array_equal(shard, window)
+
+
+def test_config4_share_gram_form_vs_oracle(pkg, monkeypatch):
+    """Config 4's rank-share size (125 000 x 10 000, H = 128) on a plain whole-matrix context, which takes the Gram form by the
+    size rule (no comm_init: test_config4_rank_share_vs_oracle's collective context runs the streaming path).  Separated data
+    as in tests/test_gpu_gram_path.py's _problem (each column one latent column of scale 1 .. 3, noise 0.05), so the VB fixed
+    point is well conditioned and a ten-sweep trajectory is a meaningful target.  Against the fused fp64 oracle on the stored Y,
+    and against the streaming path (VBMF_GRAM=0) on the same stored Y; bounds: the 25-sweep trajectory bounds of
+    test_run_trajectory_well_conditioned (factors 4e-5, SigmaA / SigmaB / sigma2 1.6e-4, d rtol 8e-3, ELBO rtol 4e-4)."""
+    Ls, H, noise, n = L4 // SHARDS4, H4, 0.05, 10
+    rng = np.random.default_rng(20170105)
+    Bt = rng.standard_normal((Ls, H)) * np.linspace(1.0, 3.0, H)
+    col = rng.integers(0, H, size=M4)
+    Y = np.empty((Ls, M4), order="F")
+    for j0 in range(0, M4, 500):
+        j1 = min(j0 + 500, M4)
+        Y[:, j0:j1] = Bt[:, col[j0:j1]] + noise * rng.standard_normal((Ls, j1 - j0))
+    del Bt
+    po = O.vbmf_init(np.broadcast_to(0.0, (Ls, M4)), H, ca=0.1, cb=0.1, sigma2=0.1, rng=np.random.default_rng(20170106),
+                     materialize_yhat=False)
+    z = np.zeros((H, H))
+
+    def go(c):
+        c.set_state(po.AHat, po.BHat, z, z, 0.1 * np.ones(H), 0.1 * np.ones(H), 0.1)
+        it, d, tr = c.run(n, eps=0.0, est_covs=True, est_var=True, want_trace=True)
+        assert it == n
+        return d, tr.copy(), c.get_state(want_B=True)
+
+    monkeypatch.delenv("VBMF_GRAM", raising=False)
+    with pkg.capi.Context(Ls, M4, H, y_dtype=pkg.VBMF_Y_BF16) as c:
+        dims = c.dims()
+        assert dims["gram"] == 1 and dims["NH"] == 4
+        c.set_Y(Y)
+        del Y
+        gc.collect()
+        dg, trg, sg = go(c)
+        nsplit = c.dims()["gram_nsplit"]
+        Ys = c.get_Y()
+    monkeypatch.setenv("VBMF_GRAM", "0")
+    with pkg.capi.Context(Ls, M4, H, y_dtype=pkg.VBMF_Y_BF16) as c:
+        monkeypatch.delenv("VBMF_GRAM")
+        assert c.dims()["gram"] == 0
+        c.set_Y(Ys)
+        ds, trs, ss = go(c)
+    otr = []
+    O.vbmf_(Ys, po, n, eps=0.0, est_covs=True, est_var=True, fused=True, trace=otr)
+    del Ys
+    gc.collect()
+    otr = np.array(otr)
+
+    def errs(s, d, tr):
+        return dict(A=relF(s["AHat"], po.AHat), B=relF(s["BHat"], po.BHat), SA=relF(s["SigmaA"], po.SigmaA),
+                    SB=relF(s["SigmaB"], po.SigmaB), ca=relF(s["CA_diag"], np.diag(po.CA)), cb=relF(s["CB_diag"], np.diag(po.CB)),
+                    s2=abs(s["sigma2"] - po.sigma2) / po.sigma2, d=abs(d - otr[-1, 0]) / otr[-1, 0],
+                    elbo=abs(tr[-1, 2] - otr[-1, 2]) / abs(otr[-1, 2]),
+                    d_tr=float(np.max(np.abs(tr[:, 0] - otr[:, 0]) / (1e-5 + 8e-3 * otr[:, 0]))),
+                    s2_tr=float(np.max(np.abs(tr[:, 1] - otr[:, 1]) / otr[:, 1])),
+                    elbo_tr=float(np.max(np.abs(tr[:, 2] - otr[:, 2]) / (1.0 + 4e-4 * np.abs(otr[:, 2])))))
+    eg, es = errs(sg, dg, trg), errs(ss, ds, trs)
+    gs = dict(A=relF(sg["AHat"], ss["AHat"]), B=relF(sg["BHat"], ss["BHat"]), SB=relF(sg["SigmaB"], ss["SigmaB"]),
+              s2=abs(sg["sigma2"] - ss["sigma2"]) / ss["sigma2"])
+    within = np.abs(otr[:, 1] - noise ** 2) <= 0.1 * noise ** 2
+    reach = int(np.argmax(within)) + 1 if within.any() else -1
+    tail = f"  [gram_nsplit {nsplit}; oracle sigma2 {otr[-1, 1]:.7e} (noise^2 {noise ** 2:.1e}), within 10 % from sweep {reach}]"
+    report(f"cfg4 SHARE GRAM FORM {Ls}x{M4} H={H} separated, {n} sweeps, gram vs oracle: "
+           + " ".join(f"{k}={v:.2e}" for k, v in eg.items()) + tail)
+    report(f"cfg4 SHARE STREAMING {Ls}x{M4} H={H} separated, {n} sweeps, streaming vs oracle: "
+           + " ".join(f"{k}={v:.2e}" for k, v in es.items()))
+    report(f"cfg4 SHARE GRAM vs STREAMING {Ls}x{M4} H={H} separated, {n} sweeps: " + " ".join(f"{k}={v:.2e}" for k, v in gs.items())
+           + f"  [sigma2 gram {sg['sigma2']:.7e} streaming {ss['sigma2']:.7e}]")
+    assert 0 < reach <= n, (reach, otr[:, 1])
+    assert max(eg[k] for k in ("A", "B", "ca", "cb")) < 4e-5, eg
+    assert max(eg[k] for k in ("SA", "SB", "s2", "s2_tr")) < 1.6e-4, eg
+    assert eg["d_tr"] <= 1.0 and eg["elbo_tr"] <= 1.0, eg

@@ -8,6 +8,7 @@ import pytest
 
 import __graft_entry__ as G
 from oracle import vbmf_oracle as O
+from tests.helpers import frag_to_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -16,14 +17,6 @@ pytestmark = pytest.mark.gpu
 def pkg():
     G.build()
     return G.load_package()
-
-
-def _frag_to_rows(F, M, Hp):
-    """[XT][NH][64][16] fragment-major (lane (half, x), element r: column 8 (r >> 2) + 4 half + (r & 3)) -> M x Hp."""
-    XT, NH = F.size // (Hp * 32), Hp // 32
-    F = F.reshape(XT, NH, 2, 32, 4, 4)                       # x tile, h tile, half, x, r >> 2, r & 3
-    R = F.transpose(0, 3, 1, 4, 2, 5).reshape(XT * 32, Hp)  # row 32 tile + x; column 32 ht + 8 g + 4 half + e
-    return R[:M].astype(np.float64)
 
 
 def _sweep(pkg, monkeypatch, L, M, H, seed):
@@ -73,7 +66,7 @@ def test_partials_match_fp64_recomputation(pkg, monkeypatch, H):
     # gram_w: W = fp32(A (SigmaB / sigma2)) with the fp32 table the sweep used (SigmaB slot / sigma2, rounded as ctrl_cov rounds it)
     Wref = (r["A"].astype(np.float64) @ r["S"].astype(np.float64)).astype(np.float32).astype(np.float64)
     assert _rel(W, Wref) < 1e-6
-    P, Q = _frag_to_rows(r["P"], M, Hp), _frag_to_rows(r["Q"], M, Hp)
+    P, Q = frag_to_rows(r["P"], M, Hp), frag_to_rows(r["Q"], M, Hp)
     WP, DQ = W.T @ P, D.T @ Q
     assert _rel(r["GB"], 0.5 * (WP + WP.T)) < 1e-12
     assert _rel(r["GD"], 0.5 * (DQ + DQ.T)) < 1e-12

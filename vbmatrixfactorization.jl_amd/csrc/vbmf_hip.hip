@@ -1025,9 +1025,11 @@ static int gram_prepare(vbmf_ctx* c) {
         c->g_nchunk = cdiv(c->M, c->g_rpc);
         const size_t n = (size_t)c->Hp * Mp1;
         const size_t wrows = (size_t)32 * c->GT;
+        // the zero fill goes on the context's stream: a hipMemset on the null stream is not ordered before the build kernel on this
+        // non-blocking stream, and a fill still running over G's tail zeroed entries the build had already stored
         auto alloc = [&](void** p, size_t bytes) -> hipError_t {
             hipError_t e = hipMalloc(p, bytes);
-            if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+            if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, c->stream);
             return e;
         };
         hipError_t e = alloc((void**)&c->Gt, (size_t)c->GT * KT * 64 * 8 * 4);
@@ -2336,6 +2338,7 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
         case VBMF_PEEK_STATE: base = c->st; words = (size_t)c->lay.total() * 2; break;
         case VBMF_PEEK_GRAM_W: base = c->W32g[c->wcur]; words = c->W32g[c->wcur] ? (size_t)32 * c->GT * c->Hp : 0; break;
         case VBMF_PEEK_GRAM_PQ: base = c->gPQ; words = c->gPQ ? (size_t)2 * c->Hp * c->d1.XT * 32 : 0; break;
+        case VBMF_PEEK_GRAM_G: base = c->Gt; words = c->Gt ? (size_t)c->GT * 2 * c->GT * 64 * 8 : 0; break;
         default: FAIL(c, VBMF_ERR_INVALID, "vbmf_debug_peek: unknown buffer");
     }
     if ((size_t)(word_offset + nwords) > words) FAIL(c, VBMF_ERR_INVALID, "vbmf_debug_peek: range exceeds buffer (%zu words)", words);
@@ -2679,7 +2682,7 @@ static int dual_update_priors(vbmf_ctx* c) {
 static int launch_sparse_t2(vbmf_ctx* c) {
     if (!c->t2part) {
         HIPCHK(c, hipMalloc((void**)&c->t2part, T2_BLOCKS * 8));
-        HIPCHK(c, hipMemset(c->t2part, 0, T2_BLOCKS * 8));
+        HIPCHK(c, hipMemsetAsync(c->t2part, 0, T2_BLOCKS * 8, ctrl_stream(c)));   // ordered before the kernel below
     }
     hipLaunchKernelGGL(sparse_t2_kernel, dim3(T2_BLOCKS), dim3(256), 0, ctrl_stream(c), c->st, c->lay, (int)c->H, (double)c->Lg, c->t2part, c->ints);
     HIPCHK(c, hipGetLastError());
@@ -3081,12 +3084,12 @@ int vbmf_sparse_set_full_cov(vbmf_ctx* c, int on) {
         if (c->H > 128) HIPCHK(c, hipMalloc((void**)&c->fws, (size_t)c->fblocks * FULL256_WS * 8));
         const size_t bytes = (size_t)c->fblocks * c->Hp * c->Hp * 8;
         HIPCHK(c, hipMalloc((void**)&c->fpart, bytes));
-        HIPCHK(c, hipMemset(c->fpart, 0, bytes));
+        HIPCHK(c, hipMemsetAsync(c->fpart, 0, bytes, c->stream));   // its kernels run on c->stream
     }
     if (on && c->diagvar && !c->gw) {
         const size_t bytes = (size_t)2 * c->Hp * c->Hp * 8;
         HIPCHK(c, hipMalloc((void**)&c->gw, bytes));
-        HIPCHK(c, hipMemset(c->gw, 0, bytes));
+        HIPCHK(c, hipMemsetAsync(c->gw, 0, bytes, c->stream));
     }
     c->full_cov = on != 0;
     return VBMF_OK;
