@@ -466,7 +466,6 @@ def test_streamk_split_of_the_long_pass(pkg, monkeypatch):
             compare(f"stream-K {name} bf16x2 {L}x{M} H{H} run2", out[name], qo, {k: 3 * v for k, v in tol.items()})
         a, b = out["split"], out["whole"]
         assert relF(a.BHat, b.BHat) < 5e-6 and relF(a.AHat, b.AHat) < 5e-6 and relF(a.SigmaB, b.SigmaB) < 2e-5
-        assert not np.array_equal(a.BHat, b.BHat) or True        # (summation order differs: equality is not expected, nor required)
     finally:
         pkg.set_defaults(y_dtype=pkg.VBMF_Y_F32, factor_dtype=pkg.VBMF_FACTOR_AUTO)
 

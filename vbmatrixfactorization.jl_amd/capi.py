@@ -44,7 +44,7 @@ VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, V
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
 SSTEP_A, SSTEP_B, SSTEP_CA, SSTEP_CB, SSTEP_SIGMA, SSTEP_PRIORS = 1, 2, 4, 8, 16, 32
 (PEEK_P, PEEK_Q, PEEK_A32, PEEK_B32, PEEK_FA, PEEK_FB, PEEK_Y1, PEEK_Y2, PEEK_DIMS, PEEK_CHAIN, PEEK_STATE, PEEK_GRAM_W,
- PEEK_GRAM_PQ, PEEK_GRAM_G) = range(14)
+ PEEK_GRAM_PQ, PEEK_GRAM_G, PEEK_SA32, PEEK_SB32) = range(16)
 
 
 class VbmfOpts(C.Structure):
@@ -528,10 +528,12 @@ class Context:
                         (float(x) * 0.01 for x in v)))
 
     def dims(self):
-        v = self.peek(PEEK_DIMS, 20, dtype=np.int32)
+        v = self.peek(PEEK_DIMS, 26, dtype=np.int32)
         keys = ["Hp", "NH", "mode", "XT1", "KS1", "nsplit1", "sps1", "XT2", "KS2", "nsplit2", "sps2", "kstep", "npart", "narrow",
                 "streamk_per", "streamk_grid",       # segment-list plan of the Y*A pass: pieces per cut block (0: off), segments = workgroups
-                "gram", "gram_built", "gram_build_us", "gram_nsplit"]   # vbmf_run takes the Gram form; G built; its build time; split-K
+                "gram", "gram_built", "gram_build_us", "gram_nsplit",   # vbmf_run takes the Gram form; G built; its build time; split-K
+                "p_frag", "q_frag", "q_epi",         # the last pass 1 / pass 2 product is fragment-major; the last pass 2 ran the register epilogue
+                "lds8", "xcd_map", "post3"]          # variant switches as the context resolved them (VBMF_LDS8, VBMF_XCD_MAP, VBMF_POST3)
         return dict(zip(keys, (int(x) for x in v)))
 
     def time_pass(self, p, iters=10):

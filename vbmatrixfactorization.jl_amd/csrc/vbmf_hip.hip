@@ -131,6 +131,8 @@ struct vbmf_ctx {
     bool sparse_a_fused = true;       // ARD-sparse A update writes its operand tiles itself (VBMF_SPARSE_A_FUSED=0: update kernel + retile)
     bool post3 = true;                // H >= 128 factor update with the table shared through LDS (post_frag3_kernel); VBMF_POST3=0: post_frag2
     bool P_frag = false;              // the Y'B product in c->P / c->Pred is fragment-major (stream_gemm.hpp, frag_out)
+    bool frag_last[2] = {false, false};   // test surface (VBMF_PEEK_DIMS): the last launch of pass 1 / pass 2 wrote fragment-major output
+    bool epi_last = false;            // ... the last launch of pass 2 ran the register epilogue (no product stored)
     bool B32_stale = false;           // the register epilogue skipped the fp32 store of B (inside vbmf_run): tiles are current
     int sready_seq = 0;               // sequence number of the Sigma-table release flag (register epilogue)
     bool epi_balance = false;         // x groups of the register-epilogue pass dealt three per workgroup over the whole chip instead
@@ -427,6 +429,8 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
         GSLAB_CHECK(c, bps, 2 * (c->NH * (c->NH + 1) / 2) * 1024);
     }
     const size_t lds = ctrl_mode ? ctrl_lds_bytes(c->NH) : 0;
+    c->frag_last[pass] = frag_out && !epi;
+    if (pass == 1) c->epi_last = epi;
     prof_begin(c, pass);
     if (use_lds8(c) && !epi) {
         if (lds > (size_t)LDS8_BYTES) FAIL(c, VBMF_ERR_INVALID, "internal: control chain needs %zu bytes of LDS", lds);
@@ -2313,10 +2317,12 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (what == VBMF_PEEK_DIMS) {
-        const int v[20] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
+        const int v[26] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
                            c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
-                           gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit};
-        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(20, nwords));
+                           gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
+                           c->frag_last[0] ? 1 : 0, c->frag_last[1] ? 1 : 0, c->epi_last ? 1 : 0, use_lds8(c) ? 1 : 0, c->xcd_map ? 1 : 0,
+                           c->post3 ? 1 : 0};
+        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(26, nwords));
         return VBMF_OK;
     }
     if (what == VBMF_PEEK_CHAIN) {
@@ -2339,6 +2345,8 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
         case VBMF_PEEK_GRAM_W: base = c->W32g[c->wcur]; words = c->W32g[c->wcur] ? (size_t)32 * c->GT * c->Hp : 0; break;
         case VBMF_PEEK_GRAM_PQ: base = c->gPQ; words = c->gPQ ? (size_t)2 * c->Hp * c->d1.XT * 32 : 0; break;
         case VBMF_PEEK_GRAM_G: base = c->Gt; words = c->Gt ? (size_t)c->GT * 2 * c->GT * 64 * 8 : 0; break;
+        case VBMF_PEEK_SA32: base = c->SA32; words = (size_t)c->Hp * c->Hp; break;
+        case VBMF_PEEK_SB32: base = c->SB32; words = (size_t)c->Hp * c->Hp; break;
         default: FAIL(c, VBMF_ERR_INVALID, "vbmf_debug_peek: unknown buffer");
     }
     if ((size_t)(word_offset + nwords) > words) FAIL(c, VBMF_ERR_INVALID, "vbmf_debug_peek: range exceeds buffer (%zu words)", words);
