@@ -24,9 +24,10 @@ importing/using it without that library (or without an MI355X) raises.
 """
 from __future__ import annotations
 
+import copy as _copy
 import weakref
 from dataclasses import dataclass, field, fields
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -343,6 +344,38 @@ def elbo(Y, params):
     return s.ctx.elbo()
 
 
+def _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run, pull, yhat, say_saving=False):
+    """The sweep loop of vbmf! and of the ARD models' twins around two callables: run(k) runs up to k sweeps on the device and
+    returns (sweeps done, d, trace), pull() brings the device state into params.  logdir != "": the trajectory is logged like the
+    reference does (slice 0 = the initial state, then one slice per chunk of log_every sweeps, src/vbmf.jl:181-184,205-207) and
+    saved under logdir/desc (data_manip.py).  Sets params.YHat (yhat(), up to YHAT_AUTO_LIMIT elements) and params._last_run;
+    returns d."""
+    if logdir != "":
+        logVar = create_log(params)
+        i, d, iters = 1, eps + 1.0, 0
+        while i <= niter and d > eps:                          # src/vbmf.jl:193 on the host, one device call per chunk
+            k = int(min(max(1, log_every), niter - i + 1))
+            done, d, _ = run(k)
+            pull()
+            update_log_(logVar, params)
+            iters += done
+            i += done
+            if done < k:
+                break
+    else:
+        iters, d, _ = run(int(niter))
+        pull()
+    params.YHat = yhat() if params.L * params.M <= YHAT_AUTO_LIMIT else None    # src/vbmf.jl:217
+    if verb:
+        print(f"Factorization finished after {iters} iterations, eps = {d}")   # :221
+    if logdir != "":
+        if say_saving:
+            print(f"Saving outputs and inputs under {logdir}/")                # :226
+        save_log(logVar, Y, {}, logdir, desc=desc)
+    params._last_run = (iters, d)
+    return d
+
+
 def vbmf_(Y, params, niter, eps=1e-6, est_covs=False, est_var=False, logdir="", desc="", verb=False, log_every=1):
     """vbmf! -- src/vbmf.jl:175-231.  `params` is modified in place and returned.
     logdir != "": the trajectory is logged like the reference does (slice 0 = the initial state, then one slice per
@@ -351,31 +384,8 @@ def vbmf_(Y, params, niter, eps=1e-6, est_covs=False, est_var=False, logdir="", 
     _check(Y, params)
     s = _session_for(Y, params.H)
     s.push(params)
-    if logdir != "":
-        logVar = create_log(params)
-        i, d, iters = 1, eps + 1.0, 0
-        while i <= niter and d > eps:                          # src/vbmf.jl:193 on the host, one device call per chunk
-            k = int(min(max(1, log_every), niter - i + 1))
-            done, d, _ = s.run(k, eps=eps, est_covs=est_covs, est_var=est_var)
-            s.pull(params)
-            update_log_(logVar, params)
-            iters += done
-            i += done
-            if done < k:
-                break
-    else:
-        iters, d, _ = s.run(int(niter), eps=eps, est_covs=est_covs, est_var=est_var)
-        s.pull(params)
-    if params.L * params.M <= YHAT_AUTO_LIMIT:
-        params.YHat = s.ctx.YHat()                             # :217
-    else:
-        params.YHat = None
-    if verb:
-        print(f"Factorization finished after {iters} iterations, eps = {d}")   # :221
-    if logdir != "":
-        print(f"Saving outputs and inputs under {logdir}/")                    # :226
-        save_log(logVar, Y, {}, logdir, desc=desc)
-    params._last_run = (iters, d)
+    _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run=lambda k: s.run(k, eps=eps, est_covs=est_covs, est_var=est_var),
+         pull=lambda: s.pull(params), yhat=s.ctx.YHat, say_saving=True)
     return params
 
 
@@ -435,27 +445,42 @@ class vbmf_sparse_parameters:
 def vbmf_sparse_init(Y, H, ca=1.0, alpha0=1e-10, beta0=1e-10, cb=1.0, gamma0=1e-10, delta0=1e-10, sigma=1.0,
                      eta0=1e-10, zeta0=1e-10, H1=0, labels=(), rng=None):
     """src/vbmf_sparse.jl:101-153 (host side)."""
+    p = vbmf_sparse_parameters()
+    p.L, p.M = np.shape(Y)
+    p.H, p.MH, p.H1 = int(H), p.M * int(H), int(H1)
+    p.labels = np.asarray(labels, dtype=np.int64)
+    return _ard_init(p, Y, ca, alpha0, beta0, cb, gamma0, delta0, sigma, eta0, zeta0, rng)
+
+
+def _ard_init(p, Y, ca, alpha0, beta0, cb, gamma0, delta0, sigma, eta0, zeta0, rng):
+    """What vbmf_sparse_init and its grouped twins (src/vbmf_dual.jl:122-193, src/vbmf_trial.jl:139-226) fill alike once the
+    sizes of p are set: every ARD group starts from the same hyper-priors, so CA and beta are constant and the group views
+    are cut from them."""
+    m = _MODELS[type(p)]
     Y = np.asarray(Y)
     rng = np.random.default_rng() if rng is None else rng
-    p = vbmf_sparse_parameters()
-    L, M = Y.shape
-    p.L, p.M, p.H, p.MH, p.H1 = L, M, int(H), M * int(H), int(H1)
-    p.labels = np.asarray(labels, dtype=np.int64)
+    L, M, H = p.L, p.M, p.H
     p.AHat = rng.standard_normal((M, H))
-    if p.H1 > 0 and p.labels.size:
+    if m.labels and p.H1 > 0 and p.labels.size:
         p.AHat[_labels0(p), H - p.H1:] = 0.0
     p.ATVecHat = p.AHat.reshape(M * H).copy()
     p.diagSigmaATVec = np.ones(M * H)
     p.SigmaA = np.zeros((H, H))
     p.BHat = rng.standard_normal((L, H))
     p.SigmaB = np.zeros((H, H))
-    p.CA = ca * np.ones(M * H)
-    p.alpha0, p.beta0, p.alpha, p.beta = alpha0, beta0, alpha0 + 0.5, beta0 * np.ones(M * H)
+    p.CA, p.beta = ca * np.ones(M * H), beta0 * np.ones(M * H)
+    for a0, b0, a in m.groups:
+        setattr(p, a0, alpha0)
+        setattr(p, b0, beta0)
+        setattr(p, a, alpha0 + 0.5)
+    if m.views is not None:
+        m.views(p)
+        p.alpha = _posterior_shapes(p, m)
     p.CB = cb * np.ones(H)
     p.gamma0, p.delta0, p.gamma, p.delta = gamma0, delta0, gamma0 + L / 2, delta0 * np.ones(H)
     p.sigmaHat, p.eta0, p.zeta0, p.eta, p.zeta = float(sigma), eta0, zeta0, eta0 + L * M / 2, zeta0
     p.sigmaVecHat, p.etaVec, p.zetaVec = sigma * np.ones(L), (eta0 + M / 2) * np.ones(L), zeta0 * np.ones(L)   # :145-147
-    p.YHat = p.BHat @ p.AHat.T if L * M <= YHAT_AUTO_LIMIT else None
+    p.YHat = _host_YHat(p)
     p.trYTY = float(np.sum(Y * Y))
     return p
 
@@ -463,62 +488,49 @@ def vbmf_sparse_init(Y, H, ca=1.0, alpha0=1e-10, beta0=1e-10, cb=1.0, gamma0=1e-
 _sparse_sessions = {}
 
 
-def _sparse_ctx(Y, p, diag_var=False, dual=False, trial=False):
+class _SparseKey(NamedTuple):
+    Y: object                  # id() of the caller's matrix, or "noY": the context that is never given one
+    shape: tuple               # (L, M)
+    data: int                  # address of the matrix's buffer (0 without one)
+    H: int
+    diag_var: bool
+    model: object              # the _Model of the parameter type
+    defaults: tuple            # sorted _defaults
+
+
+def _sparse_ctx(Y, p, diag_var, model):
     """Y = None: the updates whose reference signatures take no Y (updateCA!, updateCB!: src/vbmf_sparse.jl:284-300 and the
     grouped models' twins) -- a cached context of the same problem serves, else one that is never given a matrix."""
+    defaults = tuple(sorted(_defaults.items()))
     if Y is None:
-        # updateCA! / updateCB! do not depend on the noise model: ANY cached context of this problem and grouping serves, whatever
+        # updateCA! / updateCB! do not depend on the noise model: ANY cached context of this problem and model serves, whatever
         # its diag_var (a heteroscedastic step-wise loop would otherwise evict -- and re-upload -- its own Y-holding session on every
         # CA / CB call), and a context that holds no matrix lives in its own slot instead of closing the ones that do
-        want = (int(p.H), bool(diag_var), bool(dual), bool(trial), tuple(sorted(_defaults.items())))
         for k, v in _sparse_sessions.items():
-            if k[1] == (p.L, p.M) and k[3] == want[0] and k[5:] == want[2:]:
+            if k.shape == (p.L, p.M) and k.H == int(p.H) and k.model is model and k.defaults == defaults:
                 return v[0]
-        key = ("noY", (p.L, p.M), 0) + want
-        if trial:
-            variant = VBMF_VARIANT_TRIAL_DIAG
-        elif dual:
-            variant = VBMF_VARIANT_DUAL_DIAG
-        else:
-            variant = VBMF_VARIANT_SPARSE_DIAG
-        for k in [k for k in _sparse_sessions if k[0] == "noY"]:
+        for k in [k for k in _sparse_sessions if k.Y == "noY"]:
             _sparse_sessions.pop(k)[0].close()
-        c = Context(p.L, p.M, p.H, variant=variant, **_defaults)
-        _sparse_sessions[key] = (c, lambda: None, None)
+        c = Context(p.L, p.M, p.H, variant=model.diag, **_defaults)
+        _sparse_sessions[_SparseKey("noY", (p.L, p.M), 0, int(p.H), bool(diag_var), model, defaults)] = (c, lambda: None, None)
         return c
-    else:
-        Y = np.asarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("Y must be a matrix")
-        key = (id(Y), Y.shape, Y.__array_interface__["data"][0], int(p.H), bool(diag_var), bool(dual), bool(trial), tuple(sorted(_defaults.items())))
-        fp = _fingerprint(Y)
-        ent = _sparse_sessions.get(key)
-        if ent is not None and ent[1]() is Y:
-            if ent[2] != fp:                   # same array object, new contents (see _session_for)
-                ent[0].set_Y(Y)
-                _sparse_sessions[key] = (ent[0], ent[1], fp)
-            return ent[0]
-    for k in [k for k in _sparse_sessions if k[0] != "noY"]:
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ValueError("Y must be a matrix")
+    key = _SparseKey(id(Y), Y.shape, Y.__array_interface__["data"][0], int(p.H), bool(diag_var), model, defaults)
+    fp = _fingerprint(Y)
+    ent = _sparse_sessions.get(key)
+    if ent is not None and ent[1]() is Y:
+        if ent[2] != fp:                       # same array object, new contents (see _session_for)
+            ent[0].set_Y(Y)
+            _sparse_sessions[key] = (ent[0], ent[1], fp)
+        return ent[0]
+    for k in [k for k in _sparse_sessions if k.Y != "noY"]:
         _sparse_sessions.pop(k)[0].close()
-    if trial:
-        variant = VBMF_VARIANT_TRIAL_DIAGVAR if diag_var else VBMF_VARIANT_TRIAL_DIAG
-    elif dual:
-        variant = VBMF_VARIANT_DUAL_DIAGVAR if diag_var else VBMF_VARIANT_DUAL_DIAG
-    else:
-        variant = VBMF_VARIANT_SPARSE_DIAGVAR if diag_var else VBMF_VARIANT_SPARSE_DIAG
-    c = Context(Y.shape[0], Y.shape[1], p.H, variant=variant, **_defaults)
+    c = Context(Y.shape[0], Y.shape[1], p.H, variant=model.diag_var if diag_var else model.diag, **_defaults)
     c.set_Y(Y)
     _sparse_sessions[key] = (c, weakref.ref(Y), fp)
     return c
-
-
-def _push_SigmaA(c, p, full_cov):
-    """full_cov on/off for the calls that follow, and the caller's SigmaA as it is: vbmf_sparse_set_state derives a diagonal
-    one from diagSigmaATVec, which is NOT what a fresh vbmf_sparse_init state holds (SigmaA = zeros beside
-    diagSigmaATVec = ones, src/vbmf_sparse.jl:120-123) nor what a full_cov state holds."""
-    c.sparse_set_full_cov(full_cov)
-    if p.SigmaA is not None:
-        c.sparse_set_SigmaA(np.asarray(p.SigmaA, dtype=np.float64))
 
 
 def _check_derived(p):
@@ -532,19 +544,45 @@ def _check_derived(p):
                              f"(src/vbmf_sparse.jl:131-143): set the hyper-prior instead")
 
 
-def _spush(c, p, diag_var=False, full_cov=False):
+def _alpha_not_derived(m, p):
+    """The sparse model's scalar alpha set to something other than alpha0 + 1/2 (src/vbmf_sparse.jl:131)."""
+    return m.labels and np.isscalar(p.alpha) and p.alpha != 0.0 and abs(p.alpha - (p.alpha0 + 0.5)) > 1e-12
+
+
+def _check_full_cov(full_cov, diag_var, H):
+    if full_cov and H > 256:
+        raise NotImplementedError("full_cov=true is built for H <= 256 (either noise model)")
+
+
+def _push(c, p, m, diag_var=False, full_cov=False):
+    """params -> device, in this order: the state, the grouped models' priors, full_cov on/off for the calls that follow, the
+    caller's SigmaA as it is (vbmf_sparse_set_state derives a diagonal one from diagSigmaATVec, which is NOT what a fresh init
+    state holds -- SigmaA = zeros beside diagSigmaATVec = ones, src/vbmf_sparse.jl:120-123 -- nor what a full_cov state holds),
+    and under diag_var the per-row noise."""
     _check_derived(p)
-    if np.isscalar(p.alpha) and p.alpha != 0.0 and abs(p.alpha - (p.alpha0 + 0.5)) > 1e-12:
+    if _alpha_not_derived(m, p):
         raise ValueError(f"params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131): set alpha0 instead")
-    hyper = dict(alpha0=p.alpha0, beta0=p.beta0, gamma0=p.gamma0, delta0=p.delta0, eta0=p.eta0, zeta0=p.zeta0)
-    c.sparse_set_state(p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta, p.BHat, p.SigmaB, p.CB, p.delta, p.sigmaHat,
-                       p.zeta, hyper, labels0=_labels0(p), H1=p.H1)
-    _push_SigmaA(c, p, full_cov)                                      # either noise model: the caller's SigmaA as it is
+    a0, b0, _ = m.groups[0]
+    hyper = dict(alpha0=getattr(p, a0), beta0=getattr(p, b0), gamma0=p.gamma0, delta0=p.delta0, eta0=p.eta0, zeta0=p.zeta0)
+    mask = dict(labels0=_labels0(p), H1=p.H1) if m.labels else {}
+    c.sparse_set_state(p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta, p.BHat, p.SigmaB, p.CB, p.delta, p.sigmaHat, p.zeta, hyper,
+                       **mask)
+    if m.set_priors is not None:
+        m.set_priors(c, p)
+    c.sparse_set_full_cov(full_cov)
+    if p.SigmaA is not None:
+        c.sparse_set_SigmaA(np.asarray(p.SigmaA, dtype=np.float64))
     if diag_var:
         c.sparse_set_noise_rows(p.sigmaVecHat, p.zetaVec, float(np.asarray(p.etaVec).reshape(-1)[0]))
 
 
-def _spull(c, p, diag_var=False):
+def _posterior_shapes(p, m):
+    return np.array([getattr(p, a) for _, _, a in m.groups])
+
+
+def _pull(c, p, m, diag_var=False):
+    """device -> params: the state, the group views, and the grouped models' priors as the last updateCA! left them (dual
+    :324-325).  Under diag_var the per-row noise replaces sigmaHat / zeta, which stay as they are."""
     s = c.sparse_get_state()
     if diag_var:
         p.sigmaVecHat, p.zetaVec = c.sparse_get_noise_rows()
@@ -554,106 +592,97 @@ def _spull(c, p, diag_var=False):
     p.BHat, p.SigmaB, p.CB, p.delta = s["BHat"], s["SigmaB"], s["CB"], s["delta"]
     if not diag_var:
         p.sigmaHat, p.zeta = s["sigmaHat"], s["zeta"]
+    if m.views is not None:
+        m.views(p)
+    if m.get_priors is not None:
+        for k, v in m.get_priors(c).items():
+            setattr(p, k, float(v))
+        p.alpha = _posterior_shapes(p, m)
 
 
-def _check_full_cov(full_cov, diag_var, H):
-    if full_cov and H > 256:
-        raise NotImplementedError("full_cov=true is built for H <= 256 (either noise model)")
+def _pushed(Y, p, diag_var=False, full_cov=False):
+    """The device context of p's model for Y (None: see _sparse_ctx) with p pushed into it: (context, model)."""
+    m = _MODELS[type(p)]
+    _check_full_cov(full_cov, diag_var, p.H)
+    c = _sparse_ctx(Y, p, diag_var, m)
+    _push(c, p, m, diag_var, full_cov)
+    return c, m
 
 
-def _sone(Y, p, which, diag_var=False, full_cov=False):
-    c = _sparse_ctx(Y, p, diag_var)
-    _spush(c, p, diag_var, full_cov)
+def _step(Y, p, which, diag_var=False, full_cov=False):
+    c, m = _pushed(Y, p, diag_var, full_cov)
     c.sparse_step(which)
-    _spull(c, p, diag_var)
+    _pull(c, p, m, diag_var)
+
+
+def _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors=True):
+    """vbmf_sparse! / vbmf_dual! / vbmf_trial!: returns d (like the reference)."""
+    c, m = _pushed(Y, params, diag_var, full_cov)
+    return _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run=lambda k: m.run(c, k, eps, est_cb, est_priors),
+                pull=lambda: _pull(c, params, m, diag_var), yhat=lambda: params.BHat @ params.AHat.T)   # host, small problems only
+
+
+def _on_deep_copy(fit, Y, params_in, niter, kw):
+    """vbmf_sparse / vbmf_dual / vbmf_trial: `fit` on a deep copy of params_in; returns (params, d)."""
+    p = _copy.deepcopy(params_in)
+    return p, fit(Y, p, niter, **kw)
+
+
+def _lower_bound(Y, p, clamp, trim=None):
+    c, _ = _pushed(Y, p)
+    return c.sparse_lower_bound(clamp=clamp) if trim is None else c.sparse_lower_bound_trimmed(trim, clamp=clamp)
+
+
+def _host_YHat(p):
+    return p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None
 
 
 def sparse_updateA_(Y, params, full_cov=False, diag_var=False):
     """updateA! -- src/vbmf_sparse.jl:176-247.  full_cov=true (:178-202): the M diagonal blocks of the reference's dense
     MH x MH covariance, inverted one per column on the device; SigmaATVec/invSigmaATVec are not materialised."""
-    _check_full_cov(full_cov, diag_var, params.H)
-    _sone(Y, params, SSTEP_A, diag_var, full_cov)
+    _step(Y, params, SSTEP_A, diag_var, full_cov)
 
 
 def sparse_updateB_(Y, params, diag_var=False):
     """updateB! -- src/vbmf_sparse.jl:254-268."""
-    _sone(Y, params, SSTEP_B, diag_var)
+    _step(Y, params, SSTEP_B, diag_var)
 
 
 def sparse_updateCA_(params, Y=None):
     """updateCA! -- src/vbmf_sparse.jl:284-288."""
-    _sone(Y, params, SSTEP_CA)
+    _step(Y, params, SSTEP_CA)
 
 
 def sparse_updateCB_(params, Y=None):
     """updateCB! -- src/vbmf_sparse.jl:295-300."""
-    _sone(Y, params, SSTEP_CB)
+    _step(Y, params, SSTEP_CB)
 
 
 def sparse_updateSigma_(Y, params, diag_var=False):
     """updateSigma! -- src/vbmf_sparse.jl:307-322 (diag_var: one Gamma posterior per row, :308-315)."""
-    _sone(Y, params, SSTEP_SIGMA, diag_var)
+    _step(Y, params, SSTEP_SIGMA, diag_var)
 
 
 def vbmf_sparse_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_cb=True,
                  log_every=1):
     """vbmf_sparse! -- src/vbmf_sparse.jl:344-410.  Returns d (like the reference).  logdir: see vbmf_."""
-    _check_full_cov(full_cov, diag_var, params.H)
-    c = _sparse_ctx(Y, params, diag_var)
-    _spush(c, params, diag_var, full_cov)
-    if logdir != "":
-        logVar = create_log(params)
-        i, d, iters = 1, eps + 1.0, 0
-        while i <= niter and d > eps:
-            k = int(min(max(1, log_every), niter - i + 1))
-            done, d, _ = c.sparse_run(k, eps=eps, est_cb=est_cb)
-            _spull(c, params, diag_var)
-            update_log_(logVar, params)
-            iters += done
-            i += done
-            if done < k:
-                break
-    else:
-        iters, d, _ = c.sparse_run(int(niter), eps=eps, est_cb=est_cb)
-        _spull(c, params, diag_var)
-    params.YHat = params.BHat @ params.AHat.T if params.L * params.M <= YHAT_AUTO_LIMIT else None   # :396 (host, small only)
-    if verb:
-        print(f"Factorization finished after {iters} iterations, eps = {d}")
-    if logdir != "":
-        save_log(logVar, Y, {}, logdir, desc=desc)
-    params._last_run = (iters, d)
-    return d
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every)
 
 
 def vbmf_sparse(Y, params_in, niter, **kw):
     """vbmf_sparse -- src/vbmf_sparse.jl:418-428: deep-copies params_in (:160-168), returns (params, d)."""
-    import copy as _copy
-    p = _copy.deepcopy(params_in)
-    d = vbmf_sparse_(Y, p, niter, **kw)
-    return p, d
+    return _on_deep_copy(vbmf_sparse_, Y, params_in, niter, kw)
 
 
 def lowerBound(Y, params, clamp=True):
     """lowerBound -- src/vbmf_sparse.jl:435-471."""
-    c = _sparse_ctx(Y, params)
-    _spush(c, params)
-    return c.sparse_lower_bound(clamp=clamp)
+    return _lower_bound(Y, params, clamp)
 
 
 def lowerBoundTrimmed(Y, params, trim=1e-1, clamp=True):
     """lowerBoundTrimmed -- src/vbmf_sparse.jl:478-489 (dual: src/vbmf_dual.jl:606-617, trial: src/vbmf_trial.jl:687-698): the
     bound without the entries of vec(A') with |ATVecHat| <= trim (the mask sits in front of the device's M*H-long sums)."""
-    if isinstance(params, vbmf_trial_parameters):
-        c = _sparse_ctx(Y, params, trial=True)
-        _tpush(c, params)
-    elif isinstance(params, vbmf_dual_parameters):
-        c = _sparse_ctx(Y, params, dual=True)
-        _dpush(c, params)
-    else:
-        c = _sparse_ctx(Y, params)
-        _spush(c, params)
-    return c.sparse_lower_bound_trimmed(trim, clamp=clamp)
-
+    return _lower_bound(Y, params, clamp, trim)
 
 # =================================================================================================
 # Two-group ARD variant -- src/vbmf_dual.jl with full_cov=false (either noise model)
@@ -714,168 +743,70 @@ def _dual_split(v, M, H, H0):
     return a[:, :H0].reshape(M * H0).copy(), a[:, H0:].reshape(M * (H - H0)).copy()
 
 
-def _dual_join(v0, v1, M, H, H0):
-    return np.concatenate([np.asarray(v0).reshape(M, H0), np.asarray(v1).reshape(M, H - H0)], axis=1).reshape(M * H)
-
-
 def vbmf_dual_init(Y, H, H0, ca=1.0, alpha0=1e-10, beta0=1e-10, cb=1.0, gamma0=1e-10, delta0=1e-10, sigma=1.0,
                    eta0=1e-10, zeta0=1e-10, rng=None):
     """src/vbmf_dual.jl:122-193 (host side)."""
     if H < H0:
         raise ValueError("H must be at least H0!")                        # :126-128
-    Y = np.asarray(Y)
-    rng = np.random.default_rng() if rng is None else rng
     p = vbmf_dual_parameters()
-    L, M = Y.shape
-    H, H0 = int(H), int(H0)
-    H1 = H - H0
-    p.L, p.M, p.H, p.MH, p.H0, p.H1 = L, M, H, M * H, H0, H1
-    p.AHat = rng.standard_normal((M, H))
-    p.ATVecHat = p.AHat.reshape(M * H).copy()
-    p.diagSigmaATVec = np.ones(M * H)
-    p.SigmaA = np.zeros((H, H))
-    p.A0Hat, p.A1Hat = p.AHat[:, :H0].copy(), p.AHat[:, H0:].copy()
-    p.BHat = rng.standard_normal((L, H))
-    p.SigmaB = np.zeros((H, H))
-    p.CA0, p.CA1 = ca * np.ones(M * H0), ca * np.ones(M * H1)
-    p.CA = _dual_join(p.CA0, p.CA1, M, H, H0)
-    p.alpha00 = p.alpha01 = alpha0
-    p.beta00 = p.beta01 = beta0
-    p.alpha0 = p.alpha1 = alpha0 + 0.5
-    p.beta0, p.beta1 = beta0 * np.ones(M * H0), beta0 * np.ones(M * H1)
-    p.alpha = np.array([p.alpha0, p.alpha1])
-    p.beta = _dual_join(p.beta0, p.beta1, M, H, H0)
-    p.CB = cb * np.ones(H)
-    p.gamma0, p.delta0, p.gamma, p.delta = gamma0, delta0, gamma0 + L / 2, delta0 * np.ones(H)
-    p.sigmaHat, p.eta0, p.zeta0, p.eta, p.zeta = float(sigma), eta0, zeta0, eta0 + L * M / 2, zeta0
-    p.sigmaVecHat, p.etaVec, p.zetaVec = sigma * np.ones(L), (eta0 + M / 2) * np.ones(L), zeta0 * np.ones(L)
-    p.YHat = p.BHat @ p.AHat.T if L * M <= YHAT_AUTO_LIMIT else None
-    p.trYTY = float(np.sum(Y * Y))
-    return p
+    p.L, p.M = np.shape(Y)
+    p.H, p.H0 = int(H), int(H0)
+    p.MH, p.H1 = p.M * p.H, p.H - p.H0
+    return _ard_init(p, Y, ca, alpha0, beta0, cb, gamma0, delta0, sigma, eta0, zeta0, rng)
 
 
-def _dpush(c, p, diag_var=False, full_cov=False):
-    _check_derived(p)
-    hyper = dict(alpha0=p.alpha00, beta0=p.beta00, gamma0=p.gamma0, delta0=p.delta0, eta0=p.eta0, zeta0=p.zeta0)
-    c.sparse_set_state(p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta, p.BHat, p.SigmaB, p.CB, p.delta, p.sigmaHat, p.zeta, hyper)
-    c.dual_set_priors(p.H0, p.alpha00, p.beta00, p.alpha01, p.beta01, p.alpha0, p.alpha1)
-    _push_SigmaA(c, p, full_cov)                                      # either noise model: the caller's SigmaA as it is
-    if diag_var:
-        c.sparse_set_noise_rows(p.sigmaVecHat, p.zetaVec, float(np.asarray(p.etaVec).reshape(-1)[0]))
-
-
-def _dpull(c, p, diag_var=False):
-    s = c.sparse_get_state()
-    if diag_var:
-        p.sigmaVecHat, p.zetaVec = c.sparse_get_noise_rows()
-    p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta = s["ATVecHat"], s["diagSigmaATVec"], s["CA"], s["beta"]
-    p.AHat = p.ATVecHat.reshape(p.M, p.H).copy()
+def _dual_views(p):
+    """The per-group copies of AHat, CA and beta (src/vbmf_dual.jl:146-165)."""
     p.A0Hat, p.A1Hat = p.AHat[:, :p.H0].copy(), p.AHat[:, p.H0:].copy()
     p.CA0, p.CA1 = _dual_split(p.CA, p.M, p.H, p.H0)
     p.beta0, p.beta1 = _dual_split(p.beta, p.M, p.H, p.H0)
-    p.SigmaA = np.ascontiguousarray(c.sparse_get_SigmaA())
-    p.BHat, p.SigmaB, p.CB, p.delta = s["BHat"], s["SigmaB"], s["CB"], s["delta"]
-    if not diag_var:
-        p.sigmaHat, p.zeta = s["sigmaHat"], s["zeta"]
-    return s
-
-
-def _dpull_priors(c, p):
-    """The four hyper-priors and the posterior shapes alpha0/alpha1 as the last updateCA! set them (:324-325)."""
-    _, pr = c.dual_get_priors()
-    p.alpha00, p.beta00, p.alpha01, p.beta01 = float(pr["alpha00"]), float(pr["beta00"]), float(pr["alpha01"]), float(pr["beta01"])
-    p.alpha0, p.alpha1 = float(pr["alpha0"]), float(pr["alpha1"])
-    p.alpha = np.array([p.alpha0, p.alpha1])
-
-
-def _done(Y, p, which, diag_var=False, full_cov=False):
-    c = _sparse_ctx(Y, p, diag_var, dual=True)
-    _dpush(c, p, diag_var, full_cov)
-    c.sparse_step(which)
-    _dpull(c, p, diag_var)
-    _dpull_priors(c, p)
 
 
 def dual_updateA_(Y, params, full_cov=False, diag_var=False):
     """updateA! -- src/vbmf_dual.jl:216-285 (full_cov=true, :218-243: per-column blocks, see sparse_updateA_)."""
-    _check_full_cov(full_cov, diag_var, params.H)
-    _done(Y, params, SSTEP_A, diag_var, full_cov)
+    _step(Y, params, SSTEP_A, diag_var, full_cov)
 
 
 def dual_updateB_(Y, params, diag_var=False):
     """updateB! -- src/vbmf_dual.jl:292-306."""
-    _done(Y, params, SSTEP_B, diag_var)
+    _step(Y, params, SSTEP_B, diag_var)
 
 
 def dual_updateCA_(params, Y=None):
     """updateCA! -- src/vbmf_dual.jl:322-351."""
-    _done(Y, params, SSTEP_CA)
+    _step(Y, params, SSTEP_CA)
 
 
 def dual_updateCB_(params, Y=None):
     """updateCB! -- src/vbmf_dual.jl:358-363."""
-    _done(Y, params, SSTEP_CB)
+    _step(Y, params, SSTEP_CB)
 
 
 def dual_updateSigma_(Y, params, diag_var=False):
     """updateSigma! -- src/vbmf_dual.jl:370-386 (diag_var: one Gamma posterior per row, :371-378)."""
-    _done(Y, params, SSTEP_SIGMA, diag_var)
+    _step(Y, params, SSTEP_SIGMA, diag_var)
 
 
 def dual_updateCA_and_priors_(params, Y=None):
     """updateCA! followed by updateAlpha00!, updateAlpha01!, updateBeta00!, updateBeta01! (src/vbmf_dual.jl:393-434):
     the fits read the group sums of the CA update, so the device does the pair in one call."""
-    _done(Y, params, SSTEP_CA | SSTEP_PRIORS)
+    _step(Y, params, SSTEP_CA | SSTEP_PRIORS)
 
 
 def vbmf_dual_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_priors=True,
                est_cb=True, log_every=1):
     """vbmf_dual! -- src/vbmf_dual.jl:455-530.  Returns d (like the reference).  logdir: see vbmf_."""
-    _check_full_cov(full_cov, diag_var, params.H)
-    c = _sparse_ctx(Y, params, diag_var, dual=True)
-    _dpush(c, params, diag_var, full_cov)
-    iters, d = 0, eps + 1.0
-    if logdir != "":
-        logVar = create_log(params)
-        i = 1
-        while i <= niter and d > eps:
-            k = int(min(max(1, log_every), niter - i + 1))
-            done, d, _ = c.dual_run(k, eps=eps, est_cb=est_cb, est_priors=est_priors)
-            _dpull(c, params, diag_var)
-            _dpull_priors(c, params)
-            update_log_(logVar, params)
-            iters += done
-            i += done
-            if done < k:
-                break
-    else:
-        iters, d, _ = c.dual_run(int(niter), eps=eps, est_cb=est_cb, est_priors=est_priors)
-        _dpull(c, params, diag_var)
-        _dpull_priors(c, params)
-    params.YHat = params.BHat @ params.AHat.T if params.L * params.M <= YHAT_AUTO_LIMIT else None   # :516
-    if verb:
-        print(f"Factorization finished after {iters} iterations, eps = {d}")
-    if logdir != "":
-        save_log(logVar, Y, {}, logdir, desc=desc)
-    params._last_run = (iters, d)
-    return d
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors)
 
 
 def vbmf_dual(Y, params_in, niter, **kw):
     """vbmf_dual -- src/vbmf_dual.jl:538-549: deep-copies params_in (:200-208), returns (params, d)."""
-    import copy as _copy
-    p = _copy.deepcopy(params_in)
-    d = vbmf_dual_(Y, p, niter, **kw)
-    return p, d
+    return _on_deep_copy(vbmf_dual_, Y, params_in, niter, kw)
 
 
 def lowerBound_dual(Y, params, clamp=True):
     """lowerBound(Y, ::vbmf_dual_parameters) -- src/vbmf_dual.jl:556-599."""
-    c = _sparse_ctx(Y, params, dual=True)
-    _dpush(c, params)
-    return c.sparse_lower_bound(clamp=clamp)
-
-
+    return _lower_bound(Y, params, clamp)
 # =================================================================================================
 # Three-group ARD variant -- src/vbmf_trial.jl with full_cov=false (either noise model)
 # =================================================================================================
@@ -943,161 +874,106 @@ def _trial_split(v, M, H, H0, M0):
     return (a[:, :H0].reshape(M * H0).copy(), a[:M0, H0:].reshape(M0 * H1).copy(), a[M0:, H0:].reshape((M - M0) * H1).copy())
 
 
-def _trial_join(v1, v2, v3, M, H, H0, M0):
-    H1 = H - H0
-    right = np.concatenate([np.asarray(v2).reshape(M0, H1), np.asarray(v3).reshape(M - M0, H1)], axis=0)
-    return np.concatenate([np.asarray(v1).reshape(M, H0), right], axis=1).reshape(M * H)
-
-
 def vbmf_trial_init(Y, H, H0, M0, ca=1.0, alpha0=1e-10, beta0=1e-10, cb=1.0, gamma0=1e-10, delta0=1e-10, sigma=1.0,
                     eta0=1e-10, zeta0=1e-10, rng=None):
     """src/vbmf_trial.jl:139-226 (host side)."""
     if H < H0:
         raise ValueError("H must be at least H0!")                        # :143-145
-    Y = np.asarray(Y)
-    rng = np.random.default_rng() if rng is None else rng
     p = vbmf_trial_parameters()
-    L, M = Y.shape
-    H, H0, M0 = int(H), int(H0), int(M0)
-    if not 0 <= M0 <= M:
+    p.L, p.M = np.shape(Y)
+    p.H, p.H0, p.M0 = int(H), int(H0), int(M0)
+    if not 0 <= p.M0 <= p.M:
         raise ValueError("M0 must lie in 0..M")
-    H1, M1 = H - H0, M - M0
-    p.L, p.M, p.H, p.MH, p.H0, p.H1, p.M0, p.M1 = L, M, H, M * H, H0, H1, M0, M1
-    p.AHat = rng.standard_normal((M, H))
-    p.ATVecHat = p.AHat.reshape(M * H).copy()
-    p.diagSigmaATVec = np.ones(M * H)
-    p.SigmaA = np.zeros((H, H))
-    p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, :H0].copy(), p.AHat[:M0, H0:].copy(), p.AHat[M0:, H0:].copy()
-    p.BHat = rng.standard_normal((L, H))
-    p.SigmaB = np.zeros((H, H))
-    p.CA1, p.CA2, p.CA3 = ca * np.ones(M * H0), ca * np.ones(M0 * H1), ca * np.ones(M1 * H1)
-    p.CA = _trial_join(p.CA1, p.CA2, p.CA3, M, H, H0, M0)
-    p.alpha01 = p.alpha02 = p.alpha03 = alpha0
-    p.beta01 = p.beta02 = p.beta03 = beta0
-    p.alpha1 = p.alpha2 = p.alpha3 = alpha0 + 0.5
-    p.beta1, p.beta2, p.beta3 = beta0 * np.ones(M * H0), beta0 * np.ones(M0 * H1), beta0 * np.ones(M1 * H1)
-    p.alpha = np.array([p.alpha1, p.alpha2, p.alpha3])
-    p.beta = _trial_join(p.beta1, p.beta2, p.beta3, M, H, H0, M0)
-    p.CB = cb * np.ones(H)
-    p.gamma0, p.delta0, p.gamma, p.delta = gamma0, delta0, gamma0 + L / 2, delta0 * np.ones(H)
-    p.sigmaHat, p.eta0, p.zeta0, p.eta, p.zeta = float(sigma), eta0, zeta0, eta0 + L * M / 2, zeta0
-    p.sigmaVecHat, p.etaVec, p.zetaVec = sigma * np.ones(L), (eta0 + M / 2) * np.ones(L), zeta0 * np.ones(L)
-    p.YHat = p.BHat @ p.AHat.T if L * M <= YHAT_AUTO_LIMIT else None
-    p.trYTY = float(np.sum(Y * Y))
-    return p
+    p.MH, p.H1, p.M1 = p.M * p.H, p.H - p.H0, p.M - p.M0
+    return _ard_init(p, Y, ca, alpha0, beta0, cb, gamma0, delta0, sigma, eta0, zeta0, rng)
 
 
-def _tpush(c, p, diag_var=False, full_cov=False):
-    _check_derived(p)
-    hyper = dict(alpha0=p.alpha01, beta0=p.beta01, gamma0=p.gamma0, delta0=p.delta0, eta0=p.eta0, zeta0=p.zeta0)
-    c.sparse_set_state(p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta, p.BHat, p.SigmaB, p.CB, p.delta, p.sigmaHat, p.zeta, hyper)
-    c.trial_set_priors(p.H0, p.M0, {k: getattr(p, k) for k in Context.TRIAL_KEYS})
-    _push_SigmaA(c, p, full_cov)                                      # either noise model: the caller's SigmaA as it is
-    if diag_var:
-        c.sparse_set_noise_rows(p.sigmaVecHat, p.zetaVec, float(np.asarray(p.etaVec).reshape(-1)[0]))
-
-
-def _tpull(c, p, diag_var=False):
-    s = c.sparse_get_state()
-    if diag_var:
-        p.sigmaVecHat, p.zetaVec = c.sparse_get_noise_rows()
-    p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta = s["ATVecHat"], s["diagSigmaATVec"], s["CA"], s["beta"]
-    p.AHat = p.ATVecHat.reshape(p.M, p.H).copy()
+def _trial_views(p):
+    """The per-group copies of AHat, CA and beta."""
     p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, :p.H0].copy(), p.AHat[:p.M0, p.H0:].copy(), p.AHat[p.M0:, p.H0:].copy()
     p.CA1, p.CA2, p.CA3 = _trial_split(p.CA, p.M, p.H, p.H0, p.M0)
     p.beta1, p.beta2, p.beta3 = _trial_split(p.beta, p.M, p.H, p.H0, p.M0)
-    p.SigmaA = np.ascontiguousarray(c.sparse_get_SigmaA())
-    p.BHat, p.SigmaB, p.CB, p.delta = s["BHat"], s["SigmaB"], s["CB"], s["delta"]
-    if not diag_var:
-        p.sigmaHat, p.zeta = s["sigmaHat"], s["zeta"]
-    _, _, pr = c.trial_get_priors()
-    for k, v in pr.items():
-        setattr(p, k, v)
-    p.alpha = np.array([p.alpha1, p.alpha2, p.alpha3])
-
-
-def _tone(Y, p, which, diag_var=False, full_cov=False):
-    c = _sparse_ctx(Y, p, diag_var, trial=True)
-    _tpush(c, p, diag_var, full_cov)
-    c.sparse_step(which)
-    _tpull(c, p, diag_var)
 
 
 def trial_updateA_(Y, params, full_cov=False, diag_var=False):
     """updateA! -- src/vbmf_trial.jl:250-320 (full_cov=true, :252-277: per-column blocks, see sparse_updateA_)."""
-    _check_full_cov(full_cov, diag_var, params.H)
-    _tone(Y, params, SSTEP_A, diag_var, full_cov)
+    _step(Y, params, SSTEP_A, diag_var, full_cov)
 
 
 def trial_updateB_(Y, params, diag_var=False):
     """updateB! -- src/vbmf_trial.jl:327-341."""
-    _tone(Y, params, SSTEP_B, diag_var)
+    _step(Y, params, SSTEP_B, diag_var)
 
 
 def trial_updateCA_(params, Y=None):
     """updateCA! -- src/vbmf_trial.jl:357-400."""
-    _tone(Y, params, SSTEP_CA)
+    _step(Y, params, SSTEP_CA)
 
 
 def trial_updateCB_(params, Y=None):
     """updateCB! -- src/vbmf_trial.jl:407-412."""
-    _tone(Y, params, SSTEP_CB)
+    _step(Y, params, SSTEP_CB)
 
 
 def trial_updateSigma_(Y, params, diag_var=False):
     """updateSigma! -- src/vbmf_trial.jl:419-435."""
-    _tone(Y, params, SSTEP_SIGMA, diag_var)
+    _step(Y, params, SSTEP_SIGMA, diag_var)
 
 
 def trial_updateCA_and_priors_(params, Y=None):
     """updateCA! followed by updateAlpha01!..03!, updateBeta01!..03! (src/vbmf_trial.jl:442-507)."""
-    _tone(Y, params, SSTEP_CA | SSTEP_PRIORS)
+    _step(Y, params, SSTEP_CA | SSTEP_PRIORS)
 
 
 def vbmf_trial_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_priors=True,
                 est_cb=True, log_every=1):
     """vbmf_trial! -- src/vbmf_trial.jl:528-604.  Returns d (like the reference).  logdir: see vbmf_."""
-    _check_full_cov(full_cov, diag_var, params.H)
-    c = _sparse_ctx(Y, params, diag_var, trial=True)
-    _tpush(c, params, diag_var, full_cov)
-    iters, d = 0, eps + 1.0
-    if logdir != "":
-        logVar = create_log(params)
-        i = 1
-        while i <= niter and d > eps:
-            k = int(min(max(1, log_every), niter - i + 1))
-            done, d, _ = c.trial_run(k, eps=eps, est_cb=est_cb, est_priors=est_priors)
-            _tpull(c, params, diag_var)
-            update_log_(logVar, params)
-            iters += done
-            i += done
-            if done < k:
-                break
-    else:
-        iters, d, _ = c.trial_run(int(niter), eps=eps, est_cb=est_cb, est_priors=est_priors)
-        _tpull(c, params, diag_var)
-    params.YHat = params.BHat @ params.AHat.T if params.L * params.M <= YHAT_AUTO_LIMIT else None   # :590
-    if verb:
-        print(f"Factorization finished after {iters} iterations, eps = {d}")
-    if logdir != "":
-        save_log(logVar, Y, {}, logdir, desc=desc)
-    params._last_run = (iters, d)
-    return d
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors)
 
 
 def vbmf_trial(Y, params_in, niter, **kw):
     """vbmf_trial -- src/vbmf_trial.jl:612-623: deep-copies params_in (:234-242), returns (params, d)."""
-    import copy as _copy
-    p = _copy.deepcopy(params_in)
-    d = vbmf_trial_(Y, p, niter, **kw)
-    return p, d
+    return _on_deep_copy(vbmf_trial_, Y, params_in, niter, kw)
 
 
 def lowerBound_trial(Y, params, clamp=True):
     """lowerBound(Y, ::vbmf_trial_parameters) -- src/vbmf_trial.jl:630-680."""
-    c = _sparse_ctx(Y, params, trial=True)
-    _tpush(c, params)
-    return c.sparse_lower_bound(clamp=clamp)
+    return _lower_bound(Y, params, clamp)
+
+
+# =================================================================================================
+# What differs between the ARD-sparse model and its grouped siblings; everything else is one code path (_push, _pull, _step,
+# _vbmf_ard, _lower_bound, vbls_, vbls_sparse_batch_) over the one vbmf_sparse_* device context
+# =================================================================================================
+@dataclass(frozen=True, eq=False)
+class _Model:
+    diag: int                              # variant id, one noise variance
+    diag_var: int                          # variant id, one noise variance per row of Y
+    groups: tuple                          # per ARD group: (hyper-prior shape, hyper-prior rate, posterior shape) field names;
+                                           # group 0 feeds alpha0 / beta0 of vbmf_sparse_hyper
+    run: Callable                          # (ctx, niter, eps, est_cb, est_priors) -> (sweeps done, d, trace)
+    labels: bool = False                   # sparse only: labels0 / H1 pushed, alpha == alpha0 + 1/2 checked
+    set_priors: Optional[Callable] = None  # (ctx, params)
+    get_priors: Optional[Callable] = None  # ctx -> {field: value}
+    views: Optional[Callable] = None       # params: the group views of AHat / CA / beta
+
+
+_MODELS = {
+    vbmf_sparse_parameters: _Model(
+        VBMF_VARIANT_SPARSE_DIAG, VBMF_VARIANT_SPARSE_DIAGVAR, (("alpha0", "beta0", "alpha"),), labels=True,
+        run=lambda c, k, eps, est_cb, est_priors: c.sparse_run(k, eps=eps, est_cb=est_cb)),
+    vbmf_dual_parameters: _Model(
+        VBMF_VARIANT_DUAL_DIAG, VBMF_VARIANT_DUAL_DIAGVAR, (("alpha00", "beta00", "alpha0"), ("alpha01", "beta01", "alpha1")),
+        run=lambda c, k, eps, est_cb, est_priors: c.dual_run(k, eps=eps, est_cb=est_cb, est_priors=est_priors),
+        set_priors=lambda c, p: c.dual_set_priors(p.H0, p.alpha00, p.beta00, p.alpha01, p.beta01, p.alpha0, p.alpha1),
+        get_priors=lambda c: c.dual_get_priors()[1], views=_dual_views),
+    vbmf_trial_parameters: _Model(
+        VBMF_VARIANT_TRIAL_DIAG, VBMF_VARIANT_TRIAL_DIAGVAR,
+        (("alpha01", "beta01", "alpha1"), ("alpha02", "beta02", "alpha2"), ("alpha03", "beta03", "alpha3")),
+        run=lambda c, k, eps, est_cb, est_priors: c.trial_run(k, eps=eps, est_cb=est_cb, est_priors=est_priors),
+        set_priors=lambda c, p: c.trial_set_priors(p.H0, p.M0, {k: getattr(p, k) for k in Context.TRIAL_KEYS}),
+        get_priors=lambda c: c.trial_get_priors()[2], views=_trial_views),
+}
 
 
 # =================================================================================================
@@ -1109,31 +985,13 @@ def vbls_(Y, params, niter, diag_var=False, full_cov=False):
     """vbls! -- examples/mil_util.jl:179-203: solves Y = B A' + E for A with B (and SigmaB, CB) fixed: niter x
     (updateA!, updateCA!, updateSigma2! / updateSigma!), then updateYHat!; returns params.AHat.
     On the device Y'B is formed once per call (B is fixed), so the call reads Y once, not 2 x niter times."""
-    if full_cov:
-        _check_full_cov(full_cov, diag_var, params.H)
-    if isinstance(params, vbmf_dual_parameters):                         # examples/mil_util.jl:190-193
-        c = _sparse_ctx(Y, params, diag_var, dual=True)
-        _dpush(c, params, diag_var, full_cov)
+    if type(params) in _MODELS:                                          # examples/mil_util.jl:187-197
+        c, m = _pushed(Y, params, diag_var, full_cov)
         c.sparse_run_fixed_basis(int(niter))
-        _dpull(c, params, diag_var)
-        _dpull_priors(c, params)
-        params.YHat = params.BHat @ params.AHat.T if params.L * params.M <= YHAT_AUTO_LIMIT else None
+        _pull(c, params, m, diag_var)
+        params.YHat = _host_YHat(params)
         return params.AHat
-    if isinstance(params, vbmf_trial_parameters):                        # examples/mil_util.jl:194-197
-        c = _sparse_ctx(Y, params, diag_var, trial=True)
-        _tpush(c, params, diag_var, full_cov)
-        c.sparse_run_fixed_basis(int(niter))
-        _tpull(c, params, diag_var)
-        params.YHat = params.BHat @ params.AHat.T if params.L * params.M <= YHAT_AUTO_LIMIT else None
-        return params.AHat
-    if isinstance(params, vbmf_sparse_parameters):
-        _check_full_cov(full_cov, diag_var, params.H)
-        c = _sparse_ctx(Y, params, diag_var)
-        _spush(c, params, diag_var, full_cov)
-        c.sparse_run_fixed_basis(int(niter))
-        _spull(c, params, diag_var)
-        params.YHat = params.BHat @ params.AHat.T if params.L * params.M <= YHAT_AUTO_LIMIT else None
-        return params.AHat
+    _check_full_cov(full_cov, diag_var, params.H)
     _check(Y, params)
     s = _session_for(Y, params.H)
     s.push(params)
@@ -1168,18 +1026,24 @@ def _batch_shapes(Ys, H, refuse=_batch_refuse):
     return Ls[0], Ms
 
 
+def _side_by_side(Ys, H, refuse):
+    """Bags (L x M_b matrices with one L, checked by _batch_shapes) laid side by side: (L, [M_b], column offsets, the
+    L x sum(M_b) matrix)."""
+    L, Ms = _batch_shapes(Ys, H, refuse)
+    col_off = np.concatenate([[0], np.cumsum(Ms)]).astype(np.int64)
+    Yall = np.empty((L, int(col_off[-1])), order="F")
+    for Y, c0, c1 in zip(Ys, col_off[:-1], col_off[1:]):
+        Yall[:, c0:c1] = Y
+    return L, Ms, col_off, Yall
+
+
 class Bags:
     """Many bags (L x M_b matrices with one L) uploaded side by side as ONE L x sum(M_b) matrix on the device, for vbls_batch_.
     One upload serves several bases: the MIL classifier runs every bag against two trained models (examples/mil_util.jl:473-479)."""
 
     def __init__(self, Ys, H):
-        self.L, self.Ms = _batch_shapes(Ys, H)
-        self.H = int(H)
-        self.col_off = np.concatenate([[0], np.cumsum(self.Ms)]).astype(np.int64)
-        self.M = int(self.col_off[-1])
-        Yall = np.empty((self.L, self.M), order="F")
-        for Y, c0, c1 in zip(Ys, self.col_off[:-1], self.col_off[1:]):
-            Yall[:, c0:c1] = Y
+        self.L, self.Ms, self.col_off, Yall = _side_by_side(Ys, H, _batch_refuse)
+        self.H, self.M = int(H), Yall.shape[1]
         self.session = Session(self.L, self.M, self.H)
         self.session.set_Y(Yall)
 
@@ -1188,7 +1052,6 @@ class Bags:
 
     def close(self):
         self.session.close()
-
 
 def _batch_check_params(L, Ms, H, params):
     if len(params) != len(Ms):
@@ -1239,7 +1102,7 @@ def vbls_batch_(Ys, params, niter):
         p.CA[idx, idx] = ca                                          # in place (src/vbmf.jl:131)
         p.invCA = np.diag(1.0 / ca)
         p.sigma2 = float(r["sigma2"][b])
-        p.YHat = p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None     # :201
+        p.YHat = _host_YHat(p)                                       # :201
         out.append(p.AHat)
     return out
 
@@ -1254,13 +1117,8 @@ class SparseBags:
     ctx_kw: Context options over the package defaults (e.g. reference_compat)."""
 
     def __init__(self, Ys, H, **ctx_kw):
-        self.L, self.Ms = _batch_shapes(Ys, H, _sbatch_refuse)
-        self.H = int(H)
-        self.col_off = np.concatenate([[0], np.cumsum(self.Ms)]).astype(np.int64)
-        self.M = int(self.col_off[-1])
-        Yall = np.empty((self.L, self.M), order="F")
-        for Y, c0, c1 in zip(Ys, self.col_off[:-1], self.col_off[1:]):
-            Yall[:, c0:c1] = Y
+        self.L, self.Ms, self.col_off, Yall = _side_by_side(Ys, H, _sbatch_refuse)
+        self.H, self.M = int(H), Yall.shape[1]
         self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **{**_defaults, **ctx_kw})
         self.ctx.set_Y(Yall)
 
@@ -1271,15 +1129,13 @@ class SparseBags:
         self.ctx.close()
 
 
-_SBATCH_TYPES = (vbmf_sparse_parameters, vbmf_dual_parameters, vbmf_trial_parameters)
-
-
 def _sbatch_check_params(L, Ms, H, params):
     if len(params) != len(Ms):
         _sbatch_refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
     p0 = params[0]
     kind = type(p0)
-    if kind not in _SBATCH_TYPES:
+    m = _MODELS.get(kind)
+    if m is None:
         _sbatch_refuse(f"{kind.__name__} (vbmf_sparse_parameters, vbmf_dual_parameters or vbmf_trial_parameters only)")
     for b, (p, M) in enumerate(zip(params, Ms)):
         if type(p) is not kind:
@@ -1288,7 +1144,7 @@ def _sbatch_check_params(L, Ms, H, params):
             _sbatch_refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
         if p.L != L or p.M != M:
             _sbatch_refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
-        if kind is vbmf_sparse_parameters and (int(p.H1) > 0 or np.asarray(p.labels).size > 0):
+        if m.labels and (int(p.H1) > 0 or np.asarray(p.labels).size > 0):
             _sbatch_refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
         if kind is vbmf_trial_parameters and int(p.M0) != M:
             _sbatch_refuse(f"bag {b}: trial set with M0 = {p.M0} != M = {M} (copy_vbmf_params gives M0 = M)")
@@ -1297,21 +1153,18 @@ def _sbatch_check_params(L, Ms, H, params):
         if p is not p0 and not (np.array_equal(p.BHat, p0.BHat) and np.array_equal(p.SigmaB, p0.SigmaB)):
             _sbatch_refuse(f"bag {b} does not share BHat and SigmaB with bag 0 (one fixed basis per call)")
         _check_derived(p)
-        if kind is vbmf_sparse_parameters and np.isscalar(p.alpha) and p.alpha != 0.0 and abs(p.alpha - (p.alpha0 + 0.5)) > 1e-12:
+        if _alpha_not_derived(m, p):
             _sbatch_refuse(f"bag {b}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
+    return m
 
 
-def _sbatch_priors(p, H):
+def _sbatch_priors(m, p, H):
     """updateCA!'s per-column (alpha_h, beta0_h) of one parameter set (src/vbmf_sparse.jl:284-288, src/vbmf_dual.jl:322-351,
     src/vbmf_trial.jl:357-400 with M0 = M: its third group is empty)."""
-    if isinstance(p, vbmf_dual_parameters):
-        g0, (a0, b0), (a1, b1) = p.H0, (p.alpha00, p.beta00), (p.alpha01, p.beta01)
-    elif isinstance(p, vbmf_trial_parameters):
-        g0, (a0, b0), (a1, b1) = p.H0, (p.alpha01, p.beta01), (p.alpha02, p.beta02)
-    else:
-        g0, (a0, b0), (a1, b1) = H, (p.alpha0, p.beta0), (p.alpha0, p.beta0)
-    h = np.arange(H)
-    return np.where(h < g0, a0, a1) + 0.5, np.where(h < g0, b0, b1).astype(np.float64)
+    (a0, b0, _), (a1, b1, _) = m.groups[0], m.groups[min(1, len(m.groups) - 1)]
+    first = np.arange(H) < getattr(p, "H0", H)
+    return (np.where(first, getattr(p, a0), getattr(p, a1)) + 0.5,
+            np.where(first, getattr(p, b0), getattr(p, b1)).astype(np.float64))
 
 
 def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
@@ -1330,19 +1183,18 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
         bags = Ys
         if bags.H != H:
             _sbatch_refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
-        _sbatch_check_params(bags.L, bags.Ms, H, params)
+        m = _sbatch_check_params(bags.L, bags.Ms, H, params)
     else:
         L, Ms = _batch_shapes(Ys, H, _sbatch_refuse)
-        _sbatch_check_params(L, Ms, H, params)
+        m = _sbatch_check_params(L, Ms, H, params)
         bags = SparseBags(Ys, H)
     try:
         p0 = params[0]
-        nb = len(params)
         ctx = bags.ctx
         zero = np.zeros(bags.M * H)
         hyper = dict(alpha0=1e-10, beta0=1e-10, gamma0=p0.gamma0, delta0=p0.delta0, eta0=p0.eta0, zeta0=p0.zeta0)
         ctx.sparse_set_state(zero, zero + 1.0, zero + 1.0, zero + 1.0, p0.BHat, p0.SigmaB, np.ones(H), np.ones(H), 1.0, 0.0, hyper)
-        pri = [_sbatch_priors(p, H) for p in params]
+        pri = [_sbatch_priors(m, p, H) for p in params]
         r = ctx.sparse_run_fixed_basis_batched(bags.col_off, int(niter), np.array([a for a, _ in pri]), np.array([b for _, b in pri]),
                                                [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
                                                [p.sigmaHat for p in params], np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1)
@@ -1353,25 +1205,17 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
     out = []
     for b, p in enumerate(params):
         s0, s1 = bags.col_off[b] * H, bags.col_off[b + 1] * H
-        M = p.M
         p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
         p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
-        p.AHat = p.ATVecHat.reshape(M, H).copy()
+        p.AHat = p.ATVecHat.reshape(p.M, H).copy()
         p.SigmaA = r["SigmaA"][b].copy()
         p.sigmaHat, p.zeta = float(r["sigmaHat"][b]), float(r["zeta"][b])
-        if isinstance(p, vbmf_dual_parameters):                         # _dpull, _dpull_priors
-            p.A0Hat, p.A1Hat = p.AHat[:, :p.H0].copy(), p.AHat[:, p.H0:].copy()
-            p.CA0, p.CA1 = _dual_split(p.CA, M, H, p.H0)
-            p.beta0, p.beta1 = _dual_split(p.beta, M, H, p.H0)
-            p.alpha0, p.alpha1 = p.alpha00 + 0.5, p.alpha01 + 0.5        # src/vbmf_dual.jl:324-325
-            p.alpha = np.array([p.alpha0, p.alpha1])
-        elif isinstance(p, vbmf_trial_parameters):                      # _tpull
-            p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, :p.H0].copy(), p.AHat[:p.M0, p.H0:].copy(), p.AHat[p.M0:, p.H0:].copy()
-            p.CA1, p.CA2, p.CA3 = _trial_split(p.CA, M, H, p.H0, p.M0)
-            p.beta1, p.beta2, p.beta3 = _trial_split(p.beta, M, H, p.H0, p.M0)
-            p.alpha1, p.alpha2, p.alpha3 = p.alpha01 + 0.5, p.alpha02 + 0.5, p.alpha03 + 0.5   # src/vbmf_trial.jl:359-361
-            p.alpha = np.array([p.alpha1, p.alpha2, p.alpha3])
-        p.YHat = p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None     # :201
+        if m.views is not None:                                         # what _pull fills, the priors as updateCA! sets them:
+            m.views(p)                                                  # src/vbmf_dual.jl:324-325, src/vbmf_trial.jl:359-361
+            for a0, _, a in m.groups:
+                setattr(p, a, getattr(p, a0) + 0.5)
+            p.alpha = _posterior_shapes(p, m)
+        p.YHat = _host_YHat(p)                                          # :201
         out.append(p.AHat)
     return out
 
