@@ -213,22 +213,53 @@ __device__ __forceinline__ void split3_frag(const float4& x0, const float4& x1, 
 __device__ __forceinline__ f32x16 mfma_bf(const uint4& a, const uint4& b, const f32x16& c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
+// gram_prod's W / D plane fragments travel as native vectors: a uint4 (HIP_vector_type) array copied into LDS or out of it was
+// kept in scratch
+__device__ __forceinline__ f32x16 mfma_bf(const u32x4v& a, const uint4& b, const f32x16& c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
 
 // [P | Q] = G [W | D], split-K.  Workgroup b: row group b % nrg (4 waves x NXW row tiles), k-steps [s sps, (s + 1) sps) of split
 // s = b / nrg.  Out: slab s at Out + s * slab_floats, P fragment-major (tiles x < XT1) followed by Q at Out + s * slab_floats + n.
-// Each wave loads its G fragments one k-step ahead and reads the W / D planes (5 NH fragments per k-step, small and shared by every
-// workgroup) from L2.  Measured alternatives at 100k x 10k, H = 64 (this kernel: 0.157-0.162 ms): the planes shared through LDS (one
-// load per workgroup, a barrier per k-step) 0.26 ms; a three-deep G ring plus the planes one k-step ahead 0.178 ms; twice the split-K
-// workgroups (two waves per SIMD) 0.157 ms.
+//
+// Pipeline.  G is the only stream a wave waits for inside the k-loop: each wave keeps its own G fragments GramProd::D k-steps ahead in
+// a register ring (slot = k-step mod D, static because the loop body is unrolled over U = max(D, CH) k-steps), and refills a slot
+// right after it has been split into bf16 parts.  The W / D planes (5 NH fragments per k-step, the same for every wave of the
+// workgroup) go through LDS, double-buffered by chunks of CH k-steps: at the first k-step of chunk c the workgroup's 256 threads
+// load chunk c + 1 in full lines, before that k-step's G loads, so the wait for them at the chunk's last k-step retires no G load that
+// is still ahead; they are written to the other buffer there, and one barrier per chunk publishes it.  The waves read their plane
+// fragments with ds_read_b128.  Loads past the split's end are clamped to its last k-step (always in bounds, never branched round);
+// the k-steps they stand for do no MFMA.  Every accumulator sees the MFMA sequence of the one-k-step-ahead kernel this replaced (term
+// order, k-step order, split plan), so [P | Q] is bitwise what it was.
+// Measured at 100k x 10k, H = 64 (config 4, H = 128, in brackets): this kernel 0.133 ms (0.252 ms).  The compiled loop still copies
+// the ring back into its registers at the back edge and waits vmcnt(0) there, once per U k-steps.
+// Alternatives: the one-k-step-ahead kernel this replaced, G and the planes read straight to registers, 0.154-0.162 ms (0.446 ms;
+// vmcnt(0) every k-step); its planes shared through LDS with a barrier per k-step 0.26 ms; a three-deep G ring with the planes
+// read from L2 one k-step ahead 0.178 ms; twice the split-K workgroups (two waves per SIMD) 0.157 ms.
+template <int NH>
+struct GramProd {
+    static constexpr int NXW = 4 / NH;                        // row tiles per wave
+    static constexpr int CH = 4;                              // k-steps per plane chunk (one barrier each)
+    static constexpr int D = 4;                               // G ring depth in k-steps: 32-128 KB of G in flight per CU
+    static constexpr int U = D > CH ? D : CH;                 // k-steps per unrolled loop body
+    static constexpr int CHUNK_U4 = GRAM_PLANES * CH * NH * 64;   // one chunk of planes, 16-byte units
+    static constexpr int STAGE = CHUNK_U4 / 256;              // per thread
+    static constexpr int LDS_BYTES = 2 * CHUNK_U4 * 16;       // 40 / 80 / 160 KB
+    static_assert(U % D == 0 && U % CH == 0 && CHUNK_U4 % 256 == 0, "gram_prod pipeline geometry");
+};
 template <int NH, int NXW>
 __global__ __launch_bounds__(256) void gram_prod_kernel(const float4* __restrict__ Gt, const uint4* __restrict__ Wt,
                                                         float* __restrict__ Out, int GT, int XT1, int sps, int nrg, long long n,
                                                         long long slab_floats, const int* __restrict__ stop) {
+    using C = GramProd<NH>;
+    static_assert(C::NXW == NXW, "gram_prod instantiation");
+    constexpr int D = C::D, CH = C::CH, U = C::U, STAGE = C::STAGE, CHUNK_U4 = C::CHUNK_U4;
+    extern __shared__ u32x4v gram_planes[];                    // [buffer][plane][k-step of the chunk][h tile][lane]
     if (*stop) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int rg = blockIdx.x % nrg, s = blockIdx.x / nrg;
     const int KT = 2 * GT;
-    const int j0 = s * sps, j1 = min(j0 + sps, KT);
+    const int j0 = s * sps, j1 = min(j0 + sps, KT), nk = j1 - j0;
     const int pt0 = (rg * 4 + w) * NXW;
     const long long plane = (long long)KT * NH * 64;
     f32x16 accP[NXW][NH], accQ[NXW][NH];
@@ -238,46 +269,98 @@ __global__ __launch_bounds__(256) void gram_prod_kernel(const float4* __restrict
         for (int h = 0; h < NH; ++h)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { accP[i][h][r] = 0.f; accQ[i][h][r] = 0.f; }
-    const float4* gp[NXW];
+    const f32x4* gp[NXW];
 #pragma unroll
-    for (int i = 0; i < NXW; ++i) gp[i] = Gt + (((long long)(pt0 + i) * KT) * 64 + lane) * 2;
-    float4 gn[NXW][2];
+    for (int i = 0; i < NXW; ++i) gp[i] = reinterpret_cast<const f32x4*>(Gt) + (((long long)(pt0 + i) * KT) * 64 + lane) * 2;
+    f32x4 ring[D][NXW][2];                                    // native vectors, as the planes: float4 copies lost the coalescing
+    auto load_g = [&](f32x4 (&slot)[NXW][2], int t) {        // k-step j0 + t, clamped to the split
+        const long long o = (long long)min(j0 + t, j1 - 1) * 128;
 #pragma unroll
-    for (int i = 0; i < NXW; ++i) { gn[i][0] = gp[i][(long long)j0 * 128]; gn[i][1] = gp[i][(long long)j0 * 128 + 1]; }
-    for (int j = j0; j < j1; ++j) {
-        float4 gc[NXW][2];
+        for (int i = 0; i < NXW; ++i) { slot[i][0] = gp[i][o]; slot[i][1] = gp[i][o + 1]; }
+    };
+    // the planes of the chunk starting at k-step j0 + t, in [plane][k-step][h tile][lane] order: thread x holds units x + 256 u
+    auto plane_src = [&](int u, int t) -> const u32x4v* {
+        const int x = threadIdx.x + 256 * u;
+        const int q = x / (CH * NH * 64), r = x % (CH * NH * 64);
+        const int j = min(j0 + t + r / (NH * 64), j1 - 1);
+        return reinterpret_cast<const u32x4v*>(Wt) + q * plane + (long long)j * NH * 64 + r % (NH * 64);
+    };
+    {
+        u32x4v st[STAGE];
 #pragma unroll
-        for (int i = 0; i < NXW; ++i) { gc[i][0] = gn[i][0]; gc[i][1] = gn[i][1]; }
-        if (j + 1 < j1) {
+        for (int u = 0; u < STAGE; ++u) st[u] = *plane_src(u, 0);
 #pragma unroll
-            for (int i = 0; i < NXW; ++i) { gn[i][0] = gp[i][(long long)(j + 1) * 128]; gn[i][1] = gp[i][(long long)(j + 1) * 128 + 1]; }
-        }
-        uint4 wf[GRAM_PLANES][NH];
+        for (int d = 0; d < D; ++d) load_g(ring[d], d);
 #pragma unroll
-        for (int q = 0; q < GRAM_PLANES; ++q)
-#pragma unroll
-            for (int h = 0; h < NH; ++h) wf[q][h] = Wt[q * plane + ((long long)j * NH + h) * 64 + lane];
-#pragma unroll
-        for (int i = 0; i < NXW; ++i) {
-            uint4 g0, g1, g2;
-            split3_frag(gc[i][0], gc[i][1], g0, g1, g2);
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                // smallest terms first: W2 G0, W1 G1, W0 G2, W1 G0, W0 G1, W0 G0
-                f32x16 a = accP[i][h];
-                a = mfma_bf(wf[2][h], g0, a);
-                a = mfma_bf(wf[1][h], g1, a);
-                a = mfma_bf(wf[0][h], g2, a);
-                a = mfma_bf(wf[1][h], g0, a);
-                a = mfma_bf(wf[0][h], g1, a);
-                accP[i][h] = mfma_bf(wf[0][h], g0, a);
-                f32x16 d = accQ[i][h];
-                d = mfma_bf(wf[4][h], g0, d);
-                d = mfma_bf(wf[3][h], g1, d);
-                accQ[i][h] = mfma_bf(wf[3][h], g0, d);
-            }
-        }
+        for (int u = 0; u < STAGE; ++u) gram_planes[threadIdx.x + 256 * u] = st[u];
+        __syncthreads();
     }
+    // U k-steps from t0 (a multiple of U): chunk c of them loads the planes of the chunk after it at its first k-step, before that
+    // k-step's G loads, and stores them into the other buffer after its last k-step; ring slot u % D is refilled with k-step t + D
+    // as soon as it has been split.  live: k-steps at or past nk do no MFMA.
+    auto body = [&](int t0, bool tail) {
+#pragma unroll
+        for (int c = 0; c < U / CH; ++c) {
+            const int cc = ((t0 + c * CH) / CH) & 1;
+            u32x4v st[STAGE];
+#pragma unroll
+            for (int kk = 0; kk < CH; ++kk) {
+                const int u = c * CH + kk, t = t0 + u;
+                const bool live = !tail || t < nk;
+                u32x4v wf[GRAM_PLANES][NH];
+                if (live) {
+                    const u32x4v* pl = gram_planes + cc * CHUNK_U4 + kk * NH * 64 + lane;
+#pragma unroll
+                    for (int q = 0; q < GRAM_PLANES; ++q)
+#pragma unroll
+                        for (int h = 0; h < NH; ++h) wf[q][h] = pl[(q * CH * NH + h) * 64];
+                }
+                uint4 g[NXW][3];
+#pragma unroll
+                for (int i = 0; i < NXW; ++i) {
+                    const f32x4 x0 = ring[u % D][i][0], x1 = ring[u % D][i][1];
+                    split3_frag(make_float4(x0.x, x0.y, x0.z, x0.w), make_float4(x1.x, x1.y, x1.z, x1.w), g[i][0], g[i][1], g[i][2]);
+                }
+                // Scheduling fences: each k-step's loads stay where they are issued, the ring slot's refill after its split (left
+                // to itself the scheduler issued the refills early into fresh registers and sank them to the end of the loop body,
+                // where copying them back into the ring waited for every load: vmcnt(0)).  The plane reads and the split of a
+                // k-step still overlap the MFMAs of the one before.
+                __builtin_amdgcn_sched_barrier(0);
+                if (kk == 0) {
+#pragma unroll
+                    for (int v = 0; v < STAGE; ++v) st[v] = *plane_src(v, t + CH);
+                }
+                load_g(ring[u % D], t + D);
+                __builtin_amdgcn_sched_barrier(0);
+                if (live) {
+#pragma unroll
+                    for (int i = 0; i < NXW; ++i) {
+#pragma unroll
+                        for (int h = 0; h < NH; ++h) {
+                            // smallest terms first: W2 G0, W1 G1, W0 G2, W1 G0, W0 G1, W0 G0
+                            f32x16 a = accP[i][h];
+                            a = mfma_bf(wf[2][h], g[i][0], a);
+                            a = mfma_bf(wf[1][h], g[i][1], a);
+                            a = mfma_bf(wf[0][h], g[i][2], a);
+                            a = mfma_bf(wf[1][h], g[i][0], a);
+                            a = mfma_bf(wf[0][h], g[i][1], a);
+                            accP[i][h] = mfma_bf(wf[0][h], g[i][0], a);
+                            f32x16 d = accQ[i][h];
+                            d = mfma_bf(wf[4][h], g[i][0], d);
+                            d = mfma_bf(wf[3][h], g[i][1], d);
+                            accQ[i][h] = mfma_bf(wf[3][h], g[i][0], d);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < STAGE; ++v) gram_planes[(cc ^ 1) * CHUNK_U4 + threadIdx.x + 256 * v] = st[v];
+            __syncthreads();
+        }
+    };
+    int t0 = 0;
+    for (; t0 + U <= nk; t0 += U) body(t0, false);
+    if (t0 < nk) body(t0, true);
     float4* oP = reinterpret_cast<float4*>(Out + (long long)s * slab_floats);
     float4* oQ = reinterpret_cast<float4*>(Out + (long long)s * slab_floats + n);
 #pragma unroll
