@@ -193,174 +193,229 @@ __global__ __launch_bounds__(HP * 4) void gram_w_kernel(const float* __restrict_
     }
 }
 
-// three bf16 parts of 8 fp32 values as MFMA operand fragments
-__device__ __forceinline__ void split3_frag(const float4& x0, const float4& x1, uint4& g0, uint4& g1, uint4& g2) {
+// a - b as one v_sub_f32.  Written out because the compiler packs neighbouring fp32 subtractions into v_pk_add_f32, which beside
+// MFMAs costs more than the two scalar instructions it replaces; the result is the same IEEE difference.
+__device__ __forceinline__ float sub_f32(float a, float b) {
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// two fp32 values rounded to bf16 (RNE) in one v_cvt_pk_bf16_f32: lo in bits 0..15, hi in bits 16..31
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2v;
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+    const f32x2v v = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
+}
+// three bf16 parts of 8 fp32 values as MFMA operand fragments: x = p0 + p1 + p2 to an fp32 rounding, each part the RNE bf16 of what
+// the parts before it left.  Pairs stay packed as the conversion leaves them: the high half is unpacked by one v_and_b32, the low
+// half by one v_lshlrev_b32.
+__device__ __forceinline__ void split3_frag(const f32x4& x0, const f32x4& x1, u32x4v& g0, u32x4v& g1, u32x4v& g2) {
     const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    unsigned short p[3][8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        p[0][e] = f2bf(v[e]);
-        float r = v[e] - bf2f(p[0][e]);
-        p[1][e] = f2bf(r);
-        r -= bf2f(p[1][e]);
-        p[2][e] = f2bf(r);
+    for (int e = 0; e < 4; ++e) {
+        float a = v[2 * e], b = v[2 * e + 1];
+        const unsigned p0 = cvt_pk_bf16(a, b);
+        a = sub_f32(a, bitsf(p0 << 16));
+        b = sub_f32(b, bitsf(p0 & 0xffff0000u));
+        const unsigned p1 = cvt_pk_bf16(a, b);
+        a = sub_f32(a, bitsf(p1 << 16));
+        b = sub_f32(b, bitsf(p1 & 0xffff0000u));
+        g0[e] = p0;
+        g1[e] = p1;
+        g2[e] = cvt_pk_bf16(a, b);
     }
-    g0 = make_uint4(pack_bf2(p[0][0], p[0][1]), pack_bf2(p[0][2], p[0][3]), pack_bf2(p[0][4], p[0][5]), pack_bf2(p[0][6], p[0][7]));
-    g1 = make_uint4(pack_bf2(p[1][0], p[1][1]), pack_bf2(p[1][2], p[1][3]), pack_bf2(p[1][4], p[1][5]), pack_bf2(p[1][6], p[1][7]));
-    g2 = make_uint4(pack_bf2(p[2][0], p[2][1]), pack_bf2(p[2][2], p[2][3]), pack_bf2(p[2][4], p[2][5]), pack_bf2(p[2][6], p[2][7]));
 }
 
-__device__ __forceinline__ f32x16 mfma_bf(const uint4& a, const uint4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// gram_prod's W / D plane fragments travel as native vectors: a uint4 (HIP_vector_type) array copied into LDS or out of it was
-// kept in scratch
-__device__ __forceinline__ f32x16 mfma_bf(const u32x4v& a, const uint4& b, const f32x16& c) {
+__device__ __forceinline__ f32x16 mfma_bf(const u32x4v& a, const u32x4v& b, const f32x16& c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-// [P | Q] = G [W | D], split-K.  Workgroup b: row group b % nrg (4 waves x NXW row tiles), k-steps [s sps, (s + 1) sps) of split
+// [P | Q] = G [W | D], split-K.  Workgroup b: row group b % nrg (TPG = 16 / NH row tiles), k-steps [s sps, (s + 1) sps) of split
 // s = b / nrg.  Out: slab s at Out + s * slab_floats, P fragment-major (tiles x < XT1) followed by Q at Out + s * slab_floats + n.
 //
-// Pipeline.  G is the only stream a wave waits for inside the k-loop: each wave keeps its own G fragments GramProd::D k-steps ahead in
-// a register ring (slot = k-step mod D, static because the loop body is unrolled over U = max(D, CH) k-steps), and refills a slot
-// right after it has been split into bf16 parts.  The W / D planes (5 NH fragments per k-step, the same for every wave of the
-// workgroup) go through LDS, double-buffered by chunks of CH k-steps: at the first k-step of chunk c the workgroup's 256 threads
-// load chunk c + 1 in full lines, before that k-step's G loads, so the wait for them at the chunk's last k-step retires no G load that
-// is still ahead; they are written to the other buffer there, and one barrier per chunk publishes it.  The waves read their plane
-// fragments with ds_read_b128.  Loads past the split's end are clamped to its last k-step (always in bounds, never branched round);
-// the k-steps they stand for do no MFMA.  Every accumulator sees the MFMA sequence of the one-k-step-ahead kernel this replaced (term
-// order, k-step order, split plan), so [P | Q] is bitwise what it was.
-// Measured at 100k x 10k, H = 64 (config 4, H = 128, in brackets): this kernel 0.133 ms (0.252 ms).  The compiled loop still copies
-// the ring back into its registers at the back edge and waits vmcnt(0) there, once per U k-steps.
-// Alternatives: the one-k-step-ahead kernel this replaced, G and the planes read straight to registers, 0.154-0.162 ms (0.446 ms;
-// vmcnt(0) every k-step); its planes shared through LDS with a barrier per k-step 0.26 ms; a three-deep G ring with the planes
-// read from L2 one k-step ahead 0.178 ms; twice the split-K workgroups (two waves per SIMD) 0.157 ms.
+// Geometry.  NW = 8 waves, two per SIMD: while one wave splits its G fragment into bf16 parts (vector ALU) or waits for a load, the
+// other keeps the SIMD's matrix pipe busy.  Wave w takes NXW = TPG / 8 row tiles with all NH h tiles (NH = 1, 2); at NH = 4 the
+// row group has four tiles, so waves w and w + 4 share tile w % 4 and take two h tiles each (both stream and split that tile's G).
+//
+// Pipeline.  Nothing the k-loop loads passes through registers: G and the W / D planes arrive by LDS-DMA in 1 KB pieces (one
+// wave-instruction each, lds_dma_piece), so no load result is carried round the loop edge and every wait is a counted vmcnt that
+// the source states.  G: each wave owns a ring of D slots of its own fragments (2 NXW pieces per k-step, LDS image = memory image,
+// lane l's 32 bytes at 32 l), filled D k-steps ahead; slot t % D is refilled with k-step t + D right after k-step t has been read
+// out of it and split.  The wait before reading k-step t leaves the D - 1 younger k-steps (and any plane pieces issued among them)
+// in flight.  No other wave reads the ring, so it needs no barrier.  Planes: 5 NH pieces per k-step, the same for every wave,
+// double-buffered by chunks of CH k-steps; the workgroup's waves issue chunk c + 1 (PPW pieces each; where 5 NH CH is no multiple
+// of 8 the last piece is issued more than once so that every wave counts the same loads) at the first k-step of chunk c, wait for
+// them after its last k-step with the G refills issued since still in flight, and one raw s_barrier per chunk publishes them
+// (__syncthreads would drain vmcnt).  The prologue issues the same sequence the loop would have issued for k-steps -D .. -1, so
+// the loop's wait counts hold from its first trip.  Loads past the split's end are clamped to its last k-step (always in bounds,
+// never branched round); the k-steps they stand for do no MFMA.  Every DMA is waited for before the workgroup's LDS is given up.
+// Every accumulator sees the MFMA sequence of the kernels this replaced (term order, k-step order, split plan), so [P | Q] is
+// bitwise what it was.
+// Measured at 100k x 10k, H = 64 (config 4, 1M x 10k, H = 128, in brackets; roofline.pass1 of the bench, parent and this build
+// alternated on one machine, profiles/gram_prod_overlap_bench_ab.txt): 0.119-0.120 ms (0.201-0.204 ms); the kernel this replaced,
+// G in a register ring and four waves per workgroup, 0.130-0.131 ms (0.249-0.251 ms).  Its counters (profiles/gram_prod_overlap_*): the matrix pipe was busy for 50 % of a
+// wave's life, the wave parked at a wait or barrier for 16 % only; the rest was its own vector work, issued between the MFMA
+// blocks and not beside them.  With two waves per SIMD the pipe is busy for 63 %.
+// Tried on this kernel in an earlier alternated run (this form 0.118-0.119 ms there, the parent 0.134 ms), all within 1 % of it
+// at the headline and therefore not kept: a ring five k-steps deep (all 160 KB of
+// LDS) 0.119 ms (0.206-0.207 ms); waves 4-7 rotated by half a k-step, so that SIMD partners alternate between split and MFMAs
+// from every barrier on, 0.118-0.119 ms (0.205-0.206 ms); the k-step's DMA pieces issued between its MFMAs (sched_group_barrier,
+// one per two to six MFMAs) instead of ahead of them 0.119 ms (0.213-0.214 ms).  None of ring depth, barrier lockstep or the
+// place of the DMA issue is what bounds it now.
 template <int NH>
 struct GramProd {
-    static constexpr int NXW = 4 / NH;                        // row tiles per wave
-    static constexpr int CH = 4;                              // k-steps per plane chunk (one barrier each)
-    static constexpr int D = 4;                               // G ring depth in k-steps: 32-128 KB of G in flight per CU
-    static constexpr int U = D > CH ? D : CH;                 // k-steps per unrolled loop body
-    static constexpr int CHUNK_U4 = GRAM_PLANES * CH * NH * 64;   // one chunk of planes, 16-byte units
-    static constexpr int STAGE = CHUNK_U4 / 256;              // per thread
-    static constexpr int LDS_BYTES = 2 * CHUNK_U4 * 16;       // 40 / 80 / 160 KB
-    static_assert(U % D == 0 && U % CH == 0 && CHUNK_U4 % 256 == 0, "gram_prod pipeline geometry");
+    static constexpr int NW = 8;                              // waves per workgroup
+    static constexpr int THREADS = 64 * NW;
+    static constexpr int TPG = 16 / NH;                       // row tiles per row group (the split plan's unit: gram_prepare)
+    static constexpr int NXW = TPG >= NW ? TPG / NW : 1;      // row tiles per wave
+    static constexpr int HS = TPG >= NW ? 1 : NW / TPG;       // waves sharing a row tile
+    static constexpr int NHW = NH / HS;                       // h tiles per wave
+    static constexpr int CH = NH == 2 ? 4 : 2;                // k-steps per plane chunk (one barrier each)
+    static constexpr int D = 4;                               // G ring depth in k-steps (slot = k-step mod D, a scalar counter)
+    static constexpr int U = CH;                              // k-steps per unrolled loop body
+    static constexpr int NP = GRAM_PLANES * CH * NH;          // 1 KB pieces of one plane chunk
+    static constexpr int PPW = (NP + NW - 1) / NW;            // plane pieces a wave issues per chunk
+    static constexpr int GL = 2 * NXW;                        // G pieces a wave issues per k-step
+    static constexpr int PLANE_BYTES = 2 * NP * 1024;         // 20 / 80 / 80 KB
+    static constexpr int RING_BYTES = NW * D * GL * 1024;     // 128 / 64 / 64 KB
+    static constexpr int LDS_BYTES = PLANE_BYTES + RING_BYTES;
+    static_assert(NXW * (NW / HS) == TPG && NHW * HS == NH, "gram_prod geometry");
+    static_assert(LDS_BYTES <= 160 * 1024, "gram_prod LDS");
+    // loads a wave has issued after the G pieces of k-step t (t mod U = u) by the time it reads them: the G refills of the D - 1
+    // k-steps t - D + 1 .. t - 1 and the plane pieces issued at those of them that open a chunk
+    static constexpr int g_wait(int u) {
+        int n = (D - 1) * GL;
+        for (int d = 1; d < D; ++d) n += ((u + CH * D - d) % CH == 0) ? PPW : 0;
+        return n;
+    }
 };
-template <int NH, int NXW>
-__global__ __launch_bounds__(256) void gram_prod_kernel(const float4* __restrict__ Gt, const uint4* __restrict__ Wt,
-                                                        float* __restrict__ Out, int GT, int XT1, int sps, int nrg, long long n,
-                                                        long long slab_floats, const int* __restrict__ stop) {
+template <int NH>
+__global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const float4* __restrict__ Gt, const uint4* __restrict__ Wt,
+                                                                          float* __restrict__ Out, int GT, int XT1, int sps, int nrg,
+                                                                          long long n, long long slab_floats,
+                                                                          const int* __restrict__ stop) {
     using C = GramProd<NH>;
-    static_assert(C::NXW == NXW, "gram_prod instantiation");
-    constexpr int D = C::D, CH = C::CH, U = C::U, STAGE = C::STAGE, CHUNK_U4 = C::CHUNK_U4;
-    extern __shared__ u32x4v gram_planes[];                    // [buffer][plane][k-step of the chunk][h tile][lane]
+    constexpr int NW = C::NW, NXW = C::NXW, NHW = C::NHW, D = C::D, CH = C::CH, U = C::U, NP = C::NP, PPW = C::PPW, GL = C::GL;
+    extern __shared__ __attribute__((aligned(1024))) unsigned char gram_lds[];   // [2][plane][k-step of the chunk][h tile] 1 KB, then [wave][slot][tile][2] 1 KB
     if (*stop) return;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int rg = blockIdx.x % nrg, s = blockIdx.x / nrg;
     const int KT = 2 * GT;
     const int j0 = s * sps, j1 = min(j0 + sps, KT), nk = j1 - j0;
-    const int pt0 = (rg * 4 + w) * NXW;
+    const int pt0 = rg * C::TPG + (w % (C::TPG / NXW)) * NXW;          // first row tile of this wave
+    const int h0 = (w / (C::TPG / NXW)) * NHW;                        // first h tile of this wave
     const long long plane = (long long)KT * NH * 64;
-    f32x16 accP[NXW][NH], accQ[NXW][NH];
+    f32x16 accP[NXW][NHW], accQ[NXW][NHW];
 #pragma unroll
     for (int i = 0; i < NXW; ++i)
 #pragma unroll
-        for (int h = 0; h < NH; ++h)
+        for (int h = 0; h < NHW; ++h)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { accP[i][h][r] = 0.f; accQ[i][h][r] = 0.f; }
-    const f32x4* gp[NXW];
+    // one descriptor per row tile (its KT k-steps of 2 KB) and one for the planes: a load is range-checked against its own array
+    __amdgpu_buffer_rsrc_t gr[NXW];
 #pragma unroll
-    for (int i = 0; i < NXW; ++i) gp[i] = reinterpret_cast<const f32x4*>(Gt) + (((long long)(pt0 + i) * KT) * 64 + lane) * 2;
-    f32x4 ring[D][NXW][2];                                    // native vectors, as the planes: float4 copies lost the coalescing
-    auto load_g = [&](f32x4 (&slot)[NXW][2], int t) {        // k-step j0 + t, clamped to the split
-        const long long o = (long long)min(j0 + t, j1 - 1) * 128;
+    for (int i = 0; i < NXW; ++i)
+        gr[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(Gt + (long long)(pt0 + i) * KT * 128), 0, (unsigned)KT * 2048u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)Wt, 0, (unsigned)(GRAM_PLANES * plane * 16), 0x00020000);
+    const int voff = lane * 16;
+    unsigned char* const ring = gram_lds + C::PLANE_BYTES + w * (D * GL * 1024);
+    auto load_g = [&](int slot, int t) __attribute__((always_inline)) {      // k-step j0 + t, clamped to the split
+        const int so = min(j0 + t, j1 - 1) * 2048;
 #pragma unroll
-        for (int i = 0; i < NXW; ++i) { slot[i][0] = gp[i][o]; slot[i][1] = gp[i][o + 1]; }
+        for (int i = 0; i < NXW; ++i) {
+            lds_dma_piece(gr[i], ring + (slot * GL + 2 * i) * 1024, voff, so);
+            lds_dma_piece(gr[i], ring + (slot * GL + 2 * i + 1) * 1024, voff, so + 1024);
+        }
     };
-    // the planes of the chunk starting at k-step j0 + t, in [plane][k-step][h tile][lane] order: thread x holds units x + 256 u
-    auto plane_src = [&](int u, int t) -> const u32x4v* {
-        const int x = threadIdx.x + 256 * u;
-        const int q = x / (CH * NH * 64), r = x % (CH * NH * 64);
-        const int j = min(j0 + t + r / (NH * 64), j1 - 1);
-        return reinterpret_cast<const u32x4v*>(Wt) + q * plane + (long long)j * NH * 64 + r % (NH * 64);
+    // this wave's pieces of the plane chunk starting at k-step j0 + t into buffer cc: piece x = (plane q, k-step kk, h tile h)
+    auto load_planes = [&](int cc, int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int v = 0; v < PPW; ++v) {
+            const int x = min(w + NW * v, NP - 1);
+            const int q = x / (CH * NH), r = x % (CH * NH);
+            const int j = min(j0 + t + r / NH, j1 - 1);
+            lds_dma_piece(wr, gram_lds + (cc * NP + x) * 1024, voff, (int)(q * plane + ((long long)j * NH + r % NH) * 64) * 16);
+        }
     };
-    {
-        u32x4v st[STAGE];
+    // the sequence the loop issues at k-steps -D .. -1: chunk 0's planes (at each chunk start among them; the same bytes to the same
+    // place) and G k-steps 0 .. D - 1
 #pragma unroll
-        for (int u = 0; u < STAGE; ++u) st[u] = *plane_src(u, 0);
-#pragma unroll
-        for (int d = 0; d < D; ++d) load_g(ring[d], d);
-#pragma unroll
-        for (int u = 0; u < STAGE; ++u) gram_planes[threadIdx.x + 256 * u] = st[u];
-        __syncthreads();
+    for (int d = 0; d < D; ++d) {
+        if ((d + CH * D - D) % CH == 0) load_planes(0, 0);
+        load_g(d, d);
     }
-    // U k-steps from t0 (a multiple of U): chunk c of them loads the planes of the chunk after it at its first k-step, before that
-    // k-step's G loads, and stores them into the other buffer after its last k-step; ring slot u % D is refilled with k-step t + D
-    // as soon as it has been split.  live: k-steps at or past nk do no MFMA.
-    auto body = [&](int t0, bool tail) {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CH * GL) : "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    u32x4v wf[GRAM_PLANES][NHW], g[NXW][3];
+    auto mma = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int c = 0; c < U / CH; ++c) {
-            const int cc = ((t0 + c * CH) / CH) & 1;
-            u32x4v st[STAGE];
+        for (int i = 0; i < NXW; ++i) {
 #pragma unroll
-            for (int kk = 0; kk < CH; ++kk) {
-                const int u = c * CH + kk, t = t0 + u;
-                const bool live = !tail || t < nk;
-                u32x4v wf[GRAM_PLANES][NH];
-                if (live) {
-                    const u32x4v* pl = gram_planes + cc * CHUNK_U4 + kk * NH * 64 + lane;
+            for (int h = 0; h < NHW; ++h) {
+                // smallest terms first: W2 G0, W1 G1, W0 G2, W1 G0, W0 G1, W0 G0
+                f32x16 a = accP[i][h];
+                a = mfma_bf(wf[2][h], g[i][0], a);
+                a = mfma_bf(wf[1][h], g[i][1], a);
+                a = mfma_bf(wf[0][h], g[i][2], a);
+                a = mfma_bf(wf[1][h], g[i][0], a);
+                a = mfma_bf(wf[0][h], g[i][1], a);
+                accP[i][h] = mfma_bf(wf[0][h], g[i][0], a);
+                f32x16 d = accQ[i][h];
+                d = mfma_bf(wf[4][h], g[i][0], d);
+                d = mfma_bf(wf[3][h], g[i][1], d);
+                accQ[i][h] = mfma_bf(wf[3][h], g[i][0], d);
+            }
+        }
+    };
+    int slot = 0;                                             // ring slot of the current k-step
+    // U k-steps from t0 (a multiple of U).  tail: k-steps at or past nk do no MFMA (their loads and waits still run).
+    auto body = [&](int t0, bool tail) __attribute__((always_inline)) {
 #pragma unroll
-                    for (int q = 0; q < GRAM_PLANES; ++q)
-#pragma unroll
-                        for (int h = 0; h < NH; ++h) wf[q][h] = pl[(q * CH * NH + h) * 64];
-                }
-                uint4 g[NXW][3];
+        for (int u = 0; u < U; ++u) {
+            const int t = t0 + u, kk = u % CH;
+            const int cc = (t / CH) & 1;
+            const bool live = !tail || t < nk;
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::g_wait(u)) : "memory");
+            if (live) {
+                const unsigned char* gs = ring + slot * (GL * 1024) + lane * 32;
+                f32x4 x[NXW][2];
 #pragma unroll
                 for (int i = 0; i < NXW; ++i) {
-                    const f32x4 x0 = ring[u % D][i][0], x1 = ring[u % D][i][1];
-                    split3_frag(make_float4(x0.x, x0.y, x0.z, x0.w), make_float4(x1.x, x1.y, x1.z, x1.w), g[i][0], g[i][1], g[i][2]);
+                    x[i][0] = *reinterpret_cast<const f32x4*>(gs + i * 2048);
+                    x[i][1] = *reinterpret_cast<const f32x4*>(gs + i * 2048 + 16);
                 }
-                // Scheduling fences: each k-step's loads stay where they are issued, the ring slot's refill after its split (left
-                // to itself the scheduler issued the refills early into fresh registers and sank them to the end of the loop body,
-                // where copying them back into the ring waited for every load: vmcnt(0)).  The plane reads and the split of a
-                // k-step still overlap the MFMAs of the one before.
-                __builtin_amdgcn_sched_barrier(0);
-                if (kk == 0) {
+                const unsigned char* pl = gram_lds + (cc * NP + kk * NH + h0) * 1024 + lane * 16;
 #pragma unroll
-                    for (int v = 0; v < STAGE; ++v) st[v] = *plane_src(v, t + CH);
-                }
-                load_g(ring[u % D], t + D);
-                __builtin_amdgcn_sched_barrier(0);
-                if (live) {
+                for (int q = 0; q < GRAM_PLANES; ++q)
 #pragma unroll
-                    for (int i = 0; i < NXW; ++i) {
+                    for (int h = 0; h < NHW; ++h) wf[q][h] = *reinterpret_cast<const u32x4v*>(pl + (q * CH * NH + h) * 1024);
 #pragma unroll
-                        for (int h = 0; h < NH; ++h) {
-                            // smallest terms first: W2 G0, W1 G1, W0 G2, W1 G0, W0 G1, W0 G0
-                            f32x16 a = accP[i][h];
-                            a = mfma_bf(wf[2][h], g[i][0], a);
-                            a = mfma_bf(wf[1][h], g[i][1], a);
-                            a = mfma_bf(wf[0][h], g[i][2], a);
-                            a = mfma_bf(wf[1][h], g[i][0], a);
-                            a = mfma_bf(wf[0][h], g[i][1], a);
-                            accP[i][h] = mfma_bf(wf[0][h], g[i][0], a);
-                            f32x16 d = accQ[i][h];
-                            d = mfma_bf(wf[4][h], g[i][0], d);
-                            d = mfma_bf(wf[3][h], g[i][1], d);
-                            accQ[i][h] = mfma_bf(wf[3][h], g[i][0], d);
-                        }
-                    }
-                }
+                for (int i = 0; i < NXW; ++i) split3_frag(x[i][0], x[i][1], g[i][0], g[i][1], g[i][2]);
             }
-#pragma unroll
-            for (int v = 0; v < STAGE; ++v) gram_planes[(cc ^ 1) * CHUNK_U4 + threadIdx.x + 256 * v] = st[v];
-            __syncthreads();
+            // the slot is refilled only after its fragments have arrived in registers (the split has consumed them)
+            __builtin_amdgcn_sched_barrier(0);
+            if (kk == 0) load_planes(cc ^ 1, t + CH);
+            load_g(slot, t + D);
+            slot = slot + 1 == D ? 0 : slot + 1;
+            __builtin_amdgcn_sched_barrier(0);
+            if (live) mma();
+            if (kk == CH - 1) {
+                // my pieces of the next chunk have landed (the G refills issued since stay in flight) and my reads of this chunk's
+                // buffer have returned; after the barrier everybody's have, and the next chunk's first k-step may refill the buffer
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(CH * GL) : "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
         }
     };
     int t0 = 0;
     for (; t0 + U <= nk; t0 += U) body(t0, false);
     if (t0 < nk) body(t0, true);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // run-ahead pieces still target this workgroup's LDS
     float4* oP = reinterpret_cast<float4*>(Out + (long long)s * slab_floats);
     float4* oQ = reinterpret_cast<float4*>(Out + (long long)s * slab_floats + n);
 #pragma unroll
@@ -368,8 +423,8 @@ __global__ __launch_bounds__(256) void gram_prod_kernel(const float4* __restrict
         const int p = pt0 + i;
         if (p >= XT1) continue;
 #pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const long long o = (((long long)p * NH + h) * 64 + lane) * 4;
+        for (int h = 0; h < NHW; ++h) {
+            const long long o = (((long long)p * NH + h0 + h) * 64 + lane) * 4;
             const f32x16 a = accP[i][h], d = accQ[i][h];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {

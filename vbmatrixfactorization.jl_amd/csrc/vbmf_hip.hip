@@ -1016,8 +1016,7 @@ static int gram_prepare(vbmf_ctx* c) {
     if (!c->Gt) {
         c->GT = (int)rup(c->d1.XT, 16);
         const int KT = 2 * c->GT;
-        const int nxw = c->NH == 4 ? 1 : (c->NH == 2 ? 2 : 4);                 // = the gram_prod_kernel instantiations below
-        c->g_nrg = c->GT / (4 * nxw);
+        c->g_nrg = c->GT / (16 / c->NH);                                       // row groups of GramProd<NH>::TPG row tiles
         // split-K: about one workgroup per CU, each split at least 8 k-steps
         c->g_nsplit = std::max(1, std::min(KT / 8, NUM_CU / std::max(1, c->g_nrg)));
         c->g_sps = cdiv(KT, c->g_nsplit);
@@ -1094,9 +1093,9 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     const dim3 grid(c->g_nrg * c->g_nsplit);
     const float4* G4 = reinterpret_cast<const float4*>(c->Gt);
     prof_begin(c, 0);
-    if (c->NH == 1) hipLaunchKernelGGL((gram_prod_kernel<1, 4>), grid, dim3(256), GramProd<1>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    else if (c->NH == 2) hipLaunchKernelGGL((gram_prod_kernel<2, 2>), grid, dim3(256), GramProd<2>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    else hipLaunchKernelGGL((gram_prod_kernel<4, 1>), grid, dim3(256), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    if (c->NH == 1) hipLaunchKernelGGL((gram_prod_kernel<1>), grid, dim3(GramProd<1>::THREADS), GramProd<1>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    else if (c->NH == 2) hipLaunchKernelGGL((gram_prod_kernel<2>), grid, dim3(GramProd<2>::THREADS), GramProd<2>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    else hipLaunchKernelGGL((gram_prod_kernel<4>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
     prof_end(c);
     HIPCHK(c, hipGetLastError());
     if (c->g_nsplit > 1) {
@@ -1557,13 +1556,13 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<8, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
         if (e == hipSuccess && c->NH == 8)
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<8, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-        // the Gram-form product's double-buffered W / D planes (40 / 80 / 160 KB at NH = 1 / 2 / 4)
+        // the Gram-form product's W / D plane buffers and G rings (148 / 144 / 144 KB at NH = 1 / 2 / 4)
         if (e == hipSuccess && c->NH == 1)
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<1>::LDS_BYTES);
+            e = hipFuncSetAttribute((const void*)gram_prod_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<1>::LDS_BYTES);
         if (e == hipSuccess && c->NH == 2)
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<2>::LDS_BYTES);
+            e = hipFuncSetAttribute((const void*)gram_prod_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<2>::LDS_BYTES);
         if (e == hipSuccess && c->NH == 4)
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<4>::LDS_BYTES);
+            e = hipFuncSetAttribute((const void*)gram_prod_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<4>::LDS_BYTES);
         if (e != hipSuccess) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return bail(VBMF_ERR_HIP); }
     }
     // the zero-fills above ran on the null stream; all later work runs on a non-blocking stream
