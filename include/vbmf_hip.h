@@ -212,6 +212,38 @@ int vbmf_sparse_lower_bound(vbmf_ctx* ctx, int clamp, double* lb);
  * are not trimmed there either, so for them only MH, the CA-weighted second moment and H(vec(A')) change).
  * The comparison runs on the device's fp32 copy of ATVecHat. */
 int vbmf_sparse_lower_bound_trimmed(vbmf_ctx* ctx, int clamp, double trim, double* lb);
+
+/* ---- per-bag scoring: what the MIL classifier compares after a batched vbls! (examples/mil_util.jl:469-530) ----
+ * The context's Y is the bags side by side (col_off as in vbmf_run_fixed_basis_batched).  Both entries refuse, with VBMF_ERR_INVALID
+ * and before any launch: col_off not running from 0 to M or not increasing (an empty bag), a *_DIAGVAR context, nranks > 1, a NULL
+ * required pointer.  A non-finite sum in a bag returns VBMF_ERR_NUMERIC and vbmf_last_error names the bag.  The context's state is
+ * not changed by either call.
+ *
+ * vbmf_bag_residuals: r2[b] = ||Y_b - BHat*AHat_b'||_F^2, the square of norm(Y - BHat*AHat') of examples/mil_util.jl:476-479 (and of
+ * norm(YHat - Y), :518-521), for every bag.  Formed entry by entry in fp64 from Y as stored (what vbmf_get_Y returns), the context's
+ * BHat as stored (vbmf_set_state / vbmf_sparse_set_state keep it in fp32: the values vbmf_get_state returns) and the caller's fp64
+ * AHat (M x H column-major, ldA >= M) -- never from the trace form ||Y||^2 - 2 tr(B'YA) + tr(A'A B'B), whose cancellation costs the
+ * digits the comparison between two models needs.  Basic and sparse-family contexts, any H up to 1024. */
+int vbmf_bag_residuals(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, const double* AHat, int64_t ldA, double* r2);
+/* lowerBound (src/vbmf_sparse.jl:435-471; dual src/vbmf_dual.jl:556-599; trial src/vbmf_trial.jl:630-680) for trim < 0 and
+ * lowerBoundTrimmed (src/vbmf_sparse.jl:478-489; dual :606-617; trial :687-698) for trim >= 0 of every bag, as called per bag by
+ * examples/mil_util.jl:502-514.  Sparse-family context, homoscedastic, one fixed basis: BHat, SigmaB, CB, delta and the hyper-priors
+ * gamma0, delta0 (with gamma = gamma0 + L/2) from vbmf_sparse_set_state.  Per bag, laid out as vbmf_sparse_run_fixed_basis_batched
+ * leaves them: ATVecHat, diagSigmaATVec, CA, beta (M*H, vec(A') order), SigmaA (nbags*H*H), sigmaHat, zeta (nbags); eta, eta0, zeta0
+ * (nbags: the noise precision's Gamma posterior shape and prior); a_pri, b_pri, a_post (nbags*H): the Gamma hyper-prior (shape, rate)
+ * and the posterior shape of the ARD precisions of column h of A -- one pair for the sparse model, per column group for the dual and
+ * trial models (a trial set with M0 = M_b, what copy_vbmf_params gives: its third group is empty).
+ * grouped = 0: the sparse model's lowerBoundTrimmed, which trims beta and CA with ATVecHat (src/vbmf_sparse.jl:482-486); != 0: the
+ * grouped models', whose per-group fields stay whole (see vbmf_sparse_lower_bound_trimmed).  The mask |ATVecHat| > trim runs on the
+ * fp32 rounding of ATVecHat, like that entry's.  clamp as in vbmf_sparse_lower_bound.
+ * Data term: r2 + L tr(A'A SigmaB) + tr(SigmaA (B'B + L SigmaB)) with r2 the direct residual of vbmf_bag_residuals formed in the same
+ * call -- algebraically the reference's ||Y||^2 - 2 tr(B'YA) + tr((A'A + SigmaA)(B'B + L SigmaB)) (:439-440) without its cancellation.
+ * Out: lb[nbags]; r2[nbags] (may be NULL). */
+int vbmf_sparse_lower_bound_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int clamp, double trim, int grouped,
+                                    const double* ATVecHat, const double* diagSigmaATVec, const double* CA, const double* beta,
+                                    const double* SigmaA, const double* sigmaHat, const double* zeta, const double* eta,
+                                    const double* eta0, const double* zeta0, const double* a_pri, const double* b_pri,
+                                    const double* a_post, double* lb, double* r2);
 /* full_cov = true of updateA! (src/vbmf_sparse.jl:178-202; dual :218-243; trial :252-277).  The reference's dense MH x MH
  * invSigmaATVec = sigmaHat*kron(I_M, B'B + L*SigmaB) + diag(CA) is block diagonal, so the device inverts the M H x H blocks
  * (one workgroup per column of Y) and never forms it: diagSigmaATVec = the blocks' diagonals, SigmaA = their sum (a full

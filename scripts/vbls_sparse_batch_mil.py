@@ -9,7 +9,12 @@ vbls_ are timed on the first 128 bags of a case at most (per-bag vbls_ in the di
 refuses one column under the QS1 layout); the oracle's full_cov form (a dense M H x M H inverse) only up to M H = 1600,
 the classifier's own gate (examples/mil_util.jl:393-416).
     python scripts/vbls_sparse_batch_mil.py              (GPU box, repo root)
-    python scripts/vbls_sparse_batch_mil.py --profile    (the 1024-bag batched calls only: run it under rocprofv3 --kernel-trace --stats)"""
+    python scripts/vbls_sparse_batch_mil.py --profile    (the 1024-bag batched calls only: run it under rocprofv3 --kernel-trace --stats)
+    python scripts/vbls_sparse_batch_mil.py --score a|b  (the whole classifier step, examples/mil_util.jl:453-535, on 256 bags of
+        166 x 30 at H = 5 against two models, per bag amortised, one warm-up and five timed windows per classifier.  a: the batched
+        fits, then the scores one bag at a time -- NumPy residuals, lowerBound / lowerBoundTrimmed through a context per bag; it uses
+        nothing newer than the batched fits, so it also runs on a build without the scoring entries.  b: classify_batch.  With
+        --profile: three classify_batch calls per classifier and no timing, for rocprofv3 --kernel-trace --stats)"""
 import os
 import sys
 import time
@@ -86,8 +91,105 @@ def relA(a, b):
     return np.linalg.norm(a.ATVecHat - b.ATVecHat) / np.linalg.norm(b.ATVecHat)
 
 
+def score_models(L, H, H1):
+    """two trained models per family (bags come alternately from their bases), as the package's types"""
+    rng = np.random.default_rng(11)
+    Bs = [rng.standard_normal((L, H)) * np.linspace(1.0, 2.5, H) for _ in range(2)]
+
+    def draw(k, m):
+        As = np.zeros((m, H)); As[np.arange(m), rng.integers(0, H, m)] = 1.0
+        return Bs[k] @ As.T + 0.05 * rng.standard_normal((L, m))
+
+    def twin(cls, res):
+        out = cls()
+        for f in out.__dataclass_fields__:
+            if hasattr(res, f):
+                v = getattr(res, f)
+                setattr(out, f, v.copy() if isinstance(v, np.ndarray) else v)
+        return out
+    models = {"vbls": [], "dual": [], "lower_bound": []}
+    for k in range(2):
+        Ytr = draw(k, 400)
+        r = O.vbmf_init(Ytr, H, ca=0.1, cb=0.1, sigma2=0.1, rng=np.random.default_rng(3 + k), materialize_yhat=False)
+        O.vbmf_(Ytr, r, 15, eps=0.0, est_covs=True, est_var=True)
+        b = twin(pkg.vbmf_parameters, r)
+        b.labels = np.zeros(0, dtype=np.int64)
+        models["vbls"].append(b)
+        r = O.vbmf_dual_init(Ytr, H, max(1, H // 2), rng=np.random.default_rng(5 + k), materialize_yhat=False)
+        O.vbmf_dual_(Ytr, r, 20, eps=0.0, est_priors=False)
+        models["dual"].append(twin(pkg.vbmf_dual_parameters, r))
+        r = O.vbmf_sparse_init(Ytr, H, rng=np.random.default_rng(7 + k), full_cov=False, materialize_yhat=False)
+        O.vbmf_sparse_(Ytr, r, 20, eps=0.0)
+        s = twin(pkg.vbmf_sparse_parameters, r)
+        s.H1 = H1
+        models["lower_bound"].append(s)
+    return models, draw
+
+
+def classify_per_bag_scores(res0, res1, Ys, alg, threshold=1e-1):
+    """classify over many bags with the batched fits and the scores one bag at a time (what a build without the scoring entries does)"""
+    L = Ys[0].shape[0]
+    if alg == "lower_bound":
+        H, H0 = res0.H, res0.H - res0.H1
+        ps0 = []
+        for Y in Ys:
+            p = pkg.vbmf_sparse_init(Y, H0)
+            p.BHat, p.SigmaB, p.CB = res0.BHat[:, :H0].copy(), res0.SigmaB[:H0, :H0].copy(), res0.CB[:H0].copy()
+            p.gamma, p.delta = res0.gamma, res0.delta[:H0].copy()
+            ps0.append(p)
+        ps1 = [pkg.copy_vbmf_params(Y, res0) for Y in Ys]
+        full_cov = Ys[0].shape[1] * H0 < 1600                          # (one bag size here: one group)
+        pkg.vbls_sparse_batch_(Ys, ps0, 20, full_cov=full_cov)
+        pkg.vbls_sparse_batch_(Ys, ps1, 20, full_cov=full_cov)
+        e0 = np.array([pkg.lowerBound(Y, p) for Y, p in zip(Ys, ps0)])
+        e1 = np.array([pkg.lowerBoundTrimmed(Y, p, threshold) for Y, p in zip(Ys, ps1)])
+        return (e1 > e0).astype(np.int64), e0, e1
+    errs = []
+    bags = pkg.Bags(Ys, res0.H) if alg == "vbls" else pkg.SparseBags(Ys, res0.H)
+    for res in (res0, res1):
+        ps = [pkg.copy_vbmf_params(Y, res) for Y in Ys]
+        if alg == "vbls":
+            pkg.vbls_batch_(bags, ps, 150)
+        else:
+            pkg.vbls_sparse_batch_(bags, ps, 20, full_cov=True)
+        errs.append(np.array([np.linalg.norm(Y - p.BHat @ p.AHat.T) for Y, p in zip(Ys, ps)]))
+    bags.close()
+    if alg == "vbls":
+        return (errs[0] > errs[1]).astype(np.int64), errs[0], errs[1]
+    e0, e1 = errs[0] / (L * Ys[0].shape[1]), errs[1] / (L * Ys[0].shape[1])
+    return np.where(e0 < e1, 0, 1), e0, e1
+
+
+def score_main(how, prof):
+    L, M, H, H1, nb = 166, 30, 5, 2, 256
+    models, draw = score_models(L, H, H1)
+    Ys = [draw(b % 2, M).astype(np.float32).astype(np.float64) for b in range(nb)]
+    print(f"# classify over {nb} bags of {L} x {M} at H = {H}, two models, per BAG amortised (ms): "
+          + ("(a) batched fits, scores one bag at a time" if how == "a" else "(b) classify_batch"))
+    print(f"{'classifier':12s} {'median':>9s} {'min':>9s} {'max':>9s} {'label 1':>8s}")
+    for alg in ("vbls", "dual", "lower_bound"):
+        res0, res1 = models[alg]
+        run = ((lambda: classify_per_bag_scores(res0, res1, Ys, alg)) if how == "a"
+               else (lambda: pkg.classify_batch(res0, res1, Ys, alg)))
+        labels, _, _ = run()                                            # warm-up: library, kernels, allocator
+        if prof:
+            for _ in range(3):
+                run()
+            print(f"profiled: 3 x classify_batch {alg}")
+            continue
+        ts = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            run()
+            ts.append((time.perf_counter() - t0) / nb * 1e3)
+        pkg.invalidate()
+        print(f"{alg:12s} {np.median(ts):9.4f} {min(ts):9.4f} {max(ts):9.4f} {int(np.sum(labels)):8d}")
+
+
 def main():
     prof = "--profile" in sys.argv
+    if "--score" in sys.argv:
+        return score_main(sys.argv[sys.argv.index("--score") + 1], prof)
     rng = np.random.default_rng(7)
     cases = [("L=166 M=6 H=2", 166, 400, [6] * 40, 2), ("L=166 M=30 H=5", 166, 400, [30] * 40, 5),
              ("L=230 M=60 H=10", 230, 600, [60] * 30, 10), ("L=1000 M=200 H=10", 1000, 2000, [200] * 10, 10),

@@ -46,7 +46,8 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "dual_updateB_", "dual_updateCA_", "dual_updateCB_", "dual_updateSigma_", "dual_updateCA_and_priors_",
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
-           "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags"]
+           "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags",
+           "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
 # elements the field is left None and computed on demand with updateYHat_ (8 GB at 100k x 10k).
@@ -1053,22 +1054,22 @@ class Bags:
     def close(self):
         self.session.close()
 
-def _batch_check_params(L, Ms, H, params):
+def _batch_check_params(L, Ms, H, params, refuse=_batch_refuse):
     if len(params) != len(Ms):
-        _batch_refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
+        refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
     p0 = params[0]
     for b, (p, M) in enumerate(zip(params, Ms)):
         if type(p) is not vbmf_parameters:
-            _batch_refuse(f"bag {b}: {type(p).__name__} (the basic model's vbmf_parameters only)")
+            refuse(f"bag {b}: {type(p).__name__} (the basic model's vbmf_parameters only)")
         if int(p.H) != H:
-            _batch_refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
+            refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
         if p.L != L or p.M != M:
-            _batch_refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
+            refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
         if int(p.H1) > 0 or np.asarray(p.labels).size > 0:
-            _batch_refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
+            refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
         if p is not p0 and not (np.array_equal(p.BHat, p0.BHat) and np.array_equal(p.SigmaB, p0.SigmaB)
                                 and np.array_equal(p.CB, p0.CB)):
-            _batch_refuse(f"bag {b} does not share BHat, SigmaB and CB with bag 0 (one fixed basis per call)")
+            refuse(f"bag {b} does not share BHat, SigmaB and CB with bag 0 (one fixed basis per call)")
 
 
 def vbls_batch_(Ys, params, niter):
@@ -1129,32 +1130,32 @@ class SparseBags:
         self.ctx.close()
 
 
-def _sbatch_check_params(L, Ms, H, params):
+def _sbatch_check_params(L, Ms, H, params, refuse=_sbatch_refuse):
     if len(params) != len(Ms):
-        _sbatch_refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
+        refuse(f"{len(Ms)} bags but {len(params)} parameter sets")
     p0 = params[0]
     kind = type(p0)
     m = _MODELS.get(kind)
     if m is None:
-        _sbatch_refuse(f"{kind.__name__} (vbmf_sparse_parameters, vbmf_dual_parameters or vbmf_trial_parameters only)")
+        refuse(f"{kind.__name__} (vbmf_sparse_parameters, vbmf_dual_parameters or vbmf_trial_parameters only)")
     for b, (p, M) in enumerate(zip(params, Ms)):
         if type(p) is not kind:
-            _sbatch_refuse(f"bag {b}: {type(p).__name__} beside {kind.__name__} (one model type per call)")
+            refuse(f"bag {b}: {type(p).__name__} beside {kind.__name__} (one model type per call)")
         if int(p.H) != H:
-            _sbatch_refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
+            refuse(f"bag {b}: H = {p.H}, the bags are for H = {H}")
         if p.L != L or p.M != M:
-            _sbatch_refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
+            refuse(f"bag {b} is {L} x {M}, its parameters describe {(p.L, p.M)}")
         if m.labels and (int(p.H1) > 0 or np.asarray(p.labels).size > 0):
-            _sbatch_refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
+            refuse(f"bag {b} has labels / H1 > 0 (a label mask)")
         if kind is vbmf_trial_parameters and int(p.M0) != M:
-            _sbatch_refuse(f"bag {b}: trial set with M0 = {p.M0} != M = {M} (copy_vbmf_params gives M0 = M)")
+            refuse(f"bag {b}: trial set with M0 = {p.M0} != M = {M} (copy_vbmf_params gives M0 = M)")
         if np.size(p.CA) != M * H:
-            _sbatch_refuse(f"bag {b}: CA has {np.size(p.CA)} entries, not M H = {M * H}")
+            refuse(f"bag {b}: CA has {np.size(p.CA)} entries, not M H = {M * H}")
         if p is not p0 and not (np.array_equal(p.BHat, p0.BHat) and np.array_equal(p.SigmaB, p0.SigmaB)):
-            _sbatch_refuse(f"bag {b} does not share BHat and SigmaB with bag 0 (one fixed basis per call)")
+            refuse(f"bag {b} does not share BHat and SigmaB with bag 0 (one fixed basis per call)")
         _check_derived(p)
         if _alpha_not_derived(m, p):
-            _sbatch_refuse(f"bag {b}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
+            refuse(f"bag {b}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
     return m
 
 
@@ -1251,6 +1252,242 @@ def copy_vbmf_params(Y, old_params, rng=None):
     p.BHat, p.SigmaB = old_params.BHat.copy(), old_params.SigmaB.copy()
     p.CB, p.invCB = old_params.CB.copy(), old_params.invCB.copy()
     return p
+
+
+# =================================================================================================
+# Scoring many bags -- what classify (examples/mil_util.jl:453-535) compares once vbls! has run: residual norms and lower bounds,
+# per bag, in one device call each (include/vbmf_hip.h: vbmf_bag_residuals, vbmf_sparse_lower_bound_batched)
+# =================================================================================================
+def _score_refuser(fn):
+    def refuse(why):
+        raise ValueError(f"{fn}: {why}; score such bags one at a time")
+    return refuse
+
+
+def _score_open(fn, Ys, params, bound=False):
+    """The uploaded bags for `params` (a Bags for the basic model, a SparseBags for the sparse family), the _Model (None: basic) and
+    whether they were opened here.  Every refusal of the batched vbls! entries applies, before any device call."""
+    refuse = _score_refuser(fn)
+    params = list(params)
+    if not params:
+        refuse("no parameter sets")
+    p0 = params[0]
+    H = int(p0.H)
+    basic = type(p0) is vbmf_parameters
+    if basic and bound:
+        refuse("vbmf_parameters (the bound is defined for vbmf_sparse_parameters, vbmf_dual_parameters and vbmf_trial_parameters)")
+    if isinstance(Ys, (Bags, SparseBags)):
+        if isinstance(Ys, Bags) != basic:
+            refuse(f"{type(Ys).__name__} uploaded for another model family than {type(p0).__name__}")
+        if Ys.H != H:
+            refuse(f"the {type(Ys).__name__} were uploaded for H = {Ys.H}, the parameters have H = {H}")
+        L, Ms = Ys.L, Ys.Ms
+    else:
+        L, Ms = _batch_shapes(Ys, H, refuse)
+    if basic:
+        _batch_check_params(L, Ms, H, params, refuse)
+        m = None
+    else:
+        m = _sbatch_check_params(L, Ms, H, params, refuse)
+        for b, p in enumerate(params):
+            if p is not p0 and not (np.array_equal(p.CB, p0.CB) and np.array_equal(p.delta, p0.delta) and p.gamma0 == p0.gamma0
+                                    and p.delta0 == p0.delta0):
+                refuse(f"bag {b} does not share CB, delta, gamma0 and delta0 with bag 0 (one fixed basis per call)")
+    if isinstance(Ys, (Bags, SparseBags)):
+        return Ys, m, False
+    return (Bags(Ys, H) if basic else SparseBags(Ys, H)), m, True
+
+
+def _score_ctx(bags, p0, m):
+    """The bags' context with p0's basis as its state (the per-bag fields of the state are placeholders: the scoring entries take
+    them as arguments)."""
+    H = bags.H
+    if m is None:
+        ctx = bags.session.ctx
+        ctx.set_state(np.zeros((bags.M, H)), p0.BHat, p0.SigmaA, p0.SigmaB, np.diag(p0.CA), np.diag(p0.CB), p0.sigma2)
+        return ctx
+    one = np.ones(bags.M * H)
+    hyper = dict(alpha0=1e-10, beta0=1e-10, gamma0=p0.gamma0, delta0=p0.delta0, eta0=p0.eta0, zeta0=p0.zeta0)
+    bags.ctx.sparse_set_state(one * 0.0, one, one, one, p0.BHat, p0.SigmaB, p0.CB, p0.delta, 1.0, 1.0, hyper)
+    return bags.ctx
+
+
+def _score_columns(m, p, H):
+    """Per column of A: the ARD hyper-prior (shape, rate) and the posterior shape the bound reads (src/vbmf_sparse.jl:452-454, 467;
+    src/vbmf_dual.jl:564-565, 575-581, 593-596; src/vbmf_trial.jl with M0 = M: its third group is empty)."""
+    (a0, b0, a), (a1, b1, a_) = m.groups[0], m.groups[min(1, len(m.groups) - 1)]
+    first = np.arange(H) < getattr(p, "H0", H)
+    shape = lambda name: float(np.asarray(getattr(p, name)).reshape(-1)[0])
+    return (np.where(first, getattr(p, a0), getattr(p, a1)).astype(np.float64),
+            np.where(first, getattr(p, b0), getattr(p, b1)).astype(np.float64),
+            np.where(first, shape(a), shape(a_)))
+
+
+def _stacked_A(params):
+    return np.concatenate([np.asarray(p.AHat, dtype=np.float64).reshape(p.M, p.H) for p in params], axis=0)
+
+
+def _residual_sq(fn, Ys, params):
+    params = list(params)
+    bags, m, own = _score_open(fn, Ys, params)
+    try:
+        return _score_ctx(bags, params[0], m).bag_residuals(bags.col_off, _stacked_A(params))
+    finally:
+        if own:
+            bags.close()
+
+
+def residual_batch(Ys, params):
+    """norm(Y_b - BHat*AHat_b') of every bag (examples/mil_util.jl:483-484) in one device call, entry by entry in fp64 from Y as the
+    device stores it.  Ys: a list of L x M_b arrays, a Bags (basic model) or a SparseBags; params: the parameter sets a batched
+    vbls! filled (one basis, no labels).  Returns the (nbags,) array."""
+    return np.sqrt(_residual_sq("residual_batch", Ys, params))
+
+
+def _bound_batch(fn, Ys, params, clamp, trim):
+    params = list(params)
+    bags, m, own = _score_open(fn, Ys, params, bound=True)
+    try:
+        H = bags.H
+        cols = [_score_columns(m, p, H) for p in params]
+        vec = lambda f: np.concatenate([np.asarray(getattr(p, f), dtype=np.float64).reshape(-1) for p in params])
+        lb, _ = _score_ctx(bags, params[0], m).sparse_lower_bound_batched(
+            bags.col_off, vec("ATVecHat"), vec("diagSigmaATVec"), vec("CA"), vec("beta"),
+            np.array([np.asarray(p.SigmaA, dtype=np.float64).reshape(H, H) for p in params]),
+            [p.sigmaHat for p in params], [p.zeta for p in params], [p.eta for p in params], [p.eta0 for p in params],
+            [p.zeta0 for p in params], np.array([c[0] for c in cols]), np.array([c[1] for c in cols]), np.array([c[2] for c in cols]),
+            trim=trim, clamp=clamp, grouped=type(params[0]) is not vbmf_sparse_parameters)
+        return lb
+    finally:
+        if own:
+            bags.close()
+
+
+def lowerBound_batch(Ys, params, clamp=True):
+    """[lowerBound(Y, p, clamp) for Y, p in zip(Ys, params)] in one device call (src/vbmf_sparse.jl:435-471, src/vbmf_dual.jl:556-599,
+    src/vbmf_trial.jl:630-680 with M0 = M_b).  Ys: a list of L x M_b arrays or a SparseBags (one upload serves several models);
+    params: one model type, one basis (BHat, SigmaB, CB, delta, gamma0, delta0 shared), no labels, H <= 64.  Returns (nbags,)."""
+    return _bound_batch("lowerBound_batch", Ys, params, clamp, None)
+
+
+def lowerBoundTrimmed_batch(Ys, params, trim=1e-1, clamp=True):
+    """[lowerBoundTrimmed(Y, p, trim, clamp) for Y, p in zip(Ys, params)] in one device call (src/vbmf_sparse.jl:478-489; dual
+    :606-617; trial :687-698); arguments as lowerBound_batch."""
+    if not trim >= 0.0:
+        raise ValueError("lowerBoundTrimmed_batch: trim must be >= 0")
+    return _bound_batch("lowerBoundTrimmed_batch", Ys, params, clamp, float(trim))
+
+
+_CLASS_ALGS = ("vbls", "dual", "lower_bound")
+
+
+def _one_set(fn, q):
+    if isinstance(q, tuple):
+        _score_refuser(fn)("a vbmf_trial_parameters model gives two parameter sets per bag (copy_vbmf_params), which classify does "
+                           "not take either")
+    return q
+
+
+def _truncated_basis(res):
+    """factorize_bag's first model (examples/mil_util.jl:398-404): the basis without its last H1 columns."""
+    H0 = int(res.H) - int(res.H1)
+    return dict(H=H0, BHat=np.array(res.BHat[:, :H0], order="F"), SigmaB=np.array(res.SigmaB[:H0, :H0], order="F"),
+                CB=np.array(res.CB[:H0]), gamma=res.gamma, delta=np.array(res.delta[:H0]))
+
+
+def _full_cov_groups(Ms, H0):
+    """factorize_bag's choice of the updateA! form (:405-409), per bag: (indices with full_cov, indices without)."""
+    full = [b for b, M in enumerate(Ms) if M * H0 < 1600]
+    diag = [b for b, M in enumerate(Ms) if not M * H0 < 1600]
+    return full, diag
+
+
+def _factorize_bags(Ys, res, niter):
+    """factorize_bag (examples/mil_util.jl:393-416) over many bags: per bag (params0, params1), fitted by the batched vbls! in at
+    most two groups per basis (full_cov or not), and scored where they sit: returns (L0, L1 as functions of the threshold)."""
+    H, H1 = int(res.H), int(res.H1)
+    tb = _truncated_basis(res)
+    L0, sets1 = np.empty(len(Ys)), []
+    for full_cov, idx in zip((True, False), _full_cov_groups([np.shape(Y)[1] for Y in Ys], H - H1)):
+        if not idx:
+            continue
+        sub = [Ys[b] for b in idx]
+        ps0 = []
+        for Y in sub:
+            p = vbmf_sparse_init(Y, tb["H"])
+            p.BHat, p.SigmaB, p.CB, p.gamma, p.delta = tb["BHat"], tb["SigmaB"], tb["CB"], tb["gamma"], tb["delta"]
+            ps0.append(p)
+        ps1 = [copy_vbmf_params(Y, res) for Y in sub]
+        bags0, bags1 = SparseBags(sub, tb["H"]), SparseBags(sub, H)
+        try:
+            vbls_sparse_batch_(bags0, ps0, niter, full_cov=full_cov)
+            L0[idx] = lowerBound_batch(bags0, ps0)
+            vbls_sparse_batch_(bags1, ps1, niter, full_cov=full_cov)
+            sets1.append((idx, bags1, ps1))
+        except BaseException:
+            for _, opened, _ in sets1 + [(idx, bags1, ps1)]:
+                opened.close()
+            raise
+        finally:
+            bags0.close()
+    return L0, sets1
+
+
+def classify_batch(res0, res1, Ys, class_alg, threshold=1e-1, niter=None):
+    """classify (examples/mil_util.jl:453-535) over many bags: (labels, err0, err1) as arrays, every number formed on the device by
+    the batched vbls! entries and the two scoring entries.  class_alg:
+      "vbls"         basic models, 150 iterations (:473-479), err = norm(Y - BHat*AHat'), label 1 where err0 > err1
+      "dual"         sparse / dual models, full_cov, 20 iterations (:516-521), err = norm(YHat - Y) / (L*M), label 0 where err0 < err1
+      "lower_bound"  factorize_bag on res0 (a vbmf_sparse_parameters with H1 > 0; res1 is not read, as in the reference), 20
+                     iterations, full_cov per bag by M_b (H - H1) < 1600; err0 = lowerBound of the truncated basis' fit, err1 =
+                     lowerBoundTrimmed(threshold) of the whole basis' fit, label 1 where err1 > err0
+    niter overrides the iteration count.  "ols", "rls" and "min_err" are not built here."""
+    fn = "classify_batch"
+    refuse = _score_refuser(fn)
+    if class_alg not in _CLASS_ALGS:
+        refuse(f"class_alg = {class_alg!r} (one of {', '.join(_CLASS_ALGS)})")
+    Ys = list(Ys)
+    if class_alg == "lower_bound":
+        if type(res0) is not vbmf_sparse_parameters or not 0 < int(res0.H1) < int(res0.H):
+            refuse("lower_bound needs res0 to be a vbmf_sparse_parameters with 0 < H1 < H (factorize_bag)")
+        _batch_shapes(Ys, int(res0.H), refuse)
+        L0, sets1 = _factorize_bags(Ys, res0, 20 if niter is None else int(niter))
+        L1 = np.empty(len(Ys))
+        try:
+            for idx, bags1, ps1 in sets1:
+                L1[idx] = lowerBoundTrimmed_batch(bags1, ps1, threshold)
+        finally:
+            for _, bags1, _ in sets1:
+                bags1.close()
+        return (L1 > L0).astype(np.int64), L0, L1
+    basic = class_alg == "vbls"
+    for r in (res0, res1):
+        if basic != (type(r) is vbmf_parameters) or (not basic and type(r) not in (vbmf_sparse_parameters, vbmf_dual_parameters)):
+            refuse(f"class_alg = {class_alg!r} with a {type(r).__name__} model")
+    if int(res0.H) != int(res1.H):
+        refuse(f"the two models have different H ({res0.H}, {res1.H}): they cannot share one upload")
+    H = int(res0.H)
+    L, Ms = _batch_shapes(Ys, H, refuse)
+    bags = Bags(Ys, H) if basic else SparseBags(Ys, H)
+    try:
+        errs = []
+        for res in (res0, res1):
+            ps = [_one_set(fn, copy_vbmf_params(Y, res)) for Y in Ys]
+            if basic:
+                vbls_batch_(bags, ps, 150 if niter is None else int(niter))
+            else:
+                vbls_sparse_batch_(bags, ps, 20 if niter is None else int(niter), full_cov=True)
+            # the batched fit has just checked these sets and left this model's basis as the context's state
+            ctx = bags.session.ctx if basic else bags.ctx
+            errs.append(np.sqrt(ctx.bag_residuals(bags.col_off, _stacked_A(ps))))
+    finally:
+        bags.close()
+    err0, err1 = errs
+    if basic:
+        return (err0 > err1).astype(np.int64), err0, err1                # :487-491
+    scale = L * np.asarray(Ms, dtype=np.float64)
+    err0, err1 = err0 / scale, err1 / scale                              # :523-524
+    return np.where(err0 < err1, 0, 1).astype(np.int64), err0, err1      # :526-530
 
 
 # =================================================================================================

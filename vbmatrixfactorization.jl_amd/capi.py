@@ -39,6 +39,7 @@ SYMBOLS = [
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
+    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
@@ -131,6 +132,8 @@ def lib():
     L.vbmf_sparse_lower_bound.argtypes = [vp, i32, dp]
     L.vbmf_sparse_lower_bound_trimmed.argtypes = [vp, i32, C.c_double, dp]
     L.vbmf_debug_set.argtypes = [vp, i32, i64]
+    L.vbmf_bag_residuals.argtypes = [vp, i64, C.POINTER(i64), dp, i64, dp]
+    L.vbmf_sparse_lower_bound_batched.argtypes = [vp, i64, C.POINTER(i64), i32, C.c_double, i32] + [dp] * 15
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
     L.vbmf_sparse_set_SigmaA.argtypes = [vp, dp]
     L.vbmf_sparse_get_SigmaA.argtypes = [vp, dp]
@@ -439,6 +442,40 @@ class Context:
         v = C.c_double()
         self._chk(self._lib.vbmf_sparse_lower_bound_trimmed(self._h, int(clamp), float(trim), C.byref(v)))
         return v.value
+
+    # ---- per-bag scoring of the bags side by side in this context's Y ----
+    def bag_residuals(self, col_off, AHat):
+        """||Y_b - BHat AHat_b'||_F^2 of every bag (vbmf_bag_residuals): bag b = columns col_off[b] .. col_off[b+1]-1, BHat from
+        set_state / sparse_set_state, AHat (M, H) the bags' rows stacked.  Returns r2 (nbags,).  The state is not changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        A = _fcol(AHat, (self.M, self.H))
+        r2 = np.empty(max(nb, 0))
+        self._chk(self._lib.vbmf_bag_residuals(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(A), self.M, _dptr(r2)))
+        return r2
+
+    def sparse_lower_bound_batched(self, col_off, ATVecHat, diagSigmaATVec, CA, beta, SigmaA, sigmaHat, zeta, eta, eta0, zeta0,
+                                   a_pri, b_pri, a_post, trim=None, clamp=True, grouped=False):
+        """lowerBound (trim None) / lowerBoundTrimmed of every bag (vbmf_sparse_lower_bound_batched): BHat, SigmaB, CB, delta, gamma0,
+        delta0 from sparse_set_state; ATVecHat, diagSigmaATVec, CA, beta (M*H,) in vec(A') order; SigmaA (nbags, H, H); sigmaHat, zeta,
+        eta, eta0, zeta0 (nbags,); a_pri, b_pri, a_post (nbags, H): per column of A the ARD hyper-prior (shape, rate) and posterior
+        shape.  grouped: the dual / trial models' trimming rule.  Returns (lb, r2), each (nbags,).  The state is not changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        MH = self.M * self.H
+        vecs = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (ATVecHat, diagSigmaATVec, CA, beta)]
+        SA = np.ascontiguousarray(SigmaA, dtype=np.float64)
+        per_bag = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (sigmaHat, zeta, eta, eta0, zeta0)]
+        per_col = [np.ascontiguousarray(v, dtype=np.float64) for v in (a_pri, b_pri, a_post)]
+        if (nb < 1 or any(v.shape != (MH,) for v in vecs) or SA.shape != (nb, self.H, self.H)
+                or any(v.shape != (nb,) for v in per_bag) or any(v.shape != (nb, self.H) for v in per_col)):
+            raise ValueError(f"col_off describes {nb} bags: the vec(A') fields must be ({MH},), SigmaA ({nb}, {self.H}, {self.H}), "
+                             f"the per-bag scalars ({nb},) and a_pri, b_pri, a_post ({nb}, {self.H})")
+        lb, r2 = np.empty(nb), np.empty(nb)
+        self._chk(self._lib.vbmf_sparse_lower_bound_batched(
+            self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), int(clamp), -1.0 if trim is None else float(trim), int(bool(grouped)),
+            *[_dptr(v) for v in vecs], _dptr(SA), *[_dptr(v) for v in per_bag], *[_dptr(v) for v in per_col], _dptr(lb), _dptr(r2)))
+        return lb, r2
 
     # ---- two-group ARD variant (variant=VBMF_VARIANT_DUAL_DIAG) ----
     def dual_set_priors(self, H0, alpha00, beta00, alpha01, beta01, alpha0=None, alpha1=None):

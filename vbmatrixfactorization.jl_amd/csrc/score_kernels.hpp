@@ -1,0 +1,166 @@
+// score_kernels.hpp -- what the MIL classifier compares after a batched vbls!: per-bag residuals and the per-bag sums of
+// lowerBound / lowerBoundTrimmed (vbmf_bag_residuals, vbmf_sparse_lower_bound_batched; examples/mil_util.jl:469-530).
+//
+// The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1 (batch_kernels.hpp); bags do not align
+// with the 32-column tiles, so every access goes through the column index.
+//   bag_resid_kernel     r2 partials: sum over a slice of a bag's columns of (Y[l,m] - sum_h B[l,h] A[m,h])^2, formed entry by
+//                        entry from Y as stored (the pass-2 tiles bag_gram_kernel reads) in fp64 -- NOT the trace form
+//                        ||Y||^2 - 2 tr(B'YA) + tr(A'A B'B): on a fitted bag r2 is 1/400 .. 1/2500 of ||Y_b||^2 and the trace
+//                        form would lose that many digits of the fp32 Y'B.  A bag is cut into slices of SCORE_CW columns counted
+//                        from ITS OWN first column, one workgroup per slice (chunk_off: the bags' first slice numbers), so a
+//                        1-column bag costs one workgroup, a 70-column bag nine, and no bag's result depends on where it sits in Y.
+//                        B is the context's BHat as stored (fp32 row-major [Lp][Hp], the values vbmf_get_state returns), widened
+//                        to fp64; A is the caller's fp64 AHat.
+//   bag_resid_fold_kernel  r2[b] = the bag's slice partials, summed in slice order
+//   bag_lb_sums_kernel   one workgroup per bag: the M_b*H-long sums of lowerBound per column h (SCORE_NS values each) and the two
+//                        H x H contractions of its data term
+// Data term of the per-bag bound: r2 + L tr(A'A SigmaB) + tr(SigmaA (B'B + L SigmaB)), algebraically the reference's
+// ||Y||^2 - 2 tr(B'YA) + tr((A'A + SigmaA)(B'B + L SigmaB)) (src/vbmf_sparse.jl:439-440) with the direct residual of the same
+// call in place of its three cancelling terms; so neither tr(B'Y_b A_b) nor ||Y_b||^2 is formed here.
+#pragma once
+#include "common.hpp"
+#include "ctrl_kernels.hpp"
+
+namespace vbmf {
+
+constexpr int SCORE_CW = 8;        // columns of a bag per residual workgroup
+constexpr int SCORE_THREADS = 256;
+// per column h of a bag: [ sum log beta, sum CA, count', sum' log beta, sum' CA, sum' CA (a^2 + dS), sum' log dS ]; sum' / count'
+// run over the entries lowerBoundTrimmed keeps, |(float)a| > trim (trim < 0 keeps everything: lowerBound)
+constexpr int SCORE_NS = 7;
+// dynamic LDS of bag_resid_kernel: the slice's rows of A
+inline size_t score_resid_lds_bytes(int H) { return (size_t)SCORE_CW * H * sizeof(double); }
+
+// the last bag whose first slice number is <= w
+__device__ __forceinline__ int score_bag_of(const long long* __restrict__ chunk_off, int nbags, long long w) {
+    int lo = 0, hi = nbags - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (chunk_off[mid] <= w) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// A[m, h] = A[m * sm + h * sh]: (1, ldA) for a column-major AHat, (H, 1) for vec(A')
+template <int MODE>
+__global__ __launch_bounds__(SCORE_THREADS) void bag_resid_kernel(const uint4* __restrict__ Y2, int KSpad, long long L,
+                                                                  const float* __restrict__ B32, int Hp, int H,
+                                                                  const double* __restrict__ A, long long sm, long long sh,
+                                                                  const long long* __restrict__ col_off,
+                                                                  const long long* __restrict__ chunk_off, int nbags,
+                                                                  double* __restrict__ part) {
+    constexpr int KSTEP = (MODE == MODE_F32) ? 8 : 16;
+    extern __shared__ __attribute__((aligned(16))) double Al[];      // [SCORE_CW][H]
+    __shared__ double red[SCORE_THREADS / 64];
+    const long long w = blockIdx.x;
+    const int b = score_bag_of(chunk_off, nbags, w);
+    const long long m0 = col_off[b] + (w - chunk_off[b]) * SCORE_CW;
+    const long long mend = col_off[b + 1];
+    const int nc = (int)(mend - m0 < SCORE_CW ? mend - m0 : SCORE_CW);
+    for (int t = threadIdx.x; t < nc * H; t += SCORE_THREADS) {
+        const int cc = t / H, h = t % H;
+        Al[t] = A[(m0 + cc) * sm + h * sh];
+    }
+    __syncthreads();
+    double acc = 0.0;
+    const long long n = (long long)nc * L;
+    for (long long t = threadIdx.x; t < n; t += SCORE_THREADS) {
+        const long long l = t % L;
+        const int cc = (int)(t / L);
+        const long long m = m0 + cc;
+        const int xt = (int)(l >> 5), c = (int)(l & 31);
+        const int ks = (int)(m / KSTEP), wi = (int)(m % KSTEP);
+        int half, e;
+        if (MODE == MODE_F32) { half = wi >> 2; e = wi & 3; }
+        else { half = (wi >> 2) & 1; e = 4 * (wi >> 3) + (wi & 3); }
+        const uint4 f = Y2[((long long)xt * KSpad + ks) * 64 + half * 32 + c];
+        const unsigned wd[4] = {f.x, f.y, f.z, f.w};
+        float v;
+        if (MODE == MODE_F32) v = bitsf(wd[e]);
+        else v = bf2f((unsigned short)((wd[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
+        const float* brow = B32 + l * Hp;
+        const double* arow = Al + cc * H;
+        double pred = 0.0;
+        for (int h = 0; h < H; ++h) pred += (double)brow[h] * arow[h];
+        const double d = (double)v - pred;
+        acc += d * d;
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) part[w] = acc;
+}
+
+__global__ void bag_resid_fold_kernel(const double* __restrict__ part, const long long* __restrict__ chunk_off, int nbags,
+                                      double* __restrict__ r2) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nbags) return;
+    double s = 0.0;
+    for (long long w = chunk_off[b]; w < chunk_off[b + 1]; ++w) s += part[w];
+    r2[b] = s;
+}
+
+// a, dS, CA, beta: M*H in vec(A') order (index m*H + h); SA: nbags x H x H.  sums: [nbags][H][SCORE_NS];
+// quad: [nbags][2] = { sum_m a_m' SigmaB a_m = tr(A_b'A_b SigmaB),  tr(SigmaA_b (B'B + L SigmaB)) }.
+// Thread (h, s) of the first (SCORE_THREADS / H) * H takes the bag's columns m = s, s + S, ... of vec column h; the S shares meet in
+// LDS in slice order, so a bag's sums depend on its own entries only.
+__global__ __launch_bounds__(SCORE_THREADS) void bag_lb_sums_kernel(const double* __restrict__ a, const double* __restrict__ dS,
+                                                                    const double* __restrict__ CA, const double* __restrict__ beta,
+                                                                    const double* __restrict__ SA, const double* __restrict__ st,
+                                                                    StateLayout lay, int H, double Lg,
+                                                                    const long long* __restrict__ col_off, double trim,
+                                                                    double* __restrict__ sums, double* __restrict__ quad) {
+    __shared__ double sh[SCORE_THREADS][SCORE_NS];
+    __shared__ double red[SCORE_THREADS / 64];
+    const int b = blockIdx.x;
+    const long long m0 = col_off[b];
+    const int Mb = (int)(col_off[b + 1] - m0);
+    const int Hc = H < SCORE_THREADS ? H : SCORE_THREADS;             // columns per round (H > 256: several rounds)
+    const int S = SCORE_THREADS / Hc;
+    for (int h0 = 0; h0 < H; h0 += Hc) {
+        const int hh = threadIdx.x % Hc, s = threadIdx.x / Hc, h = h0 + hh;
+        double v[SCORE_NS] = {0, 0, 0, 0, 0, 0, 0};
+        if (s < S && h < H) {
+            for (int m = s; m < Mb; m += S) {
+                const long long i = (m0 + m) * H + h;
+                const double av = a[i], ds = dS[i], ca = CA[i], lb = log(beta[i]);
+                v[0] += lb; v[1] += ca;
+                if (trim < 0.0 || fabs((double)(float)av) > trim) {
+                    v[2] += 1.0; v[3] += lb; v[4] += ca; v[5] += ca * (av * av + ds); v[6] += log(ds);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SCORE_NS; ++k) sh[threadIdx.x][k] = v[k];
+        __syncthreads();
+        if (s == 0 && h < H) {
+#pragma unroll
+            for (int k = 0; k < SCORE_NS; ++k) {
+                double t = 0.0;
+                for (int q = 0; q < S; ++q) t += sh[q * Hc + hh][k];
+                sums[((long long)b * H + h) * SCORE_NS + k] = t;
+            }
+        }
+        __syncthreads();
+    }
+    const double* SB = st + lay.SB();
+    const double* GB = st + lay.GB();
+    double qa = 0.0;
+    for (long long t = threadIdx.x; t < (long long)Mb * H; t += SCORE_THREADS) {
+        const int m = (int)(t / H), i = (int)(t % H);
+        const double* am = a + (m0 + m) * H;
+        double r = 0.0;
+        for (int j = 0; j < H; ++j) r += SB[(long long)i * lay.Hp + j] * am[j];
+        qa += am[i] * r;
+    }
+    qa = block_sum(qa, red);
+    double ts = 0.0;
+    const double* SAb = SA + (long long)b * H * H;
+    for (int t = threadIdx.x; t < H * H; t += SCORE_THREADS) {
+        const long long e = (long long)(t / H) * lay.Hp + (t % H);
+        ts += SAb[t] * (GB[e] + Lg * SB[e]);
+    }
+    __syncthreads();
+    ts = block_sum(ts, red);
+    if (threadIdx.x == 0) { quad[2 * b] = qa; quad[2 * b + 1] = ts; }
+}
+
+}  // namespace vbmf

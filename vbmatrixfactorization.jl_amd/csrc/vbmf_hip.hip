@@ -45,6 +45,7 @@
 #include "prep_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "sparse_batch_kernels.hpp"
+#include "score_kernels.hpp"
 #include "gram_kernels.hpp"
 
 using namespace vbmf;
@@ -166,6 +167,8 @@ struct vbmf_ctx {
     size_t bat_bytes = 0;
     double* sbat = nullptr;           // vbmf_sparse_run_fixed_basis_batched: the same for the sparse models (grown on demand)
     size_t sbat_bytes = 0;
+    double* score = nullptr;          // vbmf_bag_residuals / vbmf_sparse_lower_bound_batched: per-bag inputs, partials and sums (grown on demand)
+    size_t score_bytes = 0;
     // Gram-form sweep of vbmf_run (gram_kernels.hpp); buffers allocated by the first run that takes it
     int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows
     int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
@@ -1291,7 +1294,7 @@ int vbmf_destroy(vbmf_ctx* c) {
     void* bufs[] = {c->sk_list, c->sk_tail, c->gw, c->hmean, c->fws, c->t2part, c->Y1, c->Y2, c->FA_alloc, c->FB_alloc, c->FD, c->SBf, c->P, c->Q, c->Pred, c->A32, c->B32[0], c->B32[1], c->SA32,
                     c->SB32, c->gslab, c->st, c->gtmp, c->ypart, c->trpart, c->ints, c->mask, c->dS32, c->CA32, c->beta32, c->vtab,
                     c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bat, c->Gt, c->W32g[0], c->W32g[1], c->Wt, c->gslabs, c->gPQ,
-                    c->g_part, c->gsave, c->sbat};
+                    c->g_part, c->gsave, c->sbat, c->score};
     for (void* b : bufs) if (b) hipFree(b);
     if (c->ints_host) hipHostFree(c->ints_host);
     if (c->scal_host) hipHostFree(c->scal_host);
@@ -3234,6 +3237,85 @@ int vbmf_sparse_get_noise_rows(vbmf_ctx* c, double* sigmaVecHat, double* zetaVec
 
 }  // extern "C"
 
+// Everything lowerBound reads, as sums: filled from a whole context (sparse_lower_bound_impl, three ARD groups) or from one bag of a
+// batched call (vbmf_sparse_lower_bound_batched, one ARD group per column of A), assembled by lb_assemble.
+struct LbGroup { double n, s_logbeta, s_ca, a_pri, b_pri, a_post; };   // entries, sum log beta, sum CA, prior (shape, rate), posterior shape
+struct LbSums {
+    double L, M, H, MH;                  // MH: params.MH, the length of the (trimmed) ATVecHat (:483); every other size is the model's own
+    double sig, zeta, eta;               // noise precision, its Gamma posterior (eta, zeta)
+    double quad;                         // ||Y||^2 - 2 tr(B'YA) + tr((A'A + SigmaA)(B'B + L SigmaB))  (:439-440)
+    double s_caq, s_logds;               // sum' CA (a^2 + dS), sum' log dS
+    double cbq, sumcb, sumlogdelta;      // sum_h CB_h (B'B + L SigmaB)_hh, sum CB, sum log delta
+    double logdet_sb, gamma_;
+    vbmf_sparse_hyper hyp;               // gamma0, delta0, eta0, zeta0 (alpha0 / beta0 travel per group)
+    const LbGroup* g; int ng;
+};
+
+// src/vbmf_sparse.jl:438-469 with the group terms of src/vbmf_dual.jl:556-599 and src/vbmf_trial.jl:630-680, fp64 on the host
+static double lb_assemble(const LbSums& s, int clamp) {
+    const double L = s.L, M = s.M, H = s.H, MH = s.MH;
+    const double LN2PI = std::log(2.0 * M_PI);
+    const double sig = s.sig, zeta = s.zeta;
+    const vbmf_sparse_hyper& hp = s.hyp;
+    const double eln_sig = digamma_host(s.eta) - std::log(zeta);
+    std::vector<double> eln_g((size_t)s.ng);
+    double s_eln_ca = 0.0;
+    for (int g = 0; g < s.ng; ++g) {
+        eln_g[(size_t)g] = s.g[g].n > 0 ? s.g[g].n * digamma_host(s.g[g].a_post) - s.g[g].s_logbeta : 0.0;
+        s_eln_ca = g == 0 ? eln_g[0] : s_eln_ca + eln_g[(size_t)g];
+    }
+    const double s_eln_cb = H * digamma_host(s.gamma_) - s.sumlogdelta;
+    double Lb = 0.0;
+    Lb += -L * M / 2 * LN2PI + L * M / 2 * eln_sig;                                        // :438
+    Lb += -sig / 2 * s.quad;                                                               // :439-440
+    Lb += -MH / 2 * LN2PI + 0.5 * s_eln_ca;                                                // :442
+    Lb += -0.5 * s.s_caq;                                                                  // :443
+    Lb += -L * H / 2 * LN2PI;                                                              // :445
+    Lb += L / 2 * s_eln_cb;                                                                // :446
+    Lb += -0.5 * s.cbq;                                                                    // :447
+    Lb += hp.eta0 * std::log(hp.zeta0) - std::lgamma(hp.eta0);                             // :449
+    Lb += (hp.eta0 - 1) * eln_sig - hp.zeta0 * sig;                                        // :450
+    for (int g = 0; g < s.ng; ++g) {                                                       // one group in the sparse model
+        const LbGroup& q = s.g[g];
+        if (!(q.n > 0)) continue;
+        Lb += q.n * (q.a_pri * std::log(q.b_pri) - std::lgamma(q.a_pri));                  // :452   (dual :575, 579)
+        Lb += (q.a_pri - 1) * eln_g[(size_t)g];                                            // :453   (dual :576, 580)
+        Lb += -q.b_pri * q.s_ca;                                                           // :454   (dual :577, 581)
+    }
+    Lb += H * (hp.gamma0 * std::log(hp.delta0) - std::lgamma(hp.gamma0));                  // :456
+    Lb += (hp.gamma0 - 1) * s_eln_cb;                                                      // :457
+    Lb += -hp.gamma0 * s.sumcb;                                                            // :458 (sic: gamma0)
+    Lb += MH / 2 + MH / 2 * LN2PI + 0.5 * s.s_logds;                                       // :461 normalEntropy(diag)
+    double logdet_kron = L * s.logdet_sb;                                                  // det(kron(SigmaB, I_L)) = det(SigmaB)^L
+    if (clamp) logdet_kron = std::max(logdet_kron, std::log(4.9406564584124654e-324));     // src/util.jl:118-122
+    Lb += L * H / 2 + L * H / 2 * LN2PI + 0.5 * logdet_kron;                               // :463
+    Lb += s.eta + std::log(zeta) + std::lgamma(s.eta) + (1 - s.eta) * digamma_host(s.eta);                   // :465
+    for (int g = 0; g < s.ng; ++g) {                                                                         // :467 (dual :594, 596)
+        const LbGroup& q = s.g[g];
+        if (q.n > 0) Lb += q.n * (q.a_post + std::lgamma(q.a_post) + (1 - q.a_post) * digamma_host(q.a_post)) + q.s_logbeta;
+    }
+    Lb += H * (s.gamma_ + std::lgamma(s.gamma_) + (1 - s.gamma_) * digamma_host(s.gamma_)) + s.sumlogdelta;  // :469
+    return Lb;
+}
+
+// the basis' share of the sums (B'B, SigmaB, CB, delta of the state image `buf`)
+static void lb_basis_sums(const vbmf_ctx* c, const std::vector<double>& buf, LbSums& s) {
+    const double L = (double)c->Lg;
+    auto at = [&](long long off, int i, int j) { return buf[(size_t)off + (size_t)i * c->Hp + j]; };
+    double cbq = 0, sumcb = 0, sumlogdelta = 0;
+    for (int i = 0; i < c->H; ++i) {
+        const double cb = buf[(size_t)c->lay.cb() + i];
+        cbq += cb * (at(c->lay.GB(), i, i) + L * at(c->lay.SB(), i, i));
+        sumcb += cb;
+        sumlogdelta += std::log(buf[(size_t)c->lay.ca() + i]);
+    }
+    s.cbq = cbq; s.sumcb = sumcb; s.sumlogdelta = sumlogdelta;
+    s.logdet_sb = buf[(size_t)c->lay.scal() + S_LOGDET_SB];
+    s.gamma_ = c->gamma_;
+    s.hyp = c->hyp;
+    s.L = L; s.H = (double)c->H;
+}
+
 // trim < 0: lowerBound; trim >= 0: lowerBoundTrimmed
 static int sparse_lower_bound_impl(vbmf_ctx* c, int clamp, double trim, double* lb) {
     if (!c || !lb) return VBMF_ERR_INVALID;
@@ -3265,68 +3347,37 @@ static int sparse_lower_bound_impl(vbmf_ctx* c, int clamp, double trim, double* 
         s_logbeta_g[0] = s_logbeta_keep; s_logbeta_g[1] = s_logbeta_g[2] = 0.0;
         s_ca_g[0] = s_ca_keep; s_ca_g[1] = s_ca_g[2] = 0.0;
     }
-    const double s_logbeta = s_logbeta_g[0] + s_logbeta_g[1] + s_logbeta_g[2];
     const double* sc = buf.data() + c->lay.scal();
-    // MH: params.MH, the length of the (trimmed) ATVecHat (:483); every other size below is the model's own
-    const double L = (double)c->Lg, M = (double)c->M, H = (double)c->H, MH = trimmed ? n_keep : M * H;
-    const double LN2PI = std::log(2.0 * M_PI);
-    const double sig = sc[S_SIGMA2], zeta = sc[S_ZETA], trYY = sc[S_TRYY], trBQ = sc[S_TRYBA];
+    LbSums s{};
+    lb_basis_sums(c, buf, s);
+    const double L = s.L, M = (double)c->M;
+    s.M = M;
+    s.MH = trimmed ? n_keep : M * s.H;
+    s.sig = sc[S_SIGMA2]; s.zeta = sc[S_ZETA]; s.eta = c->eta;
+    const double trYY = sc[S_TRYY], trBQ = sc[S_TRYBA];
     auto at = [&](long long off, int i, int j) { return buf[(size_t)off + (size_t)i * c->Hp + j]; };
-    double t2 = 0, cbq = 0, sumcb = 0, sumlogdelta = 0;
-    for (int i = 0; i < c->H; ++i) {
+    double t2 = 0;
+    for (int i = 0; i < c->H; ++i)
         for (int j = 0; j < c->H; ++j)
             t2 += (at(c->lay.GA(), i, j) + at(c->lay.SA(), i, j)) * (at(c->lay.GB(), i, j) + L * at(c->lay.SB(), i, j));
-        const double cb = buf[(size_t)c->lay.cb() + i];
-        cbq += cb * (at(c->lay.GB(), i, i) + L * at(c->lay.SB(), i, i));
-        sumcb += cb;
-        sumlogdelta += std::log(buf[(size_t)c->lay.ca() + i]);
-    }
-    const vbmf_sparse_hyper& hp = c->hyp;
-    const double eln_sig = digamma_host(c->eta) - std::log(zeta);
-    double s_eln_ca = MH * digamma_host(c->alpha) - s_logbeta;
+    s.quad = trYY - 2 * trBQ + t2;
+    s.s_caq = s_caq; s.s_logds = s_logds;
     // grouped models (src/vbmf_dual.jl:556-599, src/vbmf_trial.jl:630-680): posterior shapes and priors per group
-    double n_g[3] = {MH, 0.0, 0.0}, a_post[3] = {c->alpha, c->alpha, c->alpha}, a_pri[3], b_pri[3];
-    double eln_g[3] = {s_eln_ca, 0.0, 0.0};
-    for (int g = 0; g < 3; ++g) { a_pri[g] = c->hyp.alpha0; b_pri[g] = c->hyp.beta0; }
+    LbGroup grp[3];
+    for (int g = 0; g < 3; ++g) grp[g] = LbGroup{0.0, s_logbeta_g[g], s_ca_g[g], c->hyp.alpha0, c->hyp.beta0, c->alpha};
+    grp[0].n = s.MH;
+    grp[0].s_logbeta = s_logbeta_g[0] + s_logbeta_g[1] + s_logbeta_g[2];
     if (c->dual) {
         const double H1 = (double)(c->H - c->H0);
-        n_g[0] = M * (double)c->H0; n_g[1] = (double)c->M0 * H1; n_g[2] = (M - (double)c->M0) * H1;
+        grp[0].n = M * (double)c->H0; grp[1].n = (double)c->M0 * H1; grp[2].n = (M - (double)c->M0) * H1;
         for (int g = 0; g < 3; ++g) {
-            a_pri[g] = sc[S_GPRI + 2 * g]; b_pri[g] = sc[S_GPRI + 2 * g + 1];
-            a_post[g] = sc[S_GPOST + g];
-            eln_g[g] = n_g[g] > 0 ? n_g[g] * digamma_host(a_post[g]) - s_logbeta_g[g] : 0.0;
+            grp[g].s_logbeta = s_logbeta_g[g];
+            grp[g].a_pri = sc[S_GPRI + 2 * g]; grp[g].b_pri = sc[S_GPRI + 2 * g + 1];
+            grp[g].a_post = sc[S_GPOST + g];
         }
-        s_eln_ca = eln_g[0] + eln_g[1] + eln_g[2];
     }
-    const double s_eln_cb = H * digamma_host(c->gamma_) - sumlogdelta;
-    double Lb = 0.0;
-    Lb += -L * M / 2 * LN2PI + L * M / 2 * eln_sig;                                        // :438
-    Lb += -sig / 2 * (trYY - 2 * trBQ + t2);                                               // :439-440
-    Lb += -MH / 2 * LN2PI + 0.5 * s_eln_ca;                                                // :442
-    Lb += -0.5 * s_caq;                                                                    // :443
-    Lb += -L * H / 2 * LN2PI;                                                              // :445
-    Lb += L / 2 * s_eln_cb;                                                                // :446
-    Lb += -0.5 * cbq;                                                                      // :447
-    Lb += hp.eta0 * std::log(hp.zeta0) - std::lgamma(hp.eta0);                             // :449
-    Lb += (hp.eta0 - 1) * eln_sig - hp.zeta0 * sig;                                        // :450
-    for (int g = 0; g < 3; ++g) {                                                          // one group in the sparse model
-        if (!(n_g[g] > 0)) continue;
-        Lb += n_g[g] * (a_pri[g] * std::log(b_pri[g]) - std::lgamma(a_pri[g]));            // :452   (dual :575, 579)
-        Lb += (a_pri[g] - 1) * eln_g[g];                                                   // :453   (dual :576, 580)
-        Lb += -b_pri[g] * s_ca_g[g];                                                       // :454   (dual :577, 581)
-    }
-    Lb += H * (hp.gamma0 * std::log(hp.delta0) - std::lgamma(hp.gamma0));                  // :456
-    Lb += (hp.gamma0 - 1) * s_eln_cb;                                                      // :457
-    Lb += -hp.gamma0 * sumcb;                                                              // :458 (sic: gamma0)
-    Lb += MH / 2 + MH / 2 * LN2PI + 0.5 * s_logds;                                         // :461 normalEntropy(diag)
-    double logdet_kron = L * sc[S_LOGDET_SB];                                              // det(kron(SigmaB, I_L)) = det(SigmaB)^L
-    if (clamp) logdet_kron = std::max(logdet_kron, std::log(4.9406564584124654e-324));     // src/util.jl:118-122
-    Lb += L * H / 2 + L * H / 2 * LN2PI + 0.5 * logdet_kron;                               // :463
-    Lb += c->eta + std::log(zeta) + std::lgamma(c->eta) + (1 - c->eta) * digamma_host(c->eta);               // :465
-    for (int g = 0; g < 3; ++g)                                                                              // :467 (dual :594, 596)
-        if (n_g[g] > 0) Lb += n_g[g] * (a_post[g] + std::lgamma(a_post[g]) + (1 - a_post[g]) * digamma_host(a_post[g])) + s_logbeta_g[g];
-    Lb += H * (c->gamma_ + std::lgamma(c->gamma_) + (1 - c->gamma_) * digamma_host(c->gamma_)) + sumlogdelta; // :469
-    *lb = Lb;
+    s.g = grp; s.ng = 3;
+    *lb = lb_assemble(s, clamp);
     return VBMF_OK;
 }
 
@@ -3337,6 +3388,157 @@ int vbmf_sparse_lower_bound(vbmf_ctx* c, int clamp, double* lb) { return sparse_
 int vbmf_sparse_lower_bound_trimmed(vbmf_ctx* c, int clamp, double trim, double* lb) {
     if (c && !(trim >= 0.0)) FAIL(c, VBMF_ERR_INVALID, "vbmf_sparse_lower_bound_trimmed: trim must be >= 0");
     return sparse_lower_bound_impl(c, clamp, trim, lb);
+}
+
+}  // extern "C"
+
+// ---- per-bag scoring (score_kernels.hpp) ----------------------------------------------------------------------------------------
+// what both entries refuse before any launch; nslices: the residual workgroups of the call
+static int score_check(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, int64_t* nslices) {
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only)", fn);
+    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "%s: row-sharded context (one rank only)", fn);
+    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "%s: bad nbags / col_off", fn);
+    if (col_off[0] != 0 || col_off[nbags] != c->M) FAIL(c, VBMF_ERR_INVALID, "%s: col_off must run from 0 to M = %lld", fn, (long long)c->M);
+    int64_t ns = 0;
+    for (int64_t b = 0; b < nbags; ++b) {
+        if (col_off[b + 1] <= col_off[b]) FAIL(c, VBMF_ERR_INVALID, "%s: bag %lld is empty or col_off decreases", fn, (long long)b);
+        ns += (col_off[b + 1] - col_off[b] + SCORE_CW - 1) / SCORE_CW;
+    }
+    if (score_resid_lds_bytes((int)c->H) > 64 * 1024) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (a slice's rows of A exceed 64 KiB of LDS)", fn, (long long)c->H);
+    *nslices = ns;
+    return VBMF_OK;
+}
+
+static int score_reserve(vbmf_ctx* c, int64_t doubles) {
+    if ((size_t)doubles * 8 <= c->score_bytes) return VBMF_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->score) HIPCHK(c, hipFree(c->score));
+    c->score = nullptr;
+    c->score_bytes = 0;
+    HIPCHK(c, hipMalloc((void**)&c->score, (size_t)doubles * 8));
+    c->score_bytes = (size_t)doubles * 8;
+    return VBMF_OK;
+}
+
+// uploads [col_off | chunk_off] to d_off and enqueues the two residual kernels: r2 of every bag into d_r2 (d_part: ns partials).
+// d_A: the device copy of A with element strides (sm, sh).
+static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, int64_t ns, long long* d_off, const double* d_A,
+                              long long sm, long long sh, double* d_part, double* d_r2) {
+    std::vector<long long> off((size_t)(2 * (nb + 1)));
+    off[(size_t)(nb + 1)] = 0;
+    for (int64_t b = 0; b <= nb; ++b) off[(size_t)b] = col_off[b];
+    for (int64_t b = 0; b < nb; ++b)
+        off[(size_t)(nb + 2 + b)] = off[(size_t)(nb + 1 + b)] + (col_off[b + 1] - col_off[b] + SCORE_CW - 1) / SCORE_CW;
+    HIPCHK(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                // (off is a local)
+    TRY(rebuild_B32_if_stale(c));
+    const size_t lds = score_resid_lds_bytes((int)c->H);
+    if (c->mode == MODE_F32)
+        hipLaunchKernelGGL((bag_resid_kernel<MODE_F32>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
+                           (long long)c->L, c->B32[c->bcur], c->Hp, (int)c->H, d_A, sm, sh, d_off, d_off + nb + 1, (int)nb, d_part);
+    else
+        hipLaunchKernelGGL((bag_resid_kernel<MODE_BF16>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
+                           (long long)c->L, c->B32[c->bcur], c->Hp, (int)c->H, d_A, sm, sh, d_off, d_off + nb + 1, (int)nb, d_part);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, c->stream, d_part, d_off + nb + 1, (int)nb, d_r2);
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
+extern "C" {
+
+// norm(Y - BHat*AHat')^2 of every bag (examples/mil_util.jl:476-479, :518-521) in one call, entry by entry in fp64
+int vbmf_bag_residuals(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const double* AHat, int64_t ldA, double* r2) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_bag_residuals";
+    int64_t ns = 0;
+    TRY(score_check(c, fn, nbags, col_off, &ns));
+    if (!AHat || !r2) FAIL(c, VBMF_ERR_INVALID, "%s: null AHat / r2", fn);
+    if (ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "%s: ldA < M", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    const int64_t nb = nbags, H = c->H;
+    // c->score: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | partials ns | A M H (column-major, ld M)]
+    const int64_t o_r2 = 2 * (nb + 1), o_part = o_r2 + nb, o_a = o_part + ns, total = o_a + c->M * H;
+    TRY(score_reserve(c, total));
+    double* d = c->score;
+    HIPCHK(c, hipMemcpy2DAsync(d + o_a, (size_t)c->M * 8, AHat, (size_t)ldA * 8, (size_t)c->M * 8, (size_t)H, hipMemcpyHostToDevice, c->stream));
+    TRY(score_launch_resid(c, nb, col_off, ns, reinterpret_cast<long long*>(d), d + o_a, 1, (long long)c->M, d + o_part, d + o_r2));
+    HIPCHK(c, memcpy_sync(c, r2, d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost));
+    for (int64_t b = 0; b < nb; ++b)
+        if (!std::isfinite(r2[b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
+    return VBMF_OK;
+}
+
+// lowerBound / lowerBoundTrimmed of every bag (examples/mil_util.jl:502-514 after a batched vbls!)
+int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int clamp, double trim, int grouped,
+                                    const double* ATVecHat, const double* diagSigmaATVec, const double* CA, const double* beta,
+                                    const double* SigmaA, const double* sigmaHat, const double* zeta, const double* eta,
+                                    const double* eta0, const double* zeta0, const double* a_pri, const double* b_pri,
+                                    const double* a_post, double* lb, double* r2) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_lower_bound_batched";
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse models only)", fn);
+    int64_t ns = 0;
+    TRY(score_check(c, fn, nbags, col_off, &ns));
+    if (!ATVecHat || !diagSigmaATVec || !CA || !beta || !SigmaA || !sigmaHat || !zeta || !eta || !eta0 || !zeta0 || !a_pri || !b_pri ||
+        !a_post || !lb)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only r2 may be NULL)", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    TRY(ensure_gram_B(c));
+    const int H = (int)c->H;
+    const int64_t nb = nbags, MH = (int64_t)c->M * H, h2 = (int64_t)H * H;
+    // c->score: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | partials ns | A | dS | CA | beta (M H each, vec(A') order) | SigmaA nb H^2
+    //            | sums nb H SCORE_NS | quad 2 nb]
+    const int64_t o_r2 = 2 * (nb + 1), o_part = o_r2 + nb, o_a = o_part + ns, o_ds = o_a + MH, o_ca = o_ds + MH, o_be = o_ca + MH,
+                  o_sa = o_be + MH, o_sums = o_sa + nb * h2, o_quad = o_sums + nb * H * SCORE_NS, total = o_quad + 2 * nb;
+    TRY(score_reserve(c, total));
+    double* d = c->score;
+    HIPCHK(c, hipMemcpyAsync(d + o_a, ATVecHat, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ds, diagSigmaATVec, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_be, beta, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_sa, SigmaA, (size_t)(nb * h2) * 8, hipMemcpyHostToDevice, c->stream));
+    long long* d_off = reinterpret_cast<long long*>(d);
+    TRY(score_launch_resid(c, nb, col_off, ns, d_off, d + o_a, (long long)H, 1, d + o_part, d + o_r2));
+    hipLaunchKernelGGL(bag_lb_sums_kernel, dim3((unsigned)nb), dim3(SCORE_THREADS), 0, c->stream, d + o_a, d + o_ds, d + o_ca, d + o_be,
+                       d + o_sa, c->st, c->lay, H, (double)c->Lg, d_off, trim, d + o_sums, d + o_quad);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> res((size_t)nb), sums((size_t)(total - o_sums)), buf((size_t)c->lay.total());
+    HIPCHK(c, hipMemcpyAsync(res.data(), d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), d + o_sums, sums.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, memcpy_sync(c, buf.data(), c->st, buf.size() * 8, hipMemcpyDeviceToHost));
+    LbSums s{};
+    lb_basis_sums(c, buf, s);
+    const bool trimmed = trim >= 0.0;
+    std::vector<LbGroup> grp((size_t)H);
+    const double* quad = sums.data() + (o_quad - o_sums);
+    for (int64_t b = 0; b < nb; ++b) {
+        const double Mb = (double)(col_off[b + 1] - col_off[b]);
+        const double* sb = sums.data() + (size_t)b * H * SCORE_NS;
+        double n_keep = 0, s_caq = 0, s_logds = 0;
+        for (int h = 0; h < H; ++h) {
+            const double* v = sb + (size_t)h * SCORE_NS;
+            n_keep += v[2]; s_caq += v[5]; s_logds += v[6];
+            // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
+            const bool cut = trimmed && !grouped;
+            grp[(size_t)h] = LbGroup{cut ? v[2] : Mb, cut ? v[3] : v[0], cut ? v[4] : v[1], a_pri[b * H + h], b_pri[b * H + h], a_post[b * H + h]};
+        }
+        s.M = Mb;
+        s.MH = trimmed ? n_keep : Mb * (double)H;
+        s.sig = sigmaHat[b]; s.zeta = zeta[b]; s.eta = eta[b];
+        s.hyp.eta0 = eta0[b]; s.hyp.zeta0 = zeta0[b];
+        s.quad = res[(size_t)b] + s.L * quad[2 * b] + quad[2 * b + 1];
+        s.s_caq = s_caq; s.s_logds = s_logds;
+        s.g = grp.data(); s.ng = H;
+        const double v = lb_assemble(s, clamp);
+        if (!std::isfinite(v) || !std::isfinite(s.quad) || !std::isfinite(s_caq) || !std::isfinite(s_logds))
+            FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite sum in bag %lld", fn, (long long)b);
+        lb[b] = v;
+        if (r2) r2[b] = res[(size_t)b];
+    }
+    return VBMF_OK;
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ module VBMatrixFactorizationHIP
 export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, updateCB!, updateSigma2!, updateYHat!,
        vbls!, vbls_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
+       residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!
 
@@ -619,6 +620,126 @@ function vbls_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameter
         p.alpha = [p.alpha0, p.alpha1]
     end
     return out
+end
+
+# ---- scoring many bags: what classify (examples/mil_util.jl:453-535) compares once vbls! has run ------------------------------
+# The bags go side by side into one context with the shared basis as its state; `body(h, off, M)` makes the scoring call.
+function with_scoring_ctx(body, Ys::Vector{Matrix{Float64}}, ps, variant::Int, fn::String)
+    nb = length(Ys)
+    (nb >= 1 && length(ps) == nb) || error("$fn: one parameter set per bag")
+    p0 = ps[1]
+    H, L = p0.H, size(Ys[1], 1)
+    for b in 1:nb
+        Y, p = Ys[b], ps[b]
+        size(Y, 1) == L || error("$fn: the bags have different L")
+        (size(Y, 2) >= 1 && (p.L, p.M, p.H) == (L, size(Y, 2), H)) || error("$fn: bag $b does not match its parameters")
+        (p.BHat == p0.BHat && p.SigmaB == p0.SigmaB && p.CB == p0.CB) || error("$fn: bag $b does not share BHat, SigmaB and CB with bag 1")
+    end
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    M = off[end]
+    Yall = reduce(hcat, Ys)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, variant, 0xffffffff, 1, 0, 0, 0, 0, 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        if variant == 0
+            ca0 = [p0.CA[i, i] for i in 1:H]; cb0 = [p0.CB[i, i] for i in 1:H]
+            zA = zeros(M, H)
+            chk(h[], ccall((:vbmf_set_state, libvbmf), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Float64, Ptr{Int64}, Int64, Int64),
+                h[], zA, M, p0.BHat, L, p0.SigmaA, p0.SigmaB, ca0, cb0, p0.sigma2, C_NULL, 0, 0))
+        else
+            for (b, p) in enumerate(ps)
+                (p.delta == p0.delta && p.gamma0 == p0.gamma0 && p.delta0 == p0.delta0) ||
+                    error("$fn: bag $b does not share delta, gamma0 and delta0 with bag 1")
+            end
+            hy = Ref(SparseHyper(1e-10, 1e-10, p0.gamma0, p0.delta0, p0.eta0, p0.zeta0))
+            z, o = zeros(M * H), ones(M * H)
+            chk(h[], ccall((:vbmf_sparse_set_state, libvbmf), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Float64, Float64, Ref{SparseHyper}, Ptr{Int64}, Int64, Int64),
+                h[], z, o, o, o, p0.BHat, L, p0.SigmaB, p0.CB, p0.delta, 1.0, 1.0, hy, C_NULL, 0, 0))
+        end
+        return body(h[], off, M)
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+
+function residual_batch_impl(Ys::Vector{Matrix{Float64}}, ps, variant::Int)
+    nb = length(Ys)
+    A = reduce(vcat, [Matrix{Float64}(p.AHat) for p in ps])
+    r2 = Array{Float64}(undef, nb)
+    with_scoring_ctx(Ys, ps, variant, "residual_batch") do h, off, M
+        chk(h, ccall((:vbmf_bag_residuals, libvbmf), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64}),
+                     h, nb, off, A, M, r2))
+    end
+    return sqrt.(r2)
+end
+
+"""
+norm(Y - BHat*AHat') of every bag (examples/mil_util.jl:483-484, :523-524) in ONE device call, formed entry by entry in fp64 on the
+device (vbmf_bag_residuals): `ps` are the parameter sets a `vbls_batch!` filled.
+"""
+residual_batch(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}) = residual_batch_impl(Ys, ps, 0)
+residual_batch(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}) = residual_batch_impl(Ys, ps, 1)
+residual_batch(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameters}) = residual_batch_impl(Ys, ps, 1)
+
+# apri, bpri, apost: per column of A and bag (H x nb) the ARD hyper-prior (shape, rate) and the posterior shape; trim < 0: lowerBound
+function bound_batch_impl(Ys::Vector{Matrix{Float64}}, ps, trim::Float64, grouped::Bool, apri::Matrix{Float64}, bpri::Matrix{Float64},
+                          apost::Matrix{Float64})
+    nb = length(Ys)
+    H = ps[1].H
+    H <= 64 || error("lowerBound_batch: H = $H > 64")
+    a = reduce(vcat, [Vector{Float64}(p.ATVecHat) for p in ps]); ds = reduce(vcat, [Vector{Float64}(p.diagSigmaATVec) for p in ps])
+    ca = reduce(vcat, [Vector{Float64}(p.CA) for p in ps]); be = reduce(vcat, [Vector{Float64}(p.beta) for p in ps])
+    SA = Array{Float64}(undef, H, H, nb)
+    for b in 1:nb
+        SA[:, :, b] = ps[b].SigmaA
+    end
+    sg = Float64[p.sigmaHat for p in ps]; ze = Float64[p.zeta for p in ps]; et = Float64[p.eta for p in ps]
+    e0 = Float64[p.eta0 for p in ps]; z0 = Float64[p.zeta0 for p in ps]
+    lb = Array{Float64}(undef, nb)
+    with_scoring_ctx(Ys, ps, 1, "lowerBound_batch") do h, off, M
+        chk(h, ccall((:vbmf_sparse_lower_bound_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Cint, Float64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}),
+            h, nb, off, 1, trim, grouped, a, ds, ca, be, SA, sg, ze, et, e0, z0, apri, bpri, apost, lb, C_NULL))
+    end
+    return lb
+end
+
+function bound_batch(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, trim::Float64)
+    H = ps[1].H
+    for (b, p) in enumerate(ps)
+        (p.H1 == 0 && isempty(p.labels)) || error("lowerBound_batch: bag $b has labels; use lowerBound per bag")
+    end
+    apri = Float64[p.alpha0 for h in 1:H, p in ps]; bpri = Float64[p.beta0 for h in 1:H, p in ps]
+    apost = Float64[p.alpha for h in 1:H, p in ps]
+    return bound_batch_impl(Ys, ps, trim, false, apri, bpri, apost)
+end
+
+function bound_batch(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameters}, trim::Float64)
+    H = ps[1].H
+    apri = Float64[h <= p.H0 ? p.alpha00 : p.alpha01 for h in 1:H, p in ps]
+    bpri = Float64[h <= p.H0 ? p.beta00 : p.beta01 for h in 1:H, p in ps]
+    apost = Float64[h <= p.H0 ? p.alpha0 : p.alpha1 for h in 1:H, p in ps]
+    return bound_batch_impl(Ys, ps, trim, true, apri, bpri, apost)
+end
+
+"""
+`[lowerBound(Y, p) for (Y, p) in zip(Ys, ps)]` in ONE device call (src/vbmf_sparse.jl:435-471, src/vbmf_dual.jl:556-599;
+examples/mil_util.jl:504): one model type, one fixed basis, no labels, H <= 64 (vbmf_sparse_lower_bound_batched).
+"""
+lowerBound_batch(Ys::Vector{Matrix{Float64}}, ps) = bound_batch(Ys, ps, -1.0)
+
+"`[lowerBoundTrimmed(Y, p, trim) for (Y, p) in zip(Ys, ps)]` in ONE device call (src/vbmf_sparse.jl:478-489, examples/mil_util.jl:505)"
+function lowerBoundTrimmed_batch(Ys::Vector{Matrix{Float64}}, ps, trim = 1e-1)
+    trim >= 0 || error("lowerBoundTrimmed_batch: trim must be >= 0")
+    return bound_batch(Ys, ps, Float64(trim))
 end
 
 "vbmf_dual! -- src/vbmf_dual.jl:455-530 (returns d); est_priors: the hyper-prior fits of :393-434 run on the device"
