@@ -214,10 +214,10 @@ int vbmf_sparse_lower_bound(vbmf_ctx* ctx, int clamp, double* lb);
 int vbmf_sparse_lower_bound_trimmed(vbmf_ctx* ctx, int clamp, double trim, double* lb);
 
 /* ---- per-bag scoring: what the MIL classifier compares after a batched vbls! (examples/mil_util.jl:469-530) ----
- * The context's Y is the bags side by side (col_off as in vbmf_run_fixed_basis_batched).  Both entries refuse, with VBMF_ERR_INVALID
+ * The context's Y is the bags side by side (col_off as in vbmf_run_fixed_basis_batched).  All entries refuse, with VBMF_ERR_INVALID
  * and before any launch: col_off not running from 0 to M or not increasing (an empty bag), a *_DIAGVAR context, nranks > 1, a NULL
  * required pointer.  A non-finite sum in a bag returns VBMF_ERR_NUMERIC and vbmf_last_error names the bag.  The context's state is
- * not changed by either call.
+ * not changed by any of them.
  *
  * vbmf_bag_residuals: r2[b] = ||Y_b - BHat*AHat_b'||_F^2, the square of norm(Y - BHat*AHat') of examples/mil_util.jl:476-479 (and of
  * norm(YHat - Y), :518-521), for every bag.  Formed entry by entry in fp64 from Y as stored (what vbmf_get_Y returns), the context's
@@ -225,6 +225,24 @@ int vbmf_sparse_lower_bound_trimmed(vbmf_ctx* ctx, int clamp, double trim, doubl
  * AHat (M x H column-major, ldA >= M) -- never from the trace form ||Y||^2 - 2 tr(B'YA) + tr(A'A B'B), whose cancellation costs the
  * digits the comparison between two models needs.  Basic and sparse-family contexts, any H up to 1024. */
 int vbmf_bag_residuals(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, const double* AHat, int64_t ldA, double* r2);
+/* vbmf_bag_least_squares: ols / rls of examples/mil_util.jl:159-171 and the norm(Y - BHat*AT) of :483-484 for every bag of the
+ * context's Y -- what classify's "ols" and "rls" branches compute per bag (examples/mil_util.jl:457-468).  The context supplies only Y;
+ * the basis is the argument BHat (L x H fp64 column-major, ldB >= L), used in fp64 as given: H is the call's own (1 <= H <= 64,
+ * independent of the H the context was created with, so models of different rank share one upload), the context's state is neither read
+ * nor changed (none needs to be set), and any context kind works as for vbmf_bag_residuals.
+ *   X   (H x M column-major, ldX >= H, may be NULL): columns col_off[b] .. col_off[b+1]-1 = inv(BHat'BHat + lambda I) BHat' Y_b, the
+ *       reference's ols(Y_b, BHat) for lambda == 0 and rls(Y_b, BHat, lambda) for lambda > 0
+ *   r2  (nbags, may be NULL; not both): r2[b] = ||Y_b - BHat X_b||_F^2
+ * All fp64 from Y as stored (what vbmf_get_Y returns).  K = inv(BHat'BHat + lambda I) is formed once per call on the device by the
+ * control chain's blocked inverse; per column z = BHat'y, x = K z, and the residual entry by entry as y - BHat x -- never
+ * ||y||^2 - z'Kz, which cancels 400- to 3000-fold on fitted bags.  Every sum has a fixed order and no bag's numbers depend on where
+ * it sits in Y or on the other bags of the call.
+ * Refused before any launch: H < 1 or H > 64 (VBMF_ERR_UNSUPPORTED); with VBMF_ERR_INVALID what the block above lists, lambda < 0 or
+ * not finite, a non-finite entry of BHat, ldB < L, ldX < H, NULL BHat, X and r2 both NULL.  A pivot of BHat'BHat + lambda I that is
+ * not positive or not finite (a rank-deficient basis at lambda == 0: the case rls exists for, :463-464) returns VBMF_ERR_NUMERIC and
+ * leaves X and r2 unwritten. */
+int vbmf_bag_least_squares(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, const double* BHat, int64_t ldB, int64_t H, double lambda,
+                           double* X, int64_t ldX, double* r2);
 /* lowerBound (src/vbmf_sparse.jl:435-471; dual src/vbmf_dual.jl:556-599; trial src/vbmf_trial.jl:630-680) for trim < 0 and
  * lowerBoundTrimmed (src/vbmf_sparse.jl:478-489; dual :606-617; trial :687-698) for trim >= 0 of every bag, as called per bag by
  * examples/mil_util.jl:502-514.  Sparse-family context, homoscedastic, one fixed basis: BHat, SigmaB, CB, delta and the hyper-priors

@@ -14,7 +14,11 @@ the classifier's own gate (examples/mil_util.jl:393-416).
         166 x 30 at H = 5 against two models, per bag amortised, one warm-up and five timed windows per classifier.  a: the batched
         fits, then the scores one bag at a time -- NumPy residuals, lowerBound / lowerBoundTrimmed through a context per bag; it uses
         nothing newer than the batched fits, so it also runs on a build without the scoring entries.  b: classify_batch.  With
-        --profile: three classify_batch calls per classifier and no timing, for rocprofv3 --kernel-trace --stats)"""
+        --profile: three classify_batch calls per classifier and no timing, for rocprofv3 --kernel-trace --stats.
+        The least-squares classifiers "ols", "rls" and "min_err" (:457-468, :493-501) run at the same shape.  a: inv(B'B)*B'*Y and
+        the residual per bag in NumPy on the host, for min_err the batched fits and NumPy residuals.  b: classify_bags, for
+        ols / rls also on bags uploaded once.
+        --algs ols,rls,min_err restricts either to the named classifiers)"""
 import os
 import sys
 import time
@@ -129,7 +133,14 @@ def score_models(L, H, H1):
 def classify_per_bag_scores(res0, res1, Ys, alg, threshold=1e-1):
     """classify over many bags with the batched fits and the scores one bag at a time (what a build without the scoring entries does)"""
     L = Ys[0].shape[0]
-    if alg == "lower_bound":
+    if alg in ("ols", "rls"):                                          # the reference's own per-bag expressions, :159-171, :483-484
+        errs = []
+        for res in (res0, res1):
+            B = res.BHat
+            lam = np.eye(B.shape[1]) * (0.0 if alg == "ols" else 1e-2)
+            errs.append(np.array([np.linalg.norm(Y - B @ (np.linalg.inv(B.T @ B + lam) @ B.T @ Y)) for Y in Ys]))
+        return (errs[0] > errs[1]).astype(np.int64), errs[0], errs[1]
+    if alg in ("lower_bound", "min_err"):
         H, H0 = res0.H, res0.H - res0.H1
         ps0 = []
         for Y in Ys:
@@ -141,6 +152,9 @@ def classify_per_bag_scores(res0, res1, Ys, alg, threshold=1e-1):
         full_cov = Ys[0].shape[1] * H0 < 1600                          # (one bag size here: one group)
         pkg.vbls_sparse_batch_(Ys, ps0, 20, full_cov=full_cov)
         pkg.vbls_sparse_batch_(Ys, ps1, 20, full_cov=full_cov)
+        if alg == "min_err":
+            e0, e1 = (np.array([np.linalg.norm(Y - p.BHat @ p.AHat.T) for Y, p in zip(Ys, ps)]) for ps in (ps0, ps1))
+            return np.where(np.abs((e0 - e1) / e0) < threshold, 0, 1), e0, e1
         e0 = np.array([pkg.lowerBound(Y, p) for Y, p in zip(Ys, ps0)])
         e1 = np.array([pkg.lowerBoundTrimmed(Y, p, threshold) for Y, p in zip(Ys, ps1)])
         return (e1 > e0).astype(np.int64), e0, e1
@@ -164,18 +178,25 @@ def score_main(how, prof):
     L, M, H, H1, nb = 166, 30, 5, 2, 256
     models, draw = score_models(L, H, H1)
     Ys = [draw(b % 2, M).astype(np.float32).astype(np.float64) for b in range(nb)]
+    algs = ("vbls", "dual", "lower_bound", "ols", "rls", "min_err")
+    if "--algs" in sys.argv:
+        algs = tuple(sys.argv[sys.argv.index("--algs") + 1].split(","))
+    models["ols"] = models["rls"] = models["vbls"]                     # classify reads nothing but their BHat
+    models["min_err"] = models["lower_bound"]
     print(f"# classify over {nb} bags of {L} x {M} at H = {H}, two models, per BAG amortised (ms): "
-          + ("(a) batched fits, scores one bag at a time" if how == "a" else "(b) classify_batch"))
+          + ("(a) batched fits, scores one bag at a time; ols / rls per bag in NumPy" if how == "a"
+             else "(b) classify_batch; ols / rls / min_err: classify_bags"))
     print(f"{'classifier':12s} {'median':>9s} {'min':>9s} {'max':>9s} {'label 1':>8s}")
-    for alg in ("vbls", "dual", "lower_bound"):
+    for alg in algs:
         res0, res1 = models[alg]
+        batch = pkg.classify_batch if alg in ("vbls", "dual", "lower_bound") else getattr(pkg, "classify_bags", None)
         run = ((lambda: classify_per_bag_scores(res0, res1, Ys, alg)) if how == "a"
-               else (lambda: pkg.classify_batch(res0, res1, Ys, alg)))
+               else (lambda: batch(res0, res1, Ys, alg)))
         labels, _, _ = run()                                            # warm-up: library, kernels, allocator
         if prof:
             for _ in range(3):
                 run()
-            print(f"profiled: 3 x classify_batch {alg}")
+            print(f"profiled: 3 x {batch.__name__} {alg}")
             continue
         ts = []
         for _ in range(5):
@@ -184,6 +205,15 @@ def score_main(how, prof):
             ts.append((time.perf_counter() - t0) / nb * 1e3)
         pkg.invalidate()
         print(f"{alg:12s} {np.median(ts):9.4f} {min(ts):9.4f} {max(ts):9.4f} {int(np.sum(labels)):8d}")
+        if how == "b" and alg in ("ols", "rls"):                        # the same on bags uploaded once (the two device calls alone)
+            bags = pkg.Bags(Ys, H)
+            ts = []
+            for _ in range(6):
+                t0 = time.perf_counter()
+                batch(res0, res1, bags, alg)
+                ts.append((time.perf_counter() - t0) / nb * 1e3)
+            bags.close()
+            print(f"{alg + ' uploaded':12s} {np.median(ts[1:]):9.4f} {min(ts[1:]):9.4f} {max(ts[1:]):9.4f} {int(np.sum(labels)):8d}")
 
 
 def main():

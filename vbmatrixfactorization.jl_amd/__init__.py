@@ -47,7 +47,8 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
            "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags",
-           "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch"]
+           "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
+           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
 # elements the field is left None and computed on demand with updateYHat_ (8 GB at 100k x 10k).
@@ -1402,9 +1403,10 @@ def _full_cov_groups(Ms, H0):
     return full, diag
 
 
-def _factorize_bags(Ys, res, niter):
+def _factorize_bags(Ys, res, niter, score0=None):
     """factorize_bag (examples/mil_util.jl:393-416) over many bags: per bag (params0, params1), fitted by the batched vbls! in at
-    most two groups per basis (full_cov or not), and scored where they sit: returns (L0, L1 as functions of the threshold)."""
+    most two groups per basis (full_cov or not), and scored where they sit: returns (L0, L1 as functions of the threshold).
+    score0(bags0, ps0): what is taken from the truncated basis' fit in place of lowerBound_batch (classify_bags' "min_err")."""
     H, H1 = int(res.H), int(res.H1)
     tb = _truncated_basis(res)
     L0, sets1 = np.empty(len(Ys)), []
@@ -1421,7 +1423,7 @@ def _factorize_bags(Ys, res, niter):
         bags0, bags1 = SparseBags(sub, tb["H"]), SparseBags(sub, H)
         try:
             vbls_sparse_batch_(bags0, ps0, niter, full_cov=full_cov)
-            L0[idx] = lowerBound_batch(bags0, ps0)
+            L0[idx] = lowerBound_batch(bags0, ps0) if score0 is None else score0(bags0, ps0)
             vbls_sparse_batch_(bags1, ps1, niter, full_cov=full_cov)
             sets1.append((idx, bags1, ps1))
         except BaseException:
@@ -1441,7 +1443,7 @@ def classify_batch(res0, res1, Ys, class_alg, threshold=1e-1, niter=None):
       "lower_bound"  factorize_bag on res0 (a vbmf_sparse_parameters with H1 > 0; res1 is not read, as in the reference), 20
                      iterations, full_cov per bag by M_b (H - H1) < 1600; err0 = lowerBound of the truncated basis' fit, err1 =
                      lowerBoundTrimmed(threshold) of the whole basis' fit, label 1 where err1 > err0
-    niter overrides the iteration count.  "ols", "rls" and "min_err" are not built here."""
+    niter overrides the iteration count.  "ols", "rls" and "min_err" are not taken here: classify_bags takes all six."""
     fn = "classify_batch"
     refuse = _score_refuser(fn)
     if class_alg not in _CLASS_ALGS:
@@ -1488,6 +1490,158 @@ def classify_batch(res0, res1, Ys, class_alg, threshold=1e-1, niter=None):
     scale = L * np.asarray(Ms, dtype=np.float64)
     err0, err1 = err0 / scale, err1 / scale                              # :523-524
     return np.where(err0 < err1, 0, 1).astype(np.int64), err0, err1      # :526-530
+
+
+# =================================================================================================
+# Least-squares classifiers over many bags -- ols / rls (examples/mil_util.jl:159-171), classify's "ols", "rls" and "min_err"
+# branches (:457-468, :483-501) and test_classification (:558-587); include/vbmf_hip.h: vbmf_bag_least_squares
+# =================================================================================================
+_LS_MAX_H = 64
+_LS_ALGS = ("ols", "rls", "min_err")
+
+
+def _ls_refuser(fn):
+    def refuse(why):
+        raise ValueError(f"{fn}: {why}")
+    return refuse
+
+
+def _ls_basis(fn, B, lam):
+    """The caller's basis as an fp64 L x H matrix, after the refusals that need nothing else."""
+    refuse = _ls_refuser(fn)
+    lam = float(lam)
+    if not (lam >= 0.0 and np.isfinite(lam)):
+        refuse(f"lam = {lam} (must be finite and >= 0)")
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim != 2 or B.shape[1] < 1:
+        refuse(f"B must be an L x H matrix (got shape {B.shape})")
+    if B.shape[1] > _LS_MAX_H:
+        refuse(f"H = {B.shape[1]} > {_LS_MAX_H}")
+    if not np.all(np.isfinite(B)):
+        refuse("B has non-finite entries")
+    return B
+
+
+def _ls_open(fn, Ys, Bs):
+    """(the uploaded bags, whether they were opened here) for bases Bs (checked by _ls_basis), which all must be L x H_k; the
+    upload is a Bags at the first basis' rank -- the entry takes every call's own H."""
+    refuse = _ls_refuser(fn)
+    if isinstance(Ys, (Bags, SparseBags)):
+        L, own = Ys.L, False
+    else:
+        Ys = list(Ys)
+        L, _ = _batch_shapes(Ys, Bs[0].shape[1], refuse)
+        own = True
+    for B in Bs:
+        if B.shape[0] != L:
+            refuse(f"B is {B.shape[0]} x {B.shape[1]}, the bags have L = {L} rows (B must be L x H)")
+    return (Bags(Ys, Bs[0].shape[1]) if own else Ys), own
+
+
+def _bags_ctx(bags):
+    return bags.session.ctx if isinstance(bags, Bags) else bags.ctx
+
+
+def _ls_call(fn, Ys, B, lam, want_X, want_r2):
+    B = _ls_basis(fn, B, lam)
+    bags, own = _ls_open(fn, Ys, [B])
+    try:
+        X, r2 = _bags_ctx(bags).bag_least_squares(bags.col_off, B, lam, want_X=want_X, want_r2=want_r2)
+    finally:
+        if own:
+            bags.close()
+    if want_X:
+        X = [np.array(X[:, c0:c1], order="F") for c0, c1 in zip(bags.col_off[:-1], bags.col_off[1:])]
+    return X, r2
+
+
+def ols_batch(Ys, B):
+    """[ols(Y, B) for Y in Ys] = inv(B'B)*B'*Y per bag (examples/mil_util.jl:159-161) in one device call, in fp64 from Y as the device
+    stores it and B as given.  Ys: a list of L x M_b arrays, or an uploaded Bags / SparseBags (one upload serves several bases, of
+    any rank); B: L x H, H <= 64.  Returns the list of H x M_b arrays."""
+    return _ls_call("ols_batch", Ys, B, 0.0, True, False)[0]
+
+
+def rls_batch(Ys, B, lam):
+    """[rls(Y, B, lam) for Y in Ys] = inv(B'B + lam*I)*B'*Y per bag (examples/mil_util.jl:168-171) in one device call; arguments as
+    ols_batch, lam >= 0."""
+    return _ls_call("rls_batch", Ys, B, lam, True, False)[0]
+
+
+def ls_residual_batch(Ys, B, lam=0.0):
+    """norm(Y_b - B*X_b) with X_b the ols (lam = 0) or rls estimate of every bag (examples/mil_util.jl:483-484 after :459 / :466), in
+    the same device pass that forms X_b, entry by entry in fp64.  Arguments as rls_batch.  Returns the (nbags,) array."""
+    return np.sqrt(_ls_call("ls_residual_batch", Ys, B, lam, False, True)[1])
+
+
+def classify_bags(res0, res1, Ys, class_alg="ols", threshold=1e-1, niter=None):
+    """classify (examples/mil_util.jl:453-535) over many bags with the reference's default class_alg: (labels, err0, err1) as arrays.
+      "ols", "rls"   err = norm(Y - BHat*AT) with AT = ols(Y, BHat) / rls(Y, BHat, 1e-2) (:457-468, :483-484), label 1 where
+                     err0 > err1; any two models that have a BHat (only BHat is read), of the same or different H <= 64; one upload,
+                     one device call per model
+      "min_err"      factorize_bag on res0 (a vbmf_sparse_parameters with 0 < H1 < H; res1 is not read), 20 iterations, full_cov per
+                     bag by M_b (H - H1) < 1600; err0 = norm(Y - YHat) of the truncated basis' fit, err1 of the whole basis' fit,
+                     label 0 where |(err0 - err1)/err0| < threshold (:493-501)
+      "vbls", "dual", "lower_bound"   classify_batch, unchanged
+    Ys: a list of L x M_b arrays; for "ols" / "rls" also an uploaded Bags / SparseBags.  niter overrides the iteration count of the
+    iterating classifiers."""
+    fn = "classify_bags"
+    refuse = _ls_refuser(fn)
+    if class_alg in _CLASS_ALGS:
+        return classify_batch(res0, res1, Ys, class_alg, threshold=threshold, niter=niter)
+    if class_alg not in _LS_ALGS:
+        refuse(f"class_alg = {class_alg!r} (one of {', '.join(_LS_ALGS + _CLASS_ALGS)})")
+    if class_alg == "min_err":
+        if type(res0) is not vbmf_sparse_parameters or not 0 < int(res0.H1) < int(res0.H):
+            refuse("min_err needs res0 to be a vbmf_sparse_parameters with 0 < H1 < H (factorize_bag)")
+        Ys = list(Ys)
+        _batch_shapes(Ys, int(res0.H), refuse)
+        err0, sets1 = _factorize_bags(Ys, res0, 20 if niter is None else int(niter), score0=residual_batch)
+        err1 = np.empty(len(Ys))
+        try:
+            for idx, bags1, ps1 in sets1:
+                err1[idx] = residual_batch(bags1, ps1)
+        finally:
+            for _, bags1, _ in sets1:
+                bags1.close()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            close = np.abs((err0 - err1) / err0) < threshold             # :497
+        return np.where(close, 0, 1).astype(np.int64), err0, err1
+    lam = 0.0 if class_alg == "ols" else 1e-2                            # :466
+    Bs = []
+    for k, r in enumerate((res0, res1)):
+        if getattr(r, "BHat", None) is None:
+            refuse(f"res{k} ({type(r).__name__}) has no BHat")
+        Bs.append(_ls_basis(fn, r.BHat, lam))
+    bags, own = _ls_open(fn, Ys, Bs)
+    try:
+        ctx = _bags_ctx(bags)
+        err0, err1 = (np.sqrt(ctx.bag_least_squares(bags.col_off, B, lam, want_X=False)[1]) for B in Bs)
+    finally:
+        if own:
+            bags.close()
+    return (err0 > err1).astype(np.int64), err0, err1                    # :487-491
+
+
+def test_classification_batch(res0, res1, Ys, labels, class_alg="ols", threshold=1e-1):
+    """test_classification (examples/mil_util.jl:558-587) over many bags: (mer, eer, fp, fn, n0, n1) from classify_bags' labels and the
+    true labels (0 / 1, one per bag).  label - est_label == 1 counts as a false negative, -1 as a false positive; a count of zero in
+    a denominator gives inf / nan as Julia's float division does."""
+    labels = np.asarray(labels).reshape(-1)
+    est = np.asarray(classify_bags(res0, res1, Ys, class_alg, threshold=threshold)[0]).reshape(-1)
+    if labels.shape != est.shape:
+        raise ValueError(f"test_classification_batch: {est.size} bags but {labels.size} labels")
+    diff = labels.astype(np.int64) - est.astype(np.int64)
+    fn_, fp = int(np.sum(diff == 1)), int(np.sum(diff == -1))
+    n0 = int(np.sum(labels == 0))
+    n1 = int(labels.size - n0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mer = float(np.float64(fp + fn_) / np.float64(labels.size))
+        eer = float((np.float64(fp) / np.float64(n0) + np.float64(fn_) / np.float64(n1)) / 2)
+    return mer, eer, fp, fn_, n0, n1
+
+
+test_classification_batch.__test__ = False        # (the reference's name; not a test for a collector that meets it)
 
 
 # =================================================================================================

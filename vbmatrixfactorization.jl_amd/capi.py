@@ -39,7 +39,7 @@ SYMBOLS = [
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
-    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched",
+    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
@@ -134,6 +134,7 @@ def lib():
     L.vbmf_debug_set.argtypes = [vp, i32, i64]
     L.vbmf_bag_residuals.argtypes = [vp, i64, C.POINTER(i64), dp, i64, dp]
     L.vbmf_sparse_lower_bound_batched.argtypes = [vp, i64, C.POINTER(i64), i32, C.c_double, i32] + [dp] * 15
+    L.vbmf_bag_least_squares.argtypes = [vp, i64, C.POINTER(i64), dp, i64, i64, C.c_double, dp, i64, dp]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
     L.vbmf_sparse_set_SigmaA.argtypes = [vp, dp]
     L.vbmf_sparse_get_SigmaA.argtypes = [vp, dp]
@@ -453,6 +454,22 @@ class Context:
         r2 = np.empty(max(nb, 0))
         self._chk(self._lib.vbmf_bag_residuals(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(A), self.M, _dptr(r2)))
         return r2
+
+    def bag_least_squares(self, col_off, BHat, lam=0.0, want_X=True, want_r2=True):
+        """inv(BHat'BHat + lam I) BHat' Y_b and ||Y_b - BHat X_b||_F^2 of every bag (vbmf_bag_least_squares): bag b = columns
+        col_off[b] .. col_off[b+1]-1, BHat (L, H) the caller's fp64 basis with its own H <= 64 (not this context's; no state is read).
+        Returns (X (H, M) or None, r2 (nbags,) or None).  The state is not changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        B = _fcol(BHat)
+        if B.ndim != 2 or B.shape[0] != self.L:
+            raise ValueError(f"BHat must be ({self.L}, H), got {B.shape}")
+        H = B.shape[1]
+        X = np.empty((H, self.M), order="F") if want_X else None
+        r2 = np.empty(max(nb, 0)) if want_r2 else None
+        self._chk(self._lib.vbmf_bag_least_squares(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(B), self.L, H, float(lam),
+                                                   _dptr(X), H, _dptr(r2)))
+        return X, r2
 
     def sparse_lower_bound_batched(self, col_off, ATVecHat, diagSigmaATVec, CA, beta, SigmaA, sigmaHat, zeta, eta, eta0, zeta0,
                                    a_pri, b_pri, a_post, trim=None, clamp=True, grouped=False):

@@ -14,6 +14,16 @@
 //   bag_resid_fold_kernel  r2[b] = the bag's slice partials, summed in slice order
 //   bag_lb_sums_kernel   one workgroup per bag: the M_b*H-long sums of lowerBound per column h (SCORE_NS values each) and the two
 //                        H x H contractions of its data term
+// Least squares against a caller's fp64 basis (vbmf_bag_least_squares; ols / rls of examples/mil_util.jl:159-171 and the
+// norm(Y - BHat*AT) of :483-484), H <= 64.  B travels as fp64 row-major [L][H] (reads coalesce over h); nothing of the context's state
+// is read:
+//   bag_ls_gram_kernel     B'B partials over LS_ROWS rows of B per workgroup, each entry a plain fma chain in row order
+//   bag_ls_inverse_kernel  one workgroup: the partials summed in chunk order, + lambda I, inverted by the control chain's blocked
+//                          sweep (spd_inverse_lds4); K = inv(B'B + lambda I) to global, both triangles, and the bad-pivot flag
+//   bag_ls_kernel          one workgroup per bag slice (the slices of bag_resid_kernel): z = B'y per column with Y staged LS_ROWS rows
+//                          at a time in LDS, x = K z, then the slice's sum of (y - B x)^2 entry by entry -- NOT ||y||^2 - z'Kz, which
+//                          cancels 400- to 3000-fold on fitted bags.  Every sum has one order fixed by (L, H, the slice's width): a
+//                          bag's X and r2 do not depend on where it sits in Y or on the other bags of the call.
 // Data term of the per-bag bound: r2 + L tr(A'A SigmaB) + tr(SigmaA (B'B + L SigmaB)), algebraically the reference's
 // ||Y||^2 - 2 tr(B'YA) + tr((A'A + SigmaA)(B'B + L SigmaB)) (src/vbmf_sparse.jl:439-440) with the direct residual of the same
 // call in place of its three cancelling terms; so neither tr(B'Y_b A_b) nor ||Y_b||^2 is formed here.
@@ -30,6 +40,30 @@ constexpr int SCORE_THREADS = 256;
 constexpr int SCORE_NS = 7;
 // dynamic LDS of bag_resid_kernel: the slice's rows of A
 inline size_t score_resid_lds_bytes(int H) { return (size_t)SCORE_CW * H * sizeof(double); }
+
+// vbmf_bag_least_squares
+constexpr int LS_MAX_H = 64;
+constexpr int LS_ROWS = 256;       // rows of B per Gram workgroup; rows of a slice of Y staged in LDS at a time
+// dynamic LDS of bag_ls_kernel: K | z | x | the staged rows of Y | the row stripes' shares of z
+inline size_t score_ls_lds_bytes(int H) {
+    const int P = SCORE_CW * H;
+    return (size_t)(H * H + 2 * P + SCORE_CW * LS_ROWS + (P > SCORE_THREADS ? P : SCORE_THREADS)) * sizeof(double);
+}
+
+// Y[l, m] as stored, from the pass-2 tiles
+template <int MODE>
+__device__ __forceinline__ float score_y_at(const uint4* __restrict__ Y2, int KSpad, long long l, long long m) {
+    constexpr int KSTEP = (MODE == MODE_F32) ? 8 : 16;
+    const int xt = (int)(l >> 5), c = (int)(l & 31);
+    const int ks = (int)(m / KSTEP), wi = (int)(m % KSTEP);
+    int half, e;
+    if (MODE == MODE_F32) { half = wi >> 2; e = wi & 3; }
+    else { half = (wi >> 2) & 1; e = 4 * (wi >> 3) + (wi & 3); }
+    const uint4 f = Y2[((long long)xt * KSpad + ks) * 64 + half * 32 + c];
+    const unsigned wd[4] = {f.x, f.y, f.z, f.w};
+    if (MODE == MODE_F32) return bitsf(wd[e]);
+    return bf2f((unsigned short)((wd[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
+}
 
 // the last bag whose first slice number is <= w
 __device__ __forceinline__ int score_bag_of(const long long* __restrict__ chunk_off, int nbags, long long w) {
@@ -49,7 +83,6 @@ __global__ __launch_bounds__(SCORE_THREADS) void bag_resid_kernel(const uint4* _
                                                                   const long long* __restrict__ col_off,
                                                                   const long long* __restrict__ chunk_off, int nbags,
                                                                   double* __restrict__ part) {
-    constexpr int KSTEP = (MODE == MODE_F32) ? 8 : 16;
     extern __shared__ __attribute__((aligned(16))) double Al[];      // [SCORE_CW][H]
     __shared__ double red[SCORE_THREADS / 64];
     const long long w = blockIdx.x;
@@ -67,17 +100,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void bag_resid_kernel(const uint4* _
     for (long long t = threadIdx.x; t < n; t += SCORE_THREADS) {
         const long long l = t % L;
         const int cc = (int)(t / L);
-        const long long m = m0 + cc;
-        const int xt = (int)(l >> 5), c = (int)(l & 31);
-        const int ks = (int)(m / KSTEP), wi = (int)(m % KSTEP);
-        int half, e;
-        if (MODE == MODE_F32) { half = wi >> 2; e = wi & 3; }
-        else { half = (wi >> 2) & 1; e = 4 * (wi >> 3) + (wi & 3); }
-        const uint4 f = Y2[((long long)xt * KSpad + ks) * 64 + half * 32 + c];
-        const unsigned wd[4] = {f.x, f.y, f.z, f.w};
-        float v;
-        if (MODE == MODE_F32) v = bitsf(wd[e]);
-        else v = bf2f((unsigned short)((wd[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
+        const float v = score_y_at<MODE>(Y2, KSpad, l, m0 + cc);
         const float* brow = B32 + l * Hp;
         const double* arow = Al + cc * H;
         double pred = 0.0;
@@ -96,6 +119,122 @@ __global__ void bag_resid_fold_kernel(const double* __restrict__ part, const lon
     double s = 0.0;
     for (long long w = chunk_off[b]; w < chunk_off[b + 1]; ++w) s += part[w];
     r2[b] = s;
+}
+
+// Bt: B row-major [L][H].  Gp: [gridDim.x][H * H]; entry (i, j) and entry (j, i) are the same products in the same order.
+__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_gram_kernel(const double* __restrict__ Bt, long long L, int H,
+                                                                    double* __restrict__ Gp) {
+    const long long l0 = (long long)blockIdx.x * LS_ROWS;
+    const long long l1 = l0 + LS_ROWS < L ? l0 + LS_ROWS : L;
+    for (int e = threadIdx.x; e < H * H; e += SCORE_THREADS) {
+        const int i = e / H, j = e % H;
+        double s = 0.0;
+        for (long long l = l0; l < l1; ++l) s = fma(Bt[l * H + i], Bt[l * H + j], s);
+        Gp[(long long)blockIdx.x * H * H + e] = s;
+    }
+}
+
+// K[H][H] = inv(sum of the nchunk Gram partials + lambda I); *bad != 0: a pivot was not positive / finite.  LDS: spd_inverse_lds_bytes(4).
+__global__ __launch_bounds__(256) void bag_ls_inverse_kernel(const double* __restrict__ Gp, int nchunk, int H, double lambda,
+                                                             double* __restrict__ K, int* __restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) double Wl[];
+    double logdet;
+    int notpd;
+    spd_inverse_lds4<LS_MAX_H / 16>(Wl, H, [&](int i, int j) {
+        double s = 0.0;
+        for (int q = 0; q < nchunk; ++q) s += Gp[((long long)q * H + i) * H + j];
+        return i == j ? s + lambda : s;
+    }, &logdet, &notpd);
+    __syncthreads();
+    for (int t = threadIdx.x; t < H * H; t += 256) K[t] = spd_inv_at<LS_MAX_H / 16>(Wl, t / H, t % H);
+    if (threadIdx.x == 0) *bad = notpd;
+}
+
+// X: [M][H] (column m of the H x M estimate at X + m * H) or nullptr; part: the slices' residual partials or nullptr.
+// Output o = (column cc, component h) = cc * H + h of the slice's P = nc * H.  z: with P <= 256 the threads split into S = 256 / P row
+// stripes (rows s, s + S, ... of every staged tile, tiles in order), whose shares meet in LDS in stripe order; above, every thread
+// owns outputs o and o + 256 whole.
+template <int MODE>
+__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_kernel(const uint4* __restrict__ Y2, int KSpad, long long L,
+                                                               const double* __restrict__ Bt, int H, const double* __restrict__ K,
+                                                               const long long* __restrict__ col_off,
+                                                               const long long* __restrict__ chunk_off, int nbags,
+                                                               double* __restrict__ X, double* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double ls[];
+    __shared__ double red[SCORE_THREADS / 64];
+    double* Kl = ls;                                   // [H][H]
+    double* zl = Kl + H * H;                           // [SCORE_CW][H]
+    double* xl = zl + SCORE_CW * H;                    // [SCORE_CW][H]
+    double* yt = xl + SCORE_CW * H;                    // [SCORE_CW][LS_ROWS]
+    double* zp = yt + SCORE_CW * LS_ROWS;              // [S][P]
+    const long long w = blockIdx.x;
+    const int b = score_bag_of(chunk_off, nbags, w);
+    const long long m0 = col_off[b] + (w - chunk_off[b]) * SCORE_CW;
+    const long long mend = col_off[b + 1];
+    const int nc = (int)(mend - m0 < SCORE_CW ? mend - m0 : SCORE_CW);
+    const int P = nc * H;
+    const int S = P > SCORE_THREADS ? 1 : SCORE_THREADS / P;
+    const int tid = threadIdx.x;
+    for (int t = tid; t < H * H; t += SCORE_THREADS) Kl[t] = K[t];
+    // this thread's (at most two) outputs and its row stripe
+    int o[2] = {-1, -1};
+    int s = 0;
+    if (S == 1) { o[0] = tid < P ? tid : -1; o[1] = tid + SCORE_THREADS < P ? tid + SCORE_THREADS : -1; }
+    else if (tid < P * S) { o[0] = tid % P; s = tid / P; }
+    double acc[2] = {0.0, 0.0};
+    for (long long l0 = 0; l0 < L; l0 += LS_ROWS) {
+        const int rows = (int)(L - l0 < LS_ROWS ? L - l0 : LS_ROWS);
+        for (int t = tid; t < nc * rows; t += SCORE_THREADS) {
+            const int cc = t / rows, r = t % rows;
+            yt[cc * LS_ROWS + r] = (double)score_y_at<MODE>(Y2, KSpad, l0 + r, m0 + cc);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (o[k] < 0) continue;
+            const int cc = o[k] / H, h = o[k] % H;
+            const double* bcol = Bt + l0 * H + h;
+            const double* ycol = yt + cc * LS_ROWS;
+            double a = acc[k];
+            for (int r = s; r < rows; r += S) a = fma(bcol[(long long)r * H], ycol[r], a);
+            acc[k] = a;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (o[k] >= 0) zp[s * P + o[k]] = acc[k];
+    __syncthreads();
+    for (int q = tid; q < P; q += SCORE_THREADS) {
+        double z = 0.0;
+        for (int i = 0; i < S; ++i) z += zp[i * P + q];
+        zl[q] = z;
+    }
+    __syncthreads();
+    for (int q = tid; q < P; q += SCORE_THREADS) {
+        const int cc = q / H, h = q % H;
+        const double* zc = zl + cc * H;
+        double x = 0.0;
+        for (int j = 0; j < H; ++j) x = fma(Kl[j * H + h], zc[j], x);      // (K is symmetric bit for bit: one triangle, mirrored)
+        xl[q] = x;
+        if (X != nullptr) X[(m0 + cc) * H + h] = x;
+    }
+    if (part == nullptr) return;
+    __syncthreads();
+    double r2 = 0.0;
+    const long long n = (long long)nc * L;
+    for (long long t = tid; t < n; t += SCORE_THREADS) {
+        const long long l = t % L;
+        const int cc = (int)(t / L);
+        const double* brow = Bt + l * H;
+        const double* xc = xl + cc * H;
+        double pred = 0.0;
+        for (int h = 0; h < H; ++h) pred += brow[h] * xc[h];
+        const double d = (double)score_y_at<MODE>(Y2, KSpad, l, m0 + cc) - pred;
+        r2 += d * d;
+    }
+    r2 = block_sum(r2, red);
+    if (tid == 0) part[w] = r2;
 }
 
 // a, dS, CA, beta: M*H in vec(A') order (index m*H + h); SA: nbags x H x H.  sums: [nbags][H][SCORE_NS];

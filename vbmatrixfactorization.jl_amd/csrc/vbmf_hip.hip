@@ -3420,10 +3420,8 @@ static int score_reserve(vbmf_ctx* c, int64_t doubles) {
     return VBMF_OK;
 }
 
-// uploads [col_off | chunk_off] to d_off and enqueues the two residual kernels: r2 of every bag into d_r2 (d_part: ns partials).
-// d_A: the device copy of A with element strides (sm, sh).
-static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, int64_t ns, long long* d_off, const double* d_A,
-                              long long sm, long long sh, double* d_part, double* d_r2) {
+// uploads [col_off | chunk_off] to d_off: chunk_off[b] = bag b's first slice number
+static int score_upload_offsets(vbmf_ctx* c, int64_t nb, const int64_t* col_off, long long* d_off) {
     std::vector<long long> off((size_t)(2 * (nb + 1)));
     off[(size_t)(nb + 1)] = 0;
     for (int64_t b = 0; b <= nb; ++b) off[(size_t)b] = col_off[b];
@@ -3431,6 +3429,14 @@ static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, i
         off[(size_t)(nb + 2 + b)] = off[(size_t)(nb + 1 + b)] + (col_off[b + 1] - col_off[b] + SCORE_CW - 1) / SCORE_CW;
     HIPCHK(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                // (off is a local)
+    return VBMF_OK;
+}
+
+// uploads the offsets and enqueues the two residual kernels: r2 of every bag into d_r2 (d_part: ns partials).
+// d_A: the device copy of A with element strides (sm, sh).
+static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, int64_t ns, long long* d_off, const double* d_A,
+                              long long sm, long long sh, double* d_part, double* d_r2) {
+    TRY(score_upload_offsets(c, nb, col_off, d_off));
     TRY(rebuild_B32_if_stale(c));
     const size_t lds = score_resid_lds_bytes((int)c->H);
     if (c->mode == MODE_F32)
@@ -3467,6 +3473,74 @@ int vbmf_bag_residuals(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const
     HIPCHK(c, memcpy_sync(c, r2, d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost));
     for (int64_t b = 0; b < nb; ++b)
         if (!std::isfinite(r2[b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
+    return VBMF_OK;
+}
+
+// ols / rls of examples/mil_util.jl:159-171 and the norm(Y - BHat*AT)^2 of :483-484 for every bag, against the caller's fp64 basis
+int vbmf_bag_least_squares(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const double* BHat, int64_t ldB, int64_t H, double lambda,
+                           double* X, int64_t ldX, double* r2) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_bag_least_squares";
+    if (H < 1 || H > LS_MAX_H) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for 1 <= H <= %d)", fn, (long long)H, LS_MAX_H);
+    int64_t ns = 0;
+    TRY(score_check(c, fn, nbags, col_off, &ns));
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) FAIL(c, VBMF_ERR_INVALID, "%s: lambda must be finite and >= 0", fn);
+    if (!BHat) FAIL(c, VBMF_ERR_INVALID, "%s: null BHat", fn);
+    if (!X && !r2) FAIL(c, VBMF_ERR_INVALID, "%s: X and r2 are both NULL", fn);
+    const int64_t L = c->L, M = c->M, nb = nbags;
+    if (ldB < L) FAIL(c, VBMF_ERR_INVALID, "%s: ldB < L", fn);
+    if (X && ldX < H) FAIL(c, VBMF_ERR_INVALID, "%s: ldX < H", fn);
+    std::vector<double> Bt((size_t)(L * H));                   // row-major [L][H]
+    for (int64_t h = 0; h < H; ++h)
+        for (int64_t l = 0; l < L; ++l) {
+            const double v = BHat[h * ldB + l];
+            if (!std::isfinite(v)) FAIL(c, VBMF_ERR_INVALID, "%s: BHat[%lld, %lld] is not finite", fn, (long long)l, (long long)h);
+            Bt[(size_t)(l * H + h)] = v;
+        }
+    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the basis is an argument)
+    HIPCHK(c, hipSetDevice(c->o.device));
+    const int64_t nchunk = cdiv(L, LS_ROWS), h2 = H * H;
+    // c->score: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | bad-pivot flag | partials ns | B L H (row-major) | Gram partials nchunk H^2
+    //            | K H^2 | X M H (column m at m H)]
+    const int64_t o_r2 = 2 * (nb + 1), o_flag = o_r2 + nb, o_part = o_flag + 1, o_b = o_part + ns, o_g = o_b + L * H,
+                  o_k = o_g + nchunk * h2, o_x = o_k + h2, total = o_x + M * H;
+    TRY(score_reserve(c, total));
+    double* d = c->score;
+    long long* d_off = reinterpret_cast<long long*>(d);
+    HIPCHK(c, hipMemcpyAsync(d + o_b, Bt.data(), Bt.size() * 8, hipMemcpyHostToDevice, c->stream));
+    TRY(score_upload_offsets(c, nb, col_off, d_off));           // (its synchronize also covers Bt)
+    hipLaunchKernelGGL(bag_ls_gram_kernel, dim3((unsigned)nchunk), dim3(SCORE_THREADS), 0, c->stream, d + o_b, (long long)L, (int)H, d + o_g);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(bag_ls_inverse_kernel, dim3(1), dim3(256), spd_inverse_lds_bytes(LS_MAX_H / 16), c->stream, d + o_g, (int)nchunk,
+                       (int)H, lambda, d + o_k, reinterpret_cast<int*>(d + o_flag));
+    HIPCHK(c, hipGetLastError());
+    double* d_x = X ? d + o_x : nullptr;
+    double* d_part = r2 ? d + o_part : nullptr;
+    const size_t lds = score_ls_lds_bytes((int)H);
+    if (c->mode == MODE_F32)
+        hipLaunchKernelGGL((bag_ls_kernel<MODE_F32>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
+                           d + o_b, (int)H, d + o_k, d_off, d_off + nb + 1, (int)nb, d_x, d_part);
+    else
+        hipLaunchKernelGGL((bag_ls_kernel<MODE_BF16>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
+                           d + o_b, (int)H, d + o_k, d_off, d_off + nb + 1, (int)nb, d_x, d_part);
+    HIPCHK(c, hipGetLastError());
+    if (r2) {
+        hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, c->stream, d_part, d_off + nb + 1, (int)nb, d + o_r2);
+        HIPCHK(c, hipGetLastError());
+    }
+    std::vector<double> res((size_t)(nb + 1));                  // r2 | flag
+    HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
+    int bad = 0;
+    std::memcpy(&bad, &res[(size_t)nb], sizeof(int));
+    if (bad) FAIL(c, VBMF_ERR_NUMERIC, "%s: B'B + lambda I is not positive definite (a pivot is not positive or not finite)", fn);
+    if (r2)
+        for (int64_t b = 0; b < nb; ++b)
+            if (!std::isfinite(res[(size_t)b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
+    if (X) {
+        HIPCHK(c, hipMemcpy2DAsync(X, (size_t)ldX * 8, d + o_x, (size_t)H * 8, (size_t)H * 8, (size_t)M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (r2) std::memcpy(r2, res.data(), (size_t)nb * 8);
     return VBMF_OK;
 }
 

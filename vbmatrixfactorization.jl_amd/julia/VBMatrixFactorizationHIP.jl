@@ -14,6 +14,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        vbls!, vbls_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
+       ols_batch, rls_batch, ls_residual_batch,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!
 
@@ -740,6 +741,55 @@ lowerBound_batch(Ys::Vector{Matrix{Float64}}, ps) = bound_batch(Ys, ps, -1.0)
 function lowerBoundTrimmed_batch(Ys::Vector{Matrix{Float64}}, ps, trim = 1e-1)
     trim >= 0 || error("lowerBoundTrimmed_batch: trim must be >= 0")
     return bound_batch(Ys, ps, Float64(trim))
+end
+
+# ---- least squares against a caller's basis: ols / rls (examples/mil_util.jl:159-171) over many bags ----------------------------
+# The bags go side by side into one basic context, which supplies only Y: the basis is an argument of the call, with its own H.
+# Returns (X: H x sum(M_b), the squared residual norms, the column offsets).
+function bag_least_squares(Ys::Vector{Matrix{Float64}}, B::Matrix{Float64}, lam::Float64, fn::String)
+    nb = length(Ys)
+    nb >= 1 || error("$fn: no bags")
+    L, H = size(B)
+    1 <= H <= 64 || error("$fn: H = $H (built for 1 <= H <= 64)")
+    (isfinite(lam) && lam >= 0) || error("$fn: lam must be finite and >= 0")
+    for (b, Y) in enumerate(Ys)
+        (size(Y, 1) == L && size(Y, 2) >= 1) || error("$fn: bag $b is not L x M_b with L = size(B, 1) = $L and M_b >= 1")
+    end
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    M = off[end]
+    Yall = reduce(hcat, Ys)
+    X = Array{Float64}(undef, H, M)
+    r2 = Array{Float64}(undef, nb)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, 0, 0xffffffff, 1, 0, 0, 0, 0, 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        chk(h[], ccall((:vbmf_bag_least_squares, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Int64, Float64, Ptr{Float64}, Int64, Ptr{Float64}),
+            h[], nb, off, B, L, H, lam, X, H, r2))
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+    return X, r2, off
+end
+
+"`[ols(Y, B) for Y in Ys]` = inv(B'B)*B'*Y per bag (examples/mil_util.jl:159-161) in ONE device call, fp64 (vbmf_bag_least_squares); H <= 64"
+function ols_batch(Ys::Vector{Matrix{Float64}}, B::Matrix{Float64})
+    X, _, off = bag_least_squares(Ys, B, 0.0, "ols_batch")
+    return [X[:, off[b]+1:off[b+1]] for b in 1:length(Ys)]
+end
+
+"`[rls(Y, B, lam) for Y in Ys]` = inv(B'B + lam*I)*B'*Y per bag (examples/mil_util.jl:168-171) in ONE device call"
+function rls_batch(Ys::Vector{Matrix{Float64}}, B::Matrix{Float64}, lam::Float64)
+    X, _, off = bag_least_squares(Ys, B, lam, "rls_batch")
+    return [X[:, off[b]+1:off[b+1]] for b in 1:length(Ys)]
+end
+
+"norm(Y_b - B*X_b) with X_b the ols (lam = 0) / rls estimate of every bag (examples/mil_util.jl:483-484), from the pass that forms X_b"
+function ls_residual_batch(Ys::Vector{Matrix{Float64}}, B::Matrix{Float64}, lam::Float64 = 0.0)
+    _, r2, _ = bag_least_squares(Ys, B, lam, "ls_residual_batch")
+    return sqrt.(r2)
 end
 
 "vbmf_dual! -- src/vbmf_dual.jl:455-530 (returns d); est_priors: the hyper-prior fits of :393-434 run on the device"
