@@ -8,7 +8,8 @@
 //                          k-steps, the chunks summed in fp64, rounded once); upper 128 x 128 blocks, each stored with its mirror
 //   gram_w_kernel          W_new = A (SigmaB / sigma2) on fp64 MFMA, D = W_new - W_old; fp32 W and the product's bf16 operand planes
 //   gram_prod_kernel       [P | Q] = G [W | D] as split-K slabs in the fragment-major layout of the pass-1 product
-//   gram_part_kernel       per-chunk fp64 shares of W'P, D'Q (each product once, on fp64 MFMA) and sum A o P
+//   gram_tail_kernel       the slabs folded into [P | Q] and, from the folded values, per-chunk fp64 shares of W'P, D'Q (each
+//                          product once, on fp64 MFMA) and sum A o P
 //   gram_part_reduce_kernel  fixed-order sum of the shares -> the state's [B'B | dB'dB | tr(B'YA)], symmetrised as (C + C') / 2
 //
 // Layouts.  G is stored as MFMA operand fragments, fp32: Gt[row tile p][k-step j][lane][8], lane (half, c) holds
@@ -435,112 +436,279 @@ __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const 
     }
 }
 
-// per-chunk fp64 shares on v_mfma_f64_16x16x4_f64: part[c] = [W'P (Hp^2) | D'Q (Hp^2) | sum A o P] over rows [c rpc, (c + 1) rpc) of
-// the M real rows, each product formed once (the reduction symmetrises).  1024 threads = S row subsets x 2 products x V column
-// offsets, V = HP / 16, S = 8 / V.  Lane (q, c) of wave (s, pi, tw) takes, per 4-row step of its subset (steps s, s + S, ...), row
-// m = m0 + 4 step + q: the V columns V c .. V c + V - 1 of P (pi = 0) or Q (pi = 1) as whole 16-byte pieces of the fragment-major
-// product (frag_index; V = 2: 8 bytes), which are its B operands (column V c + t in accumulator t), and the one value of W (or D,
-// formed in fp64 and rounded to fp32, as gram_w forms it) at column V c + tw, its A operand.  Accumulator t thus holds
-// C[V (q + 4 r) + tw][V c + t] in register r; fp32 x fp32 products are exact in fp64.  The pi = 0 waves also sum A o P at their
-// column.  The S subsets are folded through LDS in subset order; the share is stored in register order (gpart_index).
+// gram_tail_kernel: the split-K slabs of [P | Q] folded and the per-chunk fp64 shares formed from the folded values in one launch.
+// part[c] = [W'P (Hp^2) | D'Q (Hp^2) | sum A o P] over rows [c rpc, (c + 1) rpc) of the M real rows, on v_mfma_f64_16x16x4_f64, each
+// product formed once (the reduction symmetrises).
+//
+// Grid 2 nchunk: workgroup (chunk, pi) takes product P (pi = 0) or Q (pi = 1) of one row chunk; the two halves share nothing but the
+// chunk's trace slot, which only the P half has a share in.  512 threads = S row subsets x V column offsets, V = HP / 16, S = 8 / V.
+//
+// Fold.  The chunk's rows of the product go by in blocks of ROWS rows (three 16-byte pieces per thread, two at HP = 128: the
+// headline's 80-row chunk is one block).  Thread t takes pieces t, t + 512, t + 1024 of the block in memory order (a wave: one contiguous 1 KB of a
+// 16-row group), requests each from up to eight slabs at once, adds them in slab order in fp32 as slab_sum_kernel does
+// (((s0 + s1) + s2) + ...; further rounds of eight for more slabs), stores the sum to PQ (not when there is one slab: then PQ is the
+// product itself and is read in place) and leaves it in LDS as rows x HP.  Every piece is folded once.  The last chunk's workgroups
+// also fold the rows from the end of their chunk to Mp1, which belong to no chunk, so that all of PQ is written.  The stop flag and
+// the W / A values of the block are requested with the block's first round; only the return and the stores wait for the flag.  The
+// next block's first round is requested before the barrier that publishes this one (a raw s_barrier behind an LDS-only wait:
+// __syncthreads would drain the loads), into the other LDS buffer.
+//
+// Shares.  Lane (q, c) of wave (s, tw) takes, per 4-row step of its subset (steps s, s + S, ... of the chunk, in that order), row
+// m = m0 + 4 step + q: the V columns V c .. V c + V - 1 of the folded product from LDS, which are its B operands (column V c + t in
+// accumulator t), and the one value of W (or D, formed in fp64 and rounded to fp32, as gram_w forms it) at column V c + tw, its A
+// operand.  Accumulator t thus holds C[V (q + 4 r) + tw][V c + t] in register r; fp32 x fp32 products are exact in fp64.  Rows at or
+// past the chunk's end enter as zeros, which leave every accumulator as it was.  The P half also sums A o P at its column; the
+// workgroup's sum is taken over lanes as block_sum takes it and over waves in (s, tw) order -- the order of the 1024-thread kernel
+// this replaced, whose Q waves added exact zeros.  The S subsets are folded through LDS in subset order; the share is stored in
+// register order (gpart_index).
 template <int HP>
 struct GPart {
     static constexpr int V = HP / 16, S = 8 / V, NH = HP / 32;
+    static constexpr int NT = 512, SD = 8;                    // threads, slabs per round
+    static constexpr int PPT = HP == 128 ? 2 : 3;             // pieces per thread and block (V = 8: 64 accumulator registers)
+    static constexpr int ROWS = PPT * NT * 4 / HP;            // rows per block: 192 / 96 / 32
+    static constexpr int NSTEP = ROWS / 4 / S;                // 4-row steps per wave and block: 12 / 12 / 8
+    static constexpr int BUF = ROWS * HP;                     // floats per LDS buffer (24 / 24 / 16 KB); two of them: 48 / 48 / 32 KB
+    static constexpr int SU = V == 8 ? 2 : 4;                  // steps skipped or taken together
+    static_assert(NSTEP % SU == 0 && (ROWS / 4) % S == 0 && ROWS % 16 == 0, "gram_tail geometry");
+    static_assert((S - 1) * V * V * 64 * 32 <= 2 * BUF * 4, "gram_tail: the subset fold reuses the block buffers");
 };
-// position of C[a][b] of one product inside a share (register order of gram_part_kernel)
+// position of C[a][b] of one product inside a share (register order of gram_tail_kernel)
 template <int HP>
 __device__ __forceinline__ int gpart_index(int a, int b) {
     constexpr int V = GPart<HP>::V;
     const int tw = a % V, i = a / V, t = b % V, c = b / V;
     return ((((tw * V + t) * 4 + (i >> 2)) << 6) + 16 * (i & 3) + c);
 }
+__device__ __forceinline__ void add4(float4& s, const float4& v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+// one round of gram_tail's fold for one piece: the loads of cnt (1 .. 8) slabs as one straight-line run entered at its cnt-th last
+// load (slab u through its own descriptor r[u], the piece's byte offset in voff), and their sum in slab order
+struct GTailRound { float4 a0, a1, a2, a3, a4, a5, a6, a7; };
+__device__ __forceinline__ void gtail_load(GTailRound& v, const __amdgpu_buffer_rsrc_t (&r)[8], int voff, int cnt) {
+    const auto ld = [&](int u) __attribute__((always_inline)) {
+        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r[u], voff, 0, 0));
+    };
+    switch (cnt) {
+        default: v.a7 = ld(7); [[fallthrough]];
+        case 7: v.a6 = ld(6); [[fallthrough]];
+        case 6: v.a5 = ld(5); [[fallthrough]];
+        case 5: v.a4 = ld(4); [[fallthrough]];
+        case 4: v.a3 = ld(3); [[fallthrough]];
+        case 3: v.a2 = ld(2); [[fallthrough]];
+        case 2: v.a1 = ld(1); [[fallthrough]];
+        case 1: v.a0 = ld(0);
+    }
+}
+template <bool FIRST>
+__device__ __forceinline__ float4 gtail_sum(const GTailRound& v, float4 f, int cnt) {
+    if (FIRST) f = v.a0;
+    else add4(f, v.a0);
+    if (cnt > 1) add4(f, v.a1);
+    if (cnt > 2) add4(f, v.a2);
+    if (cnt > 3) add4(f, v.a3);
+    if (cnt > 4) add4(f, v.a4);
+    if (cnt > 5) add4(f, v.a5);
+    if (cnt > 6) add4(f, v.a6);
+    if (cnt > 7) add4(f, v.a7);
+    return f;
+}
 template <int HP>
-__global__ __launch_bounds__(1024) void gram_part_kernel(const float* __restrict__ PQ, long long n, const float* __restrict__ Wn,
-                                                         const float* __restrict__ Wo, const float* __restrict__ A32, long long M,
-                                                         int rpc, double* __restrict__ part, const int* __restrict__ stop) {
-    if (*stop) return;
-    constexpr int V = GPart<HP>::V, S = GPart<HP>::S, NH = GPart<HP>::NH, U = 4;   // U steps' loads in flight
-    __shared__ f64x4 fold[S > 1 ? (S - 1) * 2 * V * V * 64 : 1];
-    __shared__ double red[16];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int s = w / (2 * V), task = w % (2 * V), pi = task / V, tw = task % V;
+__global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int nslab, long long slab_floats, float* PQ, long long n,
+                                                        long long Mp1, const float* __restrict__ Wn, const float* __restrict__ Wo,
+                                                        const float* __restrict__ A32, long long M, int rpc, int nchunk,
+                                                        double* __restrict__ part, const int* __restrict__ stop) {
+    using C = GPart<HP>;
+    constexpr int V = C::V, S = C::S, NH = C::NH, PPT = C::PPT, SD = C::SD, ROWS = C::ROWS, NSTEP = C::NSTEP, SU = C::SU;
+    __shared__ __attribute__((aligned(32))) float stage[2 * C::BUF];
+    __shared__ double red[8];
+    const int stopv = *stop;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // known to be the same for the whole wave
+    const int s = w / V, tw = w % V;
     const int q = lane >> 4, c = lane & 15;
-    const float* src = PQ + (pi ? n : 0);
+    const int chunk = blockIdx.x >> 1, pi = blockIdx.x & 1;
+    const long long m0 = (long long)chunk * rpc, m1 = min(m0 + rpc, M);
+    const long long fend = chunk == nchunk - 1 ? Mp1 : m0 + rpc;     // rows folded here: a multiple of 16, as m0 is
+    const float* src = slabs + (pi ? n : 0);
+    float* dst = PQ + (pi ? n : 0);
+    const float* X = pi ? Wo : A32;
+    // piece j of this thread: 16-row group grp[j] of the block (the same for the whole wave), row xr of it, h tile ht, columns
+    // 32 ht + 8 r4 + 4 half .. + 3 (post_kernels.hpp, frag_index)
+    const int xr = lane >> 2, r4 = lane & 3;
+    int grp[PPT], ht[PPT], half[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const int sg = 8 * j + w;
+        grp[j] = sg / (2 * NH);
+        ht[j] = (sg % (2 * NH)) >> 1;
+        half[j] = sg & 1;
+    }
+    GTailRound v[PPT];
+    static_assert(SD == 8, "gram_tail: GTailRound");
+    float wv[NSTEP], xv[NSTEP];
+    auto piece_off = [&](long long rb, int j) __attribute__((always_inline)) {
+        const long long row = rb + 16 * grp[j] + xr;
+        return ((((row >> 5) * NH + ht[j]) * 64 + half[j] * 32 + (row & 31)) << 4) + 4 * r4;
+    };
+    // slabs k0 .. k0 + cnt - 1 of the block at row rb: cnt = 1 .. SD picks one straight-line run of loads (gtail_load) or adds.
+    // Buffer loads: a slab's descriptor is uniform and the piece's 32-bit offset serves all of its slabs.
+    auto issue_slabs = [&](long long rb, int k0) __attribute__((always_inline)) {
+        __amdgpu_buffer_rsrc_t r[SD];
+#pragma unroll
+        for (int u = 0; u < SD; ++u)
+            r[u] = __builtin_amdgcn_make_buffer_rsrc((void*)(src + (long long)(k0 + u) * slab_floats), 0, (unsigned)(n * 4), 0x00020000);
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            if (rb + 16 * grp[j] >= fend) continue;
+            gtail_load(v[j], r, (int)(piece_off(rb, j) * 4), min(SD, nslab - k0));
+        }
+    };
+    auto fold_slabs = [&](long long rb, int k0, float4 (&f)[PPT]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            if (rb + 16 * grp[j] >= fend) continue;
+            if (k0 == 0) f[j] = gtail_sum<true>(v[j], f[j], min(SD, nslab));
+            else f[j] = gtail_sum<false>(v[j], f[j], min(SD, nslab - k0));
+        }
+    };
+    // W and A (or W_old) of the block's steps.  The descriptors end with the chunk, so rows at or past its end load as zeros.
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)Wn, 0, (unsigned)(m1 * HP * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xd = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (unsigned)(m1 * HP * 4), 0x00020000);
+    auto issue_w = [&](long long rb) __attribute__((always_inline)) {
+        const int o = (int)(((rb + 4 * s + q) * HP + V * c + tw) * 4);
+#pragma unroll
+        for (int i = 0; i < NSTEP; ++i) {
+            wv[i] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(wr, o + i * (4 * S * HP * 4), 0, 0));
+            xv[i] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(xd, o + i * (4 * S * HP * 4), 0, 0));
+        }
+    };
+    issue_slabs(m0, 0);
+    issue_w(m0);
+    if (stopv) return;
     f64x4 acc[V];
 #pragma unroll
     for (int t = 0; t < V; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
     double tr = 0.0;
-    const long long m0 = (long long)blockIdx.x * rpc, m1 = min(m0 + rpc, M);
-    const int nstep = (int)((m1 - m0 + 3) / 4);
-    for (int k0 = s; k0 < nstep; k0 += S * U) {
-        float pv[U][V], wv[U], xv[U];
+    int buf = 0;
+    for (long long rb = m0; rb < fend; rb += ROWS, buf ^= 1) {
+        float* sb = stage + buf * C::BUF;
+        float4 f[PPT];
+        fold_slabs(rb, 0, f);
+        for (int k0 = SD; k0 < nslab; k0 += SD) {
+            issue_slabs(rb, k0);
+            fold_slabs(rb, k0, f);
+        }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long m = m0 + 4LL * (k0 + u * S) + q;
-            if (m < m1) {
+        for (int j = 0; j < PPT; ++j) {
+            if (rb + 16 * grp[j] >= fend) continue;
+            if (nslab > 1) *reinterpret_cast<float4*>(dst + piece_off(rb, j)) = f[j];
+            *reinterpret_cast<float4*>(sb + (16 * grp[j] + xr) * HP + 32 * ht[j] + 8 * r4 + 4 * half[j]) = f[j];
+        }
+        // this block's A operands, so that the next block's may be requested
+        float ac[NSTEP], xc[NSTEP];
+#pragma unroll
+        for (int i = 0; i < NSTEP; ++i) {
+            xc[i] = xv[i];
+            ac[i] = pi ? (float)((double)wv[i] - (double)xc[i]) : wv[i];
+        }
+        if (rb + ROWS < fend) {
+            issue_slabs(rb + ROWS, 0);
+            issue_w(rb + ROWS);
+        }
+        // everybody's pieces of this block are in LDS; the buffer is written again two blocks on, behind the next block's barrier
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int i0 = 0; i0 < NSTEP; i0 += SU) {
+            if (rb + 4 * (s + S * i0) >= m1) break;
+            __builtin_amdgcn_sched_barrier(0);                        // one group's LDS reads in registers at a time
+#pragma unroll
+            for (int i = i0; i < i0 + SU; ++i) {
+                const int rl = 4 * (s + S * i) + q;
+                const bool in = rb + rl < m1;
+                float pv[V];
                 if constexpr (V == 2) {
-                    const float2 v = *reinterpret_cast<const float2*>(src + frag_index(2 * c, m, NH));
-                    pv[u][0] = v.x; pv[u][1] = v.y;
+                    const float2 x = *reinterpret_cast<const float2*>(sb + rl * HP + 2 * c);
+                    pv[0] = x.x; pv[1] = x.y;
                 } else {
 #pragma unroll
                     for (int g = 0; g < V / 4; ++g) {
-                        const float4 v = *reinterpret_cast<const float4*>(src + frag_index(V * c + 4 * g, m, NH));
-                        pv[u][4 * g] = v.x; pv[u][4 * g + 1] = v.y; pv[u][4 * g + 2] = v.z; pv[u][4 * g + 3] = v.w;
+                        const float4 x = *reinterpret_cast<const float4*>(sb + rl * HP + V * c + 4 * g);
+                        pv[4 * g] = x.x; pv[4 * g + 1] = x.y; pv[4 * g + 2] = x.z; pv[4 * g + 3] = x.w;
                     }
                 }
-                wv[u] = Wn[m * HP + V * c + tw];
-                xv[u] = (pi ? Wo : A32)[m * HP + V * c + tw];
-            } else {
 #pragma unroll
-                for (int t = 0; t < V; ++t) pv[u][t] = 0.f;
-                wv[u] = 0.f; xv[u] = 0.f;
+                for (int t = 0; t < V; ++t) pv[t] = in ? pv[t] : 0.f;
+                if (!pi) {
+                    float p = 0.f;
+#pragma unroll
+                    for (int t = 0; t < V; ++t) p = t == tw ? pv[t] : p;
+                    tr += (double)xc[i] * (double)p;
+                }
+#pragma unroll
+                for (int t = 0; t < V; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)ac[i], (double)pv[t], acc[t], 0, 0, 0);
             }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            double a = (double)wv[u];
-            if (pi) a = (double)(float)(a - (double)xv[u]);
-            else {
-                float p = 0.f;
-#pragma unroll
-                for (int t = 0; t < V; ++t) p = t == tw ? pv[u][t] : p;
-                tr += (double)xv[u] * (double)p;
-            }
-#pragma unroll
-            for (int t = 0; t < V; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, (double)pv[u][t], acc[t], 0, 0, 0);
         }
     }
     if constexpr (S > 1) {
+        f64x4* fold = reinterpret_cast<f64x4*>(stage);
+        __syncthreads();                                              // the last block has been read
         if (s > 0) {
 #pragma unroll
-            for (int t = 0; t < V; ++t) fold[(((s - 1) * 2 * V + task) * V + t) * 64 + lane] = acc[t];
+            for (int t = 0; t < V; ++t) fold[(((s - 1) * V + tw) * V + t) * 64 + lane] = acc[t];
         }
         __syncthreads();
         if (s == 0) {
             for (int s2 = 1; s2 < S; ++s2)
 #pragma unroll
-                for (int t = 0; t < V; ++t) acc[t] += fold[(((s2 - 1) * 2 * V + task) * V + t) * 64 + lane];
+                for (int t = 0; t < V; ++t) acc[t] += fold[(((s2 - 1) * V + tw) * V + t) * 64 + lane];
         }
     }
-    double* o = part + (long long)blockIdx.x * (2 * HP * HP + 1) + pi * HP * HP;
+    double* o = part + (long long)chunk * (2 * HP * HP + 1) + pi * HP * HP;
     if (s == 0) {
 #pragma unroll
         for (int t = 0; t < V; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[(((tw * V + t) * 4 + r) << 6) + lane] = acc[t][r];
     }
-    tr = block_sum(tr, red);
-    if (threadIdx.x == 0) part[(long long)blockIdx.x * (2 * HP * HP + 1) + 2 * HP * HP] = tr;
+    if (pi) return;
+    for (int off = 32; off > 0; off >>= 1) tr += __shfl_down(tr, off);
+    if (lane == 0) red[w] = tr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < 8; ++i) t += red[i];
+        part[(long long)chunk * (2 * HP * HP + 1) + 2 * HP * HP] = t;
+    }
 }
 
 // the shares summed in a fixed order into st: GB[a][b] = (sum_c C_c[a][b] + sum_c C_c[b][a]) / 2 (every sum in chunk order, so GB is
 // exactly symmetric), GD likewise, GX[0] = sum A o P.  Workgroup: 64 share positions (register order) x 4 chunk groups (group g sums
-// chunks g, g + 4, ...; eight loads in flight), each position together with its transposed one; the group sums added in group order.
+// chunks g, g + 4, ... in that order), each position together with its transposed one; the group sums added in group order.  A
+// thread requests all of its group's values of both positions (and the workgroup the stop flag) before its first add: 8, 16 or 32
+// chunks deep, the smallest that holds the group (gram_prepare plans at most 128 chunks; more would take further rounds).  Requests
+// past the last chunk are clamped to it and their values left out of the sums.
 constexpr int GRED_E = 64, GRED_G = 4;
+template <int DP>
+__device__ __forceinline__ void gred_round(const double* __restrict__ part, int k, int nchunk, long long stride, long long i0,
+                                           long long i1, double& s0, double& s1) {
+    double v0[DP], v1[DP];
+#pragma unroll
+    for (int u = 0; u < DP; ++u) {
+        const long long o = (long long)min(k + u * GRED_G, nchunk - 1) * stride;
+        v0[u] = part[o + i0];
+        v1[u] = part[o + i1];
+    }
+    __builtin_amdgcn_sched_barrier(0);                            // no add is moved up among the loads
+#pragma unroll
+    for (int u = 0; u < DP; ++u)
+        if (k + u * GRED_G < nchunk) { s0 += v0[u]; s1 += v1[u]; }
+}
 template <int HP>
 __global__ __launch_bounds__(256) void gram_part_reduce_kernel(const double* __restrict__ part, int nchunk, double* __restrict__ st,
                                                                StateLayout lay, const int* __restrict__ stop) {
-    if (*stop) return;
+    const int stopv = *stop;
     constexpr int V = GPart<HP>::V, n2 = HP * HP;
     constexpr long long stride = 2LL * n2 + 1;
     __shared__ double sum[2][GRED_G][GRED_E];
@@ -553,17 +721,13 @@ __global__ __launch_bounds__(256) void gram_part_reduce_kernel(const double* __r
     const bool mat = e < 2 * n2, tro = e == 2 * n2;
     const long long i0 = mat ? e : 2LL * n2, i1 = mat ? (long long)pi * n2 + gpart_index<HP>(b, a) : 2LL * n2;
     double s0 = 0.0, s1 = 0.0;
-    if (mat || tro) {
-        int k = g;
-        for (; k + 7 * GRED_G < nchunk; k += 8 * GRED_G) {
-            double v0[8], v1[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { v0[u] = part[(k + u * GRED_G) * stride + i0]; v1[u] = part[(k + u * GRED_G) * stride + i1]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { s0 += v0[u]; s1 += v1[u]; }
-        }
-        for (; k < nchunk; k += GRED_G) { s0 += part[k * stride + i0]; s1 += part[k * stride + i1]; }
+    for (int k = g; k < nchunk; k += 32 * GRED_G) {
+        const int left = (nchunk - k + GRED_G - 1) / GRED_G;     // the same for the whole wave
+        if (left <= 8) gred_round<8>(part, k, nchunk, stride, i0, i1, s0, s1);
+        else if (left <= 16) gred_round<16>(part, k, nchunk, stride, i0, i1, s0, s1);
+        else gred_round<32>(part, k, nchunk, stride, i0, i1, s0, s1);
     }
+    if (stopv) return;
     sum[0][g][el] = s0;
     sum[1][g][el] = s1;
     __syncthreads();

@@ -1025,7 +1025,8 @@ static int gram_prepare(vbmf_ctx* c) {
         c->g_sps = cdiv(KT, c->g_nsplit);
         c->g_nsplit = cdiv(KT, c->g_sps);
         const int64_t Mp1 = (int64_t)c->d1.XT * 32;
-        // gram_part: 16 waves per chunk; 128 chunks (2 waves per SIMD) at Hp <= 64, 64 at Hp = 128, where a share is 4x larger
+        // gram_tail: two workgroups of 8 waves per chunk (one per product); 128 chunks at Hp <= 64 (one workgroup per CU), 64 at
+        // Hp = 128, where a share is 4x larger.  The plan is the one the 16-wave gram_part had: the sums' order depends on it.
         c->g_nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(c->Hp == 128 ? 64 : 128, cdiv(c->M, 64)));
         c->g_rpc = (int)rup(cdiv(c->M, c->g_nchunk), 16);
         c->g_nchunk = cdiv(c->M, c->g_rpc);
@@ -1079,7 +1080,8 @@ static int gram_prepare(vbmf_ctx* c) {
 }
 
 // W_new = A SigmaB / sigma2 and D = W_new - W_old (into W32g[wcur ^ 1]; the caller flips wcur), then [P | Q] = G [W_new | D];
-// partials: the state's [B'B | dB'dB | tr(B'YA)] of B = Y W_new from it.  Profile slot 1 brackets the product.
+// partials: the state's [B'B | dB'dB | tr(B'YA)] of B = Y W_new from it (gram_tail folds the slabs and forms the shares; without
+// partials the old slab_sum launch folds them).  Profile slot 1 brackets the product.
 static int gram_product(vbmf_ctx* c, bool partials) {
     const int* stop = c->ints + I_STOP;
     const int KT = 2 * c->GT;
@@ -1101,16 +1103,20 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     else hipLaunchKernelGGL((gram_prod_kernel<4>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
     prof_end(c);
     HIPCHK(c, hipGetLastError());
-    if (c->g_nsplit > 1) {
-        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(2 * n / 4, 256, 2048)), dim3(256), 0, c->stream, c->gslabs, c->g_nsplit, 2 * n,
-                           c->gPQ, 2 * n, stop, SideCopy{});
-        HIPCHK(c, hipGetLastError());
-    }
-    if (partials) {
-        const dim3 pg(c->g_nchunk);
-        if (c->Hp == 32) hipLaunchKernelGGL((gram_part_kernel<32>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
-        else if (c->Hp == 64) hipLaunchKernelGGL((gram_part_kernel<64>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
-        else hipLaunchKernelGGL((gram_part_kernel<128>), pg, dim3(1024), 0, c->stream, c->gPQ, n, Wn, Wo, c->A32, (long long)c->M, c->g_rpc, c->g_part, stop);
+    if (!partials) {
+        // no shares wanted (the run boundary): only the folded [P | Q], by the plain slab sum
+        if (c->g_nsplit > 1) {
+            hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(2 * n / 4, 256, 2048)), dim3(256), 0, c->stream, c->gslabs, c->g_nsplit, 2 * n,
+                               c->gPQ, 2 * n, stop, SideCopy{});
+            HIPCHK(c, hipGetLastError());
+        }
+    } else {
+        // the slabs folded into gPQ (one split: gPQ read in place) and the chunk shares from the folded values, in one launch
+        const dim3 tg(2 * c->g_nchunk);
+        const long long M = (long long)c->M;
+        if (c->Hp == 32) hipLaunchKernelGGL((gram_tail_kernel<32>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
+        else if (c->Hp == 64) hipLaunchKernelGGL((gram_tail_kernel<64>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
+        else hipLaunchKernelGGL((gram_tail_kernel<128>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
         HIPCHK(c, hipGetLastError());
         const dim3 rg(cdiv(2 * (int64_t)c->Hp * c->Hp + 1, GRED_E));
         if (c->Hp == 32) hipLaunchKernelGGL((gram_part_reduce_kernel<32>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
