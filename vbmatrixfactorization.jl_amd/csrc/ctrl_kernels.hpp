@@ -39,7 +39,8 @@ struct StateLayout {
 };
 enum : int { S_SIGMA2 = 0, S_TRYY, S_LOGDET_SA, S_LOGDET_SB, S_LAMB_PREV, S_LAMB_NEW, S_LAMD, S_D, S_ELBO,
              S_TRDOT, S_RESID, S_TRYBA,
-             S_LOGDET_SA_SHADOW = 20 };      // 12..18: sparse_kernels.hpp
+             S_LOGDET_SA_SHADOW = 20,        // 12..18 and 21..29 (S_GPRI, S_GPOST): sparse_kernels.hpp
+             S_LAMB_SHADOW = 30 };           // lambda_max(B_old'B_old) computed ahead by the Gram form's first chain launch (ctrl_chain)
 enum : int { I_STOP = 0, I_ITERS = 1, I_ERR = 2, I_NITER = 3, I_SREADY = 4, I_DBG_SB_PPM = 5 };   // (5: test hook, vbmf_debug_set)
 
 // Threads of the workgroup that run the control algebra: the whole block -- except in the 512-thread launch of the H >= 128
@@ -258,6 +259,17 @@ __device__ __forceinline__ bool stop_on_remote_error(const double* __restrict__ 
 //   elem(i, j): the matrix (i, j < H);  W: 16 NB x (16 NB + 2) doubles of LDS;  on return W's upper triangle holds -inverse
 //   (read it through spd_inv_at), *logdet = log det of the matrix, *bad != 0 if a pivot was not positive / finite.
 // Every thread of the control workgroup (ctrl_nthreads() = 256 of them) must call it.
+// the sweep alone, on an image some other code of the workgroup has filled (identity padding included); opens with the barrier that
+// publishes the image
+template <int NB>
+__device__ __forceinline__ void spd_sweep_lds4(double* W, int H, double* logdet, int* bad) {
+    constexpr int LD = 16 * NB + 2;
+    __syncthreads();
+    PivAcc pv;
+    blk_sweep<NB, 4>(W, LD, (H + 15) >> 4, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, pv);
+    *logdet = pv.logdet();
+    *bad = pv.bad;
+}
 template <int NB, class ElemF>
 __device__ __forceinline__ void spd_inverse_lds4(double* W, int H, ElemF elem, double* logdet, int* bad) {
     constexpr int NP = 16 * NB, LD = NP + 2;
@@ -265,11 +277,7 @@ __device__ __forceinline__ void spd_inverse_lds4(double* W, int H, ElemF elem, d
         const int i = t / NP, j = t % NP;
         W[i * LD + j] = (i < H && j < H) ? elem(i, j) : (i == j ? 1.0 : 0.0);      // identity padding
     }
-    __syncthreads();
-    PivAcc pv;
-    blk_sweep<NB, 4>(W, LD, (H + 15) >> 4, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, pv);
-    *logdet = pv.logdet();
-    *bad = pv.bad;
+    spd_sweep_lds4<NB>(W, H, logdet, bad);
 }
 template <int NB>
 __device__ __forceinline__ double spd_inv_at(const double* W, int i, int j) {          // element (i, j) of the inverse
@@ -277,6 +285,26 @@ __device__ __forceinline__ double spd_inv_at(const double* W, int i, int j) {   
     return -(i <= j ? W[i * LD + j] : W[j * LD + i]);
 }
 constexpr size_t spd_inverse_lds_bytes(int NB) { return (size_t)(16 * NB) * (16 * NB + 2) * sizeof(double); }
+
+// What follows the sweep of an H <= 128 covariance update: Sigma = sigma2 inv(K) from the swept image W to the state (which = 0:
+// SigmaA, or its shadow; 1: SigmaB), inv(K) as the post kernel's fp32 table, the error flag and the log-determinant.
+template <int NBc>
+__device__ __forceinline__ void cov_store_lds4(double* __restrict__ st, StateLayout lay, int H, int which, double sigma2,
+                                               float* __restrict__ S32, int* __restrict__ ints, const double* W, double ldK,
+                                               int badK, bool shadow) {
+    const int Hp = lay.Hp;
+    double* Sself = st + (which == 0 ? (shadow ? lay.W0() : lay.SA()) : lay.SB());
+    const double dbg = which == 1 ? 1.0 + 1e-6 * (double)ints[I_DBG_SB_PPM] : 1.0;      // test hook (normally exactly 1)
+    for (int t = threadIdx.x; t < Hp * Hp; t += 256) {
+        const int i = t / Hp, j = t % Hp;
+        const double v = (i < H && j < H) ? spd_inv_at<NBc>(W, i, j) : 0.0;
+        Sself[(long long)i * Hp + j] = sigma2 * v;
+        S32[(long long)i * Hp + j] = (float)(v * dbg);          // Sigma/sigma2: what the post kernel multiplies by
+    }
+    if (badK) atomicExch(ints + I_ERR, 1);
+    if (threadIdx.x == 0)
+        st[lay.scal() + (which == 0 ? (shadow ? S_LOGDET_SA_SHADOW : S_LOGDET_SA) : S_LOGDET_SB)] = (double)H * log(sigma2) - ldK;
+}
 
 // which = 0: SigmaA from (GB, SigmaB, ca), N = L_global.  which = 1: SigmaB from (GA, SigmaA, cb), N = M.
 // Needs T*T threads and (4*T*R + T*R) doubles of LDS at `lds`; every thread of the block must call it.
@@ -336,16 +364,7 @@ __device__ __forceinline__ void ctrl_cov_dev(double* __restrict__ st, StateLayou
             if (i == j) v += sigma2 / cdiag[i];
             return v;
         }, &ldK, &badK);
-        const double dbg = which == 1 ? 1.0 + 1e-6 * (double)ints[I_DBG_SB_PPM] : 1.0;      // test hook (normally exactly 1)
-        for (int t = threadIdx.x; t < Hp * Hp; t += 256) {
-            const int i = t / Hp, j = t % Hp;
-            const double v = (i < H && j < H) ? spd_inv_at<NBc>(lds, i, j) : 0.0;
-            Sself[(long long)i * Hp + j] = sigma2 * v;
-            S32[(long long)i * Hp + j] = (float)(v * dbg);          // Sigma/sigma2: what the post kernel multiplies by
-        }
-        if (badK) atomicExch(ints + I_ERR, 1);
-        if (threadIdx.x == 0)
-            scal[which == 0 ? (shadow ? S_LOGDET_SA_SHADOW : S_LOGDET_SA) : S_LOGDET_SB] = (double)H * log(sigma2) - ldK;
+        cov_store_lds4<NBc>(st, lay, H, which, sigma2, S32, ints, lds, ldK, badK, shadow);
         return;
     }
     __syncthreads();
@@ -370,27 +389,6 @@ __global__ __launch_bounds__(256) void commit_cov_a_kernel(double* __restrict__ 
         st[lay.SA() + i] = st[lay.W0() + i];
     if (blockIdx.x == 0 && threadIdx.x == 0) st[lay.scal() + S_LOGDET_SA] = st[lay.scal() + S_LOGDET_SA_SHADOW];
 }
-// the same commit by one workgroup (CTRL_COMMIT_A of ctrl_chain), published to the rest of the workgroup by the barrier.
-// It sits ahead of SigmaB on the critical path, so a round's loads are all issued before its stores (src and dst may alias as far
-// as the compiler knows: one element per iteration would cost a memory latency each, 64 of them per thread at Hp = 128).
-__device__ __forceinline__ void commit_cov_a_dev(double* __restrict__ st, StateLayout lay, const int* __restrict__ ints) {
-    if (load_stop(ints)) return;                               // (no other workgroup writes the flag during this launch)
-    const double* src = st + lay.W0();
-    double* dst = st + lay.SA();
-    constexpr int U = 16;
-    const int n = (int)lay.n2(), nt = ctrl_nthreads();         // n = Hp * Hp, a multiple of 4 * 256
-    for (int i0 = threadIdx.x; i0 < n; i0 += U * nt) {
-        double v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = i0 + u * nt < n ? src[i0 + u * nt] : 0.0;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (i0 + u * nt < n) dst[i0 + u * nt] = v[u];
-    }
-    if (threadIdx.x == 0) st[lay.scal() + S_LOGDET_SA] = st[lay.scal() + S_LOGDET_SA_SHADOW];
-    __syncthreads();
-}
-
 template <int R, int T>
 __global__ __launch_bounds__(T * T) void ctrl_cov_kernel(double* __restrict__ st, StateLayout lay, int H, int which,
                                                          double N, float* __restrict__ S32, int* __restrict__ ints) {
@@ -589,10 +587,10 @@ constexpr int EIG_NSQ = 10;
 // which = 0: GD -> S_LAMD, 1: GB -> S_LAMB_NEW.  256 threads, 2*NP*(NP+4) floats of LDS (NP = 16R).
 template <int R>
 __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateLayout lay, int H, int spectral, int which,
-                                        const int* __restrict__ ints, float* ldsf, int slot) {
+                                        const int* __restrict__ ints, float* ldsf, int slot, bool check_stop = true) {
     __shared__ double red[16];
     __shared__ int s_arg;
-    if (load_stop(ints)) return;
+    if (check_stop && load_stop(ints)) return;
     const int Hp = lay.Hp;
     const double* G = st + (which == 0 ? lay.GD() : lay.GB());
     double* scal = st + lay.scal();
@@ -689,16 +687,18 @@ __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateL
 }
 
 // lambda_max of a symmetric PSD H x H matrix: which = 0: GD -> S_LAMD, 1: GB -> S_LAMB_NEW (the slot is the caller's).
+// check_stop = false: the caller has taken the stop decision for the whole workgroup (the per-thread test here is safe only where
+// no other workgroup of the launch can raise the flag meanwhile: threads that disagreed would leave block_sum's barriers unmatched).
 // spectral = 0: Frobenius surrogate (trace) instead.  256 threads (the first 256 of a 512-thread pass launch).  H <= 64: repeated squaring
 // (2 * NP * (NP + 4) floats of LDS); 64 < H <= 128: Lanczos (EIG_LDS_BYTES).
 template <int R>
 __device__ __forceinline__ void eig_dev(double* __restrict__ st, StateLayout lay, int H, int spectral, int which,
-                                        const int* __restrict__ ints, float* ldsf, int slot) {
+                                        const int* __restrict__ ints, float* ldsf, int slot, bool check_stop = true) {
     if (R <= 4 && !(spectral & 2)) {                            // (uniform over the launch)
-        eig_squaring_dev<R>(st, lay, H, spectral & 1, which, ints, ldsf, slot);
+        eig_squaring_dev<R>(st, lay, H, spectral & 1, which, ints, ldsf, slot, check_stop);
     } else {
         __shared__ double red[16];
-        if (load_stop(ints)) return;
+        if (check_stop && load_stop(ints)) return;
         const int Hp = lay.Hp;
         const double* G = st + (which == 0 ? lay.GD() : lay.GB());
         double* scal = st + lay.scal();
@@ -752,9 +752,19 @@ __global__ __launch_bounds__(1024) void eig_lanczos_kernel(double* __restrict__ 
 //        bit5 S_LAMB_PREV already holds lambda_max of the old B'B (no rotation from S_LAMB_NEW)
 //        bit6 split schedule (ctrl_chain): the d / loop part (bit3) is done by ctrl_loop_dev in another workgroup;
 //             this call only files sigma2 / ELBO / residual in trace row it_row
+//
+// ho (the Gram form's first chain launch, ctrl_chain): the SigmaA update that follows in the same workgroup takes over what this
+// function holds instead of starting again from memory.  The loop that feeds the trace term leaves B'B + L SigmaB -- the fp64
+// expression ctrl_cov_dev's elem() forms -- in the inverse's LDS image (np x (np + 2), identity padding), and the final sigma2 and
+// this thread's CA entry come back in ho; live = the function ran (its stop decision, which is uniform over the launch).
+struct EndHandOff {
+    double* img; int np;           // in: the image and its order (16 NB)
+    double sigma2, ca_h;           // out: sigma2 after the update; CA[threadIdx.x] after the update (threads < H)
+    bool live;                     // out: not stopped
+};
 __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayout lay, int H, double Lg, double M,
                                              int flags, double eps, double* __restrict__ trace,
-                                             int* __restrict__ ints, int it_row = -1) {
+                                             int* __restrict__ ints, int it_row, EndHandOff& ho, bool handoff) {
     // Inside a pass launch every dependent round trip to memory costs microseconds (the chip is streaming at full HBM
     // bandwidth around this workgroup), so everything the function needs is requested up front in ONE round -- the stop
     // flag, the scalars, the old CA/CB, the H x H arrays -- and the later stages work from registers and LDS.
@@ -799,10 +809,14 @@ __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayou
                 const int e = e0 + u * ctrl_nthreads();
                 const int i = e >> sh, j = e & (Hp - 1);
                 if (e < total && i == j && i < H) { dg[0][i] = ga[u]; dg[1][i] = sa[u]; dg[2][i] = gb[u]; dg[3][i] = sb[u]; }
-                t2 += (ga[u] + M * sa[u]) * (gb[u] + Lg * sb[u]);
+                const double kb = gb[u] + Lg * sb[u];
+                t2 += (ga[u] + M * sa[u]) * kb;
+                if (handoff && e < total && i < ho.np && j < ho.np)
+                    ho.img[i * (ho.np + 2) + j] = (i < H && j < H) ? kb : (i == j ? 1.0 : 0.0);
             }
         }
     }
+    ho.live = !stopped;
     if (stopped) return;                                         // uniform
     if (hme < 32) sc_s[hme] = scv;
     t2 = block_sum(t2, red);                                     // (its barriers publish sc_s and dg)
@@ -820,6 +834,7 @@ __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayou
     double sigma2 = sc_s[S_SIGMA2];
     if (flags & 4) sigma2 = resid / (Lg * M);
     e = block_sum(e, red);
+    ho.sigma2 = sigma2; ho.ca_h = ca_h;
     if (threadIdx.x == 0) {
         const double PI2 = 6.283185307179586476925286766559;
         double F = -(Lg * M / 2.0) * log(PI2 * sigma2) - resid / (2.0 * sigma2) + e;
@@ -848,10 +863,117 @@ __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayou
     __syncthreads();
 }
 
+__device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayout lay, int H, double Lg, double M,
+                                             int flags, double eps, double* __restrict__ trace,
+                                             int* __restrict__ ints, int it_row = -1) {
+    EndHandOff none{nullptr, 0, 0.0, 1.0, false};
+    ctrl_end_dev(st, lay, H, Lg, M, flags, eps, trace, ints, it_row, none, false);
+}
+
 __global__ __launch_bounds__(1024) void ctrl_end_kernel(double* __restrict__ st, StateLayout lay, int H, double Lg,
                                                        double M, int flags, double eps,
                                                        double* __restrict__ trace, int* __restrict__ ints) {
     ctrl_end_dev(st, lay, H, Lg, M, flags, eps, trace, ints);
+}
+
+// SigmaA (into the shadow) right behind ctrl_end_dev in the same workgroup: the image holds B'B + L SigmaB, the diagonal takes
+// sigma2 / CA_ii -- the two roundings of ctrl_cov_dev's elem(), in its order -- then the sweep and the write-back of ctrl_cov_dev.
+// No stop decision of its own: ctrl_end_dev's (ho.live) stands for both, and a SigmaA left in the shadow just before a stop is
+// never committed.
+// VBMF_SEAM_STAMPS (diagnostic builds only, off by default: the shipped kernels execute no extra stamp): durations of the segments
+// of the two fused steps in 10 ns ticks, in the chain stamps' slots 4-7 (the streaming epilogue's, idle in a Gram-form sweep):
+// [4] SigmaA diagonal add, [5] SigmaA sweep, [6] SigmaA write-back + log-determinant, [7] SigmaB: assembly << 40 | sweep << 20 | write-back
+#ifndef VBMF_SEAM_STAMPS
+#define VBMF_SEAM_STAMPS 0
+#endif
+template <int R>
+__device__ __forceinline__ void cov_a_after_end_dev(double* __restrict__ st, StateLayout lay, int H, const EndHandOff& ho,
+                                                    float* __restrict__ S32, int* __restrict__ ints) {
+    constexpr int LD = 16 * R + 2;
+#if VBMF_SEAM_STAMPS
+    const unsigned long long s0 = wall_clock64();
+#endif
+    if ((int)threadIdx.x < H) ho.img[threadIdx.x * LD + threadIdx.x] += ho.sigma2 / ho.ca_h;   // (ctrl_end_dev ended on a barrier)
+    double ldK; int badK;
+#if VBMF_SEAM_STAMPS
+    __syncthreads();
+    const unsigned long long s1 = wall_clock64();
+#endif
+    spd_sweep_lds4<R>(ho.img, H, &ldK, &badK);
+#if VBMF_SEAM_STAMPS
+    __syncthreads();
+    const unsigned long long s2 = wall_clock64();
+#endif
+    cov_store_lds4<R>(st, lay, H, 0, ho.sigma2, S32, ints, ho.img, ldK, badK, true);
+#if VBMF_SEAM_STAMPS
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long* stamp = reinterpret_cast<unsigned long long*>(ints + 8);
+        stamp[4] = s1 - s0; stamp[5] = s2 - s1; stamp[6] = wall_clock64() - s2;
+    }
+#endif
+}
+
+// The Gram form's second chain launch: commit of the SigmaA shadow and SigmaB in one pass over the operands.  One round of loads of
+// the shadow and A'A per thread; from registers SigmaA goes to the state and A'A + M SigmaA (then sigma2 / CB_ii onto the diagonal:
+// the two roundings of elem() in ctrl_cov_dev, which = 1, in its order) into the inverse's image, so SigmaB does not wait for the commit's stores to come back.  Thread 0 also
+// commits the shadow's log-determinant and lambda_max(B_old'B_old) (S_LAMB_SHADOW, computed ahead by part 2 of the first launch).
+// Everything sits behind one stop gate: a stopped loop commits nothing and computes no SigmaB.
+template <int R>
+__device__ __forceinline__ void commit_cov_b_dev(double* __restrict__ st, StateLayout lay, int H, double M,
+                                                 float* __restrict__ S32, int* __restrict__ ints, double* W) {
+    if (load_stop(ints)) return;                               // uniform: no workgroup writes the flag during this launch
+#if VBMF_SEAM_STAMPS
+    const unsigned long long s0 = wall_clock64();
+#endif
+    constexpr int NP = 16 * R, LD = NP + 2, U = 16;
+    const int Hp = lay.Hp, sh = 31 - __clz(Hp), n = Hp * Hp;   // Hp is a power of two; n a multiple of 4 * 256
+    const double* src = st + lay.W0();
+    const double* GA = st + lay.GA();
+    const double* cb = st + lay.cb();
+    double* dst = st + lay.SA();
+    double* scal = st + lay.scal();
+    const double sigma2 = scal[S_SIGMA2];
+    const double cb_t = (int)threadIdx.x < H ? cb[threadIdx.x] : 1.0;
+    for (int e0 = threadIdx.x; e0 < n; e0 += U * 256) {
+        double sa[U], ga[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * 256;
+            const int ee = e < n ? e : 0;
+            sa[u] = src[ee]; ga[u] = GA[ee];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * 256;
+            if (e >= n) continue;
+            const int i = e >> sh, j = e & (Hp - 1);
+            dst[e] = sa[u];
+            if (i < NP && j < NP) W[i * LD + j] = (i < H && j < H) ? ga[u] + M * sa[u] : (i == j ? 1.0 : 0.0);   // identity padding
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < H) W[threadIdx.x * LD + threadIdx.x] += sigma2 / cb_t;   // the second rounding of elem()'s diagonal
+    if (threadIdx.x == 0) {
+        scal[S_LOGDET_SA] = scal[S_LOGDET_SA_SHADOW];
+        scal[S_LAMB_PREV] = scal[S_LAMB_SHADOW];
+    }
+    double ldK; int badK;
+#if VBMF_SEAM_STAMPS
+    __syncthreads();
+    const unsigned long long s1 = wall_clock64();
+#endif
+    spd_sweep_lds4<R>(W, H, &ldK, &badK);
+#if VBMF_SEAM_STAMPS
+    __syncthreads();
+    const unsigned long long s2 = wall_clock64();
+#endif
+    cov_store_lds4<R>(st, lay, H, 1, sigma2, S32, ints, W, ldK, badK, false);
+#if VBMF_SEAM_STAMPS
+    __syncthreads();
+    if (threadIdx.x == 0)
+        reinterpret_cast<unsigned long long*>(ints + 8)[7] = ((s1 - s0) << 40) | ((s2 - s1) << 20) | (wall_clock64() - s2);
+#endif
 }
 
 // ---- the control chain as run by workgroup 0 of a streaming-pass launch ----------------------------
@@ -874,7 +996,7 @@ struct CtrlArgs {
 // so each pass carries a chain of similar length (~75 / ~65 us at H = 64).
 // The Gram form has no pass launches: the same two parts run as a launch of their own (ctrl_chain_kernel),
 // and the commit of the SigmaA shadow rides in the SigmaB launch ahead of SigmaB (CTRL_COMMIT_A).
-enum : int { CTRL_PREV_END = 1, CTRL_COV_A = 2, CTRL_COV_B = 4, CTRL_EIG_BOLD = 8, CTRL_COMMIT_A = 16 };
+enum : int { CTRL_PREV_END = 1, CTRL_COV_A = 2, CTRL_COV_B = 4, CTRL_EIG_BOLD = 8, CTRL_COMMIT_A = 16, CTRL_EIG_AHEAD = 32 };
 
 // d = ||B_old - B_new||_2 / ||B_old||_2 (src/util.jl:27-29) and the loop test (src/vbmf.jl:193) of sweep it_row
 __device__ __forceinline__ void ctrl_loop_dev(double* __restrict__ st, StateLayout lay, double eps,
@@ -904,18 +1026,52 @@ __device__ __forceinline__ void ctrl_loop_dev(double* __restrict__ st, StateLayo
 // due whether or not the loop stops, SigmaA belongs to the next one and is not.
 // Durations of the chain's parts in 10 ns ticks of the constant 100 MHz clock, kept in ints[8..15] as four 64-bit slots
 // (vbmf_debug_peek(VBMF_PEEK_CHAIN)): [0] ctrl_end, [1] SigmaA, [2] lambda_max(dB'dB) + loop test, [3] SigmaB
-template <int R>
+//
+// SEAMS (ctrl_chain_kernel, the Gram form's launches of the chain alone; the pass launches of the streaming path keep the schedule
+// above, two control workgroups and every step starting from memory):
+//   * part 0 of the first launch hands ctrl_end_dev's operands on to SigmaA (EndHandOff, cov_a_after_end_dev): one round of loads
+//     and one stop decision for both;
+//   * part 0 of the second launch commits the shadow and assembles SigmaB's matrix from the same registers (commit_cov_b_dev);
+//   * lambda_max(B_old'B_old) is part 2 -- a THIRD workgroup -- of the first launch (CTRL_EIG_AHEAD), where it hides behind part 0,
+//     instead of part 1 of the second, which it bounded.  B'B is in place when the first launch starts.  Part 1 of that launch reads
+//     S_LAMB_PREV (for d of the previous sweep) at the same moment, so part 2 writes S_LAMB_SHADOW and thread 0 of the second
+//     launch's part 0 moves it to S_LAMB_PREV beside the commit, behind the same stop gate: S_LAMB_PREV changes exactly when it did.
+//     Part 2's stop decision is taken ONCE for the workgroup (thread 0 reads, barrier): part 1 may raise the flag while part 2
+//     starts, and threads that disagreed would leave block_sum's barriers unmatched.  As in ctrl_end_dev, the value it_row + 1
+//     that part 1 stores during this launch does not count, so the decision -- and with it S_LAMB_SHADOW -- does not depend on
+//     which of the two workgroups gets there first; launches enqueued past a stop do no work.
+// No part waits for another one of its launch.
+template <int R, bool SEAMS = false>
 __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int part) {
     unsigned long long* stamp = reinterpret_cast<unsigned long long*>(a.ints + 8);
     const unsigned long long t0 = wall_clock64();
+    if (SEAMS && part == 2) {
+        __shared__ int stop2_s;
+        if (threadIdx.x == 0) {
+            const int f = load_stop(a.ints);
+            stop2_s = (f != 0 && f != a.it_row + 1) ? 1 : 0;
+        }
+        __syncthreads();
+        if (stop2_s) return;
+        if (a.mode & CTRL_EIG_AHEAD)
+            eig_dev<R>(a.st, a.lay, a.H, a.spectral, 1, a.ints, reinterpret_cast<float*>(lds), S_LAMB_SHADOW, false);
+        return;
+    }
     if (part == 0) {
+        // CTRL_COMMIT_A comes only from gram_sweep, with CTRL_COV_B, in a SEAMS launch: commit_cov_b_dev is the one commit
+        EndHandOff ho{reinterpret_cast<double*>(lds), 16 * R, 0.0, 1.0, false};
+        const bool end_to_a = SEAMS && (a.mode & CTRL_PREV_END) && (a.mode & CTRL_COV_A);
+        const bool commit_to_b = SEAMS && (a.mode & CTRL_COMMIT_A) && (a.mode & CTRL_COV_B);
         if (a.mode & CTRL_PREV_END)
-            ctrl_end_dev(a.st, a.lay, a.H, a.Lg, a.M, (a.end_flags & ~8) | 64, a.eps, a.trace, a.ints, a.it_row);
-        if (a.mode & CTRL_COMMIT_A) commit_cov_a_dev(a.st, a.lay, a.ints);
+            ctrl_end_dev(a.st, a.lay, a.H, a.Lg, a.M, (a.end_flags & ~8) | 64, a.eps, a.trace, a.ints, a.it_row, ho, end_to_a);
         const unsigned long long t1 = wall_clock64();
-        if (a.mode & CTRL_COV_A)
+        if (end_to_a) {
+            if (ho.live) cov_a_after_end_dev<R>(a.st, a.lay, a.H, ho, a.S32, a.ints);
+        } else if (a.mode & CTRL_COV_A) {
             ctrl_cov_dev<R, 16>(a.st, a.lay, a.H, 0, a.Lg, a.S32, a.ints, reinterpret_cast<double*>(lds), true);
-        if (a.mode & CTRL_COV_B) ctrl_cov_dev<R, 16>(a.st, a.lay, a.H, 1, a.M, a.S32, a.ints, reinterpret_cast<double*>(lds));
+        }
+        if (commit_to_b) commit_cov_b_dev<R>(a.st, a.lay, a.H, a.M, a.S32, a.ints, reinterpret_cast<double*>(lds));
+        else if (a.mode & CTRL_COV_B) ctrl_cov_dev<R, 16>(a.st, a.lay, a.H, 1, a.M, a.S32, a.ints, reinterpret_cast<double*>(lds));
         if (threadIdx.x == 0) {
             const unsigned long long t2 = wall_clock64();
             if (a.mode & CTRL_PREV_END) stamp[0] = t1 - t0;
@@ -938,11 +1094,12 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
     }
 }
 
-// the chain as a launch of its own: two workgroups of 256 threads, dynamic LDS as for the pass launches' control workgroups
+// the chain as a launch of its own: workgroups of 256 threads (three in the sweep's first launch, one in its second), dynamic LDS
+// as for the pass launches' control workgroups
 template <int R>
 __global__ __launch_bounds__(256) void ctrl_chain_kernel(CtrlArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_chain[];
-    ctrl_chain<R>(a, lds_chain, blockIdx.x);
+    ctrl_chain<R, true>(a, lds_chain, blockIdx.x);
 }
 
 // ---- vbls! as H x H algebra (examples/mil_util.jl:179-203, vbmf_parameters branch, no label mask) ----------------------------

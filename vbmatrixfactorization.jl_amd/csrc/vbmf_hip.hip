@@ -1127,11 +1127,12 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     return VBMF_OK;
 }
 
-// the control chain as a launch of its own (ctrl_chain_kernel: two workgroups, the parts of ctrl_chain).  R follows H as for the
-// stand-alone control kernels, so every fp64 operation sees the inputs, the work split and the summation order it saw there.
+// the control chain as a launch of its own (ctrl_chain_kernel: one workgroup per part of ctrl_chain that the mode asks for).  R follows
+// H as for the stand-alone control kernels, so every fp64 operation sees the inputs, the work split and the summation order it saw there.
 template <int R>
 static void launch_chain_t(vbmf_ctx* c, const CtrlArgs& ca) {
-    hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(2), dim3(256), ctrl_lds_bytes_r(R), c->stream, ca);
+    const int parts = (ca.mode & CTRL_EIG_AHEAD) ? 3 : ((ca.mode & (CTRL_PREV_END | CTRL_EIG_BOLD)) ? 2 : 1);
+    hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(parts), dim3(256), ctrl_lds_bytes_r(R), c->stream, ca);
 }
 static int launch_chain(vbmf_ctx* c, int mode, float* S32) {
     CtrlArgs ca{};
@@ -1153,11 +1154,12 @@ static int launch_chain(vbmf_ctx* c, int mode, float* S32) {
 // one sweep from P = Y'B_old = G W_old (in gPQ) and the state's B'B: SigmaA, A (label mask) and A'A, SigmaB, then W and the product.
 // The H x H chain runs in two launches of ctrl_chain_kernel, split as in the pass launches of the streaming sweep:
 //   L1  part 0: [ctrl_end of the previous sweep] -> SigmaA (speculative, into the shadow)  |  part 1: [lambda_max(dB'dB) -> d, stop]
-//   L2  part 0: commit of the shadow -> SigmaB                                              |  part 1: lambda_max(B_old'B_old)
-// so the lambda_max solves leave the critical path.  L2 part 1 reads GB before gram_part_reduce overwrites it (kernel boundary).
+//                                                                                           |  part 2: lambda_max(B_old'B_old)
+//   L2  part 0: commit of the shadow and of part 2's lambda_max -> SigmaB
+// so the lambda_max solves leave the critical path.  L1 part 2 reads GB long before gram_part_reduce overwrites it.
 // This sweep's closing step rides in the next sweep's L1, or is the run's stand-alone tail (vbmf_run).
 static int gram_sweep(vbmf_ctx* c) {
-    TRY(launch_chain(c, CTRL_COV_A | (c->tail_pending ? CTRL_PREV_END : 0), c->SA32));
+    TRY(launch_chain(c, CTRL_COV_A | CTRL_EIG_AHEAD | (c->tail_pending ? CTRL_PREV_END : 0), c->SA32));
     if (c->tail_pending) ++c->ends_enqueued;
     c->tail_pending = false;
     c->P_frag = true;
@@ -1166,7 +1168,7 @@ static int gram_sweep(vbmf_ctx* c) {
         TRY(launch_post_frag(c, 0, c->gPQ));
         TRY(launch_gram(c, 0, c->A32, nullptr, true));
     }
-    TRY(launch_chain(c, CTRL_COMMIT_A | CTRL_COV_B | CTRL_EIG_BOLD, c->SB32));
+    TRY(launch_chain(c, CTRL_COMMIT_A | CTRL_COV_B, c->SB32));
     TRY(gram_product(c, true));
     c->wcur ^= 1;
     c->gA_valid = c->gB_valid = true;
