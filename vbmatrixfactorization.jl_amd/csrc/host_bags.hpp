@@ -1,0 +1,413 @@
+// host_bags.hpp -- the five many-bags entries of the C ABI (batched vbls! of the basic and the sparse models, per-bag residuals, least
+// squares and lower bounds) and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
+// helpers it uses, never on its own.  The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.
+//   bags_check     what every entry refuses about (nbags, col_off) and a sharded context; the widest bag, the residual slices
+//   bags_reserve   ONE device scratch buffer (c->bags), grown on demand.  Every entry synchronises before it returns, so no two layouts
+//                  are live together, and writes every slot before it reads it: it starts on whatever the last entry left there
+#pragma once
+
+struct BagDims { int64_t widest = 0, nslices = 0; };          // columns of the widest bag; residual workgroups (SCORE_CW columns each)
+
+static int bags_check(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, BagDims& bd) {
+    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "%s: row-sharded context (one rank only)", fn);
+    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "%s: bad nbags / col_off", fn);
+    if (col_off[0] != 0 || col_off[nbags] != c->M) FAIL(c, VBMF_ERR_INVALID, "%s: col_off must run from 0 to M = %lld", fn, (long long)c->M);
+    bd = BagDims{};
+    for (int64_t b = 0; b < nbags; ++b) {
+        const int64_t w = col_off[b + 1] - col_off[b];
+        if (w <= 0) FAIL(c, VBMF_ERR_INVALID, "%s: bag %lld is empty or col_off decreases", fn, (long long)b);
+        bd.widest = std::max(bd.widest, w);
+        bd.nslices += (w + SCORE_CW - 1) / SCORE_CW;
+    }
+    return VBMF_OK;
+}
+
+static int bags_reserve(vbmf_ctx* c, int64_t doubles, double** d) {
+    if ((size_t)doubles * 8 > c->bags_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->bags) HIPCHK(c, hipFree(c->bags));
+        c->bags = nullptr;
+        c->bags_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&c->bags, (size_t)doubles * 8));
+        c->bags_bytes = (size_t)doubles * 8;
+    }
+    *d = c->bags;
+    return VBMF_OK;
+}
+
+// S_b = P_b'P_b (S = nullptr: not formed) and ||Y_b||^2 of every bag; frag_nh: P is fragment-major (0: row-major [h][x])
+static int bags_launch_gram(vbmf_ctx* c, int64_t nb, const float* P, int frag_nh, const long long* d_off, double* S, double* yy) {
+    DISPATCH_YMODE(c->mode, {
+        hipLaunchKernelGGL((bag_gram_kernel<YMODEc>), dim3((unsigned)nb), dim3(256), 0, c->stream, P, (long long)c->d1.XT * 32, frag_nh,
+                           c->Y2, c->d2.KS, (long long)c->L, d_off, (int)c->H, S, yy);
+    });
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
+// ---- vbls! over many bags ---------------------------------------------------------------------------------------------------------
+extern "C" {
+
+// vbls! over many bags with one fixed basis (examples/mil_util.jl:473-479 in one call).  B, SigmaB, CB come from the state, every
+// other input and output is per bag and lives in c->bags -- the state itself (A, SigmaA, CA, sigma2) is not touched, so the same
+// upload can be run against another basis after another vbmf_set_state.
+int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, double* sigma2, double* CA_diag,
+                                 double* SigmaA, double* AHat, int64_t ldA) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_run_fixed_basis_batched";
+    if (c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: sparse context (the basic model only)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_run_fixed_basis per bag)", fn);
+    if (c->H > 64) FAIL(c, VBMF_ERR_INVALID, "%s: H = %lld > 64", fn, (long long)c->H);
+    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (!sigma2 || !CA_diag) FAIL(c, VBMF_ERR_INVALID, "%s: null sigma2 / CA_diag", fn);
+    if (AHat && ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "%s: ldA < M", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    c->W_valid = false;
+    TRY(ensure_gram_B(c));
+    const int H = (int)c->H;
+    const int64_t nb = nbags, h2 = (int64_t)H * H;
+    // c->bags: [col_off (nb + 1 int64) | sigma2 nb | CA nb H | SigmaA nb H^2 | T nb H^2 | S nb H^2 | ||Y_b||^2 nb | A M H]
+    const int64_t n_off = nb + 1, o_s2 = n_off, o_ca = o_s2 + nb, o_sa = o_ca + nb * H, o_t = o_sa + nb * h2, o_s = o_t + nb * h2,
+                  o_yy = o_s + nb * h2, o_a = o_yy + nb, total = o_a + (int64_t)c->M * H;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    long long* d_off = reinterpret_cast<long long*>(d);
+    std::vector<double> in((size_t)(nb + nb * H));
+    memcpy(in.data(), sigma2, (size_t)nb * 8);
+    memcpy(in.data() + nb, CA_diag, (size_t)nb * H * 8);
+    HIPCHK(c, hipMemcpyAsync(d_off, col_off, (size_t)n_off * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_s2, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+    // P = Y'B of every bag: one pass 1 with the frozen B (no control chain, no A update: the state stays as it is)
+    c->P_frag = fused_gram(c) || frag_post(c);
+    TRY(launch_stream(c, 0, 0, false, nullptr, c->P_frag));
+    c->P_valid = false;
+    if (sharded(c) || c->d1.nsplit > 1) {
+        const long long n = (long long)c->Hp * c->d1.XT * 32;
+        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(n / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, n,
+                           sharded(c) ? c->P : c->Pred, n, c->ints + I_STOP, SideCopy{});
+        HIPCHK(c, hipGetLastError());
+        if (sharded(c)) TRY(allreduce_sum(c, c->P, c->Pred, (size_t)n, false));
+    }
+    const float* Psrc = (sharded(c) || c->d1.nsplit > 1) ? c->Pred : c->P;
+    const long long ldP = (long long)c->d1.XT * 32;
+    const int fnh = c->P_frag ? c->NH : 0;
+    TRY(bags_launch_gram(c, nb, Psrc, fnh, d_off, d + o_s, d + o_yy));
+    const size_t lds = vbls_lds_bytes(nb_tier(H));
+    DISPATCH_NB(nb_tier(H), {
+        hipLaunchKernelGGL((vbls_batch_kernel<NBc>), dim3((unsigned)nb), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, d_off,
+                           (int)niter, d + o_s, d + o_yy, d + o_s2, d + o_ca, d + o_sa, d + o_t, c->ints);
+    });
+    HIPCHK(c, hipGetLastError());
+    if (AHat) {
+        hipLaunchKernelGGL(bag_a_kernel, dim3(grid_for(c->M * H)), dim3(256), 0, c->stream, Psrc, ldP, fnh, d_off, (int)nb, H, d + o_t,
+                           (long long)c->M, d + o_a);
+        HIPCHK(c, hipGetLastError());
+    }
+    // read-back: [sigma2 | CA | SigmaA] is one contiguous block, A one 2-D copy into the caller's leading dimension
+    std::vector<double> out((size_t)(o_t - o_s2));
+    HIPCHK(c, hipMemcpyAsync(out.data(), d + o_s2, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    if (AHat)
+        HIPCHK(c, hipMemcpy2DAsync(AHat, (size_t)ldA * 8, d + o_a, (size_t)c->M * 8, (size_t)c->M * 8, (size_t)H, hipMemcpyDeviceToHost,
+                                   c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(sigma2, out.data(), (size_t)nb * 8);
+    memcpy(CA_diag, out.data() + nb, (size_t)nb * H * 8);
+    if (SigmaA) memcpy(SigmaA, out.data() + (o_sa - o_s2), (size_t)nb * h2 * 8);     // symmetric: row- and column-major alike
+    return check_device_err(c);
+}
+
+// vbls! of the sparse models over many bags with one fixed basis (examples/mil_util.jl:187-197 in one call, both updateA! forms).
+// B, SigmaB come from the state, every other input and output is per bag and lives in c->bags -- the state itself (A, CA, beta,
+// SigmaA, sigma, zeta) is not touched, so one upload serves another basis.
+int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, int full_cov,
+                                        const double* alpha, const double* beta0, const double* eta, const double* zeta0,
+                                        double* sigmaHat, double* CA, double* zeta, double* beta, double* diagSigmaATVec,
+                                        double* SigmaA, double* ATVecHat) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_run_fixed_basis_batched";
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse models only; use vbmf_run_fixed_basis_batched)", fn);
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run_fixed_basis per bag)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run_fixed_basis per bag)", fn);
+    if (c->H > 64) FAIL(c, VBMF_ERR_INVALID, "%s: H = %lld > 64", fn, (long long)c->H);
+    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (!alpha || !beta0 || !eta || !zeta0 || !sigmaHat || !CA) FAIL(c, VBMF_ERR_INVALID, "%s: null alpha / beta0 / eta / zeta0 / sigmaHat / CA", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    TRY(ensure_gram_B(c));
+    const int H = (int)c->H;
+    const int64_t nb = nbags, MH = (int64_t)c->M * H, h2 = (int64_t)H * H;
+    // c->bags: [col_off nb + 1 | alpha nb H | beta0 nb H | eta | zeta0 | sigma | zeta | ||Y_b||^2 (nb each) | CA | A | dS | beta | P (M H each)
+    //           | SigmaA nb H^2 | G H^2 | diag(B'B) H | L diag(SigmaB) H]
+    const int64_t o_al = nb + 1, o_b0 = o_al + nb * H, o_eta = o_b0 + nb * H, o_z0 = o_eta + nb, o_sig = o_z0 + nb, o_zeta = o_sig + nb,
+                  o_yy = o_zeta + nb, o_ca = o_yy + nb, o_a = o_ca + MH, o_ds = o_a + MH, o_be = o_ds + MH, o_p = o_be + MH,
+                  o_sa = o_p + MH, o_g = o_sa + nb * h2, o_gd = o_g + h2, o_sd = o_gd + H, total = o_sd + H;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    long long* d_off = reinterpret_cast<long long*>(d);
+    std::vector<double> in((size_t)(o_zeta - o_al));
+    memcpy(in.data(), alpha, (size_t)nb * H * 8);
+    memcpy(in.data() + (o_b0 - o_al), beta0, (size_t)nb * H * 8);
+    memcpy(in.data() + (o_eta - o_al), eta, (size_t)nb * 8);
+    memcpy(in.data() + (o_z0 - o_al), zeta0, (size_t)nb * 8);
+    memcpy(in.data() + (o_sig - o_al), sigmaHat, (size_t)nb * 8);
+    // The pass and slab kernels are gated by the stop flag, so a raised flag is lowered for this call and raised again after it.  No
+    // path arrives here with it up: only a run loop's closing control step raises it, and every run ends (RunFrame::finish) by writing
+    // zeros over the first four ints.  It could stay up only if that copy itself failed; the step is kept as the guard for that.
+    int ints0[4];
+    HIPCHK(c, memcpy_sync(c, ints0, c->ints, sizeof ints0, hipMemcpyDeviceToHost));
+    if (ints0[I_STOP]) HIPCHK(c, hipMemsetAsync(c->ints + I_STOP, 0, sizeof(int), c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off, col_off, (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_al, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    // P = Y'B of every bag in the plain [h][m] layout: one pass 1 with the frozen B (no A update: the state stays as it is)
+    const int* stop = c->ints + I_STOP;
+    c->P_frag = false;
+    TRY(launch_stream(c, 0));
+    const long long np = (long long)c->Hp * c->d1.XT * 32;
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(np / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, np, c->Pred, np, stop,
+                       SideCopy{});
+    c->P_valid = false;
+    const long long ldP = (long long)c->d1.XT * 32;
+    TRY(bags_launch_gram(c, nb, c->Pred, 0, d_off, nullptr, d + o_yy));
+    hipLaunchKernelGGL(sbatch_g_kernel, dim3(cdiv(h2, 256)), dim3(256), 0, c->stream, c->st, c->lay, H, (double)c->Lg, d + o_g, d + o_gd,
+                       d + o_sd);
+    HIPCHK(c, hipGetLastError());
+    // the bag's state in LDS up to the launch's budget (every bag of an MIL study fits), else in its slices of c->bags
+    const int NBK = nb_tier(H);
+    const size_t cap = (full_cov && NBK == 4) ? SBATCH_LDS_BIG : SBATCH_LDS_SMALL;
+    const int nfix = sbatch_fixed_doubles(full_cov != 0, NBK, H);
+    const int64_t room = (int64_t)(cap / 8) - nfix;
+    const int lds_state = (int)std::max<int64_t>(0, std::min<int64_t>(4 * bd.widest * H, room));
+    const size_t lds = (size_t)(nfix + lds_state) * 8;
+    SbatchArgs a{c->Pred, ldP, d_off, H, (int)niter, (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) ? 1 : 0, lds_state, (double)c->Lg,
+                 d + o_g, d + o_gd, d + o_sd, d + o_al, d + o_b0, d + o_eta, d + o_z0, d + o_yy, d + o_sig, d + o_zeta,
+                 d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_p, d + o_sa, c->ints + I_ERR};
+#define SBATCH(FULLc_) \
+    DISPATCH_NB(NBK, hipLaunchKernelGGL((sparse_batch_kernel<NBc, FULLc_>), dim3((unsigned)nb), dim3(SBATCH_THREADS), lds, c->stream, a))
+    if (full_cov) { SBATCH(true); } else { SBATCH(false); }
+#undef SBATCH
+    HIPCHK(c, hipGetLastError());
+    if (ints0[I_STOP]) HIPCHK(c, hipMemcpyAsync(c->ints + I_STOP, &ints0[I_STOP], sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // read-back: [sigma | zeta] and [CA | A | dS | beta] and SigmaA are contiguous blocks
+    std::vector<double> sz((size_t)2 * nb);
+    HIPCHK(c, hipMemcpyAsync(sz.data(), d + o_sig, sz.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(CA, d + o_ca, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ATVecHat) HIPCHK(c, hipMemcpyAsync(ATVecHat, d + o_a, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (diagSigmaATVec) HIPCHK(c, hipMemcpyAsync(diagSigmaATVec, d + o_ds, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (beta) HIPCHK(c, hipMemcpyAsync(beta, d + o_be, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (SigmaA) HIPCHK(c, hipMemcpyAsync(SigmaA, d + o_sa, (size_t)(nb * h2) * 8, hipMemcpyDeviceToHost, c->stream));   // symmetric
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(sigmaHat, sz.data(), (size_t)nb * 8);
+    if (zeta) memcpy(zeta, sz.data() + nb, (size_t)nb * 8);
+    return check_device_err(c);
+}
+
+}  // extern "C"
+
+// ---- per-bag scoring (score_kernels.hpp) ----------------------------------------------------------------------------------------
+// what the three scoring entries refuse before any launch
+static int score_check(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, BagDims& bd) {
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only)", fn);
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (score_resid_lds_bytes((int)c->H) > 64 * 1024) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (a slice's rows of A exceed 64 KiB of LDS)", fn, (long long)c->H);
+    return VBMF_OK;
+}
+
+// uploads [col_off | chunk_off] to d_off: chunk_off[b] = bag b's first slice number
+static int score_upload_offsets(vbmf_ctx* c, int64_t nb, const int64_t* col_off, long long* d_off) {
+    std::vector<long long> off((size_t)(2 * (nb + 1)));
+    off[(size_t)(nb + 1)] = 0;
+    for (int64_t b = 0; b <= nb; ++b) off[(size_t)b] = col_off[b];
+    for (int64_t b = 0; b < nb; ++b)
+        off[(size_t)(nb + 2 + b)] = off[(size_t)(nb + 1 + b)] + (col_off[b + 1] - col_off[b] + SCORE_CW - 1) / SCORE_CW;
+    HIPCHK(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                // (off is a local)
+    return VBMF_OK;
+}
+
+// uploads the offsets and enqueues the two residual kernels: r2 of every bag into d_r2 (d_part: ns partials).
+// d_A: the device copy of A with element strides (sm, sh).
+static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, int64_t ns, long long* d_off, const double* d_A,
+                              long long sm, long long sh, double* d_part, double* d_r2) {
+    TRY(score_upload_offsets(c, nb, col_off, d_off));
+    TRY(rebuild_B32_if_stale(c));
+    const size_t lds = score_resid_lds_bytes((int)c->H);
+    DISPATCH_YMODE(c->mode, {
+        hipLaunchKernelGGL((bag_resid_kernel<YMODEc>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
+                           (long long)c->L, c->B32[c->bcur], c->Hp, (int)c->H, d_A, sm, sh, d_off, d_off + nb + 1, (int)nb, d_part);
+    });
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, c->stream, d_part, d_off + nb + 1, (int)nb, d_r2);
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
+extern "C" {
+
+// norm(Y - BHat*AHat')^2 of every bag (examples/mil_util.jl:476-479, :518-521) in one call, entry by entry in fp64
+int vbmf_bag_residuals(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const double* AHat, int64_t ldA, double* r2) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_bag_residuals";
+    BagDims bd;
+    TRY(score_check(c, fn, nbags, col_off, bd));
+    if (!AHat || !r2) FAIL(c, VBMF_ERR_INVALID, "%s: null AHat / r2", fn);
+    if (ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "%s: ldA < M", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    const int64_t nb = nbags, ns = bd.nslices, H = c->H;
+    // c->bags: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | partials ns | A M H (column-major, ld M)]
+    const int64_t o_r2 = 2 * (nb + 1), o_part = o_r2 + nb, o_a = o_part + ns, total = o_a + c->M * H;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    HIPCHK(c, hipMemcpy2DAsync(d + o_a, (size_t)c->M * 8, AHat, (size_t)ldA * 8, (size_t)c->M * 8, (size_t)H, hipMemcpyHostToDevice, c->stream));
+    TRY(score_launch_resid(c, nb, col_off, ns, reinterpret_cast<long long*>(d), d + o_a, 1, (long long)c->M, d + o_part, d + o_r2));
+    HIPCHK(c, memcpy_sync(c, r2, d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost));
+    for (int64_t b = 0; b < nb; ++b)
+        if (!std::isfinite(r2[b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
+    return VBMF_OK;
+}
+
+// ols / rls of examples/mil_util.jl:159-171 and the norm(Y - BHat*AT)^2 of :483-484 for every bag, against the caller's fp64 basis
+int vbmf_bag_least_squares(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const double* BHat, int64_t ldB, int64_t H, double lambda,
+                           double* X, int64_t ldX, double* r2) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_bag_least_squares";
+    if (H < 1 || H > LS_MAX_H) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for 1 <= H <= %d)", fn, (long long)H, LS_MAX_H);
+    BagDims bd;
+    TRY(score_check(c, fn, nbags, col_off, bd));
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) FAIL(c, VBMF_ERR_INVALID, "%s: lambda must be finite and >= 0", fn);
+    if (!BHat) FAIL(c, VBMF_ERR_INVALID, "%s: null BHat", fn);
+    if (!X && !r2) FAIL(c, VBMF_ERR_INVALID, "%s: X and r2 are both NULL", fn);
+    const int64_t L = c->L, M = c->M, nb = nbags, ns = bd.nslices;
+    if (ldB < L) FAIL(c, VBMF_ERR_INVALID, "%s: ldB < L", fn);
+    if (X && ldX < H) FAIL(c, VBMF_ERR_INVALID, "%s: ldX < H", fn);
+    std::vector<double> Bt((size_t)(L * H));                   // row-major [L][H]
+    for (int64_t h = 0; h < H; ++h)
+        for (int64_t l = 0; l < L; ++l) {
+            const double v = BHat[h * ldB + l];
+            if (!std::isfinite(v)) FAIL(c, VBMF_ERR_INVALID, "%s: BHat[%lld, %lld] is not finite", fn, (long long)l, (long long)h);
+            Bt[(size_t)(l * H + h)] = v;
+        }
+    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the basis is an argument)
+    HIPCHK(c, hipSetDevice(c->o.device));
+    const int64_t nchunk = cdiv(L, LS_ROWS), h2 = H * H;
+    // c->bags: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | bad-pivot flag | partials ns | B L H (row-major) | Gram partials nchunk H^2
+    //           | K H^2 | X M H (column m at m H)]
+    // (the flag slot starts with another entry's bytes: bag_ls_inverse_kernel stores it on every launch)
+    const int64_t o_r2 = 2 * (nb + 1), o_flag = o_r2 + nb, o_part = o_flag + 1, o_b = o_part + ns, o_g = o_b + L * H,
+                  o_k = o_g + nchunk * h2, o_x = o_k + h2, total = o_x + M * H;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    long long* d_off = reinterpret_cast<long long*>(d);
+    HIPCHK(c, hipMemcpyAsync(d + o_b, Bt.data(), Bt.size() * 8, hipMemcpyHostToDevice, c->stream));
+    TRY(score_upload_offsets(c, nb, col_off, d_off));           // (its synchronize also covers Bt)
+    hipLaunchKernelGGL(bag_ls_gram_kernel, dim3((unsigned)nchunk), dim3(SCORE_THREADS), 0, c->stream, d + o_b, (long long)L, (int)H, d + o_g);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(bag_ls_inverse_kernel, dim3(1), dim3(256), spd_inverse_lds_bytes(LS_MAX_H / 16), c->stream, d + o_g, (int)nchunk,
+                       (int)H, lambda, d + o_k, reinterpret_cast<int*>(d + o_flag));
+    HIPCHK(c, hipGetLastError());
+    double* d_x = X ? d + o_x : nullptr;
+    double* d_part = r2 ? d + o_part : nullptr;
+    const size_t lds = score_ls_lds_bytes((int)H);
+    DISPATCH_YMODE(c->mode, {
+        hipLaunchKernelGGL((bag_ls_kernel<YMODEc>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
+                           d + o_b, (int)H, d + o_k, d_off, d_off + nb + 1, (int)nb, d_x, d_part);
+    });
+    HIPCHK(c, hipGetLastError());
+    if (r2) {
+        hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, c->stream, d_part, d_off + nb + 1, (int)nb, d + o_r2);
+        HIPCHK(c, hipGetLastError());
+    }
+    std::vector<double> res((size_t)(nb + 1));                  // r2 | flag
+    HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
+    int bad = 0;
+    std::memcpy(&bad, &res[(size_t)nb], sizeof(int));
+    if (bad) FAIL(c, VBMF_ERR_NUMERIC, "%s: B'B + lambda I is not positive definite (a pivot is not positive or not finite)", fn);
+    if (r2)
+        for (int64_t b = 0; b < nb; ++b)
+            if (!std::isfinite(res[(size_t)b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
+    if (X) {
+        HIPCHK(c, hipMemcpy2DAsync(X, (size_t)ldX * 8, d + o_x, (size_t)H * 8, (size_t)H * 8, (size_t)M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (r2) std::memcpy(r2, res.data(), (size_t)nb * 8);
+    return VBMF_OK;
+}
+
+// lowerBound / lowerBoundTrimmed of every bag (examples/mil_util.jl:502-514 after a batched vbls!)
+int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int clamp, double trim, int grouped,
+                                    const double* ATVecHat, const double* diagSigmaATVec, const double* CA, const double* beta,
+                                    const double* SigmaA, const double* sigmaHat, const double* zeta, const double* eta,
+                                    const double* eta0, const double* zeta0, const double* a_pri, const double* b_pri,
+                                    const double* a_post, double* lb, double* r2) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_lower_bound_batched";
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse models only)", fn);
+    BagDims bd;
+    TRY(score_check(c, fn, nbags, col_off, bd));
+    if (!ATVecHat || !diagSigmaATVec || !CA || !beta || !SigmaA || !sigmaHat || !zeta || !eta || !eta0 || !zeta0 || !a_pri || !b_pri ||
+        !a_post || !lb)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only r2 may be NULL)", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_ready(c));
+    TRY(ensure_gram_B(c));
+    const int H = (int)c->H;
+    const int64_t nb = nbags, ns = bd.nslices, MH = (int64_t)c->M * H, h2 = (int64_t)H * H;
+    // c->bags: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | partials ns | A | dS | CA | beta (M H each, vec(A') order) | SigmaA nb H^2
+    //           | sums nb H SCORE_NS | quad 2 nb]
+    const int64_t o_r2 = 2 * (nb + 1), o_part = o_r2 + nb, o_a = o_part + ns, o_ds = o_a + MH, o_ca = o_ds + MH, o_be = o_ca + MH,
+                  o_sa = o_be + MH, o_sums = o_sa + nb * h2, o_quad = o_sums + nb * H * SCORE_NS, total = o_quad + 2 * nb;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    HIPCHK(c, hipMemcpyAsync(d + o_a, ATVecHat, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ds, diagSigmaATVec, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_be, beta, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_sa, SigmaA, (size_t)(nb * h2) * 8, hipMemcpyHostToDevice, c->stream));
+    long long* d_off = reinterpret_cast<long long*>(d);
+    TRY(score_launch_resid(c, nb, col_off, ns, d_off, d + o_a, (long long)H, 1, d + o_part, d + o_r2));
+    hipLaunchKernelGGL(bag_lb_sums_kernel, dim3((unsigned)nb), dim3(SCORE_THREADS), 0, c->stream, d + o_a, d + o_ds, d + o_ca, d + o_be,
+                       d + o_sa, c->st, c->lay, H, (double)c->Lg, d_off, trim, d + o_sums, d + o_quad);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> res((size_t)nb), sums((size_t)(total - o_sums)), buf((size_t)c->lay.total());
+    HIPCHK(c, hipMemcpyAsync(res.data(), d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), d + o_sums, sums.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, memcpy_sync(c, buf.data(), c->st, buf.size() * 8, hipMemcpyDeviceToHost));
+    LbSums s{};
+    lb_basis_sums(c, buf, s);
+    const bool trimmed = trim >= 0.0;
+    std::vector<LbGroup> grp((size_t)H);
+    const double* quad = sums.data() + (o_quad - o_sums);
+    for (int64_t b = 0; b < nb; ++b) {
+        const double Mb = (double)(col_off[b + 1] - col_off[b]);
+        const double* sb = sums.data() + (size_t)b * H * SCORE_NS;
+        double n_keep = 0, s_caq = 0, s_logds = 0;
+        for (int h = 0; h < H; ++h) {
+            const double* v = sb + (size_t)h * SCORE_NS;
+            n_keep += v[2]; s_caq += v[5]; s_logds += v[6];
+            // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
+            const bool cut = trimmed && !grouped;
+            grp[(size_t)h] = LbGroup{cut ? v[2] : Mb, cut ? v[3] : v[0], cut ? v[4] : v[1], a_pri[b * H + h], b_pri[b * H + h], a_post[b * H + h]};
+        }
+        s.M = Mb;
+        s.MH = trimmed ? n_keep : Mb * (double)H;
+        s.sig = sigmaHat[b]; s.zeta = zeta[b]; s.eta = eta[b];
+        s.hyp.eta0 = eta0[b]; s.hyp.zeta0 = zeta0[b];
+        s.quad = res[(size_t)b] + s.L * quad[2 * b] + quad[2 * b + 1];
+        s.s_caq = s_caq; s.s_logds = s_logds;
+        s.g = grp.data(); s.ng = H;
+        const double v = lb_assemble(s, clamp);
+        if (!std::isfinite(v) || !std::isfinite(s.quad) || !std::isfinite(s_caq) || !std::isfinite(s_logds))
+            FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite sum in bag %lld", fn, (long long)b);
+        lb[b] = v;
+        if (r2) r2[b] = res[(size_t)b];
+    }
+    return VBMF_OK;
+}
+
+}  // extern "C"

@@ -23,6 +23,8 @@
 //
 // vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): ONE pass 1 with the frozen B over the bags side by side,
 // then bag_gram (S_b = P_b'P_b, ||Y_b||^2), vbls_batch (all iterations, one workgroup per bag) and bag_a (A_b = P_b SigmaA_b / sigma2_b).
+// Here: the context, the launchers, set-up and read-back, the single-matrix updates and run loops (vbmf_run and sparse_run_impl around
+// one RunFrame), the sparse / grouped variants and the lower bounds.  The five many-bags entries and what they share: host_bags.hpp.
 #include "../../include/vbmf_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -163,12 +165,8 @@ struct vbmf_ctx {
     vbmf_allreduce_fn ar_hook = nullptr;   // bring-up transport instead of RCCL (vbmf_comm_set_transport)
     void* ar_user = nullptr;
     int lds_limit = 65536;
-    double* bat = nullptr;            // vbmf_run_fixed_basis_batched: per-bag inputs / outputs and the fp64 A (grown on demand)
-    size_t bat_bytes = 0;
-    double* sbat = nullptr;           // vbmf_sparse_run_fixed_basis_batched: the same for the sparse models (grown on demand)
-    size_t sbat_bytes = 0;
-    double* score = nullptr;          // vbmf_bag_residuals / vbmf_sparse_lower_bound_batched: per-bag inputs, partials and sums (grown on demand)
-    size_t score_bytes = 0;
+    double* bags = nullptr;           // the many-bags entries (host_bags.hpp): per-bag inputs, partials and outputs of the call in
+    size_t bags_bytes = 0;            // flight, each entry in its own layout (grown on demand)
     // Gram-form sweep of vbmf_run (gram_kernels.hpp); buffers allocated by the first run that takes it
     int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows
     int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
@@ -240,6 +238,22 @@ static hipError_t memcpy_sync(vbmf_ctx* c, void* dst, const void* src, size_t n,
         case MODE_BF16: { constexpr int MODEc = MODE_BF16; __VA_ARGS__; } break;   \
         case MODE_BF16X2: { constexpr int MODEc = MODE_BF16X2; __VA_ARGS__; } break; \
         default: break;                                                            \
+    }
+
+// Y as the per-bag kernels read it from its tiles: fp32 or bf16 (bf16x2 is a factor mode; Y itself is bf16 there)
+#define DISPATCH_YMODE(md, ...)                                               \
+    switch (md) {                                                             \
+        case MODE_F32: { constexpr int YMODEc = MODE_F32; __VA_ARGS__; } break; \
+        default: { constexpr int YMODEc = MODE_BF16; __VA_ARGS__; } break;    \
+    }
+// NB = 16 x 16 blocks across an H x H image of the one-workgroup vbls! kernels (H <= 64)
+static inline int nb_tier(int64_t H) { return H <= 16 ? 1 : (H <= 32 ? 2 : 4); }
+#define DISPATCH_NB(nb, ...)                                   \
+    switch (nb) {                                              \
+        case 1: { constexpr int NBc = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int NBc = 2; __VA_ARGS__; } break; \
+        case 4: { constexpr int NBc = 4; __VA_ARGS__; } break; \
+        default: break;                                        \
     }
 
 static inline int64_t rup(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
@@ -1264,6 +1278,79 @@ static int check_device_err(vbmf_ctx* c) {
     return VBMF_OK;
 }
 
+// What vbmf_run and sparse_run_impl do around their (deliberately different) loops.  The frame owns the device trace: its
+// destructor frees it on every path out of the run, early returns included.
+struct RunFrame {
+    vbmf_ctx* c;
+    int64_t niter;
+    double eps;
+    int64_t* iters_done;
+    double *d_last, *trace;
+    double* trace_dev = nullptr;
+    int64_t done = -1;                                     // sweeps the device executed (-1: not read back)
+
+    ~RunFrame() { release(); }
+    void release() { if (trace_dev) hipFree(trace_dev); trace_dev = nullptr; }
+    // the device, the state, the callers' defaults
+    int open() {
+        HIPCHK(c, hipSetDevice(c->o.device));
+        TRY(ensure_ready(c));
+        if (iters_done) *iters_done = 0;
+        if (d_last) *d_last = eps + 1.0;                   // src/vbmf.jl:189, src/vbmf_sparse.jl:364
+        return VBMF_OK;
+    }
+    // the trace buffer, the loop counters {stop, iters, err, niter} and the ranks' summed error flag
+    int arm() {
+        if (trace) {
+            HIPCHK(c, hipMalloc((void**)&trace_dev, (size_t)niter * 4 * 8));
+            HIPCHK(c, hipMemsetAsync(trace_dev, 0, (size_t)niter * 4 * 8, c->stream));
+        }
+        int init[4] = {0, 0, 0, (int)niter};
+        HIPCHK(c, hipMemcpyAsync(c->ints, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->st + c->lay.GX() + 1, 0, sizeof(double), c->stream));   // the ranks' summed error flags (packed message)
+        return VBMF_OK;
+    }
+    // drains both streams, reads back the counters and the 32 scalars, settles c->bcur (B moved in the first `b_sweeps` executed sweeps,
+    // from buffer `bstart`), the fp32 B, the outputs and the trace, maps the device's error flag to a status, clears the counters
+    int finish(int rc, int bstart, int64_t b_sweeps) {
+        c->in_run = false;
+        c->use_side = false;
+        c->side_pending = false;
+        hipStreamSynchronize(c->side);
+        hipStreamSynchronize(c->stream);
+        if (rc == VBMF_OK) {
+            hipError_t e = hipMemcpyAsync(c->ints_host, c->ints, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(c->scal_host, c->st + c->lay.scal(), 32 * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { c->err = std::string("run readback: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+        }
+        if (rc == VBMF_OK) {
+            done = c->ints_host[I_ITERS];                  // sweeps after `stop` were no-ops on the device
+            c->bcur = bstart ^ (int)(std::min<int64_t>(done, b_sweeps) & 1);
+            rc = rebuild_B32_if_stale(c);                  // the fp32 factor from the tiles the last executed sweep wrote
+            if (iters_done) *iters_done = done;
+            if (d_last && done > 0) *d_last = c->scal_host[S_D];
+            if (rc == VBMF_OK && trace && done > 0 && memcpy_sync(c, trace, trace_dev, (size_t)done * 4 * 8, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "trace copy failed"; rc = VBMF_ERR_HIP; }
+            const int e = c->ints_host[I_ERR];
+            if (e && c->sparse) {
+                c->err = std::string("non-positive or non-finite pivot while inverting the posterior precision of B") +
+                         ((e & 0x200) ? " (reported by another rank of the row-sharded run; every rank stopped at that sweep)" : "");
+                rc = VBMF_ERR_NUMERIC;
+            } else if (e) {
+                rc = device_err_status(c, e);
+            } else if (rc == VBMF_OK) {
+                run_note_eps(c, niter, eps, done, c->scal_host[S_D]);
+            }
+        }
+        int zero4[4] = {0, 0, 0, 0};
+        memcpy_sync(c, c->ints, zero4, sizeof zero4, hipMemcpyHostToDevice);
+        release();
+        c->gA_valid = c->gB_valid = true;
+        c->P_valid = false;
+        return rc;
+    }
+};
+
 __global__ void logdet_kernel(double* st, StateLayout lay, int H, int which, int use_lds) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ int err;
@@ -1301,8 +1388,8 @@ int vbmf_destroy(vbmf_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     void* bufs[] = {c->sk_list, c->sk_tail, c->gw, c->hmean, c->fws, c->t2part, c->Y1, c->Y2, c->FA_alloc, c->FB_alloc, c->FD, c->SBf, c->P, c->Q, c->Pred, c->A32, c->B32[0], c->B32[1], c->SA32,
                     c->SB32, c->gslab, c->st, c->gtmp, c->ypart, c->trpart, c->ints, c->mask, c->dS32, c->CA32, c->beta32, c->vtab,
-                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bat, c->Gt, c->W32g[0], c->W32g[1], c->Wt, c->gslabs, c->gPQ,
-                    c->g_part, c->gsave, c->sbat, c->score};
+                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bags, c->Gt, c->W32g[0], c->W32g[1], c->Wt, c->gslabs, c->gPQ,
+                    c->g_part, c->gsave};
     for (void* b : bufs) if (b) hipFree(b);
     if (c->ints_host) hipHostFree(c->ints_host);
     if (c->scal_host) hipHostFree(c->scal_host);
@@ -1953,11 +2040,11 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
         hipLaunchKernelGGL(identity_table_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, c->stream, c->SA32, H, c->Hp);
         TRY(launch_post_gram(c, 0, Psrc));
         hipLaunchKernelGGL(copy_doubles_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, c->stream, c->st + c->lay.GA(), c->st + c->lay.W1(), n2);
-        const int NBv = H <= 16 ? 1 : (H <= 32 ? 2 : 4);
-        const size_t lds = vbls_lds_bytes(NBv);                // (the attribute for NB = 4: vbmf_create)
-        if (NBv == 1) hipLaunchKernelGGL((vbls_loop_kernel<1>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M, (int)(niter - 1), c->SA32, c->ints);
-        else if (NBv == 2) hipLaunchKernelGGL((vbls_loop_kernel<2>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M, (int)(niter - 1), c->SA32, c->ints);
-        else hipLaunchKernelGGL((vbls_loop_kernel<4>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M, (int)(niter - 1), c->SA32, c->ints);
+        const size_t lds = vbls_lds_bytes(nb_tier(H));         // (the attribute for NB = 4: vbmf_create)
+        DISPATCH_NB(nb_tier(H), {
+            hipLaunchKernelGGL((vbls_loop_kernel<NBc>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M,
+                               (int)(niter - 1), c->SA32, c->ints);
+        });
         HIPCHK(c, hipGetLastError());
         TRY(launch_post_gram(c, 0, Psrc));                  // A = P SigmaA / sigma2 of the last updateA!, its tiles and A'A
         c->gA_valid = true;
@@ -1966,120 +2053,20 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
     return check_device_err(c);
 }
 
-// vbls! over many bags with one fixed basis (examples/mil_util.jl:473-479 in one call).  The context's Y holds the bags side by side;
-// B, SigmaB, CB come from the state, every other input and output is per bag and lives in c->bat -- the state itself (A, SigmaA, CA,
-// sigma2) is not touched, so the same upload can be run against another basis after another vbmf_set_state.
-int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, double* sigma2, double* CA_diag,
-                                 double* SigmaA, double* AHat, int64_t ldA) {
-    if (!c) return VBMF_ERR_INVALID;
-    if (c->sparse) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: sparse context (the basic model only)");
-    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: a label mask is set (use vbmf_run_fixed_basis per bag)");
-    if (c->H > 64) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: H = %lld > 64", (long long)c->H);
-    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: row-sharded context (one rank only)");
-    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: niter must be >= 1");
-    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: bad nbags / col_off");
-    if (col_off[0] != 0 || col_off[nbags] != c->M)
-        FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: col_off must run from 0 to M = %lld", (long long)c->M);
-    for (int64_t b = 0; b < nbags; ++b)
-        if (col_off[b + 1] <= col_off[b]) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: bag %lld is empty or col_off decreases", (long long)b);
-    if (!sigma2 || !CA_diag) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: null sigma2 / CA_diag");
-    if (AHat && ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis_batched: ldA < M");
-    HIPCHK(c, hipSetDevice(c->o.device));
-    TRY(ensure_ready(c));
-    c->W_valid = false;
-    TRY(ensure_gram_B(c));
-    const int H = (int)c->H;
-    const int64_t nb = nbags, h2 = (int64_t)H * H;
-    // c->bat: [col_off (nb + 1 int64) | sigma2 nb | CA nb H | SigmaA nb H^2 | T nb H^2 | S nb H^2 | ||Y_b||^2 nb | A M H]
-    const int64_t n_off = nb + 1, o_s2 = n_off, o_ca = o_s2 + nb, o_sa = o_ca + nb * H, o_t = o_sa + nb * h2, o_s = o_t + nb * h2,
-                  o_yy = o_s + nb * h2, o_a = o_yy + nb, total = o_a + (int64_t)c->M * H;
-    if ((size_t)total * 8 > c->bat_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->bat) HIPCHK(c, hipFree(c->bat));
-        c->bat = nullptr;
-        c->bat_bytes = 0;
-        HIPCHK(c, hipMalloc((void**)&c->bat, (size_t)total * 8));
-        c->bat_bytes = (size_t)total * 8;
-    }
-    double* d = c->bat;
-    long long* d_off = reinterpret_cast<long long*>(d);
-    std::vector<double> in((size_t)(nb + nb * H));
-    memcpy(in.data(), sigma2, (size_t)nb * 8);
-    memcpy(in.data() + nb, CA_diag, (size_t)nb * H * 8);
-    HIPCHK(c, hipMemcpyAsync(d_off, col_off, (size_t)n_off * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_s2, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
-    // P = Y'B of every bag: one pass 1 with the frozen B (no control chain, no A update: the state stays as it is)
-    c->P_frag = fused_gram(c) || frag_post(c);
-    TRY(launch_stream(c, 0, 0, false, nullptr, c->P_frag));
-    c->P_valid = false;
-    if (sharded(c) || c->d1.nsplit > 1) {
-        const long long n = (long long)c->Hp * c->d1.XT * 32;
-        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(n / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, n,
-                           sharded(c) ? c->P : c->Pred, n, c->ints + I_STOP, SideCopy{});
-        HIPCHK(c, hipGetLastError());
-        if (sharded(c)) TRY(allreduce_sum(c, c->P, c->Pred, (size_t)n, false));
-    }
-    const float* Psrc = (sharded(c) || c->d1.nsplit > 1) ? c->Pred : c->P;
-    const long long ldP = (long long)c->d1.XT * 32;
-    const int fnh = c->P_frag ? c->NH : 0;
-    if (c->mode == MODE_F32)
-        hipLaunchKernelGGL((bag_gram_kernel<MODE_F32>), dim3((unsigned)nb), dim3(256), 0, c->stream, Psrc, ldP, fnh, c->Y2, c->d2.KS,
-                           (long long)c->L, d_off, H, d + o_s, d + o_yy);
-    else
-        hipLaunchKernelGGL((bag_gram_kernel<MODE_BF16>), dim3((unsigned)nb), dim3(256), 0, c->stream, Psrc, ldP, fnh, c->Y2, c->d2.KS,
-                           (long long)c->L, d_off, H, d + o_s, d + o_yy);
-    HIPCHK(c, hipGetLastError());
-    const int NBv = H <= 16 ? 1 : (H <= 32 ? 2 : 4);
-    const size_t lds = vbls_lds_bytes(NBv);
-#define VBLS_BATCH(NBc_)                                                                                                              \
-    hipLaunchKernelGGL((vbls_batch_kernel<NBc_>), dim3((unsigned)nb), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg,   \
-                       d_off, (int)niter, d + o_s, d + o_yy, d + o_s2, d + o_ca, d + o_sa, d + o_t, c->ints)
-    if (NBv == 1) VBLS_BATCH(1);
-    else if (NBv == 2) VBLS_BATCH(2);
-    else VBLS_BATCH(4);
-#undef VBLS_BATCH
-    HIPCHK(c, hipGetLastError());
-    if (AHat) {
-        hipLaunchKernelGGL(bag_a_kernel, dim3(grid_for(c->M * H)), dim3(256), 0, c->stream, Psrc, ldP, fnh, d_off, (int)nb, H, d + o_t,
-                           (long long)c->M, d + o_a);
-        HIPCHK(c, hipGetLastError());
-    }
-    // read-back: [sigma2 | CA | SigmaA] is one contiguous block, A one 2-D copy into the caller's leading dimension
-    std::vector<double> out((size_t)(o_t - o_s2));
-    HIPCHK(c, hipMemcpyAsync(out.data(), d + o_s2, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    if (AHat)
-        HIPCHK(c, hipMemcpy2DAsync(AHat, (size_t)ldA * 8, d + o_a, (size_t)c->M * 8, (size_t)c->M * 8, (size_t)H, hipMemcpyDeviceToHost,
-                                   c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(sigma2, out.data(), (size_t)nb * 8);
-    memcpy(CA_diag, out.data() + nb, (size_t)nb * H * 8);
-    if (SigmaA) memcpy(SigmaA, out.data() + (o_sa - o_s2), (size_t)nb * h2 * 8);     // symmetric: row- and column-major alike
-    return check_device_err(c);
-}
-
 int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, int64_t* iters_done,
              double* d_last, double* trace) {
     if (!c) return VBMF_ERR_INVALID;
     if (c->sparse) FAIL(c, VBMF_ERR_INVALID, "sparse context: use vbmf_sparse_run");
     if (niter < 0 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "vbmf_run: bad niter");
-    HIPCHK(c, hipSetDevice(c->o.device));
-    TRY(ensure_ready(c));
-    if (iters_done) *iters_done = 0;
-    if (d_last) *d_last = eps + 1.0;                       // src/vbmf.jl:189
+    RunFrame run{c, niter, eps, iters_done, d_last, trace};
+    TRY(run.open());
     if (niter == 0) return VBMF_OK;
     // Gram form: G = Y'Y is built here once per Y; a run that starts without a valid W does its first sweep
     // by the streaming path
     const bool gram = gram_eligible(c);
     if (gram) TRY(gram_prepare(c));
     else c->W_valid = false;
-    double* trace_dev = nullptr;
-    if (trace) {
-        HIPCHK(c, hipMalloc((void**)&trace_dev, (size_t)niter * 4 * 8));
-        HIPCHK(c, hipMemsetAsync(trace_dev, 0, (size_t)niter * 4 * 8, c->stream));
-    }
-    int init[4] = {0, 0, 0, (int)niter};
-    HIPCHK(c, hipMemcpyAsync(c->ints, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->st + c->lay.GX() + 1, 0, sizeof(double), c->stream));   // the ranks' summed error flags (packed message)
+    TRY(run.arm());
     // ||B_old||_2 of the first comparison (src/vbmf.jl:187-188: old = params.BHat): in the fused schedule
     // every sweep's pass-2 launch computes it; otherwise once here, then rotated by ctrl_end
     int rc = ensure_gram_B(c);
@@ -2097,7 +2084,7 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     c->tail_pending = false;
     c->run_flags = flags;
     c->run_eps = eps;
-    c->run_trace = trace_dev;
+    c->run_trace = run.trace_dev;
     // The host runs ahead of the device; every `check` sweeps it queues a copy of the device's stop/error flags and
     // looks at the PREVIOUS copy (long complete), so the device never waits for the host.  Sweeps enqueued past the stop
     // are no-ops on the device (every kernel begins with the stop test): at most 2*check of them.
@@ -2128,13 +2115,13 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
                 c->tail_pending = true;      // rides in the next sweep's pass-1 launch (Gram form: its first chain launch)
             } else if (fused_ctrl(c)) {
                 rc = launch_eig(c, 1, 0);
-                if (rc == VBMF_OK) rc = launch_ctrl_end(c, flags | 32, eps, trace_dev);
+                if (rc == VBMF_OK) rc = launch_ctrl_end(c, flags | 32, eps, run.trace_dev);
                 ++c->ends_enqueued;
             } else {
                 // H > 128: beside the next sweep's Y'B pass (side stream)
                 if (side_overlap(c)) rc = side_fork(c);
                 if (rc == VBMF_OK) rc = launch_eig(c, 1, 1);
-                if (rc == VBMF_OK) rc = launch_ctrl_end(c, flags, eps, trace_dev);
+                if (rc == VBMF_OK) rc = launch_ctrl_end(c, flags, eps, run.trace_dev);
                 if (rc == VBMF_OK && c->use_side) rc = side_end(c);
             }
         }
@@ -2154,44 +2141,15 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
             slot ^= 1;
         }
     }
-    c->in_run = false;
     c->tail_pending = false;
     c->run_trace = nullptr;
-    c->use_side = false;
-    c->side_pending = false;
-    hipStreamSynchronize(c->side);
-    hipStreamSynchronize(c->stream);
-    if (rc == VBMF_OK) {
-        hipError_t e = hipMemcpyAsync(c->ints_host, c->ints, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->scal_host, c->st + c->lay.scal(), 32 * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { c->err = std::string("run readback: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
-    }
+    // in the Gram form only the streaming sweep (the first, if any) moves B, and every sweep moves W
+    rc = run.finish(rc, bstart, stream_sweeps);
     int64_t gram_done = 0;                                 // Gram-form sweeps the device executed
-    if (rc == VBMF_OK) {
-        const int done = c->ints_host[I_ITERS];
-        // sweeps after `stop` were no-ops on the device; in the Gram form only the streaming sweep (the first, if any) moves B,
-        // and every sweep moves W
-        const int64_t sdone = std::min<int64_t>(done, stream_sweeps);
-        c->bcur = bstart ^ (int)(sdone & 1);
-        if (gram) {
-            c->wcur = wstart ^ (done & 1);
-            gram_done = done - sdone;
-        }
-        rc = rebuild_B32_if_stale(c);                     // the fp32 factor from the tiles the last executed sweep wrote
-        if (iters_done) *iters_done = done;
-        if (d_last && done > 0) *d_last = c->scal_host[S_D];
-        if (trace && done > 0) {
-            if (memcpy_sync(c, trace, trace_dev, (size_t)done * 4 * 8, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "trace copy failed"; rc = VBMF_ERR_HIP; }
-        }
-        if (c->ints_host[I_ERR]) rc = device_err_status(c, c->ints_host[I_ERR]);
-        else run_note_eps(c, niter, eps, done, c->scal_host[S_D]);
+    if (gram && run.done >= 0) {
+        c->wcur = wstart ^ (int)(run.done & 1);
+        gram_done = run.done - std::min<int64_t>(run.done, stream_sweeps);
     }
-    int zero4[4] = {0, 0, 0, 0};
-    memcpy_sync(c, c->ints, zero4, sizeof zero4, hipMemcpyHostToDevice);
-    if (trace_dev) hipFree(trace_dev);
-    c->gA_valid = c->gB_valid = true;
-    c->P_valid = false;
     c->tr_valid = true;
     if (gram && rc != VBMF_OK) c->W_valid = false;
     if (gram && rc == VBMF_OK && gram_done > 0) {
@@ -2889,136 +2847,15 @@ int vbmf_sparse_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
     return check_device_err(c);
 }
 
-// vbls! of the sparse models over many bags with one fixed basis (examples/mil_util.jl:187-197 in one call, both updateA! forms).
-// The context's Y holds the bags side by side; B, SigmaB come from the state, every other input and output is per bag and lives in
-// c->sbat -- the state itself (A, CA, beta, SigmaA, sigma, zeta) is not touched, so one upload serves another basis.
-int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, int full_cov,
-                                        const double* alpha, const double* beta0, const double* eta, const double* zeta0,
-                                        double* sigmaHat, double* CA, double* zeta, double* beta, double* diagSigmaATVec,
-                                        double* SigmaA, double* ATVecHat) {
-    if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_sparse_run_fixed_basis_batched";
-    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse models only; use vbmf_run_fixed_basis_batched)", fn);
-    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run_fixed_basis per bag)", fn);
-    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run_fixed_basis per bag)", fn);
-    if (c->H > 64) FAIL(c, VBMF_ERR_INVALID, "%s: H = %lld > 64", fn, (long long)c->H);
-    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "%s: row-sharded context (one rank only)", fn);
-    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
-    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "%s: bad nbags / col_off", fn);
-    if (col_off[0] != 0 || col_off[nbags] != c->M) FAIL(c, VBMF_ERR_INVALID, "%s: col_off must run from 0 to M = %lld", fn, (long long)c->M);
-    int64_t Mmax = 0;
-    for (int64_t b = 0; b < nbags; ++b) {
-        if (col_off[b + 1] <= col_off[b]) FAIL(c, VBMF_ERR_INVALID, "%s: bag %lld is empty or col_off decreases", fn, (long long)b);
-        Mmax = std::max<int64_t>(Mmax, col_off[b + 1] - col_off[b]);
-    }
-    if (!alpha || !beta0 || !eta || !zeta0 || !sigmaHat || !CA) FAIL(c, VBMF_ERR_INVALID, "%s: null alpha / beta0 / eta / zeta0 / sigmaHat / CA", fn);
-    HIPCHK(c, hipSetDevice(c->o.device));
-    TRY(ensure_ready(c));
-    TRY(ensure_gram_B(c));
-    const int H = (int)c->H;
-    const int64_t nb = nbags, MH = (int64_t)c->M * H, h2 = (int64_t)H * H;
-    // c->sbat: [col_off nb + 1 | alpha nb H | beta0 nb H | eta | zeta0 | sigma | zeta | ||Y_b||^2 (nb each) | CA | A | dS | beta | P (M H each)
-    //           | SigmaA nb H^2 | G H^2 | diag(B'B) H | L diag(SigmaB) H]
-    const int64_t o_al = nb + 1, o_b0 = o_al + nb * H, o_eta = o_b0 + nb * H, o_z0 = o_eta + nb, o_sig = o_z0 + nb, o_zeta = o_sig + nb,
-                  o_yy = o_zeta + nb, o_ca = o_yy + nb, o_a = o_ca + MH, o_ds = o_a + MH, o_be = o_ds + MH, o_p = o_be + MH,
-                  o_sa = o_p + MH, o_g = o_sa + nb * h2, o_gd = o_g + h2, o_sd = o_gd + H, total = o_sd + H;
-    if ((size_t)total * 8 > c->sbat_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->sbat) HIPCHK(c, hipFree(c->sbat));
-        c->sbat = nullptr;
-        c->sbat_bytes = 0;
-        HIPCHK(c, hipMalloc((void**)&c->sbat, (size_t)total * 8));
-        c->sbat_bytes = (size_t)total * 8;
-    }
-    double* d = c->sbat;
-    long long* d_off = reinterpret_cast<long long*>(d);
-    std::vector<double> in((size_t)(o_zeta - o_al));
-    memcpy(in.data(), alpha, (size_t)nb * H * 8);
-    memcpy(in.data() + (o_b0 - o_al), beta0, (size_t)nb * H * 8);
-    memcpy(in.data() + (o_eta - o_al), eta, (size_t)nb * 8);
-    memcpy(in.data() + (o_z0 - o_al), zeta0, (size_t)nb * 8);
-    memcpy(in.data() + (o_sig - o_al), sigmaHat, (size_t)nb * 8);
-    // a finished vbmf_sparse_run leaves the stop flag raised, and the pass and slab kernels are gated by it: lowered for this call and
-    // raised again after it
-    int ints0[4];
-    HIPCHK(c, memcpy_sync(c, ints0, c->ints, sizeof ints0, hipMemcpyDeviceToHost));
-    if (ints0[I_STOP]) HIPCHK(c, hipMemsetAsync(c->ints + I_STOP, 0, sizeof(int), c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_off, col_off, (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_al, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
-    // P = Y'B of every bag in the plain [h][m] layout: one pass 1 with the frozen B (no A update: the state stays as it is)
-    const int* stop = c->ints + I_STOP;
-    c->P_frag = false;
-    TRY(launch_stream(c, 0));
-    const long long np = (long long)c->Hp * c->d1.XT * 32;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(np / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, np, c->Pred, np, stop,
-                       SideCopy{});
-    c->P_valid = false;
-    const long long ldP = (long long)c->d1.XT * 32;
-    if (c->mode == MODE_F32)
-        hipLaunchKernelGGL((bag_gram_kernel<MODE_F32>), dim3((unsigned)nb), dim3(256), 0, c->stream, c->Pred, ldP, 0, c->Y2, c->d2.KS,
-                           (long long)c->L, d_off, H, (double*)nullptr, d + o_yy);
-    else
-        hipLaunchKernelGGL((bag_gram_kernel<MODE_BF16>), dim3((unsigned)nb), dim3(256), 0, c->stream, c->Pred, ldP, 0, c->Y2, c->d2.KS,
-                           (long long)c->L, d_off, H, (double*)nullptr, d + o_yy);
-    hipLaunchKernelGGL(sbatch_g_kernel, dim3(cdiv(h2, 256)), dim3(256), 0, c->stream, c->st, c->lay, H, (double)c->Lg, d + o_g, d + o_gd,
-                       d + o_sd);
-    HIPCHK(c, hipGetLastError());
-    // the bag's state in LDS up to the launch's budget (every bag of an MIL study fits), else in its slices of c->sbat
-    const int NBK = H <= 16 ? 1 : (H <= 32 ? 2 : 4);
-    const size_t cap = (full_cov && NBK == 4) ? SBATCH_LDS_BIG : SBATCH_LDS_SMALL;
-    const int nfix = sbatch_fixed_doubles(full_cov != 0, NBK, H);
-    const int64_t room = (int64_t)(cap / 8) - nfix;
-    const int lds_state = (int)std::max<int64_t>(0, std::min<int64_t>(4 * Mmax * H, room));
-    const size_t lds = (size_t)(nfix + lds_state) * 8;
-    SbatchArgs a{c->Pred, ldP, d_off, H, (int)niter, (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) ? 1 : 0, lds_state, (double)c->Lg,
-                 d + o_g, d + o_gd, d + o_sd, d + o_al, d + o_b0, d + o_eta, d + o_z0, d + o_yy, d + o_sig, d + o_zeta,
-                 d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_p, d + o_sa, c->ints + I_ERR};
-#define SBATCH(NBc_, FULLc_) hipLaunchKernelGGL((sparse_batch_kernel<NBc_, FULLc_>), dim3((unsigned)nb), dim3(SBATCH_THREADS), lds, c->stream, a)
-    if (full_cov) {
-        if (NBK == 1) SBATCH(1, true);
-        else if (NBK == 2) SBATCH(2, true);
-        else SBATCH(4, true);
-    } else {
-        if (NBK == 1) SBATCH(1, false);
-        else if (NBK == 2) SBATCH(2, false);
-        else SBATCH(4, false);
-    }
-#undef SBATCH
-    HIPCHK(c, hipGetLastError());
-    if (ints0[I_STOP]) HIPCHK(c, hipMemcpyAsync(c->ints + I_STOP, &ints0[I_STOP], sizeof(int), hipMemcpyHostToDevice, c->stream));
-    // read-back: [sigma | zeta] and [CA | A | dS | beta] and SigmaA are contiguous blocks
-    std::vector<double> sz((size_t)2 * nb);
-    HIPCHK(c, hipMemcpyAsync(sz.data(), d + o_sig, sz.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(CA, d + o_ca, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
-    if (ATVecHat) HIPCHK(c, hipMemcpyAsync(ATVecHat, d + o_a, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
-    if (diagSigmaATVec) HIPCHK(c, hipMemcpyAsync(diagSigmaATVec, d + o_ds, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
-    if (beta) HIPCHK(c, hipMemcpyAsync(beta, d + o_be, (size_t)MH * 8, hipMemcpyDeviceToHost, c->stream));
-    if (SigmaA) HIPCHK(c, hipMemcpyAsync(SigmaA, d + o_sa, (size_t)(nb * h2) * 8, hipMemcpyDeviceToHost, c->stream));   // symmetric
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(sigmaHat, sz.data(), (size_t)nb * 8);
-    if (zeta) memcpy(zeta, sz.data() + nb, (size_t)nb * 8);
-    return check_device_err(c);
-}
-
 static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, int est_priors, int64_t* iters_done,
                            double* d_last, double* trace) {
     if (!c) return VBMF_ERR_INVALID;
     if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "not a sparse context");
     if (niter < 0 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "bad niter");
-    HIPCHK(c, hipSetDevice(c->o.device));
-    TRY(ensure_ready(c));
-    if (iters_done) *iters_done = 0;
-    if (d_last) *d_last = eps + 1.0;                      // src/vbmf_sparse.jl:364
+    RunFrame run{c, niter, eps, iters_done, d_last, trace};
+    TRY(run.open());
     if (niter == 0) return VBMF_OK;
-    double* trace_dev = nullptr;
-    if (trace) {
-        HIPCHK(c, hipMalloc((void**)&trace_dev, (size_t)niter * 4 * 8));
-        HIPCHK(c, hipMemsetAsync(trace_dev, 0, (size_t)niter * 4 * 8, c->stream));
-    }
-    int init[4] = {0, 0, 0, (int)niter};
-    HIPCHK(c, hipMemcpyAsync(c->ints, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->st + c->lay.GX() + 1, 0, sizeof(double), c->stream));   // the ranks' summed error flags (packed message)
+    TRY(run.arm());
     int rc = ensure_gram_B(c);
     if (rc == VBMF_OK) rc = launch_eig(c, 0, 1);
     if (rc == VBMF_OK)
@@ -3044,7 +2881,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         const bool t2_ahead = c->use_side && !c->diagvar;        // (diag_var: no scalar noise update, t2 is not used)
         if (rc == VBMF_OK && t2_ahead) rc = launch_sparse_t2(c);   // 64 workgroups, before the long lambda_max kernel
         if (rc == VBMF_OK) rc = launch_eig(c, 1, 1);
-        if (rc == VBMF_OK) rc = launch_sparse_ctrl_end(c, flags, eps, trace_dev, t2_ahead);
+        if (rc == VBMF_OK) rc = launch_sparse_ctrl_end(c, flags, eps, run.trace_dev, t2_ahead);
         if (rc == VBMF_OK && c->use_side) rc = side_end(c);
         ++it;
         if (rc == VBMF_OK && (it % 8 == 0 || it == niter)) {
@@ -3056,37 +2893,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
             if (c->ints_host[I_STOP] || (!sharded(c) && c->ints_host[I_ERR])) stopped = true;   // (see vbmf_run)
         }
     }
-    c->in_run = false;
-    c->use_side = false;
-    c->side_pending = false;
-    hipStreamSynchronize(c->side);
-    hipStreamSynchronize(c->stream);
-    if (rc == VBMF_OK) {
-        hipError_t e = memcpy_sync(c, c->ints_host, c->ints, 4 * sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = memcpy_sync(c, c->scal_host, c->st + c->lay.scal(), 32 * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = "sparse run readback failed"; rc = VBMF_ERR_HIP; }
-    }
-    if (rc == VBMF_OK) {
-        const int done = c->ints_host[I_ITERS];
-        c->bcur = bstart ^ (done & 1);
-        rc = rebuild_B32_if_stale(c);
-        if (iters_done) *iters_done = done;
-        if (d_last && done > 0) *d_last = c->scal_host[S_D];
-        if (rc == VBMF_OK && trace && done > 0 && memcpy_sync(c, trace, trace_dev, (size_t)done * 4 * 8, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "trace copy failed"; rc = VBMF_ERR_HIP; }
-        if (c->ints_host[I_ERR]) {
-            const bool remote = (c->ints_host[I_ERR] & 0x200) != 0;
-            c->err = std::string("non-positive or non-finite pivot while inverting the posterior precision of B") +
-                     (remote ? " (reported by another rank of the row-sharded run; every rank stopped at that sweep)" : "");
-            rc = VBMF_ERR_NUMERIC;
-        } else if (rc == VBMF_OK) {
-            run_note_eps(c, niter, eps, done, c->scal_host[S_D]);
-        }
-    }
-    int zero4[4] = {0, 0, 0, 0};
-    memcpy_sync(c, c->ints, zero4, sizeof zero4, hipMemcpyHostToDevice);
-    if (trace_dev) hipFree(trace_dev);
-    c->gA_valid = c->gB_valid = true;
-    c->P_valid = false;
+    rc = run.finish(rc, bstart, niter);                    // every sweep moves B
     c->Q_valid = false;
     c->tr_valid = !c->diagvar;
     return rc;
@@ -3400,227 +3207,4 @@ int vbmf_sparse_lower_bound_trimmed(vbmf_ctx* c, int clamp, double trim, double*
 
 }  // extern "C"
 
-// ---- per-bag scoring (score_kernels.hpp) ----------------------------------------------------------------------------------------
-// what both entries refuse before any launch; nslices: the residual workgroups of the call
-static int score_check(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, int64_t* nslices) {
-    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only)", fn);
-    if (c->o.nranks > 1) FAIL(c, VBMF_ERR_INVALID, "%s: row-sharded context (one rank only)", fn);
-    if (nbags < 1 || nbags > (1ll << 30) || !col_off) FAIL(c, VBMF_ERR_INVALID, "%s: bad nbags / col_off", fn);
-    if (col_off[0] != 0 || col_off[nbags] != c->M) FAIL(c, VBMF_ERR_INVALID, "%s: col_off must run from 0 to M = %lld", fn, (long long)c->M);
-    int64_t ns = 0;
-    for (int64_t b = 0; b < nbags; ++b) {
-        if (col_off[b + 1] <= col_off[b]) FAIL(c, VBMF_ERR_INVALID, "%s: bag %lld is empty or col_off decreases", fn, (long long)b);
-        ns += (col_off[b + 1] - col_off[b] + SCORE_CW - 1) / SCORE_CW;
-    }
-    if (score_resid_lds_bytes((int)c->H) > 64 * 1024) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (a slice's rows of A exceed 64 KiB of LDS)", fn, (long long)c->H);
-    *nslices = ns;
-    return VBMF_OK;
-}
-
-static int score_reserve(vbmf_ctx* c, int64_t doubles) {
-    if ((size_t)doubles * 8 <= c->score_bytes) return VBMF_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->score) HIPCHK(c, hipFree(c->score));
-    c->score = nullptr;
-    c->score_bytes = 0;
-    HIPCHK(c, hipMalloc((void**)&c->score, (size_t)doubles * 8));
-    c->score_bytes = (size_t)doubles * 8;
-    return VBMF_OK;
-}
-
-// uploads [col_off | chunk_off] to d_off: chunk_off[b] = bag b's first slice number
-static int score_upload_offsets(vbmf_ctx* c, int64_t nb, const int64_t* col_off, long long* d_off) {
-    std::vector<long long> off((size_t)(2 * (nb + 1)));
-    off[(size_t)(nb + 1)] = 0;
-    for (int64_t b = 0; b <= nb; ++b) off[(size_t)b] = col_off[b];
-    for (int64_t b = 0; b < nb; ++b)
-        off[(size_t)(nb + 2 + b)] = off[(size_t)(nb + 1 + b)] + (col_off[b + 1] - col_off[b] + SCORE_CW - 1) / SCORE_CW;
-    HIPCHK(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                // (off is a local)
-    return VBMF_OK;
-}
-
-// uploads the offsets and enqueues the two residual kernels: r2 of every bag into d_r2 (d_part: ns partials).
-// d_A: the device copy of A with element strides (sm, sh).
-static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, int64_t ns, long long* d_off, const double* d_A,
-                              long long sm, long long sh, double* d_part, double* d_r2) {
-    TRY(score_upload_offsets(c, nb, col_off, d_off));
-    TRY(rebuild_B32_if_stale(c));
-    const size_t lds = score_resid_lds_bytes((int)c->H);
-    if (c->mode == MODE_F32)
-        hipLaunchKernelGGL((bag_resid_kernel<MODE_F32>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
-                           (long long)c->L, c->B32[c->bcur], c->Hp, (int)c->H, d_A, sm, sh, d_off, d_off + nb + 1, (int)nb, d_part);
-    else
-        hipLaunchKernelGGL((bag_resid_kernel<MODE_BF16>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
-                           (long long)c->L, c->B32[c->bcur], c->Hp, (int)c->H, d_A, sm, sh, d_off, d_off + nb + 1, (int)nb, d_part);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, c->stream, d_part, d_off + nb + 1, (int)nb, d_r2);
-    HIPCHK(c, hipGetLastError());
-    return VBMF_OK;
-}
-
-extern "C" {
-
-// norm(Y - BHat*AHat')^2 of every bag (examples/mil_util.jl:476-479, :518-521) in one call, entry by entry in fp64
-int vbmf_bag_residuals(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const double* AHat, int64_t ldA, double* r2) {
-    if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_bag_residuals";
-    int64_t ns = 0;
-    TRY(score_check(c, fn, nbags, col_off, &ns));
-    if (!AHat || !r2) FAIL(c, VBMF_ERR_INVALID, "%s: null AHat / r2", fn);
-    if (ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "%s: ldA < M", fn);
-    HIPCHK(c, hipSetDevice(c->o.device));
-    TRY(ensure_ready(c));
-    const int64_t nb = nbags, H = c->H;
-    // c->score: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | partials ns | A M H (column-major, ld M)]
-    const int64_t o_r2 = 2 * (nb + 1), o_part = o_r2 + nb, o_a = o_part + ns, total = o_a + c->M * H;
-    TRY(score_reserve(c, total));
-    double* d = c->score;
-    HIPCHK(c, hipMemcpy2DAsync(d + o_a, (size_t)c->M * 8, AHat, (size_t)ldA * 8, (size_t)c->M * 8, (size_t)H, hipMemcpyHostToDevice, c->stream));
-    TRY(score_launch_resid(c, nb, col_off, ns, reinterpret_cast<long long*>(d), d + o_a, 1, (long long)c->M, d + o_part, d + o_r2));
-    HIPCHK(c, memcpy_sync(c, r2, d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost));
-    for (int64_t b = 0; b < nb; ++b)
-        if (!std::isfinite(r2[b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
-    return VBMF_OK;
-}
-
-// ols / rls of examples/mil_util.jl:159-171 and the norm(Y - BHat*AT)^2 of :483-484 for every bag, against the caller's fp64 basis
-int vbmf_bag_least_squares(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, const double* BHat, int64_t ldB, int64_t H, double lambda,
-                           double* X, int64_t ldX, double* r2) {
-    if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_bag_least_squares";
-    if (H < 1 || H > LS_MAX_H) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for 1 <= H <= %d)", fn, (long long)H, LS_MAX_H);
-    int64_t ns = 0;
-    TRY(score_check(c, fn, nbags, col_off, &ns));
-    if (!(lambda >= 0.0) || !std::isfinite(lambda)) FAIL(c, VBMF_ERR_INVALID, "%s: lambda must be finite and >= 0", fn);
-    if (!BHat) FAIL(c, VBMF_ERR_INVALID, "%s: null BHat", fn);
-    if (!X && !r2) FAIL(c, VBMF_ERR_INVALID, "%s: X and r2 are both NULL", fn);
-    const int64_t L = c->L, M = c->M, nb = nbags;
-    if (ldB < L) FAIL(c, VBMF_ERR_INVALID, "%s: ldB < L", fn);
-    if (X && ldX < H) FAIL(c, VBMF_ERR_INVALID, "%s: ldX < H", fn);
-    std::vector<double> Bt((size_t)(L * H));                   // row-major [L][H]
-    for (int64_t h = 0; h < H; ++h)
-        for (int64_t l = 0; l < L; ++l) {
-            const double v = BHat[h * ldB + l];
-            if (!std::isfinite(v)) FAIL(c, VBMF_ERR_INVALID, "%s: BHat[%lld, %lld] is not finite", fn, (long long)l, (long long)h);
-            Bt[(size_t)(l * H + h)] = v;
-        }
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the basis is an argument)
-    HIPCHK(c, hipSetDevice(c->o.device));
-    const int64_t nchunk = cdiv(L, LS_ROWS), h2 = H * H;
-    // c->score: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | bad-pivot flag | partials ns | B L H (row-major) | Gram partials nchunk H^2
-    //            | K H^2 | X M H (column m at m H)]
-    const int64_t o_r2 = 2 * (nb + 1), o_flag = o_r2 + nb, o_part = o_flag + 1, o_b = o_part + ns, o_g = o_b + L * H,
-                  o_k = o_g + nchunk * h2, o_x = o_k + h2, total = o_x + M * H;
-    TRY(score_reserve(c, total));
-    double* d = c->score;
-    long long* d_off = reinterpret_cast<long long*>(d);
-    HIPCHK(c, hipMemcpyAsync(d + o_b, Bt.data(), Bt.size() * 8, hipMemcpyHostToDevice, c->stream));
-    TRY(score_upload_offsets(c, nb, col_off, d_off));           // (its synchronize also covers Bt)
-    hipLaunchKernelGGL(bag_ls_gram_kernel, dim3((unsigned)nchunk), dim3(SCORE_THREADS), 0, c->stream, d + o_b, (long long)L, (int)H, d + o_g);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(bag_ls_inverse_kernel, dim3(1), dim3(256), spd_inverse_lds_bytes(LS_MAX_H / 16), c->stream, d + o_g, (int)nchunk,
-                       (int)H, lambda, d + o_k, reinterpret_cast<int*>(d + o_flag));
-    HIPCHK(c, hipGetLastError());
-    double* d_x = X ? d + o_x : nullptr;
-    double* d_part = r2 ? d + o_part : nullptr;
-    const size_t lds = score_ls_lds_bytes((int)H);
-    if (c->mode == MODE_F32)
-        hipLaunchKernelGGL((bag_ls_kernel<MODE_F32>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
-                           d + o_b, (int)H, d + o_k, d_off, d_off + nb + 1, (int)nb, d_x, d_part);
-    else
-        hipLaunchKernelGGL((bag_ls_kernel<MODE_BF16>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
-                           d + o_b, (int)H, d + o_k, d_off, d_off + nb + 1, (int)nb, d_x, d_part);
-    HIPCHK(c, hipGetLastError());
-    if (r2) {
-        hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nb, 256)), dim3(256), 0, c->stream, d_part, d_off + nb + 1, (int)nb, d + o_r2);
-        HIPCHK(c, hipGetLastError());
-    }
-    std::vector<double> res((size_t)(nb + 1));                  // r2 | flag
-    HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
-    int bad = 0;
-    std::memcpy(&bad, &res[(size_t)nb], sizeof(int));
-    if (bad) FAIL(c, VBMF_ERR_NUMERIC, "%s: B'B + lambda I is not positive definite (a pivot is not positive or not finite)", fn);
-    if (r2)
-        for (int64_t b = 0; b < nb; ++b)
-            if (!std::isfinite(res[(size_t)b])) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in bag %lld", fn, (long long)b);
-    if (X) {
-        HIPCHK(c, hipMemcpy2DAsync(X, (size_t)ldX * 8, d + o_x, (size_t)H * 8, (size_t)H * 8, (size_t)M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (r2) std::memcpy(r2, res.data(), (size_t)nb * 8);
-    return VBMF_OK;
-}
-
-// lowerBound / lowerBoundTrimmed of every bag (examples/mil_util.jl:502-514 after a batched vbls!)
-int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int clamp, double trim, int grouped,
-                                    const double* ATVecHat, const double* diagSigmaATVec, const double* CA, const double* beta,
-                                    const double* SigmaA, const double* sigmaHat, const double* zeta, const double* eta,
-                                    const double* eta0, const double* zeta0, const double* a_pri, const double* b_pri,
-                                    const double* a_post, double* lb, double* r2) {
-    if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_sparse_lower_bound_batched";
-    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse models only)", fn);
-    int64_t ns = 0;
-    TRY(score_check(c, fn, nbags, col_off, &ns));
-    if (!ATVecHat || !diagSigmaATVec || !CA || !beta || !SigmaA || !sigmaHat || !zeta || !eta || !eta0 || !zeta0 || !a_pri || !b_pri ||
-        !a_post || !lb)
-        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only r2 may be NULL)", fn);
-    HIPCHK(c, hipSetDevice(c->o.device));
-    TRY(ensure_ready(c));
-    TRY(ensure_gram_B(c));
-    const int H = (int)c->H;
-    const int64_t nb = nbags, MH = (int64_t)c->M * H, h2 = (int64_t)H * H;
-    // c->score: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | partials ns | A | dS | CA | beta (M H each, vec(A') order) | SigmaA nb H^2
-    //            | sums nb H SCORE_NS | quad 2 nb]
-    const int64_t o_r2 = 2 * (nb + 1), o_part = o_r2 + nb, o_a = o_part + ns, o_ds = o_a + MH, o_ca = o_ds + MH, o_be = o_ca + MH,
-                  o_sa = o_be + MH, o_sums = o_sa + nb * h2, o_quad = o_sums + nb * H * SCORE_NS, total = o_quad + 2 * nb;
-    TRY(score_reserve(c, total));
-    double* d = c->score;
-    HIPCHK(c, hipMemcpyAsync(d + o_a, ATVecHat, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_ds, diagSigmaATVec, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_be, beta, (size_t)MH * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_sa, SigmaA, (size_t)(nb * h2) * 8, hipMemcpyHostToDevice, c->stream));
-    long long* d_off = reinterpret_cast<long long*>(d);
-    TRY(score_launch_resid(c, nb, col_off, ns, d_off, d + o_a, (long long)H, 1, d + o_part, d + o_r2));
-    hipLaunchKernelGGL(bag_lb_sums_kernel, dim3((unsigned)nb), dim3(SCORE_THREADS), 0, c->stream, d + o_a, d + o_ds, d + o_ca, d + o_be,
-                       d + o_sa, c->st, c->lay, H, (double)c->Lg, d_off, trim, d + o_sums, d + o_quad);
-    HIPCHK(c, hipGetLastError());
-    std::vector<double> res((size_t)nb), sums((size_t)(total - o_sums)), buf((size_t)c->lay.total());
-    HIPCHK(c, hipMemcpyAsync(res.data(), d + o_r2, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sums.data(), d + o_sums, sums.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, memcpy_sync(c, buf.data(), c->st, buf.size() * 8, hipMemcpyDeviceToHost));
-    LbSums s{};
-    lb_basis_sums(c, buf, s);
-    const bool trimmed = trim >= 0.0;
-    std::vector<LbGroup> grp((size_t)H);
-    const double* quad = sums.data() + (o_quad - o_sums);
-    for (int64_t b = 0; b < nb; ++b) {
-        const double Mb = (double)(col_off[b + 1] - col_off[b]);
-        const double* sb = sums.data() + (size_t)b * H * SCORE_NS;
-        double n_keep = 0, s_caq = 0, s_logds = 0;
-        for (int h = 0; h < H; ++h) {
-            const double* v = sb + (size_t)h * SCORE_NS;
-            n_keep += v[2]; s_caq += v[5]; s_logds += v[6];
-            // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
-            const bool cut = trimmed && !grouped;
-            grp[(size_t)h] = LbGroup{cut ? v[2] : Mb, cut ? v[3] : v[0], cut ? v[4] : v[1], a_pri[b * H + h], b_pri[b * H + h], a_post[b * H + h]};
-        }
-        s.M = Mb;
-        s.MH = trimmed ? n_keep : Mb * (double)H;
-        s.sig = sigmaHat[b]; s.zeta = zeta[b]; s.eta = eta[b];
-        s.hyp.eta0 = eta0[b]; s.hyp.zeta0 = zeta0[b];
-        s.quad = res[(size_t)b] + s.L * quad[2 * b] + quad[2 * b + 1];
-        s.s_caq = s_caq; s.s_logds = s_logds;
-        s.g = grp.data(); s.ng = H;
-        const double v = lb_assemble(s, clamp);
-        if (!std::isfinite(v) || !std::isfinite(s.quad) || !std::isfinite(s_caq) || !std::isfinite(s_logds))
-            FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite sum in bag %lld", fn, (long long)b);
-        lb[b] = v;
-        if (r2) r2[b] = res[(size_t)b];
-    }
-    return VBMF_OK;
-}
-
-}  // extern "C"
+#include "host_bags.hpp"
