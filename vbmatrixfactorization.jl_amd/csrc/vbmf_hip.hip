@@ -2292,12 +2292,12 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (what == VBMF_PEEK_DIMS) {
-        const int v[26] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
+        const int v[27] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
                            c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
                            gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
                            c->frag_last[0] ? 1 : 0, c->frag_last[1] ? 1 : 0, c->epi_last ? 1 : 0, use_lds8(c) ? 1 : 0, c->xcd_map ? 1 : 0,
-                           c->post3 ? 1 : 0};
-        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(26, nwords));
+                           c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0};
+        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(27, nwords));
         return VBMF_OK;
     }
     if (what == VBMF_PEEK_CHAIN) {
