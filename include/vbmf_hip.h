@@ -198,7 +198,34 @@ int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* ctx, int64_t nbags, const int6
                                         const double* alpha, const double* beta0, const double* eta, const double* zeta0,
                                         double* sigmaHat, double* CA, double* zeta, double* beta, double* diagSigmaATVec,
                                         double* SigmaA, double* ATVecHat);
-int vbmf_sparse_step(vbmf_ctx* ctx, int which);            /* reference order A, B, CA, CB, SIGMA (:369-376) */
+/* vbmf_sparse_fit_batched: many independent vbmf_sparse! / vbmf_dual! fits (B moves too) in ONE launch, one workgroup per fit with the
+ * whole `while i <= niter && d > eps` loop inside it -- the restart loops of examples/mil_util.jl:124-145,347-379 and the folds x
+ * classes around them (:670-788) in one call.  The context supplies only Y, bags side by side (bag b = columns col_off[b] ..
+ * col_off[b+1]-1); its own state is neither read nor changed (none needs to be set).  Fit f works on bag fit_bag[f], so several fits
+ * (restarts) may share a bag.  A sparse-model or two-group context (`*_DIAG` variants), one rank, no label mask, H <= 32.
+ *   per fit (nfits): gamma, delta0, eta, zeta0 -- the derived shapes gamma0 + L/2, eta0 + L M_b/2 and the prior rates
+ *   priors4 (nfits*4, in/out): alpha00, beta00, alpha01, beta01 -- columns h < H0 of A take the first pair, the others the second
+ *       (src/vbmf_dual.jl:322-351); the sparse model passes its pair twice with H0 = H.  est_priors != 0 refits them every sweep
+ *       (:393-434) and returns the fitted values
+ *   in/out, per-fit blocks in fit order: BHat (L*H, column-major), SigmaB (H*H), CB (H), sigmaHat (1), CA (M_b*H, vec(A') order,
+ *       concatenated by each fit's own M_b)
+ *   out (any may be NULL): delta (H; written only when est_cb), zeta (1), beta, diagSigmaATVec, ATVecHat (M_b*H), SigmaA (H*H:
+ *       diagonal in the diagonal form, the sum of the per-column blocks under full_cov)
+ *   iters_done, d_last, status (nfits): the sweeps run, the last d, and 1 for a fit that met a non-finite precision or a pivot that is
+ *       not positive and left its loop after that sweep (0 otherwise).  Such fits do not fail the call: the restart loops expect them
+ *       (:130-132).  trace (nfits*niter*2, may be NULL): (d, sigmaHat) per sweep run, zeros after.
+ * d = norm(B_old - B) / norm(B_old) with operator 2-norms under VBMF_COMPAT_SPECTRAL_DELTA (src/util.jl:27-29), Frobenius norms
+ * otherwise; the loop ends when !(d > eps), so a NaN d ends it as the reference's comparison does.  Everything is fp64 on Y as stored.
+ * VBMF_ERR_UNSUPPORTED: H > 32.  VBMF_ERR_INVALID, all before any launch: a `*_DIAGVAR`, basic or trial context, a label mask,
+ * nranks > 1, a bad col_off, a fit_bag entry outside 0..nbags-1, nfits < 1, niter < 1, H0 outside 1..H, a required pointer NULL, a
+ * 1-column bag in the diagonal form under VBMF_COMPAT_SPARSE_REPEAT (repeat(v, inner = M-1) needs M >= 2). */
+int vbmf_sparse_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                            int64_t niter, double eps, int full_cov, int est_cb, int est_priors, int64_t H0,
+                            const double* gamma, const double* delta0, const double* eta, const double* zeta0,
+                            double* priors4, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA,
+                            double* delta, double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
+                            int64_t* iters_done, double* d_last, int64_t* status, double* trace);
+int vbmf_sparse_step(vbmf_ctx* ctx, int which);           /* reference order A, B, CA, CB, SIGMA (:369-376) */
 /* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0) */
 int vbmf_sparse_run(vbmf_ctx* ctx, int64_t niter, double eps, int est_cb, int64_t* iters_done, double* d_last,
                     double* trace);

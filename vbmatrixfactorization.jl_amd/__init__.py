@@ -46,7 +46,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "dual_updateB_", "dual_updateCA_", "dual_updateCB_", "dual_updateSigma_", "dual_updateCA_and_priors_",
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
-           "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags",
+           "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags", "vbmf_sparse_batch_", "vbmf_dual_batch_", "fit_restarts",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
@@ -1121,7 +1121,8 @@ class SparseBags:
     def __init__(self, Ys, H, **ctx_kw):
         self.L, self.Ms, self.col_off, Yall = _side_by_side(Ys, H, _sbatch_refuse)
         self.H, self.M = int(H), Yall.shape[1]
-        self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **{**_defaults, **ctx_kw})
+        self.ctx_kw = {**_defaults, **ctx_kw}
+        self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **self.ctx_kw)
         self.ctx.set_Y(Yall)
 
     def __len__(self):
@@ -1220,6 +1221,150 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
         p.YHat = _host_YHat(p)                                          # :201
         out.append(p.AHat)
     return out
+
+
+# =================================================================================================
+# Many fits in one device call -- the restart loops of examples/mil_util.jl:124-145 (train, solver "sparse") and :347-379
+# (train_dual), and the folds x classes validate_dataset wraps around them (:670-788)
+# =================================================================================================
+_FIT_MAX_H = 32
+
+
+def _fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of):
+    def refuse(why):
+        raise ValueError(f"{fn}: {why}; run such fits one at a time with {one}")
+    params = list(params)
+    if not params:
+        refuse("no parameter sets")
+    H = int(params[0].H)
+    if H > _FIT_MAX_H:
+        refuse(f"H = {H} > {_FIT_MAX_H}")
+    if int(niter) < 1:
+        refuse(f"niter = {niter} < 1")
+    if isinstance(Ys, SparseBags):
+        bags = Ys
+        if bags.H != H:
+            refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
+        L, Ms, ctx_kw = bags.L, bags.Ms, bags.ctx_kw
+    else:
+        bags = None
+        (L, Ms), ctx_kw = _batch_shapes(Ys, H, refuse), _defaults
+    if bag_of is None:
+        if len(params) != len(Ms):
+            refuse(f"{len(Ms)} bags but {len(params)} parameter sets and no bag_of")
+        bag_of = range(len(Ms))
+    bag_of = [int(b) for b in bag_of]
+    if len(bag_of) != len(params):
+        refuse(f"{len(params)} parameter sets but {len(bag_of)} entries in bag_of")
+    m = _MODELS[kind]
+    repeat = bool(ctx_kw.get("reference_compat", capi.VBMF_COMPAT_DEFAULT) & capi.VBMF_COMPAT_SPARSE_REPEAT)
+    for f, (p, b) in enumerate(zip(params, bag_of)):
+        if type(p) is not kind:
+            refuse(f"fit {f}: {type(p).__name__} ({kind.__name__} only, one model type per call)")
+        if not 0 <= b < len(Ms):
+            refuse(f"fit {f}: bag_of = {b} outside 0..{len(Ms) - 1}")
+        if int(p.H) != H:
+            refuse(f"fit {f}: H = {p.H} beside H = {H}")
+        if (p.L, p.M) != (L, Ms[b]):
+            refuse(f"fit {f}: bag {b} is {L} x {Ms[b]}, its parameters describe {(p.L, p.M)}")
+        if m.labels and (int(p.H1) > 0 or np.asarray(p.labels).size > 0):
+            refuse(f"fit {f} has labels / H1 > 0 (a label mask)")
+        if not m.labels and (int(p.H0) != int(params[0].H0) or not 1 <= int(p.H0) <= H):
+            refuse(f"fit {f}: H0 = {p.H0} (one H0 in 1..H per call)")
+        if np.shape(p.BHat) != (L, H) or np.shape(p.SigmaB) != (H, H) or np.size(p.CB) != H or np.size(p.CA) != Ms[b] * H:
+            refuse(f"fit {f}: BHat, SigmaB, CB or CA does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
+        if not full_cov and repeat and Ms[b] < 2:
+            refuse(f"fit {f} works on a 1-column bag: the diagonal form under the repeat layout needs M >= 2")
+        _check_derived(p)
+        if _alpha_not_derived(m, p):
+            refuse(f"fit {f}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
+    own = bags is None
+    if own:
+        bags = SparseBags(Ys, H)
+    (a0, b0, _), (a1, b1, _) = m.groups[0], m.groups[-1]
+    try:
+        r = bags.ctx.sparse_fit_batched(
+            bags.col_off, bag_of, int(niter), float(eps), [p.gamma0 + p.L / 2 for p in params], [p.delta0 for p in params],
+            [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
+            [[getattr(p, a0), getattr(p, b0), getattr(p, a1), getattr(p, b1)] for p in params],
+            np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]), np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]),
+            np.stack([np.asarray(p.CB, dtype=np.float64).reshape(H) for p in params]), [p.sigmaHat for p in params],
+            np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]),
+            H0=H if m.labels else int(params[0].H0), full_cov=full_cov, est_cb=est_cb, est_priors=est_priors and not m.labels)
+    finally:
+        if own:
+            bags.close()
+    s0 = 0
+    for f, p in enumerate(params):
+        s1 = s0 + p.M * H
+        p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
+        p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
+        s0 = s1
+        p.AHat = p.ATVecHat.reshape(p.M, H).copy()
+        p.SigmaA = r["SigmaA"][f].copy()
+        p.BHat, p.SigmaB, p.CB = np.array(r["BHat"][f], order="F"), r["SigmaB"][f].copy(), r["CB"][f].copy()
+        if est_cb:
+            p.delta = r["delta"][f].copy()
+        p.sigmaHat, p.zeta = float(r["sigmaHat"][f]), float(r["zeta"][f])
+        p.iters, p.status = int(r["iters"][f]), int(r["status"][f])
+        if m.views is not None:
+            m.views(p)
+            # the posterior shapes as the last updateCA! left them (src/vbmf_dual.jl:324-325): the hyper-prior that sweep STARTED
+            # from + 1/2, which est_priors has since refitted -- recovered as CA * beta of the group's first entry
+            # (a fit that stopped on a non-finite value, status 1, keeps the shapes of its start values)
+            ok = est_priors and p.iters > 0 and p.status == 0
+            p.alpha0 = float(p.CA0[0] * p.beta0[0]) if ok else p.alpha00 + 0.5
+            p.alpha1 = float(p.CA1[0] * p.beta1[0]) if ok and p.CA1.size else p.alpha01 + 0.5
+            p.alpha00, p.beta00, p.alpha01, p.beta01 = (float(v) for v in r["priors4"][f])
+            p.alpha = _posterior_shapes(p, m)
+        p.YHat = _host_YHat(p)
+    return [float(v) for v in r["d"]]
+
+
+def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None):
+    """vbmf_sparse! for many independent fits in one device call: does what [vbmf_sparse_(Ys[bag_of[f]], p, niter, eps=eps, ...) for
+    f, p in enumerate(params)] does (the restart loop of examples/mil_util.jl:124-145) -- fills on every p the fields vbmf_sparse_
+    fills, plus p.iters (sweeps run) and p.status (1: the fit met a non-finite precision or a bad pivot and stopped), and returns the
+    list of d.  Ys: a list of L x M_b arrays or a SparseBags; params: one vbmf_sparse_parameters per fit, one H <= 32, no labels;
+    bag_of[f]: the fit's bag (default: fit f on bag f), so restarts share one upload.  Every fit's whole loop runs in one workgroup of
+    one launch (include/vbmf_hip.h, vbmf_sparse_fit_batched)."""
+    return _fit_batch("vbmf_sparse_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb, False, bag_of)
+
+
+def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True):
+    """vbmf_dual! for many independent fits in one device call (the restart loop of examples/mil_util.jl:347-379): see
+    vbmf_sparse_batch_; params: one vbmf_dual_parameters per fit, all with one H0."""
+    return _fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of)
+
+
+def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, full_cov=None, diag_var=False, rng=None):
+    """The restart loops of examples/mil_util.jl:124-134 (model="sparse": eps = 1e-6, full_cov = false) and :347-354 (model="dual":
+    eps = 1e-4, full_cov = true) with all nstarts initialisations drawn in order and run in ONE device call.  Returns the parameter set
+    the reference's loop would have returned: sparse -- the first with d <= 2 eps and not NaN, else the last; dual -- the first with
+    norm(AHat) + norm(BHat) >= 1e-2, else the last.  All nstarts fits run, also when the first would have been accepted: the launch
+    costs what its slowest fit costs, and the starts behind the accepted one are discarded."""
+    if model not in ("sparse", "dual"):
+        raise ValueError(f"fit_restarts: model = {model!r} ('sparse' or 'dual')")
+    if diag_var:
+        raise ValueError("fit_restarts: diag_var=True is not batched; run the restarts one at a time with vbmf_sparse_ / vbmf_dual_")
+    if int(nstarts) < 1:
+        raise ValueError("fit_restarts: nstarts must be >= 1")
+    rng = np.random.default_rng() if rng is None else rng
+    if model == "sparse":
+        eps = 1e-6 if eps is None else eps
+        ps = [vbmf_sparse_init(Y, H, rng=rng) for _ in range(int(nstarts))]
+        ds = vbmf_sparse_batch_([Y], ps, niter, eps=eps, full_cov=bool(full_cov), bag_of=[0] * len(ps))
+        for p, d in zip(ps, ds):
+            if d <= 2 * eps:                                             # (false for NaN, which :130-132 turns into a restart)
+                return p
+        return ps[-1]
+    eps = 1e-4 if eps is None else eps
+    ps = [vbmf_dual_init(Y, H, H if H0 is None else H0, rng=rng) for _ in range(int(nstarts))]
+    vbmf_dual_batch_([Y], ps, niter, eps=eps, full_cov=True if full_cov is None else bool(full_cov), bag_of=[0] * len(ps))
+    for p in ps:
+        if not (np.linalg.norm(p.AHat, 2) + np.linalg.norm(p.BHat, 2) < 1e-2):   # Julia 0.5 norm(::Matrix): the operator 2-norm
+            return p
+    return ps[-1]
 
 
 def copy_vbmf_params(Y, old_params, rng=None):

@@ -33,7 +33,7 @@ SYMBOLS = [
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
-    "vbmf_sparse_run_fixed_basis_batched",
+    "vbmf_sparse_run_fixed_basis_batched", "vbmf_sparse_fit_batched",
     "vbmf_sparse_lower_bound", "vbmf_sparse_set_noise_rows", "vbmf_sparse_get_noise_rows", "vbmf_preprocess_open", "vbmf_preprocess_rows", "vbmf_set_Y_preprocessed",
     "vbmf_preprocess_close", "vbmf_dual_set_priors", "vbmf_dual_get_priors", "vbmf_dual_run",
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
@@ -112,6 +112,8 @@ def lib():
     L.vbmf_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, dp, dp, dp, dp, i64]
     L.vbmf_sparse_run_fixed_basis.argtypes = [vp, i64]
     L.vbmf_sparse_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]
+    L.vbmf_sparse_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64] + [dp] * 16
+                                          + [C.POINTER(i64), dp, C.POINTER(i64), dp])
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
     L.vbmf_elbo.argtypes = [vp, dp]
     L.vbmf_comm_unique_id.argtypes = [vp]
@@ -362,6 +364,44 @@ class Context:
                                                                 _dptr(sg), _dptr(ca), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA),
                                                                 _dptr(A)))
         return dict(sigmaHat=sg, zeta=zeta, CA=ca, beta=beta, diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA)
+
+    def sparse_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors4, BHat, SigmaB, CB, sigmaHat, CA,
+                           H0=None, full_cov=False, est_cb=True, est_priors=False, want_trace=False):
+        """Many independent vbmf_sparse! / vbmf_dual! fits in one launch (vbmf_sparse_fit_batched): fit f works on bag fit_bag[f] of the
+        bags side by side in this context's Y (bag b = columns col_off[b] .. col_off[b+1]-1).  Per fit: gamma, delta0, eta, zeta0,
+        sigmaHat (nfits,), priors4 (nfits, 4) = alpha00, beta00, alpha01, beta01 (the sparse model: its pair twice, H0 = H), the start
+        values BHat (nfits, L, H), SigmaB (nfits, H, H), CB (nfits, H) and CA: the fits' vec(A')-ordered vectors concatenated.
+        Returns dict(BHat, SigmaB, CB, delta (None unless est_cb), sigmaHat, zeta, priors4, CA, beta, diagSigmaATVec, ATVecHat, SigmaA,
+        iters, d, status, trace (nfits, niter, 2) or None).  Neither the context's state nor its Y is changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
+        nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
+        vec = lambda v: np.array(v, dtype=np.float64, copy=True).reshape(-1)
+        ga, d0, et, z0, sg, ca = vec(gamma), vec(delta0), vec(eta), vec(zeta0), vec(sigmaHat), vec(CA)
+        pri = np.array(priors4, dtype=np.float64, copy=True, order="C")
+        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, L, H).transpose(0, 2, 1))   # per fit column-major
+        SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
+        cb = np.array(CB, dtype=np.float64, copy=True, order="C")
+        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
+            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
+        MH = int(np.sum(off[fb + 1] - off[fb])) * H
+        if (any(v.shape != (nf,) for v in (ga, d0, et, z0, sg)) or pri.shape != (nf, 4) or SB.shape != (nf, H, H) or cb.shape != (nf, H)
+                or ca.shape != (MH,)):
+            raise ValueError(f"{nf} fits: gamma, delta0, eta, zeta0, sigmaHat must be ({nf},), priors4 ({nf}, 4), SigmaB ({nf}, {H}, {H}), "
+                             f"CB ({nf}, {H}) and CA ({MH},)")
+        delta = np.empty((nf, H)) if est_cb else None
+        zeta, beta, dS, A = np.empty(nf), np.empty(MH), np.empty(MH), np.empty(MH)
+        SA = np.empty((nf, H, H))
+        iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
+        tr = np.zeros((nf, int(niter), 2)) if want_trace else None
+        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._chk(self._lib.vbmf_sparse_fit_batched(
+            self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
+            int(H if H0 is None else H0), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0), _dptr(pri), _dptr(B), _dptr(SB), _dptr(cb),
+            _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA), _dptr(A), p64(iters), _dptr(dl),
+            p64(st), _dptr(tr)))
+        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, priors4=pri, CA=ca, beta=beta,
+                    diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA, iters=iters, d=dl, status=st, trace=tr)
 
     def YHat(self):
         out = np.empty((self.L, self.M), order="F")

@@ -411,3 +411,129 @@ int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* c
 }
 
 }  // extern "C"
+
+// ---- many fits in one launch (fit_batch_kernels.hpp) ------------------------------------------------------------------------------
+extern "C" {
+
+// The restart loops of examples/mil_util.jl:124-145,347-379 (and the folds x classes around them) in one call: every fit's whole
+// vbmf_sparse! / vbmf_dual! loop in one workgroup of one launch.  The context supplies Y only; its state is neither read nor changed,
+// so no RunFrame: that frame settles the context's own B buffers and counters, which this call leaves alone.
+int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
+                            double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const double* gamma, const double* delta0,
+                            const double* eta, const double* zeta0, double* priors4, double* BHat, double* SigmaB, double* CB,
+                            double* sigmaHat, double* CA, double* delta, double* zeta, double* beta, double* diagSigmaATVec,
+                            double* SigmaA, double* ATVecHat, int64_t* iters_done, double* d_last, int64_t* status, double* trace) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_fit_batched";
+    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse and two-group models only)", fn);
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run / vbmf_dual_run per fit)", fn);
+    if (c->trial) FAIL(c, VBMF_ERR_INVALID, "%s: trial context (the sparse and two-group models only)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run per fit)", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (H0 < 1 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: H0 = %lld outside 1..H = %lld", fn, (long long)H0, (long long)c->H);
+    if (!fit_bag || !gamma || !delta0 || !eta || !zeta0 || !priors4 || !BHat || !SigmaB || !CB || !sigmaHat || !CA || !iters_done ||
+        !d_last || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat and trace may be NULL)", fn);
+    const bool compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
+    const int H = (int)c->H, NBK = nb_tier(H);
+    const int64_t L = c->L, nf = nfits, nb = nbags, h2 = (int64_t)H * H, LH = L * H;
+    std::vector<long long> idx((size_t)(nb + 1 + nf + nf + 1));               // col_off | fit_bag | fit_off
+    long long* fit_off = idx.data() + nb + 1 + nf;
+    fit_off[0] = 0;
+    size_t lds_doubles = 0;
+    for (int64_t f = 0; f < nf; ++f) {
+        const int64_t b = fit_bag[f];
+        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: fit_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)f, (long long)b);
+        const int64_t Mb = col_off[b + 1] - col_off[b];
+        if (!full_cov && compat && Mb < 2)
+            FAIL(c, VBMF_ERR_INVALID, "%s: fit %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)f);
+        fit_off[f + 1] = fit_off[f] + Mb;
+        lds_doubles = std::max(lds_doubles, (size_t)fitb_lds_doubles(full_cov != 0, NBK, L, Mb, H));
+        idx[(size_t)(nb + 1 + f)] = b;
+    }
+    for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
+    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
+    // the staging vectors outlive every copy: an error between the first asynchronous copy and the synchronise drains the stream below
+    std::vector<double> in, out, sg;
+    auto run = [&]() -> int {
+    HIPCHK(c, hipSetDevice(c->o.device));
+    const int64_t SMH = fit_off[nf] * H, nidx = (int64_t)idx.size(), ntr = trace ? 2 * nf * niter : 0, ny = (L * c->M + 1) / 2;
+    // c->bags: [col_off | fit_bag | fit_off (int64) | gamma | delta0 | eta | zeta0 | sigma (nf each) | priors4 4 nf | zeta | d_last | iters
+    //           | status (int64) (nf each) | B | Bw | Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | CB | delta (nf H) | CA | A | dS |
+    //           beta (sum M_b H each) | trace | Yr | Yc (L M floats each)]
+    const int64_t o_sc = nidx, o_pri = o_sc + 5 * nf, o_zeta = o_pri + 4 * nf, o_dl = o_zeta + nf, o_it = o_dl + nf, o_st = o_it + nf,
+                  o_b = o_st + nf, o_bw = o_b + nf * LH, o_qw = o_bw + nf * LH, o_sb = o_qw + nf * LH, o_sa = o_sb + nf * h2,
+                  o_cb = o_sa + nf * h2, o_de = o_cb + nf * H, o_ca = o_de + nf * H, o_a = o_ca + SMH, o_ds = o_a + SMH, o_be = o_ds + SMH,
+                  o_tr = o_be + SMH, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    in.resize((size_t)(9 * nf));
+    memcpy(in.data(), gamma, (size_t)nf * 8);
+    memcpy(in.data() + nf, delta0, (size_t)nf * 8);
+    memcpy(in.data() + 2 * nf, eta, (size_t)nf * 8);
+    memcpy(in.data() + 3 * nf, zeta0, (size_t)nf * 8);
+    memcpy(in.data() + 4 * nf, sigmaHat, (size_t)nf * 8);
+    memcpy(in.data() + 5 * nf, priors4, (size_t)nf * 4 * 8);
+    HIPCHK(c, hipMemcpyAsync(d, idx.data(), (size_t)nidx * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_sc, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_b, BHat, (size_t)(nf * LH) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_sb, SigmaB, (size_t)(nf * h2) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_cb, CB, (size_t)(nf * H) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)SMH * 8, hipMemcpyHostToDevice, c->stream));
+    if (ntr) HIPCHK(c, hipMemsetAsync(d + o_tr, 0, (size_t)ntr * 8, c->stream));
+    float* Yr = reinterpret_cast<float*>(d + o_yr);
+    float* Yc = reinterpret_cast<float*>(d + o_yc);
+    DISPATCH_YMODE(c->mode, {
+        hipLaunchKernelGGL((fit_stage_kernel<YMODEc>), dim3(grid_for(L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
+                           (long long)L, (long long)c->M, Yr, Yc);
+    });
+    HIPCHK(c, hipGetLastError());
+    long long* di = reinterpret_cast<long long*>(d);
+    FitArgs a{Yr, Yc, (long long)L, (long long)c->M, di, di + nb + 1, di + nb + 1 + nf, H, (int)H0, (int)niter, compat ? 1 : 0,
+              (c->o.reference_compat & VBMF_COMPAT_SPECTRAL_DELTA) ? 1 : 0, est_cb ? 1 : 0, est_priors ? 1 : 0, eps,
+              d + o_sc, d + o_sc + nf, d + o_sc + 2 * nf, d + o_sc + 3 * nf, d + o_pri,
+              d + o_b, d + o_sb, d + o_cb, d + o_sc + 4 * nf, d + o_ca,
+              d + o_de, d + o_zeta, d + o_be, d + o_ds, d + o_sa, d + o_a, d + o_bw, d + o_qw,
+              reinterpret_cast<long long*>(d + o_it), d + o_dl, reinterpret_cast<long long*>(d + o_st), trace ? d + o_tr : nullptr};
+    const size_t lds = lds_doubles * 8;
+#define FITB(FULLc_)                                                                                                               \
+    DISPATCH_NB(NBK, {                                                                                                             \
+        hipLaunchKernelGGL((fit_batch_kernel<(NBc > 2 ? 2 : NBc), FULLc_>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a); \
+    })
+    if (full_cov) { FITB(true); } else { FITB(false); }
+#undef FITB
+    HIPCHK(c, hipGetLastError());
+    // read-back: [priors4 | zeta | d_last | iters | status] is one block; the per-fit matrices and the M H-long fields one block each
+    out.resize((size_t)(o_b - o_pri));
+    sg.resize((size_t)nf);
+    HIPCHK(c, hipMemcpyAsync(out.data(), d + o_pri, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sg.data(), d + o_sc + 4 * nf, (size_t)nf * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(BHat, d + o_b, (size_t)(nf * LH) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(SigmaB, d + o_sb, (size_t)(nf * h2) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(CB, d + o_cb, (size_t)(nf * H) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(CA, d + o_ca, (size_t)SMH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (delta && est_cb) HIPCHK(c, hipMemcpyAsync(delta, d + o_de, (size_t)(nf * H) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (SigmaA) HIPCHK(c, hipMemcpyAsync(SigmaA, d + o_sa, (size_t)(nf * h2) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ATVecHat) HIPCHK(c, hipMemcpyAsync(ATVecHat, d + o_a, (size_t)SMH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (diagSigmaATVec) HIPCHK(c, hipMemcpyAsync(diagSigmaATVec, d + o_ds, (size_t)SMH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (beta) HIPCHK(c, hipMemcpyAsync(beta, d + o_be, (size_t)SMH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (trace) HIPCHK(c, hipMemcpyAsync(trace, d + o_tr, (size_t)ntr * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(priors4, out.data(), (size_t)nf * 4 * 8);
+    if (zeta) memcpy(zeta, out.data() + (o_zeta - o_pri), (size_t)nf * 8);
+    memcpy(d_last, out.data() + (o_dl - o_pri), (size_t)nf * 8);
+    memcpy(iters_done, out.data() + (o_it - o_pri), (size_t)nf * 8);
+    memcpy(status, out.data() + (o_st - o_pri), (size_t)nf * 8);
+    memcpy(sigmaHat, sg.data(), (size_t)nf * 8);
+    return VBMF_OK;
+    };
+    const int rc = run();
+    if (rc != VBMF_OK) hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+}  // extern "C"

@@ -47,6 +47,7 @@
 #include "prep_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "sparse_batch_kernels.hpp"
+#include "fit_batch_kernels.hpp"
 #include "score_kernels.hpp"
 #include "gram_kernels.hpp"
 
@@ -1646,6 +1647,11 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_batch_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
         // batched vbls! of the sparse models, full_cov at 32 < H <= 64: four 64 x 66 fp64 images and the bag's state
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_batch_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SBATCH_LDS_BIG);
+        // many fits in one launch: the images, the H x H matrices and a fit's state (fit_batch_kernels.hpp)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess && c->NH == 4)
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
         if (e == hipSuccess && c->NH == 4)

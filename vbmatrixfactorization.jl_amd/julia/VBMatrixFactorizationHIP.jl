@@ -11,7 +11,7 @@
 module VBMatrixFactorizationHIP
 
 export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, updateCB!, updateSigma2!, updateYHat!,
-       vbls!, vbls_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
+       vbls!, vbls_batch!, vbmf_sparse_batch!, vbmf_dual_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
@@ -618,6 +618,104 @@ function vbls_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameter
         p.A0Hat, p.A1Hat = p.AHat[:, 1:p.H0], p.AHat[:, p.H0+1:end]
         p.CA0, p.CA1 = dual_split(p.CA, p.M, p.H, p.H0); p.beta0, p.beta1 = dual_split(p.beta, p.M, p.H, p.H0)
         p.alpha0, p.alpha1 = p.alpha00 + 0.5, p.alpha01 + 0.5                                 # src/vbmf_dual.jl:324-325
+        p.alpha = [p.alpha0, p.alpha1]
+    end
+    return out
+end
+
+# ---- many fits in ONE device call: the restart loops of examples/mil_util.jl:124-145 (train) and :347-379 (train_dual) -------------
+# Fit f works on bag bag_of[f] (1-based), so restarts share one upload; every fit's whole `while i <= niter && d > eps` loop runs in
+# one workgroup of one launch (vbmf_sparse_fit_batched).  pri: 4 x nfits = alpha00, beta00, alpha01, beta01 per fit.
+function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int, eps::Float64, full_cov::Bool, est_cb::Bool,
+                        est_priors::Bool, H0::Int, pri::Matrix{Float64}, bag_of::Vector{Int}, variant::Int)
+    nb, nf = length(Ys), length(ps)
+    (nb >= 1 && nf >= 1 && length(bag_of) == nf) || error("$fn: one bag_of entry per parameter set")
+    niter >= 1 || error("$fn: niter must be >= 1")
+    H, L = ps[1].H, size(Ys[1], 1)
+    H <= 32 || error("$fn: H = $H > 32; run such fits one at a time")
+    all(size(Y, 1) == L && size(Y, 2) >= 1 for Y in Ys) || error("$fn: the bags have different L; run such fits one at a time")
+    for (f, p) in enumerate(ps)
+        1 <= bag_of[f] <= nb || error("$fn: bag_of[$f] = $(bag_of[f]) outside 1..$nb")
+        (p.L, p.M, p.H) == (L, size(Ys[bag_of[f]], 2), H) || error("$fn: fit $f does not match its bag")
+        (full_cov || p.M >= 2) || error("$fn: fit $f works on a 1-column bag: the diagonal form needs M >= 2")
+    end
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    M = off[end]
+    Yall = reduce(hcat, Ys)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, Int32(variant), 0xffffffff, 1, 0, 0, 0, 0, 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
+    fb = Int64[b - 1 for b in bag_of]
+    ga = Float64[p.gamma0 + p.L / 2 for p in ps]; d0 = Float64[p.delta0 for p in ps]
+    eta = Float64[p.eta0 + p.L * p.M / 2 for p in ps]; z0 = Float64[p.zeta0 for p in ps]
+    B = reduce(vcat, [vec(Matrix{Float64}(p.BHat)) for p in ps]); SB = reduce(vcat, [vec(Matrix{Float64}(p.SigmaB)) for p in ps])
+    cb = reduce(vcat, [Vector{Float64}(p.CB) for p in ps]); sg = Float64[p.sigmaHat for p in ps]
+    ca = reduce(vcat, [Vector{Float64}(p.CA) for p in ps])
+    n = length(ca)
+    dl = Array{Float64}(undef, nf * H); ze = Array{Float64}(undef, nf); be = Array{Float64}(undef, n); ds = similar(be); a = similar(be)
+    SA = Array{Float64}(undef, H, H, nf)
+    it = zeros(Int64, nf); dlast = Array{Float64}(undef, nf); st = zeros(Int64, nf)
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        chk(h[], ccall((:vbmf_sparse_fit_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64},
+             Ptr{Float64}),
+            h[], nb, off, nf, fb, niter, eps, full_cov, est_cb, est_priors, H0, ga, d0, eta, z0, pri, B, SB, cb, sg, ca, dl, ze, be, ds,
+            SA, a, it, dlast, st, C_NULL))
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+    s = 0
+    for (f, p) in enumerate(ps)
+        r = s+1:s+p.M*H
+        s += p.M * H
+        p.ATVecHat, p.diagSigmaATVec, p.CA, p.beta = a[r], ds[r], ca[r], be[r]
+        p.AHat = permutedims(reshape(p.ATVecHat, H, p.M))
+        p.SigmaA = SA[:, :, f]
+        p.BHat = reshape(B[(f-1)*L*H+1:f*L*H], L, H)
+        p.SigmaB = reshape(SB[(f-1)*H*H+1:f*H*H], H, H)
+        p.CB = cb[(f-1)*H+1:f*H]
+        est_cb && (p.delta = dl[(f-1)*H+1:f*H])
+        p.sigmaHat, p.zeta = sg[f], ze[f]
+        p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')
+    end
+    return dlast, it, st
+end
+
+"""
+vbmf_sparse! for many independent fits in ONE device call (the restart loop of examples/mil_util.jl:124-145): does what
+`[vbmf_sparse!(Ys[bag_of[f]], ps[f], niter; eps = eps, full_cov = full_cov) for f in 1:length(ps)]` does and returns
+(d, sweeps run, status) per fit; status 1 = the fit met a non-finite precision or a bad pivot and stopped.  No labels, H <= 32.
+"""
+function vbmf_sparse_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; eps::Float64 = 1e-6,
+                            full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)))
+    for (f, p) in enumerate(ps)
+        (p.H1 == 0 && isempty(p.labels)) || error("vbmf_sparse_batch!: fit $f has labels; use vbmf_sparse! per fit")
+    end
+    pri = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0)[k] for k in 1:4, p in ps]
+    return fit_batch_run!("vbmf_sparse_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri, bag_of, 1)
+end
+
+"""
+vbmf_dual! for many independent fits in ONE device call (the restart loop of examples/mil_util.jl:347-379): see vbmf_sparse_batch!;
+all fits share one H0; est_priors refits (alpha00, beta00, alpha01, beta01) every sweep (src/vbmf_dual.jl:393-434).
+"""
+function vbmf_dual_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameters}, niter::Int; eps::Float64 = 1e-6,
+                          full_cov::Bool = false, est_cb::Bool = true, est_priors::Bool = true,
+                          bag_of::Vector{Int} = collect(1:length(ps)))
+    H0 = ps[1].H0
+    all(p.H0 == H0 for p in ps) || error("vbmf_dual_batch!: one H0 per call")
+    pri = Float64[(p.alpha00, p.beta00, p.alpha01, p.beta01)[k] for k in 1:4, p in ps]
+    out = fit_batch_run!("vbmf_dual_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri, bag_of, 3)
+    for (f, p) in enumerate(ps)
+        p.A0Hat, p.A1Hat = p.AHat[:, 1:p.H0], p.AHat[:, p.H0+1:end]
+        p.CA0, p.CA1 = dual_split(p.CA, p.M, p.H, p.H0); p.beta0, p.beta1 = dual_split(p.beta, p.M, p.H, p.H0)
+        # the posterior shapes as the last updateCA! left them (src/vbmf_dual.jl:324-325): the hyper-prior that sweep started from + 1/2
+        p.alpha0 = est_priors && out[2][f] > 0 ? p.CA0[1] * p.beta0[1] : p.alpha00 + 0.5
+        p.alpha1 = est_priors && out[2][f] > 0 && !isempty(p.CA1) ? p.CA1[1] * p.beta1[1] : p.alpha01 + 0.5
+        p.alpha00, p.beta00, p.alpha01, p.beta01 = pri[1, f], pri[2, f], pri[3, f], pri[4, f]
         p.alpha = [p.alpha0, p.alpha1]
     end
     return out
