@@ -135,6 +135,27 @@ int vbmf_run_fixed_basis(vbmf_ctx* ctx, int64_t niter);
 int vbmf_run_fixed_basis_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t niter,
                                  double* sigma2, double* CA_diag, double* SigmaA, double* AHat, int64_t ldA);
 
+/* vbmf_fit_batched: many independent vbmf! fits of the basic model (A and B both move) in ONE launch, one workgroup per fit with the
+ * whole `while i <= niter && d > eps` loop of src/vbmf.jl:175-231 inside it -- the two basic-model fits of examples/mil_util.jl:110-114
+ * and the folds x p x repetitions around them in one call.  The context is VBMF_VARIANT_BASIC and supplies only Y, bags side by side
+ * (bag b = columns col_off[b] .. col_off[b+1]-1); its own state is neither read nor changed (none needs to be set).  Fit f works on bag
+ * fit_bag[f], so several fits may share a bag.  One rank, no label mask, H <= 32; a 1-column bag is valid.
+ *   est_covs / est_var: updateCA! + updateCB! / updateSigma2! after every sweep's updateA!, updateB!, as vbmf! takes them
+ *   in/out, per-fit blocks in fit order: BHat (L*H, column-major), SigmaB (H*H), CA, CB (H: the diagonals), sigma2 (1)
+ *   out (either may be NULL): AHat (M_b*H column-major per fit, concatenated by each fit's own M_b), SigmaA (H*H)
+ *   iters_done, d_last, status (nfits): the sweeps run, the last d, and 1 for a fit that met a non-finite sigma2, a CA_h or CB_h that
+ *       is not positive and finite, or a pivot that is not positive and finite in either inverse, and left its loop after that sweep
+ *       (0 otherwise).  Such fits do not fail the call.  trace (nfits*niter*2, may be NULL): (d, sigma2) per sweep run, zeros after.
+ * d = norm(B - B_old) / norm(B_old) with operator 2-norms under VBMF_COMPAT_SPECTRAL_DELTA (src/util.jl:27-29), Frobenius norms
+ * otherwise; the loop ends when !(d > eps), so a NaN d ends it as the reference's comparison does.  Everything is fp64 on Y as stored.
+ * VBMF_ERR_UNSUPPORTED: H > 32.  VBMF_ERR_INVALID, all before any launch: a non-basic context, a label mask, nranks > 1, a bad
+ * col_off, a fit_bag entry outside 0..nbags-1, nfits < 1, niter < 1, a required pointer NULL, no Y. */
+int vbmf_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                     int64_t niter, double eps, int est_covs, int est_var,
+                     double* BHat, double* SigmaB, double* CA, double* CB, double* sigma2,
+                     double* AHat, double* SigmaA,
+                     int64_t* iters_done, double* d_last, int64_t* status, double* trace);
+
 /* The vbmf! loop (src/vbmf.jl:187-214): while i <= niter && d > eps { A; B; [CA; CB]; [sigma2]; d }.
  * Runs entirely on the device; the stop test is evaluated device-side so the state freezes exactly
  * where the reference would stop.  iters_done = i-1 (src/vbmf.jl:221), d_last = last d.

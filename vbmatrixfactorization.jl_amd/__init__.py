@@ -47,6 +47,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
            "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags", "vbmf_sparse_batch_", "vbmf_dual_batch_", "fit_restarts",
+           "vbmf_batch_", "train_folds",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
@@ -1365,6 +1366,123 @@ def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, ful
         if not (np.linalg.norm(p.AHat, 2) + np.linalg.norm(p.BHat, 2) < 1e-2):   # Julia 0.5 norm(::Matrix): the operator 2-norm
             return p
     return ps[-1]
+
+
+def vbmf_batch_(Ys, params, niter, eps=1e-6, est_covs=False, est_var=False, bag_of=None):
+    """vbmf! for many independent fits of the basic model in one device call: does what [vbmf_(Ys[bag_of[f]], p, niter, eps=eps,
+    est_covs=est_covs, est_var=est_var) for f, p in enumerate(params)] does (the two fits of examples/mil_util.jl:110-114, and the
+    folds around them) -- fills on every p AHat, BHat, SigmaA, SigmaB (rebound), the diagonals of CA and CB (in place), invCA, invCB,
+    sigma2 and YHat (under YHAT_AUTO_LIMIT), plus p.iters (sweeps run), p.d (the last d) and p.status (1: the fit met a non-finite
+    sigma2, a CA / CB entry that is not positive, or a bad pivot, and stopped) -- and returns the list of params.  Ys: a list of
+    L x M_b arrays or a Bags; params: one vbmf_parameters per fit, one H <= 32, no labels; bag_of[f]: the fit's bag (default: fit f on
+    bag f).  Every fit's whole loop runs in fp64 in one workgroup of one launch (include/vbmf_hip.h, vbmf_fit_batched)."""
+    def refuse(why):
+        raise ValueError(f"vbmf_batch_: {why}; run such fits one at a time with vbmf_")
+    params = list(params)
+    if not params:
+        refuse("no parameter sets")
+    if type(params[0]) is not vbmf_parameters:
+        refuse(f"fit 0: {type(params[0]).__name__} (the basic model's vbmf_parameters only)")
+    H = int(params[0].H)
+    if H > _FIT_MAX_H:
+        refuse(f"H = {H} > {_FIT_MAX_H}")
+    if int(niter) < 1:
+        refuse(f"niter = {niter} < 1")
+    if isinstance(Ys, Bags):
+        bags = Ys
+        if bags.H != H:
+            refuse(f"the Bags were uploaded for H = {bags.H}, the parameters have H = {H}")
+        L, Ms = bags.L, bags.Ms
+    else:
+        bags = None
+        L, Ms = _batch_shapes(Ys, H, refuse)
+    if bag_of is None:
+        if len(params) != len(Ms):
+            refuse(f"{len(Ms)} bags but {len(params)} parameter sets and no bag_of")
+        bag_of = range(len(Ms))
+    bag_of = [int(b) for b in bag_of]
+    if len(bag_of) != len(params):
+        refuse(f"{len(params)} parameter sets but {len(bag_of)} entries in bag_of")
+    for f, (p, b) in enumerate(zip(params, bag_of)):
+        if type(p) is not vbmf_parameters:
+            refuse(f"fit {f}: {type(p).__name__} (the basic model's vbmf_parameters only)")
+        if not 0 <= b < len(Ms):
+            refuse(f"fit {f}: bag_of = {b} outside 0..{len(Ms) - 1}")
+        if int(p.H) != H:
+            refuse(f"fit {f}: H = {p.H} beside H = {H}")
+        if (p.L, p.M) != (L, Ms[b]):
+            refuse(f"fit {f}: bag {b} is {L} x {Ms[b]}, its parameters describe {(p.L, p.M)}")
+        if int(p.H1) > 0 or np.asarray(p.labels).size > 0:
+            refuse(f"fit {f} has labels / H1 > 0 (a label mask)")
+        if (np.shape(p.BHat) != (L, H) or np.shape(p.SigmaB) != (H, H) or np.shape(p.CA) != (H, H) or np.shape(p.CB) != (H, H)):
+            refuse(f"fit {f}: BHat, SigmaB, CA or CB does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
+    own = bags is None
+    if own:
+        bags = Bags(Ys, H)
+    try:
+        r = bags.session.ctx.fit_batched(
+            bags.col_off, bag_of, int(niter), float(eps), np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]),
+            np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]), np.stack([np.diag(p.CA) for p in params]),
+            np.stack([np.diag(p.CB) for p in params]), [p.sigma2 for p in params], est_covs=est_covs, est_var=est_var)
+    finally:
+        if own:
+            bags.close()
+    idx = np.arange(H)
+    for f, p in enumerate(params):
+        p.AHat = np.array(r["AHat"][f], order="F")                  # rebound, like updateA! / updateB! (src/vbmf.jl:96-98,110-112)
+        p.BHat = np.array(r["BHat"][f], order="F")
+        p.SigmaA, p.SigmaB = r["SigmaA"][f].copy(), r["SigmaB"][f].copy()
+        p.CA[idx, idx] = r["CA"][f]                                  # in place (src/vbmf.jl:131,143)
+        p.CB[idx, idx] = r["CB"][f]
+        p.invCA, p.invCB = np.diag(1.0 / r["CA"][f]), np.diag(1.0 / r["CB"][f])
+        p.sigma2 = float(r["sigma2"][f])
+        p.iters, p.d, p.status = int(r["iters"][f]), float(r["d"][f]), int(r["status"][f])
+        p.YHat = _host_YHat(p)                                       # :217
+    return params
+
+
+def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None):
+    """The reference's train (examples/mil_util.jl:93-152) over many (Y0, Y1) pairs -- the folds, p and repetitions of a validation
+    run -- with all the fits in ONE device call.  solver="basic": 2 x len(folds) fits through vbmf_batch_ with est_covs = est_var =
+    True (:110-114), vbmf_init drawn in the order (fold, class) from the one generator.  solver="sparse": ten vbmf_sparse_init per class
+    per fold, drawn in the order (fold, class, restart), one vbmf_sparse_batch_ call with full_cov=False, and per class the set the
+    restart loop of :124-145 keeps (fit_restarts): the first with d <= 2 eps and not NaN, else the last.  Returns a list of
+    (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns (:97-100)."""
+    if solver not in ("basic", "sparse"):
+        raise ValueError(f"train_folds: solver = {solver!r} ('basic' or 'sparse')")
+    if diag_var:
+        raise ValueError("train_folds: diag_var=True is not batched; train such folds one at a time with vbmf_sparse_ / vbmf_")
+    rng = np.random.default_rng() if rng is None else rng
+    nstarts = 1 if solver == "basic" else 10                        # max_restarts of :108
+    init = vbmf_init if solver == "basic" else vbmf_sparse_init
+    Ys, ps, bag_of, where = [], [], [], []
+    for k, pair in enumerate(folds):
+        if any(np.shape(Y)[1:] == (0,) for Y in pair):              # n0 == 0 || n1 == 0 (:97-100)
+            continue
+        for c, Y in enumerate(pair):
+            Ys.append(Y)
+            for _ in range(nstarts):
+                ps.append(init(Y, H, rng=rng))
+                bag_of.append(len(Ys) - 1)
+            where.append((k, c))
+    out = [(0, 0)] * len(folds)
+    if not ps:
+        return out
+    if solver == "basic":
+        vbmf_batch_(Ys, ps, niter, eps=eps, est_covs=True, est_var=True, bag_of=bag_of)
+        kept = ps
+    else:
+        ds = vbmf_sparse_batch_(Ys, ps, niter, eps=eps, full_cov=False, bag_of=bag_of)
+        kept = []
+        for b in range(len(Ys)):
+            sets = list(zip(ps[b * nstarts:(b + 1) * nstarts], ds[b * nstarts:(b + 1) * nstarts]))
+            kept.append(next((p for p, d in sets if d <= 2 * eps), sets[-1][0]))   # (d <= 2 eps is false for NaN: :130-132)
+    res = {}
+    for (k, c), p in zip(where, kept):
+        res[k, c] = p
+    for k in {k for k, _ in where}:
+        out[k] = (res[k, 0], res[k, 1])
+    return out
 
 
 def copy_vbmf_params(Y, old_params, rng=None):

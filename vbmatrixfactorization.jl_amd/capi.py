@@ -29,7 +29,7 @@ UNIQUE_ID_BYTES = 128
 SYMBOLS = [
     "vbmf_default_opts", "vbmf_create", "vbmf_destroy", "vbmf_last_error", "vbmf_set_Y", "vbmf_set_Y_synthetic",
     "vbmf_get_Y", "vbmf_get_trYY", "vbmf_set_state", "vbmf_get_state", "vbmf_step", "vbmf_run", "vbmf_run_fixed_basis",
-    "vbmf_run_fixed_basis_batched", "vbmf_get_YHat",
+    "vbmf_run_fixed_basis_batched", "vbmf_fit_batched", "vbmf_get_YHat",
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
@@ -110,6 +110,8 @@ def lib():
     L.vbmf_run.argtypes = [vp, i64, C.c_double, i32, i32, C.POINTER(i64), dp, dp]
     L.vbmf_run_fixed_basis.argtypes = [vp, i64]
     L.vbmf_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, dp, dp, dp, dp, i64]
+    L.vbmf_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32] + [dp] * 7
+                                   + [C.POINTER(i64), dp, C.POINTER(i64), dp])
     L.vbmf_sparse_run_fixed_basis.argtypes = [vp, i64]
     L.vbmf_sparse_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]
     L.vbmf_sparse_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64] + [dp] * 16
@@ -335,6 +337,38 @@ class Context:
         self._chk(self._lib.vbmf_run_fixed_basis_batched(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), int(niter), _dptr(s2),
                                                          _dptr(ca), _dptr(SA), _dptr(A), self.M))
         return dict(sigma2=s2, CA_diag=ca, SigmaA=SA, AHat=A)
+
+    def fit_batched(self, col_off, fit_bag, niter, eps, BHat, SigmaB, CA, CB, sigma2, est_covs=False, est_var=False, want_trace=False):
+        """Many independent vbmf! fits of the basic model in one launch (vbmf_fit_batched): fit f works on bag fit_bag[f] of the bags
+        side by side in this context's Y (bag b = columns col_off[b] .. col_off[b+1]-1).  Per fit the start values BHat (nfits, L, H),
+        SigmaB (nfits, H, H), the diagonals CA, CB (nfits, H) and sigma2 (nfits,).  Returns dict(BHat, SigmaB, CA, CB, sigma2, SigmaA
+        (nfits, H, H), AHat (a list of M_b x H arrays), iters, d, status, trace (nfits, niter, 2) or None).  Neither the context's state
+        nor its Y is changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
+        nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
+        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
+            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
+        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, L, H).transpose(0, 2, 1))   # per fit column-major
+        SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
+        ca = np.array(CA, dtype=np.float64, copy=True, order="C")
+        cb = np.array(CB, dtype=np.float64, copy=True, order="C")
+        s2 = np.array(sigma2, dtype=np.float64, copy=True).reshape(-1)
+        if SB.shape != (nf, H, H) or ca.shape != (nf, H) or cb.shape != (nf, H) or s2.shape != (nf,):
+            raise ValueError(f"{nf} fits: SigmaB must be ({nf}, {H}, {H}), CA and CB ({nf}, {H}) and sigma2 ({nf},)")
+        Ms = off[fb + 1] - off[fb]
+        A = np.empty(int(np.sum(Ms)) * H)
+        SA = np.empty((nf, H, H))
+        iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
+        tr = np.zeros((nf, int(niter), 2)) if want_trace else None
+        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._chk(self._lib.vbmf_fit_batched(
+            self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(est_covs)), int(bool(est_var)), _dptr(B), _dptr(SB),
+            _dptr(ca), _dptr(cb), _dptr(s2), _dptr(A), _dptr(SA), p64(iters), _dptr(dl), p64(st), _dptr(tr)))
+        ends = np.cumsum(Ms) * H
+        As = [A[e - m * H:e].reshape(H, m).T for e, m in zip(ends, Ms)]       # column-major M_b x H blocks
+        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CA=ca, CB=cb, sigma2=s2, SigmaA=SA, AHat=As, iters=iters, d=dl, status=st,
+                    trace=tr)
 
     def sparse_run_fixed_basis(self, niter):
         self._chk(self._lib.vbmf_sparse_run_fixed_basis(self._h, int(niter)))

@@ -1,5 +1,5 @@
-// host_bags.hpp -- the five many-bags entries of the C ABI (batched vbls! of the basic and the sparse models, per-bag residuals, least
-// squares and lower bounds) and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
+// host_bags.hpp -- the many-bags entries of the C ABI (batched vbls! of the basic and the sparse models, per-bag residuals, least
+// squares and lower bounds, many whole fits of the sparse and of the basic model) and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
 // helpers it uses, never on its own.  The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.
 //   bags_check     what every entry refuses about (nbags, col_off) and a sharded context; the widest bag, the residual slices
 //   bags_reserve   ONE device scratch buffer (c->bags), grown on demand.  Every entry synchronises before it returns, so no two layouts
@@ -529,6 +529,104 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
     memcpy(iters_done, out.data() + (o_it - o_pri), (size_t)nf * 8);
     memcpy(status, out.data() + (o_st - o_pri), (size_t)nf * 8);
     memcpy(sigmaHat, sg.data(), (size_t)nf * 8);
+    return VBMF_OK;
+    };
+    const int rc = run();
+    if (rc != VBMF_OK) hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- many basic-model fits in one launch (fit_basic_kernels.hpp) -------------------------------------------------------------------
+extern "C" {
+
+// The two vbmf! calls of examples/mil_util.jl:110-114 (and the folds x p x repetitions around them) in one call: every fit's whole
+// loop of src/vbmf.jl:175-231 in one workgroup of one launch.  The context supplies Y only; its state is neither read nor changed, so
+// no RunFrame (see vbmf_sparse_fit_batched).
+int vbmf_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter, double eps,
+                     int est_covs, int est_var, double* BHat, double* SigmaB, double* CA, double* CB, double* sigma2, double* AHat,
+                     double* SigmaA, int64_t* iters_done, double* d_last, int64_t* status, double* trace) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_fit_batched";
+    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
+    if (c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: sparse context (the basic model only; use vbmf_sparse_fit_batched)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_run per fit)", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (!fit_bag || !BHat || !SigmaB || !CA || !CB || !sigma2 || !iters_done || !d_last || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only AHat, SigmaA and trace may be NULL)", fn);
+    const int H = (int)c->H, NBK = nb_tier(H);
+    const int64_t L = c->L, nf = nfits, nb = nbags, h2 = (int64_t)H * H, LH = L * H;
+    std::vector<long long> idx((size_t)(nb + 1 + nf + nf + 1));               // col_off | fit_bag | fit_off
+    long long* fit_off = idx.data() + nb + 1 + nf;
+    fit_off[0] = 0;
+    size_t lds_doubles = 0;
+    for (int64_t f = 0; f < nf; ++f) {
+        const int64_t b = fit_bag[f];
+        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: fit_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)f, (long long)b);
+        const int64_t Mb = col_off[b + 1] - col_off[b];
+        fit_off[f + 1] = fit_off[f] + Mb;
+        lds_doubles = std::max(lds_doubles, (size_t)fitb_basic_lds_doubles(NBK, L, Mb, H));
+        idx[(size_t)(nb + 1 + f)] = b;
+    }
+    for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
+    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
+    // the staging vectors outlive every copy: an error between the first asynchronous copy and the synchronise drains the stream below
+    std::vector<double> in, out;
+    auto run = [&]() -> int {
+    HIPCHK(c, hipSetDevice(c->o.device));
+    const int64_t SMH = fit_off[nf] * H, nidx = (int64_t)idx.size(), ntr = trace ? 2 * nf * niter : 0, ny = (L * c->M + 1) / 2;
+    // c->bags: [col_off | fit_bag | fit_off (int64) | sigma2 nf | CA | CB (nf H each) | d_last | iters | status (int64) (nf each) | B | Bw |
+    //           Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | A | Aw (sum M_b H each) | trace | Yr | Yc (L M floats each)]
+    const int64_t o_s2 = nidx, o_ca = o_s2 + nf, o_cb = o_ca + nf * H, o_dl = o_cb + nf * H, o_it = o_dl + nf, o_st = o_it + nf,
+                  o_b = o_st + nf, o_bw = o_b + nf * LH, o_qw = o_bw + nf * LH, o_sb = o_qw + nf * LH, o_sa = o_sb + nf * h2,
+                  o_a = o_sa + nf * h2, o_aw = o_a + SMH, o_tr = o_aw + SMH, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
+    double* d = nullptr;
+    TRY(bags_reserve(c, total, &d));
+    in.resize((size_t)(o_dl - o_s2));
+    memcpy(in.data(), sigma2, (size_t)nf * 8);
+    memcpy(in.data() + (o_ca - o_s2), CA, (size_t)(nf * H) * 8);
+    memcpy(in.data() + (o_cb - o_s2), CB, (size_t)(nf * H) * 8);
+    HIPCHK(c, hipMemcpyAsync(d, idx.data(), (size_t)nidx * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_s2, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_b, BHat, (size_t)(nf * LH) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_sb, SigmaB, (size_t)(nf * h2) * 8, hipMemcpyHostToDevice, c->stream));
+    if (ntr) HIPCHK(c, hipMemsetAsync(d + o_tr, 0, (size_t)ntr * 8, c->stream));
+    float* Yr = reinterpret_cast<float*>(d + o_yr);
+    float* Yc = reinterpret_cast<float*>(d + o_yc);
+    DISPATCH_YMODE(c->mode, {
+        hipLaunchKernelGGL((fit_stage_kernel<YMODEc>), dim3(grid_for(L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
+                           (long long)L, (long long)c->M, Yr, Yc);
+    });
+    HIPCHK(c, hipGetLastError());
+    long long* di = reinterpret_cast<long long*>(d);
+    FitBasicArgs a{Yr, Yc, (long long)L, (long long)c->M, di, di + nb + 1, di + nb + 1 + nf, H, (int)niter,
+                   (c->o.reference_compat & VBMF_COMPAT_SPECTRAL_DELTA) ? 1 : 0, est_covs ? 1 : 0, est_var ? 1 : 0, eps,
+                   d + o_b, d + o_sb, d + o_ca, d + o_cb, d + o_s2, d + o_sa, d + o_a, d + o_bw, d + o_qw, d + o_aw,
+                   reinterpret_cast<long long*>(d + o_it), d + o_dl, reinterpret_cast<long long*>(d + o_st), trace ? d + o_tr : nullptr};
+    const size_t lds = lds_doubles * 8;
+    DISPATCH_NB(NBK, {
+        hipLaunchKernelGGL((fit_basic_kernel<(NBc > 2 ? 2 : NBc)>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
+    });
+    HIPCHK(c, hipGetLastError());
+    // read-back: [sigma2 | CA | CB | d_last | iters | status] is one block; the per-fit matrices one block each
+    out.resize((size_t)(o_b - o_s2));
+    HIPCHK(c, hipMemcpyAsync(out.data(), d + o_s2, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(BHat, d + o_b, (size_t)(nf * LH) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(SigmaB, d + o_sb, (size_t)(nf * h2) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (SigmaA) HIPCHK(c, hipMemcpyAsync(SigmaA, d + o_sa, (size_t)(nf * h2) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (AHat) HIPCHK(c, hipMemcpyAsync(AHat, d + o_a, (size_t)SMH * 8, hipMemcpyDeviceToHost, c->stream));
+    if (trace) HIPCHK(c, hipMemcpyAsync(trace, d + o_tr, (size_t)ntr * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(sigma2, out.data(), (size_t)nf * 8);
+    memcpy(CA, out.data() + (o_ca - o_s2), (size_t)(nf * H) * 8);
+    memcpy(CB, out.data() + (o_cb - o_s2), (size_t)(nf * H) * 8);
+    memcpy(d_last, out.data() + (o_dl - o_s2), (size_t)nf * 8);
+    memcpy(iters_done, out.data() + (o_it - o_s2), (size_t)nf * 8);
+    memcpy(status, out.data() + (o_st - o_s2), (size_t)nf * 8);
     return VBMF_OK;
     };
     const int rc = run();

@@ -24,7 +24,7 @@
 // vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): ONE pass 1 with the frozen B over the bags side by side,
 // then bag_gram (S_b = P_b'P_b, ||Y_b||^2), vbls_batch (all iterations, one workgroup per bag) and bag_a (A_b = P_b SigmaA_b / sigma2_b).
 // Here: the context, the launchers, set-up and read-back, the single-matrix updates and run loops (vbmf_run and sparse_run_impl around
-// one RunFrame), the sparse / grouped variants and the lower bounds.  The five many-bags entries and what they share: host_bags.hpp.
+// one RunFrame), the sparse / grouped variants and the lower bounds.  The many-bags entries and what they share: host_bags.hpp.
 #include "../../include/vbmf_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -48,6 +48,7 @@
 #include "batch_kernels.hpp"
 #include "sparse_batch_kernels.hpp"
 #include "fit_batch_kernels.hpp"
+#include "fit_basic_kernels.hpp"
 #include "score_kernels.hpp"
 #include "gram_kernels.hpp"
 
@@ -1652,6 +1653,8 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess && c->NH == 4)
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
         if (e == hipSuccess && c->NH == 4)

@@ -11,7 +11,7 @@
 module VBMatrixFactorizationHIP
 
 export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, updateCB!, updateSigma2!, updateYHat!,
-       vbls!, vbls_batch!, vbmf_sparse_batch!, vbmf_dual_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
+       vbls!, vbls_batch!, vbmf_batch!, vbmf_sparse_batch!, vbmf_dual_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
@@ -310,6 +310,66 @@ function vbls_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}, n
         p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')        # :201
     end
     return [p.AHat for p in ps]
+end
+
+"""
+vbmf! for many independent fits of the basic model in ONE device call (the two fits of examples/mil_util.jl:110-114 and the folds
+around them): does what `[vbmf!(Ys[bag_of[f]], ps[f], niter; eps = eps, est_covs = est_covs, est_var = est_var) for f in 1:length(ps)]`
+does -- every fit's whole loop of src/vbmf.jl:175-231 in one workgroup of one launch (vbmf_fit_batched) -- and returns
+(d, sweeps run, status) per fit; status 1 = the fit met a non-finite sigma2, a CA / CB entry that is not positive, or a bad pivot, and
+stopped.  Fit f works on bag bag_of[f] (1-based).  The bags share L; no labels, H <= 32 (anything else: vbmf! per fit).
+"""
+function vbmf_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}, niter::Int; eps::Float64 = 1e-6, est_covs::Bool = false,
+                     est_var::Bool = false, bag_of::Vector{Int} = collect(1:length(ps)))
+    nb, nf = length(Ys), length(ps)
+    (nb >= 1 && nf >= 1 && length(bag_of) == nf) || error("vbmf_batch!: one bag_of entry per parameter set")
+    niter >= 1 || error("vbmf_batch!: niter must be >= 1")
+    H, L = ps[1].H, size(Ys[1], 1)
+    H <= 32 || error("vbmf_batch!: H = $H > 32; use vbmf! per fit")
+    all(size(Y, 1) == L && size(Y, 2) >= 1 for Y in Ys) || error("vbmf_batch!: the bags have different L; use vbmf! per fit")
+    for (f, p) in enumerate(ps)
+        1 <= bag_of[f] <= nb || error("vbmf_batch!: bag_of[$f] = $(bag_of[f]) outside 1..$nb")
+        (p.L, p.M, p.H) == (L, size(Ys[bag_of[f]], 2), H) || error("vbmf_batch!: fit $f does not match its bag")
+        (p.H1 == 0 && isempty(p.labels)) || error("vbmf_batch!: fit $f has labels; use vbmf! per fit")
+    end
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    M = off[end]
+    Yall = reduce(hcat, Ys)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, 0, 0xffffffff, 1, 0, 0, 0, 0, 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
+    fb = Int64[b - 1 for b in bag_of]
+    B = reduce(vcat, [vec(Matrix{Float64}(p.BHat)) for p in ps]); SB = reduce(vcat, [vec(Matrix{Float64}(p.SigmaB)) for p in ps])
+    ca = Float64[p.CA[i, i] for i in 1:H, p in ps]; cb = Float64[p.CB[i, i] for i in 1:H, p in ps]
+    s2 = Float64[p.sigma2 for p in ps]
+    A = Array{Float64}(undef, sum(p.M for p in ps) * H)
+    SA = Array{Float64}(undef, H, H, nf)
+    it = zeros(Int64, nf); dlast = Array{Float64}(undef, nf); st = zeros(Int64, nf)
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        chk(h[], ccall((:vbmf_fit_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+            h[], nb, off, nf, fb, niter, eps, est_covs, est_var, B, SB, ca, cb, s2, A, SA, it, dlast, st, C_NULL))
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+    s = 0
+    for (f, p) in enumerate(ps)
+        p.AHat = reshape(A[s+1:s+p.M*H], p.M, H)                    # rebound, like updateA! / updateB! (src/vbmf.jl:96-98,110-112)
+        s += p.M * H
+        p.BHat = reshape(B[(f-1)*L*H+1:f*L*H], L, H)
+        p.SigmaA = SA[:, :, f]
+        p.SigmaB = reshape(SB[(f-1)*H*H+1:f*H*H], H, H)
+        for i in 1:H                                                # the diagonals in place (src/vbmf.jl:131,143)
+            p.CA[i, i] = ca[i, f]
+            p.CB[i, i] = cb[i, f]
+        end
+        p.invCA = inv(p.CA); p.invCB = inv(p.CB)
+        p.sigma2 = s2[f]
+        p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')        # :217
+    end
+    return dlast, it, st
 end
 
 "copy_vbmf_params -- examples/mil_util.jl:212-236 (vbmf_parameters branch)"
