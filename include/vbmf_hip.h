@@ -99,6 +99,30 @@ const char* vbmf_last_error(const vbmf_ctx* ctx); /* ctx may be NULL: error of a
  * the two MFMA-fragment-tiled copies and caches ||Y||_F^2 (of the values as stored).  Replaces the
  * `Y::Array{Float64,2}` argument of vbmf!/updateA!/updateB!/updateSigma2! (src/vbmf.jl:95,109,153,175). */
 int vbmf_set_Y(vbmf_ctx* ctx, const double* Y, int64_t ldY);
+/* The same Y from the caller's own number format, layout and memory, whole or in row blocks: no fp64 copy is made anywhere.  The
+ * reference has Float32 methods on this path (scaleY, preprocess: src/util.jl:60,94).
+ *   src: element (l, m) of the block, l in 0..nrows-1, m in 0..M-1, is src[l*row_stride + m*col_stride]; strides count elements of
+ *     src_dtype (VBMF_SRC_*).  Rows are this rank's local rows, as for vbmf_get_Y.  Every value is converted ONCE to the context's
+ *     storage type, round-to-nearest-even through fp64, as vbmf_set_Y does: the same values give the same stored bits, pad tiles included.
+ *   Blocks come in ascending, contiguous order: row0 equals the number of rows supplied so far and is a multiple of 32; nrows is a
+ *     multiple of 32 unless row0 + nrows = L.  The block with row0 = 0 starts a new Y: from then on the context has no Y (every entry
+ *     that needs one fails as on a fresh context), ||Y||^2 starts from zero and G, W of the Gram form are invalid.  The block that
+ *     reaches L completes Y (the per-row norms of the *_DIAGVAR variants included).  row0 = 0, nrows = L is the whole matrix at once.
+ *   src_on_device != 0: src is device memory on the context's device; any positive strides (views, slices, transposes).  The caller
+ *     guarantees that the buffer is complete and stays valid until the call returns; the entry runs on the context's stream and
+ *     returns after that stream is idle.
+ *   src_on_device == 0: src is host memory with row_stride = 1 or col_stride = 1 (and the other stride no shorter than a line).  It is
+ *     staged through a device buffer of its OWN dtype in chunks of at most 256 MB.
+ * VBMF_ERR_INVALID, before any launch or copy and with the context -- its current Y included -- untouched, for: NULL src; an unknown
+ * dtype; a non-positive stride; a host source with neither stride 1 (or with overlapping lines); a row0 / nrows that is misaligned,
+ * out of order or past L; a pointer whose kind contradicts src_on_device or that lives on another device (hipPointerGetAttributes); a
+ * device source whose extent [src, src + ((nrows-1)*row_stride + (M-1)*col_stride + 1) elements) does not lie inside one allocation
+ * (hipMemGetAddressRange).  A wrong pointer comes back as an error code; no kernel reads it. */
+#define VBMF_SRC_F64 0
+#define VBMF_SRC_F32 1
+#define VBMF_SRC_BF16 2
+int vbmf_set_Y_rows(vbmf_ctx* ctx, const void* src, int32_t src_dtype, int32_t src_on_device,
+                    int64_t row0, int64_t nrows, int64_t row_stride, int64_t col_stride);
 /* Device-side generator of the toy model (examples/toy_data.jl:7-18): Y = B* A*' + noise_std*N(0,1),
  * A* one-hot rows over Hstar columns, values rounded to the device dtype; counter-based, so the
  * matrix does not depend on nranks. */
@@ -401,12 +425,13 @@ int vbmf_device_sync(vbmf_ctx* ctx);
 #define VBMF_PEEK_FB 5     /* BHat MFMA operand tiles */
 #define VBMF_PEEK_Y1 6     /* Y tiled for pass 1 */
 #define VBMF_PEEK_Y2 7     /* Y tiled for pass 2 */
-#define VBMF_PEEK_DIMS 8   /* int32 x 27: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
+#define VBMF_PEEK_DIMS 8   /* int32 x 28: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
                               p_frag / q_frag (the last pass 1 / pass 2 launch wrote its product fragment-major: [XT][NH][64][16]),
                               q_epi (the last pass 2 launch ran the register epilogue and stored no product), lds8 (H >= 128 bf16x2
                               passes run the LDS-DMA kernel), xcd_map (split-K launches use the XCD-aware work map), post3 (H >= 128
                               bf16 factor updates run post_frag3 rather than post_frag2), sparse_a_fused (the ARD-sparse A update writes its
-                              operand tiles itself, VBMF_SPARSE_A_FUSED) */
+                              operand tiles itself, VBMF_SPARSE_A_FUSED), set_y_rows_us (device time of the last vbmf_set_Y_rows call
+                              between two HIP events on the context's stream: staged copies, tiling kernels, ||Y||^2) */
 #define VBMF_PEEK_CHAIN 9  /* uint64 x 8 (16 words): last durations in 10 ns ticks of the in-launch control chain's parts
                               (ctrl_end, SigmaA, lambda_max(dB'dB) + loop test, SigmaB) and of the register epilogue's tail in
                               workgroup 0 of the Y*A pass (wait for + load of the SigmaB table, tiles, fold + store, reserved) */

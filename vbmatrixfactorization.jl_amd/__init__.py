@@ -106,15 +106,20 @@ def _labels0(p):
     return lab - 1
 
 
+def _shape2(Y):
+    """(L, M) of a matrix: a NumPy array, anything np.asarray takes, or a torch tensor (left where it is)."""
+    shape = tuple(Y.shape) if capi._is_tensor(Y) else np.asarray(Y).shape
+    if len(shape) != 2:
+        raise ValueError("Y must be a matrix")
+    return int(shape[0]), int(shape[1])
+
+
 def vbmf_init(Y, H, ca=1.0, cb=1.0, sigma2=1.0, H1=0, labels=(), rng=None, materialize_yhat=None):
     """src/vbmf.jl:48-73.  Host-side (the random draw is outside the hot path); `rng` is a
     numpy Generator standing in for Julia's global RNG."""
-    Y = np.asarray(Y)
-    if Y.ndim != 2:
-        raise ValueError("Y must be a matrix")
+    L, M = _shape2(Y)                                          # the shape is all that is read of Y
     rng = np.random.default_rng() if rng is None else rng
     p = vbmf_parameters()
-    L, M = Y.shape
     p.L, p.M, p.H, p.H1 = L, M, int(H), int(H1)
     p.labels = np.asarray(labels, dtype=np.int64)
     p.AHat = rng.standard_normal((M, H))
@@ -148,7 +153,20 @@ class Session:
 
     # -- data --
     def set_Y(self, Y):
-        self.ctx.set_Y(Y)
+        """The whole matrix.  A float64 NumPy array (or anything that is not an array or tensor: converted to one) goes through
+        vbmf_set_Y; a float32 array or a torch tensor (float64, float32, bfloat16; CPU or this session's GPU) is read where it lies,
+        in its own dtype, through vbmf_set_Y_rows."""
+        if capi._is_tensor(Y) or (isinstance(Y, np.ndarray) and Y.dtype != np.float64):
+            if _shape2(Y) != (self.L, self.M):
+                raise ValueError(f"expected shape {(self.L, self.M)}, got {tuple(Y.shape)}")
+            self.ctx.set_Y_rows(Y, 0, self.L)
+        else:
+            self.ctx.set_Y(Y)
+
+    def set_Y_rows(self, block, row0):
+        """Rows row0 .. of a matrix that never exists whole on the host: blocks in ascending order, each a multiple of 32 rows but
+        the last (capi.Context.set_Y_rows).  The session has no Y between the first block and the last."""
+        self.ctx.set_Y_rows(block, row0)
 
     def set_Y_synthetic(self, seed, Hstar, noise_std):
         self.ctx.set_Y_synthetic(seed, Hstar, noise_std)
@@ -228,12 +246,21 @@ def invalidate(Y=None):
 
 
 def _session_for(Y, H):
-    Y = np.asarray(Y, dtype=np.float64)
-    if Y.ndim != 2:
-        raise ValueError("Y must be a matrix")
-    key = (id(Y), Y.shape, Y.__array_interface__["data"][0], int(H), tuple(sorted(_defaults.items())))
+    if capi._is_tensor(Y):
+        # a tensor: keyed on where it lies; torch counts its in-place edits (no content fingerprint, which on a GPU tensor would
+        # need a read-back of the matrix)
+        _shape2(Y)
+        key = (id(Y), tuple(Y.shape), Y.data_ptr(), int(H), tuple(sorted(_defaults.items())), str(Y.dtype), str(Y.device))
+        fp = ("version", Y._version)
+    else:
+        if not (isinstance(Y, np.ndarray) and Y.dtype == np.float32):   # a float32 array is uploaded, and fingerprinted, as it is
+            Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("Y must be a matrix")
+        key = (id(Y), Y.shape, Y.__array_interface__["data"][0], int(H), tuple(sorted(_defaults.items())))
+        fp = _fingerprint(Y)
     ent = _sessions.get(key)
-    fp = _fingerprint(Y)
+
     if ent is not None and ent[1]() is Y:
         if ent[2] != fp:                       # same array object, new contents: upload again
             ent[0].set_Y(Y)
@@ -246,7 +273,7 @@ def _session_for(Y, H):
     dead = [k for k, v in _sessions.items() if v[1]() is None or k[:3] == key[:3]]
     s = None
     for k in dead:
-        if s is None and k[0] != "noY" and k[1] == key[1] and k[3:] == key[3:] and Y.size <= _POOL_ELEMS:
+        if s is None and k[0] != "noY" and k[1] == key[1] and k[3:] == key[3:] and key[1][0] * key[1][1] <= _POOL_ELEMS:
             s = _sessions.pop(k)[0]
     keep = 0
     for k in dead:
@@ -283,9 +310,8 @@ def _session_for_params(p):
 
 
 def _check(Y, p):
-    Y = np.asarray(Y)
-    if Y.shape != (p.L, p.M):
-        raise ValueError(f"Y is {Y.shape}, params describe {(p.L, p.M)}")
+    if _shape2(Y) != (p.L, p.M):
+        raise ValueError(f"Y is {_shape2(Y)}, params describe {(p.L, p.M)}")
 
 
 def _one(Y, p, which, want_B):

@@ -17,6 +17,7 @@ if os.environ.get("VBMF_HIP_LIB") and not os.path.isfile(LIB_PATH):
     raise FileNotFoundError(f"VBMF_HIP_LIB={LIB_PATH}: no such library (A/B variant builds: scripts/README.md)")
 
 VBMF_Y_F32, VBMF_Y_BF16 = 0, 1
+VBMF_SRC_F64, VBMF_SRC_F32, VBMF_SRC_BF16 = 0, 1, 2      # src_dtype of vbmf_set_Y_rows
 VBMF_FACTOR_AUTO, VBMF_FACTOR_BF16, VBMF_FACTOR_BF16X2 = 0, 1, 2
 VBMF_FACTOR_BF16_MAX_H = 128      # vbmf_create refuses the single-bf16 factor operand above this rank (include/vbmf_hip.h)
 VBMF_VARIANT_BASIC, VBMF_VARIANT_SPARSE_DIAG, VBMF_VARIANT_SPARSE_DIAGVAR, VBMF_VARIANT_DUAL_DIAG, VBMF_VARIANT_TRIAL_DIAG = 0, 1, 2, 3, 4
@@ -27,7 +28,7 @@ UNIQUE_ID_BYTES = 128
 
 # every symbol include/vbmf_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
-    "vbmf_default_opts", "vbmf_create", "vbmf_destroy", "vbmf_last_error", "vbmf_set_Y", "vbmf_set_Y_synthetic",
+    "vbmf_default_opts", "vbmf_create", "vbmf_destroy", "vbmf_last_error", "vbmf_set_Y", "vbmf_set_Y_rows", "vbmf_set_Y_synthetic",
     "vbmf_get_Y", "vbmf_get_trYY", "vbmf_set_state", "vbmf_get_state", "vbmf_step", "vbmf_run", "vbmf_run_fixed_basis",
     "vbmf_run_fixed_basis_batched", "vbmf_fit_batched", "vbmf_get_YHat",
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
@@ -101,6 +102,7 @@ def lib():
     L.vbmf_last_error.argtypes = [vp]
     L.vbmf_last_error.restype = C.c_char_p
     L.vbmf_set_Y.argtypes = [vp, dp, i64]
+    L.vbmf_set_Y_rows.argtypes = [vp, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
     L.vbmf_set_Y_synthetic.argtypes = [vp, C.c_uint64, i64, C.c_double]
     L.vbmf_get_Y.argtypes = [vp, dp, i64, i64, i64]
     L.vbmf_get_trYY.argtypes = [vp, dp]
@@ -173,6 +175,58 @@ def _fcol(a, shape=None):
     return np.asfortranarray(a)
 
 
+def _is_tensor(a):
+    """A torch tensor, told by its surface: torch itself is imported only once such an object has been passed."""
+    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
+
+
+def y_source(src, device=0):
+    """What vbmf_set_Y_rows needs to read `src` where it lies: (keep, address, VBMF_SRC_*, on_device, row_stride, col_stride), strides in
+    elements; `keep` owns the memory for the duration of the call.  A float64 / float32 NumPy array that is C- or F-contiguous, or a
+    view with one unit stride, is passed by its own address; any other view takes ONE contiguous copy in its own dtype.  A torch
+    tensor (float64, float32, bfloat16; CPU, or the GPU with index `device`) is passed by data_ptr() and stride(); a CPU tensor with
+    no unit stride is made contiguous first.  Raises TypeError / ValueError on anything else, before the library is touched."""
+    if _is_tensor(src):
+        import torch
+        codes = {torch.float64: VBMF_SRC_F64, torch.float32: VBMF_SRC_F32, torch.bfloat16: VBMF_SRC_BF16}
+        if src.dtype not in codes:
+            raise TypeError(f"Y must be float64, float32 or bfloat16, got {src.dtype}")
+        if src.dim() != 2:
+            raise ValueError("Y must be a matrix")
+        if src.is_cuda:
+            if src.device.index != device:
+                raise ValueError(f"Y lives on {src.device}, the context on GPU {device}")
+            torch.cuda.current_stream(src.device).synchronize()         # whatever produces the tensor has finished
+        elif src.device.type != "cpu":
+            raise ValueError(f"Y lives on {src.device}: only CPU and GPU tensors can be read")
+        rs, cs = _unit(src.shape, src.stride())
+        if min(rs, cs) <= 0 or (not src.is_cuda and 1 not in (rs, cs)):  # an expanded tensor; a host view with no unit stride
+            src = src.contiguous()
+            rs, cs = _unit(src.shape, src.stride())
+        return src, src.data_ptr(), codes[src.dtype], int(src.is_cuda), rs, cs
+    a = src if isinstance(src, np.ndarray) else np.asarray(src)
+    if a.dtype not in (np.float64, np.float32):
+        raise TypeError(f"Y must be float64 or float32, got {a.dtype}")
+    if a.ndim != 2:
+        raise ValueError("Y must be a matrix")
+    es = a.itemsize
+    st = _unit(a.shape, tuple(x // es if x % es == 0 else 0 for x in a.strides))
+    if min(st) <= 0 or 1 not in st:
+        a = np.ascontiguousarray(a)                                     # one copy, in its own dtype
+        st = _unit(a.shape, tuple(x // es for x in a.strides))
+    return a, a.ctypes.data, VBMF_SRC_F64 if a.dtype == np.float64 else VBMF_SRC_F32, 0, st[0], st[1]
+
+
+def _unit(shape, strides):
+    """Element strides of a matrix with the free stride of a length-1 dimension set so that lines do not overlap."""
+    rs, cs = int(strides[0]), int(strides[1])
+    if shape[0] == 1:
+        rs = max(1, shape[1] * cs) if cs > 0 else rs
+    if shape[1] == 1:
+        cs = max(1, shape[0] * rs) if rs > 0 else cs
+    return rs, cs
+
+
 class PreprocessPlan:
     """preprocess (src/util.jl:73-86) fused into the upload: holds the caller's fp64 Y on the device with its row
     statistics and the kept rows; Context.set_Y_preprocessed tiles from it.  Use as a context manager."""
@@ -231,6 +285,7 @@ class Context:
             self._h = C.c_void_p()
             raise VbmfError(rc, msg)
         self.L, self.M, self.H = int(L), int(M), int(H)
+        self.device = int(device)
 
     def _chk(self, rc):
         if rc != 0:
@@ -257,6 +312,22 @@ class Context:
     def set_Y(self, Y):
         Y = _fcol(Y, (self.L, self.M))
         self._chk(self._lib.vbmf_set_Y(self._h, _dptr(Y), Y.shape[0]))
+
+    def set_Y_rows(self, src, row0=0, nrows=None):
+        """Rows [row0, row0 + nrows) of Y from `src` as it lies (vbmf_set_Y_rows): a float64 / float32 NumPy array or a torch tensor
+        (float64, float32, bfloat16; CPU or this context's GPU), see y_source.  nrows defaults to src's rows; blocks come in
+        ascending order, each a multiple of 32 rows but the last."""
+        shape = tuple(src.shape) if hasattr(src, "shape") else np.shape(src)
+        if len(shape) != 2:
+            raise ValueError("Y must be a matrix")
+        n = shape[0] if nrows is None else int(nrows)
+        if shape[1] != self.M or shape[0] != n:
+            raise ValueError(f"expected a block of shape ({n}, {self.M}), got {shape}")
+        if row0 < 0 or n < 1 or row0 + n > self.L:
+            raise ValueError(f"rows [{row0}, {row0 + n}) do not lie in a matrix of {self.L} rows")
+        keep, addr, code, on_dev, rs, cs = y_source(src, self.device)
+        self._chk(self._lib.vbmf_set_Y_rows(self._h, addr, code, on_dev, int(row0), int(n), rs, cs))
+        del keep
 
     def set_Y_preprocessed(self, plan, lam):
         self._chk(self._lib.vbmf_set_Y_preprocessed(self._h, plan._h, float(lam)))
@@ -656,13 +727,14 @@ class Context:
                         (float(x) * 0.01 for x in v)))
 
     def dims(self):
-        v = self.peek(PEEK_DIMS, 27, dtype=np.int32)
+        v = self.peek(PEEK_DIMS, 28, dtype=np.int32)
         keys = ["Hp", "NH", "mode", "XT1", "KS1", "nsplit1", "sps1", "XT2", "KS2", "nsplit2", "sps2", "kstep", "npart", "narrow",
                 "streamk_per", "streamk_grid",       # segment-list plan of the Y*A pass: pieces per cut block (0: off), segments = workgroups
                 "gram", "gram_built", "gram_build_us", "gram_nsplit",   # vbmf_run takes the Gram form; G built; its build time; split-K
                 "p_frag", "q_frag", "q_epi",         # the last pass 1 / pass 2 product is fragment-major; the last pass 2 ran the register epilogue
                 "lds8", "xcd_map", "post3",          # variant switches as the context resolved them (VBMF_LDS8, VBMF_XCD_MAP, VBMF_POST3)
-                "sparse_a_fused"]                    # the ARD-sparse A update writes its operand tiles itself (VBMF_SPARSE_A_FUSED)
+                "sparse_a_fused",                    # the ARD-sparse A update writes its operand tiles itself (VBMF_SPARSE_A_FUSED)
+                "set_y_rows_us"]                     # device time of the last vbmf_set_Y_rows call (HIP events: staged copies, tiling, ||Y||^2)
         return dict(zip(keys, (int(x) for x in v)))
 
     def time_pass(self, p, iters=10):

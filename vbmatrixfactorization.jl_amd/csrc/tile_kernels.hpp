@@ -30,6 +30,22 @@ struct SynthSrc {
     }
 };
 
+// A block of rows in the caller's own dtype and layout (vbmf_set_Y_rows): local row l, column m at buf[(l - row0) * rs + m * cs],
+// strides in elements, rows [row0, row1) present.  The block ends at L or at a multiple of 32, so the tiles it owns never ask for a
+// row of another block; anything outside it reads as zero padding and is never fetched.
+__device__ __forceinline__ double src_f64(double v) { return v; }
+__device__ __forceinline__ double src_f64(float v) { return (double)v; }
+__device__ __forceinline__ double src_f64(__bf16 v) { return (double)bf2f(__builtin_bit_cast(unsigned short, v)); }
+template <class T>
+struct StridedSrc {
+    const T* buf; long long rs, cs;
+    long long row0, row1, M;
+    __device__ __forceinline__ double operator()(long long l, long long m) const {
+        if (l < row0 || l >= row1 || m >= M) return 0.0;
+        return src_f64(buf[(l - row0) * rs + m * cs]);
+    }
+};
+
 // One thread = one 16-byte fragment.  TRANSPOSED=false: x=m,k=l (Y1); true: x=l,k=m (Y2).
 // Fragments in [xt0,xt1) x [ks0,ks1) are produced.  When sumsq != nullptr each block writes the fp64 sum of
 // its squared stored values to sumsq[blockIdx.x] -- done on exactly one of the two copies.
@@ -83,6 +99,96 @@ __global__ __launch_bounds__(256) void tile_y_kernel(uint4* __restrict__ out, Sr
         __syncthreads();
         if (threadIdx.x == 0) sumsq[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
     }
+}
+
+// ---- both copies from ONE read of a source with a unit stride (vbmf_set_Y_rows) --------------------------------------------------
+// A workgroup takes a block of 32 (dimension s, any stride) x 128 (dimension u, unit stride) source values -- s = row, u = column for a
+// row-major source; s = column, u = row for a column-major one -- loads it coalesced along u, rounds every value once to the storage
+// type exactly as tile_y_kernel does, and keeps the rounded values as fp32 in LDS (a bf16 value is an fp32 with a zero low half).  It
+// then writes the fragments of both copies from LDS with 16-byte stores:
+//     copy A  x along s, k along u: one x tile, 128 / KSTEP k-steps; a lane's elements are 4 consecutive u (one or two 16-byte LDS reads)
+//     copy B  x along u, k along s: four x tiles, 32 / KSTEP k-steps; a lane's elements are NE single reads, lanes along u
+// Rows are PAIR_PITCH = 132 floats apart: 16-byte aligned, and the 16 lanes of a 16-byte read (16 consecutive s) fall on 16 different
+// 16-byte slots of the 256-byte bank row (132 / 4 = 33 = 1 mod 16); the single reads and all writes run along u and have no conflict.
+// The blocks also cover the padding of both copies (zeros, never fetched); each copy's own tile / k-step ranges decide what is stored.
+struct PairGeom {
+    long long ss;                          // source stride along s, in elements
+    long long s_org, u_org;                // source element 0 is (s_org, u_org)
+    long long s_lo, s_hi, u_lo, u_hi;      // the source holds [s_lo, s_hi) x [u_lo, u_hi); everything else is zero padding
+    long long s0, u0;                      // origin of block (0, 0): multiples of 32
+    int ns, nu;                            // blocks along s and along u
+    int xa0, xa1, ka0, ka1, KSA;           // copy A: x tiles and k-steps this call owns, k-steps per x tile of the buffer
+    int xb0, xb1, kb0, kb1, KSB;           // copy B
+};
+constexpr int PAIR_U = 128, PAIR_PITCH = PAIR_U + 4;
+
+template <int MODE, class T>
+__global__ __launch_bounds__(256) void tile_pair_kernel(uint4* __restrict__ outA, uint4* __restrict__ outB, const T* __restrict__ src,
+                                                        PairGeom g, double* sumsq) {
+    constexpr int KSTEP = (MODE == MODE_F32) ? 8 : 16;
+    constexpr int NE = (MODE == MODE_F32) ? 4 : 8;
+    constexpr int KA = PAIR_U / KSTEP, KB = 32 / KSTEP;
+    __shared__ __attribute__((aligned(16))) float S[32 * PAIR_PITCH];
+    const int t = threadIdx.x;
+    const long long nblk = (long long)g.ns * g.nu;
+    double acc = 0.0;
+    for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const long long sb = g.s0 + (blk / g.nu) * 32, ub = g.u0 + (blk % g.nu) * PAIR_U;
+#pragma unroll
+        for (int i = 0; i < 32 * PAIR_U / 256; ++i) {
+            const int idx = t + 256 * i, u = idx & (PAIR_U - 1), s = idx / PAIR_U;
+            const long long sg = sb + s, ug = ub + u;
+            float r = 0.0f;
+            if (sg >= g.s_lo && sg < g.s_hi && ug >= g.u_lo && ug < g.u_hi) {
+                // rounded ONCE, from the source's fp64, to the device dtype (round-to-nearest-even), as in tile_y_kernel
+                const double v = src_f64(src[(sg - g.s_org) * g.ss + (ug - g.u_org)]);
+                if (MODE == MODE_F32) r = (float)v;
+                else { const __bf16 q = (__bf16)v; r = bf2f(__builtin_bit_cast(unsigned short, q)); }
+                acc += (double)r * (double)r;
+            }
+            S[s * PAIR_PITCH + u] = r;
+        }
+        __syncthreads();
+        const int xtA = (int)(sb >> 5);
+        if (xtA >= g.xa0 && xtA < g.xa1) {
+            for (int f = t; f < KA * 64; f += 256) {
+                const int lane = f & 63, ksl = f >> 6, c = lane & 31, half = lane >> 5;
+                const int ks = (int)(ub / KSTEP) + ksl;
+                if (ks < g.ka0 || ks >= g.ka1) continue;
+                const float* row = S + c * PAIR_PITCH + ksl * KSTEP + 4 * half;
+                const float4 a = *reinterpret_cast<const float4*>(row);
+                uint4 o;
+                if (MODE == MODE_F32) { o.x = fbits(a.x); o.y = fbits(a.y); o.z = fbits(a.z); o.w = fbits(a.w); }
+                else {
+                    const float4 b = *reinterpret_cast<const float4*>(row + 8);
+                    o.x = (fbits(a.x) >> 16) | (fbits(a.y) & 0xFFFF0000u); o.y = (fbits(a.z) >> 16) | (fbits(a.w) & 0xFFFF0000u);
+                    o.z = (fbits(b.x) >> 16) | (fbits(b.y) & 0xFFFF0000u); o.w = (fbits(b.z) >> 16) | (fbits(b.w) & 0xFFFF0000u);
+                }
+                outA[((long long)xtA * g.KSA + ks) * 64 + lane] = o;
+            }
+        }
+        for (int f = t; f < 4 * KB * 64; f += 256) {
+            const int lane = f & 63, q = f >> 6, ksl = q % KB, xtl = q / KB, c = lane & 31, half = lane >> 5;
+            const int xt = (int)(ub >> 5) + xtl, ks = (int)(sb / KSTEP) + ksl;
+            if (xt < g.xb0 || xt >= g.xb1 || ks < g.kb0 || ks >= g.kb1) continue;
+            unsigned w[NE];
+#pragma unroll
+            for (int e = 0; e < NE; ++e) w[e] = fbits(S[(ksl * KSTEP + kperm(MODE, half, e)) * PAIR_PITCH + xtl * 32 + c]);
+            uint4 o;
+            if (MODE == MODE_F32) { o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3]; }
+            else {
+                o.x = (w[0] >> 16) | (w[1] & 0xFFFF0000u); o.y = (w[2] >> 16) | (w[3] & 0xFFFF0000u);
+                o.z = (w[NE - 4] >> 16) | (w[NE - 3] & 0xFFFF0000u); o.w = (w[NE - 2] >> 16) | (w[NE - 1] & 0xFFFF0000u);
+            }
+            outB[((long long)xt * g.KSB + ks) * 64 + lane] = o;
+        }
+        __syncthreads();
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);   // one partial per workgroup, summed later in a fixed order
+    __shared__ double part[4];
+    if ((t & 63) == 0) part[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) sumsq[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
 // *dst += sum(partials[0..n)) in a fixed order (run-to-run reproducible ||Y||^2)

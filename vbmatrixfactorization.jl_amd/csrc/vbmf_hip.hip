@@ -152,6 +152,9 @@ struct vbmf_ctx {
     double run_eps = 0.0;
     double* run_trace = nullptr;
     bool haveY = false, haveState = false;
+    hipEvent_t ev_y[2] = {nullptr, nullptr};   // around the device work of the last vbmf_set_Y_rows call (created by the first one)
+    double set_y_ms = 0.0;            // ... and what they measured: staged copies, tiling kernels, ||Y||^2 (VBMF_PEEK_DIMS word 27, us)
+    int64_t y_rows = 0;               // vbmf_set_Y_rows: rows of the Y being built that have arrived (L once Y is complete)
     bool gA_valid = false, gB_valid = false, P_valid = false;
     bool tr_valid = false;            // st[GX] = tr(B'YA) of the current (AHat, BHat)
     double trYY_local = 0.0;
@@ -1400,6 +1403,7 @@ int vbmf_destroy(vbmf_ctx* c) {
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_side) hipEventDestroy(c->ev_side);
     for (auto& e : c->ev_chk) if (e) hipEventDestroy(e);
+    for (auto& e : c->ev_y) if (e) hipEventDestroy(e);
     delete c;
     return VBMF_OK;
 }
@@ -1682,23 +1686,89 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
 // ---- Y -----------------------------------------------------------------------------------------
 }  // extern "C"
 
+// Tiles of both copies from a source functor: fragments [xa, xb) x [ka, kb) of the pass-1 copy (r1) and of the pass-2 copy (r2).
+// ||.||^2 of the stored values is taken on the pass-2 copy and ADDED to *sumsq.
+struct TileRange { int xa, xb, ka, kb; };
+template <class Src>
+static int launch_tiles(vbmf_ctx* c, const Src& src, TileRange r1, TileRange r2, double* sumsq) {
+    const int64_t n1 = (int64_t)(r1.xb - r1.xa) * (r1.kb - r1.ka) * 64, n2 = (int64_t)(r2.xb - r2.xa) * (r2.kb - r2.ka) * 64;
+    DISPATCH_MODE(c->mode, {
+        constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
+        hipLaunchKernelGGL((tile_y_kernel<TM, false, Src>), dim3(grid_for(n1, 256, 16384)), dim3(256), 0, c->stream, c->Y1,
+                           src, r1.xa, r1.xb, r1.ka, r1.kb, c->d1.KS, (double*)nullptr);
+        const int g2 = grid_for(n2, 256, 16384);
+        hipLaunchKernelGGL((tile_y_kernel<TM, true, Src>), dim3(g2), dim3(256), 0, c->stream, c->Y2,
+                           src, r2.xa, r2.xb, r2.ka, r2.kb, c->d2.KS, sumsq ? c->ypart : nullptr);
+        if (sumsq) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, c->ypart, g2, sumsq);
+    });
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
 template <class Src>
 static int build_tiles(vbmf_ctx* c, const Src& src, int64_t m0, int64_t m1, double* sumsq) {
     // pass-1 copy: x tiles covering columns [m0,m1), all k-steps; pass-2 copy: all x tiles, k-steps of [m0,m1)
     const int xt0 = (int)(m0 / 32), xt1 = (m1 >= c->M) ? c->d1.XT : (int)(m1 / 32);
     const int ks0 = (int)(m0 / c->kstep), ks1 = (m1 >= c->M) ? c->d2.KS : (int)(m1 / c->kstep);
-    const int64_t n1 = (int64_t)(xt1 - xt0) * c->d1.KS * 64, n2 = (int64_t)c->d2.XT * (ks1 - ks0) * 64;
+    return launch_tiles(c, src, TileRange{xt0, xt1, 0, c->d1.KS}, TileRange{0, c->d2.XT, ks0, ks1}, sumsq);
+}
+
+template <class Src>
+static int build_tiles_rows(vbmf_ctx* c, const Src& src, int64_t l0, int64_t l1, double* sumsq) {
+    // rows [l0,l1), l0 a multiple of 32 and l1 one too unless l1 = L.  pass-1 copy: all x tiles, k-steps of the rows; pass-2 copy:
+    // x tiles of the rows, all k-steps.  The block that ends at L also writes every pad tile behind it, as build_tiles does.
+    const int ks0 = (int)(l0 / c->kstep), ks1 = (l1 >= c->L) ? c->d1.KS : (int)(l1 / c->kstep);
+    const int xt0 = (int)(l0 / 32), xt1 = (l1 >= c->L) ? c->d2.XT : (int)(l1 / 32);
+    return launch_tiles(c, src, TileRange{0, c->d1.XT, ks0, ks1}, TileRange{xt0, xt1, 0, c->d2.KS}, sumsq);
+}
+
+// rows [l0, l1) from a device buffer with one unit stride: both copies from one read (tile_pair_kernel)
+template <class T>
+static int launch_tile_pair(vbmf_ctx* c, const T* dev, int64_t l0, int64_t l1, int64_t rs, int64_t cs, double* sumsq) {
+    const bool last = l1 >= c->L;
+    const int ks = c->kstep;
+    // what this block of rows owns: in the pass-1 copy all x tiles and the rows' k-steps, in the pass-2 copy the rows' x tiles and all
+    // k-steps; the block that ends at L owns every pad tile behind it (build_tiles_rows)
+    const int k1a = (int)(l0 / ks), k1b = last ? c->d1.KS : (int)(l1 / ks);
+    const int x2a = (int)(l0 / 32), x2b = last ? c->d2.XT : (int)(l1 / 32);
+    const int64_t l_end = last ? std::max<int64_t>((int64_t)c->d2.XT * 32, (int64_t)c->d1.KS * ks) : l1;
+    const int64_t m_end = std::max<int64_t>((int64_t)c->d1.XT * 32, (int64_t)c->d2.KS * ks);
+    PairGeom g;
+    uint4 *outA, *outB;
+    if (cs == 1) {                                     // row-major: s = row, u = column; copy A = pass 2 (x = l), copy B = pass 1 (x = m)
+        g.ss = rs; g.s_org = l0; g.u_org = 0; g.s_lo = l0; g.s_hi = l1; g.u_lo = 0; g.u_hi = c->M; g.s0 = l0; g.u0 = 0;
+        g.ns = (int)cdiv(l_end - l0, 32); g.nu = (int)cdiv(m_end, PAIR_U);
+        g.xa0 = x2a; g.xa1 = x2b; g.ka0 = 0; g.ka1 = c->d2.KS; g.KSA = c->d2.KS; outA = c->Y2;
+        g.xb0 = 0; g.xb1 = c->d1.XT; g.kb0 = k1a; g.kb1 = k1b; g.KSB = c->d1.KS; outB = c->Y1;
+    } else {                                           // column-major: s = column, u = row; copy A = pass 1, copy B = pass 2
+        g.ss = cs; g.s_org = 0; g.u_org = l0; g.s_lo = 0; g.s_hi = c->M; g.u_lo = l0; g.u_hi = l1; g.s0 = 0; g.u0 = l0;
+        g.ns = (int)cdiv(m_end, 32); g.nu = (int)cdiv(l_end - l0, PAIR_U);
+        g.xa0 = 0; g.xa1 = c->d1.XT; g.ka0 = k1a; g.ka1 = k1b; g.KSA = c->d1.KS; outA = c->Y1;
+        g.xb0 = x2a; g.xb1 = x2b; g.kb0 = 0; g.kb1 = c->d2.KS; g.KSB = c->d2.KS; outB = c->Y2;
+    }
+    const int grid = (int)std::min<int64_t>((int64_t)g.ns * g.nu, 16384);   // c->ypart holds 16384 partials
     DISPATCH_MODE(c->mode, {
         constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
-        hipLaunchKernelGGL((tile_y_kernel<TM, false, Src>), dim3(grid_for(n1, 256, 16384)), dim3(256), 0, c->stream, c->Y1,
-                           src, xt0, xt1, 0, c->d1.KS, c->d1.KS, (double*)nullptr);
-        const int g2 = grid_for(n2, 256, 16384);
-        hipLaunchKernelGGL((tile_y_kernel<TM, true, Src>), dim3(g2), dim3(256), 0, c->stream, c->Y2,
-                           src, 0, c->d2.XT, ks0, ks1, c->d2.KS, sumsq ? c->ypart : nullptr);
-        if (sumsq) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, c->ypart, g2, sumsq);
+        hipLaunchKernelGGL((tile_pair_kernel<TM, T>), dim3(grid), dim3(256), 0, c->stream, outA, outB, dev, g, c->ypart);
+        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, c->ypart, grid, sumsq);
     });
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
+}
+
+template <class T>
+static int tile_rows_typed(vbmf_ctx* c, const T* dev, int64_t l0, int64_t n, int64_t rs, int64_t cs, double* tr) {
+    // one unit stride: both copies from one coalesced read (2.2-3.0 ms against 4.5-5.3 ms at 100k x 10k, profiles/set_y_sources.txt);
+    // general strides: tile_y_kernel gathers once per copy
+    if (rs == 1 || cs == 1) return launch_tile_pair(c, dev, l0, l0 + n, rs, cs, tr);
+    return build_tiles_rows(c, StridedSrc<T>{dev, rs, cs, l0, l0 + n, c->M}, l0, l0 + n, tr);
+}
+
+// tiles of rows [l0, l0+n) from a DEVICE buffer whose element (0, 0) is row l0
+static int tile_rows_from(vbmf_ctx* c, const void* dev, int dt, int64_t l0, int64_t n, int64_t rs, int64_t cs, double* tr) {
+    if (dt == VBMF_SRC_F64) return tile_rows_typed(c, (const double*)dev, l0, n, rs, cs, tr);
+    if (dt == VBMF_SRC_F32) return tile_rows_typed(c, (const float*)dev, l0, n, rs, cs, tr);
+    return tile_rows_typed(c, (const __bf16*)dev, l0, n, rs, cs, tr);
 }
 
 static int finish_Y(vbmf_ctx* c) {
@@ -1708,6 +1778,7 @@ static int finish_Y(vbmf_ctx* c) {
     c->trYY_local = c->scal_host[0];
     c->trYY_reduced = !sharded(c) && c->o.nranks == 1;
     c->haveY = true;
+    c->y_rows = c->L;
     c->P_valid = false;
     c->Q_valid = false;
     c->G_valid = c->W_valid = false;                   // G = Y'Y is rebuilt by the next run that takes the Gram form
@@ -1749,6 +1820,90 @@ int vbmf_set_Y(vbmf_ctx* c, const double* Y, int64_t ldY) {
     hipFree(stage);
     if (rc != VBMF_OK) return rc;
     return finish_Y(c);
+}
+
+// ---- Y from the caller's own dtype, layout and memory, in row blocks ------------------------------------------------------------
+static size_t src_elem_size(int dt) { return dt == VBMF_SRC_F64 ? 8 : dt == VBMF_SRC_F32 ? 4 : 2; }
+
+int vbmf_set_Y_rows(vbmf_ctx* c, const void* src, int32_t dt, int32_t on_device, int64_t row0, int64_t nrows, int64_t rs, int64_t cs) {
+    if (!c) return VBMF_ERR_INVALID;
+    // every refusal comes before the first launch or copy and leaves the context, its current Y included, as it was
+    if (!src) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: null source");
+    if (dt != VBMF_SRC_F64 && dt != VBMF_SRC_F32 && dt != VBMF_SRC_BF16) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: unknown src_dtype %d", (int)dt);
+    if (rs <= 0 || cs <= 0) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: strides must be positive");
+    if (row0 < 0 || nrows <= 0 || row0 % 32 != 0 || nrows > c->L - row0 || (nrows % 32 != 0 && row0 + nrows != c->L))
+        FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: rows [%lld, %lld) of %lld: a block starts at a multiple of 32 and ends at one or at L",
+             (long long)row0, (long long)(row0 + nrows), (long long)c->L);
+    if (row0 != 0 && (c->haveY || row0 != c->y_rows))
+        FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: blocks come in ascending, contiguous order (row0 = %lld, the next block starts at %lld)",
+             (long long)row0, (long long)(c->haveY ? 0 : c->y_rows));
+    const size_t es = src_elem_size(dt);
+    if (!on_device) {
+        if (rs != 1 && cs != 1) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: a host source needs row_stride = 1 or col_stride = 1");
+        // the staged 2-D copy takes whole lines of the unit-stride dimension: they must not overlap
+        if (cs == 1 ? (rs < c->M && nrows > 1) : (cs < nrows && c->M > 1))
+            FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: the host source's lines overlap (the other stride is shorter than a line)");
+    }
+    HIPCHK(c, hipSetDevice(c->o.device));
+    {   // what kind of memory is it?  A wrong pointer comes back as an error code: no kernel and no copy ever reads it.
+        hipPointerAttribute_t at;
+        hipError_t e = hipPointerGetAttributes(&at, src);
+        if (e != hipSuccess) (void)hipGetLastError();                  // memory the runtime has never seen: plain host memory
+        const bool is_dev = e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+        if (on_device) {
+            if (!is_dev) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: src_on_device is set but src is not device memory");
+            if (at.device != c->o.device) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: src lives on device %d, the context on device %d", at.device, c->o.device);
+            const unsigned __int128 last = (unsigned __int128)(nrows - 1) * (unsigned __int128)rs + (unsigned __int128)(c->M - 1) * (unsigned __int128)cs;
+            hipDeviceptr_t base = nullptr;
+            size_t size = 0;
+            e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)src);
+            if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: src belongs to no device allocation"); }
+            const uintptr_t b = (uintptr_t)base, p = (uintptr_t)src;
+            if (p < b || p - b > size || (last + 1) * es > (unsigned __int128)(size - (p - b)))
+                FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: the strided extent of the block leaves its device allocation");
+        } else if (e == hipSuccess && at.type == hipMemoryTypeDevice) {
+            FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: src is device memory but src_on_device is 0");
+        }
+    }
+    if (!c->ev_y[0]) { HIPCHK(c, hipEventCreate(&c->ev_y[0])); HIPCHK(c, hipEventCreate(&c->ev_y[1])); }
+    HIPCHK(c, hipEventRecord(c->ev_y[0], c->stream));
+    double* tr = c->st + c->lay.scal() + S_TRYY;
+    if (row0 == 0) {                                   // a new Y begins: none until its last block has arrived
+        c->haveY = false;
+        c->y_rows = 0;
+        c->P_valid = c->Q_valid = c->tr_valid = false;
+        c->G_valid = c->W_valid = false;
+        HIPCHK(c, hipMemsetAsync(tr, 0, sizeof(double), c->stream));
+    }
+    if (on_device) {
+        TRY(tile_rows_from(c, src, dt, row0, nrows, rs, cs, tr));
+    } else {
+        // staged in the source's own dtype and order, whole 32-row groups per chunk of at most 256 MB (one group if that is larger)
+        const bool rowmajor = cs == 1;
+        int64_t rc = std::max<int64_t>(32, ((int64_t)(256ll << 20) / (c->M * (int64_t)es)) / 32 * 32);
+        rc = std::min<int64_t>(rc, rup(nrows, 32));
+        void* stage = nullptr;
+        HIPCHK(c, hipMalloc(&stage, (size_t)rc * c->M * es));
+        int rcode = VBMF_OK;
+        for (int64_t r = 0; r < nrows && rcode == VBMF_OK; r += rc) {
+            const int64_t n = std::min(rc, nrows - r);
+            const char* from = (const char*)src + (size_t)r * rs * es;
+            hipError_t e = rowmajor ? hipMemcpy2DAsync(stage, (size_t)c->M * es, from, (size_t)rs * es, (size_t)c->M * es, (size_t)n, hipMemcpyHostToDevice, c->stream)
+                                    : hipMemcpy2DAsync(stage, (size_t)n * es, from, (size_t)cs * es, (size_t)n * es, (size_t)c->M, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { c->err = std::string("vbmf_set_Y_rows: hipMemcpy2DAsync: ") + hipGetErrorString(e); rcode = VBMF_ERR_HIP; break; }
+            rcode = rowmajor ? tile_rows_from(c, stage, dt, row0 + r, n, c->M, 1, tr) : tile_rows_from(c, stage, dt, row0 + r, n, 1, n, tr);
+            if (rcode == VBMF_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed in vbmf_set_Y_rows"; rcode = VBMF_ERR_HIP; }
+        }
+        hipFree(stage);
+        if (rcode != VBMF_OK) return rcode;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_y[1], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));        // the caller may reuse its buffer once this returns
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_y[0], c->ev_y[1]));
+    c->set_y_ms = ms;
+    c->y_rows = row0 + nrows;
+    return c->y_rows == c->L ? finish_Y(c) : VBMF_OK;
 }
 
 // ---- preprocess (src/util.jl:36-54, 73-86) fused into the upload ---------------------------------
@@ -2301,12 +2456,12 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (what == VBMF_PEEK_DIMS) {
-        const int v[27] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
+        const int v[28] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
                            c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
                            gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
                            c->frag_last[0] ? 1 : 0, c->frag_last[1] ? 1 : 0, c->epi_last ? 1 : 0, use_lds8(c) ? 1 : 0, c->xcd_map ? 1 : 0,
-                           c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0};
-        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(27, nwords));
+                           c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0, (int)std::lround(c->set_y_ms * 1000.0)};
+        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(28, nwords));
         return VBMF_OK;
     }
     if (what == VBMF_PEEK_CHAIN) {

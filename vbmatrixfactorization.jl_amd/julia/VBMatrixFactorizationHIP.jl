@@ -59,17 +59,21 @@ end
 const VBMF_Y_F32, VBMF_Y_BF16 = Int32(0), Int32(1)
 const STEP_A, STEP_B, STEP_CA, STEP_CB, STEP_SIGMA2 = 1, 2, 4, 8, 16
 
+# what the basic model takes as Y: the reference's Array{Float64,2}, or an Array{Float32,2} that is uploaded as it is (the
+# reference has Float32 methods on this path: scaleY, preprocess, src/util.jl:60,94)
+const HostY = Union{Array{Float64,2},Array{Float32,2}}
+
 mutable struct Ctx
     h::Ptr{Cvoid}
-    Y::Array{Float64,2}       # keeps the identity of the uploaded Y
+    Y::HostY                  # keeps the identity of the uploaded Y
     fp::UInt                  # content fingerprint of Y at upload time (see fingerprint)
 end
-Ctx(h::Ptr{Cvoid}, Y::Array{Float64,2}) = Ctx(h, Y, fingerprint(Y))
+Ctx(h::Ptr{Cvoid}, Y::HostY) = Ctx(h, Y, fingerprint(Y))
 
 # The reference reads the caller's Y on every call; here it is uploaded once per array object, so a cache hit re-checks a
 # content fingerprint (all of Y up to 4M entries, an evenly strided sample of ~64k beyond) and uploads again when the SAME
 # array was changed in place (Y .*= lam, Y[:] = other).  invalidate!(Y) drops the device copy explicitly.
-function fingerprint(Y::Array{Float64,2})
+function fingerprint(Y::HostY)
     n = length(Y)
     st = n > (1 << 22) ? max(1, n >> 16) : 1
     h = hash(n)
@@ -92,16 +96,27 @@ function warn_note(h::Ptr{Cvoid})
     startswith(msg, "note:") && @warn msg
 end
 
+const VBMF_SRC_F64, VBMF_SRC_F32, VBMF_SRC_BF16 = Int32(0), Int32(1), Int32(2)
+
+"Upload Y into the context: a Float64 matrix through vbmf_set_Y; a Float32 matrix in its own format, with no Float64 copy, through vbmf_set_Y_rows (host source, whole matrix, column-major: row stride 1, column stride L)."
+set_Y!(h::Ptr{Cvoid}, Y::Array{Float64,2}) =
+    chk(h, ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h, Y, size(Y, 1)))
+function set_Y!(h::Ptr{Cvoid}, Y::Array{Float32,2})
+    L = size(Y, 1)
+    chk(h, ccall((:vbmf_set_Y_rows, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
+                 h, Y, VBMF_SRC_F32, Int32(0), 0, L, 1, L))
+end
+
 const _cache = Dict{UInt,Ctx}()
 
 # fp32 storage of the caller's Float64 Y by default; ENV["VBMF_HIP_Y"] = "bf16" opts into bf16 storage (the BASELINE headline
 # configuration): that changes the data the model sees and must be chosen knowingly
 y_dtype() = get(ENV, "VBMF_HIP_Y", "f32") == "bf16" ? VBMF_Y_BF16 : VBMF_Y_F32
 
-function refresh!(c::Ctx, Y::Array{Float64,2})
+function refresh!(c::Ctx, Y::HostY)
     fp = fingerprint(Y)
     if fp != c.fp                                          # same array object, new contents: upload again
-        chk(c.h, ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), c.h, Y, size(Y, 1)))
+        set_Y!(c.h, Y)
         c.fp = fp
     end
     return c
@@ -115,7 +130,7 @@ function invalidate!(Y = nothing)
 end
 
 "One device context per Y array (uploaded once, re-uploaded when its contents change)."
-function ctx_for(Y::Array{Float64,2}, H::Int)
+function ctx_for(Y::HostY, H::Int)
     key = hash((objectid(Y), size(Y), H))
     haskey(_cache, key) && return refresh!(_cache[key], Y)
     L, M = size(Y)
@@ -124,9 +139,9 @@ function ctx_for(Y::Array{Float64,2}, H::Int)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts)
     chk(Ptr{Cvoid}(C_NULL), rc)
-    chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Y, L))
     c = Ctx(h[], Y)
     finalizer(x -> ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), x.h), c)
+    set_Y!(c.h, Y)
     _cache[key] = c
     return c
 end
@@ -174,7 +189,7 @@ step!(Y, p, which) = (c = ctx_for(Y, p.H); push!(c, p); chk(c.h, ccall((:vbmf_st
 
 # ---- the reference surface ---------------------------------------------------------------------------
 "src/vbmf.jl:48-73 (host side: the random draw is not part of the accelerated path)"
-function vbmf_init(Y::Array{Float64,2}, H::Int; ca::Float64 = 1.0, cb::Float64 = 1.0, sigma2::Float64 = 1.0,
+function vbmf_init(Y::HostY, H::Int; ca::Float64 = 1.0, cb::Float64 = 1.0, sigma2::Float64 = 1.0,
                    H1::Int = 0, labels::Array{Int64,1} = Array{Int64,1}())
     params = vbmf_parameters()
     L, M = size(Y)
@@ -221,6 +236,14 @@ end
 "vbmf! -- src/vbmf.jl:175-231"
 function vbmf!(Y::Array{Float64,2}, params::vbmf_parameters, niter::Int; eps::Float64 = 1e-6, est_covs::Bool = false,
                est_var::Bool = false, logdir = "", desc = "", verb = false)
+    return fit_basic!(Y, params, niter, eps, est_covs, est_var, logdir, verb)
+end
+"vbmf! on a Float32 matrix: uploaded in its own format (vbmf_set_Y_rows), everything else as above"
+function vbmf!(Y::Array{Float32,2}, params::vbmf_parameters, niter::Int; eps::Float64 = 1e-6, est_covs::Bool = false,
+               est_var::Bool = false, logdir = "", desc = "", verb = false)
+    return fit_basic!(Y, params, niter, eps, est_covs, est_var, logdir, verb)
+end
+function fit_basic!(Y::HostY, params::vbmf_parameters, niter::Int, eps::Float64, est_covs::Bool, est_var::Bool, logdir, verb)
     logdir == "" || error("per-iteration logging: drive the sweeps from the reference's own create_log / update_log! / save_log " *
                           "(src/data_manip.jl works unchanged on these structs) around vbmf!(Y, params, 1; ...) calls")
     c = ctx_for(Y, params.H)
@@ -237,7 +260,7 @@ function vbmf!(Y::Array{Float64,2}, params::vbmf_parameters, niter::Int; eps::Fl
 end
 
 "vbmf -- src/vbmf.jl:238-248"
-function vbmf(Y::Array{Float64,2}, params_in::vbmf_parameters, niter::Int; kwargs...)
+function vbmf(Y::HostY, params_in::vbmf_parameters, niter::Int; kwargs...)
     params = copy(params_in)
     params.CA, params.CB = copy(params.CA), copy(params.CB)     # keep params_in reusable (see SURVEY App. A Q2)
     vbmf!(Y, params, niter; kwargs...)
