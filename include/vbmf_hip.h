@@ -270,6 +270,32 @@ int vbmf_sparse_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off
                             double* priors4, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA,
                             double* delta, double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
                             int64_t* iters_done, double* d_last, int64_t* status, double* trace);
+/* vbmf_local_fit_batched: many independent fits on concatenated matrices [Y0 Y1] whose first M0 columns are the negative instances, in
+ * ONE launch -- the three-group model (vbmf_trial!, src/vbmf_trial.jl:528-604) and the label-masked sparse model (train_local,
+ * examples/mil_util.jl:302-320: vbmf_sparse! with labels = 1:M0 and H1).  Everything is as in vbmf_sparse_fit_batched (shapes, in/out
+ * rules, status, trace, d under either compat bit, the QS1 layout by each fit's own M_b, the 1-column refusal in the diagonal form)
+ * except:
+ *   M0 (nfits): the fit's leading columns of its bag, 0 <= M0[f] <= M_b
+ *   H0: entry (m, h) of A belongs to prior group 1 if h < H0, to group 2 if h >= H0 and m < M0[f], to group 3 otherwise
+ *       (src/vbmf_trial.jl:357-400); 0 <= H0 <= H.  est_priors != 0 refits the three pairs every sweep (:442-507); an empty group keeps
+ *       its pair
+ *   mask_H1 > 0: once updateA! has produced a(m, h), the entries with m < M0[f], h >= H - mask_H1 become exactly 0 before updateCA!,
+ *       A'A and Y*A read them; diagSigmaATVec and SigmaA are not masked (src/vbmf_sparse.jl:236-246), so beta = beta0 + ds/2 there.
+ *       Needs H0 = H and est_priors = 0: the masked model has one prior group (slots 0, 1 of priors9) and no hyper-prior fit
+ *   priors9 (nfits*9), laid out as vbmf_trial_get_priors lays it out: slots 0-5 alpha01, beta01, alpha02, beta02, alpha03, beta03 are
+ *       in/out; slots 6-8 are out: the posterior shapes alpha1, alpha2, alpha3 the last updateCA! used
+ * The context is any `*_DIAG` sparse, two-group or three-group context; its state is neither read nor changed.
+ * VBMF_ERR_UNSUPPORTED: H > 32.  VBMF_ERR_INVALID, all before any launch, copy or change: a basic or `*_DIAGVAR` context, a label mask
+ * set on the context, nranks > 1, no Y, a bad col_off, a fit_bag entry outside 0..nbags-1, nfits < 1, niter < 1, a required pointer
+ * NULL, H0 outside 0..H, an M0[f] outside 0..M_b, mask_H1 outside 0..H, mask_H1 > 0 together with H0 != H or est_priors != 0, a 1-column
+ * bag in the diagonal form under VBMF_COMPAT_SPARSE_REPEAT. */
+int vbmf_local_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                           int64_t niter, double eps, int full_cov, int est_cb, int est_priors,
+                           int64_t H0, const int64_t* M0, int64_t mask_H1,
+                           const double* gamma, const double* delta0, const double* eta, const double* zeta0,
+                           double* priors9, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA,
+                           double* delta, double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
+                           int64_t* iters_done, double* d_last, int64_t* status, double* trace);
 int vbmf_sparse_step(vbmf_ctx* ctx, int which);           /* reference order A, B, CA, CB, SIGMA (:369-376) */
 /* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0) */
 int vbmf_sparse_run(vbmf_ctx* ctx, int64_t niter, double eps, int est_cb, int64_t* iters_done, double* d_last,

@@ -47,7 +47,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
            "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags", "vbmf_sparse_batch_", "vbmf_dual_batch_", "fit_restarts",
-           "vbmf_batch_", "train_folds",
+           "vbmf_batch_", "train_folds", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
@@ -1362,6 +1362,151 @@ def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, b
     """vbmf_dual! for many independent fits in one device call (the restart loop of examples/mil_util.jl:347-379): see
     vbmf_sparse_batch_; params: one vbmf_dual_parameters per fit, all with one H0."""
     return _fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of)
+
+
+def _local_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of):
+    """vbmf_trial_batch_ / vbmf_sparse_masked_batch_: the host checks, the one vbmf_local_fit_batched call, the fields of every set."""
+    def refuse(why):
+        raise ValueError(f"{fn}: {why}; run such fits one at a time with {one}")
+    params = list(params)
+    if not params:
+        refuse("no parameter sets")
+    if type(params[0]) is not kind:
+        refuse(f"fit 0: {type(params[0]).__name__} ({kind.__name__} only, one model type per call)")
+    H = int(params[0].H)
+    if H > _FIT_MAX_H:
+        refuse(f"H = {H} > {_FIT_MAX_H}")
+    if int(niter) < 1:
+        refuse(f"niter = {niter} < 1")
+    if isinstance(Ys, SparseBags):
+        bags = Ys
+        if bags.H != H:
+            refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
+        L, Ms, ctx_kw = bags.L, bags.Ms, bags.ctx_kw
+    else:
+        bags = None
+        (L, Ms), ctx_kw = _batch_shapes(Ys, H, refuse), _defaults
+    if bag_of is None:
+        if len(params) != len(Ms):
+            refuse(f"{len(Ms)} bags but {len(params)} parameter sets and no bag_of")
+        bag_of = range(len(Ms))
+    bag_of = [int(b) for b in bag_of]
+    if len(bag_of) != len(params):
+        refuse(f"{len(params)} parameter sets but {len(bag_of)} entries in bag_of")
+    m = _MODELS[kind]
+    masked = m.labels
+    repeat = bool(ctx_kw.get("reference_compat", capi.VBMF_COMPAT_DEFAULT) & capi.VBMF_COMPAT_SPARSE_REPEAT)
+    M0s = []
+    for f, (p, b) in enumerate(zip(params, bag_of)):
+        if type(p) is not kind:
+            refuse(f"fit {f}: {type(p).__name__} ({kind.__name__} only, one model type per call)")
+        if not 0 <= b < len(Ms):
+            refuse(f"fit {f}: bag_of = {b} outside 0..{len(Ms) - 1}")
+        if int(p.H) != H:
+            refuse(f"fit {f}: H = {p.H} beside H = {H}")
+        if (p.L, p.M) != (L, Ms[b]):
+            refuse(f"fit {f}: bag {b} is {L} x {Ms[b]}, its parameters describe {(p.L, p.M)}")
+        if masked:
+            if int(p.H1) != int(params[0].H1) or not 0 <= int(p.H1) <= H:
+                refuse(f"fit {f}: H1 = {p.H1} (one H1 in 0..H per call)")
+            lab = np.asarray(p.labels).reshape(-1)
+            if lab.size > Ms[b] or not np.array_equal(lab, np.arange(1, lab.size + 1)):
+                refuse(f"fit {f}: labels are not the prefix 1..M0 of the columns (the rows of AHat the batched mask covers)")
+            M0s.append(int(lab.size))
+        else:
+            if int(p.H0) != int(params[0].H0) or not 0 <= int(p.H0) <= H:
+                refuse(f"fit {f}: H0 = {p.H0} (one H0 in 0..H per call)")
+            if not 0 <= int(p.M0) <= Ms[b]:
+                refuse(f"fit {f}: M0 = {p.M0} outside 0..M = {Ms[b]}")
+            M0s.append(int(p.M0))
+        if np.shape(p.BHat) != (L, H) or np.shape(p.SigmaB) != (H, H) or np.size(p.CB) != H or np.size(p.CA) != Ms[b] * H:
+            refuse(f"fit {f}: BHat, SigmaB, CB or CA does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
+        if not full_cov and repeat and Ms[b] < 2:
+            refuse(f"fit {f} works on a 1-column bag: the diagonal form under the repeat layout needs M >= 2")
+        _check_derived(p)
+        if _alpha_not_derived(m, p):
+            refuse(f"fit {f}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
+    own = bags is None
+    if own:
+        bags = SparseBags(Ys, H)
+    groups = [m.groups[min(k, len(m.groups) - 1)] for k in range(3)]       # (the masked model: its one pair three times)
+    try:
+        r = bags.ctx.local_fit_batched(
+            bags.col_off, bag_of, int(niter), float(eps), [p.gamma0 + p.L / 2 for p in params], [p.delta0 for p in params],
+            [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
+            [[getattr(p, k) for a0, b0, _ in groups for k in (a0, b0)] for p in params],
+            np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]), np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]),
+            np.stack([np.asarray(p.CB, dtype=np.float64).reshape(H) for p in params]), [p.sigmaHat for p in params],
+            np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]), M0s,
+            H0=H if masked else int(params[0].H0), mask_H1=int(params[0].H1) if masked else 0, full_cov=full_cov, est_cb=est_cb,
+            est_priors=est_priors and not masked)
+    finally:
+        if own:
+            bags.close()
+    s0 = 0
+    for f, p in enumerate(params):
+        s1 = s0 + p.M * H
+        p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
+        p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
+        s0 = s1
+        p.AHat = p.ATVecHat.reshape(p.M, H).copy()
+        p.SigmaA = r["SigmaA"][f].copy()
+        p.BHat, p.SigmaB, p.CB = np.array(r["BHat"][f], order="F"), r["SigmaB"][f].copy(), r["CB"][f].copy()
+        if est_cb:
+            p.delta = r["delta"][f].copy()
+        p.sigmaHat, p.zeta = float(r["sigmaHat"][f]), float(r["zeta"][f])
+        p.iters, p.status = int(r["iters"][f]), int(r["status"][f])
+        if not masked:
+            m.views(p)
+            for k, v in zip(Context.TRIAL_KEYS, r["priors9"][f]):   # the pairs, and the shapes the last updateCA! used
+                setattr(p, k, float(v))
+            p.alpha = _posterior_shapes(p, m)
+        p.YHat = _host_YHat(p)
+    return [float(v) for v in r["d"]]
+
+
+def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True):
+    """vbmf_trial! for many independent fits in one device call: does what [vbmf_trial_(Ys[bag_of[f]], p, niter, eps=eps, ...) for f, p
+    in enumerate(params)] does (src/vbmf_trial.jl:528-604) -- fills on every p the fields vbmf_trial_ fills (the group views A1Hat..A3Hat,
+    CA1..3, beta1..3, the posterior shapes alpha1..3 and the six hyper-priors included), plus p.iters and p.status as vbmf_sparse_batch_
+    does, and returns the list of d.  params: one vbmf_trial_parameters per fit, one H <= 32 and one H0 per call, M0 per fit.  Every
+    fit's whole loop runs in one workgroup of one launch (include/vbmf_hip.h, vbmf_local_fit_batched)."""
+    return _local_fit_batch("vbmf_trial_batch_", "vbmf_trial_", vbmf_trial_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors,
+                            bag_of)
+
+
+def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None):
+    """vbmf_sparse! with a label mask for many independent fits in one device call (the fit of train_local, examples/mil_util.jl:302-320,
+    on Y = [Y0 Y1]): see vbmf_sparse_batch_.  params: one vbmf_sparse_parameters per fit whose labels are exactly the prefix 1..M0 of
+    the columns (possibly empty; M0 per fit), with one H1 per call: the last H1 columns of AHat stay zero in the rows 1..M0
+    (src/vbmf_sparse.jl:245).  Any other label set is refused: run it with vbmf_sparse_."""
+    return _local_fit_batch("vbmf_sparse_masked_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb,
+                            False, bag_of)
+
+
+def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None):
+    """The reference's train_local (examples/mil_util.jl:302-320) over many (Y0, Y1) pairs with all the fits in ONE device call per
+    round: per pair Y = [Y0 Y1] and vbmf_sparse_init(Y, H, H1=H1, labels=1:M0), drawn in fold order from the one generator; every fold
+    runs vbmf_sparse! in the diagonal form (:314); then, as the loop of :312-317 does, a fold whose norm(AHat) and norm(BHat) (operator
+    2-norms) are both below 1e-2 runs again from where it stands, one further call per round, ten rounds at most.  Returns the list of
+    parameter sets."""
+    rng = np.random.default_rng() if rng is None else rng
+    Ys, ps = [], []
+    for Y0, Y1 in folds:
+        Y = np.concatenate([np.asarray(Y0, dtype=np.float64), np.asarray(Y1, dtype=np.float64)], axis=1)
+        Ys.append(Y)
+        ps.append(vbmf_sparse_init(Y, H, H1=H1, labels=np.arange(1, np.shape(Y0)[1] + 1), rng=rng))
+    if not ps:
+        return ps
+    norms = lambda p: (np.linalg.norm(p.AHat, 2), np.linalg.norm(p.BHat, 2))   # Julia 0.5 norm(::Matrix): the operator 2-norm
+    bound = [sum(norms(p)) for p in ps]                             # delta of :312: the first round runs whatever the norms are
+    for _ in range(10):                                             # max_restarts (:310)
+        again = [k for k, p in enumerate(ps) if all(v < bound[k] for v in norms(p))]
+        if not again:
+            break
+        vbmf_sparse_masked_batch_([Ys[k] for k in again], [ps[k] for k in again], niter, eps=eps, full_cov=False)
+        bound = [1e-2] * len(ps)                                    # :315
+    return ps
 
 
 def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, full_cov=None, diag_var=False, rng=None):

@@ -34,7 +34,7 @@ SYMBOLS = [
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
-    "vbmf_sparse_run_fixed_basis_batched", "vbmf_sparse_fit_batched",
+    "vbmf_sparse_run_fixed_basis_batched", "vbmf_sparse_fit_batched", "vbmf_local_fit_batched",
     "vbmf_sparse_lower_bound", "vbmf_sparse_set_noise_rows", "vbmf_sparse_get_noise_rows", "vbmf_preprocess_open", "vbmf_preprocess_rows", "vbmf_set_Y_preprocessed",
     "vbmf_preprocess_close", "vbmf_dual_set_priors", "vbmf_dual_get_priors", "vbmf_dual_run",
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
@@ -118,6 +118,8 @@ def lib():
     L.vbmf_sparse_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]
     L.vbmf_sparse_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64] + [dp] * 16
                                           + [C.POINTER(i64), dp, C.POINTER(i64), dp])
+    L.vbmf_local_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64,
+                                          C.POINTER(i64), i64] + [dp] * 16 + [C.POINTER(i64), dp, C.POINTER(i64), dp])
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
     L.vbmf_elbo.argtypes = [vp, dp]
     L.vbmf_comm_unique_id.argtypes = [vp]
@@ -506,6 +508,49 @@ class Context:
             _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA), _dptr(A), p64(iters), _dptr(dl),
             p64(st), _dptr(tr)))
         return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, priors4=pri, CA=ca, beta=beta,
+                    diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA, iters=iters, d=dl, status=st, trace=tr)
+
+    def local_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors9, BHat, SigmaB, CB, sigmaHat, CA, M0,
+                          H0=None, mask_H1=0, full_cov=False, est_cb=True, est_priors=False, want_trace=False):
+        """Many independent three-group (vbmf_trial!) or label-masked sparse (train_local) fits in one launch (vbmf_local_fit_batched): as
+        sparse_fit_batched, with M0 (nfits,) the leading columns of each fit's bag that are its negative instances.  Entry (m, h) of A takes
+        the prior pair of group 1 if h < H0, of group 2 if m < M0[f], else of group 3; with mask_H1 > 0 (H0 = H, est_priors off) the
+        entries m < M0[f], h >= H - mask_H1 of A are held at zero.  priors9 (nfits, 9) in trial_get_priors' order: three (alpha0g, beta0g)
+        pairs in, the pairs and the three posterior shapes out; (nfits, 6) is accepted and padded.  Returns sparse_fit_batched's dict with
+        priors9 in place of priors4."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
+        nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
+        vec = lambda v: np.array(v, dtype=np.float64, copy=True).reshape(-1)
+        ga, d0, et, z0, sg, ca = vec(gamma), vec(delta0), vec(eta), vec(zeta0), vec(sigmaHat), vec(CA)
+        m0 = np.array(M0, dtype=np.int64, copy=True).reshape(-1)
+        pin = np.asarray(priors9, dtype=np.float64)
+        pri = np.zeros((nf, 9))
+        if pin.ndim == 2 and pin.shape[0] == nf and pin.shape[1] in (6, 9):
+            pri[:, :pin.shape[1]] = pin
+        else:
+            raise ValueError(f"{nf} fits: priors9 must be ({nf}, 9) or ({nf}, 6)")
+        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, L, H).transpose(0, 2, 1))   # per fit column-major
+        SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
+        cb = np.array(CB, dtype=np.float64, copy=True, order="C")
+        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
+            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
+        MH = int(np.sum(off[fb + 1] - off[fb])) * H
+        if (any(v.shape != (nf,) for v in (ga, d0, et, z0, sg, m0)) or SB.shape != (nf, H, H) or cb.shape != (nf, H) or ca.shape != (MH,)):
+            raise ValueError(f"{nf} fits: gamma, delta0, eta, zeta0, sigmaHat, M0 must be ({nf},), SigmaB ({nf}, {H}, {H}), "
+                             f"CB ({nf}, {H}) and CA ({MH},)")
+        delta = np.empty((nf, H)) if est_cb else None
+        zeta, beta, dS, A = np.empty(nf), np.empty(MH), np.empty(MH), np.empty(MH)
+        SA = np.empty((nf, H, H))
+        iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
+        tr = np.zeros((nf, int(niter), 2)) if want_trace else None
+        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._chk(self._lib.vbmf_local_fit_batched(
+            self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
+            int(H if H0 is None else H0), p64(m0), int(mask_H1), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0), _dptr(pri), _dptr(B), _dptr(SB),
+            _dptr(cb), _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA), _dptr(A), p64(iters), _dptr(dl),
+            p64(st), _dptr(tr)))
+        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, priors9=pri, CA=ca, beta=beta,
                     diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA, iters=iters, d=dl, status=st, trace=tr)
 
     def YHat(self):

@@ -1,5 +1,6 @@
 // fit_batch_kernels.hpp -- many small ARD-sparse / two-group fits in one launch (vbmf_sparse_fit_batched; the restart loops of
-// examples/mil_util.jl:124-145, 347-379 and the folds x classes around them in one call).
+// examples/mil_util.jl:124-145, 347-379 and the folds x classes around them in one call), and with LOCAL = true the three-group and
+// label-masked fits on concatenated matrices [Y0 Y1] (vbmf_local_fit_batched; src/vbmf_trial.jl:528-604, examples/mil_util.jl:302-320).
 //
 // The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.  fit_stage_kernel copies Y as stored (the
 // pass-2 tiles) ONCE per call into two dense fp32 planes, row-major Yr[l][m] and column-major Yc[m][l], so that each of the two products
@@ -18,8 +19,10 @@
 // The fit leaves the loop when !(d > eps) (a NaN d stops it) or when it met a non-finite precision or a bad pivot (status = 1).
 // State: B, Q (L x H) and PA, CA, dS (M_b x H; P and A share storage) in LDS when they fit under FITB_LDS_CAP, else in the fit's own
 // slices of the scratch buffer.  Every sum's order is fixed by (L, M_b, H): chunked partials folded in chunk order, xor-butterflies over
-// a lane group whose width depends on the row count alone.  No atomics, no hand-off between workgroups.
+// a lane group whose width depends on the row count alone (LOCAL: and by H0, M0 for the per-group sums).  No atomics, no hand-off
+// between workgroups.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 #include "ctrl_kernels.hpp"
 #include "blk_inverse.hpp"
@@ -68,11 +71,19 @@ struct FitArgs {
     int H, H0, niter, compat, spectral, est_cb, est_priors;
     double eps;
     const double* gamma; const double* delta0; const double* eta; const double* zeta0;   // nfits
-    double* priors4;                               // nfits x 4
+    double* priors4;                               // nfits x 4 (FitLocalArgs: nfits x 9)
     double* B; double* SB; double* CB; double* sigma; double* CA;                        // in / out
     double* delta; double* zeta; double* beta; double* dS; double* SA; double* A;       // out
     double* Bw; double* Qw;                        // nfits x L x H each: working B (row-major) and Q for fits whose B is not in LDS
     long long* iters; double* dlast; long long* status; double* trace;
+};
+
+// vbmf_local_fit_batched: the same sweep with two per-entry rules on A (M0[f] = the fit's leading rows, the negative instances)
+//   three prior groups (src/vbmf_trial.jl:357-400)  entry (m, h): group 1 if h < H0, group 2 if m < M0[f], else group 3; `priors4` then
+//                 holds nine doubles per fit in vbmf_trial_get_priors' order (three pairs in/out, the three posterior shapes out)
+//   prefix mask (src/vbmf_sparse.jl:245)            mask_H1 > 0: a(m, h) = 0 for m < M0[f], h >= H - mask_H1, before anything reads it
+struct FitLocalArgs : FitArgs {
+    const long long* M0; int mask_H1;
 };
 
 // sum over the workgroup's 512 threads, lanes first, then the eight waves in order (block_sum of ctrl_kernels.hpp folds the first 256
@@ -238,18 +249,26 @@ __device__ __forceinline__ void fitb_lambda_max(const double* M0, const double* 
     }
 }
 
-template <int NBK, bool FULL>
-__global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
+template <int NBK, bool FULL, bool LOCAL = false>
+__global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditional_t<LOCAL, FitLocalArgs, FitArgs> g) {
     extern __shared__ __attribute__((aligned(16))) double lds_fb[];
     __shared__ double part[1024];
     __shared__ double red[16];
-    __shared__ double v_s[32], al_s[32], b0_s[32], sa_s[32], cb_s[32], dl_s[32], vec_s[64], pri_s[4];
-    __shared__ int bad_s;
+    __shared__ double v_s[32], al_s[32], b0_s[32], sa_s[32], cb_s[32], dl_s[32], vec_s[64];
     constexpr int NP = 16 * NBK, LD = NP + 2, NUP = NBK * (NBK + 1) / 2, NW = FITB_NW;
+    constexpr int NPRI = LOCAL ? 9 : 4, NGS = LOCAL ? 6 : 4;      // doubles of priors per fit; running sums (log beta, CA per group)
+    __shared__ double pri_s[NPRI];
+    __shared__ int bad_s;
     const int f = blockIdx.x, H = g.H, H0 = g.H0, tid = threadIdx.x, h2 = H * H;
     const long long L = g.L, b = g.fit_bag[f], m0 = g.col_off[b], Mb = g.col_off[b + 1] - m0;
     const long long n = Mb * H, o = g.fit_off[f] * H, nb = L * H;
     const int place = fitb_placement(FULL, NBK, L, Mb, H);
+    long long M0f = 0;                                              // LOCAL: rows m < M0f are the fit's negative instances
+    int hmask = H;                                                  // LOCAL: columns h >= hmask of those rows are zeroed
+    if constexpr (LOCAL) {
+        M0f = g.M0[f];
+        hmask = H - g.mask_H1;
+    }
     // dynamic LDS: [images (+ p_m, a_m) | B'B | A'A + SigmaA | SigmaB | dB'dB | eigen 4 H^2 | B, Q | PA, CA, dS]
     double* Wk = lds_fb;                                            // the image of updateB!'s inverse (full_cov: wave 0's)
     double* BB = lds_fb + (fitb_fixed_doubles(FULL, NBK, H) - 8 * h2);
@@ -281,7 +300,8 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
         cb_s[tid] = g.CB[(long long)f * H + tid];
         dl_s[tid] = 0.0;
     }
-    if (tid < 4) pri_s[tid] = g.priors4[(long long)f * 4 + tid];
+    if (tid < NPRI) pri_s[tid] = LOCAL && tid >= 6 ? g.priors4[(long long)f * NPRI + 2 * (tid - 6)] + 0.5
+                                                   : g.priors4[(long long)f * NPRI + tid];
     if (tid == 0) bad_s = 0;
     const double eta = g.eta[f], zeta0 = g.zeta0[f], gam = g.gamma[f], delta0 = g.delta0[f], Lg = (double)L;
     double sig = g.sigma[f], zeta = 0.0, d = g.eps + 1.0;
@@ -320,7 +340,9 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
         fitb_product<NP>(Mb, L, Yr, g.Mtot, Yc, L, Bl, H, PAb);
         __syncthreads();
         int bad = 0;
-        double gs[4] = {0.0, 0.0, 0.0, 0.0};                       // sum log beta, sum CA of the two column groups: this thread's shares
+        double gs[NGS];                                            // sum log beta, sum CA of each prior group: this thread's shares
+#pragma unroll
+        for (int k = 0; k < NGS; ++k) gs[k] = 0.0;
         if constexpr (!FULL) {
             for (long long t = tid; t < n; t += FITB_THREADS) {
                 const long long m = t / H;
@@ -328,6 +350,22 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
                 const long long vi = !g.compat ? h : (t < H ? t : (t - H) / (Mb - 1));   // repeat(v, inner = M_b - 1) after the first H
                 const double prec = v_s[vi] + CAb[t];
                 bad |= !isfinite(prec);
+                if constexpr (LOCAL) {
+                    const double ds = 1.0 / prec, a = (m < M0f && h >= hmask) ? 0.0 : sig * ds * PAb[t];
+                    PAb[t] = a;
+                    dSb[t] = ds;
+                    const int grp = h < H0 ? 0 : (m < M0f ? 1 : 2);
+                    const double be = pri_s[2 * grp + 1] + 0.5 * (a * a + ds), ca = (pri_s[2 * grp] + 0.5) / be;
+                    CAb[t] = ca;
+                    g.beta[o + t] = be;
+                    const double lb = log(be);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        gs[2 * k] += grp == k ? lb : 0.0;
+                        gs[2 * k + 1] += grp == k ? ca : 0.0;
+                    }
+                    continue;
+                }
                 const double ds = 1.0 / prec, a = sig * ds * PAb[t];
                 PAb[t] = a;
                 dSb[t] = ds;
@@ -391,8 +429,25 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
                     const int lo = j < i ? j : i, hi = j < i ? i : j;
                     sm += W[lo * LD + hi] * pvec[j];                    // (pvec is zero beyond H; W is the identity padding there)
                 }
-                const double a = lane < H ? -sig * sm : 0.0;
-                if (lane < H) {
+                const double a = (lane < H && !(LOCAL && m < M0f && lane >= hmask)) ? -sig * sm : 0.0;
+                if constexpr (LOCAL) {
+                    if (lane < H) {
+                        const long long t = m * H + lane;
+                        const double ds = -W[lane * LD + lane];
+                        PAb[t] = a;
+                        dSb[t] = ds;
+                        const int grp = lane < H0 ? 0 : (m < M0f ? 1 : 2);
+                        const double be = pri_s[2 * grp + 1] + 0.5 * (a * a + ds), ca = (pri_s[2 * grp] + 0.5) / be;
+                        CAb[t] = ca;
+                        g.beta[o + t] = be;
+                        const double lb = log(be);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            gs[2 * k] += grp == k ? lb : 0.0;
+                            gs[2 * k + 1] += grp == k ? ca : 0.0;
+                        }
+                    }
+                } else if (lane < H) {
                     const long long t = m * H + lane;
                     const double ds = -W[lane * LD + lane];
                     PAb[t] = a;
@@ -435,7 +490,7 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
         }
         if (g.est_priors) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) gs[k] = fitb_sum(gs[k], red);
+            for (int k = 0; k < NGS; ++k) gs[k] = fitb_sum(gs[k], red);
         }
         // ---- updateB! -----------------------------------------------------------------------------------------------------------
         fitb_chunk_reduce(h2, Mb, part, AA, [&](int e, long long m) { return PAb[m * H + e / H] * PAb[m * H + e % H]; });
@@ -503,9 +558,12 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
         zeta = zeta0 + 0.5 * yy - bq + 0.5 * tr;
         sig = eta / zeta;
         if (g.est_priors && tid == 0) {
-            const double ng[2] = {(double)Mb * (double)H0, (double)Mb * (double)(H - H0)};
-            for (int grp = 0; grp < 2; ++grp) {
+            // group sizes: M H0, M H1 (two groups); M H0, M0 H1, (M - M0) H1 (three: src/vbmf_trial.jl:442-507)
+            const double ng[3] = {(double)Mb * (double)H0, (double)(LOCAL ? M0f : Mb) * (double)(H - H0),
+                                  (double)(Mb - M0f) * (double)(H - H0)};
+            for (int grp = 0; grp < NGS / 2; ++grp) {
                 const double nn = ng[grp];
+                if constexpr (LOCAL) pri_s[6 + grp] = pri_s[2 * grp] + 0.5;   // the posterior shape this sweep's updateCA! used
                 if (!(nn > 0.0)) continue;                          // empty group: nothing to fit
                 const double a_post = pri_s[2 * grp] + 0.5;         // what this sweep's updateCA! used
                 const double y = log(pri_s[2 * grp + 1]) + digamma_dev(a_post) - gs[2 * grp] / nn;
@@ -552,7 +610,7 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(FitArgs g) {
         }
         if (place == 2) g.A[o + t] = PAb[t];                        // (otherwise PAb is the fit's slice of g.A)
     }
-    if (tid < 4) g.priors4[(long long)f * 4 + tid] = pri_s[tid];
+    if (tid < NPRI) g.priors4[(long long)f * NPRI + tid] = pri_s[tid];
     if (tid == 0) {
         g.sigma[f] = sig;
         g.zeta[f] = zeta;

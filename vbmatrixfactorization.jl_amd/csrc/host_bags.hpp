@@ -413,35 +413,21 @@ int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* c
 }  // extern "C"
 
 // ---- many fits in one launch (fit_batch_kernels.hpp) ------------------------------------------------------------------------------
-extern "C" {
-
-// The restart loops of examples/mil_util.jl:124-145,347-379 (and the folds x classes around them) in one call: every fit's whole
-// vbmf_sparse! / vbmf_dual! loop in one workgroup of one launch.  The context supplies Y only; its state is neither read nor changed,
-// so no RunFrame: that frame settles the context's own B buffers and counters, which this call leaves alone.
-int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
-                            double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const double* gamma, const double* delta0,
-                            const double* eta, const double* zeta0, double* priors4, double* BHat, double* SigmaB, double* CB,
-                            double* sigmaHat, double* CA, double* delta, double* zeta, double* beta, double* diagSigmaATVec,
-                            double* SigmaA, double* ATVecHat, int64_t* iters_done, double* d_last, int64_t* status, double* trace) {
-    if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_sparse_fit_batched";
-    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
-    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse and two-group models only)", fn);
-    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run / vbmf_dual_run per fit)", fn);
-    if (c->trial) FAIL(c, VBMF_ERR_INVALID, "%s: trial context (the sparse and two-group models only)", fn);
-    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run per fit)", fn);
-    BagDims bd;
-    TRY(bags_check(c, fn, nbags, col_off, bd));
-    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
-    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
-    if (H0 < 1 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: H0 = %lld outside 1..H = %lld", fn, (long long)H0, (long long)c->H);
-    if (!fit_bag || !gamma || !delta0 || !eta || !zeta0 || !priors4 || !BHat || !SigmaB || !CB || !sigmaHat || !CA || !iters_done ||
-        !d_last || !status)
-        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat and trace may be NULL)", fn);
+// What vbmf_sparse_fit_batched and vbmf_local_fit_batched share once each has refused what it refuses about the context and the scalar
+// arguments: the per-fit checks, the layout of c->bags, the staging, the one launch and the read-back.  M0 = nullptr: the two-group
+// sweep with four priors per fit; else the three-group / masked sweep with nine (M0[f] checked against the fit's own M_b here).
+static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                           int64_t niter, double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const int64_t* M0,
+                           int64_t mask_H1, const double* gamma, const double* delta0, const double* eta, const double* zeta0,
+                           double* priors, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA, double* delta,
+                           double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat, int64_t* iters_done,
+                           double* d_last, int64_t* status, double* trace) {
+    const bool local = M0 != nullptr;
+    const int64_t npri = local ? 9 : 4;
     const bool compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
     const int H = (int)c->H, NBK = nb_tier(H);
     const int64_t L = c->L, nf = nfits, nb = nbags, h2 = (int64_t)H * H, LH = L * H;
-    std::vector<long long> idx((size_t)(nb + 1 + nf + nf + 1));               // col_off | fit_bag | fit_off
+    std::vector<long long> idx((size_t)(nb + 1 + nf + nf + 1 + (local ? nf : 0)));   // col_off | fit_bag | fit_off | M0
     long long* fit_off = idx.data() + nb + 1 + nf;
     fit_off[0] = 0;
     size_t lds_doubles = 0;
@@ -451,9 +437,12 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
         const int64_t Mb = col_off[b + 1] - col_off[b];
         if (!full_cov && compat && Mb < 2)
             FAIL(c, VBMF_ERR_INVALID, "%s: fit %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)f);
+        if (local && (M0[f] < 0 || M0[f] > Mb))
+            FAIL(c, VBMF_ERR_INVALID, "%s: M0[%lld] = %lld outside 0..M_b = %lld", fn, (long long)f, (long long)M0[f], (long long)Mb);
         fit_off[f + 1] = fit_off[f] + Mb;
         lds_doubles = std::max(lds_doubles, (size_t)fitb_lds_doubles(full_cov != 0, NBK, L, Mb, H));
         idx[(size_t)(nb + 1 + f)] = b;
+        if (local) idx[(size_t)(nb + 1 + nf + nf + 1 + f)] = M0[f];
     }
     for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
     if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
@@ -462,22 +451,22 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
     auto run = [&]() -> int {
     HIPCHK(c, hipSetDevice(c->o.device));
     const int64_t SMH = fit_off[nf] * H, nidx = (int64_t)idx.size(), ntr = trace ? 2 * nf * niter : 0, ny = (L * c->M + 1) / 2;
-    // c->bags: [col_off | fit_bag | fit_off (int64) | gamma | delta0 | eta | zeta0 | sigma (nf each) | priors4 4 nf | zeta | d_last | iters
-    //           | status (int64) (nf each) | B | Bw | Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | CB | delta (nf H) | CA | A | dS |
+    // c->bags: [col_off | fit_bag | fit_off | M0 (int64) | gamma | delta0 | eta | zeta0 | sigma (nf each) | priors 4 or 9 nf | zeta | d_last
+    //           | iters | status (int64) (nf each) | B | Bw | Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | CB | delta (nf H) | CA | A | dS |
     //           beta (sum M_b H each) | trace | Yr | Yc (L M floats each)]
-    const int64_t o_sc = nidx, o_pri = o_sc + 5 * nf, o_zeta = o_pri + 4 * nf, o_dl = o_zeta + nf, o_it = o_dl + nf, o_st = o_it + nf,
+    const int64_t o_sc = nidx, o_pri = o_sc + 5 * nf, o_zeta = o_pri + npri * nf, o_dl = o_zeta + nf, o_it = o_dl + nf, o_st = o_it + nf,
                   o_b = o_st + nf, o_bw = o_b + nf * LH, o_qw = o_bw + nf * LH, o_sb = o_qw + nf * LH, o_sa = o_sb + nf * h2,
                   o_cb = o_sa + nf * h2, o_de = o_cb + nf * H, o_ca = o_de + nf * H, o_a = o_ca + SMH, o_ds = o_a + SMH, o_be = o_ds + SMH,
                   o_tr = o_be + SMH, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
     double* d = nullptr;
     TRY(bags_reserve(c, total, &d));
-    in.resize((size_t)(9 * nf));
+    in.resize((size_t)((5 + npri) * nf));
     memcpy(in.data(), gamma, (size_t)nf * 8);
     memcpy(in.data() + nf, delta0, (size_t)nf * 8);
     memcpy(in.data() + 2 * nf, eta, (size_t)nf * 8);
     memcpy(in.data() + 3 * nf, zeta0, (size_t)nf * 8);
     memcpy(in.data() + 4 * nf, sigmaHat, (size_t)nf * 8);
-    memcpy(in.data() + 5 * nf, priors4, (size_t)nf * 4 * 8);
+    memcpy(in.data() + 5 * nf, priors, (size_t)(nf * npri) * 8);
     HIPCHK(c, hipMemcpyAsync(d, idx.data(), (size_t)nidx * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_sc, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_b, BHat, (size_t)(nf * LH) * 8, hipMemcpyHostToDevice, c->stream));
@@ -504,10 +493,18 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
     DISPATCH_NB(NBK, {                                                                                                             \
         hipLaunchKernelGGL((fit_batch_kernel<(NBc > 2 ? 2 : NBc), FULLc_>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a); \
     })
-    if (full_cov) { FITB(true); } else { FITB(false); }
+#define FITB_LOCAL(FULLc_)                                                                                                         \
+    DISPATCH_NB(NBK, {                                                                                                             \
+        hipLaunchKernelGGL((fit_batch_kernel<(NBc > 2 ? 2 : NBc), FULLc_, true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, la); \
+    })
+    if (local) {
+        FitLocalArgs la{a, di + nb + 1 + nf + nf + 1, (int)mask_H1};
+        if (full_cov) { FITB_LOCAL(true); } else { FITB_LOCAL(false); }
+    } else if (full_cov) { FITB(true); } else { FITB(false); }
 #undef FITB
+#undef FITB_LOCAL
     HIPCHK(c, hipGetLastError());
-    // read-back: [priors4 | zeta | d_last | iters | status] is one block; the per-fit matrices and the M H-long fields one block each
+    // read-back: [priors | zeta | d_last | iters | status] is one block; the per-fit matrices and the M H-long fields one block each
     out.resize((size_t)(o_b - o_pri));
     sg.resize((size_t)nf);
     HIPCHK(c, hipMemcpyAsync(out.data(), d + o_pri, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -523,7 +520,7 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
     if (beta) HIPCHK(c, hipMemcpyAsync(beta, d + o_be, (size_t)SMH * 8, hipMemcpyDeviceToHost, c->stream));
     if (trace) HIPCHK(c, hipMemcpyAsync(trace, d + o_tr, (size_t)ntr * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(priors4, out.data(), (size_t)nf * 4 * 8);
+    memcpy(priors, out.data(), (size_t)(nf * npri) * 8);
     if (zeta) memcpy(zeta, out.data() + (o_zeta - o_pri), (size_t)nf * 8);
     memcpy(d_last, out.data() + (o_dl - o_pri), (size_t)nf * 8);
     memcpy(iters_done, out.data() + (o_it - o_pri), (size_t)nf * 8);
@@ -534,6 +531,66 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
     const int rc = run();
     if (rc != VBMF_OK) hipStreamSynchronize(c->stream);
     return rc;
+}
+
+extern "C" {
+
+// The restart loops of examples/mil_util.jl:124-145,347-379 (and the folds x classes around them) in one call: every fit's whole
+// vbmf_sparse! / vbmf_dual! loop in one workgroup of one launch.  The context supplies Y only; its state is neither read nor changed,
+// so no RunFrame: that frame settles the context's own B buffers and counters, which this call leaves alone.
+int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
+                            double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const double* gamma, const double* delta0,
+                            const double* eta, const double* zeta0, double* priors4, double* BHat, double* SigmaB, double* CB,
+                            double* sigmaHat, double* CA, double* delta, double* zeta, double* beta, double* diagSigmaATVec,
+                            double* SigmaA, double* ATVecHat, int64_t* iters_done, double* d_last, int64_t* status, double* trace) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_fit_batched";
+    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse and two-group models only)", fn);
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run / vbmf_dual_run per fit)", fn);
+    if (c->trial) FAIL(c, VBMF_ERR_INVALID, "%s: trial context (the sparse and two-group models only)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run per fit)", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (H0 < 1 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: H0 = %lld outside 1..H = %lld", fn, (long long)H0, (long long)c->H);
+    if (!fit_bag || !gamma || !delta0 || !eta || !zeta0 || !priors4 || !BHat || !SigmaB || !CB || !sigmaHat || !CA || !iters_done ||
+        !d_last || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat and trace may be NULL)", fn);
+    return fit_batched_run(c, fn, nbags, col_off, nfits, fit_bag, niter, eps, full_cov, est_cb, est_priors, H0, nullptr, 0, gamma, delta0,
+                           eta, zeta0, priors4, BHat, SigmaB, CB, sigmaHat, CA, delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat,
+                           iters_done, d_last, status, trace);
+}
+
+// The three-group fit (vbmf_trial!, src/vbmf_trial.jl:528-604) and the label-masked sparse fit (train_local, examples/mil_util.jl:302-320)
+// of many [Y0 Y1] matrices in one call: vbmf_sparse_fit_batched's launch with a per-fit M0 and the two per-entry rules of FitLocalArgs.
+int vbmf_local_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
+                           double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const int64_t* M0, int64_t mask_H1,
+                           const double* gamma, const double* delta0, const double* eta, const double* zeta0, double* priors9,
+                           double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA, double* delta, double* zeta,
+                           double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat, int64_t* iters_done, double* d_last,
+                           int64_t* status, double* trace) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_local_fit_batched";
+    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse, two-group and three-group models only)", fn);
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_trial_run / vbmf_sparse_run per fit)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set on the context (the call's own M0 / mask_H1 describe the mask)", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (H0 < 0 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: H0 = %lld outside 0..H = %lld", fn, (long long)H0, (long long)c->H);
+    if (mask_H1 < 0 || mask_H1 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: mask_H1 = %lld outside 0..H = %lld", fn, (long long)mask_H1, (long long)c->H);
+    if (mask_H1 > 0 && (H0 != c->H || est_priors))
+        FAIL(c, VBMF_ERR_INVALID, "%s: mask_H1 > 0 needs H0 = H and est_priors = 0 (the masked model has one prior group and no hyper-prior fit)", fn);
+    if (!fit_bag || !M0 || !gamma || !delta0 || !eta || !zeta0 || !priors9 || !BHat || !SigmaB || !CB || !sigmaHat || !CA || !iters_done ||
+        !d_last || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat and trace may be NULL)", fn);
+    return fit_batched_run(c, fn, nbags, col_off, nfits, fit_bag, niter, eps, full_cov, est_cb, est_priors, H0, M0, mask_H1, gamma, delta0,
+                           eta, zeta0, priors9, BHat, SigmaB, CB, sigmaHat, CA, delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat,
+                           iters_done, d_last, status, trace);
 }
 
 }  // extern "C"

@@ -1657,6 +1657,11 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        // ... and their three-group / masked twins (vbmf_local_fit_batched)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess && c->NH == 4)

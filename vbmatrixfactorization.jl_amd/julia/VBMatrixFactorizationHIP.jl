@@ -11,7 +11,7 @@
 module VBMatrixFactorizationHIP
 
 export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, updateCB!, updateSigma2!, updateYHat!,
-       vbls!, vbls_batch!, vbmf_batch!, vbmf_sparse_batch!, vbmf_dual_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
+       vbls!, vbls_batch!, vbmf_batch!, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
@@ -709,8 +709,12 @@ end
 # ---- many fits in ONE device call: the restart loops of examples/mil_util.jl:124-145 (train) and :347-379 (train_dual) -------------
 # Fit f works on bag bag_of[f] (1-based), so restarts share one upload; every fit's whole `while i <= niter && d > eps` loop runs in
 # one workgroup of one launch (vbmf_sparse_fit_batched).  pri: 4 x nfits = alpha00, beta00, alpha01, beta01 per fit.
+# With M0 (one entry per fit: the leading columns of its bag that are the negative instances) the call is vbmf_local_fit_batched: pri is
+# 9 x nfits in vbmf_trial_get_priors' order, H0 splits the columns into prior groups 1 and 2 / 3, mask_H1 > 0 holds the last mask_H1
+# columns of A at zero in the rows 1:M0.
 function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int, eps::Float64, full_cov::Bool, est_cb::Bool,
-                        est_priors::Bool, H0::Int, pri::Matrix{Float64}, bag_of::Vector{Int}, variant::Int)
+                        est_priors::Bool, H0::Int, pri::Matrix{Float64}, bag_of::Vector{Int}, variant::Int;
+                        M0::Union{Nothing,Vector{Int64}} = nothing, mask_H1::Int = 0)
     nb, nf = length(Ys), length(ps)
     (nb >= 1 && nf >= 1 && length(bag_of) == nf) || error("$fn: one bag_of entry per parameter set")
     niter >= 1 || error("$fn: niter must be >= 1")
@@ -740,6 +744,7 @@ function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int,
     it = zeros(Int64, nf); dlast = Array{Float64}(undef, nf); st = zeros(Int64, nf)
     try
         chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        if M0 === nothing
         chk(h[], ccall((:vbmf_sparse_fit_batched, libvbmf), Cint,
             (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Float64}, Ptr{Float64},
              Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
@@ -747,6 +752,15 @@ function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int,
              Ptr{Float64}),
             h[], nb, off, nf, fb, niter, eps, full_cov, est_cb, est_priors, H0, ga, d0, eta, z0, pri, B, SB, cb, sg, ca, dl, ze, be, ds,
             SA, a, it, dlast, st, C_NULL))
+        else
+        chk(h[], ccall((:vbmf_local_fit_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Int64}, Int64, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64},
+             Ptr{Int64}, Ptr{Float64}),
+            h[], nb, off, nf, fb, niter, eps, full_cov, est_cb, est_priors, H0, M0, mask_H1, ga, d0, eta, z0, pri, B, SB, cb, sg, ca, dl,
+            ze, be, ds, SA, a, it, dlast, st, C_NULL))
+        end
     finally
         ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
     end
@@ -1122,6 +1136,48 @@ function vbmf_trial!(Y::Array{Float64,2}, p::vbmf_trial_parameters, niter::Int; 
     p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')                                       # :590
     verb && print("Factorization finished after ", iters[], " iterations, eps = ", d[], "\n")
     return d[]
+end
+
+# ---- many fits on concatenated matrices [Y0 Y1] in ONE device call (vbmf_local_fit_batched) ------------------------------------------
+"""
+vbmf_trial! for many independent fits in ONE device call (src/vbmf_trial.jl:528-604): see vbmf_sparse_batch!; all fits share one H0,
+M0 is per fit; est_priors refits the three (alpha0g, beta0g) pairs every sweep (:442-507).  Fills what vbmf_trial! fills.
+"""
+function vbmf_trial_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_trial_parameters}, niter::Int; eps::Float64 = 1e-6,
+                           full_cov::Bool = false, est_cb::Bool = true, est_priors::Bool = true,
+                           bag_of::Vector{Int} = collect(1:length(ps)))
+    H0 = ps[1].H0
+    all(p.H0 == H0 for p in ps) || error("vbmf_trial_batch!: one H0 per call")
+    all(0 <= p.M0 <= p.M for p in ps) || error("vbmf_trial_batch!: M0 outside 0..M")
+    pri = Float64[(p.alpha01, p.beta01, p.alpha02, p.beta02, p.alpha03, p.beta03, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
+    out = fit_batch_run!("vbmf_trial_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri, bag_of, 4;
+                         M0 = Int64[p.M0 for p in ps])
+    for (f, p) in enumerate(ps)
+        p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, 1:p.H0], p.AHat[1:p.M0, p.H0+1:end], p.AHat[p.M0+1:end, p.H0+1:end]
+        p.CA1, p.CA2, p.CA3 = trial_split(p.CA, p.M, p.H, p.H0, p.M0)
+        p.beta1, p.beta2, p.beta3 = trial_split(p.beta, p.M, p.H, p.H0, p.M0)
+        p.alpha01, p.beta01, p.alpha02, p.beta02, p.alpha03, p.beta03, p.alpha1, p.alpha2, p.alpha3 = pri[:, f]
+        p.alpha = [p.alpha1, p.alpha2, p.alpha3]
+    end
+    return out
+end
+
+"""
+vbmf_sparse! with a label mask for many independent fits in ONE device call (the fit of train_local, examples/mil_util.jl:302-320, on
+Y = [Y0 Y1]): see vbmf_sparse_batch!.  The labels of every fit are exactly 1:M0 (possibly empty; M0 per fit) and all fits share one H1:
+the last H1 columns of AHat stay zero in the rows 1:M0 (src/vbmf_sparse.jl:245).  Any other label set: vbmf_sparse! per fit.
+"""
+function vbmf_sparse_masked_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; eps::Float64 = 1e-6,
+                                   full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)))
+    H1 = ps[1].H1
+    for (f, p) in enumerate(ps)
+        (p.H1 == H1 && 0 <= H1 <= p.H) || error("vbmf_sparse_masked_batch!: one H1 in 0..H per call")
+        (length(p.labels) <= p.M && p.labels == collect(1:length(p.labels))) ||
+            error("vbmf_sparse_masked_batch!: the labels of fit $f are not the prefix 1:M0; use vbmf_sparse! per fit")
+    end
+    pri = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0, p.alpha0, p.beta0, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
+    return fit_batch_run!("vbmf_sparse_masked_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri, bag_of, 1;
+                          M0 = Int64[length(p.labels) for p in ps], mask_H1 = H1)
 end
 
 end # module
