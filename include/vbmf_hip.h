@@ -297,7 +297,15 @@ int vbmf_local_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off,
                            double* delta, double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
                            int64_t* iters_done, double* d_last, int64_t* status, double* trace);
 int vbmf_sparse_step(vbmf_ctx* ctx, int which);           /* reference order A, B, CA, CB, SIGMA (:369-376) */
-/* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0) */
+/* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0)
+ * Gram form.  A VBMF_VARIANT_SPARSE_DIAG context with full_cov off, one rank, bf16 Y, bf16x2 factors and
+ * H <= 128 iterates on G = Y'Y instead of streaming Y twice per sweep under the size rule of vbmf_run (L >= 4 M and L M >= 2^27), or
+ * at any size when it was created under VBMF_GRAM=2 (VBMF_GRAM=1 forces the basic model only; VBMF_GRAM=0 and every other sparse
+ * context -- the grouped models, diag_var, full_cov, H > 128, row shards, fp32 storage -- keep the streaming sweep).  In that form B = Y W with W = sigmaHat A SigmaB: the first sweep
+ * of a run that holds no W streams Y and forms W, the later ones read G only, and W is carried from run to run.  Before the run returns,
+ * BHat of the last executed sweep is formed by one streaming pass, so vbmf_sparse_get_state, the lower bounds and a following run see
+ * what a streaming run leaves, and run(3) + run(3) computes what run(6) computes.  vbmf_sparse_set_state, vbmf_set_Y*,
+ * vbmf_sparse_step, vbmf_sparse_run_fixed_basis, vbmf_sparse_set_full_cov and a failed run drop W: the next run starts by streaming. */
 int vbmf_sparse_run(vbmf_ctx* ctx, int64_t niter, double eps, int est_cb, int64_t* iters_done, double* d_last,
                     double* trace);
 /* lowerBound (src/vbmf_sparse.jl:435-471), verbatim quirks QS4; H(B) as L*logdet(SigmaB), clamped like
@@ -451,7 +459,7 @@ int vbmf_device_sync(vbmf_ctx* ctx);
 #define VBMF_PEEK_FB 5     /* BHat MFMA operand tiles */
 #define VBMF_PEEK_Y1 6     /* Y tiled for pass 1 */
 #define VBMF_PEEK_Y2 7     /* Y tiled for pass 2 */
-#define VBMF_PEEK_DIMS 8   /* int32 x 28: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
+#define VBMF_PEEK_DIMS 8   /* int32 x 28: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run / vbmf_sparse_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
                               p_frag / q_frag (the last pass 1 / pass 2 launch wrote its product fragment-major: [XT][NH][64][16]),
                               q_epi (the last pass 2 launch ran the register epilogue and stored no product), lds8 (H >= 128 bf16x2
                               passes run the LDS-DMA kernel), xcd_map (split-K launches use the XCD-aware work map), post3 (H >= 128

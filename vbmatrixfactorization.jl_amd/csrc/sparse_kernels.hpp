@@ -132,6 +132,72 @@ __global__ __launch_bounds__(256) void sparse_update_a_tiles_kernel(const float*
     }
 }
 
+// The same update for the Gram-form sweep (vbmf_hip.hip, sparse_gram_sweep): P = G W arrives in the
+// fragment-major layout gram_prod writes (post_kernels.hpp, frag_index) -- the block (row tile xt, column tile h) is 4 KiB contiguous,
+// lane (half, c) owns 64 bytes of it: P[h*32 + rho(r, half)][x0 + c], r = 0..15 -- so the block comes in as four 16-byte loads per lane.
+// That is the product's accumulator tile (row h, column m), the transpose of the tile write_factor_tiles takes (row m, column h).  The
+// turn is 16 exact-f32 MFMAs (k = 2) against the identity, the contraction of post_gram_tile_regs with I for the table: every output
+// element is one value times 1.0 plus zeros, so it is the stored fp32 value bit for bit.  No LDS, no barrier; one wave per block.
+// Homoscedastic only (the Gram form has no row-noise variant): sigmaHat multiplies diagSigma .* P.
+template <int MODE, int NH>
+__global__ __launch_bounds__(256) void sparse_update_a_frag_kernel(const float4* __restrict__ P4, const float* __restrict__ CA32,
+                                                                   const double* __restrict__ v, const double* __restrict__ st,
+                                                                   StateLayout lay, float* __restrict__ A32, float* __restrict__ dS32,
+                                                                   uint4* __restrict__ Ft, const unsigned char* __restrict__ mask,
+                                                                   int hmask_start, long long M, int H, int compat, int XT,
+                                                                   const int* __restrict__ stop) {
+    constexpr int Hp = NH * 32;
+    if (stop && *stop) return;
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int wv = blockIdx.x * 4 + wib;
+    const int xt = wv / NH, h = wv % NH;
+    if (xt >= XT) return;
+    const int c = lane & 31, half = lane >> 5;
+    const long long x0 = (long long)xt * 32;
+    const double sig = st[lay.scal() + S_SIGMA2];
+    const float4* src = P4 + (((long long)xt * NH + h) * 64 + lane) * 4;
+    float4 pv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pv[j] = src[j];
+    f32x16 p;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) p[r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float q[4] = {pv[j].x, pv[j].y, pv[j].z, pv[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int t = 4 * j + e;
+            p = __builtin_amdgcn_mfma_f32_32x32x2f32(q[e], rho(t, half) == c ? 1.f : 0.f, p, 0, 0, 0);
+        }
+    }
+    // p[r] on lane (half, c) = P[h*32 + c][x0 + rho(r, half)]: lane = column h of A, registers = rows m
+    const int hcol = h * 32 + c;
+    f32x16 a, ds;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long long m = x0 + rho(r, half);
+        float av = 0.f, dv = 0.f;
+        if (m < M && hcol < H) {
+            const long long pos = m * H + hcol;                                // 0-based position in vec(A')
+            long long vi = hcol;
+            if (compat) vi = (pos < H) ? pos : (pos - H) / (M - 1);            // repeat(v, inner = M-1) after the first H
+            const double prec = v[vi] + (double)CA32[m * Hp + hcol];
+            const double dd = 1.0 / prec;
+            dv = (float)dd;
+            av = (float)(sig * dd * (double)p[r]);
+            if (mask != nullptr && hcol >= hmask_start && mask[m]) av = 0.f;
+        }
+        a[r] = av; ds[r] = dv;
+    }
+    write_factor_tiles<MODE, NH>(Ft, a, xt, h, lane);                           // a := the value the tiles encode
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long long m = x0 + rho(r, half);
+        if (m < M) { A32[m * Hp + hcol] = a[r]; dS32[m * Hp + hcol] = ds[r]; }
+    }
+}
+
 // dst[x][h] = sqrt(w[x]) * src[x][h]: B' diag(w) B is then the plain Gram of dst (full_cov with diag_var, :180-182)
 __global__ void sqrt_rowscale_kernel(const float* __restrict__ src, const float* __restrict__ w, float* __restrict__ dst,
                                      long long n, int Hp, const int* __restrict__ stop) {

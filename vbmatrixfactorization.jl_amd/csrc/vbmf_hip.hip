@@ -19,7 +19,8 @@
 // without a per-sweep synchronisation and the state still freezes at the reference's iteration.
 //
 // Tall matrices (gram_eligible): vbmf_run takes the Gram form instead -- B = Y W with W = A SigmaB / sigma2, so a sweep reads the
-// M x M matrix G = Y'Y (built once per Y) in place of Y (gram_kernels.hpp).
+// M x M matrix G = Y'Y (built once per Y) in place of Y (gram_kernels.hpp); so does vbmf_sparse_run for the
+// diagonal homoscedastic ARD-sparse model (sparse_gram_sweep).
 //
 // vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): ONE pass 1 with the frozen B over the bags side by side,
 // then bag_gram (S_b = P_b'P_b, ||Y_b||^2), vbls_batch (all iterations, one workgroup per bag) and bag_a (A_b = P_b SigmaA_b / sigma2_b).
@@ -173,7 +174,7 @@ struct vbmf_ctx {
     double* bags = nullptr;           // the many-bags entries (host_bags.hpp): per-bag inputs, partials and outputs of the call in
     size_t bags_bytes = 0;            // flight, each entry in its own layout (grown on demand)
     // Gram-form sweep of vbmf_run (gram_kernels.hpp); buffers allocated by the first run that takes it
-    int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows
+    int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows (basic model), 2 the sparse model too
     int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
     int g_nsplit = 1, g_sps = 0, g_nrg = 0, g_nchunk = 0, g_rpc = 0;
     float* Gt = nullptr;              // G = Y'Y as fp32 MFMA operand fragments [GT][2 GT][64][8]
@@ -1023,13 +1024,17 @@ static int do_update_B(vbmf_ctx* c, bool keep_sigma = false) {
 // Taken by vbmf_run when the structure allows it (basic variant, one rank, bf16 Y, bf16x2 factors, Hp <= 128) and Y is tall enough
 // for building G = Y'Y once to pay: L >= 4 M and L M >= 2^27 (below that a streaming pass costs a few launch latencies).
 // VBMF_GRAM=0 turns it off, VBMF_GRAM=1 on whenever the structure allows.
+// The ARD-sparse model's diagonal homoscedastic branch (vbmf_sparse_run, sparse_gram_sweep below) has the same structure -- nothing on
+// the B side is masked, B = Y W with W = sigmaHat A SigmaB -- and follows the same size rule (measured at 100k x 10k: 2.7x the streaming
+// sweep at H = 64, 2.1x at H = 128).  It is forced on by VBMF_GRAM=2, which forces the basic model too; VBMF_GRAM=1
+// forces the basic model only and leaves a sparse context to the size rule.
 static bool gram_structural(const vbmf_ctx* c) {
-    return !c->sparse && !c->diagvar && !c->dual && !c->trial && !sharded(c) && c->o.nranks == 1 && c->o.y_dtype == VBMF_Y_BF16 &&
+    return !c->diagvar && !c->dual && !c->trial && !c->full_cov && !sharded(c) && c->o.nranks == 1 && c->o.y_dtype == VBMF_Y_BF16 &&
            c->mode == MODE_BF16X2 && c->Hp <= 128;
 }
 static bool gram_eligible(const vbmf_ctx* c) {
     if (c->gram_env == 0 || !gram_structural(c)) return false;
-    if (c->gram_env == 1) return true;
+    if (c->gram_env == 2 || (c->gram_env == 1 && !c->sparse)) return true;
     return c->L >= 4 * c->M && (double)c->L * (double)c->M >= 134217728.0;
 }
 
@@ -1456,7 +1461,10 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
     if (c->Hp > 128 && c->Hp < 256) c->Hp = 256;
     c->NH = c->Hp / 32;
     if (const char* e = getenv("VBMF_XCD_MAP")) c->xcd_map = atoi(e) != 0;      // A/B switch for the tuning record
-    if (const char* e = getenv("VBMF_GRAM")) c->gram_env = atoi(e) != 0 ? 1 : 0;  // Gram-form sweep: force off / on (gram_eligible)
+    if (const char* e = getenv("VBMF_GRAM")) {          // Gram-form sweep: force off / on / on for the ARD-sparse model too (gram_eligible)
+        const int v = atoi(e);
+        c->gram_env = v == 0 ? 0 : (v == 2 ? 2 : 1);
+    }
     if (const char* e = getenv("VBMF_EPI_BALANCE")) c->epi_balance = atoi(e) != 0;
     if (const char* e = getenv("VBMF_LDS8")) c->lds8 = atoi(e) != 0;
     if (const char* e = getenv("VBMF_POST3")) c->post3 = atoi(e) != 0;
@@ -2755,13 +2763,14 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
     return VBMF_OK;
 }
 
-static int do_sparse_update_B(vbmf_ctx* c) {
+// keep_sigma: B from the sigmaHat SigmaB table already in place (the end of a Gram-form run materialises B with the last sweep's table)
+static int do_sparse_update_B(vbmf_ctx* c, bool keep_sigma = false) {
     TRY(ensure_gram_A(c));
-    if (side_overlap(c)) {                          // SigmaB beside the pass: only the post kernel needs it
+    if (!keep_sigma && side_overlap(c)) {           // SigmaB beside the pass: only the post kernel needs it
         TRY(side_fork(c));
         TRY(launch_sparse_cov_b(c));
         TRY(side_end(c));
-    } else {
+    } else if (!keep_sigma) {
         TRY(launch_sparse_cov_b(c));
     }
     // fragment-major product: H <= 64 always (folded element-wise when split), H >= 128 when un-split; the row-noise update
@@ -2844,6 +2853,43 @@ static int launch_sparse_ctrl_end(vbmf_ctx* c, int flags, double eps, double* tr
     hipLaunchKernelGGL(sparse_ctrl_end_kernel, dim3(1), dim3(c->H > 64 ? 1024 : 256), 0, ctrl_stream(c), c->st, c->lay, (int)c->H, (double)c->Lg, flags, eps, trace, c->ints,
                        t2_ahead ? (const double*)c->t2part : (const double*)nullptr);
     HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
+// One sweep of the diagonal homoscedastic model from P = Y'B_old = G W_old (in gPQ) and the state's B'B = W'P:
+// v, the A update straight from the fragment-major P (label mask, operand tiles), A'A, SigmaA, SigmaB with its sigmaHat SigmaB table, then
+// W_new = A (sigmaHat SigmaB), [P | Q] = G [W_new | W_new - W_old] and the state's [B'B | dB'dB | tr(B'YA)] from them.  Y is not read.
+// updateCA!, lambda_max and the closing control step follow in sparse_run_impl, as after a streaming sweep.
+static int sparse_gram_sweep(vbmf_ctx* c) {
+    const int* stop = c->ints + I_STOP;
+    hipLaunchKernelGGL(sparse_v_kernel, dim3((c->Hp + 63) / 64), dim3(64), 0, c->stream, c->st, c->lay, (int)c->H, (double)c->Lg, c->vtab,
+                       (const double*)nullptr, stop);
+    const int compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) ? 1 : 0;
+    if (compat && c->M < 2) FAIL(c, VBMF_ERR_INVALID, "repeat(v, inner=M-1) needs M >= 2");
+    const float4* P4 = reinterpret_cast<const float4*>(c->gPQ);
+    const unsigned char* mk = c->has_mask ? c->mask : nullptr;
+    const int hstart = (int)(c->H - c->H1);
+    const dim3 grid((c->d1.XT * c->NH + 3) / 4);
+#define SPARSE_A_FRAG(NHc_)                                                                                                          \
+    hipLaunchKernelGGL((sparse_update_a_frag_kernel<MODE_BF16X2, NHc_>), grid, dim3(256), 0, c->stream, P4, c->CA32, c->vtab, c->st,  \
+                       c->lay, c->A32, c->dS32, c->FA, mk, hstart, (long long)c->M, (int)c->H, compat, c->d1.XT, stop)
+    if (c->NH == 1) SPARSE_A_FRAG(1);
+    else if (c->NH == 2) SPARSE_A_FRAG(2);
+    else if (c->NH == 4) SPARSE_A_FRAG(4);
+    else FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 128");
+#undef SPARSE_A_FRAG
+    HIPCHK(c, hipGetLastError());
+    c->P_frag = true;
+    c->frag_last[0] = true;                         // test surface: this sweep's Y'B was the fragment-major G W, not a pass over Y
+    TRY(launch_gram(c, 0, c->A32, nullptr, true));
+    TRY(sparse_colsum(c));                          // SigmaA = diag(sum_m diagSigma)
+    TRY(launch_sparse_cov_b(c));
+    TRY(gram_product(c, true));
+    c->wcur ^= 1;
+    c->gA_valid = c->gB_valid = true;
+    c->P_valid = false;
+    c->Q_valid = false;
+    c->tr_valid = true;
     return VBMF_OK;
 }
 
@@ -2934,6 +2980,7 @@ int vbmf_sparse_set_state(vbmf_ctx* c, const double* ATVecHat, const double* dia
     c->have_noise = false;
     c->B32_stale = false;
     c->haveState = true;
+    c->W_valid = false;                                // B is no longer Y W: the next run starts by the streaming path
     return VBMF_OK;
 }
 
@@ -2972,6 +3019,7 @@ int vbmf_sparse_step(vbmf_ctx* c, int which) {
         FAIL(c, VBMF_ERR_INVALID, "VBMF_SSTEP_PRIORS needs the group sums of VBMF_SSTEP_CA in the same call");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c, (which & (VBMF_SSTEP_A | VBMF_SSTEP_B | VBMF_SSTEP_SIGMA)) != 0));
+    c->W_valid = false;
     if (which & VBMF_SSTEP_A) TRY(do_sparse_update_A(c));
     if (which & VBMF_SSTEP_B) TRY(do_sparse_update_B(c));
     if (which & VBMF_SSTEP_CA) TRY(sparse_update_CA(c));
@@ -3000,6 +3048,7 @@ int vbmf_sparse_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
     if (niter < 0 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "bad niter");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c));
+    c->W_valid = false;
     for (int64_t it = 0; it < niter; ++it) {
         TRY(do_sparse_update_A(c, true));
         TRY(sparse_update_CA(c));
@@ -3024,6 +3073,11 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
     RunFrame run{c, niter, eps, iters_done, d_last, trace};
     TRY(run.open());
     if (niter == 0) return VBMF_OK;
+    // Gram form: G = Y'Y is built here once per Y; a run that starts without a valid W does its first sweep
+    // by the streaming path
+    const bool gram = gram_eligible(c);
+    if (gram) TRY(gram_prepare(c));
+    else c->W_valid = false;
     TRY(run.arm());
     int rc = ensure_gram_B(c);
     if (rc == VBMF_OK) rc = launch_eig(c, 0, 1);
@@ -3031,13 +3085,25 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         hipLaunchKernelGGL(copy_scalar_kernel, dim3(1), dim3(1), 0, c->stream, c->st, c->lay, (int)S_LAMB_PREV, (int)S_LAMB_NEW);
     // diag_var: the rows' noise update (:308-315) replaces the scalar one and runs before the stop test of the sweep
     const int flags = (est_cb ? 2 : 0) | (c->diagvar ? 0 : 4 | 16) | 8;
-    const int bstart = c->bcur;
+    const int bstart = c->bcur, wstart = c->wcur;
+    int64_t stream_sweeps = 0;                             // sweeps enqueued by the streaming path (Gram form: at most the first)
     int64_t it = 0;
     bool stopped = false;
     c->in_run = true;
     while (rc == VBMF_OK && it < niter && !stopped) {
-        rc = do_sparse_update_A(c);
-        if (rc == VBMF_OK) rc = do_sparse_update_B(c);
+        if (gram && c->W_valid) {
+            rc = sparse_gram_sweep(c);
+        } else {
+            rc = do_sparse_update_A(c);
+            if (rc == VBMF_OK) rc = do_sparse_update_B(c);
+            ++stream_sweeps;
+            if (rc == VBMF_OK && gram) {
+                // W of this sweep and P = G W for the next one; the Grams of this sweep came from the B update
+                rc = gram_product(c, false);
+                c->wcur ^= 1;
+                c->W_valid = true;
+            }
+        }
         // updateCA! reads what the A update left and writes what the NEXT A update reads: with a side stream (H > 128) it runs there too,
         // beside the next sweep's Y'B pass, instead of 13 us between the sweeps (not with the group priors or the row noise behind it)
         const bool ca_on_side = side_overlap(c) && !est_priors && !c->diagvar;
@@ -3062,9 +3128,33 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
             if (c->ints_host[I_STOP] || (!sharded(c) && c->ints_host[I_ERR])) stopped = true;   // (see vbmf_run)
         }
     }
-    rc = run.finish(rc, bstart, niter);                    // every sweep moves B
+    // every streaming sweep moves B; in the Gram form only the streaming sweep (the first, if any) does, and every sweep moves W
+    rc = run.finish(rc, bstart, gram ? stream_sweeps : niter);
     c->Q_valid = false;
     c->tr_valid = !c->diagvar;
+    int64_t gram_done = 0;                                 // Gram-form sweeps the device executed
+    if (gram && run.done >= 0) {
+        c->wcur = wstart ^ (int)(run.done & 1);
+        gram_done = run.done - std::min<int64_t>(run.done, stream_sweeps);
+    }
+    if (gram && rc != VBMF_OK) c->W_valid = false;
+    if (gram && rc == VBMF_OK && gram_done > 0) {
+        // B of the last executed sweep, eagerly, by the streaming pass 2 with that sweep's A and sigmaHat SigmaB table (in place): B, its
+        // operand tiles and the fp32 copy as a streaming run leaves them.  The state's [B'B | dB'dB | tr(B'YA)] stay the Gram form's, so
+        // a run that continues from here computes what one longer run computes.
+        const size_t nsave = 2 * (size_t)c->Hp * c->Hp + 8;
+        hipError_t e = hipMemcpyAsync(c->gsave, c->st + c->lay.GB(), nsave * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) rc = do_sparse_update_B(c, true);
+        else { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+        if (rc == VBMF_OK) {
+            e = hipMemcpyAsync(c->st + c->lay.GB(), c->gsave, nsave * 8, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+        }
+        if (rc == VBMF_OK) rc = check_device_err(c);
+        if (rc != VBMF_OK) c->W_valid = false;
+        c->Q_valid = false;
+    }
     return rc;
 }
 
@@ -3093,6 +3183,7 @@ int vbmf_sparse_set_full_cov(vbmf_ctx* c, int on) {
         HIPCHK(c, hipMemsetAsync(c->gw, 0, bytes, c->stream));
     }
     c->full_cov = on != 0;
+    c->W_valid = false;                                // (full_cov on: the context leaves the Gram form, gram_structural)
     return VBMF_OK;
 }
 
