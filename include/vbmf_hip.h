@@ -180,6 +180,38 @@ int vbmf_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64
                      double* AHat, double* SigmaA,
                      int64_t* iters_done, double* d_last, int64_t* status, double* trace);
 
+/* vbmf_fit_batched_form: vbmf_fit_batched with a choice of how a fit's sweep takes what it needs from Y.  updateA! of the basic model
+ * is A = Y'B SigmaA / sigma2 with no mask (src/vbmf.jl:95-98), so after any sweep A = Y'V with V = B SigmaA / sigma2 (L x H), and
+ * updateB!, updateCA! and updateSigma2! (src/vbmf.jl:95-157) need only K = Y Y' (L x L): Y A = K V, A'A = V'K V,
+ * tr(B'Y A) = sum B o (K V), ||Y||^2 = tr K.  The same iteration, 2 L^2 H flops per sweep instead of 4 L M_b H: the form for WIDE bags.
+ * K is built once per bag (fits that share a bag share it), A is formed once after the loop.
+ *   form = VBMF_FIT_FORM_STREAM (0)  every fit streams Y_b twice per sweep: every output is bit-identical to vbmf_fit_batched
+ *   form = VBMF_FIT_FORM_GRAM (1)    every fit iterates on K.  Its state is 3 L H doubles of LDS behind a fixed part F; when
+ *        3 L H > VBMF_FIT_LDS_CAP_BYTES / 8 - F the call returns VBMF_ERR_UNSUPPORTED before any launch.
+ *        F = P (P + 2) + 9 H^2 with P = 16 for H <= 16 and P = 32 for H <= 32
+ *   form = VBMF_FIT_FORM_AUTO (2)    per fit: the Gram form when M_b >= VBMF_FIT_GRAM_WIDE_FACTOR * L and its state fits, else the
+ *        streaming form -- a function of (L, M_b, H) alone, so a fit's numbers depend neither on its place in the call nor on the
+ *        other fits in it
+ * Any other form returns VBMF_ERR_INVALID before a launch.  form_used (nfits, may be NULL): 0 / 1 per fit, the form it ran in.
+ * Both forms run the reference's updates in the reference's order in fp64 on Y as stored; they differ by rounding only. */
+#define VBMF_FIT_FORM_STREAM 0
+#define VBMF_FIT_FORM_GRAM 1
+#define VBMF_FIT_FORM_AUTO 2
+#define VBMF_FIT_GRAM_WIDE_FACTOR 2
+#define VBMF_FIT_LDS_CAP_BYTES 147456
+int vbmf_fit_batched_form(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                          int64_t niter, double eps, int est_covs, int est_var,
+                          double* BHat, double* SigmaB, double* CA, double* CB, double* sigma2,
+                          double* AHat, double* SigmaA,
+                          int64_t* iters_done, double* d_last, int64_t* status, double* trace,
+                          int64_t form, int64_t* form_used);
+
+/* K_b = Y_b Y_b' of every bag in fp64 on Y as stored (bags side by side as in vbmf_fit_batched; any variant, no state needed):
+ * K holds nbags blocks of L x L doubles, each symmetric bit for bit and a function of (L, M_b) and the bag's data alone.  What
+ * vbmf_fit_batched_form iterates on; callers of ols / rls (examples/mil_util.jl:159-171) form B'K_b B from it.
+ * VBMF_ERR_INVALID before any launch: nranks > 1, a bad col_off, K NULL, no Y. */
+int vbmf_bags_row_gram(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, double* K);
+
 /* The vbmf! loop (src/vbmf.jl:187-214): while i <= niter && d > eps { A; B; [CA; CB]; [sigma2]; d }.
  * Runs entirely on the device; the stop test is evaluated device-side so the state freezes exactly
  * where the reference would stop.  iters_done = i-1 (src/vbmf.jl:221), d_last = last d.

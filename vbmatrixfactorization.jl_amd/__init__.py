@@ -47,7 +47,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_trial_parameters", "vbmf_trial_init", "vbmf_trial", "vbmf_trial_", "lowerBound_trial", "trial_updateA_",
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
            "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags", "vbmf_sparse_batch_", "vbmf_dual_batch_", "fit_restarts",
-           "vbmf_batch_", "train_folds", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
+           "vbmf_batch_", "train_folds", "row_gram_batch", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
@@ -1539,16 +1539,20 @@ def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, ful
     return ps[-1]
 
 
-def vbmf_batch_(Ys, params, niter, eps=1e-6, est_covs=False, est_var=False, bag_of=None):
+def vbmf_batch_(Ys, params, niter, eps=1e-6, est_covs=False, est_var=False, bag_of=None, form="stream"):
     """vbmf! for many independent fits of the basic model in one device call: does what [vbmf_(Ys[bag_of[f]], p, niter, eps=eps,
     est_covs=est_covs, est_var=est_var) for f, p in enumerate(params)] does (the two fits of examples/mil_util.jl:110-114, and the
     folds around them) -- fills on every p AHat, BHat, SigmaA, SigmaB (rebound), the diagonals of CA and CB (in place), invCA, invCB,
     sigma2 and YHat (under YHAT_AUTO_LIMIT), plus p.iters (sweeps run), p.d (the last d) and p.status (1: the fit met a non-finite
     sigma2, a CA / CB entry that is not positive, or a bad pivot, and stopped) -- and returns the list of params.  Ys: a list of
     L x M_b arrays or a Bags; params: one vbmf_parameters per fit, one H <= 32, no labels; bag_of[f]: the fit's bag (default: fit f on
-    bag f).  Every fit's whole loop runs in fp64 in one workgroup of one launch (include/vbmf_hip.h, vbmf_fit_batched)."""
+    bag f).  Every fit's whole loop runs in fp64 in one workgroup of one launch (include/vbmf_hip.h, vbmf_fit_batched).
+    form: "stream" (Y is read twice per sweep), "gram" (the sweep runs on Y Y', built once per bag: the form for bags much wider than
+    tall; refused by the library where 3 L H doubles do not fit in LDS) or "auto" (capi.fit_form_auto per fit) -- the same iteration,
+    different rounding (include/vbmf_hip.h, vbmf_fit_batched_form).  p.form_used: 0 (stream) or 1 (Gram)."""
     def refuse(why):
         raise ValueError(f"vbmf_batch_: {why}; run such fits one at a time with vbmf_")
+    capi.fit_form_code(form)
     params = list(params)
     if not params:
         refuse("no parameter sets")
@@ -1594,12 +1598,13 @@ def vbmf_batch_(Ys, params, niter, eps=1e-6, est_covs=False, est_var=False, bag_
         r = bags.session.ctx.fit_batched(
             bags.col_off, bag_of, int(niter), float(eps), np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]),
             np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]), np.stack([np.diag(p.CA) for p in params]),
-            np.stack([np.diag(p.CB) for p in params]), [p.sigma2 for p in params], est_covs=est_covs, est_var=est_var)
+            np.stack([np.diag(p.CB) for p in params]), [p.sigma2 for p in params], est_covs=est_covs, est_var=est_var, form=form)
     finally:
         if own:
             bags.close()
     idx = np.arange(H)
     for f, p in enumerate(params):
+        p.form_used = int(r["form_used"][f])
         p.AHat = np.array(r["AHat"][f], order="F")                  # rebound, like updateA! / updateB! (src/vbmf.jl:96-98,110-112)
         p.BHat = np.array(r["BHat"][f], order="F")
         p.SigmaA, p.SigmaB = r["SigmaA"][f].copy(), r["SigmaB"][f].copy()
@@ -1612,15 +1617,35 @@ def vbmf_batch_(Ys, params, niter, eps=1e-6, est_covs=False, est_var=False, bag_
     return params
 
 
-def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None):
+def row_gram_batch(bags):
+    """K_b = Y_b Y_b' of every bag in one device call, in fp64 on Y as stored: an (nbags, L, L) array, each block symmetric bit for
+    bit (include/vbmf_hip.h, vbmf_bags_row_gram).  bags: a list of L x M_b arrays (uploaded in fp32 storage for H = 1), a Bags or a
+    SparseBags."""
+    if isinstance(bags, Bags):
+        return bags.session.ctx.row_gram(bags.col_off)
+    if isinstance(bags, SparseBags):
+        return bags.ctx.row_gram(bags.col_off)
+    def refuse(why):
+        raise ValueError(f"row_gram_batch: {why}")
+    _batch_shapes(bags, 1, refuse)
+    own = Bags(bags, 1)
+    try:
+        return own.session.ctx.row_gram(own.col_off)
+    finally:
+        own.close()
+
+
+def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, form="stream"):
     """The reference's train (examples/mil_util.jl:93-152) over many (Y0, Y1) pairs -- the folds, p and repetitions of a validation
     run -- with all the fits in ONE device call.  solver="basic": 2 x len(folds) fits through vbmf_batch_ with est_covs = est_var =
     True (:110-114), vbmf_init drawn in the order (fold, class) from the one generator.  solver="sparse": ten vbmf_sparse_init per class
     per fold, drawn in the order (fold, class, restart), one vbmf_sparse_batch_ call with full_cov=False, and per class the set the
     restart loop of :124-145 keeps (fit_restarts): the first with d <= 2 eps and not NaN, else the last.  Returns a list of
-    (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns (:97-100)."""
+    (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns (:97-100).  form: vbmf_batch_'s, for solver="basic" (the sparse
+    solver has no Gram form and ignores it)."""
     if solver not in ("basic", "sparse"):
         raise ValueError(f"train_folds: solver = {solver!r} ('basic' or 'sparse')")
+    capi.fit_form_code(form)
     if diag_var:
         raise ValueError("train_folds: diag_var=True is not batched; train such folds one at a time with vbmf_sparse_ / vbmf_")
     rng = np.random.default_rng() if rng is None else rng
@@ -1640,7 +1665,8 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None):
     if not ps:
         return out
     if solver == "basic":
-        vbmf_batch_(Ys, ps, niter, eps=eps, est_covs=True, est_var=True, bag_of=bag_of)
+        kw = {} if form == "stream" else dict(form=form)            # (the default call is what it was)
+        vbmf_batch_(Ys, ps, niter, eps=eps, est_covs=True, est_var=True, bag_of=bag_of, **kw)
         kept = ps
     else:
         ds = vbmf_sparse_batch_(Ys, ps, niter, eps=eps, full_cov=False, bag_of=bag_of)

@@ -25,12 +25,36 @@ VBMF_VARIANT_DUAL_DIAGVAR, VBMF_VARIANT_TRIAL_DIAGVAR = 5, 6
 VBMF_COMPAT_SPECTRAL_DELTA, VBMF_COMPAT_SPARSE_REPEAT, VBMF_COMPAT_DEFAULT = 1, 2, 0xFFFFFFFF
 STEP_A, STEP_B, STEP_CA, STEP_CB, STEP_SIGMA2 = 1, 2, 4, 8, 16
 UNIQUE_ID_BYTES = 128
+# vbmf_fit_batched_form (include/vbmf_hip.h): the forms, form = 2's width factor and the LDS a fit may use
+VBMF_FIT_FORM_STREAM, VBMF_FIT_FORM_GRAM, VBMF_FIT_FORM_AUTO = 0, 1, 2
+VBMF_FIT_GRAM_WIDE_FACTOR = 2
+VBMF_FIT_LDS_CAP_BYTES = 144 * 1024
+FIT_FORMS = {"stream": VBMF_FIT_FORM_STREAM, "gram": VBMF_FIT_FORM_GRAM, "auto": VBMF_FIT_FORM_AUTO}
+
+
+def fit_form_code(form):
+    """'stream' / 'gram' / 'auto' -> the C ABI's form; anything else is refused (before the library is touched)"""
+    if not isinstance(form, str) or form not in FIT_FORMS:
+        raise ValueError(f"form = {form!r} ('stream', 'gram' or 'auto')")
+    return FIT_FORMS[form]
+
+
+def fit_gram_fits(L, H):
+    """the Gram form's state (B, T, V: 3 L H doubles) fits in LDS behind the fixed part: one P x (P + 2) inverse image and nine
+    H x H matrices, P = 16 for H <= 16, else 32 (include/vbmf_hip.h)"""
+    P = 16 if H <= 16 else 32
+    return 3 * L * H <= VBMF_FIT_LDS_CAP_BYTES // 8 - (P * (P + 2) + 9 * H * H)
+
+
+def fit_form_auto(L, Mb, H):
+    """the form a fit of an L x Mb bag takes under form='auto': 1 (Gram) or 0 (stream)"""
+    return int(Mb >= VBMF_FIT_GRAM_WIDE_FACTOR * L and fit_gram_fits(L, H))
 
 # every symbol include/vbmf_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "vbmf_default_opts", "vbmf_create", "vbmf_destroy", "vbmf_last_error", "vbmf_set_Y", "vbmf_set_Y_rows", "vbmf_set_Y_synthetic",
     "vbmf_get_Y", "vbmf_get_trYY", "vbmf_set_state", "vbmf_get_state", "vbmf_step", "vbmf_run", "vbmf_run_fixed_basis",
-    "vbmf_run_fixed_basis_batched", "vbmf_fit_batched", "vbmf_get_YHat",
+    "vbmf_run_fixed_basis_batched", "vbmf_fit_batched", "vbmf_fit_batched_form", "vbmf_bags_row_gram", "vbmf_get_YHat",
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
@@ -114,6 +138,8 @@ def lib():
     L.vbmf_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, dp, dp, dp, dp, i64]
     L.vbmf_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32] + [dp] * 7
                                    + [C.POINTER(i64), dp, C.POINTER(i64), dp])
+    L.vbmf_fit_batched_form.argtypes = L.vbmf_fit_batched.argtypes + [i64, C.POINTER(i64)]
+    L.vbmf_bags_row_gram.argtypes = [vp, i64, C.POINTER(i64), dp]
     L.vbmf_sparse_run_fixed_basis.argtypes = [vp, i64]
     L.vbmf_sparse_run_fixed_basis_batched.argtypes = [vp, i64, C.POINTER(i64), i64, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]
     L.vbmf_sparse_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64] + [dp] * 16
@@ -411,12 +437,15 @@ class Context:
                                                          _dptr(ca), _dptr(SA), _dptr(A), self.M))
         return dict(sigma2=s2, CA_diag=ca, SigmaA=SA, AHat=A)
 
-    def fit_batched(self, col_off, fit_bag, niter, eps, BHat, SigmaB, CA, CB, sigma2, est_covs=False, est_var=False, want_trace=False):
+    def fit_batched(self, col_off, fit_bag, niter, eps, BHat, SigmaB, CA, CB, sigma2, est_covs=False, est_var=False, want_trace=False,
+                    form="stream", want_A=True):
         """Many independent vbmf! fits of the basic model in one launch (vbmf_fit_batched): fit f works on bag fit_bag[f] of the bags
         side by side in this context's Y (bag b = columns col_off[b] .. col_off[b+1]-1).  Per fit the start values BHat (nfits, L, H),
         SigmaB (nfits, H, H), the diagonals CA, CB (nfits, H) and sigma2 (nfits,).  Returns dict(BHat, SigmaB, CA, CB, sigma2, SigmaA
-        (nfits, H, H), AHat (a list of M_b x H arrays), iters, d, status, trace (nfits, niter, 2) or None).  Neither the context's state
-        nor its Y is changed."""
+        (nfits, H, H), AHat (a list of M_b x H arrays; None with want_A=False), iters, d, status, trace (nfits, niter, 2) or None,
+        form_used (nfits,)).  form: "stream" (vbmf_fit_batched itself), "gram" (every fit iterates on Y Y': the form for wide bags) or
+        "auto" (fit_form_auto per fit) -- vbmf_fit_batched_form.  Neither the context's state nor its Y is changed."""
+        code = fit_form_code(form)
         off = np.ascontiguousarray(col_off, dtype=np.int64)
         fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
         nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
@@ -430,18 +459,32 @@ class Context:
         if SB.shape != (nf, H, H) or ca.shape != (nf, H) or cb.shape != (nf, H) or s2.shape != (nf,):
             raise ValueError(f"{nf} fits: SigmaB must be ({nf}, {H}, {H}), CA and CB ({nf}, {H}) and sigma2 ({nf},)")
         Ms = off[fb + 1] - off[fb]
-        A = np.empty(int(np.sum(Ms)) * H)
+        A = np.empty(int(np.sum(Ms)) * H) if want_A else None
         SA = np.empty((nf, H, H))
+        used = np.zeros(nf, dtype=np.int64)
         iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
         tr = np.zeros((nf, int(niter), 2)) if want_trace else None
         p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        self._chk(self._lib.vbmf_fit_batched(
-            self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(est_covs)), int(bool(est_var)), _dptr(B), _dptr(SB),
-            _dptr(ca), _dptr(cb), _dptr(s2), _dptr(A), _dptr(SA), p64(iters), _dptr(dl), p64(st), _dptr(tr)))
+        args = (self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(est_covs)), int(bool(est_var)), _dptr(B), _dptr(SB),
+                _dptr(ca), _dptr(cb), _dptr(s2), _dptr(A), _dptr(SA), p64(iters), _dptr(dl), p64(st), _dptr(tr))
+        if code == VBMF_FIT_FORM_STREAM:
+            self._chk(self._lib.vbmf_fit_batched(*args))
+        else:
+            self._chk(self._lib.vbmf_fit_batched_form(*args, code, p64(used)))
         ends = np.cumsum(Ms) * H
-        As = [A[e - m * H:e].reshape(H, m).T for e, m in zip(ends, Ms)]       # column-major M_b x H blocks
+        As = [A[e - m * H:e].reshape(H, m).T for e, m in zip(ends, Ms)] if want_A else None   # column-major M_b x H blocks
         return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CA=ca, CB=cb, sigma2=s2, SigmaA=SA, AHat=As, iters=iters, d=dl, status=st,
-                    trace=tr)
+                    trace=tr, form_used=used)
+
+    def row_gram(self, col_off):
+        """K_b = Y_b Y_b' of every bag side by side in this context's Y, in fp64 on Y as stored (vbmf_bags_row_gram): (nbags, L, L)."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        if nb < 1 or off.ndim != 1:
+            raise ValueError("col_off must describe at least one bag")
+        K = np.empty((nb, self.L, self.L))
+        self._chk(self._lib.vbmf_bags_row_gram(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(K)))
+        return K
 
     def sparse_run_fixed_basis(self, niter):
         self._chk(self._lib.vbmf_sparse_run_fixed_basis(self._h, int(niter)))

@@ -46,6 +46,7 @@ struct FitBasicArgs {
     double* SA; double* A;                                                          // out (A: M_b x H column-major per fit)
     double* Bw; double* Qw; double* Aw;            // working B, Q (nfits x L x H) and P / A (sum M_b x H) of fits whose state is not in LDS
     long long* iters; double* dlast; long long* status; double* trace;
+    const long long* form;                         // nullptr: every fit streams; else form[f] != 0: fit f belongs to fit_basic_gram_kernel
 };
 
 // the H x H block of -inv(W) a blk_sweep left in the upper blocks of the image, times -scale, into the dense symmetric out
@@ -65,6 +66,7 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_basic_kernel(FitBasicArgs g)
     __shared__ int bad_s;
     constexpr int NP = 16 * NBK, LD = NP + 2;
     const int f = blockIdx.x, H = g.H, tid = threadIdx.x, h2 = H * H;
+    if (g.form && g.form[f]) return;                                // (uniform, before any barrier)
     const long long L = g.L, b = g.fit_bag[f], m0 = g.col_off[b], Mb = g.col_off[b + 1] - m0;
     const long long n = Mb * H, o = g.fit_off[f] * H, nb = L * H;
     const int place = fitb_basic_placement(NBK, L, Mb, H);

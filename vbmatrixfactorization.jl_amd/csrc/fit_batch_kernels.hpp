@@ -143,10 +143,11 @@ __device__ __forceinline__ void fitb_chunk_reduce(int nitem, long long rows, dou
 
 // out[r * H + h] = sum_k y(r, k) X[k * H + h] for r < R: T lanes per row (T = the power of two that fills the workgroup, from R alone)
 // split k, an xor-butterfly folds them.  y(r, k) = yc[k * ldc + r] when T = 1 (neighbouring lanes = neighbouring r), else
-// yk[r * ldk + k] (neighbouring lanes = neighbouring k).  Every thread of the workgroup must call it.
-template <int HP>
-__device__ __forceinline__ void fitb_product(long long R, long long K, const float* __restrict__ yc, long long ldc,
-                                             const float* __restrict__ yk, long long ldk, const double* X, int H, double* out) {
+// yk[r * ldk + k] (neighbouring lanes = neighbouring k).  YT: float (the planes of Y) or double (fit_basic_gram_kernels.hpp's K).
+// Every thread of the workgroup must call it.
+template <int HP, class YT>
+__device__ __forceinline__ void fitb_product(long long R, long long K, const YT* __restrict__ yc, long long ldc,
+                                             const YT* __restrict__ yk, long long ldk, const double* X, int H, double* out) {
     int T = 1;
     while (T < 64 && R * T < FITB_THREADS) T <<= 1;
     const long long items = R * T;

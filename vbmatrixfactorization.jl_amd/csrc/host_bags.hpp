@@ -1,5 +1,5 @@
 // host_bags.hpp -- the many-bags entries of the C ABI (batched vbls! of the basic and the sparse models, per-bag residuals, least
-// squares and lower bounds, many whole fits of the sparse and of the basic model) and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
+// squares and lower bounds, many whole fits of the sparse and of the basic model, the bags' Y Y') and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
 // helpers it uses, never on its own.  The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.
 //   bags_check     what every entry refuses about (nbags, col_off) and a sharded context; the widest bag, the residual slices
 //   bags_reserve   ONE device scratch buffer (c->bags), grown on demand.  Every entry synchronises before it returns, so no two layouts
@@ -413,6 +413,16 @@ int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* c
 }  // extern "C"
 
 // ---- many fits in one launch (fit_batch_kernels.hpp) ------------------------------------------------------------------------------
+// enqueues fit_stage_kernel: Y as stored into the two fp32 planes
+static int fit_stage(vbmf_ctx* c, float* Yr, float* Yc) {
+    DISPATCH_YMODE(c->mode, {
+        hipLaunchKernelGGL((fit_stage_kernel<YMODEc>), dim3(grid_for(c->L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
+                           (long long)c->L, (long long)c->M, Yr, Yc);
+    });
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
 // What vbmf_sparse_fit_batched and vbmf_local_fit_batched share once each has refused what it refuses about the context and the scalar
 // arguments: the per-fit checks, the layout of c->bags, the staging, the one launch and the read-back.  M0 = nullptr: the two-group
 // sweep with four priors per fit; else the three-group / masked sweep with nine (M0[f] checked against the fit's own M_b here).
@@ -476,11 +486,7 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     if (ntr) HIPCHK(c, hipMemsetAsync(d + o_tr, 0, (size_t)ntr * 8, c->stream));
     float* Yr = reinterpret_cast<float*>(d + o_yr);
     float* Yc = reinterpret_cast<float*>(d + o_yc);
-    DISPATCH_YMODE(c->mode, {
-        hipLaunchKernelGGL((fit_stage_kernel<YMODEc>), dim3(grid_for(L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
-                           (long long)L, (long long)c->M, Yr, Yc);
-    });
-    HIPCHK(c, hipGetLastError());
+    TRY(fit_stage(c, Yr, Yc));
     long long* di = reinterpret_cast<long long*>(d);
     FitArgs a{Yr, Yc, (long long)L, (long long)c->M, di, di + nb + 1, di + nb + 1 + nf, H, (int)H0, (int)niter, compat ? 1 : 0,
               (c->o.reference_compat & VBMF_COMPAT_SPECTRAL_DELTA) ? 1 : 0, est_cb ? 1 : 0, est_priors ? 1 : 0, eps,
@@ -595,17 +601,33 @@ int vbmf_local_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, i
 
 }  // extern "C"
 
-// ---- many basic-model fits in one launch (fit_basic_kernels.hpp) -------------------------------------------------------------------
-extern "C" {
+// ---- many basic-model fits in one launch (fit_basic_kernels.hpp, fit_basic_gram_kernels.hpp) ---------------------------------------
+static_assert(FITB_LDS_CAP == VBMF_FIT_LDS_CAP_BYTES, "include/vbmf_hip.h documents the LDS a fit may use");
+
+// form = 2's per-fit rule, a function of (L, M_b, H) alone: the Gram form where the bag is wide enough and B, T, V fit in LDS
+static bool fit_basic_auto_gram(int NBK, int64_t L, int64_t Mb, int H) {
+    return Mb >= VBMF_FIT_GRAM_WIDE_FACTOR * L && fitb_gram_fits(NBK, L, H);
+}
+
+// enqueues fit_rowgram_kernel for the nk bags listed in d_kbag
+static int fit_rowgram(vbmf_ctx* c, const char* fn, const float* Yc, const long long* d_off, const long long* d_kbag, int64_t nk, double* K) {
+    const int64_t NT = (c->L + 15) / 16, blocks = nk * (NT * (NT + 1) / 2);
+    if (blocks > (1ll << 31) - 1) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld bags of %lld rows need more than 2^31 - 1 tiles of K", fn, (long long)nk, (long long)c->L);
+    hipLaunchKernelGGL(fit_rowgram_kernel, dim3((unsigned)blocks), dim3(RG_THREADS), 0, c->stream, Yc, (long long)c->L, d_off, d_kbag, (int)NT, K);
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
 
 // The two vbmf! calls of examples/mil_util.jl:110-114 (and the folds x p x repetitions around them) in one call: every fit's whole
 // loop of src/vbmf.jl:175-231 in one workgroup of one launch.  The context supplies Y only; its state is neither read nor changed, so
-// no RunFrame (see vbmf_sparse_fit_batched).
-int vbmf_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter, double eps,
-                     int est_covs, int est_var, double* BHat, double* SigmaB, double* CA, double* CB, double* sigma2, double* AHat,
-                     double* SigmaA, int64_t* iters_done, double* d_last, int64_t* status, double* trace) {
+// no RunFrame (see vbmf_sparse_fit_batched).  form: 0 = every fit streams Y (fit_basic_kernel), 1 = every fit iterates on K = Y Y'
+// (fit_basic_gram_kernel), 2 = fit_basic_auto_gram per fit.
+static int fit_basic_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                         int64_t niter, double eps, int est_covs, int est_var, double* BHat, double* SigmaB, double* CA, double* CB,
+                         double* sigma2, double* AHat, double* SigmaA, int64_t* iters_done, double* d_last, int64_t* status, double* trace,
+                         int64_t form, int64_t* form_used) {
     if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_fit_batched";
+    if (form < 0 || form > 2) FAIL(c, VBMF_ERR_INVALID, "%s: form = %lld (0: stream, 1: Gram, 2: per fit)", fn, (long long)form);
     if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
     if (c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: sparse context (the basic model only; use vbmf_sparse_fit_batched)", fn);
     if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_run per fit)", fn);
@@ -617,30 +639,55 @@ int vbmf_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t
         FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only AHat, SigmaA and trace may be NULL)", fn);
     const int H = (int)c->H, NBK = nb_tier(H);
     const int64_t L = c->L, nf = nfits, nb = nbags, h2 = (int64_t)H * H, LH = L * H;
-    std::vector<long long> idx((size_t)(nb + 1 + nf + nf + 1));               // col_off | fit_bag | fit_off
+    if (form == 1 && !fitb_gram_fits(NBK, L, H))
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: form = 1 at L = %lld, H = %d: the Gram form's state (3 L H doubles) does not fit in LDS", fn,
+             (long long)L, H);
+    if (form && bd.widest > 65535ll * RG_THREADS) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: form = %lld with a bag of %lld columns", fn, (long long)form, (long long)bd.widest);
+    // col_off | fit_bag | fit_off | fit_form | fit_k | kbag (the last three only when a fit may take the Gram form)
+    std::vector<long long> idx((size_t)(nb + 1 + nf + nf + 1 + (form ? nf + nf + nb : 0)));
     long long* fit_off = idx.data() + nb + 1 + nf;
+    long long* fit_form = form ? fit_off + nf + 1 : nullptr;
+    long long* fit_k = form ? fit_form + nf : nullptr;
+    long long* kbag = form ? fit_k + nf : nullptr;
     fit_off[0] = 0;
     size_t lds_doubles = 0;
+    int64_t nk = 0, ngram = 0, widest_gram = 0;                    // bags whose K is built; Gram-form fits; their widest bag
+    std::vector<long long> k_of(form ? (size_t)nb : 0, -1);
     for (int64_t f = 0; f < nf; ++f) {
         const int64_t b = fit_bag[f];
         if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: fit_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)f, (long long)b);
         const int64_t Mb = col_off[b + 1] - col_off[b];
         fit_off[f + 1] = fit_off[f] + Mb;
-        lds_doubles = std::max(lds_doubles, (size_t)fitb_basic_lds_doubles(NBK, L, Mb, H));
         idx[(size_t)(nb + 1 + f)] = b;
+        const bool gram = form == 1 || (form == 2 && fit_basic_auto_gram(NBK, L, Mb, H));
+        if (form) {
+            fit_form[f] = gram;
+            fit_k[f] = 0;
+        }
+        if (gram) {
+            if (k_of[(size_t)b] < 0) { k_of[(size_t)b] = nk; kbag[nk++] = b; }
+            fit_k[f] = k_of[(size_t)b];
+            ++ngram;
+            widest_gram = std::max(widest_gram, Mb);
+        } else {
+            lds_doubles = std::max(lds_doubles, (size_t)fitb_basic_lds_doubles(NBK, L, Mb, H));
+        }
     }
     for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
+    for (int64_t k = nk; form && k < nb; ++k) kbag[k] = 0;
     if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
     // the staging vectors outlive every copy: an error between the first asynchronous copy and the synchronise drains the stream below
     std::vector<double> in, out;
     auto run = [&]() -> int {
     HIPCHK(c, hipSetDevice(c->o.device));
     const int64_t SMH = fit_off[nf] * H, nidx = (int64_t)idx.size(), ntr = trace ? 2 * nf * niter : 0, ny = (L * c->M + 1) / 2;
-    // c->bags: [col_off | fit_bag | fit_off (int64) | sigma2 nf | CA | CB (nf H each) | d_last | iters | status (int64) (nf each) | B | Bw |
-    //           Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | A | Aw (sum M_b H each) | trace | Yr | Yc (L M floats each)]
+    // c->bags: [col_off | fit_bag | fit_off | fit_form | fit_k | kbag (int64) | sigma2 nf | CA | CB (nf H each) | d_last | iters | status (int64) (nf each) | B | Bw |
+    //           Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | A | Aw (sum M_b H each) | trace | Yr | Yc (L M floats each) | K (L^2 per bag a
+    //           Gram-form fit works on) | V (nf L H, when there is such a fit)]
     const int64_t o_s2 = nidx, o_ca = o_s2 + nf, o_cb = o_ca + nf * H, o_dl = o_cb + nf * H, o_it = o_dl + nf, o_st = o_it + nf,
                   o_b = o_st + nf, o_bw = o_b + nf * LH, o_qw = o_bw + nf * LH, o_sb = o_qw + nf * LH, o_sa = o_sb + nf * h2,
-                  o_a = o_sa + nf * h2, o_aw = o_a + SMH, o_tr = o_aw + SMH, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
+                  o_a = o_sa + nf * h2, o_aw = o_a + SMH, o_tr = o_aw + SMH, o_yr = o_tr + ntr, o_yc = o_yr + ny, o_k = o_yc + ny,
+                  o_v = o_k + nk * L * L, total = o_v + (ngram ? nf * LH : 0);
     double* d = nullptr;
     TRY(bags_reserve(c, total, &d));
     in.resize((size_t)(o_dl - o_s2));
@@ -654,21 +701,37 @@ int vbmf_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t
     if (ntr) HIPCHK(c, hipMemsetAsync(d + o_tr, 0, (size_t)ntr * 8, c->stream));
     float* Yr = reinterpret_cast<float*>(d + o_yr);
     float* Yc = reinterpret_cast<float*>(d + o_yc);
-    DISPATCH_YMODE(c->mode, {
-        hipLaunchKernelGGL((fit_stage_kernel<YMODEc>), dim3(grid_for(L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
-                           (long long)L, (long long)c->M, Yr, Yc);
-    });
-    HIPCHK(c, hipGetLastError());
+    TRY(fit_stage(c, Yr, Yc));
     long long* di = reinterpret_cast<long long*>(d);
+    long long* d_form = di + nb + 1 + nf + nf + 1;                  // fit_form | fit_k | kbag
     FitBasicArgs a{Yr, Yc, (long long)L, (long long)c->M, di, di + nb + 1, di + nb + 1 + nf, H, (int)niter,
                    (c->o.reference_compat & VBMF_COMPAT_SPECTRAL_DELTA) ? 1 : 0, est_covs ? 1 : 0, est_var ? 1 : 0, eps,
                    d + o_b, d + o_sb, d + o_ca, d + o_cb, d + o_s2, d + o_sa, d + o_a, d + o_bw, d + o_qw, d + o_aw,
-                   reinterpret_cast<long long*>(d + o_it), d + o_dl, reinterpret_cast<long long*>(d + o_st), trace ? d + o_tr : nullptr};
-    const size_t lds = lds_doubles * 8;
-    DISPATCH_NB(NBK, {
-        hipLaunchKernelGGL((fit_basic_kernel<(NBc > 2 ? 2 : NBc)>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
-    });
-    HIPCHK(c, hipGetLastError());
+                   reinterpret_cast<long long*>(d + o_it), d + o_dl, reinterpret_cast<long long*>(d + o_st), trace ? d + o_tr : nullptr,
+                   form ? d_form : nullptr};
+    if (ngram < nf) {
+        const size_t lds = lds_doubles * 8;
+        DISPATCH_NB(NBK, {
+            hipLaunchKernelGGL((fit_basic_kernel<(NBc > 2 ? 2 : NBc)>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
+        });
+        HIPCHK(c, hipGetLastError());
+    }
+    if (ngram) {
+        TRY(fit_rowgram(c, fn, Yc, di, d_form + nf + nf, nk, d + o_k));
+        FitBasicGramArgs ga{a, d + o_k, d_form + nf, d + o_v};
+        const size_t lds = (size_t)fitb_gram_lds_doubles(NBK, L, H) * 8;
+        DISPATCH_NB(NBK, {
+            hipLaunchKernelGGL((fit_basic_gram_kernel<(NBc > 2 ? 2 : NBc)>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, ga);
+        });
+        HIPCHK(c, hipGetLastError());
+        if (AHat) {
+            const dim3 grid((unsigned)nf, (unsigned)cdiv(widest_gram, RG_THREADS));
+            DISPATCH_NB(NBK, {
+                hipLaunchKernelGGL((fit_rowgram_finish_kernel<(NBc > 2 ? 32 : 16 * NBc)>), grid, dim3(RG_THREADS), (size_t)LH * 8, c->stream, ga);
+            });
+            HIPCHK(c, hipGetLastError());
+        }
+    }
     // read-back: [sigma2 | CA | CB | d_last | iters | status] is one block; the per-fit matrices one block each
     out.resize((size_t)(o_b - o_s2));
     HIPCHK(c, hipMemcpyAsync(out.data(), d + o_s2, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -684,10 +747,60 @@ int vbmf_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t
     memcpy(d_last, out.data() + (o_dl - o_s2), (size_t)nf * 8);
     memcpy(iters_done, out.data() + (o_it - o_s2), (size_t)nf * 8);
     memcpy(status, out.data() + (o_st - o_s2), (size_t)nf * 8);
+    for (int64_t f = 0; form_used && f < nf; ++f) form_used[f] = form ? fit_form[f] : 0;
     return VBMF_OK;
     };
     const int rc = run();
     if (rc != VBMF_OK) hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+extern "C" {
+
+int vbmf_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter, double eps,
+                     int est_covs, int est_var, double* BHat, double* SigmaB, double* CA, double* CB, double* sigma2, double* AHat,
+                     double* SigmaA, int64_t* iters_done, double* d_last, int64_t* status, double* trace) {
+    return fit_basic_run(c, "vbmf_fit_batched", nbags, col_off, nfits, fit_bag, niter, eps, est_covs, est_var, BHat, SigmaB, CA, CB, sigma2,
+                         AHat, SigmaA, iters_done, d_last, status, trace, 0, nullptr);
+}
+
+int vbmf_fit_batched_form(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
+                          double eps, int est_covs, int est_var, double* BHat, double* SigmaB, double* CA, double* CB, double* sigma2,
+                          double* AHat, double* SigmaA, int64_t* iters_done, double* d_last, int64_t* status, double* trace, int64_t form,
+                          int64_t* form_used) {
+    return fit_basic_run(c, "vbmf_fit_batched_form", nbags, col_off, nfits, fit_bag, niter, eps, est_covs, est_var, BHat, SigmaB, CA, CB,
+                         sigma2, AHat, SigmaA, iters_done, d_last, status, trace, form, form_used);
+}
+
+// K_b = Y_b Y_b' of every bag (fit_rowgram_kernel): what the Gram form iterates on, and the B'K B of the least-squares callers
+int vbmf_bags_row_gram(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, double* K) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_bags_row_gram";
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (!K) FAIL(c, VBMF_ERR_INVALID, "%s: null K", fn);
+    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    const int64_t nb = nbags, L = c->L, ny = (L * c->M + 1) / 2;
+    std::vector<long long> idx((size_t)(2 * nb + 1));               // col_off | kbag = 0 .. nb - 1
+    for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
+    for (int64_t b = 0; b < nb; ++b) idx[(size_t)(nb + 1 + b)] = b;
+    auto run = [&]() -> int {
+        // c->bags: [col_off | kbag (int64) | K nb L^2 | Yr | Yc (L M floats each)]
+        const int64_t o_k = (int64_t)idx.size(), o_yr = o_k + nb * L * L, o_yc = o_yr + ny, total = o_yc + ny;
+        double* d = nullptr;
+        TRY(bags_reserve(c, total, &d));
+        long long* di = reinterpret_cast<long long*>(d);
+        HIPCHK(c, hipMemcpyAsync(d, idx.data(), idx.size() * 8, hipMemcpyHostToDevice, c->stream));
+        float* Yc = reinterpret_cast<float*>(d + o_yc);
+        TRY(fit_stage(c, reinterpret_cast<float*>(d + o_yr), Yc));
+        TRY(fit_rowgram(c, fn, Yc, di, di + nb + 1, nb, d + o_k));
+        HIPCHK(c, hipMemcpyAsync(K, d + o_k, (size_t)(nb * L * L) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return VBMF_OK;
+    };
+    const int rc = run();
+    if (rc != VBMF_OK) hipStreamSynchronize(c->stream);             // (idx is a local)
     return rc;
 }
 

@@ -50,6 +50,7 @@
 #include "sparse_batch_kernels.hpp"
 #include "fit_batch_kernels.hpp"
 #include "fit_basic_kernels.hpp"
+#include "fit_basic_gram_kernels.hpp"
 #include "score_kernels.hpp"
 #include "gram_kernels.hpp"
 
@@ -1672,6 +1673,8 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_gram_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_gram_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
         if (e == hipSuccess && c->NH == 4)
             e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
         if (e == hipSuccess && c->NH == 4)

@@ -11,7 +11,7 @@
 module VBMatrixFactorizationHIP
 
 export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, updateCB!, updateSigma2!, updateYHat!,
-       vbls!, vbls_batch!, vbmf_batch!, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
+       vbls!, vbls_batch!, vbmf_batch!, row_gram_batch, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
@@ -58,6 +58,7 @@ end
 
 const VBMF_Y_F32, VBMF_Y_BF16 = Int32(0), Int32(1)
 const STEP_A, STEP_B, STEP_CA, STEP_CB, STEP_SIGMA2 = 1, 2, 4, 8, 16
+const FIT_FORMS = Dict(:stream => 0, :gram => 1, :auto => 2)     # vbmf_fit_batched_form (include/vbmf_hip.h)
 
 # what the basic model takes as Y: the reference's Array{Float64,2}, or an Array{Float32,2} that is uploaded as it is (the
 # reference has Float32 methods on this path: scaleY, preprocess, src/util.jl:60,94)
@@ -341,9 +342,13 @@ around them): does what `[vbmf!(Ys[bag_of[f]], ps[f], niter; eps = eps, est_covs
 does -- every fit's whole loop of src/vbmf.jl:175-231 in one workgroup of one launch (vbmf_fit_batched) -- and returns
 (d, sweeps run, status) per fit; status 1 = the fit met a non-finite sigma2, a CA / CB entry that is not positive, or a bad pivot, and
 stopped.  Fit f works on bag bag_of[f] (1-based).  The bags share L; no labels, H <= 32 (anything else: vbmf! per fit).
+form: :stream (Y is read twice per sweep), :gram (the sweep runs on Y*Y', built once per bag: the form for bags much wider than tall) or
+:auto (per fit: Gram where M_b >= 2L and its 3*L*H doubles of state fit in LDS) -- the same iteration, different rounding
+(vbmf_fit_batched_form).
 """
 function vbmf_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}, niter::Int; eps::Float64 = 1e-6, est_covs::Bool = false,
-                     est_var::Bool = false, bag_of::Vector{Int} = collect(1:length(ps)))
+                     est_var::Bool = false, bag_of::Vector{Int} = collect(1:length(ps)), form::Symbol = :stream)
+    haskey(FIT_FORMS, form) || error("vbmf_batch!: form = $form (:stream, :gram or :auto)")
     nb, nf = length(Ys), length(ps)
     (nb >= 1 && nf >= 1 && length(bag_of) == nf) || error("vbmf_batch!: one bag_of entry per parameter set")
     niter >= 1 || error("vbmf_batch!: niter must be >= 1")
@@ -370,10 +375,19 @@ function vbmf_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}, n
     it = zeros(Int64, nf); dlast = Array{Float64}(undef, nf); st = zeros(Int64, nf)
     try
         chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
-        chk(h[], ccall((:vbmf_fit_batched, libvbmf), Cint,
-            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
-            h[], nb, off, nf, fb, niter, eps, est_covs, est_var, B, SB, ca, cb, s2, A, SA, it, dlast, st, C_NULL))
+        if form == :stream
+            chk(h[], ccall((:vbmf_fit_batched, libvbmf), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                h[], nb, off, nf, fb, niter, eps, est_covs, est_var, B, SB, ca, cb, s2, A, SA, it, dlast, st, C_NULL))
+        else
+            chk(h[], ccall((:vbmf_fit_batched_form, libvbmf), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int64,
+                 Ptr{Int64}),
+                h[], nb, off, nf, fb, niter, eps, est_covs, est_var, B, SB, ca, cb, s2, A, SA, it, dlast, st, C_NULL, FIT_FORMS[form],
+                C_NULL))
+        end
     finally
         ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
     end
@@ -393,6 +407,30 @@ function vbmf_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_parameters}, n
         p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')        # :217
     end
     return dlast, it, st
+end
+
+"""
+K_b = Y_b*Y_b' of every bag in ONE device call, in fp64 on Y as stored (vbmf_bags_row_gram): an L x L x nbags array, every slice
+symmetric bit for bit.  What vbmf_batch!(...; form = :gram) iterates on; ols / rls callers form B'*K_b*B from it.
+"""
+function row_gram_batch(Ys::Vector{Matrix{Float64}})
+    nb = length(Ys)
+    nb >= 1 || error("row_gram_batch: no bags")
+    L = size(Ys[1], 1)
+    all(size(Y, 1) == L && size(Y, 2) >= 1 for Y in Ys) || error("row_gram_batch: the bags have different L, or one is empty")
+    off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
+    Yall = reduce(hcat, Ys)
+    opts = Ref(VbmfOpts(Int32(sizeof(VbmfOpts)), 0, y_dtype(), 0, 0, 0xffffffff, 1, 0, 0, 0, 0, 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, off[end], 1, opts))
+    K = Array{Float64}(undef, L, L, nb)
+    try
+        chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
+        chk(h[], ccall((:vbmf_bags_row_gram, libvbmf), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}), h[], nb, off, K))
+    finally
+        ccall((:vbmf_destroy, libvbmf), Cint, (Ptr{Cvoid},), h[])
+    end
+    return K
 end
 
 "copy_vbmf_params -- examples/mil_util.jl:212-236 (vbmf_parameters branch)"
