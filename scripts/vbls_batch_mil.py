@@ -46,7 +46,7 @@ def batched(Ys, resg):
     ps = [pkg.copy_vbmf_params(Y, resg, rng=np.random.default_rng(1)) for Y in Ys]
     bags = pkg.Bags(Ys, resg.H)
     pkg.vbls_batch_(bags, ps, NITER)
-    bags.session.ctx.sync()
+    bags.ctx.sync()
     return ps, bags
 
 
@@ -95,7 +95,7 @@ def main():
             ps = [pkg.copy_vbmf_params(Y, resg, rng=np.random.default_rng(1)) for Y in Ys]
             t0 = time.perf_counter()
             pkg.vbls_batch_(bags, ps, NITER)
-            bags.session.ctx.sync()
+            bags.ctx.sync()
             ts.append(time.perf_counter() - t0)
         t_up = float(np.median(ts)) / nb
         bags.close()

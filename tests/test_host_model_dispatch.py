@@ -1,7 +1,9 @@
 """What the Python host sends to the device for the ARD-sparse model and its grouped siblings (vbmf_dual, vbmf_trial), and for
 the basic model's paths that share code with them: the package's Context is replaced by a recorder that logs every method call
 with its bound arguments and returns deterministic results.  Each case checks the full call sequence and every field written
-back to params (and that no other field changed).  No GPU and no library are needed."""
+back to params (and that no other field changed).  The whole-fit batched calls (vbmf_sparse_batch_, vbmf_dual_batch_,
+vbmf_trial_batch_, vbmf_sparse_masked_batch_, vbmf_batch_) and their callers are covered the same way.  No GPU and no library are
+needed."""
 import copy
 import inspect
 from dataclasses import fields
@@ -51,6 +53,7 @@ def bound(pkg, cid, name, *a, **k):
 class Recorder:
     """Stands in for capi.Context.  Every value it returns is distinct (a running serial number), positive and exact in fp64."""
     log, serial, runs, count = [], 0, 0, 0
+    fit_iters = fit_status = fit_d = None
 
     def __init__(self, *a, **k):
         self.L, self.M, self.H = a[:3]
@@ -97,6 +100,10 @@ def _returns(c, name, a):
         return c.v(c.L).ravel(), c.v(c.L).ravel()
     if name == "sparse_get_SigmaA":
         return c.v(c.H, c.H)
+    if name == "row_gram":
+        return c.v(nb, c.L, c.L)
+    if name in ("fit_batched", "sparse_fit_batched", "local_fit_batched"):
+        return _fit_returns(c, name, a)
     if name == "dual_get_priors":
         pr = c.v(6).ravel()
         return H0, dict(alpha00=pr[0], beta00=pr[1], alpha01=pr[2], beta01=pr[3], alpha0=pr[4], alpha1=pr[5])
@@ -104,6 +111,27 @@ def _returns(c, name, a):
         pr = c.v(9).ravel()
         return H0, M0, {k: float(pr[i]) for i, k in enumerate(c.TRIAL_KEYS)}
     return None
+
+
+def _fit_returns(c, name, a):
+    """The whole-fit batched calls: the shapes capi.Context documents.  iters, status and d are 3 + f, 0 and distinct values unless the
+    test scripts them through Recorder.fit_iters / fit_status / fit_d."""
+    fb = np.asarray(a["fit_bag"])
+    Ms = np.asarray(a["col_off"])[fb + 1] - np.asarray(a["col_off"])[fb]
+    nf, Hc = fb.size, c.H
+    MH = int(Ms.sum()) * Hc
+    scripted = lambda v, default: np.asarray(default if v is None else v)
+    out = dict(BHat=c.v(nf, c.L, Hc), SigmaB=c.v(nf, Hc, Hc), SigmaA=c.v(nf, Hc, Hc), iters=scripted(Recorder.fit_iters, 3 + np.arange(nf)),
+               d=scripted(Recorder.fit_d, c.v(nf)), status=scripted(Recorder.fit_status, np.zeros(nf, dtype=np.int64)),
+               trace=c.v(nf, a["niter"], 2) if a["want_trace"] else None)
+    if name == "fit_batched":
+        used = dict(stream=np.zeros(nf), gram=np.ones(nf), auto=np.arange(nf) % 2)[a["form"]].astype(np.int64)
+        out.update(CA=c.v(nf, Hc), CB=c.v(nf, Hc), sigma2=c.v(nf), AHat=[c.v(m, Hc) for m in Ms] if a["want_A"] else None, form_used=used)
+    else:
+        width = 4 if name == "sparse_fit_batched" else 9
+        out.update({f"priors{width}": c.v(nf, width)}, CB=c.v(nf, Hc), delta=c.v(nf, Hc) if a["est_cb"] else None, sigmaHat=c.v(nf),
+                   zeta=c.v(nf), CA=c.v(MH), beta=c.v(MH), diagSigmaATVec=c.v(MH), ATVecHat=c.v(MH))
+    return out
 
 
 def _method(name):
@@ -119,7 +147,8 @@ for _name in ("set_Y", "close", "set_state", "get_state", "step", "run", "run_fi
               "elbo", "sparse_set_state", "sparse_get_state", "sparse_step", "sparse_run", "sparse_run_fixed_basis",
               "sparse_run_fixed_basis_batched", "sparse_set_noise_rows", "sparse_get_noise_rows", "sparse_set_full_cov",
               "sparse_set_SigmaA", "sparse_get_SigmaA", "sparse_lower_bound", "sparse_lower_bound_trimmed", "dual_set_priors",
-              "dual_get_priors", "dual_run", "trial_set_priors", "trial_get_priors", "trial_run"):
+              "dual_get_priors", "dual_run", "trial_set_priors", "trial_get_priors", "trial_run", "fit_batched", "sparse_fit_batched",
+              "local_fit_batched", "row_gram"):
     setattr(Recorder, _name, _method(_name))
 
 
@@ -127,6 +156,7 @@ for _name in ("set_Y", "close", "set_state", "get_state", "step", "run", "run_fi
 def rec(pkg, monkeypatch):
     """The recorder in place of Context, empty session caches, and the log writers as stubs that log too."""
     Recorder.log, Recorder.serial, Recorder.runs, Recorder.count = [], 0, 0, 0
+    Recorder.fit_iters = Recorder.fit_status = Recorder.fit_d = None
     Recorder.TRIAL_KEYS = pkg.capi.Context.TRIAL_KEYS
     monkeypatch.setattr(pkg, "Context", Recorder)
     monkeypatch.setattr(pkg, "_sessions", {})
@@ -605,3 +635,254 @@ def test_sparse_ctx_cache(pkg, rec):
     assert opened()[n:] == [(2, "close"), (4, "close")]
     pkg.invalidate()
     assert len(opened()) == n + 2
+
+
+# ---- whole fits, many in one device call -----------------------------------------------------------------------------------------
+BAG_OF = [2, 0, 2, 1]                       # a bag twice, not sorted
+FIT_M0 = (1, 3, 0, 1)                       # per fit: inside its bag, all of it, none of it
+FIT_FN = dict(sparse="vbmf_sparse_batch_", dual="vbmf_dual_batch_", trial="vbmf_trial_batch_", masked="vbmf_sparse_masked_batch_")
+FIT_GROUPS = dict(sparse=(("alpha0", "beta0"),) * 2, dual=(("alpha00", "beta00"), ("alpha01", "beta01")),
+                  trial=(("alpha01", "beta01"), ("alpha02", "beta02"), ("alpha03", "beta03")), masked=(("alpha0", "beta0"),) * 3)
+
+
+def _fit_sets(pkg, model, Ms, h0=H0, bag_of=BAG_OF):
+    """Bags of unequal width and one parameter set per entry of bag_of, no two alike in anything the device call is given."""
+    rng = np.random.default_rng(11)
+    Ys = [rng.standard_normal((L, m)) for m in Ms]
+    hyp = lambda f: dict(gamma0=0.3 + f, delta0=0.4 + f, eta0=0.5 + f, zeta0=0.6 + f)
+    ps = []
+    for f, b in enumerate(bag_of):
+        m0 = min(FIT_M0[f], Ms[b])
+        if model == "basic":
+            p = pkg.vbmf_init(Ys[b], H, ca=0.5 + f, cb=0.7 + f, sigma2=0.9 + f, rng=rng)
+            p.SigmaB = rng.standard_normal((H, H))
+            p.CA, p.CB = p.CA + np.diag(np.arange(H) / 4.0) + 0.125, p.CB + np.diag(np.arange(H) / 8.0) + 0.25   # off-diagonals too
+            ps.append(p)
+            continue
+        if model == "sparse":
+            p = pkg.vbmf_sparse_init(Ys[b], H, alpha0=0.1 + f, beta0=0.2 + f, rng=rng, **hyp(f))
+        elif model == "masked":
+            p = pkg.vbmf_sparse_init(Ys[b], H, alpha0=0.1 + f, beta0=0.2 + f, H1=1, labels=np.arange(1, m0 + 1), rng=rng, **hyp(f))
+        elif model == "dual":
+            p = pkg.vbmf_dual_init(Ys[b], H, h0, rng=rng, **hyp(f))
+            p.alpha00, p.beta00, p.alpha01, p.beta01 = 0.15 + f, 0.25 + f, 0.35 + f, 0.45 + f
+        else:
+            p = pkg.vbmf_trial_init(Ys[b], H, h0, m0, rng=rng, **hyp(f))
+            for g in (1, 2, 3):
+                setattr(p, f"alpha0{g}", 0.1 * g + f)
+                setattr(p, f"beta0{g}", 0.2 * g + f)
+        p.SigmaB = rng.standard_normal((H, H))
+        p.CB, p.sigmaHat = p.CB + np.arange(H) / 4.0 + f, 1.5 + f
+        p.CA = p.CA + f + np.arange(p.CA.size) / 16.0
+        ps.append(p)
+    return Ys, ps, np.concatenate(Ys, axis=1), np.concatenate([[0], np.cumsum(Ms)])
+
+
+def _open_bags(pkg, cid, model, Yall):
+    kw = {} if model == "basic" else dict(variant=pkg.VBMF_VARIANT_SPARSE_DIAG)
+    return [bound(pkg, cid, "__init__", L, Yall.shape[1], H, **kw, **pkg._defaults), bound(pkg, cid, "set_Y", Yall)]
+
+
+def _want_sparse_family_call(pkg, model, p0s, col_off, niter, eps, full_cov, est_cb, est_priors, bag_of=BAG_OF):
+    common = (col_off, bag_of, niter, eps, [p.gamma0 + p.L / 2 for p in p0s], [p.delta0 for p in p0s],
+              [p.eta0 + p.L * p.M / 2 for p in p0s], [p.zeta0 for p in p0s],
+              [[getattr(p, k) for pair in FIT_GROUPS[model] for k in pair] for p in p0s],
+              [p.BHat for p in p0s], [p.SigmaB for p in p0s], [p.CB for p in p0s], [p.sigmaHat for p in p0s],
+              np.concatenate([p.CA for p in p0s]))
+    grouped = model in ("dual", "trial")
+    kw = dict(H0=p0s[0].H0 if grouped else H, full_cov=full_cov, est_cb=est_cb, est_priors=est_priors and grouped)
+    if model in ("sparse", "dual"):
+        return bound(pkg, 0, "sparse_fit_batched", *common, **kw)
+    M0s = [p.M0 if model == "trial" else len(p.labels) for p in p0s]
+    return bound(pkg, 0, "local_fit_batched", *common, M0s, mask_H1=1 if model == "masked" else 0, **kw)
+
+
+def _sparse_family_written(model, p0, r, f, s0, est_cb, est_priors):
+    s1 = s0 + p0.M * H
+    w = {k: r[k][s0:s1] for k in ("ATVecHat", "diagSigmaATVec", "CA", "beta")}
+    w.update(AHat=w["ATVecHat"].reshape(p0.M, H), SigmaA=r["SigmaA"][f], BHat=r["BHat"][f], SigmaB=r["SigmaB"][f], CB=r["CB"][f],
+             sigmaHat=r["sigmaHat"][f], zeta=r["zeta"][f])
+    if est_cb:
+        w["delta"] = r["delta"][f]
+    if model in ("dual", "trial"):
+        w.update(views(model, p0, w["AHat"], w["CA"], w["beta"]))
+    if model == "dual":
+        # the posterior shapes of the last updateCA!: read back from CA * beta where est_priors refitted them and the fit ran and
+        # ended well, else the start values' (src/vbmf_dual.jl:324-325)
+        ok = est_priors and r["iters"][f] > 0 and r["status"][f] == 0
+        w["alpha0"] = w["CA0"][0] * w["beta0"][0] if ok else p0.alpha00 + 0.5
+        w["alpha1"] = w["CA1"][0] * w["beta1"][0] if ok and w["CA1"].size else p0.alpha01 + 0.5
+        w["alpha00"], w["beta00"], w["alpha01"], w["beta01"] = r["priors4"][f]
+    if model == "trial":
+        w.update(zip(("alpha01", "beta01", "alpha02", "beta02", "alpha03", "beta03", "alpha1", "alpha2", "alpha3"), r["priors9"][f]))
+    if model in ("dual", "trial"):
+        w["alpha"] = [w[a] for a in SHAPES[model]]
+    w["YHat"] = w["BHat"] @ w["AHat"].T
+    return w
+
+
+@pytest.mark.parametrize("model,h0,est_priors", [("sparse", H0, True), ("masked", H0, True)]      # (these two have no est_priors)
+                         + [(m, h, e) for m, h in (("dual", H0), ("dual", H), ("trial", H0), ("trial", 0)) for e in (True, False)])
+@pytest.mark.parametrize("full_cov", [False, True])
+@pytest.mark.parametrize("est_cb", [True, False])
+@pytest.mark.parametrize("prebuilt", [False, True])
+def test_fit_batch_sparse_family(pkg, rec, model, h0, full_cov, est_cb, est_priors, prebuilt):
+    grouped = model in ("dual", "trial")
+    Ys, ps, Yall, col_off = _fit_sets(pkg, model, (3, 1, 2) if full_cov else (3, 2, 4), h0)   # (the diagonal form needs M >= 2)
+    p0s = copy.deepcopy(ps)
+    Recorder.fit_iters, Recorder.fit_status = [5, 0, 7, 6], [0, 0, 1, 0]      # one fit that never ran, one that stopped on a bad value
+    bags = pkg.SparseBags(Ys, H) if prebuilt else Ys
+    kw = dict(est_priors=est_priors) if grouped else {}
+    ds = getattr(pkg, FIT_FN[model])(bags, ps, 9, eps=1e-3, full_cov=full_cov, est_cb=est_cb, bag_of=list(BAG_OF), **kw)
+    want = _open_bags(pkg, 0, model, Yall) + [_want_sparse_family_call(pkg, model, p0s, col_off, 9, 1e-3, full_cov, est_cb, est_priors)]
+    if not prebuilt:
+        want.append(bound(pkg, 0, "close"))
+    check_calls(rec, want)
+    r = rec[2].ret
+    assert ds == [float(v) for v in r["d"]] and all(type(v) is float for v in ds)
+    s0 = 0
+    for f, (p, p0) in enumerate(zip(ps, p0s)):
+        check_fields(p, p0, _sparse_family_written(model, p0, r, f, s0, est_cb, est_priors))
+        assert (p.iters, p.status) == (Recorder.fit_iters[f], Recorder.fit_status[f])
+        assert type(p.iters) is int and type(p.status) is int and type(p.sigmaHat) is float and type(p.zeta) is float
+        assert p.BHat.flags.f_contiguous
+        s0 += p0.M * H
+
+
+@pytest.mark.parametrize("model", ["sparse", "dual", "trial", "masked", "basic"])
+def test_fit_batch_defaults(pkg, rec, model):
+    """bag_of left out: fit f on bag f; eps, full_cov, est_cb, est_priors and form at their defaults."""
+    Ys, ps, Yall, col_off = _fit_sets(pkg, model, (3, 2, 4), bag_of=[0, 1, 2])
+    p0s = copy.deepcopy(ps)
+    if model == "basic":
+        pkg.vbmf_batch_(Ys, ps, 4)
+        want = _want_basic_call(pkg, p0s, col_off, 4, 1e-6, False, False, "stream", bag_of=[0, 1, 2])
+    else:
+        getattr(pkg, FIT_FN[model])(Ys, ps, 4)
+        want = _want_sparse_family_call(pkg, model, p0s, col_off, 4, 1e-6, False, True, True, bag_of=[0, 1, 2])
+    check_calls(rec, _open_bags(pkg, 0, model, Yall) + [want, bound(pkg, 0, "close")])
+
+
+def _want_basic_call(pkg, p0s, col_off, niter, eps, est_covs, est_var, form, bag_of=BAG_OF):
+    return bound(pkg, 0, "fit_batched", col_off, bag_of, niter, eps, [p.BHat for p in p0s], [p.SigmaB for p in p0s],
+                 [np.diag(p.CA) for p in p0s], [np.diag(p.CB) for p in p0s], [p.sigma2 for p in p0s], est_covs=est_covs, est_var=est_var,
+                 form=form)
+
+
+@pytest.mark.parametrize("form", ["stream", "gram", "auto"])
+@pytest.mark.parametrize("est", [(False, False), (True, False), (True, True)])
+@pytest.mark.parametrize("prebuilt", [False, True])
+def test_fit_batch_basic(pkg, rec, form, est, prebuilt):
+    Ys, ps, Yall, col_off = _fit_sets(pkg, "basic", (3, 1, 2))
+    p0s = copy.deepcopy(ps)
+    CAs, CBs = [p.CA for p in ps], [p.CB for p in ps]
+    Recorder.fit_iters, Recorder.fit_status = [5, 0, 7, 6], [0, 0, 1, 0]
+    bags = pkg.Bags(Ys, H) if prebuilt else Ys
+    out = pkg.vbmf_batch_(bags, ps, 9, eps=1e-3, est_covs=est[0], est_var=est[1], bag_of=list(BAG_OF), form=form)
+    want = _open_bags(pkg, 0, "basic", Yall) + [_want_basic_call(pkg, p0s, col_off, 9, 1e-3, est[0], est[1], form)]
+    if not prebuilt:
+        want.append(bound(pkg, 0, "close"))
+    check_calls(rec, want)
+    r = rec[2].ret
+    assert len(out) == len(ps) and all(a is b for a, b in zip(out, ps))
+    for f, (p, p0) in enumerate(zip(ps, p0s)):
+        ca, cb = p0.CA.copy(), p0.CB.copy()
+        np.fill_diagonal(ca, r["CA"][f])
+        np.fill_diagonal(cb, r["CB"][f])
+        check_fields(p, p0, dict(AHat=r["AHat"][f], BHat=r["BHat"][f], SigmaA=r["SigmaA"][f], SigmaB=r["SigmaB"][f], CA=ca, CB=cb,
+                                 invCA=np.diag(1.0 / r["CA"][f]), invCB=np.diag(1.0 / r["CB"][f]), sigma2=r["sigma2"][f],
+                                 YHat=r["BHat"][f] @ r["AHat"][f].T))
+        assert p.CA is CAs[f] and p.CB is CBs[f]                         # the diagonals are written in place (src/vbmf.jl:131,143)
+        assert (p.form_used, p.iters, p.d, p.status) == (r["form_used"][f], Recorder.fit_iters[f], r["d"][f], Recorder.fit_status[f])
+        assert [type(v) for v in (p.form_used, p.iters, p.d, p.status, p.sigma2)] == [int, int, float, int, float]
+        assert p.AHat.flags.f_contiguous and p.BHat.flags.f_contiguous
+
+
+@pytest.mark.parametrize("kind", ["list", "Bags", "SparseBags"])
+def test_row_gram_batch(pkg, rec, kind):
+    Ys, _, Yall, col_off = _fit_sets(pkg, "basic", (3, 1, 2))
+    if kind == "list":
+        K = pkg.row_gram_batch(Ys)
+        want = [bound(pkg, 0, "__init__", L, 6, 1, **pkg._defaults), bound(pkg, 0, "set_Y", Yall), bound(pkg, 0, "row_gram", col_off),
+                bound(pkg, 0, "close")]
+    else:
+        K = pkg.row_gram_batch(getattr(pkg, kind)(Ys, H))
+        want = _open_bags(pkg, 0, "basic" if kind == "Bags" else "sparse", Yall) + [bound(pkg, 0, "row_gram", col_off)]
+    check_calls(rec, want)
+    assert K is rec[2].ret
+
+
+# ---- the callers of the batched fits: which call, which sets in which order, what comes back ---------------------------------------
+def _only_fit_call(rec, name, n_bags_cols):
+    assert [c.name for c in rec] == ["__init__", "set_Y", name, "close"]
+    assert rec[0].args["M"] == n_bags_cols
+    return rec[2]
+
+
+@pytest.mark.parametrize("accepted", [None, 2])
+def test_fit_restarts_sparse(pkg, rec, accepted):
+    Y = np.random.default_rng(3).standard_normal((L, M))
+    Recorder.fit_d = [0.5, np.nan, 2e-5 if accepted else 0.25, 1e-9 if accepted else 0.125]
+    p = pkg.fit_restarts(Y, H, 30, nstarts=4, eps=1e-5, rng=np.random.default_rng(5))
+    c = _only_fit_call(rec, "sparse_fit_batched", M)
+    rng = np.random.default_rng(5)
+    inits = [pkg.vbmf_sparse_init(Y, H, rng=rng) for _ in range(4)]
+    a = c.args
+    assert same(rec[1].args["Y"], Y) and same(a["col_off"], [0, M]) and same(a["fit_bag"], [0, 0, 0, 0])
+    assert (a["niter"], a["eps"], a["H0"], a["full_cov"], a["est_cb"], a["est_priors"]) == (30, 1e-5, H, False, True, False)
+    assert same(a["BHat"], [q.BHat for q in inits]) and same(a["CA"], np.concatenate([q.CA for q in inits]))
+    k = 3 if accepted is None else accepted                         # the first with d <= 2 eps, else the last
+    assert same(p.BHat, c.ret["BHat"][k]) and p.iters == 3 + k
+
+
+def test_fit_restarts_dual(pkg, rec):
+    Y = np.random.default_rng(3).standard_normal((L, M))
+    p = pkg.fit_restarts(Y, H, 30, model="dual", H0=H0, nstarts=3, rng=np.random.default_rng(5))
+    c = _only_fit_call(rec, "sparse_fit_batched", M)
+    rng = np.random.default_rng(5)
+    inits = [pkg.vbmf_dual_init(Y, H, H0, rng=rng) for _ in range(3)]
+    a = c.args
+    assert same(a["fit_bag"], [0, 0, 0]) and same(a["BHat"], [q.BHat for q in inits])
+    assert (a["niter"], a["eps"], a["H0"], a["full_cov"], a["est_cb"], a["est_priors"]) == (30, 1e-4, H0, True, True, True)
+    assert same(p.BHat, c.ret["BHat"][0])                           # the recorder's factors are far from zero: the first set
+
+
+def test_train_local_folds(pkg, rec):
+    rng = np.random.default_rng(4)
+    folds = [(rng.standard_normal((L, a)), rng.standard_normal((L, b))) for a, b in ((2, 3), (0, 2), (3, 1))]
+    ps = pkg.train_local_folds(folds, H, 1, 25, rng=np.random.default_rng(5))
+    c = _only_fit_call(rec, "local_fit_batched", 11)                # one round: the recorder's factors are far from zero
+    rng = np.random.default_rng(5)
+    inits = [pkg.vbmf_sparse_init(np.concatenate(f, axis=1), H, H1=1, labels=np.arange(1, f[0].shape[1] + 1), rng=rng) for f in folds]
+    a = c.args
+    assert same(rec[1].args["Y"], np.concatenate([np.concatenate(f, axis=1) for f in folds], axis=1))
+    assert same(a["col_off"], [0, 5, 7, 11]) and same(a["fit_bag"], [0, 1, 2]) and same(a["M0"], [2, 0, 3])
+    assert (a["niter"], a["eps"], a["H0"], a["mask_H1"], a["full_cov"], a["est_cb"], a["est_priors"]) == (25, 1e-4, H, 1, False, True, False)
+    assert same(a["BHat"], [q.BHat for q in inits])
+    assert len(ps) == 3 and all(same(p.BHat, c.ret["BHat"][f]) for f, p in enumerate(ps))
+
+
+@pytest.mark.parametrize("solver", ["basic", "sparse"])
+def test_train_folds(pkg, rec, solver):
+    rng = np.random.default_rng(4)
+    folds = [(rng.standard_normal((L, a)), rng.standard_normal((L, b))) for a, b in ((2, 3), (0, 2), (3, 2))]
+    n = 1 if solver == "basic" else 10
+    Recorder.fit_d = None if solver == "basic" else [1.0] * 10 + [1.0, 1e-7] + [1.0] * 8 + [1.0] * 20   # bag 1: the second start is kept
+    out = pkg.train_folds(folds, solver, H, 25, eps=1e-5, rng=np.random.default_rng(5), **(dict(form="auto") if solver == "basic" else {}))
+    c = _only_fit_call(rec, "fit_batched" if solver == "basic" else "sparse_fit_batched", 10)
+    used = [Y for k in (0, 2) for Y in folds[k]]                    # the fold with an empty class is left out (:97-100)
+    rng = np.random.default_rng(5)
+    init = pkg.vbmf_init if solver == "basic" else pkg.vbmf_sparse_init
+    inits = [init(Y, H, rng=rng) for Y in used for _ in range(n)]
+    a = c.args
+    assert same(rec[1].args["Y"], np.concatenate(used, axis=1)) and same(a["col_off"], [0, 2, 5, 8, 10])
+    assert same(a["fit_bag"], np.repeat(np.arange(4), n)) and same(a["BHat"], [q.BHat for q in inits])
+    if solver == "basic":
+        assert (a["niter"], a["eps"], a["est_covs"], a["est_var"], a["form"]) == (25, 1e-5, True, True, "auto")
+        kept = [0, 1, 2, 3]
+    else:
+        assert (a["niter"], a["eps"], a["H0"], a["full_cov"], a["est_cb"], a["est_priors"]) == (25, 1e-5, H, False, True, False)
+        kept = [9, 11, 29, 39]                                      # the first start with d <= 2 eps, else the last
+    assert out[1] == (0, 0)
+    got = [out[0][0], out[0][1], out[2][0], out[2][1]]
+    assert all(same(p.BHat, c.ret["BHat"][f]) for p, f in zip(got, kept))

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import copy as _copy
 import weakref
+from contextlib import contextmanager
 from dataclasses import dataclass, field, fields
 from typing import Callable, NamedTuple, Optional
 
@@ -972,7 +973,7 @@ def lowerBound_trial(Y, params, clamp=True):
 
 # =================================================================================================
 # What differs between the ARD-sparse model and its grouped siblings; everything else is one code path (_push, _pull, _step,
-# _vbmf_ard, _lower_bound, vbls_, vbls_sparse_batch_) over the one vbmf_sparse_* device context
+# _vbmf_ard, _lower_bound, vbls_, vbls_sparse_batch_, _sparse_fit_batch) over the one vbmf_sparse_* device context
 # =================================================================================================
 @dataclass(frozen=True, eq=False)
 class _Model:
@@ -982,6 +983,7 @@ class _Model:
                                            # group 0 feeds alpha0 / beta0 of vbmf_sparse_hyper
     run: Callable                          # (ctx, niter, eps, est_cb, est_priors) -> (sweeps done, d, trace)
     labels: bool = False                   # sparse only: labels0 / H1 pushed, alpha == alpha0 + 1/2 checked
+    M0: bool = False                       # trial only: the last group is split at row M0 of A (a batched fit takes M0 per fit)
     set_priors: Optional[Callable] = None  # (ctx, params)
     get_priors: Optional[Callable] = None  # ctx -> {field: value}
     views: Optional[Callable] = None       # params: the group views of AHat / CA / beta
@@ -1001,7 +1003,7 @@ _MODELS = {
         (("alpha01", "beta01", "alpha1"), ("alpha02", "beta02", "alpha2"), ("alpha03", "beta03", "alpha3")),
         run=lambda c, k, eps, est_cb, est_priors: c.trial_run(k, eps=eps, est_cb=est_cb, est_priors=est_priors),
         set_priors=lambda c, p: c.trial_set_priors(p.H0, p.M0, {k: getattr(p, k) for k in Context.TRIAL_KEYS}),
-        get_priors=lambda c: c.trial_get_priors()[2], views=_trial_views),
+        get_priors=lambda c: c.trial_get_priors()[2], views=_trial_views, M0=True),
 }
 
 
@@ -1066,21 +1068,60 @@ def _side_by_side(Ys, H, refuse):
     return L, Ms, col_off, Yall
 
 
-class Bags:
-    """Many bags (L x M_b matrices with one L) uploaded side by side as ONE L x sum(M_b) matrix on the device, for vbls_batch_.
-    One upload serves several bases: the MIL classifier runs every bag against two trained models (examples/mil_util.jl:473-479)."""
+class _Uploaded:
+    """Many bags (L x M_b matrices with one L) uploaded side by side as ONE L x sum(M_b) matrix on the device: .ctx holds it, bag b is
+    its columns col_off[b] .. col_off[b+1]-1."""
 
-    def __init__(self, Ys, H):
-        self.L, self.Ms, self.col_off, Yall = _side_by_side(Ys, H, _batch_refuse)
+    def _lay_out(self, Ys, H, refuse):
+        self.L, self.Ms, self.col_off, Yall = _side_by_side(Ys, H, refuse)
         self.H, self.M = int(H), Yall.shape[1]
-        self.session = Session(self.L, self.M, self.H)
-        self.session.set_Y(Yall)
+        return Yall
 
     def __len__(self):
         return len(self.Ms)
 
     def close(self):
-        self.session.close()
+        self.ctx.close()
+
+
+class Bags(_Uploaded):
+    """The bags in a basic-model context, for vbls_batch_ and vbmf_batch_.  One upload serves several bases: the MIL classifier runs
+    every bag against two trained models (examples/mil_util.jl:473-479)."""
+
+    def __init__(self, Ys, H):
+        Yall = self._lay_out(Ys, H, _batch_refuse)
+        self.session = Session(self.L, self.M, self.H)
+        self.session.set_Y(Yall)
+
+    @property
+    def ctx(self):
+        return self.session.ctx
+
+
+def _bag_shapes(Ys, H, cls, refuse):
+    """(L, [M_b]) of the bags the sets of rank H are for, checked on the host: an upload (a `cls` made for this H) or a list of
+    matrices (_batch_shapes)."""
+    if isinstance(Ys, _Uploaded):
+        if not isinstance(Ys, cls):
+            refuse(f"a {type(Ys).__name__} where a {cls.__name__} or a list of matrices is taken")
+        if Ys.H != H:
+            refuse(f"the {type(Ys).__name__} were uploaded for H = {Ys.H}, the parameters have H = {H}")
+        return Ys.L, Ys.Ms
+    return _batch_shapes(Ys, H, refuse)
+
+
+@contextmanager
+def _on_device(Ys, H, cls):
+    """Ys on the device: itself where it is an upload already, else a `cls` opened here and closed on the way out."""
+    if isinstance(Ys, _Uploaded):
+        yield Ys
+        return
+    bags = cls(Ys, H)
+    try:
+        yield bags
+    finally:
+        bags.close()
+
 
 def _batch_check_params(L, Ms, H, params, refuse=_batch_refuse):
     if len(params) != len(Ms):
@@ -1108,17 +1149,11 @@ def vbls_batch_(Ys, params, niter):
     Every bag runs all niter iterations in one workgroup of one launch (include/vbmf_hip.h, vbmf_run_fixed_basis_batched)."""
     params = list(params)
     H = int(params[0].H) if params else 0
-    if isinstance(Ys, Bags):
-        bags = Ys
-        if bags.H != H:
-            _batch_refuse(f"the Bags were uploaded for H = {bags.H}, the parameters have H = {H}")
-        _batch_check_params(bags.L, bags.Ms, H, params)
-    else:
-        L, Ms = _batch_shapes(Ys, H)
-        _batch_check_params(L, Ms, H, params)
-        bags = Bags(Ys, H)
+    L, Ms = _bag_shapes(Ys, H, Bags, _batch_refuse)
+    _batch_check_params(L, Ms, H, params)
+    bags = Ys if isinstance(Ys, Bags) else Bags(Ys, H)
     p0 = params[0]
-    ctx = bags.session.ctx
+    ctx = bags.ctx
     ctx.set_state(np.zeros((bags.M, H)), p0.BHat, p0.SigmaA, p0.SigmaB, np.diag(p0.CA), np.diag(p0.CB), p0.sigma2)
     r = ctx.run_fixed_basis_batched(bags.col_off, int(niter), [p.sigma2 for p in params], [np.diag(p.CA) for p in params])
     idx = np.arange(H)
@@ -1140,23 +1175,16 @@ def _sbatch_refuse(why):
     raise ValueError(f"vbls_sparse_batch_: {why}; run such bags one at a time with vbls_")
 
 
-class SparseBags:
-    """Many bags (L x M_b matrices with one L) uploaded side by side as ONE L x sum(M_b) matrix into a sparse-variant context, for
-    vbls_sparse_batch_.  One upload serves several bases (examples/mil_util.jl:469-521 runs every bag against two trained models).
-    ctx_kw: Context options over the package defaults (e.g. reference_compat)."""
+class SparseBags(_Uploaded):
+    """The bags in a sparse-variant context, for vbls_sparse_batch_ and the sparse family's batched fits.  One upload serves several
+    bases (examples/mil_util.jl:469-521 runs every bag against two trained models).  ctx_kw: Context options over the package
+    defaults (e.g. reference_compat)."""
 
     def __init__(self, Ys, H, **ctx_kw):
-        self.L, self.Ms, self.col_off, Yall = _side_by_side(Ys, H, _sbatch_refuse)
-        self.H, self.M = int(H), Yall.shape[1]
+        Yall = self._lay_out(Ys, H, _sbatch_refuse)
         self.ctx_kw = {**_defaults, **ctx_kw}
         self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **self.ctx_kw)
         self.ctx.set_Y(Yall)
-
-    def __len__(self):
-        return len(self.Ms)
-
-    def close(self):
-        self.ctx.close()
 
 
 def _sbatch_check_params(L, Ms, H, params, refuse=_sbatch_refuse):
@@ -1209,16 +1237,9 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
     H = int(params[0].H) if params else 0
     if H > _BATCH_MAX_H:
         _sbatch_refuse(f"H = {H} > {_BATCH_MAX_H}")
-    if isinstance(Ys, SparseBags):
-        bags = Ys
-        if bags.H != H:
-            _sbatch_refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
-        m = _sbatch_check_params(bags.L, bags.Ms, H, params)
-    else:
-        L, Ms = _batch_shapes(Ys, H, _sbatch_refuse)
-        m = _sbatch_check_params(L, Ms, H, params)
-        bags = SparseBags(Ys, H)
-    try:
+    L, Ms = _bag_shapes(Ys, H, SparseBags, _sbatch_refuse)
+    m = _sbatch_check_params(L, Ms, H, params)
+    with _on_device(Ys, H, SparseBags) as bags:
         p0 = params[0]
         ctx = bags.ctx
         zero = np.zeros(bags.M * H)
@@ -1229,17 +1250,9 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
                                                [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
                                                [p.sigmaHat for p in params], np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1)
                                                                                               for p in params]), full_cov=full_cov)
-    finally:
-        if not isinstance(Ys, SparseBags):
-            bags.close()
     out = []
     for b, p in enumerate(params):
-        s0, s1 = bags.col_off[b] * H, bags.col_off[b + 1] * H
-        p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
-        p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
-        p.AHat = p.ATVecHat.reshape(p.M, H).copy()
-        p.SigmaA = r["SigmaA"][b].copy()
-        p.sigmaHat, p.zeta = float(r["sigmaHat"][b]), float(r["zeta"][b])
+        _write_A_side(p, r, b, bags.col_off[b] * H)
         if m.views is not None:                                         # what _pull fills, the priors as updateCA! sets them:
             m.views(p)                                                  # src/vbmf_dual.jl:324-325, src/vbmf_trial.jl:359-361
             for a0, _, a in m.groups:
@@ -1257,25 +1270,24 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
 _FIT_MAX_H = 32
 
 
-def _fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of):
+def _fit_front(fn, one, kind, cls, Ys, params, niter, bag_of):
+    """What every whole-fit batched function does before its own checks: the refuser, the sets as a list, one H <= 32, niter >= 1, the
+    bags' shapes (Ys: a list of matrices or a `cls`), bag_of defaulted and validated, and per fit its type, bag, H and (L, M).
+    Returns (refuse, params, bag_of, H, L, [M_b])."""
     def refuse(why):
         raise ValueError(f"{fn}: {why}; run such fits one at a time with {one}")
+    only = "the basic model's vbmf_parameters only" if kind is vbmf_parameters else f"{kind.__name__} only, one model type per call"
     params = list(params)
     if not params:
         refuse("no parameter sets")
+    if type(params[0]) is not kind:
+        refuse(f"fit 0: {type(params[0]).__name__} ({only})")
     H = int(params[0].H)
     if H > _FIT_MAX_H:
         refuse(f"H = {H} > {_FIT_MAX_H}")
     if int(niter) < 1:
         refuse(f"niter = {niter} < 1")
-    if isinstance(Ys, SparseBags):
-        bags = Ys
-        if bags.H != H:
-            refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
-        L, Ms, ctx_kw = bags.L, bags.Ms, bags.ctx_kw
-    else:
-        bags = None
-        (L, Ms), ctx_kw = _batch_shapes(Ys, H, refuse), _defaults
+    L, Ms = _bag_shapes(Ys, H, cls, refuse)
     if bag_of is None:
         if len(params) != len(Ms):
             refuse(f"{len(Ms)} bags but {len(params)} parameter sets and no bag_of")
@@ -1283,21 +1295,59 @@ def _fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_prio
     bag_of = [int(b) for b in bag_of]
     if len(bag_of) != len(params):
         refuse(f"{len(params)} parameter sets but {len(bag_of)} entries in bag_of")
-    m = _MODELS[kind]
-    repeat = bool(ctx_kw.get("reference_compat", capi.VBMF_COMPAT_DEFAULT) & capi.VBMF_COMPAT_SPARSE_REPEAT)
     for f, (p, b) in enumerate(zip(params, bag_of)):
         if type(p) is not kind:
-            refuse(f"fit {f}: {type(p).__name__} ({kind.__name__} only, one model type per call)")
+            refuse(f"fit {f}: {type(p).__name__} ({only})")
         if not 0 <= b < len(Ms):
             refuse(f"fit {f}: bag_of = {b} outside 0..{len(Ms) - 1}")
         if int(p.H) != H:
             refuse(f"fit {f}: H = {p.H} beside H = {H}")
         if (p.L, p.M) != (L, Ms[b]):
             refuse(f"fit {f}: bag {b} is {L} x {Ms[b]}, its parameters describe {(p.L, p.M)}")
-        if m.labels and (int(p.H1) > 0 or np.asarray(p.labels).size > 0):
-            refuse(f"fit {f} has labels / H1 > 0 (a label mask)")
-        if not m.labels and (int(p.H0) != int(params[0].H0) or not 1 <= int(p.H0) <= H):
-            refuse(f"fit {f}: H0 = {p.H0} (one H0 in 1..H per call)")
+    return refuse, params, bag_of, H, L, Ms
+
+
+def _write_A_side(p, r, k, s0):
+    """What a batched call's results r hold of set k's A side, its M H-long vectors starting at s0: ATVecHat, diagSigmaATVec, CA, beta,
+    AHat, SigmaA, sigmaHat, zeta (all copies).  Returns where the next set's vectors start."""
+    s1 = s0 + p.M * p.H
+    p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
+    p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
+    p.AHat = p.ATVecHat.reshape(p.M, p.H).copy()
+    p.SigmaA = r["SigmaA"][k].copy()
+    p.sigmaHat, p.zeta = float(r["sigmaHat"][k]), float(r["zeta"][k])
+    return s1
+
+
+def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of, masked=False):
+    """The four batched fits of the sparse family: the host checks, the one device call, the fields of every set; returns the list of d.
+    The models with a per-fit M0 -- the three-group one and, with masked, the sparse one under a label mask -- go through
+    vbmf_local_fit_batched (H0 in 0..H), the other two through vbmf_sparse_fit_batched (H0 in 1..H)."""
+    refuse, params, bag_of, H, L, Ms = _fit_front(fn, one, kind, SparseBags, Ys, params, niter, bag_of)
+    m = _MODELS[kind]
+    local = masked or m.M0
+    ctx_kw = Ys.ctx_kw if isinstance(Ys, SparseBags) else _defaults
+    repeat = bool(ctx_kw.get("reference_compat", capi.VBMF_COMPAT_DEFAULT) & capi.VBMF_COMPAT_SPARSE_REPEAT)
+    M0s = []
+    for f, (p, b) in enumerate(zip(params, bag_of)):
+        if masked:
+            if int(p.H1) != int(params[0].H1) or not 0 <= int(p.H1) <= H:
+                refuse(f"fit {f}: H1 = {p.H1} (one H1 in 0..H per call)")
+            lab = np.asarray(p.labels).reshape(-1)
+            if lab.size > Ms[b] or not np.array_equal(lab, np.arange(1, lab.size + 1)):
+                refuse(f"fit {f}: labels are not the prefix 1..M0 of the columns (the rows of AHat the batched mask covers)")
+            M0s.append(int(lab.size))
+        elif m.labels:
+            if int(p.H1) > 0 or np.asarray(p.labels).size > 0:
+                refuse(f"fit {f} has labels / H1 > 0 (a label mask)")
+        else:
+            lo = 0 if local else 1
+            if int(p.H0) != int(params[0].H0) or not lo <= int(p.H0) <= H:
+                refuse(f"fit {f}: H0 = {p.H0} (one H0 in {lo}..H per call)")
+            if local:
+                if not 0 <= int(p.M0) <= Ms[b]:
+                    refuse(f"fit {f}: M0 = {p.M0} outside 0..M = {Ms[b]}")
+                M0s.append(int(p.M0))
         if np.shape(p.BHat) != (L, H) or np.shape(p.SigmaB) != (H, H) or np.size(p.CB) != H or np.size(p.CA) != Ms[b] * H:
             refuse(f"fit {f}: BHat, SigmaB, CB or CA does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
         if not full_cov and repeat and Ms[b] < 2:
@@ -1305,44 +1355,39 @@ def _fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_prio
         _check_derived(p)
         if _alpha_not_derived(m, p):
             refuse(f"fit {f}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
-    own = bags is None
-    if own:
-        bags = SparseBags(Ys, H)
-    (a0, b0, _), (a1, b1, _) = m.groups[0], m.groups[-1]
-    try:
-        r = bags.ctx.sparse_fit_batched(
-            bags.col_off, bag_of, int(niter), float(eps), [p.gamma0 + p.L / 2 for p in params], [p.delta0 for p in params],
-            [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
-            [[getattr(p, a0), getattr(p, b0), getattr(p, a1), getattr(p, b1)] for p in params],
+    # the hyper-prior pairs of the entry's two (three) groups; a model with fewer groups gives its last pair again
+    pairs = [k for g in range(3 if local else 2) for k in m.groups[min(g, len(m.groups) - 1)][:2]]
+    args = (bag_of, int(niter), float(eps), [p.gamma0 + p.L / 2 for p in params], [p.delta0 for p in params],
+            [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params], [[getattr(p, k) for k in pairs] for p in params],
             np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]), np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]),
             np.stack([np.asarray(p.CB, dtype=np.float64).reshape(H) for p in params]), [p.sigmaHat for p in params],
-            np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]),
-            H0=H if m.labels else int(params[0].H0), full_cov=full_cov, est_cb=est_cb, est_priors=est_priors and not m.labels)
-    finally:
-        if own:
-            bags.close()
+            np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]))
+    kw = dict(H0=H if m.labels else int(params[0].H0), full_cov=full_cov, est_cb=est_cb, est_priors=est_priors and not m.labels)
+    with _on_device(Ys, H, SparseBags) as bags:
+        if local:
+            r = bags.ctx.local_fit_batched(bags.col_off, *args, M0s, mask_H1=int(params[0].H1) if masked else 0, **kw)
+        else:
+            r = bags.ctx.sparse_fit_batched(bags.col_off, *args, **kw)
     s0 = 0
     for f, p in enumerate(params):
-        s1 = s0 + p.M * H
-        p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
-        p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
-        s0 = s1
-        p.AHat = p.ATVecHat.reshape(p.M, H).copy()
-        p.SigmaA = r["SigmaA"][f].copy()
+        s0 = _write_A_side(p, r, f, s0)
         p.BHat, p.SigmaB, p.CB = np.array(r["BHat"][f], order="F"), r["SigmaB"][f].copy(), r["CB"][f].copy()
         if est_cb:
             p.delta = r["delta"][f].copy()
-        p.sigmaHat, p.zeta = float(r["sigmaHat"][f]), float(r["zeta"][f])
         p.iters, p.status = int(r["iters"][f]), int(r["status"][f])
         if m.views is not None:
             m.views(p)
-            # the posterior shapes as the last updateCA! left them (src/vbmf_dual.jl:324-325): the hyper-prior that sweep STARTED
-            # from + 1/2, which est_priors has since refitted -- recovered as CA * beta of the group's first entry
-            # (a fit that stopped on a non-finite value, status 1, keeps the shapes of its start values)
-            ok = est_priors and p.iters > 0 and p.status == 0
-            p.alpha0 = float(p.CA0[0] * p.beta0[0]) if ok else p.alpha00 + 0.5
-            p.alpha1 = float(p.CA1[0] * p.beta1[0]) if ok and p.CA1.size else p.alpha01 + 0.5
-            p.alpha00, p.beta00, p.alpha01, p.beta01 = (float(v) for v in r["priors4"][f])
+            if local:
+                for k, v in zip(Context.TRIAL_KEYS, r["priors9"][f]):   # the pairs, and the shapes the last updateCA! used
+                    setattr(p, k, float(v))
+            else:
+                # the posterior shapes as the last updateCA! left them (src/vbmf_dual.jl:324-325): the hyper-prior that sweep STARTED
+                # from + 1/2, which est_priors has since refitted -- recovered as CA * beta of the group's first entry
+                # (a fit that stopped on a non-finite value, status 1, keeps the shapes of its start values)
+                ok = est_priors and p.iters > 0 and p.status == 0
+                p.alpha0 = float(p.CA0[0] * p.beta0[0]) if ok else p.alpha00 + 0.5
+                p.alpha1 = float(p.CA1[0] * p.beta1[0]) if ok and p.CA1.size else p.alpha01 + 0.5
+                p.alpha00, p.beta00, p.alpha01, p.beta01 = (float(v) for v in r["priors4"][f])
             p.alpha = _posterior_shapes(p, m)
         p.YHat = _host_YHat(p)
     return [float(v) for v in r["d"]]
@@ -1355,114 +1400,13 @@ def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True,
     list of d.  Ys: a list of L x M_b arrays or a SparseBags; params: one vbmf_sparse_parameters per fit, one H <= 32, no labels;
     bag_of[f]: the fit's bag (default: fit f on bag f), so restarts share one upload.  Every fit's whole loop runs in one workgroup of
     one launch (include/vbmf_hip.h, vbmf_sparse_fit_batched)."""
-    return _fit_batch("vbmf_sparse_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb, False, bag_of)
+    return _sparse_fit_batch("vbmf_sparse_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb, False, bag_of)
 
 
 def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True):
     """vbmf_dual! for many independent fits in one device call (the restart loop of examples/mil_util.jl:347-379): see
     vbmf_sparse_batch_; params: one vbmf_dual_parameters per fit, all with one H0."""
-    return _fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of)
-
-
-def _local_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of):
-    """vbmf_trial_batch_ / vbmf_sparse_masked_batch_: the host checks, the one vbmf_local_fit_batched call, the fields of every set."""
-    def refuse(why):
-        raise ValueError(f"{fn}: {why}; run such fits one at a time with {one}")
-    params = list(params)
-    if not params:
-        refuse("no parameter sets")
-    if type(params[0]) is not kind:
-        refuse(f"fit 0: {type(params[0]).__name__} ({kind.__name__} only, one model type per call)")
-    H = int(params[0].H)
-    if H > _FIT_MAX_H:
-        refuse(f"H = {H} > {_FIT_MAX_H}")
-    if int(niter) < 1:
-        refuse(f"niter = {niter} < 1")
-    if isinstance(Ys, SparseBags):
-        bags = Ys
-        if bags.H != H:
-            refuse(f"the SparseBags were uploaded for H = {bags.H}, the parameters have H = {H}")
-        L, Ms, ctx_kw = bags.L, bags.Ms, bags.ctx_kw
-    else:
-        bags = None
-        (L, Ms), ctx_kw = _batch_shapes(Ys, H, refuse), _defaults
-    if bag_of is None:
-        if len(params) != len(Ms):
-            refuse(f"{len(Ms)} bags but {len(params)} parameter sets and no bag_of")
-        bag_of = range(len(Ms))
-    bag_of = [int(b) for b in bag_of]
-    if len(bag_of) != len(params):
-        refuse(f"{len(params)} parameter sets but {len(bag_of)} entries in bag_of")
-    m = _MODELS[kind]
-    masked = m.labels
-    repeat = bool(ctx_kw.get("reference_compat", capi.VBMF_COMPAT_DEFAULT) & capi.VBMF_COMPAT_SPARSE_REPEAT)
-    M0s = []
-    for f, (p, b) in enumerate(zip(params, bag_of)):
-        if type(p) is not kind:
-            refuse(f"fit {f}: {type(p).__name__} ({kind.__name__} only, one model type per call)")
-        if not 0 <= b < len(Ms):
-            refuse(f"fit {f}: bag_of = {b} outside 0..{len(Ms) - 1}")
-        if int(p.H) != H:
-            refuse(f"fit {f}: H = {p.H} beside H = {H}")
-        if (p.L, p.M) != (L, Ms[b]):
-            refuse(f"fit {f}: bag {b} is {L} x {Ms[b]}, its parameters describe {(p.L, p.M)}")
-        if masked:
-            if int(p.H1) != int(params[0].H1) or not 0 <= int(p.H1) <= H:
-                refuse(f"fit {f}: H1 = {p.H1} (one H1 in 0..H per call)")
-            lab = np.asarray(p.labels).reshape(-1)
-            if lab.size > Ms[b] or not np.array_equal(lab, np.arange(1, lab.size + 1)):
-                refuse(f"fit {f}: labels are not the prefix 1..M0 of the columns (the rows of AHat the batched mask covers)")
-            M0s.append(int(lab.size))
-        else:
-            if int(p.H0) != int(params[0].H0) or not 0 <= int(p.H0) <= H:
-                refuse(f"fit {f}: H0 = {p.H0} (one H0 in 0..H per call)")
-            if not 0 <= int(p.M0) <= Ms[b]:
-                refuse(f"fit {f}: M0 = {p.M0} outside 0..M = {Ms[b]}")
-            M0s.append(int(p.M0))
-        if np.shape(p.BHat) != (L, H) or np.shape(p.SigmaB) != (H, H) or np.size(p.CB) != H or np.size(p.CA) != Ms[b] * H:
-            refuse(f"fit {f}: BHat, SigmaB, CB or CA does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
-        if not full_cov and repeat and Ms[b] < 2:
-            refuse(f"fit {f} works on a 1-column bag: the diagonal form under the repeat layout needs M >= 2")
-        _check_derived(p)
-        if _alpha_not_derived(m, p):
-            refuse(f"fit {f}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
-    own = bags is None
-    if own:
-        bags = SparseBags(Ys, H)
-    groups = [m.groups[min(k, len(m.groups) - 1)] for k in range(3)]       # (the masked model: its one pair three times)
-    try:
-        r = bags.ctx.local_fit_batched(
-            bags.col_off, bag_of, int(niter), float(eps), [p.gamma0 + p.L / 2 for p in params], [p.delta0 for p in params],
-            [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
-            [[getattr(p, k) for a0, b0, _ in groups for k in (a0, b0)] for p in params],
-            np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]), np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]),
-            np.stack([np.asarray(p.CB, dtype=np.float64).reshape(H) for p in params]), [p.sigmaHat for p in params],
-            np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]), M0s,
-            H0=H if masked else int(params[0].H0), mask_H1=int(params[0].H1) if masked else 0, full_cov=full_cov, est_cb=est_cb,
-            est_priors=est_priors and not masked)
-    finally:
-        if own:
-            bags.close()
-    s0 = 0
-    for f, p in enumerate(params):
-        s1 = s0 + p.M * H
-        p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
-        p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
-        s0 = s1
-        p.AHat = p.ATVecHat.reshape(p.M, H).copy()
-        p.SigmaA = r["SigmaA"][f].copy()
-        p.BHat, p.SigmaB, p.CB = np.array(r["BHat"][f], order="F"), r["SigmaB"][f].copy(), r["CB"][f].copy()
-        if est_cb:
-            p.delta = r["delta"][f].copy()
-        p.sigmaHat, p.zeta = float(r["sigmaHat"][f]), float(r["zeta"][f])
-        p.iters, p.status = int(r["iters"][f]), int(r["status"][f])
-        if not masked:
-            m.views(p)
-            for k, v in zip(Context.TRIAL_KEYS, r["priors9"][f]):   # the pairs, and the shapes the last updateCA! used
-                setattr(p, k, float(v))
-            p.alpha = _posterior_shapes(p, m)
-        p.YHat = _host_YHat(p)
-    return [float(v) for v in r["d"]]
+    return _sparse_fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of)
 
 
 def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True):
@@ -1471,8 +1415,8 @@ def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, 
     CA1..3, beta1..3, the posterior shapes alpha1..3 and the six hyper-priors included), plus p.iters and p.status as vbmf_sparse_batch_
     does, and returns the list of d.  params: one vbmf_trial_parameters per fit, one H <= 32 and one H0 per call, M0 per fit.  Every
     fit's whole loop runs in one workgroup of one launch (include/vbmf_hip.h, vbmf_local_fit_batched)."""
-    return _local_fit_batch("vbmf_trial_batch_", "vbmf_trial_", vbmf_trial_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors,
-                            bag_of)
+    return _sparse_fit_batch("vbmf_trial_batch_", "vbmf_trial_", vbmf_trial_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors,
+                             bag_of)
 
 
 def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None):
@@ -1480,8 +1424,8 @@ def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_c
     on Y = [Y0 Y1]): see vbmf_sparse_batch_.  params: one vbmf_sparse_parameters per fit whose labels are exactly the prefix 1..M0 of
     the columns (possibly empty; M0 per fit), with one H1 per call: the last H1 columns of AHat stay zero in the rows 1..M0
     (src/vbmf_sparse.jl:245).  Any other label set is refused: run it with vbmf_sparse_."""
-    return _local_fit_batch("vbmf_sparse_masked_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb,
-                            False, bag_of)
+    return _sparse_fit_batch("vbmf_sparse_masked_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb,
+                             False, bag_of, masked=True)
 
 
 def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None):
@@ -1550,58 +1494,18 @@ def vbmf_batch_(Ys, params, niter, eps=1e-6, est_covs=False, est_var=False, bag_
     form: "stream" (Y is read twice per sweep), "gram" (the sweep runs on Y Y', built once per bag: the form for bags much wider than
     tall; refused by the library where 3 L H doubles do not fit in LDS) or "auto" (capi.fit_form_auto per fit) -- the same iteration,
     different rounding (include/vbmf_hip.h, vbmf_fit_batched_form).  p.form_used: 0 (stream) or 1 (Gram)."""
-    def refuse(why):
-        raise ValueError(f"vbmf_batch_: {why}; run such fits one at a time with vbmf_")
     capi.fit_form_code(form)
-    params = list(params)
-    if not params:
-        refuse("no parameter sets")
-    if type(params[0]) is not vbmf_parameters:
-        refuse(f"fit 0: {type(params[0]).__name__} (the basic model's vbmf_parameters only)")
-    H = int(params[0].H)
-    if H > _FIT_MAX_H:
-        refuse(f"H = {H} > {_FIT_MAX_H}")
-    if int(niter) < 1:
-        refuse(f"niter = {niter} < 1")
-    if isinstance(Ys, Bags):
-        bags = Ys
-        if bags.H != H:
-            refuse(f"the Bags were uploaded for H = {bags.H}, the parameters have H = {H}")
-        L, Ms = bags.L, bags.Ms
-    else:
-        bags = None
-        L, Ms = _batch_shapes(Ys, H, refuse)
-    if bag_of is None:
-        if len(params) != len(Ms):
-            refuse(f"{len(Ms)} bags but {len(params)} parameter sets and no bag_of")
-        bag_of = range(len(Ms))
-    bag_of = [int(b) for b in bag_of]
-    if len(bag_of) != len(params):
-        refuse(f"{len(params)} parameter sets but {len(bag_of)} entries in bag_of")
+    refuse, params, bag_of, H, L, Ms = _fit_front("vbmf_batch_", "vbmf_", vbmf_parameters, Bags, Ys, params, niter, bag_of)
     for f, (p, b) in enumerate(zip(params, bag_of)):
-        if type(p) is not vbmf_parameters:
-            refuse(f"fit {f}: {type(p).__name__} (the basic model's vbmf_parameters only)")
-        if not 0 <= b < len(Ms):
-            refuse(f"fit {f}: bag_of = {b} outside 0..{len(Ms) - 1}")
-        if int(p.H) != H:
-            refuse(f"fit {f}: H = {p.H} beside H = {H}")
-        if (p.L, p.M) != (L, Ms[b]):
-            refuse(f"fit {f}: bag {b} is {L} x {Ms[b]}, its parameters describe {(p.L, p.M)}")
         if int(p.H1) > 0 or np.asarray(p.labels).size > 0:
             refuse(f"fit {f} has labels / H1 > 0 (a label mask)")
         if (np.shape(p.BHat) != (L, H) or np.shape(p.SigmaB) != (H, H) or np.shape(p.CA) != (H, H) or np.shape(p.CB) != (H, H)):
             refuse(f"fit {f}: BHat, SigmaB, CA or CB does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
-    own = bags is None
-    if own:
-        bags = Bags(Ys, H)
-    try:
-        r = bags.session.ctx.fit_batched(
+    with _on_device(Ys, H, Bags) as bags:
+        r = bags.ctx.fit_batched(
             bags.col_off, bag_of, int(niter), float(eps), np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]),
             np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]), np.stack([np.diag(p.CA) for p in params]),
             np.stack([np.diag(p.CB) for p in params]), [p.sigma2 for p in params], est_covs=est_covs, est_var=est_var, form=form)
-    finally:
-        if own:
-            bags.close()
     idx = np.arange(H)
     for f, p in enumerate(params):
         p.form_used = int(r["form_used"][f])
@@ -1621,18 +1525,12 @@ def row_gram_batch(bags):
     """K_b = Y_b Y_b' of every bag in one device call, in fp64 on Y as stored: an (nbags, L, L) array, each block symmetric bit for
     bit (include/vbmf_hip.h, vbmf_bags_row_gram).  bags: a list of L x M_b arrays (uploaded in fp32 storage for H = 1), a Bags or a
     SparseBags."""
-    if isinstance(bags, Bags):
-        return bags.session.ctx.row_gram(bags.col_off)
-    if isinstance(bags, SparseBags):
-        return bags.ctx.row_gram(bags.col_off)
     def refuse(why):
         raise ValueError(f"row_gram_batch: {why}")
-    _batch_shapes(bags, 1, refuse)
-    own = Bags(bags, 1)
-    try:
-        return own.session.ctx.row_gram(own.col_off)
-    finally:
-        own.close()
+    if not isinstance(bags, _Uploaded):
+        _batch_shapes(bags, 1, refuse)
+    with _on_device(bags, 1, Bags) as up:
+        return up.ctx.row_gram(up.col_off)
 
 
 def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, form="stream"):
@@ -1725,9 +1623,9 @@ def _score_refuser(fn):
     return refuse
 
 
-def _score_open(fn, Ys, params, bound=False):
-    """The uploaded bags for `params` (a Bags for the basic model, a SparseBags for the sparse family), the _Model (None: basic) and
-    whether they were opened here.  Every refusal of the batched vbls! entries applies, before any device call."""
+def _score_check(fn, Ys, params, bound=False):
+    """Every refusal of the batched vbls! entries, before any device call.  Returns the class of the upload `params` take (Bags for
+    the basic model, SparseBags for the sparse family) and the _Model (None: basic)."""
     refuse = _score_refuser(fn)
     params = list(params)
     if not params:
@@ -1737,14 +1635,10 @@ def _score_open(fn, Ys, params, bound=False):
     basic = type(p0) is vbmf_parameters
     if basic and bound:
         refuse("vbmf_parameters (the bound is defined for vbmf_sparse_parameters, vbmf_dual_parameters and vbmf_trial_parameters)")
-    if isinstance(Ys, (Bags, SparseBags)):
-        if isinstance(Ys, Bags) != basic:
-            refuse(f"{type(Ys).__name__} uploaded for another model family than {type(p0).__name__}")
-        if Ys.H != H:
-            refuse(f"the {type(Ys).__name__} were uploaded for H = {Ys.H}, the parameters have H = {H}")
-        L, Ms = Ys.L, Ys.Ms
-    else:
-        L, Ms = _batch_shapes(Ys, H, refuse)
+    cls = Bags if basic else SparseBags
+    if isinstance(Ys, _Uploaded) and not isinstance(Ys, cls):
+        refuse(f"{type(Ys).__name__} uploaded for another model family than {type(p0).__name__}")
+    L, Ms = _bag_shapes(Ys, H, cls, refuse)
     if basic:
         _batch_check_params(L, Ms, H, params, refuse)
         m = None
@@ -1754,9 +1648,7 @@ def _score_open(fn, Ys, params, bound=False):
             if p is not p0 and not (np.array_equal(p.CB, p0.CB) and np.array_equal(p.delta, p0.delta) and p.gamma0 == p0.gamma0
                                     and p.delta0 == p0.delta0):
                 refuse(f"bag {b} does not share CB, delta, gamma0 and delta0 with bag 0 (one fixed basis per call)")
-    if isinstance(Ys, (Bags, SparseBags)):
-        return Ys, m, False
-    return (Bags(Ys, H) if basic else SparseBags(Ys, H)), m, True
+    return cls, m
 
 
 def _score_ctx(bags, p0, m):
@@ -1764,9 +1656,8 @@ def _score_ctx(bags, p0, m):
     them as arguments)."""
     H = bags.H
     if m is None:
-        ctx = bags.session.ctx
-        ctx.set_state(np.zeros((bags.M, H)), p0.BHat, p0.SigmaA, p0.SigmaB, np.diag(p0.CA), np.diag(p0.CB), p0.sigma2)
-        return ctx
+        bags.ctx.set_state(np.zeros((bags.M, H)), p0.BHat, p0.SigmaA, p0.SigmaB, np.diag(p0.CA), np.diag(p0.CB), p0.sigma2)
+        return bags.ctx
     one = np.ones(bags.M * H)
     hyper = dict(alpha0=1e-10, beta0=1e-10, gamma0=p0.gamma0, delta0=p0.delta0, eta0=p0.eta0, zeta0=p0.zeta0)
     bags.ctx.sparse_set_state(one * 0.0, one, one, one, p0.BHat, p0.SigmaB, p0.CB, p0.delta, 1.0, 1.0, hyper)
@@ -1790,12 +1681,9 @@ def _stacked_A(params):
 
 def _residual_sq(fn, Ys, params):
     params = list(params)
-    bags, m, own = _score_open(fn, Ys, params)
-    try:
+    cls, m = _score_check(fn, Ys, params)
+    with _on_device(Ys, params[0].H, cls) as bags:
         return _score_ctx(bags, params[0], m).bag_residuals(bags.col_off, _stacked_A(params))
-    finally:
-        if own:
-            bags.close()
 
 
 def residual_batch(Ys, params):
@@ -1807,8 +1695,8 @@ def residual_batch(Ys, params):
 
 def _bound_batch(fn, Ys, params, clamp, trim):
     params = list(params)
-    bags, m, own = _score_open(fn, Ys, params, bound=True)
-    try:
+    cls, m = _score_check(fn, Ys, params, bound=True)
+    with _on_device(Ys, params[0].H, cls) as bags:
         H = bags.H
         cols = [_score_columns(m, p, H) for p in params]
         vec = lambda f: np.concatenate([np.asarray(getattr(p, f), dtype=np.float64).reshape(-1) for p in params])
@@ -1819,9 +1707,6 @@ def _bound_batch(fn, Ys, params, clamp, trim):
             [p.zeta0 for p in params], np.array([c[0] for c in cols]), np.array([c[1] for c in cols]), np.array([c[2] for c in cols]),
             trim=trim, clamp=clamp, grouped=type(params[0]) is not vbmf_sparse_parameters)
         return lb
-    finally:
-        if own:
-            bags.close()
 
 
 def lowerBound_batch(Ys, params, clamp=True):
@@ -1940,8 +1825,7 @@ def classify_batch(res0, res1, Ys, class_alg, threshold=1e-1, niter=None):
             else:
                 vbls_sparse_batch_(bags, ps, 20 if niter is None else int(niter), full_cov=True)
             # the batched fit has just checked these sets and left this model's basis as the context's state
-            ctx = bags.session.ctx if basic else bags.ctx
-            errs.append(np.sqrt(ctx.bag_residuals(bags.col_off, _stacked_A(ps))))
+            errs.append(np.sqrt(bags.ctx.bag_residuals(bags.col_off, _stacked_A(ps))))
     finally:
         bags.close()
     err0, err1 = errs
@@ -1983,33 +1867,24 @@ def _ls_basis(fn, B, lam):
 
 
 def _ls_open(fn, Ys, Bs):
-    """(the uploaded bags, whether they were opened here) for bases Bs (checked by _ls_basis), which all must be L x H_k; the
-    upload is a Bags at the first basis' rank -- the entry takes every call's own H."""
+    """The bags on the device (_on_device) for bases Bs (checked by _ls_basis), which all must be L x H_k; an upload made here is a
+    Bags at the first basis' rank -- the entry takes every call's own H."""
     refuse = _ls_refuser(fn)
-    if isinstance(Ys, (Bags, SparseBags)):
-        L, own = Ys.L, False
+    if isinstance(Ys, _Uploaded):
+        L = Ys.L
     else:
         Ys = list(Ys)
         L, _ = _batch_shapes(Ys, Bs[0].shape[1], refuse)
-        own = True
     for B in Bs:
         if B.shape[0] != L:
             refuse(f"B is {B.shape[0]} x {B.shape[1]}, the bags have L = {L} rows (B must be L x H)")
-    return (Bags(Ys, Bs[0].shape[1]) if own else Ys), own
-
-
-def _bags_ctx(bags):
-    return bags.session.ctx if isinstance(bags, Bags) else bags.ctx
+    return _on_device(Ys, Bs[0].shape[1], Bags)
 
 
 def _ls_call(fn, Ys, B, lam, want_X, want_r2):
     B = _ls_basis(fn, B, lam)
-    bags, own = _ls_open(fn, Ys, [B])
-    try:
-        X, r2 = _bags_ctx(bags).bag_least_squares(bags.col_off, B, lam, want_X=want_X, want_r2=want_r2)
-    finally:
-        if own:
-            bags.close()
+    with _ls_open(fn, Ys, [B]) as bags:
+        X, r2 = bags.ctx.bag_least_squares(bags.col_off, B, lam, want_X=want_X, want_r2=want_r2)
     if want_X:
         X = [np.array(X[:, c0:c1], order="F") for c0, c1 in zip(bags.col_off[:-1], bags.col_off[1:])]
     return X, r2
@@ -2073,13 +1948,8 @@ def classify_bags(res0, res1, Ys, class_alg="ols", threshold=1e-1, niter=None):
         if getattr(r, "BHat", None) is None:
             refuse(f"res{k} ({type(r).__name__}) has no BHat")
         Bs.append(_ls_basis(fn, r.BHat, lam))
-    bags, own = _ls_open(fn, Ys, Bs)
-    try:
-        ctx = _bags_ctx(bags)
-        err0, err1 = (np.sqrt(ctx.bag_least_squares(bags.col_off, B, lam, want_X=False)[1]) for B in Bs)
-    finally:
-        if own:
-            bags.close()
+    with _ls_open(fn, Ys, Bs) as bags:
+        err0, err1 = [np.sqrt(bags.ctx.bag_least_squares(bags.col_off, B, lam, want_X=False)[1]) for B in Bs]
     return (err0 > err1).astype(np.int64), err0, err1                    # :487-491
 
 

@@ -195,6 +195,10 @@ def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
 
+def _i64ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None else None
+
+
 def _fcol(a, shape=None):
     """float64, column-major (Julia Array{Float64,2} memory)."""
     a = np.asarray(a, dtype=np.float64)
@@ -446,12 +450,8 @@ class Context:
         form_used (nfits,)).  form: "stream" (vbmf_fit_batched itself), "gram" (every fit iterates on Y Y': the form for wide bags) or
         "auto" (fit_form_auto per fit) -- vbmf_fit_batched_form.  Neither the context's state nor its Y is changed."""
         code = fit_form_code(form)
-        off = np.ascontiguousarray(col_off, dtype=np.int64)
-        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
-        nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
-        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
-            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
-        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, L, H).transpose(0, 2, 1))   # per fit column-major
+        H = self.H
+        off, fb, nb, nf, B, per_fit, tail = self._fit_prologue(col_off, fit_bag, niter, BHat, want_trace)
         SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
         ca = np.array(CA, dtype=np.float64, copy=True, order="C")
         cb = np.array(CB, dtype=np.float64, copy=True, order="C")
@@ -462,19 +462,30 @@ class Context:
         A = np.empty(int(np.sum(Ms)) * H) if want_A else None
         SA = np.empty((nf, H, H))
         used = np.zeros(nf, dtype=np.int64)
-        iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
-        tr = np.zeros((nf, int(niter), 2)) if want_trace else None
-        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        args = (self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(est_covs)), int(bool(est_var)), _dptr(B), _dptr(SB),
-                _dptr(ca), _dptr(cb), _dptr(s2), _dptr(A), _dptr(SA), p64(iters), _dptr(dl), p64(st), _dptr(tr))
+        args = (self._h, nb, _i64ptr(off), nf, _i64ptr(fb), int(niter), float(eps), int(bool(est_covs)), int(bool(est_var)), _dptr(B),
+                _dptr(SB), _dptr(ca), _dptr(cb), _dptr(s2), _dptr(A), _dptr(SA), *tail)
         if code == VBMF_FIT_FORM_STREAM:
             self._chk(self._lib.vbmf_fit_batched(*args))
         else:
-            self._chk(self._lib.vbmf_fit_batched_form(*args, code, p64(used)))
+            self._chk(self._lib.vbmf_fit_batched_form(*args, code, _i64ptr(used)))
         ends = np.cumsum(Ms) * H
         As = [A[e - m * H:e].reshape(H, m).T for e, m in zip(ends, Ms)] if want_A else None   # column-major M_b x H blocks
-        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CA=ca, CB=cb, sigma2=s2, SigmaA=SA, AHat=As, iters=iters, d=dl, status=st,
-                    trace=tr, form_used=used)
+        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CA=ca, CB=cb, sigma2=s2, SigmaA=SA, AHat=As, form_used=used, **per_fit)
+
+    def _fit_prologue(self, col_off, fit_bag, niter, BHat, want_trace):
+        """What the whole-fit batched calls marshal alike: col_off and fit_bag as int64 arrays (every fit_bag entry checked against the
+        bags), nbags, nfits, the start values BHat (nfits, L, H) copied per fit column-major, the per-fit outputs as the entries of the
+        returned dictionary -- iters, d, status, trace (None unless want_trace) -- and the pointers to them, every entry's last four
+        arguments."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
+        nb, nf = off.size - 1, fb.size
+        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
+            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
+        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, self.L, self.H).transpose(0, 2, 1))
+        per_fit = dict(iters=np.zeros(nf, dtype=np.int64), d=np.empty(nf), status=np.zeros(nf, dtype=np.int64),
+                       trace=np.zeros((nf, int(niter), 2)) if want_trace else None)
+        return off, fb, nb, nf, B, per_fit, (_i64ptr(per_fit["iters"]), _dptr(per_fit["d"]), _i64ptr(per_fit["status"]), _dptr(per_fit["trace"]))
 
     def row_gram(self, col_off):
         """K_b = Y_b Y_b' of every bag side by side in this context's Y, in fp64 on Y as stored (vbmf_bags_row_gram): (nbags, L, L)."""
@@ -523,35 +534,8 @@ class Context:
         values BHat (nfits, L, H), SigmaB (nfits, H, H), CB (nfits, H) and CA: the fits' vec(A')-ordered vectors concatenated.
         Returns dict(BHat, SigmaB, CB, delta (None unless est_cb), sigmaHat, zeta, priors4, CA, beta, diagSigmaATVec, ATVecHat, SigmaA,
         iters, d, status, trace (nfits, niter, 2) or None).  Neither the context's state nor its Y is changed."""
-        off = np.ascontiguousarray(col_off, dtype=np.int64)
-        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
-        nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
-        vec = lambda v: np.array(v, dtype=np.float64, copy=True).reshape(-1)
-        ga, d0, et, z0, sg, ca = vec(gamma), vec(delta0), vec(eta), vec(zeta0), vec(sigmaHat), vec(CA)
-        pri = np.array(priors4, dtype=np.float64, copy=True, order="C")
-        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, L, H).transpose(0, 2, 1))   # per fit column-major
-        SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
-        cb = np.array(CB, dtype=np.float64, copy=True, order="C")
-        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
-            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
-        MH = int(np.sum(off[fb + 1] - off[fb])) * H
-        if (any(v.shape != (nf,) for v in (ga, d0, et, z0, sg)) or pri.shape != (nf, 4) or SB.shape != (nf, H, H) or cb.shape != (nf, H)
-                or ca.shape != (MH,)):
-            raise ValueError(f"{nf} fits: gamma, delta0, eta, zeta0, sigmaHat must be ({nf},), priors4 ({nf}, 4), SigmaB ({nf}, {H}, {H}), "
-                             f"CB ({nf}, {H}) and CA ({MH},)")
-        delta = np.empty((nf, H)) if est_cb else None
-        zeta, beta, dS, A = np.empty(nf), np.empty(MH), np.empty(MH), np.empty(MH)
-        SA = np.empty((nf, H, H))
-        iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
-        tr = np.zeros((nf, int(niter), 2)) if want_trace else None
-        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        self._chk(self._lib.vbmf_sparse_fit_batched(
-            self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
-            int(H if H0 is None else H0), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0), _dptr(pri), _dptr(B), _dptr(SB), _dptr(cb),
-            _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA), _dptr(A), p64(iters), _dptr(dl),
-            p64(st), _dptr(tr)))
-        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, priors4=pri, CA=ca, beta=beta,
-                    diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA, iters=iters, d=dl, status=st, trace=tr)
+        return self._ard_fit_batched(col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors4, BHat, SigmaB, CB, sigmaHat, CA, H0,
+                                     full_cov, est_cb, est_priors, want_trace)
 
     def local_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors9, BHat, SigmaB, CB, sigmaHat, CA, M0,
                           H0=None, mask_H1=0, full_cov=False, est_cb=True, est_priors=False, want_trace=False):
@@ -561,40 +545,46 @@ class Context:
         entries m < M0[f], h >= H - mask_H1 of A are held at zero.  priors9 (nfits, 9) in trial_get_priors' order: three (alpha0g, beta0g)
         pairs in, the pairs and the three posterior shapes out; (nfits, 6) is accepted and padded.  Returns sparse_fit_batched's dict with
         priors9 in place of priors4."""
-        off = np.ascontiguousarray(col_off, dtype=np.int64)
-        fb = np.ascontiguousarray(fit_bag, dtype=np.int64).reshape(-1)
-        nb, nf, H, L = off.size - 1, fb.size, self.H, self.L
+        return self._ard_fit_batched(col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors9, BHat, SigmaB, CB, sigmaHat, CA, H0,
+                                     full_cov, est_cb, est_priors, want_trace, M0=M0, mask_H1=mask_H1)
+
+    def _ard_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors, BHat, SigmaB, CB, sigmaHat, CA, H0, full_cov,
+                         est_cb, est_priors, want_trace, M0=None, mask_H1=0):
+        """sparse_fit_batched (M0 is None: vbmf_sparse_fit_batched, four prior values per fit) and local_fit_batched
+        (vbmf_local_fit_batched: M0 and mask_H1 behind H0, nine prior values per fit, six accepted and padded)."""
+        local = M0 is not None
+        H = self.H
+        off, fb, nb, nf, B, per_fit, tail = self._fit_prologue(col_off, fit_bag, niter, BHat, want_trace)
         vec = lambda v: np.array(v, dtype=np.float64, copy=True).reshape(-1)
         ga, d0, et, z0, sg, ca = vec(gamma), vec(delta0), vec(eta), vec(zeta0), vec(sigmaHat), vec(CA)
-        m0 = np.array(M0, dtype=np.int64, copy=True).reshape(-1)
-        pin = np.asarray(priors9, dtype=np.float64)
-        pri = np.zeros((nf, 9))
-        if pin.ndim == 2 and pin.shape[0] == nf and pin.shape[1] in (6, 9):
+        if local:
+            m0 = np.array(M0, dtype=np.int64, copy=True).reshape(-1)
+            pin = np.asarray(priors, dtype=np.float64)
+            if not (pin.ndim == 2 and pin.shape[0] == nf and pin.shape[1] in (6, 9)):
+                raise ValueError(f"{nf} fits: priors9 must be ({nf}, 9) or ({nf}, 6)")
+            pri = np.zeros((nf, 9))
             pri[:, :pin.shape[1]] = pin
         else:
-            raise ValueError(f"{nf} fits: priors9 must be ({nf}, 9) or ({nf}, 6)")
-        B = np.ascontiguousarray(np.asarray(BHat, dtype=np.float64).reshape(nf, L, H).transpose(0, 2, 1))   # per fit column-major
+            pri = np.array(priors, dtype=np.float64, copy=True, order="C")
         SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
         cb = np.array(CB, dtype=np.float64, copy=True, order="C")
-        if nb < 1 or nf < 1 or off.ndim != 1 or np.any(fb < 0) or np.any(fb >= nb):
-            raise ValueError(f"col_off describes {nb} bags: every fit_bag entry must lie in 0..{nb - 1}")
         MH = int(np.sum(off[fb + 1] - off[fb])) * H
-        if (any(v.shape != (nf,) for v in (ga, d0, et, z0, sg, m0)) or SB.shape != (nf, H, H) or cb.shape != (nf, H) or ca.shape != (MH,)):
-            raise ValueError(f"{nf} fits: gamma, delta0, eta, zeta0, sigmaHat, M0 must be ({nf},), SigmaB ({nf}, {H}, {H}), "
-                             f"CB ({nf}, {H}) and CA ({MH},)")
+        scalars = (ga, d0, et, z0, sg, m0) if local else (ga, d0, et, z0, sg)
+        if (any(v.shape != (nf,) for v in scalars) or pri.shape != (nf, 9 if local else 4) or SB.shape != (nf, H, H) or cb.shape != (nf, H)
+                or ca.shape != (MH,)):
+            raise ValueError(f"{nf} fits: gamma, delta0, eta, zeta0, sigmaHat{', M0' if local else ''} must be ({nf},), "
+                             f"{'' if local else f'priors4 ({nf}, 4), '}SigmaB ({nf}, {H}, {H}), CB ({nf}, {H}) and CA ({MH},)")
         delta = np.empty((nf, H)) if est_cb else None
         zeta, beta, dS, A = np.empty(nf), np.empty(MH), np.empty(MH), np.empty(MH)
         SA = np.empty((nf, H, H))
-        iters, dl, st = np.zeros(nf, dtype=np.int64), np.empty(nf), np.zeros(nf, dtype=np.int64)
-        tr = np.zeros((nf, int(niter), 2)) if want_trace else None
-        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        self._chk(self._lib.vbmf_local_fit_batched(
-            self._h, nb, p64(off), nf, p64(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
-            int(H if H0 is None else H0), p64(m0), int(mask_H1), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0), _dptr(pri), _dptr(B), _dptr(SB),
-            _dptr(cb), _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA), _dptr(A), p64(iters), _dptr(dl),
-            p64(st), _dptr(tr)))
-        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, priors9=pri, CA=ca, beta=beta,
-                    diagSigmaATVec=dS, ATVecHat=A, SigmaA=SA, iters=iters, d=dl, status=st, trace=tr)
+        entry = self._lib.vbmf_local_fit_batched if local else self._lib.vbmf_sparse_fit_batched
+        self._chk(entry(
+            self._h, nb, _i64ptr(off), nf, _i64ptr(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
+            int(H if H0 is None else H0), *((_i64ptr(m0), int(mask_H1)) if local else ()), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0),
+            _dptr(pri), _dptr(B), _dptr(SB), _dptr(cb), _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA),
+            _dptr(A), *tail))
+        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, CA=ca, beta=beta, diagSigmaATVec=dS,
+                    ATVecHat=A, SigmaA=SA, **{"priors9" if local else "priors4": pri}, **per_fit)
 
     def YHat(self):
         out = np.empty((self.L, self.M), order="F")
