@@ -411,6 +411,24 @@ __global__ __launch_bounds__(T * T) void ctrl_cov_kernel(double* __restrict__ st
 // the copies of converged Ritz values that its absence breeds never exceed lambda_max.  Measured (tests/test_gpu_lambda_max.py: flat,
 // Marchenko-Pastur, near-degenerate pair, rank-deficient, dominant, 2^-k, identity): <= 8e-8 relative at H = 128, 130, 200, 256 (and at H = 40 when
 // routed here; H <= 64 keeps the squaring kernel below for its speed inside short pass launches).
+// Breakdown and restart.  At beta = 0 the vectors so far span an invariant subspace and T_k carries lambda_max of everything q_0
+// touches -- which is all it carries: a q_0 that lies in a non-dominant invariant subspace ends there with that subspace's top value.
+// The start vector diag(G) / tr + 1e-3 is the all-ones vector on a constant diagonal, and an exact eigenvector of e.g.
+// blockdiag([[1 + c, -c], [-c, 1 + c]], ...) (eigenvalue 1 where lambda_max = 1 + 2c: every row of G q_0 is the same fp32 number in any
+// summation order, so the first step breaks down exactly).  So a breakdown before k = H does not end the solve: the iteration runs
+// again from lanczos_restart_entry's vector -- fixed, positive, non-uniform (an integer hash of the row index in (0.5, 1.5]), no
+// random state, the same from run to run -- at most EIG_LANCZOS_RESTARTS times, and the largest value found is returned (each is a
+// Ritz value, none exceeds lambda_max beyond the product's rounding).  A step also counts as a breakdown when beta_(j+1) <=
+// 2^-16 alpha_0 (alpha_0 = q_0'G q_0 / tr, the scale of the spectrum as q_0 sees it; a row of the fp32 product is good to NP 2^-24
+// <= 2^-16 of it at worst): a residual at the rounding of the product means the subspace is invariant as far as this arithmetic can
+// tell, and the steps that followed would iterate on rounding that inherits every symmetry G and q_0 share.  Two cases met on the
+// device: I + c (e_i - e_j)(e_i - e_j)' from a q_0 with equal entries i and j never leaves the symmetric subspace (rows i and j of
+// every product are the same two terms: beta_1 ~ 1e-8 alpha_0, never 0); the paired blocks at odd H, where q_0 spans the eigenvalues 1
+// and 1 + c, exhaust at the second step the same way.  An input that meets neither test takes the first pass alone and gets the bits
+// it always got.  This is a repair of the cases found, not a guarantee: three fixed start vectors can still all be orthogonal to the
+// dominant eigenvector of some matrix (take one built for them), and a q_0 that is NEARLY but not numerically inside a non-dominant
+// invariant subspace is resolved only by the rounding that seeds the missing direction before the growth test at two looks 12 steps
+// apart gives up (tests/test_gpu_lambda_max_structured.py).
 // Layout: NT threads (256 inside a pass launch and for 64 < H <= 128, 1024 for H > 128), matrix padded to NP = 16, 32, 64, 128 or 256.  Thread
 // (group = t / NCQ, cq = t % NCQ), NCQ = NP / 16, holds the RB x 16 block G[RB group .. +RB][16 cq .. +16] / tr in registers as fp32
 // pairs (the products go out as v_pk_fma_f32: a step is VALU-bound), reads its 16 entries of q from LDS (four 16-byte reads), forms RB
@@ -469,6 +487,9 @@ __device__ __forceinline__ double tri_lambda_max(const double* al, const double*
             const double x = t == 255 ? hi : lo + step * (double)(t + 1);
             double d = al[0] - x;
             int cnt = d < 0.0 ? 1 : 0;
+            // eight steps' LDS reads ahead of the serial rcp chain (stated: the compiler's own choice depends on the loop nest around
+            // the call, and without it a look costs 5 % of the solve at H = 128)
+#pragma unroll 8
             for (int i = 1; i < k; ++i) {
                 if (fabs(d) < 1e-290) d = -1e-290;
                 d = al[i] - x - be2[i] * __builtin_amdgcn_rcp(d);
@@ -486,6 +507,17 @@ __device__ __forceinline__ double tri_lambda_max(const double* al, const double*
     return 0.5 * (lo + hi);
 }
 constexpr double EIG_LANCZOS_TOL = 2e-7;                        // growth of the top Ritz value between two looks, relative
+constexpr int EIG_LANCZOS_RESTARTS = 2;                         // further start vectors after a breakdown before k = H
+constexpr double EIG_LANCZOS_EXHAUSTED = 0x1p-32;               // (beta_(j+1) / alpha_0)^2 at or below which the subspace counts as invariant:
+                                                                // a row of the fp32 product is good to NP 2^-24 <= 2^-16 at worst
+// entry `row` of restart vector `attempt` (1, 2): murmur3's 32-bit finaliser of the pair, its top 24 bits mapped to (0.5, 1.5]
+__device__ __forceinline__ double lanczos_restart_entry(int row, int attempt) {
+    unsigned x = (unsigned)(row + 1) * 0x9E3779B1u + (unsigned)attempt * 0x85EBCA77u;
+    x ^= x >> 16; x *= 0x85EBCA6Bu;
+    x ^= x >> 13; x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return 0.5 + (double)((x >> 8) + 1u) * 0x1p-24;
+}
 // LDS of a call: NP floats (q) + 2 NP + 1 doubles (alpha, beta^2) + 16 doubles + 1 int; the caller hands over >= EIG_LDS_BYTES
 constexpr int EIG_LDS_BYTES = 256 * 4 + (2 * 256 + 2) * 8 + 16 * 8 + 16;
 // lambda_max(G) / tr for the H x H matrix G (row stride Hp, H <= NP, tr = its trace > 0).  Every one of the NT threads gets the value.
@@ -517,58 +549,71 @@ __device__ __forceinline__ double lanczos_lambda_max(const double* __restrict__ 
                 g[r][j >> 1][j & 1] = (active && row < H && col < H) ? (float)(G[(long long)row * Hp + col] * inv) : 0.f;
             }
     }
-    // start from the diagonal (a positive vector correlated with the dominant eigenvector of a PSD matrix)
-    double q = (owner && myrow < H) ? G[(long long)myrow * Hp + myrow] / tr + 1e-3 : 0.0, qp = 0.0, beta = 0.0;
-    {
-        const double n0 = block_sum_dpp<NT>(q * q, red);
-        q *= 1.0 / sqrt(n0);
-    }
-    if (owner) vbuf[myrow] = (float)q;
-    __syncthreads();
     const int kmax = H < NP ? H : NP;
-    int next_look = 12;
-    double theta = 0.0, theta_prev = 0.0;
-    for (int j = 0; j < kmax; ++j) {
-        const float4* v4 = reinterpret_cast<const float4*>(&vbuf[cq * 16]);
-        f32x2v a2[RB];
+    double best = 0.0;
+    for (int attempt = 0; attempt <= EIG_LANCZOS_RESTARTS; ++attempt) {
+        // start from the diagonal (a positive vector correlated with the dominant eigenvector of a PSD matrix); after a breakdown from
+        // lanczos_restart_entry's fixed non-uniform vector
+        double q = 0.0, qp = 0.0, beta = 0.0;
+        if (owner && myrow < H) q = attempt == 0 ? G[(long long)myrow * Hp + myrow] / tr + 1e-3 : lanczos_restart_entry(myrow, attempt);
+        {
+            const double n0 = block_sum_dpp<NT>(q * q, red);
+            q *= 1.0 / sqrt(n0);
+        }
+        if (owner) vbuf[myrow] = (float)q;
+        __syncthreads();
+        int next_look = 12;
+        double theta = 0.0, theta_prev = 0.0, a0 = 0.0;
+        bool again = false;                                         // (uniform: alpha and b2 are the same in every thread)
+        for (int j = 0; j < kmax; ++j) {
+            const float4* v4 = reinterpret_cast<const float4*>(&vbuf[cq * 16]);
+            f32x2v a2[RB];
 #pragma unroll
-        for (int r = 0; r < RB; ++r) a2[r] = f32x2v{0.f, 0.f};
+            for (int r = 0; r < RB; ++r) a2[r] = f32x2v{0.f, 0.f};
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const float4 v = v4[jj];
-            const f32x2v va = {v.x, v.y}, vb = {v.z, v.w};
+            for (int jj = 0; jj < 4; ++jj) {
+                const float4 v = v4[jj];
+                const f32x2v va = {v.x, v.y}, vb = {v.z, v.w};
 #pragma unroll
-            for (int r = 0; r < RB; ++r) {
-                a2[r] = __builtin_elementwise_fma(g[r][2 * jj], va, a2[r]);
-                a2[r] = __builtin_elementwise_fma(g[r][2 * jj + 1], vb, a2[r]);
+                for (int r = 0; r < RB; ++r) {
+                    a2[r] = __builtin_elementwise_fma(g[r][2 * jj], va, a2[r]);
+                    a2[r] = __builtin_elementwise_fma(g[r][2 * jj + 1], vb, a2[r]);
+                }
+            }
+            float acc[RB];
+#pragma unroll
+            for (int r = 0; r < RB; ++r) acc[r] = rowN_sum<NCQ>(a2[r][0] + a2[r][1]);
+            float mine = acc[0];
+            if constexpr (RB == 4) mine = (cq & 3) == 0 ? acc[0] : ((cq & 3) == 1 ? acc[1] : ((cq & 3) == 2 ? acc[2] : acc[3]));
+            double wv = owner ? (double)mine : 0.0;                 // (G q)[myrow]
+            const double alpha = block_sum_dpp<NT>(q * wv, red);    // (q = 0 outside the owner lanes)
+            wv = owner ? wv - alpha * q - beta * qp : 0.0;
+            const double b2 = block_sum_dpp<NT>(wv * wv, red);
+            const int k = j + 1;
+            if (t == 0) { al[j] = alpha; be2[k] = b2; }
+            // breakdown: q_0 .. q_j span an invariant subspace, and T_k carries lambda_max of THAT subspace only.  A residual that is
+            // fp32 rounding of the product and nothing else counts too: going on would iterate on that rounding, which keeps every
+            // symmetry the matrix and q_0 share
+            if (j == 0) a0 = alpha;
+            const bool brk = !(b2 > 1e-28) || !(b2 > EIG_LANCZOS_EXHAUSTED * a0 * a0);
+            again = brk && k < kmax;
+            qp = q;
+            beta = sqrt(b2);
+            q = brk ? 0.0 : wv / beta;
+            if (owner) vbuf[myrow] = (float)q;
+            __syncthreads();                                        // q_(j+1), alpha_j, beta_(j+1) are in LDS; every read of q_j is over
+            if (brk || k == next_look || k == kmax) {
+                theta = tri_lambda_max(al, be2, k, theta_prev > 1e-9 ? theta_prev - 1e-9 : 0.0, 1.0 + 1e-6, imin, 4);
+                if (brk || k == kmax || theta - theta_prev <= EIG_LANCZOS_TOL * theta) break;
+                theta_prev = theta;
+                next_look = k < 48 ? k + 12 : (k < 64 ? 64 : (k < 128 ? k + 32 : k + 64));
             }
         }
-        float acc[RB];
-#pragma unroll
-        for (int r = 0; r < RB; ++r) acc[r] = rowN_sum<NCQ>(a2[r][0] + a2[r][1]);
-        float mine = acc[0];
-        if constexpr (RB == 4) mine = (cq & 3) == 0 ? acc[0] : ((cq & 3) == 1 ? acc[1] : ((cq & 3) == 2 ? acc[2] : acc[3]));
-        double wv = owner ? (double)mine : 0.0;                 // (G q)[myrow]
-        const double alpha = block_sum_dpp<NT>(q * wv, red);    // (q = 0 outside the owner lanes)
-        wv = owner ? wv - alpha * q - beta * qp : 0.0;
-        const double b2 = block_sum_dpp<NT>(wv * wv, red);
-        const int k = j + 1;
-        if (t == 0) { al[j] = alpha; be2[k] = b2; }
-        const bool brk = !(b2 > 1e-28);                         // invariant subspace: T_k carries lambda_max of everything q_0 touches
-        qp = q;
-        beta = sqrt(b2);
-        q = brk ? 0.0 : wv / beta;
-        if (owner) vbuf[myrow] = (float)q;
-        __syncthreads();                                        // q_(j+1), alpha_j, beta_(j+1) are in LDS; every read of q_j is over
-        if (brk || k == next_look || k == kmax) {
-            theta = tri_lambda_max(al, be2, k, theta_prev > 1e-9 ? theta_prev - 1e-9 : 0.0, 1.0 + 1e-6, imin, 4);
-            if (brk || k == kmax || theta - theta_prev <= EIG_LANCZOS_TOL * theta) break;
-            theta_prev = theta;
-            next_look = k < 48 ? k + 12 : (k < 64 ? 64 : (k < 128 ? k + 32 : k + 64));
-        }
+        best = theta > best ? theta : best;
+        if (!again) break;
     }
     __syncthreads();                                            // the LDS is reused by whatever the block runs next
-    return theta;
+    return best;
 }
 
 // H <= 64: lambda_max by repeated squaring (kept for the small ranks: inside a 20-60 us pass launch of a narrow problem or a short row
@@ -694,7 +739,7 @@ __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateL
 template <int R>
 __device__ __forceinline__ void eig_dev(double* __restrict__ st, StateLayout lay, int H, int spectral, int which,
                                         const int* __restrict__ ints, float* ldsf, int slot, bool check_stop = true) {
-    if (R <= 4 && !(spectral & 2)) {                            // (uniform over the launch)
+    if (R <= 4 && __builtin_expect(!(spectral & 2), 1)) {       // (uniform over the launch; the other branch is a switch: cold)
         eig_squaring_dev<R>(st, lay, H, spectral & 1, which, ints, ldsf, slot, check_stop);
     } else {
         __shared__ double red[16];
