@@ -333,11 +333,13 @@ int vbmf_sparse_step(vbmf_ctx* ctx, int which);           /* reference order A, 
  * Gram form.  A VBMF_VARIANT_SPARSE_DIAG context with full_cov off, one rank, bf16 Y, bf16x2 factors and
  * H <= 128 iterates on G = Y'Y instead of streaming Y twice per sweep under the size rule of vbmf_run (L >= 4 M and L M >= 2^27), or
  * at any size when it was created under VBMF_GRAM=2 (VBMF_GRAM=1 forces the basic model only; VBMF_GRAM=0 and every other sparse
- * context -- the grouped models, diag_var, full_cov, H > 128, row shards, fp32 storage -- keep the streaming sweep).  In that form B = Y W with W = sigmaHat A SigmaB: the first sweep
+ * context -- the grouped models, diag_var, full_cov, H > 128, row shards, fp32 storage -- keep the streaming sweep).  128 < H <= 256
+ * takes the form only under vbmf_set_gram_form(ctx, VBMF_GRAM_FORM_ON) or VBMF_GRAM=3.  In that form B = Y W with W = sigmaHat A SigmaB: the first sweep
  * of a run that holds no W streams Y and forms W, the later ones read G only, and W is carried from run to run.  Before the run returns,
  * BHat of the last executed sweep is formed by one streaming pass, so vbmf_sparse_get_state, the lower bounds and a following run see
  * what a streaming run leaves, and run(3) + run(3) computes what run(6) computes.  vbmf_sparse_set_state, vbmf_set_Y*,
- * vbmf_sparse_step, vbmf_sparse_run_fixed_basis, vbmf_sparse_set_full_cov and a failed run drop W: the next run starts by streaming. */
+ * vbmf_sparse_step, vbmf_sparse_run_fixed_basis, vbmf_sparse_set_full_cov, vbmf_set_gram_form and a failed run drop W: the next run
+ * starts by streaming. */
 int vbmf_sparse_run(vbmf_ctx* ctx, int64_t niter, double eps, int est_cb, int64_t* iters_done, double* d_last,
                     double* trace);
 /* lowerBound (src/vbmf_sparse.jl:435-471), verbatim quirks QS4; H(B) as L*logdet(SigmaB), clamped like
@@ -409,6 +411,21 @@ int vbmf_sparse_lower_bound_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t*
  * *_DIAGVAR variants (:180-182, :192-193) the blocks are B' diag(sigmaVec) B + L mean(sigmaVec) SigmaB + diag(CA[m,:]) and the
  * mean carries no sigmaHat factor.  The dense SigmaATVec / invSigmaATVec fields are not materialised. */
 int vbmf_sparse_set_full_cov(vbmf_ctx* ctx, int on);
+/* Which form the run loops take (vbmf_run, and vbmf_sparse_run for src/vbmf_sparse.jl:344-412):
+ *   VBMF_GRAM_FORM_DEFAULT  the rule a context has from its creation: VBMF_GRAM as read then (0 never; 1 the basic model whenever
+ *                           its structure allows; 2 the ARD-sparse model too; 3 = VBMF_GRAM_FORM_ON; any other value parses as 1),
+ *                           else the size rule (L >= 4 M and L M >= 2^27).  Neither the size rule nor VBMF_GRAM = 0 / 1 / 2 ever
+ *                           takes the form at H > 128.
+ *   VBMF_GRAM_FORM_OFF      every sweep streams Y.
+ *   VBMF_GRAM_FORM_ON       the Gram form wherever the structure allows it: one rank, bf16 Y, bf16x2 factors, no full_cov / diag_var /
+ *                           grouped model, H <= 128 -- and for VBMF_VARIANT_SPARSE_DIAG also 128 < H <= 256 (stored as Hp = 256), which
+ *                           no other setting turns on.  The basic model at H > 128 keeps streaming.
+ * The call drops W, so the next run starts by a streaming sweep.  It does not fail for a structure that cannot take the form:
+ * word 16 of VBMF_PEEK_DIMS reports what was resolved.  Any other mode returns VBMF_ERR_INVALID and changes nothing. */
+#define VBMF_GRAM_FORM_DEFAULT 0
+#define VBMF_GRAM_FORM_OFF 1
+#define VBMF_GRAM_FORM_ON 2
+int vbmf_set_gram_form(vbmf_ctx* ctx, int mode);
 /* SigmaA as a full H x H matrix, column-major (vbmf_sparse_set_state derives a diagonal one from diagSigmaATVec; set it
  * explicitly to continue a full_cov state) */
 int vbmf_sparse_set_SigmaA(vbmf_ctx* ctx, const double* SigmaA);

@@ -22,7 +22,8 @@ idx = [i for i, e in enumerate(ev) if "stream_gemm_kernel" in e[2] or "stream_ld
 # pass 1 and pass 2 alternate in the run loop: take launches from the end
 starts = idx[::2] if len(idx) % 2 == 0 else idx[1::2]
 # the Gram form streams Y only at run boundaries: one sweep runs from one gram_w launch to the next
-gw = [i for i, e in enumerate(ev) if "gram_w_kernel" in e[2]]
+# (rank 256: gram_w_cols_kernel)
+gw = [i for i, e in enumerate(ev) if "gram_w_kernel" in e[2] or "gram_w_cols_kernel" in e[2]]
 if len(gw) > back + 1:
     starts = gw
 s0, s1 = starts[-back - 1], starts[-back]

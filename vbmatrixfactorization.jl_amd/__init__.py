@@ -406,13 +406,53 @@ def _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run, pull, yhat, 
     return d
 
 
-def vbmf_(Y, params, niter, eps=1e-6, est_covs=False, est_var=False, logdir="", desc="", verb=False, log_every=1):
+def _gram_refusal(H, sparse, grouped=False, diag_var=False, full_cov=False):
+    """Why a context made from the current defaults cannot take the Gram form (gram_structural of the library), as a phrase;
+    "" when nothing on the host's side stands against it."""
+    if _defaults["y_dtype"] != VBMF_Y_BF16:
+        return "Y is stored in fp32 (the hosts' default): set_defaults(y_dtype=VBMF_Y_BF16) first"
+    if _defaults["factor_dtype"] == VBMF_FACTOR_BF16:
+        return "the single-bf16 factor (factor_dtype=VBMF_FACTOR_BF16): the form needs VBMF_FACTOR_BF16X2"
+    if grouped:
+        return "a grouped model (vbmf_dual / vbmf_trial) masks its B side by group"
+    if diag_var:
+        return "diag_var=True: the rows' noise precisions change Y'diag(sigma)B every sweep"
+    if full_cov:
+        return "full_cov=True: the per-column covariance blocks are built from the streamed product"
+    if H > (256 if sparse else 128):
+        return f"H = {H} > {256 if sparse else 128}, the largest rank the {'ARD-sparse' if sparse else 'basic'} model's Gram sweep covers"
+    return ""
+
+
+def _apply_form(c, form, fn, why):
+    """form=None | "stream" | "gram" of the fit functions on context c (vbmf_set_gram_form).  None makes no call on a context
+    whose form was never pinned, and gives one that was back to its default rule.  "gram" on a context that cannot take the form
+    raises ValueError naming why (`why()`: the host's reading of gram_structural; row shards are what is left when it has none)."""
+    if form is None:
+        if getattr(c, "_form_pinned", False):
+            c.set_gram_form(capi.VBMF_GRAM_FORM_DEFAULT)
+            c._form_pinned = False
+        return
+    if form not in capi.GRAM_FORMS:
+        raise ValueError(f"{fn}: form must be None, 'stream' or 'gram', not {form!r}")
+    c.set_gram_form(capi.GRAM_FORMS[form])
+    c._form_pinned = True
+    if form == "gram" and not c.dims()["gram"]:
+        c.set_gram_form(capi.VBMF_GRAM_FORM_DEFAULT)
+        c._form_pinned = False
+        raise ValueError(f"{fn}: form='gram' refused: " + (why() or "the context is one of several row shards (nranks > 1)"))
+
+
+def vbmf_(Y, params, niter, eps=1e-6, est_covs=False, est_var=False, logdir="", desc="", verb=False, log_every=1, form=None):
     """vbmf! -- src/vbmf.jl:175-231.  `params` is modified in place and returned.
     logdir != "": the trajectory is logged like the reference does (slice 0 = the initial state, then one slice per
     sweep, src/vbmf.jl:181-184,205-207) and saved under logdir/desc (data_manip.py); that pulls the state off the
-    device every `log_every` sweeps (an extension; 1 = the reference's behaviour), so it is a debugging mode."""
+    device every `log_every` sweeps (an extension; 1 = the reference's behaviour), so it is a debugging mode.
+    form: None (the library's rule: VBMF_GRAM, then the size rule), "stream" or "gram" (iterate on Y'Y whatever the size; a
+    ValueError says why where the context cannot: fp32 storage, the single-bf16 factor, H > 128)."""
     _check(Y, params)
     s = _session_for(Y, params.H)
+    _apply_form(s.ctx, form, "vbmf_", lambda: _gram_refusal(params.H, sparse=False))
     s.push(params)
     _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run=lambda k: s.run(k, eps=eps, est_covs=est_covs, est_var=est_var),
          pull=lambda: s.pull(params), yhat=s.ctx.YHat, say_saving=True)
@@ -645,9 +685,12 @@ def _step(Y, p, which, diag_var=False, full_cov=False):
     _pull(c, p, m, diag_var)
 
 
-def _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors=True):
-    """vbmf_sparse! / vbmf_dual! / vbmf_trial!: returns d (like the reference)."""
+def _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors=True, form=None,
+              fn="vbmf_sparse_"):
+    """vbmf_sparse! / vbmf_dual! / vbmf_trial!: returns d (like the reference).  form: see vbmf_sparse_."""
     c, m = _pushed(Y, params, diag_var, full_cov)
+    _apply_form(c, form, fn, lambda: _gram_refusal(params.H, sparse=True, grouped=m.set_priors is not None, diag_var=diag_var,
+                                                   full_cov=full_cov))
     return _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run=lambda k: m.run(c, k, eps, est_cb, est_priors),
                 pull=lambda: _pull(c, params, m, diag_var), yhat=lambda: params.BHat @ params.AHat.T)   # host, small problems only
 
@@ -694,9 +737,13 @@ def sparse_updateSigma_(Y, params, diag_var=False):
 
 
 def vbmf_sparse_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_cb=True,
-                 log_every=1):
-    """vbmf_sparse! -- src/vbmf_sparse.jl:344-410.  Returns d (like the reference).  logdir: see vbmf_."""
-    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every)
+                 log_every=1, form=None):
+    """vbmf_sparse! -- src/vbmf_sparse.jl:344-410.  Returns d (like the reference).  logdir: see vbmf_.
+    form: None (the library's rule: VBMF_GRAM, then the size rule, which never takes the Gram form at H > 128), "stream", or "gram":
+    iterate on Y'Y at any size and up to H = 256.  "gram" raises ValueError naming the reason where the
+    context cannot take the form: fp32 storage (the default here: set_defaults(y_dtype=VBMF_Y_BF16)), the single-bf16 factor,
+    diag_var, full_cov, H > 256."""
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, form=form)
 
 
 def vbmf_sparse(Y, params_in, niter, **kw):

@@ -29,6 +29,8 @@ UNIQUE_ID_BYTES = 128
 VBMF_FIT_FORM_STREAM, VBMF_FIT_FORM_GRAM, VBMF_FIT_FORM_AUTO = 0, 1, 2
 VBMF_FIT_GRAM_WIDE_FACTOR = 2
 VBMF_FIT_LDS_CAP_BYTES = 144 * 1024
+VBMF_GRAM_FORM_DEFAULT, VBMF_GRAM_FORM_OFF, VBMF_GRAM_FORM_ON = 0, 1, 2
+GRAM_FORMS = {"stream": VBMF_GRAM_FORM_OFF, "gram": VBMF_GRAM_FORM_ON}
 FIT_FORMS = {"stream": VBMF_FIT_FORM_STREAM, "gram": VBMF_FIT_FORM_GRAM, "auto": VBMF_FIT_FORM_AUTO}
 
 
@@ -64,7 +66,7 @@ SYMBOLS = [
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
-    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares",
+    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_set_gram_form",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
@@ -170,6 +172,7 @@ def lib():
     L.vbmf_sparse_lower_bound_batched.argtypes = [vp, i64, C.POINTER(i64), i32, C.c_double, i32] + [dp] * 15
     L.vbmf_bag_least_squares.argtypes = [vp, i64, C.POINTER(i64), dp, i64, i64, C.c_double, dp, i64, dp]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
+    L.vbmf_set_gram_form.argtypes = [vp, i32]
     L.vbmf_sparse_set_SigmaA.argtypes = [vp, dp]
     L.vbmf_sparse_get_SigmaA.argtypes = [vp, dp]
     L.vbmf_dual_set_priors.argtypes = [vp, i64] + [C.c_double] * 6
@@ -647,6 +650,10 @@ class Context:
 
     def sparse_set_full_cov(self, on=True):
         self._chk(self._lib.vbmf_sparse_set_full_cov(self._h, int(bool(on))))
+
+    def set_gram_form(self, mode):
+        """VBMF_GRAM_FORM_DEFAULT / _OFF / _ON (vbmf_set_gram_form): which form the run loops take; dims()["gram"] reports the outcome."""
+        self._chk(self._lib.vbmf_set_gram_form(self._h, int(mode)))
 
     def sparse_set_SigmaA(self, SigmaA):
         S = _fcol(SigmaA, (self.H, self.H))

@@ -12,6 +12,10 @@
 //                          product once, on fp64 MFMA) and sum A o P
 //   gram_part_reduce_kernel  fixed-order sum of the shares -> the state's [B'B | dB'dB | tr(B'YA)], symmetrised as (C + C') / 2
 //
+// Rank 256 (Hp = 256, the ARD-sparse model under VBMF_GRAM_FORM_ON) runs on the Hp = 128 geometry of each kernel, blocked:
+// gram_w_cols_kernel<256, 2> (two workgroups per row block, one per column half), gram_prod_kernel<4, 8> (two h-tile groups),
+// gram_tail_kernel<128, 256> (four 128 x 128 blocks per product and chunk), gram_part_reduce_kernel<128, 256>.
+//
 // Layouts.  G is stored as MFMA operand fragments, fp32: Gt[row tile p][k-step j][lane][8], lane (half, c) holds
 // G[32p + c][16j + 8 half + e], e = 0..7 (GT row tiles, KT = 2 GT k-steps; rows / columns >= M are zero).  Because G is symmetric this
 // fragment is also the B operand "k = 16j + 8 half + e, column 32p + c", so mfma(W^T fragment, G fragment) yields the TRANSPOSED product
@@ -194,6 +198,77 @@ __global__ __launch_bounds__(HP * 4) void gram_w_kernel(const float* __restrict_
     }
 }
 
+// The same at HP = 256, where one workgroup would be 1024 threads (a 128-register budget) holding 64 doubles of S per lane: the
+// columns go to NCG = 2 workgroups of 512 threads (blockIdx.y = column group: HP / NCG columns, HP / NCG / 16 waves), the register
+// budget doubles and the panel fits.  Every wave still sums its column over all HP rows of S in the order above, so an element of
+// W is the value the one-workgroup form would give; the pack stage writes the column group's h tiles of the NH = HP / 32 layout.
+template <int HP, int NCG>
+__global__ __launch_bounds__(HP * 4 / NCG) void gram_w_cols_kernel(const float* __restrict__ A32, const float* __restrict__ S,
+                                                                   const float* __restrict__ Wold, float* __restrict__ Wnew,
+                                                                   uint4* __restrict__ Wt, long long M, int KT,
+                                                                   const int* __restrict__ stop) {
+    if (*stop) return;
+    constexpr int NS = HP / 16, NH = HP / 32, HC = HP / NCG, NHC = NH / NCG, NT = HP * 4 / NCG;
+    static_assert(HC % 32 == 0 && NT <= 512, "gram_w_cols geometry");
+    __shared__ float sW[GW_ROWS][HC + 1];
+    const int lane = threadIdx.x & 63, cb = threadIdx.x >> 6;
+    const int q = lane >> 4, c = lane & 15;
+    const int col0 = blockIdx.y * HC;                              // first column of this workgroup
+    const long long row0 = (long long)blockIdx.x * GW_ROWS;
+    double sb[NS][4];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sb[s][t] = (double)S[(long long)(16 * s + 4 * q + t) * HP + col0 + 16 * cb + c];
+#pragma unroll
+    for (int mb = 0; mb < GW_KS; ++mb) {
+        const long long m = row0 + 16 * mb + c;
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const float4 a = m < M ? *reinterpret_cast<const float4*>(A32 + m * HP + 16 * s + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.x, sb[s][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.y, sb[s][1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.z, sb[s][2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a.w, sb[s][3], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sW[16 * mb + q + 4 * r][16 * cb + c] = (float)acc[r];
+    }
+    __syncthreads();
+    const long long plane = (long long)KT * NH * 64;
+    for (int it = threadIdx.x; it < GW_KS * NHC * 64; it += NT) {
+        const int jj = it / (NHC * 64), htl = (it / 64) % NHC, ln = it & 63;
+        const int half = ln >> 5, hl = 32 * htl + (ln & 31), h = col0 + hl, ht = blockIdx.y * NHC + htl;
+        const long long j = (long long)blockIdx.x * GW_KS + jj;
+        if (j >= KT) continue;
+        unsigned short wp[3][8], dp[2][8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const long long m = 16 * j + 8 * half + e;
+            const float wv = sW[16 * jj + 8 * half + e][hl];
+            const float dv = (float)((double)wv - (double)Wold[m * HP + h]);
+            Wnew[m * HP + h] = wv;
+            wp[0][e] = f2bf(wv);
+            float res = wv - bf2f(wp[0][e]);
+            wp[1][e] = f2bf(res);
+            res -= bf2f(wp[1][e]);
+            wp[2][e] = f2bf(res);
+            dp[0][e] = f2bf(dv);
+            dp[1][e] = f2bf(dv - bf2f(dp[0][e]));
+        }
+        const long long o = (j * NH + ht) * 64 + ln;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+            Wt[p * plane + o] = make_uint4(pack_bf2(wp[p][0], wp[p][1]), pack_bf2(wp[p][2], wp[p][3]), pack_bf2(wp[p][4], wp[p][5]),
+                                           pack_bf2(wp[p][6], wp[p][7]));
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            Wt[(3 + p) * plane + o] = make_uint4(pack_bf2(dp[p][0], dp[p][1]), pack_bf2(dp[p][2], dp[p][3]), pack_bf2(dp[p][4], dp[p][5]),
+                                                 pack_bf2(dp[p][6], dp[p][7]));
+    }
+}
+
 // a - b as one v_sub_f32.  Written out because the compiler packs neighbouring fp32 subtractions into v_pk_add_f32, which beside
 // MFMAs costs more than the two scalar instructions it replaces; the result is the same IEEE difference.
 __device__ __forceinline__ float sub_f32(float a, float b) {
@@ -291,7 +366,11 @@ struct GramProd {
         return n;
     }
 };
-template <int NH>
+//
+// NHT > NH: the workgroup multiplies h-tile group blockIdx.y (NH tiles) of NHT in all -- the operand planes and the output are in the
+// NHT layout, the geometry, the loop and every accumulator's MFMA sequence are those of NH.  Rank 256 runs as two groups of <4>:
+// G is read once per group; the other way, GramProd<8> with one k-step per plane chunk, is in DESIGN.md section 10.
+template <int NH, int NHT = NH>
 __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const float4* __restrict__ Gt, const uint4* __restrict__ Wt,
                                                                           float* __restrict__ Out, int GT, int XT1, int sps, int nrg,
                                                                           long long n, long long slab_floats,
@@ -307,7 +386,8 @@ __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const 
     const int j0 = s * sps, j1 = min(j0 + sps, KT), nk = j1 - j0;
     const int pt0 = rg * C::TPG + (w % (C::TPG / NXW)) * NXW;          // first row tile of this wave
     const int h0 = (w / (C::TPG / NXW)) * NHW;                        // first h tile of this wave
-    const long long plane = (long long)KT * NH * 64;
+    const int hg0 = NHT == NH ? 0 : (int)blockIdx.y * NH;             // first h tile of this workgroup's group
+    const long long plane = (long long)KT * NHT * 64;
     f32x16 accP[NXW][NHW], accQ[NXW][NHW];
 #pragma unroll
     for (int i = 0; i < NXW; ++i)
@@ -338,7 +418,7 @@ __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const 
             const int x = min(w + NW * v, NP - 1);
             const int q = x / (CH * NH), r = x % (CH * NH);
             const int j = min(j0 + t + r / NH, j1 - 1);
-            lds_dma_piece(wr, gram_lds + (cc * NP + x) * 1024, voff, (int)(q * plane + ((long long)j * NH + r % NH) * 64) * 16);
+            lds_dma_piece(wr, gram_lds + (cc * NP + x) * 1024, voff, (int)(q * plane + ((long long)j * NHT + hg0 + r % NH) * 64) * 16);
         }
     };
     // the sequence the loop issues at k-steps -D .. -1: chunk 0's planes (at each chunk start among them; the same bytes to the same
@@ -425,7 +505,7 @@ __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const 
         if (p >= XT1) continue;
 #pragma unroll
         for (int h = 0; h < NHW; ++h) {
-            const long long o = (((long long)p * NH + h0 + h) * 64 + lane) * 4;
+            const long long o = (((long long)p * NHT + hg0 + h0 + h) * 64 + lane) * 4;
             const f32x16 a = accP[i][h], d = accQ[i][h];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -512,13 +592,28 @@ __device__ __forceinline__ float4 gtail_sum(const GTailRound& v, float4 f, int c
     if (cnt > 7) add4(f, v.a7);
     return f;
 }
-template <int HP>
+//
+// HPT > HP (rank 256 as HP = 128): a share of HPT x HPT would be 256 fp64 registers per thread, so it is blocked.  NQ^2 workgroups
+// (NQ = HPT / HP) per product and chunk, workgroup (qa, qb) forming the HP x HP block C[HP qa ..][HP qb ..] with the geometry above:
+// it folds the HP columns from HP qb of the chunk's rows (both workgroups of a column half fold it; the qa = 0 one stores it to PQ)
+// and takes its A operands from column HP qa on.  The share is [P blocks (qa, qb) in that order | Q blocks | NQ trace slots], each
+// block in the register order of HP; trace slot q holds sum A o P over the columns of block (q, q), from that workgroup.
+template <int HP, int HPT>
+struct GPartBlk {
+    static constexpr int NQ = HPT / HP;
+    static constexpr long long STRIDE = 2LL * HPT * HPT + (NQ == 1 ? 1 : NQ);   // doubles per chunk share
+};
+template <int HP, int HPT = HP>
 __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int nslab, long long slab_floats, float* PQ, long long n,
                                                         long long Mp1, const float* __restrict__ Wn, const float* __restrict__ Wo,
                                                         const float* __restrict__ A32, long long M, int rpc, int nchunk,
                                                         double* __restrict__ part, const int* __restrict__ stop) {
     using C = GPart<HP>;
     constexpr int V = C::V, S = C::S, NH = C::NH, PPT = C::PPT, SD = C::SD, ROWS = C::ROWS, NSTEP = C::NSTEP, SU = C::SU;
+    constexpr int NQ = GPartBlk<HP, HPT>::NQ, NHT = HPT / 32;
+    constexpr bool BLK = NQ > 1;
+    constexpr long long STRIDE = GPartBlk<HP, HPT>::STRIDE;
+    static_assert(HPT % HP == 0, "gram_tail blocks");
     __shared__ __attribute__((aligned(32))) float stage[2 * C::BUF];
     __shared__ double red[8];
     const int stopv = *stop;
@@ -526,7 +621,9 @@ __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int 
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // known to be the same for the whole wave
     const int s = w / V, tw = w % V;
     const int q = lane >> 4, c = lane & 15;
-    const int chunk = blockIdx.x >> 1, pi = blockIdx.x & 1;
+    const unsigned cp = BLK ? blockIdx.x / (NQ * NQ) : blockIdx.x;     // (chunk, product)
+    const int qa = BLK ? (blockIdx.x / NQ) % NQ : 0, qb = BLK ? blockIdx.x % NQ : 0;
+    const int chunk = cp >> 1, pi = cp & 1;
     const long long m0 = (long long)chunk * rpc, m1 = min(m0 + rpc, M);
     const long long fend = chunk == nchunk - 1 ? Mp1 : m0 + rpc;     // rows folded here: a multiple of 16, as m0 is
     const float* src = slabs + (pi ? n : 0);
@@ -548,7 +645,7 @@ __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int 
     float wv[NSTEP], xv[NSTEP];
     auto piece_off = [&](long long rb, int j) __attribute__((always_inline)) {
         const long long row = rb + 16 * grp[j] + xr;
-        return ((((row >> 5) * NH + ht[j]) * 64 + half[j] * 32 + (row & 31)) << 4) + 4 * r4;
+        return ((((row >> 5) * NHT + qb * NH + ht[j]) * 64 + half[j] * 32 + (row & 31)) << 4) + 4 * r4;
     };
     // slabs k0 .. k0 + cnt - 1 of the block at row rb: cnt = 1 .. SD picks one straight-line run of loads (gtail_load) or adds.
     // Buffer loads: a slab's descriptor is uniform and the piece's 32-bit offset serves all of its slabs.
@@ -572,14 +669,14 @@ __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int 
         }
     };
     // W and A (or W_old) of the block's steps.  The descriptors end with the chunk, so rows at or past its end load as zeros.
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)Wn, 0, (unsigned)(m1 * HP * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t xd = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (unsigned)(m1 * HP * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)Wn, 0, (unsigned)(m1 * HPT * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xd = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (unsigned)(m1 * HPT * 4), 0x00020000);
     auto issue_w = [&](long long rb) __attribute__((always_inline)) {
-        const int o = (int)(((rb + 4 * s + q) * HP + V * c + tw) * 4);
+        const int o = (int)(((rb + 4 * s + q) * HPT + qa * HP + V * c + tw) * 4);
 #pragma unroll
         for (int i = 0; i < NSTEP; ++i) {
-            wv[i] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(wr, o + i * (4 * S * HP * 4), 0, 0));
-            xv[i] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(xd, o + i * (4 * S * HP * 4), 0, 0));
+            wv[i] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(wr, o + i * (4 * S * HPT * 4), 0, 0));
+            xv[i] = bitsf(__builtin_amdgcn_raw_buffer_load_b32(xd, o + i * (4 * S * HPT * 4), 0, 0));
         }
     };
     issue_slabs(m0, 0);
@@ -601,7 +698,7 @@ __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int 
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
             if (rb + 16 * grp[j] >= fend) continue;
-            if (nslab > 1) *reinterpret_cast<float4*>(dst + piece_off(rb, j)) = f[j];
+            if (nslab > 1 && (!BLK || qa == 0)) *reinterpret_cast<float4*>(dst + piece_off(rb, j)) = f[j];
             *reinterpret_cast<float4*>(sb + (16 * grp[j] + xr) * HP + 32 * ht[j] + 8 * r4 + 4 * half[j]) = f[j];
         }
         // this block's A operands, so that the next block's may be requested
@@ -640,7 +737,7 @@ __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int 
                 }
 #pragma unroll
                 for (int t = 0; t < V; ++t) pv[t] = in ? pv[t] : 0.f;
-                if (!pi) {
+                if (!pi && (!BLK || qa == qb)) {
                     float p = 0.f;
 #pragma unroll
                     for (int t = 0; t < V; ++t) p = t == tw ? pv[t] : p;
@@ -665,21 +762,21 @@ __global__ __launch_bounds__(512) void gram_tail_kernel(const float* slabs, int 
                 for (int t = 0; t < V; ++t) acc[t] += fold[(((s2 - 1) * V + tw) * V + t) * 64 + lane];
         }
     }
-    double* o = part + (long long)chunk * (2 * HP * HP + 1) + pi * HP * HP;
+    double* o = part + (long long)chunk * STRIDE + pi * HPT * HPT + (qa * NQ + qb) * HP * HP;
     if (s == 0) {
 #pragma unroll
         for (int t = 0; t < V; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[(((tw * V + t) * 4 + r) << 6) + lane] = acc[t][r];
     }
-    if (pi) return;
+    if (pi || (BLK && qa != qb)) return;
     for (int off = 32; off > 0; off >>= 1) tr += __shfl_down(tr, off);
     if (lane == 0) red[w] = tr;
     __syncthreads();
     if (threadIdx.x == 0) {
         double t = 0.0;
         for (int i = 0; i < 8; ++i) t += red[i];
-        part[(long long)chunk * (2 * HP * HP + 1) + 2 * HP * HP] = t;
+        part[(long long)chunk * STRIDE + 2 * HPT * HPT + qa] = t;
     }
 }
 
@@ -705,21 +802,28 @@ __device__ __forceinline__ void gred_round(const double* __restrict__ part, int 
     for (int u = 0; u < DP; ++u)
         if (k + u * GRED_G < nchunk) { s0 += v0[u]; s1 += v1[u]; }
 }
-template <int HP>
+// HPT > HP: the blocked shares of gram_tail_kernel<HP, HPT>.  Position e lies in block (qa, qb) of its product; its transposed
+// position lies in block (qb, qa), at the transposed place of HP's register order.  The NQ trace slots are added in slot order.
+template <int HP, int HPT = HP>
 __global__ __launch_bounds__(256) void gram_part_reduce_kernel(const double* __restrict__ part, int nchunk, double* __restrict__ st,
                                                                StateLayout lay, const int* __restrict__ stop) {
     const int stopv = *stop;
-    constexpr int V = GPart<HP>::V, n2 = HP * HP;
-    constexpr long long stride = 2LL * n2 + 1;
+    constexpr int V = GPart<HP>::V, n2 = HPT * HPT, nb = HP * HP, NQ = GPartBlk<HP, HPT>::NQ;
+    constexpr bool BLK = NQ > 1;
+    static_assert(NQ <= 2, "gram_part_reduce: two trace slots");
+    constexpr long long stride = GPartBlk<HP, HPT>::STRIDE;
     __shared__ double sum[2][GRED_G][GRED_E];
     const int el = threadIdx.x % GRED_E, g = threadIdx.x / GRED_E;
     const int e = blockIdx.x * GRED_E + el;                       // < 2 n2 + GRED_E; e == 2 n2: the trace
     // e = pi n2 + register-order index ((tw V + t) 4 + rq) 64 + 16 q + c  <->  C[a][b], a = V (q + 4 rq) + tw, b = V c + t
-    const int pi = e / n2, x = e % n2;
+    const int pi = e / n2, blk = BLK ? (e % n2) / nb : 0, x = BLK ? e % nb : e % n2;
+    const int qa = blk / NQ, qb = blk % NQ;
     const int tw = (x >> 8) / V, t = (x >> 8) % V, rq = (x >> 6) & 3, q = (x >> 4) & 3, c = x & 15;
-    const int a = V * (q + 4 * rq) + tw, b = V * c + t;
+    const int al = V * (q + 4 * rq) + tw, bl = V * c + t;
+    const int a = qa * HP + al, b = qb * HP + bl;
     const bool mat = e < 2 * n2, tro = e == 2 * n2;
-    const long long i0 = mat ? e : 2LL * n2, i1 = mat ? (long long)pi * n2 + gpart_index<HP>(b, a) : 2LL * n2;
+    const long long i0 = mat ? e : 2LL * n2;
+    const long long i1 = mat ? (long long)pi * n2 + (qb * NQ + qa) * nb + gpart_index<HP>(bl, al) : 2LL * n2 + (BLK ? 1 : 0);
     double s0 = 0.0, s1 = 0.0;
     for (int k = g; k < nchunk; k += 32 * GRED_G) {
         const int left = (nchunk - k + GRED_G - 1) / GRED_G;     // the same for the whole wave
@@ -734,8 +838,8 @@ __global__ __launch_bounds__(256) void gram_part_reduce_kernel(const double* __r
     if (g != 0 || !(mat || tro)) return;
     double t0 = 0.0, t1 = 0.0;
     for (int k = 0; k < GRED_G; ++k) { t0 += sum[0][k][el]; t1 += sum[1][k][el]; }
-    if (tro) st[lay.GX()] = t0;
-    else st[(pi ? lay.GD() : lay.GB()) + a * HP + b] = 0.5 * (t0 + t1);
+    if (tro) st[lay.GX()] = BLK ? t0 + t1 : t0;
+    else st[(pi ? lay.GD() : lay.GB()) + a * HPT + b] = 0.5 * (t0 + t1);
 }
 
 }  // namespace vbmf

@@ -20,7 +20,8 @@
 //
 // Tall matrices (gram_eligible): vbmf_run takes the Gram form instead -- B = Y W with W = A SigmaB / sigma2, so a sweep reads the
 // M x M matrix G = Y'Y (built once per Y) in place of Y (gram_kernels.hpp); so does vbmf_sparse_run for the
-// diagonal homoscedastic ARD-sparse model (sparse_gram_sweep).
+// diagonal homoscedastic ARD-sparse model (sparse_gram_sweep), up to rank 128 by that rule and up to rank 256 when vbmf_set_gram_form
+// (or VBMF_GRAM=3) switches the form on.
 //
 // vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): ONE pass 1 with the frozen B over the bags side by side,
 // then bag_gram (S_b = P_b'P_b, ||Y_b||^2), vbls_batch (all iterations, one workgroup per bag) and bag_a (A_b = P_b SigmaA_b / sigma2_b).
@@ -175,7 +176,8 @@ struct vbmf_ctx {
     double* bags = nullptr;           // the many-bags entries (host_bags.hpp): per-bag inputs, partials and outputs of the call in
     size_t bags_bytes = 0;            // flight, each entry in its own layout (grown on demand)
     // Gram-form sweep of vbmf_run (gram_kernels.hpp); buffers allocated by the first run that takes it
-    int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows (basic model), 2 the sparse model too
+    int gram_env = -1;                // VBMF_GRAM: -1 the size rule (gram_eligible), 0 never, 1 whenever the structure allows (basic model), 2 the sparse model too, 3 VBMF_GRAM_FORM_ON
+    int gram_form = VBMF_GRAM_FORM_DEFAULT;   // vbmf_set_gram_form: DEFAULT the rule above, OFF never, ON wherever the structure allows (rank 256 included)
     int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
     int g_nsplit = 1, g_sps = 0, g_nrg = 0, g_nchunk = 0, g_rpc = 0;
     float* Gt = nullptr;              // G = Y'Y as fp32 MFMA operand fragments [GT][2 GT][64][8]
@@ -1029,30 +1031,55 @@ static int do_update_B(vbmf_ctx* c, bool keep_sigma = false) {
 // the B side is masked, B = Y W with W = sigmaHat A SigmaB -- and follows the same size rule (measured at 100k x 10k: 2.7x the streaming
 // sweep at H = 64, 2.1x at H = 128).  It is forced on by VBMF_GRAM=2, which forces the basic model too; VBMF_GRAM=1
 // forces the basic model only and leaves a sparse context to the size rule.
+// vbmf_set_gram_form (or VBMF_GRAM=3 at creation) overrides both: OFF always streams, ON takes the form wherever the structure
+// allows it -- and only ON admits the sparse model at Hp = 256 (gram_w_cols, gram_prod<4, 8>, the blocked gram_tail), which no size
+// rule and no other VBMF_GRAM value turns on.  The basic model at Hp = 256 stays streaming: its Gram sweep is the fused one (NH <= 4).
+static bool gram_form_on(const vbmf_ctx* c) {
+    return c->gram_form == VBMF_GRAM_FORM_ON || (c->gram_form == VBMF_GRAM_FORM_DEFAULT && c->gram_env == 3);
+}
 static bool gram_structural(const vbmf_ctx* c) {
     return !c->diagvar && !c->dual && !c->trial && !c->full_cov && !sharded(c) && c->o.nranks == 1 && c->o.y_dtype == VBMF_Y_BF16 &&
-           c->mode == MODE_BF16X2 && c->Hp <= 128;
+           c->mode == MODE_BF16X2 && (c->Hp <= 128 || (c->Hp == 256 && c->sparse && gram_form_on(c)));
 }
 static bool gram_eligible(const vbmf_ctx* c) {
-    if (c->gram_env == 0 || !gram_structural(c)) return false;
+    if (c->gram_form == VBMF_GRAM_FORM_OFF || !gram_structural(c)) return false;
+    if (gram_form_on(c)) return true;
+    if (c->gram_env == 0) return false;
     if (c->gram_env == 2 || (c->gram_env == 1 && !c->sparse)) return true;
     return c->L >= 4 * c->M && (double)c->L * (double)c->M >= 134217728.0;
 }
+
+// h tiles per workgroup of the product kernel: all NH up to 4; rank 256 runs as two groups of the NH = 4 geometry
+static int gram_prod_nh(const vbmf_ctx* c) { return c->NH == 8 ? 4 : c->NH; }
 
 // buffers (first time) and G of the current Y (once per Y)
 static int gram_prepare(vbmf_ctx* c) {
     if (!c->Gt) {
         c->GT = (int)rup(c->d1.XT, 16);
         const int KT = 2 * c->GT;
-        c->g_nrg = c->GT / (16 / c->NH);                                       // row groups of GramProd<NH>::TPG row tiles
+        const int nhp = gram_prod_nh(c);
+        c->g_nrg = c->GT / (16 / nhp);                                         // row groups of GramProd<nhp>::TPG row tiles
         // split-K: about one workgroup per CU, each split at least 8 k-steps
         c->g_nsplit = std::max(1, std::min(KT / 8, NUM_CU / std::max(1, c->g_nrg)));
+        if (c->NH != nhp) {
+            // rank 256: NH / nhp h-tile groups, so w = g_nrg NH / nhp workgroups per split, one per CU at a time (144 KB of LDS).  A
+            // split count s runs in ceil(w s / NUM_CU) rounds of 1 / s of the k-steps each: the s <= 4 with the smallest product, the
+            // smaller s on a tie (a slab is written and read back once per split).  Config 5: w = 160, s = 3, 480 workgroups in two
+            // rounds of 1/3; one split from w = 193 on (GT >= 400).
+            const int w = c->g_nrg * (c->NH / nhp), smax = std::max(1, std::min(KT / 8, 4));
+            int best = 1;
+            for (int s = 2; s <= smax; ++s)
+                if ((int64_t)cdiv(w * s, NUM_CU) * best < (int64_t)cdiv(w * best, NUM_CU) * s) best = s;
+            c->g_nsplit = best;
+        }
         c->g_sps = cdiv(KT, c->g_nsplit);
         c->g_nsplit = cdiv(KT, c->g_sps);
         const int64_t Mp1 = (int64_t)c->d1.XT * 32;
         // gram_tail: two workgroups of 8 waves per chunk (one per product); 128 chunks at Hp <= 64 (one workgroup per CU), 64 at
         // Hp = 128, where a share is 4x larger.  The plan is the one the 16-wave gram_part had: the sums' order depends on it.
-        c->g_nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(c->Hp == 128 ? 64 : 128, cdiv(c->M, 64)));
+        // Hp = 256: eight workgroups per chunk (two products x four 128 x 128 blocks) and a share of 1 MB: 32 chunks, one workgroup
+        // per CU, 32 MB of shares; gram_part_reduce then sums eight chunks per group in one round.
+        c->g_nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(c->Hp == 256 ? 32 : (c->Hp == 128 ? 64 : 128), cdiv(c->M, 64)));
         c->g_rpc = (int)rup(cdiv(c->M, c->g_nchunk), 16);
         c->g_nchunk = cdiv(c->M, c->g_rpc);
         const size_t n = (size_t)c->Hp * Mp1;
@@ -1070,7 +1097,7 @@ static int gram_prepare(vbmf_ctx* c) {
         if (e == hipSuccess) e = alloc((void**)&c->Wt, (size_t)GRAM_PLANES * KT * c->NH * 64 * 16);
         if (e == hipSuccess) e = alloc((void**)&c->gPQ, 2 * n * 4);
         if (e == hipSuccess && c->g_nsplit > 1) e = alloc((void**)&c->gslabs, (size_t)c->g_nsplit * 2 * n * 4);
-        if (e == hipSuccess) e = alloc((void**)&c->g_part, (size_t)c->g_nchunk * (2 * (size_t)c->Hp * c->Hp + 1) * 8);
+        if (e == hipSuccess) e = alloc((void**)&c->g_part, (size_t)c->g_nchunk * (2 * (size_t)c->Hp * c->Hp + 2) * 8);   // (+2: the blocked share's trace slots)
         if (e == hipSuccess) e = alloc((void**)&c->gsave, (2 * (size_t)c->Hp * c->Hp + 8) * 8);
         if (e != hipSuccess) {
             for (void* b : {(void*)c->Gt, (void*)c->W32g[0], (void*)c->W32g[1], (void*)c->Wt, (void*)c->gPQ, (void*)c->gslabs,
@@ -1117,15 +1144,18 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     const dim3 wg(cdiv(KT, GW_KS));
     if (c->Hp == 32) hipLaunchKernelGGL((gram_w_kernel<32>), wg, dim3(128), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
     else if (c->Hp == 64) hipLaunchKernelGGL((gram_w_kernel<64>), wg, dim3(256), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
-    else hipLaunchKernelGGL((gram_w_kernel<128>), wg, dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+    else if (c->Hp == 128) hipLaunchKernelGGL((gram_w_kernel<128>), wg, dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+    else if (c->Hp == 256) hipLaunchKernelGGL((gram_w_cols_kernel<256, 2>), dim3(wg.x, 2), dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+    else FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 256");
     HIPCHK(c, hipGetLastError());
     float* out = c->g_nsplit > 1 ? c->gslabs : c->gPQ;
-    const dim3 grid(c->g_nrg * c->g_nsplit);
+    const dim3 grid(c->g_nrg * c->g_nsplit, c->NH / gram_prod_nh(c));
     const float4* G4 = reinterpret_cast<const float4*>(c->Gt);
     prof_begin(c, 0);
     if (c->NH == 1) hipLaunchKernelGGL((gram_prod_kernel<1>), grid, dim3(GramProd<1>::THREADS), GramProd<1>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
     else if (c->NH == 2) hipLaunchKernelGGL((gram_prod_kernel<2>), grid, dim3(GramProd<2>::THREADS), GramProd<2>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    else hipLaunchKernelGGL((gram_prod_kernel<4>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    else if (c->NH == 4) hipLaunchKernelGGL((gram_prod_kernel<4>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
+    else hipLaunchKernelGGL((gram_prod_kernel<4, 8>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
     prof_end(c);
     HIPCHK(c, hipGetLastError());
     if (!partials) {
@@ -1141,12 +1171,14 @@ static int gram_product(vbmf_ctx* c, bool partials) {
         const long long M = (long long)c->M;
         if (c->Hp == 32) hipLaunchKernelGGL((gram_tail_kernel<32>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
         else if (c->Hp == 64) hipLaunchKernelGGL((gram_tail_kernel<64>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
-        else hipLaunchKernelGGL((gram_tail_kernel<128>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
+        else if (c->Hp == 128) hipLaunchKernelGGL((gram_tail_kernel<128>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
+        else hipLaunchKernelGGL((gram_tail_kernel<128, 256>), dim3(8 * c->g_nchunk), dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
         HIPCHK(c, hipGetLastError());
         const dim3 rg(cdiv(2 * (int64_t)c->Hp * c->Hp + 1, GRED_E));
         if (c->Hp == 32) hipLaunchKernelGGL((gram_part_reduce_kernel<32>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
         else if (c->Hp == 64) hipLaunchKernelGGL((gram_part_reduce_kernel<64>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
-        else hipLaunchKernelGGL((gram_part_reduce_kernel<128>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
+        else if (c->Hp == 128) hipLaunchKernelGGL((gram_part_reduce_kernel<128>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
+        else hipLaunchKernelGGL((gram_part_reduce_kernel<128, 256>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
         HIPCHK(c, hipGetLastError());
     }
     return VBMF_OK;
@@ -1464,7 +1496,7 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
     if (const char* e = getenv("VBMF_XCD_MAP")) c->xcd_map = atoi(e) != 0;      // A/B switch for the tuning record
     if (const char* e = getenv("VBMF_GRAM")) {          // Gram-form sweep: force off / on / on for the ARD-sparse model too (gram_eligible)
         const int v = atoi(e);
-        c->gram_env = v == 0 ? 0 : (v == 2 ? 2 : 1);
+        c->gram_env = v == 0 ? 0 : (v == 2 || v == 3 ? v : 1);   // 3: VBMF_GRAM_FORM_ON from creation on
     }
     if (const char* e = getenv("VBMF_EPI_BALANCE")) c->epi_balance = atoi(e) != 0;
     if (const char* e = getenv("VBMF_LDS8")) c->lds8 = atoi(e) != 0;
@@ -1690,6 +1722,8 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
             e = hipFuncSetAttribute((const void*)gram_prod_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<2>::LDS_BYTES);
         if (e == hipSuccess && c->NH == 4)
             e = hipFuncSetAttribute((const void*)gram_prod_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<4>::LDS_BYTES);
+        if (e == hipSuccess && c->NH == 8)          // rank 256: two h-tile groups of the NH = 4 geometry
+            e = hipFuncSetAttribute((const void*)gram_prod_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<4>::LDS_BYTES);
         if (e != hipSuccess) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return bail(VBMF_ERR_HIP); }
     }
     // the zero-fills above ran on the null stream; all later work runs on a non-blocking stream
@@ -2454,7 +2488,8 @@ int vbmf_pass_bytes(vbmf_ctx* c, int pass, double* bytes) {
         // Gram form: profile slot 1 times the product [G W | G D] -- G once (fp32), the five bf16 operand planes, the fp32 slabs out
         const double n = (double)c->Hp * c->d1.XT * 32.0;
         const int nsplit = c->Gt ? c->g_nsplit : 1;
-        *bytes = (double)c->M * c->M * 4.0 + 5.0 * c->M * c->H * 2.0 + 2.0 * n * 4.0 * nsplit;
+        // (rank 256: G once per h-tile group)
+        *bytes = (double)c->M * c->M * 4.0 * (c->NH / gram_prod_nh(c)) + 5.0 * c->M * c->H * 2.0 + 2.0 * n * 4.0 * nsplit;
         return VBMF_OK;
     }
     if (pass == 1) *bytes = LM * ybytes + (double)c->L * c->H * 4.0 + (double)c->M * c->H * 4.0;
@@ -2879,7 +2914,8 @@ static int sparse_gram_sweep(vbmf_ctx* c) {
     if (c->NH == 1) SPARSE_A_FRAG(1);
     else if (c->NH == 2) SPARSE_A_FRAG(2);
     else if (c->NH == 4) SPARSE_A_FRAG(4);
-    else FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 128");
+    else if (c->NH == 8) SPARSE_A_FRAG(8);
+    else FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 256");
 #undef SPARSE_A_FRAG
     HIPCHK(c, hipGetLastError());
     c->P_frag = true;
@@ -3109,12 +3145,16 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         }
         // updateCA! reads what the A update left and writes what the NEXT A update reads: with a side stream (H > 128) it runs there too,
         // beside the next sweep's Y'B pass, instead of 13 us between the sweeps (not with the group priors or the row noise behind it)
-        const bool ca_on_side = side_overlap(c) && !est_priors && !c->diagvar;
+        // In a Gram-form run (rank 256 under VBMF_GRAM_FORM_ON) nothing is forked: whatever follows this sweep -- a Gram sweep, whose
+        // first kernel (sparse_v) reads the sigmaHat, B'B and SigmaB the control step writes, or the run's end -- has no pass over Y to
+        // hide the chain behind.  The run's first, streaming sweep keeps the forks inside its two updates (joined before its post kernel).
+        const bool overlap = side_overlap(c) && !gram;
+        const bool ca_on_side = overlap && !est_priors && !c->diagvar;
         if (rc == VBMF_OK && !ca_on_side) rc = sparse_update_CA(c);
         if (rc == VBMF_OK && est_priors) rc = dual_update_priors(c);      // depends on updateCA!'s outputs only
         if (rc == VBMF_OK && c->diagvar) rc = do_hetero_sigma(c);
         // lambda_max, CB, sigma, d and the stop test: beside the next sweep's Y'B pass when they run on the side stream
-        if (rc == VBMF_OK && side_overlap(c)) rc = side_fork(c);
+        if (rc == VBMF_OK && overlap) rc = side_fork(c);
         if (rc == VBMF_OK && ca_on_side) rc = sparse_update_CA(c);
         const bool t2_ahead = c->use_side && !c->diagvar;        // (diag_var: no scalar noise update, t2 is not used)
         if (rc == VBMF_OK && t2_ahead) rc = launch_sparse_t2(c);   // 64 workgroups, before the long lambda_max kernel
@@ -3187,6 +3227,17 @@ int vbmf_sparse_set_full_cov(vbmf_ctx* c, int on) {
     }
     c->full_cov = on != 0;
     c->W_valid = false;                                // (full_cov on: the context leaves the Gram form, gram_structural)
+    return VBMF_OK;
+}
+
+// which form the run loops take (gram_eligible); never fails for a structure that cannot take the Gram form -- VBMF_PEEK_DIMS
+// reports what was resolved.  The next run starts by the streaming path.
+int vbmf_set_gram_form(vbmf_ctx* c, int mode) {
+    if (!c) return VBMF_ERR_INVALID;
+    if (mode != VBMF_GRAM_FORM_DEFAULT && mode != VBMF_GRAM_FORM_OFF && mode != VBMF_GRAM_FORM_ON)
+        FAIL(c, VBMF_ERR_INVALID, "vbmf_set_gram_form: unknown mode %d", mode);
+    c->gram_form = mode;
+    c->W_valid = false;
     return VBMF_OK;
 }
 

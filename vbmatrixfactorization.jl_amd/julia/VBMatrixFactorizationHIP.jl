@@ -16,7 +16,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
-       vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!
+       vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!
 
 const libvbmf = get(ENV, "VBMF_HIP_LIB", joinpath(@__DIR__, "..", "libvbmf_hip.so"))
 
@@ -236,18 +236,20 @@ end
 
 "vbmf! -- src/vbmf.jl:175-231"
 function vbmf!(Y::Array{Float64,2}, params::vbmf_parameters, niter::Int; eps::Float64 = 1e-6, est_covs::Bool = false,
-               est_var::Bool = false, logdir = "", desc = "", verb = false)
-    return fit_basic!(Y, params, niter, eps, est_covs, est_var, logdir, verb)
+               est_var::Bool = false, logdir = "", desc = "", verb = false, form = nothing)
+    return fit_basic!(Y, params, niter, eps, est_covs, est_var, logdir, verb, form)
 end
 "vbmf! on a Float32 matrix: uploaded in its own format (vbmf_set_Y_rows), everything else as above"
 function vbmf!(Y::Array{Float32,2}, params::vbmf_parameters, niter::Int; eps::Float64 = 1e-6, est_covs::Bool = false,
-               est_var::Bool = false, logdir = "", desc = "", verb = false)
-    return fit_basic!(Y, params, niter, eps, est_covs, est_var, logdir, verb)
+               est_var::Bool = false, logdir = "", desc = "", verb = false, form = nothing)
+    return fit_basic!(Y, params, niter, eps, est_covs, est_var, logdir, verb, form)
 end
-function fit_basic!(Y::HostY, params::vbmf_parameters, niter::Int, eps::Float64, est_covs::Bool, est_var::Bool, logdir, verb)
+function fit_basic!(Y::HostY, params::vbmf_parameters, niter::Int, eps::Float64, est_covs::Bool, est_var::Bool, logdir, verb,
+                    form = nothing)
     logdir == "" || error("per-iteration logging: drive the sweeps from the reference's own create_log / update_log! / save_log " *
                           "(src/data_manip.jl works unchanged on these structs) around vbmf!(Y, params, 1; ...) calls")
     c = ctx_for(Y, params.H)
+    apply_form!(c, form, params.H > 128 ? "H > 128 (the basic model's Gram sweep covers H <= 128)" : "")
     push!(c, params)
     iters = Ref{Int64}(0); d = Ref{Float64}(0.0)
     chk(c.h, ccall((:vbmf_run, libvbmf), Cint,
@@ -548,6 +550,31 @@ function set_full_cov!(c::Ctx, p, full_cov::Bool)
     # always: set_state derives a diagonal SigmaA from diagSigmaATVec, which is not what a fresh init holds (zeros, :120-123)
     chk(c.h, ccall((:vbmf_sparse_set_SigmaA, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}), c.h, p.SigmaA))
 end
+# Which form the run loops take (vbmf_set_gram_form, include/vbmf_hip.h): 0 the library's rule, 1 stream, 2 the Gram form
+# wherever the structure allows it -- for the ARD-sparse model up to H = 256 (src/vbmf_sparse.jl:344-412 on G = Y'Y).
+const GRAM_FORMS = Dict(:default => 0, :stream => 1, :gram => 2)
+function set_gram_form!(c::Ctx, form::Symbol)
+    haskey(GRAM_FORMS, form) || error("form must be :stream or :gram (or nothing), not $form")
+    chk(c.h, ccall((:vbmf_set_gram_form, libvbmf), Cint, (Ptr{Cvoid}, Cint), c.h, GRAM_FORMS[form]))
+end
+"true when the context's run loops take the Gram form (word 16 of VBMF_PEEK_DIMS)"
+function gram_form_resolved(c::Ctx)
+    v = zeros(UInt32, 28)
+    chk(c.h, ccall((:vbmf_debug_peek, libvbmf), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt32}, Int64, Int64), c.h, 8, v, 28, 0))
+    return v[17] != 0
+end
+# the `form` keyword of vbmf! / vbmf_sparse!: nothing makes no call; :gram on a context that cannot take the form is an error
+# that names the reason (why: what the caller's arguments rule out; the storage formats and row shards otherwise)
+function apply_form!(c::Ctx, form, why::String)
+    form === nothing && return
+    set_gram_form!(c, form)
+    if form == :gram && !gram_form_resolved(c)
+        set_gram_form!(c, :default)
+        error("form = :gram refused: " * (why != "" ? why :
+              "the Gram form needs bf16 storage of Y (ENV[\"VBMF_HIP_Y\"] = \"bf16\"; fp32 is the default), bf16x2 factors and one rank"))
+    end
+end
+
 function pull_SigmaA!(c::Ctx, p)
     S = Array{Float64}(undef, p.H, p.H)
     chk(c.h, ccall((:vbmf_sparse_get_SigmaA, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}), c.h, S))
@@ -578,11 +605,13 @@ end
 
 "vbmf_sparse! -- src/vbmf_sparse.jl:344-410 (returns d, like the reference)"
 function vbmf_sparse!(Y::Array{Float64,2}, params::vbmf_sparse_parameters, niter::Int; eps::Float64 = 1e-6, diag_var::Bool = false,
-                      full_cov::Bool = false, logdir = "", desc = "", verb = false, est_cb::Bool = true)
+                      full_cov::Bool = false, logdir = "", desc = "", verb = false, est_cb::Bool = true, form = nothing)
     full_cov && params.H > 256 && error("full_cov=true is built for H <= 256 (either noise model)")
     logdir == "" || error("trajectory logging lives in the Python host (data_manip.py)")
     c = sparse_ctx_for(Y, params.H, diag_var); spush!(c, params, diag_var)
     set_full_cov!(c, params, full_cov)
+    # form = :stream | :gram (an extension: the reference has no such keyword); :gram iterates on Y'Y up to H = 256
+    apply_form!(c, form, diag_var ? "diag_var = true" : full_cov ? "full_cov = true" : params.H > 256 ? "H > 256" : "")
     iters = Ref{Int64}(0); d = Ref{Float64}(0.0)
     chk(c.h, ccall((:vbmf_sparse_run, libvbmf), Cint, (Ptr{Cvoid}, Int64, Float64, Cint, Ref{Int64}, Ref{Float64}, Ptr{Float64}),
                    c.h, niter, eps, est_cb, iters, d, C_NULL))
