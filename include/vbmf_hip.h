@@ -508,13 +508,16 @@ int vbmf_device_sync(vbmf_ctx* ctx);
 #define VBMF_PEEK_FB 5     /* BHat MFMA operand tiles */
 #define VBMF_PEEK_Y1 6     /* Y tiled for pass 1 */
 #define VBMF_PEEK_Y2 7     /* Y tiled for pass 2 */
-#define VBMF_PEEK_DIMS 8   /* int32 x 28: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run / vbmf_sparse_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
+#define VBMF_PEEK_DIMS 8   /* int32 x 30: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run / vbmf_sparse_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
                               p_frag / q_frag (the last pass 1 / pass 2 launch wrote its product fragment-major: [XT][NH][64][16]),
                               q_epi (the last pass 2 launch ran the register epilogue and stored no product), lds8 (H >= 128 bf16x2
                               passes run the LDS-DMA kernel), xcd_map (split-K launches use the XCD-aware work map), post3 (H >= 128
                               bf16 factor updates run post_frag3 rather than post_frag2), sparse_a_fused (the ARD-sparse A update writes its
                               operand tiles itself, VBMF_SPARSE_A_FUSED), set_y_rows_us (device time of the last vbmf_set_Y_rows call
-                              between two HIP events on the context's stream: staged copies, tiling kernels, ||Y||^2) */
+                              between two HIP events on the context's stream: staged copies, tiling kernels, ||Y||^2),
+                              b_pending (a Gram-form run has ended and BHat of its last sweep is not materialised yet: the first
+                              reader of B pays one streaming pass), b_materialised (how often that pass has run on demand).
+                              This peek never materialises B; every other one does, and shows its buffer as a run's end left it */
 #define VBMF_PEEK_CHAIN 9  /* uint64 x 8 (16 words): last durations in 10 ns ticks of the in-launch control chain's parts
                               (ctrl_end, SigmaA, lambda_max(dB'dB) + loop test, SigmaB) and of the register epilogue's tail in
                               workgroup 0 of the Y*A pass (wait for + load of the SigmaB table, tiles, fold + store, reserved) */

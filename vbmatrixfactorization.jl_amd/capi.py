@@ -812,14 +812,15 @@ class Context:
                         (float(x) * 0.01 for x in v)))
 
     def dims(self):
-        v = self.peek(PEEK_DIMS, 28, dtype=np.int32)
+        v = self.peek(PEEK_DIMS, 30, dtype=np.int32)
         keys = ["Hp", "NH", "mode", "XT1", "KS1", "nsplit1", "sps1", "XT2", "KS2", "nsplit2", "sps2", "kstep", "npart", "narrow",
                 "streamk_per", "streamk_grid",       # segment-list plan of the Y*A pass: pieces per cut block (0: off), segments = workgroups
                 "gram", "gram_built", "gram_build_us", "gram_nsplit",   # vbmf_run takes the Gram form; G built; its build time; split-K
                 "p_frag", "q_frag", "q_epi",         # the last pass 1 / pass 2 product is fragment-major; the last pass 2 ran the register epilogue
                 "lds8", "xcd_map", "post3",          # variant switches as the context resolved them (VBMF_LDS8, VBMF_XCD_MAP, VBMF_POST3)
                 "sparse_a_fused",                    # the ARD-sparse A update writes its operand tiles itself (VBMF_SPARSE_A_FUSED)
-                "set_y_rows_us"]                     # device time of the last vbmf_set_Y_rows call (HIP events: staged copies, tiling, ||Y||^2)
+                "set_y_rows_us",                     # device time of the last vbmf_set_Y_rows call (HIP events: staged copies, tiling, ||Y||^2)
+                "b_pending", "b_materialised"]       # B of the last Gram-form run is still owed; how often it has been made on demand
         return dict(zip(keys, (int(x) for x in v)))
 
     def time_pass(self, p, iters=10):

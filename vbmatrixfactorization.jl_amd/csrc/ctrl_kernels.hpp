@@ -238,6 +238,18 @@ __device__ __forceinline__ int load_stop(const int* ints) {
     return __hip_atomic_load(ints + I_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The run loops' view of the loop counters: host-mapped words (vbmf_ctx::loopw) that the host reads directly, so no copy and no event
+// enters the compute stream.  Called by the one thread that has just stored the counters to `ints`; stop goes out before iters (the
+// host reads them in the other order), as relaxed system-scope stores -- ordinary vector stores to fine-grained host memory, no fence.
+// The host may see a value late, never early.  hw == nullptr: no run loop is looking (stand-alone steps).
+__device__ __forceinline__ void publish_loop_words(int* __restrict__ hw, int* __restrict__ ints, int stop, int iters) {
+    if (hw == nullptr) return;
+    const int err = __hip_atomic_load(ints + I_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (err) __hip_atomic_store(hw + I_ERR, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (stop) __hip_atomic_store(hw + I_STOP, stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(hw + I_ITERS, iters, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Row-sharded runs: the ranks' error flags travel as one more number of the packed Gram message (post_kernels.hpp,
 // publish_err_flag) and arrive summed at st[GX + 1]; every rank's loop test reads the same sum, so a hand-off timeout or a bad
 // pivot on ONE rank stops EVERY rank at the same sweep (without it the other ranks ran on into the all-reduce with that rank's
@@ -809,7 +821,8 @@ struct EndHandOff {
 };
 __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayout lay, int H, double Lg, double M,
                                              int flags, double eps, double* __restrict__ trace,
-                                             int* __restrict__ ints, int it_row, EndHandOff& ho, bool handoff) {
+                                             int* __restrict__ ints, int it_row, EndHandOff& ho, bool handoff,
+                                             int* __restrict__ hw = nullptr) {
     // Inside a pass launch every dependent round trip to memory costs microseconds (the chip is streaming at full HBM
     // bandwidth around this workgroup), so everything the function needs is requested up front in ONE round -- the stop
     // flag, the scalars, the old CA/CB, the H x H arrays -- and the later stages work from registers and LDS.
@@ -898,8 +911,9 @@ __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayou
             if (trace) { trace[4 * it + 0] = d; trace[4 * it + 1] = sigma2; trace[4 * it + 2] = F; trace[4 * it + 3] = resid; }
             ints[I_ITERS] = it + 1;
             const bool rerr = stop_on_remote_error(st, lay, ints);
-            if (!(d > eps) || it + 1 >= ints[I_NITER] || rerr)            // src/vbmf.jl:193 (NaN d exits too)
-                __hip_atomic_store(ints + I_STOP, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool stop = !(d > eps) || it + 1 >= ints[I_NITER] || rerr;   // src/vbmf.jl:193 (NaN d exits too)
+            if (stop) __hip_atomic_store(ints + I_STOP, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            publish_loop_words(hw, ints, stop ? 1 : 0, it + 1);
         }
     }
     // (no device-scope fence here: the consumers are later kernels -- the launch boundary publishes these stores -- or this
@@ -910,15 +924,16 @@ __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayou
 
 __device__ __forceinline__ void ctrl_end_dev(double* __restrict__ st, StateLayout lay, int H, double Lg, double M,
                                              int flags, double eps, double* __restrict__ trace,
-                                             int* __restrict__ ints, int it_row = -1) {
+                                             int* __restrict__ ints, int* __restrict__ hw) {
     EndHandOff none{nullptr, 0, 0.0, 1.0, false};
-    ctrl_end_dev(st, lay, H, Lg, M, flags, eps, trace, ints, it_row, none, false);
+    ctrl_end_dev(st, lay, H, Lg, M, flags, eps, trace, ints, -1, none, false, hw);
 }
 
 __global__ __launch_bounds__(1024) void ctrl_end_kernel(double* __restrict__ st, StateLayout lay, int H, double Lg,
                                                        double M, int flags, double eps,
-                                                       double* __restrict__ trace, int* __restrict__ ints) {
-    ctrl_end_dev(st, lay, H, Lg, M, flags, eps, trace, ints);
+                                                       double* __restrict__ trace, int* __restrict__ ints,
+                                                       int* __restrict__ hw) {
+    ctrl_end_dev(st, lay, H, Lg, M, flags, eps, trace, ints, hw);
 }
 
 // SigmaA (into the shadow) right behind ctrl_end_dev in the same workgroup: the image holds B'B + L SigmaB, the diagonal takes
@@ -1033,6 +1048,7 @@ struct CtrlArgs {
     int mode;              // CTRL_* bits; 0: no control workgroups in this launch
     int it_row;            // sweep index (trace row) the CTRL_PREV_END part finalises
     int* sready; int sready_val;   // release flag for the Sigma table of part 0 (the pass's register epilogue waits on it)
+    int* loopw;            // the run loop's host-mapped {stop, iters, err} (publish_loop_words); nullptr outside a run
 };
 // Schedule inside vbmf_run (sweep j; B_{j-1} is the factor the sweep starts from):
 //   pass 1 of sweep j : [lambda_max(dB'dB) of sweep j-1, ctrl_end of sweep j-1]  then  SigmaA of sweep j
@@ -1045,7 +1061,8 @@ enum : int { CTRL_PREV_END = 1, CTRL_COV_A = 2, CTRL_COV_B = 4, CTRL_EIG_BOLD = 
 
 // d = ||B_old - B_new||_2 / ||B_old||_2 (src/util.jl:27-29) and the loop test (src/vbmf.jl:193) of sweep it_row
 __device__ __forceinline__ void ctrl_loop_dev(double* __restrict__ st, StateLayout lay, double eps,
-                                              double* __restrict__ trace, int* __restrict__ ints, int it_row) {
+                                              double* __restrict__ trace, int* __restrict__ ints, int it_row,
+                                              int* __restrict__ hw) {
     if (load_stop(ints)) return;
     if (threadIdx.x == 0) {
         double* scal = st + lay.scal();
@@ -1054,9 +1071,10 @@ __device__ __forceinline__ void ctrl_loop_dev(double* __restrict__ st, StateLayo
         if (trace) trace[4 * it_row + 0] = d;
         ints[I_ITERS] = it_row + 1;
         const bool rerr = stop_on_remote_error(st, lay, ints);
-        if (!(d > eps) || it_row + 1 >= ints[I_NITER] || rerr)              // NaN d exits too
-            __hip_atomic_store(ints + I_STOP, it_row + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // non-zero = stop; the
+        const bool stop = !(d > eps) || it_row + 1 >= ints[I_NITER] || rerr;   // NaN d exits too
+        if (stop) __hip_atomic_store(ints + I_STOP, it_row + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // non-zero = stop; the
                                                                             // value names the sweep (see ctrl_end_dev)
+        publish_loop_words(hw, ints, stop ? it_row + 1 : 0, it_row + 1);
     }
     // (see ctrl_end_dev: no device-scope fence; the stop flag itself is an agent-scope atomic)
     __syncthreads();
@@ -1131,7 +1149,7 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
     } else {
         if (a.mode & CTRL_PREV_END) {
             eig_dev<R>(a.st, a.lay, a.H, a.spectral, 0, a.ints, reinterpret_cast<float*>(lds), S_LAMD);
-            ctrl_loop_dev(a.st, a.lay, a.eps, a.trace, a.ints, a.it_row);
+            ctrl_loop_dev(a.st, a.lay, a.eps, a.trace, a.ints, a.it_row, a.loopw);
             if (threadIdx.x == 0) stamp[2] = wall_clock64() - t0;
         }
         if (a.mode & CTRL_EIG_BOLD)

@@ -795,7 +795,7 @@ __global__ __launch_bounds__(256) void sparse_t2_kernel(const double* __restrict
 __global__ __launch_bounds__(1024) void sparse_ctrl_end_kernel(double* __restrict__ st, StateLayout lay, int H,
                                                               double Lg, int flags, double eps,
                                                               double* __restrict__ trace, int* __restrict__ ints,
-                                                              const double* __restrict__ t2part = nullptr) {
+                                                              const double* __restrict__ t2part, int* __restrict__ hw) {
     __shared__ double red[16];
     if (load_stop(ints)) return;
     const int Hp = lay.Hp;
@@ -842,8 +842,9 @@ __global__ __launch_bounds__(1024) void sparse_ctrl_end_kernel(double* __restric
             if (trace) { trace[4 * it + 0] = d; trace[4 * it + 1] = scal[S_SIGMA2]; trace[4 * it + 2] = 0.0; trace[4 * it + 3] = scal[S_ZETA]; }
             ints[I_ITERS] = it + 1;
             const bool rerr = stop_on_remote_error(st, lay, ints);       // row-sharded: another rank's (or this rank's) device error
-            if (!(d > eps) || it + 1 >= ints[I_NITER] || rerr)
-                __hip_atomic_store(ints + I_STOP, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool stop = !(d > eps) || it + 1 >= ints[I_NITER] || rerr;
+            if (stop) __hip_atomic_store(ints + I_STOP, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            publish_loop_words(hw, ints, stop ? 1 : 0, it + 1);
         }
     }
 }

@@ -33,10 +33,12 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "common.hpp"
@@ -113,6 +115,10 @@ struct vbmf_ctx {
     StateLayout lay{};
     int* ints = nullptr;
     int* ints_host = nullptr;        // pinned
+    // the run loops' view of {stop, iters, err}: host-mapped words that the device's loop test stores into (ctrl_kernels.hpp,
+    // publish_loop_words) and the host reads directly -- no copy and no event on the compute stream
+    int* loopw = nullptr;            // host address
+    int* loopw_dev = nullptr;        // the same words as the device sees them
     double* scal_host = nullptr;     // pinned, 32 doubles
     unsigned char* mask = nullptr;
     int64_t H1 = 0;
@@ -122,7 +128,6 @@ struct vbmf_ctx {
     // side stream beside the passes, ordered by events
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
-    hipEvent_t ev_chk[2] = {nullptr, nullptr};   // deferred look at the device's stop flag (vbmf_run)
     bool use_side = false, side_pending = false;
     bool in_run = false;              // inside vbmf_run: the control chain rides in workgroups 0-1 of the pass launches
     int gslab_cap = 256;
@@ -189,7 +194,9 @@ struct vbmf_ctx {
     float* gslabs = nullptr;          // the product's split-K slabs [g_nsplit][P | Q]
     float* gPQ = nullptr;             // [P = G W | Q = G D], fragment-major (P in the layout of the pass-1 product)
     double* g_part = nullptr;         // per-chunk shares of [W'P | D'Q | sum A o P]
-    double* gsave = nullptr;          // [GB | GD | GX] kept across the B materialisation at the end of a run
+    double* gsave = nullptr;          // [GB | GD | GX] kept across the B materialisation after a run
+    bool B_pending = false;           // a Gram-form run has ended and B of its last sweep is not materialised yet (ensure_B)
+    long long b_materialised = 0;     // test surface (VBMF_PEEK_DIMS): how often ensure_B ran its pass
     double gram_build_ms = 0.0;       // device time of the last G build (HIP events)
 };
 
@@ -406,6 +413,8 @@ static size_t ctrl_lds_bytes_r(int R) {
 }
 static size_t ctrl_lds_bytes(int NH) { return NH <= 4 ? ctrl_lds_bytes_r(2 * NH) : 0; }
 static bool fused_ctrl(const vbmf_ctx* c) { return c->in_run && c->NH <= 4; }
+// the host-mapped loop counters, for the device's loop test: only a run loop looks at them
+static int* loop_words(const vbmf_ctx* c) { return c->in_run ? c->loopw_dev : nullptr; }
 
 // ctrl_mode != 0: workgroup 0 of the launch runs that part of the control chain (CtrlArgs)
 // epi (pass 2 only, un-split, NH <= 2): B, its operand tiles and the Gram partials are produced in the kernel's register
@@ -438,7 +447,7 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
     ca.S32 = pass == 0 ? c->SA32 : c->SB32;
     ca.Lg = (double)c->Lg; ca.M = (double)c->M; ca.eps = c->run_eps;
     ca.H = (int)c->H; ca.spectral = spectral_arg(c);
-    ca.end_flags = c->run_flags; ca.mode = ctrl_mode; ca.it_row = (int)c->ends_enqueued;
+    ca.end_flags = c->run_flags; ca.mode = ctrl_mode; ca.it_row = (int)c->ends_enqueued; ca.loopw = loop_words(c);
     ea.frag_out = frag_out ? 1 : 0;
     if (epi) {
         c->sready_seq = (c->sready_seq + 1) & 0x3fffffff;
@@ -855,17 +864,20 @@ static int launch_eig(vbmf_ctx* c, int do_d, int do_b) {
 
 static int launch_ctrl_end(vbmf_ctx* c, int flags, double eps, double* trace) {
     hipLaunchKernelGGL(ctrl_end_kernel, dim3(1), dim3(c->H > 128 ? 1024 : 256), 0, ctrl_stream(c), c->st, c->lay, (int)c->H, (double)c->Lg,
-                       (double)c->M, flags, eps, trace, c->ints);
+                       (double)c->M, flags, eps, trace, c->ints, loop_words(c));
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
 
 // need_Y = false: updateCA!/updateCB! read the factors and covariances only (src/vbmf.jl:129-146, src/vbmf_sparse.jl:284-300 --
 // the reference's signatures take no Y), so a context that was never given a matrix can run them
-static int ensure_ready(vbmf_ctx* c, bool need_Y = true) {
+// want_B = false: the caller (a run loop's frame) decides itself whether it needs B -- a Gram-form run that finds W valid does not
+static int ensure_B(vbmf_ctx* c);
+static int ensure_ready(vbmf_ctx* c, bool need_Y = true, bool want_B = true) {
     if (need_Y && !c->haveY) FAIL(c, VBMF_ERR_INVALID, "no Y: call vbmf_set_Y or vbmf_set_Y_synthetic first");
     if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "no state: call vbmf_set_state first");
     if (c->o.nranks > 1 && !c->comm_ready) FAIL(c, VBMF_ERR_COMM, "nranks > 1 but vbmf_comm_init was not called");
+    if (want_B) TRY(ensure_B(c));
     if (c->haveY && !c->trYY_reduced) {
         double* dst = c->st + c->lay.scal() + S_TRYY;
         HIPCHK(c, hipMemcpyAsync(dst, &c->trYY_local, sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1197,7 +1209,7 @@ static int launch_chain(vbmf_ctx* c, int mode, float* S32) {
     ca.S32 = S32;
     ca.Lg = (double)c->Lg; ca.M = (double)c->M; ca.eps = c->run_eps;
     ca.H = (int)c->H; ca.spectral = spectral_arg(c);
-    ca.end_flags = c->run_flags; ca.mode = mode; ca.it_row = (int)c->ends_enqueued;
+    ca.end_flags = c->run_flags; ca.mode = mode; ca.it_row = (int)c->ends_enqueued; ca.loopw = loop_words(c);
     const int H = (int)c->H;
     if (H <= 16) launch_chain_t<1>(c, ca);
     else if (H <= 32) launch_chain_t<2>(c, ca);
@@ -1337,7 +1349,7 @@ struct RunFrame {
     // the device, the state, the callers' defaults
     int open() {
         HIPCHK(c, hipSetDevice(c->o.device));
-        TRY(ensure_ready(c));
+        TRY(ensure_ready(c, true, false));                 // (B: only a run that starts by the streaming path needs it, see start_B)
         if (iters_done) *iters_done = 0;
         if (d_last) *d_last = eps + 1.0;                   // src/vbmf.jl:189, src/vbmf_sparse.jl:364
         return VBMF_OK;
@@ -1351,7 +1363,39 @@ struct RunFrame {
         int init[4] = {0, 0, 0, (int)niter};
         HIPCHK(c, hipMemcpyAsync(c->ints, init, sizeof init, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(c->st + c->lay.GX() + 1, 0, sizeof(double), c->stream));   // the ranks' summed error flags (packed message)
+        // the host's view of them, before the first launch: no flag of an earlier run is left (that run's stores are all complete,
+        // finish() drained the stream)
+        volatile int* w = c->loopw;
+        w[I_STOP] = 0; w[I_ITERS] = 0; w[I_ERR] = 0;
         return VBMF_OK;
+    }
+    // The look at the device's stop and error flags after sweep `it` (a multiple of `check`) has been enqueued.  The device's loop test
+    // stores {stop, iters, err} into host-mapped words (ctrl_kernels.hpp, publish_loop_words): nothing is queued on the compute
+    // stream, the device never waits for the host, and the host sees a value late but never early.  The host in turn waits here
+    // -- on memory, not on the stream -- until the device has finished sweep it - check, so it is never more than 2 * check sweeps
+    // ahead: sweeps enqueued past the stop are no-ops on the device (every kernel tests the stop flag), at most 2 * check of them.
+    // Returns true when the enqueueing ends.  Row-sharded: only the COLLECTIVE decision (the stop flag, raised at the same sweep on
+    // every rank -- a rank's error reaches the others with the packed Gram message) may end it, or the ranks' all-reduce counts diverge.
+    bool look(int64_t it, int64_t check) {
+        volatile const int* w = c->loopw;
+        auto t_last = std::chrono::steady_clock::now();
+        int seen = -1;
+        for (;;) {
+            const int iters = w[I_ITERS];                  // iters before stop: the device stores them in the other order
+            if (w[I_STOP] || (!sharded(c) && w[I_ERR])) return true;
+            if (iters >= it - check) return false;
+            const auto now = std::chrono::steady_clock::now();
+            if (iters != seen) { seen = iters; t_last = now; }
+            else if (now - t_last > std::chrono::milliseconds(200)) {
+                // no sweep finished for a long time: is the stream still working?  (asked this rarely, the query costs nothing that matters)
+                const hipError_t q = hipStreamQuery(c->stream);
+                (void)hipGetLastError();                   // "not ready" must not surface behind the next launch
+                if (q == hipSuccess) return w[I_STOP] || (!sharded(c) && w[I_ERR]);   // drained: the words are final
+                if (q != hipErrorNotReady) return true;                               // finish() reports the failure
+                t_last = now;
+            }
+            std::this_thread::yield();
+        }
     }
     // drains both streams, reads back the counters and the 32 scalars, settles c->bcur (B moved in the first `b_sweeps` executed sweeps,
     // from buffer `bstart`), the fp32 B, the outputs and the trace, maps the device's error flag to a status, clears the counters
@@ -1435,12 +1479,12 @@ int vbmf_destroy(vbmf_ctx* c) {
                     c->g_part, c->gsave};
     for (void* b : bufs) if (b) hipFree(b);
     if (c->ints_host) hipHostFree(c->ints_host);
+    if (c->loopw) hipHostFree(c->loopw);
     if (c->scal_host) hipHostFree(c->scal_host);
     if (c->stream) hipStreamDestroy(c->stream);
     if (c->side) hipStreamDestroy(c->side);
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_side) hipEventDestroy(c->ev_side);
-    for (auto& e : c->ev_chk) if (e) hipEventDestroy(e);
     for (auto& e : c->ev_y) if (e) hipEventDestroy(e);
     delete c;
     return VBMF_OK;
@@ -1663,12 +1707,16 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
         hipHostMalloc((void**)&c->scal_host, 32 * sizeof(double)) != hipSuccess) {
         c->err = "pinned alloc failed"; return bail(VBMF_ERR_HIP);
     }
+    // the run loops' host-mapped words: fine-grained (coherent), so the device's stores reach the host while the kernel still runs
+    if (hipHostMalloc((void**)&c->loopw, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&c->loopw_dev, c->loopw, 0) != hipSuccess) {
+        c->err = "host-mapped alloc failed"; return bail(VBMF_ERR_HIP);
+    }
+    memset(c->loopw, 0, 16 * sizeof(int));
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { c->err = "stream create failed"; return bail(VBMF_ERR_HIP); }
     if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_chk[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_chk[1], hipEventDisableTiming) != hipSuccess) { c->err = "side stream create failed"; return bail(VBMF_ERR_HIP); }
+        hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess) { c->err = "side stream create failed"; return bail(VBMF_ERR_HIP); }
     // large dynamic LDS (160 KiB per CU on gfx950) for the lambda_max kernel at 64 < H <= 128
     c->lds_limit = 160 * 1024 - 16384;         // leaves room for the kernels' static LDS (ctrl_end's tables: 8.4 KB)
     {
@@ -1832,6 +1880,7 @@ static int finish_Y(vbmf_ctx* c) {
     c->P_valid = false;
     c->Q_valid = false;
     c->G_valid = c->W_valid = false;                   // G = Y'Y is rebuilt by the next run that takes the Gram form
+    c->B_pending = false;                              // ... and B = Y W of the old Y is owed no longer
     c->tr_valid = false;
     if (c->diagvar) {                                  // ||Y_l||^2 of every row (:310), from the stored values
         DISPATCH_MODE(c->mode, {
@@ -1923,6 +1972,7 @@ int vbmf_set_Y_rows(vbmf_ctx* c, const void* src, int32_t dt, int32_t on_device,
         c->y_rows = 0;
         c->P_valid = c->Q_valid = c->tr_valid = false;
         c->G_valid = c->W_valid = false;
+        c->B_pending = false;
         HIPCHK(c, hipMemsetAsync(tr, 0, sizeof(double), c->stream));
     }
     if (on_device) {
@@ -2168,6 +2218,7 @@ int vbmf_set_state(vbmf_ctx* c, const double* AHat, int64_t ldA, const double* B
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->gA_valid = c->gB_valid = c->P_valid = c->tr_valid = false;
     c->W_valid = false;                                // B is no longer Y W: the next run starts by the streaming path
+    c->B_pending = false;                              // ... from the B just set
     c->B32_stale = false;
     c->haveState = true;
     return VBMF_OK;
@@ -2178,6 +2229,7 @@ int vbmf_get_state(vbmf_ctx* c, double* AHat, int64_t ldA, double* BHat, int64_t
     if (!c) return VBMF_ERR_INVALID;
     if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "no state");
     HIPCHK(c, hipSetDevice(c->o.device));
+    if (BHat) TRY(ensure_B(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (AHat) { if (ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "ldA < M"); TRY(download_factor(c, c->A32, c->M, AHat, ldA)); }
     if (BHat) { if (ldB < c->L) FAIL(c, VBMF_ERR_INVALID, "ldB < L"); TRY(download_factor(c, c->B32[c->bcur], c->L, BHat, ldB)); }
@@ -2280,6 +2332,7 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     const bool gram = gram_eligible(c);
     if (gram) TRY(gram_prepare(c));
     else c->W_valid = false;
+    if (!(gram && c->W_valid)) TRY(ensure_B(c));           // the first sweep streams: it starts from B
     TRY(run.arm());
     // ||B_old||_2 of the first comparison (src/vbmf.jl:187-188: old = params.BHat): in the fused schedule
     // every sweep's pass-2 launch computes it; otherwise once here, then rotated by ctrl_end
@@ -2299,14 +2352,12 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     c->run_flags = flags;
     c->run_eps = eps;
     c->run_trace = run.trace_dev;
-    // The host runs ahead of the device; every `check` sweeps it queues a copy of the device's stop/error flags and
-    // looks at the PREVIOUS copy (long complete), so the device never waits for the host.  Sweeps enqueued past the stop
-    // are no-ops on the device (every kernel begins with the stop test): at most 2*check of them.
+    // The host runs ahead of the device; every `check` sweeps it looks at the device's stop/error flags in host-mapped words
+    // (RunFrame::look: nothing enters the stream, the device never waits for the host).  Sweeps enqueued past the stop are
+    // no-ops on the device (every kernel tests the stop flag): at most 2*check of them.
     const int64_t check = 8;
     int64_t it = 0;
     bool stopped = false;
-    int slot = 0;
-    bool pending[2] = {false, false};
     while (rc == VBMF_OK && it < niter && !stopped) {
         if (gram && c->W_valid) {
             rc = gram_sweep(c);              // carries the closing control step of the previous sweep
@@ -2339,21 +2390,7 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
                 if (rc == VBMF_OK && c->use_side) rc = side_end(c);
             }
         }
-        if (rc == VBMF_OK && !last && it % check == 0) {
-            if (pending[slot ^ 1]) {
-                if (hipEventSynchronize(c->ev_chk[slot ^ 1]) != hipSuccess) { c->err = "run loop sync failed"; rc = VBMF_ERR_HIP; break; }
-                const int* f = c->ints_host + 8 + 4 * (slot ^ 1);
-                // row-sharded: only the COLLECTIVE decision (the stop flag, raised at the same sweep on every rank -- a rank's
-                // error reaches the others with the packed Gram message) may end the enqueueing, or the ranks' all-reduce counts diverge
-                if (f[I_STOP] || (!sharded(c) && f[I_ERR])) stopped = true;
-                pending[slot ^ 1] = false;
-            }
-            hipError_t e = hipMemcpyAsync(c->ints_host + 8 + 4 * slot, c->ints, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipEventRecord(c->ev_chk[slot], c->stream);
-            if (e != hipSuccess) { c->err = std::string("run loop checkpoint: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; break; }
-            pending[slot] = true;
-            slot ^= 1;
-        }
+        if (rc == VBMF_OK && !last && it % check == 0) stopped = run.look(it, check);
     }
     c->tail_pending = false;
     c->run_trace = nullptr;
@@ -2366,22 +2403,9 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     }
     c->tr_valid = true;
     if (gram && rc != VBMF_OK) c->W_valid = false;
-    if (gram && rc == VBMF_OK && gram_done > 0) {
-        // B of the last executed sweep, eagerly, by the streaming pass 2 with that sweep's A and SigmaB / sigma2 (the table in place):
-        // B, its operand tiles and the fp32 copy as a streaming run leaves them.  The state's [B'B | dB'dB | tr(B'YA)] stay the Gram
-        // form's, so a run that continues from here computes what one longer run computes.
-        const size_t nsave = 2 * (size_t)c->Hp * c->Hp + 8;
-        hipError_t e = hipMemcpyAsync(c->gsave, c->st + c->lay.GB(), nsave * 8, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) rc = do_update_B(c, true);
-        else { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
-        if (rc == VBMF_OK) {
-            e = hipMemcpyAsync(c->st + c->lay.GB(), c->gsave, nsave * 8, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
-        }
-        if (rc == VBMF_OK) rc = check_device_err(c);
-        if (rc != VBMF_OK) c->W_valid = false;
-    }
+    // B of the last executed sweep is owed, not made: the first reader pays the pass (ensure_B), a Gram-form run that continues
+    // from here never does
+    if (gram && rc == VBMF_OK && gram_done > 0) c->B_pending = true;
     return rc;
 }
 
@@ -2390,6 +2414,7 @@ int vbmf_get_YHat(vbmf_ctx* c, double* YHat, int64_t ld) {
     if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "no state");
     if (!YHat || ld < c->L) FAIL(c, VBMF_ERR_INVALID, "vbmf_get_YHat: bad arguments");
     HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));
     int64_t mc = std::max<int64_t>(1, (int64_t)(256ll << 20) / (c->L * 8));
     mc = std::min(mc, c->M);
     double* tmp = nullptr;
@@ -2438,6 +2463,7 @@ int vbmf_comm_init(vbmf_ctx* c, const void* id128) {
     if (!c || !id128) return VBMF_ERR_INVALID;
     if (c->comm_ready) FAIL(c, VBMF_ERR_INVALID, "communicator already initialised");
     HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));
     ncclUniqueId id;
     memcpy(&id, id128, sizeof id);
     NCCLCHK(c, ncclCommInitRank(&c->comm, c->o.nranks, id, c->o.rank));
@@ -2450,6 +2476,8 @@ int vbmf_comm_init(vbmf_ctx* c, const void* id128) {
 int vbmf_comm_set_transport(vbmf_ctx* c, vbmf_allreduce_fn fn, void* user) {
     if (!c || !fn) return VBMF_ERR_INVALID;
     if (c->comm_ready) FAIL(c, VBMF_ERR_INVALID, "communicator already initialised");
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));                 // (a row-sharded context leaves the Gram form)
     c->ar_hook = fn;
     c->ar_user = user;
     c->comm_ready = true;
@@ -2505,14 +2533,16 @@ int vbmf_pass_bytes(vbmf_ctx* c, int pass, double* bytes) {
 int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_t word_offset) {
     if (!c || !out || nwords < 0 || word_offset < 0) return VBMF_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->o.device));
+    if (what != VBMF_PEEK_DIMS) TRY(ensure_B(c));          // every buffer is shown as an eager run end left it; the dimensions never pay
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (what == VBMF_PEEK_DIMS) {
-        const int v[28] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
+        const int v[30] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
                            c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
                            gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
                            c->frag_last[0] ? 1 : 0, c->frag_last[1] ? 1 : 0, c->epi_last ? 1 : 0, use_lds8(c) ? 1 : 0, c->xcd_map ? 1 : 0,
-                           c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0, (int)std::lround(c->set_y_ms * 1000.0)};
-        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(28, nwords));
+                           c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0, (int)std::lround(c->set_y_ms * 1000.0),
+                           c->B_pending ? 1 : 0, (int)std::min<long long>(c->b_materialised, 0x7fffffff)};
+        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(30, nwords));
         return VBMF_OK;
     }
     if (what == VBMF_PEEK_CHAIN) {
@@ -2572,6 +2602,7 @@ int vbmf_debug_time_pass(vbmf_ctx* c, int pass, int iters, double* ms) {
 int vbmf_debug_lambda_max(vbmf_ctx* c, const double* G, double* lam, double* kernel_us) {
     if (!c || !G || !lam) return VBMF_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));
     const int H = (int)c->H, Hp = c->Hp;
     std::vector<double> g((size_t)Hp * Hp, 0.0);
     for (int j = 0; j < H; ++j)
@@ -2598,6 +2629,8 @@ int vbmf_debug_lambda_max(vbmf_ctx* c, const double* G, double* lam, double* ker
 
 int vbmf_debug_set(vbmf_ctx* c, int what, int64_t value) {
     if (!c) return VBMF_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));                 // a B that is owed is made as the run left things, before a knob moves
     switch (what) {
         case VBMF_DEBUG_EXACT_LAMBDA:
             c->exact_lambda = value != 0;
@@ -2834,6 +2867,32 @@ static int do_sparse_update_B(vbmf_ctx* c, bool keep_sigma = false) {
     return VBMF_OK;
 }
 
+// B after a Gram-form run, on demand.  The run's sweeps moved W, not B; what is owed is B of the last executed sweep, by the
+// streaming pass 2 with that sweep's A and SigmaB / sigma2 (sparse model: sigmaHat SigmaB) table, which is still in place: B, its
+// operand tiles and the fp32 copy as a streaming run leaves them.  The state's [B'B | dB'dB | tr(B'YA)] stay the Gram form's, so a
+// run that continues from here computes what one longer run computes.  Every entry point that reads B, its tiles or anything
+// derived from them comes through here first (ensure_ready does it for most); vbmf_set_state and the vbmf_set_Y* calls drop the
+// debt with W; a Gram-form run that finds W valid, and vbmf_destroy, never pay it ("Run boundaries").
+static int ensure_B(vbmf_ctx* c) {
+    if (!c->B_pending) return VBMF_OK;
+    c->B_pending = false;
+    ++c->b_materialised;
+    const size_t nsave = 2 * (size_t)c->Hp * c->Hp + 8;
+    int rc = VBMF_OK;
+    hipError_t e = hipMemcpyAsync(c->gsave, c->st + c->lay.GB(), nsave * 8, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) rc = c->sparse ? do_sparse_update_B(c, true) : do_update_B(c, true);
+    else { c->err = std::string("B after a Gram-form run: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+    if (rc == VBMF_OK) {
+        e = hipMemcpyAsync(c->st + c->lay.GB(), c->gsave, nsave * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { c->err = std::string("B after a Gram-form run: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
+    }
+    if (rc == VBMF_OK) rc = check_device_err(c);
+    if (rc != VBMF_OK) c->W_valid = false;
+    if (c->sparse) c->Q_valid = false;
+    return rc;
+}
+
 // updateSigma!, diag_var = true (:308-315): every row's Gamma posterior; S_SIGMA2 := mean(sigmaVecHat)
 static int do_hetero_sigma(vbmf_ctx* c) {
     TRY(ensure_gram_A(c));
@@ -2889,7 +2948,7 @@ static int launch_sparse_t2(vbmf_ctx* c) {
 }
 static int launch_sparse_ctrl_end(vbmf_ctx* c, int flags, double eps, double* trace, bool t2_ahead = false) {
     hipLaunchKernelGGL(sparse_ctrl_end_kernel, dim3(1), dim3(c->H > 64 ? 1024 : 256), 0, ctrl_stream(c), c->st, c->lay, (int)c->H, (double)c->Lg, flags, eps, trace, c->ints,
-                       t2_ahead ? (const double*)c->t2part : (const double*)nullptr);
+                       t2_ahead ? (const double*)c->t2part : (const double*)nullptr, loop_words(c));
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
@@ -3020,6 +3079,7 @@ int vbmf_sparse_set_state(vbmf_ctx* c, const double* ATVecHat, const double* dia
     c->B32_stale = false;
     c->haveState = true;
     c->W_valid = false;                                // B is no longer Y W: the next run starts by the streaming path
+    c->B_pending = false;                              // ... from the B just set
     return VBMF_OK;
 }
 
@@ -3029,6 +3089,7 @@ int vbmf_sparse_get_state(vbmf_ctx* c, double* ATVecHat, double* diagSigmaATVec,
     if (!c) return VBMF_ERR_INVALID;
     if (!c->sparse || !c->haveState) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
     HIPCHK(c, hipSetDevice(c->o.device));
+    if (BHat) TRY(ensure_B(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (ATVecHat) TRY(download_vec(c, c->A32, ATVecHat));
     if (diagSigmaATVec) TRY(download_vec(c, c->dS32, diagSigmaATVec));
@@ -3117,6 +3178,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
     const bool gram = gram_eligible(c);
     if (gram) TRY(gram_prepare(c));
     else c->W_valid = false;
+    if (!(gram && c->W_valid)) TRY(ensure_B(c));           // the first sweep streams: it starts from B
     TRY(run.arm());
     int rc = ensure_gram_B(c);
     if (rc == VBMF_OK) rc = launch_eig(c, 0, 1);
@@ -3126,6 +3188,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
     const int flags = (est_cb ? 2 : 0) | (c->diagvar ? 0 : 4 | 16) | 8;
     const int bstart = c->bcur, wstart = c->wcur;
     int64_t stream_sweeps = 0;                             // sweeps enqueued by the streaming path (Gram form: at most the first)
+    const int64_t check = 8;                               // sweeps between two looks at the stop flag (RunFrame::look)
     int64_t it = 0;
     bool stopped = false;
     c->in_run = true;
@@ -3162,13 +3225,10 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         if (rc == VBMF_OK) rc = launch_sparse_ctrl_end(c, flags, eps, run.trace_dev, t2_ahead);
         if (rc == VBMF_OK && c->use_side) rc = side_end(c);
         ++it;
-        if (rc == VBMF_OK && (it % 8 == 0 || it == niter)) {
+        if (rc == VBMF_OK && (it % check == 0 || it == niter)) {
             rc = side_join(c);
             if (rc != VBMF_OK) break;
-            hipError_t e = hipMemcpyAsync(c->ints_host, c->ints, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { c->err = std::string("sparse run sync: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; break; }
-            if (c->ints_host[I_STOP] || (!sharded(c) && c->ints_host[I_ERR])) stopped = true;   // (see vbmf_run)
+            if (it < niter) stopped = run.look(it, check);      // (see vbmf_run; the run's end drains the stream in finish())
         }
     }
     // every streaming sweep moves B; in the Gram form only the streaming sweep (the first, if any) does, and every sweep moves W
@@ -3181,23 +3241,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         gram_done = run.done - std::min<int64_t>(run.done, stream_sweeps);
     }
     if (gram && rc != VBMF_OK) c->W_valid = false;
-    if (gram && rc == VBMF_OK && gram_done > 0) {
-        // B of the last executed sweep, eagerly, by the streaming pass 2 with that sweep's A and sigmaHat SigmaB table (in place): B, its
-        // operand tiles and the fp32 copy as a streaming run leaves them.  The state's [B'B | dB'dB | tr(B'YA)] stay the Gram form's, so
-        // a run that continues from here computes what one longer run computes.
-        const size_t nsave = 2 * (size_t)c->Hp * c->Hp + 8;
-        hipError_t e = hipMemcpyAsync(c->gsave, c->st + c->lay.GB(), nsave * 8, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) rc = do_sparse_update_B(c, true);
-        else { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
-        if (rc == VBMF_OK) {
-            e = hipMemcpyAsync(c->st + c->lay.GB(), c->gsave, nsave * 8, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { c->err = std::string("run end: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
-        }
-        if (rc == VBMF_OK) rc = check_device_err(c);
-        if (rc != VBMF_OK) c->W_valid = false;
-        c->Q_valid = false;
-    }
+    if (gram && rc == VBMF_OK && gram_done > 0) c->B_pending = true;   // B of the last executed sweep: owed (ensure_B, see vbmf_run)
     return rc;
 }
 
@@ -3212,6 +3256,7 @@ int vbmf_sparse_set_full_cov(vbmf_ctx* c, int on) {
     if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "not a sparse context");
     if (on && c->H > 256) FAIL(c, VBMF_ERR_UNSUPPORTED, "full_cov is built for H <= 256");
     HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));
     if (on && !c->fpart) {
         // two columns per round and workgroup (one for H > 64); H > 128: one 1024-thread workgroup per CU with its own workspace
         c->fblocks = (int)std::max<int64_t>(1, std::min<int64_t>(c->H > 64 ? c->M : (c->M + 1) / 2, c->H > 128 ? NUM_CU : 1024));
@@ -3236,6 +3281,8 @@ int vbmf_set_gram_form(vbmf_ctx* c, int mode) {
     if (!c) return VBMF_ERR_INVALID;
     if (mode != VBMF_GRAM_FORM_DEFAULT && mode != VBMF_GRAM_FORM_OFF && mode != VBMF_GRAM_FORM_ON)
         FAIL(c, VBMF_ERR_INVALID, "vbmf_set_gram_form: unknown mode %d", mode);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    TRY(ensure_B(c));
     c->gram_form = mode;
     c->W_valid = false;
     return VBMF_OK;
