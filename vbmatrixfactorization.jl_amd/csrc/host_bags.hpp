@@ -65,7 +65,7 @@ int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_
     if (AHat && ldA < c->M) FAIL(c, VBMF_ERR_INVALID, "%s: ldA < M", fn);
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c));
-    c->W_valid = false;
+    c->cache.W_dropped();
     TRY(ensure_gram_B(c));
     const int H = (int)c->H;
     const int64_t nb = nbags, h2 = (int64_t)H * H;
@@ -83,7 +83,7 @@ int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_
     // P = Y'B of every bag: one pass 1 with the frozen B (no control chain, no A update: the state stays as it is)
     c->P_frag = fused_gram(c) || frag_post(c);
     TRY(launch_stream(c, 0, 0, false, nullptr, c->P_frag));
-    c->P_valid = false;
+    c->cache.P_overwritten();
     if (sharded(c) || c->d1.nsplit > 1) {
         const long long n = (long long)c->Hp * c->d1.XT * 32;
         hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(n / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, n,
@@ -171,7 +171,7 @@ int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_
     const long long np = (long long)c->Hp * c->d1.XT * 32;
     hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(np / 4, 256, 2048)), dim3(256), 0, c->stream, c->P, c->d1.nsplit, np, c->Pred, np, stop,
                        SideCopy{});
-    c->P_valid = false;
+    c->cache.P_overwritten();
     const long long ldP = (long long)c->d1.XT * 32;
     TRY(bags_launch_gram(c, nb, c->Pred, 0, d_off, nullptr, d + o_yy));
     hipLaunchKernelGGL(sbatch_g_kernel, dim3(cdiv(h2, 256)), dim3(256), 0, c->stream, c->st, c->lay, H, (double)c->Lg, d + o_g, d + o_gd,
@@ -293,7 +293,7 @@ int vbmf_bag_least_squares(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, c
             if (!std::isfinite(v)) FAIL(c, VBMF_ERR_INVALID, "%s: BHat[%lld, %lld] is not finite", fn, (long long)l, (long long)h);
             Bt[(size_t)(l * H + h)] = v;
         }
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the basis is an argument)
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the basis is an argument)
     HIPCHK(c, hipSetDevice(c->o.device));
     const int64_t nchunk = cdiv(L, LS_ROWS), h2 = H * H;
     // c->bags: [col_off nb + 1 | chunk_off nb + 1 | r2 nb | bad-pivot flag | partials ns | B L H (row-major) | Gram partials nchunk H^2
@@ -455,7 +455,7 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
         if (local) idx[(size_t)(nb + 1 + nf + nf + 1 + f)] = M0[f];
     }
     for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
     // the staging vectors outlive every copy: an error between the first asynchronous copy and the synchronise drains the stream below
     std::vector<double> in, out, sg;
     auto run = [&]() -> int {
@@ -675,7 +675,7 @@ static int fit_basic_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int64
     }
     for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
     for (int64_t k = nk; form && k < nb; ++k) kbag[k] = 0;
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
     // the staging vectors outlive every copy: an error between the first asynchronous copy and the synchronise drains the stream below
     std::vector<double> in, out;
     auto run = [&]() -> int {
@@ -779,7 +779,7 @@ int vbmf_bags_row_gram(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, doubl
     BagDims bd;
     TRY(bags_check(c, fn, nbags, col_off, bd));
     if (!K) FAIL(c, VBMF_ERR_INVALID, "%s: null K", fn);
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);
     HIPCHK(c, hipSetDevice(c->o.device));
     const int64_t nb = nbags, L = c->L, ny = (L * c->M + 1) / 2;
     std::vector<long long> idx((size_t)(2 * nb + 1));               // col_off | kbag = 0 .. nb - 1

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "ctx_cache.hpp"
 #include "ctrl_kernels.hpp"
 #include "post_kernels.hpp"
 #include "rng.hpp"
@@ -74,7 +75,6 @@ struct vbmf_ctx {
     uint4 *FA_alloc = nullptr, *FB_alloc = nullptr;
     uint4* SBf = nullptr;            // SigmaB table pre-split into bf16 hi / lo MFMA fragments (H >= 128, bf16 factor modes)
     uint4* FD = nullptr;             // delta tiles of B (H >= 128, bf16 factor modes): old - new as bf16 hi + lo operand fragments
-    bool fd_valid = false;           // ... written by the post kernel of the B update just enqueued
     size_t nY1 = 0, nY2 = 0, nFA = 0, nFB = 0;
     float *P = nullptr, *Q = nullptr, *Pred = nullptr;
     float *A32 = nullptr, *B32[2] = {nullptr, nullptr};
@@ -91,7 +91,7 @@ struct vbmf_ctx {
     bool sparse = false;
     float *dS32 = nullptr, *CA32 = nullptr, *beta32 = nullptr;   // diagSigmaATVec, CA, beta as [Mp][Hp]
     // heteroscedastic rows (variant SPARSE_DIAGVAR): sigmaVecHat / zetaVec, ||Y_l||^2, G = A'A + SigmaA, scaled-B tiles
-    bool diagvar = false, Q_valid = false, have_noise = false, noise_mean_reduced = false;
+    bool diagvar = false;
     double *sigv = nullptr, *zetav = nullptr, *yrow = nullptr, *hpart = nullptr, *vsq = nullptr, *hmean = nullptr;
     float *sig32 = nullptr, *G32 = nullptr;
     uint4 *FBs_alloc = nullptr, *FBs = nullptr;
@@ -146,7 +146,6 @@ struct vbmf_ctx {
     bool P_frag = false;              // the Y'B product in c->P / c->Pred is fragment-major (stream_gemm.hpp, frag_out)
     bool frag_last[2] = {false, false};   // test surface (VBMF_PEEK_DIMS): the last launch of pass 1 / pass 2 wrote fragment-major output
     bool epi_last = false;            // ... the last launch of pass 2 ran the register epilogue (no product stored)
-    bool B32_stale = false;           // the register epilogue skipped the fp32 store of B (inside vbmf_run): tiles are current
     int sready_seq = 0;               // sequence number of the Sigma-table release flag (register epilogue)
     bool epi_balance = false;         // x groups of the register-epilogue pass dealt three per workgroup over the whole chip instead
                                       // of four per workgroup: measured SLOWER (0.372 vs 0.366 ms at 100k rows), kept behind
@@ -159,14 +158,11 @@ struct vbmf_ctx {
     int run_flags = 0;
     double run_eps = 0.0;
     double* run_trace = nullptr;
-    bool haveY = false, haveState = false;
+    CtxCache cache;                   // which derived device data are current, and the only way to change that (ctx_cache.hpp)
     hipEvent_t ev_y[2] = {nullptr, nullptr};   // around the device work of the last vbmf_set_Y_rows call (created by the first one)
     double set_y_ms = 0.0;            // ... and what they measured: staged copies, tiling kernels, ||Y||^2 (VBMF_PEEK_DIMS word 27, us)
     int64_t y_rows = 0;               // vbmf_set_Y_rows: rows of the Y being built that have arrived (L once Y is complete)
-    bool gA_valid = false, gB_valid = false, P_valid = false;
-    bool tr_valid = false;            // st[GX] = tr(B'YA) of the current (AHat, BHat)
     double trYY_local = 0.0;
-    bool trYY_reduced = true;
     int prof = 0;                     // 0 off; k: HIP events around every k-th launch of each pass
     bool prof_skip = true;
     long long prof_seen[2] = {0, 0};
@@ -186,16 +182,13 @@ struct vbmf_ctx {
     int GT = 0;                       // row tiles of G (multiple of 16); KT = 2 GT k-steps
     int g_nsplit = 1, g_sps = 0, g_nrg = 0, g_nchunk = 0, g_rpc = 0;
     float* Gt = nullptr;              // G = Y'Y as fp32 MFMA operand fragments [GT][2 GT][64][8]
-    bool G_valid = false;             // G is of the current Y
     float* W32g[2] = {nullptr, nullptr};   // W = A SigmaB / sigma2, fp32 [32 GT][Hp], double-buffered like B32
     int wcur = 0;
-    bool W_valid = false;             // B = Y W32g[wcur] and gPQ holds [G W | G D] of that W: the next sweep may take the Gram form
     uint4* Wt = nullptr;              // operand planes of the product: W in 3 bf16 parts, D in 2
     float* gslabs = nullptr;          // the product's split-K slabs [g_nsplit][P | Q]
     float* gPQ = nullptr;             // [P = G W | Q = G D], fragment-major (P in the layout of the pass-1 product)
     double* g_part = nullptr;         // per-chunk shares of [W'P | D'Q | sum A o P]
     double* gsave = nullptr;          // [GB | GD | GX] kept across the B materialisation after a run
-    bool B_pending = false;           // a Gram-form run has ended and B of its last sweep is not materialised yet (ensure_B)
     long long b_materialised = 0;     // test surface (VBMF_PEEK_DIMS): how often ensure_B ran its pass
     double gram_build_ms = 0.0;       // device time of the last G build (HIP events)
 };
@@ -458,7 +451,7 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
         ea.trpart = c->trpart;
         ea.stamp = reinterpret_cast<unsigned long long*>(c->ints + 16);
         c->ntr = 4 * bps;
-        if (c->in_run) c->B32_stale = true;
+        if (c->in_run) c->cache.B32_store_skipped();
         if (ctrl_mode) { ca.sready = c->ints + I_SREADY; ca.sready_val = c->sready_seq; }
         if (epi_slabs) *epi_slabs = bps;
         GSLAB_CHECK(c, bps, 2 * (c->NH * (c->NH + 1) / 2) * 1024);
@@ -558,8 +551,8 @@ static int launch_post(vbmf_ctx* c, int which, const float* In, int nslab) {
     //  delta tiles of the un-scaled product, and the fp32 store stays)
     uint4* fd = (which == 1 && c->NH >= 4 && !c->diagvar) ? c->FD : nullptr;
     const int store_fac = (fd != nullptr && c->in_run) ? 0 : 1;
-    if (which == 1) c->fd_valid = fd != nullptr;
-    if (!store_fac) c->B32_stale = true;
+    if (which == 1) c->cache.delta_tiles_written(fd != nullptr);
+    if (!store_fac) c->cache.B32_store_skipped();
     DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
         hipLaunchKernelGGL((post_kernel<MODEc, NHc>), dim3(grid), dim3(256), 0, c->stream, In, ld, nslab, slabStride, S,
                            Fac, Ft, mk, hstart, d.XT, c->ints + I_STOP, trp, fd, store_fac);
@@ -592,7 +585,7 @@ static int launch_post_frag(vbmf_ctx* c, int which = 1, const float* In = nullpt
         const int grid = (cdiv(d.XT, nxt) + 3) / 4;
         double* trp = (!c->diagvar && 4 * grid <= c->trpart_cap) ? c->trpart : nullptr;
         c->ntr = trp ? 4 * grid : 0;
-        c->fd_valid = false;
+        c->cache.delta_tiles_written(false);
         if (c->NH == 4) hipLaunchKernelGGL((post_frag_kernel<MODE_F32, 4>), dim3(grid), dim3(256), 0, c->stream, (const float4*)In, S, Fac, Ft, (const unsigned char*)nullptr, 0, d.XT, stop, trp, (uint4*)nullptr, 1, (const uint4*)nullptr);
         else hipLaunchKernelGGL((post_frag_kernel<MODE_F32, 8>), dim3(grid), dim3(256), 0, c->stream, (const float4*)In, S, Fac, Ft, (const unsigned char*)nullptr, 0, d.XT, stop, trp, (uint4*)nullptr, 1, (const uint4*)nullptr);
         HIPCHK(c, hipGetLastError());
@@ -608,8 +601,8 @@ static int launch_post_frag(vbmf_ctx* c, int which = 1, const float* In = nullpt
     if (which == 1) c->ntr = trp ? 4 * grid : 0;
     uint4* fd = which == 1 ? c->FD : nullptr;
     const int store_fac = (fd != nullptr && c->in_run) ? 0 : 1;
-    if (which == 1) c->fd_valid = fd != nullptr;
-    if (!store_fac) c->B32_stale = true;
+    if (which == 1) c->cache.delta_tiles_written(fd != nullptr);
+    if (!store_fac) c->cache.B32_store_skipped();
     const unsigned char* mk = (which == 0 && c->has_mask) ? c->mask : nullptr;
     const int hstart = (int)(c->H - c->H1);
     const int nthr = c->NH * 2 * c->NH * 64;
@@ -666,7 +659,7 @@ static int launch_post_gram(vbmf_ctx* c, int which, const float* In) {
     double* trp = (which == 1 && !c->diagvar) ? c->trpart : nullptr;
     // inside the run loops the fp32 copy of B is not written per sweep: the operand tiles carry the factor (rebuilt once at the end)
     const int store_fac = (which == 1 && c->in_run) ? 0 : 1;
-    if (!store_fac) c->B32_stale = true;
+    if (!store_fac) c->cache.B32_store_skipped();
     DISPATCH_MODE(c->mode, {
         if (which == 0) {
             if (c->NH == 1) hipLaunchKernelGGL((post_gram2_kernel<MODEc, 1, false>), dim3(grid), dim3(256), 0, c->stream, In, S, Fac, Ft, mk, hstart, d.XT, c->gslab, stop, trp, store_fac);
@@ -743,7 +736,7 @@ static int launch_gram(vbmf_ctx* c, int which, const float* cur, const float* pr
         const uint4* Ft = which == 0 ? c->FA : c->FB;
         // delta-Gram: a plain tile Gram of the delta tiles the post kernel left (two parts: hi + lo) -- or, without them
         // (f32-free callers that bring their own previous fp32 factor), from `prev` with row gathers
-        const bool from_fd = which == 1 && prev != nullptr && c->fd_valid && c->FD != nullptr;
+        const bool from_fd = which == 1 && prev != nullptr && c->cache.delta_tiles() && c->FD != nullptr;
         pair_slabs = from_fd || prev == nullptr;
 #define GRAM_TILES(NHc_, NPc_)                                                                                               \
     do {                                                                                                                         \
@@ -874,34 +867,34 @@ static int launch_ctrl_end(vbmf_ctx* c, int flags, double eps, double* trace) {
 // want_B = false: the caller (a run loop's frame) decides itself whether it needs B -- a Gram-form run that finds W valid does not
 static int ensure_B(vbmf_ctx* c);
 static int ensure_ready(vbmf_ctx* c, bool need_Y = true, bool want_B = true) {
-    if (need_Y && !c->haveY) FAIL(c, VBMF_ERR_INVALID, "no Y: call vbmf_set_Y or vbmf_set_Y_synthetic first");
-    if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "no state: call vbmf_set_state first");
+    if (need_Y && !c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "no Y: call vbmf_set_Y or vbmf_set_Y_synthetic first");
+    if (!c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no state: call vbmf_set_state first");
     if (c->o.nranks > 1 && !c->comm_ready) FAIL(c, VBMF_ERR_COMM, "nranks > 1 but vbmf_comm_init was not called");
     if (want_B) TRY(ensure_B(c));
-    if (c->haveY && !c->trYY_reduced) {
+    if (c->cache.have_Y() && !c->cache.trYY_reduced()) {
         double* dst = c->st + c->lay.scal() + S_TRYY;
         HIPCHK(c, hipMemcpyAsync(dst, &c->trYY_local, sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         TRY(allreduce_sum(c, dst, 1, true));
-        c->trYY_reduced = true;
+        c->cache.trYY_summed();
     }
-    if (c->diagvar && c->have_noise && !c->noise_mean_reduced) {
+    if (c->diagvar && c->cache.have_noise() && !c->cache.noise_mean_reduced()) {
         if (sharded(c)) TRY(allreduce_sum(c, c->st + c->lay.scal() + S_SIGMA2, 1, true));   // shares of mean(sigmaVecHat)
-        c->noise_mean_reduced = true;
+        c->cache.noise_mean_summed();
     }
     return VBMF_OK;
 }
 
 static int ensure_gram_A(vbmf_ctx* c) {
-    if (c->gA_valid) return VBMF_OK;
+    if (c->cache.gram_A()) return VBMF_OK;
     TRY(launch_gram(c, 0, c->A32, nullptr, false));
-    c->gA_valid = true;
+    c->cache.gram_A_made();
     return VBMF_OK;
 }
 static int ensure_gram_B(vbmf_ctx* c) {
-    if (c->gB_valid) return VBMF_OK;
+    if (c->cache.gram_B()) return VBMF_OK;
     TRY(launch_gram(c, 1, c->B32[c->bcur], nullptr, false));
-    c->gB_valid = true;
+    c->cache.gram_B_made();
     return VBMF_OK;
 }
 
@@ -912,7 +905,7 @@ static int ensure_gram_B(vbmf_ctx* c) {
 // reuse_P: B has not changed since Y'B was last formed (fixed-basis inference, vbls!): skip the pass over Y
 static int do_update_A(vbmf_ctx* c, bool reuse_P = false) {
     TRY(ensure_gram_B(c));
-    const bool have_P = reuse_P && c->P_valid;
+    const bool have_P = reuse_P && c->cache.P();
     bool commit_pending = false;
     if (have_P) {
         TRY(launch_ctrl_cov(c, 0));
@@ -967,9 +960,7 @@ static int do_update_A(vbmf_ctx* c, bool reuse_P = false) {
         else TRY(launch_post(c, 0, c->P, 1));
     }
     if (!fused_gram(c)) TRY(launch_gram(c, 0, c->A32, nullptr, true));
-    c->gA_valid = true;
-    c->P_valid = true;
-    c->tr_valid = false;
+    c->cache.A_moved_basic();
     return VBMF_OK;
 }
 
@@ -999,9 +990,7 @@ static int do_update_B(vbmf_ctx* c, bool keep_sigma = false) {
         }
         TRY(launch_pair_reduce(c, 1, nslab, c->ntr));
         c->bcur ^= 1;
-        c->gB_valid = true;
-        c->P_valid = false;
-        c->tr_valid = true;
+        c->cache.B_moved_basic();
         return VBMF_OK;
     }
     // H >= 128, un-split pass: the product travels fragment-major (16-byte accesses on both sides)
@@ -1029,9 +1018,7 @@ static int do_update_B(vbmf_ctx* c, bool keep_sigma = false) {
         TRY(launch_gram(c, 1, c->B32[c->bcur ^ 1], c->B32[c->bcur], true, c->ntr));
     }
     c->bcur ^= 1;
-    c->gB_valid = true;
-    c->P_valid = false;
-    c->tr_valid = true;
+    c->cache.B_moved_basic();
     return VBMF_OK;
 }
 
@@ -1119,9 +1106,9 @@ static int gram_prepare(vbmf_ctx* c) {
             c->g_part = nullptr; c->gsave = nullptr;
             FAIL(c, VBMF_ERR_HIP, "Gram-form sweep: device allocation failed (%s)", hipGetErrorString(e));
         }
-        c->G_valid = false;
+        c->cache.G_buffers_new();
     }
-    if (c->G_valid) return VBMF_OK;
+    if (c->cache.G()) return VBMF_OK;
     hipEvent_t a, b;
     HIPCHK(c, hipEventCreate(&a));
     HIPCHK(c, hipEventCreate(&b));
@@ -1138,8 +1125,7 @@ static int gram_prepare(vbmf_ctx* c) {
     HIPCHK(c, le);
     HIPCHK(c, se);
     c->gram_build_ms = ms;
-    c->G_valid = true;
-    c->W_valid = false;
+    c->cache.G_built();
     return VBMF_OK;
 }
 
@@ -1240,20 +1226,18 @@ static int gram_sweep(vbmf_ctx* c) {
     TRY(launch_chain(c, CTRL_COMMIT_A | CTRL_COV_B, c->SB32));
     TRY(gram_product(c, true));
     c->wcur ^= 1;
-    c->gA_valid = c->gB_valid = true;
-    c->P_valid = false;
-    c->tr_valid = true;
+    c->cache.gram_sweep_done_basic();
     return VBMF_OK;
 }
 
 // make st[GX] = tr(Y'BA') when the last B update did not leave it (state set by the caller, A changed since); *flag: legacy, 0
 static int prepare_trYBA(vbmf_ctx* c, int* flag) {
     *flag = 0;
-    if (c->tr_valid) return VBMF_OK;
+    if (c->cache.tr()) return VBMF_OK;
     double* dst = c->st + c->lay.GX();
     HIPCHK(c, hipMemsetAsync(dst, 0, sizeof(double), c->stream));
     // per-workgroup shares into c->ypart (scratch outside set_Y: <= 1024 of its 16384 doubles), folded in fixed order
-    if (c->P_valid) {
+    if (c->cache.P()) {
         const float* In = (sharded(c) || c->d1.nsplit > 1) ? c->Pred : c->P;
         const int ns = 1;
         const long long ld = (long long)c->d1.XT * 32;
@@ -1271,7 +1255,7 @@ static int prepare_trYBA(vbmf_ctx* c, int* flag) {
         if (sharded(c)) TRY(allreduce_sum(c, dst, 1, true));
     }
     HIPCHK(c, hipGetLastError());
-    c->tr_valid = true;
+    c->cache.tr_made();
     return VBMF_OK;
 }
 
@@ -1301,7 +1285,7 @@ static int device_err_status(vbmf_ctx* c, int e) {
     if ((e & 0xff) == 2) {
         // the epilogue left without touching B (stream_gemm.hpp), but A, SigmaA and the control scalars of that sweep are already
         // written: the device state is a mixture -- the handle asks for vbmf_set_state before it steps or runs again
-        c->haveState = false;
+        c->cache.state_mixed();
         FAIL(c, VBMF_ERR_SYNC, "in-launch hand-off timed out: the Y*A pass's register epilogue gave up waiting for the SigmaB "
                                "table of its own launch (bounded spin); this sweep's state is not valid, set the state again%s", where);
     }
@@ -1310,14 +1294,14 @@ static int device_err_status(vbmf_ctx* c, int e) {
 
 // the fp32 row-major BHat from its operand tiles, after run loops that skipped the per-sweep fp32 store
 static int rebuild_B32_if_stale(vbmf_ctx* c) {
-    if (!c->B32_stale) return VBMF_OK;
+    if (!c->cache.B32_stale()) return VBMF_OK;
     const int grid = (c->d2.XT + 3) / 4;
     DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
         hipLaunchKernelGGL((untile_factor_kernel<MODEc, NHc>), dim3(grid), dim3(256), 0, c->stream, c->FB, c->B32[c->bcur], c->d2.XT);
     }));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->B32_stale = false;
+    c->cache.B32_rebuilt();
     return VBMF_OK;
 }
 
@@ -1343,16 +1327,43 @@ struct RunFrame {
     double *d_last, *trace;
     double* trace_dev = nullptr;
     int64_t done = -1;                                     // sweeps the device executed (-1: not read back)
+    // the Gram form: whether this run takes it, the B and W buffers it started from, and the sweeps enqueued
+    // by the streaming path (Gram form: at most the first)
+    bool gram = false;
+    int bstart = 0, wstart = 0;
+    int64_t stream_sweeps = 0;
 
     ~RunFrame() { release(); }
     void release() { if (trace_dev) hipFree(trace_dev); trace_dev = nullptr; }
     // the device, the state, the callers' defaults
     int open() {
         HIPCHK(c, hipSetDevice(c->o.device));
-        TRY(ensure_ready(c, true, false));                 // (B: only a run that starts by the streaming path needs it, see start_B)
+        TRY(ensure_ready(c, true, false));                 // (B: only a run that starts by the streaming path needs it, see begin_gram)
         if (iters_done) *iters_done = 0;
         if (d_last) *d_last = eps + 1.0;                   // src/vbmf.jl:189, src/vbmf_sparse.jl:364
         return VBMF_OK;
+    }
+    // G = Y'Y is built here once per Y; a run that starts without a valid W does its first sweep by the streaming path, which starts
+    // from B.  After open(), before arm().
+    int begin_gram() {
+        gram = gram_eligible(c);
+        if (gram) TRY(gram_prepare(c));
+        else c->cache.W_dropped();
+        if (!(gram && c->cache.W())) TRY(ensure_B(c));
+        bstart = c->bcur;
+        wstart = c->wcur;
+        return VBMF_OK;
+    }
+    // after the two updates of a streaming sweep: in the Gram form, W of this sweep and P = G W for the next one (the Grams of this
+    // sweep came from the B update)
+    int close_stream_sweep(int rc) {
+        ++stream_sweeps;
+        if (rc == VBMF_OK && gram) {
+            rc = gram_product(c, false);
+            c->wcur ^= 1;
+            c->cache.W_made();
+        }
+        return rc;
     }
     // the trace buffer, the loop counters {stop, iters, err, niter} and the ranks' summed error flag
     int arm() {
@@ -1398,7 +1409,8 @@ struct RunFrame {
         }
     }
     // drains both streams, reads back the counters and the 32 scalars, settles c->bcur (B moved in the first `b_sweeps` executed sweeps,
-    // from buffer `bstart`), the fp32 B, the outputs and the trace, maps the device's error flag to a status, clears the counters
+    // from buffer `bstart`), the fp32 B, the outputs and the trace, maps the device's error flag to a status, clears the counters;
+    // Gram form: settles c->wcur (every executed sweep moved W) and what the run owes
     int finish(int rc, int bstart, int64_t b_sweeps) {
         c->in_run = false;
         c->use_side = false;
@@ -1432,8 +1444,16 @@ struct RunFrame {
         int zero4[4] = {0, 0, 0, 0};
         memcpy_sync(c, c->ints, zero4, sizeof zero4, hipMemcpyHostToDevice);
         release();
-        c->gA_valid = c->gB_valid = true;
-        c->P_valid = false;
+        if (c->sparse) c->cache.run_ended_sparse(c->diagvar);
+        else c->cache.run_ended_basic();
+        if (gram) {
+            int64_t gram_done = 0;                             // Gram-form sweeps the device executed
+            if (done >= 0) {
+                c->wcur = wstart ^ (int)(done & 1);
+                gram_done = done - std::min<int64_t>(done, stream_sweeps);
+            }
+            c->cache.gram_run_ended(rc == VBMF_OK, gram_done > 0);
+        }
         return rc;
     }
 };
@@ -1874,14 +1894,8 @@ static int finish_Y(vbmf_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->scal_host, tr, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->trYY_local = c->scal_host[0];
-    c->trYY_reduced = !sharded(c) && c->o.nranks == 1;
-    c->haveY = true;
+    c->cache.Y_complete(!sharded(c) && c->o.nranks == 1);
     c->y_rows = c->L;
-    c->P_valid = false;
-    c->Q_valid = false;
-    c->G_valid = c->W_valid = false;                   // G = Y'Y is rebuilt by the next run that takes the Gram form
-    c->B_pending = false;                              // ... and B = Y W of the old Y is owed no longer
-    c->tr_valid = false;
     if (c->diagvar) {                                  // ||Y_l||^2 of every row (:310), from the stored values
         DISPATCH_MODE(c->mode, {
             constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
@@ -1933,9 +1947,9 @@ int vbmf_set_Y_rows(vbmf_ctx* c, const void* src, int32_t dt, int32_t on_device,
     if (row0 < 0 || nrows <= 0 || row0 % 32 != 0 || nrows > c->L - row0 || (nrows % 32 != 0 && row0 + nrows != c->L))
         FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: rows [%lld, %lld) of %lld: a block starts at a multiple of 32 and ends at one or at L",
              (long long)row0, (long long)(row0 + nrows), (long long)c->L);
-    if (row0 != 0 && (c->haveY || row0 != c->y_rows))
+    if (row0 != 0 && (c->cache.have_Y() || row0 != c->y_rows))
         FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: blocks come in ascending, contiguous order (row0 = %lld, the next block starts at %lld)",
-             (long long)row0, (long long)(c->haveY ? 0 : c->y_rows));
+             (long long)row0, (long long)(c->cache.have_Y() ? 0 : c->y_rows));
     const size_t es = src_elem_size(dt);
     if (!on_device) {
         if (rs != 1 && cs != 1) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_rows: a host source needs row_stride = 1 or col_stride = 1");
@@ -1968,11 +1982,8 @@ int vbmf_set_Y_rows(vbmf_ctx* c, const void* src, int32_t dt, int32_t on_device,
     HIPCHK(c, hipEventRecord(c->ev_y[0], c->stream));
     double* tr = c->st + c->lay.scal() + S_TRYY;
     if (row0 == 0) {                                   // a new Y begins: none until its last block has arrived
-        c->haveY = false;
+        c->cache.Y_begins();
         c->y_rows = 0;
-        c->P_valid = c->Q_valid = c->tr_valid = false;
-        c->G_valid = c->W_valid = false;
-        c->B_pending = false;
         HIPCHK(c, hipMemsetAsync(tr, 0, sizeof(double), c->stream));
     }
     if (on_device) {
@@ -2098,7 +2109,7 @@ int vbmf_set_Y_synthetic(vbmf_ctx* c, uint64_t seed, int64_t Hstar, double noise
 
 int vbmf_get_Y(vbmf_ctx* c, double* Y, int64_t ldY, int64_t row0, int64_t nrows) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "no Y");
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "no Y");
     if (!Y || row0 < 0 || nrows <= 0 || row0 + nrows > c->L || ldY < nrows) FAIL(c, VBMF_ERR_INVALID, "vbmf_get_Y: bad range");
     HIPCHK(c, hipSetDevice(c->o.device));
     // column chunks of a multiple of 32 (= whole k-steps of the pass-2 copy)
@@ -2126,9 +2137,9 @@ int vbmf_get_Y(vbmf_ctx* c, double* Y, int64_t ldY, int64_t row0, int64_t nrows)
 
 int vbmf_get_trYY(vbmf_ctx* c, double* trYY) {
     if (!c || !trYY) return VBMF_ERR_INVALID;
-    if (!c->haveY) FAIL(c, VBMF_ERR_INVALID, "no Y");
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "no Y");
     HIPCHK(c, hipSetDevice(c->o.device));
-    if (!c->trYY_reduced) { *trYY = c->trYY_local; return VBMF_OK; }     // this rank's part until the first step/run
+    if (!c->cache.trYY_reduced()) { *trYY = c->trYY_local; return VBMF_OK; }     // this rank's part until the first step/run
     HIPCHK(c, hipMemcpyAsync(c->scal_host, c->st + c->lay.scal() + S_TRYY, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *trYY = c->scal_host[0];
@@ -2216,18 +2227,14 @@ int vbmf_set_state(vbmf_ctx* c, const double* AHat, int64_t ldA, const double* B
     HIPCHK(c, hipMemsetAsync(c->ints, 0, 16 * sizeof(int), c->stream));
     if (c->dbg_sb_ppm) HIPCHK(c, hipMemcpyAsync(c->ints + I_DBG_SB_PPM, &c->dbg_sb_ppm, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->gA_valid = c->gB_valid = c->P_valid = c->tr_valid = false;
-    c->W_valid = false;                                // B is no longer Y W: the next run starts by the streaming path
-    c->B_pending = false;                              // ... from the B just set
-    c->B32_stale = false;
-    c->haveState = true;
+    c->cache.state_set_basic();
     return VBMF_OK;
 }
 
 int vbmf_get_state(vbmf_ctx* c, double* AHat, int64_t ldA, double* BHat, int64_t ldB, double* SigmaA,
                    double* SigmaB, double* CA_diag, double* CB_diag, double* sigma2) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "no state");
+    if (!c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no state");
     HIPCHK(c, hipSetDevice(c->o.device));
     if (BHat) TRY(ensure_B(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2255,7 +2262,7 @@ int vbmf_step(vbmf_ctx* c, int which) {
     if (which & ~31) FAIL(c, VBMF_ERR_INVALID, "vbmf_step: unknown update bits");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c, (which & (VBMF_STEP_A | VBMF_STEP_B | VBMF_STEP_SIGMA2)) != 0));
-    c->W_valid = false;
+    c->cache.W_dropped();
     if (which & VBMF_STEP_A) TRY(do_update_A(c));
     if (which & VBMF_STEP_B) TRY(do_update_B(c));
     int flags = 0;
@@ -2284,7 +2291,7 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
     if (niter < 0 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "vbmf_run_fixed_basis: bad niter");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c));
-    c->W_valid = false;
+    c->cache.W_dropped();
     // Without a label mask the loop is H x H algebra on S = P'P (ctrl_kernels.hpp, vbls_loop_kernel): the first iteration runs the
     // general way (it forms P = Y'B), the rest in ONE launch of one workgroup, and A is formed once at the end.  H <= 64.
     // (VBMF_VBLS_LOOP=0: every iteration the general way -- the A/B switch of profiles/r03_f_vbls_mil.txt)
@@ -2313,8 +2320,7 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
         });
         HIPCHK(c, hipGetLastError());
         TRY(launch_post_gram(c, 0, Psrc));                  // A = P SigmaA / sigma2 of the last updateA!, its tiles and A'A
-        c->gA_valid = true;
-        c->tr_valid = false;
+        c->cache.A_moved_by_vbls_loop();
     }
     return check_device_err(c);
 }
@@ -2327,12 +2333,7 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     RunFrame run{c, niter, eps, iters_done, d_last, trace};
     TRY(run.open());
     if (niter == 0) return VBMF_OK;
-    // Gram form: G = Y'Y is built here once per Y; a run that starts without a valid W does its first sweep
-    // by the streaming path
-    const bool gram = gram_eligible(c);
-    if (gram) TRY(gram_prepare(c));
-    else c->W_valid = false;
-    if (!(gram && c->W_valid)) TRY(ensure_B(c));           // the first sweep streams: it starts from B
+    TRY(run.begin_gram());
     TRY(run.arm());
     // ||B_old||_2 of the first comparison (src/vbmf.jl:187-188: old = params.BHat): in the fused schedule
     // every sweep's pass-2 launch computes it; otherwise once here, then rotated by ctrl_end
@@ -2344,8 +2345,6 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
             hipLaunchKernelGGL(copy_scalar_kernel, dim3(1), dim3(1), 0, c->stream, c->st, c->lay, (int)S_LAMB_PREV, (int)S_LAMB_NEW);
     }
     const int flags = (est_covs ? 3 : 0) | (est_var ? 4 : 0) | 8 | 16;
-    const int bstart = c->bcur, wstart = c->wcur;
-    int64_t stream_sweeps = 0;                             // sweeps enqueued by the streaming path (Gram form: at most the first)
     c->in_run = true;
     c->ends_enqueued = 0;
     c->tail_pending = false;
@@ -2359,21 +2358,14 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     int64_t it = 0;
     bool stopped = false;
     while (rc == VBMF_OK && it < niter && !stopped) {
-        if (gram && c->W_valid) {
+        if (run.gram && c->cache.W()) {
             rc = gram_sweep(c);              // carries the closing control step of the previous sweep
-            ++it;
         } else {
             rc = do_update_A(c);             // carries lambda_max + ctrl_end of the previous sweep when fused
             if (rc == VBMF_OK) rc = do_update_B(c);
-            ++it;
-            ++stream_sweeps;
-            if (rc == VBMF_OK && gram) {
-                // W of this sweep and P = G W for the next one; the Grams of this sweep came from the pass's epilogue
-                rc = gram_product(c, false);
-                c->wcur ^= 1;
-                c->W_valid = true;
-            }
+            rc = run.close_stream_sweep(rc);
         }
+        ++it;
         const bool last = (it == niter);
         if (rc == VBMF_OK) {                 // (the Gram form is always fused: Hp <= 128)
             if (fused_ctrl(c) && !last) {
@@ -2395,23 +2387,12 @@ int vbmf_run(vbmf_ctx* c, int64_t niter, double eps, int est_covs, int est_var, 
     c->tail_pending = false;
     c->run_trace = nullptr;
     // in the Gram form only the streaming sweep (the first, if any) moves B, and every sweep moves W
-    rc = run.finish(rc, bstart, stream_sweeps);
-    int64_t gram_done = 0;                                 // Gram-form sweeps the device executed
-    if (gram && run.done >= 0) {
-        c->wcur = wstart ^ (int)(run.done & 1);
-        gram_done = run.done - std::min<int64_t>(run.done, stream_sweeps);
-    }
-    c->tr_valid = true;
-    if (gram && rc != VBMF_OK) c->W_valid = false;
-    // B of the last executed sweep is owed, not made: the first reader pays the pass (ensure_B), a Gram-form run that continues
-    // from here never does
-    if (gram && rc == VBMF_OK && gram_done > 0) c->B_pending = true;
-    return rc;
+    return run.finish(rc, run.bstart, run.stream_sweeps);
 }
 
 int vbmf_get_YHat(vbmf_ctx* c, double* YHat, int64_t ld) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "no state");
+    if (!c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no state");
     if (!YHat || ld < c->L) FAIL(c, VBMF_ERR_INVALID, "vbmf_get_YHat: bad arguments");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_B(c));
@@ -2468,8 +2449,7 @@ int vbmf_comm_init(vbmf_ctx* c, const void* id128) {
     memcpy(&id, id128, sizeof id);
     NCCLCHK(c, ncclCommInitRank(&c->comm, c->o.nranks, id, c->o.rank));
     c->comm_ready = true;
-    c->trYY_reduced = false;          // ||Y||^2 (if already set) must be summed over the ranks
-    c->gA_valid = c->gB_valid = false;
+    c->cache.communicator_attached();  // ||Y||^2 (if already set) and the Grams must be summed over the ranks
     return VBMF_OK;
 }
 
@@ -2481,8 +2461,7 @@ int vbmf_comm_set_transport(vbmf_ctx* c, vbmf_allreduce_fn fn, void* user) {
     c->ar_hook = fn;
     c->ar_user = user;
     c->comm_ready = true;
-    c->trYY_reduced = false;
-    c->gA_valid = c->gB_valid = false;
+    c->cache.communicator_attached();
     return VBMF_OK;
 }
 
@@ -2538,10 +2517,10 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
     if (what == VBMF_PEEK_DIMS) {
         const int v[30] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
                            c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
-                           gram_eligible(c) ? 1 : 0, c->G_valid ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
+                           gram_eligible(c) ? 1 : 0, c->cache.G() ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
                            c->frag_last[0] ? 1 : 0, c->frag_last[1] ? 1 : 0, c->epi_last ? 1 : 0, use_lds8(c) ? 1 : 0, c->xcd_map ? 1 : 0,
                            c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0, (int)std::lround(c->set_y_ms * 1000.0),
-                           c->B_pending ? 1 : 0, (int)std::min<long long>(c->b_materialised, 0x7fffffff)};
+                           c->cache.B_owed() ? 1 : 0, (int)std::min<long long>(c->b_materialised, 0x7fffffff)};
         memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(30, nwords));
         return VBMF_OK;
     }
@@ -2594,7 +2573,7 @@ int vbmf_debug_time_pass(vbmf_ctx* c, int pass, int iters, double* ms) {
     hipEventDestroy(a);
     hipEventDestroy(b);
     c->prof = prof;
-    c->P_valid = false;
+    c->cache.P_overwritten();
     *ms = t / iters;
     return rc;
 }
@@ -2762,7 +2741,7 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
     if (c->diagvar) {
         // :211, :230 -- B enters as diag(sigmaVecHat) * B: tiles of the row-scaled factor for the pass, and
         // sum_l (sigma_l B[l,h])^2 for the precision of vec(A')
-        if (!c->have_noise) FAIL(c, VBMF_ERR_INVALID, "no row noise state: call vbmf_sparse_set_noise_rows first");
+        if (!c->cache.have_noise()) FAIL(c, VBMF_ERR_INVALID, "no row noise state: call vbmf_sparse_set_noise_rows first");
         TRY(launch_retile_ex(c, 1, c->B32[c->bcur], c->FBs, c->sig32, 0, true));
         double* part = c->st + c->lay.W1();
         hipLaunchKernelGGL(colsum_part_kernel, dim3(c->Hp / 32, COLSUM_CHUNKS), dim3(256), 0, c->stream, c->B32[c->bcur], (long long)c->L,
@@ -2771,7 +2750,7 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
         if (sharded(c)) TRY(allreduce_sum(c, c->vsq, (size_t)c->Hp, true));    // scratch, rebuilt before every use
         reuse_P = false;                            // sigma changes every iteration, so does Y' diag(sigma) B
     }
-    if (!(reuse_P && c->P_valid)) {
+    if (!(reuse_P && c->cache.P())) {
         c->P_frag = false;                          // the element-wise A update reads the plain [h][m] product
         TRY(launch_stream(c, 0));
         const long long n = (long long)c->Hp * c->d1.XT * 32;
@@ -2798,10 +2777,7 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
         HIPCHK(c, hipGetLastError());
         TRY(launch_retile(c, 0, true));
         TRY(launch_gram(c, 0, c->A32, nullptr, true));
-        c->gA_valid = true;
-        c->P_valid = true;
-        c->Q_valid = false;
-        c->tr_valid = false;
+        c->cache.A_moved_sparse(true);
         return VBMF_OK;
     }
     hipLaunchKernelGGL(sparse_v_kernel, dim3((c->Hp + 63) / 64), dim3(64), 0, c->stream, c->st, c->lay, (int)c->H, (double)c->Lg, c->vtab,
@@ -2827,10 +2803,7 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
     }
     TRY(launch_gram(c, 0, c->A32, nullptr, true));
     TRY(sparse_colsum(c));                          // SigmaA = diag(sum_m diagSigma)
-    c->gA_valid = true;
-    c->P_valid = !c->diagvar;
-    c->Q_valid = false;
-    c->tr_valid = false;
+    c->cache.A_moved_sparse(!c->diagvar);           // (diag_var: c->Pred is Y' diag(sigma) B)
     return VBMF_OK;
 }
 
@@ -2860,10 +2833,7 @@ static int do_sparse_update_B(vbmf_ctx* c, bool keep_sigma = false) {
         TRY(launch_gram(c, 1, c->B32[c->bcur ^ 1], c->B32[c->bcur], true, c->ntr));
     }
     c->bcur ^= 1;
-    c->gB_valid = true;
-    c->P_valid = false;
-    c->Q_valid = true;
-    c->tr_valid = !c->diagvar;
+    c->cache.B_moved_sparse(c->diagvar);
     return VBMF_OK;
 }
 
@@ -2871,11 +2841,11 @@ static int do_sparse_update_B(vbmf_ctx* c, bool keep_sigma = false) {
 // streaming pass 2 with that sweep's A and SigmaB / sigma2 (sparse model: sigmaHat SigmaB) table, which is still in place: B, its
 // operand tiles and the fp32 copy as a streaming run leaves them.  The state's [B'B | dB'dB | tr(B'YA)] stay the Gram form's, so a
 // run that continues from here computes what one longer run computes.  Every entry point that reads B, its tiles or anything
-// derived from them comes through here first (ensure_ready does it for most); vbmf_set_state and the vbmf_set_Y* calls drop the
-// debt with W; a Gram-form run that finds W valid, and vbmf_destroy, never pay it ("Run boundaries").
+// derived from them comes through here first (ensure_ready does it for most); a Gram-form run that finds W valid, and vbmf_destroy,
+// never pay.  What drops the debt: ctx_cache.hpp.
 static int ensure_B(vbmf_ctx* c) {
-    if (!c->B_pending) return VBMF_OK;
-    c->B_pending = false;
+    if (!c->cache.B_owed()) return VBMF_OK;
+    c->cache.B_payment_begins();
     ++c->b_materialised;
     const size_t nsave = 2 * (size_t)c->Hp * c->Hp + 8;
     int rc = VBMF_OK;
@@ -2888,18 +2858,17 @@ static int ensure_B(vbmf_ctx* c) {
         if (e != hipSuccess) { c->err = std::string("B after a Gram-form run: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; }
     }
     if (rc == VBMF_OK) rc = check_device_err(c);
-    if (rc != VBMF_OK) c->W_valid = false;
-    if (c->sparse) c->Q_valid = false;
+    c->cache.B_payment_ends(c->sparse, rc == VBMF_OK);
     return rc;
 }
 
 // updateSigma!, diag_var = true (:308-315): every row's Gamma posterior; S_SIGMA2 := mean(sigmaVecHat)
 static int do_hetero_sigma(vbmf_ctx* c) {
     TRY(ensure_gram_A(c));
-    if (!c->Q_valid) {                              // Y*A for the current A (not left over from updateB!)
+    if (!c->cache.Q()) {                              // Y*A for the current A (not left over from updateB!)
         TRY(launch_stream(c, 1));
         TRY(fold_Q_slabs(c));
-        c->Q_valid = true;
+        c->cache.Q_made();
     }
     const int* stop = c->ints + I_STOP;
     hipLaunchKernelGGL(hetero_g_kernel, dim3(1), dim3(1024), 0, c->stream, c->st, c->lay, (int)c->H, c->G32, stop);
@@ -2984,10 +2953,7 @@ static int sparse_gram_sweep(vbmf_ctx* c) {
     TRY(launch_sparse_cov_b(c));
     TRY(gram_product(c, true));
     c->wcur ^= 1;
-    c->gA_valid = c->gB_valid = true;
-    c->P_valid = false;
-    c->Q_valid = false;
-    c->tr_valid = true;
+    c->cache.gram_sweep_done_sparse();
     return VBMF_OK;
 }
 
@@ -3073,13 +3039,7 @@ int vbmf_sparse_set_state(vbmf_ctx* c, const double* ATVecHat, const double* dia
     HIPCHK(c, hipMemsetAsync(c->ints, 0, 16 * sizeof(int), c->stream));
     if (c->dbg_sb_ppm) HIPCHK(c, hipMemcpyAsync(c->ints + I_DBG_SB_PPM, &c->dbg_sb_ppm, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->gA_valid = c->gB_valid = c->P_valid = c->tr_valid = false;
-    c->Q_valid = false;
-    c->have_noise = false;
-    c->B32_stale = false;
-    c->haveState = true;
-    c->W_valid = false;                                // B is no longer Y W: the next run starts by the streaming path
-    c->B_pending = false;                              // ... from the B just set
+    c->cache.state_set_sparse();
     return VBMF_OK;
 }
 
@@ -3087,7 +3047,7 @@ int vbmf_sparse_get_state(vbmf_ctx* c, double* ATVecHat, double* diagSigmaATVec,
                           double* SigmaA_diag, double* BHat, int64_t ldB, double* SigmaB, double* CB,
                           double* delta, double* sigmaHat, double* zeta) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->sparse || !c->haveState) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
+    if (!c->sparse || !c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
     HIPCHK(c, hipSetDevice(c->o.device));
     if (BHat) TRY(ensure_B(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3119,7 +3079,7 @@ int vbmf_sparse_step(vbmf_ctx* c, int which) {
         FAIL(c, VBMF_ERR_INVALID, "VBMF_SSTEP_PRIORS needs the group sums of VBMF_SSTEP_CA in the same call");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c, (which & (VBMF_SSTEP_A | VBMF_SSTEP_B | VBMF_SSTEP_SIGMA)) != 0));
-    c->W_valid = false;
+    c->cache.W_dropped();
     if (which & VBMF_SSTEP_A) TRY(do_sparse_update_A(c));
     if (which & VBMF_SSTEP_B) TRY(do_sparse_update_B(c));
     if (which & VBMF_SSTEP_CA) TRY(sparse_update_CA(c));
@@ -3148,7 +3108,7 @@ int vbmf_sparse_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
     if (niter < 0 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "bad niter");
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_ready(c));
-    c->W_valid = false;
+    c->cache.W_dropped();
     for (int64_t it = 0; it < niter; ++it) {
         TRY(do_sparse_update_A(c, true));
         TRY(sparse_update_CA(c));
@@ -3173,12 +3133,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
     RunFrame run{c, niter, eps, iters_done, d_last, trace};
     TRY(run.open());
     if (niter == 0) return VBMF_OK;
-    // Gram form: G = Y'Y is built here once per Y; a run that starts without a valid W does its first sweep
-    // by the streaming path
-    const bool gram = gram_eligible(c);
-    if (gram) TRY(gram_prepare(c));
-    else c->W_valid = false;
-    if (!(gram && c->W_valid)) TRY(ensure_B(c));           // the first sweep streams: it starts from B
+    TRY(run.begin_gram());
     TRY(run.arm());
     int rc = ensure_gram_B(c);
     if (rc == VBMF_OK) rc = launch_eig(c, 0, 1);
@@ -3186,32 +3141,24 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         hipLaunchKernelGGL(copy_scalar_kernel, dim3(1), dim3(1), 0, c->stream, c->st, c->lay, (int)S_LAMB_PREV, (int)S_LAMB_NEW);
     // diag_var: the rows' noise update (:308-315) replaces the scalar one and runs before the stop test of the sweep
     const int flags = (est_cb ? 2 : 0) | (c->diagvar ? 0 : 4 | 16) | 8;
-    const int bstart = c->bcur, wstart = c->wcur;
-    int64_t stream_sweeps = 0;                             // sweeps enqueued by the streaming path (Gram form: at most the first)
     const int64_t check = 8;                               // sweeps between two looks at the stop flag (RunFrame::look)
     int64_t it = 0;
     bool stopped = false;
     c->in_run = true;
     while (rc == VBMF_OK && it < niter && !stopped) {
-        if (gram && c->W_valid) {
+        if (run.gram && c->cache.W()) {
             rc = sparse_gram_sweep(c);
         } else {
             rc = do_sparse_update_A(c);
             if (rc == VBMF_OK) rc = do_sparse_update_B(c);
-            ++stream_sweeps;
-            if (rc == VBMF_OK && gram) {
-                // W of this sweep and P = G W for the next one; the Grams of this sweep came from the B update
-                rc = gram_product(c, false);
-                c->wcur ^= 1;
-                c->W_valid = true;
-            }
+            rc = run.close_stream_sweep(rc);
         }
         // updateCA! reads what the A update left and writes what the NEXT A update reads: with a side stream (H > 128) it runs there too,
         // beside the next sweep's Y'B pass, instead of 13 us between the sweeps (not with the group priors or the row noise behind it)
         // In a Gram-form run (rank 256 under VBMF_GRAM_FORM_ON) nothing is forked: whatever follows this sweep -- a Gram sweep, whose
         // first kernel (sparse_v) reads the sigmaHat, B'B and SigmaB the control step writes, or the run's end -- has no pass over Y to
         // hide the chain behind.  The run's first, streaming sweep keeps the forks inside its two updates (joined before its post kernel).
-        const bool overlap = side_overlap(c) && !gram;
+        const bool overlap = side_overlap(c) && !run.gram;
         const bool ca_on_side = overlap && !est_priors && !c->diagvar;
         if (rc == VBMF_OK && !ca_on_side) rc = sparse_update_CA(c);
         if (rc == VBMF_OK && est_priors) rc = dual_update_priors(c);      // depends on updateCA!'s outputs only
@@ -3232,17 +3179,7 @@ static int sparse_run_impl(vbmf_ctx* c, int64_t niter, double eps, int est_cb, i
         }
     }
     // every streaming sweep moves B; in the Gram form only the streaming sweep (the first, if any) does, and every sweep moves W
-    rc = run.finish(rc, bstart, gram ? stream_sweeps : niter);
-    c->Q_valid = false;
-    c->tr_valid = !c->diagvar;
-    int64_t gram_done = 0;                                 // Gram-form sweeps the device executed
-    if (gram && run.done >= 0) {
-        c->wcur = wstart ^ (int)(run.done & 1);
-        gram_done = run.done - std::min<int64_t>(run.done, stream_sweeps);
-    }
-    if (gram && rc != VBMF_OK) c->W_valid = false;
-    if (gram && rc == VBMF_OK && gram_done > 0) c->B_pending = true;   // B of the last executed sweep: owed (ensure_B, see vbmf_run)
-    return rc;
+    return run.finish(rc, run.bstart, run.gram ? run.stream_sweeps : niter);
 }
 
 int vbmf_sparse_run(vbmf_ctx* c, int64_t niter, double eps, int est_cb, int64_t* iters_done, double* d_last,
@@ -3271,7 +3208,7 @@ int vbmf_sparse_set_full_cov(vbmf_ctx* c, int on) {
         HIPCHK(c, hipMemsetAsync(c->gw, 0, bytes, c->stream));
     }
     c->full_cov = on != 0;
-    c->W_valid = false;                                // (full_cov on: the context leaves the Gram form, gram_structural)
+    c->cache.W_dropped();                              // (full_cov on: the context leaves the Gram form, gram_structural)
     return VBMF_OK;
 }
 
@@ -3284,7 +3221,7 @@ int vbmf_set_gram_form(vbmf_ctx* c, int mode) {
     HIPCHK(c, hipSetDevice(c->o.device));
     TRY(ensure_B(c));
     c->gram_form = mode;
-    c->W_valid = false;
+    c->cache.W_dropped();
     return VBMF_OK;
 }
 
@@ -3292,17 +3229,17 @@ int vbmf_set_gram_form(vbmf_ctx* c, int mode) {
 // vbmf_sparse_set_state derives it from diagSigmaATVec -- a caller continuing a full_cov state sets it explicitly.
 int vbmf_sparse_set_SigmaA(vbmf_ctx* c, const double* SigmaA) {
     if (!c || !SigmaA) return VBMF_ERR_INVALID;
-    if (!c->sparse || !c->haveState) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
+    if (!c->sparse || !c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     TRY(upload_small(c, SigmaA, c->lay.SA(), true));
-    c->tr_valid = false;
+    c->cache.SigmaA_set();
     return VBMF_OK;
 }
 
 int vbmf_sparse_get_SigmaA(vbmf_ctx* c, double* SigmaA) {
     if (!c || !SigmaA) return VBMF_ERR_INVALID;
-    if (!c->sparse || !c->haveState) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
+    if (!c->sparse || !c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no sparse state");
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<double> buf((size_t)c->Hp * c->Hp);
@@ -3315,7 +3252,7 @@ int vbmf_sparse_get_SigmaA(vbmf_ctx* c, double* SigmaA) {
 // ---- grouped ARD variants (src/vbmf_dual.jl, src/vbmf_trial.jl; full_cov=false, diag_var=false) -------------------
 // priors9 = {alpha0 prior, beta0 prior} x 3 groups, then the 3 posterior shapes
 static int group_set_priors(vbmf_ctx* c, int64_t H0, int64_t M0, const double* v9) {
-    if (!c->haveState) FAIL(c, VBMF_ERR_INVALID, "call vbmf_sparse_set_state first");
+    if (!c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "call vbmf_sparse_set_state first");
     if (H0 < 0 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "H must be at least H0!");          // src/vbmf_dual.jl:126-128
     if (M0 < 0 || M0 > c->M) FAIL(c, VBMF_ERR_INVALID, "M0 must lie in 0..M");
     for (int i = 0; i < 9; ++i)
@@ -3338,7 +3275,7 @@ int vbmf_dual_set_priors(vbmf_ctx* c, int64_t H0, double alpha00, double beta00,
 
 int vbmf_dual_get_priors(vbmf_ctx* c, int64_t* H0, double* priors6) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->dual || c->trial || !c->haveState) FAIL(c, VBMF_ERR_INVALID, "no two-group state");
+    if (!c->dual || c->trial || !c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no two-group state");
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (H0) *H0 = c->H0;
@@ -3365,7 +3302,7 @@ int vbmf_trial_set_priors(vbmf_ctx* c, int64_t H0, int64_t M0, const double* pri
 
 int vbmf_trial_get_priors(vbmf_ctx* c, int64_t* H0, int64_t* M0, double* priors9) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->trial || !c->haveState) FAIL(c, VBMF_ERR_INVALID, "no three-group state");
+    if (!c->trial || !c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "no three-group state");
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (H0) *H0 = c->H0;
@@ -3396,14 +3333,13 @@ int vbmf_sparse_set_noise_rows(vbmf_ctx* c, const double* sigmaVecHat, const dou
     HIPCHK(c, memcpy_sync(c, c->sig32, s32.data(), (size_t)c->Lp * 4, hipMemcpyHostToDevice));
     HIPCHK(c, memcpy_sync(c, c->st + c->lay.scal() + S_SIGMA2, &mean, 8, hipMemcpyHostToDevice));
     c->etaVec = etaVec;
-    c->have_noise = true;
-    c->noise_mean_reduced = false;
+    c->cache.noise_rows_set();
     return VBMF_OK;
 }
 
 int vbmf_sparse_get_noise_rows(vbmf_ctx* c, double* sigmaVecHat, double* zetaVec) {
     if (!c) return VBMF_ERR_INVALID;
-    if (!c->diagvar || !c->have_noise) FAIL(c, VBMF_ERR_INVALID, "no row noise state");
+    if (!c->diagvar || !c->cache.have_noise()) FAIL(c, VBMF_ERR_INVALID, "no row noise state");
     HIPCHK(c, hipSetDevice(c->o.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (sigmaVecHat) HIPCHK(c, memcpy_sync(c, sigmaVecHat, c->sigv, (size_t)c->L * 8, hipMemcpyDeviceToHost));
