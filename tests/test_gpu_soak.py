@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as G
+from oracle import vbmf_oracle as O
 from tests.helpers import relF
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +71,89 @@ def test_create_destroy_does_not_leak(pkg):
         cycle((pkg.capi.VBMF_VARIANT_BASIC, pkg.capi.VBMF_VARIANT_SPARSE_DIAG, pkg.capi.VBMF_VARIANT_SPARSE_DIAGVAR)[i % 3])
     after = _free_bytes()
     assert before - after < 64 << 20, (before, after)          # well under one context's footprint (~30 MB of tiles each)
+
+
+def _gram_group_bytes(d, M):
+    """Bytes of the eight buffers gram_prepare allocates together (csrc/vbmf_hip.hip), from dims() after a Gram-form run."""
+    Hp, NH, XT1, nsplit = d["Hp"], d["NH"], d["XT1"], d["gram_nsplit"]
+    GT = -(-XT1 // 16) * 16
+    KT, n = 2 * GT, Hp * XT1 * 32
+    nchunk = max(1, min(32 if Hp == 256 else 64 if Hp == 128 else 128, -(-M // 64)))
+    rpc = -(-(-(-M // nchunk)) // 16) * 16
+    nchunk = -(-M // rpc)
+    return (GT * KT * 64 * 8 * 4                    # Gt
+            + 2 * 32 * GT * Hp * 4                  # W32g[0], W32g[1]
+            + 5 * KT * NH * 64 * 16                 # Wt (GRAM_PLANES = 5)
+            + 2 * n * 4                             # gPQ
+            + (nsplit * 2 * n * 4 if nsplit > 1 else 0)   # gslabs
+            + nchunk * (2 * Hp * Hp + 2) * 8        # g_part
+            + (2 * Hp * Hp + 8) * 8)                # gsave
+
+
+def test_lazy_buffers_do_not_leak(pkg):
+    """Create, use and destroy four contexts and one preprocess plan per cycle, so that every lazily allocated device buffer exists
+    when its context goes: the Gram-form group, the many-bags scratch (grown once), the run trace, fws / fpart / t2part (rank
+    130: the side stream too), gw (diag_var) and the plan's four buffers.  After one warming cycle, 20 cycles may lower the
+    device's free memory by less than the basic context's Gram-form group of ONE cycle (23 069 120 bytes): a leak of that group, or of
+    anything larger, per cycle shows twentyfold.  Buffers too small for this count (t2part, hmean) are held by the counting
+    allocator of tests/ctx_mem_check.cpp.
+    Measured on an MI355X before csrc/ctx_mem.hpp existed (the hand-written free lists): a drop of 0 bytes over the 20 cycles."""
+    cap = pkg.capi
+    rng = np.random.default_rng(7)
+    L0, M0, H0 = 2048, 1536, 40
+    Y0 = rng.standard_normal((L0, H0)) @ rng.standard_normal((H0, M0)) + 0.05 * rng.standard_normal((L0, M0))
+    A0, B0 = rng.standard_normal((M0, H0)), rng.standard_normal((L0, H0))
+    z0 = np.zeros((H0, H0))
+    L1, M1 = 512, 96
+    sparse = {}
+    for H in (130, 40):
+        Y, _, _ = O.toy_matrix(L1, M1, 8, 0.05, np.random.default_rng(70 + H))
+        po = O.vbmf_sparse_init(Y, H, ca=0.1, cb=0.1, sigma=0.1, rng=np.random.default_rng(71 + H), full_cov=False,
+                                materialize_yhat=False)
+        sparse[H] = (Y, po, dict(alpha0=po.alpha0, beta0=po.beta0, gamma0=po.gamma0, delta0=po.delta0, eta0=po.eta0, zeta0=po.zeta0))
+    Yraw = rng.standard_normal((L1, M1)) * rng.uniform(0.5, 20.0, (L1, 1)) + rng.uniform(-5.0, 5.0, (L1, 1))
+
+    def sparse_ctx(variant, H, niter, trace):
+        Y, po, hyper = sparse[H]
+        with cap.Context(L1, M1, H, y_dtype=pkg.VBMF_Y_BF16, variant=variant) as c:
+            c.set_Y(Y)
+            c.sparse_set_state(po.ATVecHat, po.diagSigmaATVec, po.CA, po.beta, po.BHat, po.SigmaB, po.CB, po.delta, po.sigmaHat,
+                               po.zeta, hyper)
+            c.sparse_set_full_cov(True)
+            if variant == cap.VBMF_VARIANT_SPARSE_DIAGVAR:
+                c.sparse_set_noise_rows(np.ones(L1), 1e-10 * np.ones(L1), 1e-10 + M1 / 2)
+            it, _, tr = c.sparse_run(niter, eps=0.0, est_cb=True, want_trace=trace)
+            assert it == niter and (tr is None or tr.shape == (niter, 4))
+            if variant == cap.VBMF_VARIANT_SPARSE_DIAGVAR:
+                with cap.PreprocessPlan(Yraw) as plan:
+                    assert plan.L_used == L1
+                    c.set_Y_preprocessed(plan, 1.0)
+
+    def cycle():
+        with cap.Context(L0, M0, H0, y_dtype=pkg.VBMF_Y_BF16) as c:
+            c.set_Y(Y0)
+            c.set_state(A0, B0, z0, z0, 0.1 * np.ones(H0), 0.1 * np.ones(H0), 0.1)
+            c.set_gram_form(cap.VBMF_GRAM_FORM_ON)
+            it, _, tr = c.run(4, eps=0.0, est_covs=True, est_var=True, want_trace=True)
+            d = c.dims()
+            assert it == 4 and tr.shape == (4, 4) and d["gram"] == 1 and d["gram_built"] == 1, d
+            for nb in (2, 16):                      # the second call needs more scratch than the first: c->bags is regrown
+                off = np.linspace(0, M0, nb + 1).astype(np.int64)
+                c.run_fixed_basis_batched(off, 2, 0.1 * np.ones(nb), 0.1 * np.ones((nb, H0)))
+            c.YHat(); c.get_Y(); c.get_state()
+        sparse_ctx(cap.VBMF_VARIANT_SPARSE_DIAG, 130, 2, True)
+        sparse_ctx(cap.VBMF_VARIANT_SPARSE_DIAG, 40, 2, False)
+        sparse_ctx(cap.VBMF_VARIANT_SPARSE_DIAGVAR, 40, 2, False)
+        return _gram_group_bytes(d, M0)
+
+    bound = cycle()                                 # warms the runtime's pools
+    assert bound > 9 << 20, bound                   # G alone is 9 MB at M = 1536
+    before = _free_bytes()
+    for _ in range(20):
+        cycle()
+    after = _free_bytes()
+    print(f"lazy buffers: free memory dropped by {before - after} bytes over 20 cycles (bound {bound})")
+    assert before - after < bound, (before, after, bound)
 
 
 def test_numeric_error_leaves_the_handle_usable(pkg):

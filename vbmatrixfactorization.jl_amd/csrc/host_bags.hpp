@@ -25,10 +25,8 @@ static int bags_check(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t*
 static int bags_reserve(vbmf_ctx* c, int64_t doubles, double** d) {
     if ((size_t)doubles * 8 > c->bags_bytes) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->bags) HIPCHK(c, hipFree(c->bags));
-        c->bags = nullptr;
         c->bags_bytes = 0;
-        HIPCHK(c, hipMalloc((void**)&c->bags, (size_t)doubles * 8));
+        MEMCHK(c, c->mem.regrow(c->bags, (size_t)doubles * 8));
         c->bags_bytes = (size_t)doubles * 8;
     }
     *d = c->bags;

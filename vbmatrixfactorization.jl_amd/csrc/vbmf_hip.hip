@@ -43,6 +43,7 @@
 
 #include "common.hpp"
 #include "ctx_cache.hpp"
+#include "ctx_mem.hpp"
 #include "ctrl_kernels.hpp"
 #include "post_kernels.hpp"
 #include "rng.hpp"
@@ -63,6 +64,16 @@ using namespace vbmf;
 static thread_local std::string g_create_error;
 
 struct ProfEvent { hipEvent_t a, b; int pass; };
+
+// Device memory (ctx_mem.hpp): the one place that names the device allocator.  A context's and a plan's buffers go through their
+// MemOwner, a call's temporaries through a DevScratch; nothing else allocates or frees.
+struct HipMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void* p) { hipFree(p); }
+};
+template <class T>
+using DevScratch = Scratch<HipMem, T>;
+static const char* mem_errstr(int rc) { return rc == MEM_SLOT_BUSY ? "the slot already holds a buffer" : hipGetErrorString((hipError_t)rc); }
 
 struct vbmf_ctx {
     std::string err;
@@ -159,6 +170,7 @@ struct vbmf_ctx {
     double run_eps = 0.0;
     double* run_trace = nullptr;
     CtxCache cache;                   // which derived device data are current, and the only way to change that (ctx_cache.hpp)
+    MemOwner<HipMem> mem;             // every device buffer above and below: acquired through it, freed by it (ctx_mem.hpp)
     hipEvent_t ev_y[2] = {nullptr, nullptr};   // around the device work of the last vbmf_set_Y_rows call (created by the first one)
     double set_y_ms = 0.0;            // ... and what they measured: staged copies, tiling kernels, ||Y||^2 (VBMF_PEEK_DIMS word 27, us)
     int64_t y_rows = 0;               // vbmf_set_Y_rows: rows of the Y being built that have arrived (L once Y is complete)
@@ -218,6 +230,13 @@ static hipError_t memcpy_sync(vbmf_ctx* c, void* dst, const void* src, size_t n,
         hipError_t _e = (call);                                                                        \
         if (_e != hipSuccess) FAIL(ctx, VBMF_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), \
                                    __FILE__, __LINE__);                                                \
+    } while (0)
+
+// an acquire / regrow of the context's MemOwner or an alloc of a DevScratch
+#define MEMCHK(ctx, call)                                                                              \
+    do {                                                                                               \
+        int _m = (call);                                                                               \
+        if (_m != 0) FAIL(ctx, VBMF_ERR_HIP, "%s failed: %s (%s:%d)", #call, mem_errstr(_m), __FILE__, __LINE__); \
     } while (0)
 
 #define NCCLCHK(ctx, call)                                                                               \
@@ -1085,26 +1104,24 @@ static int gram_prepare(vbmf_ctx* c) {
         const size_t wrows = (size_t)32 * c->GT;
         // the zero fill goes on the context's stream: a hipMemset on the null stream is not ordered before the build kernel on this
         // non-blocking stream, and a fill still running over G's tail zeroed entries the build had already stored
-        auto alloc = [&](void** p, size_t bytes) -> hipError_t {
-            hipError_t e = hipMalloc(p, bytes);
-            if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, c->stream);
+        // all eight or none: a failure rolls the group back, so !c->Gt above stays the test for "not prepared"
+        const size_t group = c->mem.mark();
+        auto alloc = [&](auto*& slot, size_t bytes) -> int {
+            int e = c->mem.acquire(slot, bytes);
+            if (e == 0) e = (int)hipMemsetAsync(slot, 0, bytes, c->stream);
             return e;
         };
-        hipError_t e = alloc((void**)&c->Gt, (size_t)c->GT * KT * 64 * 8 * 4);
-        if (e == hipSuccess) e = alloc((void**)&c->W32g[0], wrows * c->Hp * 4);
-        if (e == hipSuccess) e = alloc((void**)&c->W32g[1], wrows * c->Hp * 4);
-        if (e == hipSuccess) e = alloc((void**)&c->Wt, (size_t)GRAM_PLANES * KT * c->NH * 64 * 16);
-        if (e == hipSuccess) e = alloc((void**)&c->gPQ, 2 * n * 4);
-        if (e == hipSuccess && c->g_nsplit > 1) e = alloc((void**)&c->gslabs, (size_t)c->g_nsplit * 2 * n * 4);
-        if (e == hipSuccess) e = alloc((void**)&c->g_part, (size_t)c->g_nchunk * (2 * (size_t)c->Hp * c->Hp + 2) * 8);   // (+2: the blocked share's trace slots)
-        if (e == hipSuccess) e = alloc((void**)&c->gsave, (2 * (size_t)c->Hp * c->Hp + 8) * 8);
-        if (e != hipSuccess) {
-            for (void* b : {(void*)c->Gt, (void*)c->W32g[0], (void*)c->W32g[1], (void*)c->Wt, (void*)c->gPQ, (void*)c->gslabs,
-                            (void*)c->g_part, (void*)c->gsave})
-                if (b) hipFree(b);
-            c->Gt = nullptr; c->W32g[0] = c->W32g[1] = nullptr; c->Wt = nullptr; c->gPQ = nullptr; c->gslabs = nullptr;
-            c->g_part = nullptr; c->gsave = nullptr;
-            FAIL(c, VBMF_ERR_HIP, "Gram-form sweep: device allocation failed (%s)", hipGetErrorString(e));
+        int e = alloc(c->Gt, (size_t)c->GT * KT * 64 * 8 * 4);
+        if (e == 0) e = alloc(c->W32g[0], wrows * c->Hp * 4);
+        if (e == 0) e = alloc(c->W32g[1], wrows * c->Hp * 4);
+        if (e == 0) e = alloc(c->Wt, (size_t)GRAM_PLANES * KT * c->NH * 64 * 16);
+        if (e == 0) e = alloc(c->gPQ, 2 * n * 4);
+        if (e == 0 && c->g_nsplit > 1) e = alloc(c->gslabs, (size_t)c->g_nsplit * 2 * n * 4);
+        if (e == 0) e = alloc(c->g_part, (size_t)c->g_nchunk * (2 * (size_t)c->Hp * c->Hp + 2) * 8);   // (+2: the blocked share's trace slots)
+        if (e == 0) e = alloc(c->gsave, (2 * (size_t)c->Hp * c->Hp + 8) * 8);
+        if (e != 0) {
+            c->mem.rollback(group);
+            FAIL(c, VBMF_ERR_HIP, "Gram-form sweep: device allocation failed (%s)", mem_errstr(e));
         }
         c->cache.G_buffers_new();
     }
@@ -1325,7 +1342,7 @@ struct RunFrame {
     double eps;
     int64_t* iters_done;
     double *d_last, *trace;
-    double* trace_dev = nullptr;
+    DevScratch<double> trace_dev;
     int64_t done = -1;                                     // sweeps the device executed (-1: not read back)
     // the Gram form: whether this run takes it, the B and W buffers it started from, and the sweeps enqueued
     // by the streaming path (Gram form: at most the first)
@@ -1333,8 +1350,6 @@ struct RunFrame {
     int bstart = 0, wstart = 0;
     int64_t stream_sweeps = 0;
 
-    ~RunFrame() { release(); }
-    void release() { if (trace_dev) hipFree(trace_dev); trace_dev = nullptr; }
     // the device, the state, the callers' defaults
     int open() {
         HIPCHK(c, hipSetDevice(c->o.device));
@@ -1368,7 +1383,7 @@ struct RunFrame {
     // the trace buffer, the loop counters {stop, iters, err, niter} and the ranks' summed error flag
     int arm() {
         if (trace) {
-            HIPCHK(c, hipMalloc((void**)&trace_dev, (size_t)niter * 4 * 8));
+            MEMCHK(c, trace_dev.alloc((size_t)niter * 4 * 8));
             HIPCHK(c, hipMemsetAsync(trace_dev, 0, (size_t)niter * 4 * 8, c->stream));
         }
         int init[4] = {0, 0, 0, (int)niter};
@@ -1443,7 +1458,7 @@ struct RunFrame {
         }
         int zero4[4] = {0, 0, 0, 0};
         memcpy_sync(c, c->ints, zero4, sizeof zero4, hipMemcpyHostToDevice);
-        release();
+        trace_dev.reset();
         if (c->sparse) c->cache.run_ended_sparse(c->diagvar);
         else c->cache.run_ended_basic();
         if (gram) {
@@ -1493,11 +1508,7 @@ int vbmf_destroy(vbmf_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     prof_harvest(c);
     if (c->comm) ncclCommDestroy(c->comm);
-    void* bufs[] = {c->sk_list, c->sk_tail, c->gw, c->hmean, c->fws, c->t2part, c->Y1, c->Y2, c->FA_alloc, c->FB_alloc, c->FD, c->SBf, c->P, c->Q, c->Pred, c->A32, c->B32[0], c->B32[1], c->SA32,
-                    c->SB32, c->gslab, c->st, c->gtmp, c->ypart, c->trpart, c->ints, c->mask, c->dS32, c->CA32, c->beta32, c->vtab,
-                    c->sigv, c->zetav, c->yrow, c->hpart, c->vsq, c->sig32, c->G32, c->FBs_alloc, c->gpart, c->fpart, c->bags, c->Gt, c->W32g[0], c->W32g[1], c->Wt, c->gslabs, c->gPQ,
-                    c->g_part, c->gsave};
-    for (void* b : bufs) if (b) hipFree(b);
+    c->mem.release_all();
     if (c->ints_host) hipHostFree(c->ints_host);
     if (c->loopw) hipHostFree(c->loopw);
     if (c->scal_host) hipHostFree(c->scal_host);
@@ -1611,12 +1622,12 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
     if ((int64_t)c->d1.KS * c->kstep < c->Lp || (int64_t)c->d2.KS * c->kstep < c->Mp) { c->err = "internal: tile plan"; return bail(VBMF_ERR_INVALID); }
     c->lay.Hp = c->Hp;
 
+    // (the fill runs on the null stream: see the hipDeviceSynchronize that closes this function)
 #define ALLOC(ptr, bytes)                                                                       \
     do {                                                                                        \
-        hipError_t _e = hipMalloc((void**)&(ptr), (bytes));                                     \
-        if (_e != hipSuccess) { c->err = std::string("hipMalloc failed for " #ptr ": ") + hipGetErrorString(_e); return bail(VBMF_ERR_HIP); } \
-        _e = hipMemset((ptr), 0, (bytes));                                                      \
-        if (_e != hipSuccess) { c->err = "hipMemset failed"; return bail(VBMF_ERR_HIP); }       \
+        const int _m = c->mem.acquire((ptr), (bytes));                                          \
+        if (_m != 0) { c->err = std::string("hipMalloc failed for " #ptr ": ") + mem_errstr(_m); return bail(VBMF_ERR_HIP); } \
+        if (hipMemset((ptr), 0, (bytes)) != hipSuccess) { c->err = "hipMemset failed"; return bail(VBMF_ERR_HIP); } \
     } while (0)
 
     const size_t slack = (size_t)PIPE_D * 64;
@@ -1740,15 +1751,41 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
     // large dynamic LDS (160 KiB per CU on gfx950) for the lambda_max kernel at 64 < H <= 128
     c->lds_limit = 160 * 1024 - 16384;         // leaves room for the kernels' static LDS (ctrl_end's tables: 8.4 KB)
     {
-        hipError_t e = hipFuncSetAttribute((const void*)eig_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        // 64 < H <= 128: the blocked inverse keeps the 128 x 130 fp64 image in LDS (133 KB)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ctrl_cov_kernel<8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ctrl_chain_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_cov_b_kernel<8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        // 128 < H <= 256: the register-resident blocked sweep's two panel strips (70 KB: above the 64 KB a launch may ask for unannounced)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ctrl_cov_kernel<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_cov_b_kernel<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_update_a_full256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+        const int lim = c->lds_limit, vb = (int)vbls_lds_bytes(4), fb = (int)FITB_LDS_CAP;
+        const struct { const void* kernel; int bytes; int nh; } big_lds[] = {        // nh: the context's NH the row applies to (0: any)
+            {(const void*)eig_kernel<8>, lim, 0},
+            // 64 < H <= 128: the blocked inverse keeps the 128 x 130 fp64 image in LDS (133 KB)
+            {(const void*)ctrl_cov_kernel<8, 16>, lim, 0},
+            {(const void*)ctrl_chain_kernel<8>, lim, 0},
+            {(const void*)sparse_cov_b_kernel<8, 16>, lim, 0},
+            // 128 < H <= 256: the register-resident blocked sweep's two panel strips (70 KB: above the 64 KB a launch may ask for unannounced)
+            {(const void*)ctrl_cov_kernel<8, 32>, lim, 0}, {(const void*)sparse_cov_b_kernel<8, 32>, lim, 0},
+            {(const void*)sparse_update_a_full256_kernel, lim, 0},
+            // vbls! as H x H algebra at 32 < H <= 64: four 64 x 66 fp64 images (135 KB)
+            {(const void*)vbls_loop_kernel<4>, vb, 0}, {(const void*)vbls_batch_kernel<4>, vb, 0},
+            // batched vbls! of the sparse models, full_cov at 32 < H <= 64: four 64 x 66 fp64 images and the bag's state
+            {(const void*)sparse_batch_kernel<4, true>, (int)SBATCH_LDS_BIG, 0},
+            // many fits in one launch: the images, the H x H matrices and a fit's state (fit_batch_kernels.hpp)
+            {(const void*)fit_batch_kernel<1, false>, fb, 0}, {(const void*)fit_batch_kernel<1, true>, fb, 0},
+            {(const void*)fit_batch_kernel<2, false>, fb, 0}, {(const void*)fit_batch_kernel<2, true>, fb, 0},
+            // ... and their three-group / masked twins (vbmf_local_fit_batched)
+            {(const void*)fit_batch_kernel<1, false, true>, fb, 0}, {(const void*)fit_batch_kernel<1, true, true>, fb, 0},
+            {(const void*)fit_batch_kernel<2, false, true>, fb, 0}, {(const void*)fit_batch_kernel<2, true, true>, fb, 0},
+            {(const void*)fit_basic_kernel<1>, fb, 0}, {(const void*)fit_basic_kernel<2>, fb, 0},
+            {(const void*)fit_basic_gram_kernel<1>, fb, 0}, {(const void*)fit_basic_gram_kernel<2>, fb, 0},
+            {(const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, LDS8_BYTES, 4},
+            {(const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, true>, LDS8_BYTES, 4},
+            {(const void*)stream_lds8_kernel<8, 0, false>, LDS8_BYTES, 8}, {(const void*)stream_lds8_kernel<8, 0, true>, LDS8_BYTES, 8},
+            // the Gram-form product's W / D plane buffers and G rings (148 / 144 / 144 KB at NH = 1 / 2 / 4)
+            {(const void*)gram_prod_kernel<1>, GramProd<1>::LDS_BYTES, 1},
+            {(const void*)gram_prod_kernel<2>, GramProd<2>::LDS_BYTES, 2},
+            {(const void*)gram_prod_kernel<4>, GramProd<4>::LDS_BYTES, 4},
+            {(const void*)gram_prod_kernel<4, 8>, GramProd<4>::LDS_BYTES, 8},          // rank 256: two h-tile groups of the NH = 4 geometry
+        };
+        hipError_t e = hipSuccess;
+        for (const auto& r : big_lds)
+            if (e == hipSuccess && (r.nh == 0 || r.nh == c->NH))
+                e = hipFuncSetAttribute(r.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, r.bytes);
         if (e == hipSuccess && c->NH == 4) {
             using Cfg = StreamCfg<4>;
             DISPATCH_MODE(c->mode, {
@@ -1756,42 +1793,6 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
                                         hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
             });
         }
-        // vbls! as H x H algebra at 32 < H <= 64: four 64 x 66 fp64 images (135 KB)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_loop_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vbls_batch_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vbls_lds_bytes(4));
-        // batched vbls! of the sparse models, full_cov at 32 < H <= 64: four 64 x 66 fp64 images and the bag's state
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sparse_batch_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SBATCH_LDS_BIG);
-        // many fits in one launch: the images, the H x H matrices and a fit's state (fit_batch_kernels.hpp)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        // ... and their three-group / masked twins (vbmf_local_fit_batched)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_batch_kernel<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_gram_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fit_basic_gram_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FITB_LDS_CAP);
-        if (e == hipSuccess && c->NH == 4)
-            e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-        if (e == hipSuccess && c->NH == 4)
-            e = hipFuncSetAttribute((const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-        if (e == hipSuccess && c->NH == 8)
-            e = hipFuncSetAttribute((const void*)stream_lds8_kernel<8, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-        if (e == hipSuccess && c->NH == 8)
-            e = hipFuncSetAttribute((const void*)stream_lds8_kernel<8, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-        // the Gram-form product's W / D plane buffers and G rings (148 / 144 / 144 KB at NH = 1 / 2 / 4)
-        if (e == hipSuccess && c->NH == 1)
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<1>::LDS_BYTES);
-        if (e == hipSuccess && c->NH == 2)
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<2>::LDS_BYTES);
-        if (e == hipSuccess && c->NH == 4)
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<4>::LDS_BYTES);
-        if (e == hipSuccess && c->NH == 8)          // rank 256: two h-tile groups of the NH = 4 geometry
-            e = hipFuncSetAttribute((const void*)gram_prod_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, GramProd<4>::LDS_BYTES);
         if (e != hipSuccess) { c->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return bail(VBMF_ERR_HIP); }
     }
     // the zero-fills above ran on the null stream; all later work runs on a non-blocking stream
@@ -1918,20 +1919,18 @@ int vbmf_set_Y(vbmf_ctx* c, const double* Y, int64_t ldY) {
     HIPCHK(c, hipMemsetAsync(tr, 0, sizeof(double), c->stream));
     int64_t mc = std::max<int64_t>(32, ((int64_t)(256ll << 20) / (c->L * 8)) / 32 * 32);
     mc = std::min<int64_t>(mc, rup(c->M, 32));
-    double* stage = nullptr;
-    HIPCHK(c, hipMalloc((void**)&stage, (size_t)c->L * mc * 8));
-    int rc = VBMF_OK;
-    for (int64_t m0 = 0; m0 < c->M && rc == VBMF_OK; m0 += mc) {
+    DevScratch<double> stage;
+    MEMCHK(c, stage.alloc((size_t)c->L * mc * 8));
+    for (int64_t m0 = 0; m0 < c->M; m0 += mc) {
         const int64_t m1 = std::min(c->M, m0 + mc);
-        hipError_t e = hipMemcpy2DAsync(stage, (size_t)c->L * 8, Y + m0 * ldY, (size_t)ldY * 8, (size_t)c->L * 8,
-                                        (size_t)(m1 - m0), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { c->err = std::string("hipMemcpy2DAsync: ") + hipGetErrorString(e); rc = VBMF_ERR_HIP; break; }
-        ColMajorF64Src src{stage, c->L, m0, m1 - m0, c->L, c->M};
-        rc = build_tiles(c, src, m0, m1, tr);
-        if (rc == VBMF_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed in vbmf_set_Y"; rc = VBMF_ERR_HIP; }
+        const hipError_t e = hipMemcpy2DAsync(stage, (size_t)c->L * 8, Y + m0 * ldY, (size_t)ldY * 8, (size_t)c->L * 8,
+                                              (size_t)(m1 - m0), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "hipMemcpy2DAsync: %s", hipGetErrorString(e));
+        ColMajorF64Src src{stage.get(), c->L, m0, m1 - m0, c->L, c->M};
+        TRY(build_tiles(c, src, m0, m1, tr));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) FAIL(c, VBMF_ERR_HIP, "sync failed in vbmf_set_Y");
     }
-    hipFree(stage);
-    if (rc != VBMF_OK) return rc;
+    stage.reset();                                     // (before finish_Y's launches, where it has always been freed)
     return finish_Y(c);
 }
 
@@ -1993,20 +1992,17 @@ int vbmf_set_Y_rows(vbmf_ctx* c, const void* src, int32_t dt, int32_t on_device,
         const bool rowmajor = cs == 1;
         int64_t rc = std::max<int64_t>(32, ((int64_t)(256ll << 20) / (c->M * (int64_t)es)) / 32 * 32);
         rc = std::min<int64_t>(rc, rup(nrows, 32));
-        void* stage = nullptr;
-        HIPCHK(c, hipMalloc(&stage, (size_t)rc * c->M * es));
-        int rcode = VBMF_OK;
-        for (int64_t r = 0; r < nrows && rcode == VBMF_OK; r += rc) {
+        DevScratch<void> stage;
+        MEMCHK(c, stage.alloc((size_t)rc * c->M * es));
+        for (int64_t r = 0; r < nrows; r += rc) {
             const int64_t n = std::min(rc, nrows - r);
             const char* from = (const char*)src + (size_t)r * rs * es;
-            hipError_t e = rowmajor ? hipMemcpy2DAsync(stage, (size_t)c->M * es, from, (size_t)rs * es, (size_t)c->M * es, (size_t)n, hipMemcpyHostToDevice, c->stream)
-                                    : hipMemcpy2DAsync(stage, (size_t)n * es, from, (size_t)cs * es, (size_t)n * es, (size_t)c->M, hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) { c->err = std::string("vbmf_set_Y_rows: hipMemcpy2DAsync: ") + hipGetErrorString(e); rcode = VBMF_ERR_HIP; break; }
-            rcode = rowmajor ? tile_rows_from(c, stage, dt, row0 + r, n, c->M, 1, tr) : tile_rows_from(c, stage, dt, row0 + r, n, 1, n, tr);
-            if (rcode == VBMF_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed in vbmf_set_Y_rows"; rcode = VBMF_ERR_HIP; }
+            const hipError_t e = rowmajor ? hipMemcpy2DAsync(stage, (size_t)c->M * es, from, (size_t)rs * es, (size_t)c->M * es, (size_t)n, hipMemcpyHostToDevice, c->stream)
+                                          : hipMemcpy2DAsync(stage, (size_t)n * es, from, (size_t)cs * es, (size_t)n * es, (size_t)c->M, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "vbmf_set_Y_rows: hipMemcpy2DAsync: %s", hipGetErrorString(e));
+            TRY(rowmajor ? tile_rows_from(c, stage, dt, row0 + r, n, c->M, 1, tr) : tile_rows_from(c, stage, dt, row0 + r, n, 1, n, tr));
+            if (hipStreamSynchronize(c->stream) != hipSuccess) FAIL(c, VBMF_ERR_HIP, "sync failed in vbmf_set_Y_rows");
         }
-        hipFree(stage);
-        if (rcode != VBMF_OK) return rcode;
     }
     HIPCHK(c, hipEventRecord(c->ev_y[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));        // the caller may reuse its buffer once this returns
@@ -2026,6 +2022,7 @@ struct vbmf_prep {
     long long* rows = nullptr;      // kept rows (device)
     std::vector<int64_t> rows_host;
     std::vector<double> mu_host, den_host;
+    MemOwner<HipMem> mem;           // owns Y, mu, den, rows (ctx_mem.hpp)
 };
 
 int vbmf_preprocess_open(vbmf_prep** out, int device, const double* Y, int64_t L, int64_t M, int64_t ldY, int64_t* L_used) {
@@ -2034,19 +2031,19 @@ int vbmf_preprocess_open(vbmf_prep** out, int device, const double* Y, int64_t L
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "vbmf_preprocess_open: bad device"; return VBMF_ERR_NO_DEVICE; }
     vbmf_prep* p = new vbmf_prep();
     p->device = device; p->L = L; p->M = M;
-    double* part = nullptr; unsigned char* keep = nullptr; double* rowsum = nullptr;
-    auto bail = [&](const char* what) { g_create_error = std::string("vbmf_preprocess_open: ") + what; hipFree(part); hipFree(keep); hipFree(rowsum);
-                                        hipFree(p->Y); hipFree(p->mu); hipFree(p->den); hipFree(p->rows); delete p; return VBMF_ERR_HIP; };
-    if (hipMalloc((void**)&p->Y, (size_t)L * M * 8) != hipSuccess) return bail("device allocation of the fp64 copy failed");
-    if (hipMalloc((void**)&p->mu, (size_t)L * 8) != hipSuccess || hipMalloc((void**)&p->den, (size_t)L * 8) != hipSuccess ||
-        hipMalloc((void**)&rowsum, (size_t)L * 8) != hipSuccess || hipMalloc((void**)&keep, (size_t)L) != hipSuccess ||
-        hipMalloc((void**)&part, (size_t)PREP_CHUNKS * L * 8) != hipSuccess) return bail("allocation failed");
+    DevScratch<double> part, rowsum;
+    DevScratch<unsigned char> keep;
+    auto bail = [&](const char* what) { g_create_error = std::string("vbmf_preprocess_open: ") + what; delete p; return VBMF_ERR_HIP; };
+    if (p->mem.acquire(p->Y, (size_t)L * M * 8) != 0) return bail("device allocation of the fp64 copy failed");
+    if (p->mem.acquire(p->mu, (size_t)L * 8) != 0 || p->mem.acquire(p->den, (size_t)L * 8) != 0 ||
+        rowsum.alloc((size_t)L * 8) != 0 || keep.alloc((size_t)L) != 0 ||
+        part.alloc((size_t)PREP_CHUNKS * L * 8) != 0) return bail("allocation failed");
     if (hipMemcpy2D(p->Y, (size_t)L * 8, Y, (size_t)ldY * 8, (size_t)L * 8, (size_t)M, hipMemcpyHostToDevice) != hipSuccess) return bail("upload failed");
     const dim3 g((unsigned)((L + 255) / 256), PREP_CHUNKS), gf((unsigned)((L + 255) / 256));
-    double* outs[3] = {p->mu, p->den, rowsum};
+    double* outs[3] = {p->mu, p->den, rowsum.get()};
     for (int what = 0; what < 3; ++what) {
-        hipLaunchKernelGGL(prep_row_partial_kernel, g, dim3(256), 0, 0, p->Y, (long long)L, (long long)M, (long long)L, what, p->mu, p->den, part);
-        hipLaunchKernelGGL(prep_row_fold_kernel, gf, dim3(256), 0, 0, part, (long long)L, (long long)M, what, outs[what], keep);
+        hipLaunchKernelGGL(prep_row_partial_kernel, g, dim3(256), 0, 0, p->Y, (long long)L, (long long)M, (long long)L, what, p->mu, p->den, part.get());
+        hipLaunchKernelGGL(prep_row_fold_kernel, gf, dim3(256), 0, 0, part.get(), (long long)L, (long long)M, what, outs[what], keep.get());
     }
     std::vector<unsigned char> kh((size_t)L);
     p->mu_host.resize((size_t)L); p->den_host.resize((size_t)L);
@@ -2055,10 +2052,10 @@ int vbmf_preprocess_open(vbmf_prep** out, int device, const double* Y, int64_t L
         hipMemcpy(p->den_host.data(), p->den, (size_t)L * 8, hipMemcpyDeviceToHost) != hipSuccess) return bail("statistics kernels failed");
     for (int64_t l = 0; l < L; ++l) if (kh[(size_t)l]) p->rows_host.push_back(l);
     p->L_used = (int64_t)p->rows_host.size();
-    if (hipMalloc((void**)&p->rows, std::max<size_t>(8, (size_t)p->L_used * 8)) != hipSuccess) return bail("allocation failed");
+    if (p->mem.acquire(p->rows, std::max<size_t>(8, (size_t)p->L_used * 8)) != 0) return bail("allocation failed");
     if (p->L_used && hipMemcpy(p->rows, p->rows_host.data(), (size_t)p->L_used * 8, hipMemcpyHostToDevice) != hipSuccess) return bail("upload failed");
     hipDeviceSynchronize();                         // (null-stream work above; the context that consumes p runs on its own stream)
-    hipFree(part); hipFree(keep); hipFree(rowsum);
+    part.reset(); keep.reset(); rowsum.reset();
     if (L_used) *L_used = p->L_used;
     *out = p;
     return VBMF_OK;
@@ -2075,7 +2072,7 @@ int vbmf_preprocess_rows(const vbmf_prep* p, int64_t* used_rows0, double* mu, do
 int vbmf_preprocess_close(vbmf_prep* p) {
     if (!p) return VBMF_ERR_INVALID;
     hipSetDevice(p->device);
-    hipFree(p->Y); hipFree(p->mu); hipFree(p->den); hipFree(p->rows);
+    p->mem.release_all();
     delete p;
     return VBMF_OK;
 }
@@ -2115,8 +2112,8 @@ int vbmf_get_Y(vbmf_ctx* c, double* Y, int64_t ldY, int64_t row0, int64_t nrows)
     // column chunks of a multiple of 32 (= whole k-steps of the pass-2 copy)
     int64_t mc = std::max<int64_t>(32, ((int64_t)(256ll << 20) / (nrows * 8)) / 32 * 32);
     mc = std::min<int64_t>(mc, rup(c->M, 32));
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc((void**)&tmp, (size_t)nrows * mc * 8));
+    DevScratch<double> tmp;
+    MEMCHK(c, tmp.alloc((size_t)nrows * mc * 8));
     for (int64_t m0 = 0; m0 < c->M; m0 += mc) {
         const int64_t m1 = std::min(c->M, m0 + mc);
         // shifting the tile pointer by whole k-steps makes the kernel's column 0 equal to column m0
@@ -2124,14 +2121,13 @@ int vbmf_get_Y(vbmf_ctx* c, double* Y, int64_t ldY, int64_t row0, int64_t nrows)
         DISPATCH_MODE(c->mode, {
             constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
             hipLaunchKernelGGL((untile_y_kernel<TM>), dim3(grid_for(nrows * (m1 - m0))), dim3(256), 0, c->stream, base,
-                               tmp, (long long)nrows, (long long)row0, (long long)nrows, (long long)(m1 - m0), c->d2.KS);
+                               tmp.get(), (long long)nrows, (long long)row0, (long long)nrows, (long long)(m1 - m0), c->d2.KS);
         });
         hipError_t e = hipMemcpy2DAsync(Y + m0 * ldY, (size_t)ldY * 8, tmp, (size_t)nrows * 8, (size_t)nrows * 8,
                                         (size_t)(m1 - m0), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { hipFree(tmp); FAIL(c, VBMF_ERR_HIP, "vbmf_get_Y copy failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "vbmf_get_Y copy failed: %s", hipGetErrorString(e));
     }
-    hipFree(tmp);
     return VBMF_OK;
 }
 
@@ -2148,28 +2144,26 @@ int vbmf_get_trYY(vbmf_ctx* c, double* trYY) {
 
 // ---- state -------------------------------------------------------------------------------------
 static int upload_factor(vbmf_ctx* c, const double* src, int64_t ld, int64_t X, int64_t Xp, float* dst) {
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc((void**)&tmp, (size_t)X * c->H * 8));
+    DevScratch<double> tmp;
+    MEMCHK(c, tmp.alloc((size_t)X * c->H * 8));
     hipError_t e = hipMemcpy2DAsync(tmp, (size_t)X * 8, src, (size_t)ld * 8, (size_t)X * 8, (size_t)c->H,
                                     hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pack_factor_kernel, dim3(grid_for(Xp * c->Hp)), dim3(256), 0, c->stream, tmp, (long long)X,
+        hipLaunchKernelGGL(pack_factor_kernel, dim3(grid_for(Xp * c->Hp)), dim3(256), 0, c->stream, tmp.get(), (long long)X,
                            (long long)X, (int)c->H, c->Hp, (long long)Xp, dst);
         e = hipStreamSynchronize(c->stream);
     }
-    hipFree(tmp);
     if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "factor upload failed: %s", hipGetErrorString(e));
     return VBMF_OK;
 }
 static int download_factor(vbmf_ctx* c, const float* src, int64_t X, double* dst, int64_t ld) {
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc((void**)&tmp, (size_t)X * c->H * 8));
+    DevScratch<double> tmp;
+    MEMCHK(c, tmp.alloc((size_t)X * c->H * 8));
     hipLaunchKernelGGL(unpack_factor_kernel, dim3(grid_for(X * c->H)), dim3(256), 0, c->stream, src, c->Hp, (long long)X,
-                       (int)c->H, tmp, (long long)X);
+                       (int)c->H, tmp.get(), (long long)X);
     hipError_t e = hipMemcpy2DAsync(dst, (size_t)ld * 8, tmp, (size_t)X * 8, (size_t)X * 8, (size_t)c->H,
                                     hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(tmp);
     if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "factor download failed: %s", hipGetErrorString(e));
     return VBMF_OK;
 }
@@ -2398,19 +2392,18 @@ int vbmf_get_YHat(vbmf_ctx* c, double* YHat, int64_t ld) {
     TRY(ensure_B(c));
     int64_t mc = std::max<int64_t>(1, (int64_t)(256ll << 20) / (c->L * 8));
     mc = std::min(mc, c->M);
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc((void**)&tmp, (size_t)c->L * mc * 8));
+    DevScratch<double> tmp;
+    MEMCHK(c, tmp.alloc((size_t)c->L * mc * 8));
     for (int64_t m0 = 0; m0 < c->M; m0 += mc) {
         const int64_t m1 = std::min(c->M, m0 + mc);
         hipLaunchKernelGGL(yhat_kernel, dim3(grid_for(c->L * (m1 - m0))), dim3(256), 0, c->stream, c->B32[c->bcur],
-                           c->A32 + (size_t)m0 * c->Hp, c->Hp, (int)c->H, (long long)c->L, (long long)(m1 - m0), tmp,
+                           c->A32 + (size_t)m0 * c->Hp, c->Hp, (int)c->H, (long long)c->L, (long long)(m1 - m0), tmp.get(),
                            (long long)c->L);
         hipError_t e = hipMemcpy2DAsync(YHat + m0 * ld, (size_t)ld * 8, tmp, (size_t)c->L * 8, (size_t)c->L * 8,
                                         (size_t)(m1 - m0), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { hipFree(tmp); FAIL(c, VBMF_ERR_HIP, "vbmf_get_YHat failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "vbmf_get_YHat failed: %s", hipGetErrorString(e));
     }
-    hipFree(tmp);
     return VBMF_OK;
 }
 
@@ -2908,7 +2901,7 @@ static int dual_update_priors(vbmf_ctx* c) {
 // t2_ahead: the shares of sum (GA + SA) o (GB + L SB) were left in c->t2part by launch_sparse_t2 (same stream, earlier)
 static int launch_sparse_t2(vbmf_ctx* c) {
     if (!c->t2part) {
-        HIPCHK(c, hipMalloc((void**)&c->t2part, T2_BLOCKS * 8));
+        MEMCHK(c, c->mem.acquire(c->t2part, T2_BLOCKS * 8));
         HIPCHK(c, hipMemsetAsync(c->t2part, 0, T2_BLOCKS * 8, ctrl_stream(c)));   // ordered before the kernel below
     }
     hipLaunchKernelGGL(sparse_t2_kernel, dim3(T2_BLOCKS), dim3(256), 0, ctrl_stream(c), c->st, c->lay, (int)c->H, (double)c->Lg, c->t2part, c->ints);
@@ -2958,26 +2951,24 @@ static int sparse_gram_sweep(vbmf_ctx* c) {
 }
 
 static int upload_vec(vbmf_ctx* c, const double* src, float* dst, float fill) {
-    double* tmp = nullptr;
+    DevScratch<double> tmp;
     const size_t n = (size_t)c->M * c->H;
-    HIPCHK(c, hipMalloc((void**)&tmp, n * 8));
+    MEMCHK(c, tmp.alloc(n * 8));
     hipError_t e = hipMemcpyAsync(tmp, src, n * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pack_vec_kernel, dim3(grid_for(c->Mp * c->Hp)), dim3(256), 0, c->stream, tmp, (long long)c->M, (int)c->H, c->Hp, (long long)c->Mp, dst, fill);
+        hipLaunchKernelGGL(pack_vec_kernel, dim3(grid_for(c->Mp * c->Hp)), dim3(256), 0, c->stream, tmp.get(), (long long)c->M, (int)c->H, c->Hp, (long long)c->Mp, dst, fill);
         e = hipStreamSynchronize(c->stream);
     }
-    hipFree(tmp);
     if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "vec upload failed: %s", hipGetErrorString(e));
     return VBMF_OK;
 }
 static int download_vec(vbmf_ctx* c, const float* src, double* dst) {
-    double* tmp = nullptr;
+    DevScratch<double> tmp;
     const size_t n = (size_t)c->M * c->H;
-    HIPCHK(c, hipMalloc((void**)&tmp, n * 8));
-    hipLaunchKernelGGL(unpack_vec_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, src, (long long)c->M, (int)c->H, c->Hp, tmp);
+    MEMCHK(c, tmp.alloc(n * 8));
+    hipLaunchKernelGGL(unpack_vec_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, c->stream, src, (long long)c->M, (int)c->H, c->Hp, tmp.get());
     hipError_t e = hipMemcpyAsync(dst, tmp, n * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(tmp);
     if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "vec download failed: %s", hipGetErrorString(e));
     return VBMF_OK;
 }
@@ -3197,14 +3188,20 @@ int vbmf_sparse_set_full_cov(vbmf_ctx* c, int on) {
     if (on && !c->fpart) {
         // two columns per round and workgroup (one for H > 64); H > 128: one 1024-thread workgroup per CU with its own workspace
         c->fblocks = (int)std::max<int64_t>(1, std::min<int64_t>(c->H > 64 ? c->M : (c->M + 1) / 2, c->H > 128 ? NUM_CU : 1024));
-        if (c->H > 128) HIPCHK(c, hipMalloc((void**)&c->fws, (size_t)c->fblocks * FULL256_WS * 8));
         const size_t bytes = (size_t)c->fblocks * c->Hp * c->Hp * 8;
-        HIPCHK(c, hipMalloc((void**)&c->fpart, bytes));
+        // fws and fpart are one group: a failure leaves both null, so the guard above never sees one without the other
+        const size_t group = c->mem.mark();
+        int e = c->H > 128 ? c->mem.acquire(c->fws, (size_t)c->fblocks * FULL256_WS * 8) : 0;
+        if (e == 0) e = c->mem.acquire(c->fpart, bytes);
+        if (e != 0) {
+            c->mem.rollback(group);
+            FAIL(c, VBMF_ERR_HIP, "vbmf_sparse_set_full_cov: device allocation failed (%s)", mem_errstr(e));
+        }
         HIPCHK(c, hipMemsetAsync(c->fpart, 0, bytes, c->stream));   // its kernels run on c->stream
     }
     if (on && c->diagvar && !c->gw) {
         const size_t bytes = (size_t)2 * c->Hp * c->Hp * 8;
-        HIPCHK(c, hipMalloc((void**)&c->gw, bytes));
+        MEMCHK(c, c->mem.acquire(c->gw, bytes));
         HIPCHK(c, hipMemsetAsync(c->gw, 0, bytes, c->stream));
     }
     c->full_cov = on != 0;
