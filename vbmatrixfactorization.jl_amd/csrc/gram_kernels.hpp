@@ -36,6 +36,10 @@ namespace vbmf {
 #define GRAM_CHUNK 256                 // k-steps (16 rows each) accumulated in fp32 before the fp64 fold: 4096 rows
 #endif
 constexpr int GRAM_PLANES = 5;         // W: 3 bf16 parts, D: 2 bf16 parts
+// gram_prod_kernel streams a G of more bytes than this past the caches ("G past the caches"): with the rest
+// of a sweep's traffic such a G no longer fits the 256 MiB Infinity Cache.  Measured at 100k rows, H = 64: the default policy is
+// 2.5-3.5 % ahead in sweeps/s at M = 4000 .. 7000 (G 67-206 MB), non-temporal pieces 1.7 % at M = 8000 (268 MB), 4 % at 10 000.
+constexpr long long GRAM_G_NT_BYTES = 240LL << 20;
 
 __device__ __forceinline__ unsigned pack_bf2(unsigned short lo, unsigned short hi) { return (unsigned)lo | ((unsigned)hi << 16); }
 
@@ -339,6 +343,26 @@ __device__ __forceinline__ f32x16 mfma_bf(const u32x4v& a, const u32x4v& b, cons
 // from every barrier on, 0.118-0.119 ms (0.205-0.206 ms); the k-step's DMA pieces issued between its MFMAs (sched_group_barrier,
 // one per two to six MFMAs) instead of ahead of them 0.119 ms (0.213-0.214 ms).  None of ring depth, barrier lockstep or the
 // place of the DMA issue is what bounds it now.
+// Cache policy.  G is read once per sweep, by one wave per fragment.  Where it is larger than the caches can keep from one sweep
+// to the next (GRAM_G_NT_BYTES), its pieces are non-temporal (lds_dma_piece_nt): the same bytes, which then do not push the
+// planes, the slabs and the other kernels' operands out of L2 and the Infinity Cache.  At the headline 4564-4580 -> 4745-4763
+// sweeps/s in a first alternated run, the kernel itself 117-118 -> 113 us (profiles/gram_prod_nt_*); a smaller G stays on the
+// default policy, under which the Infinity Cache serves it from the second sweep on.  The planes, which every workgroup
+// re-reads, always do.
+//
+// VBMF_GRAMPROD_PROBE (timing builds only, passed through VBMF_HIPCC_FLAGS; off by default: the shipped kernels execute nothing
+// extra).  A probe build's [P | Q] is wrong, so it never goes through the tests, and bench.py ends such a run after one sweep
+// (the stop test sees d = 0 or a non-finite value); scripts/gram_prod_probe_time.py launches the kernel for a kernel trace.
+//   1: G's descriptors get zero records, so the range check drops every G load (zeros arrive); the instruction stream, the waits
+//      and the barriers stay as they are.
+//   2: the loop issues no G piece; the ring keeps what the prologue loaded and the wait counts are those of the shorter queue.
+//   3: every G piece reads its row tile's first k-step (2 KB per tile, cache-resident): the stream of 1 on real operands, since
+//      all-zero operands alone let the chip hold a higher clock.
+// What the three decided (G's arrival from memory costs 11-12 us of 115, issuing its pieces 2-3): DESIGN.md section 10,
+// "Fourth form, not kept".
+#ifndef VBMF_GRAMPROD_PROBE
+#define VBMF_GRAMPROD_PROBE 0
+#endif
 template <int NH>
 struct GramProd {
     static constexpr int NW = 8;                              // waves per workgroup
@@ -353,6 +377,7 @@ struct GramProd {
     static constexpr int NP = GRAM_PLANES * CH * NH;          // 1 KB pieces of one plane chunk
     static constexpr int PPW = (NP + NW - 1) / NW;            // plane pieces a wave issues per chunk
     static constexpr int GL = 2 * NXW;                        // G pieces a wave issues per k-step
+    static constexpr int GQ = VBMF_GRAMPROD_PROBE == 2 ? 0 : GL;   // of them in the loop's queue
     static constexpr int PLANE_BYTES = 2 * NP * 1024;         // 20 / 80 / 80 KB
     static constexpr int RING_BYTES = NW * D * GL * 1024;     // 128 / 64 / 64 KB
     static constexpr int LDS_BYTES = PLANE_BYTES + RING_BYTES;
@@ -361,7 +386,7 @@ struct GramProd {
     // loads a wave has issued after the G pieces of k-step t (t mod U = u) by the time it reads them: the G refills of the D - 1
     // k-steps t - D + 1 .. t - 1 and the plane pieces issued at those of them that open a chunk
     static constexpr int g_wait(int u) {
-        int n = (D - 1) * GL;
+        int n = (D - 1) * GQ;
         for (int d = 1; d < D; ++d) n += ((u + CH * D - d) % CH == 0) ? PPW : 0;
         return n;
     }
@@ -399,16 +424,30 @@ __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const 
     __amdgpu_buffer_rsrc_t gr[NXW];
 #pragma unroll
     for (int i = 0; i < NXW; ++i)
-        gr[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(Gt + (long long)(pt0 + i) * KT * 128), 0, (unsigned)KT * 2048u, 0x00020000);
+        gr[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(Gt + (long long)(pt0 + i) * KT * 128), 0,
+                                                  VBMF_GRAMPROD_PROBE == 1 ? 0u : (unsigned)KT * 2048u, 0x00020000);
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)Wt, 0, (unsigned)(GRAM_PLANES * plane * 16), 0x00020000);
     const int voff = lane * 16;
     unsigned char* const ring = gram_lds + C::PLANE_BYTES + w * (D * GL * 1024);
+    // a G the caches cannot keep from one sweep to the next is streamed past them (non-temporal pieces): read once per sweep, it
+    // would only push out what the sweep's other kernels re-read.  One wave-uniform branch per k-step; the bytes are the same.
+    // Not at NH = 4 with one h-tile group (config 4): there the kernel itself measured 8 us slower with them (202 -> 210 us) and
+    // the sweep 0.7 % slower, so that instantiation keeps the default policy.
+    const bool g_nt = !(NH == 4 && NHT == 4) && (long long)GT * GT * 4096 > GRAM_G_NT_BYTES;
     auto load_g = [&](int slot, int t) __attribute__((always_inline)) {      // k-step j0 + t, clamped to the split
-        const int so = min(j0 + t, j1 - 1) * 2048;
+        const int so = VBMF_GRAMPROD_PROBE == 3 ? 0 : min(j0 + t, j1 - 1) * 2048;
+        if (g_nt) {
 #pragma unroll
-        for (int i = 0; i < NXW; ++i) {
-            lds_dma_piece(gr[i], ring + (slot * GL + 2 * i) * 1024, voff, so);
-            lds_dma_piece(gr[i], ring + (slot * GL + 2 * i + 1) * 1024, voff, so + 1024);
+            for (int i = 0; i < NXW; ++i) {
+                lds_dma_piece_nt(gr[i], ring + (slot * GL + 2 * i) * 1024, voff, so);
+                lds_dma_piece_nt(gr[i], ring + (slot * GL + 2 * i + 1) * 1024, voff, so + 1024);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NXW; ++i) {
+                lds_dma_piece(gr[i], ring + (slot * GL + 2 * i) * 1024, voff, so);
+                lds_dma_piece(gr[i], ring + (slot * GL + 2 * i + 1) * 1024, voff, so + 1024);
+            }
         }
     };
     // this wave's pieces of the plane chunk starting at k-step j0 + t into buffer cc: piece x = (plane q, k-step kk, h tile h)
@@ -480,14 +519,14 @@ __global__ __launch_bounds__(GramProd<NH>::THREADS) void gram_prod_kernel(const 
             // the slot is refilled only after its fragments have arrived in registers (the split has consumed them)
             __builtin_amdgcn_sched_barrier(0);
             if (kk == 0) load_planes(cc ^ 1, t + CH);
-            load_g(slot, t + D);
+            if (VBMF_GRAMPROD_PROBE != 2) load_g(slot, t + D);
             slot = slot + 1 == D ? 0 : slot + 1;
             __builtin_amdgcn_sched_barrier(0);
             if (live) mma();
             if (kk == CH - 1) {
                 // my pieces of the next chunk have landed (the G refills issued since stay in flight) and my reads of this chunk's
                 // buffer have returned; after the barrier everybody's have, and the next chunk's first k-step may refill the buffer
-                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(CH * GL) : "memory");
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(CH * C::GQ) : "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
