@@ -143,6 +143,54 @@ def test_run_three_sweeps(pkg, mode, L, M, H):
     assert relF(pg.YHat, po.BHat @ po.AHat.T) < 20 * tol["default"]
 
 
+# (mode, L, M, H, env, dims of the run: where the H x H control chain rides) -- one shape of test_run_three_sweeps per placement.
+# At 777 x 555 the planner takes the narrow geometry (both passes have two column groups of the wide one) and, forced wide, splits
+# pass 2 three ways: the register epilogue (un-split wide pass 2) is out of reach there, so a shape of test_gpu_stream_passes.py's
+# epilogue cases carries that placement.
+FLAGS_OFF = [("bf16x2", 777, 555, 64, {}, dict(NH=2)),                          # fused into the pass launches
+             ("bf16x2", 4097, 97, 64, {"VBMF_NARROW": "0"}, dict(NH=2, q_epi=1)),    # fused, pass 2 with the register epilogue
+             ("bf16x2", 1200, 900, 128, {}, dict(NH=4)),                        # fused at NH = 4
+             ("f32", 1000, 700, 200, {}, dict(NH=8))]                           # H > 128: stand-alone kernels on the side stream
+
+
+@pytest.mark.parametrize("est_covs,est_var", [(False, False), (True, False), (False, True)])
+@pytest.mark.parametrize("mode,L,M,H,env,exp", FLAGS_OFF, ids=[f"{c[0]}-{c[1]}x{c[2]}-H{c[3]}" for c in FLAGS_OFF])
+def test_flags_off_streaming(pkg, monkeypatch, mode, L, M, H, env, exp, est_covs, est_var):
+    """vbmf! with the reference's default flags (est_covs = est_var = false) and the mixed pairs on the streaming sweep
+    (VBMF_GRAM=0): what a flag switches off reads back bitwise as set, everything else follows the oracle run with the same flags
+    at the tolerance test_run_three_sweeps holds for the all-flags-on problem of that mode and shape."""
+    Y, po = _problem(L, M, H, 300 + H)
+    ydt, fdt, tol = _mode_opts(pkg, mode)
+    Ys = _stored(pkg, Y, H, ydt, fdt)
+    pg = to_pkg_params(pkg, po)
+    ca0, cb0, s20 = np.diag(po.CA).copy(), np.diag(po.CB).copy(), po.sigma2
+    env = dict({"VBMF_GRAM": "0"}, **env)                                 # (read when the context is created)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    s = pkg.Session(L, M, H, y_dtype=ydt, factor_dtype=fdt)
+    for k in env:
+        monkeypatch.delenv(k)
+    try:
+        s.set_Y(Ys)
+        s.push(pg)
+        it, d_gpu, _ = s.run(3, eps=0.0, est_covs=est_covs, est_var=est_var)
+        dims = s.ctx.dims()
+        st = s.ctx.get_state()
+        s.pull(pg)
+    finally:
+        s.close()
+    assert dims["gram"] == 0 and all(dims[k] == v for k, v in exp.items()), (dims, exp)
+    if not est_covs:
+        assert np.array_equal(st["CA_diag"], ca0) and np.array_equal(st["CB_diag"], cb0)
+    if not est_var:
+        assert st["sigma2"] == s20
+    _, n, d = O.vbmf_(Ys, po, 3, eps=0.0, est_covs=est_covs, est_var=est_var)
+    tol3 = {k: (v if k == "sigma2" else 2 * v) for k, v in tol.items()}          # (test_run_three_sweeps)
+    compare(f"flags off {mode} {L}x{M} H{H} covs={int(est_covs)} var={int(est_var)} run3", pg, po, tol3)
+    assert it == n == 3
+    assert abs(d_gpu - d) <= 5e-3 * d + D_ATOL, (d_gpu, d)
+
+
 @pytest.mark.parametrize("mode", ["f32", "bf16x2"])
 @pytest.mark.parametrize("L,M,H", [(10, 20, 2), (640, 384, 6), (900, 700, 12)])
 def test_run_trajectory_well_conditioned(pkg, mode, L, M, H):

@@ -111,8 +111,8 @@ def _state_block(c, cap, Hp):
 
 
 def _session(pkg, monkeypatch, L, M, H, mode, Y, state, env=None, splits=0, what="step"):
-    """One context: set Y and the state, then the update(s) `what` ("step": STEP_A, then STEP_B; "A": STEP_A only; "run":
-    run(1)); every buffer the checks need, read back."""
+    """One context: set Y and the state, then the update(s) `what` ("step": STEP_A, then STEP_B from the set state again; "chain":
+    STEP_A, then STEP_B on the A it left; "A": STEP_A only; "run": run(1)); every buffer the checks need, read back."""
     cap = pkg.capi
     env = dict({"VBMF_GRAM": "0"}, **(env or {}))
     for k, v in env.items():
@@ -149,7 +149,11 @@ def _session(pkg, monkeypatch, L, M, H, mode, Y, state, env=None, splits=0, what
             c.set_state(*state)
             c.step(cap.STEP_B)
             d = c.dims()
-        if what in ("step", "run"):
+        if what == "chain":
+            r["GA"] = _state_block(c, cap, Hp)[0]
+            c.step(cap.STEP_B)
+            d = c.dims()
+        if what in ("step", "chain", "run"):
             r["dB"] = d
             r["Q"] = None if d["q_epi"] else _product(c, cap, 1, d, nslab=1)[0]      # split: folded into slab 0
             r["B1"] = _f32(c, cap, cap.PEEK_B32, Lp * Hp).reshape(Lp, Hp)
@@ -276,6 +280,7 @@ def _expect(tag, d, exp):
 # (id, L, M, H, mode, env, pass1_splits, expected dims after STEP_A, expected dims after STEP_B)
 # L, M = 1 mod 32 (and 1 mod the ring depths 3 / 6 / 12 and the x groups of 128 / 256 / 512 / 1024 rows); H = 1 mod 32 or 32 n - 1.
 GT1 = lambda v: v > 1
+LONG = lambda v: v >= 2048                     # the side's 32-row tiles: launch_post_frag's NXT > 1, the long-side Gram chunks
 CASES = [
     # NH = 1 / 2, wide geometry, un-split pass 2: the register epilogue (no Q stored)
     ("f32-nh1-wide-epi", 150001, 33, 1, "f32", {"VBMF_NARROW": "0"}, 0, dict(NH=1, narrow=0, p_frag=1), dict(q_epi=1, nsplit2=1)),
@@ -317,6 +322,15 @@ CASES = [
     ("bf16x2-nh8-split1x5-noxcd", 3001, 225, 129, "bf16x2", {"VBMF_XCD_MAP": "0"}, 5, dict(nsplit1=5, xcd_map=0, lds8=1), dict()),
     # stream-K pieces and fix-up of the un-split Y*A pass (the shape of test_gpu_parity.py's stream-K test)
     ("bf16x2-streamk", 66001, 400, 140, "bf16x2", {"VBMF_STREAMK": "1"}, 0, dict(NH=8, lds8=1, streamk_per=GT1), dict(q_frag=1, nsplit2=1)),
+    # a long A side (M >= 65 536: 2051 tiles hold rows, XT1 = 2052 >= 2048 after rounding to the wave's tile count): the NXT > 1
+    # A-side instantiations of post_frag3 / post_frag2 (the AHEAD tails with BSIDE = false), the long-side Gram chunking of the A
+    # side, with a last wave and a last workgroup that are not full
+    ("bf16x2-nh4-longA-post3", 97, 65601, 128, "bf16x2", {}, 0, dict(NH=4, p_frag=1, post3=1, XT1=LONG), dict()),
+    ("bf16x2-nh4-longA-post2", 97, 65601, 128, "bf16x2", {"VBMF_POST3": "0"}, 0, dict(NH=4, p_frag=1, post3=0, XT1=LONG), dict()),
+    ("bf16x2-nh8-longA-post2", 97, 65601, 129, "bf16x2", {"VBMF_POST3": "0"}, 0, dict(NH=8, p_frag=1, post3=0, XT1=LONG), dict()),
+    ("bf16-nh4-longA", 97, 65601, 100, "bf16", {}, 0, dict(NH=4, p_frag=1, XT1=LONG), dict()),
+    ("bf16x2-nh2-longA", 97, 65601, 33, "bf16x2", {"VBMF_NARROW": "0"}, 0, dict(NH=2, XT1=LONG), dict()),
+    ("f32-nh4-longA", 97, 65601, 65, "f32", {}, 0, dict(NH=4, p_frag=0, XT1=LONG), dict()),
 ]
 
 
