@@ -227,6 +227,43 @@ int vbmf_run(vbmf_ctx* ctx, int64_t niter, double eps, int est_covs, int est_var
 
 /* updateYHat! (src/vbmf.jl:120-122) on demand: YHat = BHat*AHat' (L x M column-major). */
 int vbmf_get_YHat(vbmf_ctx* ctx, double* YHat, int64_t ld);
+/* updateYHat! (src/vbmf.jl:120-122) into memory the caller names -- the mirror of vbmf_set_Y_rows: host or device, the caller's dtype
+ * and strides, whole or in row blocks; no fp64 copy and no host round trip is made for a device dst.
+ *   what: VBMF_OUT_YHAT = BHat*AHat'; VBMF_OUT_RESIDUAL = Y as stored (what vbmf_get_Y returns) - BHat*AHat'.
+ *   dst: element (l, j) of the block, l in 0..nrows-1 (this rank's local rows row0 + l), j in 0..M-1, is dst[l*row_stride + j*col_stride];
+ *     strides count elements of dst_dtype (VBMF_DST_*).  Any row range inside L; no alignment is asked for.
+ *   Arithmetic, fixed per dst dtype and per entry -- an entry depends on row l of BHat and row j of AHat (the fp32 values vbmf_get_state
+ *     returns) and on Y[l, j] alone, never on row0, nrows, the strides or where dst lives:
+ *       VBMF_DST_F64   fp64 products and sums (v_mfma_f64_16x16x4_f64), as accurate as vbmf_get_YHat
+ *       VBMF_DST_F32   an fp32 fma chain in the order h = 0, 1, ... of exact fp32 products (v_mfma_f32_32x32x2_f32)
+ *       VBMF_DST_BF16  the round-to-nearest-even of the VBMF_DST_F32 value, bit for bit
+ *     and the residual is fl(y - s) in the accumulation type.
+ *   dst_on_device != 0: device memory on the context's device, any positive strides whose lines do not overlap.
+ *   dst_on_device == 0: host memory with row_stride = 1 or col_stride = 1; staged through a device buffer of the dst's OWN dtype in
+ *     chunks of at most 256 MB.
+ *   The entry runs on the context's stream and returns after that stream is idle.  After a Gram-form run the first call pays the owed
+ *   BHat once, as vbmf_get_state does; nothing else of the context's state or caches changes.
+ * VBMF_ERR_INVALID, in this order and before any launch, copy or materialisation of BHat, with the context and dst untouched: NULL dst;
+ * an unknown what or dtype; a non-positive stride; nrows < 1 or a row range outside 0..L; lines that overlap (neither row_stride >=
+ * (M-1)*col_stride + 1 nor col_stride >= (nrows-1)*row_stride + 1); a host dst with neither stride 1; a pointer whose kind contradicts
+ * dst_on_device or that lives on another device (hipPointerGetAttributes); a device extent [dst, dst + ((nrows-1)*row_stride +
+ * (M-1)*col_stride + 1) elements) that does not lie inside one allocation (hipMemGetAddressRange); then no state, and for
+ * VBMF_OUT_RESIDUAL no Y.  A wrong pointer comes back as an error code; no kernel writes it. */
+#define VBMF_DST_F64 0   /* same codes as VBMF_SRC_* */
+#define VBMF_DST_F32 1
+#define VBMF_DST_BF16 2
+#define VBMF_OUT_YHAT 0      /* BHat*AHat' */
+#define VBMF_OUT_RESIDUAL 1  /* Y as stored (what vbmf_get_Y returns) - BHat*AHat' */
+int vbmf_get_YHat_rows(vbmf_ctx* ctx, int32_t what, void* dst, int32_t dst_dtype, int32_t dst_on_device,
+                       int64_t row0, int64_t nrows, int64_t row_stride, int64_t col_stride);
+/* The factors of updateYHat! (src/vbmf.jl:120-122) the same way: rows row0 .. row0+nrows-1 of AHat (M x H; ATVecHat as a matrix for
+ * the sparse family) or of this rank's BHat (L x H), element (x, h) at dst[x*row_stride + h*col_stride].  The values are exactly the
+ * fp32 ones vbmf_get_state / vbmf_sparse_get_state return: VBMF_DST_F32 is a copy, VBMF_DST_F64 a widening, VBMF_DST_BF16 one
+ * round-to-nearest-even.  dst, the validation (with H columns in place of M) and the owed BHat as for vbmf_get_YHat_rows. */
+#define VBMF_FACTOR_A 0      /* M x H */
+#define VBMF_FACTOR_B 1      /* this rank's L x H */
+int vbmf_get_factor_rows(vbmf_ctx* ctx, int32_t which, void* dst, int32_t dst_dtype, int32_t dst_on_device,
+                         int64_t row0, int64_t nrows, int64_t row_stride, int64_t col_stride);
 /* Build-defined ELBO of the basic model (the reference has none). */
 int vbmf_elbo(vbmf_ctx* ctx, double* elbo);
 
@@ -508,7 +545,7 @@ int vbmf_device_sync(vbmf_ctx* ctx);
 #define VBMF_PEEK_FB 5     /* BHat MFMA operand tiles */
 #define VBMF_PEEK_Y1 6     /* Y tiled for pass 1 */
 #define VBMF_PEEK_Y2 7     /* Y tiled for pass 2 */
-#define VBMF_PEEK_DIMS 8   /* int32 x 30: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run / vbmf_sparse_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
+#define VBMF_PEEK_DIMS 8   /* int32 x 31: Hp, NH, mode, XT1, KS1, nsplit1, sps1, XT2, KS2, nsplit2, sps2, kstep, npart, narrow, streamk_per, streamk_grid, gram (vbmf_run / vbmf_sparse_run takes the Gram form), gram_built, gram_build_us, gram_nsplit,
                               p_frag / q_frag (the last pass 1 / pass 2 launch wrote its product fragment-major: [XT][NH][64][16]),
                               q_epi (the last pass 2 launch ran the register epilogue and stored no product), lds8 (H >= 128 bf16x2
                               passes run the LDS-DMA kernel), xcd_map (split-K launches use the XCD-aware work map), post3 (H >= 128
@@ -516,7 +553,8 @@ int vbmf_device_sync(vbmf_ctx* ctx);
                               operand tiles itself, VBMF_SPARSE_A_FUSED), set_y_rows_us (device time of the last vbmf_set_Y_rows call
                               between two HIP events on the context's stream: staged copies, tiling kernels, ||Y||^2),
                               b_pending (a Gram-form run has ended and BHat of its last sweep is not materialised yet: the first
-                              reader of B pays one streaming pass), b_materialised (how often that pass has run on demand).
+                              reader of B pays one streaming pass), b_materialised (how often that pass has run on demand), out_rows_us (device time of the last
+                              vbmf_get_YHat_rows / vbmf_get_factor_rows call between two HIP events on the context's stream: kernels, staged copies).
                               This peek never materialises B; every other one does, and shows its buffer as a run's end left it */
 #define VBMF_PEEK_CHAIN 9  /* uint64 x 8 (16 words): last durations in 10 ns ticks of the in-launch control chain's parts
                               (ctrl_end, SigmaA, lambda_max(dB'dB) + loop test, SigmaB) and of the register epilogue's tail in

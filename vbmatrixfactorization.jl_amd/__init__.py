@@ -199,8 +199,86 @@ class Session:
     def run(self, niter, eps=1e-6, est_covs=False, est_var=False, want_trace=False):
         return self.ctx.run(niter, eps=eps, est_covs=est_covs, est_var=est_var, want_trace=want_trace)
 
+    # -- results where the caller wants them (vbmf_get_YHat_rows / vbmf_get_factor_rows: no fp64 host round trip) --
+    def yhat(self, out=None, dtype=None, device=None, residual=False):
+        """BHat*AHat' of the state on the device (residual=True: Y as stored minus it), written into `out` as it lies -- a writable
+        NumPy array or a torch tensor, see capi.y_sink -- or, without one, into a fresh result (_alloc_out): a torch tensor on this
+        session's GPU when `device` asks for it, else a NumPy array.  Returns the result."""
+        out = _out_or_new(out, (self.L, self.M), dtype, device, self.ctx.device)
+        return self.ctx.YHat_into(out, 0, self.L, residual=residual)
+
+    def yhat_rows(self, out, row0, residual=False):
+        """Rows row0 .. row0 + out.shape[0] - 1 of the same result into `out`: a matrix that never exists whole leaves in blocks, as
+        it came (set_Y_rows); any row range, no alignment."""
+        return self.ctx.YHat_into(out, int(row0), None, residual=residual)
+
+    def factors(self, out_A=None, out_B=None, dtype=None, device=None):
+        """(AHat M x H, BHat L x H): the fp32 values pull() widens, each into `out_*` if given, else into a fresh result allocated as
+        yhat allocates its own."""
+        A = _out_or_new(out_A, (self.M, self.H), dtype, device, self.ctx.device)
+        B = _out_or_new(out_B, (self.L, self.H), dtype, device, self.ctx.device)
+        return self.ctx.factor_into("A", A), self.ctx.factor_into("B", B)
+
     def close(self):
         self.ctx.close()
+
+
+def _is_torch_dtype(dtype):
+    return type(dtype).__module__.split(".")[0] == "torch"
+
+
+def _alloc_out(shape, dtype, device, gpu):
+    """A fresh result for Session.yhat / Session.factors.  device None / False / "cpu": host memory -- a column-major NumPy array
+    (float64 unless dtype says float32), or a CPU torch tensor when dtype is a torch dtype (bfloat16 has no NumPy twin).  device True /
+    "cuda" / an index / a torch.device: a torch tensor on the session's GPU `gpu` (float32 unless dtype says otherwise; any other GPU
+    is refused).  dtype: float64, float32 (NumPy or torch) or torch.bfloat16; anything else raises TypeError."""
+    want_gpu = not (device is None or device is False or (isinstance(device, str) and device == "cpu"))
+    if want_gpu or _is_torch_dtype(dtype):
+        import torch
+        if dtype is None:
+            td = torch.float32
+        elif _is_torch_dtype(dtype):
+            td = dtype
+        else:
+            td = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32}.get(np.dtype(dtype))
+        if td not in (torch.float64, torch.float32, torch.bfloat16):
+            raise TypeError(f"the output must be float64, float32 or bfloat16, got {dtype}")
+        if not want_gpu:
+            return torch.empty(tuple(shape), dtype=td)
+        if device is True:
+            idx = gpu
+        elif isinstance(device, int):
+            idx = device
+        else:
+            dev = torch.device(device)
+            if dev.type != "cuda":
+                raise ValueError(f"device = {device!r}: a result lives on the CPU or on the session's GPU")
+            idx = gpu if dev.index is None else dev.index
+        if idx != gpu:
+            raise ValueError(f"device = {device!r}, the session lives on GPU {gpu}")
+        return torch.empty(tuple(shape), dtype=td, device=f"cuda:{gpu}")
+    nd = np.dtype(np.float64 if dtype is None else dtype)
+    if nd not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise TypeError(f"the output must be float64 or float32, got {nd}")
+    return np.empty(tuple(shape), dtype=nd, order="F")
+
+
+def _out_or_new(out, shape, dtype, device, gpu):
+    """`out` itself (its dtype must be the one asked for, if any was), or a fresh result of _alloc_out."""
+    if out is None:
+        return _alloc_out(shape, dtype, device, gpu)
+    if dtype is not None:
+        if capi._is_tensor(out):
+            same = out.dtype == dtype if _is_torch_dtype(dtype) else str(out.dtype) == "torch." + np.dtype(dtype).name
+        else:
+            same = not _is_torch_dtype(dtype) and getattr(out, "dtype", None) == np.dtype(dtype)
+        if not same:
+            raise TypeError(f"out is {getattr(out, 'dtype', type(out).__name__)}, dtype asks for {dtype}")
+    return out
+
+
+def _wants_gpu(Y):
+    return capi._is_tensor(Y) and bool(Y.is_cuda)
 
 
 # ---- cached sessions keyed on the caller's Y array ------------------------------------------------
@@ -359,11 +437,22 @@ def updateSigma2_(Y, params):
     _one(Y, params, STEP_SIGMA2, False)
 
 
-def updateYHat_(params, Y=None):
-    """updateYHat! -- src/vbmf.jl:120-122 (device GEMM, fp64 out): the reference's signature, no Y."""
+def updateYHat_(params, Y=None, out=None, dtype=None, residual=False):
+    """updateYHat! -- src/vbmf.jl:120-122 (device GEMM, fp64 out): the reference's signature, no Y.
+    out / dtype / residual (extensions): the product goes through vbmf_get_YHat_rows into `out` as it lies (a writable NumPy array or
+    a torch tensor, CPU or the session's GPU), or into a fresh result of `dtype` -- a GPU tensor when Y is one, else host memory --
+    and params.YHat is bound to it; residual=True gives Y as stored minus the product and needs Y.  Without them: the fp64 host
+    array, as before."""
+    if out is None and dtype is None and not residual:
+        s = _session_for_params(params) if Y is None else _session_for(Y, params.H)
+        s.push(params)
+        params.YHat = s.ctx.YHat()
+        return
+    if residual and Y is None:
+        raise ValueError("updateYHat_: residual=True needs Y")
     s = _session_for_params(params) if Y is None else _session_for(Y, params.H)
     s.push(params)
-    params.YHat = s.ctx.YHat()
+    params.YHat = s.yhat(out=out, dtype=dtype, device=_wants_gpu(Y), residual=residual)
 
 
 def elbo(Y, params):
@@ -686,11 +775,19 @@ def _step(Y, p, which, diag_var=False, full_cov=False):
 
 
 def _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors=True, form=None,
-              fn="vbmf_sparse_"):
-    """vbmf_sparse! / vbmf_dual! / vbmf_trial!: returns d (like the reference).  form: see vbmf_sparse_."""
+              fn="vbmf_sparse_", out=None, dtype=None):
+    """vbmf_sparse! / vbmf_dual! / vbmf_trial!: returns d (like the reference).  form: see vbmf_sparse_.  out / dtype: params.YHat
+    from the device (_ard_YHat), at any size; default: the host product up to YHAT_AUTO_LIMIT elements."""
     c, m = _pushed(Y, params, diag_var, full_cov)
     _apply_form(c, form, fn, lambda: _gram_refusal(params.H, sparse=True, grouped=m.set_priors is not None, diag_var=diag_var,
                                                    full_cov=full_cov))
+    if out is not None or dtype is not None:
+        if out is not None:
+            _out_or_new(out, (params.L, params.M), dtype, None, c.device)        # an out of another dtype is refused before the run
+        d = _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run=lambda k: m.run(c, k, eps, est_cb, est_priors),
+                 pull=lambda: _pull(c, params, m, diag_var), yhat=lambda: None)
+        params.YHat = _ard_YHat(c, params, out, dtype)
+        return d
     return _fit(Y, params, niter, eps, logdir, desc, verb, log_every, run=lambda k: m.run(c, k, eps, est_cb, est_priors),
                 pull=lambda: _pull(c, params, m, diag_var), yhat=lambda: params.BHat @ params.AHat.T)   # host, small problems only
 
@@ -708,6 +805,14 @@ def _lower_bound(Y, p, clamp, trim=None):
 
 def _host_YHat(p):
     return p.BHat @ p.AHat.T if p.L * p.M <= YHAT_AUTO_LIMIT else None
+
+
+def _ard_YHat(c, p, out, dtype):
+    """YHat of an ARD-family shell: the host product (the default), or -- only when out / dtype ask for it -- the device product
+    of context c through vbmf_get_YHat_rows, into `out` as it lies or into a fresh host result of `dtype`."""
+    if out is None and dtype is None:
+        return _host_YHat(p)
+    return c.YHat_into(_out_or_new(out, (p.L, p.M), dtype, None, c.device), 0, p.L)
 
 
 def sparse_updateA_(Y, params, full_cov=False, diag_var=False):
@@ -737,13 +842,13 @@ def sparse_updateSigma_(Y, params, diag_var=False):
 
 
 def vbmf_sparse_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_cb=True,
-                 log_every=1, form=None):
-    """vbmf_sparse! -- src/vbmf_sparse.jl:344-410.  Returns d (like the reference).  logdir: see vbmf_.
+                 log_every=1, form=None, out=None, dtype=None):
+    """vbmf_sparse! -- src/vbmf_sparse.jl:344-410.  Returns d (like the reference).  logdir: see vbmf_.  out / dtype: see _vbmf_ard.
     form: None (the library's rule: VBMF_GRAM, then the size rule, which never takes the Gram form at H > 128), "stream", or "gram":
     iterate on Y'Y at any size and up to H = 256.  "gram" raises ValueError naming the reason where the
     context cannot take the form: fp32 storage (the default here: set_defaults(y_dtype=VBMF_Y_BF16)), the single-bf16 factor,
     diag_var, full_cov, H > 256."""
-    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, form=form)
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, form=form, out=out, dtype=dtype)
 
 
 def vbmf_sparse(Y, params_in, niter, **kw):
@@ -871,9 +976,9 @@ def dual_updateCA_and_priors_(params, Y=None):
 
 
 def vbmf_dual_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_priors=True,
-               est_cb=True, log_every=1):
-    """vbmf_dual! -- src/vbmf_dual.jl:455-530.  Returns d (like the reference).  logdir: see vbmf_."""
-    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors)
+               est_cb=True, log_every=1, out=None, dtype=None):
+    """vbmf_dual! -- src/vbmf_dual.jl:455-530.  Returns d (like the reference).  logdir: see vbmf_.  out / dtype: see _vbmf_ard."""
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors, out=out, dtype=dtype)
 
 
 def vbmf_dual(Y, params_in, niter, **kw):
@@ -1003,9 +1108,9 @@ def trial_updateCA_and_priors_(params, Y=None):
 
 
 def vbmf_trial_(Y, params, niter, eps=1e-6, diag_var=False, full_cov=False, logdir="", desc="", verb=False, est_priors=True,
-                est_cb=True, log_every=1):
-    """vbmf_trial! -- src/vbmf_trial.jl:528-604.  Returns d (like the reference).  logdir: see vbmf_."""
-    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors)
+                est_cb=True, log_every=1, out=None, dtype=None):
+    """vbmf_trial! -- src/vbmf_trial.jl:528-604.  Returns d (like the reference).  logdir: see vbmf_.  out / dtype: see _vbmf_ard."""
+    return _vbmf_ard(Y, params, niter, eps, diag_var, full_cov, logdir, desc, verb, est_cb, log_every, est_priors, out=out, dtype=dtype)
 
 
 def vbmf_trial(Y, params_in, niter, **kw):
@@ -1059,15 +1164,16 @@ _MODELS = {
 # update functions outside vbmf!/vbmf_sparse! (150 resp. 20 iterations per bag in the MIL study,
 # examples/mil_util.jl:473-479,518-521)
 # =================================================================================================
-def vbls_(Y, params, niter, diag_var=False, full_cov=False):
+def vbls_(Y, params, niter, diag_var=False, full_cov=False, out=None, dtype=None):
     """vbls! -- examples/mil_util.jl:179-203: solves Y = B A' + E for A with B (and SigmaB, CB) fixed: niter x
     (updateA!, updateCA!, updateSigma2! / updateSigma!), then updateYHat!; returns params.AHat.
-    On the device Y'B is formed once per call (B is fixed), so the call reads Y once, not 2 x niter times."""
+    On the device Y'B is formed once per call (B is fixed), so the call reads Y once, not 2 x niter times.
+    out / dtype: params.YHat from the device through vbmf_get_YHat_rows (see updateYHat_), at any size; default: as before."""
     if type(params) in _MODELS:                                          # examples/mil_util.jl:187-197
         c, m = _pushed(Y, params, diag_var, full_cov)
         c.sparse_run_fixed_basis(int(niter))
         _pull(c, params, m, diag_var)
-        params.YHat = _host_YHat(params)
+        params.YHat = _ard_YHat(c, params, out, dtype)
         return params.AHat
     _check_full_cov(full_cov, diag_var, params.H)
     _check(Y, params)
@@ -1075,6 +1181,9 @@ def vbls_(Y, params, niter, diag_var=False, full_cov=False):
     s.push(params)
     s.ctx.run_fixed_basis(int(niter))
     s.pull(params)
+    if out is not None or dtype is not None:
+        params.YHat = s.yhat(out=out, dtype=dtype, device=_wants_gpu(Y))
+        return params.AHat
     params.YHat = s.ctx.YHat() if params.L * params.M <= YHAT_AUTO_LIMIT else None     # :201
     return params.AHat
 

@@ -18,6 +18,9 @@ if os.environ.get("VBMF_HIP_LIB") and not os.path.isfile(LIB_PATH):
 
 VBMF_Y_F32, VBMF_Y_BF16 = 0, 1
 VBMF_SRC_F64, VBMF_SRC_F32, VBMF_SRC_BF16 = 0, 1, 2      # src_dtype of vbmf_set_Y_rows
+VBMF_DST_F64, VBMF_DST_F32, VBMF_DST_BF16 = 0, 1, 2      # dst_dtype of vbmf_get_YHat_rows / vbmf_get_factor_rows
+VBMF_OUT_YHAT, VBMF_OUT_RESIDUAL = 0, 1                  # `what` of vbmf_get_YHat_rows
+VBMF_FACTOR_A, VBMF_FACTOR_B = 0, 1                      # `which` of vbmf_get_factor_rows
 VBMF_FACTOR_AUTO, VBMF_FACTOR_BF16, VBMF_FACTOR_BF16X2 = 0, 1, 2
 VBMF_FACTOR_BF16_MAX_H = 128      # vbmf_create refuses the single-bf16 factor operand above this rank (include/vbmf_hip.h)
 VBMF_VARIANT_BASIC, VBMF_VARIANT_SPARSE_DIAG, VBMF_VARIANT_SPARSE_DIAGVAR, VBMF_VARIANT_DUAL_DIAG, VBMF_VARIANT_TRIAL_DIAG = 0, 1, 2, 3, 4
@@ -67,6 +70,7 @@ SYMBOLS = [
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
     "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_set_gram_form",
+    "vbmf_get_YHat_rows", "vbmf_get_factor_rows",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
@@ -149,6 +153,8 @@ def lib():
     L.vbmf_local_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64,
                                           C.POINTER(i64), i64] + [dp] * 16 + [C.POINTER(i64), dp, C.POINTER(i64), dp])
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
+    L.vbmf_get_YHat_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
+    L.vbmf_get_factor_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
     L.vbmf_elbo.argtypes = [vp, dp]
     L.vbmf_comm_unique_id.argtypes = [vp]
     L.vbmf_comm_init.argtypes = [vp, vp]
@@ -250,6 +256,55 @@ def y_source(src, device=0):
         a = np.ascontiguousarray(a)                                     # one copy, in its own dtype
         st = _unit(a.shape, tuple(x // es for x in a.strides))
     return a, a.ctypes.data, VBMF_SRC_F64 if a.dtype == np.float64 else VBMF_SRC_F32, 0, st[0], st[1]
+
+
+def y_sink(dst, device=0):
+    """What vbmf_get_YHat_rows / vbmf_get_factor_rows need to write into `dst` where it lies -- the counterpart of y_source:
+    (target, address, VBMF_DST_*, on_device, row_stride, col_stride, finish), strides in elements.  `target` owns the memory the library
+    writes for the duration of the call; `finish` is None, or -- for a host view with no unit stride, which is filled through one
+    contiguous temporary of its own dtype -- the call that assigns the temporary back into dst afterwards.  Accepted: a writable
+    float64 / float32 NumPy array; a torch tensor (float64, float32, bfloat16) on the CPU or on the GPU with index `device`, whose
+    current stream is synchronised first.  Raises TypeError / ValueError, before the library is touched, on a read-only array, any other
+    dtype, anything that is not a matrix, another GPU and an expanded (stride-0) tensor."""
+    if _is_tensor(dst):
+        import torch
+        codes = {torch.float64: VBMF_DST_F64, torch.float32: VBMF_DST_F32, torch.bfloat16: VBMF_DST_BF16}
+        if dst.dtype not in codes:
+            raise TypeError(f"the output must be float64, float32 or bfloat16, got {dst.dtype}")
+        if dst.dim() != 2:
+            raise ValueError("the output must be a matrix")
+        if dst.is_cuda:
+            if dst.device.index != device:
+                raise ValueError(f"the output lives on {dst.device}, the context on GPU {device}")
+        elif dst.device.type != "cpu":
+            raise ValueError(f"the output lives on {dst.device}: only CPU and GPU tensors can be written")
+        if any(n > 1 and st == 0 for n, st in zip(dst.shape, dst.stride())):
+            raise ValueError("the output is an expanded (stride-0) tensor: its entries share memory")
+        if dst.is_cuda:
+            torch.cuda.current_stream(dst.device).synchronize()         # whatever still reads or writes the tensor has finished
+        rs, cs = _unit(dst.shape, dst.stride())
+        if not dst.is_cuda and 1 not in (rs, cs):
+            tmp = torch.empty(tuple(dst.shape), dtype=dst.dtype)
+            return tmp, tmp.data_ptr(), codes[dst.dtype], 0, *_unit(tmp.shape, tmp.stride()), (lambda: dst.copy_(tmp))
+        return dst, dst.data_ptr(), codes[dst.dtype], int(dst.is_cuda), rs, cs, None
+    if not isinstance(dst, np.ndarray):
+        raise TypeError(f"the output must be a NumPy array or a torch tensor, got {type(dst).__name__}")
+    if dst.dtype not in (np.float64, np.float32):
+        raise TypeError(f"the output must be float64 or float32, got {dst.dtype}")
+    if dst.ndim != 2:
+        raise ValueError("the output must be a matrix")
+    if not dst.flags.writeable:
+        raise ValueError("the output array is read-only")
+    es = dst.itemsize
+    code = VBMF_DST_F64 if dst.dtype == np.float64 else VBMF_DST_F32
+    st = _unit(dst.shape, tuple(x // es if x % es == 0 else 0 for x in dst.strides))
+    if min(st) <= 0 or 1 not in st:
+        tmp = np.empty(dst.shape, dtype=dst.dtype)
+
+        def finish():
+            dst[...] = tmp
+        return tmp, tmp.ctypes.data, code, 0, *_unit(tmp.shape, tuple(x // es for x in tmp.strides)), finish
+    return dst, dst.ctypes.data, code, 0, st[0], st[1], None
 
 
 def _unit(shape, strides):
@@ -594,6 +649,44 @@ class Context:
         self._chk(self._lib.vbmf_get_YHat(self._h, _dptr(out), self.L))
         return out
 
+    def _block(self, dst, row0, nrows, rows_total, ncols):
+        shape = tuple(dst.shape) if hasattr(dst, "shape") else ()
+        if len(shape) != 2:
+            raise ValueError("the output must be a matrix")
+        n = shape[0] if nrows is None else int(nrows)
+        if shape != (n, ncols):
+            raise ValueError(f"expected an output of shape ({n}, {ncols}), got {shape}")
+        if row0 < 0 or n < 1 or row0 + n > rows_total:
+            raise ValueError(f"rows [{row0}, {row0 + n}) do not lie in a matrix of {rows_total} rows")
+        return n
+
+    def YHat_into(self, dst, row0=0, nrows=None, residual=False):
+        """Rows [row0, row0 + nrows) of BHat*AHat' -- or, residual=True, of Y as stored minus it -- written into `dst` as it lies
+        (vbmf_get_YHat_rows): a writable float64 / float32 NumPy array or a torch tensor (float64, float32, bfloat16; CPU or this
+        context's GPU), see y_sink.  nrows defaults to dst's rows.  Returns dst."""
+        n = self._block(dst, row0, nrows, self.L, self.M)
+        keep, addr, code, on_dev, rs, cs, finish = y_sink(dst, self.device)
+        self._chk(self._lib.vbmf_get_YHat_rows(self._h, VBMF_OUT_RESIDUAL if residual else VBMF_OUT_YHAT, addr, code, on_dev, int(row0), n,
+                                               rs, cs))
+        if finish is not None:
+            finish()
+        del keep
+        return dst
+
+    def factor_into(self, which, dst, row0=0, nrows=None):
+        """Rows [row0, row0 + nrows) of AHat (which = "A" / VBMF_FACTOR_A: M x H) or of this rank's BHat ("B" / VBMF_FACTOR_B: L x H),
+        the fp32 values get_state returns, written into `dst` as it lies (vbmf_get_factor_rows; dst as for YHat_into).  Returns dst."""
+        w = {"A": VBMF_FACTOR_A, "B": VBMF_FACTOR_B}.get(which, which)
+        if w not in (VBMF_FACTOR_A, VBMF_FACTOR_B):
+            raise ValueError(f"which = {which!r} ('A' or 'B')")
+        n = self._block(dst, row0, nrows, self.M if w == VBMF_FACTOR_A else self.L, self.H)
+        keep, addr, code, on_dev, rs, cs, finish = y_sink(dst, self.device)
+        self._chk(self._lib.vbmf_get_factor_rows(self._h, w, addr, code, on_dev, int(row0), n, rs, cs))
+        if finish is not None:
+            finish()
+        del keep
+        return dst
+
     def elbo(self):
         v = C.c_double()
         self._chk(self._lib.vbmf_elbo(self._h, C.byref(v)))
@@ -822,6 +915,11 @@ class Context:
                 "set_y_rows_us",                     # device time of the last vbmf_set_Y_rows call (HIP events: staged copies, tiling, ||Y||^2)
                 "b_pending", "b_materialised"]       # B of the last Gram-form run is still owed; how often it has been made on demand
         return dict(zip(keys, (int(x) for x in v)))
+
+    def out_rows_us(self):
+        """Device time (microseconds) of the last vbmf_get_YHat_rows / vbmf_get_factor_rows call between two HIP events on the context's
+        stream: kernels and staged copies (word 30 of VBMF_PEEK_DIMS; dims() keeps its 30 keys)."""
+        return int(self.peek(PEEK_DIMS, 31, dtype=np.int32)[30])
 
     def time_pass(self, p, iters=10):
         v = C.c_double()

@@ -58,6 +58,7 @@
 #include "fit_basic_gram_kernels.hpp"
 #include "score_kernels.hpp"
 #include "gram_kernels.hpp"
+#include "out_kernels.hpp"
 
 using namespace vbmf;
 
@@ -173,6 +174,7 @@ struct vbmf_ctx {
     MemOwner<HipMem> mem;             // every device buffer above and below: acquired through it, freed by it (ctx_mem.hpp)
     hipEvent_t ev_y[2] = {nullptr, nullptr};   // around the device work of the last vbmf_set_Y_rows call (created by the first one)
     double set_y_ms = 0.0;            // ... and what they measured: staged copies, tiling kernels, ||Y||^2 (VBMF_PEEK_DIMS word 27, us)
+    double out_ms = 0.0;              // the same pair around the last vbmf_get_YHat_rows / vbmf_get_factor_rows call: kernels, staged copies (word 30, us)
     int64_t y_rows = 0;               // vbmf_set_Y_rows: rows of the Y being built that have arrived (L once Y is complete)
     double trYY_local = 0.0;
     int prof = 0;                     // 0 off; k: HIP events around every k-th launch of each pass
@@ -2407,6 +2409,159 @@ int vbmf_get_YHat(vbmf_ctx* c, double* YHat, int64_t ld) {
     return VBMF_OK;
 }
 
+}  // extern "C"
+
+// ---- results into the caller's own dtype, layout and memory, in row blocks (out_kernels.hpp) ----------------
+static size_t dst_elem_size(int dt) { return dt == VBMF_DST_F64 ? 8 : dt == VBMF_DST_F32 ? 4 : 2; }
+
+// Every refusal of the two output entries, in the order of include/vbmf_hip.h: nothing is launched, copied or materialised before
+// this has returned VBMF_OK, so a wrong pointer comes back as a code and no kernel writes it.
+static int check_dst(vbmf_ctx* c, const char* fn, const void* dst, int32_t dt, int32_t on_device, int64_t row0, int64_t nrows,
+                     int64_t rows_total, int64_t ncols, int64_t rs, int64_t cs) {
+    if (!dst) FAIL(c, VBMF_ERR_INVALID, "%s: null dst", fn);
+    if (dt != VBMF_DST_F64 && dt != VBMF_DST_F32 && dt != VBMF_DST_BF16) FAIL(c, VBMF_ERR_INVALID, "%s: unknown dst_dtype %d", fn, (int)dt);
+    if (rs <= 0 || cs <= 0) FAIL(c, VBMF_ERR_INVALID, "%s: strides must be positive", fn);
+    if (row0 < 0 || nrows < 1 || nrows > rows_total - row0)
+        FAIL(c, VBMF_ERR_INVALID, "%s: rows [%lld, %lld) are not inside 0 .. %lld", fn, (long long)row0, (long long)(row0 + nrows), (long long)rows_total);
+    typedef unsigned __int128 u128;
+    const u128 row_span = (u128)(ncols - 1) * (u128)cs + 1, col_span = (u128)(nrows - 1) * (u128)rs + 1;
+    if ((u128)rs < row_span && (u128)cs < col_span)
+        FAIL(c, VBMF_ERR_INVALID, "%s: the lines of dst overlap (neither stride is as long as a line of the other)", fn);
+    if (!on_device && rs != 1 && cs != 1) FAIL(c, VBMF_ERR_INVALID, "%s: a host dst needs row_stride = 1 or col_stride = 1", fn);
+    HIPCHK(c, hipSetDevice(c->o.device));
+    hipPointerAttribute_t at;
+    hipError_t e = hipPointerGetAttributes(&at, dst);
+    if (e != hipSuccess) (void)hipGetLastError();                      // memory the runtime has never seen: plain host memory
+    const bool is_dev = e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+    if (on_device) {
+        if (!is_dev) FAIL(c, VBMF_ERR_INVALID, "%s: dst_on_device is set but dst is not device memory", fn);
+        if (at.device != c->o.device) FAIL(c, VBMF_ERR_INVALID, "%s: dst lives on device %d, the context on device %d", fn, at.device, c->o.device);
+        const u128 last = (u128)(nrows - 1) * (u128)rs + (u128)(ncols - 1) * (u128)cs;
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dst);
+        if (e != hipSuccess) { (void)hipGetLastError(); FAIL(c, VBMF_ERR_INVALID, "%s: dst belongs to no device allocation", fn); }
+        const uintptr_t b = (uintptr_t)base, p = (uintptr_t)dst;
+        if (p < b || p - b > size || (last + 1) * dst_elem_size(dt) > (u128)(size - (p - b)))
+            FAIL(c, VBMF_ERR_INVALID, "%s: the strided extent of the block leaves its device allocation", fn);
+    } else if (e == hipSuccess && at.type == hipMemoryTypeDevice) {
+        FAIL(c, VBMF_ERR_INVALID, "%s: dst is device memory but dst_on_device is 0", fn);
+    }
+    return VBMF_OK;
+}
+
+// rows [l0, l0 + n) of YHat (or of Y - YHat) to DEVICE memory dev[(l - l0) rs + m cs]
+template <class ACC, class DST>
+static int launch_yhat_typed(vbmf_ctx* c, int what, DST* dev, int64_t l0, int64_t n, int64_t rs, int64_t cs) {
+    // the factor of the dst's shorter-stride dimension is the MFMA's column side: its lanes then store side by side
+    const bool swap = rs < cs;
+    const float* Bf = c->B32[c->bcur];
+    const float *Xf = swap ? c->A32 : Bf, *Yf = swap ? Bf : c->A32;
+    const int64_t X = swap ? c->M : n, Yn = swap ? n : c->M;
+    const int64_t xr0 = swap ? 0 : l0, yr0 = swap ? l0 : 0;
+    const int64_t sx = swap ? cs : rs, sy = swap ? rs : cs;
+    const int64_t ntx = (X + OUT_TILE - 1) / OUT_TILE, nty = (Yn + OUT_TILE - 1) / OUT_TILE;
+    if (ntx * nty > 0x7fffffffll) FAIL(c, VBMF_ERR_UNSUPPORTED, "vbmf_get_YHat_rows: more than 2^31 output tiles in one block of rows: pass fewer rows per call");
+    const size_t lds = out_lds_bytes<ACC>();
+#define VBMF_OUT_LAUNCH(RESIDc, YMc)                                                                                               \
+    hipLaunchKernelGGL((yhat_out_kernel<ACC, DST, RESIDc, YMc>), dim3((unsigned)(ntx * nty)), dim3(OUT_THREADS), lds, c->stream, Xf, Yf, \
+                       c->Hp, (int)c->H, (long long)X, (long long)Yn, (long long)xr0, (long long)yr0, dev, (long long)sx,        \
+                       (long long)sy, (int)nty, (int)swap, (const uint4*)c->Y2, c->d2.KS)
+    if (what == VBMF_OUT_RESIDUAL) {
+        if (c->mode == MODE_F32) VBMF_OUT_LAUNCH(true, MODE_F32); else VBMF_OUT_LAUNCH(true, MODE_BF16);
+    } else {
+        VBMF_OUT_LAUNCH(false, MODE_F32);
+    }
+#undef VBMF_OUT_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+static int launch_yhat_out(vbmf_ctx* c, int what, void* dev, int dt, int64_t l0, int64_t n, int64_t rs, int64_t cs) {
+    if (dt == VBMF_DST_F64) return launch_yhat_typed<double, double>(c, what, (double*)dev, l0, n, rs, cs);
+    if (dt == VBMF_DST_F32) return launch_yhat_typed<float, float>(c, what, (float*)dev, l0, n, rs, cs);
+    return launch_yhat_typed<float, out_bf16>(c, what, (out_bf16*)dev, l0, n, rs, cs);
+}
+static int launch_factor_out(vbmf_ctx* c, const float* F, void* dev, int dt, int64_t x0, int64_t n, int64_t rs, int64_t cs) {
+    const int grid = grid_for(n * c->H), hfast = cs <= rs;
+#define VBMF_FAC_LAUNCH(T)                                                                                                  \
+    hipLaunchKernelGGL((factor_out_kernel<T>), dim3(grid), dim3(256), 0, c->stream, F, c->Hp, (int)c->H, (long long)x0, \
+                       (long long)n, (T*)dev, (long long)rs, (long long)cs, hfast)
+    if (dt == VBMF_DST_F64) VBMF_FAC_LAUNCH(double);
+    else if (dt == VBMF_DST_F32) VBMF_FAC_LAUNCH(float);
+    else VBMF_FAC_LAUNCH(out_bf16);
+#undef VBMF_FAC_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    return VBMF_OK;
+}
+
+// The block to dst: straight into device memory, or -- host memory -- through a device buffer of the dst's OWN dtype and order, whole
+// rows per chunk of at most 256 MB (one row if that is larger).  emit(dev, first row, rows, row stride, column stride) enqueues the kernel.
+template <class Emit>
+static int write_block(vbmf_ctx* c, const char* fn, void* dst, int dt, int on_device, int64_t row0, int64_t nrows, int64_t ncols,
+                       int64_t rs, int64_t cs, Emit emit) {
+    const size_t es = dst_elem_size(dt);
+    if (!c->ev_y[0]) { HIPCHK(c, hipEventCreate(&c->ev_y[0])); HIPCHK(c, hipEventCreate(&c->ev_y[1])); }
+    HIPCHK(c, hipEventRecord(c->ev_y[0], c->stream));
+    if (on_device) {
+        TRY(emit(dst, row0, nrows, rs, cs));
+    } else {
+        const bool rowmajor = cs == 1 && (nrows == 1 || rs >= ncols);
+        int64_t rc = std::max<int64_t>(1, (int64_t)(256ll << 20) / (ncols * (int64_t)es));
+        rc = std::min(rc, nrows);
+        DevScratch<void> stage;
+        MEMCHK(c, stage.alloc((size_t)rc * ncols * es));
+        for (int64_t r = 0; r < nrows; r += rc) {
+            const int64_t n = std::min(rc, nrows - r);
+            TRY(rowmajor ? emit(stage.get(), row0 + r, n, ncols, (int64_t)1) : emit(stage.get(), row0 + r, n, (int64_t)1, n));
+            char* to = (char*)dst + (size_t)r * rs * es;
+            hipError_t e = rowmajor ? hipMemcpy2DAsync(to, (size_t)rs * es, stage, (size_t)ncols * es, (size_t)ncols * es, (size_t)n, hipMemcpyDeviceToHost, c->stream)
+                                    : hipMemcpy2DAsync(to, (size_t)cs * es, stage, (size_t)n * es, (size_t)n * es, (size_t)ncols, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) FAIL(c, VBMF_ERR_HIP, "%s: copy to the host failed: %s", fn, hipGetErrorString(e));
+        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev_y[1], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // the caller may read its buffer once this returns
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_y[0], c->ev_y[1]));
+    c->out_ms = ms;
+    return VBMF_OK;
+}
+
+extern "C" {
+
+int vbmf_get_YHat_rows(vbmf_ctx* c, int32_t what, void* dst, int32_t dt, int32_t on_device, int64_t row0, int64_t nrows,
+                       int64_t rs, int64_t cs) {
+    if (!c) return VBMF_ERR_INVALID;
+    static const char* fn = "vbmf_get_YHat_rows";
+    if (!dst) FAIL(c, VBMF_ERR_INVALID, "%s: null dst", fn);
+    if (what != VBMF_OUT_YHAT && what != VBMF_OUT_RESIDUAL) FAIL(c, VBMF_ERR_INVALID, "%s: unknown what %d", fn, (int)what);
+    TRY(check_dst(c, fn, dst, dt, on_device, row0, nrows, c->L, c->M, rs, cs));
+    if (!c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "%s: no state", fn);
+    if (what == VBMF_OUT_RESIDUAL && !c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y", fn);
+    TRY(ensure_B(c));
+    TRY(rebuild_B32_if_stale(c));
+    return write_block(c, fn, dst, dt, on_device, row0, nrows, c->M, rs, cs,
+                       [&](void* dev, int64_t l0, int64_t n, int64_t r, int64_t s) { return launch_yhat_out(c, what, dev, dt, l0, n, r, s); });
+}
+
+int vbmf_get_factor_rows(vbmf_ctx* c, int32_t which, void* dst, int32_t dt, int32_t on_device, int64_t row0, int64_t nrows,
+                         int64_t rs, int64_t cs) {
+    if (!c) return VBMF_ERR_INVALID;
+    static const char* fn = "vbmf_get_factor_rows";
+    if (!dst) FAIL(c, VBMF_ERR_INVALID, "%s: null dst", fn);
+    if (which != VBMF_FACTOR_A && which != VBMF_FACTOR_B) FAIL(c, VBMF_ERR_INVALID, "%s: unknown which %d", fn, (int)which);
+    TRY(check_dst(c, fn, dst, dt, on_device, row0, nrows, which == VBMF_FACTOR_A ? c->M : c->L, c->H, rs, cs));
+    if (!c->cache.have_state()) FAIL(c, VBMF_ERR_INVALID, "%s: no state", fn);
+    if (which == VBMF_FACTOR_B) {
+        TRY(ensure_B(c));
+        TRY(rebuild_B32_if_stale(c));
+    }
+    return write_block(c, fn, dst, dt, on_device, row0, nrows, c->H, rs, cs, [&](void* dev, int64_t x0, int64_t n, int64_t r, int64_t s) {
+        return launch_factor_out(c, which == VBMF_FACTOR_A ? c->A32 : c->B32[c->bcur], dev, dt, x0, n, r, s);
+    });
+}
+
 int vbmf_elbo(vbmf_ctx* c, double* elbo) {
     if (!c || !elbo) return VBMF_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->o.device));
@@ -2508,13 +2663,14 @@ int vbmf_debug_peek(vbmf_ctx* c, int what, uint32_t* out, int64_t nwords, int64_
     if (what != VBMF_PEEK_DIMS) TRY(ensure_B(c));          // every buffer is shown as an eager run end left it; the dimensions never pay
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (what == VBMF_PEEK_DIMS) {
-        const int v[30] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
+        const int v[31] = {c->Hp, c->NH, c->mode, c->d1.XT, c->d1.KS, c->d1.nsplit, c->d1.steps_per_split,
                            c->d2.XT, c->d2.KS, c->d2.nsplit, c->d2.steps_per_split, c->kstep, c->npart, c->narrow ? 1 : 0, c->sk_per, c->sk_grid,
                            gram_eligible(c) ? 1 : 0, c->cache.G() ? 1 : 0, (int)std::lround(c->gram_build_ms * 1000.0), c->g_nsplit,
                            c->frag_last[0] ? 1 : 0, c->frag_last[1] ? 1 : 0, c->epi_last ? 1 : 0, use_lds8(c) ? 1 : 0, c->xcd_map ? 1 : 0,
                            c->post3 ? 1 : 0, c->sparse_a_fused ? 1 : 0, (int)std::lround(c->set_y_ms * 1000.0),
-                           c->cache.B_owed() ? 1 : 0, (int)std::min<long long>(c->b_materialised, 0x7fffffff)};
-        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(30, nwords));
+                           c->cache.B_owed() ? 1 : 0, (int)std::min<long long>(c->b_materialised, 0x7fffffff),
+                           (int)std::lround(c->out_ms * 1000.0)};
+        memcpy(out, v, sizeof(int) * (size_t)std::min<int64_t>(31, nwords));
         return VBMF_OK;
     }
     if (what == VBMF_PEEK_CHAIN) {

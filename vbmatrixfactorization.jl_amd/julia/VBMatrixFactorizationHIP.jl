@@ -16,7 +16,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
-       vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!
+       vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!
 
 const libvbmf = get(ENV, "VBMF_HIP_LIB", joinpath(@__DIR__, "..", "libvbmf_hip.so"))
 
@@ -106,6 +106,47 @@ function set_Y!(h::Ptr{Cvoid}, Y::Array{Float32,2})
     L = size(Y, 1)
     chk(h, ccall((:vbmf_set_Y_rows, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
                  h, Y, VBMF_SRC_F32, Int32(0), 0, L, 1, L))
+end
+
+const VBMF_DST_F64, VBMF_DST_F32 = Int32(0), Int32(1)
+
+"""
+    get_YHat!(ctx, dst; residual = false, row0 = 0)
+
+Rows row0 .. row0 + size(dst, 1) - 1 (0-based row0, this context's local rows) of updateYHat! (src/vbmf.jl:120-122), BHat*AHat', written
+into the host matrix `dst` in its own format through vbmf_get_YHat_rows -- no Float64 copy for a Float32 `dst`; `residual = true` gives Y as
+stored minus the product.  Host arrays only (column-major: row stride 1, column stride size(dst, 1)).  Returns dst.
+"""
+function get_YHat!(c::Ctx, dst::Array{Float32,2}; residual::Bool = false, row0::Int = 0)
+    n = size(dst, 1); what = Int32(residual ? 1 : 0)
+    chk(c.h, ccall((:vbmf_get_YHat_rows, libvbmf), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
+                   c.h, what, dst, VBMF_DST_F32, Int32(0), row0, n, 1, n))
+    dst
+end
+function get_YHat!(c::Ctx, dst::Array{Float64,2}; residual::Bool = false, row0::Int = 0)
+    n = size(dst, 1); what = Int32(residual ? 1 : 0)
+    chk(c.h, ccall((:vbmf_get_YHat_rows, libvbmf), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
+                   c.h, what, dst, VBMF_DST_F64, Int32(0), row0, n, 1, n))
+    dst
+end
+
+"""
+    get_factor!(ctx, which, dst; row0 = 0)
+
+Rows row0 .. of AHat (`which = :A`, M x H) or of this context's BHat (`:B`, L x H) -- the Float32 values the device holds, what pull! widens --
+into the host matrix `dst` (Float32: a copy; Float64: a widening) through vbmf_get_factor_rows.  Returns dst.
+"""
+function get_factor!(c::Ctx, which::Symbol, dst::Array{Float32,2}; row0::Int = 0)
+    n = size(dst, 1); w = Int32(which == :B ? 1 : 0)
+    chk(c.h, ccall((:vbmf_get_factor_rows, libvbmf), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
+                   c.h, w, dst, VBMF_DST_F32, Int32(0), row0, n, 1, n))
+    dst
+end
+function get_factor!(c::Ctx, which::Symbol, dst::Array{Float64,2}; row0::Int = 0)
+    n = size(dst, 1); w = Int32(which == :B ? 1 : 0)
+    chk(c.h, ccall((:vbmf_get_factor_rows, libvbmf), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
+                   c.h, w, dst, VBMF_DST_F64, Int32(0), row0, n, 1, n))
+    dst
 end
 
 const _cache = Dict{UInt,Ctx}()
