@@ -64,12 +64,17 @@ DIAGVAR_SEQS = {
 
 
 def _cases():
-    """name -> (model kind, L, M, H, mode, sequence).  Modes: f32 (fp32 Y), bf16x2 (bf16 Y, bf16 hi + lo factors), gram (the same,
-    forced into the Gram form by VBMF_GRAM at creation), auto (bf16 Y, the factor operand the library picks)"""
+    """name -> (model kind, L, M, H, mode, sequence).  Modes: f32 (fp32 Y), bf16x2 (bf16 Y, bf16 hi + lo factors), bf16 (bf16 Y, one
+    bf16 factor operand), gram (bf16x2, forced into the Gram form by VBMF_GRAM at creation), auto (bf16 Y, the factor operand the
+    library picks)"""
     out = {}
     for mode in ("f32", "bf16x2"):
         for k, s in BASIC_SEQS.items():
             out[f"basic-{mode}-601x97xH24-{k}"] = ("basic", 601, 97, 24, mode, s)
+        for k in ("steps", "run_newY_run"):                   # two h tiles: the streaming sweep's other narrow / epilogue instances
+            out[f"basic-{mode}-601x97xH40-{k}"] = ("basic", 601, 97, 40, mode, BASIC_SEQS[k])
+    out["basic-bf16-257x161xH100-steps"] = ("basic", 257, 161, 100, "bf16", BASIC_SEQS["steps"])     # four h tiles, single-bf16 operand
+    out["sparse-257x161xH130-steps"] = ("sparse", 257, 161, 130, "auto", SPARSE_SEQS["steps"])       # eight h tiles, streaming
     out["basic-bf16x2-257x161xH130-noY_setY_run_vbls"] = ("basic", 257, 161, 130, "bf16x2", BASIC_SEQS["noY_setY_run_vbls"])   # side stream
     for M, H in ((61, 24), (353, 100)):
         for k, s in GRAM_SEQS.items():
@@ -133,7 +138,7 @@ class Runner:
     def context(self):
         cap = self.cap
         kw = dict(y_dtype=cap.VBMF_Y_F32 if self.mode == "f32" else cap.VBMF_Y_BF16,
-                  factor_dtype=cap.VBMF_FACTOR_AUTO if self.mode in ("f32", "auto") else cap.VBMF_FACTOR_BF16X2)
+                  factor_dtype=dict(f32=cap.VBMF_FACTOR_AUTO, auto=cap.VBMF_FACTOR_AUTO, bf16=cap.VBMF_FACTOR_BF16).get(self.mode, cap.VBMF_FACTOR_BF16X2))
         if self.sparse:
             kw["variant"] = cap.VBMF_VARIANT_SPARSE_DIAGVAR if self.kind == "diagvar" else cap.VBMF_VARIANT_SPARSE_DIAG
         old = os.environ.get("VBMF_GRAM")

@@ -35,8 +35,8 @@ static int bags_reserve(vbmf_ctx* c, int64_t doubles, double** d) {
 
 // S_b = P_b'P_b (S = nullptr: not formed) and ||Y_b||^2 of every bag; frag_nh: P is fragment-major (0: row-major [h][x])
 static int bags_launch_gram(vbmf_ctx* c, int64_t nb, const float* P, int frag_nh, const long long* d_off, double* S, double* yy) {
-    DISPATCH_YMODE(c->mode, {
-        hipLaunchKernelGGL((bag_gram_kernel<YMODEc>), dim3((unsigned)nb), dim3(256), 0, c->stream, P, (long long)c->d1.XT * 32, frag_nh,
+    dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+        hipLaunchKernelGGL((bag_gram_kernel<decltype(ym)::value>), dim3((unsigned)nb), dim3(256), 0, c->stream, P, (long long)c->d1.XT * 32, frag_nh,
                            c->Y2, c->d2.KS, (long long)c->L, d_off, (int)c->H, S, yy);
     });
     HIPCHK(c, hipGetLastError());
@@ -94,8 +94,8 @@ int vbmf_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_
     const int fnh = c->P_frag ? c->NH : 0;
     TRY(bags_launch_gram(c, nb, Psrc, fnh, d_off, d + o_s, d + o_yy));
     const size_t lds = vbls_lds_bytes(nb_tier(H));
-    DISPATCH_NB(nb_tier(H), {
-        hipLaunchKernelGGL((vbls_batch_kernel<NBc>), dim3((unsigned)nb), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, d_off,
+    dispatch<1, 2, 4>(nb_tier(H), [&](auto nbk) {
+        hipLaunchKernelGGL((vbls_batch_kernel<decltype(nbk)::value>), dim3((unsigned)nb), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, d_off,
                            (int)niter, d + o_s, d + o_yy, d + o_s2, d + o_ca, d + o_sa, d + o_t, c->ints);
     });
     HIPCHK(c, hipGetLastError());
@@ -185,10 +185,12 @@ int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* c, int64_t nbags, const int64_
     SbatchArgs a{c->Pred, ldP, d_off, H, (int)niter, (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) ? 1 : 0, lds_state, (double)c->Lg,
                  d + o_g, d + o_gd, d + o_sd, d + o_al, d + o_b0, d + o_eta, d + o_z0, d + o_yy, d + o_sig, d + o_zeta,
                  d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_p, d + o_sa, c->ints + I_ERR};
-#define SBATCH(FULLc_) \
-    DISPATCH_NB(NBK, hipLaunchKernelGGL((sparse_batch_kernel<NBc, FULLc_>), dim3((unsigned)nb), dim3(SBATCH_THREADS), lds, c->stream, a))
-    if (full_cov) { SBATCH(true); } else { SBATCH(false); }
-#undef SBATCH
+    dispatch<1, 2, 4>(NBK, [&](auto nbk) {
+        dispatch<0, 1>(full_cov ? 1 : 0, [&](auto full) {
+            hipLaunchKernelGGL((sparse_batch_kernel<decltype(nbk)::value, decltype(full)::value != 0>), dim3((unsigned)nb), dim3(SBATCH_THREADS), lds,
+                               c->stream, a);
+        });
+    });
     HIPCHK(c, hipGetLastError());
     if (ints0[I_STOP]) HIPCHK(c, hipMemcpyAsync(c->ints + I_STOP, &ints0[I_STOP], sizeof(int), hipMemcpyHostToDevice, c->stream));
     // read-back: [sigma | zeta] and [CA | A | dS | beta] and SigmaA are contiguous blocks
@@ -235,8 +237,8 @@ static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, i
     TRY(score_upload_offsets(c, nb, col_off, d_off));
     TRY(rebuild_B32_if_stale(c));
     const size_t lds = score_resid_lds_bytes((int)c->H);
-    DISPATCH_YMODE(c->mode, {
-        hipLaunchKernelGGL((bag_resid_kernel<YMODEc>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
+    dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+        hipLaunchKernelGGL((bag_resid_kernel<decltype(ym)::value>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS,
                            (long long)c->L, c->B32[c->bcur], c->Hp, (int)c->H, d_A, sm, sh, d_off, d_off + nb + 1, (int)nb, d_part);
     });
     HIPCHK(c, hipGetLastError());
@@ -312,8 +314,8 @@ int vbmf_bag_least_squares(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, c
     double* d_x = X ? d + o_x : nullptr;
     double* d_part = r2 ? d + o_part : nullptr;
     const size_t lds = score_ls_lds_bytes((int)H);
-    DISPATCH_YMODE(c->mode, {
-        hipLaunchKernelGGL((bag_ls_kernel<YMODEc>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
+    dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+        hipLaunchKernelGGL((bag_ls_kernel<decltype(ym)::value>), dim3((unsigned)ns), dim3(SCORE_THREADS), lds, c->stream, c->Y2, c->d2.KS, (long long)L,
                            d + o_b, (int)H, d + o_k, d_off, d_off + nb + 1, (int)nb, d_x, d_part);
     });
     HIPCHK(c, hipGetLastError());
@@ -413,8 +415,8 @@ int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* c
 // ---- many fits in one launch (fit_batch_kernels.hpp) ------------------------------------------------------------------------------
 // enqueues fit_stage_kernel: Y as stored into the two fp32 planes
 static int fit_stage(vbmf_ctx* c, float* Yr, float* Yc) {
-    DISPATCH_YMODE(c->mode, {
-        hipLaunchKernelGGL((fit_stage_kernel<YMODEc>), dim3(grid_for(c->L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
+    dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+        hipLaunchKernelGGL((fit_stage_kernel<decltype(ym)::value>), dim3(grid_for(c->L * c->M, 256, 2048)), dim3(256), 0, c->stream, c->Y2, c->d2.KS,
                            (long long)c->L, (long long)c->M, Yr, Yc);
     });
     HIPCHK(c, hipGetLastError());
@@ -493,20 +495,16 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
               d + o_de, d + o_zeta, d + o_be, d + o_ds, d + o_sa, d + o_a, d + o_bw, d + o_qw,
               reinterpret_cast<long long*>(d + o_it), d + o_dl, reinterpret_cast<long long*>(d + o_st), trace ? d + o_tr : nullptr};
     const size_t lds = lds_doubles * 8;
-#define FITB(FULLc_)                                                                                                               \
-    DISPATCH_NB(NBK, {                                                                                                             \
-        hipLaunchKernelGGL((fit_batch_kernel<(NBc > 2 ? 2 : NBc), FULLc_>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a); \
-    })
-#define FITB_LOCAL(FULLc_)                                                                                                         \
-    DISPATCH_NB(NBK, {                                                                                                             \
-        hipLaunchKernelGGL((fit_batch_kernel<(NBc > 2 ? 2 : NBc), FULLc_, true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, la); \
-    })
-    if (local) {
-        FitLocalArgs la{a, di + nb + 1 + nf + nf + 1, (int)mask_H1};
-        if (full_cov) { FITB_LOCAL(true); } else { FITB_LOCAL(false); }
-    } else if (full_cov) { FITB(true); } else { FITB(false); }
-#undef FITB
-#undef FITB_LOCAL
+    // (the fit kernels exist for NB = 1 and 2: every rank above 16 runs the NB = 2 instance)
+    const FitLocalArgs la{a, di + nb + 1 + nf + nf + 1, (int)mask_H1};
+    dispatch<1, 2>(std::min(NBK, 2), [&](auto nbk) {
+        dispatch<0, 1>(full_cov ? 1 : 0, [&](auto full) {
+            constexpr int NBc = decltype(nbk)::value;
+            constexpr bool FULLc = decltype(full)::value != 0;
+            if (local) hipLaunchKernelGGL((fit_batch_kernel<NBc, FULLc, true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, la);
+            else hipLaunchKernelGGL((fit_batch_kernel<NBc, FULLc>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
+        });
+    });
     HIPCHK(c, hipGetLastError());
     // read-back: [priors | zeta | d_last | iters | status] is one block; the per-fit matrices and the M H-long fields one block each
     out.resize((size_t)(o_b - o_pri));
@@ -709,8 +707,8 @@ static int fit_basic_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int64
                    form ? d_form : nullptr};
     if (ngram < nf) {
         const size_t lds = lds_doubles * 8;
-        DISPATCH_NB(NBK, {
-            hipLaunchKernelGGL((fit_basic_kernel<(NBc > 2 ? 2 : NBc)>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
+        dispatch<1, 2>(std::min(NBK, 2), [&](auto nbk) {
+            hipLaunchKernelGGL((fit_basic_kernel<decltype(nbk)::value>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
         });
         HIPCHK(c, hipGetLastError());
     }
@@ -718,14 +716,14 @@ static int fit_basic_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int64
         TRY(fit_rowgram(c, fn, Yc, di, d_form + nf + nf, nk, d + o_k));
         FitBasicGramArgs ga{a, d + o_k, d_form + nf, d + o_v};
         const size_t lds = (size_t)fitb_gram_lds_doubles(NBK, L, H) * 8;
-        DISPATCH_NB(NBK, {
-            hipLaunchKernelGGL((fit_basic_gram_kernel<(NBc > 2 ? 2 : NBc)>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, ga);
+        dispatch<1, 2>(std::min(NBK, 2), [&](auto nbk) {
+            hipLaunchKernelGGL((fit_basic_gram_kernel<decltype(nbk)::value>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, ga);
         });
         HIPCHK(c, hipGetLastError());
         if (AHat) {
             const dim3 grid((unsigned)nf, (unsigned)cdiv(widest_gram, RG_THREADS));
-            DISPATCH_NB(NBK, {
-                hipLaunchKernelGGL((fit_rowgram_finish_kernel<(NBc > 2 ? 32 : 16 * NBc)>), grid, dim3(RG_THREADS), (size_t)LH * 8, c->stream, ga);
+            dispatch<16, 32>(std::min(16 * NBK, 32), [&](auto ht) {
+                hipLaunchKernelGGL((fit_rowgram_finish_kernel<decltype(ht)::value>), grid, dim3(RG_THREADS), (size_t)LH * 8, c->stream, ga);
             });
             HIPCHK(c, hipGetLastError());
         }

@@ -39,6 +39,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -254,37 +255,34 @@ static hipError_t memcpy_sync(vbmf_ctx* c, void* dst, const void* src, size_t n,
         if (_rc != VBMF_OK) return _rc; \
     } while (0)
 
-#define DISPATCH_NH(nh, ...)                                   \
-    switch (nh) {                                              \
-        case 1: { constexpr int NHc = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int NHc = 2; __VA_ARGS__; } break; \
-        case 4: { constexpr int NHc = 4; __VA_ARGS__; } break; \
-        case 8: { constexpr int NHc = 8; __VA_ARGS__; } break; \
-        default: break;                                        \
-    }
-#define DISPATCH_MODE(md, ...)                                                     \
-    switch (md) {                                                                  \
-        case MODE_F32: { constexpr int MODEc = MODE_F32; __VA_ARGS__; } break;     \
-        case MODE_BF16: { constexpr int MODEc = MODE_BF16; __VA_ARGS__; } break;   \
-        case MODE_BF16X2: { constexpr int MODEc = MODE_BF16X2; __VA_ARGS__; } break; \
-        default: break;                                                            \
-    }
+// Runtime value -> template argument, the one way: dispatch<V1, V2, ...>(v, f) calls f(std::integral_constant<int, Vk>{}) for the
+// listed Vk that equals v and returns false when none does (the caller FAILs: a missing kernel is an error).  The list at the call
+// site IS the set of instances that exist -- a kernel is instantiated for exactly the values named there.  f is a generic lambda,
+// inlined: nothing is erased and nothing allocated on the launch path.  An f that returns bool hands its answer through (nested lists).
+template <int V, class F>
+static inline bool dispatch_one(F& f) {
+    if constexpr (std::is_same_v<decltype(f(std::integral_constant<int, V>{})), bool>) return f(std::integral_constant<int, V>{});
+    else { f(std::integral_constant<int, V>{}); return true; }
+}
+template <int... Vs, class F>
+static inline bool dispatch(int v, F&& f) { return ((v == Vs && dispatch_one<Vs>(f)) || ...); }
+#define NO_KERNEL(ctx) FAIL(ctx, VBMF_ERR_INVALID, "internal: no kernel instance for this rank / mode (%s:%d)", __FILE__, __LINE__)
 
-// Y as the per-bag kernels read it from its tiles: fp32 or bf16 (bf16x2 is a factor mode; Y itself is bf16 there)
-#define DISPATCH_YMODE(md, ...)                                               \
-    switch (md) {                                                             \
-        case MODE_F32: { constexpr int YMODEc = MODE_F32; __VA_ARGS__; } break; \
-        default: { constexpr int YMODEc = MODE_BF16; __VA_ARGS__; } break;    \
-    }
+// Y as the kernels read it from its tiles: fp32 or bf16 (bf16x2 is a factor mode; Y itself is bf16 there)
+static inline int ymode_of(int mode) { return mode == MODE_F32 ? MODE_F32 : MODE_BF16; }
 // NB = 16 x 16 blocks across an H x H image of the one-workgroup vbls! kernels (H <= 64)
 static inline int nb_tier(int64_t H) { return H <= 16 ? 1 : (H <= 32 ? 2 : 4); }
-#define DISPATCH_NB(nb, ...)                                   \
-    switch (nb) {                                              \
-        case 1: { constexpr int NBc = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int NBc = 2; __VA_ARGS__; } break; \
-        case 4: { constexpr int NBc = 4; __VA_ARGS__; } break; \
-        default: break;                                        \
-    }
+// The control tiers H -> (R, T): R 16-column blocks across the H x H image, T x T threads (T = 32: the 1024-thread kernels of
+// 128 < H <= 256).  f(integral_constant R, integral_constant T); every ladder over H that picks a control kernel goes through here.
+template <class F>
+static inline void ctrl_tier(int64_t H, F&& f) {
+    using std::integral_constant;
+    if (H <= 16) f(integral_constant<int, 1>{}, integral_constant<int, 16>{});
+    else if (H <= 32) f(integral_constant<int, 2>{}, integral_constant<int, 16>{});
+    else if (H <= 64) f(integral_constant<int, 4>{}, integral_constant<int, 16>{});
+    else if (H <= 128) f(integral_constant<int, 8>{}, integral_constant<int, 16>{});
+    else f(integral_constant<int, 8>{}, integral_constant<int, 32>{});
+}
 
 static inline int64_t rup(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
@@ -426,9 +424,40 @@ static size_t ctrl_lds_bytes_r(int R) {
     return std::max(eig, spd_inverse_lds_bytes(R));
 }
 static size_t ctrl_lds_bytes(int NH) { return NH <= 4 ? ctrl_lds_bytes_r(2 * NH) : 0; }
+// dynamic LDS of sparse_update_a_full_wave_kernel<NBK, NW>: per wavefront the 16 NBK x (16 NBK + 2) fp64 image and one column.  The launcher
+// and vbmf_create's table of large-LDS kernels both take it from here.
+constexpr size_t full_a_wave_lds_bytes(int NBK, int NW) { return ((size_t)NW * 16 * NBK * (16 * NBK + 2) + (size_t)NW * 16 * NBK) * sizeof(double); }
 static bool fused_ctrl(const vbmf_ctx* c) { return c->in_run && c->NH <= 4; }
 // the host-mapped loop counters, for the device's loop test: only a run loop looks at them
 static int* loop_words(const vbmf_ctx* c) { return c->in_run ? c->loopw_dev : nullptr; }
+
+// One factor side as its launchers see it.  which = 0: A (M rows, the x side of pass 1, the label mask); 1: B (L rows, pass 2).
+struct Side {
+    const Dims& d;
+    const float* S;                  // the side's Sigma / sigma2 table
+    float* Fac;                      // the fp32 factor the launch writes
+    uint4* Ft;                       // ... and its operand tiles
+    const unsigned char* mask;       // label mask (A side, when one is set) or null
+    int hstart;                      // first masked column
+};
+// B is double-buffered: an update writes the NEXT buffer (the delta-Gram reads the current one beside it), a retile rewrites the
+// CURRENT one in place.  Every caller says which.
+enum BSlot { B_CUR = 0, B_NEXT = 1 };
+static Side side_of(vbmf_ctx* c, int which, BSlot slot) {
+    if (which == 0) return Side{c->d1, c->SA32, c->A32, c->FA, c->has_mask ? c->mask : nullptr, (int)(c->H - c->H1)};
+    return Side{c->d2, c->SB32, c->B32[c->bcur ^ (int)slot], c->FB, nullptr, (int)(c->H - c->H1)};
+}
+
+// the control chain's arguments, for a pass launch that carries it (launch_stream) or a launch of its own (launch_chain)
+static CtrlArgs ctrl_args(vbmf_ctx* c, int mode, float* S32) {
+    CtrlArgs ca{};
+    ca.st = c->st; ca.lay = c->lay; ca.ints = c->ints; ca.trace = c->run_trace;
+    ca.S32 = S32;
+    ca.Lg = (double)c->Lg; ca.M = (double)c->M; ca.eps = c->run_eps;
+    ca.H = (int)c->H; ca.spectral = spectral_arg(c);
+    ca.end_flags = c->run_flags; ca.mode = mode; ca.it_row = (int)c->ends_enqueued; ca.loopw = loop_words(c);
+    return ca;
+}
 
 // ctrl_mode != 0: workgroup 0 of the launch runs that part of the control chain (CtrlArgs)
 // epi (pass 2 only, un-split, NH <= 2): B, its operand tiles and the Gram partials are produced in the kernel's register
@@ -456,12 +485,7 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
     // split-K launches use the XCD-aware work map (stream_gemm.hpp): 8 * per workgroups, per = ceil(blocks / 8)
     const int xper = (d.nsplit > 1 && c->xcd_map) ? cdiv(bps * d.nsplit, 8) : 0;
     const int grid = (xper ? 8 * xper : bps * d.nsplit) + (ctrl_mode ? 2 : 0);
-    CtrlArgs ca{};
-    ca.st = c->st; ca.lay = c->lay; ca.ints = c->ints; ca.trace = c->run_trace;
-    ca.S32 = pass == 0 ? c->SA32 : c->SB32;
-    ca.Lg = (double)c->Lg; ca.M = (double)c->M; ca.eps = c->run_eps;
-    ca.H = (int)c->H; ca.spectral = spectral_arg(c);
-    ca.end_flags = c->run_flags; ca.mode = ctrl_mode; ca.it_row = (int)c->ends_enqueued; ca.loopw = loop_words(c);
+    CtrlArgs ca = ctrl_args(c, ctrl_mode, pass == 0 ? c->SA32 : c->SB32);
     ea.frag_out = frag_out ? 1 : 0;
     if (epi) {
         c->sready_seq = (c->sready_seq + 1) & 0x3fffffff;
@@ -481,6 +505,7 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
     c->frag_last[pass] = frag_out && !epi;
     if (pass == 1) c->epi_last = epi;
     prof_begin(c, pass);
+    bool ok = true;
     if (use_lds8(c) && !epi) {
         if (lds > (size_t)LDS8_BYTES) FAIL(c, VBMF_ERR_INVALID, "internal: control chain needs %zu bytes of LDS", lds);
         // stream-K: the fragment-major product of the un-split Y*A pass, balanced over the chip (plan: vbmf_create)
@@ -489,50 +514,47 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
         const float* out2 = sk ? reinterpret_cast<const float*>(c->sk_list) : nullptr;   // ... and the segment list
         const int grid8 = sk ? c->sk_grid + (ctrl_mode ? 2 : 0) : grid;
         const int xper8 = sk ? 0 : xper;
-#define LDS8_LAUNCH(NHc_, Rc_, SKc_)                                                                                                     \
-    hipLaunchKernelGGL((stream_lds8_kernel<NHc_, Rc_, SKc_>), dim3(grid8), dim3(512), LDS8_BYTES, c->stream, Y, F, out, d.XT, d.KS,   \
-                       d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper8, ea.frag_out, sk_per, out2)
-        if (c->NH == 4) { if (sk) LDS8_LAUNCH(4, StreamCfg<4>::Rc, true); else LDS8_LAUNCH(4, StreamCfg<4>::Rc, false); }
-        else { if (sk) LDS8_LAUNCH(8, 0, true); else LDS8_LAUNCH(8, 0, false); }
-#undef LDS8_LAUNCH
+        ok = dispatch<4, 8>(c->NH, [&](auto nh) {
+            return dispatch<0, 1>(sk ? 1 : 0, [&](auto skc) {
+                constexpr int NHc = decltype(nh)::value;
+                hipLaunchKernelGGL((stream_lds8_kernel<NHc, StreamCfg<NHc>::Rc, decltype(skc)::value != 0>), dim3(grid8), dim3(512), LDS8_BYTES,
+                                   c->stream, Y, F, out, d.XT, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper8,
+                                   ea.frag_out, sk_per, out2);
+            });
+        });
         if (sk && c->sk_ntail > 0) {
             // the blocks that were cut: product += its second part (a block is contiguous in the fragment-major layout)
             const long long blk = (long long)(c->NH == 8 ? 8 : 16) * c->NH * 1024;        // x tiles per workgroup * NH tiles * 1024 floats
             hipLaunchKernelGGL(streamk_fixup_kernel, dim3(16, std::min(c->sk_ntail, 1024)), dim3(256), 0, c->stream, out, c->sk_per, c->sk_tail,
                                c->sk_ntail, blk, (long long)c->Hp * c->Lp, c->ints + I_STOP);
         }
-    } else if (epi) {
-        DISPATCH_MODE(c->mode, {
-            if (c->NH == 1) {
-                using Cfg = StreamCfg<1>;
-                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, 1, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc, 0, 1>), dim3(grid), dim3(256), lds,
-                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
-            } else {
-                using Cfg = StreamCfg<2>;
-                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, 2, Cfg::NXWc, VBMF_EPI_DY, Cfg::DFc, Cfg::Rc, 0, 1>), dim3(grid), dim3(256), lds,
-                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
-            }
-        });
-    } else if (c->narrow) {
-        DISPATCH_MODE(c->mode, {
-            if (c->NH == 1) {
-                using Cfg = NarrowCfg<1>;
-                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, 1, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>), dim3(grid), dim3(256), lds,
-                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
-            } else {
-                using Cfg = NarrowCfg<2>;
-                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, 2, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>), dim3(grid), dim3(256), lds,
-                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
-            }
-        });
     } else {
-        DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
-            using Cfg = StreamCfg<NHc>;
-            hipLaunchKernelGGL((stream_gemm_kernel<MODEc, NHc, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>), dim3(grid), dim3(256), lds,
-                               c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
-        }));
+        // the pass kernel's geometry: the register-epilogue pass and the narrow geometry exist for NH <= 2 only, the wide one for every NH
+        ok = dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+            constexpr int MODEc = decltype(md)::value;
+            if (epi) return dispatch<1, 2>(c->NH, [&](auto nh) {
+                constexpr int NHc = decltype(nh)::value;
+                using Cfg = StreamCfg<NHc>;
+                constexpr int DYc = NHc == 1 ? Cfg::DYc : VBMF_EPI_DY;
+                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, NHc, Cfg::NXWc, DYc, Cfg::DFc, Cfg::Rc, 0, 1>), dim3(grid), dim3(256), lds,
+                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
+            });
+            if (c->narrow) return dispatch<1, 2>(c->NH, [&](auto nh) {
+                constexpr int NHc = decltype(nh)::value;
+                using Cfg = NarrowCfg<NHc>;
+                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, NHc, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>), dim3(grid), dim3(256), lds,
+                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
+            });
+            return dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+                constexpr int NHc = decltype(nh)::value;
+                using Cfg = StreamCfg<NHc>;
+                hipLaunchKernelGGL((stream_gemm_kernel<MODEc, NHc, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>), dim3(grid), dim3(256), lds,
+                                   c->stream, Y, F, out, XG, d.KS, d.steps_per_split, d.nsplit, ld, c->ints + I_STOP, ca, xper, ea);
+            });
+        });
     }
     prof_end(c);
+    if (!ok) NO_KERNEL(c);
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
@@ -554,30 +576,45 @@ static int allreduce_sum(vbmf_ctx* c, const void* send, void* recv, size_t count
 }
 static int allreduce_sum(vbmf_ctx* c, void* buf, size_t count, bool is_double) { return allreduce_sum(c, buf, buf, count, is_double); }
 
-static int launch_post(vbmf_ctx* c, int which, const float* In, int nslab) {
-    const Dims& d = which == 0 ? c->d1 : c->d2;
-    const long long ld = (long long)d.XT * 32;
-    const long long slabStride = (long long)c->Hp * ld;
-    const float* S = which == 0 ? c->SA32 : c->SB32;
-    float* Fac = which == 0 ? c->A32 : c->B32[c->bcur ^ 1];
-    uint4* Ft = which == 0 ? c->FA : c->FB;
-    const unsigned char* mk = (which == 0 && c->has_mask) ? c->mask : nullptr;
-    const int hstart = (int)(c->H - c->H1);
-    const int nxt = c->NH >= 8 ? VBMF_POST_NXT8 : 1;                          // = PostCfg<NH>::NXT
-    const int grid = (cdiv(d.XT, nxt) + 3) / 4;
-    double* trp = (which == 1 && !c->diagvar && 4 * grid <= c->trpart_cap) ? c->trpart : nullptr;   // (diag_var rescales the rows afterwards)
+// What a B-side post kernel leaves beside B for the Gram reduction behind it (launch_post, both branches of launch_post_frag,
+// launch_post_gram; grid: the launch's workgroups, four waves each): trp, the per-wave shares of tr(B'YA), c->ntr of which then wait
+// in c->trpart (not with heteroscedastic rows: B is rescaled afterwards); fd, the delta tiles old - new; store_fac = 0 inside a run
+// whose delta-Gram needs no fp32 B (the operand tiles carry the factor: rebuild_B32_if_stale).  The A side touches nothing.
+// The four launchers' own copies agreed wherever each is reached: vbmf_create allocates c->FD exactly when
+// NH >= 4, the mode is not fp32 and diag_var is off, so every "may this launch write delta tiles" test IS c->FD; post_gram's grid is at
+// most gslab_cap <= trpart_cap / 4, so the capacity test it left out always held; and c->ntr is read only by the reduction of a B
+// update, behind the B-side launch of that update, so launch_post's reset on the A side was never seen.
+// fused_delta is the one real difference: post_gram2 forms the delta-Gram itself (the previous rows from their operand tiles) and skips
+// the store without delta tiles; behind the other kernels launch_gram, lacking delta tiles, needs both fp32 factors stored.
+struct BSideOut { double* trp; uint4* fd; int store_fac; };
+static BSideOut b_side_outputs(vbmf_ctx* c, int which, int grid, bool fused_delta) {
+    if (which != 1) return BSideOut{nullptr, nullptr, 1};
+    double* trp = (!c->diagvar && 4 * grid <= c->trpart_cap) ? c->trpart : nullptr;
     c->ntr = trp ? 4 * grid : 0;
+    uint4* fd = c->FD;
+    const int store_fac = (c->in_run && (fd != nullptr || fused_delta)) ? 0 : 1;
+    c->cache.delta_tiles_written(fd != nullptr);
+    if (!store_fac) c->cache.B32_store_skipped();
+    return BSideOut{trp, fd, store_fac};
+}
+
+static int launch_post(vbmf_ctx* c, int which, const float* In, int nslab) {
+    const Side sd = side_of(c, which, B_NEXT);
+    const long long ld = (long long)sd.d.XT * 32;
+    const long long slabStride = (long long)c->Hp * ld;
+    const int nxt = c->NH >= 8 ? VBMF_POST_NXT8 : 1;                          // = PostCfg<NH>::NXT
+    const int grid = (cdiv(sd.d.XT, nxt) + 3) / 4;
     // B side at H >= 128 (bf16 factor modes): delta tiles for the delta-Gram; inside the run loops no fp32 copy of B per sweep
     // (heteroscedastic rows: B = diag(sigmaVecHat) (Y A) SigmaB is scaled AFTER this kernel, from the fp32 factor it stores -- no
     //  delta tiles of the un-scaled product, and the fp32 store stays)
-    uint4* fd = (which == 1 && c->NH >= 4 && !c->diagvar) ? c->FD : nullptr;
-    const int store_fac = (fd != nullptr && c->in_run) ? 0 : 1;
-    if (which == 1) c->cache.delta_tiles_written(fd != nullptr);
-    if (!store_fac) c->cache.B32_store_skipped();
-    DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
-        hipLaunchKernelGGL((post_kernel<MODEc, NHc>), dim3(grid), dim3(256), 0, c->stream, In, ld, nslab, slabStride, S,
-                           Fac, Ft, mk, hstart, d.XT, c->ints + I_STOP, trp, fd, store_fac);
-    }));
+    const BSideOut bo = b_side_outputs(c, which, grid, false);
+    const bool ok = dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+        return dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+            hipLaunchKernelGGL((post_kernel<decltype(md)::value, decltype(nh)::value>), dim3(grid), dim3(256), 0, c->stream, In, ld, nslab,
+                               slabStride, sd.S, sd.Fac, sd.Ft, sd.mask, sd.hstart, sd.d.XT, c->ints + I_STOP, bo.trp, bo.fd, bo.store_fac);
+        });
+    });
+    if (!ok) NO_KERNEL(c);
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
@@ -585,7 +622,7 @@ static int launch_post(vbmf_ctx* c, int which, const float* In, int nslab) {
 // fused post + Gram (+ delta-Gram) for NH <= 2; reduction into the state block (or the all-reduce staging)
 static bool fused_gram(const vbmf_ctx* c) { return c->NH <= 2; }
 
-static int launch_pair_reduce(vbmf_ctx* c, int which, int nslab, int ntr = 0);
+static int gram_reduce_tail(vbmf_ctx* c, int which, bool gated, int ntr, bool pair_slabs, int nslab);
 
 // A (which = 0) or B (which = 1) from ONE fragment-major product (H >= 128): bf16 factor modes run the software-pipelined
 // post_frag2_kernel on a table pre-split into VBMF_POST_NT bf16 parts in order of use; the fp32 mode keeps the exact-f32 kernel
@@ -594,141 +631,121 @@ static int launch_pair_reduce(vbmf_ctx* c, int which, int nslab, int ntr = 0);
 #endif
 static bool frag_post(const vbmf_ctx* c) { return c->NH >= 4 && c->mode != MODE_F32; }
 static int launch_post_frag(vbmf_ctx* c, int which = 1, const float* In = nullptr) {
-    const Dims& d = which == 0 ? c->d1 : c->d2;
-    const float* S = which == 0 ? c->SA32 : c->SB32;
-    float* Fac = which == 0 ? c->A32 : c->B32[c->bcur ^ 1];
-    uint4* Ft = which == 0 ? c->FA : c->FB;
+    const Side sd = side_of(c, which, B_NEXT);
     if (In == nullptr) In = c->Q;
+    const float4* In4 = (const float4*)In;
     const int* stop = c->ints + I_STOP;
     if (c->mode == MODE_F32) {
         if (which != 1) FAIL(c, VBMF_ERR_INVALID, "fragment-major A update in the fp32 mode");
         const int nxt = c->NH >= 8 ? VBMF_POST_NXT8 : 1;                          // = PostCfg<NH>::NXT
-        const int grid = (cdiv(d.XT, nxt) + 3) / 4;
-        double* trp = (!c->diagvar && 4 * grid <= c->trpart_cap) ? c->trpart : nullptr;
-        c->ntr = trp ? 4 * grid : 0;
-        c->cache.delta_tiles_written(false);
-        if (c->NH == 4) hipLaunchKernelGGL((post_frag_kernel<MODE_F32, 4>), dim3(grid), dim3(256), 0, c->stream, (const float4*)In, S, Fac, Ft, (const unsigned char*)nullptr, 0, d.XT, stop, trp, (uint4*)nullptr, 1, (const uint4*)nullptr);
-        else hipLaunchKernelGGL((post_frag_kernel<MODE_F32, 8>), dim3(grid), dim3(256), 0, c->stream, (const float4*)In, S, Fac, Ft, (const unsigned char*)nullptr, 0, d.XT, stop, trp, (uint4*)nullptr, 1, (const uint4*)nullptr);
+        const int grid = (cdiv(sd.d.XT, nxt) + 3) / 4;
+        const BSideOut bo = b_side_outputs(c, which, grid, false);                // (no c->FD in the fp32 mode: no delta tiles, B stored)
+        if (!dispatch<4, 8>(c->NH, [&](auto nh) {
+                hipLaunchKernelGGL((post_frag_kernel<MODE_F32, decltype(nh)::value>), dim3(grid), dim3(256), 0, c->stream, In4, sd.S, sd.Fac, sd.Ft,
+                                   sd.mask, 0, sd.d.XT, stop, bo.trp, bo.fd, bo.store_fac, (const uint4*)nullptr);
+            })) NO_KERNEL(c);
         HIPCHK(c, hipGetLastError());
         return VBMF_OK;
     }
     // row tiles per wave: 256 accumulator registers' worth on the long side; ONE on a short side (the 10k-row A side would
     // otherwise occupy 20 workgroups)
-    const bool short_side = d.XT < 2048;
+    const bool short_side = sd.d.XT < 2048;
     // post_frag3 (table through LDS, two workgroups per CU): 128 accumulator registers per wave on the long side
     const int nxt = short_side ? 1 : (c->post3 ? (c->NH >= 8 ? 1 : 2) : (c->NH >= 8 ? VBMF_POST2_NXT8 : VBMF_POST2_NXT4));
-    const int grid = (cdiv(d.XT, nxt) + 3) / 4;
-    double* trp = (which == 1 && !c->diagvar && 4 * grid <= c->trpart_cap) ? c->trpart : nullptr;
-    if (which == 1) c->ntr = trp ? 4 * grid : 0;
-    uint4* fd = which == 1 ? c->FD : nullptr;
-    const int store_fac = (fd != nullptr && c->in_run) ? 0 : 1;
-    if (which == 1) c->cache.delta_tiles_written(fd != nullptr);
-    if (!store_fac) c->cache.B32_store_skipped();
-    const unsigned char* mk = (which == 0 && c->has_mask) ? c->mask : nullptr;
-    const int hstart = (int)(c->H - c->H1);
-    const int nthr = c->NH * 2 * c->NH * 64;
-    if (c->NH == 4) hipLaunchKernelGGL((split_table_parts_kernel<4, VBMF_POST_NT>), dim3((nthr + 255) / 256), dim3(256), 0, c->stream, S, c->SBf, stop);
-    else hipLaunchKernelGGL((split_table_parts_kernel<8, VBMF_POST_NT>), dim3((nthr + 255) / 256), dim3(256), 0, c->stream, S, c->SBf, stop);
-#define POST_FRAG2(NHc_, NXTc_, BS_)                                                                                              \
-    hipLaunchKernelGGL((post_frag2_kernel<MODEc, NHc_, NXTc_, VBMF_POST_NT, BS_>), dim3(grid), dim3(256), 0, c->stream,           \
-                       (const float4*)In, (const uint4*)c->SBf, Fac, Ft, mk, hstart, d.XT, stop, trp, fd, store_fac)
-#define POST_FRAG3(NHc_, NXTc_, BS_)                                                                                              \
-    hipLaunchKernelGGL((post_frag3_kernel<MODEc, NHc_, NXTc_, VBMF_POST_NT, BS_>), dim3(grid), dim3(256), 0, c->stream,           \
-                       (const float4*)In, (const uint4*)c->SBf, Fac, Ft, mk, hstart, d.XT, stop, trp, fd, store_fac)
-    if (c->post3) {
-        DISPATCH_MODE(c->mode, {
-            if constexpr (MODEc != MODE_F32) {
-                if (which == 0) {
-                    if (c->NH == 4) { if (short_side) POST_FRAG3(4, 1, false); else POST_FRAG3(4, 2, false); }
-                    else POST_FRAG3(8, 1, false);
-                } else {
-                    if (c->NH == 4) { if (short_side) POST_FRAG3(4, 1, true); else POST_FRAG3(4, 2, true); }
-                    else POST_FRAG3(8, 1, true);
-                }
-            }
+    const int grid = (cdiv(sd.d.XT, nxt) + 3) / 4;
+    const BSideOut bo = b_side_outputs(c, which, grid, false);
+    const uint4* Sf = c->SBf;
+    // one instance per (mode, NH, side) and per tile count that side length can pick: 1 or the kernel's long-side count at that NH
+    const bool ok = dispatch<MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+        return dispatch<4, 8>(c->NH, [&](auto nh) {
+            constexpr int MODEc = decltype(md)::value, NHc = decltype(nh)::value;
+            constexpr int LONG3 = NHc >= 8 ? 1 : 2, LONG2 = NHc >= 8 ? VBMF_POST2_NXT8 : VBMF_POST2_NXT4;
+            const int nthr = NHc * 2 * NHc * 64;
+            hipLaunchKernelGGL((split_table_parts_kernel<NHc, VBMF_POST_NT>), dim3((nthr + 255) / 256), dim3(256), 0, c->stream, sd.S, c->SBf, stop);
+            return dispatch<0, 1>(which, [&](auto bs) {
+                constexpr bool BS = decltype(bs)::value != 0;
+                if (c->post3) return dispatch<1, LONG3>(nxt, [&](auto nx) {
+                    hipLaunchKernelGGL((post_frag3_kernel<MODEc, NHc, decltype(nx)::value, VBMF_POST_NT, BS>), dim3(grid), dim3(256), 0, c->stream,
+                                       In4, Sf, sd.Fac, sd.Ft, sd.mask, sd.hstart, sd.d.XT, stop, bo.trp, bo.fd, bo.store_fac);
+                });
+                return dispatch<1, LONG2>(nxt, [&](auto nx) {
+                    hipLaunchKernelGGL((post_frag2_kernel<MODEc, NHc, decltype(nx)::value, VBMF_POST_NT, BS>), dim3(grid), dim3(256), 0, c->stream,
+                                       In4, Sf, sd.Fac, sd.Ft, sd.mask, sd.hstart, sd.d.XT, stop, bo.trp, bo.fd, bo.store_fac);
+                });
+            });
         });
-        HIPCHK(c, hipGetLastError());
-        return VBMF_OK;
-    }
-#undef POST_FRAG3
-    DISPATCH_MODE(c->mode, {
-        if constexpr (MODEc != MODE_F32) {
-            if (which == 0) {
-                if (c->NH == 4) { if (short_side) POST_FRAG2(4, 1, false); else POST_FRAG2(4, VBMF_POST2_NXT4, false); }
-                else { if (short_side) POST_FRAG2(8, 1, false); else POST_FRAG2(8, VBMF_POST2_NXT8, false); }
-            } else {
-                if (c->NH == 4) { if (short_side) POST_FRAG2(4, 1, true); else POST_FRAG2(4, VBMF_POST2_NXT4, true); }
-                else { if (short_side) POST_FRAG2(8, 1, true); else POST_FRAG2(8, VBMF_POST2_NXT8, true); }
-            }
-        }
     });
-#undef POST_FRAG2
+    if (!ok) NO_KERNEL(c);
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
 // post + Gram (+ delta-Gram, tr(B'YA)) of ONE fragment-major product (NH <= 2): post_gram2_kernel
 static int launch_post_gram(vbmf_ctx* c, int which, const float* In) {
-    const Dims& d = which == 0 ? c->d1 : c->d2;
-    const float* S = which == 0 ? c->SA32 : c->SB32;
-    float* Fac = which == 0 ? c->A32 : c->B32[c->bcur ^ 1];
-    uint4* Ft = which == 0 ? c->FA : c->FB;
-    const unsigned char* mk = (which == 0 && c->has_mask) ? c->mask : nullptr;
-    const int hstart = (int)(c->H - c->H1);
-    const int grid = std::min(c->gslab_cap, (d.XT + 3) / 4);
+    const Side sd = side_of(c, which, B_NEXT);
+    const int grid = std::min(c->gslab_cap, (sd.d.XT + 3) / 4);
     GSLAB_CHECK(c, grid, 2 * (c->NH * (c->NH + 1) / 2) * 1024);
-    const int* stop = c->ints + I_STOP;
-    double* trp = (which == 1 && !c->diagvar) ? c->trpart : nullptr;
     // inside the run loops the fp32 copy of B is not written per sweep: the operand tiles carry the factor (rebuilt once at the end)
-    const int store_fac = (which == 1 && c->in_run) ? 0 : 1;
-    if (!store_fac) c->cache.B32_store_skipped();
-    DISPATCH_MODE(c->mode, {
-        if (which == 0) {
-            if (c->NH == 1) hipLaunchKernelGGL((post_gram2_kernel<MODEc, 1, false>), dim3(grid), dim3(256), 0, c->stream, In, S, Fac, Ft, mk, hstart, d.XT, c->gslab, stop, trp, store_fac);
-            else hipLaunchKernelGGL((post_gram2_kernel<MODEc, 2, false>), dim3(grid), dim3(256), 0, c->stream, In, S, Fac, Ft, mk, hstart, d.XT, c->gslab, stop, trp, store_fac);
-        } else {
-            if (c->NH == 1) hipLaunchKernelGGL((post_gram2_kernel<MODEc, 1, true>), dim3(grid), dim3(256), 0, c->stream, In, S, Fac, Ft, mk, hstart, d.XT, c->gslab, stop, trp, store_fac);
-            else hipLaunchKernelGGL((post_gram2_kernel<MODEc, 2, true>), dim3(grid), dim3(256), 0, c->stream, In, S, Fac, Ft, mk, hstart, d.XT, c->gslab, stop, trp, store_fac);
-        }
+    const BSideOut bo = b_side_outputs(c, which, grid, true);
+    const bool ok = dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+        return dispatch<1, 2>(c->NH, [&](auto nh) {
+            return dispatch<0, 1>(which, [&](auto bs) {
+                hipLaunchKernelGGL((post_gram2_kernel<decltype(md)::value, decltype(nh)::value, decltype(bs)::value != 0>), dim3(grid), dim3(256), 0,
+                                   c->stream, In, sd.S, sd.Fac, sd.Ft, sd.mask, sd.hstart, sd.d.XT, c->gslab, c->ints + I_STOP, bo.trp, bo.store_fac);
+            });
+        });
     });
+    if (!ok) NO_KERNEL(c);
     HIPCHK(c, hipGetLastError());
-    return launch_pair_reduce(c, which, grid, trp ? 4 * grid : 0);
+    return gram_reduce_tail(c, which, true, bo.trp ? 4 * grid : 0, true, grid);
 }
 
-// fp64 reduction of `nslab` workgroup slabs of Gram partials in c->gslab into the state (all-reduced when row-sharded)
-static int launch_pair_reduce(vbmf_ctx* c, int which, int nslab, int ntr) {
-    const int* stop = c->ints + I_STOP;
+// The end of every Gram of a factor: fp64 reduction of the `nslab` partial slabs in c->gslab (pair slabs: the upper pairs only, as the
+// fused kernels and gram_tiles3 leave them; else dense) and of the `ntr` trace shares into the state -- or, B side of a row-sharded
+// run, into the packed message [B'B | dB'dB | tr(B'YA) | error flag] that one all-reduce puts straight into the state block (GB, GD, GX
+// are contiguous).  gated = false (ensure_gram_B: state just set, no sweep has run): no stop test, and only the Gram travels.
+static int gram_reduce_tail(vbmf_ctx* c, int which, bool gated, int ntr, bool pair_slabs, int nslab) {
+    const int* stop = gated ? c->ints + I_STOP : nullptr;
     const int n = c->Hp * c->Hp;
     const bool shard = (which == 1 && sharded(c));
     double* outG = shard ? c->gtmp : c->st + (which == 0 ? c->lay.GA() : c->lay.GB());
     double* outD = which == 0 ? nullptr : (shard ? c->gtmp + n : c->st + c->lay.GD());
     double* outTr = (which == 1 && ntr > 0) ? (shard ? c->gtmp + 2 * n : c->st + c->lay.GX()) : nullptr;
-    double* outErr = shard ? c->gtmp + 2 * n + 1 : nullptr;       // this rank's error flag rides in the packed message
-    if (c->NH == 1) hipLaunchKernelGGL((pair_slab_reduce_kernel<1>), dim3(2 * 1 * 1024 / 64), dim3(1024), 0, c->stream, c->gslab, nslab, outG, outD, stop, c->trpart, ntr, outTr, outErr);
-    else hipLaunchKernelGGL((pair_slab_reduce_kernel<2>), dim3(2 * 3 * 1024 / 64), dim3(1024), 0, c->stream, c->gslab, nslab, outG, outD, stop, c->trpart, ntr, outTr, outErr);
-    HIPCHK(c, hipGetLastError());
-    if (shard) {
-        if (!c->comm_ready) FAIL(c, VBMF_ERR_COMM, "nranks > 1 but vbmf_comm_init was not called");
-        // [B'B | dB'dB | tr(B'YA)] in one message, straight into the state block (GB, GD, GX are contiguous)
-        // [B'B | dB'dB | tr(B'YA) | error flag] in one message, straight into the state block (GB, GD, GX are contiguous)
-        TRY(allreduce_sum(c, c->gtmp, c->st + c->lay.GB(), 2 * (size_t)n + 2, true));
+    double* outErr = (shard && gated) ? c->gtmp + 2 * n + 1 : nullptr;   // this rank's error flag rides in the packed message
+    if (pair_slabs) {
+        if (!dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+                constexpr int NHc = decltype(nh)::value, NPAIR = NHc * (NHc + 1) / 2;
+                hipLaunchKernelGGL((pair_slab_reduce_kernel<NHc>), dim3(2 * NPAIR * 1024 / 64), dim3(1024), 0, c->stream, c->gslab, nslab, outG, outD,
+                                   stop, c->trpart, ntr, outTr, outErr);
+            })) NO_KERNEL(c);
+    } else {
+        hipLaunchKernelGGL(gram_reduce_kernel, dim3((2 * n + 31) / 32), dim3(256), 0, c->stream, c->gslab, nslab, n,
+                           outG, outD, stop, c->trpart, ntr, outTr, outErr);
     }
+    HIPCHK(c, hipGetLastError());
+    // (sharded(c) is "a communicator is attached": the collective below cannot find none)
+    if (shard) TRY(allreduce_sum(c, c->gtmp, c->st + c->lay.GB(), gated ? 2 * (size_t)n + 2 : (size_t)n, true));
     return VBMF_OK;
 }
 
 // which = 0: A (x tiles of pass 1's factor... i.e. M rows), 1: B (L rows).  Fac -> operand tiles Ft; with writeback the
 // fp32 factor becomes exactly what the tiles encode.  rowscale: per-row factor applied on the way (heteroscedastic rows).
 static int launch_retile_ex(vbmf_ctx* c, int which, float* Fac, uint4* Ft, const float* rowscale, int writeback, bool gated) {
-    const Dims& d = which == 0 ? c->d1 : c->d2;
-    const int grid = (d.XT + 3) / 4;
-    DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
-        hipLaunchKernelGGL((retile_kernel<MODEc, NHc>), dim3(grid), dim3(256), 0, c->stream, Fac, Ft, d.XT, rowscale, writeback,
-                           gated ? c->ints + I_STOP : (const int*)nullptr);
-    }));
+    const int XT = which == 0 ? c->d1.XT : c->d2.XT;
+    const int grid = (XT + 3) / 4;
+    const bool ok = dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+        return dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+            hipLaunchKernelGGL((retile_kernel<decltype(md)::value, decltype(nh)::value>), dim3(grid), dim3(256), 0, c->stream, Fac, Ft, XT, rowscale,
+                               writeback, gated ? c->ints + I_STOP : (const int*)nullptr);
+        });
+    });
+    if (!ok) NO_KERNEL(c);
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
+// the side's own factor, in place: the CURRENT B, not the one an update is writing
 static int launch_retile(vbmf_ctx* c, int which, bool gated = false) {
-    return launch_retile_ex(c, which, which == 0 ? c->A32 : c->B32[c->bcur], which == 0 ? c->FA : c->FB, nullptr, 1, gated);
+    const Side sd = side_of(c, which, B_CUR);
+    return launch_retile_ex(c, which, sd.Fac, sd.Ft, nullptr, 1, gated);
 }
 
 // 32-row tiles per Gram chunk (= per workgroup) of side `which`.  H >= 128: a chunk's slab is 2 Hp^2 floats (512 KiB at H = 256), so
@@ -743,68 +760,41 @@ static int gram_tiles_per_chunk(const vbmf_ctx* c, int which) {
 }
 // Gram of A (which=0) or of B with optional delta-Gram against prev (which=1) into the state block.
 static int launch_gram(vbmf_ctx* c, int which, const float* cur, const float* prev, bool gated, int ntr = 0) {
-    const Dims& d = which == 0 ? c->d1 : c->d2;
+    const Side sd = side_of(c, which, B_NEXT);         // (its Dims and tiles: the fp32 factors come as `cur` and `prev`)
+    const int XT = sd.d.XT;
     const int tpc = gram_tiles_per_chunk(c, which);
-    const int nchunk = cdiv(d.XT, tpc);
+    const int nchunk = cdiv(XT, tpc);
     const int nw = nchunk * c->NH * c->NH;
     const int* stop = gated ? c->ints + I_STOP : nullptr;
     // H >= 128 with a bf16 factor: from the operand tiles with bf16 MFMAs (the tiles of `cur` are current whenever a
     // Gram of it is asked for: every producer of the fp32 factor writes them in the same kernel)
     const bool from_tiles = c->NH >= 4 && c->mode != MODE_F32;
-    bool pair_slabs = false;
+    // delta-Gram: a plain tile Gram of the delta tiles the post kernel left (two parts: hi + lo) -- or, without them
+    // (f32-free callers that bring their own previous fp32 factor), from `prev` with row gathers
+    const bool from_fd = from_tiles && which == 1 && prev != nullptr && c->cache.delta_tiles() && c->FD != nullptr;
+    const bool pair_slabs = from_tiles && (from_fd || prev == nullptr);      // gram_tiles3 leaves pair slabs (the H <= 64 kernels' format)
     GSLAB_CHECK(c, nchunk, 2 * c->Hp * c->Hp);         // dense slabs; pair slabs (upper pairs only) are smaller
+    bool ok;
     if (from_tiles) {
-        const uint4* Ft = which == 0 ? c->FA : c->FB;
-        // delta-Gram: a plain tile Gram of the delta tiles the post kernel left (two parts: hi + lo) -- or, without them
-        // (f32-free callers that bring their own previous fp32 factor), from `prev` with row gathers
-        const bool from_fd = which == 1 && prev != nullptr && c->cache.delta_tiles() && c->FD != nullptr;
-        pair_slabs = from_fd || prev == nullptr;
-#define GRAM_TILES(NHc_, NPc_)                                                                                               \
-    do {                                                                                                                         \
-        if (from_fd || prev == nullptr) {                                                                                        \
-            hipLaunchKernelGGL((gram_tiles3_kernel<NHc_, NPc_>), dim3(nchunk), dim3(256), 0, c->stream, Ft,                        \
-                               from_fd ? (const uint4*)c->FD : (const uint4*)nullptr, c->gslab, d.XT, tpc, stop);  \
-        } else {                                                                                                                 \
-            hipLaunchKernelGGL((gram_tiles_kernel<NHc_, NPc_, 0>), dim3(nchunk), dim3(256), 0, c->stream, Ft, prev, c->gslab,      \
-                               d.XT, tpc, stop, 0);                                                               \
-            hipLaunchKernelGGL((gram_tiles_kernel<NHc_, NPc_, 1>), dim3(nchunk), dim3(256), 0, c->stream, Ft, prev, c->gslab,      \
-                               d.XT, tpc, stop, 1);                                                               \
-        }                                                                                                                        \
-    } while (0)
-        if (c->NH == 4) { if (c->npart == 2) GRAM_TILES(4, 2); else GRAM_TILES(4, 1); }
-        else { if (c->npart == 2) GRAM_TILES(8, 2); else GRAM_TILES(8, 1); }
-#undef GRAM_TILES
+        ok = dispatch<4, 8>(c->NH, [&](auto nh) {
+            return dispatch<1, 2>(c->npart, [&](auto np) {
+                constexpr int NHc = decltype(nh)::value, NPc = decltype(np)::value;
+                if (pair_slabs) {
+                    hipLaunchKernelGGL((gram_tiles3_kernel<NHc, NPc>), dim3(nchunk), dim3(256), 0, c->stream, sd.Ft,
+                                       from_fd ? (const uint4*)c->FD : (const uint4*)nullptr, c->gslab, XT, tpc, stop);
+                } else {
+                    hipLaunchKernelGGL((gram_tiles_kernel<NHc, NPc, 0>), dim3(nchunk), dim3(256), 0, c->stream, sd.Ft, prev, c->gslab, XT, tpc, stop, 0);
+                    hipLaunchKernelGGL((gram_tiles_kernel<NHc, NPc, 1>), dim3(nchunk), dim3(256), 0, c->stream, sd.Ft, prev, c->gslab, XT, tpc, stop, 1);
+                }
+            });
+        });
     } else {
-        DISPATCH_NH(c->NH, {
-            hipLaunchKernelGGL((gram_kernel<NHc>), dim3((nw + 3) / 4), dim3(256), 0, c->stream, cur, prev, c->gslab, d.XT,
-                               tpc, nchunk, stop);
+        ok = dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+            hipLaunchKernelGGL((gram_kernel<decltype(nh)::value>), dim3((nw + 3) / 4), dim3(256), 0, c->stream, cur, prev, c->gslab, XT, tpc, nchunk, stop);
         });
     }
-    const int n = c->Hp * c->Hp;
-    const bool shard = (which == 1 && sharded(c));
-    double* outG = shard ? c->gtmp : c->st + (which == 0 ? c->lay.GA() : c->lay.GB());
-    double* outD = which == 0 ? nullptr : (shard ? c->gtmp + n : c->st + c->lay.GD());
-    double* outTr = (which == 1 && ntr > 0) ? (shard ? c->gtmp + 2 * n : c->st + c->lay.GX()) : nullptr;
-    double* outErr = (shard && gated) ? c->gtmp + 2 * n + 1 : nullptr;   // this rank's error flag rides in the packed message
-    if (pair_slabs) {                              // gram_tiles3 leaves pair slabs (the H <= 64 kernels' format)
-        if (c->NH == 4) hipLaunchKernelGGL((pair_slab_reduce_kernel<4>), dim3(2 * 10 * 1024 / 64), dim3(1024), 0, c->stream, c->gslab, nchunk, outG, outD, stop, c->trpart, ntr, outTr, outErr);
-        else hipLaunchKernelGGL((pair_slab_reduce_kernel<8>), dim3(2 * 36 * 1024 / 64), dim3(1024), 0, c->stream, c->gslab, nchunk, outG, outD, stop, c->trpart, ntr, outTr, outErr);
-    } else {
-        hipLaunchKernelGGL(gram_reduce_kernel, dim3((2 * n + 31) / 32), dim3(256), 0, c->stream, c->gslab, nchunk, n,
-                           outG, outD, stop, c->trpart, ntr, outTr, outErr);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (shard) {
-        if (!c->comm_ready) FAIL(c, VBMF_ERR_COMM, "nranks > 1 but vbmf_comm_init was not called");
-        if (!gated) {
-            // an un-gated Gram (ensure_gram_B: state just set, no sweep has run) leaves the other two parts of the
-            // message alone: reduce the Gram only
-            TRY(allreduce_sum(c, c->gtmp, c->st + c->lay.GB(), (size_t)n, true));
-        } else {
-            TRY(allreduce_sum(c, c->gtmp, c->st + c->lay.GB(), 2 * (size_t)n + 2, true));
-        }
-    }
-    return VBMF_OK;
+    if (!ok) NO_KERNEL(c);
+    return gram_reduce_tail(c, which, gated, ntr, pair_slabs, nchunk);
 }
 
 static int ctrl_threads(int H) { return H <= 16 ? 64 : (H <= 32 ? 256 : 1024); }
@@ -832,46 +822,34 @@ static int side_join(vbmf_ctx* c) {
 }
 static bool side_overlap(const vbmf_ctx* c) { return c->in_run && c->NH == 8; }
 
+// dynamic LDS of the covariance kernels (ctrl_cov, sparse_cov_b) at a control tier
 template <int R, int T>
-static void launch_cov_t(vbmf_ctx* c, int which, hipStream_t s) {
-    const size_t lds = (R == 8 && T == 32) ? (size_t)(INV256_LDS_DOUBLES + 256) * sizeof(double) : spd_inverse_lds_bytes(R);
-    const double N = which == 0 ? (double)c->Lg : (double)c->M;
-    hipLaunchKernelGGL((ctrl_cov_kernel<R, T>), dim3(1), dim3(T * T), lds, s, c->st, c->lay, (int)c->H, which, N,
-                       which == 0 ? c->SA32 : c->SB32, c->ints);
-}
+constexpr size_t cov_lds_bytes() { return (R == 8 && T == 32) ? (size_t)(INV256_LDS_DOUBLES + 256) * sizeof(double) : spd_inverse_lds_bytes(R); }
 
 static int launch_ctrl_cov(vbmf_ctx* c, int which) {
-    const int H = (int)c->H;
-    hipStream_t s = ctrl_stream(c);
-    if (H <= 16) launch_cov_t<1, 16>(c, which, s);
-    else if (H <= 32) launch_cov_t<2, 16>(c, which, s);
-    else if (H <= 64) launch_cov_t<4, 16>(c, which, s);
-    else if (H <= 128) launch_cov_t<8, 16>(c, which, s);
-    else launch_cov_t<8, 32>(c, which, s);
+    const double N = which == 0 ? (double)c->Lg : (double)c->M;
+    float* S32 = which == 0 ? c->SA32 : c->SB32;
+    ctrl_tier(c->H, [&](auto r, auto t) {
+        constexpr int R = decltype(r)::value, T = decltype(t)::value;
+        hipLaunchKernelGGL((ctrl_cov_kernel<R, T>), dim3(1), dim3(T * T), (cov_lds_bytes<R, T>()), ctrl_stream(c), c->st, c->lay, (int)c->H, which,
+                           N, S32, c->ints);
+    });
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
 
-template <int R>
-static void launch_eig_t(vbmf_ctx* c, int do_d, int do_b, hipStream_t s) {
-    constexpr int NP = 16 * R;
-    const size_t lds = std::max(R <= 4 ? (size_t)2 * NP * (NP + 4) * sizeof(float) : (size_t)0, (size_t)EIG_LDS_BYTES);     // squaring | Lanczos
-    const int spectral = spectral_arg(c);
-    hipLaunchKernelGGL((eig_kernel<R>), dim3(2), dim3(256), lds, s, c->st, c->lay, (int)c->H, spectral, do_d, do_b,
-                       c->ints);
-}
-
 static int launch_eig(vbmf_ctx* c, int do_d, int do_b) {
-    const int H = (int)c->H;
+    const int H = (int)c->H, spectral = spectral_arg(c);
     hipStream_t s = ctrl_stream(c);
-    if (H <= 16) launch_eig_t<1>(c, do_d, do_b, s);
-    else if (H <= 32) launch_eig_t<2>(c, do_d, do_b, s);
-    else if (H <= 64) launch_eig_t<4>(c, do_d, do_b, s);
-    else if (H <= 128) launch_eig_t<8>(c, do_d, do_b, s);
-    else {
-        const int spectral = spectral_arg(c);
-        hipLaunchKernelGGL(eig_lanczos_kernel, dim3(2), dim3(1024), 0, s, c->st, c->lay, H, spectral, do_d, do_b, c->ints);
-    }
+    ctrl_tier(H, [&](auto r, auto t) {
+        constexpr int R = decltype(r)::value, NP = 16 * R;
+        if constexpr (decltype(t)::value == 32) {             // 128 < H <= 256: the stand-alone Lanczos kernel
+            hipLaunchKernelGGL(eig_lanczos_kernel, dim3(2), dim3(1024), 0, s, c->st, c->lay, H, spectral, do_d, do_b, c->ints);
+        } else {
+            const size_t lds = std::max(R <= 4 ? (size_t)2 * NP * (NP + 4) * sizeof(float) : (size_t)0, (size_t)EIG_LDS_BYTES);     // squaring | Lanczos
+            hipLaunchKernelGGL((eig_kernel<R>), dim3(2), dim3(256), lds, s, c->st, c->lay, H, spectral, do_d, do_b, c->ints);
+        }
+    });
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
@@ -1009,7 +987,7 @@ static int do_update_B(vbmf_ctx* c, bool keep_sigma = false) {
             if (!keep_sigma) TRY(launch_ctrl_cov(c, 1));
             TRY(launch_stream(c, 1, 0, true, &nslab));
         }
-        TRY(launch_pair_reduce(c, 1, nslab, c->ntr));
+        TRY(gram_reduce_tail(c, 1, true, c->ntr, true, nslab));
         c->bcur ^= 1;
         c->cache.B_moved_basic();
         return VBMF_OK;
@@ -1159,68 +1137,53 @@ static int gram_product(vbmf_ctx* c, bool partials) {
     const float* Wo = c->W32g[c->wcur];
     float* Wn = c->W32g[c->wcur ^ 1];
     const dim3 wg(cdiv(KT, GW_KS));
-    if (c->Hp == 32) hipLaunchKernelGGL((gram_w_kernel<32>), wg, dim3(128), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
-    else if (c->Hp == 64) hipLaunchKernelGGL((gram_w_kernel<64>), wg, dim3(256), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
-    else if (c->Hp == 128) hipLaunchKernelGGL((gram_w_kernel<128>), wg, dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
-    else if (c->Hp == 256) hipLaunchKernelGGL((gram_w_cols_kernel<256, 2>), dim3(wg.x, 2), dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
-    else FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 256");
-    HIPCHK(c, hipGetLastError());
-    float* out = c->g_nsplit > 1 ? c->gslabs : c->gPQ;
-    const dim3 grid(c->g_nrg * c->g_nsplit, c->NH / gram_prod_nh(c));
-    const float4* G4 = reinterpret_cast<const float4*>(c->Gt);
-    prof_begin(c, 0);
-    if (c->NH == 1) hipLaunchKernelGGL((gram_prod_kernel<1>), grid, dim3(GramProd<1>::THREADS), GramProd<1>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    else if (c->NH == 2) hipLaunchKernelGGL((gram_prod_kernel<2>), grid, dim3(GramProd<2>::THREADS), GramProd<2>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    else if (c->NH == 4) hipLaunchKernelGGL((gram_prod_kernel<4>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    else hipLaunchKernelGGL((gram_prod_kernel<4, 8>), grid, dim3(GramProd<4>::THREADS), GramProd<4>::LDS_BYTES, c->stream, G4, c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
-    prof_end(c);
-    HIPCHK(c, hipGetLastError());
-    if (!partials) {
-        // no shares wanted (the run boundary): only the folded [P | Q], by the plain slab sum
-        if (c->g_nsplit > 1) {
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(2 * n / 4, 256, 2048)), dim3(256), 0, c->stream, c->gslabs, c->g_nsplit, 2 * n,
-                               c->gPQ, 2 * n, stop, SideCopy{});
-            HIPCHK(c, hipGetLastError());
+    // rank 256 (Hp = 256, NH = 8) runs as blocks of the rank-128 geometry: W in two column groups, the product in two h-tile groups of
+    // the NH = 4 kernel, the shares in four 128 x 128 blocks per product
+    const bool ok = dispatch<32, 64, 128, 256>(c->Hp, [&](auto hp) {
+        constexpr int HPT = decltype(hp)::value, HPc = HPT == 256 ? 128 : HPT;
+        if constexpr (HPT == 256)
+            hipLaunchKernelGGL((gram_w_cols_kernel<256, 2>), dim3(wg.x, 2), dim3(512), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+        else
+            hipLaunchKernelGGL((gram_w_kernel<HPT>), wg, dim3(HPT * 4), 0, c->stream, c->A32, c->SB32, Wo, Wn, c->Wt, (long long)c->M, KT, stop);
+        float* out = c->g_nsplit > 1 ? c->gslabs : c->gPQ;
+        const dim3 grid(c->g_nrg * c->g_nsplit, c->NH / gram_prod_nh(c));
+        prof_begin(c, 0);
+        {
+            constexpr int NHT = HPT / 32, NHc = NHT == 8 ? 4 : NHT;           // = gram_prod_nh
+            hipLaunchKernelGGL((gram_prod_kernel<NHc, NHT>), grid, dim3(GramProd<NHc>::THREADS), GramProd<NHc>::LDS_BYTES, c->stream,
+                               reinterpret_cast<const float4*>(c->Gt), c->Wt, out, c->GT, c->d1.XT, c->g_sps, c->g_nrg, n, 2 * n, stop);
         }
-    } else {
+        prof_end(c);
+        if (!partials) {
+            // no shares wanted (the run boundary): only the folded [P | Q], by the plain slab sum
+            if (c->g_nsplit > 1)
+                hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(2 * n / 4, 256, 2048)), dim3(256), 0, c->stream, c->gslabs, c->g_nsplit, 2 * n,
+                                   c->gPQ, 2 * n, stop, SideCopy{});
+            return;
+        }
         // the slabs folded into gPQ (one split: gPQ read in place) and the chunk shares from the folded values, in one launch
-        const dim3 tg(2 * c->g_nchunk);
-        const long long M = (long long)c->M;
-        if (c->Hp == 32) hipLaunchKernelGGL((gram_tail_kernel<32>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
-        else if (c->Hp == 64) hipLaunchKernelGGL((gram_tail_kernel<64>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
-        else if (c->Hp == 128) hipLaunchKernelGGL((gram_tail_kernel<128>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
-        else hipLaunchKernelGGL((gram_tail_kernel<128, 256>), dim3(8 * c->g_nchunk), dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo, c->A32, M, c->g_rpc, c->g_nchunk, c->g_part, stop);
-        HIPCHK(c, hipGetLastError());
+        const dim3 tg((HPT == 256 ? 8 : 2) * c->g_nchunk);
+        hipLaunchKernelGGL((gram_tail_kernel<HPc, HPT>), tg, dim3(512), 0, c->stream, out, c->g_nsplit, 2 * n, c->gPQ, n, (long long)Mp1, Wn, Wo,
+                           c->A32, (long long)c->M, c->g_rpc, c->g_nchunk, c->g_part, stop);
         const dim3 rg(cdiv(2 * (int64_t)c->Hp * c->Hp + 1, GRED_E));
-        if (c->Hp == 32) hipLaunchKernelGGL((gram_part_reduce_kernel<32>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
-        else if (c->Hp == 64) hipLaunchKernelGGL((gram_part_reduce_kernel<64>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
-        else if (c->Hp == 128) hipLaunchKernelGGL((gram_part_reduce_kernel<128>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
-        else hipLaunchKernelGGL((gram_part_reduce_kernel<128, 256>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
-        HIPCHK(c, hipGetLastError());
-    }
+        hipLaunchKernelGGL((gram_part_reduce_kernel<HPc, HPT>), rg, dim3(256), 0, c->stream, c->g_part, c->g_nchunk, c->st, c->lay, stop);
+    });
+    if (!ok) FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 256");
+    HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
 
 // the control chain as a launch of its own (ctrl_chain_kernel: one workgroup per part of ctrl_chain that the mode asks for).  R follows
 // H as for the stand-alone control kernels, so every fp64 operation sees the inputs, the work split and the summation order it saw there.
-template <int R>
-static void launch_chain_t(vbmf_ctx* c, const CtrlArgs& ca) {
-    const int parts = (ca.mode & CTRL_EIG_AHEAD) ? 3 : ((ca.mode & (CTRL_PREV_END | CTRL_EIG_BOLD)) ? 2 : 1);
-    hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(parts), dim3(256), ctrl_lds_bytes_r(R), c->stream, ca);
-}
 static int launch_chain(vbmf_ctx* c, int mode, float* S32) {
-    CtrlArgs ca{};
-    ca.st = c->st; ca.lay = c->lay; ca.ints = c->ints; ca.trace = c->run_trace;
-    ca.S32 = S32;
-    ca.Lg = (double)c->Lg; ca.M = (double)c->M; ca.eps = c->run_eps;
-    ca.H = (int)c->H; ca.spectral = spectral_arg(c);
-    ca.end_flags = c->run_flags; ca.mode = mode; ca.it_row = (int)c->ends_enqueued; ca.loopw = loop_words(c);
-    const int H = (int)c->H;
-    if (H <= 16) launch_chain_t<1>(c, ca);
-    else if (H <= 32) launch_chain_t<2>(c, ca);
-    else if (H <= 64) launch_chain_t<4>(c, ca);
-    else if (H <= 128) launch_chain_t<8>(c, ca);
-    else FAIL(c, VBMF_ERR_INVALID, "internal: the stand-alone control chain covers H <= 128");
+    if (c->H > 128) FAIL(c, VBMF_ERR_INVALID, "internal: the stand-alone control chain covers H <= 128");
+    const CtrlArgs ca = ctrl_args(c, mode, S32);
+    const int parts = (mode & CTRL_EIG_AHEAD) ? 3 : ((mode & (CTRL_PREV_END | CTRL_EIG_BOLD)) ? 2 : 1);
+    ctrl_tier(c->H, [&](auto r, auto t) {
+        constexpr int R = decltype(r)::value;
+        if constexpr (decltype(t)::value == 16)
+            hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(parts), dim3(256), ctrl_lds_bytes_r(R), c->stream, ca);
+    });
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
@@ -1315,9 +1278,13 @@ static int device_err_status(vbmf_ctx* c, int e) {
 static int rebuild_B32_if_stale(vbmf_ctx* c) {
     if (!c->cache.B32_stale()) return VBMF_OK;
     const int grid = (c->d2.XT + 3) / 4;
-    DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
-        hipLaunchKernelGGL((untile_factor_kernel<MODEc, NHc>), dim3(grid), dim3(256), 0, c->stream, c->FB, c->B32[c->bcur], c->d2.XT);
-    }));
+    const bool ok = dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+        return dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+            hipLaunchKernelGGL((untile_factor_kernel<decltype(md)::value, decltype(nh)::value>), dim3(grid), dim3(256), 0, c->stream, c->FB,
+                               c->B32[c->bcur], c->d2.XT);
+        });
+    });
+    if (!ok) NO_KERNEL(c);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cache.B32_rebuilt();
@@ -1763,6 +1730,10 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
             // 128 < H <= 256: the register-resident blocked sweep's two panel strips (70 KB: above the 64 KB a launch may ask for unannounced)
             {(const void*)ctrl_cov_kernel<8, 32>, lim, 0}, {(const void*)sparse_cov_b_kernel<8, 32>, lim, 0},
             {(const void*)sparse_update_a_full256_kernel, lim, 0},
+            // full_cov A update at H <= 64, one column per wavefront: a wavefront's image and column (19 / 70 / 134 KB per workgroup)
+            {(const void*)sparse_update_a_full_wave_kernel<1, 8>, (int)full_a_wave_lds_bytes(1, 8), 0},
+            {(const void*)sparse_update_a_full_wave_kernel<2, 8>, (int)full_a_wave_lds_bytes(2, 8), 0},
+            {(const void*)sparse_update_a_full_wave_kernel<4, 4>, (int)full_a_wave_lds_bytes(4, 4), 0},
             // vbls! as H x H algebra at 32 < H <= 64: four 64 x 66 fp64 images (135 KB)
             {(const void*)vbls_loop_kernel<4>, vb, 0}, {(const void*)vbls_batch_kernel<4>, vb, 0},
             // batched vbls! of the sparse models, full_cov at 32 < H <= 64: four 64 x 66 fp64 images and the bag's state
@@ -1790,8 +1761,8 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
                 e = hipFuncSetAttribute(r.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, r.bytes);
         if (e == hipSuccess && c->NH == 4) {
             using Cfg = StreamCfg<4>;
-            DISPATCH_MODE(c->mode, {
-                e = hipFuncSetAttribute((const void*)stream_gemm_kernel<MODEc, 4, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>,
+            dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+                e = hipFuncSetAttribute((const void*)stream_gemm_kernel<decltype(md)::value, 4, Cfg::NXWc, Cfg::DYc, Cfg::DFc, Cfg::Rc>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
             });
         }
@@ -1813,8 +1784,8 @@ struct TileRange { int xa, xb, ka, kb; };
 template <class Src>
 static int launch_tiles(vbmf_ctx* c, const Src& src, TileRange r1, TileRange r2, double* sumsq) {
     const int64_t n1 = (int64_t)(r1.xb - r1.xa) * (r1.kb - r1.ka) * 64, n2 = (int64_t)(r2.xb - r2.xa) * (r2.kb - r2.ka) * 64;
-    DISPATCH_MODE(c->mode, {
-        constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
+    dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+        constexpr int TM = decltype(ym)::value;
         hipLaunchKernelGGL((tile_y_kernel<TM, false, Src>), dim3(grid_for(n1, 256, 16384)), dim3(256), 0, c->stream, c->Y1,
                            src, r1.xa, r1.xb, r1.ka, r1.kb, c->d1.KS, (double*)nullptr);
         const int g2 = grid_for(n2, 256, 16384);
@@ -1868,8 +1839,8 @@ static int launch_tile_pair(vbmf_ctx* c, const T* dev, int64_t l0, int64_t l1, i
         g.xb0 = x2a; g.xb1 = x2b; g.kb0 = 0; g.kb1 = c->d2.KS; g.KSB = c->d2.KS; outB = c->Y2;
     }
     const int grid = (int)std::min<int64_t>((int64_t)g.ns * g.nu, 16384);   // c->ypart holds 16384 partials
-    DISPATCH_MODE(c->mode, {
-        constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
+    dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+        constexpr int TM = decltype(ym)::value;
         hipLaunchKernelGGL((tile_pair_kernel<TM, T>), dim3(grid), dim3(256), 0, c->stream, outA, outB, dev, g, c->ypart);
         hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, c->ypart, grid, sumsq);
     });
@@ -1900,8 +1871,8 @@ static int finish_Y(vbmf_ctx* c) {
     c->cache.Y_complete(!sharded(c) && c->o.nranks == 1);
     c->y_rows = c->L;
     if (c->diagvar) {                                  // ||Y_l||^2 of every row (:310), from the stored values
-        DISPATCH_MODE(c->mode, {
-            constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
+        dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+            constexpr int TM = decltype(ym)::value;
             hipLaunchKernelGGL((row_sumsq_kernel<TM>), dim3((c->d2.XT + 3) / 4), dim3(256), 0, c->stream, c->Y2, c->d2.XT, c->d2.KS,
                                (long long)c->L, c->yrow);
         });
@@ -2120,8 +2091,8 @@ int vbmf_get_Y(vbmf_ctx* c, double* Y, int64_t ldY, int64_t row0, int64_t nrows)
         const int64_t m1 = std::min(c->M, m0 + mc);
         // shifting the tile pointer by whole k-steps makes the kernel's column 0 equal to column m0
         const uint4* base = c->Y2 + (size_t)(m0 / c->kstep) * 64;
-        DISPATCH_MODE(c->mode, {
-            constexpr int TM = (MODEc == MODE_F32) ? MODE_F32 : MODE_BF16;
+        dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+            constexpr int TM = decltype(ym)::value;
             hipLaunchKernelGGL((untile_y_kernel<TM>), dim3(grid_for(nrows * (m1 - m0))), dim3(256), 0, c->stream, base,
                                tmp.get(), (long long)nrows, (long long)row0, (long long)nrows, (long long)(m1 - m0), c->d2.KS);
         });
@@ -2310,8 +2281,8 @@ int vbmf_run_fixed_basis(vbmf_ctx* c, int64_t niter) {
         TRY(launch_post_gram(c, 0, Psrc));
         hipLaunchKernelGGL(copy_doubles_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, c->stream, c->st + c->lay.GA(), c->st + c->lay.W1(), n2);
         const size_t lds = vbls_lds_bytes(nb_tier(H));         // (the attribute for NB = 4: vbmf_create)
-        DISPATCH_NB(nb_tier(H), {
-            hipLaunchKernelGGL((vbls_loop_kernel<NBc>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M,
+        dispatch<1, 2, 4>(nb_tier(H), [&](auto nbk) {
+            hipLaunchKernelGGL((vbls_loop_kernel<decltype(nbk)::value>), dim3(1), dim3(256), lds, c->stream, c->st, c->lay, H, (double)c->Lg, (double)c->M,
                                (int)(niter - 1), c->SA32, c->ints);
         });
         HIPCHK(c, hipGetLastError());
@@ -2802,18 +2773,12 @@ static double digamma_host(double x) {
            f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (5.0 / 660 - f * (691.0 / 32760))))));
 }
 
-template <int R, int T>
-static void launch_scov_t(vbmf_ctx* c) {
-    const size_t lds = (R == 8 && T == 32) ? (size_t)(INV256_LDS_DOUBLES + 256) * sizeof(double) : spd_inverse_lds_bytes(R);
-    hipLaunchKernelGGL((sparse_cov_b_kernel<R, T>), dim3(1), dim3(T * T), lds, ctrl_stream(c), c->st, c->lay, (int)c->H, c->SB32, c->ints, c->diagvar ? 1 : 0);
-}
 static int launch_sparse_cov_b(vbmf_ctx* c) {
-    const int H = (int)c->H;
-    if (H <= 16) launch_scov_t<1, 16>(c);
-    else if (H <= 32) launch_scov_t<2, 16>(c);
-    else if (H <= 64) launch_scov_t<4, 16>(c);
-    else if (H <= 128) launch_scov_t<8, 16>(c);
-    else launch_scov_t<8, 32>(c);
+    ctrl_tier(c->H, [&](auto r, auto t) {
+        constexpr int R = decltype(r)::value, T = decltype(t)::value;
+        hipLaunchKernelGGL((sparse_cov_b_kernel<R, T>), dim3(1), dim3(T * T), (cov_lds_bytes<R, T>()), ctrl_stream(c), c->st, c->lay, (int)c->H,
+                           c->SB32, c->ints, c->diagvar ? 1 : 0);
+    });
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
 }
@@ -2839,12 +2804,7 @@ static void launch_full_a_t(vbmf_ctx* c, const double* Gw = nullptr) {
 // sums of Sigma_m it leaves in c->fpart (one per workgroup)
 template <int NBK, int NW>
 static int launch_full_a_wave(vbmf_ctx* c, const double* Gw) {
-    constexpr size_t lds = ((size_t)NW * 16 * NBK * (16 * NBK + 2) + (size_t)NW * 16 * NBK) * sizeof(double);
-    static bool attr_set = false;                              // (per instantiation; the attribute is per device function)
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)sparse_update_a_full_wave_kernel<NBK, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    constexpr size_t lds = full_a_wave_lds_bytes(NBK, NW);      // (the attribute that admits it: vbmf_create)
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(c->fblocks, cdiv(c->M, NW)), 2 * (NUM_CU + 2)));
     hipLaunchKernelGGL((sparse_update_a_full_wave_kernel<NBK, NW>), dim3(grid), dim3(NW * 64), lds, c->stream,
                        c->Pred, (long long)c->d1.XT * 32, c->CA32, c->st, c->lay, c->A32, c->dS32, c->has_mask ? c->mask : nullptr,
@@ -2868,10 +2828,11 @@ static int weighted_gram_B(vbmf_ctx* c, const double** out) {
     const int nchunk = cdiv(c->d2.XT, tpc);
     const int nw = nchunk * c->NH * c->NH;
     GSLAB_CHECK(c, nchunk, 2 * c->Hp * c->Hp);
-    DISPATCH_NH(c->NH, {
-        hipLaunchKernelGGL((gram_kernel<NHc>), dim3((nw + 3) / 4), dim3(256), 0, c->stream, scratch, (const float*)nullptr, c->gslab, c->d2.XT,
-                           tpc, nchunk, stop);
-    });
+    if (!dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+            hipLaunchKernelGGL((gram_kernel<decltype(nh)::value>), dim3((nw + 3) / 4), dim3(256), 0, c->stream, scratch, (const float*)nullptr,
+                               c->gslab, c->d2.XT, tpc, nchunk, stop);
+        })) NO_KERNEL(c);
+    // (its own reduction, not gram_reduce_tail: the sum goes to c->gw, not the state, and is all-reduced out of place)
     const int n = c->Hp * c->Hp;
     hipLaunchKernelGGL(gram_reduce_kernel, dim3((2 * n + 31) / 32), dim3(256), 0, c->stream, c->gslab, nchunk, n, c->gw, (double*)nullptr,
                        stop, (const double*)nullptr, 0, (double*)nullptr);
@@ -2914,14 +2875,16 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
         const double* Gw = nullptr;
         if (c->diagvar) TRY(weighted_gram_B(c, &Gw));
         int nparts = c->fblocks;
-        if (H <= 16) nparts = launch_full_a_wave<1, 8>(c, Gw);  // H <= 64: one column per wavefront, blocked sweep in the wave's LDS image
-        else if (H <= 32) nparts = launch_full_a_wave<2, 8>(c, Gw);
-        else if (H <= 64) nparts = launch_full_a_wave<4, 4>(c, Gw);
-        else if (H <= 128) launch_full_a_t<8, 16, 1>(c, Gw);   // 64 < H <= 128: one column per round and workgroup
-        else                                               // 128 < H <= 256: blocked Schur inverse through a global workspace
-            hipLaunchKernelGGL(sparse_update_a_full256_kernel, dim3(c->fblocks), dim3(1024), (size_t)(INV256_LDS_DOUBLES + 256 + 256) * sizeof(double),
-                               c->stream, c->Pred, (long long)c->d1.XT * 32, c->CA32, c->st, c->lay, c->A32, c->dS32,
-                               c->has_mask ? c->mask : nullptr, (int)(c->H - c->H1), (long long)c->M, H, (double)c->Lg, c->fpart, c->ints, Gw, c->fws);
+        ctrl_tier(H, [&](auto r, auto t) {
+            constexpr int R = decltype(r)::value;
+            if constexpr (decltype(t)::value == 32)            // 128 < H <= 256: blocked Schur inverse through a global workspace
+                hipLaunchKernelGGL(sparse_update_a_full256_kernel, dim3(c->fblocks), dim3(1024), (size_t)(INV256_LDS_DOUBLES + 256 + 256) * sizeof(double),
+                                   c->stream, c->Pred, (long long)c->d1.XT * 32, c->CA32, c->st, c->lay, c->A32, c->dS32,
+                                   c->has_mask ? c->mask : nullptr, (int)(c->H - c->H1), (long long)c->M, H, (double)c->Lg, c->fpart, c->ints, Gw, c->fws);
+            else if constexpr (R == 8) launch_full_a_t<8, 16, 1>(c, Gw);   // 64 < H <= 128: one column per round and workgroup
+            // H <= 64: one column per wavefront, blocked sweep in the wave's LDS image (eight wavefronts while their images fit)
+            else nparts = launch_full_a_wave<R, (R == 4 ? 4 : 8)>(c, Gw);
+        });
         hipLaunchKernelGGL(full_sa_fold_kernel, dim3(cdiv(c->Hp * c->Hp, 256)), dim3(256), 0, c->stream, c->fpart, nparts, c->Hp, c->st, c->lay, stop);
         HIPCHK(c, hipGetLastError());
         TRY(launch_retile(c, 0, true));
@@ -2935,12 +2898,16 @@ static int do_sparse_update_A(vbmf_ctx* c, bool reuse_P = false) {
     if (compat && c->M < 2) FAIL(c, VBMF_ERR_INVALID, "repeat(v, inner=M-1) needs M >= 2");
     if (c->sparse_a_fused) {
         // the update and the operand tiles of the next pass in one launch (A32 := the value the tiles encode, as retile leaves it)
-        DISPATCH_MODE(c->mode, DISPATCH_NH(c->NH, {
-            hipLaunchKernelGGL((sparse_update_a_tiles_kernel<MODEc, NHc>), dim3((c->d1.XT * NHc + 3) / 4), dim3(256), 0, c->stream, c->Pred,
-                               (long long)c->d1.XT * 32, c->CA32, c->vtab, c->st, c->lay, c->A32, c->dS32, c->FA,
-                               c->has_mask ? c->mask : nullptr, (int)(c->H - c->H1), (long long)c->M, (int)c->H, compat,
-                               c->diagvar ? 1 : 0, c->d1.XT, stop);
-        }));
+        const bool ok = dispatch<MODE_F32, MODE_BF16, MODE_BF16X2>(c->mode, [&](auto md) {
+            return dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+                constexpr int NHc = decltype(nh)::value;
+                hipLaunchKernelGGL((sparse_update_a_tiles_kernel<decltype(md)::value, NHc>), dim3((c->d1.XT * NHc + 3) / 4), dim3(256), 0, c->stream,
+                                   c->Pred, (long long)c->d1.XT * 32, c->CA32, c->vtab, c->st, c->lay, c->A32, c->dS32, c->FA,
+                                   c->has_mask ? c->mask : nullptr, (int)(c->H - c->H1), (long long)c->M, (int)c->H, compat,
+                                   c->diagvar ? 1 : 0, c->d1.XT, stop);
+            });
+        });
+        if (!ok) NO_KERNEL(c);
         HIPCHK(c, hipGetLastError());
     } else {
         hipLaunchKernelGGL(sparse_update_a_kernel, dim3(grid_for((int64_t)c->M * c->Hp)), dim3(256), 0, c->stream, c->Pred,
@@ -3085,15 +3052,10 @@ static int sparse_gram_sweep(vbmf_ctx* c) {
     const unsigned char* mk = c->has_mask ? c->mask : nullptr;
     const int hstart = (int)(c->H - c->H1);
     const dim3 grid((c->d1.XT * c->NH + 3) / 4);
-#define SPARSE_A_FRAG(NHc_)                                                                                                          \
-    hipLaunchKernelGGL((sparse_update_a_frag_kernel<MODE_BF16X2, NHc_>), grid, dim3(256), 0, c->stream, P4, c->CA32, c->vtab, c->st,  \
-                       c->lay, c->A32, c->dS32, c->FA, mk, hstart, (long long)c->M, (int)c->H, compat, c->d1.XT, stop)
-    if (c->NH == 1) SPARSE_A_FRAG(1);
-    else if (c->NH == 2) SPARSE_A_FRAG(2);
-    else if (c->NH == 4) SPARSE_A_FRAG(4);
-    else if (c->NH == 8) SPARSE_A_FRAG(8);
-    else FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 256");
-#undef SPARSE_A_FRAG
+    if (!dispatch<1, 2, 4, 8>(c->NH, [&](auto nh) {
+            hipLaunchKernelGGL((sparse_update_a_frag_kernel<MODE_BF16X2, decltype(nh)::value>), grid, dim3(256), 0, c->stream, P4, c->CA32, c->vtab,
+                               c->st, c->lay, c->A32, c->dS32, c->FA, mk, hstart, (long long)c->M, (int)c->H, compat, c->d1.XT, stop);
+        })) FAIL(c, VBMF_ERR_INVALID, "internal: the Gram-form sweep covers Hp <= 256");
     HIPCHK(c, hipGetLastError());
     c->P_frag = true;
     c->frag_last[0] = true;                         // test surface: this sweep's Y'B was the fragment-major G W, not a pass over Y
