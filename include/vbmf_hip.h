@@ -316,7 +316,8 @@ int vbmf_sparse_run_fixed_basis_batched(vbmf_ctx* ctx, int64_t nbags, const int6
  * whole `while i <= niter && d > eps` loop inside it -- the restart loops of examples/mil_util.jl:124-145,347-379 and the folds x
  * classes around them (:670-788) in one call.  The context supplies only Y, bags side by side (bag b = columns col_off[b] ..
  * col_off[b+1]-1); its own state is neither read nor changed (none needs to be set).  Fit f works on bag fit_bag[f], so several fits
- * (restarts) may share a bag.  A sparse-model or two-group context (`*_DIAG` variants), one rank, no label mask, H <= 32.
+ * (restarts) may share a bag.  A sparse-model or two-group context (`*_DIAG` variants), one rank, no label mask, H <= 32.  This entry is
+ * the homoscedastic noise model; the same fits with one noise precision per row of Y (diag_var): vbmf_rows_fit_batched.
  *   per fit (nfits): gamma, delta0, eta, zeta0 -- the derived shapes gamma0 + L/2, eta0 + L M_b/2 and the prior rates
  *   priors4 (nfits*4, in/out): alpha00, beta00, alpha01, beta01 -- columns h < H0 of A take the first pair, the others the second
  *       (src/vbmf_dual.jl:322-351); the sparse model passes its pair twice with H0 = H.  est_priors != 0 refits them every sweep
@@ -353,7 +354,8 @@ int vbmf_sparse_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off
  *       Needs H0 = H and est_priors = 0: the masked model has one prior group (slots 0, 1 of priors9) and no hyper-prior fit
  *   priors9 (nfits*9), laid out as vbmf_trial_get_priors lays it out: slots 0-5 alpha01, beta01, alpha02, beta02, alpha03, beta03 are
  *       in/out; slots 6-8 are out: the posterior shapes alpha1, alpha2, alpha3 the last updateCA! used
- * The context is any `*_DIAG` sparse, two-group or three-group context; its state is neither read nor changed.
+ * The context is any `*_DIAG` sparse, two-group or three-group context; its state is neither read nor changed.  Homoscedastic noise;
+ * with one noise precision per row of Y (diag_var): vbmf_rows_fit_batched.
  * VBMF_ERR_UNSUPPORTED: H > 32.  VBMF_ERR_INVALID, all before any launch, copy or change: a basic or `*_DIAGVAR` context, a label mask
  * set on the context, nranks > 1, no Y, a bad col_off, a fit_bag entry outside 0..nbags-1, nfits < 1, niter < 1, a required pointer
  * NULL, H0 outside 0..H, an M0[f] outside 0..M_b, mask_H1 outside 0..H, mask_H1 > 0 together with H0 != H or est_priors != 0, a 1-column
@@ -365,6 +367,34 @@ int vbmf_local_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off,
                            double* priors9, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA,
                            double* delta, double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
                            int64_t* iters_done, double* d_last, int64_t* status, double* trace);
+/* vbmf_rows_fit_batched: the fits of vbmf_sparse_fit_batched and vbmf_local_fit_batched under the heteroscedastic noise model,
+ * diag_var = true -- one noise precision per row of Y, what examples/mil_util.jl:667 sets for train, train_local and train_dual (:129,
+ * :140, :314, :351, :376).  src/vbmf_sparse.jl (src/vbmf_dual.jl:222-299,370-386 and src/vbmf_trial.jl:256-334,419-435 are the same),
+ * with s = sigmaVecHat, G = A'A + SigmaA, Q = Y A:
+ *   updateA!, diagonal form (:207-230): v_h = sum_l (s_l B_lh)^2 + L mean(s) SigmaB_hh -- s enters SQUARED here, the reference takes
+ *       norm2 of the product diag(s) B, and this library keeps that; prec = spread(v) + CA, ds = 1/prec, a = ds (B' diag(s) Y), with
+ *       NO factor sigmaHat
+ *   updateA!, full_cov (:180-193): K_m = B' diag(s) B + L mean(s) SigmaB + diag(CA[m,:]) -- s to the first power; a_m = inv(K_m)
+ *       (B' diag(s) y_m), SigmaA = sum_m inv(K_m)
+ *   updateB! (:256-261): SigmaB = inv(diag(CB) + mean(s) G), B = diag(s) Q SigmaB
+ *   updateSigma! (:309-315): zetaVec_l = zeta0 + ||Y[l,:]||^2 / 2 - sum_h Q_lh B_lh + (b_l'G b_l + sum G o SigmaB) / 2,
+ *       s_l = etaVec / zetaVec_l; sigmaHat and zeta are not touched
+ * updateCA!, updateCB!, the prior groups, the prefix mask, est_priors, d and the stop test are those of vbmf_local_fit_batched, whose
+ * shapes, in/out rules, priors9 layout, status and trace hold here except:
+ *   M0 may be NULL: M0[f] = M_b, which makes the three-group rule the two-group model (with H0 = H and est_priors = 0: the sparse one)
+ *   etaVec (nfits): eta0 + M_b / 2
+ *   sigmaVec (nfits*L, in/out) and zetaVec (nfits*L, out, may be NULL) stand where sigmaHat and zeta stand
+ *   trace: (d, mean(sigmaVec)) per sweep run; status 1 also for a zetaVec_l or s_l that is not finite
+ * The context supplies only Y: any sparse-family context serves, `*_DIAG` or `*_DIAGVAR`; its state is neither read nor changed.
+ * Refusals: those of vbmf_local_fit_batched with the same codes, all before any launch, copy or change (a `*_DIAGVAR` context and a
+ * NULL M0 are accepted). */
+int vbmf_rows_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                          int64_t niter, double eps, int full_cov, int est_cb, int est_priors,
+                          int64_t H0, const int64_t* M0, int64_t mask_H1,
+                          const double* gamma, const double* delta0, const double* etaVec, const double* zeta0,
+                          double* priors9, double* BHat, double* SigmaB, double* CB, double* sigmaVec, double* CA,
+                          double* delta, double* zetaVec, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
+                          int64_t* iters_done, double* d_last, int64_t* status, double* trace);
 int vbmf_sparse_step(vbmf_ctx* ctx, int which);           /* reference order A, B, CA, CB, SIGMA (:369-376) */
 /* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0)
  * Gram form.  A VBMF_VARIANT_SPARSE_DIAG context with full_cov off, one rank, bf16 Y, bf16x2 factors and

@@ -49,6 +49,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
            "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags", "vbmf_sparse_batch_", "vbmf_dual_batch_", "fit_restarts",
            "vbmf_batch_", "train_folds", "row_gram_batch", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
+           "train_dual_folds",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
@@ -505,7 +506,8 @@ def _gram_refusal(H, sparse, grouped=False, diag_var=False, full_cov=False):
     if grouped:
         return "a grouped model (vbmf_dual / vbmf_trial) masks its B side by group"
     if diag_var:
-        return "diag_var=True: the rows' noise precisions change Y'diag(sigma)B every sweep"
+        return ("diag_var=True: the rows' noise precisions change Y'diag(sigma)B every sweep (many small fits with per-row noise: "
+                "vbmf_sparse_batch_ / vbmf_dual_batch_(..., diag_var=True))")
     if full_cov:
         return "full_cov=True: the per-column covariance blocks are built from the streamed product"
     if H > (256 if sparse else 128):
@@ -1465,20 +1467,26 @@ def _fit_front(fn, one, kind, cls, Ys, params, niter, bag_of):
 
 def _write_A_side(p, r, k, s0):
     """What a batched call's results r hold of set k's A side, its M H-long vectors starting at s0: ATVecHat, diagSigmaATVec, CA, beta,
-    AHat, SigmaA, sigmaHat, zeta (all copies).  Returns where the next set's vectors start."""
+    AHat, SigmaA, sigmaHat, zeta (all copies) -- or, from a row-noise call, sigmaVecHat and zetaVec, with sigmaHat and zeta left as they
+    were (as _pull leaves them).  Returns where the next set's vectors start."""
     s1 = s0 + p.M * p.H
     p.ATVecHat, p.diagSigmaATVec = r["ATVecHat"][s0:s1].copy(), r["diagSigmaATVec"][s0:s1].copy()
     p.CA, p.beta = r["CA"][s0:s1].copy(), r["beta"][s0:s1].copy()
     p.AHat = p.ATVecHat.reshape(p.M, p.H).copy()
     p.SigmaA = r["SigmaA"][k].copy()
-    p.sigmaHat, p.zeta = float(r["sigmaHat"][k]), float(r["zeta"][k])
+    if "sigmaVecHat" in r:
+        p.sigmaVecHat, p.zetaVec = r["sigmaVecHat"][k].copy(), r["zetaVec"][k].copy()
+    else:
+        p.sigmaHat, p.zeta = float(r["sigmaHat"][k]), float(r["zeta"][k])
     return s1
 
 
-def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of, masked=False):
+def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of, masked=False, diag_var=False):
     """The four batched fits of the sparse family: the host checks, the one device call, the fields of every set; returns the list of d.
     The models with a per-fit M0 -- the three-group one and, with masked, the sparse one under a label mask -- go through
-    vbmf_local_fit_batched (H0 in 0..H), the other two through vbmf_sparse_fit_batched (H0 in 1..H)."""
+    vbmf_local_fit_batched (H0 in 0..H), the other two through vbmf_sparse_fit_batched (H0 in 1..H).  diag_var: all four go through
+    vbmf_rows_fit_batched (the models without a per-fit M0 with M0 = None: every column in group 2), from sigmaVecHat and etaVec[0];
+    sigmaVecHat and zetaVec are filled, sigmaHat and zeta are left as they were."""
     refuse, params, bag_of, H, L, Ms = _fit_front(fn, one, kind, SparseBags, Ys, params, niter, bag_of)
     m = _MODELS[kind]
     local = masked or m.M0
@@ -1508,19 +1516,29 @@ def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, e
             refuse(f"fit {f}: BHat, SigmaB, CB or CA does not have the shape of a {L} x {Ms[b]} problem at H = {H}")
         if not full_cov and repeat and Ms[b] < 2:
             refuse(f"fit {f} works on a 1-column bag: the diagonal form under the repeat layout needs M >= 2")
+        if diag_var and (np.shape(p.sigmaVecHat) != (L,) or np.size(p.etaVec) < 1):
+            refuse(f"fit {f}: sigmaVecHat is not ({L},) or etaVec is empty (diag_var=True starts from the rows' noise)")
         _check_derived(p)
         if _alpha_not_derived(m, p):
             refuse(f"fit {f}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
+    rows_local = local or diag_var
     # the hyper-prior pairs of the entry's two (three) groups; a model with fewer groups gives its last pair again
-    pairs = [k for g in range(3 if local else 2) for k in m.groups[min(g, len(m.groups) - 1)][:2]]
+    pairs = [k for g in range(3 if rows_local else 2) for k in m.groups[min(g, len(m.groups) - 1)][:2]]
+    if diag_var:
+        eta = [float(np.asarray(p.etaVec).reshape(-1)[0]) for p in params]       # (as _push hands it down)
+        sigma = np.stack([np.asarray(p.sigmaVecHat, dtype=np.float64) for p in params])
+    else:
+        eta, sigma = [p.eta0 + p.L * p.M / 2 for p in params], [p.sigmaHat for p in params]
     args = (bag_of, int(niter), float(eps), [p.gamma0 + p.L / 2 for p in params], [p.delta0 for p in params],
-            [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params], [[getattr(p, k) for k in pairs] for p in params],
+            eta, [p.zeta0 for p in params], [[getattr(p, k) for k in pairs] for p in params],
             np.stack([np.asarray(p.BHat, dtype=np.float64) for p in params]), np.stack([np.asarray(p.SigmaB, dtype=np.float64) for p in params]),
-            np.stack([np.asarray(p.CB, dtype=np.float64).reshape(H) for p in params]), [p.sigmaHat for p in params],
+            np.stack([np.asarray(p.CB, dtype=np.float64).reshape(H) for p in params]), sigma,
             np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]))
     kw = dict(H0=H if m.labels else int(params[0].H0), full_cov=full_cov, est_cb=est_cb, est_priors=est_priors and not m.labels)
     with _on_device(Ys, H, SparseBags) as bags:
-        if local:
+        if diag_var:
+            r = bags.ctx.rows_fit_batched(bags.col_off, *args, M0s if local else None, mask_H1=int(params[0].H1) if masked else 0, **kw)
+        elif local:
             r = bags.ctx.local_fit_batched(bags.col_off, *args, M0s, mask_H1=int(params[0].H1) if masked else 0, **kw)
         else:
             r = bags.ctx.sparse_fit_batched(bags.col_off, *args, **kw)
@@ -1536,6 +1554,9 @@ def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, e
             if local:
                 for k, v in zip(Context.TRIAL_KEYS, r["priors9"][f]):   # the pairs, and the shapes the last updateCA! used
                     setattr(p, k, float(v))
+            elif diag_var:                                          # the two-group model through the nine-slot entry: slots 6, 7
+                p.alpha00, p.beta00, p.alpha01, p.beta01 = (float(v) for v in r["priors9"][f, :4])
+                p.alpha0, p.alpha1 = float(r["priors9"][f, 6]), float(r["priors9"][f, 7])
             else:
                 # the posterior shapes as the last updateCA! left them (src/vbmf_dual.jl:324-325): the hyper-prior that sweep STARTED
                 # from + 1/2, which est_priors has since refitted -- recovered as CA * beta of the group's first entry
@@ -1549,47 +1570,57 @@ def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, e
     return [float(v) for v in r["d"]]
 
 
-def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None):
+def _rows(diag_var):
+    """the keyword of the row-noise path, absent when it is off: the homoscedastic calls are made as they always were"""
+    return dict(diag_var=True) if diag_var else {}
+
+
+def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, diag_var=False):
     """vbmf_sparse! for many independent fits in one device call: does what [vbmf_sparse_(Ys[bag_of[f]], p, niter, eps=eps, ...) for
     f, p in enumerate(params)] does (the restart loop of examples/mil_util.jl:124-145) -- fills on every p the fields vbmf_sparse_
     fills, plus p.iters (sweeps run) and p.status (1: the fit met a non-finite precision or a bad pivot and stopped), and returns the
     list of d.  Ys: a list of L x M_b arrays or a SparseBags; params: one vbmf_sparse_parameters per fit, one H <= 32, no labels;
     bag_of[f]: the fit's bag (default: fit f on bag f), so restarts share one upload.  Every fit's whole loop runs in one workgroup of
-    one launch (include/vbmf_hip.h, vbmf_sparse_fit_batched)."""
-    return _sparse_fit_batch("vbmf_sparse_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb, False, bag_of)
+    one launch (include/vbmf_hip.h, vbmf_sparse_fit_batched).  diag_var=True: one noise precision per row of Y (examples/mil_util.jl:667),
+    through vbmf_rows_fit_batched -- the fits start from p.sigmaVecHat and p.etaVec[0] and fill p.sigmaVecHat and p.zetaVec; p.sigmaHat
+    and p.zeta stay as they were, as after vbmf_sparse_(..., diag_var=True)."""
+    return _sparse_fit_batch("vbmf_sparse_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb, False, bag_of,
+                             **_rows(diag_var))
 
 
-def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True):
+def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True, diag_var=False):
     """vbmf_dual! for many independent fits in one device call (the restart loop of examples/mil_util.jl:347-379): see
-    vbmf_sparse_batch_; params: one vbmf_dual_parameters per fit, all with one H0."""
-    return _sparse_fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of)
+    vbmf_sparse_batch_, diag_var included; params: one vbmf_dual_parameters per fit, all with one H0."""
+    return _sparse_fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of,
+                             **_rows(diag_var))
 
 
-def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True):
+def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True, diag_var=False):
     """vbmf_trial! for many independent fits in one device call: does what [vbmf_trial_(Ys[bag_of[f]], p, niter, eps=eps, ...) for f, p
     in enumerate(params)] does (src/vbmf_trial.jl:528-604) -- fills on every p the fields vbmf_trial_ fills (the group views A1Hat..A3Hat,
     CA1..3, beta1..3, the posterior shapes alpha1..3 and the six hyper-priors included), plus p.iters and p.status as vbmf_sparse_batch_
     does, and returns the list of d.  params: one vbmf_trial_parameters per fit, one H <= 32 and one H0 per call, M0 per fit.  Every
-    fit's whole loop runs in one workgroup of one launch (include/vbmf_hip.h, vbmf_local_fit_batched)."""
+    fit's whole loop runs in one workgroup of one launch (include/vbmf_hip.h, vbmf_local_fit_batched).  diag_var: as in
+    vbmf_sparse_batch_."""
     return _sparse_fit_batch("vbmf_trial_batch_", "vbmf_trial_", vbmf_trial_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors,
-                             bag_of)
+                             bag_of, **_rows(diag_var))
 
 
-def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None):
+def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, diag_var=False):
     """vbmf_sparse! with a label mask for many independent fits in one device call (the fit of train_local, examples/mil_util.jl:302-320,
     on Y = [Y0 Y1]): see vbmf_sparse_batch_.  params: one vbmf_sparse_parameters per fit whose labels are exactly the prefix 1..M0 of
     the columns (possibly empty; M0 per fit), with one H1 per call: the last H1 columns of AHat stay zero in the rows 1..M0
-    (src/vbmf_sparse.jl:245).  Any other label set is refused: run it with vbmf_sparse_."""
+    (src/vbmf_sparse.jl:245).  Any other label set is refused: run it with vbmf_sparse_.  diag_var: as in vbmf_sparse_batch_."""
     return _sparse_fit_batch("vbmf_sparse_masked_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb,
-                             False, bag_of, masked=True)
+                             False, bag_of, masked=True, **_rows(diag_var))
 
 
-def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None):
+def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False):
     """The reference's train_local (examples/mil_util.jl:302-320) over many (Y0, Y1) pairs with all the fits in ONE device call per
     round: per pair Y = [Y0 Y1] and vbmf_sparse_init(Y, H, H1=H1, labels=1:M0), drawn in fold order from the one generator; every fold
     runs vbmf_sparse! in the diagonal form (:314); then, as the loop of :312-317 does, a fold whose norm(AHat) and norm(BHat) (operator
-    2-norms) are both below 1e-2 runs again from where it stands, one further call per round, ten rounds at most.  Returns the list of
-    parameter sets."""
+    2-norms) are both below 1e-2 runs again from where it stands, one further call per round, ten rounds at most.  diag_var goes to
+    every vbmf_sparse! as it does at :314.  Returns the list of parameter sets."""
     rng = np.random.default_rng() if rng is None else rng
     Ys, ps = [], []
     for Y0, Y1 in folds:
@@ -1604,7 +1635,7 @@ def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None):
         again = [k for k, p in enumerate(ps) if all(v < bound[k] for v in norms(p))]
         if not again:
             break
-        vbmf_sparse_masked_batch_([Ys[k] for k in again], [ps[k] for k in again], niter, eps=eps, full_cov=False)
+        vbmf_sparse_masked_batch_([Ys[k] for k in again], [ps[k] for k in again], niter, eps=eps, full_cov=False, **_rows(diag_var))
         bound = [1e-2] * len(ps)                                    # :315
     return ps
 
@@ -1618,7 +1649,8 @@ def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, ful
     if model not in ("sparse", "dual"):
         raise ValueError(f"fit_restarts: model = {model!r} ('sparse' or 'dual')")
     if diag_var:
-        raise ValueError("fit_restarts: diag_var=True is not batched; run the restarts one at a time with vbmf_sparse_ / vbmf_dual_")
+        raise ValueError("fit_restarts: diag_var=True is not batched; run the restarts one at a time with vbmf_sparse_ / vbmf_dual_ "
+                         "(or all at once with vbmf_sparse_batch_ / vbmf_dual_batch_(..., diag_var=True))")
     if int(nstarts) < 1:
         raise ValueError("fit_restarts: nstarts must be >= 1")
     rng = np.random.default_rng() if rng is None else rng
@@ -1701,7 +1733,8 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
         raise ValueError(f"train_folds: solver = {solver!r} ('basic' or 'sparse')")
     capi.fit_form_code(form)
     if diag_var:
-        raise ValueError("train_folds: diag_var=True is not batched; train such folds one at a time with vbmf_sparse_ / vbmf_")
+        raise ValueError("train_folds: diag_var=True is not batched; train such folds one at a time with vbmf_sparse_ / vbmf_ "
+                         "(or the sparse solver's fits at once with vbmf_sparse_batch_(..., diag_var=True))")
     rng = np.random.default_rng() if rng is None else rng
     nstarts = 1 if solver == "basic" else 10                        # max_restarts of :108
     init = vbmf_init if solver == "basic" else vbmf_sparse_init
@@ -1731,6 +1764,41 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
     res = {}
     for (k, c), p in zip(where, kept):
         res[k, c] = p
+    for k in {k for k, _ in where}:
+        out[k] = (res[k, 0], res[k, 1])
+    return out
+
+
+def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, rng=None):
+    """The reference's train_dual (examples/mil_util.jl:327-385) over many (Y0, Y1) pairs with all the fits in ONE device call: nstarts
+    vbmf_dual_init per class per fold, drawn in the order (fold, class, restart) from the one generator, one vbmf_dual_batch_ call with
+    full_cov=True (:351, :376) in which the restarts of a class share its upload, and per class the set the restart loops of :347-354
+    and :372-379 keep (fit_restarts(model="dual")): the first with norm(AHat) + norm(BHat) >= 1e-2 (operator 2-norms), else the last.
+    diag_var goes to every vbmf_dual! as it does there.  The column subsample of :342-344 is the caller's: pass the columns to train
+    on.  Returns a list of (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns, as train_folds does."""
+    if int(nstarts) < 1:
+        raise ValueError("train_dual_folds: nstarts must be >= 1")
+    rng = np.random.default_rng() if rng is None else rng
+    nstarts = int(nstarts)
+    Ys, ps, bag_of, where = [], [], [], []
+    for k, pair in enumerate(folds):
+        if any(np.shape(Y)[1:] == (0,) for Y in pair):
+            continue
+        for c, Y in enumerate(pair):
+            Ys.append(Y)
+            for _ in range(nstarts):
+                ps.append(vbmf_dual_init(Y, H, H0, rng=rng))
+                bag_of.append(len(Ys) - 1)
+            where.append((k, c))
+    out = [(0, 0)] * len(folds)
+    if not ps:
+        return out
+    vbmf_dual_batch_(Ys, ps, niter, eps=eps, full_cov=True, bag_of=bag_of, **_rows(diag_var))
+    res = {}
+    for b, kc in enumerate(where):
+        sets = ps[b * nstarts:(b + 1) * nstarts]
+        # Julia 0.5 norm(::Matrix): the operator 2-norm
+        res[kc] = next((p for p in sets if not (np.linalg.norm(p.AHat, 2) + np.linalg.norm(p.BHat, 2) < 1e-2)), sets[-1])
     for k in {k for k, _ in where}:
         out[k] = (res[k, 0], res[k, 1])
     return out

@@ -63,7 +63,7 @@ SYMBOLS = [
     "vbmf_elbo", "vbmf_comm_unique_id", "vbmf_comm_init", "vbmf_comm_set_transport", "vbmf_profile_enable", "vbmf_profile_read",
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
-    "vbmf_sparse_run_fixed_basis_batched", "vbmf_sparse_fit_batched", "vbmf_local_fit_batched",
+    "vbmf_sparse_run_fixed_basis_batched", "vbmf_sparse_fit_batched", "vbmf_local_fit_batched", "vbmf_rows_fit_batched",
     "vbmf_sparse_lower_bound", "vbmf_sparse_set_noise_rows", "vbmf_sparse_get_noise_rows", "vbmf_preprocess_open", "vbmf_preprocess_rows", "vbmf_set_Y_preprocessed",
     "vbmf_preprocess_close", "vbmf_dual_set_priors", "vbmf_dual_get_priors", "vbmf_dual_run",
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
@@ -152,6 +152,7 @@ def lib():
                                           + [C.POINTER(i64), dp, C.POINTER(i64), dp])
     L.vbmf_local_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64,
                                           C.POINTER(i64), i64] + [dp] * 16 + [C.POINTER(i64), dp, C.POINTER(i64), dp])
+    L.vbmf_rows_fit_batched.argtypes = L.vbmf_local_fit_batched.argtypes
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
     L.vbmf_get_YHat_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
     L.vbmf_get_factor_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
@@ -606,17 +607,30 @@ class Context:
         return self._ard_fit_batched(col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors9, BHat, SigmaB, CB, sigmaHat, CA, H0,
                                      full_cov, est_cb, est_priors, want_trace, M0=M0, mask_H1=mask_H1)
 
+    def rows_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVecHat, CA,
+                         M0=None, H0=None, mask_H1=0, full_cov=False, est_cb=True, est_priors=False, want_trace=False):
+        """local_fit_batched under the heteroscedastic noise model, diag_var = true (vbmf_rows_fit_batched; examples/mil_util.jl:667): one
+        noise precision per row of Y.  etaVec (nfits,) = eta0 + M_b / 2; sigmaVecHat (nfits, L) the start values; M0 None: M0[f] = M_b, the
+        two-group model (with H0 = H and est_priors off: the sparse one).  The diagonal form of updateA! takes the rows' precisions
+        SQUARED into v (src/vbmf_sparse.jl:211), full_cov to the first power (:180-182).  Returns local_fit_batched's dict with
+        sigmaVecHat (nfits, L) and zetaVec (nfits, L) in place of sigmaHat and zeta; the second trace column is mean(sigmaVecHat).  The
+        context may be a `*_DIAG` or a `*_DIAGVAR` one: only its Y is used."""
+        return self._ard_fit_batched(col_off, fit_bag, niter, eps, gamma, delta0, etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVecHat, CA,
+                                     H0, full_cov, est_cb, est_priors, want_trace, M0=M0, mask_H1=mask_H1, rows=True)
+
     def _ard_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors, BHat, SigmaB, CB, sigmaHat, CA, H0, full_cov,
-                         est_cb, est_priors, want_trace, M0=None, mask_H1=0):
-        """sparse_fit_batched (M0 is None: vbmf_sparse_fit_batched, four prior values per fit) and local_fit_batched
-        (vbmf_local_fit_batched: M0 and mask_H1 behind H0, nine prior values per fit, six accepted and padded)."""
-        local = M0 is not None
+                         est_cb, est_priors, want_trace, M0=None, mask_H1=0, rows=False):
+        """sparse_fit_batched (M0 is None: vbmf_sparse_fit_batched, four prior values per fit), local_fit_batched
+        (vbmf_local_fit_batched: M0 and mask_H1 behind H0, nine prior values per fit, six accepted and padded) and rows_fit_batched
+        (vbmf_rows_fit_batched: local_fit_batched's arguments with sigmaHat and zeta (nfits, L); M0 None goes down as NULL)."""
+        local = M0 is not None or rows
         H = self.H
         off, fb, nb, nf, B, per_fit, tail = self._fit_prologue(col_off, fit_bag, niter, BHat, want_trace)
         vec = lambda v: np.array(v, dtype=np.float64, copy=True).reshape(-1)
-        ga, d0, et, z0, sg, ca = vec(gamma), vec(delta0), vec(eta), vec(zeta0), vec(sigmaHat), vec(CA)
+        ga, d0, et, z0, ca = vec(gamma), vec(delta0), vec(eta), vec(zeta0), vec(CA)
+        sg = np.array(sigmaHat, dtype=np.float64, copy=True, order="C") if rows else vec(sigmaHat)
         if local:
-            m0 = np.array(M0, dtype=np.int64, copy=True).reshape(-1)
+            m0 = None if M0 is None else np.array(M0, dtype=np.int64, copy=True).reshape(-1)
             pin = np.asarray(priors, dtype=np.float64)
             if not (pin.ndim == 2 and pin.shape[0] == nf and pin.shape[1] in (6, 9)):
                 raise ValueError(f"{nf} fits: priors9 must be ({nf}, 9) or ({nf}, 6)")
@@ -627,21 +641,26 @@ class Context:
         SB = np.array(SigmaB, dtype=np.float64, copy=True, order="C")
         cb = np.array(CB, dtype=np.float64, copy=True, order="C")
         MH = int(np.sum(off[fb + 1] - off[fb])) * H
-        scalars = (ga, d0, et, z0, sg, m0) if local else (ga, d0, et, z0, sg)
+        scalars = (ga, d0, et, z0) + (() if rows else (sg,)) + ((m0,) if local and m0 is not None else ())
         if (any(v.shape != (nf,) for v in scalars) or pri.shape != (nf, 9 if local else 4) or SB.shape != (nf, H, H) or cb.shape != (nf, H)
-                or ca.shape != (MH,)):
+                or ca.shape != (MH,) or (rows and sg.shape != (nf, self.L))):
+            if rows:
+                raise ValueError(f"{nf} fits: gamma, delta0, etaVec, zeta0{'' if m0 is None else ', M0'} must be ({nf},), sigmaVecHat "
+                                 f"({nf}, {self.L}), SigmaB ({nf}, {H}, {H}), CB ({nf}, {H}) and CA ({MH},)")
             raise ValueError(f"{nf} fits: gamma, delta0, eta, zeta0, sigmaHat{', M0' if local else ''} must be ({nf},), "
                              f"{'' if local else f'priors4 ({nf}, 4), '}SigmaB ({nf}, {H}, {H}), CB ({nf}, {H}) and CA ({MH},)")
         delta = np.empty((nf, H)) if est_cb else None
-        zeta, beta, dS, A = np.empty(nf), np.empty(MH), np.empty(MH), np.empty(MH)
+        zeta, beta, dS, A = np.empty((nf, self.L) if rows else nf), np.empty(MH), np.empty(MH), np.empty(MH)
         SA = np.empty((nf, H, H))
-        entry = self._lib.vbmf_local_fit_batched if local else self._lib.vbmf_sparse_fit_batched
+        entry = (self._lib.vbmf_rows_fit_batched if rows else self._lib.vbmf_local_fit_batched if local
+                 else self._lib.vbmf_sparse_fit_batched)
         self._chk(entry(
             self._h, nb, _i64ptr(off), nf, _i64ptr(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
             int(H if H0 is None else H0), *((_i64ptr(m0), int(mask_H1)) if local else ()), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0),
             _dptr(pri), _dptr(B), _dptr(SB), _dptr(cb), _dptr(sg), _dptr(ca), _dptr(delta), _dptr(zeta), _dptr(beta), _dptr(dS), _dptr(SA),
             _dptr(A), *tail))
-        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, sigmaHat=sg, zeta=zeta, CA=ca, beta=beta, diagSigmaATVec=dS,
+        noise = dict(sigmaVecHat=sg, zetaVec=zeta) if rows else dict(sigmaHat=sg, zeta=zeta)
+        return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, **noise, CA=ca, beta=beta, diagSigmaATVec=dS,
                     ATVecHat=A, SigmaA=SA, **{"priors9" if local else "priors4": pri}, **per_fit)
 
     def YHat(self):

@@ -21,6 +21,17 @@
 // slices of the scratch buffer.  Every sum's order is fixed by (L, M_b, H): chunked partials folded in chunk order, xor-butterflies over
 // a lane group whose width depends on the row count alone (LOCAL: and by H0, M0 for the per-group sums).  No atomics, no hand-off
 // between workgroups.
+//
+// ROWS = true (vbmf_rows_fit_batched; with LOCAL only): the heteroscedastic noise model, diag_var = true, of the same three families
+// (src/vbmf_sparse.jl:180-193, 207-230, 256-261, 309-315; src/vbmf_dual.jl:222-299, 370-386; src/vbmf_trial.jl:256-334, 419-435).  A fit
+// holds s = sigmaVecHat and the row norms ||Y_b[l,:]||^2 (L doubles each) behind the H x H matrices, in LDS when they fit, else in its
+// slices of g.sigma and g.yn.  Per sweep Ql = diag(s) B is formed where Ql is free (its B_old - B went into dB'dB), and
+//   updateA!      P = Y_b' Ql, no factor sigmaHat on a; diagonal form: v_h = sum_l Ql_lh^2 + L mean(s) SigmaB_hh -- s enters SQUARED
+//                 (:211 takes norm2 of the product); full_cov: K_m = sum_l Ql_li B_lj + L mean(s) SigmaB + diag(CA[m,:]), s to the first power
+//   updateB!      SigmaB = inv(diag(CB) + mean(s) (A'A + SigmaA)), B = diag(s) Q SigmaB
+//   updateSigma!  fused into the row-per-thread loop that forms B: zetaVec_l = zeta0 + ||Y_b[l,:]||^2 / 2 - sum_h Q_lh B_lh
+//                 + (b_l'G b_l + sum G o SigmaB) / 2, s_l = etaVec / zetaVec_l; sigmaHat and zeta do not exist here
+// The second trace column is mean(s).  A zetaVec_l or s_l that is not finite sets status = 1 like a non-finite precision.
 #pragma once
 #include <type_traits>
 #include "common.hpp"
@@ -41,13 +52,19 @@ __host__ __device__ constexpr int fitb_fixed_doubles(bool full, int NBK, int H) 
     return (full ? FITB_NW * (16 * NBK) * (16 * NBK + 2) + FITB_NW * 16 * NBK : (16 * NBK) * (16 * NBK + 2)) + 8 * H * H;
 }
 // where a fit's state lives: 2 = everything in LDS, 1 = B and Q only, 0 = nothing
-__host__ __device__ constexpr int fitb_placement(bool full, int NBK, long long L, long long Mb, int H) {
-    const long long room = (long long)(FITB_LDS_CAP / 8) - fitb_fixed_doubles(full, NBK, H);
+// rows (ROWS = true): the fit's two L-vectors (s, the row norms) come off the room first; they stay in LDS whenever they fit at all
+__host__ __device__ constexpr bool fitb_rows_in_lds(bool full, int NBK, long long L, int H) {
+    return 2 * L <= (long long)(FITB_LDS_CAP / 8) - fitb_fixed_doubles(full, NBK, H);
+}
+__host__ __device__ constexpr int fitb_placement(bool full, int NBK, long long L, long long Mb, int H, bool rows = false) {
+    const long long room = (long long)(FITB_LDS_CAP / 8) - fitb_fixed_doubles(full, NBK, H)
+                           - (rows && fitb_rows_in_lds(full, NBK, L, H) ? 2 * L : 0);
     return 2 * L * H + 3 * Mb * H <= room ? 2 : (2 * L * H <= room ? 1 : 0);
 }
-__host__ __device__ constexpr long long fitb_lds_doubles(bool full, int NBK, long long L, long long Mb, int H) {
-    const int pl = fitb_placement(full, NBK, L, Mb, H);
-    return fitb_fixed_doubles(full, NBK, H) + (pl >= 1 ? 2 * L * H : 0) + (pl == 2 ? 3 * Mb * H : 0);
+__host__ __device__ constexpr long long fitb_lds_doubles(bool full, int NBK, long long L, long long Mb, int H, bool rows = false) {
+    const int pl = fitb_placement(full, NBK, L, Mb, H, rows);
+    return fitb_fixed_doubles(full, NBK, H) + (rows && fitb_rows_in_lds(full, NBK, L, H) ? 2 * L : 0) + (pl >= 1 ? 2 * L * H : 0)
+           + (pl == 2 ? 3 * Mb * H : 0);
 }
 
 // Y as stored -> Yr[l * M + m] and Yc[m * L + l] (fp32: exact for both storage types)
@@ -84,6 +101,11 @@ struct FitArgs {
 //   prefix mask (src/vbmf_sparse.jl:245)            mask_H1 > 0: a(m, h) = 0 for m < M0[f], h >= H - mask_H1, before anything reads it
 struct FitLocalArgs : FitArgs {
     const long long* M0; int mask_H1;
+};
+// vbmf_rows_fit_batched: sigma is nfits x L (in / out), zeta nfits x L (out), eta[f] = eta0 + M_b / 2; yn: nfits x L, the row norms of
+// the fits whose L-vectors are not in LDS
+struct FitRowsArgs : FitLocalArgs {
+    double* yn;
 };
 
 // sum over the workgroup's 512 threads, lanes first, then the eight waves in order (block_sum of ctrl_kernels.hpp folds the first 256
@@ -250,8 +272,10 @@ __device__ __forceinline__ void fitb_lambda_max(const double* M0, const double* 
     }
 }
 
-template <int NBK, bool FULL, bool LOCAL = false>
-__global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditional_t<LOCAL, FitLocalArgs, FitArgs> g) {
+template <int NBK, bool FULL, bool LOCAL = false, bool ROWS = false>
+__global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(
+    std::conditional_t<ROWS, FitRowsArgs, std::conditional_t<LOCAL, FitLocalArgs, FitArgs>> g) {
+    static_assert(LOCAL || !ROWS, "the row-noise sweep is built on the three-group sweep");
     extern __shared__ __attribute__((aligned(16))) double lds_fb[];
     __shared__ double part[1024];
     __shared__ double red[16];
@@ -263,14 +287,14 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
     const int f = blockIdx.x, H = g.H, H0 = g.H0, tid = threadIdx.x, h2 = H * H;
     const long long L = g.L, b = g.fit_bag[f], m0 = g.col_off[b], Mb = g.col_off[b + 1] - m0;
     const long long n = Mb * H, o = g.fit_off[f] * H, nb = L * H;
-    const int place = fitb_placement(FULL, NBK, L, Mb, H);
+    const int place = fitb_placement(FULL, NBK, L, Mb, H, ROWS);
     long long M0f = 0;                                              // LOCAL: rows m < M0f are the fit's negative instances
     int hmask = H;                                                  // LOCAL: columns h >= hmask of those rows are zeroed
     if constexpr (LOCAL) {
         M0f = g.M0[f];
         hmask = H - g.mask_H1;
     }
-    // dynamic LDS: [images (+ p_m, a_m) | B'B | A'A + SigmaA | SigmaB | dB'dB | eigen 4 H^2 | B, Q | PA, CA, dS]
+    // dynamic LDS: [images (+ p_m, a_m) | B'B | A'A + SigmaA | SigmaB | dB'dB | eigen 4 H^2 | ROWS: s, row norms | B, Q | PA, CA, dS]
     double* Wk = lds_fb;                                            // the image of updateB!'s inverse (full_cov: wave 0's)
     double* BB = lds_fb + (fitb_fixed_doubles(FULL, NBK, H) - 8 * h2);
     double* AA = BB + h2;
@@ -278,6 +302,14 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
     double* Dm = SBm + h2;
     double* E = Dm + h2;
     double* st = E + 4 * h2;
+    double* sv = nullptr;                                           // ROWS: s = sigmaVecHat and ||Y_b[l,:]||^2
+    double* yn = nullptr;
+    if constexpr (ROWS) {
+        const bool in_lds = fitb_rows_in_lds(FULL, NBK, L, H);
+        sv = in_lds ? st : g.sigma + (long long)f * L;
+        yn = in_lds ? st + L : g.yn + (long long)f * L;
+        if (in_lds) st += 2 * L;
+    }
     double* Bl = place >= 1 ? st : g.Bw + (long long)f * nb;
     double* Ql = place >= 1 ? st + nb : g.Qw + (long long)f * nb;
     double* PAb = place == 2 ? st + 2 * nb : g.A + o;
@@ -305,15 +337,41 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
                                                    : g.priors4[(long long)f * NPRI + tid];
     if (tid == 0) bad_s = 0;
     const double eta = g.eta[f], zeta0 = g.zeta0[f], gam = g.gamma[f], delta0 = g.delta0[f], Lg = (double)L;
-    double sig = g.sigma[f], zeta = 0.0, d = g.eps + 1.0;
-    // ||Y_b||^2
+    double sig = ROWS ? 0.0 : g.sigma[f], zeta = 0.0, d = g.eps + 1.0;   // ROWS: sig = mean(s)
     double yy = 0.0;
-    for (long long t = tid; t < L * Mb; t += FITB_THREADS) {
-        const long long l = t / Mb, m = t - l * Mb;
-        const double y = (double)Yr[l * g.Mtot + m];
-        yy += y * y;
+    if constexpr (ROWS) {
+        // ||Y_b[l,:]||^2 per row: T lanes per row split the columns, an xor-butterfly folds them (T from L alone, as in fitb_product)
+        int T = 1;
+        while (T < 64 && L * T < FITB_THREADS) T <<= 1;
+        for (long long base = 0; base < L * T; base += FITB_THREADS) {
+            const long long it = base + tid;
+            const bool on = it < L * T;
+            const long long l = on ? it / T : 0;
+            double s = 0.0;
+            if (on)
+                for (long long m = it & (T - 1); m < Mb; m += T) {
+                    const double y = (double)Yr[l * g.Mtot + m];
+                    s = fma(y, y, s);
+                }
+            for (int off = T >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if (on && (it & (T - 1)) == 0) yn[l] = s;
+        }
+        double ss = 0.0;
+        for (long long l = tid; l < L; l += FITB_THREADS) {
+            const double s = g.sigma[(long long)f * L + l];
+            sv[l] = s;
+            ss += s;
+        }
+        sig = fitb_sum(ss, red) / Lg;                               // (its barriers publish B, SigmaB, CA, s and the row norms)
+    } else {
+        // ||Y_b||^2
+        for (long long t = tid; t < L * Mb; t += FITB_THREADS) {
+            const long long l = t / Mb, m = t - l * Mb;
+            const double y = (double)Yr[l * g.Mtot + m];
+            yy += y * y;
+        }
+        yy = fitb_sum(yy, red);                                    // (its barriers publish B, SigmaB, CA)
     }
-    yy = fitb_sum(yy, red);                                        // (its barriers publish B, SigmaB, CA)
     fitb_chunk_reduce(h2, L, part, BB, [&](int e, long long l) { return Bl[l * H + e / H] * Bl[l * H + e % H]; });
     // norm(B): sqrt(lambda_max(B'B)), the Gram of B scaled into range when B's own would underflow
     double nrmB;
@@ -336,9 +394,23 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
             const int grp = tid < H0 ? 0 : 1;
             al_s[tid] = pri_s[2 * grp] + 0.5;
             b0_s[tid] = pri_s[2 * grp + 1];
-            v_s[tid] = sig * BB[tid * H + tid] + Lg * SBm[tid * H + tid];
+            if constexpr (!ROWS) v_s[tid] = sig * BB[tid * H + tid] + Lg * SBm[tid * H + tid];
         }
-        fitb_product<NP>(Mb, L, Yr, g.Mtot, Yc, L, Bl, H, PAb);
+        if constexpr (ROWS) {
+            // Ql = diag(s) B (Ql is free: dB'dB has consumed its B_old - B); v_h = sum_l Ql_lh^2 + L mean(s) SigmaB_hh
+            for (long long t = tid; t < nb; t += FITB_THREADS) Ql[t] = sv[t / H] * Bl[t];
+            __syncthreads();
+            fitb_chunk_reduce(H, L, part, v_s, [&](int h, long long l) { return Ql[l * H + h] * Ql[l * H + h]; });
+            if (tid < H) v_s[tid] += Lg * sig * SBm[tid * H + tid];
+            if constexpr (FULL)                                     // B' diag(s) B, symmetric bit for bit (Dm is free until SigmaA's sum)
+                fitb_chunk_reduce(h2, L, part, Dm, [&](int e, long long l) {
+                    const int i = e / H, j = e % H;
+                    return Ql[l * H + (i < j ? i : j)] * Bl[l * H + (i < j ? j : i)];
+                });
+            fitb_product<NP>(Mb, L, Yr, g.Mtot, Yc, L, Ql, H, PAb);
+        } else {
+            fitb_product<NP>(Mb, L, Yr, g.Mtot, Yc, L, Bl, H, PAb);
+        }
         __syncthreads();
         int bad = 0;
         double gs[NGS];                                            // sum log beta, sum CA of each prior group: this thread's shares
@@ -352,7 +424,7 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
                 const double prec = v_s[vi] + CAb[t];
                 bad |= !isfinite(prec);
                 if constexpr (LOCAL) {
-                    const double ds = 1.0 / prec, a = (m < M0f && h >= hmask) ? 0.0 : sig * ds * PAb[t];
+                    const double ds = 1.0 / prec, a = (m < M0f && h >= hmask) ? 0.0 : (ROWS ? ds * PAb[t] : sig * ds * PAb[t]);
                     PAb[t] = a;
                     dSb[t] = ds;
                     const int grp = h < H0 ? 0 : (m < M0f ? 1 : 2);
@@ -392,7 +464,8 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int i = 16 * I + q16 + 4 * r, j = 16 * J + c16;
-                            g0[u][r] = (i < H && j < H) ? BB[i * H + j] + Lg * SBm[i * H + j] : 0.0;
+                            if constexpr (ROWS) g0[u][r] = (i < H && j < H) ? Dm[i * H + j] + Lg * sig * SBm[i * H + j] : 0.0;
+                            else g0[u][r] = (i < H && j < H) ? BB[i * H + j] + Lg * SBm[i * H + j] : 0.0;
                             acc[u][r] = 0.0;
                         }
             }
@@ -410,7 +483,9 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
                     for (int I = 0; I < NBK; ++I)
 #pragma unroll
                         for (int J = I; J < NBK; ++J, ++u) {
-                            f64x4 x = sig * g0[u];
+                            f64x4 x;
+                            if constexpr (ROWS) x = g0[u];          // (s is inside g0)
+                            else x = sig * g0[u];
                             if (I == J) {
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) x[r] += (q16 == (c16 & 3) && r == (c16 >> 2)) ? cad[I] : 0.0;
@@ -430,7 +505,7 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
                     const int lo = j < i ? j : i, hi = j < i ? i : j;
                     sm += W[lo * LD + hi] * pvec[j];                    // (pvec is zero beyond H; W is the identity padding there)
                 }
-                const double a = (lane < H && !(LOCAL && m < M0f && lane >= hmask)) ? -sig * sm : 0.0;
+                const double a = (lane < H && !(LOCAL && m < M0f && lane >= hmask)) ? (ROWS ? -sm : -sig * sm) : 0.0;
                 if constexpr (LOCAL) {
                     if (lane < H) {
                         const long long t = m * H + lane;
@@ -504,7 +579,7 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
         __syncthreads();
         for (int t = tid; t < NP * NP; t += FITB_THREADS) {
             const int i = t / NP, j = t % NP;
-            Wk[i * LD + j] = (i < H && j < H) ? sig * AA[i * H + j] + (i == j ? cb_s[i] : 0.0) : (i == j ? 1.0 : 0.0);
+            Wk[i * LD + j] = (i < H && j < H) ? sig * AA[i * H + j] + (i == j ? cb_s[i] : 0.0) : (i == j ? 1.0 : 0.0);   // (ROWS: mean(s))
         }
         __syncthreads();
         if (w == 0) {
@@ -519,24 +594,52 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
         }
         fitb_product<NP>(L, Mb, Yc, L, Yr, g.Mtot, PAb, H, Ql);
         __syncthreads();
-        // B = sigma Q SigmaB, a row per thread; Q's row then holds B_old - B
-        double bq = 0.0;
+        double trG = 0.0;                                           // ROWS: sum G o SigmaB, G = A'A + SigmaA
+        if constexpr (ROWS) {
+            for (int t = tid; t < h2; t += FITB_THREADS) trG += AA[t] * SBm[t];
+            trG = fitb_sum(trG, red);
+        }
+        // B = sigma Q SigmaB, a row per thread; Q's row then holds B_old - B (ROWS: sigma = s_l, and the row's updateSigma! follows)
+        double bq = 0.0, ssum = 0.0;
         for (long long l = tid; l < L; l += FITB_THREADS) {
             double q[NP];
 #pragma unroll
             for (int j = 0; j < NP; ++j) q[j] = j < H ? Ql[l * H + j] : 0.0;
+            double sl = sig, rl = 0.0;
+            if constexpr (ROWS) sl = sv[l];
             for (int h = 0; h < H; ++h) {
                 double s = 0.0;
 #pragma unroll
                 for (int j = 0; j < NP; ++j)
                     if (j < H) s += q[j] * SBm[j * H + h];
-                const double bn = sig * s, bo = Bl[l * H + h];
-                bq += bn * Ql[l * H + h];
+                const double bn = sl * s, bo = Bl[l * H + h];
+                if constexpr (ROWS) rl += bn * Ql[l * H + h];
+                else bq += bn * Ql[l * H + h];
                 Bl[l * H + h] = bn;
                 Ql[l * H + h] = bo - bn;
             }
+            if constexpr (ROWS) {
+                // zetaVec_l = zeta0 + ||Y_b[l,:]||^2 / 2 - r_l + (b_l'G b_l + tr) / 2 with the row's new b_l; then the new s_l
+#pragma unroll
+                for (int j = 0; j < NP; ++j) q[j] = j < H ? Bl[l * H + j] : 0.0;
+                double quad = 0.0;
+                for (int h = 0; h < H; ++h) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NP; ++j)
+                        if (j < H) s += q[j] * AA[j * H + h];
+                    quad += s * Bl[l * H + h];
+                }
+                const double zv = zeta0 + 0.5 * yn[l] - rl + 0.5 * (quad + trG), sn = eta / zv;
+                bad |= !isfinite(zv) || !isfinite(sn);
+                g.zeta[(long long)f * L + l] = zv;
+                sv[l] = sn;
+                ssum += sn;
+            }
         }
-        bq = fitb_sum(bq, red);
+        // (either sum's barriers publish the new B to the Grams below)
+        if constexpr (ROWS) sig = fitb_sum(ssum, red) / Lg;         // mean(s): every thread summed the rows it wrote, in row order
+        else bq = fitb_sum(bq, red);
         fitb_chunk_reduce(h2, L, part, BB, [&](int e, long long l) { return Bl[l * H + e / H] * Bl[l * H + e % H]; });
         double mB = 0.0, mD = 0.0;
         for (long long t = tid; t < nb; t += FITB_THREADS) {
@@ -553,11 +656,13 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
             dl_s[tid] = dl;
             cb_s[tid] = gam / dl;
         }
-        double tr = 0.0;
-        for (int t = tid; t < h2; t += FITB_THREADS) tr += AA[t] * (BB[t] + Lg * SBm[t]);
-        tr = fitb_sum(tr, red);
-        zeta = zeta0 + 0.5 * yy - bq + 0.5 * tr;
-        sig = eta / zeta;
+        if constexpr (!ROWS) {
+            double tr = 0.0;
+            for (int t = tid; t < h2; t += FITB_THREADS) tr += AA[t] * (BB[t] + Lg * SBm[t]);
+            tr = fitb_sum(tr, red);
+            zeta = zeta0 + 0.5 * yy - bq + 0.5 * tr;
+            sig = eta / zeta;
+        }
         if (g.est_priors && tid == 0) {
             // group sizes: M H0, M H1 (two groups); M H0, M0 H1, (M - M0) H1 (three: src/vbmf_trial.jl:442-507)
             const double ng[3] = {(double)Mb * (double)H0, (double)(LOCAL ? M0f : Mb) * (double)(H - H0),
@@ -612,9 +717,15 @@ __global__ __launch_bounds__(FITB_THREADS) void fit_batch_kernel(std::conditiona
         if (place == 2) g.A[o + t] = PAb[t];                        // (otherwise PAb is the fit's slice of g.A)
     }
     if (tid < NPRI) g.priors4[(long long)f * NPRI + tid] = pri_s[tid];
+    if constexpr (ROWS) {
+        if (sv != g.sigma + (long long)f * L)
+            for (long long l = tid; l < L; l += FITB_THREADS) g.sigma[(long long)f * L + l] = sv[l];
+    }
     if (tid == 0) {
-        g.sigma[f] = sig;
-        g.zeta[f] = zeta;
+        if constexpr (!ROWS) {
+            g.sigma[f] = sig;
+            g.zeta[f] = zeta;
+        }
         g.iters[f] = it;
         g.dlast[f] = d;
         g.status[f] = status;

@@ -423,16 +423,18 @@ static int fit_stage(vbmf_ctx* c, float* Yr, float* Yc) {
     return VBMF_OK;
 }
 
-// What vbmf_sparse_fit_batched and vbmf_local_fit_batched share once each has refused what it refuses about the context and the scalar
-// arguments: the per-fit checks, the layout of c->bags, the staging, the one launch and the read-back.  M0 = nullptr: the two-group
-// sweep with four priors per fit; else the three-group / masked sweep with nine (M0[f] checked against the fit's own M_b here).
+// What vbmf_sparse_fit_batched, vbmf_local_fit_batched and vbmf_rows_fit_batched share once each has refused what it refuses about the
+// context and the scalar arguments: the per-fit checks, the layout of c->bags, the staging, the one launch and the read-back.
+// M0 = nullptr without rows: the two-group sweep with four priors per fit; else the three-group / masked sweep with nine (M0[f] checked
+// against the fit's own M_b here).  rows: the row-noise sweep -- sigmaHat and zeta are nfits x L, eta[f] = eta0 + M_b / 2, and
+// M0 = nullptr stands for M0[f] = M_b.
 static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
                            int64_t niter, double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const int64_t* M0,
                            int64_t mask_H1, const double* gamma, const double* delta0, const double* eta, const double* zeta0,
                            double* priors, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA, double* delta,
                            double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat, int64_t* iters_done,
-                           double* d_last, int64_t* status, double* trace) {
-    const bool local = M0 != nullptr;
+                           double* d_last, int64_t* status, double* trace, bool rows = false) {
+    const bool local = M0 != nullptr || rows;
     const int64_t npri = local ? 9 : 4;
     const bool compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
     const int H = (int)c->H, NBK = nb_tier(H);
@@ -447,12 +449,12 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
         const int64_t Mb = col_off[b + 1] - col_off[b];
         if (!full_cov && compat && Mb < 2)
             FAIL(c, VBMF_ERR_INVALID, "%s: fit %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)f);
-        if (local && (M0[f] < 0 || M0[f] > Mb))
+        if (M0 && (M0[f] < 0 || M0[f] > Mb))
             FAIL(c, VBMF_ERR_INVALID, "%s: M0[%lld] = %lld outside 0..M_b = %lld", fn, (long long)f, (long long)M0[f], (long long)Mb);
         fit_off[f + 1] = fit_off[f] + Mb;
-        lds_doubles = std::max(lds_doubles, (size_t)fitb_lds_doubles(full_cov != 0, NBK, L, Mb, H));
+        lds_doubles = std::max(lds_doubles, (size_t)fitb_lds_doubles(full_cov != 0, NBK, L, Mb, H, rows));
         idx[(size_t)(nb + 1 + f)] = b;
-        if (local) idx[(size_t)(nb + 1 + nf + nf + 1 + f)] = M0[f];
+        if (local) idx[(size_t)(nb + 1 + nf + nf + 1 + f)] = M0 ? M0[f] : Mb;
     }
     for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
     if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
@@ -461,13 +463,14 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     auto run = [&]() -> int {
     HIPCHK(c, hipSetDevice(c->o.device));
     const int64_t SMH = fit_off[nf] * H, nidx = (int64_t)idx.size(), ntr = trace ? 2 * nf * niter : 0, ny = (L * c->M + 1) / 2;
+    const int64_t nrow = rows ? nf * L : 0;                         // rows: sigmaVec | zetaVec | the row norms, nf L each, behind beta
     // c->bags: [col_off | fit_bag | fit_off | M0 (int64) | gamma | delta0 | eta | zeta0 | sigma (nf each) | priors 4 or 9 nf | zeta | d_last
     //           | iters | status (int64) (nf each) | B | Bw | Qw (nf L H each) | SigmaB | SigmaA (nf H^2) | CB | delta (nf H) | CA | A | dS |
-    //           beta (sum M_b H each) | trace | Yr | Yc (L M floats each)]
+    //           beta (sum M_b H each) | rows: sigmaVec | zetaVec | row norms (nf L each) | trace | Yr | Yc (L M floats each)]
     const int64_t o_sc = nidx, o_pri = o_sc + 5 * nf, o_zeta = o_pri + npri * nf, o_dl = o_zeta + nf, o_it = o_dl + nf, o_st = o_it + nf,
                   o_b = o_st + nf, o_bw = o_b + nf * LH, o_qw = o_bw + nf * LH, o_sb = o_qw + nf * LH, o_sa = o_sb + nf * h2,
                   o_cb = o_sa + nf * h2, o_de = o_cb + nf * H, o_ca = o_de + nf * H, o_a = o_ca + SMH, o_ds = o_a + SMH, o_be = o_ds + SMH,
-                  o_tr = o_be + SMH, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
+                  o_sv = o_be + SMH, o_zv = o_sv + nrow, o_yn = o_zv + nrow, o_tr = o_yn + nrow, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
     double* d = nullptr;
     TRY(bags_reserve(c, total, &d));
     in.resize((size_t)((5 + npri) * nf));
@@ -475,7 +478,7 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     memcpy(in.data() + nf, delta0, (size_t)nf * 8);
     memcpy(in.data() + 2 * nf, eta, (size_t)nf * 8);
     memcpy(in.data() + 3 * nf, zeta0, (size_t)nf * 8);
-    memcpy(in.data() + 4 * nf, sigmaHat, (size_t)nf * 8);
+    if (!rows) memcpy(in.data() + 4 * nf, sigmaHat, (size_t)nf * 8);
     memcpy(in.data() + 5 * nf, priors, (size_t)(nf * npri) * 8);
     HIPCHK(c, hipMemcpyAsync(d, idx.data(), (size_t)nidx * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_sc, in.data(), in.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -483,6 +486,7 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     HIPCHK(c, hipMemcpyAsync(d + o_sb, SigmaB, (size_t)(nf * h2) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_cb, CB, (size_t)(nf * H) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_ca, CA, (size_t)SMH * 8, hipMemcpyHostToDevice, c->stream));
+    if (rows) HIPCHK(c, hipMemcpyAsync(d + o_sv, sigmaHat, (size_t)nrow * 8, hipMemcpyHostToDevice, c->stream));
     if (ntr) HIPCHK(c, hipMemsetAsync(d + o_tr, 0, (size_t)ntr * 8, c->stream));
     float* Yr = reinterpret_cast<float*>(d + o_yr);
     float* Yc = reinterpret_cast<float*>(d + o_yc);
@@ -491,17 +495,19 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     FitArgs a{Yr, Yc, (long long)L, (long long)c->M, di, di + nb + 1, di + nb + 1 + nf, H, (int)H0, (int)niter, compat ? 1 : 0,
               (c->o.reference_compat & VBMF_COMPAT_SPECTRAL_DELTA) ? 1 : 0, est_cb ? 1 : 0, est_priors ? 1 : 0, eps,
               d + o_sc, d + o_sc + nf, d + o_sc + 2 * nf, d + o_sc + 3 * nf, d + o_pri,
-              d + o_b, d + o_sb, d + o_cb, d + o_sc + 4 * nf, d + o_ca,
-              d + o_de, d + o_zeta, d + o_be, d + o_ds, d + o_sa, d + o_a, d + o_bw, d + o_qw,
+              d + o_b, d + o_sb, d + o_cb, rows ? d + o_sv : d + o_sc + 4 * nf, d + o_ca,
+              d + o_de, rows ? d + o_zv : d + o_zeta, d + o_be, d + o_ds, d + o_sa, d + o_a, d + o_bw, d + o_qw,
               reinterpret_cast<long long*>(d + o_it), d + o_dl, reinterpret_cast<long long*>(d + o_st), trace ? d + o_tr : nullptr};
     const size_t lds = lds_doubles * 8;
     // (the fit kernels exist for NB = 1 and 2: every rank above 16 runs the NB = 2 instance)
     const FitLocalArgs la{a, di + nb + 1 + nf + nf + 1, (int)mask_H1};
+    const FitRowsArgs ra{la, d + o_yn};
     dispatch<1, 2>(std::min(NBK, 2), [&](auto nbk) {
         dispatch<0, 1>(full_cov ? 1 : 0, [&](auto full) {
             constexpr int NBc = decltype(nbk)::value;
             constexpr bool FULLc = decltype(full)::value != 0;
-            if (local) hipLaunchKernelGGL((fit_batch_kernel<NBc, FULLc, true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, la);
+            if (rows) hipLaunchKernelGGL((fit_batch_kernel<NBc, FULLc, true, true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, ra);
+            else if (local) hipLaunchKernelGGL((fit_batch_kernel<NBc, FULLc, true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, la);
             else hipLaunchKernelGGL((fit_batch_kernel<NBc, FULLc>), dim3((unsigned)nf), dim3(FITB_THREADS), lds, c->stream, a);
         });
     });
@@ -510,7 +516,12 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     out.resize((size_t)(o_b - o_pri));
     sg.resize((size_t)nf);
     HIPCHK(c, hipMemcpyAsync(out.data(), d + o_pri, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sg.data(), d + o_sc + 4 * nf, (size_t)nf * 8, hipMemcpyDeviceToHost, c->stream));
+    if (rows) {
+        HIPCHK(c, hipMemcpyAsync(sigmaHat, d + o_sv, (size_t)nrow * 8, hipMemcpyDeviceToHost, c->stream));
+        if (zeta) HIPCHK(c, hipMemcpyAsync(zeta, d + o_zv, (size_t)nrow * 8, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(sg.data(), d + o_sc + 4 * nf, (size_t)nf * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(c, hipMemcpyAsync(BHat, d + o_b, (size_t)(nf * LH) * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(SigmaB, d + o_sb, (size_t)(nf * h2) * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(CB, d + o_cb, (size_t)(nf * H) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -523,11 +534,11 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     if (trace) HIPCHK(c, hipMemcpyAsync(trace, d + o_tr, (size_t)ntr * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(priors, out.data(), (size_t)(nf * npri) * 8);
-    if (zeta) memcpy(zeta, out.data() + (o_zeta - o_pri), (size_t)nf * 8);
+    if (zeta && !rows) memcpy(zeta, out.data() + (o_zeta - o_pri), (size_t)nf * 8);
     memcpy(d_last, out.data() + (o_dl - o_pri), (size_t)nf * 8);
     memcpy(iters_done, out.data() + (o_it - o_pri), (size_t)nf * 8);
     memcpy(status, out.data() + (o_st - o_pri), (size_t)nf * 8);
-    memcpy(sigmaHat, sg.data(), (size_t)nf * 8);
+    if (!rows) memcpy(sigmaHat, sg.data(), (size_t)nf * 8);
     return VBMF_OK;
     };
     const int rc = run();
@@ -549,7 +560,7 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
     const char* fn = "vbmf_sparse_fit_batched";
     if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
     if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse and two-group models only)", fn);
-    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_sparse_run / vbmf_dual_run per fit)", fn);
+    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_rows_fit_batched, or vbmf_sparse_run / vbmf_dual_run per fit)", fn);
     if (c->trial) FAIL(c, VBMF_ERR_INVALID, "%s: trial context (the sparse and two-group models only)", fn);
     if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set (use vbmf_sparse_run per fit)", fn);
     BagDims bd;
@@ -565,6 +576,33 @@ int vbmf_sparse_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, 
                            iters_done, d_last, status, trace);
 }
 
+}  // extern "C"
+
+// What vbmf_local_fit_batched and vbmf_rows_fit_batched refuse alike before fit_batched_run's per-fit checks.  rows: a *_DIAGVAR context
+// serves as well (only its Y is used), and M0 may be NULL (M0[f] = M_b).
+static int local_fit_checks(vbmf_ctx* c, const char* fn, bool rows, int64_t nbags, const int64_t* col_off, int64_t nfits, int64_t niter,
+                            int est_priors, int64_t H0, int64_t mask_H1, bool null_required) {
+    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
+    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse, two-group and three-group models only)", fn);
+    if (c->diagvar && !rows)
+        FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_rows_fit_batched, or vbmf_trial_run / vbmf_sparse_run per fit)", fn);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set on the context (the call's own M0 / mask_H1 describe the mask)", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (H0 < 0 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: H0 = %lld outside 0..H = %lld", fn, (long long)H0, (long long)c->H);
+    if (mask_H1 < 0 || mask_H1 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: mask_H1 = %lld outside 0..H = %lld", fn, (long long)mask_H1, (long long)c->H);
+    if (mask_H1 > 0 && (H0 != c->H || est_priors))
+        FAIL(c, VBMF_ERR_INVALID, "%s: mask_H1 > 0 needs H0 = H and est_priors = 0 (the masked model has one prior group and no hyper-prior fit)", fn);
+    if (null_required)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only %sdelta, %s, beta, diagSigmaATVec, SigmaA, ATVecHat and trace may be NULL)", fn,
+             rows ? "M0, " : "", rows ? "zetaVec" : "zeta");
+    return VBMF_OK;
+}
+
+extern "C" {
+
 // The three-group fit (vbmf_trial!, src/vbmf_trial.jl:528-604) and the label-masked sparse fit (train_local, examples/mil_util.jl:302-320)
 // of many [Y0 Y1] matrices in one call: vbmf_sparse_fit_batched's launch with a per-fit M0 and the two per-entry rules of FitLocalArgs.
 int vbmf_local_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
@@ -575,24 +613,34 @@ int vbmf_local_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, i
                            int64_t* status, double* trace) {
     if (!c) return VBMF_ERR_INVALID;
     const char* fn = "vbmf_local_fit_batched";
-    if (c->H > 32) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for H <= 32)", fn, (long long)c->H);
-    if (!c->sparse) FAIL(c, VBMF_ERR_INVALID, "%s: basic context (the sparse, two-group and three-group models only)", fn);
-    if (c->diagvar) FAIL(c, VBMF_ERR_INVALID, "%s: diag_var context (homoscedastic only; use vbmf_trial_run / vbmf_sparse_run per fit)", fn);
-    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set on the context (the call's own M0 / mask_H1 describe the mask)", fn);
-    BagDims bd;
-    TRY(bags_check(c, fn, nbags, col_off, bd));
-    if (nfits < 1 || nfits > (1ll << 20)) FAIL(c, VBMF_ERR_INVALID, "%s: nfits must be >= 1", fn);
-    if (niter < 1 || niter > (1ll << 24)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
-    if (H0 < 0 || H0 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: H0 = %lld outside 0..H = %lld", fn, (long long)H0, (long long)c->H);
-    if (mask_H1 < 0 || mask_H1 > c->H) FAIL(c, VBMF_ERR_INVALID, "%s: mask_H1 = %lld outside 0..H = %lld", fn, (long long)mask_H1, (long long)c->H);
-    if (mask_H1 > 0 && (H0 != c->H || est_priors))
-        FAIL(c, VBMF_ERR_INVALID, "%s: mask_H1 > 0 needs H0 = H and est_priors = 0 (the masked model has one prior group and no hyper-prior fit)", fn);
-    if (!fit_bag || !M0 || !gamma || !delta0 || !eta || !zeta0 || !priors9 || !BHat || !SigmaB || !CB || !sigmaHat || !CA || !iters_done ||
-        !d_last || !status)
-        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat and trace may be NULL)", fn);
+    TRY(local_fit_checks(c, fn, false, nbags, col_off, nfits, niter, est_priors, H0, mask_H1,
+                         !fit_bag || !M0 || !gamma || !delta0 || !eta || !zeta0 || !priors9 || !BHat || !SigmaB || !CB || !sigmaHat || !CA ||
+                             !iters_done || !d_last || !status));
     return fit_batched_run(c, fn, nbags, col_off, nfits, fit_bag, niter, eps, full_cov, est_cb, est_priors, H0, M0, mask_H1, gamma, delta0,
                            eta, zeta0, priors9, BHat, SigmaB, CB, sigmaHat, CA, delta, zeta, beta, diagSigmaATVec, SigmaA, ATVecHat,
                            iters_done, d_last, status, trace);
+}
+
+// The same fits under the heteroscedastic noise model, diag_var = true (examples/mil_util.jl:667 sets it for train, train_local and
+// train_dual): one noise precision per row of Y.  src/vbmf_sparse.jl:180-193 (updateA!, full_cov: s to the first power), :207-230
+// (updateA!, diagonal: v_h = sum_l (s_l B_lh)^2 + L mean(s) SigmaB_hh -- s enters SQUARED, the reference takes norm2 of the product),
+// :256-261 (updateB!), :309-315 (updateSigma!, row by row; sigmaHat and zeta are not touched); src/vbmf_dual.jl:222-299,370-386 and
+// src/vbmf_trial.jl:256-334,419-435 are the same.  One kernel family serves the sparse (H0 = H, est_priors = 0), two-group
+// (M0 = NULL: M0[f] = M_b), three-group and masked fits.  The context supplies Y only: a *_DIAG or a *_DIAGVAR context serves alike.
+int vbmf_rows_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
+                          double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const int64_t* M0, int64_t mask_H1,
+                          const double* gamma, const double* delta0, const double* etaVec, const double* zeta0, double* priors9,
+                          double* BHat, double* SigmaB, double* CB, double* sigmaVec, double* CA, double* delta, double* zetaVec,
+                          double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat, int64_t* iters_done, double* d_last,
+                          int64_t* status, double* trace) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_rows_fit_batched";
+    TRY(local_fit_checks(c, fn, true, nbags, col_off, nfits, niter, est_priors, H0, mask_H1,
+                         !fit_bag || !gamma || !delta0 || !etaVec || !zeta0 || !priors9 || !BHat || !SigmaB || !CB || !sigmaVec || !CA ||
+                             !iters_done || !d_last || !status));
+    return fit_batched_run(c, fn, nbags, col_off, nfits, fit_bag, niter, eps, full_cov, est_cb, est_priors, H0, M0, mask_H1, gamma, delta0,
+                           etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVec, CA, delta, zetaVec, beta, diagSigmaATVec, SigmaA, ATVecHat,
+                           iters_done, d_last, status, trace, true);
 }
 
 }  // extern "C"

@@ -1744,6 +1744,9 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
             // ... and their three-group / masked twins (vbmf_local_fit_batched)
             {(const void*)fit_batch_kernel<1, false, true>, fb, 0}, {(const void*)fit_batch_kernel<1, true, true>, fb, 0},
             {(const void*)fit_batch_kernel<2, false, true>, fb, 0}, {(const void*)fit_batch_kernel<2, true, true>, fb, 0},
+            // ... and the row-noise sweeps built on those (vbmf_rows_fit_batched)
+            {(const void*)fit_batch_kernel<1, false, true, true>, fb, 0}, {(const void*)fit_batch_kernel<1, true, true, true>, fb, 0},
+            {(const void*)fit_batch_kernel<2, false, true, true>, fb, 0}, {(const void*)fit_batch_kernel<2, true, true, true>, fb, 0},
             {(const void*)fit_basic_kernel<1>, fb, 0}, {(const void*)fit_basic_kernel<2>, fb, 0},
             {(const void*)fit_basic_gram_kernel<1>, fb, 0}, {(const void*)fit_basic_gram_kernel<2>, fb, 0},
             {(const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, LDS8_BYTES, 4},

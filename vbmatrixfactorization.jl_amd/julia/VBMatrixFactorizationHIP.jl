@@ -820,9 +820,12 @@ end
 # With M0 (one entry per fit: the leading columns of its bag that are the negative instances) the call is vbmf_local_fit_batched: pri is
 # 9 x nfits in vbmf_trial_get_priors' order, H0 splits the columns into prior groups 1 and 2 / 3, mask_H1 > 0 holds the last mask_H1
 # columns of A at zero in the rows 1:M0.
+# With rows (diag_var = true, examples/mil_util.jl:667: one noise precision per row of Y) the call is vbmf_rows_fit_batched: pri is
+# 9 x nfits, M0 = nothing goes down as NULL (M0[f] = M_b: the two-group model), the fits start from sigmaVecHat and etaVec[1] and fill
+# sigmaVecHat and zetaVec; sigmaHat and zeta stay as they were.
 function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int, eps::Float64, full_cov::Bool, est_cb::Bool,
                         est_priors::Bool, H0::Int, pri::Matrix{Float64}, bag_of::Vector{Int}, variant::Int;
-                        M0::Union{Nothing,Vector{Int64}} = nothing, mask_H1::Int = 0)
+                        M0::Union{Nothing,Vector{Int64}} = nothing, mask_H1::Int = 0, rows::Bool = false)
     nb, nf = length(Ys), length(ps)
     (nb >= 1 && nf >= 1 && length(bag_of) == nf) || error("$fn: one bag_of entry per parameter set")
     niter >= 1 || error("$fn: niter must be >= 1")
@@ -833,6 +836,7 @@ function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int,
         1 <= bag_of[f] <= nb || error("$fn: bag_of[$f] = $(bag_of[f]) outside 1..$nb")
         (p.L, p.M, p.H) == (L, size(Ys[bag_of[f]], 2), H) || error("$fn: fit $f does not match its bag")
         (full_cov || p.M >= 2) || error("$fn: fit $f works on a 1-column bag: the diagonal form needs M >= 2")
+        (!rows || (length(p.sigmaVecHat) == L && length(p.etaVec) >= 1)) || error("$fn: fit $f: diag_var starts from sigmaVecHat (L) and etaVec")
     end
     off = Int64[0; cumsum([Int64(size(Y, 2)) for Y in Ys])]
     M = off[end]
@@ -842,17 +846,26 @@ function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int,
     chk(Ptr{Cvoid}(C_NULL), ccall((:vbmf_create, libvbmf), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Ref{VbmfOpts}), h, L, M, H, opts))
     fb = Int64[b - 1 for b in bag_of]
     ga = Float64[p.gamma0 + p.L / 2 for p in ps]; d0 = Float64[p.delta0 for p in ps]
-    eta = Float64[p.eta0 + p.L * p.M / 2 for p in ps]; z0 = Float64[p.zeta0 for p in ps]
+    eta = rows ? Float64[p.etaVec[1] for p in ps] : Float64[p.eta0 + p.L * p.M / 2 for p in ps]; z0 = Float64[p.zeta0 for p in ps]
     B = reduce(vcat, [vec(Matrix{Float64}(p.BHat)) for p in ps]); SB = reduce(vcat, [vec(Matrix{Float64}(p.SigmaB)) for p in ps])
-    cb = reduce(vcat, [Vector{Float64}(p.CB) for p in ps]); sg = Float64[p.sigmaHat for p in ps]
+    cb = reduce(vcat, [Vector{Float64}(p.CB) for p in ps])
+    sg = rows ? reduce(vcat, [Vector{Float64}(p.sigmaVecHat) for p in ps]) : Float64[p.sigmaHat for p in ps]
     ca = reduce(vcat, [Vector{Float64}(p.CA) for p in ps])
     n = length(ca)
-    dl = Array{Float64}(undef, nf * H); ze = Array{Float64}(undef, nf); be = Array{Float64}(undef, n); ds = similar(be); a = similar(be)
+    dl = Array{Float64}(undef, nf * H); ze = Array{Float64}(undef, rows ? nf * L : nf); be = Array{Float64}(undef, n); ds = similar(be); a = similar(be)
     SA = Array{Float64}(undef, H, H, nf)
     it = zeros(Int64, nf); dlast = Array{Float64}(undef, nf); st = zeros(Int64, nf)
     try
         chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
-        if M0 === nothing
+        if rows
+        chk(h[], ccall((:vbmf_rows_fit_batched, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Int64}, Int64, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64},
+             Ptr{Int64}, Ptr{Float64}),
+            h[], nb, off, nf, fb, niter, eps, full_cov, est_cb, est_priors, H0, M0 === nothing ? C_NULL : M0, mask_H1, ga, d0, eta, z0,
+            pri, B, SB, cb, sg, ca, dl, ze, be, ds, SA, a, it, dlast, st, C_NULL))
+        elseif M0 === nothing
         chk(h[], ccall((:vbmf_sparse_fit_batched, libvbmf), Cint,
             (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Float64}, Ptr{Float64},
              Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
@@ -883,7 +896,11 @@ function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int,
         p.SigmaB = reshape(SB[(f-1)*H*H+1:f*H*H], H, H)
         p.CB = cb[(f-1)*H+1:f*H]
         est_cb && (p.delta = dl[(f-1)*H+1:f*H])
-        p.sigmaHat, p.zeta = sg[f], ze[f]
+        if rows
+            p.sigmaVecHat, p.zetaVec = sg[(f-1)*L+1:f*L], ze[(f-1)*L+1:f*L]
+        else
+            p.sigmaHat, p.zeta = sg[f], ze[f]
+        end
         p.L * p.M <= (1 << 24) && (p.YHat = p.BHat * p.AHat')
     end
     return dlast, it, st
@@ -893,11 +910,17 @@ end
 vbmf_sparse! for many independent fits in ONE device call (the restart loop of examples/mil_util.jl:124-145): does what
 `[vbmf_sparse!(Ys[bag_of[f]], ps[f], niter; eps = eps, full_cov = full_cov) for f in 1:length(ps)]` does and returns
 (d, sweeps run, status) per fit; status 1 = the fit met a non-finite precision or a bad pivot and stopped.  No labels, H <= 32.
+diag_var = true: one noise precision per row of Y (examples/mil_util.jl:667), through vbmf_rows_fit_batched.
 """
 function vbmf_sparse_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; eps::Float64 = 1e-6,
-                            full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)))
+                            full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)),
+                            diag_var::Bool = false)
     for (f, p) in enumerate(ps)
         (p.H1 == 0 && isempty(p.labels)) || error("vbmf_sparse_batch!: fit $f has labels; use vbmf_sparse! per fit")
+    end
+    if diag_var
+        pri9 = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0, p.alpha0, p.beta0, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
+        return fit_batch_run!("vbmf_sparse_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri9, bag_of, 1; rows = true)
     end
     pri = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0)[k] for k in 1:4, p in ps]
     return fit_batch_run!("vbmf_sparse_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri, bag_of, 1)
@@ -909,9 +932,21 @@ all fits share one H0; est_priors refits (alpha00, beta00, alpha01, beta01) ever
 """
 function vbmf_dual_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameters}, niter::Int; eps::Float64 = 1e-6,
                           full_cov::Bool = false, est_cb::Bool = true, est_priors::Bool = true,
-                          bag_of::Vector{Int} = collect(1:length(ps)))
+                          bag_of::Vector{Int} = collect(1:length(ps)), diag_var::Bool = false)
     H0 = ps[1].H0
     all(p.H0 == H0 for p in ps) || error("vbmf_dual_batch!: one H0 per call")
+    if diag_var                                                     # the nine-slot entry: group 3 is empty, slots 7, 8 the posterior shapes
+        pri9 = Float64[(p.alpha00, p.beta00, p.alpha01, p.beta01, p.alpha01, p.beta01, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
+        out = fit_batch_run!("vbmf_dual_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri9, bag_of, 3; rows = true)
+        for (f, p) in enumerate(ps)
+            p.A0Hat, p.A1Hat = p.AHat[:, 1:p.H0], p.AHat[:, p.H0+1:end]
+            p.CA0, p.CA1 = dual_split(p.CA, p.M, p.H, p.H0); p.beta0, p.beta1 = dual_split(p.beta, p.M, p.H, p.H0)
+            p.alpha00, p.beta00, p.alpha01, p.beta01 = pri9[1, f], pri9[2, f], pri9[3, f], pri9[4, f]
+            p.alpha0, p.alpha1 = pri9[7, f], pri9[8, f]
+            p.alpha = [p.alpha0, p.alpha1]
+        end
+        return out
+    end
     pri = Float64[(p.alpha00, p.beta00, p.alpha01, p.beta01)[k] for k in 1:4, p in ps]
     out = fit_batch_run!("vbmf_dual_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri, bag_of, 3)
     for (f, p) in enumerate(ps)
@@ -1253,13 +1288,13 @@ M0 is per fit; est_priors refits the three (alpha0g, beta0g) pairs every sweep (
 """
 function vbmf_trial_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_trial_parameters}, niter::Int; eps::Float64 = 1e-6,
                            full_cov::Bool = false, est_cb::Bool = true, est_priors::Bool = true,
-                           bag_of::Vector{Int} = collect(1:length(ps)))
+                           bag_of::Vector{Int} = collect(1:length(ps)), diag_var::Bool = false)
     H0 = ps[1].H0
     all(p.H0 == H0 for p in ps) || error("vbmf_trial_batch!: one H0 per call")
     all(0 <= p.M0 <= p.M for p in ps) || error("vbmf_trial_batch!: M0 outside 0..M")
     pri = Float64[(p.alpha01, p.beta01, p.alpha02, p.beta02, p.alpha03, p.beta03, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
     out = fit_batch_run!("vbmf_trial_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri, bag_of, 4;
-                         M0 = Int64[p.M0 for p in ps])
+                         M0 = Int64[p.M0 for p in ps], rows = diag_var)
     for (f, p) in enumerate(ps)
         p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, 1:p.H0], p.AHat[1:p.M0, p.H0+1:end], p.AHat[p.M0+1:end, p.H0+1:end]
         p.CA1, p.CA2, p.CA3 = trial_split(p.CA, p.M, p.H, p.H0, p.M0)
@@ -1276,7 +1311,8 @@ Y = [Y0 Y1]): see vbmf_sparse_batch!.  The labels of every fit are exactly 1:M0 
 the last H1 columns of AHat stay zero in the rows 1:M0 (src/vbmf_sparse.jl:245).  Any other label set: vbmf_sparse! per fit.
 """
 function vbmf_sparse_masked_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; eps::Float64 = 1e-6,
-                                   full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)))
+                                   full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)),
+                                   diag_var::Bool = false)
     H1 = ps[1].H1
     for (f, p) in enumerate(ps)
         (p.H1 == H1 && 0 <= H1 <= p.H) || error("vbmf_sparse_masked_batch!: one H1 in 0..H per call")
@@ -1285,7 +1321,7 @@ function vbmf_sparse_masked_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_
     end
     pri = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0, p.alpha0, p.beta0, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
     return fit_batch_run!("vbmf_sparse_masked_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri, bag_of, 1;
-                          M0 = Int64[length(p.labels) for p in ps], mask_H1 = H1)
+                          M0 = Int64[length(p.labels) for p in ps], mask_H1 = H1, rows = diag_var)
 end
 
 end # module
