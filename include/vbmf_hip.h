@@ -395,6 +395,48 @@ int vbmf_rows_fit_batched(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, 
                           double* priors9, double* BHat, double* SigmaB, double* CB, double* sigmaVec, double* CA,
                           double* delta, double* zetaVec, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
                           int64_t* iters_done, double* d_last, int64_t* status, double* trace);
+/* vbmf_ard_fit_batched_form: the fits of vbmf_local_fit_batched (diag_var = 0) and of vbmf_rows_fit_batched (diag_var != 0) with the
+ * form chosen by the caller.  The argument list is vbmf_rows_fit_batched's.  diag_var = 0: etaVec, sigmaVec and zetaVec are the per-fit
+ * scalars eta, sigmaHat and zeta of vbmf_local_fit_batched, a `*_DIAG` context is required, and M0 may be NULL (M0[f] = M_b).
+ *   form = VBMF_FIT_FORM_STREAM (0)  one workgroup per fit, the whole loop in one launch: every output is bit-identical to
+ *        vbmf_local_fit_batched / vbmf_rows_fit_batched for the same arguments
+ *   form = VBMF_FIT_FORM_SPLIT (3)   every fit is spread over ceil(M_b / slice_cols) workgroups.  A fit's columns are cut into slices of
+ *        slice_cols columns counted from its own first column (the last may be short); a sweep is two launches, a column pass with one
+ *        workgroup per (fit, slice) -- updateA!, updateCA! and the slice's shares of A'A, SigmaA, Q = Y A and the prior sums -- and a
+ *        fold with one workgroup per fit that sums the shares in slice order and does the rest of the sweep.  No workgroup waits for
+ *        another and nothing is an atomic: a fit's numbers are a function of (L, M_b, H, H0, M0, slice_cols) and its own inputs, not of
+ *        its place in the call.  They differ from form 0's in rounding only (another summation order).  The host enqueues
+ *        VBMF_FIT_SPLIT_CHUNK sweeps at a time and reads the fits' done words in between; a stopped fit's workgroups return at once.
+ *        iters_done, d_last, status and trace mean what they mean in form 0.
+ *   form = VBMF_FIT_FORM_AUTO (2)    per fit: split when M_b >= VBMF_FIT_SPLIT_MIN_COLS (full_cov: VBMF_FIT_SPLIT_MIN_COLS_FULL), else
+ *        the one-workgroup loop; the two groups run one after the other
+ *   form = VBMF_FIT_FORM_GRAM (1)    VBMF_ERR_UNSUPPORTED: these models have no Gram form.  Any other form: VBMF_ERR_INVALID.
+ * slice_cols: 0 = VBMF_FIT_SPLIT_COLS (narrowed to the widest multiple of 8 whose state, 3 slice_cols H doubles, fits in LDS beside
+ * full_cov's images); otherwise a multiple of 8, at least 8 (else VBMF_ERR_INVALID); one too wide for LDS returns VBMF_ERR_UNSUPPORTED.
+ * form_used (nfits, may be NULL): 0 / 3 per fit.  Refusals: those of vbmf_local_fit_batched / vbmf_rows_fit_batched with their codes,
+ * then form and slice_cols, all before any launch, copy or change.
+ * The constants are measured ones (MI355X, L = 166, H = 5, 50 sweeps, profiles/fit_split_tune.txt, fit_split_widths.txt; DESIGN.md
+ * section 19).  VBMF_FIT_SPLIT_COLS: of 64 / 128 / 256 / 512 the fastest on 20 diagonal fits at 166 x 3000; 20 full_cov fits at
+ * 166 x 640 prefer 64 by 15 %, and the two cases together tie at 64 and 128.  VBMF_FIT_SPLIT_MIN_COLS (diagonal form) and
+ * VBMF_FIT_SPLIT_MIN_COLS_FULL: the split form beat the one-workgroup loop by more than the spread at every width tested, 160 the
+ * narrowest; narrower bags were not measured and stay with the loop.  VBMF_FIT_SPLIT_CHUNK: 4, 8, 16 and 50 sweeps between two reads
+ * of the done words came out within the spread of each other; 8 bounds the empty launches behind the last stop at sixteen.
+ * Tuning switch, like the library's other VBMF_* environment variables: VBMF_FIT_SPLIT_CHUNK = 1 .. 65536 in the environment replaces
+ * the chunk length for the calls of that process (scripts/fit_split_mil.py measures with it).  It changes how often the host looks,
+ * never a number a fit computes.  In a mixed form = 2 call the caller's arrays are written only after both groups have run. */
+#define VBMF_FIT_FORM_SPLIT 3
+#define VBMF_FIT_SPLIT_COLS 128
+#define VBMF_FIT_SPLIT_MIN_COLS 160
+#define VBMF_FIT_SPLIT_MIN_COLS_FULL 160
+#define VBMF_FIT_SPLIT_CHUNK 8
+int vbmf_ard_fit_batched_form(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag,
+                              int64_t niter, double eps, int full_cov, int est_cb, int est_priors,
+                              int64_t H0, const int64_t* M0, int64_t mask_H1,
+                              const double* gamma, const double* delta0, const double* etaVec, const double* zeta0,
+                              double* priors9, double* BHat, double* SigmaB, double* CB, double* sigmaVec, double* CA,
+                              double* delta, double* zetaVec, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat,
+                              int64_t* iters_done, double* d_last, int64_t* status, double* trace,
+                              int diag_var, int64_t form, int64_t slice_cols, int64_t* form_used);
 int vbmf_sparse_step(vbmf_ctx* ctx, int which);           /* reference order A, B, CA, CB, SIGMA (:369-376) */
 /* vbmf_sparse! loop (src/vbmf_sparse.jl:344-410): returns d like the reference; trace: niter x 4 (d, sigmaHat, 0, 0)
  * Gram form.  A VBMF_VARIANT_SPARSE_DIAG context with full_cov off, one rank, bf16 Y, bf16x2 factors and

@@ -1481,12 +1481,17 @@ def _write_A_side(p, r, k, s0):
     return s1
 
 
-def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of, masked=False, diag_var=False):
+def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of, masked=False, diag_var=False,
+                      form="stream", slice_cols=None):
     """The four batched fits of the sparse family: the host checks, the one device call, the fields of every set; returns the list of d.
     The models with a per-fit M0 -- the three-group one and, with masked, the sparse one under a label mask -- go through
     vbmf_local_fit_batched (H0 in 0..H), the other two through vbmf_sparse_fit_batched (H0 in 1..H).  diag_var: all four go through
     vbmf_rows_fit_batched (the models without a per-fit M0 with M0 = None: every column in group 2), from sigmaVecHat and etaVec[0];
-    sigmaVecHat and zetaVec are filled, sigmaHat and zeta are left as they were."""
+    sigmaVecHat and zetaVec are filled, sigmaHat and zeta are left as they were.  form "split" / "auto" (and "stream" with a
+    slice_cols): all four go through vbmf_ard_fit_batched_form in either noise model, nine prior values per fit; the default, "stream"
+    with slice_cols None, makes the calls above as it always did.  Every set gets p.form: 0 (one workgroup) or 3 (split)."""
+    code, sc = capi.ard_fit_form_code(form), capi.ard_slice_cols(slice_cols)
+    by_form = code != capi.VBMF_FIT_FORM_STREAM or sc != 0
     refuse, params, bag_of, H, L, Ms = _fit_front(fn, one, kind, SparseBags, Ys, params, niter, bag_of)
     m = _MODELS[kind]
     local = masked or m.M0
@@ -1521,7 +1526,7 @@ def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, e
         _check_derived(p)
         if _alpha_not_derived(m, p):
             refuse(f"fit {f}: params.alpha = {p.alpha} is not alpha0 + 1/2 (src/vbmf_sparse.jl:131)")
-    rows_local = local or diag_var
+    rows_local = local or diag_var or by_form
     # the hyper-prior pairs of the entry's two (three) groups; a model with fewer groups gives its last pair again
     pairs = [k for g in range(3 if rows_local else 2) for k in m.groups[min(g, len(m.groups) - 1)][:2]]
     if diag_var:
@@ -1536,7 +1541,10 @@ def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, e
             np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1) for p in params]))
     kw = dict(H0=H if m.labels else int(params[0].H0), full_cov=full_cov, est_cb=est_cb, est_priors=est_priors and not m.labels)
     with _on_device(Ys, H, SparseBags) as bags:
-        if diag_var:
+        if by_form:
+            r = bags.ctx.ard_fit_batched_form(bags.col_off, *args, M0s if local else None, mask_H1=int(params[0].H1) if masked else 0, **kw,
+                                              diag_var=diag_var, form=form, slice_cols=slice_cols)
+        elif diag_var:
             r = bags.ctx.rows_fit_batched(bags.col_off, *args, M0s if local else None, mask_H1=int(params[0].H1) if masked else 0, **kw)
         elif local:
             r = bags.ctx.local_fit_batched(bags.col_off, *args, M0s, mask_H1=int(params[0].H1) if masked else 0, **kw)
@@ -1549,12 +1557,13 @@ def _sparse_fit_batch(fn, one, kind, Ys, params, niter, eps, full_cov, est_cb, e
         if est_cb:
             p.delta = r["delta"][f].copy()
         p.iters, p.status = int(r["iters"][f]), int(r["status"][f])
+        p.form = int(r["form_used"][f]) if by_form else capi.VBMF_FIT_FORM_STREAM
         if m.views is not None:
             m.views(p)
             if local:
                 for k, v in zip(Context.TRIAL_KEYS, r["priors9"][f]):   # the pairs, and the shapes the last updateCA! used
                     setattr(p, k, float(v))
-            elif diag_var:                                          # the two-group model through the nine-slot entry: slots 6, 7
+            elif rows_local:                                        # the two-group model through the nine-slot entry: slots 6, 7
                 p.alpha00, p.beta00, p.alpha01, p.beta01 = (float(v) for v in r["priors9"][f, :4])
                 p.alpha0, p.alpha1 = float(r["priors9"][f, 6]), float(r["priors9"][f, 7])
             else:
@@ -1575,7 +1584,12 @@ def _rows(diag_var):
     return dict(diag_var=True) if diag_var else {}
 
 
-def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, diag_var=False):
+def _split(form, slice_cols):
+    """the keywords of the form choice, absent at their defaults: the default calls are made as they always were"""
+    return {} if form == "stream" and slice_cols is None else dict(form=form, slice_cols=slice_cols)
+
+
+def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, diag_var=False, form="stream", slice_cols=None):
     """vbmf_sparse! for many independent fits in one device call: does what [vbmf_sparse_(Ys[bag_of[f]], p, niter, eps=eps, ...) for
     f, p in enumerate(params)] does (the restart loop of examples/mil_util.jl:124-145) -- fills on every p the fields vbmf_sparse_
     fills, plus p.iters (sweeps run) and p.status (1: the fit met a non-finite precision or a bad pivot and stopped), and returns the
@@ -1583,44 +1597,54 @@ def vbmf_sparse_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True,
     bag_of[f]: the fit's bag (default: fit f on bag f), so restarts share one upload.  Every fit's whole loop runs in one workgroup of
     one launch (include/vbmf_hip.h, vbmf_sparse_fit_batched).  diag_var=True: one noise precision per row of Y (examples/mil_util.jl:667),
     through vbmf_rows_fit_batched -- the fits start from p.sigmaVecHat and p.etaVec[0] and fill p.sigmaVecHat and p.zetaVec; p.sigmaHat
-    and p.zeta stay as they were, as after vbmf_sparse_(..., diag_var=True)."""
+    and p.zeta stay as they were, as after vbmf_sparse_(..., diag_var=True).
+    form: "stream" (the default: as above), "split" (every fit spread over ceil(M_b / slice_cols) workgroups, two launches per sweep:
+    the form for a few wide fits; slice_cols None = capi.VBMF_FIT_SPLIT_COLS, else a multiple of 8) or "auto" (capi.ard_fit_form_auto
+    per fit) -- the same iteration, another summation order (include/vbmf_hip.h, vbmf_ard_fit_batched_form).  p.form: 0 or 3.  These
+    models have no Gram form: form="gram" is refused (it is vbmf_batch_'s, for the basic model)."""
     return _sparse_fit_batch("vbmf_sparse_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb, False, bag_of,
-                             **_rows(diag_var))
+                             **_rows(diag_var), **_split(form, slice_cols))
 
 
-def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True, diag_var=False):
+def vbmf_dual_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True, diag_var=False,
+                     form="stream", slice_cols=None):
     """vbmf_dual! for many independent fits in one device call (the restart loop of examples/mil_util.jl:347-379): see
-    vbmf_sparse_batch_, diag_var included; params: one vbmf_dual_parameters per fit, all with one H0."""
+    vbmf_sparse_batch_, diag_var, form and slice_cols included; params: one vbmf_dual_parameters per fit, all with one H0."""
     return _sparse_fit_batch("vbmf_dual_batch_", "vbmf_dual_", vbmf_dual_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors, bag_of,
-                             **_rows(diag_var))
+                             **_rows(diag_var), **_split(form, slice_cols))
 
 
-def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True, diag_var=False):
+def vbmf_trial_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, est_priors=True, diag_var=False,
+                      form="stream", slice_cols=None):
     """vbmf_trial! for many independent fits in one device call: does what [vbmf_trial_(Ys[bag_of[f]], p, niter, eps=eps, ...) for f, p
     in enumerate(params)] does (src/vbmf_trial.jl:528-604) -- fills on every p the fields vbmf_trial_ fills (the group views A1Hat..A3Hat,
     CA1..3, beta1..3, the posterior shapes alpha1..3 and the six hyper-priors included), plus p.iters and p.status as vbmf_sparse_batch_
     does, and returns the list of d.  params: one vbmf_trial_parameters per fit, one H <= 32 and one H0 per call, M0 per fit.  Every
-    fit's whole loop runs in one workgroup of one launch (include/vbmf_hip.h, vbmf_local_fit_batched).  diag_var: as in
-    vbmf_sparse_batch_."""
+    fit's whole loop runs in one workgroup of one launch (include/vbmf_hip.h, vbmf_local_fit_batched).  diag_var, form, slice_cols: as
+    in vbmf_sparse_batch_."""
     return _sparse_fit_batch("vbmf_trial_batch_", "vbmf_trial_", vbmf_trial_parameters, Ys, params, niter, eps, full_cov, est_cb, est_priors,
-                             bag_of, **_rows(diag_var))
+                             bag_of, **_rows(diag_var), **_split(form, slice_cols))
 
 
-def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, diag_var=False):
+def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_cb=True, bag_of=None, diag_var=False, form="stream",
+                              slice_cols=None):
     """vbmf_sparse! with a label mask for many independent fits in one device call (the fit of train_local, examples/mil_util.jl:302-320,
     on Y = [Y0 Y1]): see vbmf_sparse_batch_.  params: one vbmf_sparse_parameters per fit whose labels are exactly the prefix 1..M0 of
     the columns (possibly empty; M0 per fit), with one H1 per call: the last H1 columns of AHat stay zero in the rows 1..M0
-    (src/vbmf_sparse.jl:245).  Any other label set is refused: run it with vbmf_sparse_.  diag_var: as in vbmf_sparse_batch_."""
+    (src/vbmf_sparse.jl:245).  Any other label set is refused: run it with vbmf_sparse_.  diag_var, form,
+    slice_cols: as in vbmf_sparse_batch_."""
     return _sparse_fit_batch("vbmf_sparse_masked_batch_", "vbmf_sparse_", vbmf_sparse_parameters, Ys, params, niter, eps, full_cov, est_cb,
-                             False, bag_of, masked=True, **_rows(diag_var))
+                             False, bag_of, masked=True, **_rows(diag_var), **_split(form, slice_cols))
 
 
-def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False):
+def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False, form="stream", slice_cols=None):
     """The reference's train_local (examples/mil_util.jl:302-320) over many (Y0, Y1) pairs with all the fits in ONE device call per
     round: per pair Y = [Y0 Y1] and vbmf_sparse_init(Y, H, H1=H1, labels=1:M0), drawn in fold order from the one generator; every fold
     runs vbmf_sparse! in the diagonal form (:314); then, as the loop of :312-317 does, a fold whose norm(AHat) and norm(BHat) (operator
     2-norms) are both below 1e-2 runs again from where it stands, one further call per round, ten rounds at most.  diag_var goes to
-    every vbmf_sparse! as it does at :314.  Returns the list of parameter sets."""
+    every vbmf_sparse! as it does at :314; form and slice_cols to every vbmf_sparse_masked_batch_ call.  Returns the list of parameter
+    sets."""
+    capi.ard_fit_form_code(form)
     rng = np.random.default_rng() if rng is None else rng
     Ys, ps = [], []
     for Y0, Y1 in folds:
@@ -1635,17 +1659,21 @@ def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False):
         again = [k for k, p in enumerate(ps) if all(v < bound[k] for v in norms(p))]
         if not again:
             break
-        vbmf_sparse_masked_batch_([Ys[k] for k in again], [ps[k] for k in again], niter, eps=eps, full_cov=False, **_rows(diag_var))
+        vbmf_sparse_masked_batch_([Ys[k] for k in again], [ps[k] for k in again], niter, eps=eps, full_cov=False, **_rows(diag_var),
+                                  **_split(form, slice_cols))
         bound = [1e-2] * len(ps)                                    # :315
     return ps
 
 
-def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, full_cov=None, diag_var=False, rng=None):
+def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, full_cov=None, diag_var=False, rng=None, form="stream",
+                 slice_cols=None):
     """The restart loops of examples/mil_util.jl:124-134 (model="sparse": eps = 1e-6, full_cov = false) and :347-354 (model="dual":
     eps = 1e-4, full_cov = true) with all nstarts initialisations drawn in order and run in ONE device call.  Returns the parameter set
     the reference's loop would have returned: sparse -- the first with d <= 2 eps and not NaN, else the last; dual -- the first with
     norm(AHat) + norm(BHat) >= 1e-2, else the last.  All nstarts fits run, also when the first would have been accepted: the launch
-    costs what its slowest fit costs, and the starts behind the accepted one are discarded."""
+    costs what its slowest fit costs, and the starts behind the accepted one are discarded.  form, slice_cols: vbmf_sparse_batch_'s
+    (a wide Y is the case form="split" exists for)."""
+    capi.ard_fit_form_code(form)
     if model not in ("sparse", "dual"):
         raise ValueError(f"fit_restarts: model = {model!r} ('sparse' or 'dual')")
     if diag_var:
@@ -1657,14 +1685,15 @@ def fit_restarts(Y, H, niter, model="sparse", H0=None, nstarts=10, eps=None, ful
     if model == "sparse":
         eps = 1e-6 if eps is None else eps
         ps = [vbmf_sparse_init(Y, H, rng=rng) for _ in range(int(nstarts))]
-        ds = vbmf_sparse_batch_([Y], ps, niter, eps=eps, full_cov=bool(full_cov), bag_of=[0] * len(ps))
+        ds = vbmf_sparse_batch_([Y], ps, niter, eps=eps, full_cov=bool(full_cov), bag_of=[0] * len(ps), **_split(form, slice_cols))
         for p, d in zip(ps, ds):
             if d <= 2 * eps:                                             # (false for NaN, which :130-132 turns into a restart)
                 return p
         return ps[-1]
     eps = 1e-4 if eps is None else eps
     ps = [vbmf_dual_init(Y, H, H if H0 is None else H0, rng=rng) for _ in range(int(nstarts))]
-    vbmf_dual_batch_([Y], ps, niter, eps=eps, full_cov=True if full_cov is None else bool(full_cov), bag_of=[0] * len(ps))
+    vbmf_dual_batch_([Y], ps, niter, eps=eps, full_cov=True if full_cov is None else bool(full_cov), bag_of=[0] * len(ps),
+                     **_split(form, slice_cols))
     for p in ps:
         if not (np.linalg.norm(p.AHat, 2) + np.linalg.norm(p.BHat, 2) < 1e-2):   # Julia 0.5 norm(::Matrix): the operator 2-norm
             return p
@@ -1721,17 +1750,21 @@ def row_gram_batch(bags):
         return up.ctx.row_gram(up.col_off)
 
 
-def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, form="stream"):
+def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, form="stream", slice_cols=None):
     """The reference's train (examples/mil_util.jl:93-152) over many (Y0, Y1) pairs -- the folds, p and repetitions of a validation
     run -- with all the fits in ONE device call.  solver="basic": 2 x len(folds) fits through vbmf_batch_ with est_covs = est_var =
     True (:110-114), vbmf_init drawn in the order (fold, class) from the one generator.  solver="sparse": ten vbmf_sparse_init per class
     per fold, drawn in the order (fold, class, restart), one vbmf_sparse_batch_ call with full_cov=False, and per class the set the
     restart loop of :124-145 keeps (fit_restarts): the first with d <= 2 eps and not NaN, else the last.  Returns a list of
-    (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns (:97-100).  form: vbmf_batch_'s, for solver="basic" (the sparse
-    solver has no Gram form and ignores it)."""
+    (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns (:97-100).  form: vbmf_batch_'s for solver="basic"; for
+    solver="sparse" vbmf_sparse_batch_'s "stream", "split" or "auto" with its slice_cols (that solver has no Gram form: "gram" is
+    refused)."""
     if solver not in ("basic", "sparse"):
         raise ValueError(f"train_folds: solver = {solver!r} ('basic' or 'sparse')")
-    capi.fit_form_code(form)
+    if solver == "sparse":
+        capi.ard_fit_form_code(form)
+    else:
+        capi.fit_form_code(form)
     if diag_var:
         raise ValueError("train_folds: diag_var=True is not batched; train such folds one at a time with vbmf_sparse_ / vbmf_ "
                          "(or the sparse solver's fits at once with vbmf_sparse_batch_(..., diag_var=True))")
@@ -1756,7 +1789,7 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
         vbmf_batch_(Ys, ps, niter, eps=eps, est_covs=True, est_var=True, bag_of=bag_of, **kw)
         kept = ps
     else:
-        ds = vbmf_sparse_batch_(Ys, ps, niter, eps=eps, full_cov=False, bag_of=bag_of)
+        ds = vbmf_sparse_batch_(Ys, ps, niter, eps=eps, full_cov=False, bag_of=bag_of, **_split(form, slice_cols))
         kept = []
         for b in range(len(Ys)):
             sets = list(zip(ps[b * nstarts:(b + 1) * nstarts], ds[b * nstarts:(b + 1) * nstarts]))
@@ -1769,13 +1802,15 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
     return out
 
 
-def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, rng=None):
+def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, rng=None, form="stream", slice_cols=None):
     """The reference's train_dual (examples/mil_util.jl:327-385) over many (Y0, Y1) pairs with all the fits in ONE device call: nstarts
     vbmf_dual_init per class per fold, drawn in the order (fold, class, restart) from the one generator, one vbmf_dual_batch_ call with
     full_cov=True (:351, :376) in which the restarts of a class share its upload, and per class the set the restart loops of :347-354
     and :372-379 keep (fit_restarts(model="dual")): the first with norm(AHat) + norm(BHat) >= 1e-2 (operator 2-norms), else the last.
     diag_var goes to every vbmf_dual! as it does there.  The column subsample of :342-344 is the caller's: pass the columns to train
-    on.  Returns a list of (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns, as train_folds does."""
+    on.  form, slice_cols: vbmf_dual_batch_'s.  Returns a list of (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns, as
+    train_folds does."""
+    capi.ard_fit_form_code(form)
     if int(nstarts) < 1:
         raise ValueError("train_dual_folds: nstarts must be >= 1")
     rng = np.random.default_rng() if rng is None else rng
@@ -1793,7 +1828,7 @@ def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, 
     out = [(0, 0)] * len(folds)
     if not ps:
         return out
-    vbmf_dual_batch_(Ys, ps, niter, eps=eps, full_cov=True, bag_of=bag_of, **_rows(diag_var))
+    vbmf_dual_batch_(Ys, ps, niter, eps=eps, full_cov=True, bag_of=bag_of, **_rows(diag_var), **_split(form, slice_cols))
     res = {}
     for b, kc in enumerate(where):
         sets = ps[b * nstarts:(b + 1) * nstarts]

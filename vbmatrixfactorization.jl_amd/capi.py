@@ -35,6 +35,10 @@ VBMF_FIT_LDS_CAP_BYTES = 144 * 1024
 VBMF_GRAM_FORM_DEFAULT, VBMF_GRAM_FORM_OFF, VBMF_GRAM_FORM_ON = 0, 1, 2
 GRAM_FORMS = {"stream": VBMF_GRAM_FORM_OFF, "gram": VBMF_GRAM_FORM_ON}
 FIT_FORMS = {"stream": VBMF_FIT_FORM_STREAM, "gram": VBMF_FIT_FORM_GRAM, "auto": VBMF_FIT_FORM_AUTO}
+# vbmf_ard_fit_batched_form (include/vbmf_hip.h): one wide ARD-family fit over many workgroups.  The four constants are measured there
+VBMF_FIT_FORM_SPLIT = 3
+VBMF_FIT_SPLIT_COLS, VBMF_FIT_SPLIT_MIN_COLS, VBMF_FIT_SPLIT_MIN_COLS_FULL, VBMF_FIT_SPLIT_CHUNK = 128, 160, 160, 8
+ARD_FIT_FORMS = {"stream": VBMF_FIT_FORM_STREAM, "auto": VBMF_FIT_FORM_AUTO, "split": VBMF_FIT_FORM_SPLIT}
 
 
 def fit_form_code(form):
@@ -42,6 +46,35 @@ def fit_form_code(form):
     if not isinstance(form, str) or form not in FIT_FORMS:
         raise ValueError(f"form = {form!r} ('stream', 'gram' or 'auto')")
     return FIT_FORMS[form]
+
+
+def ard_fit_form_code(form):
+    """'stream' / 'split' / 'auto' -> the C ABI's form for the ARD families; 'gram' is the basic model's alone"""
+    if form == "gram":
+        raise ValueError("form = 'gram': the ARD-sparse, two-group and three-group models have no Gram form (the element-wise precision "
+                         "on A breaks A = Y'V); it serves the basic model's wide bags through vbmf_batch_")
+    if not isinstance(form, str) or form not in ARD_FIT_FORMS:
+        raise ValueError(f"form = {form!r} ('stream', 'split' or 'auto')")
+    return ARD_FIT_FORMS[form]
+
+
+def ard_slice_cols(slice_cols):
+    """None / 0 -> 0 (VBMF_FIT_SPLIT_COLS); otherwise a multiple of 8, at least 8"""
+    sc = 0 if slice_cols is None else int(slice_cols)
+    if sc != 0 and (sc < 8 or sc % 8):
+        raise ValueError(f"slice_cols = {slice_cols!r} (None, or a multiple of 8)")
+    return sc
+
+
+def ard_fit_slices(Mb, slice_cols=None):
+    """the workgroups of the column pass a fit of Mb columns takes under form='split'"""
+    sc = ard_slice_cols(slice_cols) or VBMF_FIT_SPLIT_COLS
+    return -(-int(Mb) // sc)
+
+
+def ard_fit_form_auto(Mb, full_cov=False):
+    """the form a fit of Mb columns takes under form='auto': 3 (split) or 0 (stream)"""
+    return VBMF_FIT_FORM_SPLIT if Mb >= (VBMF_FIT_SPLIT_MIN_COLS_FULL if full_cov else VBMF_FIT_SPLIT_MIN_COLS) else VBMF_FIT_FORM_STREAM
 
 
 def fit_gram_fits(L, H):
@@ -64,6 +97,7 @@ SYMBOLS = [
     "vbmf_pass_bytes", "vbmf_device_sync", "vbmf_debug_peek", "vbmf_debug_time_pass", "vbmf_debug_lambda_max",
     "vbmf_sparse_set_state", "vbmf_sparse_get_state", "vbmf_sparse_step", "vbmf_sparse_run", "vbmf_sparse_run_fixed_basis",
     "vbmf_sparse_run_fixed_basis_batched", "vbmf_sparse_fit_batched", "vbmf_local_fit_batched", "vbmf_rows_fit_batched",
+    "vbmf_ard_fit_batched_form",
     "vbmf_sparse_lower_bound", "vbmf_sparse_set_noise_rows", "vbmf_sparse_get_noise_rows", "vbmf_preprocess_open", "vbmf_preprocess_rows", "vbmf_set_Y_preprocessed",
     "vbmf_preprocess_close", "vbmf_dual_set_priors", "vbmf_dual_get_priors", "vbmf_dual_run",
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
@@ -153,6 +187,7 @@ def lib():
     L.vbmf_local_fit_batched.argtypes = ([vp, i64, C.POINTER(i64), i64, C.POINTER(i64), i64, C.c_double, i32, i32, i32, i64,
                                           C.POINTER(i64), i64] + [dp] * 16 + [C.POINTER(i64), dp, C.POINTER(i64), dp])
     L.vbmf_rows_fit_batched.argtypes = L.vbmf_local_fit_batched.argtypes
+    L.vbmf_ard_fit_batched_form.argtypes = L.vbmf_local_fit_batched.argtypes + [C.c_int, i64, i64, C.POINTER(i64)]
     L.vbmf_get_YHat.argtypes = [vp, dp, i64]
     L.vbmf_get_YHat_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
     L.vbmf_get_factor_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
@@ -618,12 +653,23 @@ class Context:
         return self._ard_fit_batched(col_off, fit_bag, niter, eps, gamma, delta0, etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVecHat, CA,
                                      H0, full_cov, est_cb, est_priors, want_trace, M0=M0, mask_H1=mask_H1, rows=True)
 
+    def ard_fit_batched_form(self, col_off, fit_bag, niter, eps, gamma, delta0, etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVecHat, CA,
+                             M0=None, H0=None, mask_H1=0, full_cov=False, est_cb=True, est_priors=False, want_trace=False,
+                             diag_var=False, form="split", slice_cols=None):
+        """local_fit_batched (diag_var False: etaVec and sigmaVecHat are its per-fit scalars eta and sigmaHat; M0 None: M0[f] = M_b) or
+        rows_fit_batched (diag_var True) with the form chosen by the caller (vbmf_ard_fit_batched_form): "stream" = one workgroup per
+        fit, bit-identical to those calls; "split" = every fit over ceil(M_b / slice_cols) workgroups, two launches per sweep; "auto" =
+        ard_fit_form_auto per fit.  slice_cols None: VBMF_FIT_SPLIT_COLS.  Returns their dict with form_used (nfits,): 0 / 3."""
+        return self._ard_fit_batched(col_off, fit_bag, niter, eps, gamma, delta0, etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVecHat, CA,
+                                     H0, full_cov, est_cb, est_priors, want_trace, M0=M0, mask_H1=mask_H1, rows=bool(diag_var),
+                                     form=(ard_fit_form_code(form), ard_slice_cols(slice_cols)))
+
     def _ard_fit_batched(self, col_off, fit_bag, niter, eps, gamma, delta0, eta, zeta0, priors, BHat, SigmaB, CB, sigmaHat, CA, H0, full_cov,
-                         est_cb, est_priors, want_trace, M0=None, mask_H1=0, rows=False):
+                         est_cb, est_priors, want_trace, M0=None, mask_H1=0, rows=False, form=None):
         """sparse_fit_batched (M0 is None: vbmf_sparse_fit_batched, four prior values per fit), local_fit_batched
         (vbmf_local_fit_batched: M0 and mask_H1 behind H0, nine prior values per fit, six accepted and padded) and rows_fit_batched
         (vbmf_rows_fit_batched: local_fit_batched's arguments with sigmaHat and zeta (nfits, L); M0 None goes down as NULL)."""
-        local = M0 is not None or rows
+        local = M0 is not None or rows or form is not None
         H = self.H
         off, fb, nb, nf, B, per_fit, tail = self._fit_prologue(col_off, fit_bag, niter, BHat, want_trace)
         vec = lambda v: np.array(v, dtype=np.float64, copy=True).reshape(-1)
@@ -652,8 +698,11 @@ class Context:
         delta = np.empty((nf, H)) if est_cb else None
         zeta, beta, dS, A = np.empty((nf, self.L) if rows else nf), np.empty(MH), np.empty(MH), np.empty(MH)
         SA = np.empty((nf, H, H))
-        entry = (self._lib.vbmf_rows_fit_batched if rows else self._lib.vbmf_local_fit_batched if local
-                 else self._lib.vbmf_sparse_fit_batched)
+        entry = (self._lib.vbmf_ard_fit_batched_form if form is not None else self._lib.vbmf_rows_fit_batched if rows
+                 else self._lib.vbmf_local_fit_batched if local else self._lib.vbmf_sparse_fit_batched)
+        used = np.zeros(nf, dtype=np.int64)
+        if form is not None:
+            tail = tail + (int(rows), int(form[0]), int(form[1]), _i64ptr(used))
         self._chk(entry(
             self._h, nb, _i64ptr(off), nf, _i64ptr(fb), int(niter), float(eps), int(bool(full_cov)), int(bool(est_cb)), int(bool(est_priors)),
             int(H if H0 is None else H0), *((_i64ptr(m0), int(mask_H1)) if local else ()), _dptr(ga), _dptr(d0), _dptr(et), _dptr(z0),
@@ -661,7 +710,8 @@ class Context:
             _dptr(A), *tail))
         noise = dict(sigmaVecHat=sg, zetaVec=zeta) if rows else dict(sigmaHat=sg, zeta=zeta)
         return dict(BHat=B.transpose(0, 2, 1), SigmaB=SB, CB=cb, delta=delta, **noise, CA=ca, beta=beta, diagSigmaATVec=dS,
-                    ATVecHat=A, SigmaA=SA, **{"priors9" if local else "priors4": pri}, **per_fit)
+                    ATVecHat=A, SigmaA=SA, **{"priors9" if local else "priors4": pri}, **per_fit,
+                    **(dict(form_used=used) if form is not None else {}))
 
     def YHat(self):
         out = np.empty((self.L, self.M), order="F")

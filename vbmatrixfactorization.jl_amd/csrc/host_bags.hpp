@@ -433,8 +433,9 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
                            int64_t mask_H1, const double* gamma, const double* delta0, const double* eta, const double* zeta0,
                            double* priors, double* BHat, double* SigmaB, double* CB, double* sigmaHat, double* CA, double* delta,
                            double* zeta, double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat, int64_t* iters_done,
-                           double* d_last, int64_t* status, double* trace, bool rows = false) {
+                           double* d_last, int64_t* status, double* trace, bool rows = false, int64_t slice_cols = 0) {
     const bool local = M0 != nullptr || rows;
+    const bool split = slice_cols > 0;                              // (the split schedule is the three-group sweep: its callers pass M0)
     const int64_t npri = local ? 9 : 4;
     const bool compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
     const int H = (int)c->H, NBK = nb_tier(H);
@@ -443,6 +444,7 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     long long* fit_off = idx.data() + nb + 1 + nf;
     fit_off[0] = 0;
     size_t lds_doubles = 0;
+    std::vector<long long> sl_fit, sl_c0, fit_sl0;                  // split: the slices (fit_split_kernels.hpp)
     for (int64_t f = 0; f < nf; ++f) {
         const int64_t b = fit_bag[f];
         if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: fit_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)f, (long long)b);
@@ -455,11 +457,22 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
         lds_doubles = std::max(lds_doubles, (size_t)fitb_lds_doubles(full_cov != 0, NBK, L, Mb, H, rows));
         idx[(size_t)(nb + 1 + f)] = b;
         if (local) idx[(size_t)(nb + 1 + nf + nf + 1 + f)] = M0 ? M0[f] : Mb;
+        if (split) {
+            fit_sl0.push_back((long long)sl_fit.size());
+            for (int64_t c0 = 0; c0 < Mb; c0 += slice_cols) {
+                sl_fit.push_back(f);
+                sl_c0.push_back(c0);
+            }
+        }
     }
+    fit_sl0.push_back((long long)sl_fit.size());
+    const int64_t nsl = (int64_t)sl_fit.size();
+    if (nsl > (1ll << 31) - 1) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld slices (more than 2^31 - 1 workgroups)", fn, (long long)nsl);
     for (int64_t b = 0; b <= nb; ++b) idx[(size_t)b] = col_off[b];
     if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);           // (no state needed)
     // the staging vectors outlive every copy: an error between the first asynchronous copy and the synchronise drains the stream below
     std::vector<double> in, out, sg;
+    std::vector<long long> done;                                    // split: the fits' done words, read between chunks of sweeps
     auto run = [&]() -> int {
     HIPCHK(c, hipSetDevice(c->o.device));
     const int64_t SMH = fit_off[nf] * H, nidx = (int64_t)idx.size(), ntr = trace ? 2 * nf * niter : 0, ny = (L * c->M + 1) / 2;
@@ -470,7 +483,10 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     const int64_t o_sc = nidx, o_pri = o_sc + 5 * nf, o_zeta = o_pri + npri * nf, o_dl = o_zeta + nf, o_it = o_dl + nf, o_st = o_it + nf,
                   o_b = o_st + nf, o_bw = o_b + nf * LH, o_qw = o_bw + nf * LH, o_sb = o_qw + nf * LH, o_sa = o_sb + nf * h2,
                   o_cb = o_sa + nf * h2, o_de = o_cb + nf * H, o_ca = o_de + nf * H, o_a = o_ca + SMH, o_ds = o_a + SMH, o_be = o_ds + SMH,
-                  o_sv = o_be + SMH, o_zv = o_sv + nrow, o_yn = o_zv + nrow, o_tr = o_yn + nrow, o_yr = o_tr + ntr, o_yc = o_yr + ny, total = o_yc + ny;
+                  o_sv = o_be + SMH, o_zv = o_sv + nrow, o_yn = o_zv + nrow, o_tr = o_yn + nrow, o_yr = o_tr + ntr, o_yc = o_yr + ny;
+    // split: [sl_fit | sl_c0 (nsl) | fit_sl0 (nf + 1) | done (nf) (int64) | the fits' published blocks | the slices' slots] behind Yc
+    const int64_t o_sl = o_yc + ny, o_done = o_sl + (split ? 2 * nsl + nf + 1 : 0), o_pub = o_done + (split ? nf : 0),
+                  o_slot = o_pub + (split ? nf * fits_pub_doubles(H) : 0), total = o_slot + (split ? nsl * fits_slot_doubles(L, H) : 0);
     double* d = nullptr;
     TRY(bags_reserve(c, total, &d));
     in.resize((size_t)((5 + npri) * nf));
@@ -502,6 +518,47 @@ static int fit_batched_run(vbmf_ctx* c, const char* fn, int64_t nbags, const int
     // (the fit kernels exist for NB = 1 and 2: every rank above 16 runs the NB = 2 instance)
     const FitLocalArgs la{a, di + nb + 1 + nf + nf + 1, (int)mask_H1};
     const FitRowsArgs ra{la, d + o_yn};
+    if (split) {
+        // a sweep = the column pass over every slice + the fold per fit; the host reads the done words between chunks of sweeps
+        sl_fit.insert(sl_fit.end(), sl_c0.begin(), sl_c0.end());
+        sl_fit.insert(sl_fit.end(), fit_sl0.begin(), fit_sl0.end());
+        HIPCHK(c, hipMemcpyAsync(d + o_sl, sl_fit.data(), sl_fit.size() * 8, hipMemcpyHostToDevice, c->stream));
+        const int NB2 = std::min(NBK, 2);
+        long long* dsl = reinterpret_cast<long long*>(d + o_sl);
+        const bool x_lds = fits_cols_x_lds(full_cov != 0, NB2, L, H, slice_cols), b_lds = fits_fold_b_lds(NB2, L, H);
+        const FitSplitArgs sa{ra, dsl, dsl + nsl, dsl + 2 * nsl, (int)slice_cols, full_cov ? 1 : 0, x_lds ? 1 : 0, b_lds ? 1 : 0,
+                              d + o_pub, d + o_slot, reinterpret_cast<long long*>(d + o_done)};
+        const size_t lds_i = (size_t)6 * h2 * 8,
+                     lds_c = (size_t)(fits_cols_min_doubles(full_cov != 0, NB2, H, slice_cols) + (x_lds ? LH : 0)) * 8,
+                     lds_f = (size_t)(fits_fold_fixed_doubles(NB2, H) + (b_lds ? 2 * LH : 0)) * 8;
+        if (rows) hipLaunchKernelGGL((fit_split_init_kernel<true>), dim3((unsigned)nf), dim3(FITB_THREADS), lds_i, c->stream, sa);
+        else hipLaunchKernelGGL((fit_split_init_kernel<false>), dim3((unsigned)nf), dim3(FITB_THREADS), lds_i, c->stream, sa);
+        HIPCHK(c, hipGetLastError());
+        done.resize((size_t)nf);
+        int64_t chunk_len = VBMF_FIT_SPLIT_CHUNK;
+        if (const char* e = getenv("VBMF_FIT_SPLIT_CHUNK")) {       // tuning switch (include/vbmf_hip.h)
+            if (atoll(e) >= 1 && atoll(e) <= (1 << 16)) chunk_len = atoll(e);
+        }
+        for (int64_t enq = 0; enq < niter;) {
+            const int64_t chunk = std::min<int64_t>(chunk_len, niter - enq);
+            for (int64_t k = 0; k < chunk; ++k)
+                dispatch<1, 2>(NB2, [&](auto nbk) {
+                    dispatch<0, 1>(rows ? 1 : 0, [&](auto rw) {
+                        constexpr int NBc = decltype(nbk)::value;
+                        constexpr bool ROWSc = decltype(rw)::value != 0;
+                        if (full_cov) hipLaunchKernelGGL((fit_cols_kernel<NBc, true, ROWSc>), dim3((unsigned)nsl), dim3(FITB_THREADS), lds_c, c->stream, sa);
+                        else hipLaunchKernelGGL((fit_cols_kernel<NBc, false, ROWSc>), dim3((unsigned)nsl), dim3(FITB_THREADS), lds_c, c->stream, sa);
+                        hipLaunchKernelGGL((fit_fold_kernel<NBc, ROWSc>), dim3((unsigned)nf), dim3(FITB_THREADS), lds_f, c->stream, sa);
+                    });
+                });
+            HIPCHK(c, hipGetLastError());
+            enq += chunk;
+            if (enq >= niter) break;
+            HIPCHK(c, hipMemcpyAsync(done.data(), d + o_done, (size_t)nf * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (std::all_of(done.begin(), done.end(), [](long long x) { return x != 0; })) break;
+        }
+    } else
     dispatch<1, 2>(std::min(NBK, 2), [&](auto nbk) {
         dispatch<0, 1>(full_cov ? 1 : 0, [&](auto full) {
             constexpr int NBc = decltype(nbk)::value;
@@ -641,6 +698,132 @@ int vbmf_rows_fit_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, in
     return fit_batched_run(c, fn, nbags, col_off, nfits, fit_bag, niter, eps, full_cov, est_cb, est_priors, H0, M0, mask_H1, gamma, delta0,
                            etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVec, CA, delta, zetaVec, beta, diagSigmaATVec, SigmaA, ATVecHat,
                            iters_done, d_last, status, trace, true);
+}
+
+// vbmf_ard_fit_batched_form: the same fits with the form chosen per call or per fit.  form = 0 is the entry above (rows) or
+// vbmf_local_fit_batched (M0 = NULL: M0[f] = M_b) unchanged; form = 3 runs every fit in the split schedule of fit_split_kernels.hpp;
+// form = 2 picks per fit by (M_b, full_cov) alone and runs the two groups one after the other, each on its own compact copy of the
+// per-fit arguments (a call whose fits all take one form runs on the caller's arrays).
+int vbmf_ard_fit_batched_form(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nfits, const int64_t* fit_bag, int64_t niter,
+                              double eps, int full_cov, int est_cb, int est_priors, int64_t H0, const int64_t* M0, int64_t mask_H1,
+                              const double* gamma, const double* delta0, const double* etaVec, const double* zeta0, double* priors9,
+                              double* BHat, double* SigmaB, double* CB, double* sigmaVec, double* CA, double* delta, double* zetaVec,
+                              double* beta, double* diagSigmaATVec, double* SigmaA, double* ATVecHat, int64_t* iters_done, double* d_last,
+                              int64_t* status, double* trace, int diag_var, int64_t form, int64_t slice_cols, int64_t* form_used) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_ard_fit_batched_form";
+    const bool rows = diag_var != 0;
+    TRY(local_fit_checks(c, fn, rows, nbags, col_off, nfits, niter, est_priors, H0, mask_H1,
+                         !fit_bag || !gamma || !delta0 || !etaVec || !zeta0 || !priors9 || !BHat || !SigmaB || !CB || !sigmaVec || !CA ||
+                             !iters_done || !d_last || !status));
+    if (form == VBMF_FIT_FORM_GRAM)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: form = 1: the ARD families have no Gram form (the element-wise precision on A breaks A = Y'V)", fn);
+    if (form != VBMF_FIT_FORM_STREAM && form != VBMF_FIT_FORM_AUTO && form != VBMF_FIT_FORM_SPLIT)
+        FAIL(c, VBMF_ERR_INVALID, "%s: form = %lld (0 = stream, 2 = auto, 3 = split)", fn, (long long)form);
+    if (slice_cols != 0 && (slice_cols < 8 || slice_cols % 8 != 0 || slice_cols > (1ll << 30)))
+        FAIL(c, VBMF_ERR_INVALID, "%s: slice_cols = %lld (0, or a multiple of 8)", fn, (long long)slice_cols);
+    const int H = (int)c->H, NB2 = std::min(nb_tier(H), 2);
+    int64_t sc = slice_cols ? slice_cols : VBMF_FIT_SPLIT_COLS;
+    const bool sc_fits = fits_cols_min_doubles(full_cov != 0, NB2, H, sc) <= (long long)(FITB_LDS_CAP / 8);
+    if (!sc_fits && slice_cols == 0) {                              // the default width, narrowed to what a slice's state leaves of LDS
+        sc = ((long long)(FITB_LDS_CAP / 8) - fits_cols_min_doubles(full_cov != 0, NB2, H, 0)) / (3 * H) / 8 * 8;
+    } else if (!sc_fits && form != VBMF_FIT_FORM_STREAM) {
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: slice_cols = %lld at H = %d: a slice's state (3 slice_cols H doubles) does not fit in LDS", fn,
+             (long long)slice_cols, H);
+    }
+    const int64_t nf = nfits, nb = nbags;
+    std::vector<int64_t> M0v, Mbs((size_t)nf), used((size_t)nf);
+    int64_t nsplit = 0;
+    for (int64_t f = 0; f < nf; ++f) {
+        const int64_t b = fit_bag[f];
+        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: fit_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)f, (long long)b);
+        const int64_t Mb = Mbs[(size_t)f] = col_off[b + 1] - col_off[b];
+        // fit_batched_run's per-fit refusals, made here on the caller's own indices before either group of a mixed call runs
+        if (!full_cov && (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) && Mb < 2)
+            FAIL(c, VBMF_ERR_INVALID, "%s: fit %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)f);
+        if (M0 && (M0[f] < 0 || M0[f] > Mb))
+            FAIL(c, VBMF_ERR_INVALID, "%s: M0[%lld] = %lld outside 0..M_b = %lld", fn, (long long)f, (long long)M0[f], (long long)Mb);
+        used[(size_t)f] = form == VBMF_FIT_FORM_SPLIT ||
+                                  (form == VBMF_FIT_FORM_AUTO && Mbs[(size_t)f] >= (full_cov ? VBMF_FIT_SPLIT_MIN_COLS_FULL : VBMF_FIT_SPLIT_MIN_COLS))
+                              ? VBMF_FIT_FORM_SPLIT : VBMF_FIT_FORM_STREAM;
+        nsplit += used[(size_t)f] != 0;
+    }
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);
+    if (!M0 && !rows) {                                             // the homoscedastic sweeps take M0 per fit: M0[f] = M_b
+        M0v = Mbs;
+        M0 = M0v.data();
+    }
+    auto run = [&](bool split, int64_t nfr, const int64_t* fb, const int64_t* m0, const double* ga, const double* de0, const double* et,
+                   const double* ze0, double* pri, double* B, double* SB, double* cb, double* sg, double* ca, double* de, double* ze,
+                   double* be, double* ds, double* SA, double* A, int64_t* itd, double* dl, int64_t* stt, double* tr) {
+        return fit_batched_run(c, fn, nbags, col_off, nfr, fb, niter, eps, full_cov, est_cb, est_priors, H0, m0, mask_H1, ga, de0, et, ze0,
+                               pri, B, SB, cb, sg, ca, de, ze, be, ds, SA, A, itd, dl, stt, tr, rows, split ? sc : 0);
+    };
+    if (nsplit == 0 || nsplit == nf) {
+        TRY(run(nsplit != 0, nf, fit_bag, M0, gamma, delta0, etaVec, zeta0, priors9, BHat, SigmaB, CB, sigmaVec, CA, delta, zetaVec, beta,
+                diagSigmaATVec, SigmaA, ATVecHat, iters_done, d_last, status, trace));
+        if (form_used) memcpy(form_used, used.data(), (size_t)nf * 8);
+        return VBMF_OK;
+    }
+    // a mixed call: each group on compact copies; the results are scattered into the caller's arrays only once BOTH groups have run, so
+    // a failure in the second (device memory, a HIP error) leaves them as they were.  A field is (pointer, doubles per fit or 0 = M_b H)
+    const int64_t L = c->L, LH = L * H, h2 = (int64_t)H * H, nsg = rows ? L : 1;
+    std::vector<int64_t> off((size_t)nf + 1, 0);
+    for (int64_t f = 0; f < nf; ++f) off[(size_t)f + 1] = off[(size_t)f] + Mbs[(size_t)f] * H;
+    struct Field { double* p; int64_t per; bool in; };
+    const Field fields[] = {{const_cast<double*>(gamma), 1, true}, {const_cast<double*>(delta0), 1, true}, {const_cast<double*>(etaVec), 1, true},
+                            {const_cast<double*>(zeta0), 1, true}, {priors9, 9, true}, {BHat, LH, true}, {SigmaB, h2, true}, {CB, H, true},
+                            {sigmaVec, nsg, true}, {CA, 0, true}, {delta, H, false}, {zetaVec, nsg, false}, {beta, 0, false},
+                            {diagSigmaATVec, 0, false}, {SigmaA, h2, false}, {ATVecHat, 0, false}, {d_last, 1, false}, {trace, 2 * niter, false}};
+    constexpr int NFLD = sizeof(fields) / sizeof(fields[0]);
+    std::vector<int64_t> sels[2], itds[2], stts[2];
+    std::vector<double> bufs[2][NFLD];
+    for (int grp = 0; grp < 2; ++grp) {
+        const int64_t want = grp ? VBMF_FIT_FORM_SPLIT : VBMF_FIT_FORM_STREAM;
+        std::vector<int64_t>&sel = sels[grp], &itd = itds[grp], &stt = stts[grp];
+        std::vector<int64_t> fb, m0;
+        for (int64_t f = 0; f < nf; ++f)
+            if (used[(size_t)f] == want) {
+                sel.push_back(f);
+                fb.push_back(fit_bag[f]);
+                if (M0) m0.push_back(M0[f]);
+            }
+        const int64_t ng = (int64_t)sel.size();
+        itd.resize((size_t)ng);
+        stt.resize((size_t)ng);
+        std::vector<double>* buf = bufs[grp];
+        for (int k = 0; k < NFLD; ++k) {
+            if (!fields[k].p) continue;
+            for (int64_t f : sel) {
+                const int64_t per = fields[k].per ? fields[k].per : Mbs[(size_t)f] * H, o = fields[k].per ? f * per : off[(size_t)f];
+                if (fields[k].in) buf[k].insert(buf[k].end(), fields[k].p + o, fields[k].p + o + per);
+                else buf[k].insert(buf[k].end(), (size_t)per, 0.0);
+            }
+        }
+        auto P = [&](int k) { return fields[k].p ? buf[k].data() : nullptr; };
+        TRY(run(grp != 0, ng, fb.data(), M0 ? m0.data() : nullptr, P(0), P(1), P(2), P(3), P(4), P(5), P(6), P(7), P(8), P(9), P(10), P(11),
+                P(12), P(13), P(14), P(15), itd.data(), P(16), stt.data(), P(17)));
+    }
+    for (int grp = 0; grp < 2; ++grp) {
+        const std::vector<int64_t>&sel = sels[grp], &itd = itds[grp], &stt = stts[grp];
+        const std::vector<double>* buf = bufs[grp];
+        const int64_t ng = (int64_t)sel.size();
+        for (int k = 4; k < NFLD; ++k) {
+            if (!fields[k].p) continue;
+            int64_t at = 0;
+            for (int64_t f : sel) {
+                const int64_t per = fields[k].per ? fields[k].per : Mbs[(size_t)f] * H, o = fields[k].per ? f * per : off[(size_t)f];
+                memcpy(fields[k].p + o, buf[k].data() + at, (size_t)per * 8);
+                at += per;
+            }
+        }
+        for (int64_t i = 0; i < ng; ++i) {
+            iters_done[sel[(size_t)i]] = itd[(size_t)i];
+            status[sel[(size_t)i]] = stt[(size_t)i];
+        }
+    }
+    if (form_used) memcpy(form_used, used.data(), (size_t)nf * 8);
+    return VBMF_OK;
 }
 
 }  // extern "C"

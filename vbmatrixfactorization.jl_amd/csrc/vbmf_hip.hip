@@ -55,6 +55,7 @@
 #include "batch_kernels.hpp"
 #include "sparse_batch_kernels.hpp"
 #include "fit_batch_kernels.hpp"
+#include "fit_split_kernels.hpp"
 #include "fit_basic_kernels.hpp"
 #include "fit_basic_gram_kernels.hpp"
 #include "score_kernels.hpp"
@@ -1747,6 +1748,13 @@ int vbmf_create(vbmf_ctx** out, int64_t L, int64_t M, int64_t H, const vbmf_opts
             // ... and the row-noise sweeps built on those (vbmf_rows_fit_batched)
             {(const void*)fit_batch_kernel<1, false, true, true>, fb, 0}, {(const void*)fit_batch_kernel<1, true, true, true>, fb, 0},
             {(const void*)fit_batch_kernel<2, false, true, true>, fb, 0}, {(const void*)fit_batch_kernel<2, true, true, true>, fb, 0},
+            // ... and one fit over many workgroups: the column pass and the fold (vbmf_ard_fit_batched_form, fit_split_kernels.hpp)
+            {(const void*)fit_cols_kernel<1, false, false>, fb, 0}, {(const void*)fit_cols_kernel<1, true, false>, fb, 0},
+            {(const void*)fit_cols_kernel<2, false, false>, fb, 0}, {(const void*)fit_cols_kernel<2, true, false>, fb, 0},
+            {(const void*)fit_cols_kernel<1, false, true>, fb, 0}, {(const void*)fit_cols_kernel<1, true, true>, fb, 0},
+            {(const void*)fit_cols_kernel<2, false, true>, fb, 0}, {(const void*)fit_cols_kernel<2, true, true>, fb, 0},
+            {(const void*)fit_fold_kernel<1, false>, fb, 0}, {(const void*)fit_fold_kernel<2, false>, fb, 0},
+            {(const void*)fit_fold_kernel<1, true>, fb, 0}, {(const void*)fit_fold_kernel<2, true>, fb, 0},
             {(const void*)fit_basic_kernel<1>, fb, 0}, {(const void*)fit_basic_kernel<2>, fb, 0},
             {(const void*)fit_basic_gram_kernel<1>, fb, 0}, {(const void*)fit_basic_gram_kernel<2>, fb, 0},
             {(const void*)stream_lds8_kernel<4, StreamCfg<4>::Rc, false>, LDS8_BYTES, 4},

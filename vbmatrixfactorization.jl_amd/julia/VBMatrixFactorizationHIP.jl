@@ -59,6 +59,7 @@ end
 const VBMF_Y_F32, VBMF_Y_BF16 = Int32(0), Int32(1)
 const STEP_A, STEP_B, STEP_CA, STEP_CB, STEP_SIGMA2 = 1, 2, 4, 8, 16
 const FIT_FORMS = Dict(:stream => 0, :gram => 1, :auto => 2)     # vbmf_fit_batched_form (include/vbmf_hip.h)
+const ARD_FIT_FORMS = Dict(:stream => 0, :auto => 2, :split => 3)  # vbmf_ard_fit_batched_form: these models have no Gram form
 
 # what the basic model takes as Y: the reference's Array{Float64,2}, or an Array{Float32,2} that is uploaded as it is (the
 # reference has Float32 methods on this path: scaleY, preprocess, src/util.jl:60,94)
@@ -823,9 +824,17 @@ end
 # With rows (diag_var = true, examples/mil_util.jl:667: one noise precision per row of Y) the call is vbmf_rows_fit_batched: pri is
 # 9 x nfits, M0 = nothing goes down as NULL (M0[f] = M_b: the two-group model), the fits start from sigmaVecHat and etaVec[1] and fill
 # sigmaVecHat and zetaVec; sigmaHat and zeta stay as they were.
+# With form = :split / :auto (or a slice_cols) the call is vbmf_ard_fit_batched_form in either noise model: pri is 9 x nfits, M0 = nothing
+# goes down as NULL; :split spreads every fit over ceil(M_b / slice_cols) workgroups (slice_cols = 0: VBMF_FIT_SPLIT_COLS, else a
+# multiple of 8), :auto picks per fit by its width.  :gram is the basic model's alone (vbmf_batch!).
 function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int, eps::Float64, full_cov::Bool, est_cb::Bool,
                         est_priors::Bool, H0::Int, pri::Matrix{Float64}, bag_of::Vector{Int}, variant::Int;
-                        M0::Union{Nothing,Vector{Int64}} = nothing, mask_H1::Int = 0, rows::Bool = false)
+                        M0::Union{Nothing,Vector{Int64}} = nothing, mask_H1::Int = 0, rows::Bool = false,
+                        form::Symbol = :stream, slice_cols::Int = 0)
+    form == :gram && error("$fn: form = :gram: the ARD families have no Gram form; it serves the basic model's wide bags through vbmf_batch!")
+    haskey(ARD_FIT_FORMS, form) || error("$fn: form = $form (:stream, :split or :auto)")
+    (slice_cols == 0 || (slice_cols >= 8 && slice_cols % 8 == 0)) || error("$fn: slice_cols = $slice_cols (0, or a multiple of 8)")
+    by_form = form != :stream || slice_cols != 0
     nb, nf = length(Ys), length(ps)
     (nb >= 1 && nf >= 1 && length(bag_of) == nf) || error("$fn: one bag_of entry per parameter set")
     niter >= 1 || error("$fn: niter must be >= 1")
@@ -857,7 +866,15 @@ function fit_batch_run!(fn::String, Ys::Vector{Matrix{Float64}}, ps, niter::Int,
     it = zeros(Int64, nf); dlast = Array{Float64}(undef, nf); st = zeros(Int64, nf)
     try
         chk(h[], ccall((:vbmf_set_Y, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h[], Yall, L))
-        if rows
+        if by_form
+        chk(h[], ccall((:vbmf_ard_fit_batched_form, libvbmf), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Int64}, Int64, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64},
+             Ptr{Int64}, Ptr{Float64}, Cint, Int64, Int64, Ptr{Int64}),
+            h[], nb, off, nf, fb, niter, eps, full_cov, est_cb, est_priors, H0, M0 === nothing ? C_NULL : M0, mask_H1, ga, d0, eta, z0,
+            pri, B, SB, cb, sg, ca, dl, ze, be, ds, SA, a, it, dlast, st, C_NULL, rows, ARD_FIT_FORMS[form], slice_cols, C_NULL))
+        elseif rows
         chk(h[], ccall((:vbmf_rows_fit_batched, libvbmf), Cint,
             (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Float64, Cint, Cint, Cint, Int64, Ptr{Int64}, Int64, Ptr{Float64},
              Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
@@ -911,16 +928,20 @@ vbmf_sparse! for many independent fits in ONE device call (the restart loop of e
 `[vbmf_sparse!(Ys[bag_of[f]], ps[f], niter; eps = eps, full_cov = full_cov) for f in 1:length(ps)]` does and returns
 (d, sweeps run, status) per fit; status 1 = the fit met a non-finite precision or a bad pivot and stopped.  No labels, H <= 32.
 diag_var = true: one noise precision per row of Y (examples/mil_util.jl:667), through vbmf_rows_fit_batched.
+form = :split spreads every fit over ceil(M_b / slice_cols) workgroups, two launches per sweep (the form for a few wide fits;
+slice_cols = 0: VBMF_FIT_SPLIT_COLS), :auto picks per fit by its width, :stream (the default) is one workgroup per fit
+(vbmf_ard_fit_batched_form); the same iteration in another summation order.
 """
 function vbmf_sparse_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; eps::Float64 = 1e-6,
                             full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)),
-                            diag_var::Bool = false)
+                            diag_var::Bool = false, form::Symbol = :stream, slice_cols::Int = 0)
     for (f, p) in enumerate(ps)
         (p.H1 == 0 && isempty(p.labels)) || error("vbmf_sparse_batch!: fit $f has labels; use vbmf_sparse! per fit")
     end
-    if diag_var
+    if diag_var || form != :stream || slice_cols != 0               # the nine-slot entries
         pri9 = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0, p.alpha0, p.beta0, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
-        return fit_batch_run!("vbmf_sparse_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri9, bag_of, 1; rows = true)
+        return fit_batch_run!("vbmf_sparse_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri9, bag_of, 1; rows = diag_var,
+                              form = form, slice_cols = slice_cols)
     end
     pri = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0)[k] for k in 1:4, p in ps]
     return fit_batch_run!("vbmf_sparse_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri, bag_of, 1)
@@ -932,12 +953,14 @@ all fits share one H0; est_priors refits (alpha00, beta00, alpha01, beta01) ever
 """
 function vbmf_dual_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_dual_parameters}, niter::Int; eps::Float64 = 1e-6,
                           full_cov::Bool = false, est_cb::Bool = true, est_priors::Bool = true,
-                          bag_of::Vector{Int} = collect(1:length(ps)), diag_var::Bool = false)
+                          bag_of::Vector{Int} = collect(1:length(ps)), diag_var::Bool = false, form::Symbol = :stream,
+                          slice_cols::Int = 0)
     H0 = ps[1].H0
     all(p.H0 == H0 for p in ps) || error("vbmf_dual_batch!: one H0 per call")
-    if diag_var                                                     # the nine-slot entry: group 3 is empty, slots 7, 8 the posterior shapes
+    if diag_var || form != :stream || slice_cols != 0               # the nine-slot entries: group 3 is empty, slots 7, 8 the posterior shapes
         pri9 = Float64[(p.alpha00, p.beta00, p.alpha01, p.beta01, p.alpha01, p.beta01, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
-        out = fit_batch_run!("vbmf_dual_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri9, bag_of, 3; rows = true)
+        out = fit_batch_run!("vbmf_dual_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri9, bag_of, 3; rows = diag_var,
+                             form = form, slice_cols = slice_cols)
         for (f, p) in enumerate(ps)
             p.A0Hat, p.A1Hat = p.AHat[:, 1:p.H0], p.AHat[:, p.H0+1:end]
             p.CA0, p.CA1 = dual_split(p.CA, p.M, p.H, p.H0); p.beta0, p.beta1 = dual_split(p.beta, p.M, p.H, p.H0)
@@ -1288,13 +1311,14 @@ M0 is per fit; est_priors refits the three (alpha0g, beta0g) pairs every sweep (
 """
 function vbmf_trial_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_trial_parameters}, niter::Int; eps::Float64 = 1e-6,
                            full_cov::Bool = false, est_cb::Bool = true, est_priors::Bool = true,
-                           bag_of::Vector{Int} = collect(1:length(ps)), diag_var::Bool = false)
+                           bag_of::Vector{Int} = collect(1:length(ps)), diag_var::Bool = false, form::Symbol = :stream,
+                           slice_cols::Int = 0)
     H0 = ps[1].H0
     all(p.H0 == H0 for p in ps) || error("vbmf_trial_batch!: one H0 per call")
     all(0 <= p.M0 <= p.M for p in ps) || error("vbmf_trial_batch!: M0 outside 0..M")
     pri = Float64[(p.alpha01, p.beta01, p.alpha02, p.beta02, p.alpha03, p.beta03, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
     out = fit_batch_run!("vbmf_trial_batch!", Ys, ps, niter, eps, full_cov, est_cb, est_priors, H0, pri, bag_of, 4;
-                         M0 = Int64[p.M0 for p in ps], rows = diag_var)
+                         M0 = Int64[p.M0 for p in ps], rows = diag_var, form = form, slice_cols = slice_cols)
     for (f, p) in enumerate(ps)
         p.A1Hat, p.A2Hat, p.A3Hat = p.AHat[:, 1:p.H0], p.AHat[1:p.M0, p.H0+1:end], p.AHat[p.M0+1:end, p.H0+1:end]
         p.CA1, p.CA2, p.CA3 = trial_split(p.CA, p.M, p.H, p.H0, p.M0)
@@ -1312,7 +1336,7 @@ the last H1 columns of AHat stay zero in the rows 1:M0 (src/vbmf_sparse.jl:245).
 """
 function vbmf_sparse_masked_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_sparse_parameters}, niter::Int; eps::Float64 = 1e-6,
                                    full_cov::Bool = false, est_cb::Bool = true, bag_of::Vector{Int} = collect(1:length(ps)),
-                                   diag_var::Bool = false)
+                                   diag_var::Bool = false, form::Symbol = :stream, slice_cols::Int = 0)
     H1 = ps[1].H1
     for (f, p) in enumerate(ps)
         (p.H1 == H1 && 0 <= H1 <= p.H) || error("vbmf_sparse_masked_batch!: one H1 in 0..H per call")
@@ -1321,7 +1345,7 @@ function vbmf_sparse_masked_batch!(Ys::Vector{Matrix{Float64}}, ps::Vector{vbmf_
     end
     pri = Float64[(p.alpha0, p.beta0, p.alpha0, p.beta0, p.alpha0, p.beta0, 0.0, 0.0, 0.0)[k] for k in 1:9, p in ps]
     return fit_batch_run!("vbmf_sparse_masked_batch!", Ys, ps, niter, eps, full_cov, est_cb, false, ps[1].H, pri, bag_of, 1;
-                          M0 = Int64[length(p.labels) for p in ps], mask_H1 = H1, rows = diag_var)
+                          M0 = Int64[length(p.labels) for p in ps], mask_H1 = H1, rows = diag_var, form = form, slice_cols = slice_cols)
 end
 
 end # module
