@@ -123,6 +123,20 @@ int vbmf_set_Y(vbmf_ctx* ctx, const double* Y, int64_t ldY);
 #define VBMF_SRC_BF16 2
 int vbmf_set_Y_rows(vbmf_ctx* ctx, const void* src, int32_t src_dtype, int32_t src_on_device,
                     int64_t row0, int64_t nrows, int64_t row_stride, int64_t col_stride);
+/* Y of dst := columns col_index[0..ncols) of the Y stored in src, in that order: the device-side get_matrices
+ * (examples/mil_util.jl:46-58), which the reference's drivers call with the bag ids of every fold (validate_with_cvs :627,
+ * validate_dataset :670) on one resident data set.  src is a context that holds the whole data set; dst is a context of ncols columns.
+ *   dst is left exactly as vbmf_set_Y(dst, Ysrc_as_stored[:, col_index]) leaves it: both tiled copies, pad tiles included, bit for bit
+ *     (the stored values are on the storage grid already, so the one rounding cannot move them); ||Y||^2 of the stored values, summed
+ *     over the same partials in the same order; the per-row norms of the *_DIAGVAR variants; and the same "new Y" event, so G, W, P, Q
+ *     and everything else derived from the old Y are dropped.  A row-block upload in progress on dst is abandoned.
+ *   col_index is host memory; duplicates are allowed and ncols may exceed src's M.  src is only read.
+ *   src's stream is synchronised first; the kernels run on dst's stream and the entry returns after that stream is idle.
+ * VBMF_ERR_INVALID, before any launch, copy or change and with dst -- its current Y included -- untouched: NULL dst, src or col_index;
+ * dst == src; ncols != dst's M; a different local L; a different y_dtype; a different device; src without a complete Y (fresh, or in
+ * the middle of a row-block upload); an index outside 0 .. src's M - 1 (the whole table is checked on the host: no kernel sees a bad
+ * index).  VBMF_ERR_UNSUPPORTED: either context with nranks > 1 or a communicator. */
+int vbmf_set_Y_gather(vbmf_ctx* dst, vbmf_ctx* src, const int64_t* col_index, int64_t ncols);
 /* Device-side generator of the toy model (examples/toy_data.jl:7-18): Y = B* A*' + noise_std*N(0,1),
  * A* one-hot rows over Hstar columns, values rounded to the device dtype; counter-based, so the
  * matrix does not depend on nranks. */

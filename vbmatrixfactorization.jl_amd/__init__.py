@@ -49,7 +49,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "trial_updateB_", "trial_updateCA_", "trial_updateCB_", "trial_updateSigma_", "trial_updateCA_and_priors_",
            "vbls_batch_", "Bags", "vbls_sparse_batch_", "SparseBags", "vbmf_sparse_batch_", "vbmf_dual_batch_", "fit_restarts",
            "vbmf_batch_", "train_folds", "row_gram_batch", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
-           "train_dual_folds",
+           "train_dual_folds", "BagPool",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
 
@@ -1235,6 +1235,22 @@ class _Uploaded:
         self.H, self.M = int(H), Yall.shape[1]
         return Yall
 
+    @classmethod
+    def _gathered(cls, pool_ctx, idx, L, Ms, H, ctx_kw):
+        """An upload whose matrices are columns `idx` of the Y in pool_ctx (BagPool.select): one Context of the class's kind and one
+        set_Y_gather -- no host matrix, no set_Y.  Ms: the widths of the matrices, in order; they sum to len(idx)."""
+        self = cls.__new__(cls)
+        self.L, self.Ms, self.H = int(L), [int(m) for m in Ms], int(H)
+        self.col_off = np.concatenate([[0], np.cumsum(self.Ms)]).astype(np.int64)
+        self.M = int(self.col_off[-1])
+        self._open(ctx_kw)
+        try:
+            self.ctx.set_Y_gather(pool_ctx, idx)
+        except Exception:
+            self.close()
+            raise
+        return self
+
     def __len__(self):
         return len(self.Ms)
 
@@ -1250,6 +1266,9 @@ class Bags(_Uploaded):
         Yall = self._lay_out(Ys, H, _batch_refuse)
         self.session = Session(self.L, self.M, self.H)
         self.session.set_Y(Yall)
+
+    def _open(self, ctx_kw):
+        self.session = Session(self.L, self.M, self.H, **ctx_kw)
 
     @property
     def ctx(self):
@@ -1343,6 +1362,176 @@ class SparseBags(_Uploaded):
         self.ctx_kw = {**_defaults, **ctx_kw}
         self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **self.ctx_kw)
         self.ctx.set_Y(Yall)
+
+    def _open(self, ctx_kw):
+        self.ctx_kw = {**_defaults, **ctx_kw}
+        self.ctx = Context(self.L, self.M, self.H, variant=VBMF_VARIANT_SPARSE_DIAG, **self.ctx_kw)
+
+
+# =================================================================================================
+# The data set on the device once, a call's bags gathered there -- get_matrices (examples/mil_util.jl:46) as the drivers call it
+# with the bag ids of every fold (validate_with_cvs :627, validate_dataset :670)
+# =================================================================================================
+class BagPool:
+    """A data set of bags (L x M_b matrices with one L) resident on the GPU, uploaded ONCE: a basic-variant context of rank 1 that holds
+    them side by side.  select() lays chosen bags side by side in a fresh Bags / SparseBags by a device-to-device gather
+    (vbmf_set_Y_gather) -- what the reference's get_matrices does on the host for every fold, p_known and repetition -- and every
+    function that takes an upload takes that selection.  shapes() gives stand-ins of the selections' shapes for the initialisers.
+
+    Ys: a list of float64 or float32 NumPy arrays (laid side by side in their own dtype: float32 when all are, else float64), or of
+    torch tensors of one dtype (float64, float32, bfloat16) on the CPU or on the context's GPU (concatenated where they are); no fp64
+    copy is made of a non-fp64 source.  ctx_kw: Context options over the package defaults (y_dtype, device, ...); a selection is
+    stored as the pool is.  .session is the Session that holds the matrix: set_Y / set_Y_rows on it refill the pool in place with a
+    matrix of the same shape (row blocks, a tensor produced on the GPU)."""
+
+    def __init__(self, Ys, **ctx_kw):
+        fn = "BagPool"
+        Ys = list(Ys)
+        if not Ys:
+            _pool_refuse(fn, "no bags")
+        shapes = []
+        for b, Y in enumerate(Ys):
+            shape = tuple(Y.shape) if capi._is_tensor(Y) else np.shape(Y)
+            if len(shape) != 2 or shape[1] < 1:
+                _pool_refuse(fn, f"every bag must be a matrix with at least one column (bag {b} has shape {tuple(shape)})")
+            shapes.append((int(shape[0]), int(shape[1])))
+        if len({l for l, _ in shapes}) != 1:
+            _pool_refuse(fn, f"the bags have different row counts L {sorted({l for l, _ in shapes})}")
+        tens = [capi._is_tensor(Y) for Y in Ys]
+        if any(tens):
+            if not all(tens) or len({(Y.dtype, str(Y.device)) for Y in Ys}) != 1:
+                _pool_refuse(fn, "the bags must be all arrays, or all tensors of one dtype on one device")
+            import torch
+            Yall = Ys[0] if len(Ys) == 1 else torch.cat(Ys, dim=1)       # where they are, in their own dtype
+        else:
+            Ys = [Y if isinstance(Y, np.ndarray) else np.asarray(Y, dtype=np.float64) for Y in Ys]
+            dtype = np.float32 if all(Y.dtype == np.float32 for Y in Ys) else np.float64
+            Yall = np.empty((shapes[0][0], sum(m for _, m in shapes)), dtype=dtype, order="F")
+            c0 = 0
+            for Y, (_, m) in zip(Ys, shapes):
+                Yall[:, c0:c0 + m] = Y
+                c0 += m
+        self._fill(Yall, [m for _, m in shapes], ctx_kw)
+
+    @classmethod
+    def from_matrix(cls, Yall, col_off, **ctx_kw):
+        """The pool of a data set that is one L x M matrix already (an array or tensor Session.set_Y takes, as it lies): bag b is its
+        columns col_off[b] .. col_off[b+1]-1."""
+        fn = "BagPool.from_matrix"
+        shape = tuple(Yall.shape) if capi._is_tensor(Yall) else np.shape(Yall)
+        off = np.asarray(col_off, dtype=np.int64).reshape(-1)
+        if len(shape) != 2:
+            _pool_refuse(fn, f"Yall must be a matrix (got shape {tuple(shape)})")
+        if off.size < 2 or off[0] != 0 or off[-1] != shape[1] or np.any(np.diff(off) < 1):
+            _pool_refuse(fn, f"col_off must run from 0 to M = {shape[1]}, increasing (no empty bag)")
+        self = cls.__new__(cls)
+        self._fill(Yall if capi._is_tensor(Yall) or isinstance(Yall, np.ndarray) else np.asarray(Yall, dtype=np.float64),
+                   np.diff(off), ctx_kw)
+        return self
+
+    def _fill(self, Yall, Ms, ctx_kw):
+        self.Ms = [int(m) for m in Ms]
+        self.col_off = np.concatenate([[0], np.cumsum(self.Ms)]).astype(np.int64)
+        self.L, self.M = int(Yall.shape[0]), int(self.col_off[-1])
+        self.ctx_kw = dict(ctx_kw)
+        self.session = Session(self.L, self.M, 1, **ctx_kw)
+        try:
+            self.session.set_Y(Yall)
+        except Exception:
+            self.session.close()
+            raise
+        self._closed = False
+
+    @property
+    def ctx(self):
+        return self.session.ctx
+
+    def __len__(self):
+        return len(self.Ms)
+
+    def close(self):
+        self._closed = True
+        self.session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _groups(self, fn, groups, need_columns):
+        """The groups as lists of bag ids, checked on the host: a group is one id or a sequence of ids."""
+        if getattr(self, "_closed", True):
+            _pool_refuse(fn, "the pool is closed")
+        out = []
+        for k, g in enumerate(groups):
+            ids = [int(g)] if np.ndim(g) == 0 else [int(b) for b in g]
+            for b in ids:
+                if not 0 <= b < len(self.Ms):
+                    _pool_refuse(fn, f"group {k}: bag id {b} outside 0..{len(self.Ms) - 1}")
+            if need_columns and not ids:
+                _pool_refuse(fn, f"group {k} is empty (a matrix needs at least one bag)")
+            out.append(ids)
+        return out
+
+    def widths(self, groups, _fn="BagPool.widths"):
+        """Columns of every group: the sum of its bags' widths."""
+        return [sum(self.Ms[b] for b in ids) for ids in self._groups(_fn, groups, False)]
+
+    def shapes(self, groups, _fn="BagPool.shapes"):
+        """One stand-in per group (a bag id or a sequence of ids; may be empty): a read-only L x M_g view of a single zero that holds
+        no L x M memory, for the functions that read only the shape of Y -- vbmf_init, vbmf_sparse_init, vbmf_dual_init,
+        vbmf_trial_init, copy_vbmf_params."""
+        return [np.broadcast_to(np.float64(0.0), (self.L, m)) for m in self.widths(groups, _fn)]
+
+    def select(self, groups, H, kind="basic", _fn="BagPool.select", **ctx_kw):
+        """The bags of every group side by side, as a Bags (kind="basic") or a SparseBags (kind="sparse") for rank H: matrix k of the
+        result is the pool's bags groups[k] in the order given (a group is a bag id or a sequence of ids; ids may repeat).  One
+        Context, one vbmf_set_Y_gather: no host matrix and no upload.  ctx_kw: options over the pool's own.  Close it like any
+        upload."""
+        if kind not in ("basic", "sparse"):
+            _pool_refuse(_fn, f"kind = {kind!r} ('basic' or 'sparse')")
+        if int(H) > _BATCH_MAX_H:
+            _pool_refuse(_fn, f"H = {int(H)} > {_BATCH_MAX_H}")
+        if int(H) < 1:
+            _pool_refuse(_fn, f"H = {int(H)} < 1")
+        ids = self._groups(_fn, groups, True)
+        if not ids:
+            _pool_refuse(_fn, "no groups")
+        off = self.col_off
+        idx = np.concatenate([np.arange(off[b], off[b + 1]) for g in ids for b in g]).astype(np.int64)
+        cls = Bags if kind == "basic" else SparseBags
+        return cls._gathered(self.ctx, idx, self.L, [sum(self.Ms[b] for b in g) for g in ids], H, {**self.ctx_kw, **ctx_kw})
+
+
+def _pool_refuse(fn, why):
+    raise ValueError(f"{fn}: {why}")
+
+
+def _pool_front(pool, fn, H):
+    """What a training loop refuses about its pool before it draws a set or touches the library"""
+    if pool is None:
+        return
+    if not isinstance(pool, BagPool):
+        _pool_refuse(fn, f"pool is a {type(pool).__name__}, not a BagPool")
+    if pool._closed:
+        _pool_refuse(fn, "the pool is closed")
+    if int(H) > _FIT_MAX_H:
+        _pool_refuse(fn, f"H = {int(H)} > {_FIT_MAX_H}")
+
+
+@contextmanager
+def _selected(pool, groups, Ys, H, kind, fn):
+    """What a training loop hands to its batched call: the matrices themselves, or with a pool the one selection of their groups,
+    closed on the way out."""
+    if pool is None:
+        yield Ys
+        return
+    bags = pool.select(groups, H, kind=kind, _fn=fn)
+    try:
+        yield bags
+    finally:
+        bags.close()
 
 
 def _sbatch_check_params(L, Ms, H, params, refuse=_sbatch_refuse):
@@ -1637,15 +1826,21 @@ def vbmf_sparse_masked_batch_(Ys, params, niter, eps=1e-6, full_cov=False, est_c
                              False, bag_of, masked=True, **_rows(diag_var), **_split(form, slice_cols))
 
 
-def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False, form="stream", slice_cols=None):
+def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False, form="stream", slice_cols=None, pool=None):
     """The reference's train_local (examples/mil_util.jl:302-320) over many (Y0, Y1) pairs with all the fits in ONE device call per
     round: per pair Y = [Y0 Y1] and vbmf_sparse_init(Y, H, H1=H1, labels=1:M0), drawn in fold order from the one generator; every fold
     runs vbmf_sparse! in the diagonal form (:314); then, as the loop of :312-317 does, a fold whose norm(AHat) and norm(BHat) (operator
     2-norms) are both below 1e-2 runs again from where it stands, one further call per round, ten rounds at most.  diag_var goes to
     every vbmf_sparse! as it does at :314; form and slice_cols to every vbmf_sparse_masked_batch_ call.  Returns the list of parameter
-    sets."""
+    sets.
+    pool: a BagPool; every fold is then a pair of groups (bag ids of class 0, bag ids of class 1) in place of the two matrices -- the
+    fit's matrix is the bags of group 0 followed by those of group 1, M0 group 0's width -- the same sets are drawn in the same order
+    (from pool.shapes), the folds are selected ONCE on the device, and every round's call runs on that selection."""
     capi.ard_fit_form_code(form)
     rng = np.random.default_rng() if rng is None else rng
+    if pool is not None:
+        _pool_front(pool, "train_local_folds", H)
+        return _train_local_pool(pool, folds, H, H1, niter, eps, rng, diag_var, form, slice_cols)
     Ys, ps = [], []
     for Y0, Y1 in folds:
         Y = np.concatenate([np.asarray(Y0, dtype=np.float64), np.asarray(Y1, dtype=np.float64)], axis=1)
@@ -1662,6 +1857,28 @@ def train_local_folds(folds, H, H1, niter, eps=1e-4, rng=None, diag_var=False, f
         vbmf_sparse_masked_batch_([Ys[k] for k in again], [ps[k] for k in again], niter, eps=eps, full_cov=False, **_rows(diag_var),
                                   **_split(form, slice_cols))
         bound = [1e-2] * len(ps)                                    # :315
+    return ps
+
+
+def _train_local_pool(pool, folds, H, H1, niter, eps, rng, diag_var, form, slice_cols):
+    """train_local_folds on the bags of a pool: its loop, with one selection in place of the matrices"""
+    fn = "train_local_folds"
+    groups = [[b for g in pool._groups(fn, pair, False) for b in g] for pair in folds]
+    pool._groups(fn, groups, True)                                  # a fold needs at least one bag
+    M0s = [pool.widths([pair[0]], fn)[0] for pair in folds]
+    ps = [vbmf_sparse_init(Y, H, H1=H1, labels=np.arange(1, M0 + 1), rng=rng) for Y, M0 in zip(pool.shapes(groups, fn), M0s)]
+    if not ps:
+        return ps
+    norms = lambda p: (np.linalg.norm(p.AHat, 2), np.linalg.norm(p.BHat, 2))
+    bound = [sum(norms(p)) for p in ps]
+    with _selected(pool, groups, None, H, "sparse", fn) as bags:
+        for _ in range(10):
+            again = [k for k, p in enumerate(ps) if all(v < bound[k] for v in norms(p))]
+            if not again:
+                break
+            vbmf_sparse_masked_batch_(bags, [ps[k] for k in again], niter, eps=eps, full_cov=False, bag_of=again, **_rows(diag_var),
+                                      **_split(form, slice_cols))
+            bound = [1e-2] * len(ps)
     return ps
 
 
@@ -1750,7 +1967,7 @@ def row_gram_batch(bags):
         return up.ctx.row_gram(up.col_off)
 
 
-def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, form="stream", slice_cols=None):
+def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, form="stream", slice_cols=None, pool=None):
     """The reference's train (examples/mil_util.jl:93-152) over many (Y0, Y1) pairs -- the folds, p and repetitions of a validation
     run -- with all the fits in ONE device call.  solver="basic": 2 x len(folds) fits through vbmf_batch_ with est_covs = est_var =
     True (:110-114), vbmf_init drawn in the order (fold, class) from the one generator.  solver="sparse": ten vbmf_sparse_init per class
@@ -1758,7 +1975,10 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
     restart loop of :124-145 keeps (fit_restarts): the first with d <= 2 eps and not NaN, else the last.  Returns a list of
     (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns (:97-100).  form: vbmf_batch_'s for solver="basic"; for
     solver="sparse" vbmf_sparse_batch_'s "stream", "split" or "auto" with its slice_cols (that solver has no Gram form: "gram" is
-    refused)."""
+    refused).
+    pool: a BagPool; every fold is then a pair of groups (bag ids of class 0, bag ids of class 1) in place of the two matrices, as
+    get_matrices (:46) takes them: the same sets are drawn in the same order (from pool.shapes), the classes are selected once on the
+    device and the one batched call runs on that selection.  (0, 0) for a pair with an empty group."""
     if solver not in ("basic", "sparse"):
         raise ValueError(f"train_folds: solver = {solver!r} ('basic' or 'sparse')")
     if solver == "sparse":
@@ -1768,15 +1988,17 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
     if diag_var:
         raise ValueError("train_folds: diag_var=True is not batched; train such folds one at a time with vbmf_sparse_ / vbmf_ "
                          "(or the sparse solver's fits at once with vbmf_sparse_batch_(..., diag_var=True))")
+    _pool_front(pool, "train_folds", H)
     rng = np.random.default_rng() if rng is None else rng
     nstarts = 1 if solver == "basic" else 10                        # max_restarts of :108
     init = vbmf_init if solver == "basic" else vbmf_sparse_init
-    Ys, ps, bag_of, where = [], [], [], []
-    for k, pair in enumerate(folds):
+    Ys, ps, bag_of, where, groups = [], [], [], [], []
+    for k, pair in enumerate(folds if pool is None else [pool.shapes(pair, "train_folds") for pair in folds]):
         if any(np.shape(Y)[1:] == (0,) for Y in pair):              # n0 == 0 || n1 == 0 (:97-100)
             continue
         for c, Y in enumerate(pair):
             Ys.append(Y)
+            groups.append(folds[k][c])
             for _ in range(nstarts):
                 ps.append(init(Y, H, rng=rng))
                 bag_of.append(len(Ys) - 1)
@@ -1786,10 +2008,12 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
         return out
     if solver == "basic":
         kw = {} if form == "stream" else dict(form=form)            # (the default call is what it was)
-        vbmf_batch_(Ys, ps, niter, eps=eps, est_covs=True, est_var=True, bag_of=bag_of, **kw)
+        with _selected(pool, groups, Ys, H, "basic", "train_folds") as bags:
+            vbmf_batch_(bags, ps, niter, eps=eps, est_covs=True, est_var=True, bag_of=bag_of, **kw)
         kept = ps
     else:
-        ds = vbmf_sparse_batch_(Ys, ps, niter, eps=eps, full_cov=False, bag_of=bag_of, **_split(form, slice_cols))
+        with _selected(pool, groups, Ys, H, "sparse", "train_folds") as bags:
+            ds = vbmf_sparse_batch_(bags, ps, niter, eps=eps, full_cov=False, bag_of=bag_of, **_split(form, slice_cols))
         kept = []
         for b in range(len(Ys)):
             sets = list(zip(ps[b * nstarts:(b + 1) * nstarts], ds[b * nstarts:(b + 1) * nstarts]))
@@ -1802,25 +2026,27 @@ def train_folds(folds, solver, H, niter, eps=1e-6, diag_var=False, rng=None, for
     return out
 
 
-def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, rng=None, form="stream", slice_cols=None):
+def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, rng=None, form="stream", slice_cols=None, pool=None):
     """The reference's train_dual (examples/mil_util.jl:327-385) over many (Y0, Y1) pairs with all the fits in ONE device call: nstarts
     vbmf_dual_init per class per fold, drawn in the order (fold, class, restart) from the one generator, one vbmf_dual_batch_ call with
     full_cov=True (:351, :376) in which the restarts of a class share its upload, and per class the set the restart loops of :347-354
     and :372-379 keep (fit_restarts(model="dual")): the first with norm(AHat) + norm(BHat) >= 1e-2 (operator 2-norms), else the last.
     diag_var goes to every vbmf_dual! as it does there.  The column subsample of :342-344 is the caller's: pass the columns to train
     on.  form, slice_cols: vbmf_dual_batch_'s.  Returns a list of (res0, res1); (0, 0) for a pair whose Y0 or Y1 has no columns, as
-    train_folds does."""
+    train_folds does.  pool: a BagPool and folds of (bag ids of class 0, bag ids of class 1), as in train_folds."""
     capi.ard_fit_form_code(form)
     if int(nstarts) < 1:
         raise ValueError("train_dual_folds: nstarts must be >= 1")
+    _pool_front(pool, "train_dual_folds", H)
     rng = np.random.default_rng() if rng is None else rng
     nstarts = int(nstarts)
-    Ys, ps, bag_of, where = [], [], [], []
-    for k, pair in enumerate(folds):
+    Ys, ps, bag_of, where, groups = [], [], [], [], []
+    for k, pair in enumerate(folds if pool is None else [pool.shapes(pair, "train_dual_folds") for pair in folds]):
         if any(np.shape(Y)[1:] == (0,) for Y in pair):
             continue
         for c, Y in enumerate(pair):
             Ys.append(Y)
+            groups.append(folds[k][c])
             for _ in range(nstarts):
                 ps.append(vbmf_dual_init(Y, H, H0, rng=rng))
                 bag_of.append(len(Ys) - 1)
@@ -1828,7 +2054,8 @@ def train_dual_folds(folds, H, H0, niter, eps=1e-4, diag_var=False, nstarts=10, 
     out = [(0, 0)] * len(folds)
     if not ps:
         return out
-    vbmf_dual_batch_(Ys, ps, niter, eps=eps, full_cov=True, bag_of=bag_of, **_rows(diag_var), **_split(form, slice_cols))
+    with _selected(pool, groups, Ys, H, "sparse", "train_dual_folds") as bags:
+        vbmf_dual_batch_(bags, ps, niter, eps=eps, full_cov=True, bag_of=bag_of, **_rows(diag_var), **_split(form, slice_cols))
     res = {}
     for b, kc in enumerate(where):
         sets = ps[b * nstarts:(b + 1) * nstarts]

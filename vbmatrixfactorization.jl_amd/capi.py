@@ -104,7 +104,7 @@ SYMBOLS = [
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
     "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_set_gram_form",
-    "vbmf_get_YHat_rows", "vbmf_get_factor_rows",
+    "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
@@ -167,6 +167,7 @@ def lib():
     L.vbmf_last_error.restype = C.c_char_p
     L.vbmf_set_Y.argtypes = [vp, dp, i64]
     L.vbmf_set_Y_rows.argtypes = [vp, vp, C.c_int32, C.c_int32, i64, i64, i64, i64]
+    L.vbmf_set_Y_gather.argtypes = [vp, vp, C.POINTER(i64), i64]
     L.vbmf_set_Y_synthetic.argtypes = [vp, C.c_uint64, i64, C.c_double]
     L.vbmf_get_Y.argtypes = [vp, dp, i64, i64, i64]
     L.vbmf_get_trYY.argtypes = [vp, dp]
@@ -454,6 +455,12 @@ class Context:
         keep, addr, code, on_dev, rs, cs = y_source(src, self.device)
         self._chk(self._lib.vbmf_set_Y_rows(self._h, addr, code, on_dev, int(row0), int(n), rs, cs))
         del keep
+
+    def set_Y_gather(self, src_ctx, col_index):
+        """Y := columns col_index (0-based, in that order, duplicates allowed) of the Y stored in the context src_ctx, gathered on the
+        device (vbmf_set_Y_gather): what set_Y(src_ctx.get_Y()[:, col_index]) leaves, bit for bit, with no host matrix and no upload."""
+        idx = np.ascontiguousarray(col_index, dtype=np.int64).reshape(-1)
+        self._chk(self._lib.vbmf_set_Y_gather(self._h, src_ctx._h, _i64ptr(idx), idx.size))
 
     def set_Y_preprocessed(self, plan, lam):
         self._chk(self._lib.vbmf_set_Y_preprocessed(self._h, plan._h, float(lam)))

@@ -46,6 +46,28 @@ struct StridedSrc {
     }
 };
 
+// Columns of ANOTHER context's Y (vbmf_set_Y_gather): column m of the Y being built is column idx[m] of the source, decoded from the
+// source's pass-2 copy (x = l, k = column) with untile_y_kernel's index arithmetic.  f32 names the storage type both contexts share, so
+// the value is on the storage grid already and tile_y_kernel's one rounding returns it unchanged.  The host has checked every idx
+// against the source's M and both contexts have one L: the fragment read lies inside the source's copy.  KS: k-steps per x tile there.
+struct GatherSrc {
+    const uint4* Y2; const int* idx; int KS; bool f32;
+    long long L, M;
+    __device__ __forceinline__ double operator()(long long l, long long m) const {
+        const int KSTEP = f32 ? 8 : 16;
+        if (l >= L || m >= M) return 0.0;
+        const int j = idx[m];
+        const int xt = (int)(l >> 5), c = (int)(l & 31);
+        const int ks = j / KSTEP, w = j % KSTEP;
+        int half, e;
+        if (f32) { half = w >> 2; e = w & 3; }
+        else { half = (w >> 2) & 1; e = 4 * (w >> 3) + (w & 3); }
+        const unsigned* f = reinterpret_cast<const unsigned*>(Y2 + ((long long)xt * KS + ks) * 64 + half * 32 + c);
+        if (f32) return (double)bitsf(f[e]);
+        return (double)bf2f((unsigned short)((f[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
+    }
+};
+
 // One thread = one 16-byte fragment.  TRANSPOSED=false: x=m,k=l (Y1); true: x=l,k=m (Y2).
 // Fragments in [xt0,xt1) x [ks0,ks1) are produced.  When sumsq != nullptr each block writes the fp64 sum of
 // its squared stored values to sumsq[blockIdx.x] -- done on exactly one of the two copies.

@@ -1918,6 +1918,45 @@ int vbmf_set_Y(vbmf_ctx* c, const double* Y, int64_t ldY) {
     return finish_Y(c);
 }
 
+// ---- Y from the columns of another context's Y (get_matrices, examples/mil_util.jl:46) -------------------------------------------
+int vbmf_set_Y_gather(vbmf_ctx* c, vbmf_ctx* s, const int64_t* col_index, int64_t ncols) {
+    if (!c) { g_create_error = "vbmf_set_Y_gather: NULL dst"; return VBMF_ERR_INVALID; }
+    // every refusal comes before the first launch or copy and leaves dst, its current Y included, as it was
+    if (!s) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: NULL src");
+    if (!col_index) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: NULL col_index");
+    if (c == s) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: dst and src are the same context");
+    if (c->o.nranks > 1 || s->o.nranks > 1 || sharded(c) || sharded(s))
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "vbmf_set_Y_gather: row-sharded contexts (nranks > 1 or a communicator) are not supported");
+    if (ncols != c->M) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: ncols = %lld, dst has M = %lld columns", (long long)ncols, (long long)c->M);
+    if (s->L != c->L) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: src has L = %lld rows, dst has L = %lld", (long long)s->L, (long long)c->L);
+    if (s->o.y_dtype != c->o.y_dtype)
+        FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: src stores Y as y_dtype %d, dst as y_dtype %d", (int)s->o.y_dtype, (int)c->o.y_dtype);
+    if (s->o.device != c->o.device) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: src lives on device %d, dst on device %d", s->o.device, c->o.device);
+    if (!s->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: src has no complete Y");
+    if (s->M > (int64_t)INT32_MAX) FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: src has M = %lld columns, more than an int32 index names", (long long)s->M);
+    std::vector<int> idx((size_t)ncols);               // the whole table is checked here: no kernel ever sees a bad index
+    for (int64_t m = 0; m < ncols; ++m) {
+        if (col_index[m] < 0 || col_index[m] >= s->M)
+            FAIL(c, VBMF_ERR_INVALID, "vbmf_set_Y_gather: col_index[%lld] = %lld outside 0..%lld", (long long)m, (long long)col_index[m], (long long)(s->M - 1));
+        idx[(size_t)m] = (int)col_index[m];
+    }
+    HIPCHK(c, hipSetDevice(c->o.device));
+    HIPCHK(c, hipStreamSynchronize(s->stream));        // whatever still writes src's tiles has finished
+    DevScratch<int> table;
+    MEMCHK(c, table.alloc((size_t)ncols * sizeof(int)));
+    HIPCHK(c, hipMemcpyAsync(table, idx.data(), (size_t)ncols * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    double* tr = c->st + c->lay.scal() + S_TRYY;
+    HIPCHK(c, hipMemsetAsync(tr, 0, sizeof(double), c->stream));
+    // the column chunks of vbmf_set_Y, so that the partials of ||Y||^2 have its shape and are summed in its order
+    int64_t mc = std::max<int64_t>(32, ((int64_t)(256ll << 20) / (c->L * 8)) / 32 * 32);
+    mc = std::min<int64_t>(mc, rup(c->M, 32));
+    const GatherSrc src{s->Y2, table.get(), s->d2.KS, ymode_of(c->mode) == MODE_F32, c->L, c->M};
+    for (int64_t m0 = 0; m0 < c->M; m0 += mc) TRY(build_tiles(c, src, m0, std::min(c->M, m0 + mc), tr));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) FAIL(c, VBMF_ERR_HIP, "sync failed in vbmf_set_Y_gather");
+    table.reset();
+    return finish_Y(c);
+}
+
 // ---- Y from the caller's own dtype, layout and memory, in row blocks ------------------------------------------------------------
 static size_t src_elem_size(int dt) { return dt == VBMF_SRC_F64 ? 8 : dt == VBMF_SRC_F32 ? 4 : 2; }
 

@@ -16,7 +16,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
        ols_batch, rls_batch, ls_residual_batch,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
-       vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!
+       vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!, set_Y_gather!
 
 const libvbmf = get(ENV, "VBMF_HIP_LIB", joinpath(@__DIR__, "..", "libvbmf_hip.so"))
 
@@ -107,6 +107,18 @@ function set_Y!(h::Ptr{Cvoid}, Y::Array{Float32,2})
     L = size(Y, 1)
     chk(h, ccall((:vbmf_set_Y_rows, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Int64),
                  h, Y, VBMF_SRC_F32, Int32(0), 0, L, 1, L))
+end
+
+"""
+    set_Y_gather!(dst, src, cols)
+
+Y of the context handle `dst` := columns `cols` (1-based, in that order, duplicates allowed) of the Y stored in the context handle `src`,
+gathered on the device through vbmf_set_Y_gather: what get_matrices (examples/mil_util.jl:46) builds on the host for every fold, from
+a data set that was uploaded once.  `dst` must have length(cols) columns and `src`'s L, storage type and device.
+"""
+function set_Y_gather!(dst::Ptr{Cvoid}, src::Ptr{Cvoid}, cols::AbstractVector{<:Integer})
+    idx = Int64[c - 1 for c in cols]
+    chk(dst, ccall((:vbmf_set_Y_gather, libvbmf), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64), dst, src, idx, length(idx)))
 end
 
 const VBMF_DST_F64, VBMF_DST_F32 = Int32(0), Int32(1)
