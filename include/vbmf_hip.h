@@ -506,6 +506,35 @@ int vbmf_bag_residuals(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, con
  * leaves X and r2 unwritten. */
 int vbmf_bag_least_squares(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, const double* BHat, int64_t ldB, int64_t H, double lambda,
                            double* X, int64_t ldX, double* r2);
+/* vbmf_bag_least_squares_jobs: test_classification (examples/mil_util.jl:558-587) of every fold of validate_with_cvs
+ * (examples/mil_util.jl:627-648) in one call -- many bases and a list of (bag, basis) jobs on the one context that holds every bag of the
+ * data set (col_off as in vbmf_bag_least_squares).
+ *   Hs, BHat, lambda   basis k is L x Hs[k] fp64 column-major with leading dimension L, 1 <= Hs[k] <= 64; the bases are packed one after
+ *                      the other in BHat; lambda[k] is that basis' own value (0 = ols, > 0 = rls)
+ *   job_bag, job_basis job j scores bag job_bag[j] against basis job_basis[j].  Jobs may come in any order, a bag may appear in many
+ *                      jobs, a basis in many or none, and a job may repeat
+ *   X       (may be NULL) per-job blocks in job order, Hs[k] x M_b column-major with ld = Hs[k]: inv(B_k'B_k + lambda_k I) B_k' Y_b
+ *   r2      (njobs, may be NULL; not both) r2[j] = ||Y_b - B_k X_j||_F^2, formed entry by entry
+ *   status  (nbasis, required) 1 for a basis whose B'B + lambda I met a pivot that is not positive or not finite, else 0
+ * Job j's X block and r2[j] are bit for bit what vbmf_bag_least_squares returns for that bag with that basis and lambda, whatever
+ * else is in the call and wherever the job, the bag or the basis sits: both entries run the same device functions.  Four launches
+ * (Gram partials per (basis, row chunk); one inverse per basis; one workgroup per (job, 8-column slice of its bag); the fold of the
+ * slices per job) and one synchronising read-back, whatever nbasis and njobs are.
+ * A bad basis (status 1) does not fail the call, as in the *_fit_batched entries: its jobs get NaN in r2 and in every entry of their X
+ * block (written on the device), the other jobs are computed as if it were not in the call.  A non-finite r2 of a job whose basis has
+ * status 0 returns VBMF_ERR_NUMERIC and vbmf_last_error names the job; X, r2 and status HAVE been written by then (they come back
+ * with the one read-back that the scan follows), unlike vbmf_bag_least_squares, which leaves its outputs unwritten on a numeric
+ * failure.  Every refusal leaves X, r2 and status untouched.  The context's state, caches and Y are not changed; only Y is read.
+ * Refused before any launch, copy or change: VBMF_ERR_UNSUPPORTED for an Hs[k] outside 1..64 or more job slices than one grid holds
+ * -- a launch is kept to 2^32 - 1 threads, which is 16 777 215 workgroups of 256: that many 8-column job slices in all (so at most
+ * that many jobs), and that many (basis, 256-row chunk) pairs; nbasis and njobs have no other cap -- or a call whose bases and job
+ * tables the host cannot stage in memory;
+ * VBMF_ERR_INVALID for everything vbmf_bag_least_squares refuses, nbasis < 1, njobs < 1, a NULL Hs, BHat, lambda, job_bag, job_basis
+ * or status, X and r2 both NULL, a lambda[k] that is negative or not finite, a non-finite entry of any basis, a job_bag[j] outside
+ * 0..nbags-1, a job_basis[j] outside 0..nbasis-1, no Y. */
+int vbmf_bag_least_squares_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nbasis, const int64_t* Hs, const double* BHat,
+                                const double* lambda, int64_t njobs, const int64_t* job_bag, const int64_t* job_basis, double* X,
+                                double* r2, int64_t* status);
 /* lowerBound (src/vbmf_sparse.jl:435-471; dual src/vbmf_dual.jl:556-599; trial src/vbmf_trial.jl:630-680) for trim < 0 and
  * lowerBoundTrimmed (src/vbmf_sparse.jl:478-489; dual :606-617; trial :687-698) for trim >= 0 of every bag, as called per bag by
  * examples/mil_util.jl:502-514.  Sparse-family context, homoscedastic, one fixed basis: BHat, SigmaB, CB, delta and the hyper-priors

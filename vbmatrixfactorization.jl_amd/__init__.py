@@ -51,7 +51,8 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_batch_", "train_folds", "row_gram_batch", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
            "train_dual_folds", "BagPool",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
-           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch"]
+           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch",
+           "classify_folds", "test_classification_folds", "validate_folds"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
 # elements the field is left None and computed on demand with updateYHat_ (8 GB at 100k x 10k).
@@ -2445,8 +2446,13 @@ def test_classification_batch(res0, res1, Ys, labels, class_alg="ols", threshold
     a denominator gives inf / nan as Julia's float division does."""
     labels = np.asarray(labels).reshape(-1)
     est = np.asarray(classify_bags(res0, res1, Ys, class_alg, threshold=threshold)[0]).reshape(-1)
+    return _classification_counts("test_classification_batch", labels, est)
+
+
+def _classification_counts(fn, labels, est):
+    """(mer, eer, fp, fn, n0, n1) of test_classification (examples/mil_util.jl:574-586) from the true and the estimated labels"""
     if labels.shape != est.shape:
-        raise ValueError(f"test_classification_batch: {est.size} bags but {labels.size} labels")
+        raise ValueError(f"{fn}: {est.size} bags but {labels.size} labels")
     diff = labels.astype(np.int64) - est.astype(np.int64)
     fn_, fp = int(np.sum(diff == 1)), int(np.sum(diff == -1))
     n0 = int(np.sum(labels == 0))
@@ -2458,6 +2464,184 @@ def test_classification_batch(res0, res1, Ys, labels, class_alg="ols", threshold
 
 
 test_classification_batch.__test__ = False        # (the reference's name; not a test for a collector that meets it)
+
+
+# =================================================================================================
+# Every fold's test bags against its own models in one device call -- test_classification (examples/mil_util.jl:558-587) as
+# validate_with_cvs (:627-648), validate (:594-620) and validate_dataset (:670-788) run it per fold, p_known and repetition;
+# include/vbmf_hip.h: vbmf_bag_least_squares_jobs
+# =================================================================================================
+_FOLD_LAMS = {"ols": 0.0, "rls": 1e-2}                                   # :459, :466
+
+
+def _untrained(pair):
+    """(0, 0): what train_folds returns for a fold it could not train (:97-100)"""
+    return isinstance(pair, (tuple, list)) and len(pair) == 2 and all(type(r) is int and r == 0 for r in pair)
+
+
+def _folds_bags(fn, Ys):
+    """(L, number of bags) of what the fold functions classify, checked on the host: a BagPool, an upload or a list of matrices"""
+    refuse = _ls_refuser(fn)
+    if isinstance(Ys, BagPool):
+        if getattr(Ys, "_closed", True):
+            refuse("the pool is closed")
+        return Ys.L, len(Ys.Ms)
+    if isinstance(Ys, _Uploaded):
+        return Ys.L, len(Ys.Ms)
+    L, Ms = _batch_shapes(Ys, 1, refuse)
+    return L, len(Ms)
+
+
+def _fold_ids(fn, tests, nb):
+    """the folds' bag indices as lists of ints, each inside 0..nb-1"""
+    out = []
+    for f, t in enumerate(tests):
+        ids = []
+        for b in (t if np.ndim(t) else [t]):
+            if isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, np.integer)):
+                _ls_refuser(fn)(f"fold {f}: bag index {b!r} is not an integer")
+            if not 0 <= b < nb:
+                _ls_refuser(fn)(f"fold {f}: bag index {b} outside 0..{nb - 1}")
+            ids.append(int(b))
+        out.append(ids)
+    return out
+
+
+def _fold_alg(fn, class_alg):
+    if class_alg not in _FOLD_LAMS:
+        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols' or 'rls'; the other classifiers keep one basis per context: run them per "
+                        f"fold with classify_bags)")
+    return _FOLD_LAMS[class_alg]
+
+
+def _fold_labels(fn, labels, nb):
+    labels = np.asarray(labels).reshape(-1)
+    if labels.size != nb:
+        _ls_refuser(fn)(f"{nb} bags but {labels.size} labels")
+    if not np.all((labels == 0) | (labels == 1)):
+        _ls_refuser(fn)("labels must be 0 or 1")
+    return labels.astype(np.int64)
+
+
+def classify_folds(models, tests, Ys, class_alg="ols"):
+    """classify (examples/mil_util.jl:453-535) with class_alg "ols" or "rls" for every fold of a validation run in ONE device call:
+    fold f's test bags tests[f] (bag indices into Ys) against its own pair models[f] = (res0, res1).  Any objects with a BHat serve as
+    models, of the same or different H <= 64; (0, 0) -- what train_folds returns for a fold it could not train -- is accepted.
+    Ys: a BagPool (the indices are pool bag ids and the call runs on the pool's own context: no select, no gather, no new context), an
+    uploaded Bags / SparseBags, or a list of L x M_b matrices (uploaded once as Bags).
+    The call's bases are the trained folds' res0.BHat, res1.BHat in fold order -- 2 t and 2 t + 1 for the t-th trained fold, 2 f and
+    2 f + 1 when every fold is trained -- with lambda 0 for "ols" and 1e-2 for "rls" (:466), its jobs (bag, 2 t) and (bag, 2 t + 1)
+    for every tested bag (Context.bag_least_squares_jobs).  Returns a list with (labels, err0, err1) per fold as classify_bags gives
+    them (err = sqrt(r2), label 1 where err0 > err1, bit for bit classify_bags' on that fold alone); None for a (0, 0) fold, three
+    empty arrays for a fold with no test bags.
+    A fold one of whose bases has a B'B + lambda I that is not positive definite (a rank-deficient basis at "ols") raises VbmfError
+    naming the fold, after the other folds have been computed (the exception's .results holds them, None in that fold's place):
+    "rls" is the classifier for such bases, as the reference says (:463-464).  The iterating classifiers ("vbls", "dual",
+    "lower_bound", "min_err") keep one basis per context: classify_bags per fold."""
+    fn = "classify_folds"
+    refuse = _ls_refuser(fn)
+    lam = _fold_alg(fn, class_alg)
+    models, tests = list(models), list(tests)
+    if len(models) != len(tests):
+        refuse(f"{len(models)} models but {len(tests)} test lists")
+    L, nb = _folds_bags(fn, Ys)
+    ids = _fold_ids(fn, tests, nb)
+    bases, trained = [], []
+    for f, pair in enumerate(models):
+        if _untrained(pair):
+            continue
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            refuse(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
+        for k, r in enumerate(pair):
+            if getattr(r, "BHat", None) is None:
+                refuse(f"fold {f}: res{k} ({type(r).__name__}) has no BHat")
+            B = _ls_basis(f"{fn}: fold {f}: res{k}", r.BHat, lam)
+            if B.shape[0] != L:
+                refuse(f"fold {f}: res{k}.BHat is {B.shape[0]} x {B.shape[1]}, the bags have L = {L} rows")
+            bases.append(B)
+        trained.append(f)
+    job_bag, job_basis, where = [], [], {}
+    for t, f in enumerate(trained):
+        n = len(ids[f])
+        if n:
+            where[f] = len(job_bag)
+            job_bag += ids[f] + ids[f]
+            job_basis += [2 * t] * n + [2 * t + 1] * n
+    out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
+    if not job_bag:
+        return out
+    if isinstance(Ys, BagPool):
+        _, r2, status = Ys.ctx.bag_least_squares_jobs(Ys.col_off, bases, [lam] * len(bases), job_bag, job_basis)
+    else:
+        with _on_device(Ys, bases[0].shape[1], Bags) as bags:
+            _, r2, status = bags.ctx.bag_least_squares_jobs(bags.col_off, bases, [lam] * len(bases), job_bag, job_basis)
+    bad = []
+    for t, f in enumerate(trained):
+        if f not in where:
+            continue
+        if status[2 * t] or status[2 * t + 1]:
+            bad.append((f, 0 if status[2 * t] else 1))
+            out[f] = None
+            continue
+        n, j0 = len(ids[f]), where[f]
+        err0, err1 = np.sqrt(r2[j0:j0 + n]), np.sqrt(r2[j0 + n:j0 + 2 * n])
+        out[f] = ((err0 > err1).astype(np.int64), err0, err1)           # :487-491
+    if bad:
+        f, k = bad[0]
+        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: BHat'BHat + lambda I of res{k} is not positive definite (a pivot is not "
+                                             f"positive or not finite); class_alg='rls' is the classifier for such bases")
+        e.results = out
+        raise e
+    return out
+
+
+def test_classification_folds(models, tests, Ys, labels, class_alg="ols"):
+    """test_classification (examples/mil_util.jl:558-587) of every fold in one device call (classify_folds): a list with
+    (mer, eer, fp, fn, n0, n1) per fold, counted as test_classification_batch counts, from the fold's estimated labels and
+    labels[tests[f]].  labels: 0 / 1, one per bag of Ys.  A (0, 0) fold gives (-1.0,) * 6 (:612-614)."""
+    fn = "test_classification_folds"
+    _fold_alg(fn, class_alg)
+    models, tests = list(models), list(tests)
+    if len(models) != len(tests):
+        _ls_refuser(fn)(f"{len(models)} models but {len(tests)} test lists")
+    _, nb = _folds_bags(fn, Ys)
+    labels = _fold_labels(fn, labels, nb)
+    ids = _fold_ids(fn, tests, nb)
+    out = []
+    for t, r in zip(ids, classify_folds(models, ids, Ys, class_alg)):
+        if r is None:
+            out.append((-1.0,) * 6)
+        else:
+            out.append(_classification_counts(fn, labels[np.asarray(t, dtype=np.int64)], np.asarray(r[0]).reshape(-1)))
+    return out
+
+
+test_classification_folds.__test__ = False        # (named after the reference's test_classification; not a test)
+
+
+def validate_folds(pool, labels, splits, solver, H, niter, eps=1e-6, class_alg="ols", rng=None, form="stream", slice_cols=None):
+    """validate_with_cvs (examples/mil_util.jl:627-648) over all splits = [(train_ids, test_ids), ...] of a BagPool in two device
+    calls: one train_folds(..., pool=pool) on the folds' training groups -- the train_ids with label 0 and those with label 1, in the
+    order given (get_matrices, :46) -- and one test_classification_folds on the test_ids.  labels: 0 / 1, one per bag of the pool;
+    solver, H, niter, eps, rng, form, slice_cols: train_folds'; class_alg: "ols" or "rls".  Returns the list of
+    (mer, eer, fp, fn, n0, n1) per split, (-1.0,) * 6 for a split with an empty class."""
+    fn = "validate_folds"
+    refuse = _ls_refuser(fn)
+    _fold_alg(fn, class_alg)
+    if not isinstance(pool, BagPool):
+        refuse(f"pool is a {type(pool).__name__}, not a BagPool")
+    _, nb = _folds_bags(fn, pool)
+    if int(H) > _LS_MAX_H:
+        refuse(f"H = {int(H)} > {_LS_MAX_H}")
+    labels = _fold_labels(fn, labels, nb)
+    splits = [tuple(s) for s in splits]
+    if any(len(s) != 2 for s in splits):
+        refuse("every split is a pair (train_ids, test_ids)")
+    train = _fold_ids(fn, [s[0] for s in splits], nb)
+    tests = _fold_ids(fn, [s[1] for s in splits], nb)
+    folds = [([b for b in t if labels[b] == 0], [b for b in t if labels[b] == 1]) for t in train]
+    models = train_folds(folds, solver, H, niter, eps=eps, rng=rng, form=form, slice_cols=slice_cols, pool=pool)
+    return test_classification_folds(models, tests, pool, labels, class_alg)
 
 
 # =================================================================================================

@@ -103,7 +103,7 @@ SYMBOLS = [
     "vbmf_trial_set_priors", "vbmf_trial_get_priors", "vbmf_trial_run",
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
-    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_set_gram_form",
+    "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_bag_least_squares_jobs", "vbmf_set_gram_form",
     "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
@@ -214,6 +214,8 @@ def lib():
     L.vbmf_bag_residuals.argtypes = [vp, i64, C.POINTER(i64), dp, i64, dp]
     L.vbmf_sparse_lower_bound_batched.argtypes = [vp, i64, C.POINTER(i64), i32, C.c_double, i32] + [dp] * 15
     L.vbmf_bag_least_squares.argtypes = [vp, i64, C.POINTER(i64), dp, i64, i64, C.c_double, dp, i64, dp]
+    L.vbmf_bag_least_squares_jobs.argtypes = [vp, i64, C.POINTER(i64), i64, C.POINTER(i64), dp, dp, i64, C.POINTER(i64), C.POINTER(i64), dp, dp,
+                                              C.POINTER(i64)]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
     L.vbmf_set_gram_form.argtypes = [vp, i32]
     L.vbmf_sparse_set_SigmaA.argtypes = [vp, dp]
@@ -869,6 +871,40 @@ class Context:
         self._chk(self._lib.vbmf_bag_least_squares(self._h, nb, off.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(B), self.L, H, float(lam),
                                                    _dptr(X), H, _dptr(r2)))
         return X, r2
+
+    def bag_least_squares_jobs(self, col_off, bases, lams, job_bag, job_basis, want_X=False, want_r2=True):
+        """Many bases and a list of (bag, basis) jobs in one device call (vbmf_bag_least_squares_jobs): bases[k] (L, H_k) fp64 with its
+        own H_k <= 64 and lams[k] its lambda, job j scores bag job_bag[j] of col_off against basis job_basis[j].  Returns (Xs, r2,
+        status): Xs a list of (H_k, M_b) arrays per job or None, r2 (njobs,) or None, status (nbasis,) with 1 for a basis whose
+        B'B + lam I is not positive definite (its jobs are NaN, the others are computed).  Every job is bit for bit what
+        bag_least_squares gives for that bag with that basis and lambda.  The state is not changed."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        Bs = [_fcol(B) for B in bases]
+        for B in Bs:
+            if B.ndim != 2 or B.shape[0] != self.L:
+                raise ValueError(f"every basis must be ({self.L}, H), got {B.shape}")
+        lam = np.ascontiguousarray(lams, dtype=np.float64).reshape(-1)
+        jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
+        jk = np.ascontiguousarray(job_basis, dtype=np.int64).reshape(-1)
+        if lam.size != len(Bs) or jb.size != jk.size:
+            raise ValueError(f"{len(Bs)} bases but {lam.size} lambdas, or {jb.size} job bags but {jk.size} job bases")
+        Hs = np.array([B.shape[1] for B in Bs], dtype=np.int64)
+        Ball = np.concatenate([B.reshape(-1, order="F") for B in Bs]) if Bs else np.empty(0)
+        X = shapes = None
+        if want_X:                                                   # (a job out of range is the library's to refuse: no block for it)
+            ok = (jb >= 0) & (jb < nb) & (jk >= 0) & (jk < len(Bs))
+            shapes = [(int(Hs[k]), int(off[b + 1] - off[b])) if g else (0, 0) for b, k, g in zip(jb, jk, ok)]
+            xoff = np.concatenate([[0], np.cumsum([h * m for h, m in shapes])]).astype(np.int64)
+            X = np.empty(max(int(xoff[-1]), 1))
+        r2 = np.empty(jb.size) if want_r2 else None
+        status = np.zeros(len(Bs), dtype=np.int64)
+        self._chk(self._lib.vbmf_bag_least_squares_jobs(self._h, nb, _i64ptr(off), len(Bs), _i64ptr(Hs), _dptr(Ball), _dptr(lam), jb.size,
+                                                        _i64ptr(jb), _i64ptr(jk), _dptr(X), _dptr(r2), _i64ptr(status)))
+        Xs = None
+        if want_X:
+            Xs = [X[xoff[j]:xoff[j + 1]].reshape(shapes[j], order="F") for j in range(jb.size)]
+        return Xs, r2, status
 
     def sparse_lower_bound_batched(self, col_off, ATVecHat, diagSigmaATVec, CA, beta, SigmaA, sigmaHat, zeta, eta, eta0, zeta0,
                                    a_pri, b_pri, a_post, trim=None, clamp=True, grouped=False):

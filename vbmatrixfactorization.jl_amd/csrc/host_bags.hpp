@@ -339,6 +339,149 @@ int vbmf_bag_least_squares(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, c
     return VBMF_OK;
 }
 
+// test_classification (examples/mil_util.jl:558-587) of every fold of validate_with_cvs (:627-648) at once: many bases, and a list of
+// (bag, basis) jobs each of which is what vbmf_bag_least_squares computes for that bag with that basis and lambda, bit for bit -- the
+// kernels of both entries run the same __device__ functions (score_kernels.hpp).  Four launches and one synchronising read-back,
+// whatever nbasis and njobs are.
+int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t nbasis, const int64_t* Hs, const double* BHat,
+                                const double* lambda, int64_t njobs, const int64_t* job_bag, const int64_t* job_basis, double* X,
+                                double* r2, int64_t* status) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_bag_least_squares_jobs";
+    if (nbasis < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nbasis must be >= 1", fn);
+    if (njobs < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    if (!Hs || !BHat || !lambda || !job_bag || !job_basis || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only X or r2 may be NULL)", fn);
+    if (!X && !r2) FAIL(c, VBMF_ERR_INVALID, "%s: X and r2 are both NULL", fn);
+    const int64_t L = c->L, nb = nbags, nk = nbasis, nj = njobs, nchunk = cdiv(L, LS_ROWS);
+    // what one grid holds: a launch is kept to 2^32 - 1 threads in all, so to LS_MAX_GROUPS workgroups of SCORE_THREADS
+    if (nk > LS_MAX_GROUPS / nchunk)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld bases of %lld row chunks (more than %lld workgroups in one grid)", fn, (long long)nk, (long long)nchunk,
+             (long long)LS_MAX_GROUPS);
+    if (nj > LS_MAX_GROUPS)                                       // (a job has at least one slice)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs (more job slices than the %lld workgroups of one grid)", fn, (long long)nj, (long long)LS_MAX_GROUPS);
+    int64_t sumH = 0, sumH2 = 0, Hmax = 0;
+    for (int64_t k = 0; k < nk; ++k) {
+        if (Hs[k] < 1 || Hs[k] > LS_MAX_H)
+            FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: Hs[%lld] = %lld (built for 1 <= H <= %d)", fn, (long long)k, (long long)Hs[k], LS_MAX_H);
+        sumH += Hs[k];
+        sumH2 += Hs[k] * Hs[k];
+        Hmax = std::max(Hmax, Hs[k]);
+    }
+    BagDims bd;
+    TRY(score_check(c, fn, nbags, col_off, bd));
+    for (int64_t k = 0; k < nk; ++k)
+        if (!(lambda[k] >= 0.0) || !std::isfinite(lambda[k]))
+            FAIL(c, VBMF_ERR_INVALID, "%s: lambda[%lld] must be finite and >= 0", fn, (long long)k);
+    int64_t nsl = 0, sumX = 0;
+    for (int64_t j = 0; j < nj; ++j) {
+        const int64_t b = job_bag[j], k = job_basis[j];
+        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
+        if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_basis[%lld] = %lld outside 0..nbasis-1", fn, (long long)j, (long long)k);
+        const int64_t Mb = col_off[b + 1] - col_off[b];
+        nsl += (Mb + SCORE_CW - 1) / SCORE_CW;                    // (at most 2^24 terms of at most 2^60 / 8: no overflow)
+        sumX += Hs[k] * Mb;
+    }
+    if (nsl > LS_MAX_GROUPS)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld job slices (more than the %lld workgroups of one grid)", fn, (long long)nsl, (long long)LS_MAX_GROUPS);
+    // the upload, one block: [col_off nb + 1 | sl0 nj + 1 | job_bag | job_basis | x_off (nj each) | Hs | b_off | k_off (nk each) (int64)
+    //                         | lambda nk | the bases row-major [L][H_k], one after the other]
+    const int64_t u_sl = nb + 1, u_bag = u_sl + nj + 1, u_bas = u_bag + nj, u_xo = u_bas + nj, u_hs = u_xo + nj, u_bo = u_hs + nk,
+                  u_ko = u_bo + nk, u_lam = u_ko + nk, u_b = u_lam + nk, n_up = u_b + L * sumH;
+    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
+    try {
+        up.resize((size_t)n_up);
+        res.resize((size_t)(nj + nk));                            // r2 | the flags
+    } catch (const std::bad_alloc&) {
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of bases and job tables", fn, (long long)(n_up * 8));
+    }
+    long long* ui = reinterpret_cast<long long*>(up.data());
+    for (int64_t j = 0, sl = 0, xo = 0; j < nj; ++j) {
+        const int64_t b = job_bag[j], k = job_basis[j], Mb = col_off[b + 1] - col_off[b];
+        ui[u_sl + j] = sl;
+        ui[u_bag + j] = b;
+        ui[u_bas + j] = k;
+        ui[u_xo + j] = xo;
+        sl += (Mb + SCORE_CW - 1) / SCORE_CW;
+        xo += Hs[k] * Mb;
+    }
+    ui[u_sl + nj] = nsl;
+    for (int64_t b = 0; b <= nb; ++b) ui[b] = col_off[b];
+    for (int64_t k = 0, bo = 0, ko = 0; k < nk; ++k) {
+        const int64_t H = Hs[k];
+        ui[u_hs + k] = H;
+        ui[u_bo + k] = bo;
+        ui[u_ko + k] = ko;
+        up[(size_t)(u_lam + k)] = lambda[k];
+        double* Bt = up.data() + u_b + bo;
+        for (int64_t h = 0; h < H; ++h)
+            for (int64_t l = 0; l < L; ++l) {
+                const double v = BHat[bo + h * L + l];
+                if (!std::isfinite(v))
+                    FAIL(c, VBMF_ERR_INVALID, "%s: BHat of basis %lld [%lld, %lld] is not finite", fn, (long long)k, (long long)l, (long long)h);
+                Bt[l * H + h] = v;
+            }
+        bo += L * H;
+        ko += H * H;
+    }
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
+    auto run = [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->o.device));
+        // c->bags: [the upload | r2 nj | bad-pivot flags nk (an int in each slot) | partials nsl | Gram partials nchunk sum H_k^2
+        //           | K sum H_k^2 | X sum H_k M_b (job j's block at x_off[j])]
+        // (every slot is written before it is read: the flags by the inverse kernel, the partials by the job kernel)
+        const int64_t o_r2 = n_up, o_flag = o_r2 + nj, o_part = o_flag + nk, o_g = o_part + nsl, o_k = o_g + nchunk * sumH2,
+                      o_x = o_k + sumH2, total = o_x + (X ? sumX : 0);
+        double* d = nullptr;
+        TRY(bags_reserve(c, total, &d));
+        HIPCHK(c, hipMemcpyAsync(d, up.data(), (size_t)n_up * 8, hipMemcpyHostToDevice, c->stream));
+        const long long* di = reinterpret_cast<const long long*>(d);
+        const LsBases bs{di + u_hs, di + u_bo, di + u_ko, d + u_lam, d + u_b};
+        const LsJobs jobs{di + u_sl, di + u_bag, di + u_bas, di + u_xo, (int)nj};
+        int* d_flag = reinterpret_cast<int*>(d + o_flag);
+        hipLaunchKernelGGL(bag_ls_gram_jobs_kernel, dim3((unsigned)(nk * nchunk)), dim3(SCORE_THREADS), 0, c->stream, bs, (long long)L,
+                           (int)nchunk, d + o_g);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(bag_ls_inverse_jobs_kernel, dim3((unsigned)nk), dim3(256), spd_inverse_lds_bytes(LS_MAX_H / 16), c->stream, bs,
+                           d + o_g, (int)nchunk, d + o_k, d_flag);
+        HIPCHK(c, hipGetLastError());
+        double* d_x = X ? d + o_x : nullptr;
+        double* d_part = r2 ? d + o_part : nullptr;
+        const size_t lds = score_ls_lds_bytes((int)Hmax);
+        dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+            hipLaunchKernelGGL((bag_ls_jobs_kernel<decltype(ym)::value>), dim3((unsigned)nsl), dim3(SCORE_THREADS), lds, c->stream, c->Y2,
+                               c->d2.KS, (long long)L, bs, d + o_k, d_flag, di, jobs, d_x, d_part);
+        });
+        HIPCHK(c, hipGetLastError());
+        if (r2) {
+            hipLaunchKernelGGL(bag_resid_fold_kernel, dim3(cdiv(nj, 256)), dim3(256), 0, c->stream, d_part, di + u_sl, (int)nj, d + o_r2);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (X) HIPCHK(c, hipMemcpyAsync(X, d + o_x, (size_t)sumX * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
+        return VBMF_OK;
+    };
+    const int rc = run();
+    if (rc != VBMF_OK) {
+        hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    // (the outputs are written whatever the scan below finds: X came back with the one read-back)
+    for (int64_t k = 0; k < nk; ++k) {
+        int bad = 0;
+        std::memcpy(&bad, &res[(size_t)(nj + k)], sizeof(int));
+        status[k] = bad ? 1 : 0;
+    }
+    if (r2) {
+        std::memcpy(r2, res.data(), (size_t)nj * 8);
+        for (int64_t j = 0; j < nj; ++j)
+            if (!std::isfinite(r2[j]) && status[job_basis[j]] == 0)
+                FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite residual in job %lld (bag %lld, basis %lld)", fn, (long long)j, (long long)job_bag[j],
+                     (long long)job_basis[j]);
+    }
+    return VBMF_OK;
+}
+
 // lowerBound / lowerBoundTrimmed of every bag (examples/mil_util.jl:502-514 after a batched vbls!)
 int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int clamp, double trim, int grouped,
                                     const double* ATVecHat, const double* diagSigmaATVec, const double* CA, const double* beta,

@@ -24,6 +24,15 @@
 //                          at a time in LDS, x = K z, then the slice's sum of (y - B x)^2 entry by entry -- NOT ||y||^2 - z'Kz, which
 //                          cancels 400- to 3000-fold on fitted bags.  Every sum has one order fixed by (L, H, the slice's width): a
 //                          bag's X and r2 do not depend on where it sits in Y or on the other bags of the call.
+// Many bases and a list of (bag, basis) jobs in one call (vbmf_bag_least_squares_jobs; test_classification of every fold of
+// examples/mil_util.jl:627-648 at once).  The arithmetic of the three kernels above lives in __device__ functions (ls_gram_chunk,
+// ls_inverse, ls_slice) that these call with their own basis, so a job's numbers are the one-basis entry's by construction:
+//   bag_ls_gram_jobs_kernel     one workgroup per (basis, chunk of LS_ROWS rows), each with its own H_k
+//   bag_ls_inverse_jobs_kernel  one workgroup per basis, its own lambda_k and bad-pivot flag
+//   bag_ls_jobs_kernel          one workgroup per (job, slice of SCORE_CW columns of the job's bag, counted from the bag's own first
+//                               column), found by score_bag_of on the jobs' first slice numbers; ls_slice on that job's Bt, K, H and
+//                               X block.  A job whose basis raised its flag gets NaN in its X block and its partials instead.
+//   bag_resid_fold_kernel       r2[j] = the job's slice partials in slice order (the jobs' first slice numbers as chunk_off)
 // Data term of the per-bag bound: r2 + L tr(A'A SigmaB) + tr(SigmaA (B'B + L SigmaB)), algebraically the reference's
 // ||Y||^2 - 2 tr(B'YA) + tr((A'A + SigmaA)(B'B + L SigmaB)) (src/vbmf_sparse.jl:439-440) with the direct residual of the same
 // call in place of its three cancelling terms; so neither tr(B'Y_b A_b) nor ||Y_b||^2 is formed here.
@@ -44,6 +53,8 @@ inline size_t score_resid_lds_bytes(int H) { return (size_t)SCORE_CW * H * sizeo
 // vbmf_bag_least_squares
 constexpr int LS_MAX_H = 64;
 constexpr int LS_ROWS = 256;       // rows of B per Gram workgroup; rows of a slice of Y staged in LDS at a time
+// vbmf_bag_least_squares_jobs: the workgroups of SCORE_THREADS one grid is given, so that a launch stays within 2^32 - 1 threads
+constexpr long long LS_MAX_GROUPS = ((1ll << 32) - 1) / SCORE_THREADS;
 // dynamic LDS of bag_ls_kernel: K | z | x | the staged rows of Y | the row stripes' shares of z
 inline size_t score_ls_lds_bytes(int H) {
     const int P = SCORE_CW * H;
@@ -121,23 +132,48 @@ __global__ void bag_resid_fold_kernel(const double* __restrict__ part, const lon
     r2[b] = s;
 }
 
-// Bt: B row-major [L][H].  Gp: [gridDim.x][H * H]; entry (i, j) and entry (j, i) are the same products in the same order.
-__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_gram_kernel(const double* __restrict__ Bt, long long L, int H,
-                                                                    double* __restrict__ Gp) {
-    const long long l0 = (long long)blockIdx.x * LS_ROWS;
-    const long long l1 = l0 + LS_ROWS < L ? l0 + LS_ROWS : L;
+// The H x H Gram partial of rows l0 .. l1-1 of Bt (B row-major [L][H]) into Gc; entry (i, j) and entry (j, i) are the same products in
+// the same order.
+__device__ __forceinline__ void ls_gram_chunk(const double* __restrict__ Bt, long long l0, long long l1, int H, double* __restrict__ Gc) {
     for (int e = threadIdx.x; e < H * H; e += SCORE_THREADS) {
         const int i = e / H, j = e % H;
         double s = 0.0;
         for (long long l = l0; l < l1; ++l) s = fma(Bt[l * H + i], Bt[l * H + j], s);
-        Gp[(long long)blockIdx.x * H * H + e] = s;
+        Gc[e] = s;
     }
 }
 
-// K[H][H] = inv(sum of the nchunk Gram partials + lambda I); *bad != 0: a pivot was not positive / finite.  LDS: spd_inverse_lds_bytes(4).
-__global__ __launch_bounds__(256) void bag_ls_inverse_kernel(const double* __restrict__ Gp, int nchunk, int H, double lambda,
-                                                             double* __restrict__ K, int* __restrict__ bad) {
-    extern __shared__ __attribute__((aligned(16))) double Wl[];
+// Bt: B row-major [L][H].  Gp: [gridDim.x][H * H]
+__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_gram_kernel(const double* __restrict__ Bt, long long L, int H,
+                                                                    double* __restrict__ Gp) {
+    const long long l0 = (long long)blockIdx.x * LS_ROWS;
+    const long long l1 = l0 + LS_ROWS < L ? l0 + LS_ROWS : L;
+    ls_gram_chunk(Bt, l0, l1, H, Gp + (long long)blockIdx.x * H * H);
+}
+
+// The bases of a jobs call: basis k is Bt + b_off[k] (row-major [L][Hs[k]]); its Gram partials are Gp + nchunk * k_off[k]
+// ([nchunk][H_k^2]), its inverse K + k_off[k]: k_off[k] = the sum of H_q^2 over q < k.
+struct LsBases {
+    const long long* Hs;
+    const long long* b_off;
+    const long long* k_off;
+    const double* lambda;
+    const double* Bt;
+};
+
+// workgroup (k, q) = blockIdx.x: chunk q of basis k
+__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_gram_jobs_kernel(LsBases bs, long long L, int nchunk, double* __restrict__ Gp) {
+    const int k = blockIdx.x / nchunk, q = blockIdx.x % nchunk;
+    const int H = (int)bs.Hs[k];
+    const long long l0 = (long long)q * LS_ROWS;
+    const long long l1 = l0 + LS_ROWS < L ? l0 + LS_ROWS : L;
+    ls_gram_chunk(bs.Bt + bs.b_off[k], l0, l1, H, Gp + (long long)nchunk * bs.k_off[k] + (long long)q * H * H);
+}
+
+// K[H][H] = inv(sum of the nchunk Gram partials + lambda I); *bad != 0: a pivot was not positive / finite.  Wl: spd_inverse_lds_bytes(4)
+// of LDS; the whole workgroup of 256 calls it.
+__device__ __forceinline__ void ls_inverse(double* Wl, const double* __restrict__ Gp, int nchunk, int H, double lambda,
+                                           double* __restrict__ K, int* __restrict__ bad) {
     double logdet;
     int notpd;
     spd_inverse_lds4<LS_MAX_H / 16>(Wl, H, [&](int i, int j) {
@@ -150,28 +186,35 @@ __global__ __launch_bounds__(256) void bag_ls_inverse_kernel(const double* __res
     if (threadIdx.x == 0) *bad = notpd;
 }
 
-// X: [M][H] (column m of the H x M estimate at X + m * H) or nullptr; part: the slices' residual partials or nullptr.
+__global__ __launch_bounds__(256) void bag_ls_inverse_kernel(const double* __restrict__ Gp, int nchunk, int H, double lambda,
+                                                             double* __restrict__ K, int* __restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) double Wl[];
+    ls_inverse(Wl, Gp, nchunk, H, lambda, K, bad);
+}
+
+// one workgroup per basis; bad: one int per basis, 8 bytes apart (the slots of the call's read-back block)
+__global__ __launch_bounds__(256) void bag_ls_inverse_jobs_kernel(LsBases bs, const double* __restrict__ Gp, int nchunk,
+                                                                  double* __restrict__ K, int* __restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) double Wl[];
+    const int k = blockIdx.x;
+    ls_inverse(Wl, Gp + (long long)nchunk * bs.k_off[k], nchunk, (int)bs.Hs[k], bs.lambda[k], K + bs.k_off[k], bad + 2 * k);
+}
+
+// One slice of a bag against one basis: columns m0 .. m0 + nc - 1 of Y (nc <= SCORE_CW), Bt row-major [L][H], K = inv(B'B + lambda I).
+// Xs: the slice's columns of the estimate (column cc at Xs + cc * H) or nullptr; part_w: the slice's residual partial or nullptr.
+// ls: score_ls_lds_bytes(H) of LDS; red: SCORE_THREADS / 64 doubles.
 // Output o = (column cc, component h) = cc * H + h of the slice's P = nc * H.  z: with P <= 256 the threads split into S = 256 / P row
 // stripes (rows s, s + S, ... of every staged tile, tiles in order), whose shares meet in LDS in stripe order; above, every thread
 // owns outputs o and o + 256 whole.
 template <int MODE>
-__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_kernel(const uint4* __restrict__ Y2, int KSpad, long long L,
-                                                               const double* __restrict__ Bt, int H, const double* __restrict__ K,
-                                                               const long long* __restrict__ col_off,
-                                                               const long long* __restrict__ chunk_off, int nbags,
-                                                               double* __restrict__ X, double* __restrict__ part) {
-    extern __shared__ __attribute__((aligned(16))) double ls[];
-    __shared__ double red[SCORE_THREADS / 64];
+__device__ __forceinline__ void ls_slice(const uint4* __restrict__ Y2, int KSpad, long long L, const double* __restrict__ Bt, int H,
+                                         const double* __restrict__ K, long long m0, int nc, double* __restrict__ Xs,
+                                         double* __restrict__ part_w, double* ls, double* red) {
     double* Kl = ls;                                   // [H][H]
     double* zl = Kl + H * H;                           // [SCORE_CW][H]
     double* xl = zl + SCORE_CW * H;                    // [SCORE_CW][H]
     double* yt = xl + SCORE_CW * H;                    // [SCORE_CW][LS_ROWS]
     double* zp = yt + SCORE_CW * LS_ROWS;              // [S][P]
-    const long long w = blockIdx.x;
-    const int b = score_bag_of(chunk_off, nbags, w);
-    const long long m0 = col_off[b] + (w - chunk_off[b]) * SCORE_CW;
-    const long long mend = col_off[b + 1];
-    const int nc = (int)(mend - m0 < SCORE_CW ? mend - m0 : SCORE_CW);
     const int P = nc * H;
     const int S = P > SCORE_THREADS ? 1 : SCORE_THREADS / P;
     const int tid = threadIdx.x;
@@ -217,9 +260,9 @@ __global__ __launch_bounds__(SCORE_THREADS) void bag_ls_kernel(const uint4* __re
         double x = 0.0;
         for (int j = 0; j < H; ++j) x = fma(Kl[j * H + h], zc[j], x);      // (K is symmetric bit for bit: one triangle, mirrored)
         xl[q] = x;
-        if (X != nullptr) X[(m0 + cc) * H + h] = x;
+        if (Xs != nullptr) Xs[cc * H + h] = x;
     }
-    if (part == nullptr) return;
+    if (part_w == nullptr) return;
     __syncthreads();
     double r2 = 0.0;
     const long long n = (long long)nc * L;
@@ -234,7 +277,62 @@ __global__ __launch_bounds__(SCORE_THREADS) void bag_ls_kernel(const uint4* __re
         r2 += d * d;
     }
     r2 = block_sum(r2, red);
-    if (tid == 0) part[w] = r2;
+    if (tid == 0) *part_w = r2;
+}
+
+// X: [M][H] (column m of the H x M estimate at X + m * H) or nullptr; part: the slices' residual partials or nullptr.
+template <int MODE>
+__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_kernel(const uint4* __restrict__ Y2, int KSpad, long long L,
+                                                               const double* __restrict__ Bt, int H, const double* __restrict__ K,
+                                                               const long long* __restrict__ col_off,
+                                                               const long long* __restrict__ chunk_off, int nbags,
+                                                               double* __restrict__ X, double* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double ls[];
+    __shared__ double red[SCORE_THREADS / 64];
+    const long long w = blockIdx.x;
+    const int b = score_bag_of(chunk_off, nbags, w);
+    const long long m0 = col_off[b] + (w - chunk_off[b]) * SCORE_CW;
+    const long long mend = col_off[b + 1];
+    const int nc = (int)(mend - m0 < SCORE_CW ? mend - m0 : SCORE_CW);
+    ls_slice<MODE>(Y2, KSpad, L, Bt, H, K, m0, nc, X ? X + m0 * H : nullptr, part ? part + w : nullptr, ls, red);
+}
+
+// The jobs of a call: job j scores bag job_bag[j] against basis job_basis[j]; its slices are numbers sl0[j] .. sl0[j+1]-1 and its
+// H_k x M_b block of X starts at x_off[j] (column-major, ld = H_k).
+struct LsJobs {
+    const long long* sl0;
+    const long long* bag;
+    const long long* basis;
+    const long long* x_off;
+    int njobs;
+};
+
+// One workgroup per job slice.  bad: the bases' flags as bag_ls_inverse_jobs_kernel left them; X, part: nullptr = not wanted.
+// Dynamic LDS: score_ls_lds_bytes(the largest H of the call).
+template <int MODE>
+__global__ __launch_bounds__(SCORE_THREADS) void bag_ls_jobs_kernel(const uint4* __restrict__ Y2, int KSpad, long long L, LsBases bs,
+                                                                    const double* __restrict__ K, const int* __restrict__ bad,
+                                                                    const long long* __restrict__ col_off, LsJobs jobs,
+                                                                    double* __restrict__ X, double* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double ls[];
+    __shared__ double red[SCORE_THREADS / 64];
+    const long long w = blockIdx.x;
+    const int j = score_bag_of(jobs.sl0, jobs.njobs, w);
+    const long long c0 = (w - jobs.sl0[j]) * SCORE_CW;            // the slice's first column within the bag
+    const int b = (int)jobs.bag[j], k = (int)jobs.basis[j];
+    const long long m0 = col_off[b] + c0;
+    const long long mend = col_off[b + 1];
+    const int nc = (int)(mend - m0 < SCORE_CW ? mend - m0 : SCORE_CW);
+    const int H = (int)bs.Hs[k];
+    double* Xs = X ? X + jobs.x_off[j] + c0 * H : nullptr;
+    if (bad[2 * k]) {                                             // (the same for the whole workgroup)
+        const double nan = __longlong_as_double(0x7FF8000000000000ll);
+        if (Xs != nullptr)
+            for (int t = threadIdx.x; t < nc * H; t += SCORE_THREADS) Xs[t] = nan;
+        if (part != nullptr && threadIdx.x == 0) part[w] = nan;
+        return;
+    }
+    ls_slice<MODE>(Y2, KSpad, L, bs.Bt + bs.b_off[k], H, K + bs.k_off[k], m0, nc, Xs, part ? part + w : nullptr, ls, red);
 }
 
 // a, dS, CA, beta: M*H in vec(A') order (index m*H + h); SA: nbags x H x H.  sums: [nbags][H][SCORE_NS];

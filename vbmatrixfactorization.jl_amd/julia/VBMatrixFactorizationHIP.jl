@@ -14,7 +14,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        vbls!, vbls_batch!, vbmf_batch!, row_gram_batch, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
-       ols_batch, rls_batch, ls_residual_batch,
+       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!, set_Y_gather!
 
@@ -1163,6 +1163,40 @@ end
 function ls_residual_batch(Ys::Vector{Matrix{Float64}}, B::Matrix{Float64}, lam::Float64 = 0.0)
     _, r2, _ = bag_least_squares(Ys, B, lam, "ls_residual_batch")
     return sqrt.(r2)
+end
+
+"""
+    bag_least_squares_jobs(ctx, col_off, bases, lams, job_bag, job_basis)
+
+test_classification (examples/mil_util.jl:558-587) of every fold of validate_with_cvs (examples/mil_util.jl:627-648) in ONE device call
+(vbmf_bag_least_squares_jobs): `ctx` holds every bag of the data set side by side (bag b = columns col_off[b]+1 .. col_off[b+1], col_off
+0-based offsets), `bases[k]` is L x H_k with H_k <= 64 and `lams[k]` its lambda (0 = ols, > 0 = rls), job j scores bag `job_bag[j]`
+against basis `job_basis[j]` (both 1-based).  Returns (Xs, r2, status): Xs[j] = inv(B'B + lam I) B' Y_b (H_k x M_b), r2[j] =
+norm(Y_b - B Xs[j])^2, status[k] = 1 for a basis whose B'B + lam I is not positive definite (its jobs are NaN; the others are computed).
+Every job is bit for bit what vbmf_bag_least_squares gives for that bag with that basis.
+"""
+function bag_least_squares_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, bases::Vector{Matrix{Float64}}, lams::Vector{Float64},
+                                job_bag::AbstractVector{<:Integer}, job_basis::AbstractVector{<:Integer})
+    nb, nk, nj = length(col_off) - 1, length(bases), length(job_bag)
+    (nk >= 1 && length(lams) == nk) || error("bag_least_squares_jobs: one lambda per basis, at least one basis")
+    (nj >= 1 && length(job_basis) == nj) || error("bag_least_squares_jobs: job_bag and job_basis must have one entry per job, at least one")
+    L = size(bases[1], 1)
+    all(B -> size(B, 1) == L && 1 <= size(B, 2) <= 64, bases) || error("bag_least_squares_jobs: every basis must be L x H with 1 <= H <= 64")
+    all(j -> 1 <= job_bag[j] <= nb && 1 <= job_basis[j] <= nk, 1:nj) || error("bag_least_squares_jobs: a job names a bag or a basis that is not there")
+    Hs = Int64[size(B, 2) for B in bases]
+    Ball = reduce(vcat, [vec(B) for B in bases])
+    jb, jk = Int64[b - 1 for b in job_bag], Int64[k - 1 for k in job_basis]
+    shapes = [(Hs[jk[j]+1], col_off[jb[j]+2] - col_off[jb[j]+1]) for j in 1:nj]
+    xoff = Int64[0; cumsum([h * m for (h, m) in shapes])]
+    X = Array{Float64}(undef, xoff[end])
+    r2 = Array{Float64}(undef, nj)
+    status = Array{Int64}(undef, nk)
+    chk(ctx, ccall((:vbmf_bag_least_squares_jobs, libvbmf), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int64}),
+        ctx, nb, col_off, nk, Hs, Ball, lams, nj, jb, jk, X, r2, status))
+    Xs = [reshape(X[xoff[j]+1:xoff[j+1]], shapes[j]) for j in 1:nj]
+    return Xs, r2, status
 end
 
 "vbmf_dual! -- src/vbmf_dual.jl:455-530 (returns d); est_priors: the hyper-prior fits of :393-434 run on the device"
