@@ -535,6 +535,46 @@ int vbmf_bag_least_squares(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off,
 int vbmf_bag_least_squares_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t nbasis, const int64_t* Hs, const double* BHat,
                                 const double* lambda, int64_t njobs, const int64_t* job_bag, const int64_t* job_basis, double* X,
                                 double* r2, int64_t* status);
+/* vbmf_sparse_fixed_basis_jobs: vbls! of the ARD families (examples/mil_util.jl:187-197) for a list of (bag, model) jobs and each job's
+ * norm(Y - BHat*AHat')^2 -- the "dual" classifier of examples/mil_util.jl:515-530 (20 vbls! iterations with full_cov = true against each
+ * of a fold's two models) for every fold of validate_with_cvs in one call, on the one context that holds every bag of the data set
+ * (col_off as in vbmf_bag_least_squares).  Any context variant serves, with one rank and no label mask: only its Y is read, and the
+ * call's H has nothing to do with the context's own.
+ *   H, niter, full_cov  1 <= H <= 32 for every model of the call (the whole-fit entries' cap), niter >= 1 iterations of updateA! with
+ *                       updateCA! behind it and updateSigma!, the diagonal (0) or the full_cov (1) form of updateA!; homoscedastic noise
+ *   per model k < nmodels, packed in model order:
+ *   BHat, SigmaB        L x H fp64 column-major with ld = L, used in fp64 as given; H x H
+ *   alpha, beta0        (H each) updateCA!'s posterior shape and prior rate per column of A: the three families differ only there
+ *   eta0, zeta0         the noise precision's Gamma prior; the device forms eta = eta0 + L M_b / 2 per job
+ *   sigma0, ca0         every job of the model starts from sigmaHat = sigma0[k] and CA = ca0[k] ones (what copy_vbmf_params gives)
+ *   job_bag, job_model  job j runs bag job_bag[j] against model job_model[j].  Jobs may come in any order, a bag may appear in many
+ *                       jobs, a model in many or none, and a job may repeat
+ *   r2                  (njobs, may be NULL) ||Y_b - BHat_k AHat_j'||_F^2, formed entry by entry in fp64, never by the trace form
+ *   ATVecHat, diagSigmaATVec, CA, beta   (each may be NULL; r2 and ATVecHat not both) per-job blocks in job order, each M_b H long in
+ *                       vec(A') order as in vbmf_sparse_run_fixed_basis_batched
+ *   SigmaA (njobs H H), sigmaHat, zeta (njobs)   may be NULL
+ *   status              (njobs, required) 1 for a job that met a non-finite precision or a pivot that is not positive and finite (or ended
+ *                       with a non-finite sigmaHat, zeta or r2), else 0
+ * Everything is fp64, Y widened on load from Y as stored.  Every sum has an order fixed by (L, M_b, H) alone, so a job's numbers do not
+ * depend on the other jobs, on their order, or on where the bag sits in Y.  Two launches (one workgroup per model: G = B'B + L SigmaB;
+ * one workgroup per job: Y_b'B_k, the iterations, the residual) and one synchronising read-back, whatever nmodels and njobs are.
+ * A failed job (status 1) does not fail the call, as in the *_fit_batched entries: it gets NaN in r2 and in every entry of its blocks
+ * (written on the device), the other jobs are computed as if it were not in the call.  The context's state, caches and Y are not
+ * changed.  Under VBMF_COMPAT_SPARSE_REPEAT the diagonal form carries the QS1 layout with the job's own M_b.
+ * Refused before any launch, copy or change, every output left untouched: VBMF_ERR_UNSUPPORTED for H outside 1..32, more jobs or models
+ * than the 16 777 215 workgroups one grid holds, or a call whose models and results the host cannot stage in memory;
+ * VBMF_ERR_INVALID for everything bags_check refuses (a sharded context, nbags < 1, a col_off that does not run from 0 to M or that
+ * decreases), nmodels < 1, njobs < 1, niter < 1, a NULL input or status, r2 and ATVecHat both NULL, a non-finite entry of any BHat,
+ * SigmaB, alpha, beta0, eta0, zeta0, sigma0 or ca0, a job_bag[j] outside 0..nbags-1, a job_model[j] outside 0..nmodels-1, a label
+ * mask, no Y, and a 1-column bag in the diagonal form under VBMF_COMPAT_SPARSE_REPEAT (as vbmf_sparse_fit_batched). */
+int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t H, int64_t niter, int full_cov,
+                                 int64_t nmodels, const double* BHat, const double* SigmaB, const double* alpha, const double* beta0,
+                                 const double* eta0, const double* zeta0, const double* sigma0, const double* ca0, int64_t njobs,
+                                 const int64_t* job_bag, const int64_t* job_model, double* r2, double* ATVecHat, double* diagSigmaATVec,
+                                 double* CA, double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status);
+/* test hook: the widest bag whose job keeps its state in LDS in vbmf_sparse_fixed_basis_jobs at this H and form (wider ones work in the
+ * call's scratch buffer); 0 for an H outside 1..32 */
+int vbmf_debug_vbls_jobs_lds_cols(int64_t H, int full_cov);
 /* lowerBound (src/vbmf_sparse.jl:435-471; dual src/vbmf_dual.jl:556-599; trial src/vbmf_trial.jl:630-680) for trim < 0 and
  * lowerBoundTrimmed (src/vbmf_sparse.jl:478-489; dual :606-617; trial :687-698) for trim >= 0 of every bag, as called per bag by
  * examples/mil_util.jl:502-514.  Sparse-family context, homoscedastic, one fixed basis: BHat, SigmaB, CB, delta and the hyper-priors

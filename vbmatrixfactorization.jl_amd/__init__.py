@@ -51,7 +51,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_batch_", "train_folds", "row_gram_batch", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
            "train_dual_folds", "BagPool",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
-           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch",
+           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch", "vbls_sparse_jobs_",
            "classify_folds", "test_classification_folds", "validate_folds"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
@@ -1598,17 +1598,20 @@ def vbls_sparse_batch_(Ys, params, niter, full_cov=False):
                                                [p.eta0 + p.L * p.M / 2 for p in params], [p.zeta0 for p in params],
                                                [p.sigmaHat for p in params], np.concatenate([np.asarray(p.CA, dtype=np.float64).reshape(-1)
                                                                                               for p in params]), full_cov=full_cov)
-    out = []
-    for b, p in enumerate(params):
-        _write_A_side(p, r, b, bags.col_off[b] * H)
-        if m.views is not None:                                         # what _pull fills, the priors as updateCA! sets them:
-            m.views(p)                                                  # src/vbmf_dual.jl:324-325, src/vbmf_trial.jl:359-361
-            for a0, _, a in m.groups:
-                setattr(p, a, getattr(p, a0) + 0.5)
-            p.alpha = _posterior_shapes(p, m)
-        p.YHat = _host_YHat(p)                                          # :201
-        out.append(p.AHat)
-    return out
+    return [_vbls_filled(p, m, r, b, bags.col_off[b] * H) for b, p in enumerate(params)]
+
+
+def _vbls_filled(p, m, r, k, s0):
+    """What a batched vbls! call's results r give set p (entry k, its M H-long vectors starting at s0): the fields per-bag vbls_ fills.
+    Returns p.AHat."""
+    _write_A_side(p, r, k, s0)
+    if m.views is not None:                                             # what _pull fills, the priors as updateCA! sets them:
+        m.views(p)                                                      # src/vbmf_dual.jl:324-325, src/vbmf_trial.jl:359-361
+        for a0, _, a in m.groups:
+            setattr(p, a, getattr(p, a0) + 0.5)
+        p.alpha = _posterior_shapes(p, m)
+    p.YHat = _host_YHat(p)                                              # :201
+    return p.AHat
 
 
 # =================================================================================================
@@ -2214,10 +2217,13 @@ def lowerBoundTrimmed_batch(Ys, params, trim=1e-1, clamp=True):
 _CLASS_ALGS = ("vbls", "dual", "lower_bound")
 
 
+_TRIAL_TWO_SETS = ("a vbmf_trial_parameters model gives two parameter sets per bag (copy_vbmf_params), which classify does not take "
+                   "either")
+
+
 def _one_set(fn, q):
     if isinstance(q, tuple):
-        _score_refuser(fn)("a vbmf_trial_parameters model gives two parameter sets per bag (copy_vbmf_params), which classify does "
-                           "not take either")
+        _score_refuser(fn)(_TRIAL_TWO_SETS)
     return q
 
 
@@ -2275,12 +2281,18 @@ def classify_batch(res0, res1, Ys, class_alg, threshold=1e-1, niter=None):
       "lower_bound"  factorize_bag on res0 (a vbmf_sparse_parameters with H1 > 0; res1 is not read, as in the reference), 20
                      iterations, full_cov per bag by M_b (H - H1) < 1600; err0 = lowerBound of the truncated basis' fit, err1 =
                      lowerBoundTrimmed(threshold) of the whole basis' fit, label 1 where err1 > err0
-    niter overrides the iteration count.  "ols", "rls" and "min_err" are not taken here: classify_bags takes all six."""
+    niter overrides the iteration count.  "ols", "rls" and "min_err" are not taken here: classify_bags takes all six.
+    Ys: a list of L x M_b arrays; for "vbls" also an uploaded Bags, for "dual" an uploaded SparseBags, of the models' H (a BagPool
+    selection: nothing is uploaded and the upload is left open)."""
     fn = "classify_batch"
     refuse = _score_refuser(fn)
     if class_alg not in _CLASS_ALGS:
         refuse(f"class_alg = {class_alg!r} (one of {', '.join(_CLASS_ALGS)})")
-    Ys = list(Ys)
+    uploaded = isinstance(Ys, _Uploaded)
+    if uploaded and class_alg == "lower_bound":
+        refuse("lower_bound takes a list of matrices (it uploads them for two bases of different H)")
+    if not uploaded:
+        Ys = list(Ys)
     if class_alg == "lower_bound":
         if type(res0) is not vbmf_sparse_parameters or not 0 < int(res0.H1) < int(res0.H):
             refuse("lower_bound needs res0 to be a vbmf_sparse_parameters with 0 < H1 < H (factorize_bag)")
@@ -2301,20 +2313,20 @@ def classify_batch(res0, res1, Ys, class_alg, threshold=1e-1, niter=None):
     if int(res0.H) != int(res1.H):
         refuse(f"the two models have different H ({res0.H}, {res1.H}): they cannot share one upload")
     H = int(res0.H)
-    L, Ms = _batch_shapes(Ys, H, refuse)
-    bags = Bags(Ys, H) if basic else SparseBags(Ys, H)
-    try:
+    cls = Bags if basic else SparseBags
+    L, Ms = _bag_shapes(Ys, H, cls, refuse)
+    # (copy_vbmf_params reads only the shape of Y: stand-ins for an upload's bags, as BagPool.shapes gives them)
+    like = [np.broadcast_to(np.float64(0.0), (L, m)) for m in Ms] if uploaded else Ys
+    with _on_device(Ys, H, cls) as bags:
         errs = []
         for res in (res0, res1):
-            ps = [_one_set(fn, copy_vbmf_params(Y, res)) for Y in Ys]
+            ps = [_one_set(fn, copy_vbmf_params(Y, res)) for Y in like]
             if basic:
                 vbls_batch_(bags, ps, 150 if niter is None else int(niter))
             else:
                 vbls_sparse_batch_(bags, ps, 20 if niter is None else int(niter), full_cov=True)
             # the batched fit has just checked these sets and left this model's basis as the context's state
             errs.append(np.sqrt(bags.ctx.bag_residuals(bags.col_off, _stacked_A(ps))))
-    finally:
-        bags.close()
     err0, err1 = errs
     if basic:
         return (err0 > err1).astype(np.int64), err0, err1                # :487-491
@@ -2405,8 +2417,8 @@ def classify_bags(res0, res1, Ys, class_alg="ols", threshold=1e-1, niter=None):
                      bag by M_b (H - H1) < 1600; err0 = norm(Y - YHat) of the truncated basis' fit, err1 of the whole basis' fit,
                      label 0 where |(err0 - err1)/err0| < threshold (:493-501)
       "vbls", "dual", "lower_bound"   classify_batch, unchanged
-    Ys: a list of L x M_b arrays; for "ols" / "rls" also an uploaded Bags / SparseBags.  niter overrides the iteration count of the
-    iterating classifiers."""
+    Ys: a list of L x M_b arrays; for "ols" / "rls" also an uploaded Bags / SparseBags, for "vbls" an uploaded Bags and for "dual" an
+    uploaded SparseBags of the models' H.  niter overrides the iteration count of the iterating classifiers."""
     fn = "classify_bags"
     refuse = _ls_refuser(fn)
     if class_alg in _CLASS_ALGS:
@@ -2467,11 +2479,104 @@ test_classification_batch.__test__ = False        # (the reference's name; not a
 
 
 # =================================================================================================
+# vbls! for a list of (bag, model) jobs, every model with its own basis, in one device call -- what classify's "dual" branch
+# (examples/mil_util.jl:515-530) runs per bag and model; include/vbmf_hip.h: vbmf_sparse_fixed_basis_jobs
+# =================================================================================================
+_JOBS_MAX_H = 32
+_JOBS_KINDS = (vbmf_sparse_parameters, vbmf_dual_parameters)
+
+
+def _jobs_refuser(fn):
+    def refuse(why):
+        raise ValueError(f"{fn}: {why}; run such jobs one at a time with vbls_")
+    return refuse
+
+
+def _jobs_model(fn, res, L, H, name, refuse):
+    """One trained set as the arrays of one model of Context.sparse_fixed_basis_jobs, checked on the host.  The start values are
+    copy_vbmf_params': vbmf_sparse_init / vbmf_dual_init with their default ca = 1 and sigma = 1 (_ard_init: CA = ca ones, sigmaHat =
+    sigma)."""
+    if isinstance(res, vbmf_trial_parameters):
+        _score_refuser(fn)(_TRIAL_TWO_SETS)
+    if type(res) not in _JOBS_KINDS:
+        refuse(f"{name} is a {type(res).__name__} (vbmf_sparse_parameters or vbmf_dual_parameters only)")
+    if int(res.H) != H:
+        refuse(f"{name} has H = {res.H} beside H = {H} (one H per call)")
+    B, SB = np.asarray(res.BHat, dtype=np.float64), np.asarray(res.SigmaB, dtype=np.float64)
+    if B.shape != (L, H) or SB.shape != (H, H):
+        refuse(f"{name}: BHat is {B.shape} and SigmaB {SB.shape}, the bags have L = {L} rows and H = {H}")
+    al, b0 = _sbatch_priors(_MODELS[type(res)], res, H)
+    if not all(np.all(np.isfinite(v)) for v in (B, SB, al, b0, res.eta0, res.zeta0)):
+        refuse(f"{name} has a BHat, SigmaB, hyper-prior, eta0 or zeta0 that is not finite")
+    return dict(BHat=B, SigmaB=SB, alpha=al, beta0=b0, eta0=float(res.eta0), zeta0=float(res.zeta0), sigma0=1.0, ca0=1.0)
+
+
+def _jobs_bags(fn, Ys, refuse):
+    """(L, [M_b]) of what a jobs call runs on, checked on the host: a BagPool, an upload or a list of matrices"""
+    if isinstance(Ys, BagPool):
+        if getattr(Ys, "_closed", True):
+            refuse("the pool is closed")
+        return Ys.L, Ys.Ms
+    if isinstance(Ys, _Uploaded):
+        return Ys.L, Ys.Ms
+    return _batch_shapes(Ys, 1, refuse)
+
+
+def _jobs_run(Ys, H, mods, job_bag, job_model, niter, full_cov):
+    """The one device call: on the pool's own context, on the upload's, or on a Bags of rank 1 opened for the list and closed after"""
+    if isinstance(Ys, BagPool):
+        return Ys.ctx.sparse_fixed_basis_jobs(Ys.col_off, H, mods, job_bag, job_model, int(niter), full_cov=full_cov)
+    with _on_device(Ys, 1, Bags) as bags:
+        return bags.ctx.sparse_fixed_basis_jobs(bags.col_off, H, mods, job_bag, job_model, int(niter), full_cov=full_cov)
+
+
+def vbls_sparse_jobs_(Ys, models, job_bag, job_model, niter, full_cov=False):
+    """vbls! of the ARD-sparse models for a list of (bag, model) jobs in ONE device call: job j does what
+    vbls_(Ys[job_bag[j]], copy_vbmf_params(Ys[job_bag[j]], models[job_model[j]]), niter, full_cov=full_cov) does
+    (examples/mil_util.jl:187-197), every model with its own fp64 basis.
+    Ys: a BagPool (the call runs on the pool's own context: no select, no gather, no new context), an uploaded Bags / SparseBags of
+    any rank, or a list of L x M_b matrices.  models: trained vbmf_sparse_parameters / vbmf_dual_parameters, all of one H <= 32.  Jobs
+    may come in any order and repeat.  Returns (sets, r2, status): per job the parameter set copy_vbmf_params gives for that bag,
+    filled as vbls_sparse_batch_ fills it; r2[j] = norm(Y_b - BHat*AHat')^2 formed entry by entry on the device; status[j] = 1 for a
+    job that met a non-finite precision or a bad pivot (NaN in its fields and r2; the other jobs are computed)."""
+    fn = "vbls_sparse_jobs_"
+    refuse = _jobs_refuser(fn)
+    models = list(models)
+    if not models:
+        refuse("no models")
+    if isinstance(models[0], vbmf_trial_parameters):
+        _score_refuser(fn)(_TRIAL_TWO_SETS)
+    H = int(getattr(models[0], "H", 0))
+    if H > _JOBS_MAX_H:
+        refuse(f"H = {H} > {_JOBS_MAX_H}")
+    if int(niter) < 1:
+        refuse(f"niter = {niter} < 1")
+    L, Ms = _jobs_bags(fn, Ys, refuse)
+    mods = [_jobs_model(fn, res, L, H, f"model {k}", refuse) for k, res in enumerate(models)]
+    job_bag, job_model = [int(b) for b in job_bag], [int(k) for k in job_model]
+    if len(job_bag) != len(job_model) or not job_bag:
+        refuse(f"{len(job_bag)} job bags and {len(job_model)} job models (as many of each, at least one)")
+    for j, (b, k) in enumerate(zip(job_bag, job_model)):
+        if not 0 <= b < len(Ms):
+            refuse(f"job {j}: bag {b} outside 0..{len(Ms) - 1}")
+        if not 0 <= k < len(models):
+            refuse(f"job {j}: model {k} outside 0..{len(models) - 1}")
+    r = _jobs_run(Ys, H, mods, job_bag, job_model, niter, full_cov)
+    sets = []
+    for j, (b, k) in enumerate(zip(job_bag, job_model)):
+        p = copy_vbmf_params(np.broadcast_to(np.float64(0.0), (L, Ms[b])), models[k])
+        _vbls_filled(p, _MODELS[type(p)], r, j, int(r["off"][j]))
+        sets.append(p)
+    return sets, r["r2"], r["status"]
+
+
+# =================================================================================================
 # Every fold's test bags against its own models in one device call -- test_classification (examples/mil_util.jl:558-587) as
 # validate_with_cvs (:627-648), validate (:594-620) and validate_dataset (:670-788) run it per fold, p_known and repetition;
-# include/vbmf_hip.h: vbmf_bag_least_squares_jobs
+# include/vbmf_hip.h: vbmf_bag_least_squares_jobs ("ols", "rls"), vbmf_sparse_fixed_basis_jobs ("dual")
 # =================================================================================================
 _FOLD_LAMS = {"ols": 0.0, "rls": 1e-2}                                   # :459, :466
+_FOLD_ALGS = tuple(_FOLD_LAMS) + ("dual",)
 
 
 def _untrained(pair):
@@ -2508,10 +2613,11 @@ def _fold_ids(fn, tests, nb):
 
 
 def _fold_alg(fn, class_alg):
-    if class_alg not in _FOLD_LAMS:
-        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols' or 'rls'; the other classifiers keep one basis per context: run them per "
-                        f"fold with classify_bags)")
-    return _FOLD_LAMS[class_alg]
+    """lambda of the least-squares classifiers, None for 'dual'"""
+    if class_alg not in _FOLD_ALGS:
+        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols', 'rls' or 'dual'; 'vbls' runs the basic model on one basis per context, "
+                        f"'lower_bound' and 'min_err' two bases of different H per bag: run them per fold with classify_bags)")
+    return _FOLD_LAMS.get(class_alg)
 
 
 def _fold_labels(fn, labels, nb):
@@ -2523,8 +2629,8 @@ def _fold_labels(fn, labels, nb):
     return labels.astype(np.int64)
 
 
-def classify_folds(models, tests, Ys, class_alg="ols"):
-    """classify (examples/mil_util.jl:453-535) with class_alg "ols" or "rls" for every fold of a validation run in ONE device call:
+def classify_folds(models, tests, Ys, class_alg="ols", niter=None):
+    """classify (examples/mil_util.jl:453-535) with class_alg "ols", "rls" or "dual" for every fold of a validation run in ONE device call:
     fold f's test bags tests[f] (bag indices into Ys) against its own pair models[f] = (res0, res1).  Any objects with a BHat serve as
     models, of the same or different H <= 64; (0, 0) -- what train_folds returns for a fold it could not train -- is accepted.
     Ys: a BagPool (the indices are pool bag ids and the call runs on the pool's own context: no select, no gather, no new context), an
@@ -2536,8 +2642,14 @@ def classify_folds(models, tests, Ys, class_alg="ols"):
     empty arrays for a fold with no test bags.
     A fold one of whose bases has a B'B + lambda I that is not positive definite (a rank-deficient basis at "ols") raises VbmfError
     naming the fold, after the other folds have been computed (the exception's .results holds them, None in that fold's place):
-    "rls" is the classifier for such bases, as the reference says (:463-464).  The iterating classifiers ("vbls", "dual",
-    "lower_bound", "min_err") keep one basis per context: classify_bags per fold."""
+    "rls" is the classifier for such bases, as the reference says (:463-464).
+    "dual" (:515-530): the pairs are vbmf_sparse_parameters or vbmf_dual_parameters sets, the two of a fold of one type and every
+    set of the call of one H <= 32; the call's models are the trained folds' res0, res1 in fold order as above, its jobs (bag, 2 t)
+    and (bag, 2 t + 1) run niter = 20 iterations of vbls! with full_cov = true (niter overrides; the least-squares classifiers do not
+    read it) from what copy_vbmf_params gives (Context.sparse_fixed_basis_jobs); err = sqrt(r2) / (L M_b), label 0 where
+    err0 < err1.  A fold with a job that met a non-finite precision or a bad pivot raises VbmfError naming the fold after the others
+    have been computed, with .results as above.
+    "vbls", "lower_bound" and "min_err" stay per fold: classify_bags."""
     fn = "classify_folds"
     refuse = _ls_refuser(fn)
     lam = _fold_alg(fn, class_alg)
@@ -2546,6 +2658,8 @@ def classify_folds(models, tests, Ys, class_alg="ols"):
         refuse(f"{len(models)} models but {len(tests)} test lists")
     L, nb = _folds_bags(fn, Ys)
     ids = _fold_ids(fn, tests, nb)
+    if class_alg == "dual":
+        return _classify_folds_dual(fn, models, ids, Ys, L, 20 if niter is None else int(niter))
     bases, trained = [], []
     for f, pair in enumerate(models):
         if _untrained(pair):
@@ -2595,10 +2709,71 @@ def classify_folds(models, tests, Ys, class_alg="ols"):
     return out
 
 
-def test_classification_folds(models, tests, Ys, labels, class_alg="ols"):
+def _classify_folds_dual(fn, models, ids, Ys, L, niter):
+    """classify_folds' "dual" branch: the folds' sets as one call's models, two jobs per tested bag"""
+    refuse = _ls_refuser(fn)
+    if niter < 1:
+        refuse(f"niter = {niter} < 1")
+    Ms = Ys.Ms if isinstance(Ys, (BagPool, _Uploaded)) else [int(np.shape(Y)[1]) for Y in Ys]
+    mods, trained, H = [], [], None
+    for f, pair in enumerate(models):
+        if _untrained(pair):
+            continue
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            refuse(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
+        if any(isinstance(r, vbmf_trial_parameters) for r in pair):
+            _score_refuser(fn)(f"fold {f}: " + _TRIAL_TWO_SETS)
+        for k, r in enumerate(pair):
+            if type(r) not in _JOBS_KINDS:
+                refuse(f"fold {f}: res{k} is a {type(r).__name__} (class_alg = 'dual' takes vbmf_sparse_parameters or "
+                       f"vbmf_dual_parameters sets)")
+        if type(pair[0]) is not type(pair[1]) or int(pair[0].H) != int(pair[1].H):
+            refuse(f"fold {f}: res0 is a {type(pair[0]).__name__} with H = {pair[0].H}, res1 a {type(pair[1]).__name__} with "
+                   f"H = {pair[1].H} (one type and one H per fold)")
+        H = int(pair[0].H) if H is None else H
+        if H > _JOBS_MAX_H:
+            refuse(f"fold {f}: H = {H} > {_JOBS_MAX_H}")
+        mods += [_jobs_model(fn, r, L, H, f"fold {f}: res{k}", refuse) for k, r in enumerate(pair)]
+        trained.append(f)
+    job_bag, job_model, where = [], [], {}
+    for t, f in enumerate(trained):
+        n = len(ids[f])
+        if n:
+            where[f] = len(job_bag)
+            job_bag += ids[f] + ids[f]
+            job_model += [2 * t] * n + [2 * t + 1] * n
+    out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
+    if not job_bag:
+        return out
+    r = _jobs_run(Ys, H, mods, job_bag, job_model, niter, True)
+    r2, status = r["r2"], r["status"]
+    bad = []
+    for f in trained:
+        if f not in where:
+            continue
+        n, j0 = len(ids[f]), where[f]
+        st = np.asarray(status[j0:j0 + 2 * n])
+        if st.any():
+            j = int(np.flatnonzero(st)[0])
+            bad.append((f, j // n, ids[f][j % n]))
+            out[f] = None
+            continue
+        scale = L * np.asarray([Ms[b] for b in ids[f]], dtype=np.float64)
+        err0, err1 = np.sqrt(r2[j0:j0 + n]) / scale, np.sqrt(r2[j0 + n:j0 + 2 * n]) / scale      # :523-524
+        out[f] = (np.where(err0 < err1, 0, 1).astype(np.int64), err0, err1)                     # :526-530
+    if bad:
+        f, k, b = bad[0]
+        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against res{k} met a precision that is not finite or a "
+                                             f"pivot that is not positive and finite")
+        e.results = out
+        raise e
+    return out
+
+
+def test_classification_folds(models, tests, Ys, labels, class_alg="ols", niter=None):
     """test_classification (examples/mil_util.jl:558-587) of every fold in one device call (classify_folds): a list with
     (mer, eer, fp, fn, n0, n1) per fold, counted as test_classification_batch counts, from the fold's estimated labels and
-    labels[tests[f]].  labels: 0 / 1, one per bag of Ys.  A (0, 0) fold gives (-1.0,) * 6 (:612-614)."""
+    labels[tests[f]].  labels: 0 / 1, one per bag of Ys.  A (0, 0) fold gives (-1.0,) * 6 (:612-614).  niter: classify_folds'."""
     fn = "test_classification_folds"
     _fold_alg(fn, class_alg)
     models, tests = list(models), list(tests)
@@ -2608,7 +2783,7 @@ def test_classification_folds(models, tests, Ys, labels, class_alg="ols"):
     labels = _fold_labels(fn, labels, nb)
     ids = _fold_ids(fn, tests, nb)
     out = []
-    for t, r in zip(ids, classify_folds(models, ids, Ys, class_alg)):
+    for t, r in zip(ids, classify_folds(models, ids, Ys, class_alg, **({} if niter is None else {"niter": niter}))):
         if r is None:
             out.append((-1.0,) * 6)
         else:
@@ -2619,11 +2794,14 @@ def test_classification_folds(models, tests, Ys, labels, class_alg="ols"):
 test_classification_folds.__test__ = False        # (named after the reference's test_classification; not a test)
 
 
-def validate_folds(pool, labels, splits, solver, H, niter, eps=1e-6, class_alg="ols", rng=None, form="stream", slice_cols=None):
+def validate_folds(pool, labels, splits, solver, H, niter, eps=1e-6, class_alg="ols", rng=None, form="stream", slice_cols=None, H1=1,
+                   diag_var=False, nstarts=10):
     """validate_with_cvs (examples/mil_util.jl:627-648) over all splits = [(train_ids, test_ids), ...] of a BagPool in two device
     calls: one train_folds(..., pool=pool) on the folds' training groups -- the train_ids with label 0 and those with label 1, in the
     order given (get_matrices, :46) -- and one test_classification_folds on the test_ids.  labels: 0 / 1, one per bag of the pool;
-    solver, H, niter, eps, rng, form, slice_cols: train_folds'; class_alg: "ols" or "rls".  Returns the list of
+    solver, H, niter, eps, rng, form, slice_cols: train_folds'; class_alg: "ols", "rls" or "dual".  With "dual" the third branch of
+    validate_with_cvs (:633-634) runs instead: train_dual_folds(folds, H, H - H1, niter, eps, diag_var=diag_var, nstarts=nstarts,
+    pool=pool) trains and solver is not read; H1, diag_var and nstarts are read by that branch only.  Returns the list of
     (mer, eer, fp, fn, n0, n1) per split, (-1.0,) * 6 for a split with an empty class."""
     fn = "validate_folds"
     refuse = _ls_refuser(fn)
@@ -2640,7 +2818,11 @@ def validate_folds(pool, labels, splits, solver, H, niter, eps=1e-6, class_alg="
     train = _fold_ids(fn, [s[0] for s in splits], nb)
     tests = _fold_ids(fn, [s[1] for s in splits], nb)
     folds = [([b for b in t if labels[b] == 0], [b for b in t if labels[b] == 1]) for t in train]
-    models = train_folds(folds, solver, H, niter, eps=eps, rng=rng, form=form, slice_cols=slice_cols, pool=pool)
+    if class_alg == "dual":
+        models = train_dual_folds(folds, H, int(H) - int(H1), niter, eps=eps, diag_var=diag_var, nstarts=nstarts, rng=rng, form=form,
+                                  slice_cols=slice_cols, pool=pool)
+    else:
+        models = train_folds(folds, solver, H, niter, eps=eps, rng=rng, form=form, slice_cols=slice_cols, pool=pool)
     return test_classification_folds(models, tests, pool, labels, class_alg)
 
 

@@ -104,6 +104,7 @@ SYMBOLS = [
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
     "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_bag_least_squares_jobs", "vbmf_set_gram_form",
+    "vbmf_sparse_fixed_basis_jobs", "vbmf_debug_vbls_jobs_lds_cols",
     "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
@@ -216,6 +217,9 @@ def lib():
     L.vbmf_bag_least_squares.argtypes = [vp, i64, C.POINTER(i64), dp, i64, i64, C.c_double, dp, i64, dp]
     L.vbmf_bag_least_squares_jobs.argtypes = [vp, i64, C.POINTER(i64), i64, C.POINTER(i64), dp, dp, i64, C.POINTER(i64), C.POINTER(i64), dp, dp,
                                               C.POINTER(i64)]
+    L.vbmf_sparse_fixed_basis_jobs.argtypes = [vp, i64, C.POINTER(i64), i64, i64, i32, i64, dp, dp, dp, dp, dp, dp, dp, dp, i64,
+                                               C.POINTER(i64), C.POINTER(i64), dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(i64)]
+    L.vbmf_debug_vbls_jobs_lds_cols.argtypes = [i64, i32]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
     L.vbmf_set_gram_form.argtypes = [vp, i32]
     L.vbmf_sparse_set_SigmaA.argtypes = [vp, dp]
@@ -906,6 +910,46 @@ class Context:
             Xs = [X[xoff[j]:xoff[j + 1]].reshape(shapes[j], order="F") for j in range(jb.size)]
         return Xs, r2, status
 
+    def sparse_fixed_basis_jobs(self, col_off, H, models, job_bag, job_model, niter, full_cov=False):
+        """vbls! of the ARD families for a list of (bag, model) jobs in one device call (vbmf_sparse_fixed_basis_jobs): models[k] is a
+        dict of BHat (L, H) and SigmaB (H, H) fp64, alpha and beta0 (H,), eta0, zeta0, sigma0, ca0 (scalars), all of the one H <= 32;
+        job j runs bag job_bag[j] of col_off against model job_model[j] for niter iterations from sigmaHat = sigma0, CA = ca0.  Only
+        this context's Y is read.  Returns dict(r2, sigmaHat, zeta (njobs,), status (njobs,) with 1 for a failed job (NaN in its
+        outputs, the others are computed), SigmaA (njobs, H, H), CA, beta, diagSigmaATVec, ATVecHat: the jobs' M_b*H-long blocks in
+        vec(A') order one after the other, and off (njobs + 1,): job j's block is [off[j] : off[j + 1]])."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        H = int(H)
+        nk = len(models)
+        for m in models:
+            if np.shape(m["BHat"]) != (self.L, H) or np.shape(m["SigmaB"]) != (H, H) or np.size(m["alpha"]) != H or np.size(m["beta0"]) != H:
+                raise ValueError(f"every model needs BHat ({self.L}, {H}), SigmaB ({H}, {H}), alpha and beta0 ({H},)")
+
+        def pack(key, order="C"):
+            if not nk:
+                return np.empty(0)
+            return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
+        B, SB, al, b0 = pack("BHat", "F"), pack("SigmaB", "F"), pack("alpha"), pack("beta0")
+        e0, z0, s0, c0 = pack("eta0"), pack("zeta0"), pack("sigma0"), pack("ca0")
+        jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
+        jk = np.ascontiguousarray(job_model, dtype=np.int64).reshape(-1)
+        if jb.size != jk.size:
+            raise ValueError(f"{jb.size} job bags but {jk.size} job models")
+        nj = jb.size
+        ok = (jb >= 0) & (jb < nb)                                   # (a job out of range is the library's to refuse: no block for it)
+        widths = np.where(ok, off[np.clip(jb, 0, max(nb - 1, 0)) + 1] - off[np.clip(jb, 0, max(nb - 1, 0))], 0) if nb >= 1 else np.zeros(nj, np.int64)
+        boff = np.concatenate([[0], np.cumsum(widths * H)]).astype(np.int64)
+        n = max(int(boff[-1]), 1)
+        r2, sg, zeta = np.empty(nj), np.empty(nj), np.empty(nj)
+        A, dS, CA, beta = np.empty(n), np.empty(n), np.empty(n), np.empty(n)
+        SA = np.empty((nj, H, H))
+        status = np.zeros(nj, dtype=np.int64)
+        self._chk(self._lib.vbmf_sparse_fixed_basis_jobs(self._h, nb, _i64ptr(off), H, int(niter), int(bool(full_cov)), nk, _dptr(B), _dptr(SB),
+                                                         _dptr(al), _dptr(b0), _dptr(e0), _dptr(z0), _dptr(s0), _dptr(c0), nj, _i64ptr(jb),
+                                                         _i64ptr(jk), _dptr(r2), _dptr(A), _dptr(dS), _dptr(CA), _dptr(beta), _dptr(SA),
+                                                         _dptr(sg), _dptr(zeta), _i64ptr(status)))
+        return dict(r2=r2, sigmaHat=sg, zeta=zeta, status=status, SigmaA=SA, CA=CA, beta=beta, diagSigmaATVec=dS, ATVecHat=A, off=boff)
+
     def sparse_lower_bound_batched(self, col_off, ATVecHat, diagSigmaATVec, CA, beta, SigmaA, sigmaHat, zeta, eta, eta0, zeta0,
                                    a_pri, b_pri, a_post, trim=None, clamp=True, grouped=False):
         """lowerBound (trim None) / lowerBoundTrimmed of every bag (vbmf_sparse_lower_bound_batched): BHat, SigmaB, CB, delta, gamma0,
@@ -1051,3 +1095,8 @@ class Context:
 
     def debug_set(self, what, value):
         self._chk(self._lib.vbmf_debug_set(self._h, int(what), int(value)))
+
+
+def vbls_jobs_lds_cols(H, full_cov=False):
+    """The widest bag whose job keeps its state in LDS in Context.sparse_fixed_basis_jobs (vbmf_debug_vbls_jobs_lds_cols)."""
+    return int(lib().vbmf_debug_vbls_jobs_lds_cols(int(H), int(bool(full_cov))))

@@ -1,5 +1,5 @@
 // host_bags.hpp -- the many-bags entries of the C ABI (batched vbls! of the basic and the sparse models, per-bag residuals, least
-// squares and lower bounds, many whole fits of the sparse and of the basic model, the bags' Y Y') and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
+// squares and lower bounds, vbls! for (bag, model) jobs, many whole fits of the sparse and of the basic model, the bags' Y Y') and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
 // helpers it uses, never on its own.  The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.
 //   bags_check     what every entry refuses about (nbags, col_off) and a sharded context; the widest bag, the residual slices
 //   bags_reserve   ONE device scratch buffer (c->bags), grown on demand.  Every entry synchronises before it returns, so no two layouts
@@ -480,6 +480,145 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
                      (long long)job_basis[j]);
     }
     return VBMF_OK;
+}
+
+// vbls! of the ARD families (examples/mil_util.jl:187-197) for a list of (bag, model) jobs, every model with its own fp64 basis, and
+// each job's norm(Y - BHat*AHat')^2 (:518-521) in the same launch: the "dual" classifier of :515-530 for every fold of
+// validate_with_cvs at once.  The context supplies Y only.  Two launches (per model, per job) and one synchronising read-back,
+// whatever nmodels and njobs are (vbls_jobs_kernels.hpp).
+int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t H, int64_t niter, int full_cov,
+                                 int64_t nmodels, const double* BHat, const double* SigmaB, const double* alpha, const double* beta0,
+                                 const double* eta0, const double* zeta0, const double* sigma0, const double* ca0, int64_t njobs,
+                                 const int64_t* job_bag, const int64_t* job_model, double* r2, double* ATVecHat, double* diagSigmaATVec,
+                                 double* CA, double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_fixed_basis_jobs";
+    if (H < 1 || H > VJOBS_MAX_H) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for 1 <= H <= %d)", fn, (long long)H, VJOBS_MAX_H);
+    if (nmodels < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nmodels must be >= 1", fn);
+    if (njobs < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (!BHat || !SigmaB || !alpha || !beta0 || !eta0 || !zeta0 || !sigma0 || !ca0 || !job_bag || !job_model || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
+    if (!r2 && !ATVecHat) FAIL(c, VBMF_ERR_INVALID, "%s: r2 and ATVecHat are both NULL", fn);
+    // what one grid holds: a launch is kept to 2^32 - 1 threads in all, so to LS_MAX_GROUPS workgroups of 256
+    if (njobs > LS_MAX_GROUPS || nmodels > LS_MAX_GROUPS)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs, %lld models (more than the %lld workgroups of one grid)", fn, (long long)njobs,
+             (long long)nmodels, (long long)LS_MAX_GROUPS);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nbags, col_off, bd));
+    const bool full = full_cov != 0, compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
+    const int NBK = nb_tier(H);
+    const int64_t L = c->L, nb = nbags, nk = nmodels, nj = njobs, h2 = H * H, LH = L * H;
+    int64_t ncols = 0, lds_cols = 0;                              // the jobs' columns; the widest job that keeps its state in LDS
+    bool spill = false;
+    for (int64_t j = 0; j < nj; ++j) {
+        const int64_t b = job_bag[j], k = job_model[j];
+        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
+        if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_model[%lld] = %lld outside 0..nmodels-1", fn, (long long)j, (long long)k);
+        const int64_t Mb = col_off[b + 1] - col_off[b];
+        if (!full && compat && Mb < 2)
+            FAIL(c, VBMF_ERR_INVALID, "%s: job %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)j);
+        ncols += Mb;                                              // (at most 2^24 terms of at most 2^60 / 8: no overflow)
+        if (vjobs_in_lds(full, NBK, (int)H, Mb)) lds_cols = std::max(lds_cols, Mb);
+        else spill = true;
+    }
+    auto finite = [](const double* v, int64_t n) {
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(v[i])) return i;
+        return (int64_t)-1;
+    };
+    const struct { const char* name; const double* v; int64_t per; } ins[] = {
+        {"BHat", BHat, LH}, {"SigmaB", SigmaB, h2}, {"alpha", alpha, H}, {"beta0", beta0, H},
+        {"eta0", eta0, 1}, {"zeta0", zeta0, 1}, {"sigma0", sigma0, 1}, {"ca0", ca0, 1}};
+    for (const auto& in : ins) {
+        const int64_t bad = finite(in.v, in.per * nk);
+        if (bad >= 0) FAIL(c, VBMF_ERR_INVALID, "%s: %s of model %lld is not finite (entry %lld)", fn, in.name, (long long)(bad / in.per), (long long)(bad % in.per));
+    }
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
+    // the upload, one block: [col_off nb + 1 | job_bag | job_model | job_off (nj each) (int64) | alpha | beta0 (nk H each) | eta0 | zeta0 |
+    //                         sigma0 | ca0 (nk each) | the bases, column-major L x H | SigmaB (nk H^2)]
+    const int64_t SMH = ncols * H;
+    const int64_t u_bag = nb + 1, u_mod = u_bag + nj, u_off = u_mod + nj, u_al = u_off + nj, u_b0 = u_al + nk * H, u_eta = u_b0 + nk * H,
+                  u_z0 = u_eta + nk, u_sig = u_z0 + nk, u_ca0 = u_sig + nk, u_b = u_ca0 + nk, u_sb = u_b + nk * LH, n_up = u_sb + nk * h2;
+    // behind it: [Bt nk L H | G nk H^2 | gd | sd (nk H) | r2 | sigma | zeta | status (nj each) | SigmaA nj H^2 | CA | A | dS | beta (the
+    //             jobs' M_b H-long blocks in job order) | P of the jobs whose state is not in LDS]; [r2 .. beta] is the read-back
+    const int64_t o_bt = n_up, o_g = o_bt + nk * LH, o_gd = o_g + nk * h2, o_sd = o_gd + nk * H, o_r2 = o_sd + nk * H, o_sig = o_r2 + nj,
+                  o_zeta = o_sig + nj, o_st = o_zeta + nj, o_sa = o_st + nj, o_ca = o_sa + nj * h2, o_a = o_ca + SMH, o_ds = o_a + SMH,
+                  o_be = o_ds + SMH, o_p = o_be + SMH, total = o_p + (spill ? SMH : 0);
+    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
+    try {
+        up.resize((size_t)n_up);
+        res.resize((size_t)(o_p - o_r2));
+    } catch (const std::bad_alloc&) {
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of models, job tables and results", fn, (long long)((n_up + o_p - o_r2) * 8));
+    }
+    long long* ui = reinterpret_cast<long long*>(up.data());
+    for (int64_t b = 0; b <= nb; ++b) ui[b] = col_off[b];
+    for (int64_t j = 0, off = 0; j < nj; ++j) {
+        ui[u_bag + j] = job_bag[j];
+        ui[u_mod + j] = job_model[j];
+        ui[u_off + j] = off;
+        off += col_off[job_bag[j] + 1] - col_off[job_bag[j]];
+    }
+    memcpy(up.data() + u_al, alpha, (size_t)(nk * H) * 8);
+    memcpy(up.data() + u_b0, beta0, (size_t)(nk * H) * 8);
+    memcpy(up.data() + u_eta, eta0, (size_t)nk * 8);
+    memcpy(up.data() + u_z0, zeta0, (size_t)nk * 8);
+    memcpy(up.data() + u_sig, sigma0, (size_t)nk * 8);
+    memcpy(up.data() + u_ca0, ca0, (size_t)nk * 8);
+    memcpy(up.data() + u_b, BHat, (size_t)(nk * LH) * 8);
+    memcpy(up.data() + u_sb, SigmaB, (size_t)(nk * h2) * 8);
+    auto run = [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->o.device));
+        double* d = nullptr;
+        TRY(bags_reserve(c, total, &d));
+        HIPCHK(c, hipMemcpyAsync(d, up.data(), (size_t)n_up * 8, hipMemcpyHostToDevice, c->stream));
+        const long long* di = reinterpret_cast<const long long*>(d);
+        hipLaunchKernelGGL(vbls_jobs_model_kernel, dim3((unsigned)nk), dim3(SCORE_THREADS), 0, c->stream, d + u_b, d + u_sb, (long long)L,
+                           (int)H, d + o_bt, d + o_g, d + o_gd, d + o_sd);
+        HIPCHK(c, hipGetLastError());
+        const VjobsArgs a{c->Y2, c->d2.KS, (long long)L, di, di + u_bag, di + u_mod, di + u_off, (int)H, (int)niter, compat ? 1 : 0,
+                          d + o_bt, d + o_g, d + o_gd, d + o_sd, d + u_al, d + u_b0, d + u_eta, d + u_z0, d + u_sig, d + u_ca0,
+                          spill ? d + o_p : nullptr, d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_sa, d + o_sig, d + o_zeta, d + o_r2,
+                          reinterpret_cast<long long*>(d + o_st)};
+        const size_t lds = (size_t)(vjobs_fixed_doubles(full, NBK, (int)H) + 4 * lds_cols * H) * 8;
+        dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+            dispatch<1, 2>(NBK, [&](auto nbk) {
+                dispatch<0, 1>(full ? 1 : 0, [&](auto fc) {
+                    hipLaunchKernelGGL((vbls_jobs_kernel<decltype(ym)::value, decltype(nbk)::value, decltype(fc)::value != 0>), dim3((unsigned)nj),
+                                       dim3(SBATCH_THREADS), lds, c->stream, a);
+                });
+            });
+        });
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
+        return VBMF_OK;
+    };
+    const int rc = run();
+    if (rc != VBMF_OK) {
+        hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    auto at = [&](int64_t o_x) { return res.data() + (o_x - o_r2); };   // block x of the read-back
+    if (r2) memcpy(r2, at(o_r2), (size_t)nj * 8);
+    if (sigmaHat) memcpy(sigmaHat, at(o_sig), (size_t)nj * 8);
+    if (zeta) memcpy(zeta, at(o_zeta), (size_t)nj * 8);
+    memcpy(status, at(o_st), (size_t)nj * 8);
+    if (SigmaA) memcpy(SigmaA, at(o_sa), (size_t)(nj * h2) * 8);   // symmetric: row- and column-major alike
+    if (CA) memcpy(CA, at(o_ca), (size_t)SMH * 8);
+    if (ATVecHat) memcpy(ATVecHat, at(o_a), (size_t)SMH * 8);
+    if (diagSigmaATVec) memcpy(diagSigmaATVec, at(o_ds), (size_t)SMH * 8);
+    if (beta) memcpy(beta, at(o_be), (size_t)SMH * 8);
+    return VBMF_OK;
+}
+
+// the widest bag whose job keeps its state in LDS at this H and form (vjobs_in_lds): the tests place a bag on either side of it
+int vbmf_debug_vbls_jobs_lds_cols(int64_t H, int full_cov) {
+    if (H < 1 || H > VJOBS_MAX_H) return 0;
+    int64_t Mb = 0;
+    while (vjobs_in_lds(full_cov != 0, nb_tier(H), (int)H, Mb + 1)) ++Mb;
+    return (int)Mb;
 }
 
 // lowerBound / lowerBoundTrimmed of every bag (examples/mil_util.jl:502-514 after a batched vbls!)

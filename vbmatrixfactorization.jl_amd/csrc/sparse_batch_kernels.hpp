@@ -14,6 +14,7 @@
 //   updateSigma! (:317-321)  zeta = zeta0 + ||Y_b||^2 / 2 - sum P o A + tr((A'A + SigmaA) G) / 2, sigma = eta / zeta
 // The bag's state (P, CA, A, dS) is fp64: in LDS when it fits (lds_state), else in the bag's own slices of the device buffers.
 // Bags do not align with the 32-column tiles of P: every access goes through the column index.
+// The loop itself is sbatch_iterate, a __device__ function that vbls_jobs_kernel (vbls_jobs_kernels.hpp: many bases, fp64 P) calls too.
 #pragma once
 #include "common.hpp"
 #include "ctrl_kernels.hpp"
@@ -59,36 +60,34 @@ struct SbatchArgs {
     int* err;
 };
 
+// What one workgroup's vbls! loop works on: a bag's state (P, CA, A, dS; LDS or global, M_b x H in vec(A') order), the basis' G, gd, sd
+// (global), updateCA!'s (alpha_h, beta0_h) in al_s / b0_s, and where the last iteration's beta and SigmaA go (nullptr: not wanted).
+// lds_sb: sbatch_fixed_doubles of dynamic LDS; red: 16 doubles, v_s, al_s, b0_s, sa_s: 64 each (static LDS of the calling kernel).
+struct SbatchBody {
+    int H, niter, compat;
+    long long Mb;
+    const double* G; const double* gd; const double* sd;
+    double* Pb; double* CAb; double* Ab; double* dSb;
+    double* beta; double* SA;
+    double eta, zeta0, yy;
+    double* lds_sb; double* red; double* v_s; double* al_s; double* b0_s; double* sa_s;
+};
+
+// The niter iterations of one bag, by the whole workgroup of SBATCH_THREADS: sparse_batch_kernel's loop, shared with vbls_jobs_kernel
+// (vbls_jobs_kernels.hpp).  The caller has filled Pb, CAb, al_s, b0_s (no barrier needed after that: the one below covers it).
+// sig: the start value in, the final one out; bad: raised on a non-finite precision or a bad pivot.
 template <int NBK, bool FULL>
-__global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs g) {
-    extern __shared__ __attribute__((aligned(16))) double lds_sb[];
-    __shared__ double red[16];
-    __shared__ double v_s[64], al_s[64], b0_s[64], sa_s[64];
+__device__ __forceinline__ void sbatch_iterate(const SbatchBody& q, double& sig, double& zeta, int& bad) {
     constexpr int NP = 16 * NBK, LD = NP + 2, NUP = NBK * (NBK + 1) / 2, NW = SBATCH_NW;
-    const int b = blockIdx.x, H = g.H, tid = threadIdx.x;
-    const long long m0 = g.col_off[b], Mb = g.col_off[b + 1] - m0;
-    const long long n = Mb * H, o = m0 * H;
-    const int nfix = sbatch_fixed_doubles(FULL, NBK, H);
-    const bool in_lds = 4 * n <= (long long)g.lds_state;
-    double* Pb = in_lds ? lds_sb + nfix : g.Pd + o;
-    double* CAb = in_lds ? Pb + n : g.ca + o;
-    double* Ab = in_lds ? CAb + n : g.A + o;
-    double* dSb = in_lds ? Ab + n : g.dS + o;
-    for (long long t = tid; t < n; t += SBATCH_THREADS) {
-        const long long m = t / H;
-        const int h = (int)(t - m * H);
-        Pb[t] = (double)g.P[(long long)h * g.ldP + m0 + m];
-        if (in_lds) CAb[t] = g.ca[o + t];
-    }
-    if (tid < H) {
-        al_s[tid] = g.alpha[(long long)b * H + tid];
-        b0_s[tid] = g.beta0[(long long)b * H + tid];
-    }
+    const int H = q.H, tid = threadIdx.x;
+    const long long Mb = q.Mb, n = Mb * H;
+    double* const lds_sb = q.lds_sb;
+    double* const red = q.red;
+    double* const v_s = q.v_s; double* const al_s = q.al_s; double* const b0_s = q.b0_s; double* const sa_s = q.sa_s;
+    double* const Pb = q.Pb; double* const CAb = q.CAb; double* const Ab = q.Ab; double* const dSb = q.dSb;
+    const double eta = q.eta, zeta0 = q.zeta0, yy = q.yy;
     if constexpr (!FULL)
-        for (int t = tid; t < H * H; t += SBATCH_THREADS) lds_sb[t] = g.G[t];
-    const double eta = g.eta[b], zeta0 = g.zeta0[b], yy = g.yy[b];
-    double sig = g.sigma[b], zeta = 0.0;
-    int bad = 0;
+        for (int t = tid; t < H * H; t += SBATCH_THREADS) lds_sb[t] = q.G[t];
     // full_cov: G's upper blocks in the MFMA's C/D layout (zero beyond H), the running sum of this wave's Sigma_m
     const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, q16 = lane >> 4;
@@ -103,21 +102,21 @@ __global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int i = 16 * I + q16 + 4 * r, j = 16 * J + c16;
-                    g0[u][r] = (i < H && j < H) ? g.G[i * H + j] : 0.0;
+                    g0[u][r] = (i < H && j < H) ? q.G[i * H + j] : 0.0;
                 }
     }
     __syncthreads();
-    for (int it = 0; it < g.niter; ++it) {
-        const bool last = it + 1 == g.niter;
+    for (int it = 0; it < q.niter; ++it) {
+        const bool last = it + 1 == q.niter;
         double pa = 0.0, tq = 0.0, tsa = 0.0;          // sum P o A, sum_m a_m' G a_m, tr(SigmaA G): this thread's shares
         if constexpr (!FULL) {
             const double* Gs = lds_sb;
-            if (tid < H) v_s[tid] = sig * g.gd[tid] + g.sd[tid];
+            if (tid < H) v_s[tid] = sig * q.gd[tid] + q.sd[tid];
             __syncthreads();
             for (long long t = tid; t < n; t += SBATCH_THREADS) {
                 const long long m = t / H;
                 const int h = (int)(t - m * H);
-                const long long vi = !g.compat ? h : (t < H ? t : (t - H) / (Mb - 1));   // repeat(v, inner = M_b - 1) after the first H
+                const long long vi = !q.compat ? h : (t < H ? t : (t - H) / (Mb - 1));   // repeat(v, inner = M_b - 1) after the first H
                 const double prec = v_s[vi] + CAb[t];
                 bad |= !isfinite(prec);
                 const double d = 1.0 / prec, p = Pb[t], a = sig * d * p;
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs
                 dSb[t] = d;
                 const double be = b0_s[h] + 0.5 * (a * a + d);
                 CAb[t] = al_s[h] / be;
-                if (last && g.beta) g.beta[o + t] = be;
+                if (last && q.beta) q.beta[t] = be;
                 pa += p * a;
             }
             __syncthreads();
@@ -192,10 +191,10 @@ __global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs
                     dSb[t] = d;
                     const double be = b0_s[lane] + 0.5 * (a * a + d);
                     CAb[t] = al_s[lane] / be;
-                    if (last && g.beta) g.beta[o + t] = be;
+                    if (last && q.beta) q.beta[t] = be;
                     pa += pvec[lane] * a;
                     double s = 0.0;
-                    for (int j = 0; j < H; ++j) s += g.G[lane * H + j] * avec[j];
+                    for (int j = 0; j < H; ++j) s += q.G[lane * H + j] * avec[j];
                     tq += a * s;
                 }
                 {
@@ -222,8 +221,8 @@ __global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs
                 double s = 0.0;
 #pragma unroll
                 for (int ww = 0; ww < NW; ++ww) s += lds_sb[(size_t)ww * NP * LD + lo * LD + hi];
-                tsa += s * g.G[t];
-                if (last && g.SA) g.SA[(long long)b * H * H + t] = s;
+                tsa += s * q.G[t];
+                if (last && q.SA) q.SA[t] = s;
             }
         }
         pa = block_sum(pa, red);                        // (its barriers also end every read of this iteration's LDS)
@@ -231,12 +230,43 @@ __global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs
         tsa = block_sum(tsa, red);
         zeta = zeta0 + 0.5 * yy - pa + 0.5 * (tq + tsa);
         sig = eta / zeta;
-        if (!FULL && last && g.SA)
+        if (!FULL && last && q.SA)
             for (int t = tid; t < H * H; t += SBATCH_THREADS) {
                 const int i = t / H, j = t % H;
-                g.SA[(long long)b * H * H + t] = i == j ? sa_s[i] : 0.0;
+                q.SA[t] = i == j ? sa_s[i] : 0.0;
             }
     }
+}
+
+template <int NBK, bool FULL>
+__global__ __launch_bounds__(SBATCH_THREADS) void sparse_batch_kernel(SbatchArgs g) {
+    extern __shared__ __attribute__((aligned(16))) double lds_sb[];
+    __shared__ double red[16];
+    __shared__ double v_s[64], al_s[64], b0_s[64], sa_s[64];
+    const int b = blockIdx.x, H = g.H, tid = threadIdx.x;
+    const long long m0 = g.col_off[b], Mb = g.col_off[b + 1] - m0;
+    const long long n = Mb * H, o = m0 * H;
+    const int nfix = sbatch_fixed_doubles(FULL, NBK, H);
+    const bool in_lds = 4 * n <= (long long)g.lds_state;
+    double* Pb = in_lds ? lds_sb + nfix : g.Pd + o;
+    double* CAb = in_lds ? Pb + n : g.ca + o;
+    double* Ab = in_lds ? CAb + n : g.A + o;
+    double* dSb = in_lds ? Ab + n : g.dS + o;
+    for (long long t = tid; t < n; t += SBATCH_THREADS) {
+        const long long m = t / H;
+        const int h = (int)(t - m * H);
+        Pb[t] = (double)g.P[(long long)h * g.ldP + m0 + m];
+        if (in_lds) CAb[t] = g.ca[o + t];
+    }
+    if (tid < H) {
+        al_s[tid] = g.alpha[(long long)b * H + tid];
+        b0_s[tid] = g.beta0[(long long)b * H + tid];
+    }
+    double sig = g.sigma[b], zeta = 0.0;
+    int bad = 0;
+    const SbatchBody q{H, g.niter, g.compat, Mb, g.G, g.gd, g.sd, Pb, CAb, Ab, dSb, g.beta ? g.beta + o : nullptr,
+                       g.SA ? g.SA + (long long)b * H * H : nullptr, g.eta[b], g.zeta0[b], g.yy[b], lds_sb, red, v_s, al_s, b0_s, sa_s};
+    sbatch_iterate<NBK, FULL>(q, sig, zeta, bad);
     if (in_lds)
         for (long long t = tid; t < n; t += SBATCH_THREADS) {
             g.ca[o + t] = CAb[t];

@@ -59,6 +59,7 @@
 #include "fit_basic_kernels.hpp"
 #include "fit_basic_gram_kernels.hpp"
 #include "score_kernels.hpp"
+#include "vbls_jobs_kernels.hpp"
 #include "gram_kernels.hpp"
 #include "out_kernels.hpp"
 

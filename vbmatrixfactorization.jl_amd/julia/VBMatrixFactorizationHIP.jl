@@ -14,7 +14,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        vbls!, vbls_batch!, vbmf_batch!, row_gram_batch, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
-       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs,
+       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs, sparse_fixed_basis_jobs,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!, set_Y_gather!
 
@@ -1197,6 +1197,49 @@ function bag_least_squares_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, bases::
         ctx, nb, col_off, nk, Hs, Ball, lams, nj, jb, jk, X, r2, status))
     Xs = [reshape(X[xoff[j]+1:xoff[j+1]], shapes[j]) for j in 1:nj]
     return Xs, r2, status
+end
+
+"""
+    sparse_fixed_basis_jobs(ctx, col_off, H, BHat, SigmaB, alpha, beta0, eta0, zeta0, sigma0, ca0, job_bag, job_model, niter; full_cov)
+
+vbls! of the ARD families (examples/mil_util.jl:187-197) for a list of (bag, model) jobs in ONE device call
+(vbmf_sparse_fixed_basis_jobs) -- the "dual" classifier of examples/mil_util.jl:515-530 for every fold at once.  `ctx` holds every bag
+of the data set side by side (col_off: 0-based offsets); only its Y is read.  Model k: `BHat[k]` (L x H, H <= 32), `SigmaB[k]` (H x H),
+columns k of `alpha` and `beta0` (H x nmodels: updateCA!'s posterior shape and prior rate per column of A), `eta0[k]`, `zeta0[k]` and
+the start values `sigma0[k]`, `ca0[k]`.  Job j runs bag `job_bag[j]` against model `job_model[j]` (both 1-based).  Returns a named
+tuple: r2, sigmaHat, zeta, status (per job; status 1 = a failed job, NaN in its outputs), SigmaA (H x H x njobs), and ATVecHat,
+diagSigmaATVec, CA, beta as one vec(A')-ordered vector per job.
+"""
+function sparse_fixed_basis_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, H::Int, BHat::Vector{Matrix{Float64}},
+                                 SigmaB::Vector{Matrix{Float64}}, alpha::Matrix{Float64}, beta0::Matrix{Float64}, eta0::Vector{Float64},
+                                 zeta0::Vector{Float64}, sigma0::Vector{Float64}, ca0::Vector{Float64},
+                                 job_bag::AbstractVector{<:Integer}, job_model::AbstractVector{<:Integer}, niter::Int;
+                                 full_cov::Bool = false)
+    nb, nk, nj = length(col_off) - 1, length(BHat), length(job_bag)
+    (nk >= 1 && length(SigmaB) == nk && size(alpha) == (H, nk) && size(beta0) == (H, nk) && length(eta0) == nk && length(zeta0) == nk &&
+     length(sigma0) == nk && length(ca0) == nk) || error("sparse_fixed_basis_jobs: every per-model input needs one entry per model, at least one model")
+    (nj >= 1 && length(job_model) == nj) || error("sparse_fixed_basis_jobs: job_bag and job_model must have one entry per job, at least one")
+    L = size(BHat[1], 1)
+    all(k -> size(BHat[k]) == (L, H) && size(SigmaB[k]) == (H, H), 1:nk) || error("sparse_fixed_basis_jobs: every model needs BHat L x H and SigmaB H x H")
+    all(j -> 1 <= job_bag[j] <= nb && 1 <= job_model[j] <= nk, 1:nj) || error("sparse_fixed_basis_jobs: a job names a bag or a model that is not there")
+    Ball = reduce(vcat, [vec(B) for B in BHat])
+    SBall = reduce(vcat, [vec(S) for S in SigmaB])
+    jb, jk = Int64[b - 1 for b in job_bag], Int64[k - 1 for k in job_model]
+    off = Int64[0; cumsum([H * (col_off[b+2] - col_off[b+1]) for b in jb])]
+    r2, sg, zeta = Array{Float64}(undef, nj), Array{Float64}(undef, nj), Array{Float64}(undef, nj)
+    A, dS = Array{Float64}(undef, off[end]), Array{Float64}(undef, off[end])
+    CA, beta = Array{Float64}(undef, off[end]), Array{Float64}(undef, off[end])
+    SA = Array{Float64}(undef, H, H, nj)
+    status = Array{Int64}(undef, nj)
+    chk(ctx, ccall((:vbmf_sparse_fixed_basis_jobs, libvbmf), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Int64, Cint, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        ctx, nb, col_off, H, niter, Cint(full_cov), nk, Ball, SBall, alpha, beta0, eta0, zeta0, sigma0, ca0, nj, jb, jk, r2, A, dS, CA, beta,
+        SA, sg, zeta, status))
+    blocks(v) = [v[off[j]+1:off[j+1]] for j in 1:nj]
+    return (r2 = r2, sigmaHat = sg, zeta = zeta, status = status, SigmaA = SA, ATVecHat = blocks(A), diagSigmaATVec = blocks(dS),
+            CA = blocks(CA), beta = blocks(beta))
 end
 
 "vbmf_dual! -- src/vbmf_dual.jl:455-530 (returns d); est_priors: the hyper-prior fits of :393-434 run on the device"
