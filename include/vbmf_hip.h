@@ -741,6 +741,13 @@ int vbmf_debug_set(vbmf_ctx* ctx, int what, int64_t value);
    quotient; H > 64: Lanczos), and the kernel's time in microseconds.  Overwrites the context's delta-Gram scratch (recomputed by every
    sweep), nothing else. */
 int vbmf_debug_lambda_max(vbmf_ctx* ctx, const double* G, double* lambda_max, double* kernel_us);
+/* test hook for the blocked inverse of the H x H covariance updates (csrc/blk_inverse.hpp): one 256-thread workgroup on the current
+   device sweeps the identity-padded LDS image of the symmetric matrix K (row-major doubles, order 1 <= H <= 128) at the tier H selects
+   (16, 32, 64 or 128 rows), with the four-wave schedule of the control chain (waves = 4) or with one wave of it running the one-wave
+   schedule of the per-column inverses (waves = 1).  out: the n x n image afterwards, n = H rounded up to a multiple of 16, row-major --
+   the upper 16 x 16 blocks hold -inv(K) (identity padding beyond H), the lower blocks are returned as zeros; logdet: log det K from
+   the pivots; bad: != 0 if a pivot was not positive or not finite.  Needs no context. */
+int vbmf_debug_blk_sweep(const double* K, int64_t H, int waves, double* out, double* logdet, int* bad);
 
 #ifdef __cplusplus
 }

@@ -105,7 +105,7 @@ SYMBOLS = [
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
     "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_bag_least_squares_jobs", "vbmf_set_gram_form",
     "vbmf_sparse_fixed_basis_jobs", "vbmf_debug_vbls_jobs_lds_cols",
-    "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather",
+    "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather", "vbmf_debug_blk_sweep",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
 DEBUG_EPI_SPIN_LIMIT, DEBUG_EPI_EXPECT_SKEW, DEBUG_SIGMA_B_PPM, DEBUG_EXACT_LAMBDA = 0, 1, 2, 3
@@ -220,6 +220,7 @@ def lib():
     L.vbmf_sparse_fixed_basis_jobs.argtypes = [vp, i64, C.POINTER(i64), i64, i64, i32, i64, dp, dp, dp, dp, dp, dp, dp, dp, i64,
                                                C.POINTER(i64), C.POINTER(i64), dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(i64)]
     L.vbmf_debug_vbls_jobs_lds_cols.argtypes = [i64, i32]
+    L.vbmf_debug_blk_sweep.argtypes = [dp, i64, i32, dp, dp, C.POINTER(i32)]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
     L.vbmf_set_gram_form.argtypes = [vp, i32]
     L.vbmf_sparse_set_SigmaA.argtypes = [vp, dp]
@@ -1095,6 +1096,22 @@ class Context:
 
     def debug_set(self, what, value):
         self._chk(self._lib.vbmf_debug_set(self._h, int(what), int(value)))
+
+
+def blk_sweep(K, waves=4):
+    """The blocked LDS inverse of the H x H covariance updates on one 256-thread workgroup (vbmf_debug_blk_sweep): K symmetric of order
+    H <= 128, waves = 4 (the control chain's schedule) or 1 (the one-wave schedule).  Returns (image, log det K, bad): the n x n image,
+    n = H rounded up to 16, whose upper 16 x 16 blocks hold -inv(K); lower blocks zero."""
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    H = K.shape[0]
+    assert K.shape == (H, H)
+    n = 16 * ((H + 15) // 16)
+    out = np.empty((n, n), dtype=np.float64)
+    ld, bad = C.c_double(), C.c_int32()
+    rc = lib().vbmf_debug_blk_sweep(_dptr(K), H, int(waves), _dptr(out), C.byref(ld), C.byref(bad))
+    if rc != VBMF_OK:
+        raise RuntimeError("vbmf_debug_blk_sweep failed: %d" % rc)
+    return out, ld.value, bad.value
 
 
 def vbls_jobs_lds_cols(H, full_cov=False):

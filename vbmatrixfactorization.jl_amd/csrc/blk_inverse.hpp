@@ -5,14 +5,15 @@
 //     traffic by DPP row broadcasts and v_permlane swaps only -- and every rank-16 update of the rest is four
 //     v_mfma_f64_16x16x4_f64 per block;
 //   * a whole inverse can therefore run on a single wavefront with no barrier at all (one matrix per wave: the per-column
-//     blocks of full_cov), or on the waves of a workgroup with two barriers per block step (the control chain) instead of
-//     one barrier + two LDS round trips per PIVOT (round 2's register-tiled Gauss-Jordan: 0.5 us per pivot inside a pass).
+//     blocks of full_cov), or on the waves of a workgroup with one or two barriers per block step (the control chain: one, with
+//     look-ahead on the diagonal blocks, up to 64 rows; two at 128) instead of one barrier + two LDS round trips per PIVOT
+//     (round 2's register-tiled Gauss-Jordan: 0.5 us per pivot inside a pass).
 //
 // Sweep operator on a block K of a symmetric matrix W (S = inv(W_KK)):
 //     W_IJ <- W_IJ - W_IK S W_KJ      W_KJ <- S W_KJ      W_IK <- W_IK S      W_KK <- -S          (I, J != K)
 // keeps W symmetric at every stage and leaves -inv(W) after all blocks; the scalar pivots met inside the diagonal blocks are
 // the pivots of the unblocked elimination, so their logs sum to log det W.  Only blocks (I, J) with I <= J are stored
-// authoritatively ("upper blocks"); a lower block is read as the transpose of its mirror.
+// authoritatively ("upper blocks"); a lower block is read as the transpose of its mirror, and its place in the image is scratch.
 //
 // Register layouts (v_mfma_f64_16x16x4_f64; lane l = 16 q + c):
 //     C/D:  4 doubles per lane, register r holds element [row q + 4 r][column c]
@@ -166,14 +167,131 @@ __device__ __forceinline__ f64x4 blk_mma(const f64x4& a, const f64x4& b, f64x4 a
     return acc;
 }
 
+// ---- the blocked sweep on the waves of a workgroup: look-ahead on the diagonal blocks -----------------------------------------------
+// Between one in-wave sweep16 and the next the matrix needs exactly ONE rank-16 update, W(K+1,K+1) -= T(K+1) R(K+1); everything else
+// of block step K can run beside sweep16(K+1).  So wave 0 is the critical wave -- sweep16(K), S to the image, the barrier, two
+// blk_mma from old values, sweep16(K+1) -- and waves 1 .. NW-1 are the bulk waves: the row panel (each forms all of it: redundant
+// MFMAs, no exchange), every other pair update of step K dealt round-robin among them, the panel stores.  ONE workgroup barrier per
+// block step (B_K, behind wave 0's store of S), two more behind the last step; "interval K" is what runs between B_K and B_(K+1).
+// Every block sees the operations of the one-wave schedule on the same operands in the same order -- only who runs them, when, and
+// where a block stands in between differ -- so the result is that schedule's bit for bit.
+//
+// The hazard: the old panel of step K (row K / column K of the upper blocks) is read by every bulk wave, and its (K, K+1) block by
+// wave 0, in the interval in which the new panel R is formed.  R therefore never goes where the old value stands: the image's LOWER
+// blocks are scratch (callers fill them, nobody reads them: the upper blocks are authoritative), and a new panel block is written
+// TRANSPOSED into its mirror position (J, I) instead of its home (I, J).  It stands there for exactly one interval: step K+1 reads
+// it from the mirror (as the pair update's C, or -- block (K, K+1) -- as the next old panel) and stores the result home, whose old
+// content every reader left before B_(K+1).  The one panel block of step K that already stands in its mirror, (K-1, K), goes home.
+// Ordering of every LDS read (st = store, ld = load, all waves pass every barrier):
+//   S(K,K)             st by wave 0 before B_K; ld by the bulk waves in interval K.  Next st: -- (it is final).
+//   W(K+1,K+1)         st by a bulk wave in interval K-1 (a pair update of step K-1; the image itself at K = 0) -> B_K -> ld by
+//                      wave 0 in interval K.  No bulk wave touches it in interval K (the pair is wave 0's); wave 0 overwrites it
+//                      with S(K+1,K+1) before B_(K+1).
+//   old panel of K     blocks (K, J), J > K, and (J, K), J < K-1: at home, st in interval K-1 or earlier -> B_K -> ld in interval K
+//                      (bulk waves; wave 0: (K, K+1) only).  Home is next written in interval K+1 (behind B_(K+1)).
+//                      Block (K-1, K): in its mirror, st in interval K-1 -> B_K -> ld in interval K; the mirror (K, K-1) is
+//                      next written at step K+1 at the earliest (as a mirror of panel K+1 it is never: J = K is that step's "goes home").
+//   new panel of K     st to the mirror (or home for (K-1, K)) in interval K by one bulk wave: nobody reads those positions in
+//                      interval K (mirrors in use then are those of panel K-1: (J, K-1), J > K-1, and (K-1, J), J < K-2; home
+//                      (K-1, K) was last read in interval K-1) -> B_(K+1) -> ld in interval K+1.
+//   pair block (I, J)  ld and st by the one wave the pair is dealt to; an update of interval K-1 is read behind B_K.
+//   last step          no look-ahead is left: every wave is a bulk wave, the new panel goes home behind a barrier of its own (its
+//                      readers are done), and a closing barrier publishes the image, as the schedule before did.
+// pv carries the pivots on wave 0 only (threads 0 .. 63: log det and the bad flag are taken there).
+__device__ __forceinline__ bool blk_in_mirror(int I, int J, int K) {        // off-diagonal upper block (I < J) during interval K
+    return I == K - 1 || (J == K - 1 && I != K - 2);
+}
+// block (I, J), I < J, standing at home or transposed in its mirror: its C/D layout ...
+__device__ __forceinline__ f64x4 blk_ld_at(const double* W, int ld, int I, int J, int lane, bool mir) {
+    return mir ? blk_ld_cols(W, ld, J, I, lane) : blk_ld_rows(W, ld, I, J, lane);
+}
+// ... and the C/D layout of its transpose (what blk_ld_cols reads at home)
+__device__ __forceinline__ f64x4 blk_ld_at_t(const double* W, int ld, int I, int J, int lane, bool mir) {
+    return mir ? blk_ld_rows(W, ld, J, I, lane) : blk_ld_cols(W, ld, I, J, lane);
+}
+template <int NB, int NW>
+__device__ __forceinline__ void blk_sweep_ahead(double* W, int ld, int nb_used, int w, int lane, PivAcc& pv) {
+    static_assert(NW > 1, "one critical wave and at least one bulk wave");
+    f64x4 D = {0.0, 0.0, 0.0, 0.0};
+    if (w == 0) D = blk_ld_rows(W, ld, 0, 0, lane);               // (the caller's barrier published the image)
+    for (int K = 0; K < nb_used; ++K) {
+        const bool last = K == nb_used - 1;
+        if (w == 0) {
+            sweep16(D, lane, pv);                                 // D = S = -inv(W_KK), symmetric
+            blk_st_rows(W, ld, K, K, lane, D);
+        }
+        __syncthreads();                                          // B_K
+        if (w == 0 && !last) {
+            // look-ahead: the one update the next diagonal block waits for, from old values
+            const f64x4 b = blk_ld_rows(W, ld, K, K + 1, lane);   // W_(K,K+1): B operand of the panel product, A operand of T_(K+1)
+            const f64x4 R = blk_mma(-D, b, f64x4{0.0, 0.0, 0.0, 0.0});
+            D = blk_mma(-b, R, blk_ld_rows(W, ld, K + 1, K + 1, lane));
+        } else if (w != 0 || last) {                              // (wave-uniform; the barriers below are met by all waves or none)
+            const int nbulk = last ? NW : NW - 1, me = last ? w : w - 1;
+            const f64x4 Sn = -blk_ld_rows(W, ld, K, K, lane);     // inv(W_KK): its own A operand (symmetric)
+            // old panel b_J = W_KJ (block (K, J) for J > K, the transpose of block (J, K) for J < K) and R_J = inv(W_KK) * W_KJ
+            f64x4 b[NB], R[NB];
+#pragma unroll
+            for (int J = 0; J < NB; ++J) {
+                if (J >= nb_used || J == K) continue;             // uniform
+                b[J] = J > K ? blk_ld_rows(W, ld, K, J, lane) : blk_ld_at_t(W, ld, J, K, lane, J == K - 1);
+                R[J] = blk_mma(Sn, b[J], f64x4{0.0, 0.0, 0.0, 0.0});
+            }
+            // rank-16 update of the upper blocks: W_IJ -= T_I R_J, T_I = old W_IK = b_I'
+            int pairno = 0;
+#pragma unroll
+            for (int I = 0; I < NB; ++I) {
+                if (I >= nb_used || I == K) continue;
+                const f64x4 T = -b[I];
+#pragma unroll
+                for (int J = I; J < NB; ++J) {
+                    if (J >= nb_used || J == K) continue;
+                    if (I == K + 1 && J == K + 1) continue;       // wave 0's (not the last step: K + 1 < nb_used)
+                    if (pairno % nbulk == me) {
+                        f64x4 C = I == J ? blk_ld_rows(W, ld, I, I, lane) : blk_ld_at(W, ld, I, J, lane, blk_in_mirror(I, J, K));
+                        C = blk_mma(T, R[J], C);
+                        blk_st_rows(W, ld, I, J, lane, C);
+                    }
+                    ++pairno;
+                }
+            }
+            if (!last) {
+                // the new panel, away from the old one: transposed into the mirror; (K-1, K), read from its mirror, goes home
+#pragma unroll
+                for (int J = 0; J < NB; ++J) {
+                    if (J >= nb_used || J == K || J % nbulk != me) continue;
+                    if (J > K) blk_st_cols(W, ld, J, K, lane, R[J]);          // mirror (J, K) = (block (K, J))' = R_J'
+                    else if (J == K - 1) blk_st_cols(W, ld, J, K, lane, R[J]);   // home (K-1, K) = R_J'
+                    else blk_st_rows(W, ld, K, J, lane, R[J]);                // mirror (K, J) = (block (J, K))' = R_J
+                }
+            } else {
+                __syncthreads();                                  // every reader of the old panel is done
+#pragma unroll
+                for (int J = 0; J < NB; ++J) {
+                    if (J >= nb_used || J == K || J % nbulk != me) continue;
+                    blk_st_cols(W, ld, J, K, lane, R[J]);         // block (J, K) = R_J'  (J < K: K is the last block)
+                }
+                __syncthreads();
+            }
+        }
+    }
+}
+
 // Blocked sweep of the NB x NB blocks of W (upper blocks authoritative) by the NW waves of the workgroup that call it
-// (wave index w, all with the same arguments).  On return the upper blocks hold -inv(W); pv carries the pivots of every
-// diagonal block (identical on every wave).  NW = 1: a single wave, no barrier anywhere.  NW > 1: two workgroup barriers per
-// block step; every wave sweeps the diagonal block and forms the row panel R_J = inv(W_KK) W_KJ itself (redundant MFMAs, no
-// exchange), the block pairs (I <= J) of the rank-16 update are dealt round-robin, wave 0 stores the panel.
+// (wave index w, all with the same arguments).  On return the upper blocks hold -inv(W); the lower blocks are scratch.
+// NW = 1: a single wave, no barrier anywhere; pv carries the pivots of every diagonal block.
+// NW > 1, NB <= 4: blk_sweep_ahead above (pv on wave 0 only).
+// NW > 1, NB = 8: two workgroup barriers per block step; every wave sweeps the diagonal block and forms the row panel
+// R_J = inv(W_KK) W_KJ itself (redundant MFMAs, no exchange), the block pairs (I <= J) of the rank-16 update are dealt
+// round-robin, wave 0 stores the panel; pv identical on every wave.  With 7 panel blocks and 27 pair updates on three bulk waves
+// the look-ahead's interval is longer than this schedule's step (measured), so this tier keeps it.
 // nb_used: blocks actually present (nb_used <= NB); n: matrix order (pivots beyond n are identity padding: their sweep is exact).
 template <int NB, int NW>
 __device__ __forceinline__ void blk_sweep(double* W, int ld, int nb_used, int w, int lane, PivAcc& pv) {
+    if constexpr (NW > 1 && NB <= 4) {
+        blk_sweep_ahead<NB, NW>(W, ld, nb_used, w, lane, pv);
+        return;
+    }
     for (int K = 0; K < nb_used; ++K) {
         f64x4 S = blk_ld_rows(W, ld, K, K, lane);
         sweep16(S, lane, pv);                                     // S = -inv(W_KK), symmetric
@@ -302,6 +420,36 @@ __device__ __forceinline__ void inv256_blk(const double* __restrict__ Kg, double
         if (bi[t] != bj[t]) blk_st_cols(Out, 256, bj[t], bi[t], lane, v);
     }
     __syncthreads();
+}
+
+// Test hook (vbmf_debug_blk_sweep): one 256-thread workgroup sweeps the identity-padded image of the order-H matrix Kg (row-major,
+// ld H) with the four-wave schedule (NW = 4) or, on the same image, with wave 0 alone running the one-wave schedule (NW = 1).
+// out: the 16 nbu x 16 nbu image afterwards, upper blocks as they stand, lower blocks (scratch) as zeros.
+template <int NB, int NW>
+__global__ __launch_bounds__(256) void debug_blk_sweep_kernel(const double* __restrict__ Kg, int H, double* __restrict__ out,
+                                                              double* __restrict__ logdet, int* __restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) double lds_dbs[];
+    constexpr int NP = 16 * NB, LD = NP + 2;
+    double* W = lds_dbs;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nbu = (H + 15) >> 4, n = 16 * nbu;
+    for (int t = threadIdx.x; t < NP * NP; t += 256) {
+        const int i = t / NP, j = t % NP;
+        W[i * LD + j] = (i < H && j < H) ? Kg[(long long)i * H + j] : (i == j ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    PivAcc pv;
+    if constexpr (NW == 1) {
+        if (w == 0) blk_sweep<NB, 1>(W, LD, nbu, 0, lane, pv);
+    } else {
+        blk_sweep<NB, NW>(W, LD, nbu, w, lane, pv);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < n * n; t += 256) {
+        const int i = t / n, j = t % n;
+        out[t] = (i >> 4) <= (j >> 4) ? W[i * LD + j] : 0.0;
+    }
+    if (threadIdx.x == 0) { *logdet = pv.logdet(); *bad = pv.bad; }
 }
 
 }  // namespace vbmf

@@ -266,10 +266,11 @@ __device__ __forceinline__ bool stop_on_remote_error(const double* __restrict__ 
 }
 
 // Inverse of an SPD matrix of order H <= 16 NB in LDS by the FOUR waves of a 256-thread control workgroup (blk_inverse.hpp:
-// blocked symmetric sweep, the 16 x 16 diagonal blocks inside a wavefront, rank-16 updates on the fp64 MFMA, two barriers per
-// BLOCK step where round 2's register-tiled Gauss-Jordan had a barrier and two LDS round trips per pivot).
+// blocked symmetric sweep, the 16 x 16 diagonal blocks inside a wavefront, rank-16 updates on the fp64 MFMA, one or two barriers
+// per BLOCK step where round 2's register-tiled Gauss-Jordan had a barrier and two LDS round trips per pivot).
 //   elem(i, j): the matrix (i, j < H);  W: 16 NB x (16 NB + 2) doubles of LDS;  on return W's upper triangle holds -inverse
-//   (read it through spd_inv_at), *logdet = log det of the matrix, *bad != 0 if a pivot was not positive / finite.
+//   (read it through spd_inv_at; the lower 16 x 16 blocks are the sweep's scratch), *logdet = log det of the matrix -- valid on
+//   thread 0, which files it --, *bad != 0 if a pivot was not positive / finite -- on the threads of wave 0 at least.
 // Every thread of the control workgroup (ctrl_nthreads() = 256 of them) must call it.
 // the sweep alone, on an image some other code of the workgroup has filled (identity padding included); opens with the barrier that
 // publishes the image

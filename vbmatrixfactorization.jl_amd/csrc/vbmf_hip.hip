@@ -2550,6 +2550,18 @@ static int write_block(vbmf_ctx* c, const char* fn, void* dst, int dt, int on_de
     return VBMF_OK;
 }
 
+// vbmf_debug_blk_sweep: the test kernel of blk_inverse.hpp at tier NB, one workgroup, default stream
+template <int NB>
+static hipError_t debug_blk_sweep_launch(int waves, const double* dK, int H, double* dOut, double* dLd, int* dBad) {
+    const void* fn = waves == 1 ? (const void*)debug_blk_sweep_kernel<NB, 1> : (const void*)debug_blk_sweep_kernel<NB, 4>;
+    const size_t lds = spd_inverse_lds_bytes(NB);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (waves == 1) hipLaunchKernelGGL((debug_blk_sweep_kernel<NB, 1>), dim3(1), dim3(256), lds, 0, dK, H, dOut, dLd, dBad);
+    else hipLaunchKernelGGL((debug_blk_sweep_kernel<NB, 4>), dim3(1), dim3(256), lds, 0, dK, H, dOut, dLd, dBad);
+    return hipGetLastError();
+}
+
 extern "C" {
 
 int vbmf_get_YHat_rows(vbmf_ctx* c, int32_t what, void* dst, int32_t dt, int32_t on_device, int64_t row0, int64_t nrows,
@@ -2775,6 +2787,29 @@ int vbmf_debug_lambda_max(vbmf_ctx* c, const double* G, double* lam, double* ker
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (kernel_us) *kernel_us = 1e3 * (double)t;
     return VBMF_OK;
+}
+
+int vbmf_debug_blk_sweep(const double* K, int64_t H, int waves, double* out, double* logdet, int* bad) {
+    if (!K || !out || !logdet || !bad || H < 1 || H > 128 || (waves != 1 && waves != 4)) return VBMF_ERR_INVALID;
+    const int h = (int)H, n = 16 * ((h + 15) >> 4);
+    const size_t kb = (size_t)h * h * sizeof(double), ob = (size_t)n * n * sizeof(double);
+    double* d = nullptr;                                          // [K | out | logdet | bad]
+    if (hipMalloc(&d, kb + ob + 2 * sizeof(double)) != hipSuccess) return VBMF_ERR_HIP;
+    double* dOut = d + (size_t)h * h;
+    double* dLd = dOut + (size_t)n * n;
+    int* dBad = reinterpret_cast<int*>(dLd + 1);
+    hipError_t e = hipMemcpy(d, K, kb, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = h <= 16 ? debug_blk_sweep_launch<1>(waves, d, h, dOut, dLd, dBad)
+          : h <= 32 ? debug_blk_sweep_launch<2>(waves, d, h, dOut, dLd, dBad)
+          : h <= 64 ? debug_blk_sweep_launch<4>(waves, d, h, dOut, dLd, dBad)
+                    : debug_blk_sweep_launch<8>(waves, d, h, dOut, dLd, dBad);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, dOut, ob, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logdet, dLd, sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(bad, dBad, sizeof(int), hipMemcpyDeviceToHost);
+    hipFree(d);
+    return e == hipSuccess ? VBMF_OK : VBMF_ERR_HIP;
 }
 
 int vbmf_debug_set(vbmf_ctx* c, int what, int64_t value) {
