@@ -572,6 +572,46 @@ int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* co
                                  const double* eta0, const double* zeta0, const double* sigma0, const double* ca0, int64_t njobs,
                                  const int64_t* job_bag, const int64_t* job_model, double* r2, double* ATVecHat, double* diagSigmaATVec,
                                  double* CA, double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status);
+/* vbmf_sparse_scored_jobs: factorize_bag (examples/mil_util.jl:393-416) and the scores behind it -- lowerBound of the fit against the
+ * basis without its last H1 columns, lowerBoundTrimmed(threshold) of the fit against the whole basis (:502-514), and the two residual
+ * norms (:493-501) -- for a list of (bag, model) jobs in one call: the "lower_bound" and "min_err" classifiers of every fold of
+ * validate_with_cvs (:627-648) at once.  It is vbmf_sparse_fixed_basis_jobs (same context, same kernels, same numbers: for a job with the
+ * same bag, model and form every block and r2 are that entry's bit for bit) with a rank per model, a form and a trim per job, and the
+ * bound of every job.
+ *   niter, clamp, grouped   niter >= 1 iterations; clamp and grouped as in vbmf_sparse_lower_bound_batched
+ *   per model k < nmodels, packed in model order (model k's blocks behind those of the models before it):
+ *   model_H             the model's own rank, 1 <= H_k <= 32
+ *   BHat, SigmaB        L x H_k fp64 column-major with ld = L; H_k x H_k
+ *   CB, delta           (H_k each) the precisions of B's columns and their Gamma posterior rates
+ *   gamma, gamma0, delta0   their posterior shape and prior (one each)
+ *   a_pri, b_pri, a_post    (H_k each) per column of A the ARD hyper-prior (shape, rate) and the posterior shape, the layout of
+ *                       vbmf_sparse_lower_bound_batched; a_post and b_pri are what updateCA! reads (vbmf_sparse_fixed_basis_jobs' alpha, beta0)
+ *   eta0, zeta0, sigma0, ca0   as in vbmf_sparse_fixed_basis_jobs
+ *   per job j < njobs:
+ *   job_bag, job_model  as in vbmf_sparse_fixed_basis_jobs
+ *   job_full_cov        0: the diagonal form of updateA!, 1: full_cov
+ *   job_trim            < 0: lowerBound; >= 0: lowerBoundTrimmed(job_trim[j]).  The mask |ATVecHat| > trim compares the fp64 ATVecHat, as
+ *                       the reference does (src/vbmf_sparse.jl:481)
+ *   lb, r2              (njobs each, may be NULL; lb, r2 and ATVecHat not all three) the bound and ||Y_b - BHat_k AHat_j'||_F^2.  The
+ *                       bound's data term is r2 + L tr(A'A SigmaB) + tr(SigmaA (B'B + L SigmaB)) with that direct residual, never the
+ *                       trace form
+ *   ATVecHat, diagSigmaATVec, CA, beta, SigmaA, sigmaHat, zeta   as in vbmf_sparse_fixed_basis_jobs (SigmaA: the jobs' H_k x H_k blocks one
+ *                       after the other), in the caller's job order
+ *   status              (njobs, required) 1 for a job the device flagged (as in vbmf_sparse_fixed_basis_jobs) or whose bound or sums are not
+ *                       finite: NaN in lb, r2 and every block of that job; the other jobs are computed as if it were not in the call
+ * One launch of the model kernel (which also leaves the basis' share of the bound: sum CB_h (B'B + L SigmaB)_hh, sum CB, sum log delta and
+ * log det SigmaB from an in-LDS Cholesky), one launch of the job kernel per non-empty (16-block tier of H_k, form) group of jobs -- at
+ * most four; the host sorts the jobs into them through an index table -- and one synchronising read-back.  The host assembles lb.
+ * Refused before any launch, copy or change, every output left untouched: what vbmf_sparse_fixed_basis_jobs refuses (a 1-column bag only
+ * for a job whose own form is the diagonal one under VBMF_COMPAT_SPARSE_REPEAT), a model_H[k] outside 1..32 (VBMF_ERR_UNSUPPORTED), a
+ * job_full_cov[j] other than 0 or 1, and a non-finite CB, delta, gamma, gamma0, delta0, a_pri or job_trim. */
+int vbmf_sparse_scored_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t niter, int clamp, int grouped, int64_t nmodels,
+                            const int64_t* model_H, const double* BHat, const double* SigmaB, const double* CB, const double* delta,
+                            const double* gamma, const double* gamma0, const double* delta0, const double* a_pri, const double* b_pri,
+                            const double* a_post, const double* eta0, const double* zeta0, const double* sigma0, const double* ca0,
+                            int64_t njobs, const int64_t* job_bag, const int64_t* job_model, const int64_t* job_full_cov,
+                            const double* job_trim, double* lb, double* r2, double* ATVecHat, double* diagSigmaATVec, double* CA,
+                            double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status);
 /* test hook: the widest bag whose job keeps its state in LDS in vbmf_sparse_fixed_basis_jobs at this H and form (wider ones work in the
  * call's scratch buffer); 0 for an H outside 1..32 */
 int vbmf_debug_vbls_jobs_lds_cols(int64_t H, int full_cov);

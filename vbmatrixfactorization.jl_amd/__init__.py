@@ -52,7 +52,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "train_dual_folds", "BagPool",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
            "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch", "vbls_sparse_jobs_",
-           "classify_folds", "test_classification_folds", "validate_folds"]
+           "classify_folds", "test_classification_folds", "validate_folds", "factorize_folds", "validate_local_folds"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
 # elements the field is left None and computed on demand with updateYHat_ (8 GB at 100k x 10k).
@@ -2522,12 +2522,13 @@ def _jobs_bags(fn, Ys, refuse):
     return _batch_shapes(Ys, 1, refuse)
 
 
-def _jobs_run(Ys, H, mods, job_bag, job_model, niter, full_cov):
-    """The one device call: on the pool's own context, on the upload's, or on a Bags of rank 1 opened for the list and closed after"""
+def _jobs_run(Ys, call):
+    """The one device call, call(context, col_off): on the pool's own context, on the upload's, or on a Bags of rank 1 opened for the
+    list and closed after"""
     if isinstance(Ys, BagPool):
-        return Ys.ctx.sparse_fixed_basis_jobs(Ys.col_off, H, mods, job_bag, job_model, int(niter), full_cov=full_cov)
+        return call(Ys.ctx, Ys.col_off)
     with _on_device(Ys, 1, Bags) as bags:
-        return bags.ctx.sparse_fixed_basis_jobs(bags.col_off, H, mods, job_bag, job_model, int(niter), full_cov=full_cov)
+        return call(bags.ctx, bags.col_off)
 
 
 def vbls_sparse_jobs_(Ys, models, job_bag, job_model, niter, full_cov=False):
@@ -2561,7 +2562,7 @@ def vbls_sparse_jobs_(Ys, models, job_bag, job_model, niter, full_cov=False):
             refuse(f"job {j}: bag {b} outside 0..{len(Ms) - 1}")
         if not 0 <= k < len(models):
             refuse(f"job {j}: model {k} outside 0..{len(models) - 1}")
-    r = _jobs_run(Ys, H, mods, job_bag, job_model, niter, full_cov)
+    r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_fixed_basis_jobs(off, H, mods, job_bag, job_model, int(niter), full_cov=full_cov))
     sets = []
     for j, (b, k) in enumerate(zip(job_bag, job_model)):
         p = copy_vbmf_params(np.broadcast_to(np.float64(0.0), (L, Ms[b])), models[k])
@@ -2620,6 +2621,19 @@ def _fold_alg(fn, class_alg):
     return _FOLD_LAMS.get(class_alg)
 
 
+_FOLD_SCORED_ALGS = ("lower_bound", "min_err")                           # factorize_bag's classifiers (:493-514): factorize_folds
+
+
+def _fold_alg_scored(fn, class_alg):
+    """_fold_alg for the functions that take factorize_bag's classifiers too (classify_folds, test_classification_folds)"""
+    if class_alg in _FOLD_SCORED_ALGS:
+        return None
+    if class_alg not in _FOLD_ALGS:
+        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols', 'rls' or 'dual', 'lower_bound' or 'min_err'; 'vbls' runs the basic model on "
+                        f"one basis per context: run it per fold with classify_bags)")
+    return _FOLD_LAMS.get(class_alg)
+
+
 def _fold_labels(fn, labels, nb):
     labels = np.asarray(labels).reshape(-1)
     if labels.size != nb:
@@ -2629,9 +2643,9 @@ def _fold_labels(fn, labels, nb):
     return labels.astype(np.int64)
 
 
-def classify_folds(models, tests, Ys, class_alg="ols", niter=None):
-    """classify (examples/mil_util.jl:453-535) with class_alg "ols", "rls" or "dual" for every fold of a validation run in ONE device call:
-    fold f's test bags tests[f] (bag indices into Ys) against its own pair models[f] = (res0, res1).  Any objects with a BHat serve as
+def classify_folds(models, tests, Ys, class_alg="ols", niter=None, threshold=1e-1):
+    """classify (examples/mil_util.jl:453-535) with class_alg "ols", "rls", "dual", "lower_bound" or "min_err" for every fold of a
+    validation run in ONE device call: fold f's test bags tests[f] (bag indices into Ys) against its own pair models[f] = (res0, res1).  Any objects with a BHat serve as
     models, of the same or different H <= 64; (0, 0) -- what train_folds returns for a fold it could not train -- is accepted.
     Ys: a BagPool (the indices are pool bag ids and the call runs on the pool's own context: no select, no gather, no new context), an
     uploaded Bags / SparseBags, or a list of L x M_b matrices (uploaded once as Bags).
@@ -2649,10 +2663,25 @@ def classify_folds(models, tests, Ys, class_alg="ols", niter=None):
     read it) from what copy_vbmf_params gives (Context.sparse_fixed_basis_jobs); err = sqrt(r2) / (L M_b), label 0 where
     err0 < err1.  A fold with a job that met a non-finite precision or a bad pivot raises VbmfError naming the fold after the others
     have been computed, with .results as above.
-    "vbls", "lower_bound" and "min_err" stay per fold: classify_bags."""
+    "lower_bound" and "min_err" (:493-514): factorize_folds(models, tests, Ys, niter, threshold) -- fold f's model is the
+    vbmf_sparse_parameters with 0 < H1 < H that train_local_folds returns, bare or as the first of a pair -- and from its scores
+    (labels = L1 > L0, L0, L1) for "lower_bound", (label 0 where |(err0 - err1) / err0| < threshold (:497), err0, err1) for "min_err".
+    The folds may differ in H and H1.  A fold with a failed job raises VbmfError as "dual" does.  threshold is read by these two only.
+    "vbls" stays per fold: classify_bags."""
     fn = "classify_folds"
     refuse = _ls_refuser(fn)
-    lam = _fold_alg(fn, class_alg)
+    lam = _fold_alg_scored(fn, class_alg)
+    if class_alg in _FOLD_SCORED_ALGS:
+        models, tests = list(models), list(tests)
+        if len(models) != len(tests):
+            refuse(f"{len(models)} models but {len(tests)} test lists")
+        try:
+            scores = _factorize_folds(fn, models, tests, Ys, 20 if niter is None else int(niter), threshold, class_alg)
+        except VbmfError as e:
+            if hasattr(e, "results"):
+                e.results = [_scored_labels(r, class_alg, threshold) for r in e.results]
+            raise
+        return [_scored_labels(r, class_alg, threshold) for r in scores]
     models, tests = list(models), list(tests)
     if len(models) != len(tests):
         refuse(f"{len(models)} models but {len(tests)} test lists")
@@ -2745,7 +2774,7 @@ def _classify_folds_dual(fn, models, ids, Ys, L, niter):
     out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
     if not job_bag:
         return out
-    r = _jobs_run(Ys, H, mods, job_bag, job_model, niter, True)
+    r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_fixed_basis_jobs(off, H, mods, job_bag, job_model, int(niter), full_cov=True))
     r2, status = r["r2"], r["status"]
     bad = []
     for f in trained:
@@ -2770,12 +2799,131 @@ def _classify_folds_dual(fn, models, ids, Ys, L, niter):
     return out
 
 
-def test_classification_folds(models, tests, Ys, labels, class_alg="ols", niter=None):
+def _scored_labels(r, class_alg, threshold):
+    """classify's "lower_bound" (:502-514) or "min_err" (:493-501) triple from one fold's scores"""
+    if r is None:
+        return None
+    if class_alg == "lower_bound":
+        return (r["L1"] > r["L0"]).astype(np.int64), r["L0"], r["L1"]
+    err0, err1 = r["err0"], r["err1"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        close = np.abs((err0 - err1) / err0) < threshold                 # :497
+    return np.where(close, 0, 1).astype(np.int64), err0, err1
+
+
+def _scored_model(res, H, d):
+    """One model of Context.sparse_scored_jobs from the fields copy_vbmf_params keeps (d: BHat, SigmaB, CB, gamma, delta) and the
+    sparse model's hyper-priors `res` carries (vbmf_sparse_init's defaults for the truncated basis); the start values are
+    vbmf_sparse_init's (CA = ones, sigmaHat = 1)."""
+    one = np.ones(H)
+    return dict(BHat=d["BHat"], SigmaB=d["SigmaB"], CB=np.asarray(d["CB"], dtype=np.float64), delta=np.asarray(d["delta"], dtype=np.float64),
+                gamma=float(d["gamma"]), gamma0=float(res.gamma0), delta0=float(res.delta0), a_pri=one * float(res.alpha0),
+                b_pri=one * float(res.beta0), a_post=one * (float(res.alpha0) + 0.5), eta0=float(res.eta0), zeta0=float(res.zeta0),
+                sigma0=1.0, ca0=1.0)
+
+
+class _SparseInitPriors:
+    """vbmf_sparse_init's default hyper-priors (src/vbmf_sparse.jl:101-103): what factorize_bag's truncated model carries (:398-404)"""
+    alpha0 = beta0 = gamma0 = delta0 = eta0 = zeta0 = 1e-10
+
+
+def _factorize_folds(fn, models, tests, Ys, niter, threshold, alg=None):
+    """factorize_folds for fn; alg: the class_alg the refusal of a model names (None: factorize_bag itself)"""
+    refuse = _ls_refuser(fn)
+    what = "factorize_bag" if alg is None else f"class_alg = {alg!r}"
+    if len(models) != len(tests):
+        refuse(f"{len(models)} models but {len(tests)} test lists")
+    if niter < 1:
+        refuse(f"niter = {niter} < 1")
+    threshold = float(threshold)
+    if not np.isfinite(threshold) or threshold < 0.0:
+        refuse(f"threshold = {threshold} (lowerBoundTrimmed takes a finite threshold >= 0)")
+    L, Ms = _jobs_bags(fn, Ys, refuse)
+    ids = _fold_ids(fn, tests, len(Ms))
+    mods, trained = [], []
+    for f, m in enumerate(models):
+        if _untrained(m) or (type(m) is int and m == 0):
+            continue
+        res = m[0] if isinstance(m, (tuple, list)) and len(m) == 2 else m            # (res0, anything): the second is not read (:610)
+        if type(res) is not vbmf_sparse_parameters or not 0 < int(getattr(res, "H1", 0)) < int(res.H):
+            refuse(f"fold {f}: {what} takes a vbmf_sparse_parameters with 0 < H1 < H (what train_local_folds returns), bare or first "
+                   f"in a pair, not a {type(res).__name__}"
+                   + (f" with H = {res.H}, H1 = {getattr(res, 'H1', None)}" if type(res) is vbmf_sparse_parameters else "")
+                   + "; 'ols', 'rls' or 'dual' take other models, and any pair of models runs per fold with classify_bags")
+        H = int(res.H)
+        if H > _JOBS_MAX_H:
+            refuse(f"fold {f}: H = {H} > {_JOBS_MAX_H}")
+        B, SB = np.asarray(res.BHat, dtype=np.float64), np.asarray(res.SigmaB, dtype=np.float64)
+        if B.shape != (L, H) or SB.shape != (H, H):
+            refuse(f"fold {f}: BHat is {B.shape} and SigmaB {SB.shape}, the bags have L = {L} rows and H = {H}")
+        if not all(np.all(np.isfinite(np.asarray(v, dtype=np.float64))) for v in (B, SB, res.CB, res.delta, res.gamma, res.gamma0, res.delta0,
+                                                                                    res.alpha0, res.beta0, res.eta0, res.zeta0)):
+            refuse(f"fold {f}: the model has a BHat, SigmaB, CB, delta, gamma or hyper-prior that is not finite")
+        tb = _truncated_basis(res)
+        mods.append(_scored_model(_SparseInitPriors, tb["H"], tb))                             # :398-404
+        mods.append(_scored_model(res, H, dict(BHat=B, SigmaB=SB, CB=res.CB, gamma=res.gamma, delta=res.delta)))
+        trained.append((f, H - int(res.H1)))
+    job_bag, job_model, job_full, job_trim, where = [], [], [], [], {}
+    for t, (f, H0) in enumerate(trained):
+        n = len(ids[f])
+        if n:
+            where[f] = len(job_bag)
+            job_bag += ids[f] + ids[f]
+            job_model += [2 * t] * n + [2 * t + 1] * n
+            job_full += [Ms[b] * H0 < 1600 for b in ids[f]] * 2                              # :405-409
+            job_trim += [-1.0] * n + [threshold] * n
+    empty = lambda: dict(L0=np.empty(0), L1=np.empty(0), err0=np.empty(0), err1=np.empty(0), status=np.empty(0, dtype=np.int64))
+    is_trained = {f for f, _ in trained}
+    out = [empty() if f in is_trained else None for f in range(len(models))]
+    if not job_bag:
+        return out
+    r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_scored_jobs(off, mods, job_bag, job_model, job_full, job_trim, niter))
+    bad = []
+    for f, _ in trained:
+        if f not in where:
+            continue
+        n, j0 = len(ids[f]), where[f]
+        st = np.asarray(r["status"][j0:j0 + 2 * n])
+        out[f] = dict(L0=r["lb"][j0:j0 + n].copy(), L1=r["lb"][j0 + n:j0 + 2 * n].copy(), err0=np.sqrt(r["r2"][j0:j0 + n]),
+                      err1=np.sqrt(r["r2"][j0 + n:j0 + 2 * n]), status=(st[:n] | st[n:]).astype(np.int64))
+        if st.any():
+            j = int(np.flatnonzero(st)[0])
+            bad.append((f, j // n, ids[f][j % n]))
+    if bad:
+        f, k, b = bad[0]
+        results = [None if any(f == g for g, _, _ in bad) else o for f, o in enumerate(out)]
+        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against {'the whole' if k else 'the truncated'} basis met a "
+                                             f"precision that is not finite or a pivot that is not positive and finite, or its bound is "
+                                             f"not finite")
+        e.results = results
+        raise e
+    return out
+
+
+def factorize_folds(models, tests, Ys, niter=20, threshold=1e-1):
+    """factorize_bag (examples/mil_util.jl:393-416) and its four scores for every fold's test bags in ONE device call
+    (Context.sparse_scored_jobs): per tested bag 20 vbls! iterations against the fold's basis without its last H1 columns and 20
+    against the whole basis, both in the full_cov form where M_b (H - H1) < 1600 (:405-409) and in the diagonal one otherwise, then
+    lowerBound of the first fit, lowerBoundTrimmed(threshold) of the second, and the two residual norms.
+    models[f]: the vbmf_sparse_parameters with 0 < H1 < H that train_local_folds returns for fold f, bare or as the first of a pair
+    (res0, anything) -- the second is not read (:610) --, or (0, 0) / 0 for an untrained fold; the folds may differ in H <= 32 and
+    H1.  tests[f]: bag indices into Ys; Ys: a BagPool (the call runs on the pool's own context), an uploaded Bags / SparseBags or a
+    list of L x M_b matrices.
+    The call's models are 2 t and 2 t + 1 for the t-th trained fold: the truncated basis with vbmf_sparse_init's default priors
+    (:398-404), and what copy_vbmf_params keeps; its jobs (bag, 2 t, lowerBound) then (bag, 2 t + 1, lowerBoundTrimmed(threshold)).
+    Returns per fold dict(L0, L1, err0, err1, status) with one entry per tested bag (err = norm(Y_b - BHat*AHat'), formed entry by
+    entry on the device), None for an untrained fold.  A fold with a job the device flagged or whose bound is not finite raises
+    VbmfError naming it after the others have been computed; the exception's .results holds them, None in that fold's place."""
+    return _factorize_folds("factorize_folds", list(models), list(tests), Ys, int(niter), threshold)
+
+
+def test_classification_folds(models, tests, Ys, labels, class_alg="ols", niter=None, threshold=None):
     """test_classification (examples/mil_util.jl:558-587) of every fold in one device call (classify_folds): a list with
     (mer, eer, fp, fn, n0, n1) per fold, counted as test_classification_batch counts, from the fold's estimated labels and
-    labels[tests[f]].  labels: 0 / 1, one per bag of Ys.  A (0, 0) fold gives (-1.0,) * 6 (:612-614).  niter: classify_folds'."""
+    labels[tests[f]].  labels: 0 / 1, one per bag of Ys.  A (0, 0) fold gives (-1.0,) * 6 (:612-614).  niter, threshold:
+    classify_folds', handed on only when given."""
     fn = "test_classification_folds"
-    _fold_alg(fn, class_alg)
+    _fold_alg_scored(fn, class_alg)
     models, tests = list(models), list(tests)
     if len(models) != len(tests):
         _ls_refuser(fn)(f"{len(models)} models but {len(tests)} test lists")
@@ -2783,7 +2931,8 @@ def test_classification_folds(models, tests, Ys, labels, class_alg="ols", niter=
     labels = _fold_labels(fn, labels, nb)
     ids = _fold_ids(fn, tests, nb)
     out = []
-    for t, r in zip(ids, classify_folds(models, ids, Ys, class_alg, **({} if niter is None else {"niter": niter}))):
+    kw = {k: v for k, v in (("niter", niter), ("threshold", threshold)) if v is not None}
+    for t, r in zip(ids, classify_folds(models, ids, Ys, class_alg, **kw)):
         if r is None:
             out.append((-1.0,) * 6)
         else:
@@ -2824,6 +2973,36 @@ def validate_folds(pool, labels, splits, solver, H, niter, eps=1e-6, class_alg="
     else:
         models = train_folds(folds, solver, H, niter, eps=eps, rng=rng, form=form, slice_cols=slice_cols, pool=pool)
     return test_classification_folds(models, tests, pool, labels, class_alg)
+
+
+def validate_local_folds(pool, labels, splits, H, H1, niter, eps=1e-6, class_alg="lower_bound", threshold=1e-1, diag_var=False, rng=None,
+                         form="stream", slice_cols=None):
+    """The train_local branch of validate_with_cvs (examples/mil_util.jl:635-637, "the better approach") over all splits =
+    [(train_ids, test_ids), ...] of a BagPool: one train_local_folds(folds, H, H1, niter, eps, pool=pool) per round on the folds'
+    training groups (as validate_folds forms them) and one test_classification_folds on the test_ids with class_alg "lower_bound" or
+    "min_err" (factorize_folds: one device call).  labels: 0 / 1, one per bag of the pool; threshold: classify's; diag_var, rng,
+    form, slice_cols: train_local_folds'.  Returns the list of (mer, eer, fp, fn, n0, n1) per split."""
+    fn = "validate_local_folds"
+    refuse = _ls_refuser(fn)
+    if class_alg not in _FOLD_SCORED_ALGS:
+        refuse(f"class_alg = {class_alg!r} ('lower_bound' or 'min_err': the classifiers of a train_local model; validate_folds takes "
+               f"'ols', 'rls' and 'dual')")
+    if not isinstance(pool, BagPool):
+        refuse(f"pool is a {type(pool).__name__}, not a BagPool")
+    _, nb = _folds_bags(fn, pool)
+    if int(H) > _JOBS_MAX_H:
+        refuse(f"H = {int(H)} > {_JOBS_MAX_H}")
+    if not 0 < int(H1) < int(H):
+        refuse(f"H1 = {int(H1)} (factorize_bag needs 0 < H1 < H = {int(H)})")
+    labels = _fold_labels(fn, labels, nb)
+    splits = [tuple(s) for s in splits]
+    if any(len(s) != 2 for s in splits):
+        refuse("every split is a pair (train_ids, test_ids)")
+    train = _fold_ids(fn, [s[0] for s in splits], nb)
+    tests = _fold_ids(fn, [s[1] for s in splits], nb)
+    folds = [([b for b in t if labels[b] == 0], [b for b in t if labels[b] == 1]) for t in train]
+    models = train_local_folds(folds, H, H1, niter, eps=eps, rng=rng, diag_var=diag_var, form=form, slice_cols=slice_cols, pool=pool)
+    return test_classification_folds(models, tests, pool, labels, class_alg, threshold=threshold)
 
 
 # =================================================================================================

@@ -104,7 +104,7 @@ SYMBOLS = [
     "vbmf_sparse_set_full_cov", "vbmf_sparse_set_SigmaA", "vbmf_sparse_get_SigmaA",
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
     "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_bag_least_squares_jobs", "vbmf_set_gram_form",
-    "vbmf_sparse_fixed_basis_jobs", "vbmf_debug_vbls_jobs_lds_cols",
+    "vbmf_sparse_fixed_basis_jobs", "vbmf_sparse_scored_jobs", "vbmf_debug_vbls_jobs_lds_cols",
     "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather", "vbmf_debug_blk_sweep",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
@@ -219,6 +219,8 @@ def lib():
                                               C.POINTER(i64)]
     L.vbmf_sparse_fixed_basis_jobs.argtypes = [vp, i64, C.POINTER(i64), i64, i64, i32, i64, dp, dp, dp, dp, dp, dp, dp, dp, i64,
                                                C.POINTER(i64), C.POINTER(i64), dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(i64)]
+    L.vbmf_sparse_scored_jobs.argtypes = ([vp, i64, C.POINTER(i64), i64, i32, i32, i64, C.POINTER(i64)] + [dp] * 14
+                                          + [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)] + [dp] * 10 + [C.POINTER(i64)])
     L.vbmf_debug_vbls_jobs_lds_cols.argtypes = [i64, i32]
     L.vbmf_debug_blk_sweep.argtypes = [dp, i64, i32, dp, dp, C.POINTER(i32)]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
@@ -950,6 +952,54 @@ class Context:
                                                          _i64ptr(jk), _dptr(r2), _dptr(A), _dptr(dS), _dptr(CA), _dptr(beta), _dptr(SA),
                                                          _dptr(sg), _dptr(zeta), _i64ptr(status)))
         return dict(r2=r2, sigmaHat=sg, zeta=zeta, status=status, SigmaA=SA, CA=CA, beta=beta, diagSigmaATVec=dS, ATVecHat=A, off=boff)
+
+    def sparse_scored_jobs(self, col_off, models, job_bag, job_model, job_full_cov, job_trim, niter, clamp=True, grouped=False):
+        """factorize_bag and its scores for a list of (bag, model) jobs in one device call (vbmf_sparse_scored_jobs): models[k] is a dict
+        of BHat (L, H_k) and SigmaB (H_k, H_k) fp64, CB, delta, a_pri, b_pri, a_post (H_k,), gamma, gamma0, delta0, eta0, zeta0, sigma0,
+        ca0 (scalars), each model of its own H_k <= 32; job j runs bag job_bag[j] against model job_model[j] for niter iterations in
+        the diagonal (job_full_cov[j] = 0) or the full_cov form, and scores it with lowerBound (job_trim[j] < 0 or None) or
+        lowerBoundTrimmed(job_trim[j]).  Only this context's Y is read.  Returns what sparse_fixed_basis_jobs returns plus lb (njobs,);
+        SigmaA is a list of (H_k, H_k) arrays, and status is 1 also for a job whose bound is not finite."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        nk = len(models)
+        Hs = np.array([np.shape(m["BHat"])[1] if np.ndim(m["BHat"]) == 2 else -1 for m in models], dtype=np.int64)
+        for m, H in zip(models, Hs):
+            H = int(H)
+            if (np.shape(m["BHat"]) != (self.L, H) or np.shape(m["SigmaB"]) != (H, H)
+                    or any(np.size(m[f]) != H for f in ("CB", "delta", "a_pri", "b_pri", "a_post"))):
+                raise ValueError(f"every model needs BHat ({self.L}, H), SigmaB (H, H), CB, delta, a_pri, b_pri and a_post (H,)")
+
+        def pack(key, order="C"):
+            if not nk:
+                return np.empty(0)
+            return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
+        per_model = [pack("BHat", "F"), pack("SigmaB", "F")] + [pack(f) for f in (
+            "CB", "delta", "gamma", "gamma0", "delta0", "a_pri", "b_pri", "a_post", "eta0", "zeta0", "sigma0", "ca0")]
+        jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
+        jk = np.ascontiguousarray(job_model, dtype=np.int64).reshape(-1)
+        jf = np.ascontiguousarray([int(bool(f)) for f in job_full_cov], dtype=np.int64).reshape(-1)
+        jt = np.ascontiguousarray([-1.0 if t is None else float(t) for t in job_trim], dtype=np.float64).reshape(-1)
+        nj = jb.size
+        if not (jk.size == jf.size == jt.size == nj):
+            raise ValueError(f"{nj} job bags but {jk.size} job models, {jf.size} forms and {jt.size} trims")
+        ok = (jb >= 0) & (jb < nb) & (jk >= 0) & (jk < nk)           # (a job out of range is the library's to refuse: no block for it)
+        Hj = np.where(ok, Hs[np.clip(jk, 0, max(nk - 1, 0))], 0) if nk >= 1 else np.zeros(nj, np.int64)
+        widths = np.where(ok, off[np.clip(jb, 0, max(nb - 1, 0)) + 1] - off[np.clip(jb, 0, max(nb - 1, 0))], 0) if nb >= 1 else np.zeros(nj, np.int64)
+        boff = np.concatenate([[0], np.cumsum(widths * Hj)]).astype(np.int64)
+        soff = np.concatenate([[0], np.cumsum(Hj * Hj)]).astype(np.int64)
+        n = max(int(boff[-1]), 1)
+        lb, r2, sg, zeta = np.empty(nj), np.empty(nj), np.empty(nj), np.empty(nj)
+        A, dS, CA, beta = np.empty(n), np.empty(n), np.empty(n), np.empty(n)
+        SA = np.empty(max(int(soff[-1]), 1))
+        status = np.zeros(nj, dtype=np.int64)
+        self._chk(self._lib.vbmf_sparse_scored_jobs(self._h, nb, _i64ptr(off), int(niter), int(bool(clamp)), int(bool(grouped)), nk, _i64ptr(Hs),
+                                                    *[_dptr(v) for v in per_model], nj, _i64ptr(jb), _i64ptr(jk), _i64ptr(jf), _dptr(jt),
+                                                    _dptr(lb), _dptr(r2), _dptr(A), _dptr(dS), _dptr(CA), _dptr(beta), _dptr(SA), _dptr(sg),
+                                                    _dptr(zeta), _i64ptr(status)))
+        SAs = [SA[soff[j]:soff[j + 1]].reshape(int(Hj[j]), int(Hj[j])) for j in range(nj)]
+        return dict(lb=lb, r2=r2, sigmaHat=sg, zeta=zeta, status=status, SigmaA=SAs, CA=CA, beta=beta, diagSigmaATVec=dS, ATVecHat=A,
+                    off=boff)
 
     def sparse_lower_bound_batched(self, col_off, ATVecHat, diagSigmaATVec, CA, beta, SigmaA, sigmaHat, zeta, eta, eta0, zeta0,
                                    a_pri, b_pri, a_post, trim=None, clamp=True, grouped=False):

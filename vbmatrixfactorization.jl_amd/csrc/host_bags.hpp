@@ -1,5 +1,5 @@
 // host_bags.hpp -- the many-bags entries of the C ABI (batched vbls! of the basic and the sparse models, per-bag residuals, least
-// squares and lower bounds, vbls! for (bag, model) jobs, many whole fits of the sparse and of the basic model, the bags' Y Y') and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
+// squares and lower bounds, vbls! for (bag, model) jobs with and without each job's bound, many whole fits of the sparse and of the basic model, the bags' Y Y') and the host bookkeeping they share.  Part of vbmf_hip.hip's one translation unit: included there after the
 // helpers it uses, never on its own.  The context's Y holds the bags side by side: bag b = columns col_off[b] .. col_off[b+1]-1.
 //   bags_check     what every entry refuses about (nbags, col_off) and a sharded context; the widest bag, the residual slices
 //   bags_reserve   ONE device scratch buffer (c->bags), grown on demand.  Every entry synchronises before it returns, so no two layouts
@@ -482,45 +482,75 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
     return VBMF_OK;
 }
 
-// vbls! of the ARD families (examples/mil_util.jl:187-197) for a list of (bag, model) jobs, every model with its own fp64 basis, and
-// each job's norm(Y - BHat*AHat')^2 (:518-521) in the same launch: the "dual" classifier of :515-530 for every fold of
-// validate_with_cvs at once.  The context supplies Y only.  Two launches (per model, per job) and one synchronising read-back,
-// whatever nmodels and njobs are (vbls_jobs_kernels.hpp).
-int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t H, int64_t niter, int full_cov,
-                                 int64_t nmodels, const double* BHat, const double* SigmaB, const double* alpha, const double* beta0,
-                                 const double* eta0, const double* zeta0, const double* sigma0, const double* ca0, int64_t njobs,
-                                 const int64_t* job_bag, const int64_t* job_model, double* r2, double* ATVecHat, double* diagSigmaATVec,
-                                 double* CA, double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status) {
-    if (!c) return VBMF_ERR_INVALID;
-    const char* fn = "vbmf_sparse_fixed_basis_jobs";
-    if (H < 1 || H > VJOBS_MAX_H) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for 1 <= H <= %d)", fn, (long long)H, VJOBS_MAX_H);
-    if (nmodels < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nmodels must be >= 1", fn);
-    if (njobs < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
-    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
-    if (!BHat || !SigmaB || !alpha || !beta0 || !eta0 || !zeta0 || !sigma0 || !ca0 || !job_bag || !job_model || !status)
+// What vbmf_sparse_fixed_basis_jobs and vbmf_sparse_scored_jobs share: vbls! of the ARD families (examples/mil_util.jl:187-197) for a
+// list of (bag, model) jobs, every model with its own fp64 basis, each job's norm(Y - BHat*AHat')^2 and -- for a scored call -- its bound.
+struct VjobsCall {
+    const char* fn;
+    int64_t nbags; const int64_t* col_off; int64_t niter;
+    // per model (packed in model order); model_H nullptr: every model has rank H_all.  CB .. gamma0, delta0, a_pri: a scored call's only
+    int64_t nmodels; const int64_t* model_H; int64_t H_all;
+    const double* BHat; const double* SigmaB; const double* CB; const double* delta; const double* gamma; const double* gamma0;
+    const double* delta0; const double* a_pri; const double* b_pri; const double* a_post; const double* eta0; const double* zeta0;
+    const double* sigma0; const double* ca0;
+    // per job; job_full_cov nullptr: every job has the form full_all.  job_trim: a scored call's only
+    int64_t njobs; const int64_t* job_bag; const int64_t* job_model; const int64_t* job_full_cov; int full_all; const double* job_trim;
+    bool scored; int clamp, grouped;
+    double* lb; double* r2; double* ATVecHat; double* diagSigmaATVec; double* CA; double* beta; double* SigmaA; double* sigmaHat;
+    double* zeta; int64_t* status;
+};
+
+// One launch per model, one per non-empty (16-block tier of H_k, form) group of jobs -- at most four, the jobs sorted into them through
+// an index table -- and one synchronising read-back, whatever nmodels and njobs are (vbls_jobs_kernels.hpp).  Every refusal comes
+// before any launch or copy and leaves every output untouched.
+static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
+    const char* fn = a.fn;
+    const int64_t nk = a.nmodels, nj = a.njobs, nb = a.nbags, L = c->L;
+    if (nk < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nmodels must be >= 1", fn);
+    if (nj < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    if (a.niter < 1 || a.niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (!a.BHat || !a.SigmaB || !a.b_pri || !a.a_post || !a.eta0 || !a.zeta0 || !a.sigma0 || !a.ca0 || !a.job_bag || !a.job_model || !a.status)
         FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
-    if (!r2 && !ATVecHat) FAIL(c, VBMF_ERR_INVALID, "%s: r2 and ATVecHat are both NULL", fn);
+    if (a.scored && (!a.model_H || !a.CB || !a.delta || !a.gamma || !a.gamma0 || !a.delta0 || !a.a_pri || !a.job_full_cov || !a.job_trim))
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
+    if (!a.lb && !a.r2 && !a.ATVecHat) FAIL(c, VBMF_ERR_INVALID, "%s: %sr2 and ATVecHat are both NULL", fn, a.scored ? "lb, " : "");
     // what one grid holds: a launch is kept to 2^32 - 1 threads in all, so to LS_MAX_GROUPS workgroups of 256
-    if (njobs > LS_MAX_GROUPS || nmodels > LS_MAX_GROUPS)
-        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs, %lld models (more than the %lld workgroups of one grid)", fn, (long long)njobs,
-             (long long)nmodels, (long long)LS_MAX_GROUPS);
+    if (nj > LS_MAX_GROUPS || nk > LS_MAX_GROUPS)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs, %lld models (more than the %lld workgroups of one grid)", fn, (long long)nj,
+             (long long)nk, (long long)LS_MAX_GROUPS);
     if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set", fn);
     BagDims bd;
-    TRY(bags_check(c, fn, nbags, col_off, bd));
-    const bool full = full_cov != 0, compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
-    const int NBK = nb_tier(H);
-    const int64_t L = c->L, nb = nbags, nk = nmodels, nj = njobs, h2 = H * H, LH = L * H;
-    int64_t ncols = 0, lds_cols = 0;                              // the jobs' columns; the widest job that keeps its state in LDS
+    TRY(bags_check(c, fn, nb, a.col_off, bd));
+    const bool compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
+    auto Hof = [&](int64_t k) { return a.model_H ? a.model_H[k] : a.H_all; };
+    int64_t sumH = 0, sumH2 = 0;
+    for (int64_t k = 0; k < nk; ++k) {
+        const int64_t H = Hof(k);
+        if (H < 1 || H > VJOBS_MAX_H)
+            FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: model_H[%lld] = %lld (built for 1 <= H <= %d)", fn, (long long)k, (long long)H, VJOBS_MAX_H);
+        sumH += H;
+        sumH2 += H * H;
+    }
+    // the jobs' groups (tier of H_k, form): NBK - 1 + 2 * full; per group the widest state kept in LDS (doubles)
+    int64_t SMH = 0, SJH = 0, SJH2 = 0, grp_n[4] = {0, 0, 0, 0}, grp_lds[4] = {0, 0, 0, 0};
     bool spill = false;
     for (int64_t j = 0; j < nj; ++j) {
-        const int64_t b = job_bag[j], k = job_model[j];
+        const int64_t b = a.job_bag[j], k = a.job_model[j];
         if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
         if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_model[%lld] = %lld outside 0..nmodels-1", fn, (long long)j, (long long)k);
-        const int64_t Mb = col_off[b + 1] - col_off[b];
+        const int64_t fc = a.job_full_cov ? a.job_full_cov[j] : (int64_t)a.full_all;
+        if (a.job_full_cov && fc != 0 && fc != 1)
+            FAIL(c, VBMF_ERR_INVALID, "%s: job_full_cov[%lld] = %lld (0 or 1)", fn, (long long)j, (long long)fc);
+        const bool full = fc != 0;
+        const int64_t Mb = a.col_off[b + 1] - a.col_off[b], H = Hof(k);
         if (!full && compat && Mb < 2)
             FAIL(c, VBMF_ERR_INVALID, "%s: job %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)j);
-        ncols += Mb;                                              // (at most 2^24 terms of at most 2^60 / 8: no overflow)
-        if (vjobs_in_lds(full, NBK, (int)H, Mb)) lds_cols = std::max(lds_cols, Mb);
+        if (a.scored && !std::isfinite(a.job_trim[j])) FAIL(c, VBMF_ERR_INVALID, "%s: job_trim[%lld] is not finite", fn, (long long)j);
+        SMH += Mb * H;                                            // (at most 2^24 terms of at most 2^60 / 8: no overflow)
+        SJH += H;
+        SJH2 += H * H;
+        const int NBK = nb_tier(H), gi = NBK - 1 + (full ? 2 : 0);
+        ++grp_n[gi];
+        if (vjobs_in_lds(full, NBK, (int)H, Mb)) grp_lds[gi] = std::max(grp_lds[gi], 4 * Mb * H);
         else spill = true;
     }
     auto finite = [](const double* v, int64_t n) {
@@ -528,24 +558,53 @@ int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_
             if (!std::isfinite(v[i])) return i;
         return (int64_t)-1;
     };
-    const struct { const char* name; const double* v; int64_t per; } ins[] = {
-        {"BHat", BHat, LH}, {"SigmaB", SigmaB, h2}, {"alpha", alpha, H}, {"beta0", beta0, H},
-        {"eta0", eta0, 1}, {"zeta0", zeta0, 1}, {"sigma0", sigma0, 1}, {"ca0", ca0, 1}};
-    for (const auto& in : ins) {
-        const int64_t bad = finite(in.v, in.per * nk);
-        if (bad >= 0) FAIL(c, VBMF_ERR_INVALID, "%s: %s of model %lld is not finite (entry %lld)", fn, in.name, (long long)(bad / in.per), (long long)(bad % in.per));
+    {
+        int64_t bad = finite(a.BHat, L * sumH);
+        if (bad >= 0) {                                          // (the model by its offset)
+            int64_t k = 0, off = 0;
+            while (k + 1 < nk && off + L * Hof(k) <= bad) off += L * Hof(k++);
+            FAIL(c, VBMF_ERR_INVALID, "%s: BHat of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
+        }
+        bad = finite(a.SigmaB, sumH2);
+        if (bad >= 0) {
+            int64_t k = 0, off = 0;
+            while (k + 1 < nk && off + Hof(k) * Hof(k) <= bad) off += Hof(k) * Hof(k), ++k;
+            FAIL(c, VBMF_ERR_INVALID, "%s: SigmaB of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
+        }
+        const struct { const char* name; const double* v; bool per_col; } ins[] = {
+            {a.scored ? "a_post" : "alpha", a.a_post, true}, {a.scored ? "b_pri" : "beta0", a.b_pri, true}, {"eta0", a.eta0, false},
+            {"zeta0", a.zeta0, false}, {"sigma0", a.sigma0, false}, {"ca0", a.ca0, false}, {"a_pri", a.a_pri, true}, {"CB", a.CB, true},
+            {"delta", a.delta, true}, {"gamma", a.gamma, false}, {"gamma0", a.gamma0, false}, {"delta0", a.delta0, false}};
+        for (const auto& in : ins) {
+            if (!in.v) continue;                                 // (a call without the bound)
+            bad = finite(in.v, in.per_col ? sumH : nk);
+            if (bad < 0) continue;
+            int64_t k = bad, e = 0;
+            if (in.per_col) {
+                int64_t off = 0;
+                k = 0;
+                while (k + 1 < nk && off + Hof(k) <= bad) off += Hof(k++);
+                e = bad - off;
+            }
+            FAIL(c, VBMF_ERR_INVALID, "%s: %s of model %lld is not finite (entry %lld)", fn, in.name, (long long)k, (long long)e);
+        }
     }
     if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
-    // the upload, one block: [col_off nb + 1 | job_bag | job_model | job_off (nj each) (int64) | alpha | beta0 (nk H each) | eta0 | zeta0 |
-    //                         sigma0 | ca0 (nk each) | the bases, column-major L x H | SigmaB (nk H^2)]
-    const int64_t SMH = ncols * H;
-    const int64_t u_bag = nb + 1, u_mod = u_bag + nj, u_off = u_mod + nj, u_al = u_off + nj, u_b0 = u_al + nk * H, u_eta = u_b0 + nk * H,
-                  u_z0 = u_eta + nk, u_sig = u_z0 + nk, u_ca0 = u_sig + nk, u_b = u_ca0 + nk, u_sb = u_b + nk * LH, n_up = u_sb + nk * h2;
-    // behind it: [Bt nk L H | G nk H^2 | gd | sd (nk H) | r2 | sigma | zeta | status (nj each) | SigmaA nj H^2 | CA | A | dS | beta (the
-    //             jobs' M_b H-long blocks in job order) | P of the jobs whose state is not in LDS]; [r2 .. beta] is the read-back
-    const int64_t o_bt = n_up, o_g = o_bt + nk * LH, o_gd = o_g + nk * h2, o_sd = o_gd + nk * H, o_r2 = o_sd + nk * H, o_sig = o_r2 + nj,
-                  o_zeta = o_sig + nj, o_st = o_zeta + nj, o_sa = o_st + nj, o_ca = o_sa + nj * h2, o_a = o_ca + SMH, o_ds = o_a + SMH,
-                  o_be = o_ds + SMH, o_p = o_be + SMH, total = o_p + (spill ? SMH : 0);
+    const int64_t nsc = a.scored ? 1 : 0;
+    // the upload, one block: [col_off nb + 1 | job_bag | job_model | job_off | job_sa | job_h | idx (nj each) | model_H | b_off | k_off |
+    //                         h_off (nk each) (int64) | trim nj | a_post | b_pri | CB | delta (sum H each) | eta0 | zeta0 | sigma0 | ca0
+    //                         (nk each) | the bases, column-major L x H_k | SigmaB (H_k^2 each)]; trim, CB, delta: a scored call's only
+    const int64_t u_bag = nb + 1, u_mod = u_bag + nj, u_off = u_mod + nj, u_jsa = u_off + nj, u_jh = u_jsa + nj, u_idx = u_jh + nj,
+                  u_mh = u_idx + nj, u_bo = u_mh + nk, u_ko = u_bo + nk, u_ho = u_ko + nk, u_trim = u_ho + nk, u_al = u_trim + nsc * nj,
+                  u_b0 = u_al + sumH, u_cb = u_b0 + sumH, u_de = u_cb + nsc * sumH, u_eta = u_de + nsc * sumH, u_z0 = u_eta + nk,
+                  u_sig = u_z0 + nk, u_ca0 = u_sig + nk, u_b = u_ca0 + nk, u_sb = u_b + L * sumH, n_up = u_sb + sumH2;
+    // behind it: [Bt L sum H | G sum H^2 | gd | sd (sum H) | r2 | sigma | zeta | status (nj each) | quad 2 nj | the bases' sums VJOBS_NB nk
+    //             | SigmaA (the jobs' H_k^2) | the bound's column sums (SCORE_NS per job and column) | CA | A | dS | beta (the jobs'
+    //             M_b H_k-long blocks in job order) | P of the jobs whose state is not in LDS]; [r2 .. beta] is the read-back
+    const int64_t o_bt = n_up, o_g = o_bt + L * sumH, o_gd = o_g + sumH2, o_sd = o_gd + sumH, o_r2 = o_sd + sumH, o_sig = o_r2 + nj,
+                  o_zeta = o_sig + nj, o_st = o_zeta + nj, o_quad = o_st + nj, o_nb = o_quad + nsc * 2 * nj, o_sa = o_nb + nsc * VJOBS_NB * nk,
+                  o_sums = o_sa + SJH2, o_ca = o_sums + nsc * SCORE_NS * SJH, o_a = o_ca + SMH, o_ds = o_a + SMH, o_be = o_ds + SMH,
+                  o_p = o_be + SMH, total = o_p + (spill ? SMH : 0);
     std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
     try {
         up.resize((size_t)n_up);
@@ -554,44 +613,71 @@ int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_
         FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of models, job tables and results", fn, (long long)((n_up + o_p - o_r2) * 8));
     }
     long long* ui = reinterpret_cast<long long*>(up.data());
-    for (int64_t b = 0; b <= nb; ++b) ui[b] = col_off[b];
-    for (int64_t j = 0, off = 0; j < nj; ++j) {
-        ui[u_bag + j] = job_bag[j];
-        ui[u_mod + j] = job_model[j];
-        ui[u_off + j] = off;
-        off += col_off[job_bag[j] + 1] - col_off[job_bag[j]];
+    for (int64_t b = 0; b <= nb; ++b) ui[b] = a.col_off[b];
+    for (int64_t k = 0, bo = 0, ko = 0, ho = 0; k < nk; ++k) {
+        const int64_t H = Hof(k);
+        ui[u_mh + k] = H; ui[u_bo + k] = bo; ui[u_ko + k] = ko; ui[u_ho + k] = ho;
+        bo += L * H; ko += H * H; ho += H;
     }
-    memcpy(up.data() + u_al, alpha, (size_t)(nk * H) * 8);
-    memcpy(up.data() + u_b0, beta0, (size_t)(nk * H) * 8);
-    memcpy(up.data() + u_eta, eta0, (size_t)nk * 8);
-    memcpy(up.data() + u_z0, zeta0, (size_t)nk * 8);
-    memcpy(up.data() + u_sig, sigma0, (size_t)nk * 8);
-    memcpy(up.data() + u_ca0, ca0, (size_t)nk * 8);
-    memcpy(up.data() + u_b, BHat, (size_t)(nk * LH) * 8);
-    memcpy(up.data() + u_sb, SigmaB, (size_t)(nk * h2) * 8);
+    int64_t grp_at[4];                                            // the groups' first slots of idx
+    for (int gi = 0, at = 0; gi < 4; ++gi) { grp_at[gi] = at; at += grp_n[gi]; }
+    {
+        int64_t fill[4] = {grp_at[0], grp_at[1], grp_at[2], grp_at[3]};
+        for (int64_t j = 0, off = 0, sa = 0, jh = 0; j < nj; ++j) {
+            const int64_t b = a.job_bag[j], k = a.job_model[j], H = Hof(k);
+            const bool full = (a.job_full_cov ? a.job_full_cov[j] : (int64_t)a.full_all) != 0;
+            ui[u_bag + j] = b; ui[u_mod + j] = k; ui[u_off + j] = off; ui[u_jsa + j] = sa; ui[u_jh + j] = jh;
+            ui[u_idx + fill[nb_tier(H) - 1 + (full ? 2 : 0)]++] = j;
+            off += (a.col_off[b + 1] - a.col_off[b]) * H; sa += H * H; jh += H;
+        }
+    }
+    if (a.scored) {
+        memcpy(up.data() + u_trim, a.job_trim, (size_t)nj * 8);
+        memcpy(up.data() + u_cb, a.CB, (size_t)sumH * 8);
+        memcpy(up.data() + u_de, a.delta, (size_t)sumH * 8);
+    }
+    memcpy(up.data() + u_al, a.a_post, (size_t)sumH * 8);
+    memcpy(up.data() + u_b0, a.b_pri, (size_t)sumH * 8);
+    memcpy(up.data() + u_eta, a.eta0, (size_t)nk * 8);
+    memcpy(up.data() + u_z0, a.zeta0, (size_t)nk * 8);
+    memcpy(up.data() + u_sig, a.sigma0, (size_t)nk * 8);
+    memcpy(up.data() + u_ca0, a.ca0, (size_t)nk * 8);
+    memcpy(up.data() + u_b, a.BHat, (size_t)(L * sumH) * 8);
+    memcpy(up.data() + u_sb, a.SigmaB, (size_t)sumH2 * 8);
     auto run = [&]() -> int {
         HIPCHK(c, hipSetDevice(c->o.device));
         double* d = nullptr;
         TRY(bags_reserve(c, total, &d));
         HIPCHK(c, hipMemcpyAsync(d, up.data(), (size_t)n_up * 8, hipMemcpyHostToDevice, c->stream));
         const long long* di = reinterpret_cast<const long long*>(d);
-        hipLaunchKernelGGL(vbls_jobs_model_kernel, dim3((unsigned)nk), dim3(SCORE_THREADS), 0, c->stream, d + u_b, d + u_sb, (long long)L,
-                           (int)H, d + o_bt, d + o_g, d + o_gd, d + o_sd);
+        const VjobsModels ms{di + u_mh, di + u_bo, di + u_ko, di + u_ho};
+        hipLaunchKernelGGL(vbls_jobs_model_kernel, dim3((unsigned)nk), dim3(SCORE_THREADS), 0, c->stream, ms, d + u_b, d + u_sb, (long long)L,
+                           d + o_bt, d + o_g, d + o_gd, d + o_sd, a.scored ? d + u_cb : nullptr, a.scored ? d + u_de : nullptr,
+                           a.scored ? d + o_nb : nullptr);
         HIPCHK(c, hipGetLastError());
-        const VjobsArgs a{c->Y2, c->d2.KS, (long long)L, di, di + u_bag, di + u_mod, di + u_off, (int)H, (int)niter, compat ? 1 : 0,
-                          d + o_bt, d + o_g, d + o_gd, d + o_sd, d + u_al, d + u_b0, d + u_eta, d + u_z0, d + u_sig, d + u_ca0,
-                          spill ? d + o_p : nullptr, d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_sa, d + o_sig, d + o_zeta, d + o_r2,
-                          reinterpret_cast<long long*>(d + o_st)};
-        const size_t lds = (size_t)(vjobs_fixed_doubles(full, NBK, (int)H) + 4 * lds_cols * H) * 8;
-        dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
-            dispatch<1, 2>(NBK, [&](auto nbk) {
-                dispatch<0, 1>(full ? 1 : 0, [&](auto fc) {
-                    hipLaunchKernelGGL((vbls_jobs_kernel<decltype(ym)::value, decltype(nbk)::value, decltype(fc)::value != 0>), dim3((unsigned)nj),
-                                       dim3(SBATCH_THREADS), lds, c->stream, a);
+        VjobsArgs g{c->Y2, c->d2.KS, (long long)L, di, di + u_bag, di + u_mod, di + u_off, di + u_jsa, di + u_jh, nullptr, ms,
+                    (int)a.niter, compat ? 1 : 0,
+                    d + o_bt, d + o_g, d + u_sb, d + o_gd, d + o_sd, d + u_al, d + u_b0, d + u_eta, d + u_z0, d + u_sig, d + u_ca0,
+                    spill ? d + o_p : nullptr, d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_sa, d + o_sig, d + o_zeta, d + o_r2,
+                    reinterpret_cast<long long*>(d + o_st), a.scored ? d + u_trim : nullptr, a.scored ? d + o_sums : nullptr,
+                    a.scored ? d + o_quad : nullptr};
+        for (int gi = 0; gi < 4; ++gi) {
+            if (!grp_n[gi]) continue;
+            const int NBK = (gi & 1) + 1;
+            const bool full = gi >= 2;
+            g.idx = di + u_idx + grp_at[gi];
+            // (the fixed part does not depend on H up to VJOBS_MAX_H within a tier: H^2 <= VJOBS_STAGE)
+            const size_t lds = (size_t)(vjobs_fixed_doubles(full, NBK, 16 * NBK) + grp_lds[gi]) * 8;
+            dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+                dispatch<1, 2>(NBK, [&](auto nbk) {
+                    dispatch<0, 1>(full ? 1 : 0, [&](auto fc) {
+                        hipLaunchKernelGGL((vbls_jobs_kernel<decltype(ym)::value, decltype(nbk)::value, decltype(fc)::value != 0>),
+                                           dim3((unsigned)grp_n[gi]), dim3(SBATCH_THREADS), lds, c->stream, g);
+                    });
                 });
             });
-        });
-        HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipGetLastError());
+        }
         HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
         return VBMF_OK;
     };
@@ -601,16 +687,107 @@ int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_
         return rc;
     }
     auto at = [&](int64_t o_x) { return res.data() + (o_x - o_r2); };   // block x of the read-back
-    if (r2) memcpy(r2, at(o_r2), (size_t)nj * 8);
-    if (sigmaHat) memcpy(sigmaHat, at(o_sig), (size_t)nj * 8);
-    if (zeta) memcpy(zeta, at(o_zeta), (size_t)nj * 8);
-    memcpy(status, at(o_st), (size_t)nj * 8);
-    if (SigmaA) memcpy(SigmaA, at(o_sa), (size_t)(nj * h2) * 8);   // symmetric: row- and column-major alike
-    if (CA) memcpy(CA, at(o_ca), (size_t)SMH * 8);
-    if (ATVecHat) memcpy(ATVecHat, at(o_a), (size_t)SMH * 8);
-    if (diagSigmaATVec) memcpy(diagSigmaATVec, at(o_ds), (size_t)SMH * 8);
-    if (beta) memcpy(beta, at(o_be), (size_t)SMH * 8);
+    int64_t* st = reinterpret_cast<int64_t*>(at(o_st));
+    if (a.lb) {
+        // the bound of every job from its sums (lb_assemble); a job whose bound or sums are not finite fails like one the device flagged
+        const double nan = std::nan("");
+        std::vector<int64_t> h_off((size_t)nk);
+        for (int64_t k = 0, ho = 0; k < nk; ho += Hof(k), ++k) h_off[(size_t)k] = ho;
+        LbGroup grp[VJOBS_MAX_H];
+        for (int64_t j = 0, off = 0, sa = 0, jh = 0; j < nj; ++j) {
+            const int64_t b = a.job_bag[j], k = a.job_model[j], H = Hof(k), ho = h_off[(size_t)k];
+            const double Mb = (double)(a.col_off[b + 1] - a.col_off[b]);
+            const int64_t n = (a.col_off[b + 1] - a.col_off[b]) * H;
+            double v = nan;
+            if (st[j] == 0) {
+                const bool trimmed = a.job_trim[j] >= 0.0, cut = trimmed && !a.grouped;
+                const double* sb = at(o_sums) + (size_t)jh * SCORE_NS;
+                const double* quad = at(o_quad) + 2 * j;
+                const double* mb = at(o_nb) + VJOBS_NB * k;
+                double n_keep = 0, s_caq = 0, s_logds = 0;
+                for (int64_t h = 0; h < H; ++h) {
+                    const double* q = sb + (size_t)h * SCORE_NS;
+                    n_keep += q[2]; s_caq += q[5]; s_logds += q[6];
+                    // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
+                    grp[h] = LbGroup{cut ? q[2] : Mb, cut ? q[3] : q[0], cut ? q[4] : q[1], a.a_pri[ho + h], a.b_pri[ho + h], a.a_post[ho + h]};
+                }
+                LbSums s{};
+                s.L = (double)L; s.H = (double)H; s.M = Mb;
+                s.MH = trimmed ? n_keep : Mb * (double)H;
+                s.sig = at(o_sig)[j]; s.zeta = at(o_zeta)[j]; s.eta = a.eta0[k] + 0.5 * (double)L * Mb;
+                s.hyp.gamma0 = a.gamma0[k]; s.hyp.delta0 = a.delta0[k]; s.hyp.eta0 = a.eta0[k]; s.hyp.zeta0 = a.zeta0[k];
+                s.quad = at(o_r2)[j] + s.L * quad[0] + quad[1];
+                s.s_caq = s_caq; s.s_logds = s_logds;
+                s.cbq = mb[0]; s.sumcb = mb[1]; s.sumlogdelta = mb[2]; s.logdet_sb = mb[3]; s.gamma_ = a.gamma[k];
+                s.g = grp; s.ng = (int)H;
+                v = lb_assemble(s, a.clamp);
+                if (!std::isfinite(v) || !std::isfinite(s.quad) || !std::isfinite(s_caq) || !std::isfinite(s_logds)) {
+                    v = nan;
+                    st[j] = 1;
+                    at(o_r2)[j] = at(o_sig)[j] = at(o_zeta)[j] = nan;
+                    std::fill(at(o_sa) + sa, at(o_sa) + sa + H * H, nan);
+                    for (const int64_t o_x : {o_ca, o_a, o_ds, o_be}) std::fill(at(o_x) + off, at(o_x) + off + n, nan);
+                }
+            }
+            a.lb[j] = v;
+            off += n; sa += H * H; jh += H;
+        }
+    }
+    if (a.r2) memcpy(a.r2, at(o_r2), (size_t)nj * 8);
+    if (a.sigmaHat) memcpy(a.sigmaHat, at(o_sig), (size_t)nj * 8);
+    if (a.zeta) memcpy(a.zeta, at(o_zeta), (size_t)nj * 8);
+    memcpy(a.status, st, (size_t)nj * 8);
+    if (a.SigmaA) memcpy(a.SigmaA, at(o_sa), (size_t)SJH2 * 8);     // symmetric: row- and column-major alike
+    if (a.CA) memcpy(a.CA, at(o_ca), (size_t)SMH * 8);
+    if (a.ATVecHat) memcpy(a.ATVecHat, at(o_a), (size_t)SMH * 8);
+    if (a.diagSigmaATVec) memcpy(a.diagSigmaATVec, at(o_ds), (size_t)SMH * 8);
+    if (a.beta) memcpy(a.beta, at(o_be), (size_t)SMH * 8);
     return VBMF_OK;
+}
+
+// vbls! of the ARD families (examples/mil_util.jl:187-197) for a list of (bag, model) jobs, every model with its own fp64 basis, and
+// each job's norm(Y - BHat*AHat')^2 (:518-521) in the same launch: the "dual" classifier of :515-530 for every fold of
+// validate_with_cvs at once.  The context supplies Y only.  Two launches (per model, per job) and one synchronising read-back,
+// whatever nmodels and njobs are: vjobs_call with one H and one form.
+int vbmf_sparse_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t H, int64_t niter, int full_cov,
+                                 int64_t nmodels, const double* BHat, const double* SigmaB, const double* alpha, const double* beta0,
+                                 const double* eta0, const double* zeta0, const double* sigma0, const double* ca0, int64_t njobs,
+                                 const int64_t* job_bag, const int64_t* job_model, double* r2, double* ATVecHat, double* diagSigmaATVec,
+                                 double* CA, double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_fixed_basis_jobs";
+    if (H < 1 || H > VJOBS_MAX_H) FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: H = %lld (built for 1 <= H <= %d)", fn, (long long)H, VJOBS_MAX_H);
+    VjobsCall a{};
+    a.fn = fn; a.nbags = nbags; a.col_off = col_off; a.niter = niter;
+    a.nmodels = nmodels; a.H_all = H; a.BHat = BHat; a.SigmaB = SigmaB; a.b_pri = beta0; a.a_post = alpha; a.eta0 = eta0; a.zeta0 = zeta0;
+    a.sigma0 = sigma0; a.ca0 = ca0;
+    a.njobs = njobs; a.job_bag = job_bag; a.job_model = job_model; a.full_all = full_cov != 0;
+    a.r2 = r2; a.ATVecHat = ATVecHat; a.diagSigmaATVec = diagSigmaATVec; a.CA = CA; a.beta = beta; a.SigmaA = SigmaA; a.sigmaHat = sigmaHat;
+    a.zeta = zeta; a.status = status;
+    return vjobs_call(c, a);
+}
+
+// factorize_bag (examples/mil_util.jl:393-416) and the bound of each fit (:502-514) for a list of (bag, model) jobs: the jobs of
+// vbmf_sparse_fixed_basis_jobs with a rank per model, a form and a trim per job, and lowerBound / lowerBoundTrimmed of every job
+// assembled on the host (lb_assemble) from the sums the job kernel leaves.
+int vbmf_sparse_scored_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, int clamp, int grouped, int64_t nmodels,
+                            const int64_t* model_H, const double* BHat, const double* SigmaB, const double* CB, const double* delta,
+                            const double* gamma, const double* gamma0, const double* delta0, const double* a_pri, const double* b_pri,
+                            const double* a_post, const double* eta0, const double* zeta0, const double* sigma0, const double* ca0,
+                            int64_t njobs, const int64_t* job_bag, const int64_t* job_model, const int64_t* job_full_cov,
+                            const double* job_trim, double* lb, double* r2, double* ATVecHat, double* diagSigmaATVec, double* CA,
+                            double* beta, double* SigmaA, double* sigmaHat, double* zeta, int64_t* status) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_sparse_scored_jobs";
+    VjobsCall a{};
+    a.fn = fn; a.nbags = nbags; a.col_off = col_off; a.niter = niter;
+    a.nmodels = nmodels; a.model_H = model_H; a.BHat = BHat; a.SigmaB = SigmaB; a.CB = CB; a.delta = delta; a.gamma = gamma; a.gamma0 = gamma0;
+    a.delta0 = delta0; a.a_pri = a_pri; a.b_pri = b_pri; a.a_post = a_post; a.eta0 = eta0; a.zeta0 = zeta0; a.sigma0 = sigma0; a.ca0 = ca0;
+    a.njobs = njobs; a.job_bag = job_bag; a.job_model = job_model; a.job_full_cov = job_full_cov; a.job_trim = job_trim;
+    a.scored = true; a.clamp = clamp; a.grouped = grouped;
+    a.lb = lb; a.r2 = r2; a.ATVecHat = ATVecHat; a.diagSigmaATVec = diagSigmaATVec; a.CA = CA; a.beta = beta; a.SigmaA = SigmaA;
+    a.sigmaHat = sigmaHat; a.zeta = zeta; a.status = status;
+    return vjobs_call(c, a);
 }
 
 // the widest bag whose job keeps its state in LDS at this H and form (vjobs_in_lds): the tests place a bag on either side of it

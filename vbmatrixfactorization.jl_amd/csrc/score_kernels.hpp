@@ -12,7 +12,8 @@
 //                        B is the context's BHat as stored (fp32 row-major [Lp][Hp], the values vbmf_get_state returns), widened
 //                        to fp64; A is the caller's fp64 AHat.
 //   bag_resid_fold_kernel  r2[b] = the bag's slice partials, summed in slice order
-//   bag_lb_sums_kernel   one workgroup per bag: the M_b*H-long sums of lowerBound per column h (SCORE_NS values each) and the two
+//   bag_lb_sums_kernel   one workgroup per bag: the M_b*H-long sums of lowerBound per column h (SCORE_NS values each; lb_column_sums,
+//                        the __device__ function vbls_jobs_kernel of vbls_jobs_kernels.hpp calls on its own state) and the two
 //                        H x H contractions of its data term
 // Least squares against a caller's fp64 basis (vbmf_bag_least_squares; ols / rls of examples/mil_util.jl:159-171 and the
 // norm(Y - BHat*AT) of :483-484), H <= 64.  B travels as fp64 row-major [L][H] (reads coalesce over h); nothing of the context's state
@@ -335,21 +336,14 @@ __global__ __launch_bounds__(SCORE_THREADS) void bag_ls_jobs_kernel(const uint4*
     ls_slice<MODE>(Y2, KSpad, L, bs.Bt + bs.b_off[k], H, K + bs.k_off[k], m0, nc, Xs, part ? part + w : nullptr, ls, red);
 }
 
-// a, dS, CA, beta: M*H in vec(A') order (index m*H + h); SA: nbags x H x H.  sums: [nbags][H][SCORE_NS];
-// quad: [nbags][2] = { sum_m a_m' SigmaB a_m = tr(A_b'A_b SigmaB),  tr(SigmaA_b (B'B + L SigmaB)) }.
+// The per-column sums of one bag (SCORE_NS per column h into out[h * SCORE_NS ..]), by the whole workgroup of SCORE_THREADS.  a, dS, CA,
+// beta: the bag's own M_b H-long blocks in vec(A') order (LDS or global).  sh: SCORE_THREADS * SCORE_NS doubles of LDS.
 // Thread (h, s) of the first (SCORE_THREADS / H) * H takes the bag's columns m = s, s + S, ... of vec column h; the S shares meet in
-// LDS in slice order, so a bag's sums depend on its own entries only.
-__global__ __launch_bounds__(SCORE_THREADS) void bag_lb_sums_kernel(const double* __restrict__ a, const double* __restrict__ dS,
-                                                                    const double* __restrict__ CA, const double* __restrict__ beta,
-                                                                    const double* __restrict__ SA, const double* __restrict__ st,
-                                                                    StateLayout lay, int H, double Lg,
-                                                                    const long long* __restrict__ col_off, double trim,
-                                                                    double* __restrict__ sums, double* __restrict__ quad) {
-    __shared__ double sh[SCORE_THREADS][SCORE_NS];
-    __shared__ double red[SCORE_THREADS / 64];
-    const int b = blockIdx.x;
-    const long long m0 = col_off[b];
-    const int Mb = (int)(col_off[b + 1] - m0);
+// LDS in slice order, so a bag's sums depend on its own entries only.  F32CMP: the mask compares the fp32 rounding of a
+// (vbmf_sparse_lower_bound_batched, like the whole-context entry) or a itself (src/vbmf_sparse.jl:481; vbmf_sparse_scored_jobs).
+template <bool F32CMP>
+__device__ __forceinline__ void lb_column_sums(const double* a, const double* dS, const double* CA, const double* beta, int H, int Mb,
+                                               double trim, double* sh, double* __restrict__ out) {
     const int Hc = H < SCORE_THREADS ? H : SCORE_THREADS;             // columns per round (H > 256: several rounds)
     const int S = SCORE_THREADS / Hc;
     for (int h0 = 0; h0 < H; h0 += Hc) {
@@ -357,27 +351,43 @@ __global__ __launch_bounds__(SCORE_THREADS) void bag_lb_sums_kernel(const double
         double v[SCORE_NS] = {0, 0, 0, 0, 0, 0, 0};
         if (s < S && h < H) {
             for (int m = s; m < Mb; m += S) {
-                const long long i = (m0 + m) * H + h;
+                const long long i = (long long)m * H + h;
                 const double av = a[i], ds = dS[i], ca = CA[i], lb = log(beta[i]);
                 v[0] += lb; v[1] += ca;
-                if (trim < 0.0 || fabs((double)(float)av) > trim) {
+                if (trim < 0.0 || fabs(F32CMP ? (double)(float)av : av) > trim) {
                     v[2] += 1.0; v[3] += lb; v[4] += ca; v[5] += ca * (av * av + ds); v[6] += log(ds);
                 }
             }
         }
 #pragma unroll
-        for (int k = 0; k < SCORE_NS; ++k) sh[threadIdx.x][k] = v[k];
+        for (int k = 0; k < SCORE_NS; ++k) sh[threadIdx.x * SCORE_NS + k] = v[k];
         __syncthreads();
         if (s == 0 && h < H) {
 #pragma unroll
             for (int k = 0; k < SCORE_NS; ++k) {
                 double t = 0.0;
-                for (int q = 0; q < S; ++q) t += sh[q * Hc + hh][k];
-                sums[((long long)b * H + h) * SCORE_NS + k] = t;
+                for (int q = 0; q < S; ++q) t += sh[(q * Hc + hh) * SCORE_NS + k];
+                out[(long long)h * SCORE_NS + k] = t;
             }
         }
         __syncthreads();
     }
+}
+
+// a, dS, CA, beta: M*H in vec(A') order (index m*H + h); SA: nbags x H x H.  sums: [nbags][H][SCORE_NS] (lb_column_sums);
+// quad: [nbags][2] = { sum_m a_m' SigmaB a_m = tr(A_b'A_b SigmaB),  tr(SigmaA_b (B'B + L SigmaB)) }.
+__global__ __launch_bounds__(SCORE_THREADS) void bag_lb_sums_kernel(const double* __restrict__ a, const double* __restrict__ dS,
+                                                                    const double* __restrict__ CA, const double* __restrict__ beta,
+                                                                    const double* __restrict__ SA, const double* __restrict__ st,
+                                                                    StateLayout lay, int H, double Lg,
+                                                                    const long long* __restrict__ col_off, double trim,
+                                                                    double* __restrict__ sums, double* __restrict__ quad) {
+    __shared__ double sh[SCORE_THREADS * SCORE_NS];
+    __shared__ double red[SCORE_THREADS / 64];
+    const int b = blockIdx.x;
+    const long long m0 = col_off[b];
+    const int Mb = (int)(col_off[b + 1] - m0);
+    lb_column_sums<true>(a + m0 * H, dS + m0 * H, CA + m0 * H, beta + m0 * H, H, Mb, trim, sh, sums + (long long)b * H * SCORE_NS);
     const double* SB = st + lay.SB();
     const double* GB = st + lay.GB();
     double qa = 0.0;

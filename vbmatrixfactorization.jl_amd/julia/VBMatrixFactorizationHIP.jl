@@ -14,7 +14,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        vbls!, vbls_batch!, vbmf_batch!, row_gram_batch, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
-       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs, sparse_fixed_basis_jobs,
+       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs, sparse_fixed_basis_jobs, sparse_scored_jobs,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!, set_Y_gather!
 
@@ -1240,6 +1240,63 @@ function sparse_fixed_basis_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, H::Int
     blocks(v) = [v[off[j]+1:off[j+1]] for j in 1:nj]
     return (r2 = r2, sigmaHat = sg, zeta = zeta, status = status, SigmaA = SA, ATVecHat = blocks(A), diagSigmaATVec = blocks(dS),
             CA = blocks(CA), beta = blocks(beta))
+end
+
+"""
+    sparse_scored_jobs(ctx, col_off, BHat, SigmaB, CB, delta, gamma, gamma0, delta0, a_pri, b_pri, a_post, eta0, zeta0, sigma0, ca0,
+                       job_bag, job_model, job_full_cov, job_trim, niter; clamp, grouped)
+
+factorize_bag (examples/mil_util.jl:393-416) and its scores for a list of (bag, model) jobs in ONE device call
+(vbmf_sparse_scored_jobs) -- the "lower_bound" and "min_err" classifiers of examples/mil_util.jl:493-514 for every fold at once.  `ctx`
+holds every bag side by side (col_off: 0-based offsets); only its Y is read.  Model k has its own rank H_k = size(BHat[k], 2) <= 32:
+`BHat[k]` (L x H_k), `SigmaB[k]` (H_k x H_k), `CB[k]`, `delta[k]`, `a_pri[k]`, `b_pri[k]`, `a_post[k]` (H_k each), and the scalars
+`gamma[k]`, `gamma0[k]`, `delta0[k]`, `eta0[k]`, `zeta0[k]`, `sigma0[k]`, `ca0[k]`.  Job j runs bag `job_bag[j]` against model
+`job_model[j]` (both 1-based) in the full_cov form where `job_full_cov[j]`, and is scored with lowerBound (`job_trim[j] < 0`) or
+lowerBoundTrimmed(`job_trim[j]`).  Returns a named tuple: lb, r2, sigmaHat, zeta, status (per job; status 1 = a failed job, NaN in its
+outputs), and SigmaA, ATVecHat, diagSigmaATVec, CA, beta as one array per job.
+"""
+function sparse_scored_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, BHat::Vector{Matrix{Float64}}, SigmaB::Vector{Matrix{Float64}},
+                            CB::Vector{Vector{Float64}}, delta::Vector{Vector{Float64}}, gamma::Vector{Float64}, gamma0::Vector{Float64},
+                            delta0::Vector{Float64}, a_pri::Vector{Vector{Float64}}, b_pri::Vector{Vector{Float64}},
+                            a_post::Vector{Vector{Float64}}, eta0::Vector{Float64}, zeta0::Vector{Float64}, sigma0::Vector{Float64},
+                            ca0::Vector{Float64}, job_bag::AbstractVector{<:Integer}, job_model::AbstractVector{<:Integer},
+                            job_full_cov::AbstractVector{Bool}, job_trim::Vector{Float64}, niter::Int; clamp::Bool = true,
+                            grouped::Bool = false)
+    nb, nk, nj = length(col_off) - 1, length(BHat), length(job_bag)
+    (nk >= 1 && all(v -> length(v) == nk, (SigmaB, CB, delta, gamma, gamma0, delta0, a_pri, b_pri, a_post, eta0, zeta0, sigma0, ca0))) ||
+        error("sparse_scored_jobs: every per-model input needs one entry per model, at least one model")
+    (nj >= 1 && length(job_model) == nj && length(job_full_cov) == nj && length(job_trim) == nj) ||
+        error("sparse_scored_jobs: job_bag, job_model, job_full_cov and job_trim must have one entry per job, at least one")
+    L = size(BHat[1], 1)
+    Hs = Int64[size(B, 2) for B in BHat]
+    all(k -> size(BHat[k], 1) == L && size(SigmaB[k]) == (Hs[k], Hs[k]) &&
+             all(v -> length(v[k]) == Hs[k], (CB, delta, a_pri, b_pri, a_post)), 1:nk) ||
+        error("sparse_scored_jobs: every model needs BHat L x H, SigmaB H x H and CB, delta, a_pri, b_pri, a_post of length H")
+    all(j -> 1 <= job_bag[j] <= nb && 1 <= job_model[j] <= nk, 1:nj) || error("sparse_scored_jobs: a job names a bag or a model that is not there")
+    cat1(vs) = reduce(vcat, [vec(v) for v in vs])
+    jb, jk = Int64[b - 1 for b in job_bag], Int64[k - 1 for k in job_model]
+    jf = Int64[f ? 1 : 0 for f in job_full_cov]
+    Hj = Int64[Hs[k] for k in job_model]
+    off = Int64[0; cumsum([Hj[j] * (col_off[jb[j]+2] - col_off[jb[j]+1]) for j in 1:nj])]
+    soff = Int64[0; cumsum(Hj .* Hj)]
+    lb, r2 = Array{Float64}(undef, nj), Array{Float64}(undef, nj)
+    sg, zeta = Array{Float64}(undef, nj), Array{Float64}(undef, nj)
+    A, dS = Array{Float64}(undef, off[end]), Array{Float64}(undef, off[end])
+    CA, beta = Array{Float64}(undef, off[end]), Array{Float64}(undef, off[end])
+    SA = Array{Float64}(undef, soff[end])
+    status = Array{Int64}(undef, nj)
+    chk(ctx, ccall((:vbmf_sparse_scored_jobs, libvbmf), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Cint, Cint, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        ctx, nb, col_off, niter, Cint(clamp), Cint(grouped), nk, Hs, cat1(BHat), cat1(SigmaB), cat1(CB), cat1(delta), gamma, gamma0, delta0,
+        cat1(a_pri), cat1(b_pri), cat1(a_post), eta0, zeta0, sigma0, ca0, nj, jb, jk, jf, job_trim, lb, r2, A, dS, CA, beta, SA, sg, zeta,
+        status))
+    blocks(v) = [v[off[j]+1:off[j+1]] for j in 1:nj]
+    return (lb = lb, r2 = r2, sigmaHat = sg, zeta = zeta, status = status,
+            SigmaA = [reshape(SA[soff[j]+1:soff[j+1]], Hj[j], Hj[j]) for j in 1:nj], ATVecHat = blocks(A),
+            diagSigmaATVec = blocks(dS), CA = blocks(CA), beta = blocks(beta))
 end
 
 "vbmf_dual! -- src/vbmf_dual.jl:455-530 (returns d); est_priors: the hyper-prior fits of :393-434 run on the device"
