@@ -642,10 +642,89 @@ __device__ __forceinline__ double lanczos_lambda_max(const double* __restrict__ 
 // of the same matrix measured 2.9 ms on one CU; this is a few tens of microseconds.
 constexpr int EIG_NSQ = 10;
 
+// One squaring of the WIDE form (512 threads, R = 4): the raw C = T * T' on the upper block triangle only, into nxt.
+// c_ij and c_ji are the same products in the same order (fmaf(x, y, c) = fmaf(y, x, c)), bitwise equal for ANY T, so the 256-thread
+// form computes every off-diagonal entry twice.  Here C is cut into a 4 x 4 grid of 16 x 16 blocks and each of the 10 blocks
+// (Ib <= Jb) goes to one 32-lane half of a wave -- five waves, so one SIMD holds two -- as 8 x 4 thread tiles of 2 x 4 entries: 6
+// ds_read_b128 per 32 FMAs.  Every entry is the chain of the 256-thread form: k ascending from 0, x, y, z, w within a float4, from 0.f.
+// Both operands are ROW reads, as there, so nothing is assumed about the symmetry of the input.  A quad of lanes reads four
+// neighbouring column tiles and the eight quads of a half eight neighbouring row tiles: under any grouping of whole quads a
+// ds_read_b128 sees distinct rows 4 banks apart or one row (rows r and r + 16 share banks at LD = NP + 4).  The diagonal blocks are
+// computed whole (6 % of the work).  The caller's barrier follows.
+// What the loop is bound by (profiles/lambda_sq_parts.txt): NOT the FMA issue rate alone.  The 256-thread form's loop, as compiled, is
+// v_pk_fma_f32 at full rate plus 8 ds_read_b128 per step that it waits for before it multiplies; the triangle halves the FMAs, but
+// 2 x 4 tiles read as many bytes from LDS as 4 x 4 tiles on the whole matrix (480 against 512 ds_read_b128 per squaring), and a first
+// version that waited for each step's reads in the same way took the parent's time per squaring (3.8 against 3.6 us at H = 64).  So:
+//   * the reads of k-step s + 1 are issued ahead of the FMAs of step s, in two register sets, and the scheduler is held to that order
+//     (sched_barrier): left alone it either gathers the reads of two steps in front of their FMAs again, or -- with fmaf() -- packs
+//     pairs of chains into v_pk_fma_f32 at the price of a v_mov_b32 per FMA pair, which was no faster than the parent;
+//   * the FMAs are written as v_fmac_f32, one chain step each: the same fused multiply-add as fmaf() (one rounding, the mode
+//     register's denormal setting), which the packer cannot touch.
+// 2.4 us per squaring at H = 64 (3.6 in the 256-thread form).  At R = 2 (1 x 2 tiles) the same form measured no gain -- ten squarings
+// 20.0 -> 19.5-20.0 us: 0.8 us of each squaring's 1.1 are the fp64 sum, its tree and the scale -- so R = 2 keeps the 256-thread form.
+template <int R>
+__device__ __forceinline__ void eig_square_tri(const float* __restrict__ cur, float* __restrict__ nxt) {
+    static_assert(R == 4, "thread tiles of 2 x 4 on a 64 x 64 matrix");
+    constexpr int TR = R / 2, TC = R, NP = 16 * R, LD = NP + 4;
+    const int hw = threadIdx.x >> 5;                             // block = 32-lane half: (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+    if (hw >= 10) return;
+    const int Ib = hw < 4 ? 0 : (hw < 7 ? 1 : (hw < 9 ? 2 : 3));
+    const int Jb = hw < 4 ? hw : (hw < 7 ? hw - 3 : (hw < 9 ? hw - 5 : 3));
+    const int l = threadIdx.x & 31;
+    const int i0 = (8 * Ib + (l >> 2)) * TR, j0 = (4 * Jb + (l & 3)) * TC;     // i0 + TR <= NP, j0 + TC <= NP
+    float c[TR][TC];
+#pragma unroll
+    for (int a = 0; a < TR; ++a)
+#pragma unroll
+        for (int b = 0; b < TC; ++b) c[a][b] = 0.f;
+    const float* pa = cur + i0 * LD;
+    const float* pb = cur + j0 * LD;
+    float4 ai[2][TR], bj[2][TC];
+    auto load = [&](int s, int k) {
+#pragma unroll
+        for (int a = 0; a < TR; ++a) ai[s][a] = *reinterpret_cast<const float4*>(pa + a * LD + k);
+#pragma unroll
+        for (int b = 0; b < TC; ++b) bj[s][b] = *reinterpret_cast<const float4*>(pb + b * LD + k);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mac = [&](int s) {
+#pragma unroll
+        for (int a = 0; a < TR; ++a)
+#pragma unroll
+            for (int b = 0; b < TC; ++b) {
+                asm("v_fmac_f32 %0, %1, %2" : "+v"(c[a][b]) : "v"(ai[s][a].x), "v"(bj[s][b].x));
+                asm("v_fmac_f32 %0, %1, %2" : "+v"(c[a][b]) : "v"(ai[s][a].y), "v"(bj[s][b].y));
+                asm("v_fmac_f32 %0, %1, %2" : "+v"(c[a][b]) : "v"(ai[s][a].z), "v"(bj[s][b].z));
+                asm("v_fmac_f32 %0, %1, %2" : "+v"(c[a][b]) : "v"(ai[s][a].w), "v"(bj[s][b].w));
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    load(0, 0);
+#pragma unroll
+    for (int k = 0; k < NP; k += 8) {
+        load(1, k + 4);
+        mac(0);
+        if (k + 8 < NP) load(0, k + 8);
+        mac(1);
+    }
+#pragma unroll
+    for (int a = 0; a < TR; ++a)
+#pragma unroll
+        for (int b = 0; b < TC; ++b) nxt[(i0 + a) * LD + j0 + b] = c[a][b];
+}
+
 // which = 0: GD -> S_LAMD, 1: GB -> S_LAMB_NEW.  256 threads, 2*NP*(NP+4) floats of LDS (NP = 16R).
+// wide (R = 4; uniform; the block then has 512 threads -- eig_kernel and ctrl_chain_kernel, never a pass launch, whose control
+// workgroups have no spare waves at H <= 64): the products of a squaring come from eig_square_tri.  Every value stored is bitwise the
+// 256-thread form's: the raw entries go through LDS, the first 256 threads -- (ty, tx) of that form -- read their R x R cyclic
+// entries back (the lower ones from their mirror), form the Frobenius sum in its (a, b) order, block_sum runs its tree on those same
+// 256 positions (ctrl_nthreads() = 256: the other waves' partial sums, exact zeros, are not even read), and the owners scale and
+// store what they hold.  One barrier more per squaring than the 256-thread form.  The first load of the matrix is dealt over all 512
+// threads (one correctly rounded fp64 division per entry, whoever does it).  tests/test_gpu_lambda_max_bits.py holds lambda to the
+// 256-thread form's bits.
 template <int R>
 __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateLayout lay, int H, int spectral, int which,
-                                        const int* __restrict__ ints, float* ldsf, int slot, bool check_stop = true) {
+                                        const int* __restrict__ ints, float* ldsf, int slot, bool check_stop, bool wide) {
     __shared__ double red[16];
     __shared__ int s_arg;
     if (check_stop && load_stop(ints)) return;
@@ -665,7 +744,7 @@ __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateL
     float* A0 = ldsf;
     float* A1 = ldsf + NP * LD;
     const int tx = threadIdx.x % T, ty = threadIdx.x / T;
-    for (int t = threadIdx.x; t < NP * NP; t += ctrl_nthreads()) {
+    for (int t = threadIdx.x; t < NP * NP; t += wide ? 512 : ctrl_nthreads()) {
         const int i = t / NP, j = t - i * NP;
         A0[i * LD + j] = (i < H && j < H) ? (float)(G[(long long)i * Hp + j] / tr) : 0.f;   // |G_ij| <= tr: no overflow
     }
@@ -674,37 +753,57 @@ __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateL
     float* nxt = A1;
     for (int sq = 0; sq < EIG_NSQ; ++sq) {
         float c[R][R];
+        if (wide) {
+            // upper block triangle of C on five waves, raw into nxt; the 256 owners pick their old entries up from there
+            if constexpr (R == 4) eig_square_tri<R>(cur, nxt);
+            __syncthreads();
+            if (threadIdx.x < 256) {
 #pragma unroll
-        for (int a = 0; a < R; ++a)
+                for (int a = 0; a < R; ++a)
 #pragma unroll
-            for (int b = 0; b < R; ++b) c[a][b] = 0.f;
-        for (int k = 0; k < NP; k += 4) {                    // C = T * T' (T symmetric): both operands are row reads
-            float4 ai[R], bj[R];
-#pragma unroll
-            for (int a = 0; a < R; ++a) ai[a] = *reinterpret_cast<const float4*>(cur + (ty + T * a) * LD + k);
-#pragma unroll
-            for (int b = 0; b < R; ++b) bj[b] = *reinterpret_cast<const float4*>(cur + (tx + T * b) * LD + k);
+                    for (int b = 0; b < R; ++b) {
+                        const int i = ty + T * a, j = tx + T * b;
+                        c[a][b] = nxt[min(i, j) * LD + max(i, j)];
+                    }
+            }
+        } else {
 #pragma unroll
             for (int a = 0; a < R; ++a)
 #pragma unroll
-                for (int b = 0; b < R; ++b) {
-                    c[a][b] = fmaf(ai[a].x, bj[b].x, c[a][b]);
-                    c[a][b] = fmaf(ai[a].y, bj[b].y, c[a][b]);
-                    c[a][b] = fmaf(ai[a].z, bj[b].z, c[a][b]);
-                    c[a][b] = fmaf(ai[a].w, bj[b].w, c[a][b]);
-                }
+                for (int b = 0; b < R; ++b) c[a][b] = 0.f;
+            for (int k = 0; k < NP; k += 4) {                // C = T * T' (T symmetric): both operands are row reads
+                float4 ai[R], bj[R];
+#pragma unroll
+                for (int a = 0; a < R; ++a) ai[a] = *reinterpret_cast<const float4*>(cur + (ty + T * a) * LD + k);
+#pragma unroll
+                for (int b = 0; b < R; ++b) bj[b] = *reinterpret_cast<const float4*>(cur + (tx + T * b) * LD + k);
+#pragma unroll
+                for (int a = 0; a < R; ++a)
+#pragma unroll
+                    for (int b = 0; b < R; ++b) {
+                        c[a][b] = fmaf(ai[a].x, bj[b].x, c[a][b]);
+                        c[a][b] = fmaf(ai[a].y, bj[b].y, c[a][b]);
+                        c[a][b] = fmaf(ai[a].z, bj[b].z, c[a][b]);
+                        c[a][b] = fmaf(ai[a].w, bj[b].w, c[a][b]);
+                    }
+            }
         }
+        const bool owner = !wide || threadIdx.x < 256;       // (ty, tx) of the 256-thread form: its sum, its tree, its stores
         double ss = 0.0;
+        if (owner) {
 #pragma unroll
-        for (int a = 0; a < R; ++a)
+            for (int a = 0; a < R; ++a)
 #pragma unroll
-            for (int b = 0; b < R; ++b) ss += (double)c[a][b] * (double)c[a][b];
+                for (int b = 0; b < R; ++b) ss += (double)c[a][b] * (double)c[a][b];
+        }
         ss = block_sum(ss, red);                             // ||T^2||_F^2 with ||T||_F = 1: -> 1 iff T is a rank-1 projector
         const float sc = (ss > 0.0) ? (float)(1.0 / sqrt(ss)) : 0.f;
+        if (owner) {                                         // (wide: every read of the raw entries is behind block_sum's barriers)
 #pragma unroll
-        for (int a = 0; a < R; ++a)
+            for (int a = 0; a < R; ++a)
 #pragma unroll
-            for (int b = 0; b < R; ++b) nxt[(ty + T * a) * LD + tx + T * b] = c[a][b] * sc;
+                for (int b = 0; b < R; ++b) nxt[(ty + T * a) * LD + tx + T * b] = c[a][b] * sc;
+        }
         __syncthreads();
         float* tmp = cur; cur = nxt; nxt = tmp;
         if (sq > 0 && fabs(ss - 1.0) < 1e-5) break;          // uniform: converged to the dominant projector (the fp64
@@ -749,11 +848,14 @@ __device__ __forceinline__ void eig_squaring_dev(double* __restrict__ st, StateL
 // no other workgroup of the launch can raise the flag meanwhile: threads that disagreed would leave block_sum's barriers unmatched).
 // spectral = 0: Frobenius surrogate (trace) instead.  256 threads (the first 256 of a 512-thread pass launch).  H <= 64: repeated squaring
 // (2 * NP * (NP + 4) floats of LDS); 64 < H <= 128: Lanczos (EIG_LDS_BYTES).
-template <int R>
+// WIDE_OK: the caller is a kernel of the chain's own (eig_kernel, ctrl_chain_kernel), which the host launches with 512 threads
+// exactly where the wide squaring applies (eig_wide_launch in vbmf_hip.hip: R = 4 and not the Lanczos switch) and with 256 otherwise.
+template <int R, bool WIDE_OK = false>
 __device__ __forceinline__ void eig_dev(double* __restrict__ st, StateLayout lay, int H, int spectral, int which,
                                         const int* __restrict__ ints, float* ldsf, int slot, bool check_stop = true) {
     if (R <= 4 && __builtin_expect(!(spectral & 2), 1)) {       // (uniform over the launch; the other branch is a switch: cold)
-        eig_squaring_dev<R>(st, lay, H, spectral & 1, which, ints, ldsf, slot, check_stop);
+        const bool wide = WIDE_OK && R == 4 && blockDim.x == 512u;
+        eig_squaring_dev<R>(st, lay, H, spectral & 1, which, ints, ldsf, slot, check_stop, wide);
     } else {
         __shared__ double red[16];
         if (check_stop && load_stop(ints)) return;
@@ -773,12 +875,12 @@ __device__ __forceinline__ void eig_dev(double* __restrict__ st, StateLayout lay
 }
 
 template <int R>
-__global__ __launch_bounds__(256) void eig_kernel(double* __restrict__ st, StateLayout lay, int H, int spectral,
+__global__ __launch_bounds__(R == 4 ? 512 : 256) void eig_kernel(double* __restrict__ st, StateLayout lay, int H, int spectral,
                                                   int do_d, int do_b, const int* __restrict__ ints) {
     extern __shared__ __attribute__((aligned(16))) float lds_eig[];
     const int which = blockIdx.x;           // 0: GD, 1: GB
     if ((which == 0 && !do_d) || (which == 1 && !do_b)) return;
-    eig_dev<R>(st, lay, H, spectral, which, ints, lds_eig, which == 0 ? S_LAMD : S_LAMB_NEW);
+    eig_dev<R, true>(st, lay, H, spectral, which, ints, lds_eig, which == 0 ? S_LAMD : S_LAMB_NEW);
 }
 
 // H > 128: the same iteration on 1024 threads (NP = 256)
@@ -943,7 +1045,8 @@ __global__ __launch_bounds__(1024) void ctrl_end_kernel(double* __restrict__ st,
 // never committed.
 // VBMF_SEAM_STAMPS (diagnostic builds only, off by default: the shipped kernels execute no extra stamp): durations of the segments
 // of the two fused steps in 10 ns ticks, in the chain stamps' slots 4-7 (the streaming epilogue's, idle in a Gram-form sweep):
-// [4] SigmaA diagonal add, [5] SigmaA sweep, [6] SigmaA write-back + log-determinant, [7] SigmaB: assembly << 40 | sweep << 20 | write-back
+// [4] part 2 of the first chain launch (lambda_max(B_old'B_old), stamped in ctrl_chain; the other two parts are slots 0-2),
+// [5] SigmaA diagonal add + sweep, [6] SigmaA write-back + log-determinant, [7] SigmaB: assembly << 40 | sweep << 20 | write-back
 #ifndef VBMF_SEAM_STAMPS
 #define VBMF_SEAM_STAMPS 0
 #endif
@@ -956,10 +1059,6 @@ __device__ __forceinline__ void cov_a_after_end_dev(double* __restrict__ st, Sta
 #endif
     if ((int)threadIdx.x < H) ho.img[threadIdx.x * LD + threadIdx.x] += ho.sigma2 / ho.ca_h;   // (ctrl_end_dev ended on a barrier)
     double ldK; int badK;
-#if VBMF_SEAM_STAMPS
-    __syncthreads();
-    const unsigned long long s1 = wall_clock64();
-#endif
     spd_sweep_lds4<R>(ho.img, H, &ldK, &badK);
 #if VBMF_SEAM_STAMPS
     __syncthreads();
@@ -970,7 +1069,7 @@ __device__ __forceinline__ void cov_a_after_end_dev(double* __restrict__ st, Sta
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long* stamp = reinterpret_cast<unsigned long long*>(ints + 8);
-        stamp[4] = s1 - s0; stamp[5] = s2 - s1; stamp[6] = wall_clock64() - s2;
+        stamp[5] = s2 - s0; stamp[6] = wall_clock64() - s2;
     }
 #endif
 }
@@ -1118,10 +1217,15 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
         __syncthreads();
         if (stop2_s) return;
         if (a.mode & CTRL_EIG_AHEAD)
-            eig_dev<R>(a.st, a.lay, a.H, a.spectral, 1, a.ints, reinterpret_cast<float*>(lds), S_LAMB_SHADOW, false);
+            eig_dev<R, SEAMS>(a.st, a.lay, a.H, a.spectral, 1, a.ints, reinterpret_cast<float*>(lds), S_LAMB_SHADOW, false);
+#if VBMF_SEAM_STAMPS
+        if (threadIdx.x == 0) stamp[4] = wall_clock64() - t0;
+#endif
         return;
     }
     if (part == 0) {
+        if (SEAMS && threadIdx.x >= 256) return;            // a launch at the wide lambda_max's 512 threads: part 0 keeps its 256, the
+                                                            // other waves leave the kernel at once (a barrier counts live waves only)
         // CTRL_COMMIT_A comes only from gram_sweep, with CTRL_COV_B, in a SEAMS launch: commit_cov_b_dev is the one commit
         EndHandOff ho{reinterpret_cast<double*>(lds), 16 * R, 0.0, 1.0, false};
         const bool end_to_a = SEAMS && (a.mode & CTRL_PREV_END) && (a.mode & CTRL_COV_A);
@@ -1149,19 +1253,19 @@ __device__ __forceinline__ void ctrl_chain(const CtrlArgs& a, void* lds, int par
         }
     } else {
         if (a.mode & CTRL_PREV_END) {
-            eig_dev<R>(a.st, a.lay, a.H, a.spectral, 0, a.ints, reinterpret_cast<float*>(lds), S_LAMD);
+            eig_dev<R, SEAMS>(a.st, a.lay, a.H, a.spectral, 0, a.ints, reinterpret_cast<float*>(lds), S_LAMD);
             ctrl_loop_dev(a.st, a.lay, a.eps, a.trace, a.ints, a.it_row, a.loopw);
             if (threadIdx.x == 0) stamp[2] = wall_clock64() - t0;
         }
         if (a.mode & CTRL_EIG_BOLD)
-            eig_dev<R>(a.st, a.lay, a.H, a.spectral, 1, a.ints, reinterpret_cast<float*>(lds), S_LAMB_PREV);
+            eig_dev<R, SEAMS>(a.st, a.lay, a.H, a.spectral, 1, a.ints, reinterpret_cast<float*>(lds), S_LAMB_PREV);
     }
 }
 
-// the chain as a launch of its own: workgroups of 256 threads (three in the sweep's first launch, one in its second), dynamic LDS
-// as for the pass launches' control workgroups
+// the chain as a launch of its own: workgroups of 256 threads -- 512 where a part runs the wide squaring (eig_dev, WIDE_OK) -- three
+// in the sweep's first launch, one in its second; dynamic LDS as for the pass launches' control workgroups
 template <int R>
-__global__ __launch_bounds__(256) void ctrl_chain_kernel(CtrlArgs a) {
+__global__ __launch_bounds__(R == 4 ? 512 : 256) void ctrl_chain_kernel(CtrlArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_chain[];
     ctrl_chain<R, true>(a, lds_chain, blockIdx.x);
 }

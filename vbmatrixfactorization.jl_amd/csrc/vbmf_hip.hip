@@ -416,6 +416,9 @@ static void prof_harvest(vbmf_ctx* c) {
 static int spectral_arg(const vbmf_ctx* c) {
     return ((c->o.reference_compat & VBMF_COMPAT_SPECTRAL_DELTA) ? 1 : 0) | (c->exact_lambda ? 2 : 0);
 }
+// threads per workgroup of the lambda_max kernels of the chain's own (eig_kernel, ctrl_chain_kernel): 512 where the squaring runs in
+// its wide form (eig_squaring_dev: R = 4, 32 < H <= 64), else 256 -- R = 1 and 2, the Lanczos tiers and the Lanczos switch
+static int eig_wide_launch(int R, int spectral) { return (R == 4 && !(spectral & 2)) ? 512 : 256; }
 static bool use_lds8(const vbmf_ctx* c) { return c->lds8 && c->NH >= 4 && c->mode == MODE_BF16X2; }
 
 // dynamic LDS of the control chain's workgroups at R = NP / 16 (pass launches: R = 2 NH; ctrl_chain_kernel: R of the stand-alone kernels)
@@ -496,7 +499,11 @@ static int launch_stream(vbmf_ctx* c, int pass, int ctrl_mode = 0, bool epi = fa
         ea.spin_limit = c->epi_spin_limit;
         ea.store_fac = c->in_run ? 0 : 1;
         ea.trpart = c->trpart;
+#if VBMF_SEAM_STAMPS
+        ea.stamp = nullptr;                                        // slots 4-7 carry the seams' stamps past a run's closing pass
+#else
         ea.stamp = reinterpret_cast<unsigned long long*>(c->ints + 16);
+#endif
         c->ntr = 4 * bps;
         if (c->in_run) c->cache.B32_store_skipped();
         if (ctrl_mode) { ca.sready = c->ints + I_SREADY; ca.sready_val = c->sready_seq; }
@@ -849,7 +856,8 @@ static int launch_eig(vbmf_ctx* c, int do_d, int do_b) {
             hipLaunchKernelGGL(eig_lanczos_kernel, dim3(2), dim3(1024), 0, s, c->st, c->lay, H, spectral, do_d, do_b, c->ints);
         } else {
             const size_t lds = std::max(R <= 4 ? (size_t)2 * NP * (NP + 4) * sizeof(float) : (size_t)0, (size_t)EIG_LDS_BYTES);     // squaring | Lanczos
-            hipLaunchKernelGGL((eig_kernel<R>), dim3(2), dim3(256), lds, s, c->st, c->lay, H, spectral, do_d, do_b, c->ints);
+            hipLaunchKernelGGL((eig_kernel<R>), dim3(2), dim3(eig_wide_launch(R, spectral)), lds, s, c->st, c->lay, H, spectral, do_d, do_b,
+                               c->ints);
         }
     });
     HIPCHK(c, hipGetLastError());
@@ -1183,8 +1191,10 @@ static int launch_chain(vbmf_ctx* c, int mode, float* S32) {
     const int parts = (mode & CTRL_EIG_AHEAD) ? 3 : ((mode & (CTRL_PREV_END | CTRL_EIG_BOLD)) ? 2 : 1);
     ctrl_tier(c->H, [&](auto r, auto t) {
         constexpr int R = decltype(r)::value;
+        // part 0 runs on the first 256 threads whatever the width; a launch without a lambda_max part (the sweep's second) stays at 256
+        const int nthr = (mode & (CTRL_PREV_END | CTRL_EIG_AHEAD | CTRL_EIG_BOLD)) ? eig_wide_launch(R, ca.spectral) : 256;
         if constexpr (decltype(t)::value == 16)
-            hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(parts), dim3(256), ctrl_lds_bytes_r(R), c->stream, ca);
+            hipLaunchKernelGGL((ctrl_chain_kernel<R>), dim3(parts), dim3(nthr), ctrl_lds_bytes_r(R), c->stream, ca);
     });
     HIPCHK(c, hipGetLastError());
     return VBMF_OK;
