@@ -615,6 +615,49 @@ int vbmf_sparse_scored_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off
 /* test hook: the widest bag whose job keeps its state in LDS in vbmf_sparse_fixed_basis_jobs at this H and form (wider ones work in the
  * call's scratch buffer); 0 for an H outside 1..32 */
 int vbmf_debug_vbls_jobs_lds_cols(int64_t H, int full_cov);
+/* vbmf_fixed_basis_jobs: vbls! of the basic model (examples/mil_util.jl:182-185: niter x (updateA!, updateCA!, updateSigma2!) with B, SigmaB
+ * frozen) for a list of (bag, model) jobs and each job's norm(Y - BHat*AHat')^2 -- the "vbls" classifier of examples/mil_util.jl:469-479
+ * (150 vbls! iterations against each of a fold's two models) for every fold of validate_with_cvs in one call, on the one context that
+ * holds every bag of the data set (col_off as in vbmf_bag_least_squares).  Any context variant serves, with one rank and no label mask:
+ * only its Y is read, and the models' ranks have nothing to do with the context's own.
+ *   niter               >= 1 iterations
+ *   per model k < nmodels, packed in model order (model k's blocks behind those of the models before it):
+ *   model_H             the model's own rank, 1 <= H_k <= 32 (vbmf_fit_batched's cap, which produces these models)
+ *   BHat, SigmaB        L x H_k fp64 column-major with ld = L, used in fp64 as given; H_k x H_k.  CB is not an argument: updateA!
+ *                       (src/vbmf.jl:95-98) never reads it
+ *   sigma2_0, ca0       every job of the model starts from sigma2 = sigma2_0[k] and CA = ca0[k] I (copy_vbmf_params: the trained
+ *                       sigma2 and 1.0)
+ *   job_bag, job_model  job j runs bag job_bag[j] against model job_model[j].  Jobs may come in any order, a bag may appear in many
+ *                       jobs, a model in many or none, and a job may repeat
+ *   r2                  (njobs, may be NULL) ||Y_b - BHat_k AHat_j'||_F^2, formed entry by entry in fp64, never by the trace form
+ *   AHat                (may be NULL; r2 and AHat not both) per-job M_b x H_k blocks, column-major, one after the other in job order, as
+ *                       vbmf_fit_batched lays them out
+ *   SigmaA, CA_diag, sigma2   (each may be NULL) the jobs' H_k x H_k blocks, H_k-long blocks, one value per job
+ *   status              (njobs, required) 1 for a job that met a pivot that is not positive and finite (or ended with a non-finite
+ *                       sigma2, CA or r2), else 0
+ * Per job, with S = P'P, P = Y_b'BHat_k and G_k = BHat_k'BHat_k + L SigmaB_k (vbmf_run_fixed_basis' H x H form of the loop):
+ *   K = G_k + sigma2 inv(CA);  SigmaA = sigma2 inv(K);  A'A = SigmaA S SigmaA / sigma2^2;  CA_hh = (A'A)_hh / M_b + SigmaA_hh;
+ *   sigma2 = (||Y_b||^2 - 2 tr(S SigmaA) / sigma2 + tr((A'A + M_b SigmaA) G_k)) / (L M_b);  AHat = P SigmaA / sigma2 once, from the last
+ *   updateA!.
+ * Everything is fp64, Y widened on load from Y as stored.  Every sum has an order fixed by (L, M_b, H_k) alone, so a job's numbers do
+ * not depend on the other jobs, on their order or tier, or on where the bag sits in Y.  One launch of the model kernel (one workgroup
+ * per model: G_k), one launch of the job kernel per non-empty 16-block tier of H_k -- at most two; the host sorts the jobs into them
+ * through an index table -- and one synchronising read-back, whatever nmodels and njobs are.
+ * A failed job (status 1) does not fail the call, as in the *_fit_batched entries: it gets NaN in r2, sigma2 and every entry of its
+ * blocks (written on the device), the other jobs are computed as if it were not in the call.  The context's state, caches and Y are
+ * not changed.
+ * Refused before any launch, copy or change, every output left untouched: VBMF_ERR_UNSUPPORTED for a model_H[k] outside 1..32, more
+ * jobs or models than the 16 777 215 workgroups one grid holds, or a call whose models and results the host cannot stage in memory;
+ * VBMF_ERR_INVALID for everything bags_check refuses (a sharded context, nbags < 1, a col_off that does not run from 0 to M or that
+ * decreases), nmodels < 1, njobs < 1, niter < 1, a NULL input or status, r2 and AHat both NULL, a non-finite entry of any BHat, SigmaB,
+ * sigma2_0 or ca0, a job_bag[j] outside 0..nbags-1, a job_model[j] outside 0..nmodels-1, a label mask, no Y. */
+int vbmf_fixed_basis_jobs(vbmf_ctx* ctx, int64_t nbags, const int64_t* col_off, int64_t niter, int64_t nmodels, const int64_t* model_H,
+                          const double* BHat, const double* SigmaB, const double* sigma2_0, const double* ca0, int64_t njobs,
+                          const int64_t* job_bag, const int64_t* job_model, double* r2, double* AHat, double* SigmaA, double* CA_diag,
+                          double* sigma2, int64_t* status);
+/* test hook: the widest bag whose job keeps its P in LDS in vbmf_fixed_basis_jobs at this H (wider ones work in the call's scratch
+ * buffer); 0 for an H outside 1..32 */
+int vbmf_debug_fixed_basis_jobs_lds_cols(int64_t H);
 /* lowerBound (src/vbmf_sparse.jl:435-471; dual src/vbmf_dual.jl:556-599; trial src/vbmf_trial.jl:630-680) for trim < 0 and
  * lowerBoundTrimmed (src/vbmf_sparse.jl:478-489; dual :606-617; trial :687-698) for trim >= 0 of every bag, as called per bag by
  * examples/mil_util.jl:502-514.  Sparse-family context, homoscedastic, one fixed basis: BHat, SigmaB, CB, delta and the hyper-priors

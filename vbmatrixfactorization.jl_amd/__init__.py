@@ -51,7 +51,7 @@ __all__ = ["vbmf_parameters", "vbmf_init", "vbmf", "vbmf_", "copy", "updateA_", 
            "vbmf_batch_", "train_folds", "row_gram_batch", "vbmf_trial_batch_", "vbmf_sparse_masked_batch_", "train_local_folds",
            "train_dual_folds", "BagPool",
            "residual_batch", "lowerBound_batch", "lowerBoundTrimmed_batch", "classify_batch",
-           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch", "vbls_sparse_jobs_",
+           "ols_batch", "rls_batch", "ls_residual_batch", "classify_bags", "test_classification_batch", "vbls_sparse_jobs_", "vbls_jobs_",
            "classify_folds", "test_classification_folds", "validate_folds", "factorize_folds", "validate_local_folds"]
 
 # YHat (L x M float64) is materialised eagerly by the reference (src/vbmf.jl:70,217); above this many
@@ -2571,13 +2571,71 @@ def vbls_sparse_jobs_(Ys, models, job_bag, job_model, niter, full_cov=False):
     return sets, r["r2"], r["status"]
 
 
+def _basic_jobs_model(res, L, name, refuse, what="vbmf_parameters only"):
+    """One trained basic-model set as the arrays of one model of Context.fixed_basis_jobs, checked on the host.  The start values are
+    copy_vbmf_params': sigma2 = the trained sigma2, CA = I (vbmf_init's default ca = 1).  CB is not read (src/vbmf.jl:95-98)."""
+    if type(res) is not vbmf_parameters:
+        refuse(f"{name} is a {type(res).__name__} ({what})")
+    H = int(res.H)
+    if not 1 <= H <= _JOBS_MAX_H:
+        refuse(f"{name}: H = {H} > {_JOBS_MAX_H}" if H > _JOBS_MAX_H else f"{name}: H = {H} < 1")
+    B, SB = np.asarray(res.BHat, dtype=np.float64), np.asarray(res.SigmaB, dtype=np.float64)
+    if B.shape != (L, H) or SB.shape != (H, H):
+        refuse(f"{name}: BHat is {B.shape} and SigmaB {SB.shape}, the bags have L = {L} rows and H = {H}")
+    if not (np.all(np.isfinite(B)) and np.all(np.isfinite(SB)) and np.isfinite(float(res.sigma2))):
+        refuse(f"{name} has a BHat, SigmaB or sigma2 that is not finite")
+    return dict(BHat=B, SigmaB=SB, sigma2_0=float(res.sigma2), ca0=1.0)
+
+
+def vbls_jobs_(Ys, models, job_bag, job_model, niter):
+    """vbls! of the basic model for a list of (bag, model) jobs in ONE device call: job j does what
+    vbls_(Ys[job_bag[j]], copy_vbmf_params(Ys[job_bag[j]], models[job_model[j]]), niter) does (examples/mil_util.jl:182-185), every
+    model with its own fp64 basis and its own H <= 32.
+    Ys: a BagPool (the call runs on the pool's own context: no select, no gather, no new context), an uploaded Bags / SparseBags of
+    any rank, or a list of L x M_b matrices.  models: trained vbmf_parameters.  Jobs may come in any order and repeat.  Returns
+    (sets, r2, status): per job a parameter set for that bag with AHat, SigmaA, CA, invCA, sigma2 as the iterations leave them and the
+    model's BHat, SigmaB, CB, invCB (YHat is not formed); r2[j] = norm(Y_b - BHat*AHat')^2 formed entry by entry on the device;
+    status[j] = 1 for a job that met a bad pivot or ended non-finite (NaN in its fields and r2; the other jobs are computed)."""
+    fn = "vbls_jobs_"
+    refuse = _jobs_refuser(fn)
+    models = list(models)
+    if not models:
+        refuse("no models")
+    if int(niter) < 1:
+        refuse(f"niter = {niter} < 1")
+    L, Ms = _jobs_bags(fn, Ys, refuse)
+    mods = [_basic_jobs_model(res, L, f"model {k}", refuse) for k, res in enumerate(models)]
+    job_bag, job_model = [int(b) for b in job_bag], [int(k) for k in job_model]
+    if len(job_bag) != len(job_model) or not job_bag:
+        refuse(f"{len(job_bag)} job bags and {len(job_model)} job models (as many of each, at least one)")
+    for j, (b, k) in enumerate(zip(job_bag, job_model)):
+        if not 0 <= b < len(Ms):
+            refuse(f"job {j}: bag {b} outside 0..{len(Ms) - 1}")
+        if not 0 <= k < len(models):
+            refuse(f"job {j}: model {k} outside 0..{len(models) - 1}")
+    r = _jobs_run(Ys, lambda ctx, off: ctx.fixed_basis_jobs(off, mods, job_bag, job_model, int(niter)))
+    sets = []
+    for j, (b, k) in enumerate(zip(job_bag, job_model)):
+        old, p = models[k], vbmf_parameters()
+        p.L, p.M, p.H = L, int(Ms[b]), int(old.H)
+        p.BHat, p.SigmaB = mods[k]["BHat"].copy(), mods[k]["SigmaB"].copy()
+        p.CB, p.invCB = np.array(old.CB, dtype=np.float64), np.array(old.invCB, dtype=np.float64)
+        ca = np.asarray(r["CA"][j])
+        p.AHat, p.SigmaA = np.array(r["AHat"][j], order="F"), np.array(r["SigmaA"][j])
+        with np.errstate(divide="ignore"):
+            p.CA, p.invCA = np.diag(ca), np.diag(1.0 / ca)
+        p.sigma2 = float(r["sigma2"][j])
+        sets.append(p)
+    return sets, r["r2"], r["status"]
+
+
 # =================================================================================================
 # Every fold's test bags against its own models in one device call -- test_classification (examples/mil_util.jl:558-587) as
 # validate_with_cvs (:627-648), validate (:594-620) and validate_dataset (:670-788) run it per fold, p_known and repetition;
-# include/vbmf_hip.h: vbmf_bag_least_squares_jobs ("ols", "rls"), vbmf_sparse_fixed_basis_jobs ("dual")
+# include/vbmf_hip.h: vbmf_bag_least_squares_jobs ("ols", "rls"), vbmf_sparse_fixed_basis_jobs ("dual"), vbmf_fixed_basis_jobs ("vbls")
 # =================================================================================================
 _FOLD_LAMS = {"ols": 0.0, "rls": 1e-2}                                   # :459, :466
-_FOLD_ALGS = tuple(_FOLD_LAMS) + ("dual",)
+_FOLD_ALGS = tuple(_FOLD_LAMS) + ("dual", "vbls")
 
 
 def _untrained(pair):
@@ -2614,10 +2672,10 @@ def _fold_ids(fn, tests, nb):
 
 
 def _fold_alg(fn, class_alg):
-    """lambda of the least-squares classifiers, None for 'dual'"""
+    """lambda of the least-squares classifiers, None for 'dual' and 'vbls'"""
     if class_alg not in _FOLD_ALGS:
-        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols', 'rls' or 'dual'; 'vbls' runs the basic model on one basis per context, "
-                        f"'lower_bound' and 'min_err' two bases of different H per bag: run them per fold with classify_bags)")
+        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols', 'rls' or 'dual', or 'vbls' with solver = 'basic'; 'lower_bound' and 'min_err' "
+                        f"take a train_local model: validate_local_folds, or run them per fold with classify_bags)")
     return _FOLD_LAMS.get(class_alg)
 
 
@@ -2629,8 +2687,8 @@ def _fold_alg_scored(fn, class_alg):
     if class_alg in _FOLD_SCORED_ALGS:
         return None
     if class_alg not in _FOLD_ALGS:
-        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols', 'rls' or 'dual', 'lower_bound' or 'min_err'; 'vbls' runs the basic model on "
-                        f"one basis per context: run it per fold with classify_bags)")
+        _ls_refuser(fn)(f"class_alg = {class_alg!r} ('ols', 'rls' or 'dual', 'vbls', 'lower_bound' or 'min_err'; any other classifier "
+                        f"runs per fold with classify_bags)")
     return _FOLD_LAMS.get(class_alg)
 
 
@@ -2644,7 +2702,7 @@ def _fold_labels(fn, labels, nb):
 
 
 def classify_folds(models, tests, Ys, class_alg="ols", niter=None, threshold=1e-1):
-    """classify (examples/mil_util.jl:453-535) with class_alg "ols", "rls", "dual", "lower_bound" or "min_err" for every fold of a
+    """classify (examples/mil_util.jl:453-535) with class_alg "ols", "rls", "dual", "vbls", "lower_bound" or "min_err" for every fold of a
     validation run in ONE device call: fold f's test bags tests[f] (bag indices into Ys) against its own pair models[f] = (res0, res1).  Any objects with a BHat serve as
     models, of the same or different H <= 64; (0, 0) -- what train_folds returns for a fold it could not train -- is accepted.
     Ys: a BagPool (the indices are pool bag ids and the call runs on the pool's own context: no select, no gather, no new context), an
@@ -2667,7 +2725,11 @@ def classify_folds(models, tests, Ys, class_alg="ols", niter=None, threshold=1e-
     vbmf_sparse_parameters with 0 < H1 < H that train_local_folds returns, bare or as the first of a pair -- and from its scores
     (labels = L1 > L0, L0, L1) for "lower_bound", (label 0 where |(err0 - err1) / err0| < threshold (:497), err0, err1) for "min_err".
     The folds may differ in H and H1.  A fold with a failed job raises VbmfError as "dual" does.  threshold is read by these two only.
-    "vbls" stays per fold: classify_bags."""
+    "vbls" (:469-479): the pairs are the basic model's vbmf_parameters, as train_folds(..., "basic") returns them, each of its own
+    H <= 32 (a fold's two may differ); the call's models are the trained folds' res0, res1 in fold order as above, its jobs (bag, 2 t)
+    and (bag, 2 t + 1) run niter = 150 iterations of vbls! (niter overrides) from what copy_vbmf_params gives -- sigma2 = the trained
+    sigma2, CA = I -- (Context.fixed_basis_jobs); err = sqrt(r2), label 1 where err0 > err1 (:483-491).  A fold with a job that met
+    a bad pivot or ended non-finite raises VbmfError naming the fold after the others have been computed, with .results as above."""
     fn = "classify_folds"
     refuse = _ls_refuser(fn)
     lam = _fold_alg_scored(fn, class_alg)
@@ -2689,6 +2751,8 @@ def classify_folds(models, tests, Ys, class_alg="ols", niter=None, threshold=1e-
     ids = _fold_ids(fn, tests, nb)
     if class_alg == "dual":
         return _classify_folds_dual(fn, models, ids, Ys, L, 20 if niter is None else int(niter))
+    if class_alg == "vbls":
+        return _classify_folds_vbls(fn, models, ids, Ys, L, 150 if niter is None else int(niter))
     bases, trained = [], []
     for f, pair in enumerate(models):
         if _untrained(pair):
@@ -2794,6 +2858,64 @@ def _classify_folds_dual(fn, models, ids, Ys, L, niter):
         f, k, b = bad[0]
         e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against res{k} met a precision that is not finite or a "
                                              f"pivot that is not positive and finite")
+        e.results = out
+        raise e
+    return out
+
+
+def _fold_models_vbls(fn, models, L):
+    """(the call's models, the trained folds) of the "vbls" classifier, checked on the host: models 2 t and 2 t + 1 are the t-th trained
+    fold's res0 and res1"""
+    refuse = _ls_refuser(fn)
+    mods, trained = [], []
+    for f, pair in enumerate(models):
+        if _untrained(pair):
+            continue
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            refuse(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
+        mods += [_basic_jobs_model(r, L, f"fold {f}: res{k}", refuse,
+                                   "class_alg = 'vbls' takes the basic model's vbmf_parameters, as train_folds(..., 'basic') returns them; "
+                                   "'ols', 'rls' or 'dual' take other models, and any pair of models runs per fold with classify_bags")
+                 for k, r in enumerate(pair)]
+        trained.append(f)
+    return mods, trained
+
+
+def _classify_folds_vbls(fn, models, ids, Ys, L, niter):
+    """classify_folds' "vbls" branch: the folds' basic-model sets as one call's models, two jobs per tested bag"""
+    refuse = _ls_refuser(fn)
+    if niter < 1:
+        refuse(f"niter = {niter} < 1")
+    mods, trained = _fold_models_vbls(fn, models, L)
+    job_bag, job_model, where = [], [], {}
+    for t, f in enumerate(trained):
+        n = len(ids[f])
+        if n:
+            where[f] = len(job_bag)
+            job_bag += ids[f] + ids[f]
+            job_model += [2 * t] * n + [2 * t + 1] * n
+    out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
+    if not job_bag:
+        return out
+    r = _jobs_run(Ys, lambda ctx, off: ctx.fixed_basis_jobs(off, mods, job_bag, job_model, int(niter)))
+    r2, status = r["r2"], r["status"]
+    bad = []
+    for f in trained:
+        if f not in where:
+            continue
+        n, j0 = len(ids[f]), where[f]
+        st = np.asarray(status[j0:j0 + 2 * n])
+        if st.any():
+            j = int(np.flatnonzero(st)[0])
+            bad.append((f, j // n, ids[f][j % n]))
+            out[f] = None
+            continue
+        err0, err1 = np.sqrt(r2[j0:j0 + n]), np.sqrt(r2[j0 + n:j0 + 2 * n])                     # :483-484
+        out[f] = ((err0 > err1).astype(np.int64), err0, err1)                                   # :487-491
+    if bad:
+        f, k, b = bad[0]
+        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against res{k} met a pivot that is not positive and finite "
+                                             f"or ended with a sigma2, CA or residual that is not finite")
         e.results = out
         raise e
     return out
@@ -2927,9 +3049,11 @@ def test_classification_folds(models, tests, Ys, labels, class_alg="ols", niter=
     models, tests = list(models), list(tests)
     if len(models) != len(tests):
         _ls_refuser(fn)(f"{len(models)} models but {len(tests)} test lists")
-    _, nb = _folds_bags(fn, Ys)
+    L, nb = _folds_bags(fn, Ys)
     labels = _fold_labels(fn, labels, nb)
     ids = _fold_ids(fn, tests, nb)
+    if class_alg == "vbls":
+        _fold_models_vbls(fn, models, L)                                 # (its refusals under this function's name)
     out = []
     kw = {k: v for k, v in (("niter", niter), ("threshold", threshold)) if v is not None}
     for t, r in zip(ids, classify_folds(models, ids, Ys, class_alg, **kw)):
@@ -2948,18 +3072,22 @@ def validate_folds(pool, labels, splits, solver, H, niter, eps=1e-6, class_alg="
     """validate_with_cvs (examples/mil_util.jl:627-648) over all splits = [(train_ids, test_ids), ...] of a BagPool in two device
     calls: one train_folds(..., pool=pool) on the folds' training groups -- the train_ids with label 0 and those with label 1, in the
     order given (get_matrices, :46) -- and one test_classification_folds on the test_ids.  labels: 0 / 1, one per bag of the pool;
-    solver, H, niter, eps, rng, form, slice_cols: train_folds'; class_alg: "ols", "rls" or "dual".  With "dual" the third branch of
+    solver, H, niter, eps, rng, form, slice_cols: train_folds'; class_alg: "ols", "rls", "dual", or "vbls" with solver = "basic" (the
+    basic model's classifier, :469-479: H <= 32).  With "dual" the third branch of
     validate_with_cvs (:633-634) runs instead: train_dual_folds(folds, H, H - H1, niter, eps, diag_var=diag_var, nstarts=nstarts,
     pool=pool) trains and solver is not read; H1, diag_var and nstarts are read by that branch only.  Returns the list of
     (mer, eer, fp, fn, n0, n1) per split, (-1.0,) * 6 for a split with an empty class."""
     fn = "validate_folds"
     refuse = _ls_refuser(fn)
     _fold_alg(fn, class_alg)
+    if class_alg == "vbls" and solver != "basic":
+        refuse(f"class_alg = 'vbls' with solver = {solver!r} (it takes the basic model's vbmf_parameters: solver = 'basic'; 'ols', 'rls' or "
+               f"'dual' take the other solvers' models, and any pair of models runs per fold with classify_bags)")
     if not isinstance(pool, BagPool):
         refuse(f"pool is a {type(pool).__name__}, not a BagPool")
     _, nb = _folds_bags(fn, pool)
-    if int(H) > _LS_MAX_H:
-        refuse(f"H = {int(H)} > {_LS_MAX_H}")
+    if int(H) > (_JOBS_MAX_H if class_alg == "vbls" else _LS_MAX_H):
+        refuse(f"H = {int(H)} > {_JOBS_MAX_H if class_alg == 'vbls' else _LS_MAX_H}")
     labels = _fold_labels(fn, labels, nb)
     splits = [tuple(s) for s in splits]
     if any(len(s) != 2 for s in splits):

@@ -105,6 +105,7 @@ SYMBOLS = [
     "vbmf_sparse_lower_bound_trimmed", "vbmf_debug_set",
     "vbmf_bag_residuals", "vbmf_sparse_lower_bound_batched", "vbmf_bag_least_squares", "vbmf_bag_least_squares_jobs", "vbmf_set_gram_form",
     "vbmf_sparse_fixed_basis_jobs", "vbmf_sparse_scored_jobs", "vbmf_debug_vbls_jobs_lds_cols",
+    "vbmf_fixed_basis_jobs", "vbmf_debug_fixed_basis_jobs_lds_cols",
     "vbmf_get_YHat_rows", "vbmf_get_factor_rows", "vbmf_set_Y_gather", "vbmf_debug_blk_sweep",
 ]
 VBMF_OK, VBMF_ERR_INVALID, VBMF_ERR_NO_DEVICE, VBMF_ERR_HIP, VBMF_ERR_NUMERIC, VBMF_ERR_COMM, VBMF_ERR_UNSUPPORTED, VBMF_ERR_SYNC = 0, -1, -2, -3, -4, -5, -6, -7
@@ -222,6 +223,9 @@ def lib():
     L.vbmf_sparse_scored_jobs.argtypes = ([vp, i64, C.POINTER(i64), i64, i32, i32, i64, C.POINTER(i64)] + [dp] * 14
                                           + [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)] + [dp] * 10 + [C.POINTER(i64)])
     L.vbmf_debug_vbls_jobs_lds_cols.argtypes = [i64, i32]
+    L.vbmf_fixed_basis_jobs.argtypes = [vp, i64, C.POINTER(i64), i64, i64, C.POINTER(i64), dp, dp, dp, dp, i64, C.POINTER(i64),
+                                        C.POINTER(i64), dp, dp, dp, dp, dp, C.POINTER(i64)]
+    L.vbmf_debug_fixed_basis_jobs_lds_cols.argtypes = [i64]
     L.vbmf_debug_blk_sweep.argtypes = [dp, i64, i32, dp, dp, C.POINTER(i32)]
     L.vbmf_sparse_set_full_cov.argtypes = [vp, i32]
     L.vbmf_set_gram_form.argtypes = [vp, i32]
@@ -953,6 +957,48 @@ class Context:
                                                          _dptr(sg), _dptr(zeta), _i64ptr(status)))
         return dict(r2=r2, sigmaHat=sg, zeta=zeta, status=status, SigmaA=SA, CA=CA, beta=beta, diagSigmaATVec=dS, ATVecHat=A, off=boff)
 
+    def fixed_basis_jobs(self, col_off, models, job_bag, job_model, niter):
+        """vbls! of the basic model for a list of (bag, model) jobs in one device call (vbmf_fixed_basis_jobs): models[k] is a dict of
+        BHat (L, H_k) and SigmaB (H_k, H_k) fp64, sigma2_0 and ca0 (scalars), each model of its own H_k <= 32; job j runs bag job_bag[j]
+        of col_off against model job_model[j] for niter iterations from sigma2 = sigma2_0, CA = ca0 I.  Only this context's Y is read.
+        Returns dict(r2, sigma2 (njobs,), status (njobs,) with 1 for a failed job (NaN in its outputs, the others are computed), and
+        the lists AHat (M_b, H_k), SigmaA (H_k, H_k), CA (H_k,) per job)."""
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        nb = off.size - 1
+        nk = len(models)
+        Hs = np.array([np.shape(m["BHat"])[1] if np.ndim(m["BHat"]) == 2 else -1 for m in models], dtype=np.int64)
+        for m, H in zip(models, Hs):
+            H = int(H)
+            if np.shape(m["BHat"]) != (self.L, H) or np.shape(m["SigmaB"]) != (H, H):
+                raise ValueError(f"every model needs BHat ({self.L}, H) and SigmaB (H, H)")
+
+        def pack(key, order="C"):
+            if not nk:
+                return np.empty(0)
+            return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
+        B, SB, s0, c0 = pack("BHat", "F"), pack("SigmaB", "F"), pack("sigma2_0"), pack("ca0")
+        jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
+        jk = np.ascontiguousarray(job_model, dtype=np.int64).reshape(-1)
+        nj = jb.size
+        if jk.size != nj:
+            raise ValueError(f"{nj} job bags but {jk.size} job models")
+        ok = (jb >= 0) & (jb < nb) & (jk >= 0) & (jk < nk)           # (a job out of range is the library's to refuse: no block for it)
+        Hj = np.where(ok, Hs[np.clip(jk, 0, max(nk - 1, 0))], 0) if nk >= 1 else np.zeros(nj, np.int64)
+        widths = np.where(ok, off[np.clip(jb, 0, max(nb - 1, 0)) + 1] - off[np.clip(jb, 0, max(nb - 1, 0))], 0) if nb >= 1 else np.zeros(nj, np.int64)
+        boff = np.concatenate([[0], np.cumsum(widths * Hj)]).astype(np.int64)
+        soff = np.concatenate([[0], np.cumsum(Hj * Hj)]).astype(np.int64)
+        hoff = np.concatenate([[0], np.cumsum(Hj)]).astype(np.int64)
+        r2, sg = np.empty(nj), np.empty(nj)
+        A, SA, CA = np.empty(max(int(boff[-1]), 1)), np.empty(max(int(soff[-1]), 1)), np.empty(max(int(hoff[-1]), 1))
+        status = np.zeros(nj, dtype=np.int64)
+        self._chk(self._lib.vbmf_fixed_basis_jobs(self._h, nb, _i64ptr(off), int(niter), nk, _i64ptr(Hs), _dptr(B), _dptr(SB), _dptr(s0),
+                                                  _dptr(c0), nj, _i64ptr(jb), _i64ptr(jk), _dptr(r2), _dptr(A), _dptr(SA), _dptr(CA),
+                                                  _dptr(sg), _i64ptr(status)))
+        As = [A[boff[j]:boff[j + 1]].reshape((int(widths[j]), int(Hj[j])), order="F") for j in range(nj)]
+        SAs = [SA[soff[j]:soff[j + 1]].reshape(int(Hj[j]), int(Hj[j])) for j in range(nj)]
+        CAs = [CA[hoff[j]:hoff[j + 1]] for j in range(nj)]
+        return dict(r2=r2, sigma2=sg, status=status, AHat=As, SigmaA=SAs, CA=CAs)
+
     def sparse_scored_jobs(self, col_off, models, job_bag, job_model, job_full_cov, job_trim, niter, clamp=True, grouped=False):
         """factorize_bag and its scores for a list of (bag, model) jobs in one device call (vbmf_sparse_scored_jobs): models[k] is a dict
         of BHat (L, H_k) and SigmaB (H_k, H_k) fp64, CB, delta, a_pri, b_pri, a_post (H_k,), gamma, gamma0, delta0, eta0, zeta0, sigma0,
@@ -1167,3 +1213,8 @@ def blk_sweep(K, waves=4):
 def vbls_jobs_lds_cols(H, full_cov=False):
     """The widest bag whose job keeps its state in LDS in Context.sparse_fixed_basis_jobs (vbmf_debug_vbls_jobs_lds_cols)."""
     return int(lib().vbmf_debug_vbls_jobs_lds_cols(int(H), int(bool(full_cov))))
+
+
+def fixed_basis_jobs_lds_cols(H):
+    """The widest bag whose job keeps its P in LDS in Context.fixed_basis_jobs (vbmf_debug_fixed_basis_jobs_lds_cols)."""
+    return int(lib().vbmf_debug_fixed_basis_jobs_lds_cols(int(H)))

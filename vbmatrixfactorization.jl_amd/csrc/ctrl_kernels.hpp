@@ -1297,9 +1297,17 @@ struct VblsBag {
     double* T;                     // out (optional): the same table in fp64
     double* logdet;                // out (optional): log det SigmaA
 };
-template <int NB>
-__device__ __forceinline__ void vbls_loop_dev(const double* st, StateLayout lay, int H, double Lg, int niter,
-                                              const VblsBag& g, double* lds_vl, int* __restrict__ err) {
+// K0 = B'B + L SigmaB comes through k0(i, j) (i, j < H): VblsK0State reads the context's state; the jobs form (vbls_basic_jobs_kernels.hpp)
+// hands in its model's G.  Returns nonzero -- on wave 0's threads, where the sweep keeps its pivots -- when an inverse met a pivot that
+// is not positive and finite: the caller owns the flag (one per call here, one per job there).
+struct VblsK0State {
+    const double* st; StateLayout lay; double Lg;
+    __device__ __forceinline__ double operator()(int i, int j) const {
+        return st[lay.GB() + (long long)i * lay.Hp + j] + Lg * st[lay.SB() + (long long)i * lay.Hp + j];
+    }
+};
+template <int NB, class K0>
+__device__ __forceinline__ int vbls_loop_dev(const K0& k0at, int H, double Lg, int niter, const VblsBag& g, double* lds_vl) {
     __shared__ double red[16];
     __shared__ double ca_s[16 * NB], dg_s[16 * NB];
     constexpr int NP = 16 * NB, LD = NP + 2, IMG = NP * LD;
@@ -1310,7 +1318,7 @@ __device__ __forceinline__ void vbls_loop_dev(const double* st, StateLayout lay,
     double* Tm = lds_vl + 3 * IMG;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c16 = lane & 15, q16 = lane >> 4;
-    const int Hp = lay.Hp, nbu = (H + 15) >> 4;
+    const int nbu = (H + 15) >> 4;
     const double M = g.M;
     double sigma2 = *g.sigma2;
     const double trYY = g.trYY;
@@ -1323,7 +1331,7 @@ __device__ __forceinline__ void vbls_loop_dev(const double* st, StateLayout lay,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * I + q16 + 4 * r, j = 16 * J + c16;
-            k0[o][r] = (b < NB * NB && i < H && j < H) ? st[lay.GB() + (long long)i * Hp + j] + Lg * st[lay.SB() + (long long)i * Hp + j] : 0.0;
+            k0[o][r] = (b < NB * NB && i < H && j < H) ? k0at(i, j) : 0.0;
         }
     }
     for (int t = threadIdx.x; t < NP * NP; t += 256) {
@@ -1410,7 +1418,7 @@ __device__ __forceinline__ void vbls_loop_dev(const double* st, StateLayout lay,
     }
     if (threadIdx.x < H) g.ca[threadIdx.x] = ca_s[threadIdx.x];
     if (threadIdx.x == 0) *g.sigma2 = sigma2;
-    if (bad) atomicExch(err, 1);
+    return bad;
 }
 
 // Reads GB, SB, ca, sigma2, ||Y||^2 and S (at st + lay.W1()); writes SA, ca, sigma2, log det SigmaA and the fp32 table inv(K).
@@ -1421,7 +1429,7 @@ __global__ __launch_bounds__(256) void vbls_loop_kernel(double* __restrict__ st,
     double* scal = st + lay.scal();
     const VblsBag g{st + lay.W1(), lay.Hp, scal[S_TRYY], M, scal + S_SIGMA2, st + lay.ca(), st + lay.SA(), lay.Hp, lay.Hp, SA32,
                     nullptr, scal + S_LOGDET_SA};
-    vbls_loop_dev<NB>(st, lay, H, Lg, niter, g, lds_vl, ints + I_ERR);
+    if (vbls_loop_dev<NB>(VblsK0State{st, lay, Lg}, H, Lg, niter, g, lds_vl)) atomicExch(ints + I_ERR, 1);
 }
 
 // vbls! over many bags with one fixed basis (vbmf_run_fixed_basis_batched): workgroup b runs ALL niter iterations of bag b = columns
@@ -1439,7 +1447,7 @@ __global__ __launch_bounds__(256) void vbls_batch_kernel(const double* __restric
     const long long o2 = (long long)b * H * H;
     const VblsBag g{S + o2, H, yy[b], (double)(col_off[b + 1] - col_off[b]), sigma2 + b, ca + (long long)b * H, SA + o2, H, H,
                     nullptr, T + o2, nullptr};
-    vbls_loop_dev<NB>(st, lay, H, Lg, niter, g, lds_vl, ints + I_ERR);
+    if (vbls_loop_dev<NB>(VblsK0State{st, lay, Lg}, H, Lg, niter, g, lds_vl)) atomicExch(ints + I_ERR, 1);
 }
 
 // identity (H x H, zero-padded to Hp) as a post kernel's table: A = P I, whose Gram is S = P'P

@@ -798,6 +798,168 @@ int vbmf_debug_vbls_jobs_lds_cols(int64_t H, int full_cov) {
     return (int)Mb;
 }
 
+// vbls! of the basic model (examples/mil_util.jl:182-185) for a list of (bag, model) jobs, every model with its own fp64 basis and rank, and
+// each job's norm(Y - BHat*AHat')^2: the "vbls" classifier of :469-479 for every fold of validate_with_cvs at once.  The context supplies Y
+// only.  One launch per model (vbls_jobs_model_kernel, no bound), one per non-empty 16-block tier of H_k -- at most two, the jobs sorted
+// into them through an index table -- and one synchronising read-back, whatever nmodels and njobs are (vbls_basic_jobs_kernels.hpp).
+// Every refusal comes before any launch or copy and leaves every output untouched.
+int vbmf_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int64_t niter, int64_t nmodels, const int64_t* model_H,
+                          const double* BHat, const double* SigmaB, const double* sigma2_0, const double* ca0, int64_t njobs,
+                          const int64_t* job_bag, const int64_t* job_model, double* r2, double* AHat, double* SigmaA, double* CA_diag,
+                          double* sigma2, int64_t* status) {
+    if (!c) return VBMF_ERR_INVALID;
+    const char* fn = "vbmf_fixed_basis_jobs";
+    const int64_t nk = nmodels, nj = njobs, nb = nbags, L = c->L;
+    if (nk < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nmodels must be >= 1", fn);
+    if (nj < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
+    if (!model_H || !BHat || !SigmaB || !sigma2_0 || !ca0 || !job_bag || !job_model || !status)
+        FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
+    if (!r2 && !AHat) FAIL(c, VBMF_ERR_INVALID, "%s: r2 and AHat are both NULL", fn);
+    if (nj > LS_MAX_GROUPS || nk > LS_MAX_GROUPS)
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs, %lld models (more than the %lld workgroups of one grid)", fn, (long long)nj,
+             (long long)nk, (long long)LS_MAX_GROUPS);
+    if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set", fn);
+    BagDims bd;
+    TRY(bags_check(c, fn, nb, col_off, bd));
+    int64_t sumH = 0, sumH2 = 0;
+    for (int64_t k = 0; k < nk; ++k) {
+        const int64_t H = model_H[k];
+        if (H < 1 || H > VJOBS_MAX_H)
+            FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: model_H[%lld] = %lld (built for 1 <= H <= %d)", fn, (long long)k, (long long)H, VJOBS_MAX_H);
+        sumH += H;
+        sumH2 += H * H;
+    }
+    // the jobs' tiers of H_k; per tier the widest P kept in LDS (doubles)
+    int64_t SMH = 0, SJH = 0, SJH2 = 0, grp_n[2] = {0, 0}, grp_lds[2] = {0, 0};
+    bool spill = false;
+    for (int64_t j = 0; j < nj; ++j) {
+        const int64_t b = job_bag[j], k = job_model[j];
+        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
+        if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_model[%lld] = %lld outside 0..nmodels-1", fn, (long long)j, (long long)k);
+        const int64_t Mb = col_off[b + 1] - col_off[b], H = model_H[k];
+        SMH += Mb * H;                                            // (at most 2^24 terms of at most 2^60 / 32: no overflow)
+        SJH += H;
+        SJH2 += H * H;
+        const int gi = nb_tier(H) - 1;
+        ++grp_n[gi];
+        if (fjobs_in_lds(gi + 1, (int)H, Mb)) grp_lds[gi] = std::max(grp_lds[gi], Mb * H);
+        else spill = true;
+    }
+    {
+        auto finite = [](const double* v, int64_t n) {
+            for (int64_t i = 0; i < n; ++i)
+                if (!std::isfinite(v[i])) return i;
+            return (int64_t)-1;
+        };
+        int64_t bad = finite(BHat, L * sumH);
+        if (bad >= 0) {                                          // (the model by its offset)
+            int64_t k = 0, off = 0;
+            while (k + 1 < nk && off + L * model_H[k] <= bad) off += L * model_H[k++];
+            FAIL(c, VBMF_ERR_INVALID, "%s: BHat of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
+        }
+        bad = finite(SigmaB, sumH2);
+        if (bad >= 0) {
+            int64_t k = 0, off = 0;
+            while (k + 1 < nk && off + model_H[k] * model_H[k] <= bad) off += model_H[k] * model_H[k], ++k;
+            FAIL(c, VBMF_ERR_INVALID, "%s: SigmaB of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
+        }
+        bad = finite(sigma2_0, nk);
+        if (bad >= 0) FAIL(c, VBMF_ERR_INVALID, "%s: sigma2_0 of model %lld is not finite", fn, (long long)bad);
+        bad = finite(ca0, nk);
+        if (bad >= 0) FAIL(c, VBMF_ERR_INVALID, "%s: ca0 of model %lld is not finite", fn, (long long)bad);
+    }
+    if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
+    // the upload, one block: [col_off nb + 1 | job_bag | job_model | job_off | job_sa | job_h | idx (nj each) | model_H | b_off | k_off |
+    //                         h_off (nk each) (int64) | sigma2_0 | ca0 (nk each) | the bases, column-major L x H_k | SigmaB (H_k^2 each)]
+    const int64_t u_bag = nb + 1, u_mod = u_bag + nj, u_off = u_mod + nj, u_jsa = u_off + nj, u_jh = u_jsa + nj, u_idx = u_jh + nj,
+                  u_mh = u_idx + nj, u_bo = u_mh + nk, u_ko = u_bo + nk, u_ho = u_ko + nk, u_sig = u_ho + nk, u_ca0 = u_sig + nk,
+                  u_b = u_ca0 + nk, u_sb = u_b + L * sumH, n_up = u_sb + sumH2;
+    // behind it: [Bt L sum H | G sum H^2 | gd | sd (sum H) | r2 | sigma2 | status (nj each) | SigmaA (the jobs' H_k^2) | CA (the jobs' H_k)
+    //             | A (the jobs' M_b x H_k blocks in job order) | T (the jobs' H_k^2) | P of the jobs that do not keep it in LDS];
+    //             [r2 .. A] is the read-back
+    const int64_t o_bt = n_up, o_g = o_bt + L * sumH, o_gd = o_g + sumH2, o_sd = o_gd + sumH, o_r2 = o_sd + sumH, o_sig = o_r2 + nj,
+                  o_st = o_sig + nj, o_sa = o_st + nj, o_ca = o_sa + SJH2, o_a = o_ca + SJH, o_t = o_a + SMH, o_p = o_t + SJH2,
+                  total = o_p + (spill ? SMH : 0);
+    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
+    try {
+        up.resize((size_t)n_up);
+        res.resize((size_t)(o_t - o_r2));
+    } catch (const std::bad_alloc&) {
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of models, job tables and results", fn, (long long)((n_up + o_t - o_r2) * 8));
+    }
+    long long* ui = reinterpret_cast<long long*>(up.data());
+    for (int64_t b = 0; b <= nb; ++b) ui[b] = col_off[b];
+    for (int64_t k = 0, bo = 0, ko = 0, ho = 0; k < nk; ++k) {
+        const int64_t H = model_H[k];
+        ui[u_mh + k] = H; ui[u_bo + k] = bo; ui[u_ko + k] = ko; ui[u_ho + k] = ho;
+        bo += L * H; ko += H * H; ho += H;
+    }
+    const int64_t grp_at[2] = {0, grp_n[0]};                      // the tiers' first slots of idx
+    {
+        int64_t fill[2] = {grp_at[0], grp_at[1]};
+        for (int64_t j = 0, off = 0, sa = 0, jh = 0; j < nj; ++j) {
+            const int64_t b = job_bag[j], k = job_model[j], H = model_H[k];
+            ui[u_bag + j] = b; ui[u_mod + j] = k; ui[u_off + j] = off; ui[u_jsa + j] = sa; ui[u_jh + j] = jh;
+            ui[u_idx + fill[nb_tier(H) - 1]++] = j;
+            off += (col_off[b + 1] - col_off[b]) * H; sa += H * H; jh += H;
+        }
+    }
+    memcpy(up.data() + u_sig, sigma2_0, (size_t)nk * 8);
+    memcpy(up.data() + u_ca0, ca0, (size_t)nk * 8);
+    memcpy(up.data() + u_b, BHat, (size_t)(L * sumH) * 8);
+    memcpy(up.data() + u_sb, SigmaB, (size_t)sumH2 * 8);
+    auto run = [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->o.device));
+        double* d = nullptr;
+        TRY(bags_reserve(c, total, &d));
+        HIPCHK(c, hipMemcpyAsync(d, up.data(), (size_t)n_up * 8, hipMemcpyHostToDevice, c->stream));
+        const long long* di = reinterpret_cast<const long long*>(d);
+        const VjobsModels ms{di + u_mh, di + u_bo, di + u_ko, di + u_ho};
+        hipLaunchKernelGGL(vbls_jobs_model_kernel, dim3((unsigned)nk), dim3(SCORE_THREADS), 0, c->stream, ms, d + u_b, d + u_sb, (long long)L,
+                           d + o_bt, d + o_g, d + o_gd, d + o_sd, (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
+        HIPCHK(c, hipGetLastError());
+        FjobsArgs g{c->Y2, c->d2.KS, (long long)L, di, di + u_bag, di + u_mod, di + u_off, di + u_jsa, di + u_jh, nullptr, ms, (int)niter,
+                    d + o_bt, d + o_g, d + u_sig, d + u_ca0, spill ? d + o_p : nullptr, d + o_a, d + o_sa, d + o_t, d + o_ca, d + o_sig,
+                    d + o_r2, reinterpret_cast<long long*>(d + o_st)};
+        for (int gi = 0; gi < 2; ++gi) {
+            if (!grp_n[gi]) continue;
+            g.idx = di + u_idx + grp_at[gi];
+            const size_t lds = (size_t)(fjobs_fixed_doubles(gi + 1) + grp_lds[gi]) * 8;
+            dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
+                dispatch<1, 2>(gi + 1, [&](auto nbk) {
+                    hipLaunchKernelGGL((vbls_basic_jobs_kernel<decltype(ym)::value, decltype(nbk)::value>), dim3((unsigned)grp_n[gi]),
+                                       dim3(FJOBS_THREADS), lds, c->stream, g);
+                });
+            });
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
+        return VBMF_OK;
+    };
+    const int rc = run();
+    if (rc != VBMF_OK) {
+        hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    auto at = [&](int64_t o_x) { return res.data() + (o_x - o_r2); };   // block x of the read-back
+    if (r2) memcpy(r2, at(o_r2), (size_t)nj * 8);
+    if (sigma2) memcpy(sigma2, at(o_sig), (size_t)nj * 8);
+    memcpy(status, at(o_st), (size_t)nj * 8);
+    if (SigmaA) memcpy(SigmaA, at(o_sa), (size_t)SJH2 * 8);       // symmetric: row- and column-major alike
+    if (CA_diag) memcpy(CA_diag, at(o_ca), (size_t)SJH * 8);
+    if (AHat) memcpy(AHat, at(o_a), (size_t)SMH * 8);
+    return VBMF_OK;
+}
+
+// the widest bag whose job keeps its P in LDS at this H (fjobs_in_lds): the tests place a bag on either side of it
+int vbmf_debug_fixed_basis_jobs_lds_cols(int64_t H) {
+    if (H < 1 || H > VJOBS_MAX_H) return 0;
+    int64_t Mb = 0;
+    while (fjobs_in_lds(nb_tier(H), (int)H, Mb + 1)) ++Mb;
+    return (int)Mb;
+}
+
 // lowerBound / lowerBoundTrimmed of every bag (examples/mil_util.jl:502-514 after a batched vbls!)
 int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, int clamp, double trim, int grouped,
                                     const double* ATVecHat, const double* diagSigmaATVec, const double* CA, const double* beta,

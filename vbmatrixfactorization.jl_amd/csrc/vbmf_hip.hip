@@ -60,6 +60,7 @@
 #include "fit_basic_gram_kernels.hpp"
 #include "score_kernels.hpp"
 #include "vbls_jobs_kernels.hpp"
+#include "vbls_basic_jobs_kernels.hpp"
 #include "gram_kernels.hpp"
 #include "out_kernels.hpp"
 

@@ -14,7 +14,7 @@ export vbmf_parameters, vbmf_init, vbmf, vbmf!, updateA!, updateB!, updateCA!, u
        vbls!, vbls_batch!, vbmf_batch!, row_gram_batch, vbmf_sparse_batch!, vbmf_dual_batch!, vbmf_trial_batch!, vbmf_sparse_masked_batch!, copy_vbmf_params, preprocess_device, vbmf_on!, invalidate!,
        vbmf_sparse_parameters, vbmf_sparse_init, vbmf_sparse!, lowerBound, lowerBoundTrimmed,
        residual_batch, lowerBound_batch, lowerBoundTrimmed_batch,
-       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs, sparse_fixed_basis_jobs, sparse_scored_jobs,
+       ols_batch, rls_batch, ls_residual_batch, bag_least_squares_jobs, sparse_fixed_basis_jobs, sparse_scored_jobs, fixed_basis_jobs,
        vbmf_dual_parameters, vbmf_dual_init, vbmf_dual!,
        vbmf_trial_parameters, vbmf_trial_init, vbmf_trial!, set_gram_form!, get_YHat!, get_factor!, set_Y_gather!
 
@@ -1240,6 +1240,46 @@ function sparse_fixed_basis_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, H::Int
     blocks(v) = [v[off[j]+1:off[j+1]] for j in 1:nj]
     return (r2 = r2, sigmaHat = sg, zeta = zeta, status = status, SigmaA = SA, ATVecHat = blocks(A), diagSigmaATVec = blocks(dS),
             CA = blocks(CA), beta = blocks(beta))
+end
+
+"""
+    fixed_basis_jobs(ctx, col_off, model_H, BHat, SigmaB, sigma2_0, ca0, job_bag, job_model, niter)
+
+vbls! of the basic model (examples/mil_util.jl:182-185) for a list of (bag, model) jobs in ONE device call (vbmf_fixed_basis_jobs) --
+the "vbls" classifier of examples/mil_util.jl:469-479 for every fold at once.  `ctx` holds every bag of the data set side by side
+(col_off: 0-based offsets); only its Y is read.  Model k: its own rank `model_H[k]` <= 32, `BHat[k]` (L x H_k), `SigmaB[k]` (H_k x H_k)
+and the start values `sigma2_0[k]`, `ca0[k]` (CA = ca0 I).  Job j runs bag `job_bag[j]` against model `job_model[j]` (both 1-based).
+Returns a named tuple: r2, sigma2, status (per job; status 1 = a failed job, NaN in its outputs), and per job AHat (M_b x H_k), SigmaA
+(H_k x H_k) and CA_diag (H_k).
+"""
+function fixed_basis_jobs(ctx::Ptr{Cvoid}, col_off::Vector{Int64}, model_H::Vector{Int64}, BHat::Vector{Matrix{Float64}},
+                          SigmaB::Vector{Matrix{Float64}}, sigma2_0::Vector{Float64}, ca0::Vector{Float64},
+                          job_bag::AbstractVector{<:Integer}, job_model::AbstractVector{<:Integer}, niter::Int)
+    nb, nk, nj = length(col_off) - 1, length(BHat), length(job_bag)
+    (nk >= 1 && length(model_H) == nk && length(SigmaB) == nk && length(sigma2_0) == nk && length(ca0) == nk) ||
+        error("fixed_basis_jobs: every per-model input needs one entry per model, at least one model")
+    (nj >= 1 && length(job_model) == nj) || error("fixed_basis_jobs: job_bag and job_model must have one entry per job, at least one")
+    L = size(BHat[1], 1)
+    all(k -> size(BHat[k]) == (L, model_H[k]) && size(SigmaB[k]) == (model_H[k], model_H[k]), 1:nk) ||
+        error("fixed_basis_jobs: every model needs BHat L x H_k and SigmaB H_k x H_k")
+    all(j -> 1 <= job_bag[j] <= nb && 1 <= job_model[j] <= nk, 1:nj) || error("fixed_basis_jobs: a job names a bag or a model that is not there")
+    Ball = reduce(vcat, [vec(B) for B in BHat])
+    SBall = reduce(vcat, [vec(S) for S in SigmaB])
+    jb, jk = Int64[b - 1 for b in job_bag], Int64[k - 1 for k in job_model]
+    Hj = Int64[model_H[k] for k in job_model]
+    Mj = Int64[col_off[b+1] - col_off[b] for b in job_bag]
+    off, soff, hoff = Int64[0; cumsum(Mj .* Hj)], Int64[0; cumsum(Hj .* Hj)], Int64[0; cumsum(Hj)]
+    r2, sg = Array{Float64}(undef, nj), Array{Float64}(undef, nj)
+    A, SA, CA = Array{Float64}(undef, off[end]), Array{Float64}(undef, soff[end]), Array{Float64}(undef, hoff[end])
+    status = Array{Int64}(undef, nj)
+    chk(ctx, ccall((:vbmf_fixed_basis_jobs, libvbmf), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        ctx, nb, col_off, niter, nk, model_H, Ball, SBall, sigma2_0, ca0, nj, jb, jk, r2, A, SA, CA, sg, status))
+    return (r2 = r2, sigma2 = sg, status = status,
+            AHat = [reshape(A[off[j]+1:off[j+1]], Int(Mj[j]), Int(Hj[j])) for j in 1:nj],
+            SigmaA = [reshape(SA[soff[j]+1:soff[j+1]], Int(Hj[j]), Int(Hj[j])) for j in 1:nj],
+            CA_diag = [CA[hoff[j]+1:hoff[j+1]] for j in 1:nj])
 end
 
 """
