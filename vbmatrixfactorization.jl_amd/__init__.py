@@ -2531,6 +2531,19 @@ def _jobs_run(Ys, call):
         return call(bags.ctx, bags.col_off)
 
 
+def _job_list(job_bag, job_model, nbags, nmodels, refuse):
+    """A call's (bag, model) jobs as two lists of ints, as many of each and at least one, every one in range"""
+    job_bag, job_model = [int(b) for b in job_bag], [int(k) for k in job_model]
+    if len(job_bag) != len(job_model) or not job_bag:
+        refuse(f"{len(job_bag)} job bags and {len(job_model)} job models (as many of each, at least one)")
+    for j, (b, k) in enumerate(zip(job_bag, job_model)):
+        if not 0 <= b < nbags:
+            refuse(f"job {j}: bag {b} outside 0..{nbags - 1}")
+        if not 0 <= k < nmodels:
+            refuse(f"job {j}: model {k} outside 0..{nmodels - 1}")
+    return job_bag, job_model
+
+
 def vbls_sparse_jobs_(Ys, models, job_bag, job_model, niter, full_cov=False):
     """vbls! of the ARD-sparse models for a list of (bag, model) jobs in ONE device call: job j does what
     vbls_(Ys[job_bag[j]], copy_vbmf_params(Ys[job_bag[j]], models[job_model[j]]), niter, full_cov=full_cov) does
@@ -2554,14 +2567,7 @@ def vbls_sparse_jobs_(Ys, models, job_bag, job_model, niter, full_cov=False):
         refuse(f"niter = {niter} < 1")
     L, Ms = _jobs_bags(fn, Ys, refuse)
     mods = [_jobs_model(fn, res, L, H, f"model {k}", refuse) for k, res in enumerate(models)]
-    job_bag, job_model = [int(b) for b in job_bag], [int(k) for k in job_model]
-    if len(job_bag) != len(job_model) or not job_bag:
-        refuse(f"{len(job_bag)} job bags and {len(job_model)} job models (as many of each, at least one)")
-    for j, (b, k) in enumerate(zip(job_bag, job_model)):
-        if not 0 <= b < len(Ms):
-            refuse(f"job {j}: bag {b} outside 0..{len(Ms) - 1}")
-        if not 0 <= k < len(models):
-            refuse(f"job {j}: model {k} outside 0..{len(models) - 1}")
+    job_bag, job_model = _job_list(job_bag, job_model, len(Ms), len(models), refuse)
     r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_fixed_basis_jobs(off, H, mods, job_bag, job_model, int(niter), full_cov=full_cov))
     sets = []
     for j, (b, k) in enumerate(zip(job_bag, job_model)):
@@ -2605,14 +2611,7 @@ def vbls_jobs_(Ys, models, job_bag, job_model, niter):
         refuse(f"niter = {niter} < 1")
     L, Ms = _jobs_bags(fn, Ys, refuse)
     mods = [_basic_jobs_model(res, L, f"model {k}", refuse) for k, res in enumerate(models)]
-    job_bag, job_model = [int(b) for b in job_bag], [int(k) for k in job_model]
-    if len(job_bag) != len(job_model) or not job_bag:
-        refuse(f"{len(job_bag)} job bags and {len(job_model)} job models (as many of each, at least one)")
-    for j, (b, k) in enumerate(zip(job_bag, job_model)):
-        if not 0 <= b < len(Ms):
-            refuse(f"job {j}: bag {b} outside 0..{len(Ms) - 1}")
-        if not 0 <= k < len(models):
-            refuse(f"job {j}: model {k} outside 0..{len(models) - 1}")
+    job_bag, job_model = _job_list(job_bag, job_model, len(Ms), len(models), refuse)
     r = _jobs_run(Ys, lambda ctx, off: ctx.fixed_basis_jobs(off, mods, job_bag, job_model, int(niter)))
     sets = []
     for j, (b, k) in enumerate(zip(job_bag, job_model)):
@@ -2753,50 +2752,86 @@ def classify_folds(models, tests, Ys, class_alg="ols", niter=None, threshold=1e-
         return _classify_folds_dual(fn, models, ids, Ys, L, 20 if niter is None else int(niter))
     if class_alg == "vbls":
         return _classify_folds_vbls(fn, models, ids, Ys, L, 150 if niter is None else int(niter))
-    bases, trained = [], []
-    for f, pair in enumerate(models):
-        if _untrained(pair):
-            continue
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            refuse(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
+    def two_bases(f, pair):
+        out = []
         for k, r in enumerate(pair):
             if getattr(r, "BHat", None) is None:
                 refuse(f"fold {f}: res{k} ({type(r).__name__}) has no BHat")
             B = _ls_basis(f"{fn}: fold {f}: res{k}", r.BHat, lam)
             if B.shape[0] != L:
                 refuse(f"fold {f}: res{k}.BHat is {B.shape[0]} x {B.shape[1]}, the bags have L = {L} rows")
-            bases.append(B)
+            out.append(B)
+        return out
+
+    def call(bases, job_bag, job_basis):
+        run = lambda ctx, off: ctx.bag_least_squares_jobs(off, bases, [lam] * len(bases), job_bag, job_basis)
+        if isinstance(Ys, BagPool):                                     # (Xs, r2, status) -> (r2, status): a basis is flagged, not a job
+            return run(Ys.ctx, Ys.col_off)[1:]
+        with _on_device(Ys, bases[0].shape[1], Bags) as bags:           # (a Bags of the first basis' rank: the call reads Y only)
+            return run(bags.ctx, bags.col_off)[1:]
+    return _fold_jobs(fn, models, ids, two_bases, call, _residual_labels,
+                      lambda k, b: f"BHat'BHat + lambda I of res{k} is not positive definite (a pivot is not positive or not finite); "
+                                   f"class_alg='rls' is the classifier for such bases", model_flags=True)
+
+
+# What a fold's entry of `models` may be: (is it an untrained fold?, must it be a pair?, what a trained fold with no test bags returns).
+_PAIR_FOLDS = (_untrained, True, lambda: (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)))      # (res0, res1) or (0, 0)
+_SCORED_FOLDS = (lambda m: _untrained(m) or (type(m) is int and m == 0), False,                         # a bare model, a bare 0 too
+                 lambda: dict(L0=np.empty(0), L1=np.empty(0), err0=np.empty(0), err1=np.empty(0), status=np.empty(0, dtype=np.int64)))
+
+
+def _fold_front(fn, models, two_models, kind=_PAIR_FOLDS):
+    """(the call's models, the trained folds): models 2 t and 2 t + 1 are two_models(f, models[f]) of the t-th trained fold f; a fold
+    that was not trained is passed over"""
+    mods, trained = [], []
+    for f, pair in enumerate(models):
+        if kind[0](pair):
+            continue
+        if kind[1] and (not isinstance(pair, (tuple, list)) or len(pair) != 2):
+            _ls_refuser(fn)(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
+        mods += two_models(f, pair)
         trained.append(f)
-    job_bag, job_basis, where = [], [], {}
+    return mods, trained
+
+
+def _residual_labels(f, r2, j0, j1):
+    """"ols", "rls" and "vbls": err = norm(Y - BHat*AHat') (:483-484), label 1 where err0 > err1 (:487-491)"""
+    err0, err1 = np.sqrt(r2[j0]), np.sqrt(r2[j1])
+    return (err0 > err1).astype(np.int64), err0, err1
+
+
+def _fold_jobs(fn, models, ids, two_models, call, result, failed, kind=_PAIR_FOLDS, model_flags=False):
+    """What the fold functions share: every fold's test bags ids[f] against the fold's two models in one device call.
+    two_models(f, models[f]): the fold's two call models, checked on the host (_fold_front).  The jobs are (bag, 2 t) for every test
+    bag of the t-th trained fold, then (bag, 2 t + 1) for every one.  call(mods, job_bag, job_model) -> (r, flags): the one device call;
+    flags[j] is set for a failed job (model_flags: flags[k] for a failed model, and b below is None).  result(f, r, j0, j1): fold f's
+    result from r, j0 and j1 the slices of its jobs against its first and its second model.  Returns a list with result() per fold,
+    None for an untrained fold, kind[2]() for one with no test bags.  If anything is flagged, VbmfError is raised after every fold
+    has been computed -- f"{fn}: fold {f}: " + failed(k, b) for the first fold with a flag, k and b the model (0 / 1) and the bag of its
+    first flagged job -- with .results the list, None in every such fold's place."""
+    mods, trained = _fold_front(fn, models, two_models, kind)
+    job_bag, job_model, where = [], [], {}
     for t, f in enumerate(trained):
         n = len(ids[f])
         if n:
-            where[f] = len(job_bag)
+            where[f] = (t, len(job_bag), n)
             job_bag += ids[f] + ids[f]
-            job_basis += [2 * t] * n + [2 * t + 1] * n
-    out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
+            job_model += [2 * t] * n + [2 * t + 1] * n
+    out = [None if kind[0](pair) else kind[2]() for pair in models]
     if not job_bag:
         return out
-    if isinstance(Ys, BagPool):
-        _, r2, status = Ys.ctx.bag_least_squares_jobs(Ys.col_off, bases, [lam] * len(bases), job_bag, job_basis)
-    else:
-        with _on_device(Ys, bases[0].shape[1], Bags) as bags:
-            _, r2, status = bags.ctx.bag_least_squares_jobs(bags.col_off, bases, [lam] * len(bases), job_bag, job_basis)
+    r, flags = call(mods, job_bag, job_model)
+    for f, (t, j0, n) in where.items():
+        out[f] = result(f, r, slice(j0, j0 + n), slice(j0 + n, j0 + 2 * n))
     bad = []
-    for t, f in enumerate(trained):
-        if f not in where:
-            continue
-        if status[2 * t] or status[2 * t + 1]:
-            bad.append((f, 0 if status[2 * t] else 1))
+    for f, (t, j0, n) in where.items() if np.any(flags) else ():
+        st = np.flatnonzero(flags[2 * t:2 * t + 2] if model_flags else flags[j0:j0 + 2 * n])
+        if st.size:
+            bad.append((f, int(st[0]), None) if model_flags else (f, int(st[0]) // n, ids[f][int(st[0]) % n]))
             out[f] = None
-            continue
-        n, j0 = len(ids[f]), where[f]
-        err0, err1 = np.sqrt(r2[j0:j0 + n]), np.sqrt(r2[j0 + n:j0 + 2 * n])
-        out[f] = ((err0 > err1).astype(np.int64), err0, err1)           # :487-491
-    if bad:
-        f, k = bad[0]
-        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: BHat'BHat + lambda I of res{k} is not positive definite (a pivot is not "
-                                             f"positive or not finite); class_alg='rls' is the classifier for such bases")
+    if bad:                                                              # (a flagged basis whose fold has no test bags fails nothing)
+        f, k, b = bad[0]
+        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: " + failed(k, b))
         e.results = out
         raise e
     return out
@@ -2808,12 +2843,9 @@ def _classify_folds_dual(fn, models, ids, Ys, L, niter):
     if niter < 1:
         refuse(f"niter = {niter} < 1")
     Ms = Ys.Ms if isinstance(Ys, (BagPool, _Uploaded)) else [int(np.shape(Y)[1]) for Y in Ys]
-    mods, trained, H = [], [], None
-    for f, pair in enumerate(models):
-        if _untrained(pair):
-            continue
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            refuse(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
+    Hs = []                                                              # (the first trained fold's H is the call's)
+
+    def two_models(f, pair):
         if any(isinstance(r, vbmf_trial_parameters) for r in pair):
             _score_refuser(fn)(f"fold {f}: " + _TRIAL_TWO_SETS)
         for k, r in enumerate(pair):
@@ -2823,102 +2855,49 @@ def _classify_folds_dual(fn, models, ids, Ys, L, niter):
         if type(pair[0]) is not type(pair[1]) or int(pair[0].H) != int(pair[1].H):
             refuse(f"fold {f}: res0 is a {type(pair[0]).__name__} with H = {pair[0].H}, res1 a {type(pair[1]).__name__} with "
                    f"H = {pair[1].H} (one type and one H per fold)")
-        H = int(pair[0].H) if H is None else H
-        if H > _JOBS_MAX_H:
-            refuse(f"fold {f}: H = {H} > {_JOBS_MAX_H}")
-        mods += [_jobs_model(fn, r, L, H, f"fold {f}: res{k}", refuse) for k, r in enumerate(pair)]
-        trained.append(f)
-    job_bag, job_model, where = [], [], {}
-    for t, f in enumerate(trained):
-        n = len(ids[f])
-        if n:
-            where[f] = len(job_bag)
-            job_bag += ids[f] + ids[f]
-            job_model += [2 * t] * n + [2 * t + 1] * n
-    out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
-    if not job_bag:
-        return out
-    r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_fixed_basis_jobs(off, H, mods, job_bag, job_model, int(niter), full_cov=True))
-    r2, status = r["r2"], r["status"]
-    bad = []
-    for f in trained:
-        if f not in where:
-            continue
-        n, j0 = len(ids[f]), where[f]
-        st = np.asarray(status[j0:j0 + 2 * n])
-        if st.any():
-            j = int(np.flatnonzero(st)[0])
-            bad.append((f, j // n, ids[f][j % n]))
-            out[f] = None
-            continue
+        Hs.append(int(pair[0].H))
+        if Hs[0] > _JOBS_MAX_H:
+            refuse(f"fold {f}: H = {Hs[0]} > {_JOBS_MAX_H}")
+        return [_jobs_model(fn, r, L, Hs[0], f"fold {f}: res{k}", refuse) for k, r in enumerate(pair)]
+
+    def call(mods, job_bag, job_model):
+        r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_fixed_basis_jobs(off, Hs[0], mods, job_bag, job_model, int(niter), full_cov=True))
+        return r["r2"], r["status"]
+
+    def labels(f, r2, j0, j1):
         scale = L * np.asarray([Ms[b] for b in ids[f]], dtype=np.float64)
-        err0, err1 = np.sqrt(r2[j0:j0 + n]) / scale, np.sqrt(r2[j0 + n:j0 + 2 * n]) / scale      # :523-524
-        out[f] = (np.where(err0 < err1, 0, 1).astype(np.int64), err0, err1)                     # :526-530
-    if bad:
-        f, k, b = bad[0]
-        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against res{k} met a precision that is not finite or a "
-                                             f"pivot that is not positive and finite")
-        e.results = out
-        raise e
-    return out
+        err0, err1 = np.sqrt(r2[j0]) / scale, np.sqrt(r2[j1]) / scale                           # :523-524
+        return np.where(err0 < err1, 0, 1).astype(np.int64), err0, err1                         # :526-530
+    return _fold_jobs(fn, models, ids, two_models, call, labels,
+                      lambda k, b: f"vbls! of bag {b} against res{k} met a precision that is not finite or a pivot that is not positive "
+                                   f"and finite")
+
+
+def _vbls_two_models(fn, L):
+    """the "vbls" classifier's two call models of a fold, checked on the host"""
+    what = ("class_alg = 'vbls' takes the basic model's vbmf_parameters, as train_folds(..., 'basic') returns them; "
+            "'ols', 'rls' or 'dual' take other models, and any pair of models runs per fold with classify_bags")
+    return lambda f, pair: [_basic_jobs_model(r, L, f"fold {f}: res{k}", _ls_refuser(fn), what) for k, r in enumerate(pair)]
 
 
 def _fold_models_vbls(fn, models, L):
     """(the call's models, the trained folds) of the "vbls" classifier, checked on the host: models 2 t and 2 t + 1 are the t-th trained
     fold's res0 and res1"""
-    refuse = _ls_refuser(fn)
-    mods, trained = [], []
-    for f, pair in enumerate(models):
-        if _untrained(pair):
-            continue
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            refuse(f"fold {f}: a model is a pair (res0, res1) or (0, 0)")
-        mods += [_basic_jobs_model(r, L, f"fold {f}: res{k}", refuse,
-                                   "class_alg = 'vbls' takes the basic model's vbmf_parameters, as train_folds(..., 'basic') returns them; "
-                                   "'ols', 'rls' or 'dual' take other models, and any pair of models runs per fold with classify_bags")
-                 for k, r in enumerate(pair)]
-        trained.append(f)
-    return mods, trained
+    return _fold_front(fn, models, _vbls_two_models(fn, L))
 
 
 def _classify_folds_vbls(fn, models, ids, Ys, L, niter):
     """classify_folds' "vbls" branch: the folds' basic-model sets as one call's models, two jobs per tested bag"""
-    refuse = _ls_refuser(fn)
     if niter < 1:
-        refuse(f"niter = {niter} < 1")
-    mods, trained = _fold_models_vbls(fn, models, L)
-    job_bag, job_model, where = [], [], {}
-    for t, f in enumerate(trained):
-        n = len(ids[f])
-        if n:
-            where[f] = len(job_bag)
-            job_bag += ids[f] + ids[f]
-            job_model += [2 * t] * n + [2 * t + 1] * n
-    out = [None if _untrained(pair) else (np.empty(0, dtype=np.int64), np.empty(0), np.empty(0)) for pair in models]
-    if not job_bag:
-        return out
-    r = _jobs_run(Ys, lambda ctx, off: ctx.fixed_basis_jobs(off, mods, job_bag, job_model, int(niter)))
-    r2, status = r["r2"], r["status"]
-    bad = []
-    for f in trained:
-        if f not in where:
-            continue
-        n, j0 = len(ids[f]), where[f]
-        st = np.asarray(status[j0:j0 + 2 * n])
-        if st.any():
-            j = int(np.flatnonzero(st)[0])
-            bad.append((f, j // n, ids[f][j % n]))
-            out[f] = None
-            continue
-        err0, err1 = np.sqrt(r2[j0:j0 + n]), np.sqrt(r2[j0 + n:j0 + 2 * n])                     # :483-484
-        out[f] = ((err0 > err1).astype(np.int64), err0, err1)                                   # :487-491
-    if bad:
-        f, k, b = bad[0]
-        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against res{k} met a pivot that is not positive and finite "
-                                             f"or ended with a sigma2, CA or residual that is not finite")
-        e.results = out
-        raise e
-    return out
+        _ls_refuser(fn)(f"niter = {niter} < 1")
+
+    def call(mods, job_bag, job_model):
+        r = _jobs_run(Ys, lambda ctx, off: ctx.fixed_basis_jobs(off, mods, job_bag, job_model, int(niter)))
+        return r["r2"], r["status"]
+
+    return _fold_jobs(fn, models, ids, _vbls_two_models(fn, L), call, _residual_labels,
+                      lambda k, b: f"vbls! of bag {b} against res{k} met a pivot that is not positive and finite or ended with a sigma2, "
+                                   f"CA or residual that is not finite")
 
 
 def _scored_labels(r, class_alg, threshold):
@@ -2962,10 +2941,9 @@ def _factorize_folds(fn, models, tests, Ys, niter, threshold, alg=None):
         refuse(f"threshold = {threshold} (lowerBoundTrimmed takes a finite threshold >= 0)")
     L, Ms = _jobs_bags(fn, Ys, refuse)
     ids = _fold_ids(fn, tests, len(Ms))
-    mods, trained = [], []
-    for f, m in enumerate(models):
-        if _untrained(m) or (type(m) is int and m == 0):
-            continue
+    fulls = []                                                           # per trained fold and test bag: the full_cov form? (:405-409)
+
+    def two_models(f, m):
         res = m[0] if isinstance(m, (tuple, list)) and len(m) == 2 else m            # (res0, anything): the second is not read (:610)
         if type(res) is not vbmf_sparse_parameters or not 0 < int(getattr(res, "H1", 0)) < int(res.H):
             refuse(f"fold {f}: {what} takes a vbmf_sparse_parameters with 0 < H1 < H (what train_local_folds returns), bare or first "
@@ -2982,44 +2960,24 @@ def _factorize_folds(fn, models, tests, Ys, niter, threshold, alg=None):
                                                                                     res.alpha0, res.beta0, res.eta0, res.zeta0)):
             refuse(f"fold {f}: the model has a BHat, SigmaB, CB, delta, gamma or hyper-prior that is not finite")
         tb = _truncated_basis(res)
-        mods.append(_scored_model(_SparseInitPriors, tb["H"], tb))                             # :398-404
-        mods.append(_scored_model(res, H, dict(BHat=B, SigmaB=SB, CB=res.CB, gamma=res.gamma, delta=res.delta)))
-        trained.append((f, H - int(res.H1)))
-    job_bag, job_model, job_full, job_trim, where = [], [], [], [], {}
-    for t, (f, H0) in enumerate(trained):
-        n = len(ids[f])
-        if n:
-            where[f] = len(job_bag)
-            job_bag += ids[f] + ids[f]
-            job_model += [2 * t] * n + [2 * t + 1] * n
-            job_full += [Ms[b] * H0 < 1600 for b in ids[f]] * 2                              # :405-409
-            job_trim += [-1.0] * n + [threshold] * n
-    empty = lambda: dict(L0=np.empty(0), L1=np.empty(0), err0=np.empty(0), err1=np.empty(0), status=np.empty(0, dtype=np.int64))
-    is_trained = {f for f, _ in trained}
-    out = [empty() if f in is_trained else None for f in range(len(models))]
-    if not job_bag:
-        return out
-    r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_scored_jobs(off, mods, job_bag, job_model, job_full, job_trim, niter))
-    bad = []
-    for f, _ in trained:
-        if f not in where:
-            continue
-        n, j0 = len(ids[f]), where[f]
-        st = np.asarray(r["status"][j0:j0 + 2 * n])
-        out[f] = dict(L0=r["lb"][j0:j0 + n].copy(), L1=r["lb"][j0 + n:j0 + 2 * n].copy(), err0=np.sqrt(r["r2"][j0:j0 + n]),
-                      err1=np.sqrt(r["r2"][j0 + n:j0 + 2 * n]), status=(st[:n] | st[n:]).astype(np.int64))
-        if st.any():
-            j = int(np.flatnonzero(st)[0])
-            bad.append((f, j // n, ids[f][j % n]))
-    if bad:
-        f, k, b = bad[0]
-        results = [None if any(f == g for g, _, _ in bad) else o for f, o in enumerate(out)]
-        e = VbmfError(capi.VBMF_ERR_NUMERIC, f"{fn}: fold {f}: vbls! of bag {b} against {'the whole' if k else 'the truncated'} basis met a "
-                                             f"precision that is not finite or a pivot that is not positive and finite, or its bound is "
-                                             f"not finite")
-        e.results = results
-        raise e
-    return out
+        fulls.append([Ms[b] * (H - int(res.H1)) < 1600 for b in ids[f]])
+        return [_scored_model(_SparseInitPriors, tb["H"], tb),                                 # :398-404
+                _scored_model(res, H, dict(BHat=B, SigmaB=SB, CB=res.CB, gamma=res.gamma, delta=res.delta))]
+
+    def call(mods, job_bag, job_model):
+        job_full, job_trim = [], []                                      # (the jobs' order: a fold's bags against 2 t, then against 2 t + 1)
+        for ff in fulls:
+            job_full += ff + ff
+            job_trim += [-1.0] * len(ff) + [threshold] * len(ff)
+        r = _jobs_run(Ys, lambda ctx, off: ctx.sparse_scored_jobs(off, mods, job_bag, job_model, job_full, job_trim, niter))
+        return r, r["status"]
+
+    def scores(f, r, j0, j1):
+        return dict(L0=r["lb"][j0].copy(), L1=r["lb"][j1].copy(), err0=np.sqrt(r["r2"][j0]), err1=np.sqrt(r["r2"][j1]),
+                    status=(r["status"][j0] | r["status"][j1]).astype(np.int64))
+    return _fold_jobs(fn, models, ids, two_models, call, scores,
+                      lambda k, b: f"vbls! of bag {b} against {'the whole' if k else 'the truncated'} basis met a precision that is not "
+                                   f"finite or a pivot that is not positive and finite, or its bound is not finite", kind=_SCORED_FOLDS)
 
 
 def factorize_folds(models, tests, Ys, niter=20, threshold=1e-1):

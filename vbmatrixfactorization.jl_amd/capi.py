@@ -266,6 +266,28 @@ def _fcol(a, shape=None):
     return np.asfortranarray(a)
 
 
+def _pack_models(models, key, order="C"):
+    """every model's m[key] as fp64, flattened in `order`, one after the other: how the (bag, model) job entries take a per-model input"""
+    if not models:
+        return np.empty(0)
+    return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
+
+
+def _job_blocks(off, nb, jb, jk, Hs, noffs=3):
+    """Where the (bag, model) job entries put job j's outputs.  Hs: the models' ranks, or one int where every model has that rank (the
+    model index then does not bear on a block's size).  Returns (ok, Hj, widths) -- whether the job is in range, its model's rank, its
+    bag's width (0 and 0 for a job out of range: that one is the library's to refuse, no block for it) -- and the first noffs of
+    (boff, soff, hoff), the cumulative offsets (njobs + 1,) of the M_b*H_k-, H_k^2- and H_k-long blocks."""
+    ok = (jb >= 0) & (jb < nb)
+    Hj = Hs
+    if np.ndim(Hs):
+        ok &= (jk >= 0) & (jk < Hs.size)
+        Hj = np.where(ok, Hs[np.clip(jk, 0, max(Hs.size - 1, 0))], 0) if Hs.size >= 1 else np.zeros(jb.size, np.int64)
+    b = np.clip(jb, 0, max(nb - 1, 0))
+    widths = np.where(ok, off[b + 1] - off[b], 0) if nb >= 1 else np.zeros(jb.size, np.int64)
+    return (ok, Hj, widths) + tuple(np.concatenate([[0], np.cumsum(v)]).astype(np.int64) for v in (widths * Hj, Hj * Hj, Hj)[:noffs])
+
+
 def _is_tensor(a):
     """A torch tensor, told by its surface: torch itself is imported only once such an object has been passed."""
     return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
@@ -931,30 +953,22 @@ class Context:
         for m in models:
             if np.shape(m["BHat"]) != (self.L, H) or np.shape(m["SigmaB"]) != (H, H) or np.size(m["alpha"]) != H or np.size(m["beta0"]) != H:
                 raise ValueError(f"every model needs BHat ({self.L}, {H}), SigmaB ({H}, {H}), alpha and beta0 ({H},)")
-
-        def pack(key, order="C"):
-            if not nk:
-                return np.empty(0)
-            return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
-        B, SB, al, b0 = pack("BHat", "F"), pack("SigmaB", "F"), pack("alpha"), pack("beta0")
-        e0, z0, s0, c0 = pack("eta0"), pack("zeta0"), pack("sigma0"), pack("ca0")
+        per_model = [_pack_models(models, "BHat", "F"), _pack_models(models, "SigmaB", "F")] + [_pack_models(models, f) for f in (
+            "alpha", "beta0", "eta0", "zeta0", "sigma0", "ca0")]
         jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
         jk = np.ascontiguousarray(job_model, dtype=np.int64).reshape(-1)
         if jb.size != jk.size:
             raise ValueError(f"{jb.size} job bags but {jk.size} job models")
         nj = jb.size
-        ok = (jb >= 0) & (jb < nb)                                   # (a job out of range is the library's to refuse: no block for it)
-        widths = np.where(ok, off[np.clip(jb, 0, max(nb - 1, 0)) + 1] - off[np.clip(jb, 0, max(nb - 1, 0))], 0) if nb >= 1 else np.zeros(nj, np.int64)
-        boff = np.concatenate([[0], np.cumsum(widths * H)]).astype(np.int64)
+        boff = _job_blocks(off, nb, jb, jk, H, 1)[3]
         n = max(int(boff[-1]), 1)
         r2, sg, zeta = np.empty(nj), np.empty(nj), np.empty(nj)
         A, dS, CA, beta = np.empty(n), np.empty(n), np.empty(n), np.empty(n)
         SA = np.empty((nj, H, H))
         status = np.zeros(nj, dtype=np.int64)
-        self._chk(self._lib.vbmf_sparse_fixed_basis_jobs(self._h, nb, _i64ptr(off), H, int(niter), int(bool(full_cov)), nk, _dptr(B), _dptr(SB),
-                                                         _dptr(al), _dptr(b0), _dptr(e0), _dptr(z0), _dptr(s0), _dptr(c0), nj, _i64ptr(jb),
-                                                         _i64ptr(jk), _dptr(r2), _dptr(A), _dptr(dS), _dptr(CA), _dptr(beta), _dptr(SA),
-                                                         _dptr(sg), _dptr(zeta), _i64ptr(status)))
+        self._chk(self._lib.vbmf_sparse_fixed_basis_jobs(self._h, nb, _i64ptr(off), H, int(niter), int(bool(full_cov)), nk,
+                                                         *[_dptr(v) for v in per_model], nj, _i64ptr(jb), _i64ptr(jk), _dptr(r2), _dptr(A),
+                                                         _dptr(dS), _dptr(CA), _dptr(beta), _dptr(SA), _dptr(sg), _dptr(zeta), _i64ptr(status)))
         return dict(r2=r2, sigmaHat=sg, zeta=zeta, status=status, SigmaA=SA, CA=CA, beta=beta, diagSigmaATVec=dS, ATVecHat=A, off=boff)
 
     def fixed_basis_jobs(self, col_off, models, job_bag, job_model, niter):
@@ -971,23 +985,13 @@ class Context:
             H = int(H)
             if np.shape(m["BHat"]) != (self.L, H) or np.shape(m["SigmaB"]) != (H, H):
                 raise ValueError(f"every model needs BHat ({self.L}, H) and SigmaB (H, H)")
-
-        def pack(key, order="C"):
-            if not nk:
-                return np.empty(0)
-            return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
-        B, SB, s0, c0 = pack("BHat", "F"), pack("SigmaB", "F"), pack("sigma2_0"), pack("ca0")
+        B, SB, s0, c0 = _pack_models(models, "BHat", "F"), _pack_models(models, "SigmaB", "F"), _pack_models(models, "sigma2_0"), _pack_models(models, "ca0")
         jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
         jk = np.ascontiguousarray(job_model, dtype=np.int64).reshape(-1)
         nj = jb.size
         if jk.size != nj:
             raise ValueError(f"{nj} job bags but {jk.size} job models")
-        ok = (jb >= 0) & (jb < nb) & (jk >= 0) & (jk < nk)           # (a job out of range is the library's to refuse: no block for it)
-        Hj = np.where(ok, Hs[np.clip(jk, 0, max(nk - 1, 0))], 0) if nk >= 1 else np.zeros(nj, np.int64)
-        widths = np.where(ok, off[np.clip(jb, 0, max(nb - 1, 0)) + 1] - off[np.clip(jb, 0, max(nb - 1, 0))], 0) if nb >= 1 else np.zeros(nj, np.int64)
-        boff = np.concatenate([[0], np.cumsum(widths * Hj)]).astype(np.int64)
-        soff = np.concatenate([[0], np.cumsum(Hj * Hj)]).astype(np.int64)
-        hoff = np.concatenate([[0], np.cumsum(Hj)]).astype(np.int64)
+        _, Hj, widths, boff, soff, hoff = _job_blocks(off, nb, jb, jk, Hs)
         r2, sg = np.empty(nj), np.empty(nj)
         A, SA, CA = np.empty(max(int(boff[-1]), 1)), np.empty(max(int(soff[-1]), 1)), np.empty(max(int(hoff[-1]), 1))
         status = np.zeros(nj, dtype=np.int64)
@@ -1015,12 +1019,7 @@ class Context:
             if (np.shape(m["BHat"]) != (self.L, H) or np.shape(m["SigmaB"]) != (H, H)
                     or any(np.size(m[f]) != H for f in ("CB", "delta", "a_pri", "b_pri", "a_post"))):
                 raise ValueError(f"every model needs BHat ({self.L}, H), SigmaB (H, H), CB, delta, a_pri, b_pri and a_post (H,)")
-
-        def pack(key, order="C"):
-            if not nk:
-                return np.empty(0)
-            return np.concatenate([np.asarray(m[key], dtype=np.float64).reshape(-1, order=order) for m in models])
-        per_model = [pack("BHat", "F"), pack("SigmaB", "F")] + [pack(f) for f in (
+        per_model = [_pack_models(models, "BHat", "F"), _pack_models(models, "SigmaB", "F")] + [_pack_models(models, f) for f in (
             "CB", "delta", "gamma", "gamma0", "delta0", "a_pri", "b_pri", "a_post", "eta0", "zeta0", "sigma0", "ca0")]
         jb = np.ascontiguousarray(job_bag, dtype=np.int64).reshape(-1)
         jk = np.ascontiguousarray(job_model, dtype=np.int64).reshape(-1)
@@ -1029,11 +1028,7 @@ class Context:
         nj = jb.size
         if not (jk.size == jf.size == jt.size == nj):
             raise ValueError(f"{nj} job bags but {jk.size} job models, {jf.size} forms and {jt.size} trims")
-        ok = (jb >= 0) & (jb < nb) & (jk >= 0) & (jk < nk)           # (a job out of range is the library's to refuse: no block for it)
-        Hj = np.where(ok, Hs[np.clip(jk, 0, max(nk - 1, 0))], 0) if nk >= 1 else np.zeros(nj, np.int64)
-        widths = np.where(ok, off[np.clip(jb, 0, max(nb - 1, 0)) + 1] - off[np.clip(jb, 0, max(nb - 1, 0))], 0) if nb >= 1 else np.zeros(nj, np.int64)
-        boff = np.concatenate([[0], np.cumsum(widths * Hj)]).astype(np.int64)
-        soff = np.concatenate([[0], np.cumsum(Hj * Hj)]).astype(np.int64)
+        _, Hj, _, boff, soff = _job_blocks(off, nb, jb, jk, Hs, 2)
         n = max(int(boff[-1]), 1)
         lb, r2, sg, zeta = np.empty(nj), np.empty(nj), np.empty(nj), np.empty(nj)
         A, dS, CA, beta = np.empty(n), np.empty(n), np.empty(n), np.empty(n)

@@ -4,7 +4,14 @@
 //   bags_check     what every entry refuses about (nbags, col_off) and a sharded context; the widest bag, the residual slices
 //   bags_reserve   ONE device scratch buffer (c->bags), grown on demand.  Every entry synchronises before it returns, so no two layouts
 //                  are live together, and writes every slot before it reads it: it starts on whatever the last entry left there
+// The (bag, model) job entries keep their bookkeeping -- the shared refusals, the sums, the int64 job table, the search for a non-finite
+// input -- in job_tables.hpp, which knows nothing of the context; the parts that do are here:
+//   jobs_refused, jobs_finite, jobs_stage, jobs_run_drained   that header's refusals as this library's errors, the host copies of the one
+//                                                             upload and read-back, the launches with the stream drained on error
+//   lb_of_bag      one bag's or job's bound from the device's sums (vjobs_call, vbmf_sparse_lower_bound_batched)
 #pragma once
+
+#include "job_tables.hpp"
 
 struct BagDims { int64_t widest = 0, nslices = 0; };          // columns of the widest bag; residual workgroups (SCORE_CW columns each)
 
@@ -247,6 +254,64 @@ static int score_launch_resid(vbmf_ctx* c, int64_t nb, const int64_t* col_off, i
     return VBMF_OK;
 }
 
+// ---- what the job entries share on top of job_tables.hpp: the parts that need the context ------------------------------------------
+// a refusal of job_tables.hpp as this library's error text and code
+static int jobs_refused(vbmf_ctx* c, const JobRefusal& r) {
+    FAIL(c, r.kind == JOBS_UNSUPPORTED ? VBMF_ERR_UNSUPPORTED : VBMF_ERR_INVALID, "%s", r.msg);
+}
+
+// refuses a per-model packed input (stride(k) entries of model k) with an entry that is not finite, naming the model and the entry
+template <class Stride>
+static int jobs_finite(vbmf_ctx* c, const char* fn, const char* name, const double* v, int64_t nk, Stride stride, bool with_entry = true) {
+    int64_t k = 0, e = 0;
+    if (!first_nonfinite(v, nk, stride, k, e)) return VBMF_OK;
+    if (!with_entry) FAIL(c, VBMF_ERR_INVALID, "%s: %s of model %lld is not finite", fn, name, (long long)k);
+    FAIL(c, VBMF_ERR_INVALID, "%s: %s of model %lld is not finite (entry %lld)", fn, name, (long long)k, (long long)e);
+}
+
+// the host copies of the one upload and the one read-back; bytes, what: how the refusal words the request
+static int jobs_stage(vbmf_ctx* c, const char* fn, std::vector<double>& up, int64_t n_up, std::vector<double>& res, int64_t n_res,
+                      int64_t bytes, const char* what) {
+    try {
+        up.resize((size_t)n_up);
+        res.resize((size_t)n_res);
+    } catch (const std::bad_alloc&) {
+        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of %s", fn, (long long)bytes, what);
+    }
+    return VBMF_OK;
+}
+
+// run() enqueues from and reads back into the caller's locals: after an error nothing may still be copying when they go
+template <class Run>
+static int jobs_run_drained(vbmf_ctx* c, Run run) {
+    const int rc = run();
+    if (rc != VBMF_OK) hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// The bound of one bag (or job) from what the device summed: sums = SCORE_NS column sums for each of its H columns, quad = its pair,
+// r2 its residual; a_pri, b_pri, a_post its H prior entries.  The caller has filled s.L, s.H, the noise and hyper fields and the basis'
+// sums; this fills the rest and grp[0 .. H).  finite: the bound and every sum it was made of are.
+static double lb_of_bag(LbSums& s, LbGroup* grp, int H, double Mb, double r2, const double* sums, const double* quad, bool trimmed,
+                        bool grouped, const double* a_pri, const double* b_pri, const double* a_post, int clamp, bool& finite) {
+    // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
+    const bool cut = trimmed && !grouped;
+    double n_keep = 0, s_caq = 0, s_logds = 0;
+    for (int h = 0; h < H; ++h) {
+        const double* q = sums + (size_t)h * SCORE_NS;
+        n_keep += q[2]; s_caq += q[5]; s_logds += q[6];
+        grp[h] = LbGroup{cut ? q[2] : Mb, cut ? q[3] : q[0], cut ? q[4] : q[1], a_pri[h], b_pri[h], a_post[h]};
+    }
+    s.M = Mb;
+    s.MH = trimmed ? n_keep : Mb * (double)H;
+    s.quad = r2 + s.L * quad[0] + quad[1];
+    s.s_caq = s_caq; s.s_logds = s_logds;
+    s.g = grp; s.ng = H;
+    const double v = lb_assemble(s, clamp);
+    finite = std::isfinite(v) && std::isfinite(s.quad) && std::isfinite(s_caq) && std::isfinite(s_logds);
+    return v;
+}
+
 extern "C" {
 
 // norm(Y - BHat*AHat')^2 of every bag (examples/mil_util.jl:476-479, :518-521) in one call, entry by entry in fp64
@@ -348,8 +413,8 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
                                 double* r2, int64_t* status) {
     if (!c) return VBMF_ERR_INVALID;
     const char* fn = "vbmf_bag_least_squares_jobs";
-    if (nbasis < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nbasis must be >= 1", fn);
-    if (njobs < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    JobRefusal ref;
+    if (job_counts_check(fn, nbasis, njobs, "nbasis", ref)) return jobs_refused(c, ref);
     if (!Hs || !BHat || !lambda || !job_bag || !job_basis || !status)
         FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only X or r2 may be NULL)", fn);
     if (!X && !r2) FAIL(c, VBMF_ERR_INVALID, "%s: X and r2 are both NULL", fn);
@@ -376,8 +441,7 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
     int64_t nsl = 0, sumX = 0;
     for (int64_t j = 0; j < nj; ++j) {
         const int64_t b = job_bag[j], k = job_basis[j];
-        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
-        if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_basis[%lld] = %lld outside 0..nbasis-1", fn, (long long)j, (long long)k);
+        if (job_range_check(fn, j, b, nb, k, nk, "job_basis", "nbasis", ref)) return jobs_refused(c, ref);
         const int64_t Mb = col_off[b + 1] - col_off[b];
         nsl += (Mb + SCORE_CW - 1) / SCORE_CW;                    // (at most 2^24 terms of at most 2^60 / 8: no overflow)
         sumX += Hs[k] * Mb;
@@ -388,13 +452,8 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
     //                         | lambda nk | the bases row-major [L][H_k], one after the other]
     const int64_t u_sl = nb + 1, u_bag = u_sl + nj + 1, u_bas = u_bag + nj, u_xo = u_bas + nj, u_hs = u_xo + nj, u_bo = u_hs + nk,
                   u_ko = u_bo + nk, u_lam = u_ko + nk, u_b = u_lam + nk, n_up = u_b + L * sumH;
-    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
-    try {
-        up.resize((size_t)n_up);
-        res.resize((size_t)(nj + nk));                            // r2 | the flags
-    } catch (const std::bad_alloc&) {
-        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of bases and job tables", fn, (long long)(n_up * 8));
-    }
+    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream); res: r2 | the flags
+    TRY(jobs_stage(c, fn, up, n_up, res, nj + nk, n_up * 8, "bases and job tables"));
     long long* ui = reinterpret_cast<long long*>(up.data());
     for (int64_t j = 0, sl = 0, xo = 0; j < nj; ++j) {
         const int64_t b = job_bag[j], k = job_basis[j], Mb = col_off[b + 1] - col_off[b];
@@ -425,7 +484,7 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
         ko += H * H;
     }
     if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
-    auto run = [&]() -> int {
+    TRY(jobs_run_drained(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->o.device));
         // c->bags: [the upload | r2 nj | bad-pivot flags nk (an int in each slot) | partials nsl | Gram partials nchunk sum H_k^2
         //           | K sum H_k^2 | X sum H_k M_b (job j's block at x_off[j])]
@@ -460,12 +519,7 @@ int vbmf_bag_least_squares_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_o
         if (X) HIPCHK(c, hipMemcpyAsync(X, d + o_x, (size_t)sumX * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
         return VBMF_OK;
-    };
-    const int rc = run();
-    if (rc != VBMF_OK) {
-        hipStreamSynchronize(c->stream);
-        return rc;
-    }
+    }));
     // (the outputs are written whatever the scan below finds: X came back with the one read-back)
     for (int64_t k = 0; k < nk; ++k) {
         int bad = 0;
@@ -505,99 +559,63 @@ struct VjobsCall {
 static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
     const char* fn = a.fn;
     const int64_t nk = a.nmodels, nj = a.njobs, nb = a.nbags, L = c->L;
-    if (nk < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nmodels must be >= 1", fn);
-    if (nj < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    const JobShape js{nb, a.col_off, nk, a.model_H, a.H_all, nj, a.job_bag, a.job_model};
+    JobRefusal ref;
+    if (job_counts_check(fn, nk, nj, "nmodels", ref)) return jobs_refused(c, ref);
     if (a.niter < 1 || a.niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
     if (!a.BHat || !a.SigmaB || !a.b_pri || !a.a_post || !a.eta0 || !a.zeta0 || !a.sigma0 || !a.ca0 || !a.job_bag || !a.job_model || !a.status)
         FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
     if (a.scored && (!a.model_H || !a.CB || !a.delta || !a.gamma || !a.gamma0 || !a.delta0 || !a.a_pri || !a.job_full_cov || !a.job_trim))
         FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
     if (!a.lb && !a.r2 && !a.ATVecHat) FAIL(c, VBMF_ERR_INVALID, "%s: %sr2 and ATVecHat are both NULL", fn, a.scored ? "lb, " : "");
-    // what one grid holds: a launch is kept to 2^32 - 1 threads in all, so to LS_MAX_GROUPS workgroups of 256
-    if (nj > LS_MAX_GROUPS || nk > LS_MAX_GROUPS)
-        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs, %lld models (more than the %lld workgroups of one grid)", fn, (long long)nj,
-             (long long)nk, (long long)LS_MAX_GROUPS);
+    if (job_grid_check(fn, nk, nj, LS_MAX_GROUPS, ref)) return jobs_refused(c, ref);
     if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set", fn);
     BagDims bd;
     TRY(bags_check(c, fn, nb, a.col_off, bd));
     const bool compat = (c->o.reference_compat & VBMF_COMPAT_SPARSE_REPEAT) != 0;
-    auto Hof = [&](int64_t k) { return a.model_H ? a.model_H[k] : a.H_all; };
-    int64_t sumH = 0, sumH2 = 0;
-    for (int64_t k = 0; k < nk; ++k) {
-        const int64_t H = Hof(k);
-        if (H < 1 || H > VJOBS_MAX_H)
-            FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: model_H[%lld] = %lld (built for 1 <= H <= %d)", fn, (long long)k, (long long)H, VJOBS_MAX_H);
-        sumH += H;
-        sumH2 += H * H;
-    }
     // the jobs' groups (tier of H_k, form): NBK - 1 + 2 * full; per group the widest state kept in LDS (doubles)
-    int64_t SMH = 0, SJH = 0, SJH2 = 0, grp_n[4] = {0, 0, 0, 0}, grp_lds[4] = {0, 0, 0, 0};
+    auto full_of = [&](int64_t j) { return (a.job_full_cov ? a.job_full_cov[j] : (int64_t)a.full_all) != 0; };
+    auto group_of = [&](int64_t j) { return nb_tier(js.H(a.job_model[j])) - 1 + (full_of(j) ? 2 : 0); };
+    int64_t grp_lds[4] = {0, 0, 0, 0};
     bool spill = false;
-    for (int64_t j = 0; j < nj; ++j) {
-        const int64_t b = a.job_bag[j], k = a.job_model[j];
-        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
-        if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_model[%lld] = %lld outside 0..nmodels-1", fn, (long long)j, (long long)k);
-        const int64_t fc = a.job_full_cov ? a.job_full_cov[j] : (int64_t)a.full_all;
-        if (a.job_full_cov && fc != 0 && fc != 1)
-            FAIL(c, VBMF_ERR_INVALID, "%s: job_full_cov[%lld] = %lld (0 or 1)", fn, (long long)j, (long long)fc);
-        const bool full = fc != 0;
-        const int64_t Mb = a.col_off[b + 1] - a.col_off[b], H = Hof(k);
-        if (!full && compat && Mb < 2)
-            FAIL(c, VBMF_ERR_INVALID, "%s: job %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2", fn, (long long)j);
-        if (a.scored && !std::isfinite(a.job_trim[j])) FAIL(c, VBMF_ERR_INVALID, "%s: job_trim[%lld] is not finite", fn, (long long)j);
-        SMH += Mb * H;                                            // (at most 2^24 terms of at most 2^60 / 8: no overflow)
-        SJH += H;
-        SJH2 += H * H;
-        const int NBK = nb_tier(H), gi = NBK - 1 + (full ? 2 : 0);
-        ++grp_n[gi];
-        if (vjobs_in_lds(full, NBK, (int)H, Mb)) grp_lds[gi] = std::max(grp_lds[gi], 4 * Mb * H);
-        else spill = true;
-    }
-    auto finite = [](const double* v, int64_t n) {
-        for (int64_t i = 0; i < n; ++i)
-            if (!std::isfinite(v[i])) return i;
-        return (int64_t)-1;
-    };
+    JobSums t;
+    if (job_walk(fn, js, VJOBS_MAX_H, t, ref, [&](int64_t j, int64_t, int64_t, int64_t Mb, int64_t H, JobRefusal& r) {
+            if (a.job_full_cov && a.job_full_cov[j] != 0 && a.job_full_cov[j] != 1)
+                return r.set(JOBS_INVALID, "%s: job_full_cov[%lld] = %lld (0 or 1)", fn, (long long)j, (long long)a.job_full_cov[j]);
+            const bool full = full_of(j);
+            if (!full && compat && Mb < 2)
+                return r.set(JOBS_INVALID, "%s: job %lld works on a 1-column bag: the diagonal form under VBMF_COMPAT_SPARSE_REPEAT needs M >= 2",
+                             fn, (long long)j);
+            if (a.scored && !std::isfinite(a.job_trim[j])) return r.set(JOBS_INVALID, "%s: job_trim[%lld] is not finite", fn, (long long)j);
+            const int gi = group_of(j);
+            if (vjobs_in_lds(full, nb_tier(H), (int)H, Mb)) grp_lds[gi] = std::max(grp_lds[gi], 4 * Mb * H);
+            else spill = true;
+            return (int)JOBS_OK;
+        }))
+        return jobs_refused(c, ref);
+    const int64_t sumH = t.sumH, sumH2 = t.sumH2, SMH = t.SMH, SJH = t.SJH, SJH2 = t.SJH2;
     {
-        int64_t bad = finite(a.BHat, L * sumH);
-        if (bad >= 0) {                                          // (the model by its offset)
-            int64_t k = 0, off = 0;
-            while (k + 1 < nk && off + L * Hof(k) <= bad) off += L * Hof(k++);
-            FAIL(c, VBMF_ERR_INVALID, "%s: BHat of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
-        }
-        bad = finite(a.SigmaB, sumH2);
-        if (bad >= 0) {
-            int64_t k = 0, off = 0;
-            while (k + 1 < nk && off + Hof(k) * Hof(k) <= bad) off += Hof(k) * Hof(k), ++k;
-            FAIL(c, VBMF_ERR_INVALID, "%s: SigmaB of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
-        }
+        auto per_col = [&](int64_t k) { return js.H(k); };
+        auto per_model = [](int64_t) { return (int64_t)1; };
+        TRY(jobs_finite(c, fn, "BHat", a.BHat, nk, [&](int64_t k) { return L * js.H(k); }));
+        TRY(jobs_finite(c, fn, "SigmaB", a.SigmaB, nk, [&](int64_t k) { return js.H(k) * js.H(k); }));
         const struct { const char* name; const double* v; bool per_col; } ins[] = {
             {a.scored ? "a_post" : "alpha", a.a_post, true}, {a.scored ? "b_pri" : "beta0", a.b_pri, true}, {"eta0", a.eta0, false},
             {"zeta0", a.zeta0, false}, {"sigma0", a.sigma0, false}, {"ca0", a.ca0, false}, {"a_pri", a.a_pri, true}, {"CB", a.CB, true},
             {"delta", a.delta, true}, {"gamma", a.gamma, false}, {"gamma0", a.gamma0, false}, {"delta0", a.delta0, false}};
         for (const auto& in : ins) {
             if (!in.v) continue;                                 // (a call without the bound)
-            bad = finite(in.v, in.per_col ? sumH : nk);
-            if (bad < 0) continue;
-            int64_t k = bad, e = 0;
-            if (in.per_col) {
-                int64_t off = 0;
-                k = 0;
-                while (k + 1 < nk && off + Hof(k) <= bad) off += Hof(k++);
-                e = bad - off;
-            }
-            FAIL(c, VBMF_ERR_INVALID, "%s: %s of model %lld is not finite (entry %lld)", fn, in.name, (long long)k, (long long)e);
+            TRY(in.per_col ? jobs_finite(c, fn, in.name, in.v, nk, per_col) : jobs_finite(c, fn, in.name, in.v, nk, per_model));
         }
     }
     if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
     const int64_t nsc = a.scored ? 1 : 0;
-    // the upload, one block: [col_off nb + 1 | job_bag | job_model | job_off | job_sa | job_h | idx (nj each) | model_H | b_off | k_off |
-    //                         h_off (nk each) (int64) | trim nj | a_post | b_pri | CB | delta (sum H each) | eta0 | zeta0 | sigma0 | ca0
-    //                         (nk each) | the bases, column-major L x H_k | SigmaB (H_k^2 each)]; trim, CB, delta: a scored call's only
-    const int64_t u_bag = nb + 1, u_mod = u_bag + nj, u_off = u_mod + nj, u_jsa = u_off + nj, u_jh = u_jsa + nj, u_idx = u_jh + nj,
-                  u_mh = u_idx + nj, u_bo = u_mh + nk, u_ko = u_bo + nk, u_ho = u_ko + nk, u_trim = u_ho + nk, u_al = u_trim + nsc * nj,
-                  u_b0 = u_al + sumH, u_cb = u_b0 + sumH, u_de = u_cb + nsc * sumH, u_eta = u_de + nsc * sumH, u_z0 = u_eta + nk,
-                  u_sig = u_z0 + nk, u_ca0 = u_sig + nk, u_b = u_ca0 + nk, u_sb = u_b + L * sumH, n_up = u_sb + sumH2;
+    // the upload, one block: [the job table (job_tables.hpp) | trim nj | a_post | b_pri | CB | delta (sum H each) | eta0 | zeta0 | sigma0 |
+    //                         ca0 (nk each) | the bases, column-major L x H_k | SigmaB (H_k^2 each)]; trim, CB, delta: a scored call's only
+    const JobTable u(nb, nk, nj);
+    const int64_t u_trim = u.words, u_al = u_trim + nsc * nj, u_b0 = u_al + sumH, u_cb = u_b0 + sumH, u_de = u_cb + nsc * sumH,
+                  u_eta = u_de + nsc * sumH, u_z0 = u_eta + nk, u_sig = u_z0 + nk, u_ca0 = u_sig + nk, u_b = u_ca0 + nk, u_sb = u_b + L * sumH,
+                  n_up = u_sb + sumH2;
     // behind it: [Bt L sum H | G sum H^2 | gd | sd (sum H) | r2 | sigma | zeta | status (nj each) | quad 2 nj | the bases' sums VJOBS_NB nk
     //             | SigmaA (the jobs' H_k^2) | the bound's column sums (SCORE_NS per job and column) | CA | A | dS | beta (the jobs'
     //             M_b H_k-long blocks in job order) | P of the jobs whose state is not in LDS]; [r2 .. beta] is the read-back
@@ -605,32 +623,10 @@ static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
                   o_zeta = o_sig + nj, o_st = o_zeta + nj, o_quad = o_st + nj, o_nb = o_quad + nsc * 2 * nj, o_sa = o_nb + nsc * VJOBS_NB * nk,
                   o_sums = o_sa + SJH2, o_ca = o_sums + nsc * SCORE_NS * SJH, o_a = o_ca + SMH, o_ds = o_a + SMH, o_be = o_ds + SMH,
                   o_p = o_be + SMH, total = o_p + (spill ? SMH : 0);
-    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
-    try {
-        up.resize((size_t)n_up);
-        res.resize((size_t)(o_p - o_r2));
-    } catch (const std::bad_alloc&) {
-        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of models, job tables and results", fn, (long long)((n_up + o_p - o_r2) * 8));
-    }
-    long long* ui = reinterpret_cast<long long*>(up.data());
-    for (int64_t b = 0; b <= nb; ++b) ui[b] = a.col_off[b];
-    for (int64_t k = 0, bo = 0, ko = 0, ho = 0; k < nk; ++k) {
-        const int64_t H = Hof(k);
-        ui[u_mh + k] = H; ui[u_bo + k] = bo; ui[u_ko + k] = ko; ui[u_ho + k] = ho;
-        bo += L * H; ko += H * H; ho += H;
-    }
-    int64_t grp_at[4];                                            // the groups' first slots of idx
-    for (int gi = 0, at = 0; gi < 4; ++gi) { grp_at[gi] = at; at += grp_n[gi]; }
-    {
-        int64_t fill[4] = {grp_at[0], grp_at[1], grp_at[2], grp_at[3]};
-        for (int64_t j = 0, off = 0, sa = 0, jh = 0; j < nj; ++j) {
-            const int64_t b = a.job_bag[j], k = a.job_model[j], H = Hof(k);
-            const bool full = (a.job_full_cov ? a.job_full_cov[j] : (int64_t)a.full_all) != 0;
-            ui[u_bag + j] = b; ui[u_mod + j] = k; ui[u_off + j] = off; ui[u_jsa + j] = sa; ui[u_jh + j] = jh;
-            ui[u_idx + fill[nb_tier(H) - 1 + (full ? 2 : 0)]++] = j;
-            off += (a.col_off[b + 1] - a.col_off[b]) * H; sa += H * H; jh += H;
-        }
-    }
+    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream)
+    TRY(jobs_stage(c, fn, up, n_up, res, o_p - o_r2, (n_up + o_p - o_r2) * 8, "models, job tables and results"));
+    int64_t grp_n[4], grp_at[4];                                  // the groups' sizes and first slots of idx
+    job_table_fill(reinterpret_cast<long long*>(up.data()), js, L, 4, group_of, grp_n, grp_at);
     if (a.scored) {
         memcpy(up.data() + u_trim, a.job_trim, (size_t)nj * 8);
         memcpy(up.data() + u_cb, a.CB, (size_t)sumH * 8);
@@ -644,18 +640,18 @@ static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
     memcpy(up.data() + u_ca0, a.ca0, (size_t)nk * 8);
     memcpy(up.data() + u_b, a.BHat, (size_t)(L * sumH) * 8);
     memcpy(up.data() + u_sb, a.SigmaB, (size_t)sumH2 * 8);
-    auto run = [&]() -> int {
+    TRY(jobs_run_drained(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->o.device));
         double* d = nullptr;
         TRY(bags_reserve(c, total, &d));
         HIPCHK(c, hipMemcpyAsync(d, up.data(), (size_t)n_up * 8, hipMemcpyHostToDevice, c->stream));
         const long long* di = reinterpret_cast<const long long*>(d);
-        const VjobsModels ms{di + u_mh, di + u_bo, di + u_ko, di + u_ho};
+        const VjobsModels ms{di + u.mh, di + u.bo, di + u.ko, di + u.ho};
         hipLaunchKernelGGL(vbls_jobs_model_kernel, dim3((unsigned)nk), dim3(SCORE_THREADS), 0, c->stream, ms, d + u_b, d + u_sb, (long long)L,
                            d + o_bt, d + o_g, d + o_gd, d + o_sd, a.scored ? d + u_cb : nullptr, a.scored ? d + u_de : nullptr,
                            a.scored ? d + o_nb : nullptr);
         HIPCHK(c, hipGetLastError());
-        VjobsArgs g{c->Y2, c->d2.KS, (long long)L, di, di + u_bag, di + u_mod, di + u_off, di + u_jsa, di + u_jh, nullptr, ms,
+        VjobsArgs g{c->Y2, c->d2.KS, (long long)L, di, di + u.bag, di + u.mod, di + u.off, di + u.jsa, di + u.jh, nullptr, ms,
                     (int)a.niter, compat ? 1 : 0,
                     d + o_bt, d + o_g, d + u_sb, d + o_gd, d + o_sd, d + u_al, d + u_b0, d + u_eta, d + u_z0, d + u_sig, d + u_ca0,
                     spill ? d + o_p : nullptr, d + o_ca, d + o_a, d + o_ds, d + o_be, d + o_sa, d + o_sig, d + o_zeta, d + o_r2,
@@ -665,7 +661,7 @@ static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
             if (!grp_n[gi]) continue;
             const int NBK = (gi & 1) + 1;
             const bool full = gi >= 2;
-            g.idx = di + u_idx + grp_at[gi];
+            g.idx = di + u.idx + grp_at[gi];
             // (the fixed part does not depend on H up to VJOBS_MAX_H within a tier: H^2 <= VJOBS_STAGE)
             const size_t lds = (size_t)(vjobs_fixed_doubles(full, NBK, 16 * NBK) + grp_lds[gi]) * 8;
             dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
@@ -680,48 +676,30 @@ static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
         }
         HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
         return VBMF_OK;
-    };
-    const int rc = run();
-    if (rc != VBMF_OK) {
-        hipStreamSynchronize(c->stream);
-        return rc;
-    }
+    }));
     auto at = [&](int64_t o_x) { return res.data() + (o_x - o_r2); };   // block x of the read-back
     int64_t* st = reinterpret_cast<int64_t*>(at(o_st));
     if (a.lb) {
-        // the bound of every job from its sums (lb_assemble); a job whose bound or sums are not finite fails like one the device flagged
+        // the bound of every job from its sums (lb_of_bag); a job whose bound or sums are not finite fails like one the device flagged
         const double nan = std::nan("");
-        std::vector<int64_t> h_off((size_t)nk);
-        for (int64_t k = 0, ho = 0; k < nk; ho += Hof(k), ++k) h_off[(size_t)k] = ho;
+        const long long* ui = reinterpret_cast<const long long*>(up.data());
         LbGroup grp[VJOBS_MAX_H];
-        for (int64_t j = 0, off = 0, sa = 0, jh = 0; j < nj; ++j) {
-            const int64_t b = a.job_bag[j], k = a.job_model[j], H = Hof(k), ho = h_off[(size_t)k];
-            const double Mb = (double)(a.col_off[b + 1] - a.col_off[b]);
-            const int64_t n = (a.col_off[b + 1] - a.col_off[b]) * H;
+        for (int64_t j = 0; j < nj; ++j) {
+            const int64_t b = a.job_bag[j], k = a.job_model[j], H = js.H(k), ho = ui[u.ho + k], off = ui[u.off + j], sa = ui[u.jsa + j];
+            const double Mb = (double)js.width(b);
+            const int64_t n = js.width(b) * H;
             double v = nan;
             if (st[j] == 0) {
-                const bool trimmed = a.job_trim[j] >= 0.0, cut = trimmed && !a.grouped;
-                const double* sb = at(o_sums) + (size_t)jh * SCORE_NS;
-                const double* quad = at(o_quad) + 2 * j;
                 const double* mb = at(o_nb) + VJOBS_NB * k;
-                double n_keep = 0, s_caq = 0, s_logds = 0;
-                for (int64_t h = 0; h < H; ++h) {
-                    const double* q = sb + (size_t)h * SCORE_NS;
-                    n_keep += q[2]; s_caq += q[5]; s_logds += q[6];
-                    // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
-                    grp[h] = LbGroup{cut ? q[2] : Mb, cut ? q[3] : q[0], cut ? q[4] : q[1], a.a_pri[ho + h], a.b_pri[ho + h], a.a_post[ho + h]};
-                }
                 LbSums s{};
-                s.L = (double)L; s.H = (double)H; s.M = Mb;
-                s.MH = trimmed ? n_keep : Mb * (double)H;
+                s.L = (double)L; s.H = (double)H;
                 s.sig = at(o_sig)[j]; s.zeta = at(o_zeta)[j]; s.eta = a.eta0[k] + 0.5 * (double)L * Mb;
                 s.hyp.gamma0 = a.gamma0[k]; s.hyp.delta0 = a.delta0[k]; s.hyp.eta0 = a.eta0[k]; s.hyp.zeta0 = a.zeta0[k];
-                s.quad = at(o_r2)[j] + s.L * quad[0] + quad[1];
-                s.s_caq = s_caq; s.s_logds = s_logds;
                 s.cbq = mb[0]; s.sumcb = mb[1]; s.sumlogdelta = mb[2]; s.logdet_sb = mb[3]; s.gamma_ = a.gamma[k];
-                s.g = grp; s.ng = (int)H;
-                v = lb_assemble(s, a.clamp);
-                if (!std::isfinite(v) || !std::isfinite(s.quad) || !std::isfinite(s_caq) || !std::isfinite(s_logds)) {
+                bool finite = false;
+                v = lb_of_bag(s, grp, (int)H, Mb, at(o_r2)[j], at(o_sums) + (size_t)ui[u.jh + j] * SCORE_NS, at(o_quad) + 2 * j,
+                              a.job_trim[j] >= 0.0, a.grouped != 0, a.a_pri + ho, a.b_pri + ho, a.a_post + ho, a.clamp, finite);
+                if (!finite) {
                     v = nan;
                     st[j] = 1;
                     at(o_r2)[j] = at(o_sig)[j] = at(o_zeta)[j] = nan;
@@ -730,7 +708,6 @@ static int vjobs_call(vbmf_ctx* c, const VjobsCall& a) {
                 }
             }
             a.lb[j] = v;
-            off += n; sa += H * H; jh += H;
         }
     }
     if (a.r2) memcpy(a.r2, at(o_r2), (size_t)nj * 8);
@@ -810,121 +787,69 @@ int vbmf_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, in
     if (!c) return VBMF_ERR_INVALID;
     const char* fn = "vbmf_fixed_basis_jobs";
     const int64_t nk = nmodels, nj = njobs, nb = nbags, L = c->L;
-    if (nk < 1) FAIL(c, VBMF_ERR_INVALID, "%s: nmodels must be >= 1", fn);
-    if (nj < 1) FAIL(c, VBMF_ERR_INVALID, "%s: njobs must be >= 1", fn);
+    const JobShape js{nb, col_off, nk, model_H, 0, nj, job_bag, job_model};
+    JobRefusal ref;
+    if (job_counts_check(fn, nk, nj, "nmodels", ref)) return jobs_refused(c, ref);
     if (niter < 1 || niter > (1ll << 30)) FAIL(c, VBMF_ERR_INVALID, "%s: niter must be >= 1", fn);
     if (!model_H || !BHat || !SigmaB || !sigma2_0 || !ca0 || !job_bag || !job_model || !status)
         FAIL(c, VBMF_ERR_INVALID, "%s: null pointer (only the outputs but status may be NULL)", fn);
     if (!r2 && !AHat) FAIL(c, VBMF_ERR_INVALID, "%s: r2 and AHat are both NULL", fn);
-    if (nj > LS_MAX_GROUPS || nk > LS_MAX_GROUPS)
-        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: %lld jobs, %lld models (more than the %lld workgroups of one grid)", fn, (long long)nj,
-             (long long)nk, (long long)LS_MAX_GROUPS);
+    if (job_grid_check(fn, nk, nj, LS_MAX_GROUPS, ref)) return jobs_refused(c, ref);
     if (c->has_mask) FAIL(c, VBMF_ERR_INVALID, "%s: a label mask is set", fn);
     BagDims bd;
     TRY(bags_check(c, fn, nb, col_off, bd));
-    int64_t sumH = 0, sumH2 = 0;
-    for (int64_t k = 0; k < nk; ++k) {
-        const int64_t H = model_H[k];
-        if (H < 1 || H > VJOBS_MAX_H)
-            FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: model_H[%lld] = %lld (built for 1 <= H <= %d)", fn, (long long)k, (long long)H, VJOBS_MAX_H);
-        sumH += H;
-        sumH2 += H * H;
-    }
     // the jobs' tiers of H_k; per tier the widest P kept in LDS (doubles)
-    int64_t SMH = 0, SJH = 0, SJH2 = 0, grp_n[2] = {0, 0}, grp_lds[2] = {0, 0};
+    auto group_of = [&](int64_t j) { return nb_tier(model_H[job_model[j]]) - 1; };
+    int64_t grp_lds[2] = {0, 0};
     bool spill = false;
-    for (int64_t j = 0; j < nj; ++j) {
-        const int64_t b = job_bag[j], k = job_model[j];
-        if (b < 0 || b >= nb) FAIL(c, VBMF_ERR_INVALID, "%s: job_bag[%lld] = %lld outside 0..nbags-1", fn, (long long)j, (long long)b);
-        if (k < 0 || k >= nk) FAIL(c, VBMF_ERR_INVALID, "%s: job_model[%lld] = %lld outside 0..nmodels-1", fn, (long long)j, (long long)k);
-        const int64_t Mb = col_off[b + 1] - col_off[b], H = model_H[k];
-        SMH += Mb * H;                                            // (at most 2^24 terms of at most 2^60 / 32: no overflow)
-        SJH += H;
-        SJH2 += H * H;
-        const int gi = nb_tier(H) - 1;
-        ++grp_n[gi];
-        if (fjobs_in_lds(gi + 1, (int)H, Mb)) grp_lds[gi] = std::max(grp_lds[gi], Mb * H);
-        else spill = true;
-    }
-    {
-        auto finite = [](const double* v, int64_t n) {
-            for (int64_t i = 0; i < n; ++i)
-                if (!std::isfinite(v[i])) return i;
-            return (int64_t)-1;
-        };
-        int64_t bad = finite(BHat, L * sumH);
-        if (bad >= 0) {                                          // (the model by its offset)
-            int64_t k = 0, off = 0;
-            while (k + 1 < nk && off + L * model_H[k] <= bad) off += L * model_H[k++];
-            FAIL(c, VBMF_ERR_INVALID, "%s: BHat of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
-        }
-        bad = finite(SigmaB, sumH2);
-        if (bad >= 0) {
-            int64_t k = 0, off = 0;
-            while (k + 1 < nk && off + model_H[k] * model_H[k] <= bad) off += model_H[k] * model_H[k], ++k;
-            FAIL(c, VBMF_ERR_INVALID, "%s: SigmaB of model %lld is not finite (entry %lld)", fn, (long long)k, (long long)(bad - off));
-        }
-        bad = finite(sigma2_0, nk);
-        if (bad >= 0) FAIL(c, VBMF_ERR_INVALID, "%s: sigma2_0 of model %lld is not finite", fn, (long long)bad);
-        bad = finite(ca0, nk);
-        if (bad >= 0) FAIL(c, VBMF_ERR_INVALID, "%s: ca0 of model %lld is not finite", fn, (long long)bad);
-    }
+    JobSums t;
+    if (job_walk(fn, js, VJOBS_MAX_H, t, ref, [&](int64_t, int64_t, int64_t, int64_t Mb, int64_t H, JobRefusal&) {
+            const int gi = nb_tier(H) - 1;
+            if (fjobs_in_lds(gi + 1, (int)H, Mb)) grp_lds[gi] = std::max(grp_lds[gi], Mb * H);
+            else spill = true;
+            return (int)JOBS_OK;
+        }))
+        return jobs_refused(c, ref);
+    const int64_t sumH = t.sumH, sumH2 = t.sumH2, SMH = t.SMH, SJH = t.SJH, SJH2 = t.SJH2;
+    auto per_model = [](int64_t) { return (int64_t)1; };
+    TRY(jobs_finite(c, fn, "BHat", BHat, nk, [&](int64_t k) { return L * model_H[k]; }));
+    TRY(jobs_finite(c, fn, "SigmaB", SigmaB, nk, [&](int64_t k) { return model_H[k] * model_H[k]; }));
+    TRY(jobs_finite(c, fn, "sigma2_0", sigma2_0, nk, per_model, false));
+    TRY(jobs_finite(c, fn, "ca0", ca0, nk, per_model, false));
     if (!c->cache.have_Y()) FAIL(c, VBMF_ERR_INVALID, "%s: no Y: call vbmf_set_Y first", fn);     // (no state needed: the bases are arguments)
-    // the upload, one block: [col_off nb + 1 | job_bag | job_model | job_off | job_sa | job_h | idx (nj each) | model_H | b_off | k_off |
-    //                         h_off (nk each) (int64) | sigma2_0 | ca0 (nk each) | the bases, column-major L x H_k | SigmaB (H_k^2 each)]
-    const int64_t u_bag = nb + 1, u_mod = u_bag + nj, u_off = u_mod + nj, u_jsa = u_off + nj, u_jh = u_jsa + nj, u_idx = u_jh + nj,
-                  u_mh = u_idx + nj, u_bo = u_mh + nk, u_ko = u_bo + nk, u_ho = u_ko + nk, u_sig = u_ho + nk, u_ca0 = u_sig + nk,
-                  u_b = u_ca0 + nk, u_sb = u_b + L * sumH, n_up = u_sb + sumH2;
+    // the upload, one block: [the job table (job_tables.hpp) | sigma2_0 | ca0 (nk each) | the bases, column-major L x H_k | SigmaB (H_k^2 each)]
+    const JobTable u(nb, nk, nj);
+    const int64_t u_sig = u.words, u_ca0 = u_sig + nk, u_b = u_ca0 + nk, u_sb = u_b + L * sumH, n_up = u_sb + sumH2;
     // behind it: [Bt L sum H | G sum H^2 | gd | sd (sum H) | r2 | sigma2 | status (nj each) | SigmaA (the jobs' H_k^2) | CA (the jobs' H_k)
     //             | A (the jobs' M_b x H_k blocks in job order) | T (the jobs' H_k^2) | P of the jobs that do not keep it in LDS];
     //             [r2 .. A] is the read-back
     const int64_t o_bt = n_up, o_g = o_bt + L * sumH, o_gd = o_g + sumH2, o_sd = o_gd + sumH, o_r2 = o_sd + sumH, o_sig = o_r2 + nj,
                   o_st = o_sig + nj, o_sa = o_st + nj, o_ca = o_sa + SJH2, o_a = o_ca + SJH, o_t = o_a + SMH, o_p = o_t + SJH2,
                   total = o_p + (spill ? SMH : 0);
-    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream below)
-    try {
-        up.resize((size_t)n_up);
-        res.resize((size_t)(o_t - o_r2));
-    } catch (const std::bad_alloc&) {
-        FAIL(c, VBMF_ERR_UNSUPPORTED, "%s: no host memory to stage %lld bytes of models, job tables and results", fn, (long long)((n_up + o_t - o_r2) * 8));
-    }
-    long long* ui = reinterpret_cast<long long*>(up.data());
-    for (int64_t b = 0; b <= nb; ++b) ui[b] = col_off[b];
-    for (int64_t k = 0, bo = 0, ko = 0, ho = 0; k < nk; ++k) {
-        const int64_t H = model_H[k];
-        ui[u_mh + k] = H; ui[u_bo + k] = bo; ui[u_ko + k] = ko; ui[u_ho + k] = ho;
-        bo += L * H; ko += H * H; ho += H;
-    }
-    const int64_t grp_at[2] = {0, grp_n[0]};                      // the tiers' first slots of idx
-    {
-        int64_t fill[2] = {grp_at[0], grp_at[1]};
-        for (int64_t j = 0, off = 0, sa = 0, jh = 0; j < nj; ++j) {
-            const int64_t b = job_bag[j], k = job_model[j], H = model_H[k];
-            ui[u_bag + j] = b; ui[u_mod + j] = k; ui[u_off + j] = off; ui[u_jsa + j] = sa; ui[u_jh + j] = jh;
-            ui[u_idx + fill[nb_tier(H) - 1]++] = j;
-            off += (col_off[b + 1] - col_off[b]) * H; sa += H * H; jh += H;
-        }
-    }
+    std::vector<double> up, res;                                  // (up outlives the copy: an error after it drains the stream)
+    TRY(jobs_stage(c, fn, up, n_up, res, o_t - o_r2, (n_up + o_t - o_r2) * 8, "models, job tables and results"));
+    int64_t grp_n[2], grp_at[2];                                  // the tiers' sizes and first slots of idx
+    job_table_fill(reinterpret_cast<long long*>(up.data()), js, L, 2, group_of, grp_n, grp_at);
     memcpy(up.data() + u_sig, sigma2_0, (size_t)nk * 8);
     memcpy(up.data() + u_ca0, ca0, (size_t)nk * 8);
     memcpy(up.data() + u_b, BHat, (size_t)(L * sumH) * 8);
     memcpy(up.data() + u_sb, SigmaB, (size_t)sumH2 * 8);
-    auto run = [&]() -> int {
+    TRY(jobs_run_drained(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->o.device));
         double* d = nullptr;
         TRY(bags_reserve(c, total, &d));
         HIPCHK(c, hipMemcpyAsync(d, up.data(), (size_t)n_up * 8, hipMemcpyHostToDevice, c->stream));
         const long long* di = reinterpret_cast<const long long*>(d);
-        const VjobsModels ms{di + u_mh, di + u_bo, di + u_ko, di + u_ho};
+        const VjobsModels ms{di + u.mh, di + u.bo, di + u.ko, di + u.ho};
         hipLaunchKernelGGL(vbls_jobs_model_kernel, dim3((unsigned)nk), dim3(SCORE_THREADS), 0, c->stream, ms, d + u_b, d + u_sb, (long long)L,
                            d + o_bt, d + o_g, d + o_gd, d + o_sd, (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
         HIPCHK(c, hipGetLastError());
-        FjobsArgs g{c->Y2, c->d2.KS, (long long)L, di, di + u_bag, di + u_mod, di + u_off, di + u_jsa, di + u_jh, nullptr, ms, (int)niter,
+        FjobsArgs g{c->Y2, c->d2.KS, (long long)L, di, di + u.bag, di + u.mod, di + u.off, di + u.jsa, di + u.jh, nullptr, ms, (int)niter,
                     d + o_bt, d + o_g, d + u_sig, d + u_ca0, spill ? d + o_p : nullptr, d + o_a, d + o_sa, d + o_t, d + o_ca, d + o_sig,
                     d + o_r2, reinterpret_cast<long long*>(d + o_st)};
         for (int gi = 0; gi < 2; ++gi) {
             if (!grp_n[gi]) continue;
-            g.idx = di + u_idx + grp_at[gi];
+            g.idx = di + u.idx + grp_at[gi];
             const size_t lds = (size_t)(fjobs_fixed_doubles(gi + 1) + grp_lds[gi]) * 8;
             dispatch<MODE_F32, MODE_BF16>(ymode_of(c->mode), [&](auto ym) {
                 dispatch<1, 2>(gi + 1, [&](auto nbk) {
@@ -936,12 +861,7 @@ int vbmf_fixed_basis_jobs(vbmf_ctx* c, int64_t nbags, const int64_t* col_off, in
         }
         HIPCHK(c, memcpy_sync(c, res.data(), d + o_r2, res.size() * 8, hipMemcpyDeviceToHost));
         return VBMF_OK;
-    };
-    const int rc = run();
-    if (rc != VBMF_OK) {
-        hipStreamSynchronize(c->stream);
-        return rc;
-    }
+    }));
     auto at = [&](int64_t o_x) { return res.data() + (o_x - o_r2); };   // block x of the read-back
     if (r2) memcpy(r2, at(o_r2), (size_t)nj * 8);
     if (sigma2) memcpy(sigma2, at(o_sig), (size_t)nj * 8);
@@ -1005,26 +925,12 @@ int vbmf_sparse_lower_bound_batched(vbmf_ctx* c, int64_t nbags, const int64_t* c
     std::vector<LbGroup> grp((size_t)H);
     const double* quad = sums.data() + (o_quad - o_sums);
     for (int64_t b = 0; b < nb; ++b) {
-        const double Mb = (double)(col_off[b + 1] - col_off[b]);
-        const double* sb = sums.data() + (size_t)b * H * SCORE_NS;
-        double n_keep = 0, s_caq = 0, s_logds = 0;
-        for (int h = 0; h < H; ++h) {
-            const double* v = sb + (size_t)h * SCORE_NS;
-            n_keep += v[2]; s_caq += v[5]; s_logds += v[6];
-            // src/vbmf_sparse.jl:482-486 trims beta and CA with ATVecHat; the grouped models' per-group fields stay whole
-            const bool cut = trimmed && !grouped;
-            grp[(size_t)h] = LbGroup{cut ? v[2] : Mb, cut ? v[3] : v[0], cut ? v[4] : v[1], a_pri[b * H + h], b_pri[b * H + h], a_post[b * H + h]};
-        }
-        s.M = Mb;
-        s.MH = trimmed ? n_keep : Mb * (double)H;
         s.sig = sigmaHat[b]; s.zeta = zeta[b]; s.eta = eta[b];
         s.hyp.eta0 = eta0[b]; s.hyp.zeta0 = zeta0[b];
-        s.quad = res[(size_t)b] + s.L * quad[2 * b] + quad[2 * b + 1];
-        s.s_caq = s_caq; s.s_logds = s_logds;
-        s.g = grp.data(); s.ng = H;
-        const double v = lb_assemble(s, clamp);
-        if (!std::isfinite(v) || !std::isfinite(s.quad) || !std::isfinite(s_caq) || !std::isfinite(s_logds))
-            FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite sum in bag %lld", fn, (long long)b);
+        bool finite = false;
+        const double v = lb_of_bag(s, grp.data(), H, (double)(col_off[b + 1] - col_off[b]), res[(size_t)b], sums.data() + (size_t)b * H * SCORE_NS,
+                                   quad + 2 * b, trimmed, grouped != 0, a_pri + b * H, b_pri + b * H, a_post + b * H, clamp, finite);
+        if (!finite) FAIL(c, VBMF_ERR_NUMERIC, "%s: non-finite sum in bag %lld", fn, (long long)b);
         lb[b] = v;
         if (r2) r2[b] = res[(size_t)b];
     }
